@@ -14,6 +14,8 @@ touches a GPU) when it is not already running under a launcher; under `python -m
 Prints one JSON line (rank 0).  Extra legs outside the timed region (rank 0 of a 1-GPU run only): a counting
 pass (device work counters -> algorithmic flops and bytes for the roofline object), a second timed loop
 that includes the frame's device-to-host copy, and the CPU baseline (the oracle on a bounded sample).
+`--dump-outputs DIR` also writes the last timed step's frame (or a fixed sample of it) and ray count as .npy files, so that
+two builds can be compared output for output (dump_outputs).
 """
 import argparse
 import json
@@ -38,6 +40,11 @@ CONFIGS = {  # BASELINE.json configs that run on the GPU
     4: dict(scene="canonical", width=4096, height=4096, spp=256),
     5: dict(scene="grid", width=2048, height=2048, spp=64),
 }
+
+# --dump-outputs: a frame larger than the budget is written as a fixed pixel sample (same pixels whatever --seed is)
+DUMP_LIMIT_BYTES = 64 * 10**6
+DUMP_SAMPLE_PIXELS = 1 << 21
+DUMP_SAMPLE_SEED = 20240607
 
 
 def parse():
@@ -66,7 +73,12 @@ def parse():
     ap.add_argument("--no-counters", action="store_true")
     ap.add_argument("--no-d2h-leg", action="store_true", help="skip the extra timed loop that includes the frame's device-to-host copy")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="target wall time of the CPU baseline sample")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32/float64, "
+                         f"at most {DUMP_LIMIT_BYTES // 10**6} MB in all; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     preset = CONFIGS[args.config]
     for k, v in preset.items():
         if getattr(args, k) is None:
@@ -205,9 +217,11 @@ def main():
         gather_ms += ev[1].elapsed_time(ev[2])
     barrier()
     dt = time.perf_counter() - t0
+    # the last timed step's frame, copied before the legs below render into the same buffers again
+    last_frame = frame.cpu().numpy() if args.dump_outputs and frame is not None else None
 
     mine = torch.tensor([float(rays), dt, render_ms / args.steps, gather_ms / args.steps, t_build, t_upload,
-                         first_gather_ms if first_gather_ms is not None else -1.0], dtype=torch.float64, device=dev)
+                         first_gather_ms if first_gather_ms is not None else -1.0, float(ctx.total_rays)], dtype=torch.float64, device=dev)
     per_rank = [mine]
     if world > 1:
         per_rank = [torch.zeros_like(mine) for _ in range(world)]
@@ -225,6 +239,9 @@ def main():
     cpu_baseline = None
     incl_d2h = None
     if rank == 0:
+        if args.dump_outputs:
+            written = dump_outputs(args.dump_outputs, last_frame, sum(float(p[7]) for p in per_rank))
+            print(f"[bench] last timed step written to {args.dump_outputs}: {written}", file=sys.stderr)
         if world == 1 and not args.no_d2h_leg:
             # ---- frame device-to-host copy inside the window (SURVEY 8d's GPU window); never the headline `value`
             host = torch.empty(frame.shape, dtype=frame.dtype, pin_memory=True)
@@ -293,6 +310,31 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(outdir, frame, rays):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float .npy files.
+    frame.npy                 the (H, W, C) frame rank 0 gathered: f32 RGBA, or with --u8 the RGB bytes as f32
+    frame_sample.npy          instead of frame.npy when the frame would not fit DUMP_LIMIT_BYTES: (DUMP_SAMPLE_PIXELS, C)
+    frame_sample_pixels.npy   ... the flat pixel indices (y * W + x, f64, ascending) of that fixed, seeded sample
+    rays.npy                  (1,) f64: rays of that step over all ranks (the ProgressCtx total_rays)
+    Returns {name: shape}."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    out = {"rays": np.array([rays], np.float64)}
+    f = np.ascontiguousarray(frame, dtype=np.float32)
+    h, w, c = f.shape
+    if f.nbytes + out["rays"].nbytes <= DUMP_LIMIT_BYTES:
+        out["frame"] = f
+    else:
+        n = min(DUMP_SAMPLE_PIXELS, h * w)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(h * w, size=n, replace=False))
+        out["frame_sample"] = f.reshape(h * w, c)[idx]
+        out["frame_sample_pixels"] = idx.astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_LIMIT_BYTES
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
 
 
 def roofline_object(args, caster, scene, vp, tile, local, stream, rays_per_frame, trace_ms, kernel_ms, launches, dt):
