@@ -35,6 +35,7 @@
 #include <string>
 #include <thread>
 #include <tuple>
+#include <unordered_map>
 #include <vector>
 
 #include "../../../include/rtmi.h"
@@ -876,6 +877,161 @@ static size_t env_size(const char* name, size_t dflt) {
     return (end && *end == '\0' && (v > 0 || dflt == 0)) ? (size_t)v : dflt;
 }
 
+// Checks the flattened tree of rtmi_scene_create (every box reachable from an earlier one, 1..8 children after their
+// parent, leaf ranges and triangle indices in bounds); fills the depth of every box and the largest depth of an inner box.
+// Returns "" or what is wrong.
+static std::string validate_tree(const rtmi_box_t* boxes, uint64_t nboxes, const uint32_t* tri_refs, uint64_t nrefs, uint64_t ntris,
+                                 std::vector<uint32_t>& depth, uint32_t& max_inner_depth) {
+    depth.assign(nboxes, 0xFFFFFFFFu);
+    depth[0] = 0;
+    max_inner_depth = 0;
+    for (uint64_t i = 0; i < nboxes; i++) {
+        const rtmi_box_t& b = boxes[i];
+        if (depth[i] == 0xFFFFFFFFu) return "box " + std::to_string(i) + " is not reachable from an earlier box";
+        if (b.is_leaf) {
+            if ((uint64_t)b.first + b.count > nrefs) return "leaf triangle range out of bounds";
+            for (uint32_t k = 0; k < b.count; k++)
+                if (tri_refs[b.first + k] >= ntris) return "triangle index out of range";
+        } else {
+            // the reference's boxmap has 8 slots (raytrace.rs:929): more children would panic there
+            if (b.count < 1 || b.count > 8) return "inner box must have 1..8 children";
+            if (b.first <= i || (uint64_t)b.first + b.count > nboxes) return "child range must follow its parent";
+            for (uint32_t k = 0; k < b.count; k++) {
+                if (depth[b.first + k] != 0xFFFFFFFFu) return "box has two parents";
+                depth[b.first + k] = depth[i] + 1;
+            }
+            max_inner_depth = std::max(max_inner_depth, depth[i]);
+        }
+    }
+    return "";
+}
+
+// The exact-octree form of a validated tree (trace_oct.hpp, "Records"): fnodes, oblocks, wlinks.  Host only.
+struct OctForm {
+    std::vector<uint4> fn;     // 2 records per inner box
+    std::vector<uint4> ob;     // reference blocks, each DISTINCT leaf list once
+    std::vector<uint32_t> wl;  // explicit block indices of FN_WIDE boxes
+    uint64_t nwide = 0;        // FN_WIDE boxes
+    std::string why;           // empty: the tree is an exact octree
+};
+
+// FNV-1a over a leaf's reference sequence (the dedup table's hash; equality is checked on the whole sequence)
+struct RefListHash {
+    size_t operator()(const std::vector<uint32_t>& v) const {
+        uint64_t h = 1469598103934665603ull;
+        for (uint32_t x : v) { h ^= x; h *= 1099511628211ull; }
+        return (size_t)h;
+    }
+};
+
+// Every child must be the builder's octant of its parent, bit for bit (orig + (+-newlen2), newlen2 = len2 / 2,
+// raytrace.rs:816-824), stored in octant order.  Inner boxes get a 32-B record (centre, child masks, links); leaves only
+// their reference blocks.  Leaves that list the same triangles in the same order share ONE run of blocks (the builder
+// lists a triangle in every box its plane crosses, so neighbouring leaves often carry the same list): a list's identity
+// is its first block, which is what the walk's one-entry leaf memo compares.  Order matters: the leaf fold takes the
+// first of equal hit times, so only identical sequences are shared.
+static void build_oct_form(const rtmi_box_t* boxes, uint64_t nboxes, const uint32_t* tri_refs, uint64_t ntris,
+                           const std::vector<uint32_t>& depth, OctForm& f) {
+    auto fb = [](float v) { uint32_t u; memcpy(&u, &v, 4); return u; };
+    std::vector<uint4>& hfn = f.fn;
+    std::vector<uint4>& hob = f.ob;
+    std::vector<uint32_t>& hwl = f.wl;
+    std::string& why = f.why;
+    bool ok = !boxes[0].is_leaf;  // a one-leaf tree is the linear list (k_trace_linear)
+    if (!ok) why = "the root box is a leaf";
+    // record index of every inner box (in box order, root = 0) / first reference block of every leaf
+    std::vector<uint32_t> slot(nboxes, 0);
+    uint64_t ninner = 0;
+    const float root_len2 = boxes[0].len2;
+    std::unordered_map<std::vector<uint32_t>, uint32_t, RefListHash> seen;  // leaf list -> its first block
+    std::vector<uint32_t> list;
+    for (uint64_t i = 0; i < nboxes && ok; i++) {
+        const rtmi_box_t& b = boxes[i];
+        if (fb(b.len2) != fb(ldexpf(root_len2, -(int)depth[i])) || !(b.len2 > 0.f) || !std::isfinite(b.len2)) { ok = false; why = "box half-length is not root/2^depth"; break; }
+        if (b.is_leaf) {
+            for (uint32_t k = 0; k < b.count; k++)
+                if (tri_refs[b.first + k] == 0) { ok = false; why = "a leaf lists the sentinel triangle 0"; }
+            if (!ok) break;
+            list.assign(tri_refs + b.first, tri_refs + b.first + b.count);
+            auto it = seen.find(list);
+            if (it != seen.end()) { slot[i] = it->second | 0x80000000u; continue; }
+            if (hob.size() >= (1ull << 31)) { ok = false; why = "more than 2^31 reference blocks"; break; }
+            slot[i] = (uint32_t)hob.size() | 0x80000000u;
+            seen.emplace(list, (uint32_t)hob.size());
+            // blocks of 4 indices; the list ends at the first 0, or after a block whose 4th index carries
+            // bit 31 (a full last block: no extra all-zero block, triangle indices are < 2^30)
+            for (uint32_t k = 0; k < std::max<uint32_t>(b.count, 1u); k += 4) {
+                uint32_t v[4] = {0, 0, 0, 0};
+                for (uint32_t j = 0; j < 4; j++)
+                    if (k + j < b.count) v[j] = tri_refs[b.first + k + j];
+                if (k + 4 == b.count) v[3] |= 0x80000000u;
+                hob.push_back(make_uint4(v[0], v[1], v[2], v[3]));
+            }
+        } else {
+            slot[i] = (uint32_t)ninner++;
+        }
+    }
+    if (ok) {
+        hfn.assign(2 * ninner, make_uint4(0, 0, 0, 0));
+        for (uint64_t i = 0; i < nboxes && ok; i++) {
+            const rtmi_box_t& b = boxes[i];
+            if (b.is_leaf) continue;
+            const float h = b.len2 / 2.f;
+            uint32_t mask = 0, leafmask = 0, first_block[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            uint32_t base_inner = 0, base_block = 0xFFFFFFFFu;
+            bool have_inner = false;
+            int prev = -1;
+            for (uint32_t k = 0; k < b.count && ok; k++) {
+                const rtmi_box_t& c = boxes[b.first + k];
+                int oct = 0;
+                for (int a = 0; a < 3; a++) {
+                    const float lo = b.orig[a] + (-1.f * h), hi = b.orig[a] + h;
+                    if (fb(lo) == fb(hi)) { ok = false; why = "degenerate box"; break; }
+                    if (fb(c.orig[a]) == fb(hi)) oct |= 1 << a;
+                    else if (fb(c.orig[a]) != fb(lo)) { ok = false; why = "child centre is not an octant centre of its parent"; break; }
+                }
+                if (ok && oct <= prev) { ok = false; why = "children are not in octant order"; }
+                prev = oct;
+                mask |= 1u << oct;
+                // children follow each other in box order, so the inner ones have consecutive records: one base + a
+                // popcount.  Leaf children point at shared lists anywhere in `hob`: base = the smallest first block among
+                // them + a byte offset per octant (new lists of one box are placed consecutively, in box order)
+                if (c.is_leaf) {
+                    leafmask |= 1u << oct;
+                    first_block[oct & 7] = slot[b.first + k] & 0x7FFFFFFFu;
+                    base_block = std::min(base_block, first_block[oct & 7]);
+                } else if (!have_inner) { base_inner = slot[b.first + k]; have_inner = true; }
+            }
+            if (!leafmask) base_block = 0;
+            uint32_t w = mask | (leafmask << 8), offlo = 0, offhi = 0, q1y = base_block;
+            bool wide = false;
+            for (int o = 0; o < 8; o++)
+                if ((leafmask >> o) & 1u) wide |= first_block[o] - base_block > 255u;
+            if (wide) {
+                w |= RTMI_FN_WIDE;
+                q1y = (uint32_t)(hwl.size() / 8);
+                hwl.insert(hwl.end(), first_block, first_block + 8);
+                f.nwide++;
+            } else {
+                for (int o = 0; o < 8; o++) {
+                    const uint32_t off = ((leafmask >> o) & 1u) ? first_block[o] - base_block : 0u;
+                    if (o < 4) offlo |= off << (8 * o); else offhi |= off << (8 * (o - 4));
+                }
+            }
+            uint4* rec = &hfn[2 * (size_t)slot[i]];
+            rec[0] = make_uint4(fb(b.orig[0]), fb(b.orig[1]), fb(b.orig[2]), w);
+            rec[1] = make_uint4(base_inner, q1y, offlo, offhi);
+        }
+    }
+    // k_trace_oct addresses its records with 32-bit byte offsets (ld_off32): 32 B per inner box and per triangle plane
+    // record, 64 B per triangle edge record, 16 B per reference block; its stack keeps an inner box's record index in 22 bits
+    if (ok && (ninner >= (1ull << 22) || ntris >= (1ull << 26) || hob.size() >= (1ull << 28))) { ok = false; why = "more than 2^22 inner boxes, or an array of the octree form would exceed 4 GiB"; }
+    if (!ok) { hfn.clear(); hob.clear(); hwl.clear(); f.nwide = 0; }
+}
+
+// LDS of an octree-walk launch: the counting build keeps 2 more memo words per lane (the list's plane and edge tests)
+static size_t oct_launch_lds(const rtmi_scene* s, bool count) { return s->oct_lds + (count ? 2 * 4 * 64 : 0); }
+
 extern "C" {
 
 const char* rtmi_last_error(void) { return g_err.c_str(); }
@@ -898,26 +1054,11 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
 
     RTMI_GUARD_BEGIN
     // ---- validate the tree, compute inner depth (levels of the LDS stack)
-    std::vector<uint32_t> depth(nboxes, 0xFFFFFFFFu);
-    depth[0] = 0;
+    std::vector<uint32_t> depth;
     uint32_t max_inner_depth = 0;
-    for (uint64_t i = 0; i < nboxes; i++) {
-        const rtmi_box_t& b = boxes[i];
-        if (depth[i] == 0xFFFFFFFFu) return fail(RTMI_ERR_INVALID, "box " + std::to_string(i) + " is not reachable from an earlier box");
-        if (b.is_leaf) {
-            if ((uint64_t)b.first + b.count > nrefs) return fail(RTMI_ERR_INVALID, "leaf triangle range out of bounds");
-            for (uint32_t k = 0; k < b.count; k++)
-                if (tri_refs[b.first + k] >= ntris) return fail(RTMI_ERR_INVALID, "triangle index out of range");
-        } else {
-            // the reference's boxmap has 8 slots (raytrace.rs:929): more children would panic there
-            if (b.count < 1 || b.count > 8) return fail(RTMI_ERR_INVALID, "inner box must have 1..8 children");
-            if (b.first <= i || (uint64_t)b.first + b.count > nboxes) return fail(RTMI_ERR_INVALID, "child range must follow its parent");
-            for (uint32_t k = 0; k < b.count; k++) {
-                if (depth[b.first + k] != 0xFFFFFFFFu) return fail(RTMI_ERR_INVALID, "box has two parents");
-                depth[b.first + k] = depth[i] + 1;
-            }
-            max_inner_depth = std::max(max_inner_depth, depth[i]);
-        }
+    {
+        const std::string bad = validate_tree(boxes, nboxes, tri_refs, nrefs, ntris, depth, max_inner_depth);
+        if (!bad.empty()) return fail(RTMI_ERR_INVALID, bad);
     }
     const uint32_t levels = std::max<uint32_t>(1u, max_inner_depth);
     int block = 256;
@@ -930,97 +1071,13 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
         const rtmi_box_t& b = boxes[i];
         hn[i] = DNode{b.orig[0], b.orig[1], b.orig[2], b.len2, b.first, b.count, b.is_leaf ? 1u : 0u, 0u};
     }
-    // ---- exact-octree form: every child must be the builder's octant of its parent, bit for bit
-    //      (orig + (+-newlen2), newlen2 = len2 / 2, raytrace.rs:816-824), stored in octant order.
-    //      Inner boxes get a 64-B record (centre, child mask, 8 child links); leaves only their reference blocks.
-    std::vector<uint4> hfn;
-    std::vector<uint4> hob;
-    std::vector<uint32_t> hwl;  // explicit block indices of FN_WIDE boxes
-    std::string why;
-    {
-        auto fb = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
-        bool ok = !boxes[0].is_leaf;  // a one-leaf tree is the linear list (k_trace_linear)
-        if (!ok) why = "the root box is a leaf";
-        // record index of every inner box (in box order, root = 0) / first reference block of every leaf
-        std::vector<uint32_t> slot(nboxes, 0);
-        uint64_t ninner = 0;
-        const float root_len2 = boxes[0].len2;
-        for (uint64_t i = 0; i < nboxes && ok; i++) {
-            const rtmi_box_t& b = boxes[i];
-            if (fb(b.len2) != fb(ldexpf(root_len2, -(int)depth[i])) || !(b.len2 > 0.f) || !std::isfinite(b.len2)) { ok = false; why = "box half-length is not root/2^depth"; break; }
-            if (b.is_leaf) {
-                for (uint32_t k = 0; k < b.count; k++)
-                    if (tri_refs[b.first + k] == 0) { ok = false; why = "a leaf lists the sentinel triangle 0"; }
-                if (!ok) break;
-                if (hob.size() >= (1ull << 31)) { ok = false; why = "more than 2^31 reference blocks"; break; }
-                slot[i] = (uint32_t)hob.size() | 0x80000000u;
-                // blocks of 4 indices; the list ends at the first 0, or after a block whose 4th index carries
-                // bit 31 (a full last block: no extra all-zero block, triangle indices are < 2^30)
-                for (uint32_t k = 0; k < std::max<uint32_t>(b.count, 1u); k += 4) {
-                    uint32_t v[4] = {0, 0, 0, 0};
-                    for (uint32_t j = 0; j < 4; j++)
-                        if (k + j < b.count) v[j] = tri_refs[b.first + k + j];
-                    if (k + 4 == b.count) v[3] |= 0x80000000u;
-                    hob.push_back(make_uint4(v[0], v[1], v[2], v[3]));
-                }
-            } else {
-                slot[i] = (uint32_t)ninner++;
-            }
-        }
-        if (ok) {
-            hfn.assign(2 * ninner, make_uint4(0, 0, 0, 0));
-            for (uint64_t i = 0; i < nboxes && ok; i++) {
-                const rtmi_box_t& b = boxes[i];
-                if (b.is_leaf) continue;
-                const float h = b.len2 / 2.f;
-                uint32_t mask = 0, leafmask = 0, first_block[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                uint32_t base_inner = 0, base_block = 0;
-                bool have_inner = false, have_leaf = false;
-                int prev = -1;
-                for (uint32_t k = 0; k < b.count && ok; k++) {
-                    const rtmi_box_t& c = boxes[b.first + k];
-                    int oct = 0;
-                    for (int a = 0; a < 3; a++) {
-                        const float lo = b.orig[a] + (-1.f * h), hi = b.orig[a] + h;
-                        if (fb(lo) == fb(hi)) { ok = false; why = "degenerate box"; break; }
-                        if (fb(c.orig[a]) == fb(hi)) oct |= 1 << a;
-                        else if (fb(c.orig[a]) != fb(lo)) { ok = false; why = "child centre is not an octant centre of its parent"; break; }
-                    }
-                    if (ok && oct <= prev) { ok = false; why = "children are not in octant order"; }
-                    prev = oct;
-                    mask |= 1u << oct;
-                    // children follow each other in box order, so the inner ones have consecutive records and the leaf
-                    // ones consecutive runs of blocks: one base each + (leaves) a byte offset per octant
-                    if (c.is_leaf) {
-                        leafmask |= 1u << oct;
-                        first_block[oct & 7] = slot[b.first + k] & 0x7FFFFFFFu;
-                        if (!have_leaf) { base_block = first_block[oct & 7]; have_leaf = true; }
-                    } else if (!have_inner) { base_inner = slot[b.first + k]; have_inner = true; }
-                }
-                uint32_t w = mask | (leafmask << 8), offlo = 0, offhi = 0, q1y = base_block;
-                bool wide = false;
-                for (int o = 0; o < 8; o++)
-                    if ((leafmask >> o) & 1u) wide |= first_block[o] - base_block > 255u;
-                if (wide) {
-                    w |= RTMI_FN_WIDE;
-                    q1y = (uint32_t)(hwl.size() / 8);
-                    hwl.insert(hwl.end(), first_block, first_block + 8);
-                } else {
-                    for (int o = 0; o < 8; o++) {
-                        const uint32_t off = ((leafmask >> o) & 1u) ? first_block[o] - base_block : 0u;
-                        if (o < 4) offlo |= off << (8 * o); else offhi |= off << (8 * (o - 4));
-                    }
-                }
-                uint4* rec = &hfn[2 * (size_t)slot[i]];
-                rec[0] = make_uint4(fb(b.orig[0]), fb(b.orig[1]), fb(b.orig[2]), w);
-                rec[1] = make_uint4(base_inner, q1y, offlo, offhi);
-            }
-        }
-        // k_trace_oct addresses its records with 32-bit byte offsets (ld_off32): 32 B per inner box and per triangle plane
-        // record, 64 B per triangle edge record, 16 B per reference block; its stack keeps an inner box's record index in 22 bits
-        if (ok && (ninner >= (1ull << 22) || ntris >= (1ull << 26) || hob.size() >= (1ull << 28))) { ok = false; why = "more than 2^22 inner boxes, or an array of the octree form would exceed 4 GiB"; }
-        if (!ok) { hfn.clear(); hob.clear(); hwl.clear(); }
-    }
+    // ---- exact-octree form (trace_oct.hpp); empty when the tree is not one, `why` says why
+    OctForm of;
+    build_oct_form(boxes, nboxes, tri_refs, ntris, depth, of);
+    std::vector<uint4>& hfn = of.fn;
+    std::vector<uint4>& hob = of.ob;
+    std::vector<uint32_t>& hwl = of.wl;
+    std::string& why = of.why;
 
     std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t>, uint32_t> matmap;
     std::vector<float4> hm, hp(2 * ntris), he(4 * ntris);
@@ -1112,8 +1169,9 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
                   s->octree ? s->fnodes.p : nullptr, s->octree ? s->oblocks.p : nullptr, s->octree ? s->wlinks.p : nullptr, nullptr, 0u, boxes[0].len2, max_inner_depth + 1, (uint32_t)hob.size()};
     s->hmats = hm;
     if (s->octree) {
-        s->oct_lds = (size_t)std::max<uint32_t>(1u, max_inner_depth) * 8 * 64;  // 2 words per level per lane
-        if (s->oct_lds > 64 * 1024) { s->octree = false; s->why_generic = "octree deeper than the LDS stack allows"; }
+        // 2 words per level per lane (frame stack) + 3 per lane (leaf memo: key, t, tri | face; trace_oct.hpp)
+        s->oct_lds = ((size_t)std::max<uint32_t>(1u, max_inner_depth) * 2 + 3) * 4 * 64;
+        if (oct_launch_lds(s, true) > 64 * 1024) { s->octree = false; s->why_generic = "octree deeper than the LDS stack allows"; }
         else {
             int nb = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace_oct<false, false>, 64, s->oct_lds) == hipSuccess && nb > 0)
@@ -1313,9 +1371,9 @@ static void launch_trace(rtmi_scene* s, Work& w, hipStream_t st, const float4* q
             a.qo = qo; a.qd = qd; a.hit_tf = w.hit_tf.p; a.hit_t = w.hit_t.p; a.pass = pass;
             a.vote_s = pass == 0 ? s->vote[0] : s->vote[2]; a.vote_l = pass == 0 ? s->vote[1] : s->vote[3];
             if (s->options & RTMI_OPT_FAST)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_oct<COUNT, true>), grid, block, s->oct_lds, st, s->d, a, w.ctrl.p, refill, xcd);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_oct<COUNT, true>), grid, block, oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
             else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_oct<COUNT, false>), grid, block, s->oct_lds, st, s->d, a, w.ctrl.p, refill, xcd);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_oct<COUNT, false>), grid, block, oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
         }
     } else {
         // persistent grid: enough blocks to fill every CU at the occupancy LDS allows
@@ -1362,16 +1420,16 @@ static void launch_path(rtmi_scene* s, Work& w, hipStream_t st, int which, const
         (void)hipEventRecord(w.sgo, w.sstream);
         (void)hipStreamWaitEvent(st, w.sgo, 0);
         const dim3 sgrid((unsigned)std::max(s->num_cu / 2, 1));  // one path per wave at a time; a frame has ~100 such paths, a wave takes one after the other
-        if (fast) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow<COUNT, true>), sgrid, block, s->oct_lds, w.sstream, s->d, a, w.ctrl.p, 1, 0);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow<COUNT, false>), sgrid, block, s->oct_lds, w.sstream, s->d, a, w.ctrl.p, 1, 0);
+        if (fast) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow<COUNT, true>), sgrid, block, oct_launch_lds(s, COUNT), w.sstream, s->d, a, w.ctrl.p, 1, 0);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow<COUNT, false>), sgrid, block, oct_launch_lds(s, COUNT), w.sstream, s->d, a, w.ctrl.p, 1, 0);
         return;
     }
     if (which == W_PRIMARY) {
-        if (fast) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary<COUNT, true>), grid, block, s->oct_lds, st, s->d, a, w.ctrl.p, refill, xcd);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary<COUNT, false>), grid, block, s->oct_lds, st, s->d, a, w.ctrl.p, refill, xcd);
+        if (fast) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary<COUNT, true>), grid, block, oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary<COUNT, false>), grid, block, oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
     } else {
-        if (fast) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_bounce<COUNT, true>), grid, block, s->oct_lds, st, s->d, a, w.ctrl.p, refill, xcd);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_bounce<COUNT, false>), grid, block, s->oct_lds, st, s->d, a, w.ctrl.p, refill, xcd);
+        if (fast) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_bounce<COUNT, true>), grid, block, oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_bounce<COUNT, false>), grid, block, oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
     }
     (void)hipEventRecord(stop, st);
 }
@@ -1884,6 +1942,30 @@ int rtmi_trace(rtmi_scene_t* s, uint64_t n, const float* orig4, const float* dir
 // Test hook (not in rtmi.h): n / d as the kernels compute it for launch-constant divisors (FastDiv, shade.hpp), evaluated on
 // the host with the same inline functions; needs no device.
 uint32_t rtmi_debug_fastdiv(uint32_t n, uint32_t d) { return fdiv(n, make_fastdiv(d)); }
+
+// Test hook (not in rtmi.h): the exact-octree form rtmi_scene_create would upload for a tree (same arguments), built on
+// the host; needs no device.  sizes4 <- (fnodes records of 16 B, reference blocks, wlinks words, FN_WIDE boxes); the arrays
+// (fnodes: 4 x sizes4[0] words, oblocks: 4 x sizes4[1], wlinks: sizes4[2]) are filled when not NULL -- call once with
+// NULL arrays for the sizes.  RTMI_ERR_UNSUPPORTED (and the reason in rtmi_last_error) when the tree is no exact octree.
+int rtmi_debug_oct_form(const rtmi_box_t* boxes, uint64_t nboxes, const uint32_t* tri_refs, uint64_t nrefs, uint64_t ntris,
+                        uint32_t* fnodes, uint32_t* oblocks, uint32_t* wlinks, uint64_t* sizes4) {
+    if (!boxes || nboxes < 1 || !sizes4 || (nrefs > 0 && !tri_refs)) return fail(RTMI_ERR_INVALID, "NULL argument");
+    if (nboxes >= (1ull << 32) || nrefs >= (1ull << 32)) return fail(RTMI_ERR_UNSUPPORTED, "tree too large for 32-bit indices");
+    RTMI_GUARD_BEGIN
+    std::vector<uint32_t> depth;
+    uint32_t max_inner_depth = 0;
+    const std::string bad = validate_tree(boxes, nboxes, tri_refs, nrefs, ntris, depth, max_inner_depth);
+    if (!bad.empty()) return fail(RTMI_ERR_INVALID, bad);
+    OctForm f;
+    build_oct_form(boxes, nboxes, tri_refs, ntris, depth, f);
+    if (f.fn.empty()) return fail(RTMI_ERR_UNSUPPORTED, f.why);
+    sizes4[0] = f.fn.size(); sizes4[1] = f.ob.size(); sizes4[2] = f.wl.size(); sizes4[3] = f.nwide;
+    if (fnodes) memcpy(fnodes, f.fn.data(), f.fn.size() * sizeof(uint4));
+    if (oblocks) memcpy(oblocks, f.ob.data(), f.ob.size() * sizeof(uint4));
+    if (wlinks && !f.wl.empty()) memcpy(wlinks, f.wl.data(), f.wl.size() * sizeof(uint32_t));
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
 
 // Test hook (not in rtmi.h): the ABI status and message a HIP runtime failure `hip_error` is reported as.
 int rtmi_debug_status_of(int hip_error) {

@@ -44,14 +44,15 @@
 // Records (HBM, served from L2 / Infinity Cache):
 //   fnodes  : 2 x uint4 (32 B) per INNER box: (cx, cy, cz, present mask | leaf mask << 8 | FN_WIDE)
 //             (first inner child's record, first block of the first leaf child, 8 x u8 block offsets of the leaf
-//             children).  Children of a box are stored together: the inner ones as consecutive records in octant
-//             order, the leaf ones as consecutive runs of reference blocks in octant order, so a child's record /
-//             first block follows from the masks with a popcount / a byte extract.  Leaves have no record.  A box
-//             whose leaf children hold more than 255 blocks (FN_WIDE, rare) keeps 8 explicit 32-bit block indices in
-//             `wlinks` instead (one more dependent load).
-//   oblocks : uint4 blocks of triangle indices of a leaf, in list order.  The list ends at the first index 0
+//             children).  The inner children of a box are consecutive records in octant order, so a child's record
+//             follows from the masks with a popcount.  Leaves have no record; a leaf child's first block is the
+//             smallest first block among the box's leaf children + a byte offset per octant.  A box whose leaf children
+//             start more than 255 blocks apart (FN_WIDE) keeps 8 explicit 32-bit block indices in `wlinks` instead (one
+//             more dependent load).
+//   oblocks : uint4 blocks of triangle indices of a leaf list, in list order.  The list ends at the first index 0
 //             (the sentinel triangle is never in a tree, raytrace.rs:791) or after a full block whose 4th
-//             index has bit 31 set.
+//             index has bit 31 set.  Each DISTINCT list is stored once (leaves with the same list share its blocks), so
+//             a list's first block is its identity -- what the leaf memo of oct_walk compares.
 #pragma once
 
 namespace rtmi {
@@ -145,9 +146,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     unsigned long long cnt[5] = {0, 0, 0, 0, 0};
     // COUNT only: S steps, S lanes, L steps, L lanes, refills, refill lanes, edge steps, edge lanes, then shader-clock
     // cycles (s_memtime) this wave spent in SELECT steps, LEAF steps, refills, and in total
-    // dbg[12..15]: plane tests whose `t < 0` follows from the signs and exponents of num / den alone (the quotient is a
-    // negative NORMAL number), (LEAF step, reference k) slots in which that holds for EVERY working lane -- the only case in
-    // which leaving out the division is a saving for the wave --, all such slots, LEAF steps in which all 4 slots are so
+    // dbg[12..15]: leaf visits, leaf-memo hits, plane tests and edge tests the memo hits skipped
     unsigned long long dbg[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const unsigned long long t_begin = COUNT ? __builtin_amdgcn_s_memtime() : 0ull;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
@@ -172,6 +171,20 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     bool lhave = false;
     float lt = 0.f;
     uint32_t ltf = 0;
+    // One-entry leaf memo per lane, in LDS behind the frame stack ([word][lane], like the stack): the first block of the
+    // last leaf list this lane's ray scanned (its identity: rtmi_scene_create stores each distinct list once), that list's
+    // result (t, tri | face << 30, 0 = no hit: triangle 0 is never in a tree) and, COUNT only, its plane and edge tests.
+    // A leaf whose first block equals the key takes the stored result instead of being scanned again: the leaf fold
+    // (raytrace.rs:1012-1050) is a pure function of the ray and the list.  The key is invalidated whenever a lane takes a
+    // new ray.  Not in the slow path (its wide LEAF step keeps the ray's state in lane 0).
+    constexpr bool MEMO = MODE != W_SLOW;
+    uint32_t* const memo = lds + sc.levels * 2 * NT + lane;
+    auto take_leaf = [&](float t, uint32_t tf) {  // a finished leaf's hit into the frame and the running best
+        if (!(fw & O_HAS) || t < ft) ft = t;
+        fw |= O_HAS;
+        if (!ghave || t < gt) { gt = t; gtf = tf; }
+        ghave = true;
+    };
 
     for (;;) {
         const unsigned long long m_idle = __ballot(mode == M_IDLE);
@@ -283,6 +296,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                             // get_object_intersection_for_ray on it directly): start with its frame
                             fnode = 0; fw = 0; ft = 0.f; lvl = 0;
                             ghave = false; gt = 0.f; gtf = 0;
+                            if (MEMO) memo[0] = 0xFFFFFFFFu;  // no block index (< 2^28)
                             mode = M_SELECT;
                         }
                     }
@@ -300,6 +314,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                 path = npath; bounce = nbounce;
                 fnode = 0; fw = 0; ft = 0.f; lvl = 0;
                 ghave = false; gt = 0.f; gtf = 0;
+                if (MEMO) memo[0] = 0xFFFFFFFFu;
                 mode = M_SELECT;
             }
             if (COUNT && lane == 0) dbg[10] += __builtin_amdgcn_s_memtime() - t_r0;
@@ -408,9 +423,24 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                             const uint32_t oct = (uint32_t)__ffs((int)bit) - 1u;
                             if (q0.w & FN_WIDE) lblock = sc.wlinks[(size_t)q1.y * 8u + oct];  // rare: explicit indices
                             else lblock = q1.y + __builtin_amdgcn_ubfe(oct < 4u ? q1.z : q1.w, (oct & 3u) * 8u, 8u);
-                            lhave = false;  // lt, ltf are dead until the first hit of the leaf sets them
                             if (COUNT) cnt[4]++;
-                            mode = M_LEAF;
+                            if (COUNT && MEMO) dbg[12]++;
+                            if (MEMO && memo[0] == lblock) {  // the list this ray scanned last: its result, no LEAF steps
+                                const uint32_t mtf = memo[2 * NT];
+                                if (mtf != 0u) take_leaf(__uint_as_float(memo[NT]), mtf);
+                                if (COUNT) {
+                                    const uint32_t np = memo[3 * NT], ne = memo[4 * NT];
+                                    cnt[1] += np; cnt[2] += ne;
+                                    dbg[13]++; dbg[14] += np; dbg[15] += ne;
+                                }
+                            } else {
+                                if (MEMO) {
+                                    memo[0] = lblock;
+                                    if (COUNT) { memo[3 * NT] = (uint32_t)cnt[1]; memo[4 * NT] = (uint32_t)cnt[2]; }
+                                }
+                                lhave = false;  // lt, ltf are dead until the first hit of the leaf sets them
+                                mode = M_LEAF;
+                            }
                         } else {
                             uint32_t* fr = lds + lvl * 2 * NT + lane;
                             fr[0] = fnode | (fw << 22);  // record index (< 2^22, checked at scene creation) | visited bits, DONE, HAS
@@ -462,12 +492,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                     lhave = have; lt = best; ltf = btf;
                     if (tm == 0ull) lblock = lb0 + 16u;  // no end among these 16 blocks: the list goes on
                     else {
-                        if (lhave) {
-                            if (!(fw & O_HAS) || lt < ft) ft = lt;
-                            fw |= O_HAS;
-                            if (!ghave || lt < gt) { gt = lt; gtf = ltf; }
-                            ghave = true;
-                        }
+                        if (lhave) take_leaf(lt, ltf);
                         mode = M_SELECT;
                     }
                 }
@@ -485,7 +510,6 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                 // terms.  A reference that passes `t >= 0` and the bounding-radius test becomes the lane's pending
                 // candidate; its edge part runs below, once per step.
                 uint32_t ptri = 0u;
-                uint32_t allneg = 0u;  // COUNT only
                 float pt = 0.f, pix = 0.f, piy = 0.f, piz = 0.f, pden = 0.f;
                 auto resolve = [&]() {
                     // all four edge records are requested together and every comparison is evaluated (no
@@ -516,12 +540,6 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                     const float l2 = ((ix * ix + iy * iy) + iz * iz) + pw * pw;
                     const bool real = ids[k] != 0u;
                     if (COUNT) cnt[1] += real ? 1u : 0u;
-                    if (COUNT) {
-                        const bool dec = !real | ((t <= -1.17549435e-38f) & (t >= -FLT_MAX));
-                        const unsigned long long wm = __ballot(true), dm = __ballot(dec);
-                        if (real & dec) dbg[12]++;
-                        if (lane == __ffsll((long long)wm) - 1) { dbg[14]++; if (dm == wm) { dbg[13]++; allneg++; } }
-                    }
                     const bool c = real & !(t < 0.f) & !(l2 > p0[k].w);
                     if (c & (ptri != 0u)) resolve();  // second candidate of this lane in one block: rare
                     ptri = c ? ids[k] : ptri;
@@ -530,13 +548,12 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                     pden = c ? den : pden;
                 }
                 if (ptri != 0u) resolve();
-                if (COUNT && allneg == 4u) dbg[15]++;
                 if (!more) {
-                    if (lhave) {
-                        if (!(fw & O_HAS) || lt < ft) ft = lt;
-                        fw |= O_HAS;
-                        if (!ghave || lt < gt) { gt = lt; gtf = ltf; }
-                        ghave = true;
+                    if (lhave) take_leaf(lt, ltf);
+                    if (MEMO) {  // the key was written at leaf entry
+                        memo[NT] = __float_as_uint(lt);
+                        memo[2 * NT] = lhave ? ltf : 0u;
+                        if (COUNT) { memo[3 * NT] = (uint32_t)cnt[1] - memo[3 * NT]; memo[4 * NT] = (uint32_t)cnt[2] - memo[4 * NT]; }
                     }
                     mode = M_SELECT;
                 }

@@ -22,7 +22,8 @@ lib.rth_debug_counters.argtypes = [C.c_void_p, C.c_void_p]
 out = (C.c_ulonglong * 16)()
 lib.rth_debug_counters(scene.h, out)
 d = list(out)
-names = ["S steps", "S lanes", "L steps", "L lanes", "refills", "refill lanes", "edge blocks", "edge lanes", "S cycles", "L cycles", "refill cycles", "wave cycles"]
+names = ["S steps", "S lanes", "L steps", "L lanes", "refills", "refill lanes", "edge blocks", "edge lanes", "S cycles", "L cycles", "refill cycles", "wave cycles",
+         "leaf visits", "memo hits", "planes skipped", "edges skipped"]
 for n, v in zip(names, d):
     print(f"{n:14s} {v}")
 rays = ctx.stats["rays"]
@@ -33,6 +34,6 @@ tot = max(d[11], 1)
 print(f"shader-clock cycles of a wave (counting build, all passes of the last batch): SELECT steps {d[8] / tot:.3f}, LEAF steps {d[9] / tot:.3f}, "
       f"refills {d[10] / tot:.3f}, vote/rest {1 - (d[8] + d[9] + d[10]) / tot:.3f} of the wave's lifetime; "
       f"{d[8] / max(d[0], 1):.0f} cycles per SELECT step, {d[9] / max(d[2], 1):.0f} per LEAF step, {d[10] / max(d[4], 1):.0f} per refill")
-print(f"t < 0 decidable from signs/exponents alone: {d[12]} of {ctx.stats['tri_tests']} plane tests of the last batch's lanes "
-      f"({d[12] / max(ctx.stats['tri_tests'], 1):.3f} if the call was one batch); wave level: {d[13]} of {d[14]} (LEAF step, reference) slots "
-      f"have EVERY working lane decidable ({d[13] / max(d[14], 1):.4f}); LEAF steps with all four slots so: {d[15]} of {d[2]} ({d[15] / max(d[2], 1):.4f})")
+print(f"leaf memo: {d[13]} of {d[12]} leaf visits take the result of the list the ray scanned last ({d[13] / max(d[12], 1):.3f}); "
+      f"plane tests skipped {d[14]} ({d[14] / max(ctx.stats['tri_tests'], 1):.3f} of the call's tri_tests if it was one batch), "
+      f"edge tests skipped {d[15]} ({d[15] / max(ctx.stats['full_tests'], 1):.3f} of full_tests)")
