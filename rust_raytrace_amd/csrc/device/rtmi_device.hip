@@ -84,6 +84,7 @@ struct DScene {
 #define RTMI_DEFAULT_POOL 0
 #define RTMI_MAX_PASSES 32
 #define RTMI_MAX_STREAMS 4  // interleaved sub-tiles of one tile, each on its own internal stream
+#define RTMI_NDBG 24        // step statistics of the counting build (trace_oct.hpp: what each entry counts)
 struct DCtrl {
     uint32_t count[RTMI_MAX_PASSES + 1];  // rays queued for pass k
     uint32_t head[RTMI_MAX_PASSES + 1];   // work-fetch cursor of pass k
@@ -94,7 +95,7 @@ struct DCtrl {
     uint32_t slo[RTMI_MAX_PASSES + 1], shi[RTMI_MAX_PASSES + 1], shead[RTMI_MAX_PASSES + 1];
     unsigned long long rays;              // sum of count[] (the "Rays" statistic)
     unsigned long long counters[5];       // box_tests tri_tests full_tests nodes leaves
-    unsigned long long dbg[16];           // step statistics of the counting build (tools/step_stats.py)
+    unsigned long long dbg[RTMI_NDBG];    // step statistics of the counting build (tools/step_stats.py)
 };
 
 // The slow-path queue of one stream's batch.  A ray whose unit direction has an exactly-zero component skips that axis'
@@ -809,6 +810,7 @@ struct rtmi_scene {
     rtmi_tuning_t tune{};
     bool verbose = false;
     int vote[4] = {3, 2, 3, 2};  // SELECT : LEAF vote weights of the walk, primary rays / bounce rays (experiments: RTMI_VOTE="a,b,c,d")
+    int packet_cull = 1;         // k_path_primary culls leaf triangles per pixel packet (RTMI_PACKET_CULL=0: off, for comparison)
     unsigned long long vprev[RTMI_MAX_STREAMS][13] = {};  // verbose per-pass deltas (per handle: no shared statics)
 };
 
@@ -1030,7 +1032,9 @@ static void build_oct_form(const rtmi_box_t* boxes, uint64_t nboxes, const uint3
 }
 
 // LDS of an octree-walk launch: the counting build keeps 2 more memo words per lane (the list's plane and edge tests)
-static size_t oct_launch_lds(const rtmi_scene* s, bool count) { return s->oct_lds + (count ? 2 * 4 * 64 : 0); }
+// and every launch 64 B behind the memo for the packet of k_path_primary (trace_oct.hpp, Packet)
+static_assert(sizeof(Packet) <= 64, "packet slot in LDS");
+static size_t oct_launch_lds(const rtmi_scene* s, bool count) { return s->oct_lds + (count ? 2 * 4 * 64 : 0) + 64; }
 
 extern "C" {
 
@@ -1129,6 +1133,7 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
     s->tune.pipeline = (uint32_t)std::min<size_t>(env_size("RTMI_PIPELINE", 0), 3);
     s->tune.slow_path_off = (uint32_t)std::min<size_t>(env_size("RTMI_SLOW_PATH_OFF", 0), 1);
     s->verbose = getenv("RTMI_VERBOSE") != nullptr;
+    if (const char* v = getenv("RTMI_PACKET_CULL")) s->packet_cull = strcmp(v, "0") != 0;  // (env_size treats 0 as unset)
     if (const char* v = getenv("RTMI_VOTE")) {
         int q[4];
         if (sscanf(v, "%d,%d,%d,%d", &q[0], &q[1], &q[2], &q[3]) == 4 && q[0] > 0 && q[1] > 0 && q[2] > 0 && q[3] > 0) memcpy(s->vote, q, sizeof q);
@@ -1407,6 +1412,7 @@ static void launch_path(rtmi_scene* s, Work& w, hipStream_t st, int which, const
     a.mstack = w.mstack.p; a.scol = w.scol.p;
     a.slow = slow_queue(s, w);
     a.vote_s = which == W_PRIMARY ? s->vote[0] : s->vote[2]; a.vote_l = which == W_PRIMARY ? s->vote[1] : s->vote[3];
+    a.pcull = which == W_PRIMARY ? s->packet_cull : 0;
     const bool fast = (s->options & RTMI_OPT_FAST) != 0;
     if (which == W_SLOW) {
         // consumer launch `queue` of the slow path, on the side stream: after the producer whose event is sev[queue]
@@ -1973,16 +1979,44 @@ int rtmi_debug_status_of(int hip_error) {
     return RTMI_OK;
 }
 
-// Development aid (not in rtmi.h): step statistics of the last counting render/trace.
-int rtmi_debug_counters(rtmi_scene_t* s, unsigned long long* out16) {
-    if (!s || !out16) return fail(RTMI_ERR_INVALID, "NULL argument");
+// Development aid (not in rtmi.h): step statistics of the last counting render/trace, the first n <= RTMI_NDBG entries.
+int rtmi_debug_counters_n(rtmi_scene_t* s, unsigned long long* out, int n) {
+    if (!s || !out) return fail(RTMI_ERR_INVALID, "NULL argument");
+    if (n < 0 || n > RTMI_NDBG) return fail(RTMI_ERR_INVALID, "counter count out of range");
     HIPCHK(hipSetDevice(s->device));
-    memset(out16, 0, 16 * sizeof(unsigned long long));
+    memset(out, 0, n * sizeof(unsigned long long));
     for (int k = 0; k < RTMI_MAX_STREAMS; k++) {
         DCtrl h;
         HIPCHK(hipMemcpy(&h, s->w[k].ctrl.p, sizeof(DCtrl), hipMemcpyDeviceToHost));
-        for (int j = 0; j < 16; j++) out16[j] += h.dbg[j];
+        for (int j = 0; j < n; j++) out[j] += h.dbg[j];
     }
+    return RTMI_OK;
+}
+int rtmi_debug_counters(rtmi_scene_t* s, unsigned long long* out16) { return rtmi_debug_counters_n(s, out16, 16); }
+
+// Test hook (not in rtmi.h): the packet cull of k_path_primary evaluated on the host with the kernel's own functions
+// (trace_oct.hpp).  rays: n >= 1 rays (o.xyzw, d.xyzw: 8 floats each), the first one is the reference; recs: m plane records
+// (incenter.xyz, r2, norm.xyz, material: 8 floats each).  on <- 1 when culling is on for the packet; cull[j] <- 1 when
+// the predicate rejects record j for the whole packet (0 for all when it is off).  Needs no device.
+int rtmi_debug_packet_cull(const float* rays, uint32_t n, const float* recs, uint64_t m, int* on, uint8_t* cull) {
+    if (!rays || n < 1 || !on || (m > 0 && (!recs || !cull))) return fail(RTMI_ERR_INVALID, "NULL argument");
+    auto f4 = [](const float* v) { return make_float4(v[0], v[1], v[2], v[3]); };
+    Packet p{};
+    p.ox = rays[0]; p.oy = rays[1]; p.oz = rays[2];
+    p.dx = rays[4]; p.dy = rays[5]; p.dz = rays[6];
+    bool ok = true;
+    uint32_t mo = 0u, md = 0u;  // maxima as bit patterns, like the kernel's reduction
+    for (uint32_t i = 0; i < n; i++) {
+        float so, sd;
+        ok &= packet_spread(p, f4(rays + 8 * i), f4(rays + 8 * i + 4), so, sd);
+        uint32_t bo, bd;
+        memcpy(&bo, &so, 4); memcpy(&bd, &sd, 4);
+        mo = std::max(mo, bo); md = std::max(md, bd);
+    }
+    float so, sd;
+    memcpy(&so, &mo, 4); memcpy(&sd, &md, 4);
+    *on = ok && packet_finish(p, so, sd) ? 1 : 0;
+    for (uint64_t j = 0; j < m; j++) cull[j] = *on && packet_culls(p, f4(recs + 8 * j), f4(recs + 8 * j + 4)) ? 1 : 0;
     return RTMI_OK;
 }
 

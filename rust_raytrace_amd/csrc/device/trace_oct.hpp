@@ -92,6 +92,7 @@ struct OctArgs {
     SlowQ slow;       // W_PRIMARY: where zero-component rays go (cap == 0: nowhere, they are traced in place); W_SLOW: the queue
     uint32_t slow_k;  // W_SLOW: which consumer launch this is (its range and cursor in the control block)
     int vote_s, vote_l;  // weights of the SELECT / LEAF vote (3 : 2)
+    int pcull;           // W_PRIMARY: packet cull on (RTMI_PACKET_CULL, read at scene creation)
 };
 
 // Frame of an inner box: node = index of its record; w = visited octants (bits 0-7) | O_DONE | O_HAS;
@@ -126,6 +127,62 @@ __device__ inline T ld_off32(const T* base, uint32_t byte_off) {
     return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + (size_t)byte_off);
 }
 
+// ---- Packet cull (W_PRIMARY, DESIGN.md 4.1 "Packet cull"; rtmi_debug_packet_cull runs the same functions on the host).
+// A whole-wave refill of k_path_primary gives the 64 lanes samples of one pixel: nearly the same ray.  The refill records
+// a reference ray (o0, d0) -- the first lane's that took one -- and bounds so >= |o_i - o0|, sd >= |d_i - d0| over those
+// lanes (L1 norms, >= the Euclidean ones, rounded up).  A LEAF step whose lanes all stand at the same block then tests
+// each of its 4 triangles ONCE against the packet: packet_culls() proves that the exact plane test rejects it for every ray
+// of the packet, and only the triangles it cannot reject get the exact test.  Only IEEE + - * / and sqrtf, so host and
+// device compute the same bits.
+struct Packet {
+    float ox, oy, oz, dx, dy, dz;  // reference ray
+    float so, sd;                  // spreads of origin and direction
+    float eabs;                    // K (2 so + |o0|) (1 + K) + 1e-18: the ray-only absolute terms of the bound on |q - c|
+    float dhi, dinv;               // |d0| (1 + K); 1 / min_i |d_i|, rounded up
+    float pad;
+};
+#define PK_K 1e-5f  // relative slack: ~170 x the float rounding of any bound below
+// One ray of the packet: its spreads against the reference.  False: this ray turns culling off for the packet (nonzero
+// lane 3, huge coordinates, a direction outside the pixel's cone, NaN).
+__host__ __device__ inline bool packet_spread(const Packet& p, float4 o, float4 d, float& so, float& sd) {
+    so = ((fabsf(o.x - p.ox) + fabsf(o.y - p.oy)) + fabsf(o.z - p.oz)) * (1.f + PK_K);
+    sd = ((fabsf(d.x - p.dx) + fabsf(d.y - p.dy)) + fabsf(d.z - p.dz)) * (1.f + PK_K);
+    return (o.w == 0.f) & (d.w == 0.f) & (so <= 1e15f) & (sd <= 1.f / 64.f);
+}
+// The packet from the wave maxima of the spreads; false: no culling for it
+__host__ __device__ inline bool packet_finish(Packet& p, float so, float sd) {
+    p.so = so; p.sd = sd;
+    const float o1 = (fabsf(p.ox) + fabsf(p.oy)) + fabsf(p.oz);
+    const float dl = sqrtf((p.dx * p.dx + p.dy * p.dy) + p.dz * p.dz);
+    const float dlo = dl * (1.f - PK_K) - sd;
+    p.eabs = (PK_K * ((so + so) + o1)) * (1.f + PK_K) + 1e-18f;
+    p.dhi = dl * (1.f + PK_K);
+    p.dinv = (1.f / dlo) * (1.f + PK_K);
+    p.pad = 0.f;
+    return (o1 <= 1e15f) & (dlo >= 0.25f) & (dl <= 4.f);
+}
+// True: the exact plane test of the LEAF step (tri_test's `t < 0`, `l2 > r2`) rejects the triangle with plane record
+// (p0, p1) for EVERY ray (o_i, d_i) of the packet.  The argument: den_i is certified nonzero with margin,
+// so t_i is finite; if a ray passed, its point q = o_i + t d_i would be within emax of the incenter c (rounding of p, ip and
+// l2 included) and |t| <= tmax; but q is at least dist(c, line0) - so - |t| sd from c.  Rejected when that exceeds emax.
+__host__ __device__ inline bool packet_culls(const Packet& p, float4 p0, float4 p1) {
+    const float wx = p0.x - p.ox, wy = p0.y - p.oy, wz = p0.z - p.oz;
+    const float c1 = (fabsf(wx) + fabsf(wy)) + fabsf(wz);  // >= |c - o0|
+    // den: |n.d0| > 2 X, X >= the spread and rounding of n.d_i, so every |den_i| > X >= max(K |n| |d0|, 1e-30)
+    const float den0 = ((p1.x * p.dx + p1.y * p.dy) + p1.z * p.dz);
+    const float nn = (fabsf(p1.x) + fabsf(p1.y)) + fabsf(p1.z);
+    const float X = (nn * (p.sd + PK_K * (p.dhi + p.sd))) * (1.f + PK_K) + 1e-30f;
+    // distance: line0 must pass c farther than emax + so + tmax sd (+ the rounding of the cross product)
+    const float rho = sqrtf(p0.w);
+    const float emax = (rho + (PK_K * (c1 + p.so) + p.eabs)) * (1.f + PK_K);
+    const float tmax = (((emax + c1) + p.so) * p.dinv) * (1.f + PK_K);
+    const float lreq = (((emax + p.so) + tmax * p.sd) + PK_K * c1) * (1.f + PK_K);
+    const float cx = wy * p.dz - wz * p.dy, cy = wz * p.dx - wx * p.dz, cz = wx * p.dy - wy * p.dx;
+    const float x2 = (cx * cx + cy * cy) + cz * cz;  // |(c - o0) x d0|^2 = (dist(c, line0) |d0|)^2
+    const float y = lreq * p.dhi;
+    return (c1 <= 1e15f) & (nn <= 1e15f) & (fabsf(den0) > X + X) & (x2 > (y * y) * (1.f + PK_K));
+}
+
 template <bool COUNT, bool FAST, int MODE>
 __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCtrl* __restrict__ ctrl, uint32_t* __restrict__ lds,
                                          int refill_min, int xcd_aware) {
@@ -147,7 +204,9 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     // COUNT only: S steps, S lanes, L steps, L lanes, refills, refill lanes, edge steps, edge lanes, then shader-clock
     // cycles (s_memtime) this wave spent in SELECT steps, LEAF steps, refills, and in total
     // dbg[12..15]: leaf visits, leaf-memo hits, plane tests and edge tests the memo hits skipped
-    unsigned long long dbg[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // dbg[16..20] (W_PRIMARY): LEAF steps of the packet cull, all LEAF steps, references of those steps, references the
+    // predicate culls, violations (a culled reference whose exact test passed: must stay 0)
+    unsigned long long dbg[RTMI_NDBG] = {};
     const unsigned long long t_begin = COUNT ? __builtin_amdgcn_s_memtime() : 0ull;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     const float root_half = sc.root_half;
@@ -178,7 +237,15 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     // (raytrace.rs:1012-1050) is a pure function of the ray and the list.  The key is invalidated whenever a lane takes a
     // new ray.  Not in the slow path (its wide LEAF step keeps the ray's state in lane 0).
     constexpr bool MEMO = MODE != W_SLOW;
+    // W_PRIMARY: the packet of the last whole-wave refill (below) is wave-uniform and kept out of registers: it sits in the
+    // first 64 B of LDS (a constant address), the frame stack and the memo behind it
+    Packet* const pkl = reinterpret_cast<Packet*>(lds);
+    if (MODE == W_PRIMARY) lds += 16;
     uint32_t* const memo = lds + sc.levels * 2 * NT + lane;
+    // wave-uniform: PK_NEW = the lanes took new rays, the next LEAF step records their packet; PK_ON = LEAF steps may cull
+    // against *pkl
+    enum : uint32_t { PK_OFF = 0, PK_NEW = 1, PK_ON = 2 };
+    uint32_t pk = PK_OFF;
     auto take_leaf = [&](float t, uint32_t tf) {  // a finished leaf's hit into the frame and the running best
         if (!(fw & O_HAS) || t < ft) ft = t;
         fw |= O_HAS;
@@ -309,6 +376,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                 const float4 bo = make_float4(bc(no.x), bc(no.y), bc(no.z), bc(no.w)), bd = make_float4(bc(nd.x), bc(nd.y), bc(nd.z), bc(nd.w));
                 r = make_rayk(bo, bd);
             }
+            if (MODE == W_PRIMARY) pk = a.pcull ? PK_NEW : PK_OFF;  // every refill of k_path_primary is whole-wave
             if (MODE != W_TRACE && start) {  // one place where a path kernel's lane takes a ray: bounce in place, or refill
                 if (MODE != W_SLOW) r = make_rayk(no, nd);
                 path = npath; bounce = nbounce;
@@ -496,8 +564,130 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                         mode = M_SELECT;
                     }
                 }
-            } else
-            if (mode == M_LEAF) {
+            } else {
+            // ---- packet cull (W_PRIMARY): when every LEAF lane stands at the same block, lane i tests reference i & 3 of it
+            // against the whole packet (packet_culls); the references it cannot reject are tested in the packet step below,
+            // the full LEAF step runs when it culls none.  The counting build evaluates the predicate but tests every
+            // reference.
+            uint32_t keep = 0xFu, cullm = 0u;  // wave-uniform
+            uint4 ub = make_uint4(0u, 0u, 0u, 0u);
+            if (MODE == W_PRIMARY && __builtin_amdgcn_readfirstlane((int)pk) == (int)PK_NEW) {
+                // the packet of the last refill: the rays of every lane that has one (in W_PRIMARY a lane's ray only changes
+                // at a refill, so r still holds it; lanes whose ray went to the slow path are idle and do not count)
+                pk = PK_OFF;
+                const unsigned long long mr = __ballot(mode != M_IDLE);
+                const int l0 = __ffsll((long long)mr) - 1;
+                auto rl = [&](float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l0)); };
+                Packet p;
+                p.ox = rl(r.ox); p.oy = rl(r.oy); p.oz = rl(r.oz);
+                p.dx = rl(r.dx); p.dy = rl(r.dy); p.dz = rl(r.dz);
+                float so = 0.f, sd = 0.f;
+                bool ok = true;
+                if (mode != M_IDLE) ok = packet_spread(p, make_float4(r.ox, r.oy, r.oz, r.ow), make_float4(r.dx, r.dy, r.dz, r.dw), so, sd);
+                if (__ballot(!ok) == 0ull) {
+                    // wave maxima (non-negative finite floats order like their bit patterns)
+                    uint32_t mo = __float_as_uint(so), md = __float_as_uint(sd);
+#pragma unroll
+                    for (int k = 1; k < NT; k <<= 1) {
+                        mo = max(mo, (uint32_t)__shfl_xor((int)mo, k));
+                        md = max(md, (uint32_t)__shfl_xor((int)md, k));
+                    }
+                    if (packet_finish(p, __uint_as_float(__builtin_amdgcn_readfirstlane(mo)), __uint_as_float(__builtin_amdgcn_readfirstlane(md)))) {
+                        pk = PK_ON;
+                        if (lane == 0) *pkl = p;
+                    }
+                }
+            }
+            if (MODE == W_PRIMARY && __builtin_amdgcn_readfirstlane((int)pk) == (int)PK_ON) {
+                const uint32_t lb0 = (uint32_t)__builtin_amdgcn_readlane((int)lblock, __ffsll((long long)mL) - 1);
+                if (__ballot((mode == M_LEAF) & (lblock != lb0)) == 0ull) {
+                    const uint4 b = ld_off32(sc.oblocks, lb0 << 4);
+                    ub = b;
+                    uint32_t ln;  // (computed here: hipcc would otherwise keep lane & 1, lane & 2 live over the whole loop)
+                    asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(lane));
+                    const bool odd = (ln & 1u) != 0u;
+                    const uint32_t id = ((ln & 2u) ? (odd ? b.w : b.z) : (odd ? b.y : b.x)) & 0x7FFFFFFFu;
+                    const float4 q0 = ld_off32(sc.tplane, id << 5), q1 = ld_off32(sc.tplane, (id << 5) + 16u);
+                    cullm = (uint32_t)__ballot(packet_culls(*pkl, q0, q1)) & 0xFu;  // lanes 0..3 hold references 0..3
+                    if (!COUNT) keep = ~cullm & 0xFu;
+                    if (COUNT && lane == 0) {
+                        const uint32_t real = (b.x != 0u ? 1u : 0u) | (b.y != 0u ? 2u : 0u) | (b.z != 0u ? 4u : 0u) | ((b.w & 0x7FFFFFFFu) != 0u ? 8u : 0u);
+                        dbg[16]++; dbg[18] += __popc(real); dbg[19] += __popc(real & cullm);
+                    }
+                }
+                if (COUNT && lane == 0) dbg[17]++;
+            }
+            auto finish_leaf = [&]() {  // the list ended with this block
+                if (lhave) take_leaf(lt, ltf);
+                if (MEMO) {  // the key was written at leaf entry
+                    memo[NT] = __float_as_uint(lt);
+                    memo[2 * NT] = lhave ? ltf : 0u;
+                    if (COUNT) { memo[3 * NT] = (uint32_t)cnt[1] - memo[3 * NT]; memo[4 * NT] = (uint32_t)cnt[2] - memo[4 * NT]; }
+                }
+                mode = M_SELECT;
+            };
+            // Triangle::intersects (raytrace.rs:400-439), plane part for the 4 references, branch-free (a
+            // padding index 0 reads the sentinel's record and is masked out); see tri_test() for the lane-3
+            // terms.  A reference that passes `t >= 0` and the bounding-radius test becomes the lane's pending
+            // candidate; its edge part runs below, once per step.
+            struct Cand { uint32_t tri; float t, ix, iy, iz, den; };  // a lane's pending candidate (tri 0: none)
+            auto resolve = [&](const Cand& q) {
+                // all four edge records are requested together and every comparison is evaluated (no
+                // short-circuit): one memory round trip instead of three
+                if (COUNT) { cnt[2]++; const unsigned long long em = __ballot(true); if (lane == __ffsll((long long)em) - 1) { dbg[6]++; dbg[7] += __popcll(em); } }
+                const uint32_t eo = q.tri << 6;
+                const float4 e0 = ld_off32(sc.tedge, eo), e1 = ld_off32(sc.tedge, eo + 16u), e2 = ld_off32(sc.tedge, eo + 32u), e3 = ld_off32(sc.tedge, eo + 48u);
+                const float pz = (r.dw * q.t + r.ow) * 0.f;  // lane-3 product ip.w * side.w (side.w is +-0); ip.w as the plane part computed it
+                const float d0 = ((q.ix * e0.x + q.iy * e0.y) + q.iz * e0.z) + pz;
+                const float d1 = ((q.ix * e1.x + q.iy * e1.y) + q.iz * e1.z) + pz;
+                const float d2 = ((q.ix * e2.x + q.iy * e2.y) + q.iz * e2.z) + pz;
+                const bool inside = !(d0 > e0.w) & !(d1 > e1.w) & !(d2 > e2.w);
+                const bool edge = (d0 > e3.x) | (d1 > e3.y) | (d2 > e3.z);
+                const uint32_t face = (q.den > 0.f ? 1u : 0u) | (edge ? 2u : 0u);  // back face: norm . dir > 0
+                const bool take = inside & (!lhave | (q.t < lt));  // raytrace.rs:1028-1038
+                lt = take ? q.t : lt;
+                ltf = take ? (q.tri | (face << 30)) : ltf;
+                lhave = lhave | inside;
+            };
+            auto plane = [&](Cand& q, uint32_t id, const float4& a0, const float4& a1, bool culled) {
+                const float ax = a0.x - r.ox, ay = a0.y - r.oy, az = a0.z - r.oz;
+                const float num = (((0.f + a1.x * ax) + a1.y * ay) + a1.z * az) + r.qn;
+                const float den = (((0.f + a1.x * r.dx) + a1.y * r.dy) + a1.z * r.dz) + r.qd;
+                const float t = num / den;
+                const float px = r.dx * t + r.ox, py = r.dy * t + r.oy, pz_ = r.dz * t + r.oz, pw = r.dw * t + r.ow;
+                const float ix = px - a0.x, iy = py - a0.y, iz = pz_ - a0.z;
+                const float l2 = ((ix * ix + iy * iy) + iz * iz) + pw * pw;
+                const bool real = id != 0u;
+                if (COUNT) cnt[1] += real ? 1u : 0u;
+                const bool c = real & !(t < 0.f) & !(l2 > a0.w);
+                if (COUNT && c && culled) dbg[20]++;  // the packet predicate was wrong: must never happen
+                if (c & (q.tri != 0u)) resolve(q);  // second candidate of this lane in one block: rare
+                q.tri = c ? id : q.tri;
+                q.t = c ? t : q.t;
+                q.ix = c ? ix : q.ix; q.iy = c ? iy : q.iy; q.iz = c ? iz : q.iz;
+                q.den = c ? den : q.den;
+            };
+            bool lm = mode == M_LEAF;  // this lane runs the full LEAF step below
+            if (__builtin_amdgcn_readfirstlane((int)keep) != 0xF) {
+                // packet step that culled references: only the others are tested, one at a time (a wave-uniform loop; the
+                // block's words are wave-uniform); a block culled whole only moves the cursor
+                const uint32_t kp = (uint32_t)__builtin_amdgcn_readfirstlane((int)keep);
+                auto rf = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+                const uint32_t bx = rf(ub.x), by = rf(ub.y), bz = rf(ub.z), bw = rf(ub.w);
+                if (lm) {
+                    Cand q{0u, 0.f, 0.f, 0.f, 0.f, 0.f};
+                    for (uint32_t m = kp; m != 0u; m &= m - 1u) {  // one reference at a time, in list order
+                        const uint32_t k = (uint32_t)__builtin_ctz(m);
+                        const uint32_t id = k == 0u ? bx : k == 1u ? by : k == 2u ? bz : bw & 0x7FFFFFFFu;
+                        plane(q, id, ld_off32(sc.tplane, id << 5), ld_off32(sc.tplane, (id << 5) + 16u), false);
+                    }
+                    if (q.tri != 0u) resolve(q);
+                    if (bw != 0u && !(bw >> 31)) lblock++;
+                    else finish_leaf();
+                }
+                lm = false;
+            }
+            if (lm) {
                 const uint4 blk = ld_off32(sc.oblocks, lblock << 4);
                 const uint32_t ids[4] = {blk.x, blk.y, blk.z, blk.w & 0x7FFFFFFFu};
                 float4 p0[4], p1[4];
@@ -505,58 +695,12 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                 for (int k = 0; k < 4; k++) { p0[k] = ld_off32(sc.tplane, ids[k] << 5); p1[k] = ld_off32(sc.tplane, (ids[k] << 5) + 16u); }
                 const bool more = blk.w != 0u && !(blk.w >> 31);  // bit 31 of the 4th index: this full block is the last
                 if (more) lblock++;
-                // Triangle::intersects (raytrace.rs:400-439), plane part for the 4 references, branch-free (a
-                // padding index 0 reads the sentinel's record and is masked out); see tri_test() for the lane-3
-                // terms.  A reference that passes `t >= 0` and the bounding-radius test becomes the lane's pending
-                // candidate; its edge part runs below, once per step.
-                uint32_t ptri = 0u;
-                float pt = 0.f, pix = 0.f, piy = 0.f, piz = 0.f, pden = 0.f;
-                auto resolve = [&]() {
-                    // all four edge records are requested together and every comparison is evaluated (no
-                    // short-circuit): one memory round trip instead of three
-                    if (COUNT) { cnt[2]++; const unsigned long long em = __ballot(true); if (lane == __ffsll((long long)em) - 1) { dbg[6]++; dbg[7] += __popcll(em); } }
-                    const uint32_t eo = ptri << 6;
-                    const float4 e0 = ld_off32(sc.tedge, eo), e1 = ld_off32(sc.tedge, eo + 16u), e2 = ld_off32(sc.tedge, eo + 32u), e3 = ld_off32(sc.tedge, eo + 48u);
-                    const float pz = (r.dw * pt + r.ow) * 0.f;  // lane-3 product ip.w * side.w (side.w is +-0); ip.w as the plane part computed it
-                    const float d0 = ((pix * e0.x + piy * e0.y) + piz * e0.z) + pz;
-                    const float d1 = ((pix * e1.x + piy * e1.y) + piz * e1.z) + pz;
-                    const float d2 = ((pix * e2.x + piy * e2.y) + piz * e2.z) + pz;
-                    const bool inside = !(d0 > e0.w) & !(d1 > e1.w) & !(d2 > e2.w);
-                    const bool edge = (d0 > e3.x) | (d1 > e3.y) | (d2 > e3.z);
-                    const uint32_t face = (pden > 0.f ? 1u : 0u) | (edge ? 2u : 0u);  // back face: norm . dir > 0
-                    const bool take = inside & (!lhave | (pt < lt));  // raytrace.rs:1028-1038
-                    lt = take ? pt : lt;
-                    ltf = take ? (ptri | (face << 30)) : ltf;
-                    lhave = lhave | inside;
-                };
+                Cand q{0u, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const float ax = p0[k].x - r.ox, ay = p0[k].y - r.oy, az = p0[k].z - r.oz;
-                    const float num = (((0.f + p1[k].x * ax) + p1[k].y * ay) + p1[k].z * az) + r.qn;
-                    const float den = (((0.f + p1[k].x * r.dx) + p1[k].y * r.dy) + p1[k].z * r.dz) + r.qd;
-                    const float t = num / den;
-                    const float px = r.dx * t + r.ox, py = r.dy * t + r.oy, pz_ = r.dz * t + r.oz, pw = r.dw * t + r.ow;
-                    const float ix = px - p0[k].x, iy = py - p0[k].y, iz = pz_ - p0[k].z;
-                    const float l2 = ((ix * ix + iy * iy) + iz * iz) + pw * pw;
-                    const bool real = ids[k] != 0u;
-                    if (COUNT) cnt[1] += real ? 1u : 0u;
-                    const bool c = real & !(t < 0.f) & !(l2 > p0[k].w);
-                    if (c & (ptri != 0u)) resolve();  // second candidate of this lane in one block: rare
-                    ptri = c ? ids[k] : ptri;
-                    pt = c ? t : pt;
-                    pix = c ? ix : pix; piy = c ? iy : piy; piz = c ? iz : piz;
-                    pden = c ? den : pden;
-                }
-                if (ptri != 0u) resolve();
-                if (!more) {
-                    if (lhave) take_leaf(lt, ltf);
-                    if (MEMO) {  // the key was written at leaf entry
-                        memo[NT] = __float_as_uint(lt);
-                        memo[2 * NT] = lhave ? ltf : 0u;
-                        if (COUNT) { memo[3 * NT] = (uint32_t)cnt[1] - memo[3 * NT]; memo[4 * NT] = (uint32_t)cnt[2] - memo[4 * NT]; }
-                    }
-                    mode = M_SELECT;
-                }
+                for (int k = 0; k < 4; k++) plane(q, ids[k], p0[k], p1[k], (cullm >> k) & 1u);
+                if (q.tri != 0u) resolve(q);
+                if (!more) finish_leaf();
+            }
             }
         }
         if (COUNT && lane == 0) {  // the step is over for the wave when its slowest lane is (s_memtime is a scalar read)
@@ -576,7 +720,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
         for (int k = 0; k < 5; k++)
             if (cnt[k]) atomicAdd(&ctrl->counters[k], cnt[k]);
 #pragma unroll
-        for (int k = 0; k < 16; k++)
+        for (int k = 0; k < RTMI_NDBG; k++)
             if (dbg[k]) atomicAdd(&ctrl->dbg[k], dbg[k]);
     }
 }

@@ -256,6 +256,10 @@ int rtmi_debug_counters(rtmi_scene_t* s, unsigned long long* out16);
 int rth_debug_counters(rth_scene_t* s, unsigned long long* out16) {
     return guarded([&] { rtmi_debug_counters(caster_of(s).resident(s->scene), out16); });
 }
+int rtmi_debug_counters_n(rtmi_scene_t* s, unsigned long long* out, int n);
+int rth_debug_counters_n(rth_scene_t* s, unsigned long long* out, int n) {
+    return guarded([&] { rtmi_debug_counters_n(caster_of(s).resident(s->scene), out, n); });
+}
 
 void rth_quantize(const float* rgba, uint64_t npixels, uint8_t* rgb) {
     quantize_rgb8(reinterpret_cast<const Color*>(rgba), (size_t)npixels, rgb);

@@ -18,12 +18,13 @@ ctx = c.walk_rays(vp, scene, img)
 print(ctx.stats)
 # the resident scene handle lives inside the C++ caster; fetch the debug counters through a tiny helper
 lib = _ffi.lib()
-lib.rth_debug_counters.argtypes = [C.c_void_p, C.c_void_p]
-out = (C.c_ulonglong * 16)()
-lib.rth_debug_counters(scene.h, out)
+lib.rth_debug_counters_n.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+out = (C.c_ulonglong * 24)()
+lib.rth_debug_counters_n(scene.h, out, 24)
 d = list(out)
 names = ["S steps", "S lanes", "L steps", "L lanes", "refills", "refill lanes", "edge blocks", "edge lanes", "S cycles", "L cycles", "refill cycles", "wave cycles",
-         "leaf visits", "memo hits", "planes skipped", "edges skipped"]
+         "leaf visits", "memo hits", "planes skipped", "edges skipped",
+         "packet L steps", "primary L steps", "packet refs", "refs culled", "violations"]
 for n, v in zip(names, d):
     print(f"{n:14s} {v}")
 rays = ctx.stats["rays"]
@@ -37,3 +38,5 @@ print(f"shader-clock cycles of a wave (counting build, all passes of the last ba
 print(f"leaf memo: {d[13]} of {d[12]} leaf visits take the result of the list the ray scanned last ({d[13] / max(d[12], 1):.3f}); "
       f"plane tests skipped {d[14]} ({d[14] / max(ctx.stats['tri_tests'], 1):.3f} of the call's tri_tests if it was one batch), "
       f"edge tests skipped {d[15]} ({d[15] / max(ctx.stats['full_tests'], 1):.3f} of full_tests)")
+print(f"packet cull (primary pass): {d[16]} of {d[17]} LEAF steps qualify ({d[16] / max(d[17], 1):.3f}); "
+      f"{d[19]} of their {d[18]} references culled ({d[19] / max(d[18], 1):.3f}); violations {d[20]} (must be 0)")
