@@ -87,13 +87,13 @@ typedef struct rtmi_stats {
     double render_ms;       /* rtmi_render_tile_device of this scene's tile                                  */
     double band_copy_ms;    /* (quantise +) the band's one crossing to the root device, synchronised           */
     double deinterleave_ms; /* scenes[0] only: k_deinterleave (+ the copy to out_host)                         */
-    /* fused path pipeline (rtmi_tuning_t.pipeline): the two kernels of trace_ms apart, summed over streams and batches */
+    /* pipeline 3 (rtmi_tuning_t.pipeline): trace_ms split into its two parts, summed over streams and batches        */
     double primary_ms;      /* k_path_primary launches (pixel_ray + closest hit + color_ray of the primary rays)  */
-    double bounce_ms;       /* k_path_bounce launches (every bounce of every path, shaded in place)               */
+    double bounce_ms;       /* the bounce passes' closest-hit launches (k_trace_oct)                               */
     int32_t peer_access;    /* 1 = this device writes the root device's memory directly (peer access enabled, or the
                              * same device); 0 = the runtime refused: the band is staged (rtmi_last_error() carries a
                              * warning although the call returns RTMI_OK)                                      */
-    uint32_t pipeline;      /* which pipeline rendered (rtmi_tuning_t.pipeline: 1, 2 or 3)                         */
+    uint32_t pipeline;      /* which pipeline rendered (rtmi_tuning_t.pipeline: 1 or 3)                            */
     uint32_t slow_paths;    /* paths handed to k_path_slow (rtmi_tuning_t.slow_path_off)                           */
     uint32_t reserved;
 } rtmi_stats_t;
@@ -174,29 +174,30 @@ int rtmi_scene_set_options(rtmi_scene_t* scene, uint32_t options);
 
 /* Launch tuning of one scene handle.  Defaults are taken ONCE, at rtmi_scene_create(), from the environment
  * (RTMI_BATCH_PATHS, RTMI_STREAMS, RTMI_SUBTILE_MIN_PATHS, RTMI_OCT_WAVES_PER_CU, RTMI_REFILL_MIN0,
- * RTMI_REFILL_MIN, RTMI_XCD_AWARE, RTMI_KERNEL, RTMI_PIPELINE; RTMI_VERBOSE=1 prints per-pass timings to stderr) and can be read and changed
+ * RTMI_REFILL_MIN, RTMI_XCD_AWARE, RTMI_PIPELINE; RTMI_VERBOSE=1 prints per-pass timings to stderr) and can be read and changed
  * here.  None of them changes a pixel: any batch size, stream count or stripe split gives the same image. */
 typedef struct rtmi_tuning {
     uint64_t batch_paths;       /* paths (pixel samples) per batch of the wavefront pipeline, all streams together; default 256 Mi.
                                    A tile up to 1/8 larger is still rendered as one batch.                    */
     uint32_t streams;           /* 1..4 internal HIP streams (interleaved sub-tiles of a tile); 0 (default) = automatic:
-                                   one stream for tiles of 2^26 paths and more, three below                    */
+                                   one stream for tiles of 2^26 paths and more that run the path kernels
+                                   (pipeline 3), three otherwise (linear-list, generic-tree, BVH and sphere
+                                   scenes always get three)                                                   */
     uint32_t subtile_min_paths; /* tiles with fewer paths are not split over streams; default 32768           */
     uint32_t oct_waves_per_cu;  /* persistent waves per CU and launch of the octree kernel; 0 = automatic: what
                                    fits with one stream, at most 16 when several streams share the CUs       */
     uint32_t refill_min0;       /* idle lanes before a wave refills, primary pass (64 = whole wave); default 64 */
-    uint32_t refill_min;        /* the same for bounce passes (and the shading step of k_path_bounce); default 16       */
+    uint32_t refill_min;        /* the same for bounce passes; default 16                                      */
     uint32_t xcd_aware;         /* 1 = one ray-queue range per XCD (by XCC_ID), 2 = by block index, 0 = one queue (default) */
-    uint32_t kernel;            /* octree closest-hit kernel: 0 = automatic, 1 = one ray per lane (k_trace_oct),
-                                 * 2 = per-wave ray pool in LDS (k_trace_pool; falls back to 1 for very deep trees) */
-    uint32_t pipeline;          /* 0 = automatic (= 3), 1 = one launch per bounce pass (k_gen, then k_trace* + k_shade per
-                                 * pass), 2 = fused path kernels: primary rays generated, traced and shaded in one kernel
-                                 * (k_path_primary), all bounces in ONE persistent kernel that shades in place
-                                 * (k_path_bounce; 62 instead of 106 bytes of workspace per path), 3 = k_path_primary, then
-                                 * one closest-hit + one shading launch per bounce pass.  2 and 3 apply to octree scenes;
-                                 * anything else (linear list, generic tree, BVH mode, analytic spheres) runs 1.
-                                 * Same image whichever runs.  Environment: RTMI_PIPELINE.                              */
-    uint32_t slow_path_off;     /* 0 (default): in pipelines 2 and 3 a ray whose unit direction has an exactly-zero component
+    uint32_t kernel;            /* unused: the octree closest-hit kernel is always k_trace_oct.  0 and 1 are accepted;
+                                 * 2 (a removed kernel) is refused with RTMI_ERR_UNSUPPORTED                            */
+    uint32_t pipeline;          /* 0 = automatic (= 3), 1 = one launch per pass (k_gen, then k_trace* + k_shade per pass),
+                                 * 3 = the path kernels: primary rays generated, traced and shaded in one kernel
+                                 * (k_path_primary), then one closest-hit + one shading launch per bounce pass.  3 applies
+                                 * to octree scenes; anything else (linear list, generic tree, BVH mode, analytic spheres)
+                                 * runs 1.  Same image whichever runs.  2 (a removed pipeline) is refused with
+                                 * RTMI_ERR_UNSUPPORTED.  Environment: RTMI_PIPELINE (2 there is read as 0).            */
+    uint32_t slow_path_off;     /* 0 (default): in pipeline 3 a ray whose unit direction has an exactly-zero component
                                  * (BoundingBox::collides then skips that axis' slab, raytrace.rs:872-900: ~150 x the work of an
                                  * ordinary ray, 14 ms for the lane that traces it) is set aside and its path is traced by
                                  * k_path_slow on a side stream, one path per wave, beside the following passes; 1: such rays

@@ -80,8 +80,6 @@ struct DScene {
 };
 #define RTMI_FN_WIDE 0x10000u
 
-// which octree kernel tune.kernel == 0 selects (measured on MI355X)
-#define RTMI_DEFAULT_POOL 0
 #define RTMI_MAX_PASSES 32
 #define RTMI_MAX_STREAMS 4  // interleaved sub-tiles of one tile, each on its own internal stream
 #define RTMI_NDBG 24        // step statistics of the counting build (trace_oct.hpp: what each entry counts)
@@ -372,7 +370,6 @@ __global__ void __launch_bounds__(256) k_trace(DScene sc, const float4* __restri
 #include "build_octree.hpp"
 #include "shade.hpp"
 #include "trace_oct.hpp"
-#include "trace_pool.hpp"
 #include "bvh_fast.hpp"
 namespace rtmi {
 
@@ -492,7 +489,7 @@ __global__ void __launch_bounds__(256) k_trace_linear(DScene sc, const float4* _
 }
 
 // ---------------------------------------------------------------- generation / shading (per-pass pipeline)
-// pixel_ray / color_ray themselves are in shade.hpp (shared with the fused path kernels of trace_oct.hpp).
+// pixel_ray / color_ray themselves are in shade.hpp (shared with the path kernels of trace_oct.hpp).
 __global__ void __launch_bounds__(256) k_gen(DView v, uint64_t seed, uint32_t pix0, uint32_t npaths,
                                              float4* __restrict__ qo, float4* __restrict__ qd,
                                              uint32_t* __restrict__ qpath, DCtrl* __restrict__ ctrl) {
@@ -730,7 +727,6 @@ using namespace rtmi;
 struct Work {
     size_t cap = 0;
     uint32_t cap_depth = 0;
-    bool full = false;  // both queues + hit records allocated (per-pass pipeline, rtmi_trace)
     DevBuf<float4> qo[2], qd[2], scol;
     DevBuf<uint32_t> qpath[2], hit_tf;
     DevBuf<float> hit_t;
@@ -756,7 +752,7 @@ struct Work {
         if (sdone) { (void)hipEventDestroy(sdone); sdone = nullptr; }
         if (sgo) { (void)hipEventDestroy(sgo); sgo = nullptr; }
         if (sstream) { (void)hipStreamDestroy(sstream); sstream = nullptr; }
-        cap = 0; cap_depth = 0; full = false;
+        cap = 0; cap_depth = 0;
     }
 };
 
@@ -784,10 +780,6 @@ struct rtmi_scene {
     int oct_blocks_per_cu = 8;   // what fits (occupancy query)
     uint32_t active_streams = 1; // sub-tiles of the render call in flight: their persistent kernels share the CUs
     size_t oct_lds = 0;
-    // k_trace_pool: rays per wave, slot stride (words), LDS bytes per wave, waves per CU; pool_P == 0: not available
-    uint32_t pool_P = 0, pool_stride = 0;
-    size_t pool_lds = 0;
-    int pool_blocks_per_cu = 0;
     // A tile is rendered as up to two interleaved sub-tiles, each with its own workspace on its own internal
     // stream, so that the small deep bounce passes of one overlap the bulk of the other.
     Work w[RTMI_MAX_STREAMS];
@@ -1129,8 +1121,8 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
     s->tune.refill_min0 = (uint32_t)std::min<size_t>(env_size("RTMI_REFILL_MIN0", 64), 64);
     s->tune.refill_min = (uint32_t)std::min<size_t>(env_size("RTMI_REFILL_MIN", 16), 64);
     s->tune.xcd_aware = (uint32_t)(env_size("RTMI_XCD_AWARE", 0) % 3);
-    s->tune.kernel = (uint32_t)std::min<size_t>(env_size("RTMI_KERNEL", 0), 2);
     s->tune.pipeline = (uint32_t)std::min<size_t>(env_size("RTMI_PIPELINE", 0), 3);
+    if (s->tune.pipeline == 2u) s->tune.pipeline = 0u;  // the removed fused pipeline: automatic
     s->tune.slow_path_off = (uint32_t)std::min<size_t>(env_size("RTMI_SLOW_PATH_OFF", 0), 1);
     s->verbose = getenv("RTMI_VERBOSE") != nullptr;
     if (const char* v = getenv("RTMI_PACKET_CULL")) s->packet_cull = strcmp(v, "0") != 0;  // (env_size treats 0 as unset)
@@ -1161,6 +1153,8 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
     if (e == hipSuccess && s->octree) e = up(s->wlinks, hwl);
     for (int k = 0; k < RTMI_MAX_STREAMS && e == hipSuccess; k++) {
         e = s->w[k].ctrl.ensure(1);
+        // zeroed once here (each batch zeroes its own): rtmi_debug_counters_n also reads the blocks of streams no render used
+        if (e == hipSuccess) e = hipMemset(s->w[k].ctrl.p, 0, sizeof(DCtrl));
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->istream[k], hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreate(&s->w[k].ev[0]);
         if (e == hipSuccess) e = hipEventCreate(&s->w[k].ev[1]);
@@ -1181,21 +1175,6 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
             int nb = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace_oct<false, false>, 64, s->oct_lds) == hipSuccess && nb > 0)
                 s->oct_blocks_per_cu = nb;
-            // ray-pool form: 24 state words + 2 per stack level, an odd number of 16-B quads per slot (conflict-free
-            // ds_read_b128 of neighbouring slots); as many rays as fit 1/8 of the CU's 160 KB (8 waves per CU)
-            uint32_t quads = (24u + 2u * std::max<uint32_t>(1u, max_inner_depth) + 3u) / 4u;
-            if (!(quads & 1u)) quads++;
-            const uint32_t stride = quads * 4u;
-            const size_t budget = 160u * 1024u / 8u - 2u * RTMI_POOL_MAX;
-            const uint32_t P = (uint32_t)std::min<size_t>(RTMI_POOL_MAX, budget / (stride * 4u));
-            if (P >= 96u && hfn.size() / 2 < (1u << 22)) {
-                s->pool_P = P; s->pool_stride = stride;
-                s->pool_lds = (size_t)P * stride * 4u + 2u * RTMI_POOL_MAX;
-                nb = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace_pool<false, false>, 64, s->pool_lds) == hipSuccess && nb > 0)
-                    s->pool_blocks_per_cu = nb;
-                else s->pool_P = 0;
-            }
         }
     }
     s->htris.assign(tris, tris + ntris);  // rtmi_scene_set_corners rebuilds the fast-mode BVH from them
@@ -1289,28 +1268,24 @@ int rtmi_scene_set_tuning(rtmi_scene_t* s, const rtmi_tuning_t* in) {
     if (in->batch_paths == 0 || in->streams > RTMI_MAX_STREAMS || in->oct_waves_per_cu > 32 || in->refill_min0 < 1 ||
         in->refill_min0 > 64 || in->refill_min < 1 || in->refill_min > 64 || in->xcd_aware > 2 || in->kernel > 2 || in->pipeline > 3 || in->slow_path_off > 1)
         return fail(RTMI_ERR_INVALID, "tuning value out of range");
+    if (in->kernel == 2) return fail(RTMI_ERR_UNSUPPORTED, "tuning kernel = 2: the ray-pool kernel k_trace_pool was removed (0 and 1 select k_trace_oct)");
+    if (in->pipeline == 2) return fail(RTMI_ERR_UNSUPPORTED, "tuning pipeline = 2: the fused bounce pipeline was removed (0, 1 or 3)");
     s->tune = *in;
     return RTMI_OK;
 }
 
-// fused = the path kernels only: ONE ray queue (the bounce rays of the primary pass), no hit records -- 62 B per path at
-// depth 5 instead of 106
-static int ensure_workspace(Work& w, size_t cap, uint32_t maxdepth, bool fused) {
-    if (cap <= w.cap && maxdepth <= w.cap_depth && (fused || w.full)) return RTMI_OK;
+static int ensure_workspace(Work& w, size_t cap, uint32_t maxdepth) {
+    if (cap <= w.cap && maxdepth <= w.cap_depth) return RTMI_OK;
     cap = std::max(cap, w.cap);
     maxdepth = std::max(maxdepth, w.cap_depth);
-    const bool full = w.full || !fused;
-    for (int k = 0; k < (full ? 2 : 1); k++) {
+    for (int k = 0; k < 2; k++) {
         HIPCHK(w.qo[k].ensure(cap));
         HIPCHK(w.qd[k].ensure(cap));
         HIPCHK(w.qpath[k].ensure(cap));
     }
     HIPCHK(w.scol.ensure(cap));
-    if (full) {
-        HIPCHK(w.hit_tf.ensure(cap));
-        HIPCHK(w.hit_t.ensure(cap));
-    }
-    w.full = full;
+    HIPCHK(w.hit_tf.ensure(cap));
+    HIPCHK(w.hit_t.ensure(cap));
     HIPCHK(w.mstack.ensure(cap * (size_t)maxdepth));
     HIPCHK(w.sqo.ensure(RTMI_SLOW_CAP)); HIPCHK(w.sqd.ensure(RTMI_SLOW_CAP));
     HIPCHK(w.sqpath.ensure(RTMI_SLOW_CAP)); HIPCHK(w.sqbounce.ensure(RTMI_SLOW_CAP));
@@ -1339,6 +1314,16 @@ static int ensure_workspace(Work& w, size_t cap, uint32_t maxdepth, bool fused) 
     return RTMI_OK;
 }
 
+// Persistent grid of the octree walk kernels (trace_oct.hpp).  About 24 resident waves per CU in all is the optimum of
+// this VALU-issue-bound walk (more only adds cache pressure): one stream launches what fits, two or more share the CUs with
+// 16 each (two streams: 12 / 14 / 16 / 17 / 18 / 20 / 24 waves per launch = 929 / 962 / 980 / 985 / 971 / 965 / 955 Mrays/s;
+// one stream: 16 / 20 / 24 = 808 / 882 / 931).
+static dim3 oct_grid(const rtmi_scene* s) {
+    const int per_cu = s->tune.oct_waves_per_cu ? (int)s->tune.oct_waves_per_cu
+                                                 : s->active_streams > 1 ? std::min(s->oct_blocks_per_cu, 16) : s->oct_blocks_per_cu;
+    return dim3((unsigned)(s->num_cu * per_cu));
+}
+
 extern "C++" {
 template <bool COUNT>
 static void launch_trace(rtmi_scene* s, Work& w, hipStream_t st, const float4* qo, const float4* qd, int pass, hipEvent_t stop) {
@@ -1352,34 +1337,15 @@ static void launch_trace(rtmi_scene* s, Work& w, hipStream_t st, const float4* q
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_linear<COUNT>), dim3((unsigned)(s->num_cu * 8)), dim3(256), 0, st, s->d, qo, qd,
                            w.ctrl.p, pass, w.hit_tf.p, w.hit_t.p);
     } else if (s->octree && !(s->options & RTMI_OPT_GENERIC)) {
-        // About 24 resident waves per CU in all is the optimum of this VALU-issue-bound kernel (more only adds cache
-        // pressure): one stream launches what fits, two or more share the CUs with 16 each (two streams: 12 / 14 / 16 / 17 /
-        // 18 / 20 / 24 waves per launch = 929 / 962 / 980 / 985 / 971 / 965 / 955 Mrays/s; one stream: 16 / 20 / 24 = 808 /
-        // 882 / 931).
-        const int per_cu = s->tune.oct_waves_per_cu ? (int)s->tune.oct_waves_per_cu
-                                                     : s->active_streams > 1 ? std::min(s->oct_blocks_per_cu, 16) : s->oct_blocks_per_cu;
-        const dim3 grid((unsigned)(s->num_cu * per_cu)), block(64);
         const int refill = (int)(pass == 0 ? s->tune.refill_min0 : s->tune.refill_min);
         const int xcd = (int)(s->tune.xcd_aware % 3u);  // 1 = ranges by XCC_ID, 2 = by blockIdx % 8, 0 = one range
-        const bool pool = s->pool_P != 0 && s->tune.kernel != 1u && (s->tune.kernel == 2u || RTMI_DEFAULT_POOL);
-        if (pool) {
-            const int ppc = s->tune.oct_waves_per_cu ? std::min<int>((int)s->tune.oct_waves_per_cu, s->pool_blocks_per_cu) : s->pool_blocks_per_cu;
-            const dim3 pgrid((unsigned)(s->num_cu * ppc));
-            if (s->options & RTMI_OPT_FAST)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_pool<COUNT, true>), pgrid, block, s->pool_lds, st, s->d, qo, qd, w.ctrl.p, pass,
-                                   w.hit_tf.p, w.hit_t.p, refill, xcd, s->pool_P, s->pool_stride);
-            else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_pool<COUNT, false>), pgrid, block, s->pool_lds, st, s->d, qo, qd, w.ctrl.p, pass,
-                                   w.hit_tf.p, w.hit_t.p, refill, xcd, s->pool_P, s->pool_stride);
-        } else {
-            OctArgs a{};
-            a.qo = qo; a.qd = qd; a.hit_tf = w.hit_tf.p; a.hit_t = w.hit_t.p; a.pass = pass;
-            a.vote_s = pass == 0 ? s->vote[0] : s->vote[2]; a.vote_l = pass == 0 ? s->vote[1] : s->vote[3];
-            if (s->options & RTMI_OPT_FAST)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_oct<COUNT, true>), grid, block, oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
-            else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_oct<COUNT, false>), grid, block, oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
-        }
+        OctArgs a{};
+        a.qo = qo; a.qd = qd; a.hit_tf = w.hit_tf.p; a.hit_t = w.hit_t.p; a.pass = pass;
+        a.vote_s = pass == 0 ? s->vote[0] : s->vote[2]; a.vote_l = pass == 0 ? s->vote[1] : s->vote[3];
+        if (s->options & RTMI_OPT_FAST)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_oct<COUNT, true>), oct_grid(s), dim3(64), oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_oct<COUNT, false>), oct_grid(s), dim3(64), oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
     } else {
         // persistent grid: enough blocks to fill every CU at the occupancy LDS allows
         const int per_cu = s->trace_block == 256 ? 4 : 16;
@@ -1396,48 +1362,50 @@ static SlowQ slow_queue(rtmi_scene* s, Work& w) {
     const bool on = s->tune.slow_path_off == 0u && w.sqo.p && w.sstream;
     return SlowQ{w.sqo.p, w.sqd.p, w.sqpath.p, w.sqbounce.p, on ? RTMI_SLOW_CAP : 0u};
 }
-// The fused path kernels (trace_oct.hpp): which = W_PRIMARY, W_BOUNCE or W_SLOW.  `stop` is recorded right after the kernel.
-template <bool COUNT>
-static void launch_path(rtmi_scene* s, Work& w, hipStream_t st, int which, const DView& dv, uint64_t seed, uint32_t pix0, uint32_t npaths,
-                        hipEvent_t stop, int queue = 0) {
-    const int per_cu = s->tune.oct_waves_per_cu ? (int)s->tune.oct_waves_per_cu
-                                                 : s->active_streams > 1 ? std::min(s->oct_blocks_per_cu, 16) : s->oct_blocks_per_cu;
-    const dim3 grid((unsigned)(s->num_cu * per_cu)), block(64);
-    const int refill = (int)(which == W_PRIMARY ? s->tune.refill_min0 : s->tune.refill_min);
-    const int xcd = (int)(s->tune.xcd_aware % 3u);
+// What both path kernels (trace_oct.hpp) read: the batch's paths, their surface stacks and sample colours, the slow-path queue
+static OctArgs path_args(rtmi_scene* s, Work& w, const DView& dv, uint64_t seed, uint32_t pix0, uint32_t npaths) {
     OctArgs a{};
     a.v = dv; a.seed = seed; a.pix0 = pix0; a.npaths = npaths;
-    const int bq = which == W_SLOW ? 0 : queue;  // (for W_SLOW `queue` is the consumer launch number)
-    a.bqo = w.qo[bq].p; a.bqd = w.qd[bq].p; a.bqpath = w.qpath[bq].p;
     a.mstack = w.mstack.p; a.scol = w.scol.p;
     a.slow = slow_queue(s, w);
-    a.vote_s = which == W_PRIMARY ? s->vote[0] : s->vote[2]; a.vote_l = which == W_PRIMARY ? s->vote[1] : s->vote[3];
-    a.pcull = which == W_PRIMARY ? s->packet_cull : 0;
-    const bool fast = (s->options & RTMI_OPT_FAST) != 0;
-    if (which == W_SLOW) {
-        // consumer launch `queue` of the slow path, on the side stream: after the producer whose event is sev[queue]
-        a.slow_k = (uint32_t)queue;
-        (void)hipStreamWaitEvent(w.sstream, w.sev[queue], 0);
-        hipLaunchKernelGGL(k_slow_snapshot, dim3(1), dim3(1), 0, w.sstream, w.ctrl.p, (uint32_t)queue, a.slow.cap);
-        // The ordinary stream goes on only after the snapshot: its next persistent launch and the slow-path launch then become
-        // ready together and the high-priority one gets its few wave slots first.  (Without this the next launch, already
-        // queued in order, took every slot while the side stream was still resolving the event, and the slow paths started
-        // a whole pass late.)
-        (void)hipEventRecord(w.sgo, w.sstream);
-        (void)hipStreamWaitEvent(st, w.sgo, 0);
-        const dim3 sgrid((unsigned)std::max(s->num_cu / 2, 1));  // one path per wave at a time; a frame has ~100 such paths, a wave takes one after the other
-        if (fast) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow<COUNT, true>), sgrid, block, oct_launch_lds(s, COUNT), w.sstream, s->d, a, w.ctrl.p, 1, 0);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow<COUNT, false>), sgrid, block, oct_launch_lds(s, COUNT), w.sstream, s->d, a, w.ctrl.p, 1, 0);
-        return;
-    }
-    if (which == W_PRIMARY) {
-        if (fast) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary<COUNT, true>), grid, block, oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary<COUNT, false>), grid, block, oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
-    } else {
-        if (fast) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_bounce<COUNT, true>), grid, block, oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_bounce<COUNT, false>), grid, block, oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
-    }
+    return a;
+}
+// k_path_primary: the batch's primary rays generated, traced and shaded; the bounce rays go to queue 1, which pass 1 traces.
+// `stop` is recorded right after the kernel.
+template <bool COUNT>
+static void launch_primary(rtmi_scene* s, Work& w, hipStream_t st, const DView& dv, uint64_t seed, uint32_t pix0, uint32_t npaths,
+                           hipEvent_t stop) {
+    OctArgs a = path_args(s, w, dv, seed, pix0, npaths);
+    a.bqo = w.qo[1].p; a.bqd = w.qd[1].p; a.bqpath = w.qpath[1].p;
+    a.vote_s = s->vote[0]; a.vote_l = s->vote[1];
+    a.pcull = s->packet_cull;
+    const int refill = (int)s->tune.refill_min0, xcd = (int)(s->tune.xcd_aware % 3u);
+    if (s->options & RTMI_OPT_FAST)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary<COUNT, true>), oct_grid(s), dim3(64), oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary<COUNT, false>), oct_grid(s), dim3(64), oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
     (void)hipEventRecord(stop, st);
+}
+// Consumer launch k of the slow path (k_path_slow), on the side stream: after the producer on `st` whose event is sev[k]
+template <bool COUNT>
+static void launch_slow(rtmi_scene* s, Work& w, hipStream_t st, const DView& dv, uint64_t seed, uint32_t pix0, uint32_t npaths,
+                        uint32_t k) {
+    OctArgs a = path_args(s, w, dv, seed, pix0, npaths);
+    a.slow_k = k;
+    a.vote_s = s->vote[2]; a.vote_l = s->vote[3];
+    (void)hipStreamWaitEvent(w.sstream, w.sev[k], 0);
+    hipLaunchKernelGGL(k_slow_snapshot, dim3(1), dim3(1), 0, w.sstream, w.ctrl.p, k, a.slow.cap);
+    // The ordinary stream goes on only after the snapshot: its next persistent launch and the slow-path launch then become
+    // ready together and the high-priority one gets its few wave slots first.  (Without this the next launch, already
+    // queued in order, took every slot while the side stream was still resolving the event, and the slow paths started
+    // a whole pass late.)
+    (void)hipEventRecord(w.sgo, w.sstream);
+    (void)hipStreamWaitEvent(st, w.sgo, 0);
+    const dim3 sgrid((unsigned)std::max(s->num_cu / 2, 1));  // one path per wave at a time; a frame has ~100 such paths, a wave takes one after the other
+    if (s->options & RTMI_OPT_FAST)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow<COUNT, true>), sgrid, dim3(64), oct_launch_lds(s, COUNT), w.sstream, s->d, a, w.ctrl.p, 1, 0);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow<COUNT, false>), sgrid, dim3(64), oct_launch_lds(s, COUNT), w.sstream, s->d, a, w.ctrl.p, 1, 0);
 }
 }  // extern "C++"
 
@@ -1505,19 +1473,16 @@ int rtmi_render_tile_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t
     //      shares whatever the tile's own striping is.  (Round 2 dealt out whole stripes: with the 16-row stripes of an
     //      8-rank tiling a stream's stripes repeat every 384 image rows, the teapot covers two such periods and the slowest
     //      stream of a rank carried up to 12 % more rays than the others.)
-    // path kernels (pipelines 2 and 3): exact-octree scenes traced by k_trace_oct's walk; everything else (linear list, generic
-    // tree, BVH mode, ray-pool kernel, analytic spheres) runs one launch per bounce pass
-    const bool pool_kernel = s->pool_P != 0 && s->tune.kernel != 1u && (s->tune.kernel == 2u || RTMI_DEFAULT_POOL);
-    // 0 = automatic = 3: k_path_primary, then one launch per bounce pass (measured fastest on MI355X at every tile size,
-    // DESIGN.md 4.1c)
-    const bool hybrid_req = s->tune.pipeline == 3u || s->tune.pipeline == 0u;
-    const bool fused = s->tune.pipeline != 1u && s->octree && !s->root_is_leaf && !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) &&
-                       !pool_kernel && s->d.nspheres == 0;
+    // path kernels (pipeline 3; 0 = automatic): exact-octree scenes get pass 0 from k_path_primary, which generates, traces and
+    // shades the primary rays in one kernel.  Everything else (pipeline 1, linear list, generic tree, BVH mode,
+    // analytic spheres) starts with k_gen.  Both then run one closest-hit + one shading launch per bounce pass.
+    const bool path_kernels = s->tune.pipeline != 1u && s->octree && !s->root_is_leaf &&
+                              !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) && s->d.nspheres == 0;
     // streams = 0 (automatic): one stream for path-kernel tiles of 2^26 paths and more, three otherwise (the per-pass
     // pipelines -- BVH mode: 29.6 ms on three streams, 35.2 on one -- have elementwise kernels to hide).  Since k_shade stopped being
     // atomic-bound (round 3) there is little left for a second stream to hide: the full config-3 frame takes 366.9 ms on one
     // stream and 371.8 on three (the sub-tiles' persistent launches compete for the same wave slots); a 1/8 tile 52.1 vs 51.6.
-    const uint32_t auto_streams = (fused && npix * spp >= (1ull << 26)) ? 1u : 3u;
+    const uint32_t auto_streams = (path_kernels && npix * spp >= (1ull << 26)) ? 1u : 3u;
     uint32_t nsub = std::min<uint32_t>(s->tune.streams ? s->tune.streams : auto_streams, (uint32_t)RTMI_MAX_STREAMS);
     nsub = std::min<uint32_t>(nsub, nrows);
     if (npix * spp < s->tune.subtile_min_paths) nsub = 1;
@@ -1551,7 +1516,7 @@ int rtmi_render_tile_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t
     pix_per_batch = std::min<uint64_t>(pix_per_batch, max_sub_npix);
     if (pix_per_batch * spp >= (1ull << 31)) return fail(RTMI_ERR_UNSUPPORTED, "batch above 2^31 paths");
     for (uint32_t t = 0; t < nsub; t++) {
-        int rc = ensure_workspace(s->w[t], (size_t)(std::min<uint64_t>(pix_per_batch, sub[t].npix) * spp), maxdepth, fused && !hybrid_req);
+        int rc = ensure_workspace(s->w[t], (size_t)(std::min<uint64_t>(pix_per_batch, sub[t].npix) * spp), maxdepth);
         if (rc != RTMI_OK) return rc;
     }
 
@@ -1577,75 +1542,34 @@ int rtmi_render_tile_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t
             const uint32_t pix0 = (uint32_t)p0;  // local pixel index inside the sub-tile
             HIPCHK(hipMemsetAsync(w.ctrl.p, 0, sizeof(DCtrl), st));
             HIPCHK(hipEventRecord(w.ev[0], st));
-            if (fused && hybrid_req) {
-                // primary rays generated, traced and shaded in one kernel (its bounce rays go to the queue pass 1 reads),
-                // then one closest-hit + one shading launch per bounce pass
+            // the slow path: zero-component rays that k_path_primary and k_shade set aside, traced beside the following passes
+            const SlowQ sq = path_kernels ? slow_queue(s, w) : SlowQ{nullptr, nullptr, nullptr, nullptr, 0u};
+            auto slow_after = [&](uint32_t k) {  // after producer k: k_path_primary (0) or the shading of pass k
+                if (sq.cap == 0u) return;
+                (void)hipEventRecord(w.sev[k], st);
+                if (counting) launch_slow<true>(s, w, st, dv, seed, pix0, npaths, k);
+                else launch_slow<false>(s, w, st, dv, seed, pix0, npaths, k);
+            };
+            uint32_t pass0 = 0;  // first pass of the per-pass loop
+            if (path_kernels) {
                 HIPCHK(hipEventRecord(w.pass_ev[0], st));
-                if (counting) launch_path<true>(s, w, st, W_PRIMARY, dv, seed, pix0, npaths, w.pass_ev[1], 1);
-                else launch_path<false>(s, w, st, W_PRIMARY, dv, seed, pix0, npaths, w.pass_ev[1], 1);
+                if (counting) launch_primary<true>(s, w, st, dv, seed, pix0, npaths, w.pass_ev[1]);
+                else launch_primary<false>(s, w, st, dv, seed, pix0, npaths, w.pass_ev[1]);
                 HIPCHK(hipGetLastError());
                 launches++;
-                // the slow path (zero-component rays the producer set aside) runs beside the following passes
-                const bool slow_on = slow_queue(s, w).cap != 0u;
-                auto slow_after = [&](uint32_t k) {
-                    if (!slow_on) return;
-                    (void)hipEventRecord(w.sev[k], st);
-                    if (counting) launch_path<true>(s, w, st, W_SLOW, dv, seed, pix0, npaths, nullptr, (int)k);
-                    else launch_path<false>(s, w, st, W_SLOW, dv, seed, pix0, npaths, nullptr, (int)k);
-                };
                 slow_after(0);
-                HIPCHK(hipGetLastError());
-                for (uint32_t pass = 1; pass < maxdepth; pass++) {
-                    const int a = pass & 1, b = a ^ 1;
-                    HIPCHK(hipEventRecord(w.pass_ev[2 * pass], st));
-                    if (counting) launch_trace<true>(s, w, st, w.qo[a].p, w.qd[a].p, (int)pass, w.pass_ev[2 * pass + 1]);
-                    else launch_trace<false>(s, w, st, w.qo[a].p, w.qd[a].p, (int)pass, w.pass_ev[2 * pass + 1]);
-                    HIPCHK(hipGetLastError());
-                    hipLaunchKernelGGL(k_shade, dim3(ew_blocks), dim3(256), 0, st, s->d, dv, seed, pix0, npaths, (int)pass,
-                                       w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p,
-                                       w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, slow_queue(s, w));
-                    HIPCHK(hipGetLastError());
-                    if (pass + 1 < maxdepth) slow_after(pass);  // the last pass's shading emits no rays
-                    HIPCHK(hipGetLastError());
-                    launches++;
-                }
-                if (slow_on) {  // the sample colours of the slow paths must be there before k_accum
-                    HIPCHK(hipEventRecord(w.sdone, w.sstream));
-                    HIPCHK(hipStreamWaitEvent(st, w.sdone, 0));
-                }
-            } else if (fused) {
-                // primary rays generated, traced and shaded in one kernel; every bounce of every path in one more
-                HIPCHK(hipEventRecord(w.pass_ev[0], st));
-                if (counting) launch_path<true>(s, w, st, W_PRIMARY, dv, seed, pix0, npaths, w.pass_ev[1]);
-                else launch_path<false>(s, w, st, W_PRIMARY, dv, seed, pix0, npaths, w.pass_ev[1]);
-                HIPCHK(hipGetLastError());  // a refused launch is reported where it happens, not at the end of the batch
-                launches++;
-                const bool slow_on = slow_queue(s, w).cap != 0u;
-                if (slow_on) {  // zero-component primary rays (and bounce rays of the primary hits): beside the bounce kernel
-                    (void)hipEventRecord(w.sev[0], st);
-                    if (counting) launch_path<true>(s, w, st, W_SLOW, dv, seed, pix0, npaths, nullptr, 0);
-                    else launch_path<false>(s, w, st, W_SLOW, dv, seed, pix0, npaths, nullptr, 0);
-                    HIPCHK(hipGetLastError());
-                    HIPCHK(hipEventRecord(w.sdone, w.sstream));
-                }
-                if (maxdepth > 1) {
-                    HIPCHK(hipEventRecord(w.pass_ev[2], st));
-                    if (counting) launch_path<true>(s, w, st, W_BOUNCE, dv, seed, pix0, npaths, w.pass_ev[3]);
-                    else launch_path<false>(s, w, st, W_BOUNCE, dv, seed, pix0, npaths, w.pass_ev[3]);
-                    HIPCHK(hipGetLastError());
-                    launches++;
-                }
-                if (slow_on) HIPCHK(hipStreamWaitEvent(st, w.sdone, 0));
+                pass0 = 1;
             } else {
-            hipLaunchKernelGGL(k_gen, dim3(ew_blocks), dim3(256), 0, st, dv, seed, pix0, npaths, w.qo[0].p, w.qd[0].p, w.qpath[0].p, w.ctrl.p);
+                hipLaunchKernelGGL(k_gen, dim3(ew_blocks), dim3(256), 0, st, dv, seed, pix0, npaths, w.qo[0].p, w.qd[0].p, w.qpath[0].p, w.ctrl.p);
+            }
             HIPCHK(hipGetLastError());  // a refused launch is reported where it happens, not at the end of the batch
-            for (uint32_t pass = 0; pass < maxdepth; pass++) {
+            for (uint32_t pass = pass0; pass < maxdepth; pass++) {
                 const int a = pass & 1, b = a ^ 1;
                 HIPCHK(hipEventRecord(w.pass_ev[2 * pass], st));
                 if (counting) launch_trace<true>(s, w, st, w.qo[a].p, w.qd[a].p, (int)pass, w.pass_ev[2 * pass + 1]);
                 else launch_trace<false>(s, w, st, w.qo[a].p, w.qd[a].p, (int)pass, w.pass_ev[2 * pass + 1]);
                 HIPCHK(hipGetLastError());
-                if (counting && verbose) {
+                if (counting && verbose && !path_kernels) {
                     DCtrl hc2;
                     HIPCHK(hipMemcpyAsync(&hc2, w.ctrl.p, sizeof(DCtrl), hipMemcpyDeviceToHost, st));
                     HIPCHK(hipStreamSynchronize(st));
@@ -1663,10 +1587,17 @@ int rtmi_render_tile_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t
                 }
                 hipLaunchKernelGGL(k_shade, dim3(ew_blocks), dim3(256), 0, st, s->d, dv, seed, pix0, npaths, (int)pass,
                                    w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p,
-                                   w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, SlowQ{nullptr, nullptr, nullptr, nullptr, 0u});
+                                   w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq);
                 HIPCHK(hipGetLastError());
+                if (pass + 1 < maxdepth) {  // the last pass's shading emits no rays
+                    slow_after(pass);
+                    HIPCHK(hipGetLastError());
+                }
                 launches++;
             }
+            if (sq.cap != 0u) {  // the sample colours of the slow paths must be there before k_accum
+                HIPCHK(hipEventRecord(w.sdone, w.sstream));
+                HIPCHK(hipStreamWaitEvent(st, w.sdone, 0));
             }
             hipLaunchKernelGGL(k_accum, dim3(ew_blocks), dim3(256), 0, st, np, spp, w.scol.p, (float*)out, pix0, W, nsub, t, make_fastdiv(W));
             HIPCHK(hipEventRecord(w.ev[1], st));
@@ -1681,12 +1612,11 @@ int rtmi_render_tile_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t
             if (rc != RTMI_OK) return rc;
             DCtrl hc;
             if (verbose) HIPCHK(hipMemcpy(&hc, w.ctrl.p, sizeof(DCtrl), hipMemcpyDeviceToHost));
-            const uint32_t ntimed = (fused && !hybrid_req) ? (maxdepth > 1 ? 2u : 1u) : maxdepth;  // fused: primary kernel, bounce kernel
-            for (uint32_t pass = 0; pass < ntimed; pass++) {
+            for (uint32_t pass = 0; pass < maxdepth; pass++) {
                 float pm = 0.f;
                 HIPCHK(hipEventElapsedTime(&pm, w.pass_ev[2 * pass], w.pass_ev[2 * pass + 1]));
                 trace_ms += pm;
-                if (fused) { if (pass == 0) primary_ms += pm; else bounce_ms += pm; }
+                if (path_kernels) { if (pass == 0) primary_ms += pm; else bounce_ms += pm; }
                 if (verbose) fprintf(stderr, "[rtmi] stream %u batch@%llu pass %u: %u rays, trace %.3f ms, %.1f Mrays/s\n", t, (unsigned long long)p0, pass, hc.count[pass], pm, hc.count[pass] / (pm * 1e3));
             }
             if (stats) {
@@ -1707,7 +1637,7 @@ int rtmi_render_tile_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t
     HIPCHK(hipEventElapsedTime(&kernel_ms, s->fork_ev, s->end_ev));
     if (stats) {
         stats->kernel_ms = kernel_ms; stats->trace_ms = trace_ms; stats->trace_launches = launches; stats->streams = nsub;
-        stats->primary_ms = primary_ms; stats->bounce_ms = bounce_ms; stats->pipeline = fused ? (hybrid_req ? 3u : 2u) : 1u;
+        stats->primary_ms = primary_ms; stats->bounce_ms = bounce_ms; stats->pipeline = path_kernels ? 3u : 1u;
     }
     return RTMI_OK;
     RTMI_GUARD_END
@@ -1919,7 +1849,7 @@ int rtmi_trace(rtmi_scene_t* s, uint64_t n, const float* orig4, const float* dir
     RTMI_GUARD_BEGIN
     HIPCHK(hipSetDevice(s->device));
     Work& w = s->w[0];
-    int rc = ensure_workspace(w, (size_t)n, 1, false);
+    int rc = ensure_workspace(w, (size_t)n, 1);
     if (rc != RTMI_OK) return rc;
     hipStream_t st = s->istream[0];
     HIPCHK(hipMemcpyAsync(w.qo[0].p, orig4, n * 16, hipMemcpyHostToDevice, st));

@@ -1,8 +1,8 @@
 // shade.hpp — primary-ray generation and shading of one traced ray: Viewport::pixel_ray (raytrace_lib/src/raytrace.rs:
 // 1374-1394), color_ray + the tail of project_ray (raytrace.rs:1199-1295), lambertian_ray / reflect_ray / random_vec /
 // mix_color (raytrace.rs:278-301, :188-192) as device functions, shared by the per-pass kernels of rtmi_device.hip
-// (k_gen, k_shade) and by the fused path kernels of trace_oct.hpp (k_path_primary, k_path_bounce), so that both
-// pipelines execute the same arithmetic.  4-lane V4 values in the reference's operation order (vec4.hpp).
+// (k_gen, k_shade) and by the path kernels of trace_oct.hpp (k_path_primary, k_path_slow), so that every kernel that
+// shades a ray executes the same arithmetic.  4-lane V4 values in the reference's operation order (vec4.hpp).
 // Included by rtmi_device.hip.
 #pragma once
 

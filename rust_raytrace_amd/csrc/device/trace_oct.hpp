@@ -60,34 +60,30 @@ namespace rtmi {
 enum : uint32_t { M_IDLE = 0, M_SELECT = 1, M_LEAF = 2, M_SHADE = 3 };
 
 // What a lane does when its ray's root frame is finished -- the three kernels share one walk (oct_walk):
-//   W_TRACE    k_trace_oct     rays come from a queue, the closest hit goes to hit_tf / hit_t (one launch per bounce pass
-//                              of the per-pass pipeline; rtmi_trace)
+//   W_TRACE    k_trace_oct     rays come from a queue, the closest hit goes to hit_tf / hit_t (one launch per bounce pass,
+//                              shaded by k_shade; rtmi_trace)
 //   W_PRIMARY  k_path_primary  pixel_ray() is evaluated by the lane that takes the path (no ray queue for primary rays),
 //                              the finished ray is shaded IN the kernel (color_ray, shade.hpp): terminal paths write their
 //                              sample colour, bounce rays are compacted into the bounce queue (ballot + prefix sum, one
 //                              atomic per wave).  Whole-wave refills keep the samples of a pixel in lockstep.
-//   W_BOUNCE   k_path_bounce   ONE persistent launch for every bounce of every path: a lane pulls a bounce ray, traces
-//                              it, shades it in place and -- when the path goes on -- re-seeds ITSELF with the next bounce
-//                              ray; when the path ends it folds the surface stack into the sample colour and pulls the
-//                              next queued ray.  The recursion project_ray -> color_ray -> project_ray
-//                              (raytrace.rs:1233-1251, :1256-1295) without pass boundaries: no per-pass queues, no
-//                              per-pass tails of the persistent waves, no hit records in memory.
-// Shading is a third step kind ("exchange"): finished lanes wait in M_SHADE until `refill_min` lanes are finished or idle
-// (or nothing else is left to do), then they are shaded together and, in the same step, every lane without a ray takes
-// one from the queue.  The arithmetic per path is the per-pass pipeline's (same device functions), so the image is
+//   W_SLOW     k_path_slow     the slow-path queue (SlowQ, rtmi_device.hip: rays with an exactly-zero direction component,
+//                              ~150 x the work of an ordinary ray), one path per WAVE at a time (lane 0): the lane traces
+//                              the path's ray, shades it in place and -- when the path goes on -- re-seeds ITSELF with the
+//                              next bounce ray, until the path ends (the recursion project_ray -> color_ray -> project_ray,
+//                              raytrace.rs:1233-1251, :1256-1295, without pass boundaries).  Such a ray runs at the speed
+//                              of a lone lane while the ordinary passes go on beside it on their own stream.
+// Shading in the path kernels is a third step kind ("exchange"): finished lanes wait in M_SHADE until `refill_min` lanes
+// are finished or idle (or nothing else is left to do), then they are shaded together and, in the same step, every lane
+// without a ray takes one from the queue.  The arithmetic per path is k_shade's (same device functions), so the image is
 // bit-identical; only which lane evaluates it, and when, differs.
-//   W_SLOW     k_path_slow     W_BOUNCE for the slow-path queue (SlowQ, rtmi_device.hip: rays with an exactly-zero direction
-//                              component, ~150 x the work of an ordinary ray): one path per WAVE at a time (lane 0), traced
-//                              and shaded to its end, so that such a ray runs at the speed of a lone lane while the ordinary
-//                              passes go on beside it on their own stream.
-enum : int { W_TRACE = 0, W_PRIMARY = 1, W_BOUNCE = 2, W_SLOW = 3 };
+enum : int { W_TRACE = 0, W_PRIMARY = 1, W_SLOW = 2 };
 
 struct OctArgs {
     // W_TRACE
     const float4* qo; const float4* qd; uint32_t* hit_tf; float* hit_t; int pass;
-    // W_PRIMARY / W_BOUNCE
+    // W_PRIMARY / W_SLOW
     DView v; uint64_t seed; uint32_t pix0, npaths;
-    float4* bqo; float4* bqd; uint32_t* bqpath;  // bounce queue: filled by W_PRIMARY (ctrl->count[1] entries), drained by W_BOUNCE
+    float4* bqo; float4* bqd; uint32_t* bqpath;  // bounce queue: filled by W_PRIMARY (ctrl->count[1] entries), drained by pass 1's k_trace_oct
     uint16_t* mstack; float4* scol;
     SlowQ slow;       // W_PRIMARY: where zero-component rays go (cap == 0: nowhere, they are traced in place); W_SLOW: the queue
     uint32_t slow_k;  // W_SLOW: which consumer launch this is (its range and cursor in the control block)
@@ -189,17 +185,17 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     const int lane = threadIdx.x;  // one wave per block
     constexpr int NT = 64;
     // which queue of the control block this launch drains: W_TRACE pass `pass`, W_PRIMARY the implicit queue of all paths
-    // of the batch (slot 0), W_BOUNCE the bounce queue (slot 1)
-    const int pass = MODE == W_TRACE ? a.pass : (MODE == W_PRIMARY ? 0 : 1);
+    // of the batch (slot 0); W_SLOW does not use it (its launch drains a range of the slow-path queue)
+    const int pass = MODE == W_TRACE ? a.pass : 0;
     const uint32_t count = MODE == W_PRIMARY ? a.npaths : (MODE == W_SLOW ? ctrl->shi[a.slow_k] : ctrl->count[pass]);
     // "Rays": every queued ray of this launch (the slow path counts its rays one by one, below)
     if (MODE != W_SLOW && blockIdx.x == 0 && lane == 0) atomicAdd(&ctrl->rays, (unsigned long long)count);
-    const float4* __restrict__ qo = MODE == W_BOUNCE ? a.bqo : (MODE == W_SLOW ? a.slow.o : a.qo);
-    const float4* __restrict__ qd = MODE == W_BOUNCE ? a.bqd : (MODE == W_SLOW ? a.slow.d : a.qd);
+    const float4* __restrict__ qo = MODE == W_SLOW ? a.slow.o : a.qo;
+    const float4* __restrict__ qd = MODE == W_SLOW ? a.slow.d : a.qd;
     if (MODE == W_SLOW) refill_min = 1;
-    uint32_t path = 0;    // W_PRIMARY / W_BOUNCE: the path this lane works for (slot of its sample colour)
+    uint32_t path = 0;    // W_PRIMARY / W_SLOW: the path this lane works for (slot of its sample colour)
     uint32_t bounce = 0;  // bounces the path has behind it = the reference's maxdepth - depth of the ray being traced
-    uint32_t ncont = 0;   // W_BOUNCE: rays this lane cast beyond the queued ones (the "Rays" statistic)
+    uint32_t ncont = 0;   // W_SLOW: rays this lane cast that no queue counted (the "Rays" statistic)
     unsigned long long cnt[5] = {0, 0, 0, 0, 0};
     // COUNT only: S steps, S lanes, L steps, L lanes, refills, refill lanes, edge steps, edge lanes, then shader-clock
     // cycles (s_memtime) this wave spent in SELECT steps, LEAF steps, refills, and in total
@@ -267,7 +263,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
             float4 no = make_float4(0.f, 0.f, 0.f, 0.f), nd = make_float4(0.f, 0.f, 1.f, 0.f);
             uint32_t npath = path, nbounce = bounce;
             if (MODE != W_TRACE) {
-                bool push = false;  // W_PRIMARY: the path goes on -> its bounce ray is queued for k_path_bounce
+                bool push = false;  // W_PRIMARY: the path goes on -> its bounce ray is queued for pass 1
                 RayV nr;
                 if (mode == M_SHADE) {
                     uint32_t prow, pcol, sample;
@@ -277,7 +273,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                                                 a.mstack, a.scol, nr);
                     mode = M_IDLE;
                     if (cont) {
-                        if (MODE == W_BOUNCE || MODE == W_SLOW) {
+                        if (MODE == W_SLOW) {
                             no = make_float4(nr.orig.x, nr.orig.y, nr.orig.z, nr.orig.w);
                             nd = make_float4(nr.dir.x, nr.dir.y, nr.dir.z, nr.dir.w);
                             nbounce = bounce + 1u;
@@ -352,10 +348,6 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                             // an exactly-zero direction component: ~150 x the work of an ordinary ray and the other 63
                             // samples of the pixel would wait for it -> its path is traced by k_path_slow
                             if (a.slow.cap && has_zero_component(nd.x, nd.y, nd.z) && slow_push(a.slow, ctrl, no, nd, i, 0u)) start = false;
-                        } else if (MODE == W_BOUNCE) {
-                            no = qo[i]; nd = qd[i];
-                            npath = a.bqpath[i]; nbounce = 1u;
-                            start = true;
                         } else {
                             ridx = i;
                             r = make_rayk(qo[i], qd[i]);
@@ -708,7 +700,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
             if (stepS) dbg[8] += dt; else dbg[9] += dt;
         }
     }
-    if (MODE == W_BOUNCE || MODE == W_SLOW) {  // "Rays": the queued bounce rays were counted above, the ones cast in place here
+    if (MODE == W_SLOW) {  // "Rays": the rays this launch cast that no queue counted
         unsigned long long wsum = 0;
         for (unsigned long long m = __ballot(ncont != 0u); m; m &= m - 1ull)
             wsum += (uint32_t)__builtin_amdgcn_readlane((int)ncont, __ffsll((long long)m) - 1);
@@ -743,11 +735,6 @@ template <bool COUNT, bool FAST>
 __global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_primary(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min, int xcd_aware) {
     extern __shared__ uint32_t lds[];
     oct_walk<COUNT, FAST, W_PRIMARY>(sc, a, ctrl, lds, refill_min, xcd_aware);
-}
-template <bool COUNT, bool FAST>
-__global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_bounce(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min, int xcd_aware) {
-    extern __shared__ uint32_t lds[];
-    oct_walk<COUNT, FAST, W_BOUNCE>(sc, a, ctrl, lds, refill_min, xcd_aware);
 }
 template <bool COUNT, bool FAST>
 __global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_slow(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min, int xcd_aware) {

@@ -276,6 +276,13 @@ def test_error_behaviour(canonical_pair):
     empty = R.Scene()
     with pytest.raises(RuntimeError):
         R.HipRayCaster().walk_rays(vp, empty, np.zeros((16, 16, 4), np.float32), 1, False)  # no bounding box
+    # the removed ray-pool kernel and fused bounce pipeline are refused, not replaced by another kernel
+    for tun in ({"kernel": 2}, {"pipeline": 2}):
+        with pytest.raises(RuntimeError):
+            R.HipRayCaster(tuning=tun).walk_rays(vp, sp, np.zeros((16, 16, 4), np.float32), 1, False)
+    img = np.zeros((16, 16, 4), np.float32)
+    R.HipRayCaster(seed=1).walk_rays(R.canonical_viewport(16, 16, 5, 4), sp, img, 1, False)
+    assert_bits_equal(so.render(16, 16, _orc().canonical_viewport(16, 16), 5, 4, seed=1, threads=8)[0], img, "default tuning after a refused one")
 
 
 def test_striped_tiles_equal_whole_image(canonical_pair):
@@ -772,11 +779,10 @@ def test_octree_build_on_gpu_equals_oracle_build(which, canonical_pair, grid_pai
     assert ctx.total_rays == cn["rays"]
 
 
-def test_fused_and_per_pass_pipelines_same_image(canonical_pair, circles_pair):
-    """The default pipeline renders an octree scene with the fused path kernels (k_path_primary: pixel_ray + closest hit +
-    color_ray of the primary rays; k_path_bounce: every bounce of every path in one persistent launch, shaded in place);
-    tuning pipeline=1 runs the same frame with one launch per bounce pass (k_gen, k_trace_oct + k_shade per pass), pipeline=3
-    (the default) k_path_primary and then the bounce passes one launch each.  Same
+def test_path_kernel_and_per_pass_pipelines_same_image(canonical_pair, circles_pair):
+    """The default pipeline (3) renders an octree scene with the fused path kernel k_path_primary (pixel_ray + closest hit +
+    color_ray of the primary rays) and then one k_trace_oct + k_shade launch per bounce pass; tuning pipeline=1 runs the
+    same frame with one launch per pass (k_gen, k_trace_oct + k_shade per pass).  Same
     device functions, so: image bits, "Rays" and all work counters equal each other AND the oracle -- odd sizes, sample
     counts that are not powers of two (the path -> (pixel, sample) mapping divides by them), depth limits 1..7, batches
     smaller than a wave, refill thresholds 1..64, striped tiles."""
@@ -788,7 +794,7 @@ def test_fused_and_per_pass_pipelines_same_image(canonical_pair, circles_pair):
         vo, vp = _viewports(w, h, depth, spp)
         ref, cn = so.render(w, h, vo, depth, spp, seed=seed, threads=8)
         imgs = {}
-        for pipe in (1, 2, 3):
+        for pipe in (1, 3):
             img = np.zeros((h, w, 4), np.float32)
             ctx = R.HipRayCaster(seed=seed, options=R.OPT_COUNTERS, tuning={"pipeline": pipe}).walk_rays(vp, sp, img, 1, False)
             assert ctx.stats["pipeline"] == pipe
@@ -796,9 +802,9 @@ def test_fused_and_per_pass_pipelines_same_image(canonical_pair, circles_pair):
             for k in ("rays", "box_tests", "tri_tests", "full_tests", "nodes", "leaves"):
                 assert ctx.stats[k] == cn[k], (pipe, k)
             imgs[pipe] = img
-            assert ctx.stats["trace_launches"] == (min(depth, 2) if pipe == 2 else depth) * ctx.stats["streams"]
+            assert ctx.stats["trace_launches"] == depth * ctx.stats["streams"]
         # uncounted kernels (the ones that are timed)
-        for pipe in (1, 2, 3):
+        for pipe in (1, 3):
             img = np.zeros((h, w, 4), np.float32)
             ctx = R.HipRayCaster(seed=seed, tuning={"pipeline": pipe}).walk_rays(vp, sp, img, 1, False)
             assert_bits_equal(ref, img, f"uncounted pipeline {pipe}")
@@ -812,21 +818,20 @@ def test_fused_and_per_pass_pipelines_same_image(canonical_pair, circles_pair):
                 {"refill_min": 23, "refill_min0": 17, "streams": 4, "subtile_min_paths": 1}, {"oct_waves_per_cu": 1}, {"xcd_aware": 1},
                 {"xcd_aware": 2, "streams": 1}):
         img = np.zeros((h, w, 4), np.float32)
-        for pipe in (2, 3):
-            ctx = R.HipRayCaster(seed=21, tuning=dict(tun, pipeline=pipe)).walk_rays(vp, sp, img, 1, False)
-            assert_bits_equal(ref, img, f"pipeline {pipe}, tuning {tun}")
-            assert ctx.total_rays == cn["rays"], (pipe, tun)
-    # a striped tile (one rank of three) through the fused kernels equals those rows of the frame
+        ctx = R.HipRayCaster(seed=21, tuning=dict(tun, pipeline=3)).walk_rays(vp, sp, img, 1, False)
+        assert_bits_equal(ref, img, f"pipeline 3, tuning {tun}")
+        assert ctx.total_rays == cn["rays"], tun
+    # a striped tile (one rank of three) through the path kernels equals those rows of the frame
     import torch
     from rust_raytrace_amd import dist as rd
     tile = rd.rank_tile(1, 3, h, 4)
     buf = torch.zeros((tile[1], w, 4), dtype=torch.float32, device="cuda:0")
-    R.HipRayCaster(seed=21, tuning={"pipeline": 2}).walk_tile_device(vp, sp, tile, buf.data_ptr())
+    R.HipRayCaster(seed=21).walk_tile_device(vp, sp, tile, buf.data_ptr())
     torch.cuda.synchronize()
-    assert_bits_equal(ref[rd.tile_rows(tile, h)], buf.cpu().numpy(), "striped tile, fused")
+    assert_bits_equal(ref[rd.tile_rows(tile, h)], buf.cpu().numpy(), "striped tile, path kernels")
 
 
-def test_slow_path_for_zero_direction_components(canonical_pair):
+def test_slow_path_for_zero_direction_components_pipelines_1_3(canonical_pair):
     """A ray whose unit direction has an exactly-zero component skips that axis' slab in BoundingBox::collides
     (raytrace.rs:872, :882, :892) and enters every box of the perpendicular plane -- ~150 x the work of an ordinary ray.
     The default pipeline sets such rays aside (SlowQ) and k_path_slow traces their paths beside the ordinary passes.
@@ -844,7 +849,7 @@ def test_slow_path_for_zero_direction_components(canonical_pair):
         o4, d4 = orc.primary_rays(w, h, vo, 1, seed=6)
         nzero = int(((d4[:, :3] == 0).any(axis=1)).sum())
         assert nzero == w * h  # the premise of this test
-        for tun, want_slow in (({"pipeline": 3}, True), ({"pipeline": 2}, True), ({"pipeline": 3, "slow_path_off": 1}, False),
+        for tun, want_slow in (({"pipeline": 3}, True), ({"pipeline": 3, "slow_path_off": 1}, False),
                                ({"pipeline": 1}, False), ({"pipeline": 3, "streams": 2, "subtile_min_paths": 1, "batch_paths": 7}, True)):
             img = np.zeros((h, w, 4), np.float32)
             ctx = R.HipRayCaster(seed=6, options=R.OPT_COUNTERS, tuning=tun).walk_rays(vp, sp, img, 1, False)
@@ -890,30 +895,6 @@ def test_progress_tuples_while_rendering(canonical_pair):
         assert [r for _, r, _, _ in seen] == sorted(r for _, r, _, _ in seen)
         assert sum(px for _, _, px, _ in seen) == w * h and sum(n for _, _, _, n in seen) == cn["rays"] == ctx.total_rays
         assert ctx.stats["rays"] == cn["rays"]
-
-
-def test_pool_kernel_is_bit_exact(canonical_pair):
-    """tuning kernel=2 selects k_trace_pool (per-wave ray pool in LDS, free ray-to-lane assignment each step); measured
-    slower than the default on MI355X and therefore opt-in, but it stays exact: image bits and all six work
-    counters against the oracle, plus edge-case rays."""
-    so, sp = canonical_pair
-    orc, R = _orc(), _R()
-    w, h, spp = 48, 40, 3
-    vo = orc.canonical_viewport(w, h)
-    vp = R.canonical_viewport(w, h, 5, spp)
-    ref, cn = so.render(w, h, vo, 5, spp, seed=5, threads=8)
-    img = np.zeros((h, w, 4), np.float32)
-    ctx = R.HipRayCaster(seed=5, options=R.OPT_COUNTERS, tuning={"kernel": 2}).walk_rays(vp, sp, img, 1, False)
-    assert_bits_equal(ref, img, "pool kernel image")
-    for k in ("rays", "box_tests", "tri_tests", "full_tests", "nodes", "leaves"):
-        assert ctx.stats[k] == cn[k], k
-    pair = build_pair(recipe_axis_box())
-    vo = orc.create_viewport(33, 33, (1.0, 1.0), [0.0, 0.0, 0.0], orc.unit([0.0, 0.0, 1.0]), 90.0, 0.0)
-    vp = R.create_viewport((33, 33), (1.0, 1.0), [0.0, 0.0, 0.0], R.unit([0.0, 0.0, 1.0]), 90.0, 0.0, 5, 1)
-    ref, _ = pair[0].render(33, 33, vo, 5, 1)
-    img = np.zeros((33, 33, 4), np.float32)
-    R.HipRayCaster(tuning={"kernel": 2}).walk_rays(vp, pair[1], img, 1, False)
-    assert_bits_equal(ref, img, "pool kernel, axis-aligned scene")
 
 
 def test_bvh_fast_mode_equals_linear_list_oracle(canonical_pair):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Development aid: config 3 frame (or one rank's tile of N), per-pass pipeline vs fused path kernels, per stream count:
+"""Development aid: config 3 frame (or one rank's tile of N), per-pass pipeline (1) vs path kernels (3), per stream count:
 device time of the frame, sum of the closest-hit launches, the primary / bounce kernels apart."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -7,7 +7,7 @@ sys.path.insert(0, ROOT)
 import torch
 from rust_raytrace_amd import raytrace as R, dist as rd
 world = int(sys.argv[1]) if len(sys.argv) > 1 else 1
-PIPES = [int(x) for x in os.environ.get("PIPES", "1,2").split(",")]
+PIPES = [int(x) for x in os.environ.get("PIPES", "1,3").split(",")]
 streams = [int(x) for x in sys.argv[2].split(",")] if len(sys.argv) > 2 else [1, 2, 3]
 extra = eval(sys.argv[3]) if len(sys.argv) > 3 else {}
 W = H = 2048
