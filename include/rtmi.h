@@ -88,7 +88,9 @@ typedef struct rtmi_stats {
     double band_copy_ms;    /* (quantise +) the band's one crossing to the root device, synchronised           */
     double deinterleave_ms; /* scenes[0] only: k_deinterleave (+ the copy to out_host)                         */
     /* pipeline 3 (rtmi_tuning_t.pipeline): trace_ms split into its two parts, summed over streams and batches        */
-    double primary_ms;      /* k_path_primary launches (pixel_ray + closest hit + color_ray of the primary rays)  */
+    double primary_ms;      /* k_path_primary launches (pixel_ray + closest hit + color_ray of the primary rays;
+                             * it also traces the mirror reflections of primary hits in place:
+                             * RTMI_MIRROR_INPLACE)                                            */
     double bounce_ms;       /* the bounce passes' closest-hit launches (k_trace_oct)                               */
     int32_t peer_access;    /* 1 = this device writes the root device's memory directly (peer access enabled, or the
                              * same device); 0 = the runtime refused: the band is staged (rtmi_last_error() carries a

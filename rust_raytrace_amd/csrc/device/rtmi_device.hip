@@ -803,6 +803,9 @@ struct rtmi_scene {
     bool verbose = false;
     int vote[4] = {3, 2, 3, 2};  // SELECT : LEAF vote weights of the walk, primary rays / bounce rays (experiments: RTMI_VOTE="a,b,c,d")
     int packet_cull = 1;         // k_path_primary culls leaf triangles per pixel packet (RTMI_PACKET_CULL=0: off, for comparison)
+    // k_path_primary traces the mirror reflections of its primary rays itself when a wave has at least this many
+    // (RTMI_MIRROR_INPLACE=n; 0: off, everything above 64: never)
+    int mirror_inplace = 32;
     unsigned long long vprev[RTMI_MAX_STREAMS][13] = {};  // verbose per-pass deltas (per handle: no shared statics)
 };
 
@@ -1024,9 +1027,9 @@ static void build_oct_form(const rtmi_box_t* boxes, uint64_t nboxes, const uint3
 }
 
 // LDS of an octree-walk launch: the counting build keeps 2 more memo words per lane (the list's plane and edge tests)
-// and every launch 64 B behind the memo for the packet of k_path_primary (trace_oct.hpp, Packet)
-static_assert(sizeof(Packet) <= 64, "packet slot in LDS");
-static size_t oct_launch_lds(const rtmi_scene* s, bool count) { return s->oct_lds + (count ? 2 * 4 * 64 : 0) + 64; }
+// and every launch room for the LDS header of k_path_primary (trace_oct.hpp, PrimHdr: its packet and pass-2 queue)
+static_assert(sizeof(PrimHdr) % 16 == 0 && sizeof(PrimHdr) <= 96, "header slot in LDS");
+static size_t oct_launch_lds(const rtmi_scene* s, bool count) { return s->oct_lds + (count ? 2 * 4 * 64 : 0) + 96; }
 
 extern "C" {
 
@@ -1126,6 +1129,11 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
     s->tune.slow_path_off = (uint32_t)std::min<size_t>(env_size("RTMI_SLOW_PATH_OFF", 0), 1);
     s->verbose = getenv("RTMI_VERBOSE") != nullptr;
     if (const char* v = getenv("RTMI_PACKET_CULL")) s->packet_cull = strcmp(v, "0") != 0;  // (env_size treats 0 as unset)
+    if (const char* v = getenv("RTMI_MIRROR_INPLACE")) {
+        char* end = nullptr;
+        const unsigned long n = strtoul(v, &end, 10);
+        if (*v && end && *end == '\0') s->mirror_inplace = (int)std::min<unsigned long>(n, 65);
+    }
     if (const char* v = getenv("RTMI_VOTE")) {
         int q[4];
         if (sscanf(v, "%d,%d,%d,%d", &q[0], &q[1], &q[2], &q[3]) == 4 && q[0] > 0 && q[1] > 0 && q[2] > 0 && q[3] > 0) memcpy(s->vote, q, sizeof q);
@@ -1371,6 +1379,7 @@ static OctArgs path_args(rtmi_scene* s, Work& w, const DView& dv, uint64_t seed,
     return a;
 }
 // k_path_primary: the batch's primary rays generated, traced and shaded; the bounce rays go to queue 1, which pass 1 traces.
+// The mirror reflections it traces itself go on in queue 2 (ping-pong buffer 0, free until pass 1's k_shade appends to it).
 // `stop` is recorded right after the kernel.
 template <bool COUNT>
 static void launch_primary(rtmi_scene* s, Work& w, hipStream_t st, const DView& dv, uint64_t seed, uint32_t pix0, uint32_t npaths,
@@ -1379,6 +1388,8 @@ static void launch_primary(rtmi_scene* s, Work& w, hipStream_t st, const DView& 
     a.bqo = w.qo[1].p; a.bqd = w.qd[1].p; a.bqpath = w.qpath[1].p;
     a.vote_s = s->vote[0]; a.vote_l = s->vote[1];
     a.pcull = s->packet_cull;
+    a.b2qo = w.qo[0].p; a.b2qd = w.qd[0].p; a.b2qpath = w.qpath[0].p;
+    a.minpl = s->mirror_inplace;
     const int refill = (int)s->tune.refill_min0, xcd = (int)(s->tune.xcd_aware % 3u);
     if (s->options & RTMI_OPT_FAST)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary<COUNT, true>), oct_grid(s), dim3(64), oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);

@@ -94,10 +94,10 @@ __device__ inline V4 mix_color(V4 c1, V4 c2, float a) { return vadd(vmul(c1, 1.f
 // the bounce ray (lambertian_ray / reflect_ray with the path's RNG block pass + 1).  Returns false when the path ends
 // here: sky, Solid, edge face (Solid black, raytrace.rs:452-457) or depth exhausted (black, raytrace.rs:1261-1263); the
 // nested mix_color calls (raytrace.rs:1233-1251) are then evaluated inside-out over the stack and the sample colour is
-// written to scol[path].
+// written to scol[path].  `mirror` (optional): set to true when the path goes on through a Reflective surface.
 __device__ inline bool shade_hit(const DScene& sc, uint32_t maxdepth, uint64_t seed, uint32_t npaths, uint32_t path, uint32_t pixel,
                                  uint32_t sample, uint32_t pass, uint32_t tf, float t, V4 ro, V4 rd, uint16_t* __restrict__ mstack,
-                                 float4* __restrict__ scol, RayV& nr) {
+                                 float4* __restrict__ scol, RayV& nr, bool* mirror = nullptr) {
     const uint32_t tri = tf & 0x3FFFFFFFu, face = tf >> 30;
     V4 c;
     uint32_t npushed = pass;
@@ -138,6 +138,7 @@ __device__ inline bool shade_hit(const DScene& sc, uint32_t maxdepth, uint64_t s
                     const V4 rvf = vmul(rv, m1.x);
                     const V4 reflect_dir = vunit(vadd(reflect, rvf));
                     nr = make_ray(vadd(point, vmul(reflect_dir, 0.001f)), vunit(vadd(reflect, rvf)));
+                    if (mirror) *mirror = true;
                 }
                 return true;
             }

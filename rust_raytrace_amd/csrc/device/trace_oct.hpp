@@ -65,7 +65,9 @@ enum : uint32_t { M_IDLE = 0, M_SELECT = 1, M_LEAF = 2, M_SHADE = 3 };
 //   W_PRIMARY  k_path_primary  pixel_ray() is evaluated by the lane that takes the path (no ray queue for primary rays),
 //                              the finished ray is shaded IN the kernel (color_ray, shade.hpp): terminal paths write their
 //                              sample colour, bounce rays are compacted into the bounce queue (ballot + prefix sum, one
-//                              atomic per wave).  Whole-wave refills keep the samples of a pixel in lockstep.
+//                              atomic per wave).  Whole-wave refills keep the samples of a pixel in lockstep.  A wave whose
+//                              primary rays hit a mirror (at least a.minpl lanes) traces their reflections ITSELF, as the same
+//                              packet, and queues what follows them for pass 2 ("Mirror paths in place").
 //   W_SLOW     k_path_slow     the slow-path queue (SlowQ, rtmi_device.hip: rays with an exactly-zero direction component,
 //                              ~150 x the work of an ordinary ray), one path per WAVE at a time (lane 0): the lane traces
 //                              the path's ray, shades it in place and -- when the path goes on -- re-seeds ITSELF with the
@@ -89,6 +91,11 @@ struct OctArgs {
     uint32_t slow_k;  // W_SLOW: which consumer launch this is (its range and cursor in the control block)
     int vote_s, vote_l;  // weights of the SELECT / LEAF vote (3 : 2)
     int pcull;           // W_PRIMARY: packet cull on (RTMI_PACKET_CULL, read at scene creation)
+    // W_PRIMARY, mirror paths continued in place (RTMI_MIRROR_INPLACE): the pass-2 queue (ping-pong buffer 0, ctrl->count[2]
+    // entries; pass 1's k_shade appends to it behind them) and the least number of a wave's mirror lanes for which the wave
+    // traces their reflections itself (0: never)
+    float4* b2qo; float4* b2qd; uint32_t* b2qpath;
+    int minpl;
 };
 
 // Frame of an inner box: node = index of its record; w = visited octants (bits 0-7) | O_DONE | O_HAS;
@@ -136,6 +143,16 @@ struct Packet {
     float eabs;                    // K (2 so + |o0|) (1 + K) + 1e-18: the ray-only absolute terms of the bound on |q - c|
     float dhi, dinv;               // |d0| (1 + K); 1 / min_i |d_i|, rounded up
     float pad;
+};
+// W_PRIMARY's LDS header, in front of the frame stack (a constant address): the packet of the last whole-wave refill, and
+// what only the exchange step reads -- the pass-2 queue and the in-place threshold of OctArgs (b2qo, b2qd, b2qpath, minpl).
+// Kept out of registers: as kernel arguments they are 7 more SGPRs live over the whole loop, and the SGPR spills then take a
+// second VGPR, which hipcc wins back by spilling VGPRs inside the LEAF step.
+struct PrimHdr {
+    Packet pk;
+    unsigned long long q2[3];  // pass-2 queue: origins, directions, paths
+    uint32_t minpl;            // least number of mirror lanes that a wave continues in place (65: never)
+    uint32_t pad;
 };
 #define PK_K 1e-5f  // relative slack: ~170 x the float rounding of any bound below
 // One ray of the packet: its spreads against the reference.  False: this ray turns culling off for the packet (nonzero
@@ -193,8 +210,10 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     const float4* __restrict__ qo = MODE == W_SLOW ? a.slow.o : a.qo;
     const float4* __restrict__ qd = MODE == W_SLOW ? a.slow.d : a.qd;
     if (MODE == W_SLOW) refill_min = 1;
-    uint32_t path = 0;    // W_PRIMARY / W_SLOW: the path this lane works for (slot of its sample colour)
-    uint32_t bounce = 0;  // bounces the path has behind it = the reference's maxdepth - depth of the ray being traced
+    // W_PRIMARY / W_SLOW: the path this lane works for (slot of its sample colour); W_PRIMARY keeps the bounce (0, or 1 for
+    // a mirror reflection traced in place) in bit 31 -- a batch has < 2^31 paths -- instead of in one more loop-carried register
+    uint32_t path = 0;
+    uint32_t bounce = 0;  // W_SLOW: bounces the path has behind it = the reference's maxdepth - depth of the ray being traced
     uint32_t ncont = 0;   // W_SLOW: rays this lane cast that no queue counted (the "Rays" statistic)
     unsigned long long cnt[5] = {0, 0, 0, 0, 0};
     // COUNT only: S steps, S lanes, L steps, L lanes, refills, refill lanes, edge steps, edge lanes, then shader-clock
@@ -202,6 +221,8 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     // dbg[12..15]: leaf visits, leaf-memo hits, plane tests and edge tests the memo hits skipped
     // dbg[16..20] (W_PRIMARY): LEAF steps of the packet cull, all LEAF steps, references of those steps, references the
     // predicate culls, violations (a culled reference whose exact test passed: must stay 0)
+    // dbg[21..23] (W_PRIMARY): primary rays whose path goes on through a Reflective hit (and not to the slow path), those
+    // of them traced in place, exchange steps with >= 32 such lanes (low 32 bits) | with 64 such lanes (high 32 bits)
     unsigned long long dbg[RTMI_NDBG] = {};
     const unsigned long long t_begin = COUNT ? __builtin_amdgcn_s_memtime() : 0ull;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
@@ -234,9 +255,16 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     // new ray.  Not in the slow path (its wide LEAF step keeps the ray's state in lane 0).
     constexpr bool MEMO = MODE != W_SLOW;
     // W_PRIMARY: the packet of the last whole-wave refill (below) is wave-uniform and kept out of registers: it sits in the
-    // first 64 B of LDS (a constant address), the frame stack and the memo behind it
-    Packet* const pkl = reinterpret_cast<Packet*>(lds);
-    if (MODE == W_PRIMARY) lds += 16;
+    // LDS header (PrimHdr, a constant address), the frame stack and the memo behind it
+    PrimHdr* const hdr = reinterpret_cast<PrimHdr*>(lds);
+    Packet* const pkl = &hdr->pk;
+    if (MODE == W_PRIMARY) {
+        if (lane == 0) {
+            hdr->q2[0] = (unsigned long long)a.b2qo; hdr->q2[1] = (unsigned long long)a.b2qd; hdr->q2[2] = (unsigned long long)a.b2qpath;
+            hdr->minpl = a.minpl ? (uint32_t)a.minpl : 65u;
+        }
+        lds += sizeof(PrimHdr) / 4;
+    }
     uint32_t* const memo = lds + sc.levels * 2 * NT + lane;
     // wave-uniform: PK_NEW = the lanes took new rays, the next LEAF step records their packet; PK_ON = LEAF steps may cull
     // against *pkl
@@ -260,17 +288,20 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
             // ---- exchange step: finished rays are shaded, lanes without a ray take consecutive queued rays
             const unsigned long long t_r0 = COUNT ? __builtin_amdgcn_s_memtime() : 0ull;
             bool start = false;     // this lane begins a new ray below
+            bool inplace = false;   // W_PRIMARY (wave-uniform): this wave continues its mirror paths, no refill
             float4 no = make_float4(0.f, 0.f, 0.f, 0.f), nd = make_float4(0.f, 0.f, 1.f, 0.f);
-            uint32_t npath = path, nbounce = bounce;
+            const uint32_t pth = MODE == W_PRIMARY ? path & 0x7FFFFFFFu : path, bnc = MODE == W_PRIMARY ? path >> 31 : bounce;
+            uint32_t npath = pth, nbounce = bnc;
             if (MODE != W_TRACE) {
-                bool push = false;  // W_PRIMARY: the path goes on -> its bounce ray is queued for pass 1
+                bool push = false;  // W_PRIMARY: the path goes on -> its bounce ray is queued for pass bounce + 1
+                bool mirror = false;  // ... through a Reflective surface
                 RayV nr;
                 if (mode == M_SHADE) {
                     uint32_t prow, pcol, sample;
-                    path_pixel(a.v, a.pix0, path, prow, pcol, sample);
-                    const bool cont = shade_hit(sc, a.v.maxdepth, a.seed, a.npaths, path, prow * a.v.width + pcol, sample, bounce,
+                    path_pixel(a.v, a.pix0, pth, prow, pcol, sample);
+                    const bool cont = shade_hit(sc, a.v.maxdepth, a.seed, a.npaths, pth, prow * a.v.width + pcol, sample, bnc,
                                                 ghave ? gtf : 0u, gt, V4{r.ox, r.oy, r.oz, r.ow}, V4{r.dx, r.dy, r.dz, r.dw},
-                                                a.mstack, a.scol, nr);
+                                                a.mstack, a.scol, nr, &mirror);
                     mode = M_IDLE;
                     if (cont) {
                         if (MODE == W_SLOW) {
@@ -286,20 +317,57 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                 if (MODE == W_PRIMARY) {
                     if (push && a.slow.cap && has_zero_component(nr.dir.x, nr.dir.y, nr.dir.z) &&
                         slow_push(a.slow, ctrl, make_float4(nr.orig.x, nr.orig.y, nr.orig.z, nr.orig.w),
-                                  make_float4(nr.dir.x, nr.dir.y, nr.dir.z, nr.dir.w), path, 1u))
+                                  make_float4(nr.dir.x, nr.dir.y, nr.dir.z, nr.dir.w), pth, bnc + 1u))
                         push = false;  // its path goes on in k_path_slow
-                    const unsigned long long mask = __ballot(push);
-                    if (mask) {
-                        uint32_t qb = 0;
-                        if (lane == 0) qb = atomicAdd(&ctrl->count[1], (uint32_t)__popcll(mask));
-                        qb = __builtin_amdgcn_readfirstlane(qb);
-                        if (push) {
-                            const uint32_t slot = qb + (uint32_t)__popcll(mask & lt_mask);
-                            store_stream(&a.bqo[slot], make_float4(nr.orig.x, nr.orig.y, nr.orig.z, nr.orig.w));
-                            store_stream(&a.bqd[slot], make_float4(nr.dir.x, nr.dir.y, nr.dir.z, nr.dir.w));
-                            store_stream(&a.bqpath[slot], path);
+                    // Mirror paths in place: the reflections of a pixel's primary rays off a mirror are as coherent as the
+                    // primary rays themselves.  When at least a.minpl lanes have one, this wave traces them as bounce 1 (the
+                    // packet of the next LEAF step is theirs) and takes no new primary rays until they are done; the other
+                    // bounce rays go to queue 1 as always.  A reflection traced here is never continued here again: what
+                    // follows it goes to queue 2, which nothing reads before pass 2 (queue 3 shares the buffer of queue 1,
+                    // which pass 1 has still to read).
+                    const volatile PrimHdr* const vh = hdr;  // (volatile: read here, not kept in registers since the kernel's start)
+                    auto hword = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+                    auto hptr = [&](int k) {
+                        const unsigned long long v = vh->q2[k];
+                        return (unsigned long long)hword((uint32_t)v) | ((unsigned long long)hword((uint32_t)(v >> 32)) << 32);
+                    };
+                    const unsigned long long mm = __ballot(push && mirror && bnc == 0u);
+                    const uint32_t nm = (uint32_t)__popcll(mm);
+                    inplace = nm != 0u && nm >= hword(vh->minpl);
+                    if (COUNT && lane == 0) {
+                        dbg[21] += nm;
+                        dbg[22] += inplace ? nm : 0u;
+                        dbg[23] += (nm >= 32u ? 1ull : 0ull) | (nm == 64u ? 1ull << 32 : 0ull);
+                    }
+                    if (inplace) {
+                        if (lane == 0) atomicAdd(&ctrl->rays, (unsigned long long)nm);  // "Rays": no queue counts them
+                        if ((mm >> lane) & 1ull) {
+                            no = make_float4(nr.orig.x, nr.orig.y, nr.orig.z, nr.orig.w);
+                            nd = make_float4(nr.dir.x, nr.dir.y, nr.dir.z, nr.dir.w);
+                            nbounce = 1u;
+                            start = true;
+                            push = false;
                         }
                     }
+                    // compaction into the queue of pass bounce + 1: ballot + prefix sum, one atomic per wave and queue
+                    auto enqueue = [&](bool p, uint32_t* qcount, float4* bo, float4* bd, uint32_t* bp) {
+                        const unsigned long long mask = __ballot(p);
+                        if (mask) {
+                            uint32_t qb = 0;
+                            if (lane == 0) qb = atomicAdd(qcount, (uint32_t)__popcll(mask));
+                            qb = __builtin_amdgcn_readfirstlane(qb);
+                            if (p) {
+                                const uint32_t slot = qb + (uint32_t)__popcll(mask & lt_mask);
+                                store_stream(&bo[slot], make_float4(nr.orig.x, nr.orig.y, nr.orig.z, nr.orig.w));
+                                store_stream(&bd[slot], make_float4(nr.dir.x, nr.dir.y, nr.dir.z, nr.dir.w));
+                                store_stream(&bp[slot], pth);
+                            }
+                        }
+                    };
+                    enqueue(push && bnc == 0u, &ctrl->count[1], a.bqo, a.bqd, a.bqpath);
+                    if (__ballot(push && bnc != 0u))
+                        enqueue(push && bnc != 0u, &ctrl->count[2], reinterpret_cast<float4*>(hptr(0)), reinterpret_cast<float4*>(hptr(1)),
+                                reinterpret_cast<uint32_t*>(hptr(2)));
                 }
             }
             const unsigned long long m_want = MODE == W_TRACE ? m_idle : (MODE == W_SLOW ? (__ballot(mode == M_IDLE) & 1ull) : __ballot(mode == M_IDLE));
@@ -317,7 +385,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                     }
                 }
             } else
-            if (!exhausted && m_want != 0ull) {
+            if (!exhausted && m_want != 0ull && !inplace) {
                 const uint32_t n = (uint32_t)__popcll(m_want);
                 if (COUNT && lane == 0) { dbg[4]++; dbg[5] += n; }
                 // XCD-aware work fetch: the queue is cut into 8 contiguous ranges, one per XCD (each XCD has its own
@@ -371,7 +439,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
             if (MODE == W_PRIMARY) pk = a.pcull ? PK_NEW : PK_OFF;  // every refill of k_path_primary is whole-wave
             if (MODE != W_TRACE && start) {  // one place where a path kernel's lane takes a ray: bounce in place, or refill
                 if (MODE != W_SLOW) r = make_rayk(no, nd);
-                path = npath; bounce = nbounce;
+                path = MODE == W_PRIMARY ? npath | (nbounce << 31) : npath; bounce = nbounce;
                 fnode = 0; fw = 0; ft = 0.f; lvl = 0;
                 ghave = false; gt = 0.f; gtf = 0;
                 if (MEMO) memo[0] = 0xFFFFFFFFu;

@@ -24,7 +24,8 @@ lib.rth_debug_counters_n(scene.h, out, 24)
 d = list(out)
 names = ["S steps", "S lanes", "L steps", "L lanes", "refills", "refill lanes", "edge blocks", "edge lanes", "S cycles", "L cycles", "refill cycles", "wave cycles",
          "leaf visits", "memo hits", "planes skipped", "edges skipped",
-         "packet L steps", "primary L steps", "packet refs", "refs culled", "violations"]
+         "packet L steps", "primary L steps", "packet refs", "refs culled", "violations",
+         "mirror rays", "mirror in place", "mirror steps"]
 for n, v in zip(names, d):
     print(f"{n:14s} {v}")
 rays = ctx.stats["rays"]
@@ -38,5 +39,9 @@ print(f"shader-clock cycles of a wave (counting build, all passes of the last ba
 print(f"leaf memo: {d[13]} of {d[12]} leaf visits take the result of the list the ray scanned last ({d[13] / max(d[12], 1):.3f}); "
       f"plane tests skipped {d[14]} ({d[14] / max(ctx.stats['tri_tests'], 1):.3f} of the call's tri_tests if it was one batch), "
       f"edge tests skipped {d[15]} ({d[15] / max(ctx.stats['full_tests'], 1):.3f} of full_tests)")
-print(f"packet cull (primary pass): {d[16]} of {d[17]} LEAF steps qualify ({d[16] / max(d[17], 1):.3f}); "
-      f"{d[19]} of their {d[18]} references culled ({d[19] / max(d[18], 1):.3f}); violations {d[20]} (must be 0)")
+print(f"packet cull (k_path_primary, with the mirror reflections it traces in place): {d[16]} of {d[17]} LEAF steps qualify "
+      f"({d[16] / max(d[17], 1):.3f}); {d[19]} of their {d[18]} references culled ({d[19] / max(d[18], 1):.3f}); violations {d[20]} (must be 0)")
+# dbg[23] packs two step counts: exchange steps with >= 32 mirror lanes (low 32 bits), with 64 (high 32 bits)
+print(f"mirror paths (RTMI_MIRROR_INPLACE={os.environ.get('RTMI_MIRROR_INPLACE', 'default')}): {d[21]} primary rays go on through a "
+      f"Reflective hit ({d[21] / max(rays, 1):.4f} of all rays), {d[22]} of them traced in place by k_path_primary; exchange steps "
+      f"with >= 32 mirror lanes {d[23] & 0xFFFFFFFF}, with 64 {d[23] >> 32}")
