@@ -230,6 +230,27 @@ int rtmi_render_tile_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint
                             const rtmi_tile_t* tile, void* out_device, void* hip_stream,
                             rtmi_stats_t* stats);
 
+/* Progressive rendering: samples [sample0, sample0 + nsamples) of every pixel of the tile, where vp->samples_per_pixel = S
+ * is the frame's total (it decides the centred-ray rule of pixel_ray, raytrace.rs:1374-1394, and the final 1/S).
+ * accum: one float4 per pixel of the tile (same layout as out) holding the running per-pixel sum of the samples done; read
+ * when sample0 > 0, ignored (not read) when sample0 == 0, always rewritten.  out (optional, may be NULL; never the same
+ * buffer as accum): the preview accum * (1/(sample0 + nsamples)).
+ * Exactness: the RNG is keyed by (seed, pixel, sample, block), not by S, and a pixel's samples are summed in sample order
+ * from 0.f, so passes that cover [0, S) in order leave in out exactly the bits of rtmi_render_tile_device.  The preview
+ * after k samples equals a render at samples_per_pixel = k when k >= 2 or S == 1; with k == 1 < S it does not (sample 0 of
+ * an S-sample frame is jittered, a 1-sample frame's is centred).
+ * Passes must be issued in sample order, each continuing the previous one on the same accum: the library does not check.
+ * stats describe this call only; summed over the passes of a frame they equal the single call's.  maxdepth == 0 writes
+ * zeros to accum and out.  RTMI_ERR_INVALID also for nsamples == 0, sample0 + nsamples > S and a NULL accum.
+ * The device variant enqueues on hip_stream like rtmi_render_tile_device and copies nothing.  The host variant renders
+ * rows [row0, row0 + nrows) and copies accum in (only when sample0 > 0) and out again: 2 x 16 B per pixel of host-link
+ * traffic per pass (+ 16 B when out_host is given). */
+int rtmi_render_samples_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile,
+                               uint32_t sample0, uint32_t nsamples, void* accum_device, void* out_device,
+                               void* hip_stream, rtmi_stats_t* stats);
+int rtmi_render_samples(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
+                        uint32_t sample0, uint32_t nsamples, float* accum_host, float* out_host, rtmi_stats_t* stats);
+
 /* One whole frame over several devices of this process -- the fan-out the reference does over CPU threads
  * (DefaultRayCaster::walk_rays_internal, raytrace.rs:1175-1196: `threads` workers pulling rows from a queue) done
  * over GPUs, inside the library.  scenes[i] is the SAME scene uploaded to some device (rtmi_scene_create with

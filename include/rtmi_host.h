@@ -79,6 +79,14 @@ int rth_caster_walk_rows_device(rth_scene_t* s, uint32_t w, uint32_t h, const fl
 int rth_caster_walk_tile_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
                                 const rtmi_tile_t* tile, void* out_device, void* hip_stream, rtmi_stats_t* stats,
                                 double* wall_seconds);
+/* Progressive rendering (rtmi_render_samples / rtmi_render_samples_device in rtmi.h): samples [sample0, sample0 + nsamples)
+ * of the frame's spp, continuing the running per-pixel sums in accum; out (may be NULL) receives the preview. */
+int rth_caster_walk_samples(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                            uint64_t row0, uint64_t nrows, uint32_t sample0, uint32_t nsamples, float* accum_host, float* out_host,
+                            rtmi_stats_t* stats, double* wall_seconds);
+int rth_caster_walk_samples_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                                   const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, void* accum_device,
+                                   void* out_device, void* hip_stream, rtmi_stats_t* stats, double* wall_seconds);
 int rth_caster_trace(rth_scene_t* s, uint64_t n, const float* orig4, const float* dir4, uint32_t* tri, float* t,
                      uint32_t* face, rtmi_stats_t* stats);
 /* Multi-GPU inside the process (rtmi_render_frame_multi): the caster keeps one resident copy of the scene per entry of

@@ -490,30 +490,43 @@ __global__ void __launch_bounds__(256) k_trace_linear(DScene sc, const float4* _
 
 // ---------------------------------------------------------------- generation / shading (per-pass pipeline)
 // pixel_ray / color_ray themselves are in shade.hpp (shared with the path kernels of trace_oct.hpp).
-__global__ void __launch_bounds__(256) k_gen(DView v, uint64_t seed, uint32_t pix0, uint32_t npaths,
-                                             float4* __restrict__ qo, float4* __restrict__ qd,
-                                             uint32_t* __restrict__ qpath, DCtrl* __restrict__ ctrl) {
+// PROG = true: the kernels of progressive passes (k_gen_samples, k_shade_samples), whose sample numbers start at sample0
+template <bool PROG>
+__device__ __forceinline__ void gen_paths(const DView& v, uint64_t seed, uint32_t pix0, uint32_t npaths, float4* __restrict__ qo,
+                                          float4* __restrict__ qd, uint32_t* __restrict__ qpath, DCtrl* __restrict__ ctrl) {
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t path = blockIdx.x * blockDim.x + threadIdx.x; path < npaths; path += stride) {
         uint32_t row, col, sample;
-        path_pixel(v, pix0, path, row, col, sample);
+        path_pixel<PROG>(v, pix0, path, row, col, sample);
         const uint32_t pixel = row * v.width + col;
-        RayV r = pixel_ray(v, row, col, seed, pixel, sample);
+        RayV r = pixel_ray<PROG>(v, row, col, seed, pixel, sample);
         qo[path] = make_float4(r.orig.x, r.orig.y, r.orig.z, r.orig.w);
         qd[path] = make_float4(r.dir.x, r.dir.y, r.dir.z, r.dir.w);
         qpath[path] = path;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) ctrl->count[0] = npaths;
 }
+__global__ void __launch_bounds__(256) k_gen(DView v, uint64_t seed, uint32_t pix0, uint32_t npaths,
+                                             float4* __restrict__ qo, float4* __restrict__ qd,
+                                             uint32_t* __restrict__ qpath, DCtrl* __restrict__ ctrl) {
+    gen_paths<false>(v, seed, pix0, npaths, qo, qd, qpath, ctrl);
+}
+__global__ void __launch_bounds__(256) k_gen_samples(DView v, uint64_t seed, uint32_t pix0, uint32_t npaths,
+                                                     float4* __restrict__ qo, float4* __restrict__ qd,
+                                                     uint32_t* __restrict__ qpath, DCtrl* __restrict__ ctrl) {
+    gen_paths<true>(v, seed, pix0, npaths, qo, qd, qpath, ctrl);
+}
 
 // color_ray + the tail of project_ray for every ray of pass `pass`.
-__global__ void __launch_bounds__(256) k_shade(DScene sc, DView v, uint64_t seed, uint32_t pix0, uint32_t npaths, int pass,
-                                               const float4* __restrict__ qo, const float4* __restrict__ qd,
-                                               const uint32_t* __restrict__ qpath, const uint32_t* __restrict__ hit_tf,
-                                               const float* __restrict__ hit_t, float4* __restrict__ qo_n,
-                                               float4* __restrict__ qd_n, uint32_t* __restrict__ qpath_n,
-                                               uint16_t* __restrict__ mstack, float4* __restrict__ scol,
-                                               DCtrl* __restrict__ ctrl, SlowQ slow) {
+#define RTMI_SHADE_PARAMS DScene sc, DView v, uint64_t seed, uint32_t pix0, uint32_t npaths, int pass,                  \
+                          const float4* __restrict__ qo, const float4* __restrict__ qd,                                \
+                          const uint32_t* __restrict__ qpath, const uint32_t* __restrict__ hit_tf,                     \
+                          const float* __restrict__ hit_t, float4* __restrict__ qo_n, float4* __restrict__ qd_n,       \
+                          uint32_t* __restrict__ qpath_n, uint16_t* __restrict__ mstack, float4* __restrict__ scol,    \
+                          DCtrl* __restrict__ ctrl, SlowQ slow
+#define RTMI_SHADE_ARGS sc, v, seed, pix0, npaths, pass, qo, qd, qpath, hit_tf, hit_t, qo_n, qd_n, qpath_n, mstack, scol, ctrl, slow
+template <bool PROG>
+__device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS) {
     __shared__ uint32_t s_cnt[4], s_base;
     const uint32_t count = ctrl->count[pass];
     const uint32_t stride = gridDim.x * blockDim.x;
@@ -534,7 +547,7 @@ __global__ void __launch_bounds__(256) k_shade(DScene sc, DView v, uint64_t seed
             float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f), d4 = make_float4(0.f, 0.f, 1.f, 0.f);
             if ((tf & 0x3FFFFFFFu) != 0u && !((tf >> 30) & 2u)) { t = hit_t[i]; o4 = qo[i]; d4 = qd[i]; }
             uint32_t prow, pcol, sample;
-            path_pixel(v, pix0, path, prow, pcol, sample);
+            path_pixel<PROG>(v, pix0, path, prow, pcol, sample);
             push = shade_hit(sc, v.maxdepth, seed, npaths, path, prow * v.width + pcol, sample, (uint32_t)pass, tf, t,
                              V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr);
             // a bounce ray with an exactly-zero direction component goes to the slow path (SlowQ), not to the next pass
@@ -567,6 +580,8 @@ __global__ void __launch_bounds__(256) k_shade(DScene sc, DView v, uint64_t seed
         __syncthreads();  // s_cnt / s_base are rewritten by the next iteration
     }
 }
+__global__ void __launch_bounds__(256) k_shade(RTMI_SHADE_PARAMS) { shade_pass<false>(RTMI_SHADE_ARGS); }
+__global__ void __launch_bounds__(256) k_shade_samples(RTMI_SHADE_PARAMS) { shade_pass<true>(RTMI_SHADE_ARGS); }
 
 // walk_ray_set's per-pixel accumulation (raytrace.rs:1414-1426): acc = 0; acc += sample_i in sample order; * (1/spp).
 // The sample colours of a pixel are consecutive in `scol` ([pixel][sample]), so one thread per pixel would read 16 B at a
@@ -579,18 +594,26 @@ __global__ void __launch_bounds__(256) k_shade(DScene sc, DView v, uint64_t seed
 // the sub-tile is row lr * nsub + sub of the buffer.
 #define RTMI_ACC_PIX 64
 #define RTMI_ACC_CHUNK 1024
-__global__ void __launch_bounds__(256) k_accum(uint32_t npixels, uint32_t spp, const float4* __restrict__ scol,
-                                               float* __restrict__ out, uint32_t pix0, uint32_t W, uint32_t nsub, uint32_t sub,
-                                               FastDiv dW) {
+// RESUME = false: k_accum, the sum starts at 0.f and out = sum * inv.  RESUME = true: k_accum_samples (progressive passes),
+// the sum starts from accum when `resume`, is written back to accum, and out (when not NULL) = sum * inv.
+template <bool RESUME>
+__device__ __forceinline__ void accum_pixels(uint32_t npixels, uint32_t spp, const float4* __restrict__ scol, float* __restrict__ out,
+                                             float* __restrict__ accum, bool resume, float inv, uint32_t pix0, uint32_t W,
+                                             uint32_t nsub, uint32_t sub, FastDiv dW) {
     __shared__ float4 stage[RTMI_ACC_CHUNK + RTMI_ACC_CHUNK / 64 + 1];
     const float* stage_f = reinterpret_cast<const float*>(stage);
     const uint32_t tid = threadIdx.x, j = tid >> 2, c = tid & 3u;
-    const float inv = 1.f / (float)spp;
     for (uint32_t pb = blockIdx.x * RTMI_ACC_PIX; pb < npixels; pb += gridDim.x * RTMI_ACC_PIX) {
         const uint32_t npb = min((uint32_t)RTMI_ACC_PIX, npixels - pb);
         const uint32_t f0 = pb * spp, f1 = f0 + npb * spp;       // the block's samples: scol[f0 .. f1)
         const uint32_t my0 = f0 + j * spp, my1 = my0 + spp;      // this thread's pixel (when j < npb)
+        size_t o = 0;                                            // RESUME: this thread's float in accum / out
         float acc = 0.f;
+        if (RESUME && j < npb) {
+            const uint32_t lp = pix0 + pb + j, lr = fdiv(lp, dW), col = lp - lr * W;
+            o = (((size_t)lr * nsub + sub) * W + col) * 4u + c;
+            if (resume) acc = accum[o];
+        }
         for (uint32_t ch = f0; ch < f1; ch += RTMI_ACC_CHUNK) {
             const uint32_t n = min((uint32_t)RTMI_ACC_CHUNK, f1 - ch);
             __syncthreads();  // the previous chunk has been consumed
@@ -605,11 +628,29 @@ __global__ void __launch_bounds__(256) k_accum(uint32_t npixels, uint32_t spp, c
             }
         }
         if (j < npb) {
-            const uint32_t lp = pix0 + pb + j, lr = fdiv(lp, dW), col = lp - lr * W;
-            const size_t orow = (size_t)lr * nsub + sub;
-            out[(orow * W + col) * 4u + c] = acc * inv;
+            if (RESUME) {
+                accum[o] = acc;
+                if (out) out[o] = acc * inv;
+            } else {
+                const uint32_t lp = pix0 + pb + j, lr = fdiv(lp, dW), col = lp - lr * W;
+                const size_t orow = (size_t)lr * nsub + sub;
+                out[(orow * W + col) * 4u + c] = acc * inv;
+            }
         }
     }
+}
+__global__ void __launch_bounds__(256) k_accum(uint32_t npixels, uint32_t spp, const float4* __restrict__ scol,
+                                               float* __restrict__ out, uint32_t pix0, uint32_t W, uint32_t nsub, uint32_t sub,
+                                               FastDiv dW) {
+    accum_pixels<false>(npixels, spp, scol, out, nullptr, false, 1.f / (float)spp, pix0, W, nsub, sub, dW);
+}
+// Samples [sample0, sample0 + nsamples) of every pixel: continuing the running sum of samples [0, sample0) in accum performs
+// the same f32 additions in the same order as k_accum over all samples, so the passes of a frame end in the same bits.
+// `out` = the preview sum * (1/(sample0 + nsamples)); `accum` and `out` are the same tile layout and never overlap.
+__global__ void __launch_bounds__(256) k_accum_samples(uint32_t npixels, uint32_t nsamples, uint32_t sample0, const float4* __restrict__ scol,
+                                                       float* __restrict__ accum, float* __restrict__ out, uint32_t pix0, uint32_t W,
+                                                       uint32_t nsub, uint32_t sub, FastDiv dW) {
+    accum_pixels<true>(npixels, nsamples, scol, out, accum, sample0 != 0u, 1.f / (float)(sample0 + nsamples), pix0, W, nsub, sub, dW);
 }
 
 // write_png's quantisation (raytrace.rs:1468-1473): `as u8` truncates and saturates, NaN -> 0
@@ -786,6 +827,7 @@ struct rtmi_scene {
     hipStream_t istream[RTMI_MAX_STREAMS] = {};
     hipEvent_t fork_ev = nullptr, end_ev = nullptr, join_ev[RTMI_MAX_STREAMS] = {};
     DevBuf<float4> tile;
+    DevBuf<float4> acc;              // rtmi_render_samples: the running per-pixel sums of the host variant
     DevBuf<uint8_t> qbytes;
     DevBuf<uint8_t> mstage, mframe;  // rtmi_render_frame_multi, root scene: received bands / the frame
     hipStream_t mstream = nullptr;   // rtmi_render_frame_multi: this scene's band stream
@@ -1208,7 +1250,7 @@ int rtmi_scene_destroy(rtmi_scene_t* s) {
     }
     if (s->fork_ev) (void)hipEventDestroy(s->fork_ev);
     if (s->end_ev) (void)hipEventDestroy(s->end_ev);
-    s->tile.release(); s->qbytes.release(); s->mstage.release(); s->mframe.release();
+    s->tile.release(); s->acc.release(); s->qbytes.release(); s->mstage.release(); s->mframe.release();
     if (s->mstream) (void)hipStreamDestroy(s->mstream);
     if (!s->comms.empty()) { if (Rccl* r = rccl_api()) for (ncclComm_t c : s->comms) (void)r->CommDestroy(c); }
     delete s;
@@ -1381,7 +1423,7 @@ static OctArgs path_args(rtmi_scene* s, Work& w, const DView& dv, uint64_t seed,
 // k_path_primary: the batch's primary rays generated, traced and shaded; the bounce rays go to queue 1, which pass 1 traces.
 // The mirror reflections it traces itself go on in queue 2 (ping-pong buffer 0, free until pass 1's k_shade appends to it).
 // `stop` is recorded right after the kernel.
-template <bool COUNT>
+template <bool COUNT, bool PROG>
 static void launch_primary(rtmi_scene* s, Work& w, hipStream_t st, const DView& dv, uint64_t seed, uint32_t pix0, uint32_t npaths,
                            hipEvent_t stop) {
     OctArgs a = path_args(s, w, dv, seed, pix0, npaths);
@@ -1391,14 +1433,19 @@ static void launch_primary(rtmi_scene* s, Work& w, hipStream_t st, const DView& 
     a.b2qo = w.qo[0].p; a.b2qd = w.qd[0].p; a.b2qpath = w.qpath[0].p;
     a.minpl = s->mirror_inplace;
     const int refill = (int)s->tune.refill_min0, xcd = (int)(s->tune.xcd_aware % 3u);
-    if (s->options & RTMI_OPT_FAST)
+    const bool fast = (s->options & RTMI_OPT_FAST) != 0;
+    if (PROG && fast)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary_samples<COUNT, true>), oct_grid(s), dim3(64), oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
+    else if (PROG)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary_samples<COUNT, false>), oct_grid(s), dim3(64), oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
+    else if (fast)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary<COUNT, true>), oct_grid(s), dim3(64), oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
     else
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary<COUNT, false>), oct_grid(s), dim3(64), oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
     (void)hipEventRecord(stop, st);
 }
 // Consumer launch k of the slow path (k_path_slow), on the side stream: after the producer on `st` whose event is sev[k]
-template <bool COUNT>
+template <bool COUNT, bool PROG>
 static void launch_slow(rtmi_scene* s, Work& w, hipStream_t st, const DView& dv, uint64_t seed, uint32_t pix0, uint32_t npaths,
                         uint32_t k) {
     OctArgs a = path_args(s, w, dv, seed, pix0, npaths);
@@ -1413,7 +1460,12 @@ static void launch_slow(rtmi_scene* s, Work& w, hipStream_t st, const DView& dv,
     (void)hipEventRecord(w.sgo, w.sstream);
     (void)hipStreamWaitEvent(st, w.sgo, 0);
     const dim3 sgrid((unsigned)std::max(s->num_cu / 2, 1));  // one path per wave at a time; a frame has ~100 such paths, a wave takes one after the other
-    if (s->options & RTMI_OPT_FAST)
+    const bool fast = (s->options & RTMI_OPT_FAST) != 0;
+    if (PROG && fast)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow_samples<COUNT, true>), sgrid, dim3(64), oct_launch_lds(s, COUNT), w.sstream, s->d, a, w.ctrl.p, 1, 0);
+    else if (PROG)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow_samples<COUNT, false>), sgrid, dim3(64), oct_launch_lds(s, COUNT), w.sstream, s->d, a, w.ctrl.p, 1, 0);
+    else if (fast)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow<COUNT, true>), sgrid, dim3(64), oct_launch_lds(s, COUNT), w.sstream, s->d, a, w.ctrl.p, 1, 0);
     else
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow<COUNT, false>), sgrid, dim3(64), oct_launch_lds(s, COUNT), w.sstream, s->d, a, w.ctrl.p, 1, 0);
@@ -1447,9 +1499,12 @@ struct SubTile {
     uint32_t index = 0;
 };
 
-int rtmi_render_tile_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile,
-                            void* out_device, void* hip_stream, rtmi_stats_t* stats) {
-    if (!s || !vp || !tile) return fail(RTMI_ERR_INVALID, "NULL argument");
+// Samples [sample0, sample0 + nsamples) of every pixel of the tile.  accum == nullptr: the whole frame (0, S) into out_device
+// (rtmi_render_tile_device, k_accum).  Otherwise a progressive pass (rtmi_render_samples_device, k_accum_samples): the running
+// per-pixel sums continue in accum, out_device (optional) receives the preview.  Batches and automatic streams are sized
+// from the paths of THIS call, npix * nsamples.
+static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile, uint32_t sample0,
+                       uint32_t nsamples, float4* accum, void* out_device, void* hip_stream, rtmi_stats_t* stats) {
     const uint32_t row0 = tile->row0, nrows = tile->nrows;
     if (stats) memset(stats, 0, sizeof(*stats));
     if (nrows == 0) return RTMI_OK;
@@ -1457,7 +1512,7 @@ int rtmi_render_tile_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t
     // leftovers of the caller's own HIP calls on this thread (or of failures this library tolerated, e.g. an occupancy
     // query) must not make a launch below look refused: hipGetLastError() reports the last error of ANY runtime call
     (void)hipGetLastError();
-    if (!out_device) return fail(RTMI_ERR_INVALID, "NULL argument");
+    if (!out_device && !accum) return fail(RTMI_ERR_INVALID, "NULL argument");
     if (vp->width == 0 || vp->height == 0) return fail(RTMI_ERR_INVALID, "empty viewport");
     if (tile->stripe_rows == 0) return fail(RTMI_ERR_INVALID, "stripe_rows must be >= 1");
     {
@@ -1471,11 +1526,12 @@ int rtmi_render_tile_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t
     if ((uint64_t)vp->width * vp->height >= (1ull << 32)) return fail(RTMI_ERR_UNSUPPORTED, "more than 2^32 pixels");
     HIPCHK(hipSetDevice(s->device));
     hipStream_t ust = (hipStream_t)hip_stream;
-    const uint32_t W = vp->width, spp = vp->samples_per_pixel, maxdepth = vp->maxdepth;
+    const uint32_t W = vp->width, spp = nsamples, maxdepth = vp->maxdepth;  // spp: samples per pixel of this call
     const uint64_t npix = (uint64_t)nrows * W;
     float4* out = (float4*)out_device;
     if (maxdepth == 0) {  // project_ray returns black immediately (raytrace.rs:1261-1263); acc*(1/spp) of zeros
-        HIPCHK(hipMemsetAsync(out, 0, npix * sizeof(float4), ust));
+        if (accum) HIPCHK(hipMemsetAsync(accum, 0, npix * sizeof(float4), ust));
+        if (out) HIPCHK(hipMemsetAsync(out, 0, npix * sizeof(float4), ust));
         HIPCHK(hipStreamSynchronize(ust));
         return RTMI_OK;
     }
@@ -1506,7 +1562,8 @@ int rtmi_render_tile_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t
         dv.vu = mk(vp->vu[0], vp->vu[1], vp->vu[2]);
         dv.vv = mk(vp->vv[0], vp->vv[1], vp->vv[2]);
         dv.width = W; dv.height = vp->height; dv.maxdepth = maxdepth; dv.spp = spp;
-        dv.row0 = row0; dv.stripe_rows = tile->stripe_rows; dv.stripe_step = tile->stripe_step; dv.pad = 0;
+        dv.row0 = row0; dv.stripe_rows = tile->stripe_rows; dv.stripe_step = tile->stripe_step;
+        view_set_sampling(dv, sample0, vp->samples_per_pixel);
         dv.sub_mul = nsub; dv.sub_off = t;
         view_set_divisors(dv);
         sub[t].npix = (uint64_t)((nrows - t + nsub - 1) / nsub) * W;
@@ -1532,6 +1589,7 @@ int rtmi_render_tile_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t
     }
 
     const bool counting = (s->options & RTMI_OPT_COUNTERS) != 0;
+    const bool prog = accum != nullptr;  // progressive pass: the *_samples kernels (sample numbers from sample0)
     const bool verbose = s->verbose;
     const unsigned ew_blocks = (unsigned)(s->num_cu * 8);
     float trace_ms = 0.f, primary_ms = 0.f, bounce_ms = 0.f;
@@ -1558,20 +1616,25 @@ int rtmi_render_tile_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t
             auto slow_after = [&](uint32_t k) {  // after producer k: k_path_primary (0) or the shading of pass k
                 if (sq.cap == 0u) return;
                 (void)hipEventRecord(w.sev[k], st);
-                if (counting) launch_slow<true>(s, w, st, dv, seed, pix0, npaths, k);
-                else launch_slow<false>(s, w, st, dv, seed, pix0, npaths, k);
+                if (counting && prog) launch_slow<true, true>(s, w, st, dv, seed, pix0, npaths, k);
+                else if (counting) launch_slow<true, false>(s, w, st, dv, seed, pix0, npaths, k);
+                else if (prog) launch_slow<false, true>(s, w, st, dv, seed, pix0, npaths, k);
+                else launch_slow<false, false>(s, w, st, dv, seed, pix0, npaths, k);
             };
             uint32_t pass0 = 0;  // first pass of the per-pass loop
             if (path_kernels) {
                 HIPCHK(hipEventRecord(w.pass_ev[0], st));
-                if (counting) launch_primary<true>(s, w, st, dv, seed, pix0, npaths, w.pass_ev[1]);
-                else launch_primary<false>(s, w, st, dv, seed, pix0, npaths, w.pass_ev[1]);
+                if (counting && prog) launch_primary<true, true>(s, w, st, dv, seed, pix0, npaths, w.pass_ev[1]);
+                else if (counting) launch_primary<true, false>(s, w, st, dv, seed, pix0, npaths, w.pass_ev[1]);
+                else if (prog) launch_primary<false, true>(s, w, st, dv, seed, pix0, npaths, w.pass_ev[1]);
+                else launch_primary<false, false>(s, w, st, dv, seed, pix0, npaths, w.pass_ev[1]);
                 HIPCHK(hipGetLastError());
                 launches++;
                 slow_after(0);
                 pass0 = 1;
             } else {
-                hipLaunchKernelGGL(k_gen, dim3(ew_blocks), dim3(256), 0, st, dv, seed, pix0, npaths, w.qo[0].p, w.qd[0].p, w.qpath[0].p, w.ctrl.p);
+                hipLaunchKernelGGL(prog ? k_gen_samples : k_gen, dim3(ew_blocks), dim3(256), 0, st, dv, seed, pix0, npaths, w.qo[0].p, w.qd[0].p,
+                                   w.qpath[0].p, w.ctrl.p);
             }
             HIPCHK(hipGetLastError());  // a refused launch is reported where it happens, not at the end of the batch
             for (uint32_t pass = pass0; pass < maxdepth; pass++) {
@@ -1596,7 +1659,7 @@ int rtmi_render_tile_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t
                             (cur[8] - prev[t][8]) / n, (double)(cur[8] - prev[t][8]) / (64.0 * (cur[7] - prev[t][7] ? cur[7] - prev[t][7] : 1)));
                     memcpy(prev[t], cur, sizeof(s->vprev[t]));
                 }
-                hipLaunchKernelGGL(k_shade, dim3(ew_blocks), dim3(256), 0, st, s->d, dv, seed, pix0, npaths, (int)pass,
+                hipLaunchKernelGGL(prog ? k_shade_samples : k_shade, dim3(ew_blocks), dim3(256), 0, st, s->d, dv, seed, pix0, npaths, (int)pass,
                                    w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p,
                                    w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq);
                 HIPCHK(hipGetLastError());
@@ -1610,7 +1673,11 @@ int rtmi_render_tile_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t
                 HIPCHK(hipEventRecord(w.sdone, w.sstream));
                 HIPCHK(hipStreamWaitEvent(st, w.sdone, 0));
             }
-            hipLaunchKernelGGL(k_accum, dim3(ew_blocks), dim3(256), 0, st, np, spp, w.scol.p, (float*)out, pix0, W, nsub, t, make_fastdiv(W));
+            if (!accum)
+                hipLaunchKernelGGL(k_accum, dim3(ew_blocks), dim3(256), 0, st, np, spp, w.scol.p, (float*)out, pix0, W, nsub, t, make_fastdiv(W));
+            else
+                hipLaunchKernelGGL(k_accum_samples, dim3(ew_blocks), dim3(256), 0, st, np, spp, sample0, w.scol.p, (float*)accum,
+                                   (float*)out, pix0, W, nsub, t, make_fastdiv(W));
             HIPCHK(hipEventRecord(w.ev[1], st));
             HIPCHK(hipGetLastError());
         }
@@ -1652,6 +1719,57 @@ int rtmi_render_tile_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t
     }
     return RTMI_OK;
     RTMI_GUARD_END
+}
+
+int rtmi_render_tile_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile,
+                            void* out_device, void* hip_stream, rtmi_stats_t* stats) {
+    if (!s || !vp || !tile) return fail(RTMI_ERR_INVALID, "NULL argument");
+    return render_tile(s, vp, seed, tile, 0u, vp->samples_per_pixel, nullptr, out_device, hip_stream, stats);
+}
+
+// Checks of the progressive entry points that come before any HIP call (a CPU-only caller reaches them).
+static int check_samples(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint32_t sample0, uint32_t nsamples, const void* accum,
+                         const void* out) {
+    if (!s || !vp) return fail(RTMI_ERR_INVALID, "NULL argument (scene or viewport)");
+    if (!accum) return fail(RTMI_ERR_INVALID, "NULL accumulator");
+    if (accum == out) return fail(RTMI_ERR_INVALID, "accumulator and output must be different buffers");
+    if (vp->samples_per_pixel == 0) return fail(RTMI_ERR_INVALID, "samples_per_pixel must be >= 1");
+    if (nsamples == 0) return fail(RTMI_ERR_INVALID, "nsamples must be >= 1");
+    if ((uint64_t)sample0 + nsamples > vp->samples_per_pixel)
+        return fail(RTMI_ERR_INVALID, "samples [sample0, sample0 + nsamples) outside the frame's samples_per_pixel");
+    if (sample0 & RTMI_KEY_JITTER) return fail(RTMI_ERR_UNSUPPORTED, "sample0 above 2^31");  // DView::sample_key
+    return RTMI_OK;
+}
+
+int rtmi_render_samples_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile,
+                               uint32_t sample0, uint32_t nsamples, void* accum_device, void* out_device, void* hip_stream,
+                               rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    const int rc = check_samples(s, vp, sample0, nsamples, accum_device, out_device);
+    if (rc != RTMI_OK) return rc;
+    if (!tile) return fail(RTMI_ERR_INVALID, "NULL argument (tile)");
+    return render_tile(s, vp, seed, tile, sample0, nsamples, (float4*)accum_device, out_device, hip_stream, stats);
+}
+
+// Host variant: accum is copied in (only when sample0 > 0) and out again, 2 x 16 B per pixel over the host link per pass.
+int rtmi_render_samples(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
+                        uint32_t sample0, uint32_t nsamples, float* accum_host, float* out_host, rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    const int rc0 = check_samples(s, vp, sample0, nsamples, accum_host, out_host);
+    if (rc0 != RTMI_OK) return rc0;
+    const uint64_t npix = (uint64_t)nrows * vp->width;
+    if (npix == 0) return RTMI_OK;
+    if ((uint64_t)row0 + nrows > vp->height) return fail(RTMI_ERR_INVALID, "row range outside the viewport");
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(s->acc.ensure(npix));
+    if (out_host) HIPCHK(s->tile.ensure(npix));
+    if (sample0 > 0) HIPCHK(hipMemcpy(s->acc.p, accum_host, npix * sizeof(float4), hipMemcpyHostToDevice));
+    const rtmi_tile_t tile{row0, nrows, nrows, 0u};
+    int rc = render_tile(s, vp, seed, &tile, sample0, nsamples, s->acc.p, out_host ? (void*)s->tile.p : nullptr, nullptr, stats);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(hipMemcpy(accum_host, s->acc.p, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    if (out_host) HIPCHK(hipMemcpy(out_host, s->tile.p, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    return RTMI_OK;
 }
 
 int rtmi_render(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,

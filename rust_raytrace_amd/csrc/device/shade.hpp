@@ -30,11 +30,19 @@ __host__ __device__ inline uint32_t fdiv(uint32_t n, const FastDiv& f) {
 
 struct DView {
     V4 orig, cam, vu, vv;
-    uint32_t width, height, maxdepth, spp;
-    uint32_t row0, stripe_rows, stripe_step, pad;  // rtmi_tile_t: which image rows the tile's rows are
+    uint32_t width, height, maxdepth, spp;         // spp: samples per pixel of THIS call (paths per pixel of a batch)
+    uint32_t row0, stripe_rows, stripe_step;       // rtmi_tile_t: which image rows the tile's rows are
+    // progressive passes only (the PROG = true kernels; the whole-frame kernels never read it): bits 0-30 sample0, the
+    // frame's sample number of the call's first sample; bit 31 set when the FRAME has more than one sample per pixel
+    // (spp_frame != 1: pixel_ray jitters).  view_set_sampling() fills it.
+    uint32_t sample_key;
     uint32_t sub_mul, sub_off;                     // sub-tile of a stream: rows sub_off, sub_off + sub_mul, ... of the tile
     FastDiv dspp, dwidth, dstripe;                 // n / spp, n / width, n / stripe_rows
 };
+#define RTMI_KEY_JITTER 0x80000000u
+inline void view_set_sampling(DView& v, uint32_t sample0, uint32_t spp_frame) {
+    v.sample_key = sample0 | (spp_frame != 1u ? RTMI_KEY_JITTER : 0u);
+}
 inline void view_set_divisors(DView& v) {
     v.dspp = make_fastdiv(v.spp);
     v.dwidth = make_fastdiv(v.width);
@@ -50,10 +58,14 @@ __device__ inline void tile_pixel(const DView& v, uint32_t lp, uint32_t& row, ui
     const uint32_t k = fdiv(L, v.dstripe);
     row = v.row0 + k * v.stripe_step + (L - k * v.stripe_rows);
 }
-// path index of a batch that starts at local pixel pix0 -> image pixel index (row * width + col) and sample number
+// path index of a batch that starts at local pixel pix0 -> image pixel index (row * width + col) and the FRAME's sample
+// number (the RNG key).  PROG: a progressive pass renders samples [sample0, sample0 + spp) of its pixels; otherwise the
+// call renders all of them (sample0 = 0, and the kernel does not spend the add and the register on it: 2 % of config 3's
+// frame time when it did).
+template <bool PROG>
 __device__ inline void path_pixel(const DView& v, uint32_t pix0, uint32_t path, uint32_t& row, uint32_t& col, uint32_t& sample) {
     const uint32_t q = fdiv(path, v.dspp);
-    sample = path - q * v.spp;
+    sample = (PROG ? (v.sample_key & ~RTMI_KEY_JITTER) : 0u) + (path - q * v.spp);
     tile_pixel(v, pix0 + q, row, col);
 }
 
@@ -61,13 +73,15 @@ struct RayV { V4 orig, dir; };
 // make_ray (raytrace.rs:201-210); inv_dir is recomputed by the trace kernel
 __device__ inline RayV make_ray(V4 orig, V4 dir) { return RayV{orig, vunit(dir)}; }
 
-// Viewport::pixel_ray (raytrace.rs:1374-1394), px = (row, col)
+// Viewport::pixel_ray (raytrace.rs:1374-1394), px = (row, col).  The centred ray is the rule of a 1-sample FRAME: a
+// progressive pass of one sample of a larger frame (PROG) is jittered like every other sample of it.
+template <bool PROG>
 __device__ inline RayV pixel_ray(const DView& v, uint32_t row, uint32_t col, uint64_t seed, uint32_t pixel, uint32_t sample) {
     float px_x = (float)row, px_y = (float)col;
     V4 vu_delta = vmul(v.vu, 1.f / (float)v.width);
     V4 vv_delta = vmul(v.vv, 1.f / (float)v.height);
     float u_off = 0.5f, v_off = 0.5f;
-    if (v.spp != 1) {
+    if (PROG ? (v.sample_key & RTMI_KEY_JITTER) != 0u : v.spp != 1) {  // spp_frame != 1
         uint32_t w[4];
         rng_block(seed, pixel, sample, 0, w);
         u_off = u32_to_unit_f32(w[0]);

@@ -196,7 +196,7 @@ __host__ __device__ inline bool packet_culls(const Packet& p, float4 p0, float4 
     return (c1 <= 1e15f) & (nn <= 1e15f) & (fabsf(den0) > X + X) & (x2 > (y * y) * (1.f + PK_K));
 }
 
-template <bool COUNT, bool FAST, int MODE>
+template <bool COUNT, bool FAST, int MODE, bool PROG = false>
 __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCtrl* __restrict__ ctrl, uint32_t* __restrict__ lds,
                                          int refill_min, int xcd_aware) {
     const int lane = threadIdx.x;  // one wave per block
@@ -298,7 +298,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                 RayV nr;
                 if (mode == M_SHADE) {
                     uint32_t prow, pcol, sample;
-                    path_pixel(a.v, a.pix0, pth, prow, pcol, sample);
+                    path_pixel<PROG>(a.v, a.pix0, pth, prow, pcol, sample);
                     const bool cont = shade_hit(sc, a.v.maxdepth, a.seed, a.npaths, pth, prow * a.v.width + pcol, sample, bnc,
                                                 ghave ? gtf : 0u, gt, V4{r.ox, r.oy, r.oz, r.ow}, V4{r.dx, r.dy, r.dz, r.dw},
                                                 a.mstack, a.scol, nr, &mirror);
@@ -407,8 +407,8 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                     if (i < hi) {
                         if (MODE == W_PRIMARY) {
                             uint32_t prow, pcol, sample;
-                            path_pixel(a.v, a.pix0, i, prow, pcol, sample);
-                            const RayV pr = pixel_ray(a.v, prow, pcol, a.seed, prow * a.v.width + pcol, sample);
+                            path_pixel<PROG>(a.v, a.pix0, i, prow, pcol, sample);
+                            const RayV pr = pixel_ray<PROG>(a.v, prow, pcol, a.seed, prow * a.v.width + pcol, sample);
                             no = make_float4(pr.orig.x, pr.orig.y, pr.orig.z, pr.orig.w);
                             nd = make_float4(pr.dir.x, pr.dir.y, pr.dir.z, pr.dir.w);
                             npath = i; nbounce = 0u;
@@ -808,6 +808,17 @@ template <bool COUNT, bool FAST>
 __global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_slow(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min, int xcd_aware) {
     extern __shared__ uint32_t lds[];
     oct_walk<COUNT, FAST, W_SLOW>(sc, a, ctrl, lds, refill_min, xcd_aware);
+}
+// The same two kernels for progressive passes (rtmi_render_samples*): sample numbers start at DView::sample_key's sample0
+template <bool COUNT, bool FAST>
+__global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_primary_samples(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min, int xcd_aware) {
+    extern __shared__ uint32_t lds[];
+    oct_walk<COUNT, FAST, W_PRIMARY, true>(sc, a, ctrl, lds, refill_min, xcd_aware);
+}
+template <bool COUNT, bool FAST>
+__global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_slow_samples(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min, int xcd_aware) {
+    extern __shared__ uint32_t lds[];
+    oct_walk<COUNT, FAST, W_SLOW, true>(sc, a, ctrl, lds, refill_min, xcd_aware);
 }
 
 }  // namespace rtmi

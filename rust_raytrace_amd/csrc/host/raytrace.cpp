@@ -667,6 +667,32 @@ void HipRayCaster::walk_tile_device(const Viewport& v, const Scene& s, const rtm
     progress.stats = st;
 }
 
+void HipRayCaster::walk_samples(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
+                                Color* accum, Color* out, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_samples(h, &av, seed, (uint32_t)row0, (uint32_t)nrows, sample0, nsamples,
+                                       reinterpret_cast<float*>(accum), reinterpret_cast<float*>(out), &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_samples: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
+void HipRayCaster::walk_samples_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0,
+                                       uint32_t nsamples, void* accum_device, void* out_device, void* hip_stream,
+                                       ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_samples_device(h, &av, seed, &tile, sample0, nsamples, accum_device, out_device, hip_stream, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_samples_device: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
 void HipRayCaster::walk_rows(const Viewport& v, const Scene& s, size_t row0, size_t nrows, Color* data, ProgressCtx& progress) {
     rtmi_scene_t* h = resident(s);
     const rtmi_viewport_t av = to_abi(v);

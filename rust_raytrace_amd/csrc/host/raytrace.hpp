@@ -177,6 +177,13 @@ public:
     // Striped row set (rtmi_tile_t): rank r of N renders {r*S, H/N, S, N*S}.
     void walk_tile_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, void* out_device,
                           void* hip_stream, ProgressCtx& progress);
+    // Progressive rendering (rtmi_render_samples / rtmi_render_samples_device): samples [sample0, sample0 + nsamples) of
+    // the frame's v.samples_per_pixel, continuing the per-pixel running sums in `accum` (read only when sample0 > 0);
+    // `out` (may be null) receives the preview.  Passes over [0, spp) in order end in the bits of walk_rows / walk_tile_device.
+    void walk_samples(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
+                      Color* accum, Color* out, ProgressCtx& progress);
+    void walk_samples_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
+                             void* accum_device, void* out_device, void* hip_stream, ProgressCtx& progress);
     void set_options(uint32_t opts) { options_ = opts; }
     // Progress while rendering, as DefaultRayCaster reports it (raytrace.rs:1411, :1429-1435 send one tuple per finished
     // row / per 10 k rays: (thread, row, pixels done, {"Rays": n}); progress.rs:95-141 draws from them).  With a callback

@@ -312,6 +312,66 @@ class HipRayCaster:
                                                     C.byref(st), C.byref(wall)))
         return ProgressCtx(st.rays, wall.value, st.as_dict())
 
+    def walk_samples(self, v, s, row0, nrows, sample0, nsamples, accum, out=None):
+        """Progressive pass on host arrays (rtmi_render_samples): samples [sample0, sample0+nsamples) of the frame's
+        v.samples_per_pixel for rows [row0, row0+nrows).  accum (nrows*width*4 f32) holds the running per-pixel sums: read
+        when sample0 > 0, always rewritten.  out (optional, same shape) receives the preview accum * (1/(sample0+nsamples)).
+        Passes over [0, spp) in sample order end in the bits of walk_rows."""
+        for name, a in (("accum", accum), ("out", out)):
+            if a is not None and (a.dtype != np.float32 or not a.flags.c_contiguous or a.size != nrows * v.width * 4):
+                raise ValueError(f"{name} must be a C-contiguous float32 array of nrows*width*4 elements")
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_samples(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, row0, nrows,
+                                                sample0, nsamples, _p(accum), _p(out) if out is not None else None,
+                                                C.byref(st), C.byref(wall)))
+        return ProgressCtx(st.rays, wall.value, st.as_dict())
+
+    def walk_samples_device(self, v, s, tile, sample0, nsamples, accum_ptr, out_ptr, stream_ptr=None):
+        """The same on device memory (rtmi_render_samples_device) for a striped row set tile = (row0, nrows, stripe_rows,
+        stripe_step), enqueued on HIP stream `stream_ptr`; out_ptr may be None/0 (no preview).  No host copies."""
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        t = _ffi.Tile(*[int(x) for x in tile])
+        _chk(_ffi.lib().rth_caster_walk_samples_device(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel,
+                                                       C.byref(t), sample0, nsamples, C.c_void_p(accum_ptr),
+                                                       C.c_void_p(out_ptr or 0), C.c_void_p(stream_ptr or 0),
+                                                       C.byref(st), C.byref(wall)))
+        return ProgressCtx(st.rays, wall.value, st.as_dict())
+
+    def walk_rays_progressive(self, v, s, data, pass_samples=8, on_pass=None):
+        """walk_rays in passes of `pass_samples` samples per pixel (the last pass may be shorter).  After each pass `data`
+        ((H, W, 4) f32) holds the preview of the samples done and on_pass(samples_done, ctx) is called with the running
+        ProgressCtx; if it returns False the loop stops there.  Returns a ProgressCtx with the total rays, summed stats and
+        `samples_done`.  When every pass runs, `data` ends bit-identical to walk_rays.  The preview after k samples equals a
+        render at samples_per_pixel = k when k >= 2 (a first pass of one sample of a larger frame is jittered).  Each pass
+        copies the running sums to and from the device (2 x 16 B per pixel); walk_samples_device avoids that."""
+        if data.dtype != np.float32 or not data.flags.c_contiguous or data.size != v.height * v.width * 4:
+            raise ValueError("data must be a C-contiguous float32 array of height*width*4 elements")
+        spp, step = int(v.samples_per_pixel), int(pass_samples)
+        if step < 1:
+            raise ValueError("pass_samples must be >= 1")
+        accum = np.zeros_like(data)
+        ctx = ProgressCtx(0, 0.0, None)
+        ctx.samples_done = 0
+        for k0 in range(0, spp, step):
+            n = min(step, spp - k0)
+            p = self.walk_samples(v, s, 0, v.height, k0, n, accum, data)
+            ctx.total_rays += p.total_rays
+            ctx.seconds += p.seconds
+            if ctx.stats is None:
+                ctx.stats = dict(p.stats)
+            else:
+                for k in ("rays", "box_tests", "tri_tests", "full_tests", "nodes", "leaves", "kernel_ms", "trace_ms", "trace_launches",
+                          "primary_ms", "bounce_ms", "slow_paths"):
+                    ctx.stats[k] += p.stats[k]
+            ctx.samples_done = k0 + n
+            if on_pass is not None and on_pass(ctx.samples_done, ctx) is False:
+                break
+        return ctx
+
     def quantize_device(self, s, rgba_ptr, npixels, rgb_ptr, stream_ptr=None):
         """write_png's `(c * 255.) as u8` on device memory (f32x4 -> u8x3), enqueued on the stream."""
         self._config(s)
