@@ -284,6 +284,38 @@ int rtmi_render_frame_multi(rtmi_scene_t* const* scenes, uint32_t nscenes, const
 int rtmi_trace(rtmi_scene_t* scene, uint64_t n, const float* orig4, const float* dir4,
                uint32_t* tri, float* t, uint32_t* face, rtmi_stats_t* stats);
 
+/* Per-ray debug records (the reference's Scene { debug_ctx, debug_en }, raytrace.rs:1297-1303, debug.rs): what the
+ * octree walk did for each ray, taken from the production walk itself (k_trace_record: the walk of rtmi_trace in a
+ * recording mode).  A leaf is named by its index in the `boxes` array rtmi_scene_create received (Scene.tree()'s
+ * numbering); the leaves of a ray are listed in visiting order, a leaf entered twice twice, so their triangle lists
+ * are the reference's `check_tris` and their sizes sum to the ray's tri_tests. */
+typedef struct rtmi_ray_record {
+    float orig[4], dir[4];   /* the ray as make_ray stores it (primary records: exactly what the renderer traces) */
+    uint32_t tri;            /* closest hit, 0 = miss (then t = 0, face = 0)                                      */
+    float t;
+    uint32_t face;           /* 0 front, 1 back, 2 edge front, 3 edge back (as rtmi_trace)                        */
+    uint32_t nleaves;        /* leaves visited = the reference's `leaves` counter for this ray                    */
+    uint64_t leaf_first;     /* offset of this ray's leaf list in leaf_ids                                        */
+    uint32_t box_tests, tri_tests, full_tests, nodes;  /* this ray's counters (its share of rtmi_stats_t)      */
+} rtmi_ray_record_t;
+
+/* rtmi_trace with a record per ray (recs: n entries).  Host buffers: these are diagnostics.  *leaf_total always receives
+ * the number of leaf ids of the call.  leaf_ids == NULL: records and total only (a size query); otherwise leaf_ids
+ * receives them (ray i's at recs[i].leaf_first), and leaf_cap < total is RTMI_ERR_INVALID with nothing written to
+ * leaf_ids and the size needed in the message.  stats: rays = n, the five work counters (the sums over the records)
+ * and kernel_ms.  RTMI_ERR_UNSUPPORTED for scenes k_trace_oct does not run (trivial one-leaf tree, generic tree,
+ * RTMI_OPT_GENERIC), for RTMI_OPT_BVH and RTMI_OPT_FAST, and for scenes with analytic spheres. */
+int rtmi_trace_records(rtmi_scene_t* scene, uint64_t n, const float* orig4, const float* dir4,
+                       rtmi_ray_record_t* recs, uint32_t* leaf_ids, uint64_t leaf_cap, uint64_t* leaf_total,
+                       rtmi_stats_t* stats);
+/* The same for the primary rays of sample `sample` of every pixel of rows [row0, row0+nrows): record i is pixel
+ * (row0 + i / width, i % width), its ray generated by the renderer's own ray generation, so its bits equal the
+ * renderer's.  vp->maxdepth is not consulted (the record describes the primary ray's trace).  sample >= spp and rows
+ * outside the frame are RTMI_ERR_INVALID. */
+int rtmi_primary_records(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
+                         uint32_t sample, rtmi_ray_record_t* recs, uint32_t* leaf_ids, uint64_t leaf_cap,
+                         uint64_t* leaf_total, rtmi_stats_t* stats);
+
 /* (c * 255.) as u8 per channel, RGB (raytrace.rs:1468-1473). */
 int rtmi_quantize(rtmi_scene_t* scene, const float* rgba_host, uint64_t npixels, uint8_t* rgb_host);
 /* Same on device memory, enqueued on `hip_stream`: lets a rank hand 3 bytes per pixel to the gather instead of 16. */

@@ -89,6 +89,18 @@ int rth_caster_walk_samples_device(rth_scene_t* s, uint32_t w, uint32_t h, const
                                    void* out_device, void* hip_stream, rtmi_stats_t* stats, double* wall_seconds);
 int rth_caster_trace(rth_scene_t* s, uint64_t n, const float* orig4, const float* dir4, uint32_t* tri, float* t,
                      uint32_t* face, rtmi_stats_t* stats);
+/* Per-ray records (rtmi_trace_records / rtmi_primary_records, same buffers and size-query idiom) on the scene's
+ * resident copy; the primary records use the caster's seed. */
+int rth_caster_trace_records(rth_scene_t* s, uint64_t n, const float* orig4, const float* dir4, rtmi_ray_record_t* recs,
+                             uint32_t* leaf_ids, uint64_t leaf_cap, uint64_t* leaf_total, rtmi_stats_t* stats);
+int rth_caster_primary_records(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                               uint32_t row0, uint32_t nrows, uint32_t sample, rtmi_ray_record_t* recs, uint32_t* leaf_ids,
+                               uint64_t leaf_cap, uint64_t* leaf_total, rtmi_stats_t* stats);
+/* Scene.debug_en, and Scene.debug as HipRayCaster::walk_rays_internal left it: *nrecs / *nleaf_ids always receive the
+ * sizes; recs (nrecs entries), pixel2 ((row, col) per record) and leaf_ids are filled when not NULL. */
+int rth_scene_set_debug(rth_scene_t* s, int on);
+int rth_scene_debug_records(rth_scene_t* s, rtmi_ray_record_t* recs, uint32_t* pixel2, uint32_t* leaf_ids, uint64_t* nrecs,
+                            uint64_t* nleaf_ids);
 /* Multi-GPU inside the process (rtmi_render_frame_multi): the caster keeps one resident copy of the scene per entry of
  * `devices` (an entry may repeat a device); entry 0 is the root that receives the bands.  With more than one entry
  * walk_rays (rth_caster_walk_rows over the whole image) and rth_caster_walk_frame_multi stripe the frame over them. */

@@ -43,7 +43,8 @@
 
 // layouts the language bindings mirror (rust_raytrace_amd/_ffi.py, INTEGRATION.md ffi.rs; tests/test_host_cpu.py)
 static_assert(sizeof(rtmi_stats_t) == 128 && sizeof(rtmi_tuning_t) == 48 && sizeof(rtmi_tile_t) == 16 && sizeof(rtmi_box_t) == 32 &&
-              sizeof(rtmi_triangle_t) == 104 && sizeof(rtmi_viewport_t) == 64 && sizeof(rtmi_sphere_t) == 40, "ABI struct layout changed");
+              sizeof(rtmi_triangle_t) == 104 && sizeof(rtmi_viewport_t) == 64 && sizeof(rtmi_sphere_t) == 40 &&
+              sizeof(rtmi_ray_record_t) == 72, "ABI struct layout changed");
 
 namespace rtmi {
 
@@ -808,6 +809,10 @@ struct rtmi_scene {
     std::vector<rtmi_triangle_t> htris;  // the records (host copy): the fast-mode BVH is rebuilt from them when corners arrive
     DevBuf<uint4> fnodes, oblocks;
     DevBuf<uint32_t> wlinks;
+    std::vector<uint32_t> leaf_box;  // OctForm::leafbox: leaf ids of k_trace_record -> box index
+    // rtmi_trace_records / rtmi_primary_records: per-ray counters, leaf-list offsets and leaf ids of the last call
+    DevBuf<uint32_t> rec_cnt, rec_ids;
+    DevBuf<unsigned long long> rec_first;
     // RTMI_OPT_BVH: SAH BVH over the triangles' bounding spheres (bvh_fast.hpp)
     DevBuf<float4> bnodes;
     DevBuf<uint4> bleaves;
@@ -950,6 +955,8 @@ struct OctForm {
     std::vector<uint4> fn;     // 2 records per inner box
     std::vector<uint4> ob;     // reference blocks, each DISTINCT leaf list once
     std::vector<uint32_t> wl;  // explicit block indices of FN_WIDE boxes
+    std::vector<uint32_t> leafbox;  // 8 per inner record: box index of its leaf child in each octant (~0u: none); the
+                                    // records of k_trace_record name a leaf (record << 3) | octant
     uint64_t nwide = 0;        // FN_WIDE boxes
     std::string why;           // empty: the tree is an exact octree
 };
@@ -1012,6 +1019,7 @@ static void build_oct_form(const rtmi_box_t* boxes, uint64_t nboxes, const uint3
     }
     if (ok) {
         hfn.assign(2 * ninner, make_uint4(0, 0, 0, 0));
+        f.leafbox.assign(8 * ninner, 0xFFFFFFFFu);
         for (uint64_t i = 0; i < nboxes && ok; i++) {
             const rtmi_box_t& b = boxes[i];
             if (b.is_leaf) continue;
@@ -1037,6 +1045,7 @@ static void build_oct_form(const rtmi_box_t* boxes, uint64_t nboxes, const uint3
                 // them + a byte offset per octant (new lists of one box are placed consecutively, in box order)
                 if (c.is_leaf) {
                     leafmask |= 1u << oct;
+                    f.leafbox[8 * (size_t)slot[i] + oct] = (uint32_t)(b.first + k);
                     first_block[oct & 7] = slot[b.first + k] & 0x7FFFFFFFu;
                     base_block = std::min(base_block, first_block[oct & 7]);
                 } else if (!have_inner) { base_inner = slot[b.first + k]; have_inner = true; }
@@ -1065,7 +1074,7 @@ static void build_oct_form(const rtmi_box_t* boxes, uint64_t nboxes, const uint3
     // k_trace_oct addresses its records with 32-bit byte offsets (ld_off32): 32 B per inner box and per triangle plane
     // record, 64 B per triangle edge record, 16 B per reference block; its stack keeps an inner box's record index in 22 bits
     if (ok && (ninner >= (1ull << 22) || ntris >= (1ull << 26) || hob.size() >= (1ull << 28))) { ok = false; why = "more than 2^22 inner boxes, or an array of the octree form would exceed 4 GiB"; }
-    if (!ok) { hfn.clear(); hob.clear(); hwl.clear(); f.nwide = 0; }
+    if (!ok) { hfn.clear(); hob.clear(); hwl.clear(); f.leafbox.clear(); f.nwide = 0; }
 }
 
 // LDS of an octree-walk launch: the counting build keeps 2 more memo words per lane (the list's plane and edge tests)
@@ -1217,6 +1226,7 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
                   (uint32_t)nboxes, (uint32_t)ntris, (uint32_t)matmap.size(), levels,
                   s->octree ? s->fnodes.p : nullptr, s->octree ? s->oblocks.p : nullptr, s->octree ? s->wlinks.p : nullptr, nullptr, 0u, boxes[0].len2, max_inner_depth + 1, (uint32_t)hob.size()};
     s->hmats = hm;
+    s->leaf_box = std::move(of.leafbox);
     if (s->octree) {
         // 2 words per level per lane (frame stack) + 3 per lane (leaf memo: key, t, tri | face; trace_oct.hpp)
         s->oct_lds = ((size_t)std::max<uint32_t>(1u, max_inner_depth) * 2 + 3) * 4 * 64;
@@ -1250,6 +1260,7 @@ int rtmi_scene_destroy(rtmi_scene_t* s) {
     }
     if (s->fork_ev) (void)hipEventDestroy(s->fork_ev);
     if (s->end_ev) (void)hipEventDestroy(s->end_ev);
+    s->rec_cnt.release(); s->rec_ids.release(); s->rec_first.release();
     s->tile.release(); s->acc.release(); s->qbytes.release(); s->mstage.release(); s->mframe.release();
     if (s->mstream) (void)hipStreamDestroy(s->mstream);
     if (!s->comms.empty()) { if (Rccl* r = rccl_api()) for (ncclComm_t c : s->comms) (void)r->CommDestroy(c); }
@@ -2001,6 +2012,176 @@ int rtmi_trace(rtmi_scene_t* s, uint64_t n, const float* orig4, const float* dir
     rc = read_stats(w, st, stats, ms, ms, 1);
     if (stats) stats->streams = 1;
     return rc;
+    RTMI_GUARD_END
+}
+
+// ---------------------------------------------------------------- per-ray records (k_trace_record, trace_oct.hpp W_RECORD)
+// Scenes and modes whose rays k_trace_oct<COUNT, false> traces; RTMI_OK or RTMI_ERR_UNSUPPORTED with the reason.  Host only.
+static int records_supported(const rtmi_scene* s) {
+    if (s->root_is_leaf) return fail(RTMI_ERR_UNSUPPORTED, "records: the tree is a single leaf (k_trace_linear), not an octree walk");
+    if (!s->octree) return fail(RTMI_ERR_UNSUPPORTED, "records: the tree is not an exact octree (" + s->why_generic + "), k_trace_oct does not run");
+    if (s->options & RTMI_OPT_GENERIC) return fail(RTMI_ERR_UNSUPPORTED, "records: RTMI_OPT_GENERIC selects the generic kernel");
+    if (s->options & RTMI_OPT_BVH) return fail(RTMI_ERR_UNSUPPORTED, "records: RTMI_OPT_BVH traces a BVH, not the octree");
+    if (s->options & RTMI_OPT_FAST) return fail(RTMI_ERR_UNSUPPORTED, "records: RTMI_OPT_FAST is not the reference's walk");
+    if (s->d.nspheres) return fail(RTMI_ERR_UNSUPPORTED, "records: the scene has analytic spheres (a flat list outside the tree)");
+    return RTMI_OK;
+}
+
+// The rays are in w.qo[0] / w.qd[0] and ctrl->count[0] = n on stream st.  Launch 1 records the counters of every ray; the
+// host scans the leaf counts into offsets; launch 2 (only when leaf_ids is given) walks the same rays again and writes
+// their leaf ids.  The walk is deterministic: launch 2 must find the counts of launch 1 again (checked).
+static int run_records(rtmi_scene* s, Work& w, hipStream_t st, uint64_t n, rtmi_ray_record_t* recs, uint32_t* leaf_ids,
+                       uint64_t leaf_cap, uint64_t* leaf_total, rtmi_stats_t* stats) {
+    HIPCHK(s->rec_cnt.ensure(5 * n));
+    OctArgs a{};
+    a.qo = w.qo[0].p; a.qd = w.qd[0].p; a.hit_tf = w.hit_tf.p; a.hit_t = w.hit_t.p; a.pass = 0;
+    a.vote_s = s->vote[0]; a.vote_l = s->vote[1];
+    const int refill = (int)s->tune.refill_min0, xcd = (int)(s->tune.xcd_aware % 3u);
+    s->active_streams = 1;
+    auto launch = [&](const RecArgs& ra) {
+        hipLaunchKernelGGL(k_trace_record, oct_grid(s), dim3(64), oct_launch_lds(s, true), st, s->d, a, w.ctrl.p, refill, xcd, ra);
+    };
+    HIPCHK(hipEventRecord(w.ev[0], st));
+    launch(RecArgs{s->rec_cnt.p, nullptr, nullptr, 0ull});
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(w.ev[1], st));
+    std::vector<uint32_t> cnt(5 * n), tf(n);
+    std::vector<float> ht(n);
+    std::vector<float4> ro(n), rd(n);
+    HIPCHK(hipMemcpyAsync(cnt.data(), s->rec_cnt.p, cnt.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(tf.data(), w.hit_tf.p, n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(ht.data(), w.hit_t.p, n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(ro.data(), w.qo[0].p, n * 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(rd.data(), w.qd[0].p, n * 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
+    std::vector<unsigned long long> first(n);
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n; i++) { first[i] = total; total += cnt[5 * i + 4]; }
+    *leaf_total = total;
+    if (leaf_ids && leaf_cap < total)
+        return fail(RTMI_ERR_INVALID, "leaf_ids holds " + std::to_string(leaf_cap) + " ids, the call needs " + std::to_string(total));
+    if (leaf_ids && total > 0) {
+        HIPCHK(s->rec_first.ensure(n));
+        HIPCHK(s->rec_ids.ensure(total));
+        HIPCHK(hipMemcpyAsync(s->rec_first.p, first.data(), n * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(w.ctrl.p, 0, sizeof(DCtrl), st));
+        hipLaunchKernelGGL(k_set_count, dim3(1), dim3(1), 0, st, w.ctrl.p, (uint32_t)n);
+        HIPCHK(hipEventRecord(w.ev[0], st));
+        launch(RecArgs{s->rec_cnt.p, s->rec_first.p, s->rec_ids.p, (unsigned long long)total});
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(w.ev[1], st));
+        std::vector<uint32_t> ids(total), cnt2(5 * n);
+        HIPCHK(hipMemcpyAsync(ids.data(), s->rec_ids.p, total * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(cnt2.data(), s->rec_cnt.p, cnt2.size() * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        float ms2 = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms2, w.ev[0], w.ev[1]));
+        ms += ms2;
+        if (cnt2 != cnt) return fail(RTMI_ERR_DEVICE, "records: the leaf-id launch walked differently from the counting launch");
+        for (uint64_t k = 0; k < total; k++) {  // (inner record << 3) | octant -> index in rtmi_scene_create's boxes
+            const uint64_t j = ids[k];
+            if (j >= s->leaf_box.size() || s->leaf_box[j] == 0xFFFFFFFFu)
+                return fail(RTMI_ERR_DEVICE, "records: leaf id " + std::to_string(j) + " names no leaf of the tree");
+            ids[k] = s->leaf_box[j];
+        }
+        memcpy(leaf_ids, ids.data(), total * 4);
+    }
+    if (stats) memset(stats, 0, sizeof(*stats));
+    rtmi_stats_t sum{};
+    for (uint64_t i = 0; i < n; i++) {
+        rtmi_ray_record_t& r = recs[i];
+        memcpy(r.orig, &ro[i], 16);
+        memcpy(r.dir, &rd[i], 16);
+        r.tri = tf[i] & 0x3FFFFFFFu;
+        r.face = tf[i] >> 30;
+        r.t = ht[i];
+        const uint32_t* c = &cnt[5 * i];
+        r.box_tests = c[0]; r.tri_tests = c[1]; r.full_tests = c[2]; r.nodes = c[3]; r.nleaves = c[4];
+        r.leaf_first = first[i];
+        sum.box_tests += c[0]; sum.tri_tests += c[1]; sum.full_tests += c[2]; sum.nodes += c[3]; sum.leaves += c[4];
+    }
+    if (stats) {
+        *stats = sum;
+        stats->rays = n;
+        stats->kernel_ms = ms; stats->trace_ms = ms;
+        stats->trace_launches = leaf_ids && total > 0 ? 2u : 1u;
+        stats->streams = 1;
+    }
+    return RTMI_OK;
+}
+
+int rtmi_trace_records(rtmi_scene_t* s, uint64_t n, const float* orig4, const float* dir4, rtmi_ray_record_t* recs,
+                       uint32_t* leaf_ids, uint64_t leaf_cap, uint64_t* leaf_total, rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
+    if (!leaf_total) return fail(RTMI_ERR_INVALID, "leaf_total is NULL");
+    *leaf_total = 0;
+    if (n == 0) return RTMI_OK;
+    if (!orig4 || !dir4) return fail(RTMI_ERR_INVALID, "NULL rays");
+    if (!recs) return fail(RTMI_ERR_INVALID, "recs is NULL");
+    if (n >= (1ull << 31)) return fail(RTMI_ERR_UNSUPPORTED, "more than 2^31 rays per call");
+    int rc = records_supported(s);
+    if (rc != RTMI_OK) return rc;
+    RTMI_GUARD_BEGIN
+    (void)hipGetLastError();
+    HIPCHK(hipSetDevice(s->device));
+    Work& w = s->w[0];
+    rc = ensure_workspace(w, (size_t)n, 1);
+    if (rc != RTMI_OK) return rc;
+    hipStream_t st = s->istream[0];
+    HIPCHK(hipMemcpyAsync(w.qo[0].p, orig4, n * 16, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(w.qd[0].p, dir4, n * 16, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(w.ctrl.p, 0, sizeof(DCtrl), st));
+    hipLaunchKernelGGL(k_set_count, dim3(1), dim3(1), 0, st, w.ctrl.p, (uint32_t)n);
+    HIPCHK(hipGetLastError());
+    return run_records(s, w, st, n, recs, leaf_ids, leaf_cap, leaf_total, stats);
+    RTMI_GUARD_END
+}
+
+int rtmi_primary_records(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
+                         uint32_t sample, rtmi_ray_record_t* recs, uint32_t* leaf_ids, uint64_t leaf_cap,
+                         uint64_t* leaf_total, rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!s || !vp) return fail(RTMI_ERR_INVALID, "NULL argument (scene or viewport)");
+    if (!leaf_total) return fail(RTMI_ERR_INVALID, "leaf_total is NULL");
+    *leaf_total = 0;
+    if (vp->width == 0 || vp->height == 0) return fail(RTMI_ERR_INVALID, "empty viewport");
+    if (vp->samples_per_pixel == 0) return fail(RTMI_ERR_INVALID, "samples_per_pixel must be >= 1");
+    if (sample >= vp->samples_per_pixel) return fail(RTMI_ERR_INVALID, "sample must be < samples_per_pixel");
+    if ((uint64_t)row0 + nrows > vp->height) return fail(RTMI_ERR_INVALID, "row range outside the viewport");
+    if (nrows == 0) return RTMI_OK;
+    if (!recs) return fail(RTMI_ERR_INVALID, "recs is NULL");
+    if ((uint64_t)vp->width * vp->height >= (1ull << 32)) return fail(RTMI_ERR_UNSUPPORTED, "more than 2^32 pixels");
+    const uint64_t n = (uint64_t)nrows * vp->width;
+    if (n >= (1ull << 31)) return fail(RTMI_ERR_UNSUPPORTED, "more than 2^31 rays per call");
+    if (sample & RTMI_KEY_JITTER) return fail(RTMI_ERR_UNSUPPORTED, "sample above 2^31");
+    int rc = records_supported(s);
+    if (rc != RTMI_OK) return rc;
+    RTMI_GUARD_BEGIN
+    (void)hipGetLastError();
+    HIPCHK(hipSetDevice(s->device));
+    Work& w = s->w[0];
+    rc = ensure_workspace(w, (size_t)n, 1);
+    if (rc != RTMI_OK) return rc;
+    hipStream_t st = s->istream[0];
+    // the rows as one tile of one stream, sample `sample` of the frame's spp: k_gen_samples makes the renderer's rays
+    DView dv;
+    dv.orig = mk(vp->orig[0], vp->orig[1], vp->orig[2]);
+    dv.cam = mk(vp->cam[0], vp->cam[1], vp->cam[2]);
+    dv.vu = mk(vp->vu[0], vp->vu[1], vp->vu[2]);
+    dv.vv = mk(vp->vv[0], vp->vv[1], vp->vv[2]);
+    dv.width = vp->width; dv.height = vp->height; dv.maxdepth = vp->maxdepth; dv.spp = 1;
+    dv.row0 = row0; dv.stripe_rows = nrows; dv.stripe_step = 0;
+    view_set_sampling(dv, sample, vp->samples_per_pixel);
+    dv.sub_mul = 1; dv.sub_off = 0;
+    view_set_divisors(dv);
+    HIPCHK(hipMemsetAsync(w.ctrl.p, 0, sizeof(DCtrl), st));
+    hipLaunchKernelGGL(k_gen_samples, dim3((unsigned)(s->num_cu * 8)), dim3(256), 0, st, dv, seed, 0u, (uint32_t)n, w.qo[0].p, w.qd[0].p,
+                       w.qpath[0].p, w.ctrl.p);
+    HIPCHK(hipGetLastError());
+    return run_records(s, w, st, n, recs, leaf_ids, leaf_cap, leaf_total, stats);
     RTMI_GUARD_END
 }
 

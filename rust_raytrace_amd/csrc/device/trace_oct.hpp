@@ -74,11 +74,15 @@ enum : uint32_t { M_IDLE = 0, M_SELECT = 1, M_LEAF = 2, M_SHADE = 3 };
 //                              next bounce ray, until the path ends (the recursion project_ray -> color_ray -> project_ray,
 //                              raytrace.rs:1233-1251, :1256-1295, without pass boundaries).  Such a ray runs at the speed
 //                              of a lone lane while the ordinary passes go on beside it on their own stream.
+//   W_RECORD   k_trace_record  W_TRACE's queue and exact walk (COUNT, not FAST), and per ray a record of what the walk did:
+//                              its work counters (cnt[] from the moment the lane takes the ray until it finishes it) and,
+//                              when RecArgs::lids is given, the leaves it entered in visiting order, each as
+//                              (inner record << 3) | octant (rtmi_trace_records / rtmi_primary_records)
 // Shading in the path kernels is a third step kind ("exchange"): finished lanes wait in M_SHADE until `refill_min` lanes
 // are finished or idle (or nothing else is left to do), then they are shaded together and, in the same step, every lane
 // without a ray takes one from the queue.  The arithmetic per path is k_shade's (same device functions), so the image is
 // bit-identical; only which lane evaluates it, and when, differs.
-enum : int { W_TRACE = 0, W_PRIMARY = 1, W_SLOW = 2 };
+enum : int { W_TRACE = 0, W_PRIMARY = 1, W_SLOW = 2, W_RECORD = 3 };
 
 struct OctArgs {
     // W_TRACE
@@ -96,6 +100,15 @@ struct OctArgs {
     // traces their reflections itself (0: never)
     float4* b2qo; float4* b2qd; uint32_t* b2qpath;
     int minpl;
+};
+
+// W_RECORD's outputs, per queued ray i: rcnt[5 i .. 5 i + 4] = box_tests, tri_tests, full_tests, nodes, leaves of that ray;
+// lids (null: counts only) receives its leaf ids at [lfirst[i], lfirst[i] + leaves), never at or past lcap
+struct RecArgs {
+    uint32_t* rcnt;
+    const unsigned long long* lfirst;
+    uint32_t* lids;
+    unsigned long long lcap;
 };
 
 // Frame of an inner box: node = index of its record; w = visited octants (bits 0-7) | O_DONE | O_HAS;
@@ -198,12 +211,14 @@ __host__ __device__ inline bool packet_culls(const Packet& p, float4 p0, float4 
 
 template <bool COUNT, bool FAST, int MODE, bool PROG = false>
 __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCtrl* __restrict__ ctrl, uint32_t* __restrict__ lds,
-                                         int refill_min, int xcd_aware) {
+                                         int refill_min, int xcd_aware, const RecArgs& rec = RecArgs{}) {
     const int lane = threadIdx.x;  // one wave per block
+    // rays from the queue of pass `a.pass`, closest hit to hit_tf / hit_t (W_RECORD is W_TRACE with a record per ray)
+    constexpr bool QUEUE = MODE == W_TRACE || MODE == W_RECORD;
     constexpr int NT = 64;
     // which queue of the control block this launch drains: W_TRACE pass `pass`, W_PRIMARY the implicit queue of all paths
     // of the batch (slot 0); W_SLOW does not use it (its launch drains a range of the slow-path queue)
-    const int pass = MODE == W_TRACE ? a.pass : 0;
+    const int pass = QUEUE ? a.pass : 0;
     const uint32_t count = MODE == W_PRIMARY ? a.npaths : (MODE == W_SLOW ? ctrl->shi[a.slow_k] : ctrl->count[pass]);
     // "Rays": every queued ray of this launch (the slow path counts its rays one by one, below)
     if (MODE != W_SLOW && blockIdx.x == 0 && lane == 0) atomicAdd(&ctrl->rays, (unsigned long long)count);
@@ -243,6 +258,9 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     bool ghave = false;          // running best over the ray's leaf results
     float gt = 0.f;
     uint32_t gtf = 0;
+    // W_RECORD: the lane's counters when it took its ray, and where its next leaf id goes
+    uint32_t rc0[5] = {0, 0, 0, 0, 0};
+    unsigned long long lcur = 0;
     uint32_t lblock = 0;
     bool lhave = false;
     float lt = 0.f;
@@ -280,10 +298,10 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     for (;;) {
         const unsigned long long m_idle = __ballot(mode == M_IDLE);
         // lanes whose ray is finished and waits to be shaded (path kernels only)
-        const unsigned long long m_shade = MODE == W_TRACE ? 0ull : __ballot(mode == M_SHADE);
+        const unsigned long long m_shade = QUEUE ? 0ull : __ballot(mode == M_SHADE);
         // lanes the exchange step would serve (the slow path keeps one path per wave: only lane 0 ever takes a ray)
         const unsigned long long m_x = m_shade | (exhausted ? 0ull : (MODE == W_SLOW ? (m_idle & 1ull) : m_idle));
-        if (MODE == W_TRACE ? (m_idle == ~0ull && exhausted) : ((m_idle | m_shade) == ~0ull && m_x == 0ull)) break;
+        if (QUEUE ? (m_idle == ~0ull && exhausted) : ((m_idle | m_shade) == ~0ull && m_x == 0ull)) break;
         if (m_x != 0ull && (__popcll(m_x) >= refill_min || (m_idle | m_shade) == ~0ull)) {
             // ---- exchange step: finished rays are shaded, lanes without a ray take consecutive queued rays
             const unsigned long long t_r0 = COUNT ? __builtin_amdgcn_s_memtime() : 0ull;
@@ -292,7 +310,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
             float4 no = make_float4(0.f, 0.f, 0.f, 0.f), nd = make_float4(0.f, 0.f, 1.f, 0.f);
             const uint32_t pth = MODE == W_PRIMARY ? path & 0x7FFFFFFFu : path, bnc = MODE == W_PRIMARY ? path >> 31 : bounce;
             uint32_t npath = pth, nbounce = bnc;
-            if (MODE != W_TRACE) {
+            if (!QUEUE) {
                 bool push = false;  // W_PRIMARY: the path goes on -> its bounce ray is queued for pass bounce + 1
                 bool mirror = false;  // ... through a Reflective surface
                 RayV nr;
@@ -370,7 +388,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                                 reinterpret_cast<uint32_t*>(hptr(2)));
                 }
             }
-            const unsigned long long m_want = MODE == W_TRACE ? m_idle : (MODE == W_SLOW ? (__ballot(mode == M_IDLE) & 1ull) : __ballot(mode == M_IDLE));
+            const unsigned long long m_want = QUEUE ? m_idle : (MODE == W_SLOW ? (__ballot(mode == M_IDLE) & 1ull) : __ballot(mode == M_IDLE));
             if (MODE == W_SLOW) {
                 if (!exhausted && m_want != 0ull) {  // lane 0 takes the next entry of this launch's range
                     uint32_t i = 0;
@@ -425,6 +443,11 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                             ghave = false; gt = 0.f; gtf = 0;
                             if (MEMO) memo[0] = 0xFFFFFFFFu;  // no block index (< 2^28)
                             mode = M_SELECT;
+                            if constexpr (MODE == W_RECORD) {  // this ray's counters start here; its leaf list at lfirst[i]
+#pragma unroll
+                                for (int k = 0; k < 5; k++) rc0[k] = (uint32_t)cnt[k];
+                                lcur = rec.lids ? rec.lfirst[i] : 0ull;
+                            }
                         }
                     }
                 }
@@ -437,7 +460,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                 r = make_rayk(bo, bd);
             }
             if (MODE == W_PRIMARY) pk = a.pcull ? PK_NEW : PK_OFF;  // every refill of k_path_primary is whole-wave
-            if (MODE != W_TRACE && start) {  // one place where a path kernel's lane takes a ray: bounce in place, or refill
+            if (!QUEUE && start) {  // one place where a path kernel's lane takes a ray: bounce in place, or refill
                 if (MODE != W_SLOW) r = make_rayk(no, nd);
                 path = MODE == W_PRIMARY ? npath | (nbounce << 31) : npath; bounce = nbounce;
                 fnode = 0; fw = 0; ft = 0.f; lvl = 0;
@@ -476,7 +499,11 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                     }
                 }
                 if (fw & O_DONE) {  // the root frame is finished: the ray is
-                    if (MODE == W_TRACE) {
+                    if (QUEUE) {
+                        if constexpr (MODE == W_RECORD) {
+#pragma unroll
+                            for (int k = 0; k < 5; k++) rec.rcnt[(size_t)ridx * 5u + k] = (uint32_t)cnt[k] - rc0[k];
+                        }
                         a.hit_tf[ridx] = ghave ? gtf : 0u;
                         a.hit_t[ridx] = ghave ? gt : 0.f;
                         mode = M_IDLE;
@@ -549,6 +576,10 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                         if (leafmask & bit) {
                             // first block of this leaf child: base + byte `octant` of the offsets
                             const uint32_t oct = (uint32_t)__ffs((int)bit) - 1u;
+                            if constexpr (MODE == W_RECORD) {  // every leaf entered, a leaf-memo hit included (its list counts again)
+                                if (rec.lids && lcur < rec.lcap) rec.lids[lcur] = (fnode << 3) | oct;
+                                lcur++;
+                            }
                             if (q0.w & FN_WIDE) lblock = sc.wlinks[(size_t)q1.y * 8u + oct];  // rare: explicit indices
                             else lblock = q1.y + __builtin_amdgcn_ubfe(oct < 4u ? q1.z : q1.w, (oct & 3u) * 8u, 8u);
                             if (COUNT) cnt[4]++;
@@ -799,6 +830,12 @@ __global__ void __launch_bounds__(64, RTMI_TRACE_WAVES) k_trace_oct(DScene sc, O
 #ifndef RTMI_PATH_WAVES
 #define RTMI_PATH_WAVES 6
 #endif
+// Per-ray records of the exact walk (rtmi_trace_records / rtmi_primary_records): k_trace_oct<true, false> plus RecArgs
+__global__ void __launch_bounds__(64, RTMI_TRACE_WAVES) k_trace_record(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min, int xcd_aware,
+                                                                       RecArgs rec) {
+    extern __shared__ uint32_t lds[];
+    oct_walk<true, false, W_RECORD>(sc, a, ctrl, lds, refill_min, xcd_aware, rec);
+}
 template <bool COUNT, bool FAST>
 __global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_primary(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min, int xcd_aware) {
     extern __shared__ uint32_t lds[];

@@ -270,6 +270,41 @@ int rth_caster_trace(rth_scene_t* s, uint64_t n, const float* o4, const float* d
     });
 }
 
+int rth_caster_trace_records(rth_scene_t* s, uint64_t n, const float* o4, const float* d4, rtmi_ray_record_t* recs, uint32_t* leaf_ids,
+                             uint64_t leaf_cap, uint64_t* leaf_total, rtmi_stats_t* stats) {
+    return guarded([&] {
+        rtmi_scene_t* h = caster_of(s).resident(s->scene);
+        if (rtmi_trace_records(h, n, o4, d4, recs, leaf_ids, leaf_cap, leaf_total, stats) != RTMI_OK)
+            throw std::runtime_error(std::string("rtmi_trace_records: ") + rtmi_last_error());
+    });
+}
+int rth_caster_primary_records(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                               uint32_t row0, uint32_t nrows, uint32_t sample, rtmi_ray_record_t* recs, uint32_t* leaf_ids,
+                               uint64_t leaf_cap, uint64_t* leaf_total, rtmi_stats_t* stats) {
+    return guarded([&] {
+        const rtmi_viewport_t av = to_abi(vp_from(w, h, vp12, maxdepth, spp));
+        HipRayCaster& c = caster_of(s);
+        if (rtmi_primary_records(c.resident(s->scene), &av, c.seed, row0, nrows, sample, recs, leaf_ids, leaf_cap, leaf_total, stats) != RTMI_OK)
+            throw std::runtime_error(std::string("rtmi_primary_records: ") + rtmi_last_error());
+    });
+}
+int rth_scene_set_debug(rth_scene_t* s, int on) {
+    return guarded([&] { s->scene.debug_en = on != 0; });
+}
+int rth_scene_debug_records(rth_scene_t* s, rtmi_ray_record_t* recs, uint32_t* pixel2, uint32_t* leaf_ids, uint64_t* nrecs,
+                            uint64_t* nleaf_ids) {
+    return guarded([&] {
+        if (!nrecs || !nleaf_ids) throw std::runtime_error("NULL size argument");
+        const RayRecords& d = s->scene.debug;
+        *nrecs = d.recs.size();
+        *nleaf_ids = d.leaf_ids.size();
+        if (recs && !d.recs.empty()) memcpy(recs, d.recs.data(), d.recs.size() * sizeof(rtmi_ray_record_t));
+        if (leaf_ids && !d.leaf_ids.empty()) memcpy(leaf_ids, d.leaf_ids.data(), d.leaf_ids.size() * 4);
+        if (pixel2)
+            for (size_t i = 0; i < d.pixel.size(); i++) { pixel2[2 * i] = d.pixel[i].first; pixel2[2 * i + 1] = d.pixel[i].second; }
+    });
+}
+
 int rth_caster_quantize_device(rth_scene_t* s, const void* rgba_device, uint64_t npixels, void* rgb_device, void* hip_stream) {
     return guarded([&] {
         if (rtmi_quantize_device(caster_of(s).resident(s->scene), rgba_device, npixels, rgb_device, hip_stream) != RTMI_OK)

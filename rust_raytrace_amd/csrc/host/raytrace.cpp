@@ -733,9 +733,54 @@ void HipRayCaster::walk_frame_multi(const Viewport& v, const Scene& s, void* dat
     if (per_device) *per_device = st;
 }
 
+// Both entry points: size query, then the fill (the walk runs twice more; these are diagnostics)
+template <typename Call>
+static RayRecords records_of(Call&& call, const char* what) {
+    RayRecords r;
+    uint64_t total = 0;
+    if (call(r, nullptr, 0ull, &total) != RTMI_OK) throw std::runtime_error(std::string(what) + ": " + rtmi_last_error());
+    r.leaf_ids.resize(total);
+    if (total && call(r, r.leaf_ids.data(), total, &total) != RTMI_OK) throw std::runtime_error(std::string(what) + ": " + rtmi_last_error());
+    return r;
+}
+
+RayRecords HipRayCaster::trace_records(const Scene& s, size_t n, const float* orig4, const float* dir4, rtmi_stats_t* stats) {
+    rtmi_scene_t* h = resident(s);
+    return records_of([&](RayRecords& r, uint32_t* ids, uint64_t cap, uint64_t* total) {
+        r.recs.resize(n);
+        return rtmi_trace_records(h, n, orig4, dir4, r.recs.data(), ids, cap, total, stats);
+    }, "rtmi_trace_records");
+}
+
+RayRecords HipRayCaster::primary_records(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample,
+                                         rtmi_stats_t* stats) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    RayRecords out = records_of([&](RayRecords& r, uint32_t* ids, uint64_t cap, uint64_t* total) {
+        r.recs.resize(nrows * v.width);
+        return rtmi_primary_records(h, &av, seed, (uint32_t)row0, (uint32_t)nrows, sample, r.recs.data(), ids, cap, total, stats);
+    }, "rtmi_primary_records");
+    out.pixel.resize(out.recs.size());
+    for (size_t i = 0; i < out.pixel.size(); i++) out.pixel[i] = {(uint32_t)(row0 + i / v.width), (uint32_t)(i % v.width)};
+    return out;
+}
+
 // DefaultRayCaster fans rows out over `threads` CPU threads (raytrace.rs:1175-1196); here the fan-out is over the
 // caster's devices, inside the library.  `threads` is ignored like the reference's CudaRayCaster does.
-void HipRayCaster::walk_rays_internal(const Viewport& v, const Scene& s, Color* data, size_t /*threads*/, ProgressCtx& progress) {
+// With s.debug_en (and maxdepth > 0, where the reference traces rays at all) the frame renders exactly as without it, and
+// s.debug receives the primary records of sample 0 of every pixel, taken first: an unsupported scene throws before
+// anything is rendered.
+void HipRayCaster::walk_rays_internal(const Viewport& v, const Scene& s, Color* data, size_t threads, ProgressCtx& progress) {
+    if (s.debug_en && v.maxdepth > 0) {
+        RayRecords rec = primary_records(v, s, 0, v.height, 0);
+        render_frame(v, s, data, threads, progress);
+        s.debug = std::move(rec);
+        return;
+    }
+    render_frame(v, s, data, threads, progress);
+}
+
+void HipRayCaster::render_frame(const Viewport& v, const Scene& s, Color* data, size_t /*threads*/, ProgressCtx& progress) {
     if (devices_.size() > 1) { walk_frame_multi(v, s, data, nullptr, 0, 0, progress); return; }
     if (!on_progress_) { walk_rows(v, s, 0, v.height, data, progress); return; }
     // progress while rendering: one render call and one tuple per row band (raytrace.rs:1411, :1429-1435)

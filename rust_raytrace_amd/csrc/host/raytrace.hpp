@@ -113,11 +113,24 @@ struct Sphere {
     SurfaceKind surface;
 };
 
-// raytrace.rs:1297-1303 (debug_ctx / debug_en: out of scope)
+// Per-ray records of the octree walk (rtmi_trace_records / rtmi_primary_records), the reference's DebugCtx (debug.rs):
+// record i's leaves are leaf_ids[recs[i].leaf_first .. + recs[i].nleaves), indices into Scene.boxes.boxes.  pixel[i] =
+// (row, col) of record i for primary records; empty for explicit rays.
+struct RayRecords {
+    std::vector<rtmi_ray_record_t> recs;
+    std::vector<uint32_t> leaf_ids;
+    std::vector<std::pair<uint32_t, uint32_t>> pixel;
+};
+
+// raytrace.rs:1297-1303
 struct Scene {
     std::vector<Triangle> tris;
     BoundingBox boxes;
     std::vector<Sphere> spheres;  // analytic spheres: a flat list tested against every ray after the box tree
+    // debug_en: walk_rays also records sample 0's primary ray of every pixel into `debug` (the reference's debug_ctx, which
+    // walk_rays fills through a &Scene: hence mutable).  Octree scenes only; walk_rays throws before rendering otherwise.
+    bool debug_en = false;
+    mutable RayRecords debug;
     // Bumped by touch(): a HipRayCaster keeps the uploaded copy of a Scene resident and re-uploads when the
     // generation it saw differs.  Code that edits tris/boxes in place must call touch() afterwards.
     uint64_t generation = 0;
@@ -185,6 +198,11 @@ public:
     void walk_samples_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
                              void* accum_device, void* out_device, void* hip_stream, ProgressCtx& progress);
     void set_options(uint32_t opts) { options_ = opts; }
+    // Per-ray records of the production walk (rtmi_trace_records / rtmi_primary_records, on the first device): explicit
+    // rays (n x 4 floats each), or sample `sample` of every pixel of rows [row0, row0 + nrows).  Throws on unsupported scenes.
+    RayRecords trace_records(const Scene& s, size_t n, const float* orig4, const float* dir4, rtmi_stats_t* stats = nullptr);
+    RayRecords primary_records(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample,
+                               rtmi_stats_t* stats = nullptr);
     // Progress while rendering, as DefaultRayCaster reports it (raytrace.rs:1411, :1429-1435 send one tuple per finished
     // row / per 10 k rays: (thread, row, pixels done, {"Rays": n}); progress.rs:95-141 draws from them).  With a callback
     // set, walk_rays_internal renders the frame in `bands` row bands (default 16) and calls it after each one with
@@ -214,6 +232,7 @@ private:
     ProgressFn on_progress_;
     size_t progress_bands_ = 16;
     void apply_settings();
+    void render_frame(const Viewport& v, const Scene& s, Color* data, size_t threads, ProgressCtx& progress);  // walk_rays_internal without debug_en
 };
 
 void flatten_triangles(const std::vector<Triangle>& tris, std::vector<rtmi_triangle_t>& out);

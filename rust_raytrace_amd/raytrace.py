@@ -97,6 +97,24 @@ class Scene:
 
     def __init__(self, with_dummy=True):
         self.h = C.c_void_p(_ffi.lib().rth_scene_new(1 if with_dummy else 0))
+        self._debug_en = False
+        self._debug = None
+
+    # --- Scene.debug_en / debug_ctx (raytrace.rs:1297-1303)
+    @property
+    def debug_en(self):
+        """With debug_en set, HipRayCaster.walk_rays also records sample 0's primary ray of every pixel (the reference's
+        debug_ctx); debug_records() returns them.  Octree scenes only: walk_rays raises before rendering otherwise."""
+        return self._debug_en
+
+    @debug_en.setter
+    def debug_en(self, on):
+        _chk(_ffi.lib().rth_scene_set_debug(self.h, 1 if on else 0))
+        self._debug_en = bool(on)
+
+    def debug_records(self):
+        """The RayRecords of the last walk_rays with debug_en set (None before one)."""
+        return self._debug
 
     def __del__(self):
         if getattr(self, "h", None) and _ffi is not None:  # module globals are None while the interpreter shuts down
@@ -183,6 +201,76 @@ class Scene:
                     maxdepth=int(topo[:, 3].max()) if len(topo) else 0)
 
 
+# rtmi_ray_record_t (include/rtmi.h) as a numpy record; the natural offsets of these fields are the C layout (72 B)
+REC_DTYPE = np.dtype([("orig", "<f4", (4,)), ("dir", "<f4", (4,)), ("tri", "<u4"), ("t", "<f4"), ("face", "<u4"), ("nleaves", "<u4"),
+                      ("leaf_first", "<u8"), ("box_tests", "<u4"), ("tri_tests", "<u4"), ("full_tests", "<u4"), ("nodes", "<u4")])
+assert REC_DTYPE.itemsize == C.sizeof(_ffi.RayRecord)
+
+
+def format_f32(x):
+    """A float32 as Rust's `{}` prints an f32: the shortest digits that round-trip, never an exponent (1.0 -> "1",
+    1e-10 -> "0.0000000001", -0.0 -> "-0", NaN -> "NaN", infinities -> "inf" / "-inf")."""
+    x = np.float32(x)
+    if np.isnan(x):
+        return "NaN"
+    if np.isinf(x):
+        return "inf" if x > 0 else "-inf"
+    return np.format_float_positional(x, unique=True, trim="-")
+
+
+class RayRecords:
+    """Per-ray records of the octree walk (rtmi_trace_records / rtmi_primary_records): numpy arrays orig, dir ((n, 4)
+    f32), tri, t, face, nleaves, leaf_first, leaf_ids, counters (dict of per-ray arrays: box_tests, tri_tests, full_tests,
+    nodes, leaves) and, for primary records, pixel ((n, 2): row, col).  Leaf ids index Scene.tree()'s boxes."""
+
+    def __init__(self, recs, leaf_ids, pixel=None, stats=None):
+        recs = np.asarray(recs, REC_DTYPE)
+        self.orig, self.dir = recs["orig"].copy(), recs["dir"].copy()
+        self.tri, self.t, self.face = recs["tri"].copy(), recs["t"].copy(), recs["face"].copy()
+        self.nleaves, self.leaf_first = recs["nleaves"].copy(), recs["leaf_first"].copy()
+        self.leaf_ids = np.asarray(leaf_ids, np.uint32).copy()
+        self.counters = {k: recs[k].copy() for k in ("box_tests", "tri_tests", "full_tests", "nodes")}
+        self.counters["leaves"] = self.nleaves.copy()
+        self.pixel = None if pixel is None else np.asarray(pixel, np.uint32).reshape(-1, 2)
+        self.stats = stats
+
+    def __len__(self):
+        return len(self.tri)
+
+    def leaves(self, i):
+        """The leaves ray i entered, in visiting order (a leaf entered twice is listed twice)."""
+        a = int(self.leaf_first[i])
+        return self.leaf_ids[a:a + int(self.nleaves[i])]
+
+    @staticmethod
+    def _lists(scene):
+        _, topo, refs = scene.tree()
+        return topo, refs
+
+    def check_tris(self, i, scene, _tree=None):
+        """The reference's check_tris of ray i: the sorted, de-duplicated union of its leaves' triangle lists."""
+        topo, refs = _tree if _tree is not None else self._lists(scene)
+        parts = [refs[topo[b, 0]:topo[b, 0] + topo[b, 1]] for b in self.leaves(i)]
+        return np.unique(np.concatenate(parts)) if parts else np.zeros(0, np.uint32)
+
+    def write_csv(self, f, scene):
+        """The reference's debug CSV (main.rs writes it as debug_*.csv): one line per pixel in (row, col) order,
+        `row;col;ox,oy,oz;dx,dy,dz;tri;t;i1,i2,...` after the header.  An empty check_tris is an empty field (the
+        reference panics there).  f: a path or a text file object."""
+        if self.pixel is None:
+            raise ValueError("write_csv needs primary records (a pixel per record)")
+        if isinstance(f, str):
+            with open(f, "w") as fh:
+                return self.write_csv(fh, scene)
+        tree = self._lists(scene)
+        f.write("Pixel_x;Pixel_y;ray_p;ray_v;tri_hit;hit_t;check_tris\n")
+        for i in np.lexsort((self.pixel[:, 1], self.pixel[:, 0])):
+            p = ",".join(format_f32(x) for x in self.orig[i, :3])
+            d = ",".join(format_f32(x) for x in self.dir[i, :3])
+            ct = ",".join(str(int(x)) for x in self.check_tris(i, scene, tree))
+            f.write(f"{int(self.pixel[i, 0])};{int(self.pixel[i, 1])};{p};{d};{int(self.tri[i])};{format_f32(self.t[i])};{ct}\n")
+
+
 class ProgressCtx:
     """What progress.rs:157-184 reports."""
 
@@ -233,7 +321,17 @@ class HipRayCaster:
         """progress: callable(thread, row, pixels, stats) -- what DefaultRayCaster sends over its channel per finished row
         (raytrace.rs:1411, :1429-1435).  With a callback (or show_progress=True, which prints one line per band like the
         reference's TUI redraw) the frame is rendered in `bands` row bands, one render call and one tuple each; same image, a
-        few per cent slower than in one piece (a band's launches do not overlap the next band's)."""
+        few per cent slower than in one piece (a band's launches do not overlap the next band's).
+        With s.debug_en (and maxdepth > 0) the same image is rendered and s.debug_records() receives the primary records of
+        sample 0 of every pixel, taken first: an unsupported scene raises before anything is rendered."""
+        if s.debug_en and v.maxdepth > 0:
+            rec = self.primary_records(v, s, 0, v.height, 0)
+            ctx = self._walk_rays(v, s, data, show_progress, progress, bands)
+            s._debug = rec
+            return ctx
+        return self._walk_rays(v, s, data, show_progress, progress, bands)
+
+    def _walk_rays(self, v, s, data, show_progress, progress, bands):
         if self.devices and len(self.devices) > 1:
             return self.walk_frame_multi(v, s, data)
         if progress is None and not show_progress:
@@ -390,6 +488,35 @@ class HipRayCaster:
         st = _ffi.Stats()
         _chk(_ffi.lib().rth_caster_trace(s.h, n, _p(o4), _p(d4), _p(tri), _p(t), _p(face), C.byref(st)))
         return tri, t, face, st.as_dict()
+
+    def _records(self, n, call, pixel=None):
+        """Size query, then the fill (rth_caster_*_records)"""
+        recs = np.zeros(n, REC_DTYPE)
+        total, st = C.c_uint64(0), _ffi.Stats()
+        _chk(call(_p(recs), None, 0, C.byref(total), C.byref(st)))
+        ids = np.zeros(max(total.value, 1), np.uint32)
+        if total.value:
+            _chk(call(_p(recs), _p(ids), total.value, C.byref(total), C.byref(st)))
+        return RayRecords(recs, ids[: total.value], pixel, st.as_dict())
+
+    def trace_records(self, s, orig4, dir4):
+        """Per-ray records of the exact octree walk for explicit rays (rtmi_trace_records) -> RayRecords (.stats: the
+        call's rtmi_stats_t of the fill)."""
+        o4, d4 = _f(orig4).reshape(-1, 4), _f(dir4).reshape(-1, 4)
+        self._config(s)
+        return self._records(o4.shape[0], lambda r, ids, cap, tot, st: _ffi.lib().rth_caster_trace_records(
+            s.h, o4.shape[0], _p(o4), _p(d4), r, ids, cap, tot, st))
+
+    def primary_records(self, v, s, row0=0, nrows=None, sample=0):
+        """Records of the primary rays of sample `sample` of every pixel of rows [row0, row0 + nrows) (rtmi_primary_records):
+        record i is pixel (row0 + i // width, i % width), its ray bit-identical to the renderer's."""
+        nrows = v.height - row0 if nrows is None else int(nrows)
+        self._config(s)
+        n = nrows * v.width
+        i = np.arange(n, dtype=np.uint64)
+        pixel = np.stack([row0 + i // v.width, i % v.width], axis=1).astype(np.uint32)
+        return self._records(n, lambda r, ids, cap, tot, st: _ffi.lib().rth_caster_primary_records(
+            s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, row0, nrows, sample, r, ids, cap, tot, st), pixel)
 
 
 def quantize(rgba):
