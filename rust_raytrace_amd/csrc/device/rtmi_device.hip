@@ -83,7 +83,7 @@ struct DScene {
 
 #define RTMI_MAX_PASSES 32
 #define RTMI_MAX_STREAMS 4  // interleaved sub-tiles of one tile, each on its own internal stream
-#define RTMI_NDBG 24        // step statistics of the counting build (trace_oct.hpp: what each entry counts)
+#define RTMI_NDBG 26        // step statistics of the counting build (trace_oct.hpp: what each entry counts)
 struct DCtrl {
     uint32_t count[RTMI_MAX_PASSES + 1];  // rays queued for pass k
     uint32_t head[RTMI_MAX_PASSES + 1];   // work-fetch cursor of pass k
@@ -1208,7 +1208,13 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
     s->root_is_leaf = boxes[0].is_leaf != 0;
     s->why_generic = why;
     if (e == hipSuccess && s->octree) e = up(s->fnodes, hfn);
-    if (e == hipSuccess && s->octree) e = up(s->oblocks, hob);
+    if (e == hipSuccess && s->octree) {
+        // 15 zero blocks behind the last one: the whole-list cull of k_path_primary (trace_oct.hpp) reads the 16 blocks
+        // from any block of a list on without a bounds test (they end no earlier than the array; noblocks stays the count)
+        std::vector<uint4> hobp(hob);
+        hobp.resize(hob.size() + 15, make_uint4(0u, 0u, 0u, 0u));
+        e = up(s->oblocks, hobp);
+    }
     if (e == hipSuccess && s->octree) e = up(s->wlinks, hwl);
     for (int k = 0; k < RTMI_MAX_STREAMS && e == hipSuccess; k++) {
         e = s->w[k].ctrl.ensure(1);

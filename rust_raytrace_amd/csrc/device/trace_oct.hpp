@@ -166,6 +166,11 @@ struct PrimHdr {
     unsigned long long q2[3];  // pass-2 queue: origins, directions, paths
     uint32_t minpl;            // least number of mirror lanes that a wave continues in place (65: never)
     uint32_t pad;
+    // The last whole-list cull of the LEAF step: blocks [llo, lhi & 0x7FFFFFFF) of a list and, per reference (bit 4 j + k:
+    // reference k of block llo + j), the references that survive it (fast build; bit 31 of lhi: the list ends among
+    // these blocks) or that it culls (counting build: the range is emptied whenever the packet changes)
+    unsigned long long lmask;
+    uint32_t llo, lhi;
 };
 #define PK_K 1e-5f  // relative slack: ~170 x the float rounding of any bound below
 // One ray of the packet: its spreads against the reference.  False: this ray turns culling off for the packet (nonzero
@@ -238,6 +243,8 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     // predicate culls, violations (a culled reference whose exact test passed: must stay 0)
     // dbg[21..23] (W_PRIMARY): primary rays whose path goes on through a Reflective hit (and not to the slow path), those
     // of them traced in place, exchange steps with >= 32 such lanes (low 32 bits) | with 64 such lanes (high 32 bits)
+    // dbg[24..25] (W_PRIMARY): leaf visits whose first LEAF step is a packet step (the whole-list cull starts at the list's
+    // first block), whole-list culls (= the LEAF steps that the fast build spends on packet steps)
     unsigned long long dbg[RTMI_NDBG] = {};
     const unsigned long long t_begin = COUNT ? __builtin_amdgcn_s_memtime() : 0ull;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
@@ -280,6 +287,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
         if (lane == 0) {
             hdr->q2[0] = (unsigned long long)a.b2qo; hdr->q2[1] = (unsigned long long)a.b2qd; hdr->q2[2] = (unsigned long long)a.b2qpath;
             hdr->minpl = a.minpl ? (uint32_t)a.minpl : 65u;
+            if (COUNT) { hdr->llo = 0u; hdr->lhi = 0u; }
         }
         lds += sizeof(PrimHdr) / 4;
     }
@@ -656,12 +664,14 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                     }
                 }
             } else {
-            // ---- packet cull (W_PRIMARY): when every LEAF lane stands at the same block, lane i tests reference i & 3 of it
-            // against the whole packet (packet_culls); the references it cannot reject are tested in the packet step below,
-            // the full LEAF step runs when it culls none.  The counting build evaluates the predicate but tests every
-            // reference.
-            uint32_t keep = 0xFu, cullm = 0u;  // wave-uniform
-            uint4 ub = make_uint4(0u, 0u, 0u, 0u);
+            // ---- packet cull (W_PRIMARY, DESIGN.md 4.1 "Packet cull"): when every LEAF lane stands at the same block lb0, ONE
+            // step culls the list from lb0 on against the packet.  Lane i takes reference i & 3 of block lb0 + (i >> 2) (the
+            // addressing and end rule of the slow path's wide step below) and tests it with packet_culls; one ballot gives the
+            // references that survive, and they get the exact test one at a time, in list order, in the same step.  A list of
+            // <= 16 blocks thus costs one LEAF step, culled whole or not; a longer one goes on at block lb0 + 16 with the next
+            // step.  The full LEAF step runs when the lanes stand at different blocks.  The counting build evaluates the same
+            // mask, keeps it in the LDS header and tests every reference block by block, checking each one the mask culls.
+            uint32_t cullm = 0u;  // COUNT (wave-uniform): the references of this block that the list mask culls
             if (MODE == W_PRIMARY && __builtin_amdgcn_readfirstlane((int)pk) == (int)PK_NEW) {
                 // the packet of the last refill: the rays of every lane that has one (in W_PRIMARY a lane's ray only changes
                 // at a refill, so r still holds it; lanes whose ray went to the slow path are idle and do not count)
@@ -685,28 +695,12 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                     }
                     if (packet_finish(p, __uint_as_float(__builtin_amdgcn_readfirstlane(mo)), __uint_as_float(__builtin_amdgcn_readfirstlane(md)))) {
                         pk = PK_ON;
-                        if (lane == 0) *pkl = p;
+                        if (lane == 0) {
+                            *pkl = p;
+                            if (COUNT) { hdr->llo = 0u; hdr->lhi = 0u; }  // a list mask of the previous packet covers nothing
+                        }
                     }
                 }
-            }
-            if (MODE == W_PRIMARY && __builtin_amdgcn_readfirstlane((int)pk) == (int)PK_ON) {
-                const uint32_t lb0 = (uint32_t)__builtin_amdgcn_readlane((int)lblock, __ffsll((long long)mL) - 1);
-                if (__ballot((mode == M_LEAF) & (lblock != lb0)) == 0ull) {
-                    const uint4 b = ld_off32(sc.oblocks, lb0 << 4);
-                    ub = b;
-                    uint32_t ln;  // (computed here: hipcc would otherwise keep lane & 1, lane & 2 live over the whole loop)
-                    asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(lane));
-                    const bool odd = (ln & 1u) != 0u;
-                    const uint32_t id = ((ln & 2u) ? (odd ? b.w : b.z) : (odd ? b.y : b.x)) & 0x7FFFFFFFu;
-                    const float4 q0 = ld_off32(sc.tplane, id << 5), q1 = ld_off32(sc.tplane, (id << 5) + 16u);
-                    cullm = (uint32_t)__ballot(packet_culls(*pkl, q0, q1)) & 0xFu;  // lanes 0..3 hold references 0..3
-                    if (!COUNT) keep = ~cullm & 0xFu;
-                    if (COUNT && lane == 0) {
-                        const uint32_t real = (b.x != 0u ? 1u : 0u) | (b.y != 0u ? 2u : 0u) | (b.z != 0u ? 4u : 0u) | ((b.w & 0x7FFFFFFFu) != 0u ? 8u : 0u);
-                        dbg[16]++; dbg[18] += __popc(real); dbg[19] += __popc(real & cullm);
-                    }
-                }
-                if (COUNT && lane == 0) dbg[17]++;
             }
             auto finish_leaf = [&]() {  // the list ended with this block
                 if (lhave) take_leaf(lt, ltf);
@@ -759,22 +753,74 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                 q.den = c ? den : q.den;
             };
             bool lm = mode == M_LEAF;  // this lane runs the full LEAF step below
-            if (__builtin_amdgcn_readfirstlane((int)keep) != 0xF) {
-                // packet step that culled references: only the others are tested, one at a time (a wave-uniform loop; the
-                // block's words are wave-uniform); a block culled whole only moves the cursor
-                const uint32_t kp = (uint32_t)__builtin_amdgcn_readfirstlane((int)keep);
-                auto rf = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
-                const uint32_t bx = rf(ub.x), by = rf(ub.y), bz = rf(ub.z), bw = rf(ub.w);
+            const uint32_t* const oref = reinterpret_cast<const uint32_t*>(sc.oblocks);  // the references one word at a time
+            bool fin = false;          // W_PRIMARY: this lane's list ended in this step
+            bool wl = false;           // (wave-uniform) the whole-list step runs: its survivors and blocks are in the LDS header
+            if (MODE == W_PRIMARY && __builtin_amdgcn_readfirstlane((int)pk) == (int)PK_ON) {
+                const int l0 = __ffsll((long long)mL) - 1;
+                const uint32_t lb0 = (uint32_t)__builtin_amdgcn_readlane((int)lblock, l0);
+                if (__ballot((mode == M_LEAF) & (lblock != lb0)) == 0ull) {
+                    auto rf = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+                    const volatile PrimHdr* const vh = hdr;
+                    // counting build: a block that the last list mask covers (past the block it started at) is not culled again
+                    if (!COUNT || !(lb0 > rf(vh->llo) && lb0 < rf(vh->lhi))) {
+                        uint32_t ln;  // (computed here: hipcc would otherwise keep lane >> 2, lane & 3 live over the whole loop)
+                        asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(lane));
+                        // one word per lane (the array has 15 zero blocks behind its last one: no bounds test)
+                        const uint32_t w = ld_off32(oref, ((lb0 + (ln >> 2)) << 4) + ((ln & 3u) << 2));
+                        const uint32_t id = w & 0x7FFFFFFFu;
+                        // blocks that end the list: their 4th word (lane 4 j + 3) is 0 or has bit 31 set
+                        const unsigned long long tm = __ballot(((ln & 3u) == 3u) & ((w == 0u) | ((w >> 31) != 0u)));
+                        const uint32_t nb = tm ? ((uint32_t)(__ffsll((long long)tm) - 1) >> 2) + 1u : 16u;  // blocks of the list from lb0, <= 16
+                        const bool inl = ((ln >> 2) < nb) & (id != 0u);  // a 0 is padding behind the list's end
+                        const uint32_t pid = inl ? id : 0u;               // (the others read the sentinel's record: one line)
+                        const float4 q0 = ld_off32(sc.tplane, pid << 5), q1 = ld_off32(sc.tplane, (pid << 5) + 16u);
+                        const bool cut = packet_culls(*pkl, q0, q1);
+                        if (!COUNT) {
+                            wl = true;
+                            const unsigned long long sm = __ballot(inl & !cut);  // the survivors, in list order
+                            if (lane == 0) { hdr->lmask = sm; hdr->llo = lb0; hdr->lhi = (lb0 + nb) | (tm != 0ull ? 0x80000000u : 0u); }
+                        } else {
+                            const unsigned long long cm = __ballot(inl & cut);
+                            const uint32_t key = (uint32_t)__builtin_amdgcn_readlane((int)memo[0], l0);  // the list's first block
+                            if (lane == 0) {
+                                hdr->lmask = cm; hdr->llo = lb0; hdr->lhi = lb0 + nb;
+                                dbg[25]++;
+                                if (lb0 == key) dbg[24]++;
+                            }
+                        }
+                    }
+                    if (COUNT) {  // this block's part of the mask; the full step below tests all 4 references
+                        const uint32_t lo = rf(vh->llo);
+                        const unsigned long long cm = vh->lmask;
+                        cullm = (uint32_t)(((unsigned long long)rf((uint32_t)cm) | ((unsigned long long)rf((uint32_t)(cm >> 32)) << 32)) >> ((lb0 - lo) * 4u)) & 0xFu;
+                        const uint4 b = ld_off32(sc.oblocks, lb0 << 4);
+                        if (lane == 0) {
+                            const uint32_t real = (b.x != 0u ? 1u : 0u) | (b.y != 0u ? 2u : 0u) | (b.z != 0u ? 4u : 0u) | ((b.w & 0x7FFFFFFFu) != 0u ? 8u : 0u);
+                            dbg[16]++; dbg[18] += __popc(real); dbg[19] += __popc(real & cullm);
+                        }
+                    }
+                }
+                if (COUNT && lane == 0) dbg[17]++;
+            }
+            if (!COUNT && wl) {
+                // the whole-list step's survivors: a region of its own, apart from the full step (uniform
+                // branches around the full step's plane tests make hipcc spill)
                 if (lm) {
+                    auto rf = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+                    const volatile PrimHdr* const vh = hdr;
+                    const unsigned long long sm = vh->lmask;
+                    const uint32_t lo = rf(vh->llo), hi = rf(vh->lhi);
                     Cand q{0u, 0.f, 0.f, 0.f, 0.f, 0.f};
-                    for (uint32_t m = kp; m != 0u; m &= m - 1u) {  // one reference at a time, in list order
-                        const uint32_t k = (uint32_t)__builtin_ctz(m);
-                        const uint32_t id = k == 0u ? bx : k == 1u ? by : k == 2u ? bz : bw & 0x7FFFFFFFu;
-                        plane(q, id, ld_off32(sc.tplane, id << 5), ld_off32(sc.tplane, (id << 5) + 16u), false);
+                    // one reference at a time, in list order (a wave-uniform loop): reference l & 3 of block lo + (l >> 2)
+                    for (unsigned long long m = (unsigned long long)rf((uint32_t)sm) | ((unsigned long long)rf((uint32_t)(sm >> 32)) << 32); m != 0ull; m &= m - 1ull) {
+                        const uint32_t l = (uint32_t)(__ffsll((long long)m) - 1);
+                        const uint32_t sid = rf(ld_off32(oref, ((lo + (l >> 2)) << 4) + ((l & 3u) << 2)) & 0x7FFFFFFFu);
+                        plane(q, sid, ld_off32(sc.tplane, sid << 5), ld_off32(sc.tplane, (sid << 5) + 16u), false);
                     }
                     if (q.tri != 0u) resolve(q);
-                    if (bw != 0u && !(bw >> 31)) lblock++;
-                    else finish_leaf();
+                    if (hi >> 31) fin = true;
+                    else lblock = hi;  // no end among these 16 blocks: the list goes on
                 }
                 lm = false;
             }
@@ -790,8 +836,11 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
 #pragma unroll
                 for (int k = 0; k < 4; k++) plane(q, ids[k], p0[k], p1[k], (cullm >> k) & 1u);
                 if (q.tri != 0u) resolve(q);
-                if (!more) finish_leaf();
+                // (W_PRIMARY: one call of finish_leaf after both steps; the other modes keep it here, their code unchanged)
+                if (MODE == W_PRIMARY) fin = !more;
+                else if (!more) finish_leaf();
             }
+            if (MODE == W_PRIMARY && fin) finish_leaf();
             }
         }
         if (COUNT && lane == 0) {  // the step is over for the wave when its slowest lane is (s_memtime is a scalar read)

@@ -19,13 +19,14 @@ print(ctx.stats)
 # the resident scene handle lives inside the C++ caster; fetch the debug counters through a tiny helper
 lib = _ffi.lib()
 lib.rth_debug_counters_n.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-out = (C.c_ulonglong * 24)()
-lib.rth_debug_counters_n(scene.h, out, 24)
+out = (C.c_ulonglong * 26)()
+lib.rth_debug_counters_n(scene.h, out, 26)
 d = list(out)
 names = ["S steps", "S lanes", "L steps", "L lanes", "refills", "refill lanes", "edge blocks", "edge lanes", "S cycles", "L cycles", "refill cycles", "wave cycles",
          "leaf visits", "memo hits", "planes skipped", "edges skipped",
          "packet L steps", "primary L steps", "packet refs", "refs culled", "violations",
-         "mirror rays", "mirror in place", "mirror steps"]
+         "mirror rays", "mirror in place", "mirror steps",
+         "packet visits", "list culls"]
 for n, v in zip(names, d):
     print(f"{n:14s} {v}")
 rays = ctx.stats["rays"]
@@ -45,3 +46,10 @@ print(f"packet cull (k_path_primary, with the mirror reflections it traces in pl
 print(f"mirror paths (RTMI_MIRROR_INPLACE={os.environ.get('RTMI_MIRROR_INPLACE', 'default')}): {d[21]} primary rays go on through a "
       f"Reflective hit ({d[21] / max(rays, 1):.4f} of all rays), {d[22]} of them traced in place by k_path_primary; exchange steps "
       f"with >= 32 mirror lanes {d[23] & 0xFFFFFFFF}, with 64 {d[23] >> 32}")
+# dbg[24]: leaf visits whose first LEAF step is a packet step; dbg[25]: whole-list culls (0 before the whole-list cull existed)
+print(f"packet leaf visits (first LEAF step of the visit qualifies): {d[24]}; per such visit: {d[16] / max(d[24], 1):.2f} qualifying "
+      f"block steps, {d[18] / max(d[24], 1):.2f} references; whole-list culls {d[25]} ({d[25] / max(d[24], 1):.2f} per visit)")
+if d[25]:
+    # an estimate: the counting build still steps block by block, so its lanes may line up differently from the fast build's
+    print(f"estimated primary LEAF steps of the fast build: {d[17] - d[16] + d[25]} (counting build: {d[17]}; whole-list culls "
+          f"replacing its {d[16]} packet block steps)")
