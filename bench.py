@@ -11,9 +11,13 @@ Launch: `python bench.py --gpus N` starts the N ranks itself (torch.distributed.
 touches a GPU) when it is not already running under a launcher; under `python -m torch.distributed.run
 --nproc-per-node N bench.py --gpus N` it is one of the ranks.
 
-Prints one JSON line (rank 0).  Extra legs outside the timed region (rank 0 of a 1-GPU run only): a counting
-pass (device work counters -> algorithmic flops and bytes for the roofline object), a second timed loop
-that includes the frame's device-to-host copy, and the CPU baseline (the oracle on a bounded sample).
+Prints one JSON line (rank 0).  A plain run sets up, warms up, times the steps and prints that line; the extra legs
+outside the timed region run only with `--full` (rank 0 of a 1-GPU run only): a second timed loop that includes the
+frame's device-to-host copy (`value_incl_frame_d2h`), a counting pass (device work counters -> algorithmic flops and
+bytes for the `roofline` object), the CPU baseline (`cpu_baseline`: the oracle on a bounded sample) and, in the
+opt-in `--bvh` / `--fast` modes, the comparison with the exact render (`opt_in_mode_vs_exact`).  Without `--full`
+those keys are null; `--no-d2h-leg`, `--no-counters` and `--no-cpu-baseline` drop one leg of a full run.  `--check`
+(the gathered frame against a single-tile render) runs whenever it is asked for.
 `--dump-outputs DIR` also writes the last timed step's frame (or a fixed sample of it) and ray count as .npy files, so that
 two builds can be compared output for output (dump_outputs).
 """
@@ -66,13 +70,17 @@ def parse():
     ap.add_argument("--fast", action="store_true", help="RTMI_OPT_FAST (not bit-exact, NOT the headline): skip boxes behind the ray origin")
     ap.add_argument("--bvh", action="store_true",
                     help="RTMI_OPT_BVH fast mode (NOT the headline): linear-list semantics through the library's SAH BVH; "
-                         "prints the differing-pixel count against the exact octree render")
+                         "with --full prints the differing-pixel count against the exact octree render")
     ap.add_argument("--backend", default="nccl", help="nccl (RCCL, one rank per GPU) or gloo (rehearsal: ranks may share a GPU)")
     ap.add_argument("--check", action="store_true", help="rank 0 verifies the gathered frame against a single-tile render")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-counters", action="store_true")
-    ap.add_argument("--no-d2h-leg", action="store_true", help="skip the extra timed loop that includes the frame's device-to-host copy")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="target wall time of the CPU baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the extra legs of a 1-GPU run: the timed loop with the frame's "
+                         "device-to-host copy, the counting pass of the roofline object, the CPU baseline and, with --bvh or "
+                         "--fast, the comparison with the exact render")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-counters", action="store_true", help="with --full: skip the counting pass (roofline object)")
+    ap.add_argument("--no-d2h-leg", action="store_true", help="with --full: skip the extra timed loop that includes the frame's device-to-host copy")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="target wall time of the CPU baseline sample (--full)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32/float64, "
                          f"at most {DUMP_LIMIT_BYTES // 10**6} MB in all; see dump_outputs)")
@@ -242,7 +250,7 @@ def main():
         if args.dump_outputs:
             written = dump_outputs(args.dump_outputs, last_frame, sum(float(p[7]) for p in per_rank))
             print(f"[bench] last timed step written to {args.dump_outputs}: {written}", file=sys.stderr)
-        if world == 1 and not args.no_d2h_leg:
+        if world == 1 and args.full and not args.no_d2h_leg:
             # ---- frame device-to-host copy inside the window (SURVEY 8d's GPU window); never the headline `value`
             host = torch.empty(frame.shape, dtype=frame.dtype, pin_memory=True)
             n2 = min(args.steps, 3)
@@ -255,12 +263,12 @@ def main():
             d2 = time.perf_counter() - t1
             incl_d2h = {"value": round(rays / args.steps * n2 / d2 / 1e6, 2), "unit": "Mrays/s", "ms_per_step": round(d2 / n2 * 1e3, 3),
                         "note": f"timed window also contains the {host.numel() * host.element_size() >> 20} MiB frame copy to pinned host memory"}
-        if world == 1 and not args.no_counters and not args.bvh:
+        if world == 1 and args.full and not args.no_counters and not args.bvh:
             roofline = roofline_object(args, caster, scene, vp, tile, local, stream, rays / args.steps, trace_ms, kernel_ms, launches, dt)
-        if world == 1 and not args.no_cpu_baseline and args.scene == "canonical":
+        if world == 1 and args.full and not args.no_cpu_baseline and args.scene == "canonical":
             cpu_baseline = cpu_baseline_object(args, obj)
         fast_vs_exact = None
-        if (args.bvh or args.fast) and world == 1:
+        if (args.bvh or args.fast) and world == 1 and args.full:
             # how far the opt-in mode is from the exact (default) render of the same frame
             ex = torch.zeros((H, W, 4), dtype=torch.float32, device=dev)
             ectx = R.HipRayCaster(seed=args.seed, device=local_rank).walk_tile_device(vp, scene, (0, H, H, 0), ex.data_ptr(), stream.cuda_stream)
