@@ -251,6 +251,36 @@ int rtmi_render_samples_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, u
 int rtmi_render_samples(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
                         uint32_t sample0, uint32_t nsamples, float* accum_host, float* out_host, rtmi_stats_t* stats);
 
+/* Adaptive sampling: every pixel stops at its own sample count n, between min_samples and
+ * vp->samples_per_pixel = S (the maximum, >= 2), and its value is exactly the pixel of a uniform render at spp = n.
+ * Pass 0 renders samples [0, m) of every pixel of the tile (m = min_samples, 2 <= m <= S).  After each pass the stop rule
+ * is applied to every pixel still active; one that goes on gets samples [n, min(n + pass_samples, S)) in the next pass
+ * (all active pixels share the same n).  A pixel with n = S stops whatever the rule says.  The stop rule, in f32 and in
+ * this order (s = sum, q = per-lane sum of squares of the pixel's samples; max(a, b) = a < b ? b : a):
+ *   inv = 1/(float)n;  m_c = s_c * inv;  v_c = (q_c - s_c * m_c) / (float)(n - 1)   (c = r, g, b)
+ *   e = max(max(v_r, v_g), v_b) / (float)n;  L = max(max(m_r, m_g), m_b);  t = abs_tol + rel_tol * L
+ *   stop iff e <= t * t;  a NaN anywhere means "not stopped" (abs_tol = NaN: every pixel runs to S, in passes;
+ *   abs_tol = +inf: every pixel stops at m).
+ * passes, unconverged (pixels that reached S without the rule stopping them) and samples (the sum of counts) are outputs. */
+typedef struct rtmi_adaptive {
+    uint32_t min_samples, pass_samples; float rel_tol, abs_tol;  /* in  */
+    uint32_t passes, unconverged; uint64_t samples;              /* out */
+} rtmi_adaptive_t;
+
+/* accum, sumsq: one float4 per pixel of the tile (the layout of out): the running sum, and the per-lane sum of squares
+ * q = q + c * c in sample order from 0.f (lane 3 is 0); counts: one uint32 per pixel, its sample count; out (optional, may
+ * be NULL) = accum * (1/count) per pixel, k_accum's arithmetic.  No two of the four buffers may alias.  The device variant
+ * enqueues on hip_stream and reads back 4 bytes per pass (the number of active pixels, which sizes the next pass).  The
+ * host variant renders rows [row0, row0 + nrows), keeps accum and sumsq on the device and copies out and counts once.
+ * stats cover the whole call, summed over its passes: with abs_tol = NaN they are a single rtmi_render call's.
+ * maxdepth == 0: zeros, count = m.  RTMI_ERR_INVALID (before any HIP call) for m < 2, m > S, pass_samples == 0, S < 2, a
+ * NULL or aliased buffer, a NULL scene, viewport or ad. */
+int rtmi_render_adaptive_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile,
+                                rtmi_adaptive_t* ad, void* accum_device, void* sumsq_device, void* counts_device,
+                                void* out_device, void* hip_stream, rtmi_stats_t* stats);
+int rtmi_render_adaptive(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
+                         rtmi_adaptive_t* ad, float* out_host, uint32_t* counts_host, rtmi_stats_t* stats);
+
 /* One whole frame over several devices of this process -- the fan-out the reference does over CPU threads
  * (DefaultRayCaster::walk_rays_internal, raytrace.rs:1175-1196: `threads` workers pulling rows from a queue) done
  * over GPUs, inside the library.  scenes[i] is the SAME scene uploaded to some device (rtmi_scene_create with

@@ -87,6 +87,16 @@ int rth_caster_walk_samples(rth_scene_t* s, uint32_t w, uint32_t h, const float*
 int rth_caster_walk_samples_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
                                    const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, void* accum_device,
                                    void* out_device, void* hip_stream, rtmi_stats_t* stats, double* wall_seconds);
+/* Adaptive sampling (rtmi_render_adaptive / rtmi_render_adaptive_device in rtmi.h): spp is the maximum samples per pixel;
+ * ad carries min_samples, pass_samples and the tolerances in and passes, unconverged and samples out.  out receives every
+ * pixel at its own count, counts the per-pixel sample counts. */
+int rth_caster_walk_adaptive(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                             uint64_t row0, uint64_t nrows, rtmi_adaptive_t* ad, float* out_host, uint32_t* counts_host,
+                             rtmi_stats_t* stats, double* wall_seconds);
+int rth_caster_walk_adaptive_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                                    const rtmi_tile_t* tile, rtmi_adaptive_t* ad, void* accum_device, void* sumsq_device,
+                                    void* counts_device, void* out_device, void* hip_stream, rtmi_stats_t* stats,
+                                    double* wall_seconds);
 int rth_caster_trace(rth_scene_t* s, uint64_t n, const float* orig4, const float* dir4, uint32_t* tri, float* t,
                      uint32_t* face, rtmi_stats_t* stats);
 /* Per-ray records (rtmi_trace_records / rtmi_primary_records, same buffers and size-query idiom) on the scene's

@@ -45,6 +45,7 @@
 static_assert(sizeof(rtmi_stats_t) == 128 && sizeof(rtmi_tuning_t) == 48 && sizeof(rtmi_tile_t) == 16 && sizeof(rtmi_box_t) == 32 &&
               sizeof(rtmi_triangle_t) == 104 && sizeof(rtmi_viewport_t) == 64 && sizeof(rtmi_sphere_t) == 40 &&
               sizeof(rtmi_ray_record_t) == 72, "ABI struct layout changed");
+static_assert(sizeof(rtmi_adaptive_t) == 32 && offsetof(rtmi_adaptive_t, samples) == 24, "ABI struct layout changed");
 
 namespace rtmi {
 
@@ -491,14 +492,16 @@ __global__ void __launch_bounds__(256) k_trace_linear(DScene sc, const float4* _
 
 // ---------------------------------------------------------------- generation / shading (per-pass pipeline)
 // pixel_ray / color_ray themselves are in shade.hpp (shared with the path kernels of trace_oct.hpp).
-// PROG = true: the kernels of progressive passes (k_gen_samples, k_shade_samples), whose sample numbers start at sample0
-template <bool PROG>
+// PROG = true: the kernels of progressive passes (k_gen_samples, k_shade_samples), whose sample numbers start at sample0.
+// LIST = true (with PROG): adaptive passes (k_gen_list, k_shade_list), whose pixels come from the active-pixel list.
+template <bool PROG, bool LIST = false>
 __device__ __forceinline__ void gen_paths(const DView& v, uint64_t seed, uint32_t pix0, uint32_t npaths, float4* __restrict__ qo,
-                                          float4* __restrict__ qd, uint32_t* __restrict__ qpath, DCtrl* __restrict__ ctrl) {
+                                          float4* __restrict__ qd, uint32_t* __restrict__ qpath, DCtrl* __restrict__ ctrl,
+                                          const uint32_t* __restrict__ list = nullptr) {
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t path = blockIdx.x * blockDim.x + threadIdx.x; path < npaths; path += stride) {
         uint32_t row, col, sample;
-        path_pixel<PROG>(v, pix0, path, row, col, sample);
+        path_pixel<PROG, LIST>(v, pix0, path, row, col, sample, list);
         const uint32_t pixel = row * v.width + col;
         RayV r = pixel_ray<PROG>(v, row, col, seed, pixel, sample);
         qo[path] = make_float4(r.orig.x, r.orig.y, r.orig.z, r.orig.w);
@@ -517,6 +520,12 @@ __global__ void __launch_bounds__(256) k_gen_samples(DView v, uint64_t seed, uin
                                                      uint32_t* __restrict__ qpath, DCtrl* __restrict__ ctrl) {
     gen_paths<true>(v, seed, pix0, npaths, qo, qd, qpath, ctrl);
 }
+__global__ void __launch_bounds__(256) k_gen_list(DView v, uint64_t seed, uint32_t pix0, uint32_t npaths,
+                                                  float4* __restrict__ qo, float4* __restrict__ qd,
+                                                  uint32_t* __restrict__ qpath, DCtrl* __restrict__ ctrl,
+                                                  const uint32_t* __restrict__ list) {
+    gen_paths<true, true>(v, seed, pix0, npaths, qo, qd, qpath, ctrl, list);
+}
 
 // color_ray + the tail of project_ray for every ray of pass `pass`.
 #define RTMI_SHADE_PARAMS DScene sc, DView v, uint64_t seed, uint32_t pix0, uint32_t npaths, int pass,                  \
@@ -526,8 +535,8 @@ __global__ void __launch_bounds__(256) k_gen_samples(DView v, uint64_t seed, uin
                           uint32_t* __restrict__ qpath_n, uint16_t* __restrict__ mstack, float4* __restrict__ scol,    \
                           DCtrl* __restrict__ ctrl, SlowQ slow
 #define RTMI_SHADE_ARGS sc, v, seed, pix0, npaths, pass, qo, qd, qpath, hit_tf, hit_t, qo_n, qd_n, qpath_n, mstack, scol, ctrl, slow
-template <bool PROG>
-__device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS) {
+template <bool PROG, bool LIST = false>
+__device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list = nullptr) {
     __shared__ uint32_t s_cnt[4], s_base;
     const uint32_t count = ctrl->count[pass];
     const uint32_t stride = gridDim.x * blockDim.x;
@@ -548,7 +557,7 @@ __device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS) {
             float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f), d4 = make_float4(0.f, 0.f, 1.f, 0.f);
             if ((tf & 0x3FFFFFFFu) != 0u && !((tf >> 30) & 2u)) { t = hit_t[i]; o4 = qo[i]; d4 = qd[i]; }
             uint32_t prow, pcol, sample;
-            path_pixel<PROG>(v, pix0, path, prow, pcol, sample);
+            path_pixel<PROG, LIST>(v, pix0, path, prow, pcol, sample, list);
             push = shade_hit(sc, v.maxdepth, seed, npaths, path, prow * v.width + pcol, sample, (uint32_t)pass, tf, t,
                              V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr);
             // a bounce ray with an exactly-zero direction component goes to the slow path (SlowQ), not to the next pass
@@ -583,6 +592,9 @@ __device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS) {
 }
 __global__ void __launch_bounds__(256) k_shade(RTMI_SHADE_PARAMS) { shade_pass<false>(RTMI_SHADE_ARGS); }
 __global__ void __launch_bounds__(256) k_shade_samples(RTMI_SHADE_PARAMS) { shade_pass<true>(RTMI_SHADE_ARGS); }
+__global__ void __launch_bounds__(256) k_shade_list(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list) {
+    shade_pass<true, true>(RTMI_SHADE_ARGS, list);
+}
 
 // walk_ray_set's per-pixel accumulation (raytrace.rs:1414-1426): acc = 0; acc += sample_i in sample order; * (1/spp).
 // The sample colours of a pixel are consecutive in `scol` ([pixel][sample]), so one thread per pixel would read 16 B at a
@@ -597,10 +609,15 @@ __global__ void __launch_bounds__(256) k_shade_samples(RTMI_SHADE_PARAMS) { shad
 #define RTMI_ACC_CHUNK 1024
 // RESUME = false: k_accum, the sum starts at 0.f and out = sum * inv.  RESUME = true: k_accum_samples (progressive passes),
 // the sum starts from accum when `resume`, is written back to accum, and out (when not NULL) = sum * inv.
-template <bool RESUME>
+// LIST = true (with RESUME): k_accum_list (adaptive passes): the block's pixels are list[pix0 + pb + j], tile-local pixel
+// indices (= their float4 in accum / sumsq / out); the per-lane sum of squares q = q + c * c continues in sumsq beside the
+// sum, and counts[pixel] receives `ncount`, the pixel's samples after this pass.
+template <bool RESUME, bool LIST = false>
 __device__ __forceinline__ void accum_pixels(uint32_t npixels, uint32_t spp, const float4* __restrict__ scol, float* __restrict__ out,
                                              float* __restrict__ accum, bool resume, float inv, uint32_t pix0, uint32_t W,
-                                             uint32_t nsub, uint32_t sub, FastDiv dW) {
+                                             uint32_t nsub, uint32_t sub, FastDiv dW, const uint32_t* __restrict__ list = nullptr,
+                                             float* __restrict__ sumsq = nullptr, uint32_t* __restrict__ counts = nullptr,
+                                             uint32_t ncount = 0u) {
     __shared__ float4 stage[RTMI_ACC_CHUNK + RTMI_ACC_CHUNK / 64 + 1];
     const float* stage_f = reinterpret_cast<const float*>(stage);
     const uint32_t tid = threadIdx.x, j = tid >> 2, c = tid & 3u;
@@ -609,8 +626,15 @@ __device__ __forceinline__ void accum_pixels(uint32_t npixels, uint32_t spp, con
         const uint32_t f0 = pb * spp, f1 = f0 + npb * spp;       // the block's samples: scol[f0 .. f1)
         const uint32_t my0 = f0 + j * spp, my1 = my0 + spp;      // this thread's pixel (when j < npb)
         size_t o = 0;                                            // RESUME: this thread's float in accum / out
-        float acc = 0.f;
-        if (RESUME && j < npb) {
+        float acc = 0.f, sq = 0.f;                               // sq: LIST only
+        uint32_t lpix = 0;                                       // LIST: the tile-local pixel
+        if (LIST) {
+            if (j < npb) {
+                lpix = list[pix0 + pb + j];
+                o = (size_t)lpix * 4u + c;
+                if (resume) { acc = accum[o]; sq = sumsq[o]; }
+            }
+        } else if (RESUME && j < npb) {
             const uint32_t lp = pix0 + pb + j, lr = fdiv(lp, dW), col = lp - lr * W;
             o = (((size_t)lr * nsub + sub) * W + col) * 4u + c;
             if (resume) acc = accum[o];
@@ -624,13 +648,19 @@ __device__ __forceinline__ void accum_pixels(uint32_t npixels, uint32_t spp, con
                 const uint32_t lo = max(my0, ch), hi = min(my1, ch + n);
                 for (uint32_t s = lo; s < hi; s++) {
                     const uint32_t k = s - ch;
-                    acc = acc + stage_f[(k + (k >> 6)) * 4u + c];
+                    const float x = stage_f[(k + (k >> 6)) * 4u + c];
+                    acc = acc + x;
+                    if (LIST) sq = sq + x * x;
                 }
             }
         }
         if (j < npb) {
             if (RESUME) {
                 accum[o] = acc;
+                if (LIST) {
+                    sumsq[o] = sq;
+                    if (c == 0u) counts[lpix] = ncount;
+                }
                 if (out) out[o] = acc * inv;
             } else {
                 const uint32_t lp = pix0 + pb + j, lr = fdiv(lp, dW), col = lp - lr * W;
@@ -652,6 +682,106 @@ __global__ void __launch_bounds__(256) k_accum_samples(uint32_t npixels, uint32_
                                                        float* __restrict__ accum, float* __restrict__ out, uint32_t pix0, uint32_t W,
                                                        uint32_t nsub, uint32_t sub, FastDiv dW) {
     accum_pixels<true>(npixels, nsamples, scol, out, accum, sample0 != 0u, 1.f / (float)(sample0 + nsamples), pix0, W, nsub, sub, dW);
+}
+// Adaptive passes: samples [sample0, sample0 + nsamples) of the list's pixels pix0 .. pix0 + npixels - 1.  Every pixel of the
+// list has had exactly sample0 samples, so the sum and the sum of squares continue in sample order from 0.f (sample0 == 0)
+// and out = sum * (1/count) is k_accum's arithmetic at spp = count: the pixel of a uniform render at that many samples.
+__global__ void __launch_bounds__(256) k_accum_list(uint32_t npixels, uint32_t nsamples, uint32_t sample0, const float4* __restrict__ scol,
+                                                    float* __restrict__ accum, float* __restrict__ sumsq, uint32_t* __restrict__ counts,
+                                                    float* __restrict__ out, const uint32_t* __restrict__ list, uint32_t pix0) {
+    const uint32_t n = sample0 + nsamples;
+    accum_pixels<true, true>(npixels, nsamples, scol, out, accum, sample0 != 0u, 1.f / (float)n, pix0, 0u, 0u, 0u, FastDiv{},
+                             list, sumsq, counts, n);
+}
+
+// ---------------------------------------------------------------- adaptive sampling: the stop rule and the next list
+// The stop rule of a pixel with n >= 2 samples, sum s and per-lane sum of squares q (rtmi.h, rtmi_render_adaptive):
+// the worst channel's squared standard error of the mean against (abs_tol + rel_tol * brightest mean)^2.  f32 in this
+// order, max(a, b) = a < b ? b : a, and any NaN means "not stopped" (abs_tol = NaN disables the rule).
+__host__ __device__ inline float adapt_max(float a, float b) { return a < b ? b : a; }
+__host__ __device__ inline bool adapt_stop(float4 s, float4 q, uint32_t n, float rel_tol, float abs_tol) {
+    const float inv = 1.f / (float)n, dn1 = (float)(n - 1u);
+    const float mr = s.x * inv, mg = s.y * inv, mb = s.z * inv;
+    const float vr = (q.x - s.x * mr) / dn1, vg = (q.y - s.y * mg) / dn1, vb = (q.z - s.z * mb) / dn1;
+    const float e = adapt_max(adapt_max(vr, vg), vb) / (float)n;
+    const float L = adapt_max(adapt_max(mr, mg), mb);
+    const float t = abs_tol + rel_tol * L;
+    const bool nan = (mr != mr) | (mg != mg) | (mb != mb) | (vr != vr) | (vg != vg) | (vb != vb) | (e != e) | (t != t);
+    return !nan && e <= t * t;
+}
+// Wave-wide inclusive prefix sum (wave64).
+__device__ inline uint32_t wave_incl_scan(uint32_t v) {
+    const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const uint32_t u = __shfl_up(v, d, 64);
+        if (lane >= d) v += u;
+    }
+    return v;
+}
+// 256-thread block: exclusive prefix of v over the block's threads in thread order, and the block's total.  s_w: 4 words of LDS.
+__device__ inline uint32_t block_excl_scan256(uint32_t v, uint32_t* s_w, uint32_t& total) {
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const uint32_t inc = wave_incl_scan(v);
+    __syncthreads();  // s_w may still be read by a previous call
+    if (lane == 63u) s_w[wv] = inc;
+    __syncthreads();
+    uint32_t base = 0;
+    for (uint32_t k = 0; k < wv; k++) base += s_w[k];
+    total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    return base + inc - v;
+}
+#define RTMI_ADAPT_BLOCK 256
+// list[i] = i: the first pass of an adaptive call covers every pixel of the tile
+__global__ void __launch_bounds__(256) k_adapt_init(uint32_t npix, uint32_t* __restrict__ list) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += stride) list[i] = i;
+}
+// Compaction of the active list in three launches that keep its ascending pixel order: (1) each block of 256 entries
+// counts the pixels that go on, (2) one block turns the counts into offsets (and the total, which the host reads back), (3)
+// each block writes its survivors at its offset in entry order.  (1) and (3) evaluate the same rule on the same bits.
+__device__ inline bool adapt_goes_on(const uint32_t* __restrict__ list, uint32_t nlist, const float4* __restrict__ accum,
+                                     const float4* __restrict__ sumsq, uint32_t n, float rel_tol, float abs_tol, uint32_t i,
+                                     uint32_t& pixel) {
+    if (i >= nlist) return false;
+    pixel = list[i];
+    return !adapt_stop(accum[pixel], sumsq[pixel], n, rel_tol, abs_tol);
+}
+__global__ void __launch_bounds__(RTMI_ADAPT_BLOCK) k_adapt_count(const uint32_t* __restrict__ list, uint32_t nlist,
+                                                                  const float4* __restrict__ accum, const float4* __restrict__ sumsq,
+                                                                  uint32_t n, float rel_tol, float abs_tol, uint32_t* __restrict__ bcnt) {
+    __shared__ uint32_t s_w[4];
+    uint32_t pixel = 0;
+    const bool on = adapt_goes_on(list, nlist, accum, sumsq, n, rel_tol, abs_tol, blockIdx.x * RTMI_ADAPT_BLOCK + threadIdx.x, pixel);
+    const unsigned long long mask = __ballot(on);
+    if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = (uint32_t)__popcll(mask);
+    __syncthreads();
+    if (threadIdx.x == 0) bcnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+// one block: bcnt[0 .. nblk) -> exclusive offsets in place; bcnt[nblk] = the total
+__global__ void __launch_bounds__(256) k_adapt_scan(uint32_t* __restrict__ bcnt, uint32_t nblk) {
+    __shared__ uint32_t s_w[4];
+    uint32_t carry = 0;
+    for (uint32_t b0 = 0; b0 < nblk; b0 += 256u) {
+        const uint32_t i = b0 + threadIdx.x;
+        const uint32_t v = i < nblk ? bcnt[i] : 0u;
+        uint32_t total;
+        const uint32_t ex = block_excl_scan256(v, s_w, total);
+        if (i < nblk) bcnt[i] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) bcnt[nblk] = carry;
+}
+__global__ void __launch_bounds__(RTMI_ADAPT_BLOCK) k_adapt_scatter(const uint32_t* __restrict__ list, uint32_t nlist,
+                                                                    const float4* __restrict__ accum, const float4* __restrict__ sumsq,
+                                                                    uint32_t n, float rel_tol, float abs_tol,
+                                                                    const uint32_t* __restrict__ boff, uint32_t* __restrict__ next) {
+    __shared__ uint32_t s_w[4];
+    uint32_t pixel = 0;
+    const bool on = adapt_goes_on(list, nlist, accum, sumsq, n, rel_tol, abs_tol, blockIdx.x * RTMI_ADAPT_BLOCK + threadIdx.x, pixel);
+    uint32_t total;
+    const uint32_t slot = block_excl_scan256(on ? 1u : 0u, s_w, total);
+    if (on) next[boff[blockIdx.x] + slot] = pixel;
 }
 
 // write_png's quantisation (raytrace.rs:1468-1473): `as u8` truncates and saturates, NaN -> 0
@@ -833,6 +963,9 @@ struct rtmi_scene {
     hipEvent_t fork_ev = nullptr, end_ev = nullptr, join_ev[RTMI_MAX_STREAMS] = {};
     DevBuf<float4> tile;
     DevBuf<float4> acc;              // rtmi_render_samples: the running per-pixel sums of the host variant
+    DevBuf<float4> asq;              // rtmi_render_adaptive: the per-pixel sums of squares of the host variant
+    DevBuf<uint32_t> acnt;           // rtmi_render_adaptive: the per-pixel sample counts of the host variant
+    DevBuf<uint32_t> alist[2], ablk; // rtmi_render_adaptive*: active-pixel lists (ping-pong), per-block counts / offsets + total
     DevBuf<uint8_t> qbytes;
     DevBuf<uint8_t> mstage, mframe;  // rtmi_render_frame_multi, root scene: received bands / the frame
     hipStream_t mstream = nullptr;   // rtmi_render_frame_multi: this scene's band stream
@@ -1267,7 +1400,8 @@ int rtmi_scene_destroy(rtmi_scene_t* s) {
     if (s->fork_ev) (void)hipEventDestroy(s->fork_ev);
     if (s->end_ev) (void)hipEventDestroy(s->end_ev);
     s->rec_cnt.release(); s->rec_ids.release(); s->rec_first.release();
-    s->tile.release(); s->acc.release(); s->qbytes.release(); s->mstage.release(); s->mframe.release();
+    s->tile.release(); s->acc.release(); s->asq.release(); s->acnt.release();
+    s->alist[0].release(); s->alist[1].release(); s->ablk.release(); s->qbytes.release(); s->mstage.release(); s->mframe.release();
     if (s->mstream) (void)hipStreamDestroy(s->mstream);
     if (!s->comms.empty()) { if (Rccl* r = rccl_api()) for (ncclComm_t c : s->comms) (void)r->CommDestroy(c); }
     delete s;
@@ -1440,9 +1574,10 @@ static OctArgs path_args(rtmi_scene* s, Work& w, const DView& dv, uint64_t seed,
 // k_path_primary: the batch's primary rays generated, traced and shaded; the bounce rays go to queue 1, which pass 1 traces.
 // The mirror reflections it traces itself go on in queue 2 (ping-pong buffer 0, free until pass 1's k_shade appends to it).
 // `stop` is recorded right after the kernel.
+// list != nullptr (adaptive passes): the list variants, whose batch pixels are list[pix0 + q]
 template <bool COUNT, bool PROG>
 static void launch_primary(rtmi_scene* s, Work& w, hipStream_t st, const DView& dv, uint64_t seed, uint32_t pix0, uint32_t npaths,
-                           hipEvent_t stop) {
+                           hipEvent_t stop, const uint32_t* list = nullptr) {
     OctArgs a = path_args(s, w, dv, seed, pix0, npaths);
     a.bqo = w.qo[1].p; a.bqd = w.qd[1].p; a.bqpath = w.qpath[1].p;
     a.vote_s = s->vote[0]; a.vote_l = s->vote[1];
@@ -1451,7 +1586,11 @@ static void launch_primary(rtmi_scene* s, Work& w, hipStream_t st, const DView& 
     a.minpl = s->mirror_inplace;
     const int refill = (int)s->tune.refill_min0, xcd = (int)(s->tune.xcd_aware % 3u);
     const bool fast = (s->options & RTMI_OPT_FAST) != 0;
-    if (PROG && fast)
+    if (list && fast)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary_list<COUNT, true>), oct_grid(s), dim3(64), oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd, list);
+    else if (list)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary_list<COUNT, false>), oct_grid(s), dim3(64), oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd, list);
+    else if (PROG && fast)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary_samples<COUNT, true>), oct_grid(s), dim3(64), oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
     else if (PROG)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary_samples<COUNT, false>), oct_grid(s), dim3(64), oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
@@ -1464,7 +1603,7 @@ static void launch_primary(rtmi_scene* s, Work& w, hipStream_t st, const DView& 
 // Consumer launch k of the slow path (k_path_slow), on the side stream: after the producer on `st` whose event is sev[k]
 template <bool COUNT, bool PROG>
 static void launch_slow(rtmi_scene* s, Work& w, hipStream_t st, const DView& dv, uint64_t seed, uint32_t pix0, uint32_t npaths,
-                        uint32_t k) {
+                        uint32_t k, const uint32_t* list = nullptr) {
     OctArgs a = path_args(s, w, dv, seed, pix0, npaths);
     a.slow_k = k;
     a.vote_s = s->vote[2]; a.vote_l = s->vote[3];
@@ -1478,7 +1617,11 @@ static void launch_slow(rtmi_scene* s, Work& w, hipStream_t st, const DView& dv,
     (void)hipStreamWaitEvent(st, w.sgo, 0);
     const dim3 sgrid((unsigned)std::max(s->num_cu / 2, 1));  // one path per wave at a time; a frame has ~100 such paths, a wave takes one after the other
     const bool fast = (s->options & RTMI_OPT_FAST) != 0;
-    if (PROG && fast)
+    if (list && fast)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow_list<COUNT, true>), sgrid, dim3(64), oct_launch_lds(s, COUNT), w.sstream, s->d, a, w.ctrl.p, 1, 0, list);
+    else if (list)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow_list<COUNT, false>), sgrid, dim3(64), oct_launch_lds(s, COUNT), w.sstream, s->d, a, w.ctrl.p, 1, 0, list);
+    else if (PROG && fast)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow_samples<COUNT, true>), sgrid, dim3(64), oct_launch_lds(s, COUNT), w.sstream, s->d, a, w.ctrl.p, 1, 0);
     else if (PROG)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow_samples<COUNT, false>), sgrid, dim3(64), oct_launch_lds(s, COUNT), w.sstream, s->d, a, w.ctrl.p, 1, 0);
@@ -1514,14 +1657,38 @@ struct SubTile {
     DView dv;          // row mapping of the sub-tile's local rows (tile_pixel)
     uint64_t npix = 0; // pixels of the sub-tile
     uint32_t index = 0;
+    uint32_t base = 0;  // adaptive passes: the sub-tile's first entry of the active-pixel list
 };
+// An adaptive pass (rtmi_render_adaptive*): the n pixels of `list` (tile-local pixel indices, ascending), each with the same
+// number of samples behind it; sumsq / counts continue beside the call's accum.
+struct ListPass {
+    const uint32_t* list;
+    uint32_t n;
+    float4* sumsq;
+    uint32_t* counts;
+};
+
+// Checks of a tile against the viewport (nrows >= 1); the message, or nullptr when it is valid
+static const char* tile_error(const rtmi_viewport_t* vp, const rtmi_tile_t* tile) {
+    const uint32_t row0 = tile->row0, nrows = tile->nrows;
+    if (vp->width == 0 || vp->height == 0) return "empty viewport";
+    if (tile->stripe_rows == 0) return "stripe_rows must be >= 1";
+    const uint64_t nstripes = ((uint64_t)nrows + tile->stripe_rows - 1) / tile->stripe_rows;
+    const uint64_t last_row = (uint64_t)row0 + (nstripes - 1) * tile->stripe_step + ((uint64_t)nrows - 1 - (nstripes - 1) * tile->stripe_rows);
+    if (last_row >= vp->height) return "row range outside the viewport";
+    if (nstripes > 1 && tile->stripe_step < tile->stripe_rows) return "stripes overlap";
+    return nullptr;
+}
 
 // Samples [sample0, sample0 + nsamples) of every pixel of the tile.  accum == nullptr: the whole frame (0, S) into out_device
 // (rtmi_render_tile_device, k_accum).  Otherwise a progressive pass (rtmi_render_samples_device, k_accum_samples): the running
 // per-pixel sums continue in accum, out_device (optional) receives the preview.  Batches and automatic streams are sized
 // from the paths of THIS call, npix * nsamples.
+// lp != nullptr (with accum): an adaptive pass over the pixels of lp->list, dealt out to the streams in contiguous chunks of
+// the list (the list kernels, k_accum_list).  Batches and automatic streams are then sized from lp->n * nsamples.
 static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile, uint32_t sample0,
-                       uint32_t nsamples, float4* accum, void* out_device, void* hip_stream, rtmi_stats_t* stats) {
+                       uint32_t nsamples, float4* accum, void* out_device, void* hip_stream, rtmi_stats_t* stats,
+                       const ListPass* lp = nullptr) {
     const uint32_t row0 = tile->row0, nrows = tile->nrows;
     if (stats) memset(stats, 0, sizeof(*stats));
     if (nrows == 0) return RTMI_OK;
@@ -1530,14 +1697,7 @@ static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed
     // query) must not make a launch below look refused: hipGetLastError() reports the last error of ANY runtime call
     (void)hipGetLastError();
     if (!out_device && !accum) return fail(RTMI_ERR_INVALID, "NULL argument");
-    if (vp->width == 0 || vp->height == 0) return fail(RTMI_ERR_INVALID, "empty viewport");
-    if (tile->stripe_rows == 0) return fail(RTMI_ERR_INVALID, "stripe_rows must be >= 1");
-    {
-        const uint64_t nstripes = ((uint64_t)nrows + tile->stripe_rows - 1) / tile->stripe_rows;
-        const uint64_t last_row = (uint64_t)row0 + (nstripes - 1) * tile->stripe_step + ((uint64_t)nrows - 1 - (nstripes - 1) * tile->stripe_rows);
-        if (last_row >= vp->height) return fail(RTMI_ERR_INVALID, "row range outside the viewport");
-        if (nstripes > 1 && tile->stripe_step < tile->stripe_rows) return fail(RTMI_ERR_INVALID, "stripes overlap");
-    }
+    if (const char* e = tile_error(vp, tile)) return fail(RTMI_ERR_INVALID, e);
     if (vp->samples_per_pixel == 0) return fail(RTMI_ERR_INVALID, "samples_per_pixel must be >= 1");  // reference: 1/0 -> NaN image
     if (vp->maxdepth > RTMI_MAX_PASSES) return fail(RTMI_ERR_UNSUPPORTED, "maxdepth above 32");
     if ((uint64_t)vp->width * vp->height >= (1ull << 32)) return fail(RTMI_ERR_UNSUPPORTED, "more than 2^32 pixels");
@@ -1566,10 +1726,14 @@ static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed
     // pipelines -- BVH mode: 29.6 ms on three streams, 35.2 on one -- have elementwise kernels to hide).  Since k_shade stopped being
     // atomic-bound (round 3) there is little left for a second stream to hide: the full config-3 frame takes 366.9 ms on one
     // stream and 371.8 on three (the sub-tiles' persistent launches compete for the same wave slots); a 1/8 tile 52.1 vs 51.6.
-    const uint32_t auto_streams = (path_kernels && npix * spp >= (1ull << 26)) ? 1u : 3u;
+    // adaptive passes: sized from the pass's own pixels, lp->n.  A refinement pass (fewer pixels than the tile) takes one
+    // stream: on config 3 its few hundred thousand pixels ran 6 % faster over the whole call on one stream than on three,
+    // and no slower at the other tolerances measured.
+    const uint64_t npix_call = lp ? (uint64_t)lp->n : npix;
+    const uint32_t auto_streams = ((path_kernels && npix_call * spp >= (1ull << 26)) || (lp && npix_call < npix)) ? 1u : 3u;
     uint32_t nsub = std::min<uint32_t>(s->tune.streams ? s->tune.streams : auto_streams, (uint32_t)RTMI_MAX_STREAMS);
-    nsub = std::min<uint32_t>(nsub, nrows);
-    if (npix * spp < s->tune.subtile_min_paths) nsub = 1;
+    nsub = (uint32_t)std::min<uint64_t>(nsub, lp ? npix_call : nrows);
+    if (npix_call * spp < s->tune.subtile_min_paths) nsub = 1;
     s->active_streams = nsub;
     SubTile sub[RTMI_MAX_STREAMS];
     for (uint32_t t = 0; t < nsub; t++) {
@@ -1581,9 +1745,14 @@ static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed
         dv.width = W; dv.height = vp->height; dv.maxdepth = maxdepth; dv.spp = spp;
         dv.row0 = row0; dv.stripe_rows = tile->stripe_rows; dv.stripe_step = tile->stripe_step;
         view_set_sampling(dv, sample0, vp->samples_per_pixel);
-        dv.sub_mul = nsub; dv.sub_off = t;
+        dv.sub_mul = lp ? 1u : nsub; dv.sub_off = lp ? 0u : t;  // list entries are tile-local pixel indices
         view_set_divisors(dv);
-        sub[t].npix = (uint64_t)((nrows - t + nsub - 1) / nsub) * W;
+        if (lp) {  // a contiguous chunk of the list: neighbouring pixels stay in the same waves
+            sub[t].base = (uint32_t)(npix_call * t / nsub);
+            sub[t].npix = npix_call * (t + 1) / nsub - sub[t].base;
+        } else {
+            sub[t].npix = (uint64_t)((nrows - t + nsub - 1) / nsub) * W;
+        }
         sub[t].index = t;
     }
 
@@ -1601,12 +1770,14 @@ static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed
     pix_per_batch = std::min<uint64_t>(pix_per_batch, max_sub_npix);
     if (pix_per_batch * spp >= (1ull << 31)) return fail(RTMI_ERR_UNSUPPORTED, "batch above 2^31 paths");
     for (uint32_t t = 0; t < nsub; t++) {
+        if (sub[t].npix == 0) continue;
         int rc = ensure_workspace(s->w[t], (size_t)(std::min<uint64_t>(pix_per_batch, sub[t].npix) * spp), maxdepth);
         if (rc != RTMI_OK) return rc;
     }
 
     const bool counting = (s->options & RTMI_OPT_COUNTERS) != 0;
     const bool prog = accum != nullptr;  // progressive pass: the *_samples kernels (sample numbers from sample0)
+    const uint32_t* list = lp ? lp->list : nullptr;  // adaptive pass: the *_list kernels
     const bool verbose = s->verbose;
     const unsigned ew_blocks = (unsigned)(s->num_cu * 8);
     float trace_ms = 0.f, primary_ms = 0.f, bounce_ms = 0.f;
@@ -1625,7 +1796,7 @@ static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed
             const DView& dv = sub[t].dv;
             const uint32_t np = (uint32_t)std::min<uint64_t>(pix_per_batch, sub[t].npix - p0);
             const uint32_t npaths = np * spp;
-            const uint32_t pix0 = (uint32_t)p0;  // local pixel index inside the sub-tile
+            const uint32_t pix0 = sub[t].base + (uint32_t)p0;  // local pixel index inside the sub-tile (list entry: adaptive)
             HIPCHK(hipMemsetAsync(w.ctrl.p, 0, sizeof(DCtrl), st));
             HIPCHK(hipEventRecord(w.ev[0], st));
             // the slow path: zero-component rays that k_path_primary and k_shade set aside, traced beside the following passes
@@ -1633,22 +1804,25 @@ static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed
             auto slow_after = [&](uint32_t k) {  // after producer k: k_path_primary (0) or the shading of pass k
                 if (sq.cap == 0u) return;
                 (void)hipEventRecord(w.sev[k], st);
-                if (counting && prog) launch_slow<true, true>(s, w, st, dv, seed, pix0, npaths, k);
+                if (counting && prog) launch_slow<true, true>(s, w, st, dv, seed, pix0, npaths, k, list);
                 else if (counting) launch_slow<true, false>(s, w, st, dv, seed, pix0, npaths, k);
-                else if (prog) launch_slow<false, true>(s, w, st, dv, seed, pix0, npaths, k);
+                else if (prog) launch_slow<false, true>(s, w, st, dv, seed, pix0, npaths, k, list);
                 else launch_slow<false, false>(s, w, st, dv, seed, pix0, npaths, k);
             };
             uint32_t pass0 = 0;  // first pass of the per-pass loop
             if (path_kernels) {
                 HIPCHK(hipEventRecord(w.pass_ev[0], st));
-                if (counting && prog) launch_primary<true, true>(s, w, st, dv, seed, pix0, npaths, w.pass_ev[1]);
+                if (counting && prog) launch_primary<true, true>(s, w, st, dv, seed, pix0, npaths, w.pass_ev[1], list);
                 else if (counting) launch_primary<true, false>(s, w, st, dv, seed, pix0, npaths, w.pass_ev[1]);
-                else if (prog) launch_primary<false, true>(s, w, st, dv, seed, pix0, npaths, w.pass_ev[1]);
+                else if (prog) launch_primary<false, true>(s, w, st, dv, seed, pix0, npaths, w.pass_ev[1], list);
                 else launch_primary<false, false>(s, w, st, dv, seed, pix0, npaths, w.pass_ev[1]);
                 HIPCHK(hipGetLastError());
                 launches++;
                 slow_after(0);
                 pass0 = 1;
+            } else if (list) {
+                hipLaunchKernelGGL(k_gen_list, dim3(ew_blocks), dim3(256), 0, st, dv, seed, pix0, npaths, w.qo[0].p, w.qd[0].p,
+                                   w.qpath[0].p, w.ctrl.p, list);
             } else {
                 hipLaunchKernelGGL(prog ? k_gen_samples : k_gen, dim3(ew_blocks), dim3(256), 0, st, dv, seed, pix0, npaths, w.qo[0].p, w.qd[0].p,
                                    w.qpath[0].p, w.ctrl.p);
@@ -1676,9 +1850,14 @@ static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed
                             (cur[8] - prev[t][8]) / n, (double)(cur[8] - prev[t][8]) / (64.0 * (cur[7] - prev[t][7] ? cur[7] - prev[t][7] : 1)));
                     memcpy(prev[t], cur, sizeof(s->vprev[t]));
                 }
-                hipLaunchKernelGGL(prog ? k_shade_samples : k_shade, dim3(ew_blocks), dim3(256), 0, st, s->d, dv, seed, pix0, npaths, (int)pass,
-                                   w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p,
-                                   w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq);
+                if (list)
+                    hipLaunchKernelGGL(k_shade_list, dim3(ew_blocks), dim3(256), 0, st, s->d, dv, seed, pix0, npaths, (int)pass,
+                                       w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p,
+                                       w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, list);
+                else
+                    hipLaunchKernelGGL(prog ? k_shade_samples : k_shade, dim3(ew_blocks), dim3(256), 0, st, s->d, dv, seed, pix0, npaths, (int)pass,
+                                       w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p,
+                                       w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq);
                 HIPCHK(hipGetLastError());
                 if (pass + 1 < maxdepth) {  // the last pass's shading emits no rays
                     slow_after(pass);
@@ -1690,7 +1869,10 @@ static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed
                 HIPCHK(hipEventRecord(w.sdone, w.sstream));
                 HIPCHK(hipStreamWaitEvent(st, w.sdone, 0));
             }
-            if (!accum)
+            if (list)
+                hipLaunchKernelGGL(k_accum_list, dim3(ew_blocks), dim3(256), 0, st, np, spp, sample0, w.scol.p, (float*)accum,
+                                   (float*)lp->sumsq, lp->counts, (float*)out, list, pix0);
+            else if (!accum)
                 hipLaunchKernelGGL(k_accum, dim3(ew_blocks), dim3(256), 0, st, np, spp, w.scol.p, (float*)out, pix0, W, nsub, t, make_fastdiv(W));
             else
                 hipLaunchKernelGGL(k_accum_samples, dim3(ew_blocks), dim3(256), 0, st, np, spp, sample0, w.scol.p, (float*)accum,
@@ -1786,6 +1968,140 @@ int rtmi_render_samples(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t see
     if (rc != RTMI_OK) return rc;
     HIPCHK(hipMemcpy(accum_host, s->acc.p, npix * sizeof(float4), hipMemcpyDeviceToHost));
     if (out_host) HIPCHK(hipMemcpy(out_host, s->tile.p, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+// ---------------------------------------------------------------- adaptive sampling
+// Checks of the adaptive entry points that come before any HIP call (a CPU-only caller reaches them).  bufs: the caller's
+// buffers, nbufs of them, none NULL except an optional last one (out); no two may be the same.
+static int check_adaptive(rtmi_scene_t* s, const rtmi_viewport_t* vp, const rtmi_adaptive_t* ad, const void* const* bufs,
+                          int nbufs, bool last_optional) {
+    if (!s || !vp) return fail(RTMI_ERR_INVALID, "NULL argument (scene or viewport)");
+    if (!ad) return fail(RTMI_ERR_INVALID, "NULL argument (rtmi_adaptive_t)");
+    const uint32_t S = vp->samples_per_pixel;
+    if (S < 2) return fail(RTMI_ERR_INVALID, "adaptive sampling needs samples_per_pixel >= 2");
+    if (ad->min_samples < 2 || ad->min_samples > S) return fail(RTMI_ERR_INVALID, "min_samples must be in [2, samples_per_pixel]");
+    if (ad->pass_samples == 0) return fail(RTMI_ERR_INVALID, "pass_samples must be >= 1");
+    if (S & RTMI_KEY_JITTER) return fail(RTMI_ERR_UNSUPPORTED, "samples_per_pixel above 2^31");  // DView::sample_key
+    for (int i = 0; i < nbufs; i++) {
+        if (!bufs[i] && !(last_optional && i == nbufs - 1)) return fail(RTMI_ERR_INVALID, "NULL buffer (accum, sumsq and counts are required)");
+        for (int j = 0; j < i; j++)
+            if (bufs[i] && bufs[i] == bufs[j]) return fail(RTMI_ERR_INVALID, "buffers must not alias (accum, sumsq, counts, out)");
+    }
+    return RTMI_OK;
+}
+
+// The passes of one adaptive call on device buffers (checked): pass 0 renders samples [0, m) of the whole tile; after each
+// pass k_adapt_* apply the stop rule to the active pixels and compact the survivors into the next list, whose length
+// (4 bytes) is read back to size the next pass.  Everything is enqueued on `ust`; every pass ends synchronised.
+static int render_adaptive(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile,
+                           rtmi_adaptive_t* ad, float4* accum, float4* sumsq, uint32_t* counts, float4* out, hipStream_t ust,
+                           rtmi_stats_t* stats) {
+    ad->passes = 0; ad->unconverged = 0; ad->samples = 0;
+    if (tile->nrows == 0) return RTMI_OK;
+    RTMI_GUARD_BEGIN
+    (void)hipGetLastError();
+    if (const char* e = tile_error(vp, tile)) return fail(RTMI_ERR_INVALID, e);
+    if ((uint64_t)vp->width * vp->height >= (1ull << 32)) return fail(RTMI_ERR_UNSUPPORTED, "more than 2^32 pixels");
+    if (vp->maxdepth > RTMI_MAX_PASSES) return fail(RTMI_ERR_UNSUPPORTED, "maxdepth above 32");
+    HIPCHK(hipSetDevice(s->device));
+    const uint32_t S = vp->samples_per_pixel, m = ad->min_samples, p = ad->pass_samples;
+    const uint32_t npix = (uint32_t)((uint64_t)tile->nrows * vp->width);
+    if (vp->maxdepth == 0) {  // every sample is black: zero variance, every pixel stops at m
+        HIPCHK(hipMemsetAsync(accum, 0, (size_t)npix * sizeof(float4), ust));
+        HIPCHK(hipMemsetAsync(sumsq, 0, (size_t)npix * sizeof(float4), ust));
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)counts, (int)m, npix, ust));
+        if (out) HIPCHK(hipMemsetAsync(out, 0, (size_t)npix * sizeof(float4), ust));
+        HIPCHK(hipStreamSynchronize(ust));
+        ad->passes = 1; ad->samples = (uint64_t)npix * m;
+        return RTMI_OK;
+    }
+    const uint32_t nblk = (npix + RTMI_ADAPT_BLOCK - 1) / RTMI_ADAPT_BLOCK;
+    HIPCHK(s->alist[0].ensure(npix));
+    HIPCHK(s->alist[1].ensure(npix));
+    HIPCHK(s->ablk.ensure((size_t)nblk + 1));
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    HIPCHK(hipEventCreate(&ev0));
+    struct EvGuard { hipEvent_t& a; hipEvent_t& b; ~EvGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } evg{ev0, ev1};
+    HIPCHK(hipEventCreate(&ev1));
+    HIPCHK(hipEventRecord(ev0, ust));
+    const unsigned ew_blocks = (unsigned)(s->num_cu * 8);
+    hipLaunchKernelGGL(k_adapt_init, dim3(std::min<unsigned>(ew_blocks, (npix + 255) / 256)), dim3(256), 0, ust, npix, s->alist[0].p);
+    HIPCHK(hipGetLastError());
+    uint32_t n0 = 0, k = m, nact = npix, cur = 0, streams = 0;
+    for (;;) {
+        const ListPass lp{s->alist[cur].p, nact, sumsq, counts};
+        rtmi_stats_t ps;
+        int rc = render_tile(s, vp, seed, tile, n0, k, accum, out, ust, &ps, &lp);
+        if (rc != RTMI_OK) return rc;
+        ad->passes++;
+        ad->samples += (uint64_t)nact * k;
+        if (stats) {
+            stats->rays += ps.rays; stats->box_tests += ps.box_tests; stats->tri_tests += ps.tri_tests;
+            stats->full_tests += ps.full_tests; stats->nodes += ps.nodes; stats->leaves += ps.leaves;
+            stats->slow_paths += ps.slow_paths; stats->trace_ms += ps.trace_ms; stats->trace_launches += ps.trace_launches;
+            stats->primary_ms += ps.primary_ms; stats->bounce_ms += ps.bounce_ms; stats->pipeline = ps.pipeline;
+        }
+        streams = std::max(streams, ps.streams);
+        const uint32_t n = n0 + k;
+        // the stop rule on the pass's pixels; at n == S they all stop, and the survivors' count is the unconverged pixels
+        const unsigned nb = (nact + RTMI_ADAPT_BLOCK - 1) / RTMI_ADAPT_BLOCK;
+        hipLaunchKernelGGL(k_adapt_count, dim3(nb), dim3(RTMI_ADAPT_BLOCK), 0, ust, s->alist[cur].p, nact, accum, sumsq, n,
+                           ad->rel_tol, ad->abs_tol, s->ablk.p);
+        hipLaunchKernelGGL(k_adapt_scan, dim3(1), dim3(256), 0, ust, s->ablk.p, (uint32_t)nb);
+        if (n < S)
+            hipLaunchKernelGGL(k_adapt_scatter, dim3(nb), dim3(RTMI_ADAPT_BLOCK), 0, ust, s->alist[cur].p, nact, accum, sumsq, n,
+                               ad->rel_tol, ad->abs_tol, s->ablk.p, s->alist[cur ^ 1].p);
+        HIPCHK(hipGetLastError());
+        uint32_t next = 0;
+        HIPCHK(hipMemcpyAsync(&next, s->ablk.p + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, ust));
+        HIPCHK(hipStreamSynchronize(ust));
+        if (n >= S) { ad->unconverged = next; break; }
+        if (next == 0) break;
+        nact = next; cur ^= 1u; n0 = n; k = std::min(p, S - n);
+    }
+    HIPCHK(hipEventRecord(ev1, ust));
+    HIPCHK(hipEventSynchronize(ev1));
+    float kernel_ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&kernel_ms, ev0, ev1));
+    if (stats) { stats->kernel_ms = kernel_ms; stats->streams = streams; }
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+int rtmi_render_adaptive_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile,
+                                rtmi_adaptive_t* ad, void* accum_device, void* sumsq_device, void* counts_device, void* out_device,
+                                void* hip_stream, rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    const void* bufs[4] = {accum_device, sumsq_device, counts_device, out_device};
+    const int rc = check_adaptive(s, vp, ad, bufs, 4, true);
+    if (rc != RTMI_OK) return rc;
+    if (!tile) return fail(RTMI_ERR_INVALID, "NULL argument (tile)");
+    return render_adaptive(s, vp, seed, tile, ad, (float4*)accum_device, (float4*)sumsq_device, (uint32_t*)counts_device,
+                           (float4*)out_device, (hipStream_t)hip_stream, stats);
+}
+
+// Host variant: accum and sumsq stay on the device; out and counts are copied back once at the end.
+int rtmi_render_adaptive(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
+                         rtmi_adaptive_t* ad, float* out_host, uint32_t* counts_host, rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    const void* bufs[2] = {out_host, counts_host};
+    const int rc0 = check_adaptive(s, vp, ad, bufs, 2, false);
+    if (rc0 != RTMI_OK) return rc0;
+    ad->passes = 0; ad->unconverged = 0; ad->samples = 0;
+    const uint64_t npix = (uint64_t)nrows * vp->width;
+    if (npix == 0) return RTMI_OK;
+    if ((uint64_t)row0 + nrows > vp->height) return fail(RTMI_ERR_INVALID, "row range outside the viewport");
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(s->acc.ensure(npix));
+    HIPCHK(s->asq.ensure(npix));
+    HIPCHK(s->acnt.ensure(npix));
+    HIPCHK(s->tile.ensure(npix));
+    const rtmi_tile_t tile{row0, nrows, nrows, 0u};
+    int rc = render_adaptive(s, vp, seed, &tile, ad, s->acc.p, s->asq.p, s->acnt.p, s->tile.p, nullptr, stats);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(hipMemcpy(out_host, s->tile.p, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(counts_host, s->acnt.p, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
 

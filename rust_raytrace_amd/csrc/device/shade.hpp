@@ -62,11 +62,15 @@ __device__ inline void tile_pixel(const DView& v, uint32_t lp, uint32_t& row, ui
 // number (the RNG key).  PROG: a progressive pass renders samples [sample0, sample0 + spp) of its pixels; otherwise the
 // call renders all of them (sample0 = 0, and the kernel does not spend the add and the register on it: 2 % of config 3's
 // frame time when it did).
-template <bool PROG>
-__device__ inline void path_pixel(const DView& v, uint32_t pix0, uint32_t path, uint32_t& row, uint32_t& col, uint32_t& sample) {
+// LIST (adaptive passes, always with PROG): the batch's pixels are entries pix0, pix0 + 1, ... of the active-pixel list, each
+// a tile-local pixel index (row-major over the tile's rows; the launch's DView has sub_mul = 1, sub_off = 0).  The list
+// pointer is an argument of the list kernels only, so the other kernels keep their launch constants.
+template <bool PROG, bool LIST = false>
+__device__ inline void path_pixel(const DView& v, uint32_t pix0, uint32_t path, uint32_t& row, uint32_t& col, uint32_t& sample,
+                                  const uint32_t* __restrict__ list = nullptr) {
     const uint32_t q = fdiv(path, v.dspp);
     sample = (PROG ? (v.sample_key & ~RTMI_KEY_JITTER) : 0u) + (path - q * v.spp);
-    tile_pixel(v, pix0 + q, row, col);
+    tile_pixel(v, LIST ? list[pix0 + q] : pix0 + q, row, col);
 }
 
 struct RayV { V4 orig, dir; };

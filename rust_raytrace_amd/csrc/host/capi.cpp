@@ -261,6 +261,34 @@ int rth_caster_walk_samples_device(rth_scene_t* s, uint32_t w, uint32_t h, const
         if (stats) *stats = ctx.stats;
     });
 }
+int rth_caster_walk_adaptive(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                             uint64_t row0, uint64_t nrows, rtmi_adaptive_t* ad, float* out_host, uint32_t* counts_host,
+                             rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!ad) throw std::runtime_error("NULL rtmi_adaptive_t");
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_adaptive(v, s->scene, (size_t)row0, (size_t)nrows, *ad, reinterpret_cast<Color*>(out_host), counts_host, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
+int rth_caster_walk_adaptive_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                                    const rtmi_tile_t* tile, rtmi_adaptive_t* ad, void* accum_device, void* sumsq_device,
+                                    void* counts_device, void* out_device, void* hip_stream, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!tile) throw std::runtime_error("NULL tile");
+        if (!ad) throw std::runtime_error("NULL rtmi_adaptive_t");
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_adaptive_device(v, s->scene, *tile, *ad, accum_device, sumsq_device, counts_device, out_device,
+                                          hip_stream, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
 int rth_caster_trace(rth_scene_t* s, uint64_t n, const float* o4, const float* d4, uint32_t* tri, float* t, uint32_t* face,
                      rtmi_stats_t* stats) {
     return guarded([&] {

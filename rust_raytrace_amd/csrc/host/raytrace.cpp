@@ -693,6 +693,32 @@ void HipRayCaster::walk_samples_device(const Viewport& v, const Scene& s, const 
     progress.stats = st;
 }
 
+void HipRayCaster::walk_adaptive(const Viewport& v, const Scene& s, size_t row0, size_t nrows, rtmi_adaptive_t& ad, Color* out,
+                                 uint32_t* counts, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_adaptive(h, &av, seed, (uint32_t)row0, (uint32_t)nrows, &ad, reinterpret_cast<float*>(out), counts, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_adaptive: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
+void HipRayCaster::walk_adaptive_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, rtmi_adaptive_t& ad,
+                                        void* accum_device, void* sumsq_device, void* counts_device, void* out_device,
+                                        void* hip_stream, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_adaptive_device(h, &av, seed, &tile, &ad, accum_device, sumsq_device, counts_device, out_device,
+                                               hip_stream, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_adaptive_device: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
 void HipRayCaster::walk_rows(const Viewport& v, const Scene& s, size_t row0, size_t nrows, Color* data, ProgressCtx& progress) {
     rtmi_scene_t* h = resident(s);
     const rtmi_viewport_t av = to_abi(v);

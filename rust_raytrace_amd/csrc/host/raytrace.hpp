@@ -197,6 +197,12 @@ public:
                       Color* accum, Color* out, ProgressCtx& progress);
     void walk_samples_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
                              void* accum_device, void* out_device, void* hip_stream, ProgressCtx& progress);
+    // Adaptive sampling (rtmi_render_adaptive / rtmi_render_adaptive_device): every pixel stops at its own count between
+    // ad.min_samples and v.samples_per_pixel and equals the pixel of walk_rows at that many samples; counts receives them.
+    void walk_adaptive(const Viewport& v, const Scene& s, size_t row0, size_t nrows, rtmi_adaptive_t& ad, Color* out,
+                       uint32_t* counts, ProgressCtx& progress);
+    void walk_adaptive_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, rtmi_adaptive_t& ad, void* accum_device,
+                              void* sumsq_device, void* counts_device, void* out_device, void* hip_stream, ProgressCtx& progress);
     void set_options(uint32_t opts) { options_ = opts; }
     // Per-ray records of the production walk (rtmi_trace_records / rtmi_primary_records, on the first device): explicit
     // rays (n x 4 floats each), or sample `sample` of every pixel of rows [row0, row0 + nrows).  Throws on unsupported scenes.

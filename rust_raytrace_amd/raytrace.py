@@ -470,6 +470,70 @@ class HipRayCaster:
                 break
         return ctx
 
+    # Default stop tolerances of walk_rays_adaptive: the standard error of a pixel's mean must fall below
+    # half an 8-bit step of the PNG output (write_png's `(c * 255.) as u8`) plus 1 % of its brightest channel.
+    ADAPTIVE_REL_TOL = 0.01
+    ADAPTIVE_ABS_TOL = 0.5 / 255.0
+
+    @staticmethod
+    def _adaptive(v, min_samples, pass_samples, rel_tol, abs_tol):
+        spp, m, p = int(v.samples_per_pixel), int(min_samples), int(pass_samples)
+        if spp < 2:
+            raise ValueError("adaptive sampling needs samples_per_pixel >= 2")
+        if not 2 <= m <= spp:
+            raise ValueError("min_samples must be in [2, samples_per_pixel]")
+        if p < 1:
+            raise ValueError("pass_samples must be >= 1")
+        return _ffi.Adaptive(m, p, float(rel_tol), float(abs_tol))
+
+    @staticmethod
+    def _adaptive_ctx(st, wall, ad):
+        ctx = ProgressCtx(st.rays, wall.value, st.as_dict())
+        ctx.passes, ctx.unconverged, ctx.samples = ad.passes, ad.unconverged, ad.samples
+        return ctx
+
+    def walk_rays_adaptive(self, v, s, data, min_samples=8, pass_samples=8, rel_tol=None, abs_tol=None, counts=None):
+        """Adaptive sampling (rtmi_render_adaptive): v.samples_per_pixel is the most samples a pixel gets.  Every pixel gets
+        samples [0, min_samples), then passes of pass_samples more until its stop rule holds (include/rtmi.h) or it reaches
+        samples_per_pixel.  data ((H, W, 4) f32) receives every pixel at its own count, bit-identical to walk_rays at
+        samples_per_pixel = that count.  counts (optional, (H, W) uint32) receives the count map; it is also returned as
+        ctx.counts, with ctx.passes, ctx.samples (the sum of counts) and ctx.unconverged (pixels that reached
+        samples_per_pixel without stopping).  abs_tol = NaN runs every pixel to samples_per_pixel (in passes), +inf stops
+        every pixel at min_samples.  Defaults: ADAPTIVE_REL_TOL, ADAPTIVE_ABS_TOL."""
+        if data.dtype != np.float32 or not data.flags.c_contiguous or data.size != v.height * v.width * 4:
+            raise ValueError("data must be a C-contiguous float32 array of height*width*4 elements")
+        if counts is None:
+            counts = np.zeros((v.height, v.width), np.uint32)
+        elif counts.dtype != np.uint32 or not counts.flags.c_contiguous or counts.size != v.height * v.width:
+            raise ValueError("counts must be a C-contiguous uint32 array of height*width elements")
+        ad = self._adaptive(v, min_samples, pass_samples, self.ADAPTIVE_REL_TOL if rel_tol is None else rel_tol,
+                            self.ADAPTIVE_ABS_TOL if abs_tol is None else abs_tol)
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_adaptive(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, 0, v.height,
+                                                 C.byref(ad), _p(data), _p(counts), C.byref(st), C.byref(wall)))
+        ctx = self._adaptive_ctx(st, wall, ad)
+        ctx.counts = counts
+        return ctx
+
+    def walk_adaptive_device(self, v, s, tile, accum_ptr, sumsq_ptr, counts_ptr, out_ptr=None, stream_ptr=None, min_samples=8,
+                             pass_samples=8, rel_tol=None, abs_tol=None):
+        """The same on device memory (rtmi_render_adaptive_device) for a striped row set tile = (row0, nrows, stripe_rows,
+        stripe_step), enqueued on HIP stream `stream_ptr`: accum / sumsq (one float4 per pixel of the tile), counts (one
+        uint32 per pixel) and out (optional) stay on the device.  Returns ctx with passes, unconverged and samples."""
+        ad = self._adaptive(v, min_samples, pass_samples, self.ADAPTIVE_REL_TOL if rel_tol is None else rel_tol,
+                            self.ADAPTIVE_ABS_TOL if abs_tol is None else abs_tol)
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        t = _ffi.Tile(*[int(x) for x in tile])
+        _chk(_ffi.lib().rth_caster_walk_adaptive_device(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel,
+                                                        C.byref(t), C.byref(ad), C.c_void_p(accum_ptr), C.c_void_p(sumsq_ptr),
+                                                        C.c_void_p(counts_ptr), C.c_void_p(out_ptr or 0),
+                                                        C.c_void_p(stream_ptr or 0), C.byref(st), C.byref(wall)))
+        return self._adaptive_ctx(st, wall, ad)
+
     def quantize_device(self, s, rgba_ptr, npixels, rgb_ptr, stream_ptr=None):
         """write_png's `(c * 255.) as u8` on device memory (f32x4 -> u8x3), enqueued on the stream."""
         self._config(s)
