@@ -492,40 +492,27 @@ __global__ void __launch_bounds__(256) k_trace_linear(DScene sc, const float4* _
 
 // ---------------------------------------------------------------- generation / shading (per-pass pipeline)
 // pixel_ray / color_ray themselves are in shade.hpp (shared with the path kernels of trace_oct.hpp).
-// PROG = true: the kernels of progressive passes (k_gen_samples, k_shade_samples), whose sample numbers start at sample0.
-// LIST = true (with PROG): adaptive passes (k_gen_list, k_shade_list), whose pixels come from the active-pixel list.
-template <bool PROG, bool LIST = false>
-__device__ __forceinline__ void gen_paths(const DView& v, uint64_t seed, uint32_t pix0, uint32_t npaths, float4* __restrict__ qo,
-                                          float4* __restrict__ qd, uint32_t* __restrict__ qpath, DCtrl* __restrict__ ctrl,
-                                          const uint32_t* __restrict__ list = nullptr) {
+// S (shade.hpp): k_gen / k_shade are Samp::FRAME, k_gen_samples / k_shade_samples PASS, k_gen_list / k_shade_list LIST.
+#define RTMI_GEN_PARAMS uint64_t seed, uint32_t pix0, uint32_t npaths, float4* __restrict__ qo, float4* __restrict__ qd, \
+                        uint32_t* __restrict__ qpath, DCtrl* __restrict__ ctrl
+#define RTMI_GEN_ARGS v, seed, pix0, npaths, qo, qd, qpath, ctrl
+template <Samp S>
+__device__ __forceinline__ void gen_paths(const DView& v, RTMI_GEN_PARAMS, const uint32_t* __restrict__ list = nullptr) {
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t path = blockIdx.x * blockDim.x + threadIdx.x; path < npaths; path += stride) {
         uint32_t row, col, sample;
-        path_pixel<PROG, LIST>(v, pix0, path, row, col, sample, list);
+        path_pixel<S>(v, pix0, path, row, col, sample, list);
         const uint32_t pixel = row * v.width + col;
-        RayV r = pixel_ray<PROG>(v, row, col, seed, pixel, sample);
+        RayV r = pixel_ray<S>(v, row, col, seed, pixel, sample);
         qo[path] = make_float4(r.orig.x, r.orig.y, r.orig.z, r.orig.w);
         qd[path] = make_float4(r.dir.x, r.dir.y, r.dir.z, r.dir.w);
         qpath[path] = path;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) ctrl->count[0] = npaths;
 }
-__global__ void __launch_bounds__(256) k_gen(DView v, uint64_t seed, uint32_t pix0, uint32_t npaths,
-                                             float4* __restrict__ qo, float4* __restrict__ qd,
-                                             uint32_t* __restrict__ qpath, DCtrl* __restrict__ ctrl) {
-    gen_paths<false>(v, seed, pix0, npaths, qo, qd, qpath, ctrl);
-}
-__global__ void __launch_bounds__(256) k_gen_samples(DView v, uint64_t seed, uint32_t pix0, uint32_t npaths,
-                                                     float4* __restrict__ qo, float4* __restrict__ qd,
-                                                     uint32_t* __restrict__ qpath, DCtrl* __restrict__ ctrl) {
-    gen_paths<true>(v, seed, pix0, npaths, qo, qd, qpath, ctrl);
-}
-__global__ void __launch_bounds__(256) k_gen_list(DView v, uint64_t seed, uint32_t pix0, uint32_t npaths,
-                                                  float4* __restrict__ qo, float4* __restrict__ qd,
-                                                  uint32_t* __restrict__ qpath, DCtrl* __restrict__ ctrl,
-                                                  const uint32_t* __restrict__ list) {
-    gen_paths<true, true>(v, seed, pix0, npaths, qo, qd, qpath, ctrl, list);
-}
+__global__ void __launch_bounds__(256) k_gen(DView v, RTMI_GEN_PARAMS) { gen_paths<Samp::FRAME>(RTMI_GEN_ARGS); }
+__global__ void __launch_bounds__(256) k_gen_samples(DView v, RTMI_GEN_PARAMS) { gen_paths<Samp::PASS>(RTMI_GEN_ARGS); }
+__global__ void __launch_bounds__(256) k_gen_list(DView v, RTMI_GEN_PARAMS, const uint32_t* __restrict__ list) { gen_paths<Samp::LIST>(RTMI_GEN_ARGS, list); }
 
 // color_ray + the tail of project_ray for every ray of pass `pass`.
 #define RTMI_SHADE_PARAMS DScene sc, DView v, uint64_t seed, uint32_t pix0, uint32_t npaths, int pass,                  \
@@ -535,7 +522,7 @@ __global__ void __launch_bounds__(256) k_gen_list(DView v, uint64_t seed, uint32
                           uint32_t* __restrict__ qpath_n, uint16_t* __restrict__ mstack, float4* __restrict__ scol,    \
                           DCtrl* __restrict__ ctrl, SlowQ slow
 #define RTMI_SHADE_ARGS sc, v, seed, pix0, npaths, pass, qo, qd, qpath, hit_tf, hit_t, qo_n, qd_n, qpath_n, mstack, scol, ctrl, slow
-template <bool PROG, bool LIST = false>
+template <Samp S>
 __device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list = nullptr) {
     __shared__ uint32_t s_cnt[4], s_base;
     const uint32_t count = ctrl->count[pass];
@@ -557,7 +544,7 @@ __device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __
             float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f), d4 = make_float4(0.f, 0.f, 1.f, 0.f);
             if ((tf & 0x3FFFFFFFu) != 0u && !((tf >> 30) & 2u)) { t = hit_t[i]; o4 = qo[i]; d4 = qd[i]; }
             uint32_t prow, pcol, sample;
-            path_pixel<PROG, LIST>(v, pix0, path, prow, pcol, sample, list);
+            path_pixel<S>(v, pix0, path, prow, pcol, sample, list);
             push = shade_hit(sc, v.maxdepth, seed, npaths, path, prow * v.width + pcol, sample, (uint32_t)pass, tf, t,
                              V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr);
             // a bounce ray with an exactly-zero direction component goes to the slow path (SlowQ), not to the next pass
@@ -590,11 +577,9 @@ __device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __
         __syncthreads();  // s_cnt / s_base are rewritten by the next iteration
     }
 }
-__global__ void __launch_bounds__(256) k_shade(RTMI_SHADE_PARAMS) { shade_pass<false>(RTMI_SHADE_ARGS); }
-__global__ void __launch_bounds__(256) k_shade_samples(RTMI_SHADE_PARAMS) { shade_pass<true>(RTMI_SHADE_ARGS); }
-__global__ void __launch_bounds__(256) k_shade_list(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list) {
-    shade_pass<true, true>(RTMI_SHADE_ARGS, list);
-}
+__global__ void __launch_bounds__(256) k_shade(RTMI_SHADE_PARAMS) { shade_pass<Samp::FRAME>(RTMI_SHADE_ARGS); }
+__global__ void __launch_bounds__(256) k_shade_samples(RTMI_SHADE_PARAMS) { shade_pass<Samp::PASS>(RTMI_SHADE_ARGS); }
+__global__ void __launch_bounds__(256) k_shade_list(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list) { shade_pass<Samp::LIST>(RTMI_SHADE_ARGS, list); }
 
 // walk_ray_set's per-pixel accumulation (raytrace.rs:1414-1426): acc = 0; acc += sample_i in sample order; * (1/spp).
 // The sample colours of a pixel are consecutive in `scol` ([pixel][sample]), so one thread per pixel would read 16 B at a
@@ -607,12 +592,12 @@ __global__ void __launch_bounds__(256) k_shade_list(RTMI_SHADE_PARAMS, const uin
 // the sub-tile is row lr * nsub + sub of the buffer.
 #define RTMI_ACC_PIX 64
 #define RTMI_ACC_CHUNK 1024
-// RESUME = false: k_accum, the sum starts at 0.f and out = sum * inv.  RESUME = true: k_accum_samples (progressive passes),
-// the sum starts from accum when `resume`, is written back to accum, and out (when not NULL) = sum * inv.
-// LIST = true (with RESUME): k_accum_list (adaptive passes): the block's pixels are list[pix0 + pb + j], tile-local pixel
-// indices (= their float4 in accum / sumsq / out); the per-lane sum of squares q = q + c * c continues in sumsq beside the
-// sum, and counts[pixel] receives `ncount`, the pixel's samples after this pass.
-template <bool RESUME, bool LIST = false>
+// Samp::FRAME: k_accum, the sum starts at 0.f and out = sum * inv.  PASS: k_accum_samples (progressive passes), the sum
+// starts from accum when `resume`, is written back to accum, and out (when not NULL) = sum * inv.
+// LIST: k_accum_list (adaptive passes), a PASS whose block's pixels are list[pix0 + pb + j], tile-local pixel indices (= their
+// float4 in accum / sumsq / out); the per-lane sum of squares q = q + c * c continues in sumsq beside the sum, and
+// counts[pixel] receives `ncount`, the pixel's samples after this pass.
+template <Samp S>
 __device__ __forceinline__ void accum_pixels(uint32_t npixels, uint32_t spp, const float4* __restrict__ scol, float* __restrict__ out,
                                              float* __restrict__ accum, bool resume, float inv, uint32_t pix0, uint32_t W,
                                              uint32_t nsub, uint32_t sub, FastDiv dW, const uint32_t* __restrict__ list = nullptr,
@@ -625,16 +610,16 @@ __device__ __forceinline__ void accum_pixels(uint32_t npixels, uint32_t spp, con
         const uint32_t npb = min((uint32_t)RTMI_ACC_PIX, npixels - pb);
         const uint32_t f0 = pb * spp, f1 = f0 + npb * spp;       // the block's samples: scol[f0 .. f1)
         const uint32_t my0 = f0 + j * spp, my1 = my0 + spp;      // this thread's pixel (when j < npb)
-        size_t o = 0;                                            // RESUME: this thread's float in accum / out
+        size_t o = 0;                                            // PASS / LIST: this thread's float in accum / out
         float acc = 0.f, sq = 0.f;                               // sq: LIST only
         uint32_t lpix = 0;                                       // LIST: the tile-local pixel
-        if (LIST) {
+        if (S == Samp::LIST) {
             if (j < npb) {
                 lpix = list[pix0 + pb + j];
                 o = (size_t)lpix * 4u + c;
                 if (resume) { acc = accum[o]; sq = sumsq[o]; }
             }
-        } else if (RESUME && j < npb) {
+        } else if (S == Samp::PASS && j < npb) {
             const uint32_t lp = pix0 + pb + j, lr = fdiv(lp, dW), col = lp - lr * W;
             o = (((size_t)lr * nsub + sub) * W + col) * 4u + c;
             if (resume) acc = accum[o];
@@ -650,14 +635,14 @@ __device__ __forceinline__ void accum_pixels(uint32_t npixels, uint32_t spp, con
                     const uint32_t k = s - ch;
                     const float x = stage_f[(k + (k >> 6)) * 4u + c];
                     acc = acc + x;
-                    if (LIST) sq = sq + x * x;
+                    if (S == Samp::LIST) sq = sq + x * x;
                 }
             }
         }
         if (j < npb) {
-            if (RESUME) {
+            if (S != Samp::FRAME) {
                 accum[o] = acc;
-                if (LIST) {
+                if (S == Samp::LIST) {
                     sumsq[o] = sq;
                     if (c == 0u) counts[lpix] = ncount;
                 }
@@ -673,7 +658,7 @@ __device__ __forceinline__ void accum_pixels(uint32_t npixels, uint32_t spp, con
 __global__ void __launch_bounds__(256) k_accum(uint32_t npixels, uint32_t spp, const float4* __restrict__ scol,
                                                float* __restrict__ out, uint32_t pix0, uint32_t W, uint32_t nsub, uint32_t sub,
                                                FastDiv dW) {
-    accum_pixels<false>(npixels, spp, scol, out, nullptr, false, 1.f / (float)spp, pix0, W, nsub, sub, dW);
+    accum_pixels<Samp::FRAME>(npixels, spp, scol, out, nullptr, false, 1.f / (float)spp, pix0, W, nsub, sub, dW);
 }
 // Samples [sample0, sample0 + nsamples) of every pixel: continuing the running sum of samples [0, sample0) in accum performs
 // the same f32 additions in the same order as k_accum over all samples, so the passes of a frame end in the same bits.
@@ -681,7 +666,7 @@ __global__ void __launch_bounds__(256) k_accum(uint32_t npixels, uint32_t spp, c
 __global__ void __launch_bounds__(256) k_accum_samples(uint32_t npixels, uint32_t nsamples, uint32_t sample0, const float4* __restrict__ scol,
                                                        float* __restrict__ accum, float* __restrict__ out, uint32_t pix0, uint32_t W,
                                                        uint32_t nsub, uint32_t sub, FastDiv dW) {
-    accum_pixels<true>(npixels, nsamples, scol, out, accum, sample0 != 0u, 1.f / (float)(sample0 + nsamples), pix0, W, nsub, sub, dW);
+    accum_pixels<Samp::PASS>(npixels, nsamples, scol, out, accum, sample0 != 0u, 1.f / (float)(sample0 + nsamples), pix0, W, nsub, sub, dW);
 }
 // Adaptive passes: samples [sample0, sample0 + nsamples) of the list's pixels pix0 .. pix0 + npixels - 1.  Every pixel of the
 // list has had exactly sample0 samples, so the sum and the sum of squares continue in sample order from 0.f (sample0 == 0)
@@ -690,7 +675,7 @@ __global__ void __launch_bounds__(256) k_accum_list(uint32_t npixels, uint32_t n
                                                     float* __restrict__ accum, float* __restrict__ sumsq, uint32_t* __restrict__ counts,
                                                     float* __restrict__ out, const uint32_t* __restrict__ list, uint32_t pix0) {
     const uint32_t n = sample0 + nsamples;
-    accum_pixels<true, true>(npixels, nsamples, scol, out, accum, sample0 != 0u, 1.f / (float)n, pix0, 0u, 0u, 0u, FastDiv{},
+    accum_pixels<Samp::LIST>(npixels, nsamples, scol, out, accum, sample0 != 0u, 1.f / (float)n, pix0, 0u, 0u, 0u, FastDiv{},
                              list, sumsq, counts, n);
 }
 
@@ -1525,33 +1510,41 @@ static dim3 oct_grid(const rtmi_scene* s) {
     return dim3((unsigned)(s->num_cu * per_cu));
 }
 
-extern "C++" {
-template <bool COUNT>
-static void launch_trace(rtmi_scene* s, Work& w, hipStream_t st, const float4* qo, const float4* qd, int pass, hipEvent_t stop) {
+// The octree walk kernels of trace_oct.hpp as [count][fast] of their <bool COUNT, bool FAST> templates.  A batch's path
+// kernels follow its sampling mode (shade.hpp): k_path_primary / k_path_slow for Samp::FRAME, the *_samples kernels for
+// PASS, the *_list kernels for LIST; these take the list as one more argument and so have a function type of their own.
+#define RTMI_COUNT_FAST(k) {{k<false, false>, k<false, true>}, {k<true, false>, k<true, true>}}
+typedef void (*WalkKernel)(DScene, OctArgs, DCtrl*, int, int);
+typedef void (*ListWalkKernel)(DScene, OctArgs, DCtrl*, int, int, const uint32_t*);
+static const WalkKernel trace_oct_variant[2][2] = RTMI_COUNT_FAST(k_trace_oct);
+static const WalkKernel path_variant[2][2][2][2] = {  // [slow][mode == Samp::PASS][count][fast]
+    {RTMI_COUNT_FAST(k_path_primary), RTMI_COUNT_FAST(k_path_primary_samples)},
+    {RTMI_COUNT_FAST(k_path_slow), RTMI_COUNT_FAST(k_path_slow_samples)}};
+static const ListWalkKernel path_list_variant[2][2][2] = {RTMI_COUNT_FAST(k_path_primary_list), RTMI_COUNT_FAST(k_path_slow_list)};
+
+static void launch_trace(rtmi_scene* s, Work& w, hipStream_t st, const float4* qo, const float4* qd, int pass, bool count, hipEvent_t stop) {
     // `stop` is recorded right after the closest-hit kernel, so that the event pair of the caller times exactly
     // the kernel rocprofv3 lists as k_trace_oct / k_trace_linear / k_trace
     if ((s->options & RTMI_OPT_BVH) && s->bvh_ok) {
         const dim3 grid((unsigned)(s->num_cu * s->bvh_blocks_per_cu)), block(64);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_bvh<COUNT>), grid, block, s->bvh_lds, st, s->d, s->bnodes.p, s->bleaves.p, s->bvh_root,
-                           qo, qd, w.ctrl.p, pass, w.hit_tf.p, w.hit_t.p, (int)(pass == 0 ? s->tune.refill_min0 : s->tune.refill_min));
+        hipLaunchKernelGGL(count ? k_trace_bvh<true> : k_trace_bvh<false>, grid, block, s->bvh_lds, st, s->d, s->bnodes.p, s->bleaves.p,
+                           s->bvh_root, qo, qd, w.ctrl.p, pass, w.hit_tf.p, w.hit_t.p, (int)(pass == 0 ? s->tune.refill_min0 : s->tune.refill_min));
     } else if (s->root_is_leaf && !(s->options & RTMI_OPT_GENERIC)) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_linear<COUNT>), dim3((unsigned)(s->num_cu * 8)), dim3(256), 0, st, s->d, qo, qd,
-                           w.ctrl.p, pass, w.hit_tf.p, w.hit_t.p);
+        hipLaunchKernelGGL(count ? k_trace_linear<true> : k_trace_linear<false>, dim3((unsigned)(s->num_cu * 8)), dim3(256), 0, st, s->d,
+                           qo, qd, w.ctrl.p, pass, w.hit_tf.p, w.hit_t.p);
     } else if (s->octree && !(s->options & RTMI_OPT_GENERIC)) {
         const int refill = (int)(pass == 0 ? s->tune.refill_min0 : s->tune.refill_min);
         const int xcd = (int)(s->tune.xcd_aware % 3u);  // 1 = ranges by XCC_ID, 2 = by blockIdx % 8, 0 = one range
         OctArgs a{};
         a.qo = qo; a.qd = qd; a.hit_tf = w.hit_tf.p; a.hit_t = w.hit_t.p; a.pass = pass;
         a.vote_s = pass == 0 ? s->vote[0] : s->vote[2]; a.vote_l = pass == 0 ? s->vote[1] : s->vote[3];
-        if (s->options & RTMI_OPT_FAST)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_oct<COUNT, true>), oct_grid(s), dim3(64), oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_oct<COUNT, false>), oct_grid(s), dim3(64), oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
+        hipLaunchKernelGGL(trace_oct_variant[count][(s->options & RTMI_OPT_FAST) != 0], oct_grid(s), dim3(64), oct_launch_lds(s, count), st,
+                           s->d, a, w.ctrl.p, refill, xcd);
     } else {
         // persistent grid: enough blocks to fill every CU at the occupancy LDS allows
         const int per_cu = s->trace_block == 256 ? 4 : 16;
         const dim3 grid((unsigned)(s->num_cu * per_cu)), block((unsigned)s->trace_block);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace<COUNT>), grid, block, s->trace_lds, st, s->d, qo, qd, w.ctrl.p, pass,
+        hipLaunchKernelGGL(count ? k_trace<true> : k_trace<false>, grid, block, s->trace_lds, st, s->d, qo, qd, w.ctrl.p, pass,
                            w.hit_tf.p, w.hit_t.p);
     }
     (void)hipEventRecord(stop, st);
@@ -1563,48 +1556,30 @@ static SlowQ slow_queue(rtmi_scene* s, Work& w) {
     const bool on = s->tune.slow_path_off == 0u && w.sqo.p && w.sstream;
     return SlowQ{w.sqo.p, w.sqd.p, w.sqpath.p, w.sqbounce.p, on ? RTMI_SLOW_CAP : 0u};
 }
-// What both path kernels (trace_oct.hpp) read: the batch's paths, their surface stacks and sample colours, the slow-path queue
-static OctArgs path_args(rtmi_scene* s, Work& w, const DView& dv, uint64_t seed, uint32_t pix0, uint32_t npaths) {
-    OctArgs a{};
-    a.v = dv; a.seed = seed; a.pix0 = pix0; a.npaths = npaths;
-    a.mstack = w.mstack.p; a.scol = w.scol.p;
-    a.slow = slow_queue(s, w);
-    return a;
+// One launch of the path kernel of the batch's sampling mode: k_path_primary* (slow = false) or k_path_slow*
+static void launch_path(rtmi_scene* s, Work& w, hipStream_t st, dim3 grid, const OctArgs& a, int refill, int xcd, bool slow,
+                        bool count, Samp mode, const uint32_t* list) {
+    const bool fast = (s->options & RTMI_OPT_FAST) != 0;
+    if (mode == Samp::LIST)
+        hipLaunchKernelGGL(path_list_variant[slow][count][fast], grid, dim3(64), oct_launch_lds(s, count), st, s->d, a, w.ctrl.p, refill, xcd, list);
+    else
+        hipLaunchKernelGGL(path_variant[slow][mode == Samp::PASS][count][fast], grid, dim3(64), oct_launch_lds(s, count), st, s->d, a, w.ctrl.p, refill, xcd);
 }
 // k_path_primary: the batch's primary rays generated, traced and shaded; the bounce rays go to queue 1, which pass 1 traces.
 // The mirror reflections it traces itself go on in queue 2 (ping-pong buffer 0, free until pass 1's k_shade appends to it).
 // `stop` is recorded right after the kernel.
-// list != nullptr (adaptive passes): the list variants, whose batch pixels are list[pix0 + q]
-template <bool COUNT, bool PROG>
-static void launch_primary(rtmi_scene* s, Work& w, hipStream_t st, const DView& dv, uint64_t seed, uint32_t pix0, uint32_t npaths,
-                           hipEvent_t stop, const uint32_t* list = nullptr) {
-    OctArgs a = path_args(s, w, dv, seed, pix0, npaths);
+static void launch_primary(rtmi_scene* s, Work& w, hipStream_t st, OctArgs a, bool count, Samp mode, const uint32_t* list,
+                           hipEvent_t stop) {
     a.bqo = w.qo[1].p; a.bqd = w.qd[1].p; a.bqpath = w.qpath[1].p;
     a.vote_s = s->vote[0]; a.vote_l = s->vote[1];
     a.pcull = s->packet_cull;
     a.b2qo = w.qo[0].p; a.b2qd = w.qd[0].p; a.b2qpath = w.qpath[0].p;
     a.minpl = s->mirror_inplace;
-    const int refill = (int)s->tune.refill_min0, xcd = (int)(s->tune.xcd_aware % 3u);
-    const bool fast = (s->options & RTMI_OPT_FAST) != 0;
-    if (list && fast)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary_list<COUNT, true>), oct_grid(s), dim3(64), oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd, list);
-    else if (list)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary_list<COUNT, false>), oct_grid(s), dim3(64), oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd, list);
-    else if (PROG && fast)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary_samples<COUNT, true>), oct_grid(s), dim3(64), oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
-    else if (PROG)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary_samples<COUNT, false>), oct_grid(s), dim3(64), oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
-    else if (fast)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary<COUNT, true>), oct_grid(s), dim3(64), oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_primary<COUNT, false>), oct_grid(s), dim3(64), oct_launch_lds(s, COUNT), st, s->d, a, w.ctrl.p, refill, xcd);
+    launch_path(s, w, st, oct_grid(s), a, (int)s->tune.refill_min0, (int)(s->tune.xcd_aware % 3u), false, count, mode, list);
     (void)hipEventRecord(stop, st);
 }
 // Consumer launch k of the slow path (k_path_slow), on the side stream: after the producer on `st` whose event is sev[k]
-template <bool COUNT, bool PROG>
-static void launch_slow(rtmi_scene* s, Work& w, hipStream_t st, const DView& dv, uint64_t seed, uint32_t pix0, uint32_t npaths,
-                        uint32_t k, const uint32_t* list = nullptr) {
-    OctArgs a = path_args(s, w, dv, seed, pix0, npaths);
+static void launch_slow(rtmi_scene* s, Work& w, hipStream_t st, OctArgs a, uint32_t k, bool count, Samp mode, const uint32_t* list) {
     a.slow_k = k;
     a.vote_s = s->vote[2]; a.vote_l = s->vote[3];
     (void)hipStreamWaitEvent(w.sstream, w.sev[k], 0);
@@ -1616,34 +1591,22 @@ static void launch_slow(rtmi_scene* s, Work& w, hipStream_t st, const DView& dv,
     (void)hipEventRecord(w.sgo, w.sstream);
     (void)hipStreamWaitEvent(st, w.sgo, 0);
     const dim3 sgrid((unsigned)std::max(s->num_cu / 2, 1));  // one path per wave at a time; a frame has ~100 such paths, a wave takes one after the other
-    const bool fast = (s->options & RTMI_OPT_FAST) != 0;
-    if (list && fast)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow_list<COUNT, true>), sgrid, dim3(64), oct_launch_lds(s, COUNT), w.sstream, s->d, a, w.ctrl.p, 1, 0, list);
-    else if (list)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow_list<COUNT, false>), sgrid, dim3(64), oct_launch_lds(s, COUNT), w.sstream, s->d, a, w.ctrl.p, 1, 0, list);
-    else if (PROG && fast)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow_samples<COUNT, true>), sgrid, dim3(64), oct_launch_lds(s, COUNT), w.sstream, s->d, a, w.ctrl.p, 1, 0);
-    else if (PROG)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow_samples<COUNT, false>), sgrid, dim3(64), oct_launch_lds(s, COUNT), w.sstream, s->d, a, w.ctrl.p, 1, 0);
-    else if (fast)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow<COUNT, true>), sgrid, dim3(64), oct_launch_lds(s, COUNT), w.sstream, s->d, a, w.ctrl.p, 1, 0);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_slow<COUNT, false>), sgrid, dim3(64), oct_launch_lds(s, COUNT), w.sstream, s->d, a, w.ctrl.p, 1, 0);
+    launch_path(s, w, w.sstream, sgrid, a, 1, 0, true, count, mode, list);
 }
-}  // extern "C++"
 
-static int read_stats(Work& w, hipStream_t st, rtmi_stats_t* stats, float kernel_ms, float trace_ms, uint32_t launches) {
-    DCtrl h;
-    HIPCHK(hipMemcpyAsync(&h, w.ctrl.p, sizeof(DCtrl), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (stats) {
-        stats->rays += h.rays;
-        stats->box_tests += h.counters[0]; stats->tri_tests += h.counters[1]; stats->full_tests += h.counters[2];
-        stats->nodes += h.counters[3]; stats->leaves += h.counters[4];
-        stats->kernel_ms += kernel_ms; stats->trace_ms += trace_ms; stats->trace_launches += launches;
-        stats->slow_paths += std::min<uint32_t>(h.scount, RTMI_SLOW_CAP);
-    }
-    return RTMI_OK;
+// The work counters of a stream's control block as stats
+static rtmi_stats_t ctrl_counters(const DCtrl& h) {
+    rtmi_stats_t c{};
+    c.rays = h.rays;
+    c.box_tests = h.counters[0]; c.tri_tests = h.counters[1]; c.full_tests = h.counters[2];
+    c.nodes = h.counters[3]; c.leaves = h.counters[4];
+    c.slow_paths = std::min<uint32_t>(h.scount, RTMI_SLOW_CAP);
+    return c;
+}
+// a += the work counters of b (rays, tests, nodes, leaves, slow paths)
+static void add_counters(rtmi_stats_t& a, const rtmi_stats_t& b) {
+    a.rays += b.rays; a.box_tests += b.box_tests; a.tri_tests += b.tri_tests; a.full_tests += b.full_tests;
+    a.nodes += b.nodes; a.leaves += b.leaves; a.slow_paths += b.slow_paths;
 }
 
 int rtmi_render_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
@@ -1656,63 +1619,49 @@ int rtmi_render_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed
 struct SubTile {
     DView dv;          // row mapping of the sub-tile's local rows (tile_pixel)
     uint64_t npix = 0; // pixels of the sub-tile
-    uint32_t index = 0;
     uint32_t base = 0;  // adaptive passes: the sub-tile's first entry of the active-pixel list
 };
 // An adaptive pass (rtmi_render_adaptive*): the n pixels of `list` (tile-local pixel indices, ascending), each with the same
 // number of samples behind it; sumsq / counts continue beside the call's accum.
-struct ListPass {
-    const uint32_t* list;
-    uint32_t n;
-    float4* sumsq;
-    uint32_t* counts;
+struct ListPass { const uint32_t* list; uint32_t n; float4* sumsq; uint32_t* counts; };
+// One render_tile call: what it renders, and its plan (plan_tile)
+struct TileCall {
+    uint64_t seed;
+    uint32_t sample0, spp, maxdepth, W;  // spp: samples per pixel of this call
+    float4 *accum, *out;
+    const ListPass* lp;
+    Samp mode;  // LIST with lp, PASS with accum, FRAME otherwise
+    bool counting, path_kernels;
+    uint32_t nsub;
+    uint64_t pix_per_batch, max_npix;  // max_npix: pixels of the largest sub-tile
+    SubTile sub[RTMI_MAX_STREAMS];
+};
+// What the batches of a call add up to: work counters, closest-hit launches and their times
+struct TileSums {
+    rtmi_stats_t counters{};
+    float trace_ms = 0.f, primary_ms = 0.f, bounce_ms = 0.f;
+    uint32_t launches = 0;
 };
 
-// Checks of a tile against the viewport (nrows >= 1); the message, or nullptr when it is valid
-static const char* tile_error(const rtmi_viewport_t* vp, const rtmi_tile_t* tile) {
+// Checks of a render call's viewport and tile (nrows >= 1), before any HIP call
+static int check_view(const rtmi_viewport_t* vp, const rtmi_tile_t* tile) {
     const uint32_t row0 = tile->row0, nrows = tile->nrows;
-    if (vp->width == 0 || vp->height == 0) return "empty viewport";
-    if (tile->stripe_rows == 0) return "stripe_rows must be >= 1";
+    if (vp->width == 0 || vp->height == 0) return fail(RTMI_ERR_INVALID, "empty viewport");
+    if (tile->stripe_rows == 0) return fail(RTMI_ERR_INVALID, "stripe_rows must be >= 1");
     const uint64_t nstripes = ((uint64_t)nrows + tile->stripe_rows - 1) / tile->stripe_rows;
     const uint64_t last_row = (uint64_t)row0 + (nstripes - 1) * tile->stripe_step + ((uint64_t)nrows - 1 - (nstripes - 1) * tile->stripe_rows);
-    if (last_row >= vp->height) return "row range outside the viewport";
-    if (nstripes > 1 && tile->stripe_step < tile->stripe_rows) return "stripes overlap";
-    return nullptr;
-}
-
-// Samples [sample0, sample0 + nsamples) of every pixel of the tile.  accum == nullptr: the whole frame (0, S) into out_device
-// (rtmi_render_tile_device, k_accum).  Otherwise a progressive pass (rtmi_render_samples_device, k_accum_samples): the running
-// per-pixel sums continue in accum, out_device (optional) receives the preview.  Batches and automatic streams are sized
-// from the paths of THIS call, npix * nsamples.
-// lp != nullptr (with accum): an adaptive pass over the pixels of lp->list, dealt out to the streams in contiguous chunks of
-// the list (the list kernels, k_accum_list).  Batches and automatic streams are then sized from lp->n * nsamples.
-static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile, uint32_t sample0,
-                       uint32_t nsamples, float4* accum, void* out_device, void* hip_stream, rtmi_stats_t* stats,
-                       const ListPass* lp = nullptr) {
-    const uint32_t row0 = tile->row0, nrows = tile->nrows;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (nrows == 0) return RTMI_OK;
-    RTMI_GUARD_BEGIN
-    // leftovers of the caller's own HIP calls on this thread (or of failures this library tolerated, e.g. an occupancy
-    // query) must not make a launch below look refused: hipGetLastError() reports the last error of ANY runtime call
-    (void)hipGetLastError();
-    if (!out_device && !accum) return fail(RTMI_ERR_INVALID, "NULL argument");
-    if (const char* e = tile_error(vp, tile)) return fail(RTMI_ERR_INVALID, e);
+    if (last_row >= vp->height) return fail(RTMI_ERR_INVALID, "row range outside the viewport");
+    if (nstripes > 1 && tile->stripe_step < tile->stripe_rows) return fail(RTMI_ERR_INVALID, "stripes overlap");
     if (vp->samples_per_pixel == 0) return fail(RTMI_ERR_INVALID, "samples_per_pixel must be >= 1");  // reference: 1/0 -> NaN image
     if (vp->maxdepth > RTMI_MAX_PASSES) return fail(RTMI_ERR_UNSUPPORTED, "maxdepth above 32");
     if ((uint64_t)vp->width * vp->height >= (1ull << 32)) return fail(RTMI_ERR_UNSUPPORTED, "more than 2^32 pixels");
-    HIPCHK(hipSetDevice(s->device));
-    hipStream_t ust = (hipStream_t)hip_stream;
-    const uint32_t W = vp->width, spp = nsamples, maxdepth = vp->maxdepth;  // spp: samples per pixel of this call
-    const uint64_t npix = (uint64_t)nrows * W;
-    float4* out = (float4*)out_device;
-    if (maxdepth == 0) {  // project_ray returns black immediately (raytrace.rs:1261-1263); acc*(1/spp) of zeros
-        if (accum) HIPCHK(hipMemsetAsync(accum, 0, npix * sizeof(float4), ust));
-        if (out) HIPCHK(hipMemsetAsync(out, 0, npix * sizeof(float4), ust));
-        HIPCHK(hipStreamSynchronize(ust));
-        return RTMI_OK;
-    }
+    return RTMI_OK;
+}
 
+// The plan of a call: its streams, their sub-tiles and the batch size, with every stream's workspace sized for it.
+static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t* tile, TileCall& c) {
+    const uint32_t nrows = tile->nrows, spp = c.spp;
+    const uint64_t npix = (uint64_t)nrows * c.W;
     // ---- the tile's rows dealt out to the streams one row at a time (sub-tile t = rows t, t + nsub, ... of the tile): equal
     //      shares whatever the tile's own striping is.  (Round 2 dealt out whole stripes: with the 16-row stripes of an
     //      8-rank tiling a stream's stripes repeat every 384 image rows, the teapot covers two such periods and the slowest
@@ -1720,8 +1669,8 @@ static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed
     // path kernels (pipeline 3; 0 = automatic): exact-octree scenes get pass 0 from k_path_primary, which generates, traces and
     // shades the primary rays in one kernel.  Everything else (pipeline 1, linear list, generic tree, BVH mode,
     // analytic spheres) starts with k_gen.  Both then run one closest-hit + one shading launch per bounce pass.
-    const bool path_kernels = s->tune.pipeline != 1u && s->octree && !s->root_is_leaf &&
-                              !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) && s->d.nspheres == 0;
+    c.path_kernels = s->tune.pipeline != 1u && s->octree && !s->root_is_leaf &&
+                     !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) && s->d.nspheres == 0;
     // streams = 0 (automatic): one stream for path-kernel tiles of 2^26 paths and more, three otherwise (the per-pass
     // pipelines -- BVH mode: 29.6 ms on three streams, 35.2 on one -- have elementwise kernels to hide).  Since k_shade stopped being
     // atomic-bound (round 3) there is little left for a second stream to hide: the full config-3 frame takes 366.9 ms on one
@@ -1729,38 +1678,37 @@ static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed
     // adaptive passes: sized from the pass's own pixels, lp->n.  A refinement pass (fewer pixels than the tile) takes one
     // stream: on config 3 its few hundred thousand pixels ran 6 % faster over the whole call on one stream than on three,
     // and no slower at the other tolerances measured.
+    const ListPass* lp = c.lp;
     const uint64_t npix_call = lp ? (uint64_t)lp->n : npix;
-    const uint32_t auto_streams = ((path_kernels && npix_call * spp >= (1ull << 26)) || (lp && npix_call < npix)) ? 1u : 3u;
+    const uint32_t auto_streams = ((c.path_kernels && npix_call * spp >= (1ull << 26)) || (lp && npix_call < npix)) ? 1u : 3u;
     uint32_t nsub = std::min<uint32_t>(s->tune.streams ? s->tune.streams : auto_streams, (uint32_t)RTMI_MAX_STREAMS);
     nsub = (uint32_t)std::min<uint64_t>(nsub, lp ? npix_call : nrows);
     if (npix_call * spp < s->tune.subtile_min_paths) nsub = 1;
-    s->active_streams = nsub;
-    SubTile sub[RTMI_MAX_STREAMS];
+    s->active_streams = c.nsub = nsub;
     for (uint32_t t = 0; t < nsub; t++) {
-        DView& dv = sub[t].dv;
+        DView& dv = c.sub[t].dv;
         dv.orig = mk(vp->orig[0], vp->orig[1], vp->orig[2]);
         dv.cam = mk(vp->cam[0], vp->cam[1], vp->cam[2]);
         dv.vu = mk(vp->vu[0], vp->vu[1], vp->vu[2]);
         dv.vv = mk(vp->vv[0], vp->vv[1], vp->vv[2]);
-        dv.width = W; dv.height = vp->height; dv.maxdepth = maxdepth; dv.spp = spp;
-        dv.row0 = row0; dv.stripe_rows = tile->stripe_rows; dv.stripe_step = tile->stripe_step;
-        view_set_sampling(dv, sample0, vp->samples_per_pixel);
+        dv.width = c.W; dv.height = vp->height; dv.maxdepth = c.maxdepth; dv.spp = spp;
+        dv.row0 = tile->row0; dv.stripe_rows = tile->stripe_rows; dv.stripe_step = tile->stripe_step;
+        view_set_sampling(dv, c.sample0, vp->samples_per_pixel);
         dv.sub_mul = lp ? 1u : nsub; dv.sub_off = lp ? 0u : t;  // list entries are tile-local pixel indices
         view_set_divisors(dv);
         if (lp) {  // a contiguous chunk of the list: neighbouring pixels stay in the same waves
-            sub[t].base = (uint32_t)(npix_call * t / nsub);
-            sub[t].npix = npix_call * (t + 1) / nsub - sub[t].base;
+            c.sub[t].base = (uint32_t)(npix_call * t / nsub);
+            c.sub[t].npix = npix_call * (t + 1) / nsub - c.sub[t].base;
         } else {
-            sub[t].npix = (uint64_t)((nrows - t + nsub - 1) / nsub) * W;
+            c.sub[t].npix = (uint64_t)((nrows - t + nsub - 1) / nsub) * c.W;
         }
-        sub[t].index = t;
     }
 
     // batch = whole pixels with all their samples
     const size_t want_paths = (size_t)std::max<uint64_t>(s->tune.batch_paths, 1) / nsub;
     uint64_t pix_per_batch = std::max<uint64_t>(1, want_paths / spp);
     uint64_t max_sub_npix = 0;
-    for (uint32_t t = 0; t < nsub; t++) max_sub_npix = std::max(max_sub_npix, sub[t].npix);
+    for (uint32_t t = 0; t < nsub; t++) max_sub_npix = std::max(max_sub_npix, c.sub[t].npix);
     // equal batches: a sub-tile a little larger than the budget (thirds of a frame whose stripes do not divide evenly)
     // would otherwise get a full batch and a sliver with five tiny passes of its own
     if (pix_per_batch < max_sub_npix) {
@@ -1769,142 +1717,186 @@ static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed
     }
     pix_per_batch = std::min<uint64_t>(pix_per_batch, max_sub_npix);
     if (pix_per_batch * spp >= (1ull << 31)) return fail(RTMI_ERR_UNSUPPORTED, "batch above 2^31 paths");
+    c.pix_per_batch = pix_per_batch;
+    c.max_npix = max_sub_npix;
     for (uint32_t t = 0; t < nsub; t++) {
-        if (sub[t].npix == 0) continue;
-        int rc = ensure_workspace(s->w[t], (size_t)(std::min<uint64_t>(pix_per_batch, sub[t].npix) * spp), maxdepth);
+        if (c.sub[t].npix == 0) continue;
+        int rc = ensure_workspace(s->w[t], (size_t)(std::min<uint64_t>(pix_per_batch, c.sub[t].npix) * spp), c.maxdepth);
         if (rc != RTMI_OK) return rc;
     }
+    return RTMI_OK;
+}
 
-    const bool counting = (s->options & RTMI_OPT_COUNTERS) != 0;
-    const bool prog = accum != nullptr;  // progressive pass: the *_samples kernels (sample numbers from sample0)
-    const uint32_t* list = lp ? lp->list : nullptr;  // adaptive pass: the *_list kernels
-    const bool verbose = s->verbose;
-    const unsigned ew_blocks = (unsigned)(s->num_cu * 8);
-    float trace_ms = 0.f, primary_ms = 0.f, bounce_ms = 0.f;
-    uint32_t launches = 0;
-    // internal streams start after whatever the caller queued on its stream
-    HIPCHK(hipEventRecord(s->fork_ev, ust));
-    for (uint32_t t = 0; t < nsub; t++) HIPCHK(hipStreamWaitEvent(s->istream[t], s->fork_ev, 0));
+// verbose with counters, per-pass pipeline: what pass `pass` of stream t cost per ray (this pass's share of the counters)
+static int dump_pass_counters(rtmi_scene* s, Work& w, hipStream_t st, uint32_t t, uint32_t pass) {
+    DCtrl h;
+    HIPCHK(hipMemcpyAsync(&h, w.ctrl.p, sizeof(DCtrl), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    unsigned long long* prev = s->vprev[t], d[13];  // d: the pass's share of counters[0..4], dbg[0..7]
+    if (pass == 0) memset(prev, 0, sizeof(s->vprev[t]));
+    for (int k = 0; k < 13; k++) {
+        const unsigned long long cur = k < 5 ? h.counters[k] : h.dbg[k - 5];
+        d[k] = cur - prev[k];
+        prev[k] = cur;
+    }
+    const double n = h.count[pass] ? (double)h.count[pass] : 1.0;
+    fprintf(stderr, "[rtmi]   stream %u pass %u per ray: box %.1f tri %.1f full %.2f nodes %.1f leaves %.1f | S-steps %.1f (util %.2f) L-steps %.1f (util %.2f)\n",
+            t, pass, d[0] / n, d[1] / n, d[2] / n, d[3] / n, d[4] / n, d[6] / n, (double)d[6] / (64.0 * (d[5] ? d[5] : 1)), d[8] / n,
+            (double)d[8] / (64.0 * (d[7] ? d[7] : 1)));
+    return RTMI_OK;
+}
 
-    const uint64_t max_npix = max_sub_npix;
-    for (uint64_t p0 = 0; p0 < max_npix; p0 += pix_per_batch) {
-        // enqueue this batch of every sub-tile (no host dependency inside a batch: queue sizes live on the device)
-        for (uint32_t t = 0; t < nsub; t++) {
-            if (p0 >= sub[t].npix) continue;
-            Work& w = s->w[t];
-            hipStream_t st = s->istream[t];
-            const DView& dv = sub[t].dv;
-            const uint32_t np = (uint32_t)std::min<uint64_t>(pix_per_batch, sub[t].npix - p0);
-            const uint32_t npaths = np * spp;
-            const uint32_t pix0 = sub[t].base + (uint32_t)p0;  // local pixel index inside the sub-tile (list entry: adaptive)
-            HIPCHK(hipMemsetAsync(w.ctrl.p, 0, sizeof(DCtrl), st));
-            HIPCHK(hipEventRecord(w.ev[0], st));
-            // the slow path: zero-component rays that k_path_primary and k_shade set aside, traced beside the following passes
-            const SlowQ sq = path_kernels ? slow_queue(s, w) : SlowQ{nullptr, nullptr, nullptr, nullptr, 0u};
-            auto slow_after = [&](uint32_t k) {  // after producer k: k_path_primary (0) or the shading of pass k
-                if (sq.cap == 0u) return;
-                (void)hipEventRecord(w.sev[k], st);
-                if (counting && prog) launch_slow<true, true>(s, w, st, dv, seed, pix0, npaths, k, list);
-                else if (counting) launch_slow<true, false>(s, w, st, dv, seed, pix0, npaths, k);
-                else if (prog) launch_slow<false, true>(s, w, st, dv, seed, pix0, npaths, k, list);
-                else launch_slow<false, false>(s, w, st, dv, seed, pix0, npaths, k);
-            };
-            uint32_t pass0 = 0;  // first pass of the per-pass loop
-            if (path_kernels) {
-                HIPCHK(hipEventRecord(w.pass_ev[0], st));
-                if (counting && prog) launch_primary<true, true>(s, w, st, dv, seed, pix0, npaths, w.pass_ev[1], list);
-                else if (counting) launch_primary<true, false>(s, w, st, dv, seed, pix0, npaths, w.pass_ev[1]);
-                else if (prog) launch_primary<false, true>(s, w, st, dv, seed, pix0, npaths, w.pass_ev[1], list);
-                else launch_primary<false, false>(s, w, st, dv, seed, pix0, npaths, w.pass_ev[1]);
-                HIPCHK(hipGetLastError());
-                launches++;
-                slow_after(0);
-                pass0 = 1;
-            } else if (list) {
-                hipLaunchKernelGGL(k_gen_list, dim3(ew_blocks), dim3(256), 0, st, dv, seed, pix0, npaths, w.qo[0].p, w.qd[0].p,
-                                   w.qpath[0].p, w.ctrl.p, list);
-            } else {
-                hipLaunchKernelGGL(prog ? k_gen_samples : k_gen, dim3(ew_blocks), dim3(256), 0, st, dv, seed, pix0, npaths, w.qo[0].p, w.qd[0].p,
-                                   w.qpath[0].p, w.ctrl.p);
-            }
-            HIPCHK(hipGetLastError());  // a refused launch is reported where it happens, not at the end of the batch
-            for (uint32_t pass = pass0; pass < maxdepth; pass++) {
-                const int a = pass & 1, b = a ^ 1;
-                HIPCHK(hipEventRecord(w.pass_ev[2 * pass], st));
-                if (counting) launch_trace<true>(s, w, st, w.qo[a].p, w.qd[a].p, (int)pass, w.pass_ev[2 * pass + 1]);
-                else launch_trace<false>(s, w, st, w.qo[a].p, w.qd[a].p, (int)pass, w.pass_ev[2 * pass + 1]);
-                HIPCHK(hipGetLastError());
-                if (counting && verbose && !path_kernels) {
-                    DCtrl hc2;
-                    HIPCHK(hipMemcpyAsync(&hc2, w.ctrl.p, sizeof(DCtrl), hipMemcpyDeviceToHost, st));
-                    HIPCHK(hipStreamSynchronize(st));
-                    unsigned long long (*prev)[13] = s->vprev;
-                    if (pass == 0) memset(prev[t], 0, sizeof(s->vprev[t]));
-                    unsigned long long cur[13];
-                    for (int k = 0; k < 5; k++) cur[k] = hc2.counters[k];
-                    for (int k = 0; k < 8; k++) cur[5 + k] = hc2.dbg[k];
-                    const double n = hc2.count[pass] ? (double)hc2.count[pass] : 1.0;
-                    fprintf(stderr, "[rtmi]   stream %u pass %u per ray: box %.1f tri %.1f full %.2f nodes %.1f leaves %.1f | S-steps %.1f (util %.2f) L-steps %.1f (util %.2f)\n",
-                            t, pass, (cur[0] - prev[t][0]) / n, (cur[1] - prev[t][1]) / n, (cur[2] - prev[t][2]) / n, (cur[3] - prev[t][3]) / n, (cur[4] - prev[t][4]) / n,
-                            (cur[6] - prev[t][6]) / n, (double)(cur[6] - prev[t][6]) / (64.0 * (cur[5] - prev[t][5] ? cur[5] - prev[t][5] : 1)),
-                            (cur[8] - prev[t][8]) / n, (double)(cur[8] - prev[t][8]) / (64.0 * (cur[7] - prev[t][7] ? cur[7] - prev[t][7] : 1)));
-                    memcpy(prev[t], cur, sizeof(s->vprev[t]));
-                }
-                if (list)
-                    hipLaunchKernelGGL(k_shade_list, dim3(ew_blocks), dim3(256), 0, st, s->d, dv, seed, pix0, npaths, (int)pass,
-                                       w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p,
-                                       w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, list);
-                else
-                    hipLaunchKernelGGL(prog ? k_shade_samples : k_shade, dim3(ew_blocks), dim3(256), 0, st, s->d, dv, seed, pix0, npaths, (int)pass,
-                                       w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p,
-                                       w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq);
-                HIPCHK(hipGetLastError());
-                if (pass + 1 < maxdepth) {  // the last pass's shading emits no rays
-                    slow_after(pass);
-                    HIPCHK(hipGetLastError());
-                }
-                launches++;
-            }
-            if (sq.cap != 0u) {  // the sample colours of the slow paths must be there before k_accum
-                HIPCHK(hipEventRecord(w.sdone, w.sstream));
-                HIPCHK(hipStreamWaitEvent(st, w.sdone, 0));
-            }
-            if (list)
-                hipLaunchKernelGGL(k_accum_list, dim3(ew_blocks), dim3(256), 0, st, np, spp, sample0, w.scol.p, (float*)accum,
-                                   (float*)lp->sumsq, lp->counts, (float*)out, list, pix0);
-            else if (!accum)
-                hipLaunchKernelGGL(k_accum, dim3(ew_blocks), dim3(256), 0, st, np, spp, w.scol.p, (float*)out, pix0, W, nsub, t, make_fastdiv(W));
-            else
-                hipLaunchKernelGGL(k_accum_samples, dim3(ew_blocks), dim3(256), 0, st, np, spp, sample0, w.scol.p, (float*)accum,
-                                   (float*)out, pix0, W, nsub, t, make_fastdiv(W));
-            HIPCHK(hipEventRecord(w.ev[1], st));
+// Enqueues batch p0 of sub-tile t on its stream: the primary rays (k_path_primary, or k_gen), one closest-hit and one
+// shading launch per bounce pass with the slow path beside them, and the accumulation.  No host dependency inside a batch:
+// queue sizes live on the device.
+static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t p0) {
+    Work& w = s->w[t];
+    hipStream_t st = s->istream[t];
+    const DView& dv = c.sub[t].dv;
+    const uint32_t np = (uint32_t)std::min<uint64_t>(c.pix_per_batch, c.sub[t].npix - p0);
+    const uint32_t npaths = np * c.spp;
+    const uint32_t pix0 = c.sub[t].base + (uint32_t)p0;  // local pixel index inside the sub-tile (list entry: adaptive)
+    const uint32_t* list = c.mode == Samp::LIST ? c.lp->list : nullptr;
+    const dim3 ew_grid((unsigned)(s->num_cu * 8)), ew_block(256);
+    HIPCHK(hipMemsetAsync(w.ctrl.p, 0, sizeof(DCtrl), st));
+    HIPCHK(hipEventRecord(w.ev[0], st));
+    // what both path kernels (trace_oct.hpp) read: the batch's paths, their surface stacks and sample colours, the slow-path queue
+    OctArgs pa{};
+    pa.v = dv; pa.seed = c.seed; pa.pix0 = pix0; pa.npaths = npaths;
+    pa.mstack = w.mstack.p; pa.scol = w.scol.p; pa.slow = slow_queue(s, w);
+    // the slow path: zero-component rays that k_path_primary and k_shade set aside, traced beside the following passes
+    const SlowQ sq = c.path_kernels ? pa.slow : SlowQ{nullptr, nullptr, nullptr, nullptr, 0u};
+    auto slow_after = [&](uint32_t k) {  // after producer k: k_path_primary (0) or the shading of pass k
+        if (sq.cap == 0u) return;
+        (void)hipEventRecord(w.sev[k], st);
+        launch_slow(s, w, st, pa, k, c.counting, c.mode, list);
+    };
+    uint32_t pass0 = 0;  // first pass of the per-pass loop
+    if (c.path_kernels) {
+        HIPCHK(hipEventRecord(w.pass_ev[0], st));
+        launch_primary(s, w, st, pa, c.counting, c.mode, list, w.pass_ev[1]);
+        HIPCHK(hipGetLastError());
+        slow_after(0);
+        pass0 = 1;
+    } else if (list) {
+        hipLaunchKernelGGL(k_gen_list, ew_grid, ew_block, 0, st, dv, c.seed, pix0, npaths, w.qo[0].p, w.qd[0].p, w.qpath[0].p, w.ctrl.p, list);
+    } else {
+        hipLaunchKernelGGL(c.mode == Samp::PASS ? k_gen_samples : k_gen, ew_grid, ew_block, 0, st, dv, c.seed, pix0, npaths, w.qo[0].p,
+                           w.qd[0].p, w.qpath[0].p, w.ctrl.p);
+    }
+    HIPCHK(hipGetLastError());  // a refused launch is reported where it happens, not at the end of the batch
+    for (uint32_t pass = pass0; pass < c.maxdepth; pass++) {
+        const int a = pass & 1, b = a ^ 1;
+        HIPCHK(hipEventRecord(w.pass_ev[2 * pass], st));
+        launch_trace(s, w, st, w.qo[a].p, w.qd[a].p, (int)pass, c.counting, w.pass_ev[2 * pass + 1]);
+        HIPCHK(hipGetLastError());
+        if (c.counting && s->verbose && !c.path_kernels) {
+            int rc = dump_pass_counters(s, w, st, t, pass);
+            if (rc != RTMI_OK) return rc;
+        }
+        if (list)
+            hipLaunchKernelGGL(k_shade_list, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
+                               w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, list);
+        else
+            hipLaunchKernelGGL(c.mode == Samp::PASS ? k_shade_samples : k_shade, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths,
+                               (int)pass, w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p,
+                               w.mstack.p, w.scol.p, w.ctrl.p, sq);
+        HIPCHK(hipGetLastError());
+        if (pass + 1 < c.maxdepth) {  // the last pass's shading emits no rays
+            slow_after(pass);
             HIPCHK(hipGetLastError());
         }
-        // collect: counters and per-launch trace times of every sub-tile's batch
-        for (uint32_t t = 0; t < nsub; t++) {
-            if (p0 >= sub[t].npix) continue;
-            Work& w = s->w[t];
-            rtmi_stats_t bs; memset(&bs, 0, sizeof(bs));
-            int rc = read_stats(w, s->istream[t], &bs, 0.f, 0.f, 0);
-            if (rc != RTMI_OK) return rc;
-            DCtrl hc;
-            if (verbose) HIPCHK(hipMemcpy(&hc, w.ctrl.p, sizeof(DCtrl), hipMemcpyDeviceToHost));
-            for (uint32_t pass = 0; pass < maxdepth; pass++) {
-                float pm = 0.f;
-                HIPCHK(hipEventElapsedTime(&pm, w.pass_ev[2 * pass], w.pass_ev[2 * pass + 1]));
-                trace_ms += pm;
-                if (path_kernels) { if (pass == 0) primary_ms += pm; else bounce_ms += pm; }
-                if (verbose) fprintf(stderr, "[rtmi] stream %u batch@%llu pass %u: %u rays, trace %.3f ms, %.1f Mrays/s\n", t, (unsigned long long)p0, pass, hc.count[pass], pm, hc.count[pass] / (pm * 1e3));
-            }
-            if (stats) {
-                stats->rays += bs.rays; stats->box_tests += bs.box_tests; stats->tri_tests += bs.tri_tests;
-                stats->full_tests += bs.full_tests; stats->nodes += bs.nodes; stats->leaves += bs.leaves;
-                stats->slow_paths += bs.slow_paths;
-            }
-        }
+    }
+    if (sq.cap != 0u) {  // the sample colours of the slow paths must be there before k_accum
+        HIPCHK(hipEventRecord(w.sdone, w.sstream));
+        HIPCHK(hipStreamWaitEvent(st, w.sdone, 0));
+    }
+    switch (c.mode) {
+    case Samp::FRAME:
+        hipLaunchKernelGGL(k_accum, ew_grid, ew_block, 0, st, np, c.spp, w.scol.p, (float*)c.out, pix0, c.W, c.nsub, t, make_fastdiv(c.W));
+        break;
+    case Samp::PASS:
+        hipLaunchKernelGGL(k_accum_samples, ew_grid, ew_block, 0, st, np, c.spp, c.sample0, w.scol.p, (float*)c.accum, (float*)c.out,
+                           pix0, c.W, c.nsub, t, make_fastdiv(c.W));
+        break;
+    case Samp::LIST:
+        hipLaunchKernelGGL(k_accum_list, ew_grid, ew_block, 0, st, np, c.spp, c.sample0, w.scol.p, (float*)c.accum, (float*)c.lp->sumsq,
+                           c.lp->counts, (float*)c.out, list, pix0);
+        break;
+    }
+    HIPCHK(hipEventRecord(w.ev[1], st));
+    HIPCHK(hipGetLastError());
+    return RTMI_OK;
+}
+
+// Collects batch p0 of sub-tile t once its stream has finished it: the work counters, and the closest-hit launch of every
+// pass (k_path_primary for pass 0 of the path kernels) with its time
+static int collect_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t p0, TileSums& sum) {
+    Work& w = s->w[t];
+    DCtrl h;
+    HIPCHK(hipMemcpyAsync(&h, w.ctrl.p, sizeof(DCtrl), hipMemcpyDeviceToHost, s->istream[t]));
+    HIPCHK(hipStreamSynchronize(s->istream[t]));
+    add_counters(sum.counters, ctrl_counters(h));
+    for (uint32_t pass = 0; pass < c.maxdepth; pass++) {
+        float pm = 0.f;
+        HIPCHK(hipEventElapsedTime(&pm, w.pass_ev[2 * pass], w.pass_ev[2 * pass + 1]));
+        sum.launches++;
+        sum.trace_ms += pm;
+        if (c.path_kernels) { if (pass == 0) sum.primary_ms += pm; else sum.bounce_ms += pm; }
+        if (s->verbose) fprintf(stderr, "[rtmi] stream %u batch@%llu pass %u: %u rays, trace %.3f ms, %.1f Mrays/s\n", t, (unsigned long long)p0, pass, h.count[pass], pm, h.count[pass] / (pm * 1e3));
+    }
+    return RTMI_OK;
+}
+
+// Samples [sample0, sample0 + nsamples) of every pixel of the tile.  accum == nullptr: the whole frame (0, S) into out_device
+// (Samp::FRAME, rtmi_render_tile_device).  Otherwise a progressive pass (Samp::PASS, rtmi_render_samples_device): the running
+// per-pixel sums continue in accum, out_device (optional) receives the preview.  Batches and automatic streams are sized
+// from the paths of THIS call, npix * nsamples.
+// lp != nullptr (with accum): an adaptive pass over the pixels of lp->list (Samp::LIST), dealt out to the streams in
+// contiguous chunks of the list.  Batches and automatic streams are then sized from lp->n * nsamples.
+static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile, uint32_t sample0,
+                       uint32_t nsamples, float4* accum, void* out_device, void* hip_stream, rtmi_stats_t* stats,
+                       const ListPass* lp = nullptr) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (tile->nrows == 0) return RTMI_OK;
+    RTMI_GUARD_BEGIN
+    // leftovers of the caller's own HIP calls on this thread (or of failures this library tolerated, e.g. an occupancy
+    // query) must not make a launch below look refused: hipGetLastError() reports the last error of ANY runtime call
+    (void)hipGetLastError();
+    if (!out_device && !accum) return fail(RTMI_ERR_INVALID, "NULL argument");
+    int rc = check_view(vp, tile);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t ust = (hipStream_t)hip_stream;
+    float4* out = (float4*)out_device;
+    if (vp->maxdepth == 0) {  // project_ray returns black immediately (raytrace.rs:1261-1263); acc*(1/spp) of zeros
+        const uint64_t npix = (uint64_t)tile->nrows * vp->width;
+        if (accum) HIPCHK(hipMemsetAsync(accum, 0, npix * sizeof(float4), ust));
+        if (out) HIPCHK(hipMemsetAsync(out, 0, npix * sizeof(float4), ust));
+        HIPCHK(hipStreamSynchronize(ust));
+        return RTMI_OK;
+    }
+    TileCall c;
+    c.seed = seed; c.sample0 = sample0; c.spp = nsamples; c.maxdepth = vp->maxdepth; c.W = vp->width;
+    c.accum = accum; c.out = out; c.lp = lp;
+    c.mode = lp ? Samp::LIST : accum ? Samp::PASS : Samp::FRAME;
+    c.counting = (s->options & RTMI_OPT_COUNTERS) != 0;
+    rc = plan_tile(s, vp, tile, c);
+    if (rc != RTMI_OK) return rc;
+
+    // internal streams start after whatever the caller queued on its stream
+    HIPCHK(hipEventRecord(s->fork_ev, ust));
+    for (uint32_t t = 0; t < c.nsub; t++) HIPCHK(hipStreamWaitEvent(s->istream[t], s->fork_ev, 0));
+    TileSums sum;
+    for (uint64_t p0 = 0; p0 < c.max_npix; p0 += c.pix_per_batch) {
+        for (uint32_t t = 0; t < c.nsub && rc == RTMI_OK; t++)
+            if (p0 < c.sub[t].npix) rc = enqueue_batch(s, c, t, p0);
+        for (uint32_t t = 0; t < c.nsub && rc == RTMI_OK; t++)
+            if (p0 < c.sub[t].npix) rc = collect_batch(s, c, t, p0, sum);
+        if (rc != RTMI_OK) return rc;
     }
     // the caller's stream continues after both internal streams
-    for (uint32_t t = 0; t < nsub; t++) {
+    for (uint32_t t = 0; t < c.nsub; t++) {
         HIPCHK(hipEventRecord(s->join_ev[t], s->istream[t]));
         HIPCHK(hipStreamWaitEvent(ust, s->join_ev[t], 0));
     }
@@ -1913,8 +1905,9 @@ static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed
     float kernel_ms = 0.f;
     HIPCHK(hipEventElapsedTime(&kernel_ms, s->fork_ev, s->end_ev));
     if (stats) {
-        stats->kernel_ms = kernel_ms; stats->trace_ms = trace_ms; stats->trace_launches = launches; stats->streams = nsub;
-        stats->primary_ms = primary_ms; stats->bounce_ms = bounce_ms; stats->pipeline = path_kernels ? 3u : 1u;
+        add_counters(*stats, sum.counters);
+        stats->kernel_ms = kernel_ms; stats->trace_ms = sum.trace_ms; stats->trace_launches = sum.launches; stats->streams = c.nsub;
+        stats->primary_ms = sum.primary_ms; stats->bounce_ms = sum.bounce_ms; stats->pipeline = c.path_kernels ? 3u : 1u;
     }
     return RTMI_OK;
     RTMI_GUARD_END
@@ -2001,9 +1994,8 @@ static int render_adaptive(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t 
     if (tile->nrows == 0) return RTMI_OK;
     RTMI_GUARD_BEGIN
     (void)hipGetLastError();
-    if (const char* e = tile_error(vp, tile)) return fail(RTMI_ERR_INVALID, e);
-    if ((uint64_t)vp->width * vp->height >= (1ull << 32)) return fail(RTMI_ERR_UNSUPPORTED, "more than 2^32 pixels");
-    if (vp->maxdepth > RTMI_MAX_PASSES) return fail(RTMI_ERR_UNSUPPORTED, "maxdepth above 32");
+    int rc = check_view(vp, tile);
+    if (rc != RTMI_OK) return rc;
     HIPCHK(hipSetDevice(s->device));
     const uint32_t S = vp->samples_per_pixel, m = ad->min_samples, p = ad->pass_samples;
     const uint32_t npix = (uint32_t)((uint64_t)tile->nrows * vp->width);
@@ -2032,14 +2024,13 @@ static int render_adaptive(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t 
     for (;;) {
         const ListPass lp{s->alist[cur].p, nact, sumsq, counts};
         rtmi_stats_t ps;
-        int rc = render_tile(s, vp, seed, tile, n0, k, accum, out, ust, &ps, &lp);
+        rc = render_tile(s, vp, seed, tile, n0, k, accum, out, ust, &ps, &lp);
         if (rc != RTMI_OK) return rc;
         ad->passes++;
         ad->samples += (uint64_t)nact * k;
         if (stats) {
-            stats->rays += ps.rays; stats->box_tests += ps.box_tests; stats->tri_tests += ps.tri_tests;
-            stats->full_tests += ps.full_tests; stats->nodes += ps.nodes; stats->leaves += ps.leaves;
-            stats->slow_paths += ps.slow_paths; stats->trace_ms += ps.trace_ms; stats->trace_launches += ps.trace_launches;
+            add_counters(*stats, ps);
+            stats->trace_ms += ps.trace_ms; stats->trace_launches += ps.trace_launches;
             stats->primary_ms += ps.primary_ms; stats->bounce_ms += ps.bounce_ms; stats->pipeline = ps.pipeline;
         }
         streams = std::max(streams, ps.streams);
@@ -2320,8 +2311,7 @@ int rtmi_trace(rtmi_scene_t* s, uint64_t n, const float* orig4, const float* dir
     hipLaunchKernelGGL(k_set_count, dim3(1), dim3(1), 0, st, w.ctrl.p, (uint32_t)n);
     HIPCHK(hipEventRecord(w.ev[0], st));
     s->active_streams = 1;
-    if (s->options & RTMI_OPT_COUNTERS) launch_trace<true>(s, w, st, w.qo[0].p, w.qd[0].p, 0, w.ev[1]);
-    else launch_trace<false>(s, w, st, w.qo[0].p, w.qd[0].p, 0, w.ev[1]);
+    launch_trace(s, w, st, w.qo[0].p, w.qd[0].p, 0, (s->options & RTMI_OPT_COUNTERS) != 0, w.ev[1]);
     HIPCHK(hipGetLastError());
     std::vector<uint32_t> tf(n);
     HIPCHK(hipMemcpyAsync(tf.data(), w.hit_tf.p, n * 4, hipMemcpyDeviceToHost, st));
@@ -2331,9 +2321,14 @@ int rtmi_trace(rtmi_scene_t* s, uint64_t n, const float* orig4, const float* dir
     // face encoding of the ABI: 0 front 1 back 2 edge-front 3 edge-back (bit0 = back, bit1 = edge)
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
-    rc = read_stats(w, st, stats, ms, ms, 1);
-    if (stats) stats->streams = 1;
-    return rc;
+    DCtrl h;
+    HIPCHK(hipMemcpyAsync(&h, w.ctrl.p, sizeof(DCtrl), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (stats) {
+        add_counters(*stats, ctrl_counters(h));
+        stats->kernel_ms = ms; stats->trace_ms = ms; stats->trace_launches = 1; stats->streams = 1;
+    }
+    return RTMI_OK;
     RTMI_GUARD_END
 }
 

@@ -32,9 +32,9 @@ struct DView {
     V4 orig, cam, vu, vv;
     uint32_t width, height, maxdepth, spp;         // spp: samples per pixel of THIS call (paths per pixel of a batch)
     uint32_t row0, stripe_rows, stripe_step;       // rtmi_tile_t: which image rows the tile's rows are
-    // progressive passes only (the PROG = true kernels; the whole-frame kernels never read it): bits 0-30 sample0, the
-    // frame's sample number of the call's first sample; bit 31 set when the FRAME has more than one sample per pixel
-    // (spp_frame != 1: pixel_ray jitters).  view_set_sampling() fills it.
+    // Samp::PASS / LIST only (the whole-frame kernels never read it): bits 0-30 sample0, the frame's sample number of the
+    // call's first sample; bit 31 set when the FRAME has more than one sample per pixel (spp_frame != 1: pixel_ray
+    // jitters).  view_set_sampling() fills it.
     uint32_t sample_key;
     uint32_t sub_mul, sub_off;                     // sub-tile of a stream: rows sub_off, sub_off + sub_mul, ... of the tile
     FastDiv dspp, dwidth, dstripe;                 // n / spp, n / width, n / stripe_rows
@@ -58,19 +58,21 @@ __device__ inline void tile_pixel(const DView& v, uint32_t lp, uint32_t& row, ui
     const uint32_t k = fdiv(L, v.dstripe);
     row = v.row0 + k * v.stripe_step + (L - k * v.stripe_rows);
 }
+
+// Sampling mode of a batch.  FRAME: all samples of the call's pixels (sample0 = 0, and the kernels do not spend the add and
+// the register on it: 2 % of config 3's frame time when they did).  PASS: a progressive pass, samples [sample0, sample0 + spp)
+// of its pixels (DView::sample_key).  LIST: an adaptive pass, a PASS whose pixels are entries pix0, pix0 + 1, ... of the
+// active-pixel list, each a tile-local pixel index (row-major over the tile's rows; the launch's DView has sub_mul = 1,
+// sub_off = 0).  The list pointer is an argument of the list kernels only, so the other kernels keep their launch constants.
+enum class Samp { FRAME, PASS, LIST };
 // path index of a batch that starts at local pixel pix0 -> image pixel index (row * width + col) and the FRAME's sample
-// number (the RNG key).  PROG: a progressive pass renders samples [sample0, sample0 + spp) of its pixels; otherwise the
-// call renders all of them (sample0 = 0, and the kernel does not spend the add and the register on it: 2 % of config 3's
-// frame time when it did).
-// LIST (adaptive passes, always with PROG): the batch's pixels are entries pix0, pix0 + 1, ... of the active-pixel list, each
-// a tile-local pixel index (row-major over the tile's rows; the launch's DView has sub_mul = 1, sub_off = 0).  The list
-// pointer is an argument of the list kernels only, so the other kernels keep their launch constants.
-template <bool PROG, bool LIST = false>
+// number (the RNG key)
+template <Samp S>
 __device__ inline void path_pixel(const DView& v, uint32_t pix0, uint32_t path, uint32_t& row, uint32_t& col, uint32_t& sample,
-                                  const uint32_t* __restrict__ list = nullptr) {
+                                  const uint32_t* __restrict__ list) {
     const uint32_t q = fdiv(path, v.dspp);
-    sample = (PROG ? (v.sample_key & ~RTMI_KEY_JITTER) : 0u) + (path - q * v.spp);
-    tile_pixel(v, LIST ? list[pix0 + q] : pix0 + q, row, col);
+    sample = (S != Samp::FRAME ? (v.sample_key & ~RTMI_KEY_JITTER) : 0u) + (path - q * v.spp);
+    tile_pixel(v, S == Samp::LIST ? list[pix0 + q] : pix0 + q, row, col);
 }
 
 struct RayV { V4 orig, dir; };
@@ -78,14 +80,14 @@ struct RayV { V4 orig, dir; };
 __device__ inline RayV make_ray(V4 orig, V4 dir) { return RayV{orig, vunit(dir)}; }
 
 // Viewport::pixel_ray (raytrace.rs:1374-1394), px = (row, col).  The centred ray is the rule of a 1-sample FRAME: a
-// progressive pass of one sample of a larger frame (PROG) is jittered like every other sample of it.
-template <bool PROG>
+// pass of one sample of a larger frame (Samp::PASS / LIST) is jittered like every other sample of it.
+template <Samp S>
 __device__ inline RayV pixel_ray(const DView& v, uint32_t row, uint32_t col, uint64_t seed, uint32_t pixel, uint32_t sample) {
     float px_x = (float)row, px_y = (float)col;
     V4 vu_delta = vmul(v.vu, 1.f / (float)v.width);
     V4 vv_delta = vmul(v.vv, 1.f / (float)v.height);
     float u_off = 0.5f, v_off = 0.5f;
-    if (PROG ? (v.sample_key & RTMI_KEY_JITTER) != 0u : v.spp != 1) {  // spp_frame != 1
+    if (S != Samp::FRAME ? (v.sample_key & RTMI_KEY_JITTER) != 0u : v.spp != 1) {  // spp_frame != 1
         uint32_t w[4];
         rng_block(seed, pixel, sample, 0, w);
         u_off = u32_to_unit_f32(w[0]);

@@ -214,8 +214,8 @@ __host__ __device__ inline bool packet_culls(const Packet& p, float4 p0, float4 
     return (c1 <= 1e15f) & (nn <= 1e15f) & (fabsf(den0) > X + X) & (x2 > (y * y) * (1.f + PK_K));
 }
 
-// LIST (adaptive passes, with PROG): the batch's pixels come from the active-pixel list `list` (path_pixel, shade.hpp)
-template <bool COUNT, bool FAST, int MODE, bool PROG = false, bool LIST = false>
+// S: the batch's sampling mode (W_PRIMARY / W_SLOW; Samp::LIST takes the batch's pixels from `list`, path_pixel, shade.hpp)
+template <bool COUNT, bool FAST, int MODE, Samp S = Samp::FRAME>
 __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCtrl* __restrict__ ctrl, uint32_t* __restrict__ lds,
                                          int refill_min, int xcd_aware, const RecArgs& rec = RecArgs{},
                                          const uint32_t* __restrict__ list = nullptr) {
@@ -326,7 +326,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                 RayV nr;
                 if (mode == M_SHADE) {
                     uint32_t prow, pcol, sample;
-                    path_pixel<PROG, LIST>(a.v, a.pix0, pth, prow, pcol, sample, list);
+                    path_pixel<S>(a.v, a.pix0, pth, prow, pcol, sample, list);
                     const bool cont = shade_hit(sc, a.v.maxdepth, a.seed, a.npaths, pth, prow * a.v.width + pcol, sample, bnc,
                                                 ghave ? gtf : 0u, gt, V4{r.ox, r.oy, r.oz, r.ow}, V4{r.dx, r.dy, r.dz, r.dw},
                                                 a.mstack, a.scol, nr, &mirror);
@@ -435,8 +435,8 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                     if (i < hi) {
                         if (MODE == W_PRIMARY) {
                             uint32_t prow, pcol, sample;
-                            path_pixel<PROG, LIST>(a.v, a.pix0, i, prow, pcol, sample, list);
-                            const RayV pr = pixel_ray<PROG>(a.v, prow, pcol, a.seed, prow * a.v.width + pcol, sample);
+                            path_pixel<S>(a.v, a.pix0, i, prow, pcol, sample, list);
+                            const RayV pr = pixel_ray<S>(a.v, prow, pcol, a.seed, prow * a.v.width + pcol, sample);
                             no = make_float4(pr.orig.x, pr.orig.y, pr.orig.z, pr.orig.w);
                             nd = make_float4(pr.dir.x, pr.dir.y, pr.dir.z, pr.dir.w);
                             npath = i; nbounce = 0u;
@@ -901,12 +901,12 @@ __global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_slow(DScene sc, Oc
 template <bool COUNT, bool FAST>
 __global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_primary_samples(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min, int xcd_aware) {
     extern __shared__ uint32_t lds[];
-    oct_walk<COUNT, FAST, W_PRIMARY, true>(sc, a, ctrl, lds, refill_min, xcd_aware);
+    oct_walk<COUNT, FAST, W_PRIMARY, Samp::PASS>(sc, a, ctrl, lds, refill_min, xcd_aware);
 }
 template <bool COUNT, bool FAST>
 __global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_slow_samples(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min, int xcd_aware) {
     extern __shared__ uint32_t lds[];
-    oct_walk<COUNT, FAST, W_SLOW, true>(sc, a, ctrl, lds, refill_min, xcd_aware);
+    oct_walk<COUNT, FAST, W_SLOW, Samp::PASS>(sc, a, ctrl, lds, refill_min, xcd_aware);
 }
 // ... and for adaptive passes (rtmi_render_adaptive*): local pixel q of the batch is list[pix0 + q], a tile-local pixel index.
 // The list pointer is a kernel argument of these two only (OctArgs, shared with every other walk kernel, stays as it is).
@@ -914,13 +914,13 @@ template <bool COUNT, bool FAST>
 __global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_primary_list(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min, int xcd_aware,
                                                                            const uint32_t* __restrict__ list) {
     extern __shared__ uint32_t lds[];
-    oct_walk<COUNT, FAST, W_PRIMARY, true, true>(sc, a, ctrl, lds, refill_min, xcd_aware, RecArgs{}, list);
+    oct_walk<COUNT, FAST, W_PRIMARY, Samp::LIST>(sc, a, ctrl, lds, refill_min, xcd_aware, RecArgs{}, list);
 }
 template <bool COUNT, bool FAST>
 __global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_slow_list(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min, int xcd_aware,
                                                                         const uint32_t* __restrict__ list) {
     extern __shared__ uint32_t lds[];
-    oct_walk<COUNT, FAST, W_SLOW, true, true>(sc, a, ctrl, lds, refill_min, xcd_aware, RecArgs{}, list);
+    oct_walk<COUNT, FAST, W_SLOW, Samp::LIST>(sc, a, ctrl, lds, refill_min, xcd_aware, RecArgs{}, list);
 }
 
 }  // namespace rtmi
