@@ -65,13 +65,14 @@ def stop_rule(s, q, n, rel_tol, abs_tol):
 
 
 def replay(cols, m, p, rel_tol, abs_tol):
-    """cols: (S, h, w, 4) float32, sample k's colour of every pixel.  Returns (counts, accum, sumsq, passes)."""
+    """cols: (S, h, w, 4) float32, sample k's colour of every pixel.  Returns (counts, accum, sumsq, passes, unconverged):
+    unconverged = the pixels still active at S whose stop rule fails there (rtmi_adaptive_t.unconverged)."""
     smax = cols.shape[0]
     acc = np.zeros(cols.shape[1:], np.float32)
     sq = np.zeros(cols.shape[1:], np.float32)
     counts = np.zeros(cols.shape[1:3], np.uint32)
     active = np.ones(cols.shape[1:3], bool)
-    n, k, passes = 0, m, 0
+    n, k, passes, unconverged = 0, m, 0, 0
     while True:
         for j in range(n, n + k):
             c = cols[j]
@@ -81,21 +82,23 @@ def replay(cols, m, p, rel_tol, abs_tol):
         passes += 1
         counts[active] = n
         if n >= smax:
+            unconverged = int((active & ~stop_rule(acc, sq, n, rel_tol, abs_tol)).sum())
             break
         active &= ~stop_rule(acc, sq, n, rel_tol, abs_tol)
         if not active.any():
             break
         k = min(p, smax - n)
-    return counts, acc, sq, passes
+    return counts, acc, sq, passes, unconverged
 
 
 def pick_tol(cols, m, p):
-    for rel, ab in TOLS:
+    """The first of TOLS, then of a sweep of absolute tolerances, whose replayed count map has m, S and a value between."""
+    for rel, ab in TOLS + [(0.0, float(x)) for x in np.geomspace(1e-4, 0.5, 40)]:
         counts = replay(cols, m, p, rel, ab)[0]
         u = set(np.unique(counts).tolist())
         if m in u and cols.shape[0] in u and len(u) >= 3:
             return rel, ab
-    raise AssertionError("no tolerance in TOLS gives a count map with m, S and a value between")
+    raise AssertionError("no tolerance gives a count map with m, S and a value between")
 
 
 # ---------------------------------------------------------------- what the child processes run
@@ -293,9 +296,10 @@ def _check_per_count(img, counts, refs, what):
 
 def _check_replay(a, info, m, p):
     rel, ab = info["tol"]
-    counts, acc, sq, passes = replay(a["cols"], m, p, rel, ab)
+    counts, acc, sq, passes, unconverged = replay(a["cols"], m, p, rel, ab)
     assert np.array_equal(a["counts"], counts), "count map vs the float32 replay"
     assert info["passes"] == passes and info["samples"] == int(counts.sum())
+    assert info["unconverged"] == unconverged, (info["unconverged"], unconverged)
     return counts, acc, sq
 
 
@@ -332,6 +336,7 @@ def test_middle_tolerance_every_pixel_exact_at_its_count(tmp_path):
     assert_bits_equal(a["dev_sumsq"], sq, "sumsq vs replay")
     assert (a["dev_sumsq"][..., 3] == 0).all()
     assert info["dev"]["passes"] == info["passes"] and info["dev"]["samples"] == info["samples"]
+    assert info["dev"]["unconverged"] == info["unconverged"]
     assert info["dev"]["rays"] == info["stats"]["rays"]
 
 

@@ -138,12 +138,21 @@ def test_replay_of_the_stop_rule():
     cols = rng.random((16, 3, 5, 4), dtype=np.float32)
     cols[..., 3] = 0
     cols[:, 0, 0] = np.float32(0.25)  # zero variance
-    counts, acc, sq, passes = replay(cols, 4, 4, 0.0, NAN)
-    assert (counts == 16).all() and passes == 4
+    counts, acc, sq, passes, unconverged = replay(cols, 4, 4, 0.0, NAN)
+    assert (counts == 16).all() and passes == 4 and unconverged == 15
     assert np.array_equal(acc, np.cumsum(cols, axis=0, dtype=np.float32)[-1])
-    counts, _, _, passes = replay(cols, 4, 4, 0.0, float("inf"))
-    assert (counts == 4).all() and passes == 1
-    counts, _, _, _ = replay(cols, 4, 4, 0.0, 1e-6)
-    assert counts[0, 0] == 4 and (counts[1:] == 16).all()
+    counts, _, _, passes, unconverged = replay(cols, 4, 4, 0.0, float("inf"))
+    assert (counts == 4).all() and passes == 1 and unconverged == 0
+    counts, _, _, _, unconverged = replay(cols, 4, 4, 0.0, 1e-6)
+    assert counts[0, 0] == 4 and (counts[1:] == 16).all() and unconverged == 14
+    # the schedule's edges: m == S is one pass whose failing pixels are all unconverged; a last pass clamped to S; S = m = 2
+    counts, _, _, passes, unconverged = replay(cols[:6], 6, 4, 0.0, 1e-6)
+    assert (counts == 6).all() and passes == 1 and unconverged == 14
+    counts, _, _, passes, _ = replay(cols[:7], 2, 3, 0.0, 1e-6)
+    assert passes == 3 and set(np.unique(counts).tolist()) == {2, 7}
+    counts, _, _, passes, unconverged = replay(cols[:2], 2, 2, 0.0, NAN)
+    assert (counts == 2).all() and passes == 1 and unconverged == 15
+    counts, _, _, passes, _ = replay(cols[:9], 2, 1, 0.0, NAN)
+    assert (counts == 9).all() and passes == 8
     s = np.array([np.nan, 0, 0, 0], np.float32)
     assert not stop_rule(s, s, 4, 0.0, np.inf)
