@@ -281,6 +281,26 @@ int rtmi_render_adaptive_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, 
 int rtmi_render_adaptive(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
                          rtmi_adaptive_t* ad, float* out_host, uint32_t* counts_host, rtmi_stats_t* stats);
 
+/* A batch of views of one scene in one call: a camera move, a stereo pair, the faces of a cube map, many
+ * small windows.  vps[k] and seeds[k] are view k: what rtmi_render(scene, &vps[k], seeds[k], 0, H, ...) would render, bit
+ * for bit (the RNG of a pixel is keyed by its view's seed and its pixel index inside the view, its primary rays come from
+ * its view's camera; everything else is shared).  All views share width, height, maxdepth and samples_per_pixel
+ * (RTMI_ERR_INVALID naming the first view that differs); orig/cam/vu/vv and the seed are per view.
+ * The batch is ONE stacked image of nviews * H rows: row k*H + r is row r of view k.  rtmi_render_views renders the whole
+ * stack into out_host (nviews * H * W * 4 floats).  rtmi_render_views_device renders `tile` of the stack (rtmi_tile_t rules;
+ * stripes may cross view boundaries) and enqueues on hip_stream like rtmi_render_tile_device.  Streams, batches and the
+ * automatic stream rule apply to the stack as a whole.  stats cover the whole call: rays and the five work counters are
+ * the sums over the views' single calls.  A batch of one view runs the single-view kernels (it is that view's call).
+ * RTMI_ERR_INVALID, before any HIP call: nviews == 0; a NULL scene, vps, seeds or output; views that differ in a shared
+ * field; a tile outside the stack; every check rtmi_render_tile_device makes for one view.  RTMI_ERR_UNSUPPORTED: nviews *
+ * H * W >= 2^32.
+ * Not for views (render them one call per view): progressive and adaptive passes, rtmi_render_frame_multi, per-ray
+ * records. */
+int rtmi_render_views_device(rtmi_scene_t* scene, const rtmi_viewport_t* vps, const uint64_t* seeds, uint32_t nviews,
+                             const rtmi_tile_t* tile, void* out_device, void* hip_stream, rtmi_stats_t* stats);
+int rtmi_render_views(rtmi_scene_t* scene, const rtmi_viewport_t* vps, const uint64_t* seeds, uint32_t nviews,
+                      float* out_host, rtmi_stats_t* stats);
+
 /* One whole frame over several devices of this process -- the fan-out the reference does over CPU threads
  * (DefaultRayCaster::walk_rays_internal, raytrace.rs:1175-1196: `threads` workers pulling rows from a queue) done
  * over GPUs, inside the library.  scenes[i] is the SAME scene uploaded to some device (rtmi_scene_create with

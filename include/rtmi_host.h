@@ -97,6 +97,14 @@ int rth_caster_walk_adaptive_device(rth_scene_t* s, uint32_t w, uint32_t h, cons
                                     const rtmi_tile_t* tile, rtmi_adaptive_t* ad, void* accum_device, void* sumsq_device,
                                     void* counts_device, void* out_device, void* hip_stream, rtmi_stats_t* stats,
                                     double* wall_seconds);
+/* A batch of views (rtmi_render_views / rtmi_render_views_device in rtmi.h): nviews viewports of one size, maxdepth and spp,
+ * vp12s = 12 floats per view; seeds (nviews entries, or NULL: the caster's seed for every view).  out receives the stacked
+ * image, nviews * h rows (row k * h + r = row r of view k); the device variant renders `tile` of it. */
+int rth_caster_walk_views(rth_scene_t* s, uint32_t nviews, uint32_t w, uint32_t h, const float* vp12s, uint64_t maxdepth, uint64_t spp,
+                          const uint64_t* seeds, float* out_host, rtmi_stats_t* stats, double* wall_seconds);
+int rth_caster_walk_views_device(rth_scene_t* s, uint32_t nviews, uint32_t w, uint32_t h, const float* vp12s, uint64_t maxdepth,
+                                 uint64_t spp, const uint64_t* seeds, const rtmi_tile_t* tile, void* out_device, void* hip_stream,
+                                 rtmi_stats_t* stats, double* wall_seconds);
 int rth_caster_trace(rth_scene_t* s, uint64_t n, const float* orig4, const float* dir4, uint32_t* tri, float* t,
                      uint32_t* face, rtmi_stats_t* stats);
 /* Per-ray records (rtmi_trace_records / rtmi_primary_records, same buffers and size-query idiom) on the scene's

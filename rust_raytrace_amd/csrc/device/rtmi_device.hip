@@ -492,18 +492,20 @@ __global__ void __launch_bounds__(256) k_trace_linear(DScene sc, const float4* _
 
 // ---------------------------------------------------------------- generation / shading (per-pass pipeline)
 // pixel_ray / color_ray themselves are in shade.hpp (shared with the path kernels of trace_oct.hpp).
-// S (shade.hpp): k_gen / k_shade are Samp::FRAME, k_gen_samples / k_shade_samples PASS, k_gen_list / k_shade_list LIST.
+// S (shade.hpp): k_gen / k_shade are Samp::FRAME, k_gen_samples / k_shade_samples PASS, k_gen_list / k_shade_list LIST,
+// k_gen_views / k_shade_views VIEWS (the view table is an argument of these two only).
 #define RTMI_GEN_PARAMS uint64_t seed, uint32_t pix0, uint32_t npaths, float4* __restrict__ qo, float4* __restrict__ qd, \
                         uint32_t* __restrict__ qpath, DCtrl* __restrict__ ctrl
 #define RTMI_GEN_ARGS v, seed, pix0, npaths, qo, qd, qpath, ctrl
 template <Samp S>
-__device__ __forceinline__ void gen_paths(const DView& v, RTMI_GEN_PARAMS, const uint32_t* __restrict__ list = nullptr) {
+__device__ __forceinline__ void gen_paths(const DView& v, RTMI_GEN_PARAMS, const uint32_t* __restrict__ list = nullptr,
+                                          const ViewTab& vt = ViewTab{}) {
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t path = blockIdx.x * blockDim.x + threadIdx.x; path < npaths; path += stride) {
         uint32_t row, col, sample;
         path_pixel<S>(v, pix0, path, row, col, sample, list);
-        const uint32_t pixel = row * v.width + col;
-        RayV r = pixel_ray<S>(v, row, col, seed, pixel, sample);
+        const PixKey key = pixel_key<S>(v, row, vt);
+        RayV r = pixel_ray<S>(v, key.row, col, key_seed<S>(key, vt, seed), key.row * v.width + col, sample, S == Samp::VIEWS ? &vt.cams[key.view] : nullptr);
         qo[path] = make_float4(r.orig.x, r.orig.y, r.orig.z, r.orig.w);
         qd[path] = make_float4(r.dir.x, r.dir.y, r.dir.z, r.dir.w);
         qpath[path] = path;
@@ -513,6 +515,7 @@ __device__ __forceinline__ void gen_paths(const DView& v, RTMI_GEN_PARAMS, const
 __global__ void __launch_bounds__(256) k_gen(DView v, RTMI_GEN_PARAMS) { gen_paths<Samp::FRAME>(RTMI_GEN_ARGS); }
 __global__ void __launch_bounds__(256) k_gen_samples(DView v, RTMI_GEN_PARAMS) { gen_paths<Samp::PASS>(RTMI_GEN_ARGS); }
 __global__ void __launch_bounds__(256) k_gen_list(DView v, RTMI_GEN_PARAMS, const uint32_t* __restrict__ list) { gen_paths<Samp::LIST>(RTMI_GEN_ARGS, list); }
+__global__ void __launch_bounds__(256) k_gen_views(DView v, RTMI_GEN_PARAMS, ViewTab vt) { gen_paths<Samp::VIEWS>(RTMI_GEN_ARGS, nullptr, vt); }
 
 // color_ray + the tail of project_ray for every ray of pass `pass`.
 #define RTMI_SHADE_PARAMS DScene sc, DView v, uint64_t seed, uint32_t pix0, uint32_t npaths, int pass,                  \
@@ -523,7 +526,7 @@ __global__ void __launch_bounds__(256) k_gen_list(DView v, RTMI_GEN_PARAMS, cons
                           DCtrl* __restrict__ ctrl, SlowQ slow
 #define RTMI_SHADE_ARGS sc, v, seed, pix0, npaths, pass, qo, qd, qpath, hit_tf, hit_t, qo_n, qd_n, qpath_n, mstack, scol, ctrl, slow
 template <Samp S>
-__device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list = nullptr) {
+__device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list = nullptr, const ViewTab& vt = ViewTab{}) {
     __shared__ uint32_t s_cnt[4], s_base;
     const uint32_t count = ctrl->count[pass];
     const uint32_t stride = gridDim.x * blockDim.x;
@@ -545,7 +548,8 @@ __device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __
             if ((tf & 0x3FFFFFFFu) != 0u && !((tf >> 30) & 2u)) { t = hit_t[i]; o4 = qo[i]; d4 = qd[i]; }
             uint32_t prow, pcol, sample;
             path_pixel<S>(v, pix0, path, prow, pcol, sample, list);
-            push = shade_hit(sc, v.maxdepth, seed, npaths, path, prow * v.width + pcol, sample, (uint32_t)pass, tf, t,
+            const PixKey key = pixel_key<S>(v, prow, vt);
+            push = shade_hit(sc, v.maxdepth, key_seed<S>(key, vt, seed), npaths, path, key.row * v.width + pcol, sample, (uint32_t)pass, tf, t,
                              V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr);
             // a bounce ray with an exactly-zero direction component goes to the slow path (SlowQ), not to the next pass
             if (push && slow.cap && has_zero_component(nr.dir.x, nr.dir.y, nr.dir.z) &&
@@ -580,6 +584,7 @@ __device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __
 __global__ void __launch_bounds__(256) k_shade(RTMI_SHADE_PARAMS) { shade_pass<Samp::FRAME>(RTMI_SHADE_ARGS); }
 __global__ void __launch_bounds__(256) k_shade_samples(RTMI_SHADE_PARAMS) { shade_pass<Samp::PASS>(RTMI_SHADE_ARGS); }
 __global__ void __launch_bounds__(256) k_shade_list(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list) { shade_pass<Samp::LIST>(RTMI_SHADE_ARGS, list); }
+__global__ void __launch_bounds__(256) k_shade_views(RTMI_SHADE_PARAMS, ViewTab vt) { shade_pass<Samp::VIEWS>(RTMI_SHADE_ARGS, nullptr, vt); }
 
 // walk_ray_set's per-pixel accumulation (raytrace.rs:1414-1426): acc = 0; acc += sample_i in sample order; * (1/spp).
 // The sample colours of a pixel are consecutive in `scol` ([pixel][sample]), so one thread per pixel would read 16 B at a
@@ -951,6 +956,12 @@ struct rtmi_scene {
     DevBuf<float4> asq;              // rtmi_render_adaptive: the per-pixel sums of squares of the host variant
     DevBuf<uint32_t> acnt;           // rtmi_render_adaptive: the per-pixel sample counts of the host variant
     DevBuf<uint32_t> alist[2], ablk; // rtmi_render_adaptive*: active-pixel lists (ping-pong), per-block counts / offsets + total
+    // rtmi_render_views*: the view table (grows only), the host copy it is uploaded from and the event recorded behind that
+    // upload.  The next views call waits for the event before it rewrites the host copy, also when the call that uploaded
+    // it failed before its final synchronisation.
+    DevBuf<VCam> vcams;
+    std::vector<VCam> hvcams;
+    hipEvent_t vcams_ev = nullptr;
     DevBuf<uint8_t> qbytes;
     DevBuf<uint8_t> mstage, mframe;  // rtmi_render_frame_multi, root scene: received bands / the frame
     hipStream_t mstream = nullptr;   // rtmi_render_frame_multi: this scene's band stream
@@ -1387,6 +1398,8 @@ int rtmi_scene_destroy(rtmi_scene_t* s) {
     s->rec_cnt.release(); s->rec_ids.release(); s->rec_first.release();
     s->tile.release(); s->acc.release(); s->asq.release(); s->acnt.release();
     s->alist[0].release(); s->alist[1].release(); s->ablk.release(); s->qbytes.release(); s->mstage.release(); s->mframe.release();
+    s->vcams.release();
+    if (s->vcams_ev) (void)hipEventDestroy(s->vcams_ev);
     if (s->mstream) (void)hipStreamDestroy(s->mstream);
     if (!s->comms.empty()) { if (Rccl* r = rccl_api()) for (ncclComm_t c : s->comms) (void)r->CommDestroy(c); }
     delete s;
@@ -1512,7 +1525,8 @@ static dim3 oct_grid(const rtmi_scene* s) {
 
 // The octree walk kernels of trace_oct.hpp as [count][fast] of their <bool COUNT, bool FAST> templates.  A batch's path
 // kernels follow its sampling mode (shade.hpp): k_path_primary / k_path_slow for Samp::FRAME, the *_samples kernels for
-// PASS, the *_list kernels for LIST; these take the list as one more argument and so have a function type of their own.
+// PASS, the *_list kernels for LIST and the *_views kernels for VIEWS; these two take the list or the view table as one more
+// argument and so have function types of their own.
 #define RTMI_COUNT_FAST(k) {{k<false, false>, k<false, true>}, {k<true, false>, k<true, true>}}
 typedef void (*WalkKernel)(DScene, OctArgs, DCtrl*, int, int);
 typedef void (*ListWalkKernel)(DScene, OctArgs, DCtrl*, int, int, const uint32_t*);
@@ -1521,6 +1535,8 @@ static const WalkKernel path_variant[2][2][2][2] = {  // [slow][mode == Samp::PA
     {RTMI_COUNT_FAST(k_path_primary), RTMI_COUNT_FAST(k_path_primary_samples)},
     {RTMI_COUNT_FAST(k_path_slow), RTMI_COUNT_FAST(k_path_slow_samples)}};
 static const ListWalkKernel path_list_variant[2][2][2] = {RTMI_COUNT_FAST(k_path_primary_list), RTMI_COUNT_FAST(k_path_slow_list)};
+typedef void (*ViewsWalkKernel)(DScene, OctArgs, DCtrl*, int, int, ViewTab);
+static const ViewsWalkKernel path_views_variant[2][2][2] = {RTMI_COUNT_FAST(k_path_primary_views), RTMI_COUNT_FAST(k_path_slow_views)};
 
 static void launch_trace(rtmi_scene* s, Work& w, hipStream_t st, const float4* qo, const float4* qd, int pass, bool count, hipEvent_t stop) {
     // `stop` is recorded right after the closest-hit kernel, so that the event pair of the caller times exactly
@@ -1558,9 +1574,11 @@ static SlowQ slow_queue(rtmi_scene* s, Work& w) {
 }
 // One launch of the path kernel of the batch's sampling mode: k_path_primary* (slow = false) or k_path_slow*
 static void launch_path(rtmi_scene* s, Work& w, hipStream_t st, dim3 grid, const OctArgs& a, int refill, int xcd, bool slow,
-                        bool count, Samp mode, const uint32_t* list) {
+                        bool count, Samp mode, const uint32_t* list, const ViewTab& vt) {
     const bool fast = (s->options & RTMI_OPT_FAST) != 0;
-    if (mode == Samp::LIST)
+    if (mode == Samp::VIEWS)
+        hipLaunchKernelGGL(path_views_variant[slow][count][fast], grid, dim3(64), oct_launch_lds(s, count), st, s->d, a, w.ctrl.p, refill, xcd, vt);
+    else if (mode == Samp::LIST)
         hipLaunchKernelGGL(path_list_variant[slow][count][fast], grid, dim3(64), oct_launch_lds(s, count), st, s->d, a, w.ctrl.p, refill, xcd, list);
     else
         hipLaunchKernelGGL(path_variant[slow][mode == Samp::PASS][count][fast], grid, dim3(64), oct_launch_lds(s, count), st, s->d, a, w.ctrl.p, refill, xcd);
@@ -1569,17 +1587,18 @@ static void launch_path(rtmi_scene* s, Work& w, hipStream_t st, dim3 grid, const
 // The mirror reflections it traces itself go on in queue 2 (ping-pong buffer 0, free until pass 1's k_shade appends to it).
 // `stop` is recorded right after the kernel.
 static void launch_primary(rtmi_scene* s, Work& w, hipStream_t st, OctArgs a, bool count, Samp mode, const uint32_t* list,
-                           hipEvent_t stop) {
+                           const ViewTab& vt, hipEvent_t stop) {
     a.bqo = w.qo[1].p; a.bqd = w.qd[1].p; a.bqpath = w.qpath[1].p;
     a.vote_s = s->vote[0]; a.vote_l = s->vote[1];
     a.pcull = s->packet_cull;
     a.b2qo = w.qo[0].p; a.b2qd = w.qd[0].p; a.b2qpath = w.qpath[0].p;
     a.minpl = s->mirror_inplace;
-    launch_path(s, w, st, oct_grid(s), a, (int)s->tune.refill_min0, (int)(s->tune.xcd_aware % 3u), false, count, mode, list);
+    launch_path(s, w, st, oct_grid(s), a, (int)s->tune.refill_min0, (int)(s->tune.xcd_aware % 3u), false, count, mode, list, vt);
     (void)hipEventRecord(stop, st);
 }
 // Consumer launch k of the slow path (k_path_slow), on the side stream: after the producer on `st` whose event is sev[k]
-static void launch_slow(rtmi_scene* s, Work& w, hipStream_t st, OctArgs a, uint32_t k, bool count, Samp mode, const uint32_t* list) {
+static void launch_slow(rtmi_scene* s, Work& w, hipStream_t st, OctArgs a, uint32_t k, bool count, Samp mode, const uint32_t* list,
+                        const ViewTab& vt) {
     a.slow_k = k;
     a.vote_s = s->vote[2]; a.vote_l = s->vote[3];
     (void)hipStreamWaitEvent(w.sstream, w.sev[k], 0);
@@ -1591,7 +1610,7 @@ static void launch_slow(rtmi_scene* s, Work& w, hipStream_t st, OctArgs a, uint3
     (void)hipEventRecord(w.sgo, w.sstream);
     (void)hipStreamWaitEvent(st, w.sgo, 0);
     const dim3 sgrid((unsigned)std::max(s->num_cu / 2, 1));  // one path per wave at a time; a frame has ~100 such paths, a wave takes one after the other
-    launch_path(s, w, w.sstream, sgrid, a, 1, 0, true, count, mode, list);
+    launch_path(s, w, w.sstream, sgrid, a, 1, 0, true, count, mode, list, vt);
 }
 
 // The work counters of a stream's control block as stats
@@ -1630,7 +1649,8 @@ struct TileCall {
     uint32_t sample0, spp, maxdepth, W;  // spp: samples per pixel of this call
     float4 *accum, *out;
     const ListPass* lp;
-    Samp mode;  // LIST with lp, PASS with accum, FRAME otherwise
+    ViewTab vt;  // VIEWS: the view table (cams == nullptr otherwise)
+    Samp mode;  // LIST with lp, PASS with accum, VIEWS with vt.cams, FRAME otherwise
     bool counting, path_kernels;
     uint32_t nsub;
     uint64_t pix_per_batch, max_npix;  // max_npix: pixels of the largest sub-tile
@@ -1769,17 +1789,19 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
     auto slow_after = [&](uint32_t k) {  // after producer k: k_path_primary (0) or the shading of pass k
         if (sq.cap == 0u) return;
         (void)hipEventRecord(w.sev[k], st);
-        launch_slow(s, w, st, pa, k, c.counting, c.mode, list);
+        launch_slow(s, w, st, pa, k, c.counting, c.mode, list, c.vt);
     };
     uint32_t pass0 = 0;  // first pass of the per-pass loop
     if (c.path_kernels) {
         HIPCHK(hipEventRecord(w.pass_ev[0], st));
-        launch_primary(s, w, st, pa, c.counting, c.mode, list, w.pass_ev[1]);
+        launch_primary(s, w, st, pa, c.counting, c.mode, list, c.vt, w.pass_ev[1]);
         HIPCHK(hipGetLastError());
         slow_after(0);
         pass0 = 1;
     } else if (list) {
         hipLaunchKernelGGL(k_gen_list, ew_grid, ew_block, 0, st, dv, c.seed, pix0, npaths, w.qo[0].p, w.qd[0].p, w.qpath[0].p, w.ctrl.p, list);
+    } else if (c.mode == Samp::VIEWS) {
+        hipLaunchKernelGGL(k_gen_views, ew_grid, ew_block, 0, st, dv, c.seed, pix0, npaths, w.qo[0].p, w.qd[0].p, w.qpath[0].p, w.ctrl.p, c.vt);
     } else {
         hipLaunchKernelGGL(c.mode == Samp::PASS ? k_gen_samples : k_gen, ew_grid, ew_block, 0, st, dv, c.seed, pix0, npaths, w.qo[0].p,
                            w.qd[0].p, w.qpath[0].p, w.ctrl.p);
@@ -1797,6 +1819,9 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
         if (list)
             hipLaunchKernelGGL(k_shade_list, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
                                w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, list);
+        else if (c.mode == Samp::VIEWS)
+            hipLaunchKernelGGL(k_shade_views, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
+                               w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, c.vt);
         else
             hipLaunchKernelGGL(c.mode == Samp::PASS ? k_shade_samples : k_shade, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths,
                                (int)pass, w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p,
@@ -1813,6 +1838,7 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
     }
     switch (c.mode) {
     case Samp::FRAME:
+    case Samp::VIEWS:  // the stacked tile: k_accum does not know about views
         hipLaunchKernelGGL(k_accum, ew_grid, ew_block, 0, st, np, c.spp, w.scol.p, (float*)c.out, pix0, c.W, c.nsub, t, make_fastdiv(c.W));
         break;
     case Samp::PASS:
@@ -1854,9 +1880,11 @@ static int collect_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
 // from the paths of THIS call, npix * nsamples.
 // lp != nullptr (with accum): an adaptive pass over the pixels of lp->list (Samp::LIST), dealt out to the streams in
 // contiguous chunks of the list.  Batches and automatic streams are then sized from lp->n * nsamples.
+// views > 0 (no accum): a batch of views (Samp::VIEWS, rtmi_render_views_device); vp is the stacked image (height = views *
+// the views' height) and s->hvcams holds the view table, uploaded here on hip_stream before the internal streams fork.
 static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile, uint32_t sample0,
                        uint32_t nsamples, float4* accum, void* out_device, void* hip_stream, rtmi_stats_t* stats,
-                       const ListPass* lp = nullptr) {
+                       const ListPass* lp = nullptr, uint32_t views = 0) {
     if (stats) memset(stats, 0, sizeof(*stats));
     if (tile->nrows == 0) return RTMI_OK;
     RTMI_GUARD_BEGIN
@@ -1878,11 +1906,20 @@ static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed
     }
     TileCall c;
     c.seed = seed; c.sample0 = sample0; c.spp = nsamples; c.maxdepth = vp->maxdepth; c.W = vp->width;
-    c.accum = accum; c.out = out; c.lp = lp;
-    c.mode = lp ? Samp::LIST : accum ? Samp::PASS : Samp::FRAME;
+    c.accum = accum; c.out = out; c.lp = lp; c.vt = ViewTab{nullptr, FastDiv{}};
+    c.mode = lp ? Samp::LIST : accum ? Samp::PASS : views ? Samp::VIEWS : Samp::FRAME;
     c.counting = (s->options & RTMI_OPT_COUNTERS) != 0;
     rc = plan_tile(s, vp, tile, c);
     if (rc != RTMI_OK) return rc;
+    if (views) {  // the views share one height: pixel_ray's vv_delta and pixel_key's row split use it, not the stack's
+        const uint32_t h = vp->height / views;
+        for (uint32_t t = 0; t < c.nsub; t++) c.sub[t].dv.height = h;
+        HIPCHK(s->vcams.ensure(views));
+        HIPCHK(hipMemcpyAsync(s->vcams.p, s->hvcams.data(), views * sizeof(VCam), hipMemcpyHostToDevice, ust));
+        if (!s->vcams_ev) HIPCHK(hipEventCreateWithFlags(&s->vcams_ev, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(s->vcams_ev, ust));  // set_views of the next call waits for it
+        c.vt = ViewTab{s->vcams.p, make_fastdiv(h)};
+    }
 
     // internal streams start after whatever the caller queued on its stream
     HIPCHK(hipEventRecord(s->fork_ev, ust));
@@ -2093,6 +2130,91 @@ int rtmi_render_adaptive(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t se
     if (rc != RTMI_OK) return rc;
     HIPCHK(hipMemcpy(out_host, s->tile.p, npix * sizeof(float4), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(counts_host, s->acnt.p, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+// ---------------------------------------------------------------- batches of views
+// Checks of the views entry points, before any HIP call and before the scene is used: the arguments, the shared fields of
+// the views (the first view that differs is named), every check check_view makes for one view, the size of the stacked
+// image and (tile != nullptr, nrows >= 1) the tile against it.  stack receives the stacked viewport: view 0 with
+// height = nviews * height.
+static int check_views(rtmi_scene_t* s, const rtmi_viewport_t* vps, const uint64_t* seeds, uint32_t nviews, const rtmi_tile_t* tile,
+                       const void* out, rtmi_viewport_t& stack) {
+    if (!s) return fail(RTMI_ERR_INVALID, "NULL argument (scene)");
+    if (!vps || !seeds) return fail(RTMI_ERR_INVALID, "NULL argument (viewports or seeds)");
+    if (!out) return fail(RTMI_ERR_INVALID, "NULL argument (output)");
+    if (nviews == 0) return fail(RTMI_ERR_INVALID, "nviews must be >= 1");
+    const rtmi_viewport_t& v0 = vps[0];
+    for (uint32_t k = 1; k < nviews; k++) {
+        const rtmi_viewport_t& v = vps[k];
+        const char* field = v.width != v0.width ? "width" : v.height != v0.height ? "height" : v.maxdepth != v0.maxdepth ? "maxdepth"
+                          : v.samples_per_pixel != v0.samples_per_pixel ? "samples_per_pixel" : nullptr;
+        if (field)
+            return fail(RTMI_ERR_INVALID, "view " + std::to_string(k) + ": " + field +
+                                              " differs from view 0 (the views share width, height, maxdepth and samples_per_pixel)");
+    }
+    const rtmi_tile_t one_row{0u, 1u, 1u, 0u};
+    int rc = check_view(&v0, &one_row);  // what it checks of a view are the shared fields: view 0 speaks for all
+    if (rc != RTMI_OK) return fail(rc, "view 0: " + g_err);
+    if ((uint64_t)nviews * v0.height * v0.width >= (1ull << 32)) return fail(RTMI_ERR_UNSUPPORTED, "more than 2^32 pixels in the stack of views");
+    stack = v0;
+    stack.height = nviews * v0.height;
+    if (tile && tile->nrows != 0) {
+        rc = check_view(&stack, tile);
+        if (rc != RTMI_OK) return fail(rc, "stack of " + std::to_string(nviews) + " views: " + g_err);
+    }
+    return RTMI_OK;
+}
+// The view table of a call into s->hvcams (the host copy render_tile uploads), once the previous call's upload from it has
+// completed
+static int set_views(rtmi_scene* s, const rtmi_viewport_t* vps, const uint64_t* seeds, uint32_t nviews) {
+    HIPCHK(hipSetDevice(s->device));
+    if (s->vcams_ev) HIPCHK(hipEventSynchronize(s->vcams_ev));
+    s->hvcams.resize(nviews);
+    for (uint32_t k = 0; k < nviews; k++) {
+        const rtmi_viewport_t& v = vps[k];
+        VCam& c = s->hvcams[k];
+        c.orig = make_float4(v.orig[0], v.orig[1], v.orig[2], 0.f);
+        c.cam = make_float4(v.cam[0], v.cam[1], v.cam[2], 0.f);
+        c.vu = make_float4(v.vu[0], v.vu[1], v.vu[2], 0.f);
+        c.vv = make_float4(v.vv[0], v.vv[1], v.vv[2], 0.f);
+        c.seed = seeds[k];
+        c.pad[0] = c.pad[1] = 0u;
+    }
+    return RTMI_OK;
+}
+
+int rtmi_render_views_device(rtmi_scene_t* s, const rtmi_viewport_t* vps, const uint64_t* seeds, uint32_t nviews,
+                             const rtmi_tile_t* tile, void* out_device, void* hip_stream, rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!tile) return fail(RTMI_ERR_INVALID, "NULL argument (tile)");
+    rtmi_viewport_t stack;
+    const int rc = check_views(s, vps, seeds, nviews, tile, out_device, stack);
+    if (rc != RTMI_OK) return rc;
+    if (tile->nrows == 0) return RTMI_OK;
+    // One view has nothing to batch: it is rtmi_render_tile_device's call, on the FRAME kernels (which keep the camera in
+    // their launch constants instead of loading it from the table: 0.9 % of a config-3 frame)
+    if (nviews == 1) return render_tile(s, &vps[0], seeds[0], tile, 0u, vps[0].samples_per_pixel, nullptr, out_device, hip_stream, stats);
+    RTMI_GUARD_BEGIN
+    const int rc1 = set_views(s, vps, seeds, nviews);
+    if (rc1 != RTMI_OK) return rc1;
+    return render_tile(s, &stack, 0u, tile, 0u, stack.samples_per_pixel, nullptr, out_device, hip_stream, stats, nullptr, nviews);
+    RTMI_GUARD_END
+}
+
+int rtmi_render_views(rtmi_scene_t* s, const rtmi_viewport_t* vps, const uint64_t* seeds, uint32_t nviews, float* out_host,
+                      rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    rtmi_viewport_t stack;
+    const int rc0 = check_views(s, vps, seeds, nviews, nullptr, out_host, stack);
+    if (rc0 != RTMI_OK) return rc0;
+    const uint64_t npix = (uint64_t)stack.height * stack.width;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(s->tile.ensure(npix));
+    const rtmi_tile_t tile{0u, stack.height, stack.height, 0u};
+    const int rc = rtmi_render_views_device(s, vps, seeds, nviews, &tile, s->tile.p, nullptr, stats);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(hipMemcpy(out_host, s->tile.p, npix * sizeof(float4), hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
 

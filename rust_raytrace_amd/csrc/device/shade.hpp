@@ -64,14 +64,41 @@ __device__ inline void tile_pixel(const DView& v, uint32_t lp, uint32_t& row, ui
 // of its pixels (DView::sample_key).  LIST: an adaptive pass, a PASS whose pixels are entries pix0, pix0 + 1, ... of the
 // active-pixel list, each a tile-local pixel index (row-major over the tile's rows; the launch's DView has sub_mul = 1,
 // sub_off = 0).  The list pointer is an argument of the list kernels only, so the other kernels keep their launch constants.
-enum class Samp { FRAME, PASS, LIST };
+// VIEWS: a batch of views of one scene (rtmi_render_views*), FRAME semantics over a stacked image whose row
+// k * height + r is row r of view k; each view has its own camera and seed (ViewTab, an argument of the views kernels only).
+enum class Samp { FRAME, PASS, LIST, VIEWS };
+// Samp::VIEWS: view k's camera (lane 3 of every vector +0, as mk() makes them) and seed
+struct VCam { float4 orig, cam, vu, vv; unsigned long long seed; uint32_t pad[2]; };
+// the view table of a VIEWS launch: one VCam per view, and n / height (height = the rows of ONE view, DView::height)
+struct ViewTab { const VCam* __restrict__ cams; FastDiv dh; };
+// Samp::VIEWS: what the RNG and pixel_ray see of image row `row` of the stacked image -- its view k = row / height and its row
+// inside that view -- and (key_seed) the view's seed.  Pixel (row, col) of the stack is then pixel key.row * width + col of
+// view key.view, the RNG key of rtmi_render's call for that view.  The other modes render one view: view 0, the row itself,
+// the launch's seed.  The callers compute the pixel key and read the seed where they pass them on, in the order they always
+// did, so that those modes compile to the code they had before views existed (LLVM's reassociation orders the Philox
+// xors by where their operands are defined).
+struct PixKey { uint32_t view, row; };
+template <Samp S>
+__device__ inline PixKey pixel_key(const DView& v, uint32_t row, const ViewTab& vt) {
+    if constexpr (S == Samp::VIEWS) {
+        const uint32_t k = fdiv(row, vt.dh);
+        return PixKey{k, row - k * v.height};
+    } else {
+        return PixKey{0u, row};
+    }
+}
+template <Samp S>
+__device__ inline uint64_t key_seed(const PixKey& key, const ViewTab& vt, uint64_t seed) {
+    if constexpr (S == Samp::VIEWS) return vt.cams[key.view].seed;
+    else return seed;
+}
 // path index of a batch that starts at local pixel pix0 -> image pixel index (row * width + col) and the FRAME's sample
 // number (the RNG key)
 template <Samp S>
 __device__ inline void path_pixel(const DView& v, uint32_t pix0, uint32_t path, uint32_t& row, uint32_t& col, uint32_t& sample,
                                   const uint32_t* __restrict__ list) {
     const uint32_t q = fdiv(path, v.dspp);
-    sample = (S != Samp::FRAME ? (v.sample_key & ~RTMI_KEY_JITTER) : 0u) + (path - q * v.spp);
+    sample = (S != Samp::FRAME && S != Samp::VIEWS ? (v.sample_key & ~RTMI_KEY_JITTER) : 0u) + (path - q * v.spp);
     tile_pixel(v, S == Samp::LIST ? list[pix0 + q] : pix0 + q, row, col);
 }
 
@@ -80,14 +107,17 @@ struct RayV { V4 orig, dir; };
 __device__ inline RayV make_ray(V4 orig, V4 dir) { return RayV{orig, vunit(dir)}; }
 
 // Viewport::pixel_ray (raytrace.rs:1374-1394), px = (row, col).  The centred ray is the rule of a 1-sample FRAME: a
-// pass of one sample of a larger frame (Samp::PASS / LIST) is jittered like every other sample of it.
+// pass of one sample of a larger frame (Samp::PASS / LIST) is jittered like every other sample of it.  Samp::VIEWS: (row, col)
+// inside the view, whose camera is `cam` (FRAME's rule; width and height are shared by the views).
 template <Samp S>
-__device__ inline RayV pixel_ray(const DView& v, uint32_t row, uint32_t col, uint64_t seed, uint32_t pixel, uint32_t sample) {
+__device__ inline RayV pixel_ray(const DView& v, uint32_t row, uint32_t col, uint64_t seed, uint32_t pixel, uint32_t sample,
+                                 const VCam* cam = nullptr) {
+    auto v4 = [](float4 a) { return V4{a.x, a.y, a.z, a.w}; };
     float px_x = (float)row, px_y = (float)col;
-    V4 vu_delta = vmul(v.vu, 1.f / (float)v.width);
-    V4 vv_delta = vmul(v.vv, 1.f / (float)v.height);
+    V4 vu_delta = vmul(S == Samp::VIEWS ? v4(cam->vu) : v.vu, 1.f / (float)v.width);
+    V4 vv_delta = vmul(S == Samp::VIEWS ? v4(cam->vv) : v.vv, 1.f / (float)v.height);
     float u_off = 0.5f, v_off = 0.5f;
-    if (S != Samp::FRAME ? (v.sample_key & RTMI_KEY_JITTER) != 0u : v.spp != 1) {  // spp_frame != 1
+    if (S != Samp::FRAME && S != Samp::VIEWS ? (v.sample_key & RTMI_KEY_JITTER) != 0u : v.spp != 1) {  // spp_frame != 1
         uint32_t w[4];
         rng_block(seed, pixel, sample, 0, w);
         u_off = u32_to_unit_f32(w[0]);
@@ -95,8 +125,8 @@ __device__ inline RayV pixel_ray(const DView& v, uint32_t row, uint32_t col, uin
     }
     V4 vu_frac = vmul(vu_delta, px_y + u_off);
     V4 vv_frac = vmul(vv_delta, px_x + v_off);
-    V4 px_u = vadd(vadd(v.orig, vu_frac), vv_frac);
-    return make_ray(px_u, vunit(vsub(px_u, v.cam)));
+    V4 px_u = vadd(vadd(S == Samp::VIEWS ? v4(cam->orig) : v.orig, vu_frac), vv_frac);
+    return make_ray(px_u, vunit(vsub(px_u, S == Samp::VIEWS ? v4(cam->cam) : v.cam)));
 }
 
 // random_vec (raytrace.rs:188-192): k-th call of the path uses RNG block k

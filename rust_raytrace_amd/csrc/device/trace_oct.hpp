@@ -214,11 +214,12 @@ __host__ __device__ inline bool packet_culls(const Packet& p, float4 p0, float4 
     return (c1 <= 1e15f) & (nn <= 1e15f) & (fabsf(den0) > X + X) & (x2 > (y * y) * (1.f + PK_K));
 }
 
-// S: the batch's sampling mode (W_PRIMARY / W_SLOW; Samp::LIST takes the batch's pixels from `list`, path_pixel, shade.hpp)
+// S: the batch's sampling mode (W_PRIMARY / W_SLOW; Samp::LIST takes the batch's pixels from `list`, path_pixel, shade.hpp;
+// Samp::VIEWS each pixel's camera and seed from `vt`, pixel_key)
 template <bool COUNT, bool FAST, int MODE, Samp S = Samp::FRAME>
 __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCtrl* __restrict__ ctrl, uint32_t* __restrict__ lds,
                                          int refill_min, int xcd_aware, const RecArgs& rec = RecArgs{},
-                                         const uint32_t* __restrict__ list = nullptr) {
+                                         const uint32_t* __restrict__ list = nullptr, const ViewTab& vt = ViewTab{}) {
     const int lane = threadIdx.x;  // one wave per block
     // rays from the queue of pass `a.pass`, closest hit to hit_tf / hit_t (W_RECORD is W_TRACE with a record per ray)
     constexpr bool QUEUE = MODE == W_TRACE || MODE == W_RECORD;
@@ -327,7 +328,8 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                 if (mode == M_SHADE) {
                     uint32_t prow, pcol, sample;
                     path_pixel<S>(a.v, a.pix0, pth, prow, pcol, sample, list);
-                    const bool cont = shade_hit(sc, a.v.maxdepth, a.seed, a.npaths, pth, prow * a.v.width + pcol, sample, bnc,
+                    const PixKey key = pixel_key<S>(a.v, prow, vt);  // (VIEWS: the view's row and seed; the other modes: prow, a.seed)
+                    const bool cont = shade_hit(sc, a.v.maxdepth, key_seed<S>(key, vt, a.seed), a.npaths, pth, key.row * a.v.width + pcol, sample, bnc,
                                                 ghave ? gtf : 0u, gt, V4{r.ox, r.oy, r.oz, r.ow}, V4{r.dx, r.dy, r.dz, r.dw},
                                                 a.mstack, a.scol, nr, &mirror);
                     mode = M_IDLE;
@@ -436,7 +438,9 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                         if (MODE == W_PRIMARY) {
                             uint32_t prow, pcol, sample;
                             path_pixel<S>(a.v, a.pix0, i, prow, pcol, sample, list);
-                            const RayV pr = pixel_ray<S>(a.v, prow, pcol, a.seed, prow * a.v.width + pcol, sample);
+                            const PixKey key = pixel_key<S>(a.v, prow, vt);
+                            const RayV pr = pixel_ray<S>(a.v, key.row, pcol, key_seed<S>(key, vt, a.seed), key.row * a.v.width + pcol, sample,
+                                                         S == Samp::VIEWS ? &vt.cams[key.view] : nullptr);
                             no = make_float4(pr.orig.x, pr.orig.y, pr.orig.z, pr.orig.w);
                             nd = make_float4(pr.dir.x, pr.dir.y, pr.dir.z, pr.dir.w);
                             npath = i; nbounce = 0u;
@@ -921,6 +925,20 @@ __global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_slow_list(DScene s
                                                                         const uint32_t* __restrict__ list) {
     extern __shared__ uint32_t lds[];
     oct_walk<COUNT, FAST, W_SLOW, Samp::LIST>(sc, a, ctrl, lds, refill_min, xcd_aware, RecArgs{}, list);
+}
+// ... and for batches of views (rtmi_render_views*): each view's camera and seed from the view table, an argument of these
+// two only, like the list above
+template <bool COUNT, bool FAST>
+__global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_primary_views(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min,
+                                                                            int xcd_aware, ViewTab vt) {
+    extern __shared__ uint32_t lds[];
+    oct_walk<COUNT, FAST, W_PRIMARY, Samp::VIEWS>(sc, a, ctrl, lds, refill_min, xcd_aware, RecArgs{}, nullptr, vt);
+}
+template <bool COUNT, bool FAST>
+__global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_slow_views(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min,
+                                                                         int xcd_aware, ViewTab vt) {
+    extern __shared__ uint32_t lds[];
+    oct_walk<COUNT, FAST, W_SLOW, Samp::VIEWS>(sc, a, ctrl, lds, refill_min, xcd_aware, RecArgs{}, nullptr, vt);
 }
 
 }  // namespace rtmi

@@ -289,6 +289,39 @@ int rth_caster_walk_adaptive_device(rth_scene_t* s, uint32_t w, uint32_t h, cons
         if (stats) *stats = ctx.stats;
     });
 }
+// the views of a batch: nviews viewports of one size, vp12s = 12 floats per view
+static std::vector<Viewport> views_from(uint32_t nviews, uint32_t w, uint32_t h, const float* vp12s, uint64_t maxdepth, uint64_t spp) {
+    if (nviews && !vp12s) throw std::runtime_error("NULL viewports");
+    std::vector<Viewport> views;
+    for (uint32_t k = 0; k < nviews; k++) views.push_back(vp_from(w, h, vp12s + 12 * (size_t)k, maxdepth, spp));
+    return views;
+}
+int rth_caster_walk_views(rth_scene_t* s, uint32_t nviews, uint32_t w, uint32_t h, const float* vp12s, uint64_t maxdepth, uint64_t spp,
+                          const uint64_t* seeds, float* out_host, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        const std::vector<Viewport> views = views_from(nviews, w, h, vp12s, maxdepth, spp);
+        const std::vector<uint64_t> sd = seeds ? std::vector<uint64_t>(seeds, seeds + nviews) : std::vector<uint64_t>();
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_views(views, s->scene, sd, reinterpret_cast<Color*>(out_host), ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
+int rth_caster_walk_views_device(rth_scene_t* s, uint32_t nviews, uint32_t w, uint32_t h, const float* vp12s, uint64_t maxdepth,
+                                 uint64_t spp, const uint64_t* seeds, const rtmi_tile_t* tile, void* out_device, void* hip_stream,
+                                 rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!tile) throw std::runtime_error("NULL tile");
+        const std::vector<Viewport> views = views_from(nviews, w, h, vp12s, maxdepth, spp);
+        const std::vector<uint64_t> sd = seeds ? std::vector<uint64_t>(seeds, seeds + nviews) : std::vector<uint64_t>();
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_views_device(views, s->scene, sd, *tile, out_device, hip_stream, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
 int rth_caster_trace(rth_scene_t* s, uint64_t n, const float* o4, const float* d4, uint32_t* tri, float* t, uint32_t* face,
                      rtmi_stats_t* stats) {
     return guarded([&] {

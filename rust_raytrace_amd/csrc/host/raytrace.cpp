@@ -719,6 +719,43 @@ void HipRayCaster::walk_adaptive_device(const Viewport& v, const Scene& s, const
     progress.stats = st;
 }
 
+// The ABI viewports and seeds of a batch of views (empty seeds: the caster's seed for every view)
+static void views_abi(const std::vector<Viewport>& views, const std::vector<uint64_t>& seeds, uint64_t seed,
+                      std::vector<rtmi_viewport_t>& av, std::vector<uint64_t>& as) {
+    if (!seeds.empty() && seeds.size() != views.size()) throw std::runtime_error("walk_views: one seed per view (or none)");
+    av.clear();
+    for (const Viewport& v : views) av.push_back(to_abi(v));
+    as = seeds.empty() ? std::vector<uint64_t>(views.size(), seed) : seeds;
+}
+
+void HipRayCaster::walk_views(const std::vector<Viewport>& views, const Scene& s, const std::vector<uint64_t>& seeds, Color* data,
+                              ProgressCtx& progress) {
+    std::vector<rtmi_viewport_t> av;
+    std::vector<uint64_t> as;
+    views_abi(views, seeds, seed, av, as);
+    rtmi_scene_t* h = resident(s);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_views(h, av.data(), as.data(), (uint32_t)av.size(), reinterpret_cast<float*>(data), &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_views: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
+void HipRayCaster::walk_views_device(const std::vector<Viewport>& views, const Scene& s, const std::vector<uint64_t>& seeds,
+                                     const rtmi_tile_t& tile, void* out_device, void* hip_stream, ProgressCtx& progress) {
+    std::vector<rtmi_viewport_t> av;
+    std::vector<uint64_t> as;
+    views_abi(views, seeds, seed, av, as);
+    rtmi_scene_t* h = resident(s);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_views_device(h, av.data(), as.data(), (uint32_t)av.size(), &tile, out_device, hip_stream, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_views_device: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
 void HipRayCaster::walk_rows(const Viewport& v, const Scene& s, size_t row0, size_t nrows, Color* data, ProgressCtx& progress) {
     rtmi_scene_t* h = resident(s);
     const rtmi_viewport_t av = to_abi(v);

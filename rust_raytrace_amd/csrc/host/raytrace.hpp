@@ -203,6 +203,14 @@ public:
                        uint32_t* counts, ProgressCtx& progress);
     void walk_adaptive_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, rtmi_adaptive_t& ad, void* accum_device,
                               void* sumsq_device, void* counts_device, void* out_device, void* hip_stream, ProgressCtx& progress);
+    // A batch of views of one scene (rtmi_render_views / rtmi_render_views_device): views[k] with seeds[k] is what walk_rows
+    // of that view renders, bit for bit; the views share width, height, maxdepth and samples_per_pixel.  The batch is one
+    // stacked image of views.size() * height rows (row k * height + r = row r of view k): walk_views writes all of it,
+    // walk_views_device the rows of `tile`.  seeds empty: this caster's seed for every view.
+    void walk_views(const std::vector<Viewport>& views, const Scene& s, const std::vector<uint64_t>& seeds, Color* data,
+                    ProgressCtx& progress);
+    void walk_views_device(const std::vector<Viewport>& views, const Scene& s, const std::vector<uint64_t>& seeds,
+                           const rtmi_tile_t& tile, void* out_device, void* hip_stream, ProgressCtx& progress);
     void set_options(uint32_t opts) { options_ = opts; }
     // Per-ray records of the production walk (rtmi_trace_records / rtmi_primary_records, on the first device): explicit
     // rays (n x 4 floats each), or sample `sample` of every pixel of rows [row0, row0 + nrows).  Throws on unsupported scenes.

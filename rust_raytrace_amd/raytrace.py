@@ -534,6 +534,57 @@ class HipRayCaster:
                                                         C.c_void_p(stream_ptr or 0), C.byref(st), C.byref(wall)))
         return self._adaptive_ctx(st, wall, ad)
 
+    def _views(self, views, seeds):
+        """(count, view 0, vp12s, seeds) of a batch of views: vp12s is (count, 12) float32, seeds (count,) uint64.  Raises
+        ValueError on an empty or mismatched batch."""
+        views = list(views)
+        if not views:
+            raise ValueError("views must hold at least one Viewport")
+        v0 = views[0]
+        for k, v in enumerate(views):
+            if (v.width, v.height, v.maxdepth, v.samples_per_pixel) != (v0.width, v0.height, v0.maxdepth, v0.samples_per_pixel):
+                raise ValueError(f"view {k}: width, height, maxdepth and samples_per_pixel must equal view 0's")
+        seeds = [self.seed] * len(views) if seeds is None else [int(x) for x in seeds]
+        if len(seeds) != len(views):
+            raise ValueError("seeds must hold one seed per view")
+        vp12s = np.ascontiguousarray(np.stack([np.asarray(v.vp12, np.float32).reshape(12) for v in views]))
+        return len(views), v0, vp12s, np.asarray(seeds, np.uint64)
+
+    def walk_rays_views(self, views, s, data=None, seeds=None):
+        """A batch of views of one scene in one call (rtmi_render_views): views[k] (a Viewport) with seeds[k] (default
+        self.seed for every view) renders data[k] ((K, H, W, 4) float32; allocated when None, returned as ctx.data), the
+        bits walk_rays of that view and seed would give.  The views share width, height, maxdepth and samples_per_pixel.
+        Returns a ProgressCtx over the whole batch.  Records of views are out of scope: s.debug_en raises."""
+        n, v0, vp12s, sd = self._views(views, seeds)
+        if s.debug_en:
+            raise ValueError("per-ray records (Scene.debug_en) are not available for batches of views")
+        if data is None:
+            data = np.zeros((n, v0.height, v0.width, 4), np.float32)
+        elif data.dtype != np.float32 or not data.flags.c_contiguous or data.shape != (n, v0.height, v0.width, 4):
+            raise ValueError("data must be a C-contiguous float32 array of shape (K, H, W, 4)")
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_views(s.h, n, v0.width, v0.height, _p(vp12s), v0.maxdepth, v0.samples_per_pixel, _p(sd),
+                                              _p(data), C.byref(st), C.byref(wall)))
+        ctx = ProgressCtx(st.rays, wall.value, st.as_dict())
+        ctx.data = data
+        return ctx
+
+    def walk_views_device(self, views, s, tile, out_ptr, stream_ptr=None, seeds=None):
+        """The same on device memory (rtmi_render_views_device): the rows tile = (row0, nrows, stripe_rows, stripe_step) of
+        the stacked image (K * H rows, row k * H + r = row r of view k) into nrows * width float4 at out_ptr, enqueued on
+        HIP stream stream_ptr."""
+        n, v0, vp12s, sd = self._views(views, seeds)
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        t = _ffi.Tile(*[int(x) for x in tile])
+        _chk(_ffi.lib().rth_caster_walk_views_device(s.h, n, v0.width, v0.height, _p(vp12s), v0.maxdepth, v0.samples_per_pixel,
+                                                     _p(sd), C.byref(t), C.c_void_p(out_ptr), C.c_void_p(stream_ptr or 0),
+                                                     C.byref(st), C.byref(wall)))
+        return ProgressCtx(st.rays, wall.value, st.as_dict())
+
     def quantize_device(self, s, rgba_ptr, npixels, rgb_ptr, stream_ptr=None):
         """write_png's `(c * 255.) as u8` on device memory (f32x4 -> u8x3), enqueued on the stream."""
         self._config(s)
