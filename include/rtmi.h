@@ -183,8 +183,8 @@ typedef struct rtmi_tuning {
                                    A tile up to 1/8 larger is still rendered as one batch.                    */
     uint32_t streams;           /* 1..4 internal HIP streams (interleaved sub-tiles of a tile); 0 (default) = automatic:
                                    one stream for tiles of 2^26 paths and more that run the path kernels
-                                   (pipeline 3), three otherwise (linear-list, generic-tree, BVH and sphere
-                                   scenes always get three)                                                   */
+                                   (pipeline 3) and for rtmi_render_features*, three otherwise (renders of
+                                   linear-list, generic-tree, BVH and sphere scenes always get three)        */
     uint32_t subtile_min_paths; /* tiles with fewer paths are not split over streams; default 32768           */
     uint32_t oct_waves_per_cu;  /* persistent waves per CU and launch of the octree kernel; 0 = automatic: what
                                    fits with one stream, at most 16 when several streams share the CUs       */
@@ -250,6 +250,42 @@ int rtmi_render_samples_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, u
                                void* hip_stream, rtmi_stats_t* stats);
 int rtmi_render_samples(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
                         uint32_t sample0, uint32_t nsamples, float* accum_host, float* out_host, rtmi_stats_t* stats);
+
+/* First-hit feature buffers: per-pixel albedo, shading normal, depth, coverage and hit id of the PRIMARY
+ * rays, for denoisers, compositing and picking.  The rays are the renderer's own: samples [sample0, sample0 + nsamples) of
+ * every pixel of the tile, of a frame of S = vp->samples_per_pixel samples, exactly as rtmi_render_samples_device generates
+ * them (RNG keyed by (seed, pixel, sample, block 0); jittered iff S != 1).  vp->maxdepth is not consulted: only the primary
+ * ray is traced, and its closest hit (tri, t, face) is what rtmi_trace returns for it.  Per sample, in f32:
+ *   miss (tri == 0):          a = sky (128, 180, 255)/255,       c = 0,  n = (0, 0, 0),                          d = 0
+ *   edge face (face & 2):     a = (0, 0, 0),                     c = 1,  n = the triangle's norm, * (-1.f) when face & 1,  d = t
+ *   any other hit:            a = the surface's color (Solid, Matte, Reflective alike),  c, n, d as for an edge face
+ * albedo: one float4 per pixel = (mean a.r, mean a.g, mean a.b, mean c: coverage / alpha).
+ * normal: one float4 per pixel = (mean n.x, mean n.y, mean n.z, mean d).  The mean normal is not renormalised, and the mean
+ *         depth of the samples that hit is normal.w / albedo.w where coverage is non-zero: the division is the caller's.
+ * ids:    one uint32 per pixel = tri | face << 30 of sample `sample0` of the pixel (0 = miss): the first-hit id map (with
+ *         S == 1 the centred ray's hit).
+ * "mean" is walk_ray_set's arithmetic (raytrace.rs:1414-1426): acc = 0.f; acc = acc + x in sample order; acc * (1.f /
+ * (float)nsamples).  A non-finite t of a degenerate "hit" (raytrace.rs:402-405) propagates into normal.w; nothing filters it.
+ * Layout: the tile's, as rtmi_render_tile_device (row-major over the tile's rows).  Any of the three pointers may be NULL
+ * (that buffer is not produced), but not all three; no two may alias.
+ * stats: rays = pixels * nsamples, kernel_ms, trace_ms, trace_launches, streams, pipeline = 1, slow_paths = 0 (rays with a
+ * zero component are traced in place, as rtmi_trace does); with RTMI_OPT_COUNTERS the five work counters.
+ * Scenes: octree, generic tree (RTMI_OPT_GENERIC) and linear list; RTMI_OPT_FAST / RTMI_OPT_BVH give those modes' hits.
+ * RTMI_ERR_UNSUPPORTED for a scene with analytic spheres: that primitive is build-defined (rtmi_sphere_t) and its normal
+ * needs the hit point, which this call does not compute.
+ * RTMI_ERR_INVALID, before any HIP call and before the scene is used: a NULL scene, viewport or tile; all three outputs
+ * NULL; aliased outputs; nsamples == 0; sample0 + nsamples > S; every viewport and tile check of
+ * rtmi_render_samples_device.  An empty tile returns RTMI_OK and touches nothing.  stats come back cleared on failure.
+ * The device variant enqueues on hip_stream like rtmi_render_tile_device; the host variant renders rows [row0, row0 + nrows)
+ * and copies the requested buffers out once (16 + 16 + 4 B per pixel).  Batches, streams and sub-tiles apply as for a
+ * progressive pass (automatic streams: one); no tuning changes a bit of the result.
+ * Not here: features of batches of views or of rtmi_render_frame_multi, sums continued across calls. */
+int rtmi_render_features_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile,
+                                uint32_t sample0, uint32_t nsamples, void* albedo_device, void* normal_device,
+                                void* ids_device, void* hip_stream, rtmi_stats_t* stats);
+int rtmi_render_features(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
+                         uint32_t sample0, uint32_t nsamples, float* albedo_host, float* normal_host, uint32_t* ids_host,
+                         rtmi_stats_t* stats);
 
 /* Adaptive sampling: every pixel stops at its own sample count n, between min_samples and
  * vp->samples_per_pixel = S (the maximum, >= 2), and its value is exactly the pixel of a uniform render at spp = n.

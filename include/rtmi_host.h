@@ -87,6 +87,16 @@ int rth_caster_walk_samples(rth_scene_t* s, uint32_t w, uint32_t h, const float*
 int rth_caster_walk_samples_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
                                    const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, void* accum_device,
                                    void* out_device, void* hip_stream, rtmi_stats_t* stats, double* wall_seconds);
+/* First-hit feature buffers (rtmi_render_features / rtmi_render_features_device in rtmi.h): per-pixel means over samples
+ * [sample0, sample0 + nsamples) of the primary rays' (albedo.rgb, coverage) and (normal.xyz, depth), and the hit id of sample
+ * sample0; any of the three buffers may be NULL, not all.  maxdepth is not consulted. */
+int rth_caster_walk_features(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                             uint64_t row0, uint64_t nrows, uint32_t sample0, uint32_t nsamples, float* albedo_host,
+                             float* normal_host, uint32_t* ids_host, rtmi_stats_t* stats, double* wall_seconds);
+int rth_caster_walk_features_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                                    const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, void* albedo_device,
+                                    void* normal_device, void* ids_device, void* hip_stream, rtmi_stats_t* stats,
+                                    double* wall_seconds);
 /* Adaptive sampling (rtmi_render_adaptive / rtmi_render_adaptive_device in rtmi.h): spp is the maximum samples per pixel;
  * ad carries min_samples, pass_samples and the tolerances in and passes, unconverged and samples out.  out receives every
  * pixel at its own count, counts the per-pixel sample counts. */

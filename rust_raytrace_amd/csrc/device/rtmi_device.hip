@@ -684,6 +684,63 @@ __global__ void __launch_bounds__(256) k_accum_list(uint32_t npixels, uint32_t n
                              list, sumsq, counts, n);
 }
 
+// ---------------------------------------------------------------- first-hit feature buffers (rtmi_render_features*)
+// k_features stands where k_shade and k_accum stand in a progressive pass whose only pass is the primary one: it turns the
+// closest hits of the batch's primary rays (queue slot == path, a pixel's paths consecutive: [pixel][sample]) into per-pixel
+// means of (albedo.rgb, coverage) and (normal.xyz, depth), and the hit id of each pixel's first sample.  There is no per-path
+// intermediate in memory: 8 B per path are read, 36 B per pixel written.
+// accum_pixels' scheme with 8 lanes per pixel: a block takes RTMI_FEAT_PIX consecutive pixels and walks their paths in
+// chunks.  Staging: thread k of the chunk reads its path's hit_tf / hit_t (coalesced), gathers the features of that hit
+// (hit_features, shade.hpp: once per path) and writes the 8 floats to LDS.  Summing: thread (pixel j, lane l) adds lane l of
+// its pixel's samples in sample order from 0.f, carrying the sum across chunks: walk_ray_set's sequence of f32 additions.
+// LDS banks: a ds_read_b32 is served per 32-lane half = 4 pixels x 8 lanes, on banks (entry * 8 + l) % 32, so the 4 pixels'
+// entries must differ mod 4.  With nsamples % 4 == 0 they would all be equal (entry = j * nsamples + s); an entry is therefore
+// stored rotated by its pixel inside its aligned group of four entries (which then belong to one pixel): conflict-free for
+// nsamples = 4, 8, 16, 64, ...; other counts are left as they fall (nsamples % 4 == 2: two-way).
+#define RTMI_FEAT_PIX 32
+#define RTMI_FEAT_CHUNK 512  // paths per chunk: 16 KB of LDS
+__device__ inline uint32_t feat_slot(uint32_t k, uint32_t rot) { return (k & ~3u) | ((k + rot) & 3u); }
+// Sub-tile and stripe addressing of the outputs is accum_pixels<Samp::PASS>'s.  albedo / normal (float4 per pixel) and ids
+// (uint32 per pixel) may each be NULL.  dS: n / nsamples.
+__global__ void __launch_bounds__(256) k_features(DScene sc, uint32_t npixels, uint32_t nsamples, const uint32_t* __restrict__ hit_tf,
+                                                  const float* __restrict__ hit_t, float* __restrict__ albedo, float* __restrict__ normal,
+                                                  uint32_t* __restrict__ ids, uint32_t pix0, uint32_t W, uint32_t nsub, uint32_t sub,
+                                                  FastDiv dW, FastDiv dS) {
+    __shared__ float4 stage[2 * RTMI_FEAT_CHUNK];
+    const float* stage_f = reinterpret_cast<const float*>(stage);
+    const uint32_t tid = threadIdx.x, j = tid >> 3, l = tid & 7u;
+    const uint32_t rot = (nsamples & 3u) == 0u ? 1u : 0u;
+    const float inv = 1.f / (float)nsamples;
+    for (uint32_t pb = blockIdx.x * RTMI_FEAT_PIX; pb < npixels; pb += gridDim.x * RTMI_FEAT_PIX) {
+        const uint32_t npb = min((uint32_t)RTMI_FEAT_PIX, npixels - pb);
+        const uint32_t f0 = pb * nsamples, nb = npb * nsamples;  // the block's paths: hit_*[f0 .. f0 + nb)
+        const uint32_t my0 = j * nsamples, my1 = my0 + nsamples;  // this thread's pixel among them (when j < npb)
+        float acc = 0.f;
+        for (uint32_t r0 = 0; r0 < nb; r0 += RTMI_FEAT_CHUNK) {
+            const uint32_t n = min((uint32_t)RTMI_FEAT_CHUNK, nb - r0);
+            __syncthreads();  // the previous chunk has been consumed
+            for (uint32_t k = tid; k < n; k += 256u) {
+                const HitFeat f = hit_features(sc, hit_tf[f0 + r0 + k], hit_t[f0 + r0 + k]);
+                const uint32_t e = feat_slot(k, rot * fdiv(r0 + k, dS));
+                stage[2u * e] = f.a;
+                stage[2u * e + 1u] = f.n;
+            }
+            __syncthreads();
+            if (j < npb) {
+                const uint32_t lo = max(my0, r0), hi = min(my1, r0 + n);
+                for (uint32_t s = lo; s < hi; s++) acc = acc + stage_f[feat_slot(s - r0, rot * j) * 8u + l];
+            }
+        }
+        if (j < npb) {
+            const uint32_t lp = pix0 + pb + j, lr = fdiv(lp, dW), col = lp - lr * W;
+            const size_t o = ((size_t)lr * nsub + sub) * W + col;
+            float* __restrict__ dst = l < 4u ? albedo : normal;
+            if (dst) store_stream(&dst[o * 4u + (l & 3u)], acc * inv);
+            if (ids && l == 0u) store_stream(&ids[o], hit_tf[f0 + my0]);
+        }
+    }
+}
+
 // ---------------------------------------------------------------- adaptive sampling: the stop rule and the next list
 // The stop rule of a pixel with n >= 2 samples, sum s and per-lane sum of squares q (rtmi.h, rtmi_render_adaptive):
 // the worst channel's squared standard error of the mean against (abs_tol + rel_tol * brightest mean)^2.  f32 in this
@@ -1643,14 +1700,17 @@ struct SubTile {
 // An adaptive pass (rtmi_render_adaptive*): the n pixels of `list` (tile-local pixel indices, ascending), each with the same
 // number of samples behind it; sumsq / counts continue beside the call's accum.
 struct ListPass { const uint32_t* list; uint32_t n; float4* sumsq; uint32_t* counts; };
+// The outputs of a features call (rtmi_render_features*): one float4 / float4 / uint32 per pixel of the tile, each may be null
+struct FeatOut { float4* albedo; float4* normal; uint32_t* ids; };
 // One render_tile call: what it renders, and its plan (plan_tile)
 struct TileCall {
     uint64_t seed;
     uint32_t sample0, spp, maxdepth, W;  // spp: samples per pixel of this call
     float4 *accum, *out;
     const ListPass* lp;
+    const FeatOut* fo;  // a features call: the primary pass alone (maxdepth = 1, per-pass pipeline), k_features for k_shade + k_accum
     ViewTab vt;  // VIEWS: the view table (cams == nullptr otherwise)
-    Samp mode;  // LIST with lp, PASS with accum, VIEWS with vt.cams, FRAME otherwise
+    Samp mode;  // LIST with lp, PASS with accum or fo, VIEWS with vt.cams, FRAME otherwise
     bool counting, path_kernels;
     uint32_t nsub;
     uint64_t pix_per_batch, max_npix;  // max_npix: pixels of the largest sub-tile
@@ -1689,7 +1749,7 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
     // path kernels (pipeline 3; 0 = automatic): exact-octree scenes get pass 0 from k_path_primary, which generates, traces and
     // shades the primary rays in one kernel.  Everything else (pipeline 1, linear list, generic tree, BVH mode,
     // analytic spheres) starts with k_gen.  Both then run one closest-hit + one shading launch per bounce pass.
-    c.path_kernels = s->tune.pipeline != 1u && s->octree && !s->root_is_leaf &&
+    c.path_kernels = !c.fo && s->tune.pipeline != 1u && s->octree && !s->root_is_leaf &&
                      !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) && s->d.nspheres == 0;
     // streams = 0 (automatic): one stream for path-kernel tiles of 2^26 paths and more, three otherwise (the per-pass
     // pipelines -- BVH mode: 29.6 ms on three streams, 35.2 on one -- have elementwise kernels to hide).  Since k_shade stopped being
@@ -1700,7 +1760,11 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
     // and no slower at the other tolerances measured.
     const ListPass* lp = c.lp;
     const uint64_t npix_call = lp ? (uint64_t)lp->n : npix;
-    const uint32_t auto_streams = ((c.path_kernels && npix_call * spp >= (1ull << 26)) || (lp && npix_call < npix)) ? 1u : 3u;
+    // features calls (c.fo): one stream at any size.  Their elementwise kernels are 3 % of the call, and on three streams a
+    // sub-tile's k_features waits for wave slots behind the other sub-tiles' persistent k_trace_oct launches (config 3's frame
+    // of 2^28 paths: 108.0 and 111.0 ms on one stream in two jobs, 113.9 and 113.7 on three; 2^25 paths: 16.4 and 16.3 against
+    // 17.5 and 17.3).
+    const uint32_t auto_streams = (c.fo || (c.path_kernels && npix_call * spp >= (1ull << 26)) || (lp && npix_call < npix)) ? 1u : 3u;
     uint32_t nsub = std::min<uint32_t>(s->tune.streams ? s->tune.streams : auto_streams, (uint32_t)RTMI_MAX_STREAMS);
     nsub = (uint32_t)std::min<uint64_t>(nsub, lp ? npix_call : nrows);
     if (npix_call * spp < s->tune.subtile_min_paths) nsub = 1;
@@ -1807,6 +1871,16 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
                            w.qd[0].p, w.qpath[0].p, w.ctrl.p);
     }
     HIPCHK(hipGetLastError());  // a refused launch is reported where it happens, not at the end of the batch
+    if (c.fo) {  // the primary rays' closest hits, then their per-pixel feature means: nothing is shaded, nothing bounces
+        HIPCHK(hipEventRecord(w.pass_ev[0], st));
+        launch_trace(s, w, st, w.qo[0].p, w.qd[0].p, 0, c.counting, w.pass_ev[1]);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_features, ew_grid, ew_block, 0, st, s->d, np, c.spp, w.hit_tf.p, w.hit_t.p, (float*)c.fo->albedo,
+                           (float*)c.fo->normal, c.fo->ids, pix0, c.W, c.nsub, t, make_fastdiv(c.W), make_fastdiv(c.spp));
+        HIPCHK(hipEventRecord(w.ev[1], st));
+        HIPCHK(hipGetLastError());
+        return RTMI_OK;
+    }
     for (uint32_t pass = pass0; pass < c.maxdepth; pass++) {
         const int a = pass & 1, b = a ^ 1;
         HIPCHK(hipEventRecord(w.pass_ev[2 * pass], st));
@@ -1880,18 +1954,20 @@ static int collect_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
 // from the paths of THIS call, npix * nsamples.
 // lp != nullptr (with accum): an adaptive pass over the pixels of lp->list (Samp::LIST), dealt out to the streams in
 // contiguous chunks of the list.  Batches and automatic streams are then sized from lp->n * nsamples.
+// fo != nullptr (no accum, no out_device; the caller passes maxdepth = 1): a features call (rtmi_render_features_device).  Its
+// batches run k_gen_samples, the scene's closest-hit launch and k_features, which writes fo's buffers.
 // views > 0 (no accum): a batch of views (Samp::VIEWS, rtmi_render_views_device); vp is the stacked image (height = views *
 // the views' height) and s->hvcams holds the view table, uploaded here on hip_stream before the internal streams fork.
 static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile, uint32_t sample0,
                        uint32_t nsamples, float4* accum, void* out_device, void* hip_stream, rtmi_stats_t* stats,
-                       const ListPass* lp = nullptr, uint32_t views = 0) {
+                       const ListPass* lp = nullptr, uint32_t views = 0, const FeatOut* fo = nullptr) {
     if (stats) memset(stats, 0, sizeof(*stats));
     if (tile->nrows == 0) return RTMI_OK;
     RTMI_GUARD_BEGIN
     // leftovers of the caller's own HIP calls on this thread (or of failures this library tolerated, e.g. an occupancy
     // query) must not make a launch below look refused: hipGetLastError() reports the last error of ANY runtime call
     (void)hipGetLastError();
-    if (!out_device && !accum) return fail(RTMI_ERR_INVALID, "NULL argument");
+    if (!out_device && !accum && !fo) return fail(RTMI_ERR_INVALID, "NULL argument");
     int rc = check_view(vp, tile);
     if (rc != RTMI_OK) return rc;
     HIPCHK(hipSetDevice(s->device));
@@ -1906,8 +1982,8 @@ static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed
     }
     TileCall c;
     c.seed = seed; c.sample0 = sample0; c.spp = nsamples; c.maxdepth = vp->maxdepth; c.W = vp->width;
-    c.accum = accum; c.out = out; c.lp = lp; c.vt = ViewTab{nullptr, FastDiv{}};
-    c.mode = lp ? Samp::LIST : accum ? Samp::PASS : views ? Samp::VIEWS : Samp::FRAME;
+    c.accum = accum; c.out = out; c.lp = lp; c.fo = fo; c.vt = ViewTab{nullptr, FastDiv{}};
+    c.mode = lp ? Samp::LIST : (accum || fo) ? Samp::PASS : views ? Samp::VIEWS : Samp::FRAME;
     c.counting = (s->options & RTMI_OPT_COUNTERS) != 0;
     rc = plan_tile(s, vp, tile, c);
     if (rc != RTMI_OK) return rc;
@@ -1998,6 +2074,69 @@ int rtmi_render_samples(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t see
     if (rc != RTMI_OK) return rc;
     HIPCHK(hipMemcpy(accum_host, s->acc.p, npix * sizeof(float4), hipMemcpyDeviceToHost));
     if (out_host) HIPCHK(hipMemcpy(out_host, s->tile.p, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+// ---------------------------------------------------------------- first-hit feature buffers
+// Checks of the features entry points that come before any HIP call and before the scene is used (a CPU-only caller reaches
+// them).  RTMI_OK with *empty set: the tile has no rows, nothing to do.  v1 receives the viewport with maxdepth = 1: the
+// caller's maxdepth is not consulted, only the primary ray is traced.
+static int check_features(rtmi_scene_t* s, const rtmi_viewport_t* vp, const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples,
+                          const void* albedo, const void* normal, const void* ids, rtmi_viewport_t& v1, bool* empty) {
+    *empty = false;
+    if (!s || !vp) return fail(RTMI_ERR_INVALID, "NULL argument (scene or viewport)");
+    if (!tile) return fail(RTMI_ERR_INVALID, "NULL argument (tile)");
+    if (!albedo && !normal && !ids) return fail(RTMI_ERR_INVALID, "NULL outputs: at least one of albedo, normal and ids is required");
+    if ((albedo && (albedo == normal || albedo == ids)) || (normal && normal == ids))
+        return fail(RTMI_ERR_INVALID, "outputs must not alias (albedo, normal, ids)");
+    if (vp->samples_per_pixel == 0) return fail(RTMI_ERR_INVALID, "samples_per_pixel must be >= 1");
+    if (nsamples == 0) return fail(RTMI_ERR_INVALID, "nsamples must be >= 1");
+    if ((uint64_t)sample0 + nsamples > vp->samples_per_pixel)
+        return fail(RTMI_ERR_INVALID, "samples [sample0, sample0 + nsamples) outside the frame's samples_per_pixel");
+    if (sample0 & RTMI_KEY_JITTER) return fail(RTMI_ERR_UNSUPPORTED, "sample0 above 2^31");  // DView::sample_key
+    if (tile->nrows == 0) { *empty = true; return RTMI_OK; }
+    v1 = *vp;
+    v1.maxdepth = 1;
+    return check_view(&v1, tile);
+}
+
+int rtmi_render_features_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile,
+                                uint32_t sample0, uint32_t nsamples, void* albedo_device, void* normal_device, void* ids_device,
+                                void* hip_stream, rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    rtmi_viewport_t v1;
+    bool empty;
+    const int rc = check_features(s, vp, tile, sample0, nsamples, albedo_device, normal_device, ids_device, v1, &empty);
+    if (rc != RTMI_OK || empty) return rc;
+    if (s->d.nspheres)
+        return fail(RTMI_ERR_UNSUPPORTED, "features: the scene has analytic spheres (a build-defined primitive whose normal needs the hit point)");
+    const FeatOut fo{(float4*)albedo_device, (float4*)normal_device, (uint32_t*)ids_device};
+    return render_tile(s, &v1, seed, tile, sample0, nsamples, nullptr, nullptr, hip_stream, stats, nullptr, 0, &fo);
+}
+
+// Host variant: the requested buffers are rendered into the handle's own device buffers and copied out once.
+int rtmi_render_features(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
+                         uint32_t sample0, uint32_t nsamples, float* albedo_host, float* normal_host, uint32_t* ids_host,
+                         rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    const rtmi_tile_t tile{row0, nrows, nrows ? nrows : 1u, 0u};
+    rtmi_viewport_t v1;
+    bool empty;
+    const int rc0 = check_features(s, vp, &tile, sample0, nsamples, albedo_host, normal_host, ids_host, v1, &empty);
+    if (rc0 != RTMI_OK || empty) return rc0;
+    if (s->d.nspheres)
+        return fail(RTMI_ERR_UNSUPPORTED, "features: the scene has analytic spheres (a build-defined primitive whose normal needs the hit point)");
+    const uint64_t npix = (uint64_t)nrows * vp->width;
+    HIPCHK(hipSetDevice(s->device));
+    if (albedo_host) HIPCHK(s->tile.ensure(npix));
+    if (normal_host) HIPCHK(s->acc.ensure(npix));
+    if (ids_host) HIPCHK(s->acnt.ensure(npix));
+    const FeatOut fo{albedo_host ? s->tile.p : nullptr, normal_host ? s->acc.p : nullptr, ids_host ? s->acnt.p : nullptr};
+    const int rc = render_tile(s, &v1, seed, &tile, sample0, nsamples, nullptr, nullptr, nullptr, stats, nullptr, 0, &fo);
+    if (rc != RTMI_OK) return rc;
+    if (albedo_host) HIPCHK(hipMemcpy(albedo_host, fo.albedo, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    if (normal_host) HIPCHK(hipMemcpy(normal_host, fo.normal, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    if (ids_host) HIPCHK(hipMemcpy(ids_host, fo.ids, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
 

@@ -204,4 +204,31 @@ __device__ inline bool shade_hit(const DScene& sc, uint32_t maxdepth, uint64_t s
     return false;
 }
 
+// First-hit features of ONE traced primary ray (k_features, rtmi_render_features*): tf = hit triangle | face << 30 (0 = miss),
+// t = hit time.  a = (albedo.rgb, coverage), n = (shading normal.xyz, depth).  The gather and the face rules are shade_hit's,
+// restated so that shade_hit compiles to the code it had: a miss is the sky with no coverage, no normal and no depth; an edge
+// face is Solid black (raytrace.rs:452-457); any other hit shows its surface's colour, whatever its kind; the normal of a hit
+// is the triangle's, * (-1.f) on a back face (raytrace.rs:441-449).  Triangles only: the caller refuses analytic spheres.
+struct HitFeat { float4 a, n; };
+__device__ inline HitFeat hit_features(const DScene& sc, uint32_t tf, float t) {
+    const uint32_t tri = tf & 0x3FFFFFFFu, face = tf >> 30;
+    const bool hit = tri != 0u;
+    float4 p1 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (hit) p1 = sc.tplane[2 * tri + 1];
+    float4 m0 = make_float4(0.f / 255.f, 0.f / 255.f, 0.f / 255.f, 0.f);  // an edge face's colour
+    if (hit && !(face & 2u)) m0 = sc.mats[2 * __float_as_uint(p1.w)];
+    V4 norm = mk(p1.x, p1.y, p1.z);
+    if (face & 1u) norm = vmul(norm, -1.f);
+    HitFeat f;
+    f.a.x = hit ? m0.x : 128.f / 255.f;  // the sky, raytrace.rs:1264
+    f.a.y = hit ? m0.y : 180.f / 255.f;
+    f.a.z = hit ? m0.z : 255.f / 255.f;
+    f.a.w = hit ? 1.f : 0.f;
+    f.n.x = hit ? norm.x : 0.f;
+    f.n.y = hit ? norm.y : 0.f;
+    f.n.z = hit ? norm.z : 0.f;
+    f.n.w = hit ? t : 0.f;
+    return f;
+}
+
 }  // namespace rtmi

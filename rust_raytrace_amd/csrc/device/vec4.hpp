@@ -60,9 +60,11 @@ __device__ inline void store_stream(float4* p, float4 v) {
     __builtin_nontemporal_store(x, reinterpret_cast<v4f*>(p));
 }
 __device__ inline void store_stream(uint32_t* p, uint32_t v) { __builtin_nontemporal_store(v, p); }
+__device__ inline void store_stream(float* p, float v) { __builtin_nontemporal_store(v, p); }
 #else  // host pass of the same translation unit: never executed
 __device__ inline void store_stream(float4* p, float4 v) { *p = v; }
 __device__ inline void store_stream(uint32_t* p, uint32_t v) { *p = v; }
+__device__ inline void store_stream(float* p, float v) { *p = v; }
 #endif
 
 }  // namespace rtmi

@@ -261,6 +261,32 @@ int rth_caster_walk_samples_device(rth_scene_t* s, uint32_t w, uint32_t h, const
         if (stats) *stats = ctx.stats;
     });
 }
+int rth_caster_walk_features(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                             uint64_t row0, uint64_t nrows, uint32_t sample0, uint32_t nsamples, float* albedo_host,
+                             float* normal_host, uint32_t* ids_host, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_rays_features(v, s->scene, (size_t)row0, (size_t)nrows, sample0, nsamples, reinterpret_cast<Color*>(albedo_host),
+                                        reinterpret_cast<Color*>(normal_host), ids_host, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
+int rth_caster_walk_features_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                                    const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, void* albedo_device,
+                                    void* normal_device, void* ids_device, void* hip_stream, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!tile) throw std::runtime_error("NULL tile");
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_features_device(v, s->scene, *tile, sample0, nsamples, albedo_device, normal_device, ids_device, hip_stream, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
 int rth_caster_walk_adaptive(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
                              uint64_t row0, uint64_t nrows, rtmi_adaptive_t* ad, float* out_host, uint32_t* counts_host,
                              rtmi_stats_t* stats, double* wall) {

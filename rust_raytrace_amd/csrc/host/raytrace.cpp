@@ -693,6 +693,33 @@ void HipRayCaster::walk_samples_device(const Viewport& v, const Scene& s, const 
     progress.stats = st;
 }
 
+void HipRayCaster::walk_rays_features(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
+                                      Color* albedo, Color* normal, uint32_t* ids, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_features(h, &av, seed, (uint32_t)row0, (uint32_t)nrows, sample0, nsamples,
+                                        reinterpret_cast<float*>(albedo), reinterpret_cast<float*>(normal), ids, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_features: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
+void HipRayCaster::walk_features_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0,
+                                        uint32_t nsamples, void* albedo_device, void* normal_device, void* ids_device,
+                                        void* hip_stream, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_features_device(h, &av, seed, &tile, sample0, nsamples, albedo_device, normal_device, ids_device,
+                                               hip_stream, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_features_device: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
 void HipRayCaster::walk_adaptive(const Viewport& v, const Scene& s, size_t row0, size_t nrows, rtmi_adaptive_t& ad, Color* out,
                                  uint32_t* counts, ProgressCtx& progress) {
     rtmi_scene_t* h = resident(s);

@@ -197,6 +197,13 @@ public:
                       Color* accum, Color* out, ProgressCtx& progress);
     void walk_samples_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
                              void* accum_device, void* out_device, void* hip_stream, ProgressCtx& progress);
+    // First-hit feature buffers (rtmi_render_features / rtmi_render_features_device): per-pixel means over samples [sample0,
+    // sample0 + nsamples) of the primary rays' (albedo.rgb, coverage) and (normal.xyz, depth), one Color each, and the hit id
+    // (tri | face << 30) of each pixel's sample `sample0`.  Any of the three buffers may be null, not all; v.maxdepth is unused.
+    void walk_rays_features(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
+                            Color* albedo, Color* normal, uint32_t* ids, ProgressCtx& progress);
+    void walk_features_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
+                              void* albedo_device, void* normal_device, void* ids_device, void* hip_stream, ProgressCtx& progress);
     // Adaptive sampling (rtmi_render_adaptive / rtmi_render_adaptive_device): every pixel stops at its own count between
     // ad.min_samples and v.samples_per_pixel and equals the pixel of walk_rows at that many samples; counts receives them.
     void walk_adaptive(const Viewport& v, const Scene& s, size_t row0, size_t nrows, rtmi_adaptive_t& ad, Color* out,

@@ -585,6 +585,63 @@ class HipRayCaster:
                                                      C.byref(st), C.byref(wall)))
         return ProgressCtx(st.rays, wall.value, st.as_dict())
 
+    @staticmethod
+    def _feature_samples(v, sample0, nsamples):
+        spp, k0 = int(v.samples_per_pixel), int(sample0)
+        n = spp - k0 if nsamples is None else int(nsamples)
+        if n < 1:
+            raise ValueError("nsamples must be >= 1")
+        if k0 < 0 or k0 + n > spp:
+            raise ValueError("samples [sample0, sample0 + nsamples) must lie inside the frame's samples_per_pixel")
+        return k0, n
+
+    def walk_rays_features(self, v, s, sample0=0, nsamples=None, albedo=None, normal=None, ids=None):
+        """First-hit feature buffers of the whole frame (rtmi_render_features): the means over samples [sample0, sample0 +
+        nsamples) (default: all from sample0) of the PRIMARY rays' (albedo.rgb, coverage) -> albedo and (normal.xyz, depth)
+        -> normal, both (H, W, 4) float32, and ids (H, W) uint32 = tri | face << 30 of every pixel's sample `sample0` (0 = a
+        miss).  The rays are walk_rays' own (same seed, same jitter); v.maxdepth is not used.  The mean normal is not
+        renormalised; the mean depth of the samples that hit is normal[..., 3] / albedo[..., 3] where coverage is non-zero.
+        Each buffer: None allocates it, False leaves it out (not all three), an array is filled in place.
+        Returns (albedo, normal, ids, ctx), None for a buffer left out."""
+        k0, n = self._feature_samples(v, sample0, nsamples)
+        bufs = []
+        for name, a, shape, dt in (("albedo", albedo, (v.height, v.width, 4), np.float32), ("normal", normal, (v.height, v.width, 4), np.float32),
+                                   ("ids", ids, (v.height, v.width), np.uint32)):
+            if a is None:
+                a = np.zeros(shape, dt)
+            elif a is False:
+                a = None
+            elif not isinstance(a, np.ndarray) or a.dtype != dt or not a.flags.c_contiguous or a.shape != shape:
+                raise ValueError(f"{name} must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
+            bufs.append(a)
+        if all(a is None for a in bufs):
+            raise ValueError("at least one of albedo, normal and ids must be produced")
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_features(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, 0, v.height, k0, n,
+                                                 *[_p(a) if a is not None else None for a in bufs], C.byref(st), C.byref(wall)))
+        return bufs[0], bufs[1], bufs[2], ProgressCtx(st.rays, wall.value, st.as_dict())
+
+    def walk_features_device(self, v, s, tile, albedo_ptr, normal_ptr, ids_ptr, sample0=0, nsamples=None, stream_ptr=None):
+        """The same on device memory (rtmi_render_features_device) for a striped row set tile = (row0, nrows, stripe_rows,
+        stripe_step), enqueued on HIP stream `stream_ptr`: albedo / normal are nrows*width float4, ids nrows*width uint32; a
+        pointer of None/0 leaves that buffer out (not all three).  No host copies."""
+        k0, n = self._feature_samples(v, sample0, nsamples)
+        ptrs = [int(p or 0) for p in (albedo_ptr, normal_ptr, ids_ptr)]
+        if not any(ptrs):
+            raise ValueError("at least one of albedo_ptr, normal_ptr and ids_ptr must be given")
+        if len({p for p in ptrs if p}) != sum(1 for p in ptrs if p):
+            raise ValueError("albedo_ptr, normal_ptr and ids_ptr must be different buffers")
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        t = _ffi.Tile(*[int(x) for x in tile])
+        _chk(_ffi.lib().rth_caster_walk_features_device(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel,
+                                                        C.byref(t), k0, n, C.c_void_p(ptrs[0]), C.c_void_p(ptrs[1]), C.c_void_p(ptrs[2]),
+                                                        C.c_void_p(stream_ptr or 0), C.byref(st), C.byref(wall)))
+        return ProgressCtx(st.rays, wall.value, st.as_dict())
+
     def quantize_device(self, s, rgba_ptr, npixels, rgb_ptr, stream_ptr=None):
         """write_png's `(c * 255.) as u8` on device memory (f32x4 -> u8x3), enqueued on the stream."""
         self._config(s)
