@@ -287,6 +287,62 @@ int rtmi_render_features(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_
                          uint32_t sample0, uint32_t nsamples, float* albedo_host, float* normal_host, uint32_t* ids_host,
                          rtmi_stats_t* stats);
 
+/* Feature-guided a-trous denoiser for low-sample frames: an edge-avoiding wavelet filter (Dammertz et al.
+ * 2010) guided by the buffers of rtmi_render_features*.  NOT part of the reference, which has no denoiser: build-defined like
+ * the analytic sphere, so what follows IS the definition, and the tests pin it bit for bit.  Only + - * / and comparisons in
+ * f32, no contraction, no exp (neither the device's nor a host library's is correctly rounded).
+ * Edge-stopping function (Tukey's biweight): g(x2, s2) = (x2 < s2) ? (1 - x2/s2)^2 : 0.  A NaN argument gives 0 (the
+ * comparison is false); s2 = +inf gives exactly 1 for finite x2, so a term is switched off by passing +inf for its sigma.
+ * Inputs: whole width x height row-major images (not striped tiles), one float4 per pixel:
+ *   color   rgb, lane 3 ignored:          what rtmi_render_device writes
+ *   albedo  a = rgb, cov = lane 3:        rtmi_render_features_device's albedo buffer  } of a features call with tile
+ *   normal  n = xyz, d = lane 3 (depth):  rtmi_render_features_device's normal buffer  } {0, height, height, 0}
+ *   out     rgb, lane 3 = 0; must not be one of the inputs.
+ * Start value: u = color.rgb; with RTMI_DENOISE_DEMODULATE u = color.rgb / (albedo.rgb + 1/256) per channel.
+ * Iteration i = 0 .. iterations-1, for every pixel p, with k = {1/16, 1/4, 3/8, 1/4, 1/16}:
+ *   num = (0, 0, 0); den = 0; the taps q = p + 2^i * (dx, dy) are visited with dy outer, dx inner, both from -2 to 2;
+ *   a tap outside the image is skipped;
+ *   the centre tap has w = k[2] * k[2], always;
+ *   when cov_p == 0 && cov_q == 0 (sky beside sky): w = (k[dy+2] * k[dx+2]) * g(|u_p - u_q|^2, sc2_i);
+ *   any other tap: w = k[dy+2] * k[dx+2];  w = w * g(|n_p - n_q|^2, sigma_normal * sigma_normal);
+ *                  w = w * g((d_p - d_q) * (d_p - d_q), (sigma_depth * d_p) * (sigma_depth * d_p));
+ *                  w = w * g((cov_p - cov_q) * (cov_p - cov_q), 0.25);  w = w * g(|a_p - a_q|^2, sigma_albedo * sigma_albedo);
+ *                  w = w * g(|u_p - u_q|^2, sc2_i);
+ *   sc2_i = (sigma_color * sigma_color) * 4^-i (4^-i is exact);  |v|^2 = ((0 + v.x * v.x) + v.y * v.y) + v.z * v.z;
+ *   a tap with w == 0 is not added (a NaN or inf neighbour cannot poison the sums: its g is 0); otherwise, per channel,
+ *   num = num + w * u_q and den = den + w;
+ *   u'_p = num / den.  Every pixel reads this iteration's input u: the filter ping-pongs, it is never in place.
+ * Result: out.rgb = u, with RTMI_DENOISE_DEMODULATE u * (albedo.rgb + 1/256); out.w = 0.
+ * A NaN pixel stays NaN (its own centre tap) and makes no neighbour NaN.
+ * Defaults (rtmi_denoise_defaults): iterations 3, flags 0, sigma_color 1.0, sigma_normal 0.5, sigma_depth 0.1, sigma_albedo
+ * +inf.  Demodulation is a flag and not the default: it raised the error against a converged render on the textureless test
+ * scenes (DESIGN.md 4.12 has the figures). */
+enum { RTMI_DENOISE_DEMODULATE = 1u << 0 };
+typedef struct rtmi_denoise {
+    uint32_t iterations;   /* 1..8; iteration i uses tap spacing 2^i */
+    uint32_t flags;        /* RTMI_DENOISE_DEMODULATE */
+    float sigma_color, sigma_normal, sigma_depth, sigma_albedo;
+} rtmi_denoise_t;
+void rtmi_denoise_defaults(rtmi_denoise_t* params);
+/* rtmi_denoise_device: device images; one kernel launch per iteration is enqueued on hip_stream (like rtmi_quantize_device:
+ * nothing is synchronised).  With more than one iteration the handle keeps one width*height*16 B ping-pong image, grown on
+ * demand (growing it frees the old one, which waits for the device) and freed by rtmi_scene_destroy; no render workspace is
+ * touched.  One denoise call per handle at a time.  rtmi_denoise: host images, copied in, filtered and copied out.
+ * rtmi_render_denoised: rtmi_render_tile_device of the whole frame, rtmi_render_features_device over all
+ * vp->samples_per_pixel samples and the filter, on device images the handle keeps; only the result is copied to out_host.
+ * stats (optional) are the render call's.
+ * RTMI_ERR_INVALID, before any HIP call and before the scene is used: a NULL scene, params or image; out aliasing an input;
+ * width or height 0; iterations 0 or above 8; unknown flag bits; a sigma that is NaN or <= 0 (+inf is valid).
+ * RTMI_ERR_UNSUPPORTED: width * height >= 2^32; rtmi_render_denoised on a scene with analytic spheres (no features).
+ * Not here: temporal accumulation, variance guidance, striped tiles, batches of views, rtmi_render_frame_multi. */
+int rtmi_denoise_device(rtmi_scene_t* scene, uint32_t width, uint32_t height, const void* color_device,
+                        const void* albedo_device, const void* normal_device, const rtmi_denoise_t* params, void* out_device,
+                        void* hip_stream);
+int rtmi_denoise(rtmi_scene_t* scene, uint32_t width, uint32_t height, const float* color_host, const float* albedo_host,
+                 const float* normal_host, const rtmi_denoise_t* params, float* out_host);
+int rtmi_render_denoised(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_denoise_t* params,
+                         float* out_host, rtmi_stats_t* stats);
+
 /* Adaptive sampling: every pixel stops at its own sample count n, between min_samples and
  * vp->samples_per_pixel = S (the maximum, >= 2), and its value is exactly the pixel of a uniform render at spp = n.
  * Pass 0 renders samples [0, m) of every pixel of the tile (m = min_samples, 2 <= m <= S).  After each pass the stop rule

@@ -137,6 +137,16 @@ int rth_caster_walk_frame_multi(rth_scene_t* s, uint32_t w, uint32_t h, const fl
                                 uint32_t stripe_rows, uint32_t flags /* RTMI_FRAME_RGB8 */, void* out_host, void* out_device,
                                 rtmi_stats_t* stats_sum, rtmi_stats_t* per_device, uint32_t per_device_cap, double* wall_seconds);
 int rth_caster_upload(rth_scene_t* s);
+/* The a-trous denoiser (rtmi_denoise / rtmi_denoise_device / rtmi_render_denoised in rtmi.h, which defines the filter) on
+ * whole w x h images of this scene's caster: colour as rth_caster_walk_rows writes it, albedo and normal as
+ * rth_caster_walk_features does.  rth_caster_walk_denoised renders the frame, takes the features of all its samples and
+ * filters on the device; only the result is copied to out_host. */
+int rth_caster_denoise(rth_scene_t* s, uint32_t w, uint32_t h, const float* color_host, const float* albedo_host,
+                       const float* normal_host, const rtmi_denoise_t* params, float* out_host);
+int rth_caster_denoise_device(rth_scene_t* s, uint32_t w, uint32_t h, const void* color_device, const void* albedo_device,
+                              const void* normal_device, const rtmi_denoise_t* params, void* out_device, void* hip_stream);
+int rth_caster_walk_denoised(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                             const rtmi_denoise_t* params, float* out_host, rtmi_stats_t* stats, double* wall_seconds);
 /* Launch tuning for this scene's caster: fields that are 0 keep the library default, xcd_aware is passed as value + 1;
  * NULL restores all defaults.  Never changes a pixel. */
 int rth_caster_set_tuning(rth_scene_t* s, const rtmi_tuning_t* tuning);

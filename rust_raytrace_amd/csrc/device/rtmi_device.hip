@@ -46,6 +46,7 @@ static_assert(sizeof(rtmi_stats_t) == 128 && sizeof(rtmi_tuning_t) == 48 && size
               sizeof(rtmi_triangle_t) == 104 && sizeof(rtmi_viewport_t) == 64 && sizeof(rtmi_sphere_t) == 40 &&
               sizeof(rtmi_ray_record_t) == 72, "ABI struct layout changed");
 static_assert(sizeof(rtmi_adaptive_t) == 32 && offsetof(rtmi_adaptive_t, samples) == 24, "ABI struct layout changed");
+static_assert(sizeof(rtmi_denoise_t) == 24 && offsetof(rtmi_denoise_t, sigma_color) == 8, "ABI struct layout changed");
 
 namespace rtmi {
 
@@ -373,6 +374,7 @@ __global__ void __launch_bounds__(256) k_trace(DScene sc, const float4* __restri
 #include "shade.hpp"
 #include "trace_oct.hpp"
 #include "bvh_fast.hpp"
+#include "denoise.hpp"
 namespace rtmi {
 
 
@@ -1020,6 +1022,10 @@ struct rtmi_scene {
     std::vector<VCam> hvcams;
     hipEvent_t vcams_ev = nullptr;
     DevBuf<uint8_t> qbytes;
+    // rtmi_denoise*: the ping-pong image of calls of more than one iteration (grows only), and the four images (colour,
+    // albedo, normal, result) of the host variants.  No render call reads or writes them.
+    DevBuf<float4> dn_scratch, dn_host;
+    uint32_t dn_lds_max_step = DN_LDS_MAX_STEP;  // tap spacings up to this one stage through LDS (RTMI_DENOISE_LDS_STEP=0|1|2)
     DevBuf<uint8_t> mstage, mframe;  // rtmi_render_frame_multi, root scene: received bands / the frame
     hipStream_t mstream = nullptr;   // rtmi_render_frame_multi: this scene's band stream
     std::vector<ncclComm_t> comms;   // root scene, RTMI_FRAME_RCCL: one communicator per scene of the last device list
@@ -1366,6 +1372,7 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
     s->tune.slow_path_off = (uint32_t)std::min<size_t>(env_size("RTMI_SLOW_PATH_OFF", 0), 1);
     s->verbose = getenv("RTMI_VERBOSE") != nullptr;
     if (const char* v = getenv("RTMI_PACKET_CULL")) s->packet_cull = strcmp(v, "0") != 0;  // (env_size treats 0 as unset)
+    if (const char* v = getenv("RTMI_DENOISE_LDS_STEP")) s->dn_lds_max_step = std::min<uint32_t>((uint32_t)strtoul(v, nullptr, 10), DN_LDS_MAX_STEP);
     if (const char* v = getenv("RTMI_MIRROR_INPLACE")) {
         char* end = nullptr;
         const unsigned long n = strtoul(v, &end, 10);
@@ -1455,7 +1462,7 @@ int rtmi_scene_destroy(rtmi_scene_t* s) {
     s->rec_cnt.release(); s->rec_ids.release(); s->rec_first.release();
     s->tile.release(); s->acc.release(); s->asq.release(); s->acnt.release();
     s->alist[0].release(); s->alist[1].release(); s->ablk.release(); s->qbytes.release(); s->mstage.release(); s->mframe.release();
-    s->vcams.release();
+    s->vcams.release(); s->dn_scratch.release(); s->dn_host.release();
     if (s->vcams_ev) (void)hipEventDestroy(s->vcams_ev);
     if (s->mstream) (void)hipStreamDestroy(s->mstream);
     if (!s->comms.empty()) { if (Rccl* r = rccl_api()) for (ncclComm_t c : s->comms) (void)r->CommDestroy(c); }
@@ -2955,6 +2962,121 @@ int rtmi_builder_filter(rtmi_builder_t* b, const rtmi_build_box_t* boxes, uint64
                        b->cand.p, b->keep.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(keep, b->keep.p, nkeep, hipMemcpyDeviceToHost));
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+// ---------------------------------------------------------------- the a-trous denoiser (denoise.hpp)
+void rtmi_denoise_defaults(rtmi_denoise_t* p) {
+    if (!p) return;
+    p->iterations = 3; p->flags = 0;
+    p->sigma_color = 1.0f; p->sigma_normal = 0.5f; p->sigma_depth = 0.1f; p->sigma_albedo = INFINITY;
+}
+
+// Checks of the denoise entry points that come before any HIP call and before the scene is used (a CPU-only caller reaches
+// them).  bufs: colour, albedo, normal, output.
+static int check_denoise(const rtmi_scene_t* s, uint32_t width, uint32_t height, const void* const* bufs, const rtmi_denoise_t* p) {
+    if (!s) return fail(RTMI_ERR_INVALID, "denoise: NULL argument (scene)");
+    if (!p) return fail(RTMI_ERR_INVALID, "denoise: NULL argument (params)");
+    static const char* const names[4] = {"color", "albedo", "normal", "out"};
+    for (int k = 0; k < 4; k++)
+        if (!bufs[k]) return fail(RTMI_ERR_INVALID, std::string("denoise: NULL argument (") + names[k] + ")");
+    for (int k = 0; k < 3; k++)
+        if (bufs[k] == bufs[3]) return fail(RTMI_ERR_INVALID, std::string("denoise: out must not alias ") + names[k] + " (the filter is never in place)");
+    if (width == 0 || height == 0) return fail(RTMI_ERR_INVALID, "denoise: empty image (width or height is 0)");
+    if ((uint64_t)width * height >= (1ull << 32)) return fail(RTMI_ERR_UNSUPPORTED, "denoise: more than 2^32 pixels");
+    if (p->iterations == 0 || p->iterations > 8) return fail(RTMI_ERR_INVALID, "denoise: iterations must be 1..8");
+    if (p->flags & ~(uint32_t)RTMI_DENOISE_DEMODULATE) return fail(RTMI_ERR_INVALID, "denoise: unknown flags");
+    const float sg[4] = {p->sigma_color, p->sigma_normal, p->sigma_depth, p->sigma_albedo};
+    static const char* const sn[4] = {"sigma_color", "sigma_normal", "sigma_depth", "sigma_albedo"};
+    for (int k = 0; k < 4; k++)
+        if (!(sg[k] > 0.f)) return fail(RTMI_ERR_INVALID, std::string("denoise: ") + sn[k] + " must be > 0 (+inf switches the term off)");
+    return RTMI_OK;
+}
+
+// The launches of one call, on `st`: iteration i reads what iteration i - 1 wrote (the first: color) and the last writes out,
+// so out and the handle's scratch image alternate backwards from out.  The caller has checked the arguments.
+static int enqueue_denoise(rtmi_scene* s, uint32_t W, uint32_t H, const float4* color, const float4* albedo, const float4* normal,
+                           const rtmi_denoise_t& p, float4* out, hipStream_t st) {
+    (void)hipGetLastError();
+    const uint32_t n = p.iterations;
+    if (n > 1) HIPCHK(s->dn_scratch.ensure((size_t)W * H));
+    const bool demod = (p.flags & RTMI_DENOISE_DEMODULATE) != 0;
+    const uint32_t ntiles = ((W + DN_TW - 1) / DN_TW) * ((H + DN_TH - 1) / DN_TH);
+    const dim3 grid(std::min<uint32_t>(ntiles, 1u << 20)), block(DN_TW * DN_TH);
+    const float s2c = p.sigma_color * p.sigma_color;
+    float scale = 1.f;  // 4^-i, exact
+    const float4* src = color;
+    for (uint32_t i = 0; i < n; i++, scale = scale * 0.25f) {
+        float4* dst = ((n - 1 - i) & 1u) ? s->dn_scratch.p : out;
+        const uint32_t step = 1u << i;
+        const DenoiseK k{p.sigma_normal * p.sigma_normal, p.sigma_depth, p.sigma_albedo * p.sigma_albedo, s2c * scale};
+        const uint32_t fl = (demod && i == 0 ? DN_DEMOD_IN : 0u) | (demod && i == n - 1 ? DN_REMOD_OUT : 0u);
+        if (step <= s->dn_lds_max_step) {
+            const size_t lds = (size_t)(DN_TW + 4 * step) * (DN_TH + 4 * step) * 3 * sizeof(float4);
+            hipLaunchKernelGGL(k_atrous<true>, grid, block, lds, st, W, H, step, src, albedo, normal, dst, k, fl);
+        } else {
+            hipLaunchKernelGGL(k_atrous<false>, grid, block, 0, st, W, H, step, src, albedo, normal, dst, k, fl);
+        }
+        HIPCHK(hipGetLastError());
+        src = dst;
+    }
+    return RTMI_OK;
+}
+
+int rtmi_denoise_device(rtmi_scene_t* s, uint32_t width, uint32_t height, const void* color_device, const void* albedo_device,
+                        const void* normal_device, const rtmi_denoise_t* params, void* out_device, void* hip_stream) {
+    RTMI_GUARD_BEGIN
+    const void* const bufs[4] = {color_device, albedo_device, normal_device, out_device};
+    const int rc = check_denoise(s, width, height, bufs, params);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    return enqueue_denoise(s, width, height, (const float4*)color_device, (const float4*)albedo_device, (const float4*)normal_device,
+                           *params, (float4*)out_device, (hipStream_t)hip_stream);
+    RTMI_GUARD_END
+}
+
+// Host variant: the three images are copied into the handle's own buffers, filtered there and the result is copied out.
+int rtmi_denoise(rtmi_scene_t* s, uint32_t width, uint32_t height, const float* color_host, const float* albedo_host,
+                 const float* normal_host, const rtmi_denoise_t* params, float* out_host) {
+    RTMI_GUARD_BEGIN
+    const void* const bufs[4] = {color_host, albedo_host, normal_host, out_host};
+    const int rc0 = check_denoise(s, width, height, bufs, params);
+    if (rc0 != RTMI_OK) return rc0;
+    const size_t npix = (size_t)width * height;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(s->dn_host.ensure(4 * npix));
+    float4* d = s->dn_host.p;
+    for (int k = 0; k < 3; k++) HIPCHK(hipMemcpy(d + k * npix, bufs[k], npix * sizeof(float4), hipMemcpyHostToDevice));
+    const int rc = enqueue_denoise(s, width, height, d, d + npix, d + 2 * npix, *params, d + 3 * npix, nullptr);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(hipMemcpy(out_host, d + 3 * npix, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+// Render, features over all samples and the filter, all on the handle's own device images; only the result crosses to the host.
+int rtmi_render_denoised(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_denoise_t* params, float* out_host,
+                         rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    RTMI_GUARD_BEGIN
+    if (!vp) return fail(RTMI_ERR_INVALID, "denoise: NULL argument (viewport)");
+    static const char own[3] = {};  // stand for the handle's images in the checks: they exist and do not alias
+    const void* const bufs[4] = {own, own + 1, own + 2, out_host};
+    const int rc0 = check_denoise(s, vp->width, vp->height, bufs, params);
+    if (rc0 != RTMI_OK) return rc0;
+    const size_t npix = (size_t)vp->width * vp->height;
+    const rtmi_tile_t tile{0u, vp->height, vp->height, 0u};
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(s->dn_host.ensure(4 * npix));
+    float4* d = s->dn_host.p;
+    int rc = rtmi_render_tile_device(s, vp, seed, &tile, d, nullptr, stats);
+    if (rc != RTMI_OK) return rc;
+    rc = rtmi_render_features_device(s, vp, seed, &tile, 0u, vp->samples_per_pixel, d + npix, d + 2 * npix, nullptr, nullptr, nullptr);
+    if (rc != RTMI_OK) { if (stats) memset(stats, 0, sizeof(*stats)); return rc; }
+    rc = enqueue_denoise(s, vp->width, vp->height, d, d + npix, d + 2 * npix, *params, d + 3 * npix, nullptr);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(hipMemcpy(out_host, d + 3 * npix, npix * sizeof(float4), hipMemcpyDeviceToHost));
     return RTMI_OK;
     RTMI_GUARD_END
 }

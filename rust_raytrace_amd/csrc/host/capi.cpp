@@ -287,6 +287,33 @@ int rth_caster_walk_features_device(rth_scene_t* s, uint32_t w, uint32_t h, cons
         if (stats) *stats = ctx.stats;
     });
 }
+int rth_caster_denoise(rth_scene_t* s, uint32_t w, uint32_t h, const float* color_host, const float* albedo_host,
+                       const float* normal_host, const rtmi_denoise_t* params, float* out_host) {
+    return guarded([&] {
+        if (!params) throw std::runtime_error("NULL rtmi_denoise_t");
+        caster_of(s).denoise(s->scene, w, h, reinterpret_cast<const Color*>(color_host), reinterpret_cast<const Color*>(albedo_host),
+                             reinterpret_cast<const Color*>(normal_host), *params, reinterpret_cast<Color*>(out_host));
+    });
+}
+int rth_caster_denoise_device(rth_scene_t* s, uint32_t w, uint32_t h, const void* color_device, const void* albedo_device,
+                              const void* normal_device, const rtmi_denoise_t* params, void* out_device, void* hip_stream) {
+    return guarded([&] {
+        if (!params) throw std::runtime_error("NULL rtmi_denoise_t");
+        caster_of(s).denoise_device(s->scene, w, h, color_device, albedo_device, normal_device, *params, out_device, hip_stream);
+    });
+}
+int rth_caster_walk_denoised(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                             const rtmi_denoise_t* params, float* out_host, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!params) throw std::runtime_error("NULL rtmi_denoise_t");
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_rays_denoised(v, s->scene, *params, reinterpret_cast<Color*>(out_host), ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
 int rth_caster_walk_adaptive(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
                              uint64_t row0, uint64_t nrows, rtmi_adaptive_t* ad, float* out_host, uint32_t* counts_host,
                              rtmi_stats_t* stats, double* wall) {

@@ -720,6 +720,34 @@ void HipRayCaster::walk_features_device(const Viewport& v, const Scene& s, const
     progress.stats = st;
 }
 
+void HipRayCaster::denoise(const Scene& s, uint32_t width, uint32_t height, const Color* color, const Color* albedo,
+                           const Color* normal, const rtmi_denoise_t& params, Color* out) {
+    rtmi_scene_t* h = resident(s);
+    const int rc = rtmi_denoise(h, width, height, reinterpret_cast<const float*>(color), reinterpret_cast<const float*>(albedo),
+                                reinterpret_cast<const float*>(normal), &params, reinterpret_cast<float*>(out));
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_denoise: ") + rtmi_last_error());
+}
+
+void HipRayCaster::denoise_device(const Scene& s, uint32_t width, uint32_t height, const void* color_device,
+                                  const void* albedo_device, const void* normal_device, const rtmi_denoise_t& params,
+                                  void* out_device, void* hip_stream) {
+    rtmi_scene_t* h = resident(s);
+    const int rc = rtmi_denoise_device(h, width, height, color_device, albedo_device, normal_device, &params, out_device, hip_stream);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_denoise_device: ") + rtmi_last_error());
+}
+
+void HipRayCaster::walk_rays_denoised(const Viewport& v, const Scene& s, const rtmi_denoise_t& params, Color* out,
+                                      ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_denoised(h, &av, seed, &params, reinterpret_cast<float*>(out), &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_denoised: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
 void HipRayCaster::walk_adaptive(const Viewport& v, const Scene& s, size_t row0, size_t nrows, rtmi_adaptive_t& ad, Color* out,
                                  uint32_t* counts, ProgressCtx& progress) {
     rtmi_scene_t* h = resident(s);

@@ -204,6 +204,14 @@ public:
                             Color* albedo, Color* normal, uint32_t* ids, ProgressCtx& progress);
     void walk_features_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
                               void* albedo_device, void* normal_device, void* ids_device, void* hip_stream, ProgressCtx& progress);
+    // The a-trous denoiser (rtmi_denoise / rtmi_denoise_device / rtmi_render_denoised): whole width x height images, colour
+    // as walk_rows writes it, albedo and normal as walk_rays_features does; out may not be one of the inputs.
+    void denoise(const Scene& s, uint32_t width, uint32_t height, const Color* color, const Color* albedo, const Color* normal,
+                 const rtmi_denoise_t& params, Color* out);
+    void denoise_device(const Scene& s, uint32_t width, uint32_t height, const void* color_device, const void* albedo_device,
+                        const void* normal_device, const rtmi_denoise_t& params, void* out_device, void* hip_stream);
+    // walk_rows of the whole frame, the features of all its samples and the filter, on the device; out receives the result
+    void walk_rays_denoised(const Viewport& v, const Scene& s, const rtmi_denoise_t& params, Color* out, ProgressCtx& progress);
     // Adaptive sampling (rtmi_render_adaptive / rtmi_render_adaptive_device): every pixel stops at its own count between
     // ad.min_samples and v.samples_per_pixel and equals the pixel of walk_rows at that many samples; counts receives them.
     void walk_adaptive(const Viewport& v, const Scene& s, size_t row0, size_t nrows, rtmi_adaptive_t& ad, Color* out,

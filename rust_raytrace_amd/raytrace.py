@@ -300,8 +300,10 @@ class HipRayCaster:
         self.devices = [int(d) for d in devices] if devices else None
         if self.devices:
             self.device = self.devices[0]
+        self._scene = None
 
     def _config(self, s):
+        self._scene = s  # denoise() / denoise_device() without a scene use the last one this caster worked on
         _chk(_ffi.lib().rth_caster_config(s.h, self.seed, self.device, self.options))
         devs = self.devices or [self.device]
         arr = (C.c_int32 * len(devs))(*devs)
@@ -640,6 +642,88 @@ class HipRayCaster:
         _chk(_ffi.lib().rth_caster_walk_features_device(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel,
                                                         C.byref(t), k0, n, C.c_void_p(ptrs[0]), C.c_void_p(ptrs[1]), C.c_void_p(ptrs[2]),
                                                         C.c_void_p(stream_ptr or 0), C.byref(st), C.byref(wall)))
+        return ProgressCtx(st.rays, wall.value, st.as_dict())
+
+    DENOISE_DEMODULATE = 1
+
+    @staticmethod
+    def denoise_params(iterations=None, demodulate=None, sigma_color=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None):
+        """rtmi_denoise_t from the library's defaults (rtmi_denoise_defaults: 3 iterations, no demodulation, sigma_color 1,
+        sigma_normal 0.5, sigma_depth 0.1, sigma_albedo +inf) with the given fields replaced.  A sigma of +inf switches its
+        term off.  Raises ValueError for what the library would refuse."""
+        d = _ffi.Denoise()
+        _ffi.lib().rtmi_denoise_defaults(C.byref(d))
+        if iterations is not None:
+            if not 1 <= int(iterations) <= 8:
+                raise ValueError("iterations must be in [1, 8]")
+            d.iterations = int(iterations)
+        if demodulate is not None:
+            d.flags = HipRayCaster.DENOISE_DEMODULATE if demodulate else 0
+        for name, val in (("sigma_color", sigma_color), ("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth),
+                          ("sigma_albedo", sigma_albedo)):
+            if val is not None:
+                if not float(val) > 0.0:
+                    raise ValueError(f"{name} must be > 0 (+inf switches the term off)")
+                setattr(d, name, float(val))
+        return d
+
+    def _denoise_scene(self, scene):
+        s = self._scene if scene is None else scene
+        if s is None:
+            raise ValueError("no scene: pass scene=, or render with this caster first (the filter runs on a scene's device handle)")
+        return s
+
+    def denoise(self, color, albedo, normal, out=None, scene=None, **params):
+        """The feature-guided a-trous filter (rtmi_denoise; include/rtmi.h defines it) on host arrays: color as walk_rays
+        writes it, albedo and normal as walk_rays_features returns them for the whole frame, all C-contiguous (H, W, 4)
+        float32.  out (same shape; allocated when None; not one of the inputs) receives the result and is returned.
+        scene: the Scene whose device handle runs the filter and keeps its scratch image (default: the one this caster
+        last worked on); the result does not depend on it.
+        params: iterations, demodulate, sigma_color, sigma_normal, sigma_depth, sigma_albedo (denoise_params)."""
+        d = self.denoise_params(**params)
+        if not isinstance(color, np.ndarray) or color.ndim != 3 or color.shape[2] != 4 or color.shape[0] < 1 or color.shape[1] < 1:
+            raise ValueError("color must be a C-contiguous float32 array of shape (H, W, 4)")
+        shape = color.shape
+        if out is None:
+            out = np.zeros(shape, np.float32)
+        for name, a in (("color", color), ("albedo", albedo), ("normal", normal), ("out", out)):
+            if not isinstance(a, np.ndarray) or a.dtype != np.float32 or not a.flags.c_contiguous or a.shape != shape:
+                raise ValueError(f"{name} must be a C-contiguous float32 array of shape {shape}")
+        if any(np.shares_memory(out, a) for a in (color, albedo, normal)):
+            raise ValueError("out must not share memory with an input: the filter is never in place")
+        s = self._denoise_scene(scene)
+        self._config(s)
+        _chk(_ffi.lib().rth_caster_denoise(s.h, shape[1], shape[0], _p(color), _p(albedo), _p(normal), C.byref(d), _p(out)))
+        return out
+
+    def denoise_device(self, w, h, color_ptr, albedo_ptr, normal_ptr, out_ptr, stream=None, scene=None, **params):
+        """The same on device memory (rtmi_denoise_device): four images of w * h float4, one launch per iteration enqueued
+        on HIP stream `stream`; nothing is synchronised and nothing crosses to the host."""
+        d = self.denoise_params(**params)
+        if int(w) < 1 or int(h) < 1:
+            raise ValueError("w and h must be >= 1")
+        ptrs = [int(p or 0) for p in (color_ptr, albedo_ptr, normal_ptr, out_ptr)]
+        if not all(ptrs):
+            raise ValueError("color_ptr, albedo_ptr, normal_ptr and out_ptr must all be given")
+        if ptrs[3] in ptrs[:3]:
+            raise ValueError("out_ptr must not be one of the inputs: the filter is never in place")
+        s = self._denoise_scene(scene)
+        self._config(s)
+        _chk(_ffi.lib().rth_caster_denoise_device(s.h, int(w), int(h), C.c_void_p(ptrs[0]), C.c_void_p(ptrs[1]), C.c_void_p(ptrs[2]),
+                                                  C.byref(d), C.c_void_p(ptrs[3]), C.c_void_p(stream or 0)))
+
+    def walk_rays_denoised(self, v, s, data, **params):
+        """walk_rays, the features of all v.samples_per_pixel samples and the denoiser in one call (rtmi_render_denoised):
+        all three run on the device and only the filtered image ((H, W, 4) float32) is copied into data.  Equals denoise() of
+        walk_rays' image and walk_rays_features' albedo and normal.  Returns the render's ProgressCtx."""
+        d = self.denoise_params(**params)
+        if not isinstance(data, np.ndarray) or data.dtype != np.float32 or not data.flags.c_contiguous or data.size != v.height * v.width * 4:
+            raise ValueError("data must be a C-contiguous float32 array of height*width*4 elements")
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_denoised(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, C.byref(d),
+                                                 _p(data), C.byref(st), C.byref(wall)))
         return ProgressCtx(st.rays, wall.value, st.as_dict())
 
     def quantize_device(self, s, rgba_ptr, npixels, rgb_ptr, stream_ptr=None):
