@@ -373,6 +373,79 @@ int rtmi_render_adaptive_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, 
 int rtmi_render_adaptive(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
                          rtmi_adaptive_t* ad, float* out_host, uint32_t* counts_host, rtmi_stats_t* stats);
 
+/* Variance-guided denoising: the a-trous filter above with a colour width that follows each pixel's own
+ * measured variance, which is what an adaptive frame needs (its noise level differs by pixel by construction): the spatial
+ * half of SVGF (Schied et al. 2017).  Build-defined like rtmi_denoise, so what follows IS the definition, and
+ * tests/denoise_var_ref.py pins it bit for bit.  Only + - * / and comparisons in f32, no contraction, no exp, no sqrt.
+ *
+ * rtmi_variance*: the variance of every pixel's mean from the moments rtmi_render_adaptive_device leaves.  Per pixel: s =
+ * accum, q = sumsq (one float4 each), n = count (uint32); output one float4.  For c = r, g, b (the first line is the stop
+ * rule's own arithmetic):
+ *   inv = 1.f / (float)n;  m_c = s_c * inv;  v_c = (q_c - s_c * m_c) / (float)(n - 1)
+ *   vm_c = v_c / (float)n;  vm_c = vm_c < 0.f ? 0.f : vm_c      (a NaN stays NaN)
+ *   lane 3 = ((0.f + vm_r) + vm_g) + vm_b
+ *   n < 2 (nothing is known): all four lanes +inf.
+ * The arithmetic is per pixel, so the call takes npixels and any layout, like rtmi_quantize_device.  The device variant
+ * enqueues one launch on hip_stream and synchronises nothing; the host variant copies in, runs the kernel and copies out.
+ * npixels == 0: RTMI_OK, nothing is touched (checked after the scene, before the buffers).  RTMI_ERR_INVALID, before any HIP
+ * call and before the scene is used: a NULL scene or buffer, an output that is one of the inputs.  RTMI_ERR_UNSUPPORTED: the
+ * host variant with npixels >= 2^32.
+ *
+ * rtmi_denoise_var*: rtmi_denoise_device's arguments plus
+ *   variance  the image above for the whole width x height frame: vm = lanes 0-2, vs = lane 3
+ *   var_out   optional (NULL: not produced): the propagated variance after the last iteration, same layout; must not be any
+ *             other buffer of the call.
+ * params: an rtmi_denoise_t with the same checks and the same accepted flags, but sigma_color is in STANDARD DEVIATIONS OF THE
+ * PIXEL, not in colour units.  Defaults (rtmi_denoise_var_defaults): iterations 1, flags 0, sigma_color 3.0, sigma_normal 0.5,
+ * sigma_depth 0.1, sigma_albedo +inf (DESIGN.md 4.13 has the measurement they come from).
+ * Start value: u = color.rgb and (vm, vs) = variance; with RTMI_DENOISE_DEMODULATE u as for rtmi_denoise, vm_c = (vm_c /
+ * (albedo_c + 1/256)) / (albedo_c + 1/256) (two divisions) and vs = ((0 + vm_r) + vm_g) + vm_b of those.
+ * Iteration i is rtmi_denoise's iteration i with three differences:
+ *  1. Colour width per pixel.  For the centre pixel p, gv_p is the 3 x 3 prefilter of this iteration's input vs: taps
+ *     (dx, dy) in {-1, 0, 1}^2 at spacing 1 in every iteration, dy outer, dx inner, k3 = {1/4, 1/2, 1/4}; a tap outside the
+ *     image is skipped; num = num + (k3[dy+1] * k3[dx+1]) * vs_q, den = den + k3[dy+1] * k3[dx+1] for every tap inside (zeros
+ *     too); gv_p = num / den.  The colour term of every tap of p is g(|u_p - u_q|^2, s2c_p) with
+ *     s2c_p = (sigma_color * sigma_color) * gv_p + 0x1p-40f.  There is no 4^-i factor: the variance shrinks by itself under 2.
+ *     Everything else is unchanged: the sky-beside-sky rule, the other four factors and their order, "a tap with w == 0 is not
+ *     added", the centre tap's fixed weight, u'_p = num / den.
+ *  2. Variance propagation.  Alongside num and den, per channel, nv_c = nv_c + (w * w) * vm_{q,c} for exactly the taps that are
+ *     added; the centre tap is one of them, with w = k[2] * k[2].  The iteration's output is vm'_c = nv_c / (den * den) and
+ *     vs' = ((0 + vm'_r) + vm'_g) + vm'_b.  Colour and variance both ping-pong; no iteration is in place.
+ *  3. Result: out as for rtmi_denoise; var_out = (vm, vs), with RTMI_DENOISE_DEMODULATE vm_c = (vm_c * (albedo_c + 1/256)) *
+ *     (albedo_c + 1/256) and vs their ordered sum.
+ * Consequences:
+ *   a pixel of zero variance (sky, a Solid surface: s2c = 2^-40) mixes only with taps of identical colour, so converged
+ *   pixels are not blurred; with sigma_color = +inf such a pixel has s2c = inf * 0 = NaN and mixes with nothing;
+ *   +inf variance makes the colour term exactly 1 for finite colours: the guides alone decide;
+ *   a NaN variance gives s2c = NaN and g = 0: every pixel whose 3 x 3 neighbourhood holds it is left unfiltered in that
+ *   iteration (its centre tap alone).  No NaN ever enters a neighbour's colour; a neighbour's variance does take the NaN of a
+ *   tap it adds, which freezes that neighbour in the next iteration.
+ * Scratch: with more than one iteration the handle keeps one colour and two variance images (width*height*48 B), grown on
+ * demand and freed by rtmi_scene_destroy; no render workspace and no image of rtmi_denoise is touched.  One call per handle at
+ * a time.  RTMI_ERR_INVALID / RTMI_ERR_UNSUPPORTED as for rtmi_denoise*, and a NULL variance, out aliasing variance, var_out
+ * aliasing any other buffer.
+ *
+ * rtmi_render_adaptive_denoised: on device images the handle keeps, (1) rtmi_render_adaptive_device of the whole frame, (2)
+ * the variance image, (3) rtmi_render_features_device over samples [0, ad->min_samples), the samples every pixel has, (4) the
+ * filter.  Only the result (out_host) and the counts (counts_host, optional) are copied out.  stats are the adaptive call's;
+ * ad's outputs are filled.  RTMI_ERR_UNSUPPORTED on a scene with analytic spheres, as for rtmi_render_denoised.  Every
+ * argument check of both component calls runs before any HIP call and before the scene is used.
+ * Not here: temporal accumulation and reprojection, batches of views, striped tiles, rtmi_render_frame_multi, a sumsq output
+ * of the uniform render calls (an adaptive call with min_samples = S yields the moments of a uniform S-spp frame). */
+void rtmi_denoise_var_defaults(rtmi_denoise_t* params);
+int rtmi_variance_device(rtmi_scene_t* scene, const void* accum_device, const void* sumsq_device, const void* counts_device,
+                         uint64_t npixels, void* variance_device, void* hip_stream);
+int rtmi_variance(rtmi_scene_t* scene, const float* accum_host, const float* sumsq_host, const uint32_t* counts_host,
+                  uint64_t npixels, float* variance_host);
+int rtmi_denoise_var_device(rtmi_scene_t* scene, uint32_t width, uint32_t height, const void* color_device,
+                            const void* albedo_device, const void* normal_device, const void* variance_device,
+                            const rtmi_denoise_t* params, void* out_device, void* var_out_device, void* hip_stream);
+int rtmi_denoise_var(rtmi_scene_t* scene, uint32_t width, uint32_t height, const float* color_host, const float* albedo_host,
+                     const float* normal_host, const float* variance_host, const rtmi_denoise_t* params, float* out_host,
+                     float* var_out_host);
+int rtmi_render_adaptive_denoised(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, rtmi_adaptive_t* ad,
+                                  const rtmi_denoise_t* params, float* out_host, uint32_t* counts_host, rtmi_stats_t* stats);
+
 /* A batch of views of one scene in one call: a camera move, a stereo pair, the faces of a cube map, many
  * small windows.  vps[k] and seeds[k] are view k: what rtmi_render(scene, &vps[k], seeds[k], 0, H, ...) would render, bit
  * for bit (the RNG of a pixel is keyed by its view's seed and its pixel index inside the view, its primary rays come from

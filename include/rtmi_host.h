@@ -147,6 +147,23 @@ int rth_caster_denoise_device(rth_scene_t* s, uint32_t w, uint32_t h, const void
                               const void* normal_device, const rtmi_denoise_t* params, void* out_device, void* hip_stream);
 int rth_caster_walk_denoised(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
                              const rtmi_denoise_t* params, float* out_host, rtmi_stats_t* stats, double* wall_seconds);
+/* Variance-guided denoising (rtmi_variance* / rtmi_denoise_var* / rtmi_render_adaptive_denoised in rtmi.h, which defines it) on
+ * this scene's caster: the variance image from the moments of an adaptive render (accum, sumsq, counts of npixels pixels), the
+ * filter with that image beside rth_caster_denoise's (var_out may be NULL), and the adaptive render, its variance, the features
+ * of its first ad->min_samples samples and the filter in one call: only the result and the counts (optional) are copied out. */
+int rth_caster_variance(rth_scene_t* s, const float* accum_host, const float* sumsq_host, const uint32_t* counts_host,
+                        uint64_t npixels, float* variance_host);
+int rth_caster_variance_device(rth_scene_t* s, const void* accum_device, const void* sumsq_device, const void* counts_device,
+                               uint64_t npixels, void* variance_device, void* hip_stream);
+int rth_caster_denoise_var(rth_scene_t* s, uint32_t w, uint32_t h, const float* color_host, const float* albedo_host,
+                           const float* normal_host, const float* variance_host, const rtmi_denoise_t* params, float* out_host,
+                           float* var_out_host);
+int rth_caster_denoise_var_device(rth_scene_t* s, uint32_t w, uint32_t h, const void* color_device, const void* albedo_device,
+                                  const void* normal_device, const void* variance_device, const rtmi_denoise_t* params,
+                                  void* out_device, void* var_out_device, void* hip_stream);
+int rth_caster_walk_adaptive_denoised(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                                      rtmi_adaptive_t* ad, const rtmi_denoise_t* params, float* out_host, uint32_t* counts_host,
+                                      rtmi_stats_t* stats, double* wall_seconds);
 /* Launch tuning for this scene's caster: fields that are 0 keep the library default, xcd_aware is passed as value + 1;
  * NULL restores all defaults.  Never changes a pixel. */
 int rth_caster_set_tuning(rth_scene_t* s, const rtmi_tuning_t* tuning);

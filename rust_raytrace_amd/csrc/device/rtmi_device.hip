@@ -375,6 +375,7 @@ __global__ void __launch_bounds__(256) k_trace(DScene sc, const float4* __restri
 #include "trace_oct.hpp"
 #include "bvh_fast.hpp"
 #include "denoise.hpp"
+#include "denoise_var.hpp"
 namespace rtmi {
 
 
@@ -1026,6 +1027,11 @@ struct rtmi_scene {
     // albedo, normal, result) of the host variants.  No render call reads or writes them.
     DevBuf<float4> dn_scratch, dn_host;
     uint32_t dn_lds_max_step = DN_LDS_MAX_STEP;  // tap spacings up to this one stage through LDS (RTMI_DENOISE_LDS_STEP=0|1|2)
+    // rtmi_denoise_var*: one colour and two variance ping-pong images (grows only); the images of the host variants and of
+    // rtmi_render_adaptive_denoised, and the latter's count map.  No render call and no rtmi_denoise call reads or writes them.
+    DevBuf<float4> dnv_scratch, dnv_host;
+    DevBuf<uint32_t> dnv_cnt;
+    uint32_t dnv_lds_max_step = DNV_LDS_MAX_STEP;  // as dn_lds_max_step, for k_atrous_var (RTMI_DENOISE_VAR_LDS_STEP=0|1|2)
     DevBuf<uint8_t> mstage, mframe;  // rtmi_render_frame_multi, root scene: received bands / the frame
     hipStream_t mstream = nullptr;   // rtmi_render_frame_multi: this scene's band stream
     std::vector<ncclComm_t> comms;   // root scene, RTMI_FRAME_RCCL: one communicator per scene of the last device list
@@ -1373,6 +1379,7 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
     s->verbose = getenv("RTMI_VERBOSE") != nullptr;
     if (const char* v = getenv("RTMI_PACKET_CULL")) s->packet_cull = strcmp(v, "0") != 0;  // (env_size treats 0 as unset)
     if (const char* v = getenv("RTMI_DENOISE_LDS_STEP")) s->dn_lds_max_step = std::min<uint32_t>((uint32_t)strtoul(v, nullptr, 10), DN_LDS_MAX_STEP);
+    if (const char* v = getenv("RTMI_DENOISE_VAR_LDS_STEP")) s->dnv_lds_max_step = std::min<uint32_t>((uint32_t)strtoul(v, nullptr, 10), DNV_LDS_MAX_STEP);
     if (const char* v = getenv("RTMI_MIRROR_INPLACE")) {
         char* end = nullptr;
         const unsigned long n = strtoul(v, &end, 10);
@@ -1463,6 +1470,7 @@ int rtmi_scene_destroy(rtmi_scene_t* s) {
     s->tile.release(); s->acc.release(); s->asq.release(); s->acnt.release();
     s->alist[0].release(); s->alist[1].release(); s->ablk.release(); s->qbytes.release(); s->mstage.release(); s->mframe.release();
     s->vcams.release(); s->dn_scratch.release(); s->dn_host.release();
+    s->dnv_scratch.release(); s->dnv_host.release(); s->dnv_cnt.release();
     if (s->vcams_ev) (void)hipEventDestroy(s->vcams_ev);
     if (s->mstream) (void)hipStreamDestroy(s->mstream);
     if (!s->comms.empty()) { if (Rccl* r = rccl_api()) for (ncclComm_t c : s->comms) (void)r->CommDestroy(c); }
@@ -3077,6 +3085,183 @@ int rtmi_render_denoised(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t se
     rc = enqueue_denoise(s, vp->width, vp->height, d, d + npix, d + 2 * npix, *params, d + 3 * npix, nullptr);
     if (rc != RTMI_OK) return rc;
     HIPCHK(hipMemcpy(out_host, d + 3 * npix, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+// ---------------------------------------------------------------- variance-guided denoising (denoise_var.hpp)
+void rtmi_denoise_var_defaults(rtmi_denoise_t* p) {
+    if (!p) return;
+    p->iterations = 1; p->flags = 0;
+    p->sigma_color = 3.0f; p->sigma_normal = 0.5f; p->sigma_depth = 0.1f; p->sigma_albedo = INFINITY;
+}
+
+int rtmi_variance_device(rtmi_scene_t* s, const void* accum_device, const void* sumsq_device, const void* counts_device,
+                         uint64_t npixels, void* variance_device, void* hip_stream) {
+    if (!s) return fail(RTMI_ERR_INVALID, "variance: NULL argument (scene)");
+    if (npixels == 0) return RTMI_OK;
+    if (!accum_device || !sumsq_device || !counts_device || !variance_device)
+        return fail(RTMI_ERR_INVALID, "variance: NULL argument (accum, sumsq, counts and variance are required)");
+    if (variance_device == accum_device || variance_device == sumsq_device || variance_device == counts_device)
+        return fail(RTMI_ERR_INVALID, "variance: the output must not alias an input");
+    HIPCHK(hipSetDevice(s->device));
+    const unsigned grid = (unsigned)std::min<uint64_t>((npixels + 255) / 256, (uint64_t)s->num_cu * 8);
+    hipLaunchKernelGGL(k_variance, dim3(grid), dim3(256), 0, (hipStream_t)hip_stream, (uint64_t)npixels, (const float4*)accum_device,
+                       (const float4*)sumsq_device, (const uint32_t*)counts_device, (float4*)variance_device);
+    HIPCHK(hipGetLastError());
+    return RTMI_OK;
+}
+
+// Host variant: the moments are copied into the handle's own buffers, the kernel runs there and the image is copied out.
+int rtmi_variance(rtmi_scene_t* s, const float* accum_host, const float* sumsq_host, const uint32_t* counts_host, uint64_t npixels,
+                  float* variance_host) {
+    RTMI_GUARD_BEGIN
+    if (!s) return fail(RTMI_ERR_INVALID, "variance: NULL argument (scene)");
+    if (npixels == 0) return RTMI_OK;
+    if (!accum_host || !sumsq_host || !counts_host || !variance_host)
+        return fail(RTMI_ERR_INVALID, "variance: NULL argument (accum, sumsq, counts and variance are required)");
+    if ((const void*)variance_host == accum_host || (const void*)variance_host == sumsq_host || (const void*)variance_host == counts_host)
+        return fail(RTMI_ERR_INVALID, "variance: the output must not alias an input");
+    if (npixels >= (1ull << 32)) return fail(RTMI_ERR_UNSUPPORTED, "variance: more than 2^32 pixels in one host call");
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(s->dnv_host.ensure(3 * npixels));
+    HIPCHK(s->dnv_cnt.ensure(npixels));
+    float4* d = s->dnv_host.p;
+    HIPCHK(hipMemcpy(d, accum_host, npixels * sizeof(float4), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d + npixels, sumsq_host, npixels * sizeof(float4), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->dnv_cnt.p, counts_host, npixels * sizeof(uint32_t), hipMemcpyHostToDevice));
+    const int rc = rtmi_variance_device(s, d, d + npixels, s->dnv_cnt.p, npixels, d + 2 * npixels, nullptr);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(hipMemcpy(variance_host, d + 2 * npixels, npixels * sizeof(float4), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+// check_denoise plus the two images of this mode.  bufs: colour, albedo, normal, output; var_out may be NULL.
+static int check_denoise_var(const rtmi_scene_t* s, uint32_t width, uint32_t height, const void* const* bufs, const void* variance,
+                             const void* var_out, const rtmi_denoise_t* p) {
+    if (!s) return fail(RTMI_ERR_INVALID, "denoise: NULL argument (scene)");
+    if (!p) return fail(RTMI_ERR_INVALID, "denoise: NULL argument (params)");
+    if (!variance) return fail(RTMI_ERR_INVALID, "denoise: NULL argument (variance)");
+    if (variance == bufs[3]) return fail(RTMI_ERR_INVALID, "denoise: out must not alias variance (the filter is never in place)");
+    static const char* const names[3] = {"color", "albedo", "normal"};
+    if (var_out) {
+        for (int k = 0; k < 3; k++)
+            if (var_out == bufs[k]) return fail(RTMI_ERR_INVALID, std::string("denoise: var_out must not alias ") + names[k]);
+        if (var_out == variance) return fail(RTMI_ERR_INVALID, "denoise: var_out must not alias variance (the filter is never in place)");
+        if (var_out == bufs[3]) return fail(RTMI_ERR_INVALID, "denoise: var_out must not alias out");
+    }
+    return check_denoise(s, width, height, bufs, p);
+}
+
+// The launches of one call, on `st`.  Colour: as enqueue_denoise, out and the handle's scratch image alternate backwards from
+// out.  Variance: iteration i reads what iteration i - 1 wrote (the first: variance) into the handle's two variance images
+// in turn; the last writes var_out, or nothing.  The caller has checked the arguments.
+static int enqueue_denoise_var(rtmi_scene* s, uint32_t W, uint32_t H, const float4* color, const float4* albedo, const float4* normal,
+                               const float4* variance, const rtmi_denoise_t& p, float4* out, float4* var_out, hipStream_t st) {
+    (void)hipGetLastError();
+    const uint32_t n = p.iterations;
+    const size_t npix = (size_t)W * H;
+    if (n > 1) HIPCHK(s->dnv_scratch.ensure(3 * npix));
+    const bool demod = (p.flags & RTMI_DENOISE_DEMODULATE) != 0;
+    const uint32_t ntiles = ((W + DN_TW - 1) / DN_TW) * ((H + DN_TH - 1) / DN_TH);
+    const dim3 grid(std::min<uint32_t>(ntiles, 1u << 20)), block(DN_TW * DN_TH);
+    const DenoiseK k{p.sigma_normal * p.sigma_normal, p.sigma_depth, p.sigma_albedo * p.sigma_albedo, p.sigma_color * p.sigma_color};
+    const float4* src = color;
+    const float4* vsrc = variance;
+    for (uint32_t i = 0; i < n; i++) {
+        float4* dst = ((n - 1 - i) & 1u) ? s->dnv_scratch.p : out;
+        float4* vdst = i == n - 1 ? var_out : s->dnv_scratch.p + (1 + (i & 1u)) * npix;
+        const uint32_t step = 1u << i;
+        const uint32_t fl = (demod && i == 0 ? DN_DEMOD_IN : 0u) | (demod && i == n - 1 ? DN_REMOD_OUT : 0u);
+        if (step <= s->dnv_lds_max_step) {
+            const size_t lds = (size_t)(DN_TW + 4 * step) * (DN_TH + 4 * step) * 4 * sizeof(float4);
+            hipLaunchKernelGGL(k_atrous_var<true>, grid, block, lds, st, W, H, step, src, vsrc, albedo, normal, dst, vdst, k, fl);
+        } else {
+            hipLaunchKernelGGL(k_atrous_var<false>, grid, block, 0, st, W, H, step, src, vsrc, albedo, normal, dst, vdst, k, fl);
+        }
+        HIPCHK(hipGetLastError());
+        src = dst; vsrc = vdst;
+    }
+    return RTMI_OK;
+}
+
+int rtmi_denoise_var_device(rtmi_scene_t* s, uint32_t width, uint32_t height, const void* color_device, const void* albedo_device,
+                            const void* normal_device, const void* variance_device, const rtmi_denoise_t* params, void* out_device,
+                            void* var_out_device, void* hip_stream) {
+    RTMI_GUARD_BEGIN
+    const void* const bufs[4] = {color_device, albedo_device, normal_device, out_device};
+    const int rc = check_denoise_var(s, width, height, bufs, variance_device, var_out_device, params);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    return enqueue_denoise_var(s, width, height, (const float4*)color_device, (const float4*)albedo_device, (const float4*)normal_device,
+                               (const float4*)variance_device, *params, (float4*)out_device, (float4*)var_out_device,
+                               (hipStream_t)hip_stream);
+    RTMI_GUARD_END
+}
+
+// Host variant: the four images are copied into the handle's own buffers, filtered there and the results are copied out.
+int rtmi_denoise_var(rtmi_scene_t* s, uint32_t width, uint32_t height, const float* color_host, const float* albedo_host,
+                     const float* normal_host, const float* variance_host, const rtmi_denoise_t* params, float* out_host,
+                     float* var_out_host) {
+    RTMI_GUARD_BEGIN
+    const void* const bufs[4] = {color_host, albedo_host, normal_host, out_host};
+    const int rc0 = check_denoise_var(s, width, height, bufs, variance_host, var_out_host, params);
+    if (rc0 != RTMI_OK) return rc0;
+    const size_t npix = (size_t)width * height;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(s->dnv_host.ensure(6 * npix));
+    float4* d = s->dnv_host.p;
+    for (int k = 0; k < 3; k++) HIPCHK(hipMemcpy(d + k * npix, bufs[k], npix * sizeof(float4), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d + 3 * npix, variance_host, npix * sizeof(float4), hipMemcpyHostToDevice));
+    const int rc = enqueue_denoise_var(s, width, height, d, d + npix, d + 2 * npix, d + 3 * npix, *params, d + 4 * npix,
+                                       var_out_host ? d + 5 * npix : nullptr, nullptr);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(hipMemcpy(out_host, d + 4 * npix, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    if (var_out_host) HIPCHK(hipMemcpy(var_out_host, d + 5 * npix, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+// Adaptive render, variance image, features of the samples every pixel has and the filter, all on the handle's own device
+// images (accum, sumsq, colour, variance, albedo, normal, result); only the result and the counts cross to the host.
+int rtmi_render_adaptive_denoised(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, rtmi_adaptive_t* ad,
+                                  const rtmi_denoise_t* params, float* out_host, uint32_t* counts_host, rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    RTMI_GUARD_BEGIN
+    static const char own[8] = {};  // stand for the handle's images in the checks: they exist and do not alias
+    if (!s) return fail(RTMI_ERR_INVALID, "denoise: NULL argument (scene)");
+    if (!vp) return fail(RTMI_ERR_INVALID, "denoise: NULL argument (viewport)");
+    if (out_host && (const void*)out_host == (const void*)counts_host) return fail(RTMI_ERR_INVALID, "denoise: out must not alias counts");
+    const void* const dbufs[4] = {own, own + 1, own + 2, out_host};
+    int rc = check_denoise_var(s, vp->width, vp->height, dbufs, own + 3, nullptr, params);
+    if (rc != RTMI_OK) return rc;
+    const void* abufs[4] = {own + 4, own + 5, own + 6, own + 7};
+    rc = check_adaptive(s, vp, ad, abufs, 4, true);
+    if (rc != RTMI_OK) return rc;
+    const rtmi_tile_t tile{0u, vp->height, vp->height, 0u};
+    rtmi_viewport_t v1;
+    bool empty;
+    rc = check_features(s, vp, &tile, 0u, ad->min_samples, own, own + 1, nullptr, v1, &empty);
+    if (rc != RTMI_OK) return rc;
+    rc = check_view(vp, &tile);
+    if (rc != RTMI_OK) return rc;
+    if (s->d.nspheres)
+        return fail(RTMI_ERR_UNSUPPORTED, "denoise: the scene has analytic spheres (a build-defined primitive without feature buffers)");
+    const size_t npix = (size_t)vp->width * vp->height;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(s->dnv_host.ensure(7 * npix));
+    HIPCHK(s->dnv_cnt.ensure(npix));
+    float4* d = s->dnv_host.p;
+    float4 *accum = d, *sumsq = d + npix, *color = d + 2 * npix, *var = d + 3 * npix, *alb = d + 4 * npix, *nrm = d + 5 * npix, *res = d + 6 * npix;
+    rc = rtmi_render_adaptive_device(s, vp, seed, &tile, ad, accum, sumsq, s->dnv_cnt.p, color, nullptr, stats);
+    if (rc != RTMI_OK) return rc;
+    rc = rtmi_variance_device(s, accum, sumsq, s->dnv_cnt.p, npix, var, nullptr);
+    if (rc == RTMI_OK) rc = rtmi_render_features_device(s, vp, seed, &tile, 0u, ad->min_samples, alb, nrm, nullptr, nullptr, nullptr);
+    if (rc == RTMI_OK) rc = enqueue_denoise_var(s, vp->width, vp->height, color, alb, nrm, var, *params, res, nullptr, nullptr);
+    if (rc != RTMI_OK) { if (stats) memset(stats, 0, sizeof(*stats)); return rc; }
+    HIPCHK(hipMemcpy(out_host, res, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    if (counts_host) HIPCHK(hipMemcpy(counts_host, s->dnv_cnt.p, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return RTMI_OK;
     RTMI_GUARD_END
 }

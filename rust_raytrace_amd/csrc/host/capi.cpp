@@ -314,6 +314,50 @@ int rth_caster_walk_denoised(rth_scene_t* s, uint32_t w, uint32_t h, const float
         if (stats) *stats = ctx.stats;
     });
 }
+int rth_caster_variance(rth_scene_t* s, const float* accum_host, const float* sumsq_host, const uint32_t* counts_host,
+                        uint64_t npixels, float* variance_host) {
+    return guarded([&] {
+        caster_of(s).variance(s->scene, reinterpret_cast<const Color*>(accum_host), reinterpret_cast<const Color*>(sumsq_host),
+                              counts_host, npixels, reinterpret_cast<Color*>(variance_host));
+    });
+}
+int rth_caster_variance_device(rth_scene_t* s, const void* accum_device, const void* sumsq_device, const void* counts_device,
+                               uint64_t npixels, void* variance_device, void* hip_stream) {
+    return guarded([&] { caster_of(s).variance_device(s->scene, accum_device, sumsq_device, counts_device, npixels, variance_device, hip_stream); });
+}
+int rth_caster_denoise_var(rth_scene_t* s, uint32_t w, uint32_t h, const float* color_host, const float* albedo_host,
+                           const float* normal_host, const float* variance_host, const rtmi_denoise_t* params, float* out_host,
+                           float* var_out_host) {
+    return guarded([&] {
+        if (!params) throw std::runtime_error("NULL rtmi_denoise_t");
+        caster_of(s).denoise_var(s->scene, w, h, reinterpret_cast<const Color*>(color_host), reinterpret_cast<const Color*>(albedo_host),
+                                 reinterpret_cast<const Color*>(normal_host), reinterpret_cast<const Color*>(variance_host), *params,
+                                 reinterpret_cast<Color*>(out_host), reinterpret_cast<Color*>(var_out_host));
+    });
+}
+int rth_caster_denoise_var_device(rth_scene_t* s, uint32_t w, uint32_t h, const void* color_device, const void* albedo_device,
+                                  const void* normal_device, const void* variance_device, const rtmi_denoise_t* params,
+                                  void* out_device, void* var_out_device, void* hip_stream) {
+    return guarded([&] {
+        if (!params) throw std::runtime_error("NULL rtmi_denoise_t");
+        caster_of(s).denoise_var_device(s->scene, w, h, color_device, albedo_device, normal_device, variance_device, *params, out_device,
+                                        var_out_device, hip_stream);
+    });
+}
+int rth_caster_walk_adaptive_denoised(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                                      rtmi_adaptive_t* ad, const rtmi_denoise_t* params, float* out_host, uint32_t* counts_host,
+                                      rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!ad) throw std::runtime_error("NULL rtmi_adaptive_t");
+        if (!params) throw std::runtime_error("NULL rtmi_denoise_t");
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_adaptive_denoised(v, s->scene, *ad, *params, reinterpret_cast<Color*>(out_host), counts_host, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
 int rth_caster_walk_adaptive(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
                              uint64_t row0, uint64_t nrows, rtmi_adaptive_t* ad, float* out_host, uint32_t* counts_host,
                              rtmi_stats_t* stats, double* wall) {

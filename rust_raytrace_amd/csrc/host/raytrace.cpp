@@ -748,6 +748,50 @@ void HipRayCaster::walk_rays_denoised(const Viewport& v, const Scene& s, const r
     progress.stats = st;
 }
 
+void HipRayCaster::variance(const Scene& s, const Color* accum, const Color* sumsq, const uint32_t* counts, uint64_t npixels, Color* out) {
+    rtmi_scene_t* h = resident(s);
+    const int rc = rtmi_variance(h, reinterpret_cast<const float*>(accum), reinterpret_cast<const float*>(sumsq), counts, npixels,
+                                 reinterpret_cast<float*>(out));
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_variance: ") + rtmi_last_error());
+}
+
+void HipRayCaster::variance_device(const Scene& s, const void* accum_device, const void* sumsq_device, const void* counts_device,
+                                   uint64_t npixels, void* variance_device, void* hip_stream) {
+    rtmi_scene_t* h = resident(s);
+    const int rc = rtmi_variance_device(h, accum_device, sumsq_device, counts_device, npixels, variance_device, hip_stream);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_variance_device: ") + rtmi_last_error());
+}
+
+void HipRayCaster::denoise_var(const Scene& s, uint32_t width, uint32_t height, const Color* color, const Color* albedo,
+                               const Color* normal, const Color* variance, const rtmi_denoise_t& params, Color* out, Color* var_out) {
+    rtmi_scene_t* h = resident(s);
+    const int rc = rtmi_denoise_var(h, width, height, reinterpret_cast<const float*>(color), reinterpret_cast<const float*>(albedo),
+                                    reinterpret_cast<const float*>(normal), reinterpret_cast<const float*>(variance), &params,
+                                    reinterpret_cast<float*>(out), reinterpret_cast<float*>(var_out));
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_denoise_var: ") + rtmi_last_error());
+}
+
+void HipRayCaster::denoise_var_device(const Scene& s, uint32_t width, uint32_t height, const void* color_device,
+                                      const void* albedo_device, const void* normal_device, const void* variance_device,
+                                      const rtmi_denoise_t& params, void* out_device, void* var_out_device, void* hip_stream) {
+    rtmi_scene_t* h = resident(s);
+    const int rc = rtmi_denoise_var_device(h, width, height, color_device, albedo_device, normal_device, variance_device, &params,
+                                           out_device, var_out_device, hip_stream);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_denoise_var_device: ") + rtmi_last_error());
+}
+
+void HipRayCaster::walk_adaptive_denoised(const Viewport& v, const Scene& s, rtmi_adaptive_t& ad, const rtmi_denoise_t& params,
+                                          Color* out, uint32_t* counts, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_adaptive_denoised(h, &av, seed, &ad, &params, reinterpret_cast<float*>(out), counts, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_adaptive_denoised: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
 void HipRayCaster::walk_adaptive(const Viewport& v, const Scene& s, size_t row0, size_t nrows, rtmi_adaptive_t& ad, Color* out,
                                  uint32_t* counts, ProgressCtx& progress) {
     rtmi_scene_t* h = resident(s);

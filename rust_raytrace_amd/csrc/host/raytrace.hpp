@@ -212,6 +212,20 @@ public:
                         const void* normal_device, const rtmi_denoise_t& params, void* out_device, void* hip_stream);
     // walk_rows of the whole frame, the features of all its samples and the filter, on the device; out receives the result
     void walk_rays_denoised(const Viewport& v, const Scene& s, const rtmi_denoise_t& params, Color* out, ProgressCtx& progress);
+    // Variance-guided denoising (rtmi_variance* / rtmi_denoise_var* / rtmi_render_adaptive_denoised): variance() turns the
+    // moments of an adaptive render (accum, sumsq, counts of npixels pixels) into the variance image the filter takes beside
+    // denoise()'s images; var_out (may be null) receives the propagated variance.  walk_adaptive_denoised runs the adaptive
+    // render, the variance image, the features of the first ad.min_samples samples and the filter on the device.
+    void variance(const Scene& s, const Color* accum, const Color* sumsq, const uint32_t* counts, uint64_t npixels, Color* out);
+    void variance_device(const Scene& s, const void* accum_device, const void* sumsq_device, const void* counts_device,
+                         uint64_t npixels, void* variance_device, void* hip_stream);
+    void denoise_var(const Scene& s, uint32_t width, uint32_t height, const Color* color, const Color* albedo, const Color* normal,
+                     const Color* variance, const rtmi_denoise_t& params, Color* out, Color* var_out);
+    void denoise_var_device(const Scene& s, uint32_t width, uint32_t height, const void* color_device, const void* albedo_device,
+                            const void* normal_device, const void* variance_device, const rtmi_denoise_t& params, void* out_device,
+                            void* var_out_device, void* hip_stream);
+    void walk_adaptive_denoised(const Viewport& v, const Scene& s, rtmi_adaptive_t& ad, const rtmi_denoise_t& params, Color* out,
+                                uint32_t* counts, ProgressCtx& progress);
     // Adaptive sampling (rtmi_render_adaptive / rtmi_render_adaptive_device): every pixel stops at its own count between
     // ad.min_samples and v.samples_per_pixel and equals the pixel of walk_rows at that many samples; counts receives them.
     void walk_adaptive(const Viewport& v, const Scene& s, size_t row0, size_t nrows, rtmi_adaptive_t& ad, Color* out,

@@ -726,6 +726,127 @@ class HipRayCaster:
                                                  _p(data), C.byref(st), C.byref(wall)))
         return ProgressCtx(st.rays, wall.value, st.as_dict())
 
+    @staticmethod
+    def denoise_var_params(iterations=None, demodulate=None, sigma_color=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None):
+        """rtmi_denoise_t of the variance-guided filter from the library's defaults (rtmi_denoise_var_defaults: 1 iteration, no
+        demodulation, sigma_color 3 STANDARD DEVIATIONS OF THE PIXEL, sigma_normal 0.5, sigma_depth 0.1, sigma_albedo +inf)
+        with the given fields replaced.  Raises ValueError for what the library would refuse."""
+        base = _ffi.Denoise()
+        _ffi.lib().rtmi_denoise_var_defaults(C.byref(base))
+        d = HipRayCaster.denoise_params(iterations, demodulate, sigma_color, sigma_normal, sigma_depth, sigma_albedo)
+        if iterations is None:
+            d.iterations = base.iterations
+        if sigma_color is None:
+            d.sigma_color = base.sigma_color
+        return d
+
+    def variance(self, accum, sumsq, counts, out=None, scene=None):
+        """The variance of every pixel's mean (rtmi_variance; include/rtmi.h defines it) from the moments of an adaptive
+        render: accum and sumsq C-contiguous (..., 4) float32 of one shape, counts uint32 of that shape without the last axis.
+        out (same shape as accum; allocated when None; none of the inputs) receives (vm_r, vm_g, vm_b, their sum) per pixel,
+        +inf where count < 2, and is returned."""
+        if not isinstance(accum, np.ndarray) or accum.dtype != np.float32 or accum.ndim < 1 or accum.shape[-1] != 4 or not accum.flags.c_contiguous:
+            raise ValueError("accum must be a C-contiguous float32 array of shape (..., 4)")
+        if out is None:
+            out = np.zeros(accum.shape, np.float32)
+        for name, a in (("sumsq", sumsq), ("out", out)):
+            if not isinstance(a, np.ndarray) or a.dtype != np.float32 or not a.flags.c_contiguous or a.shape != accum.shape:
+                raise ValueError(f"{name} must be a C-contiguous float32 array of shape {accum.shape}")
+        if not isinstance(counts, np.ndarray) or counts.dtype != np.uint32 or not counts.flags.c_contiguous or counts.shape != accum.shape[:-1]:
+            raise ValueError(f"counts must be a C-contiguous uint32 array of shape {accum.shape[:-1]}")
+        if any(np.shares_memory(out, a) for a in (accum, sumsq, counts)):
+            raise ValueError("out must not share memory with an input")
+        s = self._denoise_scene(scene)
+        self._config(s)
+        _chk(_ffi.lib().rth_caster_variance(s.h, _p(accum), _p(sumsq), _p(counts), counts.size, _p(out)))
+        return out
+
+    def variance_device(self, accum_ptr, sumsq_ptr, counts_ptr, npixels, variance_ptr, stream=None, scene=None):
+        """The same on device memory (rtmi_variance_device): npixels float4 / float4 / uint32 in, npixels float4 out, one
+        launch enqueued on HIP stream `stream`; nothing is synchronised."""
+        ptrs = [int(p or 0) for p in (accum_ptr, sumsq_ptr, counts_ptr, variance_ptr)]
+        if int(npixels) < 0:
+            raise ValueError("npixels must be >= 0")
+        if not all(ptrs):
+            raise ValueError("accum_ptr, sumsq_ptr, counts_ptr and variance_ptr must all be given")
+        if ptrs[3] in ptrs[:3]:
+            raise ValueError("variance_ptr must not be one of the inputs")
+        s = self._denoise_scene(scene)
+        self._config(s)
+        _chk(_ffi.lib().rth_caster_variance_device(s.h, C.c_void_p(ptrs[0]), C.c_void_p(ptrs[1]), C.c_void_p(ptrs[2]), int(npixels),
+                                                   C.c_void_p(ptrs[3]), C.c_void_p(stream or 0)))
+
+    def denoise_var(self, color, albedo, normal, variance, out=None, var_out=None, scene=None, **params):
+        """The variance-guided a-trous filter (rtmi_denoise_var; include/rtmi.h defines it) on host arrays: denoise()'s three
+        images and variance as variance() returns it for the frame, all C-contiguous (H, W, 4) float32.  out (allocated when
+        None) receives the result and is returned.  var_out: None leaves the propagated variance out, True allocates it, an
+        array is filled; with it the call returns (out, var_out).  No output may share memory with another buffer.
+        params: iterations, demodulate, sigma_color (in standard deviations of the pixel), sigma_normal, sigma_depth,
+        sigma_albedo (denoise_var_params)."""
+        d = self.denoise_var_params(**params)
+        if not isinstance(color, np.ndarray) or color.ndim != 3 or color.shape[2] != 4 or color.shape[0] < 1 or color.shape[1] < 1:
+            raise ValueError("color must be a C-contiguous float32 array of shape (H, W, 4)")
+        shape = color.shape
+        if out is None:
+            out = np.zeros(shape, np.float32)
+        if var_out is True:
+            var_out = np.zeros(shape, np.float32)
+        bufs = [("color", color), ("albedo", albedo), ("normal", normal), ("variance", variance), ("out", out)]
+        if var_out is not None:
+            bufs.append(("var_out", var_out))
+        for name, a in bufs:
+            if not isinstance(a, np.ndarray) or a.dtype != np.float32 or not a.flags.c_contiguous or a.shape != shape:
+                raise ValueError(f"{name} must be a C-contiguous float32 array of shape {shape}")
+        for k in range(4, len(bufs)):
+            if any(np.shares_memory(bufs[k][1], bufs[j][1]) for j in range(k)):
+                raise ValueError(f"{bufs[k][0]} must not share memory with another buffer: the filter is never in place")
+        s = self._denoise_scene(scene)
+        self._config(s)
+        _chk(_ffi.lib().rth_caster_denoise_var(s.h, shape[1], shape[0], _p(color), _p(albedo), _p(normal), _p(variance), C.byref(d),
+                                               _p(out), _p(var_out) if var_out is not None else None))
+        return out if var_out is None else (out, var_out)
+
+    def denoise_var_device(self, w, h, color_ptr, albedo_ptr, normal_ptr, variance_ptr, out_ptr, var_out_ptr=None, stream=None,
+                           scene=None, **params):
+        """The same on device memory (rtmi_denoise_var_device): images of w * h float4, one launch per iteration enqueued on
+        HIP stream `stream`; nothing is synchronised and nothing crosses to the host.  var_out_ptr None/0: not produced."""
+        d = self.denoise_var_params(**params)
+        if int(w) < 1 or int(h) < 1:
+            raise ValueError("w and h must be >= 1")
+        ptrs = [int(p or 0) for p in (color_ptr, albedo_ptr, normal_ptr, variance_ptr, out_ptr)]
+        if not all(ptrs):
+            raise ValueError("color_ptr, albedo_ptr, normal_ptr, variance_ptr and out_ptr must all be given")
+        vo = int(var_out_ptr or 0)
+        if ptrs[4] in ptrs[:4] or (vo and vo in ptrs):
+            raise ValueError("out_ptr and var_out_ptr must not be another buffer of the call: the filter is never in place")
+        s = self._denoise_scene(scene)
+        self._config(s)
+        _chk(_ffi.lib().rth_caster_denoise_var_device(s.h, int(w), int(h), C.c_void_p(ptrs[0]), C.c_void_p(ptrs[1]), C.c_void_p(ptrs[2]),
+                                                      C.c_void_p(ptrs[3]), C.byref(d), C.c_void_p(ptrs[4]), C.c_void_p(vo),
+                                                      C.c_void_p(stream or 0)))
+
+    def walk_rays_adaptive_denoised(self, v, s, data, min_samples=8, pass_samples=8, rel_tol=None, abs_tol=None, counts=None, **params):
+        """walk_rays_adaptive, variance() of its moments, the features of samples [0, min_samples) and denoise_var() in one
+        call (rtmi_render_adaptive_denoised): all four run on the device and only the filtered image ((H, W, 4) float32, into
+        data) and the count map are copied out.  Adaptive arguments and ctx as walk_rays_adaptive, params as denoise_var."""
+        d = self.denoise_var_params(**params)
+        if not isinstance(data, np.ndarray) or data.dtype != np.float32 or not data.flags.c_contiguous or data.size != v.height * v.width * 4:
+            raise ValueError("data must be a C-contiguous float32 array of height*width*4 elements")
+        if counts is None:
+            counts = np.zeros((v.height, v.width), np.uint32)
+        elif not isinstance(counts, np.ndarray) or counts.dtype != np.uint32 or not counts.flags.c_contiguous or counts.size != v.height * v.width:
+            raise ValueError("counts must be a C-contiguous uint32 array of height*width elements")
+        ad = self._adaptive(v, min_samples, pass_samples, self.ADAPTIVE_REL_TOL if rel_tol is None else rel_tol,
+                            self.ADAPTIVE_ABS_TOL if abs_tol is None else abs_tol)
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_adaptive_denoised(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel,
+                                                          C.byref(ad), C.byref(d), _p(data), _p(counts), C.byref(st), C.byref(wall)))
+        ctx = self._adaptive_ctx(st, wall, ad)
+        ctx.counts = counts
+        return ctx
+
     def quantize_device(self, s, rgba_ptr, npixels, rgb_ptr, stream_ptr=None):
         """write_png's `(c * 255.) as u8` on device memory (f32x4 -> u8x3), enqueued on the stream."""
         self._config(s)
