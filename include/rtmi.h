@@ -499,6 +499,44 @@ int rtmi_render_frame_multi(rtmi_scene_t* const* scenes, uint32_t nscenes, const
 int rtmi_trace(rtmi_scene_t* scene, uint64_t n, const float* orig4, const float* dir4,
                uint32_t* tri, float* t, uint32_t* face, rtmi_stats_t* stats);
 
+/* Any-hit occlusion query: "is anything in the way?" for n explicit rays, each with its own limit -- shadow
+ * and visibility tests, ambient occlusion, line of sight between two points (the shadow ray of LightSource::get_shadow_ray,
+ * commented out at raytrace.rs:1203-1224, asks exactly this).  Rays as for rtmi_trace: float4 origin and float4 unit direction
+ * as `make_ray` stores them.  Output: one byte per ray, 0 or 1.
+ * Definition.  For ray i let (tri, t) be what rtmi_trace returns for that ray on this scene handle with its current options.
+ *   occluded[i] = (tri != 0 && t < tmax[i]) ? 1 : 0        (the comparison in f32)
+ * Consequences:
+ *   a NaN t (a degenerate "hit", raytrace.rs:402-405) does not occlude;
+ *   a hit at t == tmax does not occlude;
+ *   tmax NaN or <= -0.f gives 0 for every ray (a hit has t >= 0 or NaN);
+ *   a NULL tmax pointer means +inf for every ray: any hit of finite t occludes, a hit at t = +inf does not;
+ *   the triangle the origin lies on is not excluded and there is no epsilon: offsetting the origin is the caller's job, as it is
+ *   for bounce rays (raytrace.rs:284-296) and as the comment on rtmi_sphere_t says;
+ *   analytic spheres take part exactly as in rtmi_trace: a sphere hit that replaces the tree's hit is the (tri, t) of the rule;
+ *   RTMI_OPT_GENERIC, RTMI_OPT_FAST and RTMI_OPT_BVH each give their own mode's (tri, t).
+ * How.  An exact octree and the linear list are walked by any-hit kernels (k_occluded_oct, k_occluded_linear): the closest-hit
+ * walk's running best only ever moves to a smaller t, so a ray is answered 1 and leaves the walk as soon as that best is
+ * < tmax; a ray that is not occluded is walked to the end, step for step as rtmi_trace walks it.  Rays with a zero direction
+ * component are traced in place.  Generic trees, RTMI_OPT_GENERIC, RTMI_OPT_BVH and scenes with analytic spheres run
+ * rtmi_trace's closest-hit launch followed by one elementwise kernel (k_occl_from_hits).  Same bytes either way.
+ * rtmi_occluded: host buffers; orig4, dir4 and tmax are copied in, n bytes are copied out.
+ * rtmi_occluded_device: device buffers, read in place (no staging copy of the rays).  The library's stream starts after the work
+ * already queued on hip_stream and hip_stream is made to wait for it, as for rtmi_render_tile_device; the call returns once the
+ * work is enqueued and the counters are read back.  One call per scene handle at a time, like every call on a handle.
+ * stats: rays = n; kernel_ms, trace_ms (the walk kernel alone), trace_launches = 1, streams = 1 as rtmi_trace fills them (the
+ * device variant's kernel_ms is the span on hip_stream).  With RTMI_OPT_COUNTERS the five work counters are the work the
+ * any-hit walk actually did: each <= rtmi_trace's for the same rays, and equal to them when no ray is answered 1 (tmax all 0
+ * or all NaN, say).
+ * n == 0: RTMI_OK, nothing is touched (checked after the scene, before the buffers).  RTMI_ERR_INVALID, before any HIP call
+ * and before the scene is used: a NULL scene, orig4, dir4 or occluded; an output that overlaps an input (as byte ranges of 16 n,
+ * 16 n, 4 n and n bytes).  RTMI_ERR_UNSUPPORTED: n >= 2^31, as for rtmi_trace.  stats come back cleared on failure.
+ * Not here: shadow rays in shading, an ambient-occlusion buffer, occlusion for batches of views and for
+ * rtmi_render_frame_multi. */
+int rtmi_occluded(rtmi_scene_t* scene, uint64_t n, const float* orig4, const float* dir4, const float* tmax /* n floats or NULL */,
+                  uint8_t* occluded, rtmi_stats_t* stats);
+int rtmi_occluded_device(rtmi_scene_t* scene, uint64_t n, const void* orig4_device, const void* dir4_device,
+                         const void* tmax_device /* or NULL */, void* occluded_device, void* hip_stream, rtmi_stats_t* stats);
+
 /* Per-ray debug records (the reference's Scene { debug_ctx, debug_en }, raytrace.rs:1297-1303, debug.rs): what the
  * octree walk did for each ray, taken from the production walk itself (k_trace_record: the walk of rtmi_trace in a
  * recording mode).  A leaf is named by its index in the `boxes` array rtmi_scene_create received (Scene.tree()'s

@@ -117,6 +117,12 @@ int rth_caster_walk_views_device(rth_scene_t* s, uint32_t nviews, uint32_t w, ui
                                  rtmi_stats_t* stats, double* wall_seconds);
 int rth_caster_trace(rth_scene_t* s, uint64_t n, const float* orig4, const float* dir4, uint32_t* tri, float* t,
                      uint32_t* face, rtmi_stats_t* stats);
+/* Any-hit occlusion (rtmi_occluded* in rtmi.h, which defines it) on the scene's resident copy: one byte per ray, 1 iff the
+ * ray's closest hit lies before tmax (NULL: +inf for every ray). */
+int rth_caster_occluded(rth_scene_t* s, uint64_t n, const float* orig4, const float* dir4, const float* tmax, uint8_t* occluded,
+                        rtmi_stats_t* stats);
+int rth_caster_occluded_device(rth_scene_t* s, uint64_t n, const void* orig4_device, const void* dir4_device,
+                               const void* tmax_device, void* occluded_device, void* hip_stream, rtmi_stats_t* stats);
 /* Per-ray records (rtmi_trace_records / rtmi_primary_records, same buffers and size-query idiom) on the scene's
  * resident copy; the primary records use the caster's seed. */
 int rth_caster_trace_records(rth_scene_t* s, uint64_t n, const float* orig4, const float* dir4, rtmi_ray_record_t* recs,

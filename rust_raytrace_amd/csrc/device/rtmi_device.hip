@@ -385,11 +385,15 @@ namespace rtmi {
 // by the whole block, double-buffered against the tests) and every lane reads the records at a
 // wave-uniform LDS address (broadcast).  Fold and test exactly as get_box_min_time_intersection /
 // Triangle::intersects (raytrace.rs:1012-1050, 400-439).
+// OCCL (k_occluded_linear, rtmi_occluded*): the any-hit form.  A ray whose fold accumulator is < its tmax after a chunk is
+// answered 1 and tests no further chunk (the accumulator only falls from there; a NaN accumulator sticks and never passes
+// `lt < tmax`); its lane keeps staging, which is the whole block's work, and a block whose 256 rays are all answered
+// leaves the list.  A ray that never gets there scans the whole list and answers 0.
 #define RTMI_LIN_CHUNK 64
-template <bool COUNT>
-__global__ void __launch_bounds__(256) k_trace_linear(DScene sc, const float4* __restrict__ qo, const float4* __restrict__ qd,
-                                                      DCtrl* __restrict__ ctrl, int pass, uint32_t* __restrict__ hit_tf,
-                                                      float* __restrict__ hit_t) {
+template <bool COUNT, bool OCCL>
+__device__ __forceinline__ void trace_linear(const DScene& sc, const float4* __restrict__ qo, const float4* __restrict__ qd,
+                                             DCtrl* __restrict__ ctrl, int pass, uint32_t* __restrict__ hit_tf,
+                                             float* __restrict__ hit_t, const float* __restrict__ tmax, uint8_t* __restrict__ occ) {
     constexpr int C = RTMI_LIN_CHUNK;
     __shared__ float4 rec[2][6][C];   // [buffer][plane0, plane1, edge0..3][triangle]
     __shared__ uint32_t rid[2][C];
@@ -440,6 +444,8 @@ __global__ void __launch_bounds__(256) k_trace_linear(DScene sc, const float4* _
         bool lhave = false;
         float lt = 0.f;
         uint32_t ltf = 0;
+        const float tmx = OCCL ? (active ? (tmax ? tmax[i] : INFINITY) : 0.f) : 0.f;
+        bool done = OCCL && !active;  // OCCL: this lane tests no more (answered, or it has no ray)
         float4 v[2];
         uint32_t id[2];
         if (nchunks) { stage_load(0, v, id); stage_store(0, v, id); }
@@ -448,7 +454,7 @@ __global__ void __launch_bounds__(256) k_trace_linear(DScene sc, const float4* _
             const int buf = ch & 1;
             const bool next = ch + 1 < nchunks;
             if (next) stage_load(ch + 1, v, id);  // global gathers in flight while this chunk is tested
-            const uint32_t n = min((uint32_t)C, ntri - ch * C);
+            const uint32_t n = (OCCL && done) ? 0u : min((uint32_t)C, ntri - ch * C);
             for (uint32_t j = 0; j < n; j++) {
                 const float4 p0 = rec[buf][0][j], p1 = rec[buf][1][j];
                 const float ax = p0.x - r.ox, ay = p0.y - r.oy, az = p0.z - r.oz;
@@ -478,12 +484,18 @@ __global__ void __launch_bounds__(256) k_trace_linear(DScene sc, const float4* _
             }
             if (COUNT && active) cnt[1] += n;
             if (next) stage_store(buf ^ 1, v, id);
-            __syncthreads();
+            if (OCCL) {
+                done = done | (lhave && lt < tmx);
+                if (__syncthreads_count(!done) == 0) break;  // (the barrier of the other form, with the block's vote)
+            } else __syncthreads();
         }
         if (active) {
             if (COUNT) cnt[4]++;
-            hit_tf[i] = lhave ? ltf : 0u;
-            hit_t[i] = lhave ? lt : 0.f;
+            if (OCCL) occ[i] = (lhave && lt < tmx) ? (uint8_t)1 : (uint8_t)0;
+            else {
+                hit_tf[i] = lhave ? ltf : 0u;
+                hit_t[i] = lhave ? lt : 0.f;
+            }
         }
     }
     if (COUNT) {
@@ -491,6 +503,27 @@ __global__ void __launch_bounds__(256) k_trace_linear(DScene sc, const float4* _
         for (int k = 0; k < 5; k++)
             if (cnt[k]) atomicAdd(&ctrl->counters[k], cnt[k]);
     }
+}
+template <bool COUNT>
+__global__ void __launch_bounds__(256) k_trace_linear(DScene sc, const float4* __restrict__ qo, const float4* __restrict__ qd,
+                                                      DCtrl* __restrict__ ctrl, int pass, uint32_t* __restrict__ hit_tf,
+                                                      float* __restrict__ hit_t) {
+    trace_linear<COUNT, false>(sc, qo, qd, ctrl, pass, hit_tf, hit_t, nullptr, nullptr);
+}
+template <bool COUNT>
+__global__ void __launch_bounds__(256) k_occluded_linear(DScene sc, const float4* __restrict__ qo, const float4* __restrict__ qd,
+                                                         DCtrl* __restrict__ ctrl, int pass, const float* __restrict__ tmax,
+                                                         uint8_t* __restrict__ occ) {
+    trace_linear<COUNT, true>(sc, qo, qd, ctrl, pass, nullptr, nullptr, tmax, occ);
+}
+
+// rtmi_occluded* from closest hits (generic tree, BVH mode, scenes with analytic spheres; the definition itself, and what the
+// tests hold the any-hit kernels against): occ[i] = (tri != 0 && t < tmax[i]), tmax null = +inf
+__global__ void __launch_bounds__(256) k_occl_from_hits(uint32_t n, const uint32_t* __restrict__ hit_tf, const float* __restrict__ hit_t,
+                                                        const float* __restrict__ tmax, uint8_t* __restrict__ occ) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        occ[i] = ((hit_tf[i] & 0x3FFFFFFFu) != 0u && hit_t[i] < (tmax ? tmax[i] : INFINITY)) ? (uint8_t)1 : (uint8_t)0;
 }
 
 // ---------------------------------------------------------------- generation / shading (per-pass pipeline)
@@ -1032,6 +1065,8 @@ struct rtmi_scene {
     DevBuf<float4> dnv_scratch, dnv_host;
     DevBuf<uint32_t> dnv_cnt;
     uint32_t dnv_lds_max_step = DNV_LDS_MAX_STEP;  // as dn_lds_max_step, for k_atrous_var (RTMI_DENOISE_VAR_LDS_STEP=0|1|2)
+    DevBuf<float> occ_tmax;          // rtmi_occluded (host variant): the limits and the answers on the device
+    DevBuf<uint8_t> occ_out;
     DevBuf<uint8_t> mstage, mframe;  // rtmi_render_frame_multi, root scene: received bands / the frame
     hipStream_t mstream = nullptr;   // rtmi_render_frame_multi: this scene's band stream
     std::vector<ncclComm_t> comms;   // root scene, RTMI_FRAME_RCCL: one communicator per scene of the last device list
@@ -1047,6 +1082,7 @@ struct rtmi_scene {
     rtmi_tuning_t tune{};
     bool verbose = false;
     int vote[4] = {3, 2, 3, 2};  // SELECT : LEAF vote weights of the walk, primary rays / bounce rays (experiments: RTMI_VOTE="a,b,c,d")
+    int occl_from_hits = 0;      // rtmi_occluded* runs the closest-hit launch + k_occl_from_hits everywhere (RTMI_OCCLUDED_ANYHIT=0, for comparison)
     int packet_cull = 1;         // k_path_primary culls leaf triangles per pixel packet (RTMI_PACKET_CULL=0: off, for comparison)
     // k_path_primary traces the mirror reflections of its primary rays itself when a wave has at least this many
     // (RTMI_MIRROR_INPLACE=n; 0: off, everything above 64: never)
@@ -1378,6 +1414,7 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
     s->tune.slow_path_off = (uint32_t)std::min<size_t>(env_size("RTMI_SLOW_PATH_OFF", 0), 1);
     s->verbose = getenv("RTMI_VERBOSE") != nullptr;
     if (const char* v = getenv("RTMI_PACKET_CULL")) s->packet_cull = strcmp(v, "0") != 0;  // (env_size treats 0 as unset)
+    if (const char* v = getenv("RTMI_OCCLUDED_ANYHIT")) s->occl_from_hits = strcmp(v, "0") == 0;
     if (const char* v = getenv("RTMI_DENOISE_LDS_STEP")) s->dn_lds_max_step = std::min<uint32_t>((uint32_t)strtoul(v, nullptr, 10), DN_LDS_MAX_STEP);
     if (const char* v = getenv("RTMI_DENOISE_VAR_LDS_STEP")) s->dnv_lds_max_step = std::min<uint32_t>((uint32_t)strtoul(v, nullptr, 10), DNV_LDS_MAX_STEP);
     if (const char* v = getenv("RTMI_MIRROR_INPLACE")) {
@@ -1471,6 +1508,7 @@ int rtmi_scene_destroy(rtmi_scene_t* s) {
     s->alist[0].release(); s->alist[1].release(); s->ablk.release(); s->qbytes.release(); s->mstage.release(); s->mframe.release();
     s->vcams.release(); s->dn_scratch.release(); s->dn_host.release();
     s->dnv_scratch.release(); s->dnv_host.release(); s->dnv_cnt.release();
+    s->occ_tmax.release(); s->occ_out.release();
     if (s->vcams_ev) (void)hipEventDestroy(s->vcams_ev);
     if (s->mstream) (void)hipStreamDestroy(s->mstream);
     if (!s->comms.empty()) { if (Rccl* r = rccl_api()) for (ncclComm_t c : s->comms) (void)r->CommDestroy(c); }
@@ -1603,6 +1641,8 @@ static dim3 oct_grid(const rtmi_scene* s) {
 typedef void (*WalkKernel)(DScene, OctArgs, DCtrl*, int, int);
 typedef void (*ListWalkKernel)(DScene, OctArgs, DCtrl*, int, int, const uint32_t*);
 static const WalkKernel trace_oct_variant[2][2] = RTMI_COUNT_FAST(k_trace_oct);
+typedef void (*OcclWalkKernel)(DScene, OctArgs, DCtrl*, int, int, OcclArgs);
+static const OcclWalkKernel occluded_oct_variant[2][2] = RTMI_COUNT_FAST(k_occluded_oct);
 static const WalkKernel path_variant[2][2][2][2] = {  // [slow][mode == Samp::PASS][count][fast]
     {RTMI_COUNT_FAST(k_path_primary), RTMI_COUNT_FAST(k_path_primary_samples)},
     {RTMI_COUNT_FAST(k_path_slow), RTMI_COUNT_FAST(k_path_slow_samples)}};
@@ -2605,6 +2645,127 @@ int rtmi_trace(rtmi_scene_t* s, uint64_t n, const float* orig4, const float* dir
         stats->kernel_ms = ms; stats->trace_ms = ms; stats->trace_launches = 1; stats->streams = 1;
     }
     return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+// ---------------------------------------------------------------- any-hit occlusion (rtmi_occluded*)
+// Checks that come before any HIP call and before the scene is used (a CPU-only caller reaches them).  The buffers are
+// compared as the byte ranges the call reads and writes (16 n, 16 n, 4 n in; n out).
+static int check_occluded(const rtmi_scene_t* s, uint64_t n, const void* orig4, const void* dir4, const void* tmax, const void* occ,
+                          rtmi_stats_t* stats, bool& empty) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    empty = false;
+    if (!s) return fail(RTMI_ERR_INVALID, "occluded: NULL argument (scene)");
+    if (n == 0) { empty = true; return RTMI_OK; }
+    if (!orig4 || !dir4 || !occ) return fail(RTMI_ERR_INVALID, "occluded: NULL argument (orig4, dir4 and occluded are required)");
+    const uint64_t m = std::min<uint64_t>(n, 1ull << 40);  // (a count that is refused below anyway: the sizes must not wrap)
+    const uintptr_t o0 = (uintptr_t)occ, o1 = o0 + m;
+    const struct { const void* p; uint64_t bytes; const char* name; } in[3] = {{orig4, m * 16, "orig4"}, {dir4, m * 16, "dir4"}, {tmax, m * 4, "tmax"}};
+    for (const auto& b : in)
+        if (b.p && o0 < (uintptr_t)b.p + b.bytes && (uintptr_t)b.p < o1)
+            return fail(RTMI_ERR_INVALID, std::string("occluded: the output must not alias an input (") + b.name + ")");
+    if (n >= (1ull << 31)) return fail(RTMI_ERR_UNSUPPORTED, "occluded: more than 2^31 rays per call");
+    return RTMI_OK;
+}
+
+// The rays (device memory) -> one byte per ray, on stream st with ctrl->count[0] = n set there.  An exact octree and the
+// linear list run their any-hit kernels; everything else (generic tree, BVH mode, analytic spheres) its closest-hit launch
+// of rtmi_trace followed by k_occl_from_hits.  w.ev[0] / w.ev[1] bracket the walk kernel, as in rtmi_trace.
+static int enqueue_occluded(rtmi_scene* s, Work& w, hipStream_t st, uint64_t n, const float4* qo, const float4* qd, const float* tmax,
+                            uint8_t* occ) {
+    const bool count = (s->options & RTMI_OPT_COUNTERS) != 0;
+    const bool bvh = (s->options & RTMI_OPT_BVH) && s->bvh_ok, generic = (s->options & RTMI_OPT_GENERIC) != 0;
+    const bool anyhit = !bvh && !generic && s->d.nspheres == 0 && (s->root_is_leaf || s->octree) && !s->occl_from_hits;
+    s->active_streams = 1;
+    if (!anyhit) {
+        const int rc = ensure_workspace(w, (size_t)n, 1);
+        if (rc != RTMI_OK) return rc;
+    }
+    HIPCHK(hipMemsetAsync(w.ctrl.p, 0, sizeof(DCtrl), st));
+    hipLaunchKernelGGL(k_set_count, dim3(1), dim3(1), 0, st, w.ctrl.p, (uint32_t)n);
+    HIPCHK(hipEventRecord(w.ev[0], st));
+    if (!anyhit) {
+        launch_trace(s, w, st, qo, qd, 0, count, w.ev[1]);
+        const unsigned grid = (unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)s->num_cu * 8);
+        hipLaunchKernelGGL(k_occl_from_hits, dim3(grid), dim3(256), 0, st, (uint32_t)n, w.hit_tf.p, w.hit_t.p, tmax, occ);
+    } else if (s->root_is_leaf) {
+        hipLaunchKernelGGL(count ? k_occluded_linear<true> : k_occluded_linear<false>, dim3((unsigned)(s->num_cu * 8)), dim3(256), 0, st, s->d,
+                           qo, qd, w.ctrl.p, 0, tmax, occ);
+        HIPCHK(hipEventRecord(w.ev[1], st));
+    } else {
+        OctArgs a{};
+        a.qo = qo; a.qd = qd; a.pass = 0;
+        a.vote_s = s->vote[0]; a.vote_l = s->vote[1];
+        hipLaunchKernelGGL(occluded_oct_variant[count][(s->options & RTMI_OPT_FAST) != 0], oct_grid(s), dim3(64), oct_launch_lds(s, count), st,
+                           s->d, a, w.ctrl.p, (int)s->tune.refill_min0, (int)(s->tune.xcd_aware % 3u), OcclArgs{tmax, occ});
+        HIPCHK(hipEventRecord(w.ev[1], st));
+    }
+    HIPCHK(hipGetLastError());
+    return RTMI_OK;
+}
+
+// After the stream is drained: the control block's counters and the walk kernel's time
+static int collect_occluded(Work& w, hipStream_t st, rtmi_stats_t* stats, float kernel_ms) {
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
+    DCtrl h;
+    HIPCHK(hipMemcpyAsync(&h, w.ctrl.p, sizeof(DCtrl), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (stats) {
+        add_counters(*stats, ctrl_counters(h));
+        stats->kernel_ms = kernel_ms < 0.f ? ms : kernel_ms; stats->trace_ms = ms; stats->trace_launches = 1; stats->streams = 1;
+    }
+    return RTMI_OK;
+}
+
+int rtmi_occluded_device(rtmi_scene_t* s, uint64_t n, const void* orig4_device, const void* dir4_device, const void* tmax_device,
+                         void* occluded_device, void* hip_stream, rtmi_stats_t* stats) {
+    bool empty;
+    int rc = check_occluded(s, n, orig4_device, dir4_device, tmax_device, occluded_device, stats, empty);
+    if (rc != RTMI_OK || empty) return rc;
+    RTMI_GUARD_BEGIN
+    (void)hipGetLastError();
+    HIPCHK(hipSetDevice(s->device));
+    Work& w = s->w[0];
+    hipStream_t st = s->istream[0], ust = (hipStream_t)hip_stream;
+    // the library's stream starts after whatever the caller queued on its stream, and that stream waits for it
+    HIPCHK(hipEventRecord(s->fork_ev, ust));
+    HIPCHK(hipStreamWaitEvent(st, s->fork_ev, 0));
+    rc = enqueue_occluded(s, w, st, n, (const float4*)orig4_device, (const float4*)dir4_device, (const float*)tmax_device,
+                          (uint8_t*)occluded_device);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(hipEventRecord(s->join_ev[0], st));
+    HIPCHK(hipStreamWaitEvent(ust, s->join_ev[0], 0));
+    HIPCHK(hipEventRecord(s->end_ev, ust));
+    HIPCHK(hipEventSynchronize(s->end_ev));
+    float kernel_ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&kernel_ms, s->fork_ev, s->end_ev));
+    return collect_occluded(w, st, stats, kernel_ms);
+    RTMI_GUARD_END
+}
+
+int rtmi_occluded(rtmi_scene_t* s, uint64_t n, const float* orig4, const float* dir4, const float* tmax, uint8_t* occluded,
+                  rtmi_stats_t* stats) {
+    bool empty;
+    int rc = check_occluded(s, n, orig4, dir4, tmax, occluded, stats, empty);
+    if (rc != RTMI_OK || empty) return rc;
+    RTMI_GUARD_BEGIN
+    (void)hipGetLastError();
+    HIPCHK(hipSetDevice(s->device));
+    Work& w = s->w[0];
+    rc = ensure_workspace(w, (size_t)n, 1);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(s->occ_out.ensure(n));
+    if (tmax) HIPCHK(s->occ_tmax.ensure(n));
+    hipStream_t st = s->istream[0];
+    HIPCHK(hipMemcpyAsync(w.qo[0].p, orig4, n * 16, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(w.qd[0].p, dir4, n * 16, hipMemcpyHostToDevice, st));
+    if (tmax) HIPCHK(hipMemcpyAsync(s->occ_tmax.p, tmax, n * 4, hipMemcpyHostToDevice, st));
+    rc = enqueue_occluded(s, w, st, n, w.qo[0].p, w.qd[0].p, tmax ? s->occ_tmax.p : nullptr, s->occ_out.p);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(hipMemcpyAsync(occluded, s->occ_out.p, n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return collect_occluded(w, st, stats, -1.f);
     RTMI_GUARD_END
 }
 

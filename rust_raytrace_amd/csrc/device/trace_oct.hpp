@@ -82,7 +82,12 @@ enum : uint32_t { M_IDLE = 0, M_SELECT = 1, M_LEAF = 2, M_SHADE = 3 };
 // are finished or idle (or nothing else is left to do), then they are shaded together and, in the same step, every lane
 // without a ray takes one from the queue.  The arithmetic per path is k_shade's (same device functions), so the image is
 // bit-identical; only which lane evaluates it, and when, differs.
-enum : int { W_TRACE = 0, W_PRIMARY = 1, W_SLOW = 2, W_RECORD = 3 };
+//   W_OCCL     k_occluded_oct  W_TRACE's queue and walk as an ANY-HIT query (rtmi_occluded*): every ray has a
+//                              limit tmax, and the answer is 1 iff the closest hit's t < tmax.  The running best only ever
+//                              moves to a smaller t, so a lane retires its ray with 1 as soon as its running best -- or the
+//                              leaf accumulator that the merge would put there -- is < tmax; a ray that never gets there is
+//                              walked to the end exactly like W_TRACE's and answers 0.  One byte per ray is written.
+enum : int { W_TRACE = 0, W_PRIMARY = 1, W_SLOW = 2, W_RECORD = 3, W_OCCL = 4 };
 
 struct OctArgs {
     // W_TRACE
@@ -109,6 +114,12 @@ struct RecArgs {
     const unsigned long long* lfirst;
     uint32_t* lids;
     unsigned long long lcap;
+};
+
+// W_OCCL's buffers, per queued ray i: tmax[i] (null: +inf for every ray) in, occ[i] = 0 or 1 out
+struct OcclArgs {
+    const float* tmax;
+    uint8_t* occ;
 };
 
 // Frame of an inner box: node = index of its record; w = visited octants (bits 0-7) | O_DONE | O_HAS;
@@ -219,10 +230,12 @@ __host__ __device__ inline bool packet_culls(const Packet& p, float4 p0, float4 
 template <bool COUNT, bool FAST, int MODE, Samp S = Samp::FRAME>
 __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCtrl* __restrict__ ctrl, uint32_t* __restrict__ lds,
                                          int refill_min, int xcd_aware, const RecArgs& rec = RecArgs{},
-                                         const uint32_t* __restrict__ list = nullptr, const ViewTab& vt = ViewTab{}) {
+                                         const uint32_t* __restrict__ list = nullptr, const ViewTab& vt = ViewTab{},
+                                         const OcclArgs& oc = OcclArgs{}) {
     const int lane = threadIdx.x;  // one wave per block
     // rays from the queue of pass `a.pass`, closest hit to hit_tf / hit_t (W_RECORD is W_TRACE with a record per ray)
-    constexpr bool QUEUE = MODE == W_TRACE || MODE == W_RECORD;
+    // (W_OCCL is W_TRACE with a limit per ray and one byte out)
+    constexpr bool QUEUE = MODE == W_TRACE || MODE == W_RECORD || MODE == W_OCCL;
     constexpr int NT = 64;
     // which queue of the control block this launch drains: W_TRACE pass `pass`, W_PRIMARY the implicit queue of all paths
     // of the batch (slot 0); W_SLOW does not use it (its launch drains a range of the slow-path queue)
@@ -275,6 +288,15 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     bool lhave = false;
     float lt = 0.f;
     uint32_t ltf = 0;
+    // W_OCCL: the ray's limit.  The exit test is on the ACCUMULATORS, never on the t of the triangle just tested: a NaN
+    // accumulator sticks (`t < NaN` is false for every later hit, and a NaN running best blocks every later merge), so a
+    // real hit found behind it must not answer 1.  `ghave && gt < tmx` is the running best; inside a leaf `lhave && lt <
+    // tmx` answers early only when the merge at the leaf's end would take lt (no best yet, or lt < gt): lt only falls
+    // from there on, so the merged best is < tmx too.  Boxes are NOT pruned by tmx (a triangle's hit point need not lie in
+    // the leaf being scanned): the exit is the only thing this mode does less than the closest-hit walk.
+    // A ray answered 1 is retired where the test passes: its byte is stored and its lane goes idle, to refill like one whose
+    // walk ended.
+    float tmx = 0.f;
     // One-entry leaf memo per lane, in LDS behind the frame stack ([word][lane], like the stack): the first block of the
     // last leaf list this lane's ray scanned (its identity: rtmi_scene_create stores each distinct list once), that list's
     // result (t, tri | face << 30, 0 = no hit: triangle 0 is never in a tree) and, COUNT only, its plane and edge tests.
@@ -457,6 +479,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                             ghave = false; gt = 0.f; gtf = 0;
                             if (MEMO) memo[0] = 0xFFFFFFFFu;  // no block index (< 2^28)
                             mode = M_SELECT;
+                            if constexpr (MODE == W_OCCL) tmx = oc.tmax ? oc.tmax[i] : __uint_as_float(inf_bits);
                             if constexpr (MODE == W_RECORD) {  // this ray's counters start here; its leaf list at lfirst[i]
 #pragma unroll
                                 for (int k = 0; k < 5; k++) rc0[k] = (uint32_t)cnt[k];
@@ -518,8 +541,14 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
 #pragma unroll
                             for (int k = 0; k < 5; k++) rec.rcnt[(size_t)ridx * 5u + k] = (uint32_t)cnt[k] - rc0[k];
                         }
-                        a.hit_tf[ridx] = ghave ? gtf : 0u;
-                        a.hit_t[ridx] = ghave ? gt : 0.f;
+                        if constexpr (MODE == W_OCCL) {
+                            // the whole walk is behind the ray: the closest hit's t against the limit (a ray whose best
+                            // went below it has retired before, so this is 0 but for what the definition says itself)
+                            oc.occ[ridx] = (ghave && gt < tmx) ? (uint8_t)1 : (uint8_t)0;
+                        } else {
+                            a.hit_tf[ridx] = ghave ? gtf : 0u;
+                            a.hit_t[ridx] = ghave ? gt : 0.f;
+                        }
                         mode = M_IDLE;
                     } else mode = M_SHADE;  // shaded in the next exchange step, together with the other finished lanes
                 } else {
@@ -601,6 +630,11 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                             if (MEMO && memo[0] == lblock) {  // the list this ray scanned last: its result, no LEAF steps
                                 const uint32_t mtf = memo[2 * NT];
                                 if (mtf != 0u) take_leaf(__uint_as_float(memo[NT]), mtf);
+                                // (the exit test after the merge, as everywhere; a reused result cannot pass it, since the
+                                // scan that stored it would have)
+                                if constexpr (MODE == W_OCCL) {
+                                    if (ghave && gt < tmx) { oc.occ[ridx] = (uint8_t)1; mode = M_IDLE; }
+                                }
                                 if (COUNT) {
                                     const uint32_t np = memo[3 * NT], ne = memo[4 * NT];
                                     cnt[1] += np; cnt[2] += ne;
@@ -712,7 +746,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                 if (lhave) take_leaf(lt, ltf);
                 if (MEMO) {  // the key was written at leaf entry
                     memo[NT] = __float_as_uint(lt);
-                    memo[2 * NT] = lhave ? ltf : 0u;
+                    memo[2 * NT] = MODE == W_OCCL ? (lhave ? 1u : 0u) : (lhave ? ltf : 0u);  // (W_OCCL keeps no hit index)
                     if (COUNT) { memo[3 * NT] = (uint32_t)cnt[1] - memo[3 * NT]; memo[4 * NT] = (uint32_t)cnt[2] - memo[4 * NT]; }
                 }
                 mode = M_SELECT;
@@ -843,8 +877,13 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                 for (int k = 0; k < 4; k++) plane(q, ids[k], p0[k], p1[k], (cullm >> k) & 1u);
                 if (q.tri != 0u) resolve(q);
                 // (W_PRIMARY: one call of finish_leaf after both steps; the other modes keep it here, their code unchanged)
+                if constexpr (MODE == W_OCCL) {  // the any-hit exit, mid-list or at its end
+                    if (lhave && lt < tmx && (!ghave || lt < gt)) { oc.occ[ridx] = (uint8_t)1; mode = M_IDLE; }
+                    else if (!more) finish_leaf();
+                } else {
                 if (MODE == W_PRIMARY) fin = !more;
                 else if (!more) finish_leaf();
+                }
             }
             if (MODE == W_PRIMARY && fin) finish_leaf();
             }
@@ -885,6 +924,13 @@ __global__ void __launch_bounds__(64, RTMI_TRACE_WAVES) k_trace_oct(DScene sc, O
 #ifndef RTMI_PATH_WAVES
 #define RTMI_PATH_WAVES 6
 #endif
+// Any-hit occlusion (rtmi_occluded*): k_trace_oct's launch with a limit per ray and one byte out
+template <bool COUNT, bool FAST>
+__global__ void __launch_bounds__(64, RTMI_TRACE_WAVES) k_occluded_oct(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min, int xcd_aware,
+                                                                       OcclArgs oc) {
+    extern __shared__ uint32_t lds[];
+    oct_walk<COUNT, FAST, W_OCCL>(sc, a, ctrl, lds, refill_min, xcd_aware, RecArgs{}, nullptr, ViewTab{}, oc);
+}
 // Per-ray records of the exact walk (rtmi_trace_records / rtmi_primary_records): k_trace_oct<true, false> plus RecArgs
 __global__ void __launch_bounds__(64, RTMI_TRACE_WAVES) k_trace_record(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min, int xcd_aware,
                                                                        RecArgs rec) {

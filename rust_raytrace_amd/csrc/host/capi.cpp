@@ -419,6 +419,14 @@ int rth_caster_walk_views_device(rth_scene_t* s, uint32_t nviews, uint32_t w, ui
         if (stats) *stats = ctx.stats;
     });
 }
+int rth_caster_occluded(rth_scene_t* s, uint64_t n, const float* o4, const float* d4, const float* tmax, uint8_t* occluded,
+                        rtmi_stats_t* stats) {
+    return guarded([&] { caster_of(s).occluded(s->scene, n, o4, d4, tmax, occluded, stats); });
+}
+int rth_caster_occluded_device(rth_scene_t* s, uint64_t n, const void* orig4_device, const void* dir4_device, const void* tmax_device,
+                               void* occluded_device, void* hip_stream, rtmi_stats_t* stats) {
+    return guarded([&] { caster_of(s).occluded_device(s->scene, n, orig4_device, dir4_device, tmax_device, occluded_device, hip_stream, stats); });
+}
 int rth_caster_trace(rth_scene_t* s, uint64_t n, const float* o4, const float* d4, uint32_t* tri, float* t, uint32_t* face,
                      rtmi_stats_t* stats) {
     return guarded([&] {

@@ -748,6 +748,19 @@ void HipRayCaster::walk_rays_denoised(const Viewport& v, const Scene& s, const r
     progress.stats = st;
 }
 
+void HipRayCaster::occluded(const Scene& s, uint64_t n, const float* orig4, const float* dir4, const float* tmax, uint8_t* out,
+                            rtmi_stats_t* stats) {
+    rtmi_scene_t* h = resident(s);
+    if (rtmi_occluded(h, n, orig4, dir4, tmax, out, stats) != RTMI_OK) throw std::runtime_error(std::string("rtmi_occluded: ") + rtmi_last_error());
+}
+
+void HipRayCaster::occluded_device(const Scene& s, uint64_t n, const void* orig4_device, const void* dir4_device, const void* tmax_device,
+                                   void* occluded_device, void* hip_stream, rtmi_stats_t* stats) {
+    rtmi_scene_t* h = resident(s);
+    if (rtmi_occluded_device(h, n, orig4_device, dir4_device, tmax_device, occluded_device, hip_stream, stats) != RTMI_OK)
+        throw std::runtime_error(std::string("rtmi_occluded_device: ") + rtmi_last_error());
+}
+
 void HipRayCaster::variance(const Scene& s, const Color* accum, const Color* sumsq, const uint32_t* counts, uint64_t npixels, Color* out) {
     rtmi_scene_t* h = resident(s);
     const int rc = rtmi_variance(h, reinterpret_cast<const float*>(accum), reinterpret_cast<const float*>(sumsq), counts, npixels,

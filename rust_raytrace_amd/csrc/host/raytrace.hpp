@@ -212,6 +212,12 @@ public:
                         const void* normal_device, const rtmi_denoise_t& params, void* out_device, void* hip_stream);
     // walk_rows of the whole frame, the features of all its samples and the filter, on the device; out receives the result
     void walk_rays_denoised(const Viewport& v, const Scene& s, const rtmi_denoise_t& params, Color* out, ProgressCtx& progress);
+    // Any-hit occlusion (rtmi_occluded*): occluded[i] = 1 iff ray i's closest hit lies before tmax[i] (tmax null: +inf); rays
+    // as make_ray stores them, 8 floats each in two arrays.  The device variant reads device buffers in place.
+    void occluded(const Scene& s, uint64_t n, const float* orig4, const float* dir4, const float* tmax, uint8_t* out,
+                  rtmi_stats_t* stats = nullptr);
+    void occluded_device(const Scene& s, uint64_t n, const void* orig4_device, const void* dir4_device, const void* tmax_device,
+                         void* occluded_device, void* hip_stream, rtmi_stats_t* stats = nullptr);
     // Variance-guided denoising (rtmi_variance* / rtmi_denoise_var* / rtmi_render_adaptive_denoised): variance() turns the
     // moments of an adaptive render (accum, sumsq, counts of npixels pixels) into the variance image the filter takes beside
     // denoise()'s images; var_out (may be null) receives the propagated variance.  walk_adaptive_denoised runs the adaptive

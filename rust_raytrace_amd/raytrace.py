@@ -866,6 +866,44 @@ class HipRayCaster:
         _chk(_ffi.lib().rth_caster_trace(s.h, n, _p(o4), _p(d4), _p(tri), _p(t), _p(face), C.byref(st)))
         return tri, t, face, st.as_dict()
 
+    def occluded(self, s, orig4, dir4, tmax=None):
+        """Any-hit occlusion per explicit ray (rtmi_occluded; include/rtmi.h defines it): -> (uint8 array of 0 / 1, stats).
+        Ray i is occluded iff its closest hit (trace) has tri != 0 and t < tmax[i] in float32; tmax None means +inf for every
+        ray.  No epsilon and no exclusion of the triangle the origin lies on: offset the origins yourself."""
+        o4, d4 = _f(orig4).reshape(-1, 4), _f(dir4).reshape(-1, 4)
+        n = o4.shape[0]
+        if d4.shape[0] != n:
+            raise ValueError("orig4 and dir4 must hold the same number of rays")
+        tm = None
+        if tmax is not None:
+            tm = _f(tmax).reshape(-1)
+            if tm.shape[0] != n:
+                raise ValueError("tmax must hold one float per ray")
+        out = np.zeros(n, np.uint8)
+        self._config(s)
+        st = _ffi.Stats()
+        _chk(_ffi.lib().rth_caster_occluded(s.h, n, _p(o4), _p(d4), _p(tm) if tm is not None else None, _p(out), C.byref(st)))
+        return out, st.as_dict()
+
+    def occluded_device(self, s, n, orig4_ptr, dir4_ptr, tmax_ptr, occluded_ptr, stream=None):
+        """The same on device memory (rtmi_occluded_device): n float4 origins, n float4 directions and n floats of tmax
+        (tmax_ptr None/0: +inf) are read in place, n bytes are written at occluded_ptr.  The work starts after what is
+        queued on HIP stream `stream`, and that stream waits for it; the call returns once the counters are read back.
+        -> stats."""
+        ptrs = [int(p or 0) for p in (orig4_ptr, dir4_ptr, occluded_ptr)]
+        if int(n) < 0:
+            raise ValueError("n must be >= 0")
+        if not all(ptrs):
+            raise ValueError("orig4_ptr, dir4_ptr and occluded_ptr must all be given")
+        tm = int(tmax_ptr or 0)
+        if ptrs[2] in (ptrs[0], ptrs[1]) or (tm and ptrs[2] == tm):
+            raise ValueError("occluded_ptr must not be one of the inputs")
+        self._config(s)
+        st = _ffi.Stats()
+        _chk(_ffi.lib().rth_caster_occluded_device(s.h, int(n), C.c_void_p(ptrs[0]), C.c_void_p(ptrs[1]), C.c_void_p(tm),
+                                                   C.c_void_p(ptrs[2]), C.c_void_p(stream or 0), C.byref(st)))
+        return st.as_dict()
+
     def _records(self, n, call, pixel=None):
         """Size query, then the fill (rth_caster_*_records)"""
         recs = np.zeros(n, REC_DTYPE)
