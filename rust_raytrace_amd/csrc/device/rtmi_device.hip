@@ -375,7 +375,6 @@ __global__ void __launch_bounds__(256) k_trace(DScene sc, const float4* __restri
 #include "trace_oct.hpp"
 #include "bvh_fast.hpp"
 #include "denoise.hpp"
-#include "denoise_var.hpp"
 namespace rtmi {
 
 
@@ -1064,7 +1063,7 @@ struct rtmi_scene {
     // rtmi_render_adaptive_denoised, and the latter's count map.  No render call and no rtmi_denoise call reads or writes them.
     DevBuf<float4> dnv_scratch, dnv_host;
     DevBuf<uint32_t> dnv_cnt;
-    uint32_t dnv_lds_max_step = DNV_LDS_MAX_STEP;  // as dn_lds_max_step, for k_atrous_var (RTMI_DENOISE_VAR_LDS_STEP=0|1|2)
+    uint32_t dnv_lds_max_step = DN_LDS_MAX_STEP;  // as dn_lds_max_step, for the variance-guided filter (RTMI_DENOISE_VAR_LDS_STEP=0|1|2)
     DevBuf<float> occ_tmax;          // rtmi_occluded (host variant): the limits and the answers on the device
     DevBuf<uint8_t> occ_out;
     DevBuf<uint8_t> mstage, mframe;  // rtmi_render_frame_multi, root scene: received bands / the frame
@@ -1416,7 +1415,7 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
     if (const char* v = getenv("RTMI_PACKET_CULL")) s->packet_cull = strcmp(v, "0") != 0;  // (env_size treats 0 as unset)
     if (const char* v = getenv("RTMI_OCCLUDED_ANYHIT")) s->occl_from_hits = strcmp(v, "0") == 0;
     if (const char* v = getenv("RTMI_DENOISE_LDS_STEP")) s->dn_lds_max_step = std::min<uint32_t>((uint32_t)strtoul(v, nullptr, 10), DN_LDS_MAX_STEP);
-    if (const char* v = getenv("RTMI_DENOISE_VAR_LDS_STEP")) s->dnv_lds_max_step = std::min<uint32_t>((uint32_t)strtoul(v, nullptr, 10), DNV_LDS_MAX_STEP);
+    if (const char* v = getenv("RTMI_DENOISE_VAR_LDS_STEP")) s->dnv_lds_max_step = std::min<uint32_t>((uint32_t)strtoul(v, nullptr, 10), DN_LDS_MAX_STEP);
     if (const char* v = getenv("RTMI_MIRROR_INPLACE")) {
         char* end = nullptr;
         const unsigned long n = strtoul(v, &end, 10);
@@ -3163,33 +3162,78 @@ static int check_denoise(const rtmi_scene_t* s, uint32_t width, uint32_t height,
     return RTMI_OK;
 }
 
-// The launches of one call, on `st`: iteration i reads what iteration i - 1 wrote (the first: color) and the last writes out,
-// so out and the handle's scratch image alternate backwards from out.  The caller has checked the arguments.
-static int enqueue_denoise(rtmi_scene* s, uint32_t W, uint32_t H, const float4* color, const float4* albedo, const float4* normal,
-                           const rtmi_denoise_t& p, float4* out, hipStream_t st) {
+// check_denoise plus the two images of the variance-guided filter.  bufs: colour, albedo, normal, output; var_out may be NULL.
+static int check_denoise_var(const rtmi_scene_t* s, uint32_t width, uint32_t height, const void* const* bufs, const void* variance,
+                             const void* var_out, const rtmi_denoise_t* p) {
+    if (!s) return fail(RTMI_ERR_INVALID, "denoise: NULL argument (scene)");
+    if (!p) return fail(RTMI_ERR_INVALID, "denoise: NULL argument (params)");
+    if (!variance) return fail(RTMI_ERR_INVALID, "denoise: NULL argument (variance)");
+    if (variance == bufs[3]) return fail(RTMI_ERR_INVALID, "denoise: out must not alias variance (the filter is never in place)");
+    static const char* const names[3] = {"color", "albedo", "normal"};
+    if (var_out) {
+        for (int k = 0; k < 3; k++)
+            if (var_out == bufs[k]) return fail(RTMI_ERR_INVALID, std::string("denoise: var_out must not alias ") + names[k]);
+        if (var_out == variance) return fail(RTMI_ERR_INVALID, "denoise: var_out must not alias variance (the filter is never in place)");
+        if (var_out == bufs[3]) return fail(RTMI_ERR_INVALID, "denoise: var_out must not alias out");
+    }
+    return check_denoise(s, width, height, bufs, p);
+}
+
+// The launches of one call of either filter, on `st`; variance == NULL: the plain one (var_out is NULL then).  Colour:
+// iteration i reads what iteration i - 1 wrote (the first: color) and the last writes out, so out and the first image of the
+// mode's scratch alternate backwards from out.  Variance: iteration i reads what iteration i - 1 wrote (the first: variance)
+// into the scratch's second and third image in turn; the last writes var_out, or nothing.  The two filters keep their own
+// scratch: a plain call on one stream and a variance-guided one on another do not meet.  The caller has checked the arguments.
+static int enqueue_atrous(rtmi_scene* s, uint32_t W, uint32_t H, const float4* color, const float4* albedo, const float4* normal,
+                          const float4* variance, const rtmi_denoise_t& p, float4* out, float4* var_out, hipStream_t st) {
+    static constexpr decltype(&k_atrous<false, false>) kernels[2][2] = {{k_atrous<false, false>, k_atrous<false, true>},
+                                                                        {k_atrous<true, false>, k_atrous<true, true>}};
     (void)hipGetLastError();
+    const bool var = variance != nullptr;
+    DevBuf<float4>& scratch = var ? s->dnv_scratch : s->dn_scratch;
+    const uint32_t lds_max_step = var ? s->dnv_lds_max_step : s->dn_lds_max_step;
     const uint32_t n = p.iterations;
-    if (n > 1) HIPCHK(s->dn_scratch.ensure((size_t)W * H));
+    const size_t npix = (size_t)W * H;
+    if (n > 1) HIPCHK(scratch.ensure((var ? 3 : 1) * npix));
     const bool demod = (p.flags & RTMI_DENOISE_DEMODULATE) != 0;
     const uint32_t ntiles = ((W + DN_TW - 1) / DN_TW) * ((H + DN_TH - 1) / DN_TH);
     const dim3 grid(std::min<uint32_t>(ntiles, 1u << 20)), block(DN_TW * DN_TH);
     const float s2c = p.sigma_color * p.sigma_color;
     float scale = 1.f;  // 4^-i, exact
     const float4* src = color;
+    const float4* vsrc = variance;
     for (uint32_t i = 0; i < n; i++, scale = scale * 0.25f) {
-        float4* dst = ((n - 1 - i) & 1u) ? s->dn_scratch.p : out;
+        float4* dst = ((n - 1 - i) & 1u) ? scratch.p : out;
+        float4* vdst = !var || i == n - 1 ? var_out : scratch.p + (1 + (i & 1u)) * npix;
         const uint32_t step = 1u << i;
-        const DenoiseK k{p.sigma_normal * p.sigma_normal, p.sigma_depth, p.sigma_albedo * p.sigma_albedo, s2c * scale};
+        // the colour width: plain, sigma_color^2 * 4^-i; variance-guided, sigma_color^2 at every iteration (times 1, exact)
+        const DenoiseK k{p.sigma_normal * p.sigma_normal, p.sigma_depth, p.sigma_albedo * p.sigma_albedo, s2c * (var ? 1.f : scale)};
         const uint32_t fl = (demod && i == 0 ? DN_DEMOD_IN : 0u) | (demod && i == n - 1 ? DN_REMOD_OUT : 0u);
-        if (step <= s->dn_lds_max_step) {
-            const size_t lds = (size_t)(DN_TW + 4 * step) * (DN_TH + 4 * step) * 3 * sizeof(float4);
-            hipLaunchKernelGGL(k_atrous<true>, grid, block, lds, st, W, H, step, src, albedo, normal, dst, k, fl);
-        } else {
-            hipLaunchKernelGGL(k_atrous<false>, grid, block, 0, st, W, H, step, src, albedo, normal, dst, k, fl);
-        }
+        const bool stage = step <= lds_max_step;
+        const size_t lds = stage ? (size_t)(DN_TW + 4 * step) * (DN_TH + 4 * step) * (var ? 4 : 3) * sizeof(float4) : 0;
+        hipLaunchKernelGGL(kernels[stage][var], grid, block, lds, st, W, H, step, src, vsrc, albedo, normal, dst, vdst, k, fl);
         HIPCHK(hipGetLastError());
-        src = dst;
+        src = dst; vsrc = vdst;
     }
+    return RTMI_OK;
+}
+
+// The host variants: the images (colour, albedo, normal and, variance-guided, variance) are copied into the mode's buffer of
+// the handle, filtered there and the result(s) are copied out.  The caller has checked the arguments.
+static int denoise_host(rtmi_scene* s, uint32_t W, uint32_t H, const void* const* bufs, const float* variance, const rtmi_denoise_t& p,
+                        float* out, float* var_out) {
+    const void* const in[4] = {bufs[0], bufs[1], bufs[2], variance};
+    const size_t npix = (size_t)W * H, nin = variance ? 4 : 3;
+    DevBuf<float4>& buf = variance ? s->dnv_host : s->dn_host;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(buf.ensure((nin + (variance ? 2 : 1)) * npix));  // the inputs, the result and, variance-guided, var_out's
+    float4* d = buf.p;
+    for (size_t k = 0; k < nin; k++) HIPCHK(hipMemcpy(d + k * npix, in[k], npix * sizeof(float4), hipMemcpyHostToDevice));
+    float4 *res = d + nin * npix, *vres = var_out ? res + npix : nullptr;
+    const int rc = enqueue_atrous(s, W, H, d, d + npix, d + 2 * npix, variance ? d + 3 * npix : nullptr, p, res, vres, nullptr);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(hipMemcpy(out, res, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    if (var_out) HIPCHK(hipMemcpy(var_out, vres, npix * sizeof(float4), hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
 
@@ -3200,27 +3244,18 @@ int rtmi_denoise_device(rtmi_scene_t* s, uint32_t width, uint32_t height, const 
     const int rc = check_denoise(s, width, height, bufs, params);
     if (rc != RTMI_OK) return rc;
     HIPCHK(hipSetDevice(s->device));
-    return enqueue_denoise(s, width, height, (const float4*)color_device, (const float4*)albedo_device, (const float4*)normal_device,
-                           *params, (float4*)out_device, (hipStream_t)hip_stream);
+    return enqueue_atrous(s, width, height, (const float4*)color_device, (const float4*)albedo_device, (const float4*)normal_device,
+                          nullptr, *params, (float4*)out_device, nullptr, (hipStream_t)hip_stream);
     RTMI_GUARD_END
 }
 
-// Host variant: the three images are copied into the handle's own buffers, filtered there and the result is copied out.
 int rtmi_denoise(rtmi_scene_t* s, uint32_t width, uint32_t height, const float* color_host, const float* albedo_host,
                  const float* normal_host, const rtmi_denoise_t* params, float* out_host) {
     RTMI_GUARD_BEGIN
     const void* const bufs[4] = {color_host, albedo_host, normal_host, out_host};
-    const int rc0 = check_denoise(s, width, height, bufs, params);
-    if (rc0 != RTMI_OK) return rc0;
-    const size_t npix = (size_t)width * height;
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(s->dn_host.ensure(4 * npix));
-    float4* d = s->dn_host.p;
-    for (int k = 0; k < 3; k++) HIPCHK(hipMemcpy(d + k * npix, bufs[k], npix * sizeof(float4), hipMemcpyHostToDevice));
-    const int rc = enqueue_denoise(s, width, height, d, d + npix, d + 2 * npix, *params, d + 3 * npix, nullptr);
+    const int rc = check_denoise(s, width, height, bufs, params);
     if (rc != RTMI_OK) return rc;
-    HIPCHK(hipMemcpy(out_host, d + 3 * npix, npix * sizeof(float4), hipMemcpyDeviceToHost));
-    return RTMI_OK;
+    return denoise_host(s, width, height, bufs, nullptr, *params, out_host, nullptr);
     RTMI_GUARD_END
 }
 
@@ -3243,14 +3278,14 @@ int rtmi_render_denoised(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t se
     if (rc != RTMI_OK) return rc;
     rc = rtmi_render_features_device(s, vp, seed, &tile, 0u, vp->samples_per_pixel, d + npix, d + 2 * npix, nullptr, nullptr, nullptr);
     if (rc != RTMI_OK) { if (stats) memset(stats, 0, sizeof(*stats)); return rc; }
-    rc = enqueue_denoise(s, vp->width, vp->height, d, d + npix, d + 2 * npix, *params, d + 3 * npix, nullptr);
+    rc = enqueue_atrous(s, vp->width, vp->height, d, d + npix, d + 2 * npix, nullptr, *params, d + 3 * npix, nullptr, nullptr);
     if (rc != RTMI_OK) return rc;
     HIPCHK(hipMemcpy(out_host, d + 3 * npix, npix * sizeof(float4), hipMemcpyDeviceToHost));
     return RTMI_OK;
     RTMI_GUARD_END
 }
 
-// ---------------------------------------------------------------- variance-guided denoising (denoise_var.hpp)
+// ---------------------------------------------------------------- variance-guided denoising (denoise.hpp)
 void rtmi_denoise_var_defaults(rtmi_denoise_t* p) {
     if (!p) return;
     p->iterations = 1; p->flags = 0;
@@ -3298,55 +3333,6 @@ int rtmi_variance(rtmi_scene_t* s, const float* accum_host, const float* sumsq_h
     RTMI_GUARD_END
 }
 
-// check_denoise plus the two images of this mode.  bufs: colour, albedo, normal, output; var_out may be NULL.
-static int check_denoise_var(const rtmi_scene_t* s, uint32_t width, uint32_t height, const void* const* bufs, const void* variance,
-                             const void* var_out, const rtmi_denoise_t* p) {
-    if (!s) return fail(RTMI_ERR_INVALID, "denoise: NULL argument (scene)");
-    if (!p) return fail(RTMI_ERR_INVALID, "denoise: NULL argument (params)");
-    if (!variance) return fail(RTMI_ERR_INVALID, "denoise: NULL argument (variance)");
-    if (variance == bufs[3]) return fail(RTMI_ERR_INVALID, "denoise: out must not alias variance (the filter is never in place)");
-    static const char* const names[3] = {"color", "albedo", "normal"};
-    if (var_out) {
-        for (int k = 0; k < 3; k++)
-            if (var_out == bufs[k]) return fail(RTMI_ERR_INVALID, std::string("denoise: var_out must not alias ") + names[k]);
-        if (var_out == variance) return fail(RTMI_ERR_INVALID, "denoise: var_out must not alias variance (the filter is never in place)");
-        if (var_out == bufs[3]) return fail(RTMI_ERR_INVALID, "denoise: var_out must not alias out");
-    }
-    return check_denoise(s, width, height, bufs, p);
-}
-
-// The launches of one call, on `st`.  Colour: as enqueue_denoise, out and the handle's scratch image alternate backwards from
-// out.  Variance: iteration i reads what iteration i - 1 wrote (the first: variance) into the handle's two variance images
-// in turn; the last writes var_out, or nothing.  The caller has checked the arguments.
-static int enqueue_denoise_var(rtmi_scene* s, uint32_t W, uint32_t H, const float4* color, const float4* albedo, const float4* normal,
-                               const float4* variance, const rtmi_denoise_t& p, float4* out, float4* var_out, hipStream_t st) {
-    (void)hipGetLastError();
-    const uint32_t n = p.iterations;
-    const size_t npix = (size_t)W * H;
-    if (n > 1) HIPCHK(s->dnv_scratch.ensure(3 * npix));
-    const bool demod = (p.flags & RTMI_DENOISE_DEMODULATE) != 0;
-    const uint32_t ntiles = ((W + DN_TW - 1) / DN_TW) * ((H + DN_TH - 1) / DN_TH);
-    const dim3 grid(std::min<uint32_t>(ntiles, 1u << 20)), block(DN_TW * DN_TH);
-    const DenoiseK k{p.sigma_normal * p.sigma_normal, p.sigma_depth, p.sigma_albedo * p.sigma_albedo, p.sigma_color * p.sigma_color};
-    const float4* src = color;
-    const float4* vsrc = variance;
-    for (uint32_t i = 0; i < n; i++) {
-        float4* dst = ((n - 1 - i) & 1u) ? s->dnv_scratch.p : out;
-        float4* vdst = i == n - 1 ? var_out : s->dnv_scratch.p + (1 + (i & 1u)) * npix;
-        const uint32_t step = 1u << i;
-        const uint32_t fl = (demod && i == 0 ? DN_DEMOD_IN : 0u) | (demod && i == n - 1 ? DN_REMOD_OUT : 0u);
-        if (step <= s->dnv_lds_max_step) {
-            const size_t lds = (size_t)(DN_TW + 4 * step) * (DN_TH + 4 * step) * 4 * sizeof(float4);
-            hipLaunchKernelGGL(k_atrous_var<true>, grid, block, lds, st, W, H, step, src, vsrc, albedo, normal, dst, vdst, k, fl);
-        } else {
-            hipLaunchKernelGGL(k_atrous_var<false>, grid, block, 0, st, W, H, step, src, vsrc, albedo, normal, dst, vdst, k, fl);
-        }
-        HIPCHK(hipGetLastError());
-        src = dst; vsrc = vdst;
-    }
-    return RTMI_OK;
-}
-
 int rtmi_denoise_var_device(rtmi_scene_t* s, uint32_t width, uint32_t height, const void* color_device, const void* albedo_device,
                             const void* normal_device, const void* variance_device, const rtmi_denoise_t* params, void* out_device,
                             void* var_out_device, void* hip_stream) {
@@ -3355,32 +3341,19 @@ int rtmi_denoise_var_device(rtmi_scene_t* s, uint32_t width, uint32_t height, co
     const int rc = check_denoise_var(s, width, height, bufs, variance_device, var_out_device, params);
     if (rc != RTMI_OK) return rc;
     HIPCHK(hipSetDevice(s->device));
-    return enqueue_denoise_var(s, width, height, (const float4*)color_device, (const float4*)albedo_device, (const float4*)normal_device,
-                               (const float4*)variance_device, *params, (float4*)out_device, (float4*)var_out_device,
-                               (hipStream_t)hip_stream);
+    return enqueue_atrous(s, width, height, (const float4*)color_device, (const float4*)albedo_device, (const float4*)normal_device,
+                          (const float4*)variance_device, *params, (float4*)out_device, (float4*)var_out_device, (hipStream_t)hip_stream);
     RTMI_GUARD_END
 }
 
-// Host variant: the four images are copied into the handle's own buffers, filtered there and the results are copied out.
 int rtmi_denoise_var(rtmi_scene_t* s, uint32_t width, uint32_t height, const float* color_host, const float* albedo_host,
                      const float* normal_host, const float* variance_host, const rtmi_denoise_t* params, float* out_host,
                      float* var_out_host) {
     RTMI_GUARD_BEGIN
     const void* const bufs[4] = {color_host, albedo_host, normal_host, out_host};
-    const int rc0 = check_denoise_var(s, width, height, bufs, variance_host, var_out_host, params);
-    if (rc0 != RTMI_OK) return rc0;
-    const size_t npix = (size_t)width * height;
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(s->dnv_host.ensure(6 * npix));
-    float4* d = s->dnv_host.p;
-    for (int k = 0; k < 3; k++) HIPCHK(hipMemcpy(d + k * npix, bufs[k], npix * sizeof(float4), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d + 3 * npix, variance_host, npix * sizeof(float4), hipMemcpyHostToDevice));
-    const int rc = enqueue_denoise_var(s, width, height, d, d + npix, d + 2 * npix, d + 3 * npix, *params, d + 4 * npix,
-                                       var_out_host ? d + 5 * npix : nullptr, nullptr);
+    const int rc = check_denoise_var(s, width, height, bufs, variance_host, var_out_host, params);
     if (rc != RTMI_OK) return rc;
-    HIPCHK(hipMemcpy(out_host, d + 4 * npix, npix * sizeof(float4), hipMemcpyDeviceToHost));
-    if (var_out_host) HIPCHK(hipMemcpy(var_out_host, d + 5 * npix, npix * sizeof(float4), hipMemcpyDeviceToHost));
-    return RTMI_OK;
+    return denoise_host(s, width, height, bufs, variance_host, *params, out_host, var_out_host);
     RTMI_GUARD_END
 }
 
@@ -3419,7 +3392,7 @@ int rtmi_render_adaptive_denoised(rtmi_scene_t* s, const rtmi_viewport_t* vp, ui
     if (rc != RTMI_OK) return rc;
     rc = rtmi_variance_device(s, accum, sumsq, s->dnv_cnt.p, npix, var, nullptr);
     if (rc == RTMI_OK) rc = rtmi_render_features_device(s, vp, seed, &tile, 0u, ad->min_samples, alb, nrm, nullptr, nullptr, nullptr);
-    if (rc == RTMI_OK) rc = enqueue_denoise_var(s, vp->width, vp->height, color, alb, nrm, var, *params, res, nullptr, nullptr);
+    if (rc == RTMI_OK) rc = enqueue_atrous(s, vp->width, vp->height, color, alb, nrm, var, *params, res, nullptr, nullptr);
     if (rc != RTMI_OK) { if (stats) memset(stats, 0, sizeof(*stats)); return rc; }
     HIPCHK(hipMemcpy(out_host, res, npix * sizeof(float4), hipMemcpyDeviceToHost));
     if (counts_host) HIPCHK(hipMemcpy(counts_host, s->dnv_cnt.p, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));

@@ -673,6 +673,32 @@ class HipRayCaster:
             raise ValueError("no scene: pass scene=, or render with this caster first (the filter runs on a scene's device handle)")
         return s
 
+    @staticmethod
+    def _denoise_images(bufs, nin):
+        """The host images of denoise() / denoise_var(): bufs is [(name, array)], colour first, the outputs from index nin on;
+        an output of None is allocated.  Raises ValueError for an image that is not C-contiguous (H, W, 4) float32 of colour's
+        shape.  Returns (shape, the arrays, the name of the first output that shares memory with a buffer before it, or None)."""
+        color = bufs[0][1]
+        if not isinstance(color, np.ndarray) or color.ndim != 3 or color.shape[2] != 4 or color.shape[0] < 1 or color.shape[1] < 1:
+            raise ValueError("color must be a C-contiguous float32 array of shape (H, W, 4)")
+        shape = color.shape
+        arrays = [np.zeros(shape, np.float32) if a is None and k >= nin else a for k, (_, a) in enumerate(bufs)]
+        for (name, _), a in zip(bufs, arrays):
+            if not isinstance(a, np.ndarray) or a.dtype != np.float32 or not a.flags.c_contiguous or a.shape != shape:
+                raise ValueError(f"{name} must be a C-contiguous float32 array of shape {shape}")
+        shared = next((bufs[k][0] for k in range(nin, len(bufs)) if any(np.shares_memory(arrays[k], a) for a in arrays[:k])), None)
+        return shape, arrays, shared
+
+    @staticmethod
+    def _denoise_ptrs(w, h, ptrs, names):
+        """The device images of denoise_device() / denoise_var_device() as a list of int; all are required."""
+        if int(w) < 1 or int(h) < 1:
+            raise ValueError("w and h must be >= 1")
+        ptrs = [int(p or 0) for p in ptrs]
+        if not all(ptrs):
+            raise ValueError(f"{names} must all be given")
+        return ptrs
+
     def denoise(self, color, albedo, normal, out=None, scene=None, **params):
         """The feature-guided a-trous filter (rtmi_denoise; include/rtmi.h defines it) on host arrays: color as walk_rays
         writes it, albedo and normal as walk_rays_features returns them for the whole frame, all C-contiguous (H, W, 4)
@@ -681,15 +707,8 @@ class HipRayCaster:
         last worked on); the result does not depend on it.
         params: iterations, demodulate, sigma_color, sigma_normal, sigma_depth, sigma_albedo (denoise_params)."""
         d = self.denoise_params(**params)
-        if not isinstance(color, np.ndarray) or color.ndim != 3 or color.shape[2] != 4 or color.shape[0] < 1 or color.shape[1] < 1:
-            raise ValueError("color must be a C-contiguous float32 array of shape (H, W, 4)")
-        shape = color.shape
-        if out is None:
-            out = np.zeros(shape, np.float32)
-        for name, a in (("color", color), ("albedo", albedo), ("normal", normal), ("out", out)):
-            if not isinstance(a, np.ndarray) or a.dtype != np.float32 or not a.flags.c_contiguous or a.shape != shape:
-                raise ValueError(f"{name} must be a C-contiguous float32 array of shape {shape}")
-        if any(np.shares_memory(out, a) for a in (color, albedo, normal)):
+        shape, (_, _, _, out), shared = self._denoise_images([("color", color), ("albedo", albedo), ("normal", normal), ("out", out)], 3)
+        if shared:
             raise ValueError("out must not share memory with an input: the filter is never in place")
         s = self._denoise_scene(scene)
         self._config(s)
@@ -700,11 +719,7 @@ class HipRayCaster:
         """The same on device memory (rtmi_denoise_device): four images of w * h float4, one launch per iteration enqueued
         on HIP stream `stream`; nothing is synchronised and nothing crosses to the host."""
         d = self.denoise_params(**params)
-        if int(w) < 1 or int(h) < 1:
-            raise ValueError("w and h must be >= 1")
-        ptrs = [int(p or 0) for p in (color_ptr, albedo_ptr, normal_ptr, out_ptr)]
-        if not all(ptrs):
-            raise ValueError("color_ptr, albedo_ptr, normal_ptr and out_ptr must all be given")
+        ptrs = self._denoise_ptrs(w, h, (color_ptr, albedo_ptr, normal_ptr, out_ptr), "color_ptr, albedo_ptr, normal_ptr and out_ptr")
         if ptrs[3] in ptrs[:3]:
             raise ValueError("out_ptr must not be one of the inputs: the filter is never in place")
         s = self._denoise_scene(scene)
@@ -784,22 +799,13 @@ class HipRayCaster:
         params: iterations, demodulate, sigma_color (in standard deviations of the pixel), sigma_normal, sigma_depth,
         sigma_albedo (denoise_var_params)."""
         d = self.denoise_var_params(**params)
-        if not isinstance(color, np.ndarray) or color.ndim != 3 or color.shape[2] != 4 or color.shape[0] < 1 or color.shape[1] < 1:
-            raise ValueError("color must be a C-contiguous float32 array of shape (H, W, 4)")
-        shape = color.shape
-        if out is None:
-            out = np.zeros(shape, np.float32)
-        if var_out is True:
-            var_out = np.zeros(shape, np.float32)
         bufs = [("color", color), ("albedo", albedo), ("normal", normal), ("variance", variance), ("out", out)]
         if var_out is not None:
-            bufs.append(("var_out", var_out))
-        for name, a in bufs:
-            if not isinstance(a, np.ndarray) or a.dtype != np.float32 or not a.flags.c_contiguous or a.shape != shape:
-                raise ValueError(f"{name} must be a C-contiguous float32 array of shape {shape}")
-        for k in range(4, len(bufs)):
-            if any(np.shares_memory(bufs[k][1], bufs[j][1]) for j in range(k)):
-                raise ValueError(f"{bufs[k][0]} must not share memory with another buffer: the filter is never in place")
+            bufs.append(("var_out", None if var_out is True else var_out))
+        shape, arrays, shared = self._denoise_images(bufs, 4)
+        if shared:
+            raise ValueError(f"{shared} must not share memory with another buffer: the filter is never in place")
+        out, var_out = arrays[4], arrays[5] if var_out is not None else None
         s = self._denoise_scene(scene)
         self._config(s)
         _chk(_ffi.lib().rth_caster_denoise_var(s.h, shape[1], shape[0], _p(color), _p(albedo), _p(normal), _p(variance), C.byref(d),
@@ -811,11 +817,8 @@ class HipRayCaster:
         """The same on device memory (rtmi_denoise_var_device): images of w * h float4, one launch per iteration enqueued on
         HIP stream `stream`; nothing is synchronised and nothing crosses to the host.  var_out_ptr None/0: not produced."""
         d = self.denoise_var_params(**params)
-        if int(w) < 1 or int(h) < 1:
-            raise ValueError("w and h must be >= 1")
-        ptrs = [int(p or 0) for p in (color_ptr, albedo_ptr, normal_ptr, variance_ptr, out_ptr)]
-        if not all(ptrs):
-            raise ValueError("color_ptr, albedo_ptr, normal_ptr, variance_ptr and out_ptr must all be given")
+        ptrs = self._denoise_ptrs(w, h, (color_ptr, albedo_ptr, normal_ptr, variance_ptr, out_ptr),
+                                  "color_ptr, albedo_ptr, normal_ptr, variance_ptr and out_ptr")
         vo = int(var_out_ptr or 0)
         if ptrs[4] in ptrs[:4] or (vo and vo in ptrs):
             raise ValueError("out_ptr and var_out_ptr must not be another buffer of the call: the filter is never in place")

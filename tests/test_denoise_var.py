@@ -254,6 +254,48 @@ def test_device_variant_on_a_non_default_stream(caster, adaptive_64, iterations)
         assert torch.equal(t.view(torch.int32), k.view(torch.int32))
 
 
+@pytest.mark.parametrize("w,h", [(3, 200), (50, 37)])
+def test_staged_and_direct_taps_give_equal_bits_at_spacings_1_and_2(R, monkeypatch, w, h):
+    """Both filters, 2 iterations (tap spacings 1 and 2), on a handle that stages nothing through LDS (both *_LDS_STEP = 0:
+    every tap is global loads) and on one with the defaults (both spacings staged).  The sizes give partial tiles and halo
+    slots outside the image on every side.  The two handles must agree bit for bit, and with the restatements."""
+    import torch
+    handles = []
+    for lds in ("0", None):
+        for name in ("RTMI_DENOISE_LDS_STEP", "RTMI_DENOISE_VAR_LDS_STEP"):
+            if lds is None:
+                monkeypatch.delenv(name, raising=False)
+            else:
+                monkeypatch.setenv(name, lds)
+        sp = recipe_axis_box()(ProductApi(R))
+        c = R.HipRayCaster(seed=1)
+        c.upload(sp)  # the variables are read when the device handle is made
+        handles.append((c, sp))
+    imgs = _synthetic(h, w, 300 + w, poison=False)
+    assert (imgs[1][..., 3] == 0).any() and (imgs[1][..., 3] != 0).any()
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream().cuda_stream
+    ts = [torch.from_numpy(x).to(dev) for x in imgs]
+    names = ("plain filter", "variance-guided filter", "variance-guided filter: var_out")
+    for demodulate in (False, True):
+        fl = DR.DEMODULATE if demodulate else 0
+        want = (DR.denoise_ref(*imgs[:3], iterations=2, flags=fl),) + tuple(DV.denoise_var_ref(*imgs, iterations=2, flags=fl))
+        got = []
+        for c, sp in handles:
+            outs = [torch.full(imgs[0].shape, float("nan"), dtype=torch.float32, device=dev) for _ in range(3)]
+            c.denoise_device(w, h, *[t.data_ptr() for t in ts[:3]], outs[0].data_ptr(), stream=st, scene=sp, iterations=2,
+                             demodulate=demodulate)
+            c.denoise_var_device(w, h, *[t.data_ptr() for t in ts], outs[1].data_ptr(), var_out_ptr=outs[2].data_ptr(), stream=st,
+                                 scene=sp, iterations=2, demodulate=demodulate)
+            torch.cuda.synchronize()
+            got.append([t.cpu().numpy() for t in outs])
+        for direct, staged, ref, name in zip(got[0], got[1], want, names):
+            what = f"{w}x{h}, demodulate={demodulate}, {name}"
+            assert_bits_equal(direct, staged, what + ": direct vs staged")
+            assert_bits_equal(staged, ref, what + ": staged vs the restatement")
+            assert_bits_equal(direct, ref, what + ": direct vs the restatement")
+
+
 @pytest.mark.parametrize("kw", [dict(), dict(iterations=4, demodulate=True, sigma_color=2.0)])
 def test_walk_rays_adaptive_denoised_equals_the_four_calls(R, caster, scene, adaptive_64, kw):
     f = adaptive_64
