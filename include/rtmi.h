@@ -92,6 +92,7 @@ typedef struct rtmi_stats {
                              * it also traces the mirror reflections of primary hits in place:
                              * RTMI_MIRROR_INPLACE)                                            */
     double bounce_ms;       /* the bounce passes' closest-hit launches (k_trace_oct)                               */
+    /* (rtmi_render_ao*: primary_ms = the primary rays' closest-hit launches, bounce_ms = the AO rays' walk launches)     */
     int32_t peer_access;    /* 1 = this device writes the root device's memory directly (peer access enabled, or the
                              * same device); 0 = the runtime refused: the band is staged (rtmi_last_error() carries a
                              * warning although the call returns RTMI_OK)                                      */
@@ -530,12 +531,64 @@ int rtmi_trace(rtmi_scene_t* scene, uint64_t n, const float* orig4, const float*
  * n == 0: RTMI_OK, nothing is touched (checked after the scene, before the buffers).  RTMI_ERR_INVALID, before any HIP call
  * and before the scene is used: a NULL scene, orig4, dir4 or occluded; an output that overlaps an input (as byte ranges of 16 n,
  * 16 n, 4 n and n bytes).  RTMI_ERR_UNSUPPORTED: n >= 2^31, as for rtmi_trace.  stats come back cleared on failure.
- * Not here: shadow rays in shading, an ambient-occlusion buffer, occlusion for batches of views and for
- * rtmi_render_frame_multi. */
+ * Not here: shadow rays in shading, occlusion for batches of views and for rtmi_render_frame_multi.  (The
+ * ambient-occlusion buffer is rtmi_render_ao*, below.) */
 int rtmi_occluded(rtmi_scene_t* scene, uint64_t n, const float* orig4, const float* dir4, const float* tmax /* n floats or NULL */,
                   uint8_t* occluded, rtmi_stats_t* stats);
 int rtmi_occluded_device(rtmi_scene_t* scene, uint64_t n, const void* orig4_device, const void* dir4_device,
                          const void* tmax_device /* or NULL */, void* occluded_device, void* hip_stream, rtmi_stats_t* stats);
+
+/* Ambient occlusion rendered on the device: one f32 per pixel, the share of K hemisphere rays per primary
+ * sample that reach `radius` unoccluded -- a shaded preview, a contact-shadow layer, a guide image.  NOT part of the reference,
+ * which has no AO: build-defined like the denoiser, so what follows IS the definition, and tests/ao_ref.py pins it bit for bit.
+ * Primary rays: exactly those of rtmi_render_features_device for the same (vp, seed, tile, sample0, nsamples): RNG block 0,
+ * jittered iff S = vp->samples_per_pixel != 1, vp->maxdepth not consulted, and (tri, t, face) of a ray is what rtmi_trace
+ * returns for it under the handle's current options.
+ * Per sample s of pixel p (p = row * width + col of the image, the renderer's RNG key), with (ro, rd) the primary ray:
+ *   a miss (tri == 0) contributes K visible rays;
+ *   a hit, edge faces included:  n = the triangle's norm, * (-1.f) when face & 1 (the features call's normal);
+ *                                point = rd * t + ro   (a multiplication, then an addition, all four lanes, no contraction);
+ *   for k = 0 .. K-1:  rv   = random_vec (raytrace.rs:188-192) from RNG block 0x80000000 | k of (seed, p, s): three uniforms
+ *                             - 0.5f, made a unit vector.  The block range is disjoint from a path's own blocks 0 .. maxdepth;
+ *                      orig = point + n * bias;
+ *                      dir  = unit(n + rv): lambertian_ray's direction (raytrace.rs:292-297) with one normalisation, unit(v)
+ *                             = v * (1.f / sqrt(ordered dot)) as everywhere (raytrace.rs:93-96);
+ *                      the ray is visible iff rtmi_occluded's definition gives 0 for (orig, dir, tmax = radius) on this handle.
+ *   No case is special: a non-finite t produces whatever rays the arithmetic gives, and their answers are rtmi_occluded's.
+ * The offset is along n, not along rv as lambertian_ray's is: with rv, 59 % of the AO rays of the canonical view re-hit the
+ * surface they left (a flat open surface would read 0.5); with n, 11.7 % are occluded and none by its own triangle
+ * (DESIGN.md 4.15 has the measurement).
+ * Result: ao[p] = (float)visible * (1.f / (float)(nsamples * K)), visible = the number of visible rays over the pixel's
+ * samples.  Every term is 0 or 1 and nsamples * K < 2^24, so the value does not depend on any order of summation.  A pixel
+ * whose samples all missed reads 1.0.  Layout: the tile's, as rtmi_render_tile_device, one f32 per pixel.
+ * Scenes: octree, linear list, generic tree and RTMI_OPT_GENERIC; RTMI_OPT_FAST / RTMI_OPT_BVH give their own modes' hits and
+ * answers.  RTMI_ERR_UNSUPPORTED for a scene with analytic spheres, as for features, and for nsamples * rays >= 2^24.
+ * RTMI_ERR_INVALID, before any HIP call and before the scene is used, stats cleared: a NULL scene, viewport, tile, ao or
+ * output; rays 0 or above 256; non-zero flags; radius NaN or below 0; bias NaN or infinite; nsamples == 0; sample0 + nsamples
+ * > S; every viewport and tile check of the features call.  An empty tile returns RTMI_OK and touches nothing.
+ * stats: rays = pixels * nsamples + (samples that hit) * K; kernel_ms, streams, pipeline = 1 as for features; trace_launches
+ * and trace_ms cover the primary closest-hit launches (their share: primary_ms) and the AO rays' walk launches (bounce_ms).
+ * With RTMI_OPT_COUNTERS the five work counters are the primaries' closest-hit work plus the any-hit walk's actual work.
+ * How: per batch, on one library stream, the features call's primary pass; k_ao_rays compacts the paths that hit and writes
+ * their K rays (a sample that missed costs no walk); the ray count stays on the device; the scene's any-hit walk (or its
+ * closest-hit launch, where rtmi_occluded uses that); k_ao_resolve counts per pixel.  The AO ray queue (37 B per ray at most)
+ * lives on the handle, grows on demand and is freed by rtmi_scene_destroy; a batch holds at most batch_paths AO rays.  No
+ * tuning changes a bit of the result.  The device variant enqueues on hip_stream like rtmi_render_tile_device; the host variant
+ * renders rows [row0, row0 + nrows) and copies 4 B per pixel out.
+ * Not here: AO for batches of views and for rtmi_render_frame_multi, AO as a guide of the denoisers, cosine-weighted or
+ * otherwise importance-sampled variants. */
+typedef struct rtmi_ao {
+    uint32_t rays;    /* K: AO rays per primary sample that hits, 1..256 */
+    uint32_t flags;   /* must be 0 */
+    float radius;     /* tmax of every AO ray; +inf = unlimited; 0 is valid (nothing occludes) */
+    float bias;       /* origin offset along the shading normal */
+} rtmi_ao_t;
+void rtmi_ao_defaults(rtmi_ao_t* ao);  /* rays 4, flags 0, radius +inf, bias 0.001f (the reference's bounce offset, raytrace.rs:284-296) */
+int rtmi_render_ao_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile,
+                          uint32_t sample0, uint32_t nsamples, const rtmi_ao_t* ao, void* ao_device, void* hip_stream,
+                          rtmi_stats_t* stats);
+int rtmi_render_ao(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
+                   uint32_t sample0, uint32_t nsamples, const rtmi_ao_t* ao, float* ao_host, rtmi_stats_t* stats);
 
 /* Per-ray debug records (the reference's Scene { debug_ctx, debug_en }, raytrace.rs:1297-1303, debug.rs): what the
  * octree walk did for each ray, taken from the production walk itself (k_trace_record: the walk of rtmi_trace in a

@@ -123,6 +123,15 @@ int rth_caster_occluded(rth_scene_t* s, uint64_t n, const float* orig4, const fl
                         rtmi_stats_t* stats);
 int rth_caster_occluded_device(rth_scene_t* s, uint64_t n, const void* orig4_device, const void* dir4_device,
                                const void* tmax_device, void* occluded_device, void* hip_stream, rtmi_stats_t* stats);
+/* Ambient occlusion (rtmi_render_ao / rtmi_render_ao_device in rtmi.h, which defines it): one f32 per pixel, the share of
+ * ao->rays hemisphere rays per primary sample of [sample0, sample0 + nsamples) that are not occluded within ao->radius.
+ * maxdepth is not consulted; the primary rays use the caster's seed. */
+int rth_caster_walk_ao(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp, uint64_t row0,
+                       uint64_t nrows, uint32_t sample0, uint32_t nsamples, const rtmi_ao_t* ao, float* ao_host,
+                       rtmi_stats_t* stats, double* wall_seconds);
+int rth_caster_walk_ao_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                              const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, const rtmi_ao_t* ao, void* ao_device,
+                              void* hip_stream, rtmi_stats_t* stats, double* wall_seconds);
 /* Per-ray records (rtmi_trace_records / rtmi_primary_records, same buffers and size-query idiom) on the scene's
  * resident copy; the primary records use the caster's seed. */
 int rth_caster_trace_records(rth_scene_t* s, uint64_t n, const float* orig4, const float* dir4, rtmi_ray_record_t* recs,

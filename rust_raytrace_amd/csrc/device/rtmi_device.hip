@@ -47,6 +47,7 @@ static_assert(sizeof(rtmi_stats_t) == 128 && sizeof(rtmi_tuning_t) == 48 && size
               sizeof(rtmi_ray_record_t) == 72, "ABI struct layout changed");
 static_assert(sizeof(rtmi_adaptive_t) == 32 && offsetof(rtmi_adaptive_t, samples) == 24, "ABI struct layout changed");
 static_assert(sizeof(rtmi_denoise_t) == 24 && offsetof(rtmi_denoise_t, sigma_color) == 8, "ABI struct layout changed");
+static_assert(sizeof(rtmi_ao_t) == 16 && offsetof(rtmi_ao_t, radius) == 8, "ABI struct layout changed");
 
 namespace rtmi {
 
@@ -375,6 +376,7 @@ __global__ void __launch_bounds__(256) k_trace(DScene sc, const float4* __restri
 #include "trace_oct.hpp"
 #include "bvh_fast.hpp"
 #include "denoise.hpp"
+#include "ao.hpp"
 namespace rtmi {
 
 
@@ -1066,6 +1068,16 @@ struct rtmi_scene {
     uint32_t dnv_lds_max_step = DN_LDS_MAX_STEP;  // as dn_lds_max_step, for the variance-guided filter (RTMI_DENOISE_VAR_LDS_STEP=0|1|2)
     DevBuf<float> occ_tmax;          // rtmi_occluded (host variant): the limits and the answers on the device
     DevBuf<uint8_t> occ_out;
+    // rtmi_render_ao*: per stream, the AO ray queue of a batch (origins, directions, limits), each path's first queue entry
+    // and the answer bytes (grow only); the image of the host variant.  No other call reads or writes them.
+    struct AoBuf {
+        DevBuf<float4> qo, qd;
+        DevBuf<float> tmax;
+        DevBuf<uint32_t> slot;
+        DevBuf<uint8_t> occ;
+        void release() { qo.release(); qd.release(); tmax.release(); slot.release(); occ.release(); }
+    } ao[RTMI_MAX_STREAMS];
+    DevBuf<float> ao_out;
     DevBuf<uint8_t> mstage, mframe;  // rtmi_render_frame_multi, root scene: received bands / the frame
     hipStream_t mstream = nullptr;   // rtmi_render_frame_multi: this scene's band stream
     std::vector<ncclComm_t> comms;   // root scene, RTMI_FRAME_RCCL: one communicator per scene of the last device list
@@ -1508,6 +1520,8 @@ int rtmi_scene_destroy(rtmi_scene_t* s) {
     s->vcams.release(); s->dn_scratch.release(); s->dn_host.release();
     s->dnv_scratch.release(); s->dnv_host.release(); s->dnv_cnt.release();
     s->occ_tmax.release(); s->occ_out.release();
+    for (auto& a : s->ao) a.release();
+    s->ao_out.release();
     if (s->vcams_ev) (void)hipEventDestroy(s->vcams_ev);
     if (s->mstream) (void)hipStreamDestroy(s->mstream);
     if (!s->comms.empty()) { if (Rccl* r = rccl_api()) for (ncclComm_t c : s->comms) (void)r->CommDestroy(c); }
@@ -1678,6 +1692,39 @@ static void launch_trace(rtmi_scene* s, Work& w, hipStream_t st, const float4* q
     if (s->d.nspheres)  // analytic spheres: a flat list against every ray, after the tree (not part of the timed trace kernel)
         hipLaunchKernelGGL(k_trace_spheres, dim3((unsigned)(s->num_cu * 8)), dim3(256), 0, st, s->d, qo, qd, w.ctrl.p, pass, w.hit_tf.p, w.hit_t.p);
 }
+// rtmi_occluded*'s scene dispatch.  An exact octree and the linear list have any-hit kernels; everything else (generic tree,
+// RTMI_OPT_GENERIC, BVH mode, analytic spheres) runs its closest-hit launch of rtmi_trace followed by an elementwise kernel.
+static bool occluded_anyhit(const rtmi_scene* s) {
+    const bool bvh = (s->options & RTMI_OPT_BVH) && s->bvh_ok, generic = (s->options & RTMI_OPT_GENERIC) != 0;
+    return !bvh && !generic && s->d.nspheres == 0 && (s->root_is_leaf || s->octree) && !s->occl_from_hits;
+}
+// The any-hit walk of queue `pass` of the stream's control block (ctrl->count[pass] rays, set on the stream before this):
+// rays qo / qd, limits tmax (null: +inf), one byte per ray to occ.  pass 0 with n rays: rtmi_occluded*.  pass 1: the AO rays
+// of rtmi_render_ao*, whose count exists on the device only; n is then an upper bound (the closest-hit fallback writes the
+// workspace's hit records, sized for it).  `stop` is recorded right after the walk kernel.
+static void launch_occluded(rtmi_scene* s, Work& w, hipStream_t st, uint64_t n, const float4* qo, const float4* qd, const float* tmax,
+                            uint8_t* occ, int pass, hipEvent_t stop) {
+    const bool count = (s->options & RTMI_OPT_COUNTERS) != 0;
+    if (!occluded_anyhit(s)) {
+        launch_trace(s, w, st, qo, qd, pass, count, stop);
+        const unsigned grid = (unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)s->num_cu * 8);
+        if (pass == 0)
+            hipLaunchKernelGGL(k_occl_from_hits, dim3(grid), dim3(256), 0, st, (uint32_t)n, w.hit_tf.p, w.hit_t.p, tmax, occ);
+        else
+            hipLaunchKernelGGL(k_ao_occl_from_hits, dim3(grid), dim3(256), 0, st, w.ctrl.p, pass, w.hit_tf.p, w.hit_t.p, tmax, occ);
+    } else if (s->root_is_leaf) {
+        hipLaunchKernelGGL(count ? k_occluded_linear<true> : k_occluded_linear<false>, dim3((unsigned)(s->num_cu * 8)), dim3(256), 0, st, s->d,
+                           qo, qd, w.ctrl.p, pass, tmax, occ);
+        (void)hipEventRecord(stop, st);
+    } else {
+        OctArgs a{};
+        a.qo = qo; a.qd = qd; a.pass = pass;
+        a.vote_s = s->vote[0]; a.vote_l = s->vote[1];
+        hipLaunchKernelGGL(occluded_oct_variant[count][(s->options & RTMI_OPT_FAST) != 0], oct_grid(s), dim3(64), oct_launch_lds(s, count), st,
+                           s->d, a, w.ctrl.p, (int)s->tune.refill_min0, (int)(s->tune.xcd_aware % 3u), OcclArgs{tmax, occ});
+        (void)hipEventRecord(stop, st);
+    }
+}
 // where a stream's zero-component rays go; cap 0 (tuning slow_path = 0... or the queue not allocated) keeps them in place
 static SlowQ slow_queue(rtmi_scene* s, Work& w) {
     const bool on = s->tune.slow_path_off == 0u && w.sqo.p && w.sstream;
@@ -1756,6 +1803,8 @@ struct SubTile {
 struct ListPass { const uint32_t* list; uint32_t n; float4* sumsq; uint32_t* counts; };
 // The outputs of a features call (rtmi_render_features*): one float4 / float4 / uint32 per pixel of the tile, each may be null
 struct FeatOut { float4* albedo; float4* normal; uint32_t* ids; };
+// An ambient-occlusion call (rtmi_render_ao*): its parameters and its output, one f32 per pixel of the tile
+struct AoCall { rtmi_ao_t p; float* out; };
 // One render_tile call: what it renders, and its plan (plan_tile)
 struct TileCall {
     uint64_t seed;
@@ -1763,8 +1812,9 @@ struct TileCall {
     float4 *accum, *out;
     const ListPass* lp;
     const FeatOut* fo;  // a features call: the primary pass alone (maxdepth = 1, per-pass pipeline), k_features for k_shade + k_accum
+    const AoCall* ao;   // an AO call: a features call's primary pass, then k_ao_rays, the any-hit walk of queue 1 and k_ao_resolve
     ViewTab vt;  // VIEWS: the view table (cams == nullptr otherwise)
-    Samp mode;  // LIST with lp, PASS with accum or fo, VIEWS with vt.cams, FRAME otherwise
+    Samp mode;  // LIST with lp, PASS with accum, fo or ao, VIEWS with vt.cams, FRAME otherwise
     bool counting, path_kernels;
     uint32_t nsub;
     uint64_t pix_per_batch, max_npix;  // max_npix: pixels of the largest sub-tile
@@ -1775,6 +1825,7 @@ struct TileSums {
     rtmi_stats_t counters{};
     float trace_ms = 0.f, primary_ms = 0.f, bounce_ms = 0.f;
     uint32_t launches = 0;
+    uint64_t ao_hits = 0;  // AO calls: samples whose primary ray hit
 };
 
 // Checks of a render call's viewport and tile (nrows >= 1), before any HIP call
@@ -1803,7 +1854,7 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
     // path kernels (pipeline 3; 0 = automatic): exact-octree scenes get pass 0 from k_path_primary, which generates, traces and
     // shades the primary rays in one kernel.  Everything else (pipeline 1, linear list, generic tree, BVH mode,
     // analytic spheres) starts with k_gen.  Both then run one closest-hit + one shading launch per bounce pass.
-    c.path_kernels = !c.fo && s->tune.pipeline != 1u && s->octree && !s->root_is_leaf &&
+    c.path_kernels = !c.fo && !c.ao && s->tune.pipeline != 1u && s->octree && !s->root_is_leaf &&
                      !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) && s->d.nspheres == 0;
     // streams = 0 (automatic): one stream for path-kernel tiles of 2^26 paths and more, three otherwise (the per-pass
     // pipelines -- BVH mode: 29.6 ms on three streams, 35.2 on one -- have elementwise kernels to hide).  Since k_shade stopped being
@@ -1818,7 +1869,8 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
     // sub-tile's k_features waits for wave slots behind the other sub-tiles' persistent k_trace_oct launches (config 3's frame
     // of 2^28 paths: 108.0 and 111.0 ms on one stream in two jobs, 113.9 and 113.7 on three; 2^25 paths: 16.4 and 16.3 against
     // 17.5 and 17.3).
-    const uint32_t auto_streams = (c.fo || (c.path_kernels && npix_call * spp >= (1ull << 26)) || (lp && npix_call < npix)) ? 1u : 3u;
+    // AO calls (c.ao): as features calls.
+    const uint32_t auto_streams = (c.fo || c.ao || (c.path_kernels && npix_call * spp >= (1ull << 26)) || (lp && npix_call < npix)) ? 1u : 3u;
     uint32_t nsub = std::min<uint32_t>(s->tune.streams ? s->tune.streams : auto_streams, (uint32_t)RTMI_MAX_STREAMS);
     nsub = (uint32_t)std::min<uint64_t>(nsub, lp ? npix_call : nrows);
     if (npix_call * spp < s->tune.subtile_min_paths) nsub = 1;
@@ -1842,9 +1894,11 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
         }
     }
 
-    // batch = whole pixels with all their samples
+    // batch = whole pixels with all their samples; an AO call counts a path as its K AO rays, so that the AO queue of a
+    // batch stays within batch_paths entries and below the walk's 2^31
     const size_t want_paths = (size_t)std::max<uint64_t>(s->tune.batch_paths, 1) / nsub;
-    uint64_t pix_per_batch = std::max<uint64_t>(1, want_paths / spp);
+    const uint64_t per_pix = (uint64_t)spp * (c.ao ? c.ao->p.rays : 1u);
+    uint64_t pix_per_batch = std::max<uint64_t>(1, want_paths / per_pix);
     uint64_t max_sub_npix = 0;
     for (uint32_t t = 0; t < nsub; t++) max_sub_npix = std::max(max_sub_npix, c.sub[t].npix);
     // equal batches: a sub-tile a little larger than the budget (thirds of a frame whose stripes do not divide evenly)
@@ -1854,13 +1908,21 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
         pix_per_batch = max_sub_npix * 8 <= pix_per_batch * 9 ? max_sub_npix : (max_sub_npix + nb - 1) / nb;
     }
     pix_per_batch = std::min<uint64_t>(pix_per_batch, max_sub_npix);
-    if (pix_per_batch * spp >= (1ull << 31)) return fail(RTMI_ERR_UNSUPPORTED, "batch above 2^31 paths");
+    if (pix_per_batch * per_pix >= (1ull << 31)) return fail(RTMI_ERR_UNSUPPORTED, "batch above 2^31 paths");
     c.pix_per_batch = pix_per_batch;
     c.max_npix = max_sub_npix;
     for (uint32_t t = 0; t < nsub; t++) {
         if (c.sub[t].npix == 0) continue;
-        int rc = ensure_workspace(s->w[t], (size_t)(std::min<uint64_t>(pix_per_batch, c.sub[t].npix) * spp), c.maxdepth);
+        const size_t paths = (size_t)(std::min<uint64_t>(pix_per_batch, c.sub[t].npix) * spp);
+        // an AO call on a scene without an any-hit kernel: the closest-hit launch of the AO rays writes the workspace's hit records
+        const size_t nao = c.ao ? paths * c.ao->p.rays : 0;
+        int rc = ensure_workspace(s->w[t], c.ao && !occluded_anyhit(s) ? nao : paths, c.maxdepth);
         if (rc != RTMI_OK) return rc;
+        if (c.ao) {
+            rtmi_scene::AoBuf& a = s->ao[t];
+            HIPCHK(a.qo.ensure(nao)); HIPCHK(a.qd.ensure(nao)); HIPCHK(a.occ.ensure(nao)); HIPCHK(a.slot.ensure(paths));
+            if (!std::isinf(c.ao->p.radius)) HIPCHK(a.tmax.ensure(nao));
+        }
     }
     return RTMI_OK;
 }
@@ -1935,6 +1997,25 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
         HIPCHK(hipGetLastError());
         return RTMI_OK;
     }
+    if (c.ao) {  // the primary rays' closest hits, K AO rays per hit compacted into queue 1, their any-hit walk, the per-pixel counts
+        const rtmi_ao_t& p = c.ao->p;
+        rtmi_scene::AoBuf& a = s->ao[t];
+        float* tmax = std::isinf(p.radius) ? nullptr : a.tmax.p;  // +inf: the walk's NULL tmax
+        HIPCHK(hipEventRecord(w.pass_ev[0], st));
+        launch_trace(s, w, st, w.qo[0].p, w.qd[0].p, 0, c.counting, w.pass_ev[1]);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_ao_rays, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, p.rays, make_fastdiv(p.rays), p.radius, p.bias,
+                           w.qo[0].p, w.qd[0].p, w.hit_tf.p, w.hit_t.p, a.qo.p, a.qd.p, tmax, a.slot.p, w.ctrl.p);
+        hipLaunchKernelGGL(k_ao_count, dim3(1), dim3(1), 0, st, w.ctrl.p, p.rays);
+        HIPCHK(hipEventRecord(w.pass_ev[2], st));
+        launch_occluded(s, w, st, (uint64_t)npaths * p.rays, a.qo.p, a.qd.p, tmax, a.occ.p, 1, w.pass_ev[3]);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_ao_resolve, ew_grid, ew_block, 0, st, np, c.spp, p.rays, make_fastdiv(p.rays), a.slot.p, a.occ.p, c.ao->out, pix0,
+                           c.W, c.nsub, t, make_fastdiv(c.W));
+        HIPCHK(hipEventRecord(w.ev[1], st));
+        HIPCHK(hipGetLastError());
+        return RTMI_OK;
+    }
     for (uint32_t pass = pass0; pass < c.maxdepth; pass++) {
         const int a = pass & 1, b = a ^ 1;
         HIPCHK(hipEventRecord(w.pass_ev[2 * pass], st));
@@ -1997,7 +2078,17 @@ static int collect_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
         sum.launches++;
         sum.trace_ms += pm;
         if (c.path_kernels) { if (pass == 0) sum.primary_ms += pm; else sum.bounce_ms += pm; }
+        if (c.ao) sum.primary_ms += pm;
         if (s->verbose) fprintf(stderr, "[rtmi] stream %u batch@%llu pass %u: %u rays, trace %.3f ms, %.1f Mrays/s\n", t, (unsigned long long)p0, pass, h.count[pass], pm, h.count[pass] / (pm * 1e3));
+    }
+    if (c.ao) {  // the AO rays' walk: queue 1
+        float pm = 0.f;
+        HIPCHK(hipEventElapsedTime(&pm, w.pass_ev[2], w.pass_ev[3]));
+        sum.launches++;
+        sum.trace_ms += pm;
+        sum.bounce_ms += pm;
+        sum.ao_hits += h.count[RTMI_AO_HITS];
+        if (s->verbose) fprintf(stderr, "[rtmi] stream %u batch@%llu AO: %u rays, walk %.3f ms, %.1f Mrays/s\n", t, (unsigned long long)p0, h.count[1], pm, h.count[1] / (pm * 1e3));
     }
     return RTMI_OK;
 }
@@ -2010,18 +2101,21 @@ static int collect_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
 // contiguous chunks of the list.  Batches and automatic streams are then sized from lp->n * nsamples.
 // fo != nullptr (no accum, no out_device; the caller passes maxdepth = 1): a features call (rtmi_render_features_device).  Its
 // batches run k_gen_samples, the scene's closest-hit launch and k_features, which writes fo's buffers.
+// ao != nullptr (no accum, no out_device; maxdepth = 1 likewise): an ambient-occlusion call (rtmi_render_ao_device).  Its
+// batches run a features call's primary pass, k_ao_rays, the scene's any-hit walk of the compacted AO rays and k_ao_resolve,
+// which writes ao->out.  A batch is sized so that its AO rays (paths * K at most) stay within batch_paths.
 // views > 0 (no accum): a batch of views (Samp::VIEWS, rtmi_render_views_device); vp is the stacked image (height = views *
 // the views' height) and s->hvcams holds the view table, uploaded here on hip_stream before the internal streams fork.
 static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile, uint32_t sample0,
                        uint32_t nsamples, float4* accum, void* out_device, void* hip_stream, rtmi_stats_t* stats,
-                       const ListPass* lp = nullptr, uint32_t views = 0, const FeatOut* fo = nullptr) {
+                       const ListPass* lp = nullptr, uint32_t views = 0, const FeatOut* fo = nullptr, const AoCall* ao = nullptr) {
     if (stats) memset(stats, 0, sizeof(*stats));
     if (tile->nrows == 0) return RTMI_OK;
     RTMI_GUARD_BEGIN
     // leftovers of the caller's own HIP calls on this thread (or of failures this library tolerated, e.g. an occupancy
     // query) must not make a launch below look refused: hipGetLastError() reports the last error of ANY runtime call
     (void)hipGetLastError();
-    if (!out_device && !accum && !fo) return fail(RTMI_ERR_INVALID, "NULL argument");
+    if (!out_device && !accum && !fo && !ao) return fail(RTMI_ERR_INVALID, "NULL argument");
     int rc = check_view(vp, tile);
     if (rc != RTMI_OK) return rc;
     HIPCHK(hipSetDevice(s->device));
@@ -2036,8 +2130,8 @@ static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed
     }
     TileCall c;
     c.seed = seed; c.sample0 = sample0; c.spp = nsamples; c.maxdepth = vp->maxdepth; c.W = vp->width;
-    c.accum = accum; c.out = out; c.lp = lp; c.fo = fo; c.vt = ViewTab{nullptr, FastDiv{}};
-    c.mode = lp ? Samp::LIST : (accum || fo) ? Samp::PASS : views ? Samp::VIEWS : Samp::FRAME;
+    c.accum = accum; c.out = out; c.lp = lp; c.fo = fo; c.ao = ao; c.vt = ViewTab{nullptr, FastDiv{}};
+    c.mode = lp ? Samp::LIST : (accum || fo || ao) ? Samp::PASS : views ? Samp::VIEWS : Samp::FRAME;
     c.counting = (s->options & RTMI_OPT_COUNTERS) != 0;
     rc = plan_tile(s, vp, tile, c);
     if (rc != RTMI_OK) return rc;
@@ -2076,6 +2170,7 @@ static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed
         stats->kernel_ms = kernel_ms; stats->trace_ms = sum.trace_ms; stats->trace_launches = sum.launches; stats->streams = c.nsub;
         stats->primary_ms = sum.primary_ms; stats->bounce_ms = sum.bounce_ms; stats->pipeline = c.path_kernels ? 3u : 1u;
     }
+    if (s->verbose && ao) fprintf(stderr, "[rtmi] AO: %llu of %llu samples hit\n", (unsigned long long)sum.ao_hits, (unsigned long long)tile->nrows * c.W * nsamples);
     return RTMI_OK;
     RTMI_GUARD_END
 }
@@ -2191,6 +2286,73 @@ int rtmi_render_features(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t se
     if (albedo_host) HIPCHK(hipMemcpy(albedo_host, fo.albedo, npix * sizeof(float4), hipMemcpyDeviceToHost));
     if (normal_host) HIPCHK(hipMemcpy(normal_host, fo.normal, npix * sizeof(float4), hipMemcpyDeviceToHost));
     if (ids_host) HIPCHK(hipMemcpy(ids_host, fo.ids, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+// ---------------------------------------------------------------- ambient occlusion (rtmi_render_ao*)
+void rtmi_ao_defaults(rtmi_ao_t* p) {
+    if (!p) return;
+    p->rays = 4; p->flags = 0; p->radius = INFINITY;
+    p->bias = 0.001f;  // the reference's bounce offset (raytrace.rs:284-296)
+}
+
+// Checks of the AO entry points that come before any HIP call and before the scene is used (a CPU-only caller reaches them).
+// RTMI_OK with *empty set: the tile has no rows, nothing to do.  v1 receives the viewport with maxdepth = 1, as for features.
+static int check_ao(rtmi_scene_t* s, const rtmi_viewport_t* vp, const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples,
+                    const rtmi_ao_t* ao, const void* out, rtmi_viewport_t& v1, bool* empty) {
+    *empty = false;
+    if (!s || !vp) return fail(RTMI_ERR_INVALID, "ao: NULL argument (scene or viewport)");
+    if (!tile) return fail(RTMI_ERR_INVALID, "ao: NULL argument (tile)");
+    if (!ao) return fail(RTMI_ERR_INVALID, "ao: NULL argument (rtmi_ao_t)");
+    if (!out) return fail(RTMI_ERR_INVALID, "ao: NULL argument (output)");
+    if (ao->rays == 0 || ao->rays > 256) return fail(RTMI_ERR_INVALID, "ao: rays must be in [1, 256]");
+    if (ao->flags != 0) return fail(RTMI_ERR_INVALID, "ao: flags must be 0");
+    if (!(ao->radius >= 0.f)) return fail(RTMI_ERR_INVALID, "ao: radius must be >= 0 (+inf: unlimited) and not NaN");
+    if (!std::isfinite(ao->bias)) return fail(RTMI_ERR_INVALID, "ao: bias must be finite");
+    if (vp->samples_per_pixel == 0) return fail(RTMI_ERR_INVALID, "samples_per_pixel must be >= 1");
+    if (nsamples == 0) return fail(RTMI_ERR_INVALID, "nsamples must be >= 1");
+    if ((uint64_t)sample0 + nsamples > vp->samples_per_pixel)
+        return fail(RTMI_ERR_INVALID, "samples [sample0, sample0 + nsamples) outside the frame's samples_per_pixel");
+    if (sample0 & RTMI_KEY_JITTER) return fail(RTMI_ERR_UNSUPPORTED, "sample0 above 2^31");  // DView::sample_key
+    if ((uint64_t)nsamples * ao->rays >= (1ull << 24))
+        return fail(RTMI_ERR_UNSUPPORTED, "ao: nsamples * rays must stay below 2^24 (the per-pixel count is exact in f32)");
+    if (tile->nrows == 0) { *empty = true; return RTMI_OK; }
+    v1 = *vp;
+    v1.maxdepth = 1;
+    return check_view(&v1, tile);
+}
+
+int rtmi_render_ao_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile, uint32_t sample0,
+                          uint32_t nsamples, const rtmi_ao_t* ao, void* ao_device, void* hip_stream, rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    rtmi_viewport_t v1;
+    bool empty;
+    const int rc = check_ao(s, vp, tile, sample0, nsamples, ao, ao_device, v1, &empty);
+    if (rc != RTMI_OK || empty) return rc;
+    if (s->d.nspheres)
+        return fail(RTMI_ERR_UNSUPPORTED, "ao: the scene has analytic spheres (a build-defined primitive whose normal needs the hit point)");
+    const AoCall call{*ao, (float*)ao_device};
+    return render_tile(s, &v1, seed, tile, sample0, nsamples, nullptr, nullptr, hip_stream, stats, nullptr, 0, nullptr, &call);
+}
+
+// Host variant: the image is rendered into the handle's own device buffer and copied out once (4 B per pixel).
+int rtmi_render_ao(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows, uint32_t sample0,
+                   uint32_t nsamples, const rtmi_ao_t* ao, float* ao_host, rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    const rtmi_tile_t tile{row0, nrows, nrows ? nrows : 1u, 0u};
+    rtmi_viewport_t v1;
+    bool empty;
+    const int rc0 = check_ao(s, vp, &tile, sample0, nsamples, ao, ao_host, v1, &empty);
+    if (rc0 != RTMI_OK || empty) return rc0;
+    if (s->d.nspheres)
+        return fail(RTMI_ERR_UNSUPPORTED, "ao: the scene has analytic spheres (a build-defined primitive whose normal needs the hit point)");
+    const uint64_t npix = (uint64_t)nrows * vp->width;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(s->ao_out.ensure(npix));
+    const AoCall call{*ao, s->ao_out.p};
+    const int rc = render_tile(s, &v1, seed, &tile, sample0, nsamples, nullptr, nullptr, nullptr, stats, nullptr, 0, nullptr, &call);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(hipMemcpy(ao_host, s->ao_out.p, npix * sizeof(float), hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
 
@@ -2667,38 +2829,19 @@ static int check_occluded(const rtmi_scene_t* s, uint64_t n, const void* orig4, 
     return RTMI_OK;
 }
 
-// The rays (device memory) -> one byte per ray, on stream st with ctrl->count[0] = n set there.  An exact octree and the
-// linear list run their any-hit kernels; everything else (generic tree, BVH mode, analytic spheres) its closest-hit launch
-// of rtmi_trace followed by k_occl_from_hits.  w.ev[0] / w.ev[1] bracket the walk kernel, as in rtmi_trace.
+// The rays (device memory) -> one byte per ray, on stream st with ctrl->count[0] = n set there (launch_occluded does the
+// scene dispatch).  w.ev[0] / w.ev[1] bracket the walk kernel, as in rtmi_trace.
 static int enqueue_occluded(rtmi_scene* s, Work& w, hipStream_t st, uint64_t n, const float4* qo, const float4* qd, const float* tmax,
                             uint8_t* occ) {
-    const bool count = (s->options & RTMI_OPT_COUNTERS) != 0;
-    const bool bvh = (s->options & RTMI_OPT_BVH) && s->bvh_ok, generic = (s->options & RTMI_OPT_GENERIC) != 0;
-    const bool anyhit = !bvh && !generic && s->d.nspheres == 0 && (s->root_is_leaf || s->octree) && !s->occl_from_hits;
     s->active_streams = 1;
-    if (!anyhit) {
+    if (!occluded_anyhit(s)) {
         const int rc = ensure_workspace(w, (size_t)n, 1);
         if (rc != RTMI_OK) return rc;
     }
     HIPCHK(hipMemsetAsync(w.ctrl.p, 0, sizeof(DCtrl), st));
     hipLaunchKernelGGL(k_set_count, dim3(1), dim3(1), 0, st, w.ctrl.p, (uint32_t)n);
     HIPCHK(hipEventRecord(w.ev[0], st));
-    if (!anyhit) {
-        launch_trace(s, w, st, qo, qd, 0, count, w.ev[1]);
-        const unsigned grid = (unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)s->num_cu * 8);
-        hipLaunchKernelGGL(k_occl_from_hits, dim3(grid), dim3(256), 0, st, (uint32_t)n, w.hit_tf.p, w.hit_t.p, tmax, occ);
-    } else if (s->root_is_leaf) {
-        hipLaunchKernelGGL(count ? k_occluded_linear<true> : k_occluded_linear<false>, dim3((unsigned)(s->num_cu * 8)), dim3(256), 0, st, s->d,
-                           qo, qd, w.ctrl.p, 0, tmax, occ);
-        HIPCHK(hipEventRecord(w.ev[1], st));
-    } else {
-        OctArgs a{};
-        a.qo = qo; a.qd = qd; a.pass = 0;
-        a.vote_s = s->vote[0]; a.vote_l = s->vote[1];
-        hipLaunchKernelGGL(occluded_oct_variant[count][(s->options & RTMI_OPT_FAST) != 0], oct_grid(s), dim3(64), oct_launch_lds(s, count), st,
-                           s->d, a, w.ctrl.p, (int)s->tune.refill_min0, (int)(s->tune.xcd_aware % 3u), OcclArgs{tmax, occ});
-        HIPCHK(hipEventRecord(w.ev[1], st));
-    }
+    launch_occluded(s, w, st, n, qo, qd, tmax, occ, 0, w.ev[1]);
     HIPCHK(hipGetLastError());
     return RTMI_OK;
 }

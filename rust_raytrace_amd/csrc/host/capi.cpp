@@ -287,6 +287,33 @@ int rth_caster_walk_features_device(rth_scene_t* s, uint32_t w, uint32_t h, cons
         if (stats) *stats = ctx.stats;
     });
 }
+int rth_caster_walk_ao(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp, uint64_t row0,
+                       uint64_t nrows, uint32_t sample0, uint32_t nsamples, const rtmi_ao_t* ao, float* ao_host, rtmi_stats_t* stats,
+                       double* wall) {
+    return guarded([&] {
+        if (!ao) throw std::runtime_error("NULL rtmi_ao_t");
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_rays_ao(v, s->scene, (size_t)row0, (size_t)nrows, sample0, nsamples, *ao, ao_host, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
+int rth_caster_walk_ao_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                              const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, const rtmi_ao_t* ao, void* ao_device,
+                              void* hip_stream, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!tile) throw std::runtime_error("NULL tile");
+        if (!ao) throw std::runtime_error("NULL rtmi_ao_t");
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_ao_device(v, s->scene, *tile, sample0, nsamples, *ao, ao_device, hip_stream, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
 int rth_caster_denoise(rth_scene_t* s, uint32_t w, uint32_t h, const float* color_host, const float* albedo_host,
                        const float* normal_host, const rtmi_denoise_t* params, float* out_host) {
     return guarded([&] {

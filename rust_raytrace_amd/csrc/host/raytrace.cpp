@@ -761,6 +761,30 @@ void HipRayCaster::occluded_device(const Scene& s, uint64_t n, const void* orig4
         throw std::runtime_error(std::string("rtmi_occluded_device: ") + rtmi_last_error());
 }
 
+void HipRayCaster::walk_rays_ao(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
+                                const rtmi_ao_t& ao, float* out, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_ao(h, &av, seed, (uint32_t)row0, (uint32_t)nrows, sample0, nsamples, &ao, out, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_ao: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
+void HipRayCaster::walk_ao_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
+                                  const rtmi_ao_t& ao, void* ao_device, void* hip_stream, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_ao_device(h, &av, seed, &tile, sample0, nsamples, &ao, ao_device, hip_stream, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_ao_device: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
 void HipRayCaster::variance(const Scene& s, const Color* accum, const Color* sumsq, const uint32_t* counts, uint64_t npixels, Color* out) {
     rtmi_scene_t* h = resident(s);
     const int rc = rtmi_variance(h, reinterpret_cast<const float*>(accum), reinterpret_cast<const float*>(sumsq), counts, npixels,

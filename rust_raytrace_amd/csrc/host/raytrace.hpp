@@ -218,6 +218,12 @@ public:
                   rtmi_stats_t* stats = nullptr);
     void occluded_device(const Scene& s, uint64_t n, const void* orig4_device, const void* dir4_device, const void* tmax_device,
                          void* occluded_device, void* hip_stream, rtmi_stats_t* stats = nullptr);
+    // Ambient occlusion (rtmi_render_ao / rtmi_render_ao_device, which rtmi.h defines): one float per pixel, the share of
+    // ao.rays hemisphere rays per primary sample of [sample0, sample0 + nsamples) that are not occluded within ao.radius.
+    void walk_rays_ao(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
+                      const rtmi_ao_t& ao, float* out, ProgressCtx& progress);
+    void walk_ao_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
+                        const rtmi_ao_t& ao, void* ao_device, void* hip_stream, ProgressCtx& progress);
     // Variance-guided denoising (rtmi_variance* / rtmi_denoise_var* / rtmi_render_adaptive_denoised): variance() turns the
     // moments of an adaptive render (accum, sumsq, counts of npixels pixels) into the variance image the filter takes beside
     // denoise()'s images; var_out (may be null) receives the propagated variance.  walk_adaptive_denoised runs the adaptive

@@ -644,6 +644,69 @@ class HipRayCaster:
                                                         C.c_void_p(stream_ptr or 0), C.byref(st), C.byref(wall)))
         return ProgressCtx(st.rays, wall.value, st.as_dict())
 
+    @staticmethod
+    def ao_params(rays=None, radius=None, bias=None):
+        """rtmi_ao_t from the library's defaults (rtmi_ao_defaults: 4 rays, radius +inf, bias 0.001) with the given fields
+        replaced.  Raises ValueError for what the library would refuse."""
+        a = _ffi.Ao()
+        _ffi.lib().rtmi_ao_defaults(C.byref(a))
+        if rays is not None:
+            if not 1 <= int(rays) <= 256:
+                raise ValueError("rays must be in [1, 256]")
+            a.rays = int(rays)
+        if radius is not None:
+            if not float(radius) >= 0.0:
+                raise ValueError("radius must be >= 0 (inf: unlimited) and not NaN")
+            a.radius = float(radius)
+        if bias is not None:
+            if not np.isfinite(float(bias)):
+                raise ValueError("bias must be finite")
+            a.bias = float(bias)
+        return a
+
+    def _ao_args(self, v, sample0, nsamples, rays, radius, bias):
+        k0, n = self._feature_samples(v, sample0, nsamples)
+        a = self.ao_params(rays, radius, bias)
+        if n * a.rays >= 1 << 24:
+            raise ValueError("nsamples * rays must stay below 2^24")
+        return k0, n, a
+
+    def walk_rays_ao(self, v, s, rays=None, radius=None, bias=None, sample0=0, nsamples=None, out=None):
+        """Ambient occlusion of the whole frame (rtmi_render_ao; include/rtmi.h defines it): (H, W) float32, per pixel the
+        share of `rays` hemisphere rays per primary sample of [sample0, sample0 + nsamples) (default: all from sample0) that
+        are not occluded within `radius`; 1.0 where every sample missed.  The primary rays are walk_rays' own (same seed,
+        same jitter); v.maxdepth is not used.  None for rays / radius / bias takes the library's default (4, inf, 0.001).
+        out: None allocates it, an array is filled in place.  Returns (ao, ctx)."""
+        k0, n, a = self._ao_args(v, sample0, nsamples, rays, radius, bias)
+        shape = (v.height, v.width)
+        if out is None:
+            out = np.zeros(shape, np.float32)
+        elif not isinstance(out, np.ndarray) or out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != shape:
+            raise ValueError(f"out must be a C-contiguous float32 array of shape {shape}")
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_ao(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, 0, v.height, k0, n,
+                                           C.byref(a), _p(out), C.byref(st), C.byref(wall)))
+        return out, ProgressCtx(st.rays, wall.value, st.as_dict())
+
+    def walk_rays_ao_device(self, v, s, out, tile=None, rays=None, radius=None, bias=None, sample0=0, nsamples=None, stream=None):
+        """The same into a torch tensor on the scene's device (rtmi_render_ao_device) for a striped row set tile = (row0,
+        nrows, stripe_rows, stripe_step) (default: the whole frame): `out` is a contiguous float32 tensor of nrows * width
+        elements, written by work enqueued on `stream` (a torch stream, a raw HIP stream pointer or None).  Returns ctx."""
+        k0, n, a = self._ao_args(v, sample0, nsamples, rays, radius, bias)
+        t = _ffi.Tile(*[int(x) for x in (tile if tile is not None else (0, v.height, v.height, 0))])
+        want = int(t.nrows) * int(v.width)
+        if not hasattr(out, "data_ptr") or not out.is_cuda or str(out.dtype) != "torch.float32" or not out.is_contiguous() or out.numel() != want:
+            raise ValueError(f"out must be a contiguous float32 tensor of {want} elements on the device")
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_ao_device(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, C.byref(t), k0, n,
+                                                  C.byref(a), C.c_void_p(out.data_ptr()), C.c_void_p(getattr(stream, "cuda_stream", stream) or 0),
+                                                  C.byref(st), C.byref(wall)))
+        return ProgressCtx(st.rays, wall.value, st.as_dict())
+
     DENOISE_DEMODULATE = 1
 
     @staticmethod
