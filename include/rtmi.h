@@ -640,8 +640,12 @@ int rtmi_make_triangles(int device, const float* corners9_host, uint64_t n, cons
  * caller keeps the list bookkeeping (which is linear): see build_bounding_box_gpu in csrc/host/raytrace.cpp.
  * tris15: ntris x 15 floats (incenter, norm, corner 0, corner 1, corner 2), kept on the device by the handle.
  * boxes[b]: geometry + the range [cand_first, cand_first + cand_count) of `cand` (triangle indices) to test against it;
- * keep[keep_first + j] receives 1 when box b contains candidate j, else 0.  Ranges of different boxes may overlap in
- * `cand` (the 8 children of a box share their parent's list) but not in `keep`. */
+ * keep[keep_first + j] receives 1 when box b contains candidate j, else 0; flags outside every box's range are left as
+ * they were.  Ranges of different boxes may overlap in `cand` (the 8 children of a box share their parent's list) but not
+ * in `keep`.  Errors (RTMI_ERR_INVALID, nothing launched, `keep` untouched): a NULL builder; NULL boxes / cand / keep with
+ * nboxes and nkeep non-zero; a candidate index >= ntris; a box whose range leaves `cand` or `keep`.  rtmi_builder_create:
+ * RTMI_ERR_INVALID for ntris == 0, NULL tris15 / out, or a device index outside [0, rtmi_device_count()).
+ * rtmi_builder_destroy(NULL) is RTMI_OK. */
 typedef struct rtmi_build_box {
     float orig[3];
     float len2;

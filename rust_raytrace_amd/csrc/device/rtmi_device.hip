@@ -3267,7 +3267,8 @@ int rtmi_builder_filter(rtmi_builder_t* b, const rtmi_build_box_t* boxes, uint64
     HIPCHK(hipMemcpy(b->rng.p, rng.data(), nboxes * sizeof(uint4), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(b->items.p, items.data(), items.size() * sizeof(uint2), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(b->cand.p, cand, ncand * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(b->keep.p, 0, nkeep));
+    // the caller's flags go up and come back: those outside every box's range return as they were
+    HIPCHK(hipMemcpy(b->keep.p, keep, nkeep, hipMemcpyHostToDevice));
     const unsigned grid = (unsigned)std::min<uint64_t>(items.size(), (uint64_t)b->num_cu * 64);
     hipLaunchKernelGGL(k_box_contains, dim3(grid), dim3(256), 0, nullptr, b->tris.p, b->geo.p, b->rng.p, b->items.p, (uint32_t)items.size(),
                        b->cand.p, b->keep.p);

@@ -380,30 +380,14 @@ _SOUP_SEEDS = [1, 2, 3, 4] + [int(x) for x in os.environ.get("RTMI_TEST_EXTRA_SO
 def test_random_triangle_soups(seed):
     """Random scenes: triangle soup with random surfaces and edge thickness, random octree parameters and camera.
     Exercises boxes with many colliding children, leaves of all sizes, deep and shallow trees."""
+    from builder_cases import SOUP_ROOT, soup
     from conftest import OracleApi, ProductApi
     orc, R = _orc(), _R()
-    rng = np.random.default_rng(1000 + seed)
-    ntri = int(rng.integers(40, 400))
-    centre = rng.uniform(-3, 3, (ntri, 3)) + np.array([0, 0, 8.0])
-    pts = (centre[:, None, :] + rng.normal(scale=rng.uniform(0.2, 1.2), size=(ntri, 3, 3))).astype(np.float32)
-    kinds = rng.integers(0, 3, ntri)
-    cols = rng.integers(0, 256, (ntri, 3))
-    alphas = rng.uniform(0.05, 0.95, ntri)
-    scat = rng.uniform(0.0, 0.3, ntri)
-    edges = rng.choice([0.0, 0.05, 0.3, -1.0], ntri)
-    maxdepth, minobjs = int(rng.integers(2, 9)), int(rng.integers(2, 24))
+    rng, ntri, (maxdepth, minobjs), add = soup(seed)   # the scene recipe is shared with test_gpu_builder.py
 
     def recipe(api):
-        s = api.scene()
-        for i in range(ntri):
-            c = tuple(int(x) for x in cols[i])
-            surf = (api.solid(c), api.matte(c, float(alphas[i])), api.reflective(float(scat[i]), c, float(alphas[i])))[kinds[i]]
-            try:
-                api.add_triangle(s, pts[i], surf, float(edges[i]))
-            except RuntimeError:
-                pass  # degenerate triangle: rejected identically by both implementations
-        s.populate_triangle_numbers()
-        s.build_bounding_box([0.0, 0.0, 8.0], 8.0, maxdepth, minobjs)
+        s = add(api)
+        s.build_bounding_box(SOUP_ROOT[0], SOUP_ROOT[1], maxdepth, minobjs)
         return s
     so, sp = recipe(OracleApi(orc)), recipe(ProductApi(R))
     assert so.num_tris() == sp.num_tris()
