@@ -93,6 +93,7 @@ typedef struct rtmi_stats {
                              * RTMI_MIRROR_INPLACE)                                            */
     double bounce_ms;       /* the bounce passes' closest-hit launches (k_trace_oct)                               */
     /* (rtmi_render_ao*: primary_ms = the primary rays' closest-hit launches, bounce_ms = the AO rays' walk launches)     */
+    /* (rtmi_render_light*: likewise, bounce_ms = the live shadow rays' walk launches)                                    */
     int32_t peer_access;    /* 1 = this device writes the root device's memory directly (peer access enabled, or the
                              * same device); 0 = the runtime refused: the band is staged (rtmi_last_error() carries a
                              * warning although the call returns RTMI_OK)                                      */
@@ -532,7 +533,7 @@ int rtmi_trace(rtmi_scene_t* scene, uint64_t n, const float* orig4, const float*
  * and before the scene is used: a NULL scene, orig4, dir4 or occluded; an output that overlaps an input (as byte ranges of 16 n,
  * 16 n, 4 n and n bytes).  RTMI_ERR_UNSUPPORTED: n >= 2^31, as for rtmi_trace.  stats come back cleared on failure.
  * Not here: shadow rays in shading, occlusion for batches of views and for rtmi_render_frame_multi.  (The
- * ambient-occlusion buffer is rtmi_render_ao*, below.) */
+ * ambient-occlusion buffer is rtmi_render_ao*, the shadow layer of a box light rtmi_render_light*, both below.) */
 int rtmi_occluded(rtmi_scene_t* scene, uint64_t n, const float* orig4, const float* dir4, const float* tmax /* n floats or NULL */,
                   uint8_t* occluded, rtmi_stats_t* stats);
 int rtmi_occluded_device(rtmi_scene_t* scene, uint64_t n, const void* orig4_device, const void* dir4_device,
@@ -589,6 +590,84 @@ int rtmi_render_ao_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64
                           rtmi_stats_t* stats);
 int rtmi_render_ao(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
                    uint32_t sample0, uint32_t nsamples, const rtmi_ao_t* ao, float* ao_host, rtmi_stats_t* stats);
+
+/* Direct light rendered on the device: soft shadows from one box light, two f32 planes per pixel.
+ *   shadow     the share of K light samples per primary sample that are visible from the first hit (1.0 where every sample
+ *              missed): a shadow layer, a contact-shadow layer, a guide image;
+ *   irradiance the mean of n . dir over those visible samples: the cosine-weighted light, so that a preview is
+ *              albedo * (ambient * ao + light * irradiance) from device buffers with no bounce pass.
+ * The reference declares the light (pub struct LightSource { orig, len2 }, raytrace.rs:595-598) and spells the shadow ray out
+ * in a comment (_get_shadow_ray, raytrace.rs:600-610; its use in color_ray, :1203-1224) but never runs either, so the buffer is
+ * build-defined like the denoiser and rtmi_render_ao*: what follows IS the definition, and tests/light_ref.py pins it bit for
+ * bit.  All arithmetic is f32 on all four lanes, no contraction.
+ * Primary rays: exactly those of rtmi_render_features_device for the same (vp, seed, tile, sample0, nsamples): RNG block 0,
+ * jittered iff S = vp->samples_per_pixel != 1, vp->maxdepth not consulted, and (tri, t, face) of a ray is what rtmi_trace
+ * returns for it under the handle's current options.
+ * Per sample s of pixel p (p = row * width + col of the image, the renderer's RNG key), with (ro, rd) the primary ray and
+ * K = light->rays:
+ *   a miss (tri == 0) contributes K visible rays to shadow and nothing to irradiance;
+ *   a hit, edge faces included:  n = the triangle's norm, * (-1.f) when face & 1 (the features call's normal);
+ *                                point = rd * t + ro   (a multiplication, then an addition);
+ *   for k = 0 .. K-1:  w    = RNG block 0xC0000000 | k of (seed, p, s), u_c = top 24 bits of w_c * 2^-24: one Philox block is
+ *                             exactly the four rand::random draws of _get_shadow_ray.  The block range is disjoint from a
+ *                             path's own blocks 0 .. maxdepth and from AO's 0x80000000 | k;
+ *                      adj  = (orig.x + u_0 * len2, orig.y + u_1 * len2, orig.z + u_2 * len2, 0): per lane a multiplication,
+ *                             then an addition;
+ *                      v    = adj - point;
+ *                      d2   = the ordered four-lane dot of v with itself ((((0 + x x) + y y) + z z) + w w, as `unit` has it);
+ *                      r    = sqrt(d2);
+ *                      dir  = v * (1.f / r);
+ *                      o    = point + n * (bias * (u_3 + 1.f))   (the direction is taken from the unsmudged point, as in the
+ *                             reference);
+ *                      c    = the ordered four-lane dot of n and dir;
+ *                      cull: if !(c > 0.f) the ray is not traced and is not visible (the light behind the surface, a NaN,
+ *                             the light at the point);
+ *                      otherwise the ray is visible iff rtmi_occluded's definition gives 0 for (o, dir, tmax = r) on this
+ *                             handle; with RTMI_LIGHT_UNBOUNDED the limit is the NULL tmax instead: the reference's test as
+ *                             written, where anything along the ray shadows, even beyond the light.
+ * Results, with N = nsamples * K:
+ *   shadow[p]     = (float)visible * (1.f / (float)N), visible = the number of visible rays over the pixel's samples: an
+ *                   integer below 2^24, so the order of summation is free;
+ *   irradiance[p] = acc * (1.f / (float)N), acc = 0.f, then acc = acc + c for every visible ray of a sample that hit, in
+ *                   sample order, then in k order.
+ * Different from the reference's comment: the own triangle is NOT excluded from the test (`id != obj.getid()`): the smudge
+ * along n together with c > 0 takes its place; and the default limit is the light's distance, not infinity.
+ * Layout: the tile's, as rtmi_render_ao*, one f32 per pixel in each plane.  Either plane may be NULL, not both; the two must
+ * not be the same buffer.
+ * Scenes: octree, linear list, generic tree and RTMI_OPT_GENERIC; RTMI_OPT_FAST / RTMI_OPT_BVH give their own modes' hits and
+ * answers.  RTMI_ERR_UNSUPPORTED for a scene with analytic spheres, as for features, and for nsamples * rays >= 2^24.
+ * RTMI_ERR_INVALID, before any HIP call and before the scene is used, stats cleared: a NULL scene, viewport, tile or light;
+ * both outputs NULL, or the same pointer; rays 0 or above 256; unknown flag bits; len2 NaN, negative or infinite; a non-finite
+ * orig or bias; nsamples == 0; sample0 + nsamples > S; every viewport and tile check of the features call.  An empty tile
+ * returns RTMI_OK and touches nothing.
+ * stats: rays = pixels * nsamples + live rays (live = not culled); kernel_ms, streams, pipeline = 1 as for features;
+ * trace_launches and trace_ms cover the primary closest-hit launches (their share: primary_ms) and the shadow rays' walk
+ * launches (bounce_ms).  With RTMI_OPT_COUNTERS the five work counters are the primaries' closest-hit work plus the any-hit
+ * walk's actual work.
+ * How: per batch, on one library stream, the features call's primary pass; k_light_rays builds the candidates of the paths
+ * that hit and compacts the live ones per ray, its counter being the walk's ray count (it stays on the device; a batch whose
+ * rays are all culled walks 0 rays); the scene's any-hit walk (or its closest-hit launch, where rtmi_occluded uses that);
+ * k_light_resolve counts and folds per pixel in the defined order.  The light queue (40 B per live ray at most, 1 answer byte,
+ * 4 B per candidate) lives on the handle, grows on demand and is freed by rtmi_scene_destroy; a batch holds at most
+ * batch_paths candidates.  No tuning changes a bit of the result.  The device variant enqueues on hip_stream like
+ * rtmi_render_tile_device; the host variant renders rows [row0, row0 + nrows) and copies 4 B per pixel and plane out.
+ * Not here: several lights in one call, a light colour or intensity (the caller multiplies), shadow rays inside color_ray
+ * (DESIGN.md 7), batches of views and rtmi_render_frame_multi, the buffer as a denoiser guide, importance sampling. */
+enum { RTMI_LIGHT_UNBOUNDED = 1u << 0 };
+typedef struct rtmi_light {
+    float orig[3];   /* LightSource.orig: the corner of the light's box                 */
+    float len2;      /* LightSource.len2: its edge; 0 = a point light; >= 0, finite     */
+    uint32_t rays;   /* K: light samples per primary sample that hits, 1..256           */
+    uint32_t flags;  /* RTMI_LIGHT_UNBOUNDED or 0                                       */
+    float bias;      /* the smudge factor; default 0.005f (raytrace.rs:607)             */
+} rtmi_light_t;
+void rtmi_light_defaults(rtmi_light_t* light);  /* orig (0,0,0), len2 0, rays 4, flags 0, bias 0.005f */
+int rtmi_render_light_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile,
+                             uint32_t sample0, uint32_t nsamples, const rtmi_light_t* light, void* shadow_device,
+                             void* irradiance_device, void* hip_stream, rtmi_stats_t* stats);
+int rtmi_render_light(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
+                      uint32_t sample0, uint32_t nsamples, const rtmi_light_t* light, float* shadow_host, float* irradiance_host,
+                      rtmi_stats_t* stats);
 
 /* Per-ray debug records (the reference's Scene { debug_ctx, debug_en }, raytrace.rs:1297-1303, debug.rs): what the
  * octree walk did for each ray, taken from the production walk itself (k_trace_record: the walk of rtmi_trace in a

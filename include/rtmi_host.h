@@ -132,6 +132,17 @@ int rth_caster_walk_ao(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12
 int rth_caster_walk_ao_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
                               const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, const rtmi_ao_t* ao, void* ao_device,
                               void* hip_stream, rtmi_stats_t* stats, double* wall_seconds);
+/* Direct light (rtmi_render_light / rtmi_render_light_device in rtmi.h, which defines it): two f32 per pixel, the share of
+ * light->rays samples of the box light (the host mirror's LightSource { orig, len2 }, raytrace.rs:595-598) per primary sample
+ * of [sample0, sample0 + nsamples) that are visible from the first hit, and the mean of n . dir over them.  Either plane may
+ * be NULL.  maxdepth is not consulted; the primary rays use the caster's seed. */
+int rth_caster_walk_light(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp, uint64_t row0,
+                          uint64_t nrows, uint32_t sample0, uint32_t nsamples, const rtmi_light_t* light, float* shadow_host,
+                          float* irradiance_host, rtmi_stats_t* stats, double* wall_seconds);
+int rth_caster_walk_light_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                                 const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, const rtmi_light_t* light,
+                                 void* shadow_device, void* irradiance_device, void* hip_stream, rtmi_stats_t* stats,
+                                 double* wall_seconds);
 /* Per-ray records (rtmi_trace_records / rtmi_primary_records, same buffers and size-query idiom) on the scene's
  * resident copy; the primary records use the caster's seed. */
 int rth_caster_trace_records(rth_scene_t* s, uint64_t n, const float* orig4, const float* dir4, rtmi_ray_record_t* recs,

@@ -48,6 +48,7 @@ static_assert(sizeof(rtmi_stats_t) == 128 && sizeof(rtmi_tuning_t) == 48 && size
 static_assert(sizeof(rtmi_adaptive_t) == 32 && offsetof(rtmi_adaptive_t, samples) == 24, "ABI struct layout changed");
 static_assert(sizeof(rtmi_denoise_t) == 24 && offsetof(rtmi_denoise_t, sigma_color) == 8, "ABI struct layout changed");
 static_assert(sizeof(rtmi_ao_t) == 16 && offsetof(rtmi_ao_t, radius) == 8, "ABI struct layout changed");
+static_assert(sizeof(rtmi_light_t) == 28 && offsetof(rtmi_light_t, rays) == 16 && offsetof(rtmi_light_t, bias) == 24, "ABI struct layout changed");
 
 namespace rtmi {
 
@@ -377,6 +378,7 @@ __global__ void __launch_bounds__(256) k_trace(DScene sc, const float4* __restri
 #include "bvh_fast.hpp"
 #include "denoise.hpp"
 #include "ao.hpp"
+#include "light.hpp"
 namespace rtmi {
 
 
@@ -1078,6 +1080,17 @@ struct rtmi_scene {
         void release() { qo.release(); qd.release(); tmax.release(); slot.release(); occ.release(); }
     } ao[RTMI_MAX_STREAMS];
     DevBuf<float> ao_out;
+    // rtmi_render_light*: per stream, the shadow-ray queue of a batch (origins, directions, limits, n . dir of the live rays),
+    // each candidate's queue entry and the answer bytes (grow only); the two planes of the host variant.  No other call reads
+    // or writes them.
+    struct LightBuf {
+        DevBuf<float4> qo, qd;
+        DevBuf<float> tmax, c;
+        DevBuf<uint32_t> slot;
+        DevBuf<uint8_t> occ;
+        void release() { qo.release(); qd.release(); tmax.release(); c.release(); slot.release(); occ.release(); }
+    } light[RTMI_MAX_STREAMS];
+    DevBuf<float> light_out;
     DevBuf<uint8_t> mstage, mframe;  // rtmi_render_frame_multi, root scene: received bands / the frame
     hipStream_t mstream = nullptr;   // rtmi_render_frame_multi: this scene's band stream
     std::vector<ncclComm_t> comms;   // root scene, RTMI_FRAME_RCCL: one communicator per scene of the last device list
@@ -1522,6 +1535,8 @@ int rtmi_scene_destroy(rtmi_scene_t* s) {
     s->occ_tmax.release(); s->occ_out.release();
     for (auto& a : s->ao) a.release();
     s->ao_out.release();
+    for (auto& l : s->light) l.release();
+    s->light_out.release();
     if (s->vcams_ev) (void)hipEventDestroy(s->vcams_ev);
     if (s->mstream) (void)hipStreamDestroy(s->mstream);
     if (!s->comms.empty()) { if (Rccl* r = rccl_api()) for (ncclComm_t c : s->comms) (void)r->CommDestroy(c); }
@@ -1700,7 +1715,7 @@ static bool occluded_anyhit(const rtmi_scene* s) {
 }
 // The any-hit walk of queue `pass` of the stream's control block (ctrl->count[pass] rays, set on the stream before this):
 // rays qo / qd, limits tmax (null: +inf), one byte per ray to occ.  pass 0 with n rays: rtmi_occluded*.  pass 1: the AO rays
-// of rtmi_render_ao*, whose count exists on the device only; n is then an upper bound (the closest-hit fallback writes the
+// of rtmi_render_ao* or the shadow rays of rtmi_render_light*, whose count exists on the device only (0 is a valid count); n is then an upper bound (the closest-hit fallback writes the
 // workspace's hit records, sized for it).  `stop` is recorded right after the walk kernel.
 static void launch_occluded(rtmi_scene* s, Work& w, hipStream_t st, uint64_t n, const float4* qo, const float4* qd, const float* tmax,
                             uint8_t* occ, int pass, hipEvent_t stop) {
@@ -1805,6 +1820,8 @@ struct ListPass { const uint32_t* list; uint32_t n; float4* sumsq; uint32_t* cou
 struct FeatOut { float4* albedo; float4* normal; uint32_t* ids; };
 // An ambient-occlusion call (rtmi_render_ao*): its parameters and its output, one f32 per pixel of the tile
 struct AoCall { rtmi_ao_t p; float* out; };
+// A direct-light call (rtmi_render_light*): its parameters and its two planes, one f32 per pixel of the tile, either may be null
+struct LightCall { rtmi_light_t p; float* shadow; float* irradiance; };
 // One render_tile call: what it renders, and its plan (plan_tile)
 struct TileCall {
     uint64_t seed;
@@ -1813,8 +1830,9 @@ struct TileCall {
     const ListPass* lp;
     const FeatOut* fo;  // a features call: the primary pass alone (maxdepth = 1, per-pass pipeline), k_features for k_shade + k_accum
     const AoCall* ao;   // an AO call: a features call's primary pass, then k_ao_rays, the any-hit walk of queue 1 and k_ao_resolve
+    const LightCall* li;  // a direct-light call: likewise with k_light_rays and k_light_resolve
     ViewTab vt;  // VIEWS: the view table (cams == nullptr otherwise)
-    Samp mode;  // LIST with lp, PASS with accum, fo or ao, VIEWS with vt.cams, FRAME otherwise
+    Samp mode;  // LIST with lp, PASS with accum, fo, ao or li, VIEWS with vt.cams, FRAME otherwise
     bool counting, path_kernels;
     uint32_t nsub;
     uint64_t pix_per_batch, max_npix;  // max_npix: pixels of the largest sub-tile
@@ -1854,7 +1872,7 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
     // path kernels (pipeline 3; 0 = automatic): exact-octree scenes get pass 0 from k_path_primary, which generates, traces and
     // shades the primary rays in one kernel.  Everything else (pipeline 1, linear list, generic tree, BVH mode,
     // analytic spheres) starts with k_gen.  Both then run one closest-hit + one shading launch per bounce pass.
-    c.path_kernels = !c.fo && !c.ao && s->tune.pipeline != 1u && s->octree && !s->root_is_leaf &&
+    c.path_kernels = !c.fo && !c.ao && !c.li && s->tune.pipeline != 1u && s->octree && !s->root_is_leaf &&
                      !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) && s->d.nspheres == 0;
     // streams = 0 (automatic): one stream for path-kernel tiles of 2^26 paths and more, three otherwise (the per-pass
     // pipelines -- BVH mode: 29.6 ms on three streams, 35.2 on one -- have elementwise kernels to hide).  Since k_shade stopped being
@@ -1869,8 +1887,8 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
     // sub-tile's k_features waits for wave slots behind the other sub-tiles' persistent k_trace_oct launches (config 3's frame
     // of 2^28 paths: 108.0 and 111.0 ms on one stream in two jobs, 113.9 and 113.7 on three; 2^25 paths: 16.4 and 16.3 against
     // 17.5 and 17.3).
-    // AO calls (c.ao): as features calls.
-    const uint32_t auto_streams = (c.fo || c.ao || (c.path_kernels && npix_call * spp >= (1ull << 26)) || (lp && npix_call < npix)) ? 1u : 3u;
+    // AO and direct-light calls (c.ao, c.li): as features calls.
+    const uint32_t auto_streams = (c.fo || c.ao || c.li || (c.path_kernels && npix_call * spp >= (1ull << 26)) || (lp && npix_call < npix)) ? 1u : 3u;
     uint32_t nsub = std::min<uint32_t>(s->tune.streams ? s->tune.streams : auto_streams, (uint32_t)RTMI_MAX_STREAMS);
     nsub = (uint32_t)std::min<uint64_t>(nsub, lp ? npix_call : nrows);
     if (npix_call * spp < s->tune.subtile_min_paths) nsub = 1;
@@ -1894,10 +1912,10 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
         }
     }
 
-    // batch = whole pixels with all their samples; an AO call counts a path as its K AO rays, so that the AO queue of a
-    // batch stays within batch_paths entries and below the walk's 2^31
+    // batch = whole pixels with all their samples; an AO call counts a path as its K AO rays (a direct-light call: its K
+    // candidates), so that the ray queue of a batch stays within batch_paths entries and below the walk's 2^31
     const size_t want_paths = (size_t)std::max<uint64_t>(s->tune.batch_paths, 1) / nsub;
-    const uint64_t per_pix = (uint64_t)spp * (c.ao ? c.ao->p.rays : 1u);
+    const uint64_t per_pix = (uint64_t)spp * (c.ao ? c.ao->p.rays : c.li ? c.li->p.rays : 1u);
     uint64_t pix_per_batch = std::max<uint64_t>(1, want_paths / per_pix);
     uint64_t max_sub_npix = 0;
     for (uint32_t t = 0; t < nsub; t++) max_sub_npix = std::max(max_sub_npix, c.sub[t].npix);
@@ -1915,13 +1933,19 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
         if (c.sub[t].npix == 0) continue;
         const size_t paths = (size_t)(std::min<uint64_t>(pix_per_batch, c.sub[t].npix) * spp);
         // an AO call on a scene without an any-hit kernel: the closest-hit launch of the AO rays writes the workspace's hit records
-        const size_t nao = c.ao ? paths * c.ao->p.rays : 0;
-        int rc = ensure_workspace(s->w[t], c.ao && !occluded_anyhit(s) ? nao : paths, c.maxdepth);
+        // (a direct-light call likewise: its candidates bound its live rays)
+        const size_t nao = c.ao ? paths * c.ao->p.rays : c.li ? paths * c.li->p.rays : 0;
+        int rc = ensure_workspace(s->w[t], nao && !occluded_anyhit(s) ? nao : paths, c.maxdepth);
         if (rc != RTMI_OK) return rc;
         if (c.ao) {
             rtmi_scene::AoBuf& a = s->ao[t];
             HIPCHK(a.qo.ensure(nao)); HIPCHK(a.qd.ensure(nao)); HIPCHK(a.occ.ensure(nao)); HIPCHK(a.slot.ensure(paths));
             if (!std::isinf(c.ao->p.radius)) HIPCHK(a.tmax.ensure(nao));
+        }
+        if (c.li) {
+            rtmi_scene::LightBuf& l = s->light[t];
+            HIPCHK(l.qo.ensure(nao)); HIPCHK(l.qd.ensure(nao)); HIPCHK(l.c.ensure(nao)); HIPCHK(l.occ.ensure(nao)); HIPCHK(l.slot.ensure(nao));
+            if (!(c.li->p.flags & RTMI_LIGHT_UNBOUNDED)) HIPCHK(l.tmax.ensure(nao));
         }
     }
     return RTMI_OK;
@@ -2016,6 +2040,26 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
         HIPCHK(hipGetLastError());
         return RTMI_OK;
     }
+    if (c.li) {  // the primary rays' closest hits, the live shadow rays compacted into queue 1, their any-hit walk, the per-pixel folds
+        const rtmi_light_t& p = c.li->p;
+        rtmi_scene::LightBuf& l = s->light[t];
+        float* tmax = (p.flags & RTMI_LIGHT_UNBOUNDED) ? nullptr : l.tmax.p;  // unbounded: the walk's NULL tmax
+        HIPCHK(hipEventRecord(w.pass_ev[0], st));
+        launch_trace(s, w, st, w.qo[0].p, w.qd[0].p, 0, c.counting, w.pass_ev[1]);
+        HIPCHK(hipGetLastError());
+        // ctrl->count[1] (zero since the batch's memset) is the compaction's counter and then the walk's ray count
+        hipLaunchKernelGGL(k_light_rays, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, p.rays, make_fastdiv(p.rays),
+                           mk(p.orig[0], p.orig[1], p.orig[2]), p.len2, p.bias, w.qo[0].p, w.qd[0].p, w.hit_tf.p, w.hit_t.p, l.qo.p, l.qd.p, tmax,
+                           l.c.p, l.slot.p, w.ctrl.p);
+        HIPCHK(hipEventRecord(w.pass_ev[2], st));
+        launch_occluded(s, w, st, (uint64_t)npaths * p.rays, l.qo.p, l.qd.p, tmax, l.occ.p, 1, w.pass_ev[3]);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_light_resolve, ew_grid, ew_block, 0, st, np, c.spp * p.rays, l.slot.p, l.occ.p, l.c.p, c.li->shadow,
+                           c.li->irradiance, pix0, c.W, c.nsub, t, make_fastdiv(c.W));
+        HIPCHK(hipEventRecord(w.ev[1], st));
+        HIPCHK(hipGetLastError());
+        return RTMI_OK;
+    }
     for (uint32_t pass = pass0; pass < c.maxdepth; pass++) {
         const int a = pass & 1, b = a ^ 1;
         HIPCHK(hipEventRecord(w.pass_ev[2 * pass], st));
@@ -2078,7 +2122,7 @@ static int collect_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
         sum.launches++;
         sum.trace_ms += pm;
         if (c.path_kernels) { if (pass == 0) sum.primary_ms += pm; else sum.bounce_ms += pm; }
-        if (c.ao) sum.primary_ms += pm;
+        if (c.ao || c.li) sum.primary_ms += pm;
         if (s->verbose) fprintf(stderr, "[rtmi] stream %u batch@%llu pass %u: %u rays, trace %.3f ms, %.1f Mrays/s\n", t, (unsigned long long)p0, pass, h.count[pass], pm, h.count[pass] / (pm * 1e3));
     }
     if (c.ao) {  // the AO rays' walk: queue 1
@@ -2089,6 +2133,14 @@ static int collect_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
         sum.bounce_ms += pm;
         sum.ao_hits += h.count[RTMI_AO_HITS];
         if (s->verbose) fprintf(stderr, "[rtmi] stream %u batch@%llu AO: %u rays, walk %.3f ms, %.1f Mrays/s\n", t, (unsigned long long)p0, h.count[1], pm, h.count[1] / (pm * 1e3));
+    }
+    if (c.li) {  // the shadow rays' walk: queue 1
+        float pm = 0.f;
+        HIPCHK(hipEventElapsedTime(&pm, w.pass_ev[2], w.pass_ev[3]));
+        sum.launches++;
+        sum.trace_ms += pm;
+        sum.bounce_ms += pm;
+        if (s->verbose) fprintf(stderr, "[rtmi] stream %u batch@%llu light: %u live rays, walk %.3f ms\n", t, (unsigned long long)p0, h.count[1], pm);
     }
     return RTMI_OK;
 }
@@ -2104,18 +2156,22 @@ static int collect_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
 // ao != nullptr (no accum, no out_device; maxdepth = 1 likewise): an ambient-occlusion call (rtmi_render_ao_device).  Its
 // batches run a features call's primary pass, k_ao_rays, the scene's any-hit walk of the compacted AO rays and k_ao_resolve,
 // which writes ao->out.  A batch is sized so that its AO rays (paths * K at most) stay within batch_paths.
+// li != nullptr (no accum, no out_device; maxdepth = 1 likewise): a direct-light call (rtmi_render_light_device).  Its batches
+// run a features call's primary pass, k_light_rays, the scene's any-hit walk of the compacted live shadow rays and
+// k_light_resolve, which writes li's planes.  A batch is sized like an AO call's, in candidates.
 // views > 0 (no accum): a batch of views (Samp::VIEWS, rtmi_render_views_device); vp is the stacked image (height = views *
 // the views' height) and s->hvcams holds the view table, uploaded here on hip_stream before the internal streams fork.
 static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile, uint32_t sample0,
                        uint32_t nsamples, float4* accum, void* out_device, void* hip_stream, rtmi_stats_t* stats,
-                       const ListPass* lp = nullptr, uint32_t views = 0, const FeatOut* fo = nullptr, const AoCall* ao = nullptr) {
+                       const ListPass* lp = nullptr, uint32_t views = 0, const FeatOut* fo = nullptr, const AoCall* ao = nullptr,
+                       const LightCall* li = nullptr) {
     if (stats) memset(stats, 0, sizeof(*stats));
     if (tile->nrows == 0) return RTMI_OK;
     RTMI_GUARD_BEGIN
     // leftovers of the caller's own HIP calls on this thread (or of failures this library tolerated, e.g. an occupancy
     // query) must not make a launch below look refused: hipGetLastError() reports the last error of ANY runtime call
     (void)hipGetLastError();
-    if (!out_device && !accum && !fo && !ao) return fail(RTMI_ERR_INVALID, "NULL argument");
+    if (!out_device && !accum && !fo && !ao && !li) return fail(RTMI_ERR_INVALID, "NULL argument");
     int rc = check_view(vp, tile);
     if (rc != RTMI_OK) return rc;
     HIPCHK(hipSetDevice(s->device));
@@ -2130,8 +2186,8 @@ static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed
     }
     TileCall c;
     c.seed = seed; c.sample0 = sample0; c.spp = nsamples; c.maxdepth = vp->maxdepth; c.W = vp->width;
-    c.accum = accum; c.out = out; c.lp = lp; c.fo = fo; c.ao = ao; c.vt = ViewTab{nullptr, FastDiv{}};
-    c.mode = lp ? Samp::LIST : (accum || fo || ao) ? Samp::PASS : views ? Samp::VIEWS : Samp::FRAME;
+    c.accum = accum; c.out = out; c.lp = lp; c.fo = fo; c.ao = ao; c.li = li; c.vt = ViewTab{nullptr, FastDiv{}};
+    c.mode = lp ? Samp::LIST : (accum || fo || ao || li) ? Samp::PASS : views ? Samp::VIEWS : Samp::FRAME;
     c.counting = (s->options & RTMI_OPT_COUNTERS) != 0;
     rc = plan_tile(s, vp, tile, c);
     if (rc != RTMI_OK) return rc;
@@ -2353,6 +2409,82 @@ int rtmi_render_ao(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, ui
     const int rc = render_tile(s, &v1, seed, &tile, sample0, nsamples, nullptr, nullptr, nullptr, stats, nullptr, 0, nullptr, &call);
     if (rc != RTMI_OK) return rc;
     HIPCHK(hipMemcpy(ao_host, s->ao_out.p, npix * sizeof(float), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+// ---------------------------------------------------------------- direct light (rtmi_render_light*)
+void rtmi_light_defaults(rtmi_light_t* p) {
+    if (!p) return;
+    p->orig[0] = p->orig[1] = p->orig[2] = 0.f;
+    p->len2 = 0.f; p->rays = 4; p->flags = 0;
+    p->bias = 0.005f;  // the reference's smudge factor (raytrace.rs:607)
+}
+
+// Checks of the direct-light entry points that come before any HIP call and before the scene is used (a CPU-only caller
+// reaches them).  RTMI_OK with *empty set: the tile has no rows, nothing to do.  v1 receives the viewport with maxdepth = 1,
+// as for features.
+static int check_light(rtmi_scene_t* s, const rtmi_viewport_t* vp, const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples,
+                       const rtmi_light_t* li, const void* shadow, const void* irradiance, rtmi_viewport_t& v1, bool* empty) {
+    *empty = false;
+    if (!s || !vp) return fail(RTMI_ERR_INVALID, "light: NULL argument (scene or viewport)");
+    if (!tile) return fail(RTMI_ERR_INVALID, "light: NULL argument (tile)");
+    if (!li) return fail(RTMI_ERR_INVALID, "light: NULL argument (rtmi_light_t)");
+    if (!shadow && !irradiance) return fail(RTMI_ERR_INVALID, "light: NULL argument (both outputs)");
+    if (shadow == irradiance) return fail(RTMI_ERR_INVALID, "light: the two outputs must not alias");
+    if (li->rays == 0 || li->rays > 256) return fail(RTMI_ERR_INVALID, "light: rays must be in [1, 256]");
+    if (li->flags & ~(uint32_t)RTMI_LIGHT_UNBOUNDED) return fail(RTMI_ERR_INVALID, "light: unknown flags");
+    if (!(li->len2 >= 0.f) || std::isinf(li->len2)) return fail(RTMI_ERR_INVALID, "light: len2 must be >= 0, finite and not NaN");
+    if (!std::isfinite(li->orig[0]) || !std::isfinite(li->orig[1]) || !std::isfinite(li->orig[2]))
+        return fail(RTMI_ERR_INVALID, "light: orig must be finite");
+    if (!std::isfinite(li->bias)) return fail(RTMI_ERR_INVALID, "light: bias must be finite");
+    if (vp->samples_per_pixel == 0) return fail(RTMI_ERR_INVALID, "samples_per_pixel must be >= 1");
+    if (nsamples == 0) return fail(RTMI_ERR_INVALID, "nsamples must be >= 1");
+    if ((uint64_t)sample0 + nsamples > vp->samples_per_pixel)
+        return fail(RTMI_ERR_INVALID, "samples [sample0, sample0 + nsamples) outside the frame's samples_per_pixel");
+    if (sample0 & RTMI_KEY_JITTER) return fail(RTMI_ERR_UNSUPPORTED, "sample0 above 2^31");  // DView::sample_key
+    if ((uint64_t)nsamples * li->rays >= (1ull << 24))
+        return fail(RTMI_ERR_UNSUPPORTED, "light: nsamples * rays must stay below 2^24 (the per-pixel count is exact in f32)");
+    if (tile->nrows == 0) { *empty = true; return RTMI_OK; }
+    v1 = *vp;
+    v1.maxdepth = 1;
+    return check_view(&v1, tile);
+}
+
+int rtmi_render_light_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile, uint32_t sample0,
+                             uint32_t nsamples, const rtmi_light_t* li, void* shadow_device, void* irradiance_device, void* hip_stream,
+                             rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    rtmi_viewport_t v1;
+    bool empty;
+    const int rc = check_light(s, vp, tile, sample0, nsamples, li, shadow_device, irradiance_device, v1, &empty);
+    if (rc != RTMI_OK || empty) return rc;
+    if (s->d.nspheres)
+        return fail(RTMI_ERR_UNSUPPORTED, "light: the scene has analytic spheres (a build-defined primitive whose normal needs the hit point)");
+    const LightCall call{*li, (float*)shadow_device, (float*)irradiance_device};
+    return render_tile(s, &v1, seed, tile, sample0, nsamples, nullptr, nullptr, hip_stream, stats, nullptr, 0, nullptr, nullptr, &call);
+}
+
+// Host variant: the planes are rendered into the handle's own device buffer and copied out once (4 B per pixel and plane).
+int rtmi_render_light(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows, uint32_t sample0,
+                      uint32_t nsamples, const rtmi_light_t* li, float* shadow_host, float* irradiance_host, rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    const rtmi_tile_t tile{row0, nrows, nrows ? nrows : 1u, 0u};
+    rtmi_viewport_t v1;
+    bool empty;
+    const int rc0 = check_light(s, vp, &tile, sample0, nsamples, li, shadow_host, irradiance_host, v1, &empty);
+    if (rc0 != RTMI_OK || empty) return rc0;
+    if (s->d.nspheres)
+        return fail(RTMI_ERR_UNSUPPORTED, "light: the scene has analytic spheres (a build-defined primitive whose normal needs the hit point)");
+    const uint64_t npix = (uint64_t)nrows * vp->width;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(s->light_out.ensure(2 * npix));
+    float* const d_sh = shadow_host ? s->light_out.p : nullptr;
+    float* const d_ir = irradiance_host ? s->light_out.p + npix : nullptr;
+    const LightCall call{*li, d_sh, d_ir};
+    const int rc = render_tile(s, &v1, seed, &tile, sample0, nsamples, nullptr, nullptr, nullptr, stats, nullptr, 0, nullptr, nullptr, &call);
+    if (rc != RTMI_OK) return rc;
+    if (d_sh) HIPCHK(hipMemcpy(shadow_host, d_sh, npix * sizeof(float), hipMemcpyDeviceToHost));
+    if (d_ir) HIPCHK(hipMemcpy(irradiance_host, d_ir, npix * sizeof(float), hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
 

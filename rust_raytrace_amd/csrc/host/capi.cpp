@@ -314,6 +314,37 @@ int rth_caster_walk_ao_device(rth_scene_t* s, uint32_t w, uint32_t h, const floa
         if (stats) *stats = ctx.stats;
     });
 }
+int rth_caster_walk_light(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp, uint64_t row0,
+                          uint64_t nrows, uint32_t sample0, uint32_t nsamples, const rtmi_light_t* light, float* shadow_host,
+                          float* irradiance_host, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!light) throw std::runtime_error("NULL rtmi_light_t");
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        const LightSource ls{make_vec(light->orig), light->len2};
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_rays_light(v, s->scene, (size_t)row0, (size_t)nrows, sample0, nsamples, ls, light->rays, light->flags, light->bias,
+                                     shadow_host, irradiance_host, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
+int rth_caster_walk_light_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                                 const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, const rtmi_light_t* light,
+                                 void* shadow_device, void* irradiance_device, void* hip_stream, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!tile) throw std::runtime_error("NULL tile");
+        if (!light) throw std::runtime_error("NULL rtmi_light_t");
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        const LightSource ls{make_vec(light->orig), light->len2};
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_light_device(v, s->scene, *tile, sample0, nsamples, ls, light->rays, light->flags, light->bias, shadow_device,
+                                       irradiance_device, hip_stream, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
 int rth_caster_denoise(rth_scene_t* s, uint32_t w, uint32_t h, const float* color_host, const float* albedo_host,
                        const float* normal_host, const rtmi_denoise_t* params, float* out_host) {
     return guarded([&] {

@@ -785,6 +785,38 @@ void HipRayCaster::walk_ao_device(const Viewport& v, const Scene& s, const rtmi_
     progress.stats = st;
 }
 
+static rtmi_light_t light_abi(const LightSource& light, uint32_t rays, uint32_t flags, float bias) {
+    return rtmi_light_t{{light.orig.v[0], light.orig.v[1], light.orig.v[2]}, light.len2, rays, flags, bias};
+}
+
+void HipRayCaster::walk_rays_light(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
+                                   const LightSource& light, uint32_t rays, uint32_t flags, float bias, float* shadow, float* irradiance,
+                                   ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    const rtmi_light_t li = light_abi(light, rays, flags, bias);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_light(h, &av, seed, (uint32_t)row0, (uint32_t)nrows, sample0, nsamples, &li, shadow, irradiance, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_light: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
+void HipRayCaster::walk_light_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
+                                     const LightSource& light, uint32_t rays, uint32_t flags, float bias, void* shadow_device,
+                                     void* irradiance_device, void* hip_stream, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    const rtmi_light_t li = light_abi(light, rays, flags, bias);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_light_device(h, &av, seed, &tile, sample0, nsamples, &li, shadow_device, irradiance_device, hip_stream, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_light_device: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
 void HipRayCaster::variance(const Scene& s, const Color* accum, const Color* sumsq, const uint32_t* counts, uint64_t npixels, Color* out) {
     rtmi_scene_t* h = resident(s);
     const int rc = rtmi_variance(h, reinterpret_cast<const float*>(accum), reinterpret_cast<const float*>(sumsq), counts, npixels,

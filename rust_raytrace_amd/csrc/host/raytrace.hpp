@@ -104,6 +104,14 @@ BoundingBox build_bounding_box_gpu(const std::vector<Triangle>& tris, const Poin
                                    size_t minobjs, int device = 0);
 BoundingBox build_trivial_bounding_box(const std::vector<Triangle>& tris, const Point& orig, float len2);  // :847-856
 
+// raytrace.rs:595-598: a box light, `orig` its corner and `len2` its edge (0: a point light).  The reference declares it and
+// spells its shadow ray out in a comment (_get_shadow_ray, :600-610) without running either; here it is the light of the
+// direct-light buffer (HipRayCaster::walk_rays_light, rtmi_render_light* in rtmi.h, which defines the shadow ray).
+struct LightSource {
+    Point orig;
+    float len2;
+};
+
 // Analytic sphere: NOT in the reference at this revision (only Triangle is Collidable, raytrace.rs:399; make_sphere
 // tessellates).  A build-defined extension named by BASELINE's north_star; semantics in include/rtmi.h (rtmi_sphere_t)
 // and, operation by operation, in DESIGN.md 4.6.  Parity with the Rust binary: unpinned.
@@ -224,6 +232,15 @@ public:
                       const rtmi_ao_t& ao, float* out, ProgressCtx& progress);
     void walk_ao_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
                         const rtmi_ao_t& ao, void* ao_device, void* hip_stream, ProgressCtx& progress);
+    // Direct light (rtmi_render_light / rtmi_render_light_device, which rtmi.h defines): two floats per pixel, the share of
+    // `rays` samples of `light` per primary sample of [sample0, sample0 + nsamples) that are visible from the first hit, and
+    // the mean of n . dir over them.  flags: RTMI_LIGHT_UNBOUNDED or 0; bias: the smudge factor.  Either plane may be null.
+    void walk_rays_light(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
+                         const LightSource& light, uint32_t rays, uint32_t flags, float bias, float* shadow, float* irradiance,
+                         ProgressCtx& progress);
+    void walk_light_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
+                           const LightSource& light, uint32_t rays, uint32_t flags, float bias, void* shadow_device,
+                           void* irradiance_device, void* hip_stream, ProgressCtx& progress);
     // Variance-guided denoising (rtmi_variance* / rtmi_denoise_var* / rtmi_render_adaptive_denoised): variance() turns the
     // moments of an adaptive render (accum, sumsq, counts of npixels pixels) into the variance image the filter takes beside
     // denoise()'s images; var_out (may be null) receives the propagated variance.  walk_adaptive_denoised runs the adaptive

@@ -707,6 +707,100 @@ class HipRayCaster:
                                                   C.byref(st), C.byref(wall)))
         return ProgressCtx(st.rays, wall.value, st.as_dict())
 
+    LIGHT_UNBOUNDED = 1
+
+    @staticmethod
+    def light_params(orig=None, len2=None, rays=None, unbounded=False, bias=None):
+        """rtmi_light_t from the library's defaults (rtmi_light_defaults: orig (0, 0, 0), len2 0, 4 rays, bounded, bias 0.005)
+        with the given fields replaced.  Raises ValueError for what the library would refuse."""
+        a = _ffi.Light()
+        _ffi.lib().rtmi_light_defaults(C.byref(a))
+        if orig is not None:
+            o = [float(x) for x in orig]
+            if len(o) != 3 or not all(np.isfinite(x) for x in o):
+                raise ValueError("orig must be three finite numbers")
+            a.orig[0], a.orig[1], a.orig[2] = o
+        if len2 is not None:
+            if not float(len2) >= 0.0 or not np.isfinite(float(len2)):
+                raise ValueError("len2 must be >= 0, finite and not NaN")
+            a.len2 = float(len2)
+        if rays is not None:
+            if not 1 <= int(rays) <= 256:
+                raise ValueError("rays must be in [1, 256]")
+            a.rays = int(rays)
+        if unbounded:
+            a.flags = HipRayCaster.LIGHT_UNBOUNDED
+        if bias is not None:
+            if not np.isfinite(float(bias)):
+                raise ValueError("bias must be finite")
+            a.bias = float(bias)
+        return a
+
+    def _light_args(self, v, sample0, nsamples, orig, len2, rays, unbounded, bias):
+        k0, n = self._feature_samples(v, sample0, nsamples)
+        a = self.light_params(orig, len2, rays, unbounded, bias)
+        if n * a.rays >= 1 << 24:
+            raise ValueError("nsamples * rays must stay below 2^24")
+        return k0, n, a
+
+    def walk_rays_light(self, v, s, orig=None, len2=None, rays=None, unbounded=False, bias=None, sample0=0, nsamples=None,
+                        shadow=True, irradiance=True):
+        """Direct light of the whole frame from one box light (rtmi_render_light; include/rtmi.h defines it): two (H, W)
+        float32 planes.  shadow: per pixel the share of `rays` samples of the light (corner `orig`, edge `len2`; 0 = a point
+        light) per primary sample of [sample0, sample0 + nsamples) (default: all from sample0) that are visible from the first
+        hit, 1.0 where every sample missed.  irradiance: the mean of n . dir over those visible samples.  unbounded: anything
+        along the shadow ray shadows, even beyond the light.  The primary rays are walk_rays' own (same seed, same jitter);
+        v.maxdepth is not used.  None takes the library's default.  shadow / irradiance: True allocates the plane, an array
+        is filled in place, False / None leaves it out (not both).  Returns (shadow, irradiance, ctx)."""
+        k0, n, a = self._light_args(v, sample0, nsamples, orig, len2, rays, unbounded, bias)
+        shape = (v.height, v.width)
+        planes = []
+        for name, x in (("shadow", shadow), ("irradiance", irradiance)):
+            if x is True:
+                x = np.zeros(shape, np.float32)
+            elif x is False or x is None:
+                x = None
+            elif not isinstance(x, np.ndarray) or x.dtype != np.float32 or not x.flags.c_contiguous or x.shape != shape:
+                raise ValueError(f"{name} must be a C-contiguous float32 array of shape {shape}")
+            planes.append(x)
+        if planes[0] is None and planes[1] is None:
+            raise ValueError("at least one of shadow and irradiance is needed")
+        if planes[0] is not None and planes[1] is not None and np.shares_memory(planes[0], planes[1]):
+            raise ValueError("shadow and irradiance must not alias")
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        ptr = [_p(x) if x is not None else None for x in planes]
+        _chk(_ffi.lib().rth_caster_walk_light(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, 0, v.height, k0, n,
+                                              C.byref(a), ptr[0], ptr[1], C.byref(st), C.byref(wall)))
+        return planes[0], planes[1], ProgressCtx(st.rays, wall.value, st.as_dict())
+
+    def walk_rays_light_device(self, v, s, shadow, irradiance, tile=None, orig=None, len2=None, rays=None, unbounded=False, bias=None,
+                               sample0=0, nsamples=None, stream=None):
+        """The same into torch tensors on the scene's device (rtmi_render_light_device) for a striped row set tile = (row0,
+        nrows, stripe_rows, stripe_step) (default: the whole frame): `shadow` and `irradiance` are contiguous float32 tensors
+        of nrows * width elements each (either may be None, not both, and they must not overlap), written by work enqueued on
+        `stream` (a torch stream, a raw HIP stream pointer or None).  Returns ctx."""
+        k0, n, a = self._light_args(v, sample0, nsamples, orig, len2, rays, unbounded, bias)
+        t = _ffi.Tile(*[int(x) for x in (tile if tile is not None else (0, v.height, v.height, 0))])
+        want = int(t.nrows) * int(v.width)
+        if shadow is None and irradiance is None:
+            raise ValueError("at least one of shadow and irradiance is needed")
+        for name, x in (("shadow", shadow), ("irradiance", irradiance)):
+            if x is not None and (not hasattr(x, "data_ptr") or not x.is_cuda or str(x.dtype) != "torch.float32" or not x.is_contiguous()
+                                  or x.numel() != want):
+                raise ValueError(f"{name} must be a contiguous float32 tensor of {want} elements on the device")
+        if shadow is not None and irradiance is not None and abs(shadow.data_ptr() - irradiance.data_ptr()) < 4 * want:
+            raise ValueError("shadow and irradiance must not overlap")
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        ptr = [C.c_void_p(x.data_ptr()) if x is not None else None for x in (shadow, irradiance)]
+        _chk(_ffi.lib().rth_caster_walk_light_device(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, C.byref(t), k0, n,
+                                                     C.byref(a), ptr[0], ptr[1], C.c_void_p(getattr(stream, "cuda_stream", stream) or 0),
+                                                     C.byref(st), C.byref(wall)))
+        return ProgressCtx(st.rays, wall.value, st.as_dict())
+
     DENOISE_DEMODULATE = 1
 
     @staticmethod
