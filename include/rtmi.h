@@ -577,7 +577,8 @@ int rtmi_occluded_device(rtmi_scene_t* scene, uint64_t n, const void* orig4_devi
  * tuning changes a bit of the result.  The device variant enqueues on hip_stream like rtmi_render_tile_device; the host variant
  * renders rows [row0, row0 + nrows) and copies 4 B per pixel out.
  * Not here: AO for batches of views and for rtmi_render_frame_multi, AO as a guide of the denoisers, cosine-weighted or
- * otherwise importance-sampled variants. */
+ * otherwise importance-sampled variants.  (The shaded preview that multiplies this term in per sample, with the primary rays
+ * traced once for AO and every light, is rtmi_render_preview*, below.) */
 typedef struct rtmi_ao {
     uint32_t rays;    /* K: AO rays per primary sample that hits, 1..256 */
     uint32_t flags;   /* must be 0 */
@@ -651,8 +652,9 @@ int rtmi_render_ao(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed
  * 4 B per candidate) lives on the handle, grows on demand and is freed by rtmi_scene_destroy; a batch holds at most
  * batch_paths candidates.  No tuning changes a bit of the result.  The device variant enqueues on hip_stream like
  * rtmi_render_tile_device; the host variant renders rows [row0, row0 + nrows) and copies 4 B per pixel and plane out.
- * Not here: several lights in one call, a light colour or intensity (the caller multiplies), shadow rays inside color_ray
- * (DESIGN.md 7), batches of views and rtmi_render_frame_multi, the buffer as a denoiser guide, importance sampling. */
+ * Not here: shadow rays inside color_ray, batches of views and rtmi_render_frame_multi, the buffer as a denoiser
+ * guide, importance sampling.  (Several lights in one call, each with a colour, composed per sample with albedo and AO:
+ * rtmi_render_preview*, below, which also returns these two planes for every light.) */
 enum { RTMI_LIGHT_UNBOUNDED = 1u << 0 };
 typedef struct rtmi_light {
     float orig[3];   /* LightSource.orig: the corner of the light's box                 */
@@ -668,6 +670,79 @@ int rtmi_render_light_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uin
 int rtmi_render_light(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
                       uint32_t sample0, uint32_t nsamples, const rtmi_light_t* light, float* shadow_host, float* irradiance_host,
                       rtmi_stats_t* stats);
+
+/* A shaded preview in one call: albedo, ambient occlusion and up to four coloured box lights composed PER
+ * SAMPLE on the device, from one primary pass per batch and one any-hit walk of the AO rays and every light's live shadow
+ * rays together.  The per-pixel buffers of rtmi_render_features*, rtmi_render_ao* and rtmi_render_light* are means over a
+ * pixel's samples, and a product of means is not the mean of the products: a pixel half on a surface and half on the sky
+ * would light its sky half.  The composition therefore needs the per-sample terms, which exist on the device only.
+ * Build-defined like those three calls: what follows IS the definition, and tests/preview_ref.py pins it bit for bit.  All
+ * arithmetic is f32, no contraction.
+ * Primary rays, (tri, t, face), n and point: exactly those of rtmi_render_features_device for the same (vp, seed, tile,
+ * sample0, nsamples); vp->maxdepth is not consulted.
+ * AO rays of a sample that hit: exactly rtmi_render_ao*'s for preview->ao (RNG blocks 0x80000000 | k), Ka = ao.rays of them.
+ * Candidates of light l: exactly rtmi_render_light*'s for preview->lights[l] (RNG blocks 0xC0000000 | k), K_l = lights[l].rays
+ * of them.  The blocks are the same for every light: the lights' jitter is correlated, so that every layer equals its own
+ * single call.
+ * Per sample s of pixel p, with a = the features call's per-sample albedo (the sky's colour on a miss, 0 on an edge face):
+ *   a miss:  e = a (the sky, unlit);
+ *   a hit, edge faces included:
+ *     f   = (float)v * (1.f / (float)Ka), v = the number of the sample's Ka AO rays that are visible; f = 1.f when Ka == 0;
+ *     g_l = acc * (1.f / (float)K_l), acc = 0.f, then acc = acc + c for the live and visible candidates of light l in k order;
+ *     per channel c:  L = ambient[c] * f;  for l = 0 .. nlights-1:  L = L + light_color[l][c] * g_l  (a multiplication, then
+ *                     an addition);  e[c] = a[c] * L.
+ *   No case is special: non-finite values propagate as the arithmetic gives them.
+ * Per pixel: acc = 0.f, then acc = acc + e_s in sample order; color = acc * (1.f / (float)nsamples), lane 3 = 0.
+ * Layers (rtmi_preview_out_t; any may be NULL, not all, and no two may overlap as byte ranges): each equals, bit for bit, what
+ * the single call returns for the same parameters on the same handle: albedo / normal / ids are rtmi_render_features_device's
+ * three buffers, ao is rtmi_render_ao_device's plane for preview->ao, plane l of shadow / irradiance (at l * tile pixels) is
+ * rtmi_render_light_device's for lights[l].  color with albedo and normal feeds rtmi_denoise_device directly.
+ * Scenes: as rtmi_render_ao* and rtmi_render_light*.  RTMI_ERR_UNSUPPORTED for a scene with analytic spheres and for
+ * nsamples * Ka or any nsamples * K_l >= 2^24.
+ * RTMI_ERR_INVALID, before any HIP call and before the scene is used, stats cleared: a NULL scene, viewport, tile, preview or
+ * out; all outputs NULL, or two that overlap; nlights > RTMI_PREVIEW_MAX_LIGHTS; non-zero flags; a non-finite ambient or used
+ * light colour; every parameter check of rtmi_render_ao* on `ao` except that rays == 0 is allowed (no AO rays, f = 1.f);
+ * every parameter check of rtmi_render_light* on each used light (the message names the light's index); out->ao with ao.rays
+ * == 0; out->shadow or out->irradiance with nlights == 0; nsamples == 0; sample0 + nsamples > S; every viewport and tile check
+ * of the features call.  An empty tile returns RTMI_OK and touches nothing.  ao.rays == 0 && nlights == 0 is valid: a flat
+ * albedo preview, and no walk is launched.
+ * stats: rays = pixels * nsamples + (samples that hit) * Ka + the live rays of every light; pipeline = 1; primary_ms = the
+ * primary closest-hit launches, bounce_ms = the shared walk, trace_ms their sum; trace_launches = 2 per batch, 1 per batch
+ * without secondary rays.  With RTMI_OPT_COUNTERS the counters are the primaries' work plus the walk's actual work.
+ * How: per batch, on one library stream: the features call's primary pass (and k_features when albedo, normal or ids are
+ * asked for); k_preview_rays stages a block's hit paths once and writes their Ka AO rays and every light's live candidates
+ * into ONE queue whose counter is the walk's ray count (it never leaves the device; one limit array: AO rays store radius,
+ * bounded lights r, unbounded lights +inf, which rtmi_occluded's rule treats as the NULL limit), and each path's albedo; one
+ * any-hit walk (or the closest-hit launch, where rtmi_occluded uses that); k_preview_resolve folds per pixel in the defined
+ * order.  A path counts as Ka + the sum of K_l queue entries: a batch's entries stay within batch_paths.  The queue lives on
+ * the handle, grows on demand and is freed by rtmi_scene_destroy.  No tuning changes a bit of the result.
+ * Not here: previews of batches of views and of rtmi_render_frame_multi, sums continued across calls, importance sampling,
+ * shadow rays inside color_ray, a denoised-preview one-call wrapper. */
+enum { RTMI_PREVIEW_MAX_LIGHTS = 4 };
+typedef struct rtmi_preview {
+    float ambient[3];          /* offset 0                                                  */
+    uint32_t nlights;          /* 12: 0..RTMI_PREVIEW_MAX_LIGHTS                            */
+    uint32_t flags;            /* 16: must be 0                                             */
+    rtmi_ao_t ao;              /* 20: ao.rays == 0 is valid here: no AO rays, factor 1.f    */
+    rtmi_light_t lights[4];    /* 36: entries >= nlights are ignored                        */
+    float light_color[4][3];   /* 148                                                       */
+} rtmi_preview_t;              /* 196 bytes */
+typedef struct rtmi_preview_out {   /* any may be NULL, not all; no two may overlap as byte ranges */
+    void* color;       /* float4 per pixel of the tile: rgb, lane 3 = 0 (what rtmi_render_device writes) */
+    void* albedo;      /* float4  } exactly rtmi_render_features_device's three buffers                   */
+    void* normal;      /* float4  }                                                                        */
+    void* ids;         /* uint32  }                                                                        */
+    void* ao;          /* f32 per pixel: exactly rtmi_render_ao_device's plane for preview->ao             */
+    void* shadow;      /* nlights planes of f32, plane l at l * (tile pixels): rtmi_render_light_device's  */
+    void* irradiance;  /* likewise                                         shadow / irradiance for lights[l] */
+} rtmi_preview_out_t;
+void rtmi_preview_defaults(rtmi_preview_t* preview);  /* ambient 0.3, nlights 0, flags 0, rtmi_ao_defaults, rtmi_light_defaults x 4, colours 1 */
+int rtmi_render_preview_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile,
+                               uint32_t sample0, uint32_t nsamples, const rtmi_preview_t* preview,
+                               const rtmi_preview_out_t* out_device, void* hip_stream, rtmi_stats_t* stats);
+int rtmi_render_preview(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
+                        uint32_t sample0, uint32_t nsamples, const rtmi_preview_t* preview, const rtmi_preview_out_t* out_host,
+                        rtmi_stats_t* stats);
 
 /* Per-ray debug records (the reference's Scene { debug_ctx, debug_en }, raytrace.rs:1297-1303, debug.rs): what the
  * octree walk did for each ray, taken from the production walk itself (k_trace_record: the walk of rtmi_trace in a

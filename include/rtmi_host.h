@@ -143,6 +143,15 @@ int rth_caster_walk_light_device(rth_scene_t* s, uint32_t w, uint32_t h, const f
                                  const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, const rtmi_light_t* light,
                                  void* shadow_device, void* irradiance_device, void* hip_stream, rtmi_stats_t* stats,
                                  double* wall_seconds);
+/* The shaded preview (rtmi_render_preview / rtmi_render_preview_device, which rtmi.h defines) on the scene's resident copy:
+ * albedo, ambient occlusion and up to four coloured box lights composed per sample, with the layers `out` asks for.  maxdepth
+ * is not consulted; the primary rays use the caster's seed. */
+int rth_caster_walk_preview(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp, uint64_t row0,
+                            uint64_t nrows, uint32_t sample0, uint32_t nsamples, const rtmi_preview_t* preview,
+                            const rtmi_preview_out_t* out_host, rtmi_stats_t* stats, double* wall_seconds);
+int rth_caster_walk_preview_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                                   const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, const rtmi_preview_t* preview,
+                                   const rtmi_preview_out_t* out_device, void* hip_stream, rtmi_stats_t* stats, double* wall_seconds);
 /* Per-ray records (rtmi_trace_records / rtmi_primary_records, same buffers and size-query idiom) on the scene's
  * resident copy; the primary records use the caster's seed. */
 int rth_caster_trace_records(rth_scene_t* s, uint64_t n, const float* orig4, const float* dir4, rtmi_ray_record_t* recs,

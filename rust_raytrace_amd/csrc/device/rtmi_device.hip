@@ -379,6 +379,7 @@ __global__ void __launch_bounds__(256) k_trace(DScene sc, const float4* __restri
 #include "denoise.hpp"
 #include "ao.hpp"
 #include "light.hpp"
+#include "preview.hpp"
 namespace rtmi {
 
 
@@ -1091,6 +1092,18 @@ struct rtmi_scene {
         void release() { qo.release(); qd.release(); tmax.release(); c.release(); slot.release(); occ.release(); }
     } light[RTMI_MAX_STREAMS];
     DevBuf<float> light_out;
+    // rtmi_render_preview*: per stream, the one secondary-ray queue of a batch (origins, directions, limits, n . dir of the
+    // lights' live rays, the answer bytes), each path's first AO entry, each light candidate's entry and each path's albedo (grow
+    // only); the seven outputs of the host variant.  No other call reads or writes them.
+    struct PreviewBuf {
+        DevBuf<float4> qo, qd, alb;
+        DevBuf<float> tmax, c;
+        DevBuf<uint32_t> aslot, lslot;
+        DevBuf<uint8_t> occ;
+        void release() { qo.release(); qd.release(); alb.release(); tmax.release(); c.release(); aslot.release(); lslot.release(); occ.release(); }
+    } pv[RTMI_MAX_STREAMS];
+    DevBuf<float4> pv_out4;
+    DevBuf<float> pv_out1;
     DevBuf<uint8_t> mstage, mframe;  // rtmi_render_frame_multi, root scene: received bands / the frame
     hipStream_t mstream = nullptr;   // rtmi_render_frame_multi: this scene's band stream
     std::vector<ncclComm_t> comms;   // root scene, RTMI_FRAME_RCCL: one communicator per scene of the last device list
@@ -1537,6 +1550,8 @@ int rtmi_scene_destroy(rtmi_scene_t* s) {
     s->ao_out.release();
     for (auto& l : s->light) l.release();
     s->light_out.release();
+    for (auto& b : s->pv) b.release();
+    s->pv_out4.release(); s->pv_out1.release();
     if (s->vcams_ev) (void)hipEventDestroy(s->vcams_ev);
     if (s->mstream) (void)hipStreamDestroy(s->mstream);
     if (!s->comms.empty()) { if (Rccl* r = rccl_api()) for (ncclComm_t c : s->comms) (void)r->CommDestroy(c); }
@@ -1715,7 +1730,7 @@ static bool occluded_anyhit(const rtmi_scene* s) {
 }
 // The any-hit walk of queue `pass` of the stream's control block (ctrl->count[pass] rays, set on the stream before this):
 // rays qo / qd, limits tmax (null: +inf), one byte per ray to occ.  pass 0 with n rays: rtmi_occluded*.  pass 1: the AO rays
-// of rtmi_render_ao* or the shadow rays of rtmi_render_light*, whose count exists on the device only (0 is a valid count); n is then an upper bound (the closest-hit fallback writes the
+// of rtmi_render_ao*, the shadow rays of rtmi_render_light* or both kinds of rtmi_render_preview*, whose count exists on the device only (0 is a valid count); n is then an upper bound (the closest-hit fallback writes the
 // workspace's hit records, sized for it).  `stop` is recorded right after the walk kernel.
 static void launch_occluded(rtmi_scene* s, Work& w, hipStream_t st, uint64_t n, const float4* qo, const float4* qd, const float* tmax,
                             uint8_t* occ, int pass, hipEvent_t stop) {
@@ -1822,6 +1837,14 @@ struct FeatOut { float4* albedo; float4* normal; uint32_t* ids; };
 struct AoCall { rtmi_ao_t p; float* out; };
 // A direct-light call (rtmi_render_light*): its parameters and its two planes, one f32 per pixel of the tile, either may be null
 struct LightCall { rtmi_light_t p; float* shadow; float* irradiance; };
+// A preview call (rtmi_render_preview*): its parameters as the kernels take them, the entries a path may queue (Ka + sum K_l)
+// and its outputs, each may be null (shadow / irradiance: nlights planes of `plane` floats)
+struct PreviewCall {
+    PvArgs a;
+    uint32_t per_path;
+    float4* color; FeatOut fo; float* ao; float* shadow; float* irradiance;
+    size_t plane;
+};
 // One render_tile call: what it renders, and its plan (plan_tile)
 struct TileCall {
     uint64_t seed;
@@ -1831,8 +1854,9 @@ struct TileCall {
     const FeatOut* fo;  // a features call: the primary pass alone (maxdepth = 1, per-pass pipeline), k_features for k_shade + k_accum
     const AoCall* ao;   // an AO call: a features call's primary pass, then k_ao_rays, the any-hit walk of queue 1 and k_ao_resolve
     const LightCall* li;  // a direct-light call: likewise with k_light_rays and k_light_resolve
+    const PreviewCall* pv;  // a preview call: the primary pass once, k_preview_rays, one walk of queue 1, k_preview_resolve
     ViewTab vt;  // VIEWS: the view table (cams == nullptr otherwise)
-    Samp mode;  // LIST with lp, PASS with accum, fo, ao or li, VIEWS with vt.cams, FRAME otherwise
+    Samp mode;  // LIST with lp, PASS with accum, fo, ao, li or pv, VIEWS with vt.cams, FRAME otherwise
     bool counting, path_kernels;
     uint32_t nsub;
     uint64_t pix_per_batch, max_npix;  // max_npix: pixels of the largest sub-tile
@@ -1872,7 +1896,7 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
     // path kernels (pipeline 3; 0 = automatic): exact-octree scenes get pass 0 from k_path_primary, which generates, traces and
     // shades the primary rays in one kernel.  Everything else (pipeline 1, linear list, generic tree, BVH mode,
     // analytic spheres) starts with k_gen.  Both then run one closest-hit + one shading launch per bounce pass.
-    c.path_kernels = !c.fo && !c.ao && !c.li && s->tune.pipeline != 1u && s->octree && !s->root_is_leaf &&
+    c.path_kernels = !c.fo && !c.ao && !c.li && !c.pv && s->tune.pipeline != 1u && s->octree && !s->root_is_leaf &&
                      !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) && s->d.nspheres == 0;
     // streams = 0 (automatic): one stream for path-kernel tiles of 2^26 paths and more, three otherwise (the per-pass
     // pipelines -- BVH mode: 29.6 ms on three streams, 35.2 on one -- have elementwise kernels to hide).  Since k_shade stopped being
@@ -1887,8 +1911,8 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
     // sub-tile's k_features waits for wave slots behind the other sub-tiles' persistent k_trace_oct launches (config 3's frame
     // of 2^28 paths: 108.0 and 111.0 ms on one stream in two jobs, 113.9 and 113.7 on three; 2^25 paths: 16.4 and 16.3 against
     // 17.5 and 17.3).
-    // AO and direct-light calls (c.ao, c.li): as features calls.
-    const uint32_t auto_streams = (c.fo || c.ao || c.li || (c.path_kernels && npix_call * spp >= (1ull << 26)) || (lp && npix_call < npix)) ? 1u : 3u;
+    // AO, direct-light and preview calls (c.ao, c.li, c.pv): as features calls.
+    const uint32_t auto_streams = (c.fo || c.ao || c.li || c.pv || (c.path_kernels && npix_call * spp >= (1ull << 26)) || (lp && npix_call < npix)) ? 1u : 3u;
     uint32_t nsub = std::min<uint32_t>(s->tune.streams ? s->tune.streams : auto_streams, (uint32_t)RTMI_MAX_STREAMS);
     nsub = (uint32_t)std::min<uint64_t>(nsub, lp ? npix_call : nrows);
     if (npix_call * spp < s->tune.subtile_min_paths) nsub = 1;
@@ -1913,9 +1937,10 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
     }
 
     // batch = whole pixels with all their samples; an AO call counts a path as its K AO rays (a direct-light call: its K
-    // candidates), so that the ray queue of a batch stays within batch_paths entries and below the walk's 2^31
+    // candidates, a preview call: its Ka + sum K_l entries), so that the ray queue of a batch stays within batch_paths entries
+    // and below the walk's 2^31
     const size_t want_paths = (size_t)std::max<uint64_t>(s->tune.batch_paths, 1) / nsub;
-    const uint64_t per_pix = (uint64_t)spp * (c.ao ? c.ao->p.rays : c.li ? c.li->p.rays : 1u);
+    const uint64_t per_pix = (uint64_t)spp * (c.ao ? c.ao->p.rays : c.li ? c.li->p.rays : c.pv ? std::max(c.pv->per_path, 1u) : 1u);
     uint64_t pix_per_batch = std::max<uint64_t>(1, want_paths / per_pix);
     uint64_t max_sub_npix = 0;
     for (uint32_t t = 0; t < nsub; t++) max_sub_npix = std::max(max_sub_npix, c.sub[t].npix);
@@ -1934,7 +1959,7 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
         const size_t paths = (size_t)(std::min<uint64_t>(pix_per_batch, c.sub[t].npix) * spp);
         // an AO call on a scene without an any-hit kernel: the closest-hit launch of the AO rays writes the workspace's hit records
         // (a direct-light call likewise: its candidates bound its live rays)
-        const size_t nao = c.ao ? paths * c.ao->p.rays : c.li ? paths * c.li->p.rays : 0;
+        const size_t nao = c.ao ? paths * c.ao->p.rays : c.li ? paths * c.li->p.rays : c.pv ? paths * c.pv->per_path : 0;
         int rc = ensure_workspace(s->w[t], nao && !occluded_anyhit(s) ? nao : paths, c.maxdepth);
         if (rc != RTMI_OK) return rc;
         if (c.ao) {
@@ -1946,6 +1971,11 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
             rtmi_scene::LightBuf& l = s->light[t];
             HIPCHK(l.qo.ensure(nao)); HIPCHK(l.qd.ensure(nao)); HIPCHK(l.c.ensure(nao)); HIPCHK(l.occ.ensure(nao)); HIPCHK(l.slot.ensure(nao));
             if (!(c.li->p.flags & RTMI_LIGHT_UNBOUNDED)) HIPCHK(l.tmax.ensure(nao));
+        }
+        if (c.pv) {
+            rtmi_scene::PreviewBuf& b = s->pv[t];
+            HIPCHK(b.qo.ensure(nao)); HIPCHK(b.qd.ensure(nao)); HIPCHK(b.tmax.ensure(nao)); HIPCHK(b.c.ensure(nao)); HIPCHK(b.occ.ensure(nao));
+            HIPCHK(b.alb.ensure(paths)); HIPCHK(b.aslot.ensure(paths)); HIPCHK(b.lslot.ensure(paths * (c.pv->per_path - c.pv->a.Ka)));
         }
     }
     return RTMI_OK;
@@ -2060,6 +2090,31 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
         HIPCHK(hipGetLastError());
         return RTMI_OK;
     }
+    if (c.pv) {  // the primary rays' closest hits ONCE (and their feature means), the AO rays and every light's live rays in queue 1, one walk, the per-pixel folds
+        const PreviewCall& p = *c.pv;
+        rtmi_scene::PreviewBuf& b = s->pv[t];
+        HIPCHK(hipEventRecord(w.pass_ev[0], st));
+        launch_trace(s, w, st, w.qo[0].p, w.qd[0].p, 0, c.counting, w.pass_ev[1]);
+        HIPCHK(hipGetLastError());
+        // before the walk: its closest-hit fallback writes the workspace's hit records
+        if (p.fo.albedo || p.fo.normal || p.fo.ids)
+            hipLaunchKernelGGL(k_features, ew_grid, ew_block, 0, st, s->d, np, c.spp, w.hit_tf.p, w.hit_t.p, (float*)p.fo.albedo,
+                               (float*)p.fo.normal, p.fo.ids, pix0, c.W, c.nsub, t, make_fastdiv(c.W), make_fastdiv(c.spp));
+        // ctrl->count[1] (zero since the batch's memset) is the compaction's counter and then the walk's ray count
+        hipLaunchKernelGGL(k_preview_rays, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, p.a, w.qo[0].p, w.qd[0].p, w.hit_tf.p,
+                           w.hit_t.p, b.qo.p, b.qd.p, b.tmax.p, b.c.p, b.aslot.p, b.lslot.p, b.alb.p, w.ctrl.p);
+        HIPCHK(hipGetLastError());
+        if (p.per_path) {
+            HIPCHK(hipEventRecord(w.pass_ev[2], st));
+            launch_occluded(s, w, st, (uint64_t)npaths * p.per_path, b.qo.p, b.qd.p, b.tmax.p, b.occ.p, 1, w.pass_ev[3]);
+            HIPCHK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_preview_resolve, ew_grid, ew_block, 0, st, np, c.spp, npaths, p.a, b.alb.p, b.aslot.p, b.lslot.p, b.occ.p, b.c.p,
+                           p.color, p.ao, p.shadow, p.irradiance, p.plane, pix0, c.W, c.nsub, t, make_fastdiv(c.W));
+        HIPCHK(hipEventRecord(w.ev[1], st));
+        HIPCHK(hipGetLastError());
+        return RTMI_OK;
+    }
     for (uint32_t pass = pass0; pass < c.maxdepth; pass++) {
         const int a = pass & 1, b = a ^ 1;
         HIPCHK(hipEventRecord(w.pass_ev[2 * pass], st));
@@ -2122,7 +2177,7 @@ static int collect_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
         sum.launches++;
         sum.trace_ms += pm;
         if (c.path_kernels) { if (pass == 0) sum.primary_ms += pm; else sum.bounce_ms += pm; }
-        if (c.ao || c.li) sum.primary_ms += pm;
+        if (c.ao || c.li || c.pv) sum.primary_ms += pm;
         if (s->verbose) fprintf(stderr, "[rtmi] stream %u batch@%llu pass %u: %u rays, trace %.3f ms, %.1f Mrays/s\n", t, (unsigned long long)p0, pass, h.count[pass], pm, h.count[pass] / (pm * 1e3));
     }
     if (c.ao) {  // the AO rays' walk: queue 1
@@ -2142,6 +2197,14 @@ static int collect_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
         sum.bounce_ms += pm;
         if (s->verbose) fprintf(stderr, "[rtmi] stream %u batch@%llu light: %u live rays, walk %.3f ms\n", t, (unsigned long long)p0, h.count[1], pm);
     }
+    if (c.pv && c.pv->per_path) {  // the one walk of the AO rays and every light's live rays: queue 1
+        float pm = 0.f;
+        HIPCHK(hipEventElapsedTime(&pm, w.pass_ev[2], w.pass_ev[3]));
+        sum.launches++;
+        sum.trace_ms += pm;
+        sum.bounce_ms += pm;
+        if (s->verbose) fprintf(stderr, "[rtmi] stream %u batch@%llu preview: %u secondary rays, walk %.3f ms\n", t, (unsigned long long)p0, h.count[1], pm);
+    }
     return RTMI_OK;
 }
 
@@ -2159,19 +2222,22 @@ static int collect_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
 // li != nullptr (no accum, no out_device; maxdepth = 1 likewise): a direct-light call (rtmi_render_light_device).  Its batches
 // run a features call's primary pass, k_light_rays, the scene's any-hit walk of the compacted live shadow rays and
 // k_light_resolve, which writes li's planes.  A batch is sized like an AO call's, in candidates.
+// pv != nullptr (no accum, no out_device; maxdepth = 1 likewise): a preview call (rtmi_render_preview_device).  Its batches run
+// a features call's primary pass once (with k_features when pv->fo asks), k_preview_rays, ONE any-hit walk of the AO rays and
+// all lights' live rays and k_preview_resolve, which writes pv's colour and planes.  A batch is sized in queue entries.
 // views > 0 (no accum): a batch of views (Samp::VIEWS, rtmi_render_views_device); vp is the stacked image (height = views *
 // the views' height) and s->hvcams holds the view table, uploaded here on hip_stream before the internal streams fork.
 static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile, uint32_t sample0,
                        uint32_t nsamples, float4* accum, void* out_device, void* hip_stream, rtmi_stats_t* stats,
                        const ListPass* lp = nullptr, uint32_t views = 0, const FeatOut* fo = nullptr, const AoCall* ao = nullptr,
-                       const LightCall* li = nullptr) {
+                       const LightCall* li = nullptr, const PreviewCall* pv = nullptr) {
     if (stats) memset(stats, 0, sizeof(*stats));
     if (tile->nrows == 0) return RTMI_OK;
     RTMI_GUARD_BEGIN
     // leftovers of the caller's own HIP calls on this thread (or of failures this library tolerated, e.g. an occupancy
     // query) must not make a launch below look refused: hipGetLastError() reports the last error of ANY runtime call
     (void)hipGetLastError();
-    if (!out_device && !accum && !fo && !ao && !li) return fail(RTMI_ERR_INVALID, "NULL argument");
+    if (!out_device && !accum && !fo && !ao && !li && !pv) return fail(RTMI_ERR_INVALID, "NULL argument");
     int rc = check_view(vp, tile);
     if (rc != RTMI_OK) return rc;
     HIPCHK(hipSetDevice(s->device));
@@ -2186,8 +2252,8 @@ static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed
     }
     TileCall c;
     c.seed = seed; c.sample0 = sample0; c.spp = nsamples; c.maxdepth = vp->maxdepth; c.W = vp->width;
-    c.accum = accum; c.out = out; c.lp = lp; c.fo = fo; c.ao = ao; c.li = li; c.vt = ViewTab{nullptr, FastDiv{}};
-    c.mode = lp ? Samp::LIST : (accum || fo || ao || li) ? Samp::PASS : views ? Samp::VIEWS : Samp::FRAME;
+    c.accum = accum; c.out = out; c.lp = lp; c.fo = fo; c.ao = ao; c.li = li; c.pv = pv; c.vt = ViewTab{nullptr, FastDiv{}};
+    c.mode = lp ? Samp::LIST : (accum || fo || ao || li || pv) ? Samp::PASS : views ? Samp::VIEWS : Samp::FRAME;
     c.counting = (s->options & RTMI_OPT_COUNTERS) != 0;
     rc = plan_tile(s, vp, tile, c);
     if (rc != RTMI_OK) return rc;
@@ -2485,6 +2551,160 @@ int rtmi_render_light(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed,
     if (rc != RTMI_OK) return rc;
     if (d_sh) HIPCHK(hipMemcpy(shadow_host, d_sh, npix * sizeof(float), hipMemcpyDeviceToHost));
     if (d_ir) HIPCHK(hipMemcpy(irradiance_host, d_ir, npix * sizeof(float), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+// ---------------------------------------------------------------- shaded preview (rtmi_render_preview*)
+void rtmi_preview_defaults(rtmi_preview_t* p) {
+    if (!p) return;
+    p->ambient[0] = p->ambient[1] = p->ambient[2] = 0.3f;
+    p->nlights = 0; p->flags = 0;
+    rtmi_ao_defaults(&p->ao);
+    for (int l = 0; l < RTMI_PREVIEW_MAX_LIGHTS; l++) {
+        rtmi_light_defaults(&p->lights[l]);
+        p->light_color[l][0] = p->light_color[l][1] = p->light_color[l][2] = 1.f;
+    }
+}
+
+// Checks of the preview entry points that come before any HIP call and before the scene is used (a CPU-only caller reaches
+// them).  RTMI_OK with *empty set: the tile has no rows, nothing to do.  v1 receives the viewport with maxdepth = 1, as for
+// features.  The outputs' byte ranges are those of a tile of tile->nrows rows.
+static int check_preview(rtmi_scene_t* s, const rtmi_viewport_t* vp, const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples,
+                         const rtmi_preview_t* pv, const rtmi_preview_out_t* out, rtmi_viewport_t& v1, bool* empty) {
+    *empty = false;
+    if (!s || !vp) return fail(RTMI_ERR_INVALID, "preview: NULL argument (scene or viewport)");
+    if (!tile) return fail(RTMI_ERR_INVALID, "preview: NULL argument (tile)");
+    if (!pv) return fail(RTMI_ERR_INVALID, "preview: NULL argument (rtmi_preview_t)");
+    if (!out) return fail(RTMI_ERR_INVALID, "preview: NULL argument (rtmi_preview_out_t)");
+    if (!out->color && !out->albedo && !out->normal && !out->ids && !out->ao && !out->shadow && !out->irradiance)
+        return fail(RTMI_ERR_INVALID, "preview: NULL outputs: at least one is required");
+    if (pv->nlights > RTMI_PREVIEW_MAX_LIGHTS) return fail(RTMI_ERR_INVALID, "preview: nlights must be in [0, 4]");
+    if (pv->flags != 0) return fail(RTMI_ERR_INVALID, "preview: flags must be 0");
+    for (int c = 0; c < 3; c++)
+        if (!std::isfinite(pv->ambient[c])) return fail(RTMI_ERR_INVALID, "preview: ambient must be finite");
+    const rtmi_ao_t& ao = pv->ao;
+    if (ao.rays > 256) return fail(RTMI_ERR_INVALID, "preview: ao.rays must be in [0, 256]");
+    if (ao.flags != 0) return fail(RTMI_ERR_INVALID, "preview: ao.flags must be 0");
+    if (!(ao.radius >= 0.f)) return fail(RTMI_ERR_INVALID, "preview: ao.radius must be >= 0 (+inf: unlimited) and not NaN");
+    if (!std::isfinite(ao.bias)) return fail(RTMI_ERR_INVALID, "preview: ao.bias must be finite");
+    for (uint32_t l = 0; l < pv->nlights; l++) {
+        const rtmi_light_t& li = pv->lights[l];
+        const std::string who = "preview: light " + std::to_string(l) + ": ";
+        if (li.rays == 0 || li.rays > 256) return fail(RTMI_ERR_INVALID, who + "rays must be in [1, 256]");
+        if (li.flags & ~(uint32_t)RTMI_LIGHT_UNBOUNDED) return fail(RTMI_ERR_INVALID, who + "unknown flags");
+        if (!(li.len2 >= 0.f) || std::isinf(li.len2)) return fail(RTMI_ERR_INVALID, who + "len2 must be >= 0, finite and not NaN");
+        if (!std::isfinite(li.orig[0]) || !std::isfinite(li.orig[1]) || !std::isfinite(li.orig[2]))
+            return fail(RTMI_ERR_INVALID, who + "orig must be finite");
+        if (!std::isfinite(li.bias)) return fail(RTMI_ERR_INVALID, who + "bias must be finite");
+        for (int c = 0; c < 3; c++)
+            if (!std::isfinite(pv->light_color[l][c])) return fail(RTMI_ERR_INVALID, who + "colour must be finite");
+    }
+    if (out->ao && ao.rays == 0) return fail(RTMI_ERR_INVALID, "preview: an ao output needs ao.rays >= 1");
+    if ((out->shadow || out->irradiance) && pv->nlights == 0)
+        return fail(RTMI_ERR_INVALID, "preview: shadow / irradiance outputs need nlights >= 1");
+    if (vp->samples_per_pixel == 0) return fail(RTMI_ERR_INVALID, "samples_per_pixel must be >= 1");
+    if (nsamples == 0) return fail(RTMI_ERR_INVALID, "nsamples must be >= 1");
+    if ((uint64_t)sample0 + nsamples > vp->samples_per_pixel)
+        return fail(RTMI_ERR_INVALID, "samples [sample0, sample0 + nsamples) outside the frame's samples_per_pixel");
+    if (sample0 & RTMI_KEY_JITTER) return fail(RTMI_ERR_UNSUPPORTED, "sample0 above 2^31");  // DView::sample_key
+    {   // no two outputs may overlap as byte ranges
+        const uint64_t npix = (uint64_t)tile->nrows * vp->width;
+        const void* ptr[7] = {out->color, out->albedo, out->normal, out->ids, out->ao, out->shadow, out->irradiance};
+        const uint64_t len[7] = {16 * npix, 16 * npix, 16 * npix, 4 * npix, 4 * npix, 4 * npix * pv->nlights, 4 * npix * pv->nlights};
+        for (int i = 0; i < 7; i++)
+            for (int j = i + 1; j < 7; j++) {
+                if (!ptr[i] || !ptr[j]) continue;
+                const uintptr_t a = (uintptr_t)ptr[i], b = (uintptr_t)ptr[j];
+                if (a == b || (a < b ? b - a < len[i] : a - b < len[j])) return fail(RTMI_ERR_INVALID, "preview: outputs must not overlap");
+            }
+    }
+    if ((uint64_t)nsamples * ao.rays >= (1ull << 24))
+        return fail(RTMI_ERR_UNSUPPORTED, "preview: nsamples * ao.rays must stay below 2^24 (the per-pixel count is exact in f32)");
+    for (uint32_t l = 0; l < pv->nlights; l++)
+        if ((uint64_t)nsamples * pv->lights[l].rays >= (1ull << 24))
+            return fail(RTMI_ERR_UNSUPPORTED, "preview: light " + std::to_string(l) + ": nsamples * rays must stay below 2^24 (the per-pixel count is exact in f32)");
+    if (tile->nrows == 0) { *empty = true; return RTMI_OK; }
+    v1 = *vp;
+    v1.maxdepth = 1;
+    return check_view(&v1, tile);
+}
+
+// The call as the kernels take it; out's pointers are device memory
+static PreviewCall preview_call(const rtmi_preview_t& pv, const rtmi_preview_out_t& out, uint64_t npix) {
+    PreviewCall c{};
+    for (int k = 0; k < 3; k++) c.a.amb[k] = pv.ambient[k];
+    c.a.nlights = pv.nlights;
+    c.a.Ka = pv.ao.rays; c.a.dKa = make_fastdiv(pv.ao.rays);
+    c.a.radius = pv.ao.radius; c.a.abias = pv.ao.bias;
+    uint32_t koff = 0;
+    for (uint32_t l = 0; l < RTMI_PV_MAX_LIGHTS; l++) {
+        PvLight& L = c.a.li[l];
+        L = PvLight{};
+        L.K = 1; L.dK = make_fastdiv(1);
+        if (l >= pv.nlights) continue;
+        const rtmi_light_t& li = pv.lights[l];
+        L.orig = mk(li.orig[0], li.orig[1], li.orig[2]);
+        L.len2 = li.len2; L.bias = li.bias;
+        L.K = li.rays; L.koff = koff; L.dK = make_fastdiv(li.rays);
+        L.unbounded = (li.flags & RTMI_LIGHT_UNBOUNDED) ? 1u : 0u;
+        for (int k = 0; k < 3; k++) L.col[k] = pv.light_color[l][k];
+        koff += li.rays;
+    }
+    c.per_path = pv.ao.rays + koff;
+    c.color = (float4*)out.color;
+    c.fo = FeatOut{(float4*)out.albedo, (float4*)out.normal, (uint32_t*)out.ids};
+    c.ao = (float*)out.ao; c.shadow = (float*)out.shadow; c.irradiance = (float*)out.irradiance;
+    c.plane = (size_t)npix;
+    return c;
+}
+
+int rtmi_render_preview_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile, uint32_t sample0,
+                               uint32_t nsamples, const rtmi_preview_t* preview, const rtmi_preview_out_t* out_device, void* hip_stream,
+                               rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    rtmi_viewport_t v1;
+    bool empty;
+    const int rc = check_preview(s, vp, tile, sample0, nsamples, preview, out_device, v1, &empty);
+    if (rc != RTMI_OK || empty) return rc;
+    if (s->d.nspheres)
+        return fail(RTMI_ERR_UNSUPPORTED, "preview: the scene has analytic spheres (a build-defined primitive whose normal needs the hit point)");
+    const PreviewCall call = preview_call(*preview, *out_device, (uint64_t)tile->nrows * vp->width);
+    return render_tile(s, &v1, seed, tile, sample0, nsamples, nullptr, nullptr, hip_stream, stats, nullptr, 0, nullptr, nullptr, nullptr, &call);
+}
+
+// Host variant: the requested outputs are rendered into the handle's own device buffers and copied out once.
+int rtmi_render_preview(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows, uint32_t sample0,
+                        uint32_t nsamples, const rtmi_preview_t* preview, const rtmi_preview_out_t* out_host, rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    const rtmi_tile_t tile{row0, nrows, nrows ? nrows : 1u, 0u};
+    rtmi_viewport_t v1;
+    bool empty;
+    const int rc0 = check_preview(s, vp, &tile, sample0, nsamples, preview, out_host, v1, &empty);
+    if (rc0 != RTMI_OK || empty) return rc0;
+    if (s->d.nspheres)
+        return fail(RTMI_ERR_UNSUPPORTED, "preview: the scene has analytic spheres (a build-defined primitive whose normal needs the hit point)");
+    const uint64_t npix = (uint64_t)nrows * vp->width;
+    const uint32_t nl = preview->nlights;
+    HIPCHK(hipSetDevice(s->device));
+    // float4 images: colour, albedo, normal; f32 / u32 planes: ids, ao, nl shadow planes, nl irradiance planes
+    HIPCHK(s->pv_out4.ensure(3 * npix));
+    HIPCHK(s->pv_out1.ensure((2 + 2 * (uint64_t)nl) * npix));
+    rtmi_preview_out_t d{};
+    d.color = out_host->color ? s->pv_out4.p : nullptr;
+    d.albedo = out_host->albedo ? s->pv_out4.p + npix : nullptr;
+    d.normal = out_host->normal ? s->pv_out4.p + 2 * npix : nullptr;
+    d.ids = out_host->ids ? s->pv_out1.p : nullptr;
+    d.ao = out_host->ao ? s->pv_out1.p + npix : nullptr;
+    d.shadow = out_host->shadow ? s->pv_out1.p + 2 * npix : nullptr;
+    d.irradiance = out_host->irradiance ? s->pv_out1.p + (2 + (uint64_t)nl) * npix : nullptr;
+    const PreviewCall call = preview_call(*preview, d, npix);
+    const int rc = render_tile(s, &v1, seed, &tile, sample0, nsamples, nullptr, nullptr, nullptr, stats, nullptr, 0, nullptr, nullptr, nullptr, &call);
+    if (rc != RTMI_OK) return rc;
+    const void* src[7] = {d.color, d.albedo, d.normal, d.ids, d.ao, d.shadow, d.irradiance};
+    void* dst[7] = {out_host->color, out_host->albedo, out_host->normal, out_host->ids, out_host->ao, out_host->shadow, out_host->irradiance};
+    const uint64_t len[7] = {16 * npix, 16 * npix, 16 * npix, 4 * npix, 4 * npix, 4 * npix * nl, 4 * npix * nl};
+    for (int k = 0; k < 7; k++)
+        if (dst[k]) HIPCHK(hipMemcpy(dst[k], src[k], len[k], hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
 

@@ -345,6 +345,35 @@ int rth_caster_walk_light_device(rth_scene_t* s, uint32_t w, uint32_t h, const f
         if (stats) *stats = ctx.stats;
     });
 }
+int rth_caster_walk_preview(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp, uint64_t row0,
+                            uint64_t nrows, uint32_t sample0, uint32_t nsamples, const rtmi_preview_t* preview,
+                            const rtmi_preview_out_t* out_host, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!preview) throw std::runtime_error("NULL rtmi_preview_t");
+        if (!out_host) throw std::runtime_error("NULL rtmi_preview_out_t");
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_rays_preview(v, s->scene, (size_t)row0, (size_t)nrows, sample0, nsamples, *preview, *out_host, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
+int rth_caster_walk_preview_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                                   const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, const rtmi_preview_t* preview,
+                                   const rtmi_preview_out_t* out_device, void* hip_stream, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!tile) throw std::runtime_error("NULL tile");
+        if (!preview) throw std::runtime_error("NULL rtmi_preview_t");
+        if (!out_device) throw std::runtime_error("NULL rtmi_preview_out_t");
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_preview_device(v, s->scene, *tile, sample0, nsamples, *preview, *out_device, hip_stream, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
 int rth_caster_denoise(rth_scene_t* s, uint32_t w, uint32_t h, const float* color_host, const float* albedo_host,
                        const float* normal_host, const rtmi_denoise_t* params, float* out_host) {
     return guarded([&] {

@@ -817,6 +817,31 @@ void HipRayCaster::walk_light_device(const Viewport& v, const Scene& s, const rt
     progress.stats = st;
 }
 
+void HipRayCaster::walk_rays_preview(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
+                                     const rtmi_preview_t& preview, const rtmi_preview_out_t& out, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_preview(h, &av, seed, (uint32_t)row0, (uint32_t)nrows, sample0, nsamples, &preview, &out, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_preview: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
+void HipRayCaster::walk_preview_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
+                                       const rtmi_preview_t& preview, const rtmi_preview_out_t& out_device, void* hip_stream,
+                                       ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_preview_device(h, &av, seed, &tile, sample0, nsamples, &preview, &out_device, hip_stream, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_preview_device: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
 void HipRayCaster::variance(const Scene& s, const Color* accum, const Color* sumsq, const uint32_t* counts, uint64_t npixels, Color* out) {
     rtmi_scene_t* h = resident(s);
     const int rc = rtmi_variance(h, reinterpret_cast<const float*>(accum), reinterpret_cast<const float*>(sumsq), counts, npixels,

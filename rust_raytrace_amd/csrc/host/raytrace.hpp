@@ -241,6 +241,13 @@ public:
     void walk_light_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
                            const LightSource& light, uint32_t rays, uint32_t flags, float bias, void* shadow_device,
                            void* irradiance_device, void* hip_stream, ProgressCtx& progress);
+    // Shaded preview (rtmi_render_preview / rtmi_render_preview_device, which rtmi.h defines): albedo, AO and up to four
+    // coloured box lights composed per sample from one primary pass; `out` names the colour image and the layers wanted.
+    void walk_rays_preview(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
+                           const rtmi_preview_t& preview, const rtmi_preview_out_t& out, ProgressCtx& progress);
+    void walk_preview_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
+                             const rtmi_preview_t& preview, const rtmi_preview_out_t& out_device, void* hip_stream,
+                             ProgressCtx& progress);
     // Variance-guided denoising (rtmi_variance* / rtmi_denoise_var* / rtmi_render_adaptive_denoised): variance() turns the
     // moments of an adaptive render (accum, sumsq, counts of npixels pixels) into the variance image the filter takes beside
     // denoise()'s images; var_out (may be null) receives the propagated variance.  walk_adaptive_denoised runs the adaptive

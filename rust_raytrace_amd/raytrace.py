@@ -8,6 +8,7 @@ build_bounding_box, build_trivial_bounding_box, and the RayCaster plug-in
 """
 import ctypes as C
 import time
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -799,6 +800,136 @@ class HipRayCaster:
         _chk(_ffi.lib().rth_caster_walk_light_device(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, C.byref(t), k0, n,
                                                      C.byref(a), ptr[0], ptr[1], C.c_void_p(getattr(stream, "cuda_stream", stream) or 0),
                                                      C.byref(st), C.byref(wall)))
+        return ProgressCtx(st.rays, wall.value, st.as_dict())
+
+    PREVIEW_MAX_LIGHTS = _ffi.PREVIEW_MAX_LIGHTS
+    _PREVIEW_OUTPUTS = ("color", "albedo", "normal", "ids", "ao", "shadow", "irradiance")  # rtmi_preview_out_t's order
+
+    @staticmethod
+    def preview_params(ambient=None, ao=None, lights=()):
+        """rtmi_preview_t from the library's defaults (rtmi_preview_defaults: ambient 0.3, AO of 4 rays, no lights, white
+        lights) with the given fields replaced.  ao: None keeps the default AO, False switches it off (rays = 0), a dict of
+        ao_params' arguments (rays, radius, bias) replaces it; rays = 0 in the dict switches it off too.  lights: up to four
+        dicts of light_params' arguments (orig, len2, rays, unbounded, bias) plus color = three finite numbers (default
+        white).  Raises ValueError for what the library would refuse."""
+        p = _ffi.Preview()
+        _ffi.lib().rtmi_preview_defaults(C.byref(p))
+        if ambient is not None:
+            a = [float(x) for x in ambient]
+            if len(a) != 3 or not all(np.isfinite(x) for x in a):
+                raise ValueError("ambient must be three finite numbers")
+            p.ambient[0], p.ambient[1], p.ambient[2] = a
+        if ao is False:
+            p.ao.rays = 0
+        elif ao is not None:
+            kw = dict(ao)
+            unknown = set(kw) - {"rays", "radius", "bias"}
+            if unknown:
+                raise ValueError(f"ao: unknown keys {sorted(unknown)}")
+            off = kw.get("rays") is not None and int(kw["rays"]) == 0
+            if off:
+                kw.pop("rays")
+            p.ao = HipRayCaster.ao_params(**kw)
+            if off:
+                p.ao.rays = 0
+        lights = list(lights)
+        if len(lights) > HipRayCaster.PREVIEW_MAX_LIGHTS:
+            raise ValueError(f"at most {HipRayCaster.PREVIEW_MAX_LIGHTS} lights")
+        for l, li in enumerate(lights):
+            kw = dict(li)
+            unknown = set(kw) - {"orig", "len2", "rays", "unbounded", "bias", "color"}
+            if unknown:
+                raise ValueError(f"light {l}: unknown keys {sorted(unknown)}")
+            col = kw.pop("color", None)
+            try:
+                p.lights[l] = HipRayCaster.light_params(**kw)
+            except ValueError as e:
+                raise ValueError(f"light {l}: {e}") from None
+            if col is not None:
+                c = [float(x) for x in col]
+                if len(c) != 3 or not all(np.isfinite(x) for x in c):
+                    raise ValueError(f"light {l}: color must be three finite numbers")
+                p.light_color[l][0], p.light_color[l][1], p.light_color[l][2] = c
+        p.nlights = len(lights)
+        return p
+
+    def _preview_args(self, v, sample0, nsamples, ambient, ao, lights, wanted):
+        """(sample0, nsamples, rtmi_preview_t) after the checks the library would make; wanted: the outputs asked for, by name"""
+        k0, n = self._feature_samples(v, sample0, nsamples)
+        p = self.preview_params(ambient, ao, lights)
+        if n * p.ao.rays >= 1 << 24 or any(n * p.lights[l].rays >= 1 << 24 for l in range(p.nlights)):
+            raise ValueError("nsamples * rays must stay below 2^24")
+        if not wanted:
+            raise ValueError("at least one output is needed")
+        if "ao" in wanted and p.ao.rays == 0:
+            raise ValueError("the ao output needs AO rays")
+        if ("shadow" in wanted or "irradiance" in wanted) and p.nlights == 0:
+            raise ValueError("the shadow and irradiance outputs need at least one light")
+        return k0, n, p
+
+    def walk_rays_preview(self, v, s, ambient=None, ao=None, lights=(), sample0=0, nsamples=None, color=True, albedo=False, normal=False,
+                          ids=False, ao_out=False, shadow=False, irradiance=False):
+        """A shaded preview of the whole frame in one call (rtmi_render_preview; include/rtmi.h defines it): per sample
+        albedo * (ambient * ao + sum of light colour * irradiance), averaged per pixel, from one primary pass and one any-hit
+        walk of the AO rays and every light's shadow rays.  ambient / ao / lights: preview_params' arguments.  Each output:
+        True allocates it, an array is filled in place, False / None leaves it out (not all).  color, albedo, normal: (H, W, 4)
+        float32; ids: (H, W) uint32; ao_out: (H, W) float32; shadow, irradiance: (L, H, W) float32, one plane per light.  The
+        layers are bit for bit what walk_rays_features, walk_rays_ao and walk_rays_light return for the same parameters.
+        Returns a namespace of the requested arrays (None for one left out; the AO plane is .ao) plus ctx."""
+        h, w, nl = v.height, v.width, len(list(lights))
+        spec = (("color", color, (h, w, 4), np.float32), ("albedo", albedo, (h, w, 4), np.float32), ("normal", normal, (h, w, 4), np.float32),
+                ("ids", ids, (h, w), np.uint32), ("ao", ao_out, (h, w), np.float32), ("shadow", shadow, (nl, h, w), np.float32),
+                ("irradiance", irradiance, (nl, h, w), np.float32))
+        bufs = {}
+        for name, x, shape, dt in spec:
+            if x is True:
+                x = np.zeros(shape, dt)
+            elif x is False or x is None:
+                x = None
+            elif not isinstance(x, np.ndarray) or x.dtype != dt or not x.flags.c_contiguous or x.shape != shape:
+                raise ValueError(f"{name} must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
+            bufs[name] = x
+        given = [x for x in bufs.values() if x is not None]
+        k0, n, p = self._preview_args(v, sample0, nsamples, ambient, ao, lights, {k for k, x in bufs.items() if x is not None})
+        if any(np.shares_memory(a, b) for i, a in enumerate(given) for b in given[i + 1:]):
+            raise ValueError("the outputs must not overlap")
+        self._config(s)
+        out = _ffi.PreviewOut(*[x.ctypes.data if x is not None and x.size else None for x in bufs.values()])
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_preview(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, 0, v.height, k0, n,
+                                                C.byref(p), C.byref(out), C.byref(st), C.byref(wall)))
+        return SimpleNamespace(ctx=ProgressCtx(st.rays, wall.value, st.as_dict()), **bufs)
+
+    def walk_rays_preview_device(self, v, s, tile=None, ambient=None, ao=None, lights=(), sample0=0, nsamples=None, color=None,
+                                 albedo=None, normal=None, ids=None, ao_out=None, shadow=None, irradiance=None, stream=None):
+        """The same into torch tensors on the scene's device (rtmi_render_preview_device) for a striped row set tile = (row0,
+        nrows, stripe_rows, stripe_step) (default: the whole frame).  Each output is a contiguous tensor or None (not all):
+        color, albedo, normal float32 of nrows * width * 4 elements, ids int32 or uint32 of nrows * width, ao_out float32 of
+        nrows * width, shadow and irradiance float32 of L * nrows * width (one plane per light); no two may overlap.  They
+        are written by work enqueued on `stream` (a torch stream, a raw HIP stream pointer or None).  color, albedo and
+        normal are what denoise_device takes.  Returns ctx."""
+        t = _ffi.Tile(*[int(x) for x in (tile if tile is not None else (0, v.height, v.height, 0))])
+        npix, nl = int(t.nrows) * int(v.width), len(list(lights))
+        spec = (("color", color, 4 * npix, ("torch.float32",)), ("albedo", albedo, 4 * npix, ("torch.float32",)),
+                ("normal", normal, 4 * npix, ("torch.float32",)), ("ids", ids, npix, ("torch.int32", "torch.uint32")),
+                ("ao", ao_out, npix, ("torch.float32",)), ("shadow", shadow, nl * npix, ("torch.float32",)),
+                ("irradiance", irradiance, nl * npix, ("torch.float32",)))
+        for name, x, want, dts in spec:
+            if x is not None and (not hasattr(x, "data_ptr") or not x.is_cuda or str(x.dtype) not in dts or not x.is_contiguous()
+                                  or x.numel() != want):
+                raise ValueError(f"{name} must be a contiguous {dts[0][6:]} tensor of {want} elements on the device")
+        k0, n, p = self._preview_args(v, sample0, nsamples, ambient, ao, lights, {name for name, x, _, _ in spec if x is not None})
+        spans = sorted((x.data_ptr(), x.data_ptr() + 4 * want) for _, x, want, _ in spec if x is not None)
+        if any(a[1] > b[0] for a, b in zip(spans, spans[1:])):
+            raise ValueError("the outputs must not overlap")
+        self._config(s)
+        out = _ffi.PreviewOut(*[x.data_ptr() if x is not None else None for _, x, _, _ in spec])
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_preview_device(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, C.byref(t), k0, n,
+                                                       C.byref(p), C.byref(out), C.c_void_p(getattr(stream, "cuda_stream", stream) or 0),
+                                                       C.byref(st), C.byref(wall)))
         return ProgressCtx(st.rays, wall.value, st.as_dict())
 
     DENOISE_DEMODULATE = 1
