@@ -539,6 +539,88 @@ int rtmi_occluded(rtmi_scene_t* scene, uint64_t n, const float* orig4, const flo
 int rtmi_occluded_device(rtmi_scene_t* scene, uint64_t n, const void* orig4_device, const void* dir4_device,
                          const void* tmax_device /* or NULL */, void* occluded_device, void* hip_stream, rtmi_stats_t* stats);
 
+/* rtmi_trace on device buffers: orig4 / dir4 (n float4 each, 16-byte aligned) are read where they are, with no staging copy;
+ * tri / t / face (n uint32 / f32 / uint32) receive what rtmi_trace returns for the same rays on this handle.  One closest-hit
+ * launch on the library's stream and one elementwise kernel that unpacks the hit records.  Stream semantics as for
+ * rtmi_occluded_device: the library's stream starts after the work already queued on hip_stream, hip_stream is made to wait for
+ * it, and the call returns once the counters are read back.  stats as rtmi_trace fills them (kernel_ms: the span on hip_stream).
+ * n == 0: RTMI_OK, nothing is touched (checked after the scene, before the buffers).  RTMI_ERR_INVALID, before any HIP call and
+ * before the scene is used, stats cleared: a NULL scene or buffer; two buffers that overlap as byte ranges (16 n, 16 n, 4 n, 4 n,
+ * 4 n bytes).  RTMI_ERR_UNSUPPORTED: n >= 2^31. */
+int rtmi_trace_device(rtmi_scene_t* scene, uint64_t n, const void* orig4_device, const void* dir4_device, void* tri_device,
+                      void* t_device, void* face_device, void* hip_stream, rtmi_stats_t* stats);
+
+/* Path tracing of caller-supplied rays: the colour project_ray (raytrace.rs:1199-1295) returns for each of n
+ * explicit rays -- closest hit, color_ray, Lambert and mirror bounces, mix_color -- without Viewport::pixel_ray in front of it:
+ * for fisheye, panoramic, orthographic and thin-lens cameras, light probes, lightmap and irradiance bakes, paths continued
+ * from somebody else's G-buffer.  This is the reference's own function of a ray, not a build-defined one: the renderer's
+ * primary rays fed back with their keys reproduce rtmi_render bit for bit, ray count and work counters included.
+ * Rays: as for rtmi_trace, a float4 origin and a float4 unit direction per ray as `make_ray` stores them (raytrace.rs:201-210),
+ * 16-byte aligned.  With RTMI_RAYS_MAKE_RAY the library applies make_ray itself: dir = vunit(dir), i.e. the ordered four-lane
+ * dot ((((0 + x x) + y y) + z z) + w w), r = sqrt(.), dir * (1.f / r) (raytrace.rs:93-96); the origin is taken as given and
+ * the caller's direction buffer is not written.
+ * RNG key of ray i (what rand::random's call sites are keyed by, as in rtmi_render: (seed, pixel, sample, block)):
+ *   keys != NULL:  (pixel, sample) = (keys[2 i], keys[2 i + 1]);
+ *   keys == NULL:  (pixel, sample) = (pixel0 + i / G, i % G), G = rays->group.
+ * Keys need not be distinct (two rays with one key draw the same numbers).  Block 0, pixel_ray's jitter, is never drawn; bounce k
+ * of a path draws block k (k = 1 .. maxdepth - 1), exactly as a rendered path does.
+ * Outputs (rtmi_rays_out_t; any may be NULL, not all), rays in groups of G consecutive rays, group g = rays [g G, (g + 1) G):
+ *   color[i]   the colour of a path that starts with ray i, has ray i's key and depth rays->maxdepth; lane 3 = 0 (what a
+ *              sample of rtmi_render contributes to its pixel);
+ *   mean[g]    acc = 0.f; acc = acc + color[g G + s] for s = 0 .. G-1; acc * (1.f / (float)G): walk_ray_set's arithmetic
+ *              (raytrace.rs:1414-1426), a group standing for a pixel and its rays for the pixel's samples;
+ *   albedo[g], normal[g], ids[g]   rtmi_render_features*'s three buffers with a group for a pixel: the per-sample terms of the
+ *              rays' closest hits (what rtmi_trace returns for them) folded in the same order; ids[g] is the id of ray g G.
+ * maxdepth == 0: color and mean are zeros (project_ray returns black at depth 0, raytrace.rs:1261-1263); the guide buffers still
+ * come from the closest hits: the rays are traced when a guide is asked for and not otherwise.
+ * Scenes: every kind rtmi_render takes -- octree, linear list, generic tree, RTMI_OPT_GENERIC, RTMI_OPT_FAST, RTMI_OPT_BVH and
+ * analytic spheres, each with its own mode's hits.  The guide buffers are refused with RTMI_ERR_UNSUPPORTED on a scene with
+ * analytic spheres, as rtmi_render_features* is; the colours are not.
+ * How: always the per-pass pipeline (rtmi_tuning_t.pipeline 1) on one stream of the library: per batch k_rays_begin (the queue's
+ * count and identity path map; with RTMI_RAYS_MAKE_RAY the unit directions, into the workspace queue), then per pass the scene's
+ * closest-hit launch and k_shade_rays, k_features after pass 0 when guides are asked for, k_accum for the means.  Rays with a
+ * zero direction component are traced in place.  The device variant's pass 0 traces the caller's buffers where they are (no
+ * staging copy of the rays; with the flag only the directions are rewritten, into the workspace) and, when color is asked for,
+ * the sample colours are written straight into it.  A batch holds whole groups: rtmi_tuning_t.batch_paths rounded down to a
+ * multiple of G, at least G.  Hit records and queues are the handle's render workspace; nothing new persists on the handle.  No
+ * tuning changes a bit of the result.  An octree scene does not get k_path_primary's packet culling and in-place mirror pass
+ * here: those need to know that the rays are a camera's (DESIGN.md 4.18 has the measured cost).
+ * rtmi_render_rays_device: device buffers; stream semantics as for rtmi_occluded_device: the library's stream starts after the
+ * work already queued on hip_stream, hip_stream is made to wait for it, and the call returns once the counters are read back.
+ * rtmi_render_rays: host buffers; each batch's rays (and keys) are copied in and its outputs copied out.
+ * stats: rays = the reference's "Rays" counter, every ray traced in any pass (with maxdepth == 0 and a guide: n); trace_launches
+ * = passes x batches, trace_ms = the sum of those closest-hit launches' times, kernel_ms = the span of the call on hip_stream
+ * (host variant: on the library's stream, copies included), streams = 1, pipeline = 1, slow_paths = 0; with RTMI_OPT_COUNTERS
+ * the five work counters.
+ * Checks, all before any HIP call, stats cleared; only the last one reads the scene.  In this order:
+ *   RTMI_ERR_INVALID: a NULL scene, rays struct or out; group == 0; unknown flag bits; n % group != 0;
+ *   n == 0: RTMI_OK, nothing is touched;
+ *   RTMI_ERR_INVALID: a NULL orig4 or dir4; all five outputs NULL; two buffers overlapping as byte ranges, inputs and keys
+ *     included (16 n, 16 n, 8 n; 16 n, and 16, 16, 16, 4 times n / G); keys == NULL and pixel0 + n / G - 1 >= 2^32;
+ *   RTMI_ERR_UNSUPPORTED: n >= 2^31; maxdepth > 32; group > 65536; a guide buffer on a scene with analytic spheres.
+ * Not here: the path kernels (pipeline 3) for explicit rays, several streams, rtmi_render_frame_multi, batches of views,
+ * progressive or adaptive passes over explicit rays, built-in camera models, a denoised one-call wrapper (mean, albedo and normal
+ * feed rtmi_denoise_device directly when the groups form an image). */
+enum { RTMI_RAYS_MAKE_RAY = 1u << 0 };
+typedef struct rtmi_rays {
+    uint32_t maxdepth;  /* project_ray's depth, 0..32                                                            */
+    uint32_t group;     /* G >= 1: rays come in groups of G consecutive rays (the samples of one "pixel")        */
+    uint32_t pixel0;    /* RNG key of group 0 when keys == NULL                                                  */
+    uint32_t flags;     /* RTMI_RAYS_MAKE_RAY or 0                                                               */
+} rtmi_rays_t;          /* 16 bytes */
+typedef struct rtmi_rays_out {   /* any may be NULL, not all; no two may overlap, none may overlap an input */
+    void* color;    /* n float4: the colour project_ray returns for ray i, lane 3 = 0                            */
+    void* mean;     /* n/G float4: walk_ray_set's mean of each group                                             */
+    void* albedo;   /* n/G float4 } rtmi_render_features*'s three buffers, a group standing for a pixel and      */
+    void* normal;   /* n/G float4 } its rays for the pixel's samples                                             */
+    void* ids;      /* n/G uint32 } (id of the group's first ray)                                                */
+} rtmi_rays_out_t;
+int rtmi_render_rays_device(rtmi_scene_t* scene, uint64_t n, const void* orig4_device, const void* dir4_device,
+                            const void* keys_device /* n x 2 uint32 or NULL */, uint64_t seed, const rtmi_rays_t* rays,
+                            const rtmi_rays_out_t* out_device, void* hip_stream, rtmi_stats_t* stats);
+int rtmi_render_rays(rtmi_scene_t* scene, uint64_t n, const float* orig4, const float* dir4, const uint32_t* keys /* or NULL */,
+                     uint64_t seed, const rtmi_rays_t* rays, const rtmi_rays_out_t* out_host, rtmi_stats_t* stats);
+
 /* Ambient occlusion rendered on the device: one f32 per pixel, the share of K hemisphere rays per primary
  * sample that reach `radius` unoccluded -- a shaded preview, a contact-shadow layer, a guide image.  NOT part of the reference,
  * which has no AO: build-defined like the denoiser, so what follows IS the definition, and tests/ao_ref.py pins it bit for bit.

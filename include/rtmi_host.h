@@ -123,6 +123,17 @@ int rth_caster_occluded(rth_scene_t* s, uint64_t n, const float* orig4, const fl
                         rtmi_stats_t* stats);
 int rth_caster_occluded_device(rth_scene_t* s, uint64_t n, const void* orig4_device, const void* dir4_device,
                                const void* tmax_device, void* occluded_device, void* hip_stream, rtmi_stats_t* stats);
+/* rtmi_trace on device buffers (rtmi_trace_device in rtmi.h): the rays are read in place, tri / t / face written in place. */
+int rth_caster_trace_device(rth_scene_t* s, uint64_t n, const void* orig4_device, const void* dir4_device, void* tri_device,
+                            void* t_device, void* face_device, void* hip_stream, rtmi_stats_t* stats);
+/* Path tracing of caller-supplied rays (rtmi_render_rays / rtmi_render_rays_device in rtmi.h, which defines it) on the scene's
+ * resident copy, with the caster's seed.  keys: n x 2 uint32 (pixel, sample) or NULL. */
+int rth_caster_walk_rays_explicit(rth_scene_t* s, uint64_t n, const float* orig4, const float* dir4, const uint32_t* keys,
+                                  const rtmi_rays_t* rays, const rtmi_rays_out_t* out_host, rtmi_stats_t* stats,
+                                  double* wall_seconds);
+int rth_caster_walk_rays_explicit_device(rth_scene_t* s, uint64_t n, const void* orig4_device, const void* dir4_device,
+                                         const void* keys_device, const rtmi_rays_t* rays, const rtmi_rays_out_t* out_device,
+                                         void* hip_stream, rtmi_stats_t* stats, double* wall_seconds);
 /* Ambient occlusion (rtmi_render_ao / rtmi_render_ao_device in rtmi.h, which defines it): one f32 per pixel, the share of
  * ao->rays hemisphere rays per primary sample of [sample0, sample0 + nsamples) that are not occluded within ao->radius.
  * maxdepth is not consulted; the primary rays use the caster's seed. */

@@ -380,6 +380,7 @@ __global__ void __launch_bounds__(256) k_trace(DScene sc, const float4* __restri
 #include "ao.hpp"
 #include "light.hpp"
 #include "preview.hpp"
+#include "rays.hpp"
 namespace rtmi {
 
 
@@ -533,7 +534,8 @@ __global__ void __launch_bounds__(256) k_occl_from_hits(uint32_t n, const uint32
 // ---------------------------------------------------------------- generation / shading (per-pass pipeline)
 // pixel_ray / color_ray themselves are in shade.hpp (shared with the path kernels of trace_oct.hpp).
 // S (shade.hpp): k_gen / k_shade are Samp::FRAME, k_gen_samples / k_shade_samples PASS, k_gen_list / k_shade_list LIST,
-// k_gen_views / k_shade_views VIEWS (the view table is an argument of these two only).
+// k_gen_views / k_shade_views VIEWS (the view table is an argument of these two only), k_shade_rays RAYS (no k_gen: the rays
+// are the caller's, rays.hpp has the kernel that stands in its place).
 #define RTMI_GEN_PARAMS uint64_t seed, uint32_t pix0, uint32_t npaths, float4* __restrict__ qo, float4* __restrict__ qd, \
                         uint32_t* __restrict__ qpath, DCtrl* __restrict__ ctrl
 #define RTMI_GEN_ARGS v, seed, pix0, npaths, qo, qd, qpath, ctrl
@@ -586,11 +588,18 @@ __device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __
             float t = 0.f;
             float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f), d4 = make_float4(0.f, 0.f, 1.f, 0.f);
             if ((tf & 0x3FFFFFFFu) != 0u && !((tf >> 30) & 2u)) { t = hit_t[i]; o4 = qo[i]; d4 = qd[i]; }
+            if constexpr (S == Samp::RAYS) {  // `list` = the batch's RNG keys (or null), pix0 = the key of its first group
+                uint32_t pixel, sample;
+                rays_key(v, pix0, path, list, pixel, sample);
+                push = shade_hit(sc, v.maxdepth, seed, npaths, path, pixel, sample, (uint32_t)pass, tf, t, V4{o4.x, o4.y, o4.z, o4.w},
+                                 V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr);
+            } else {
             uint32_t prow, pcol, sample;
             path_pixel<S>(v, pix0, path, prow, pcol, sample, list);
             const PixKey key = pixel_key<S>(v, prow, vt);
             push = shade_hit(sc, v.maxdepth, key_seed<S>(key, vt, seed), npaths, path, key.row * v.width + pcol, sample, (uint32_t)pass, tf, t,
                              V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr);
+            }
             // a bounce ray with an exactly-zero direction component goes to the slow path (SlowQ), not to the next pass
             if (push && slow.cap && has_zero_component(nr.dir.x, nr.dir.y, nr.dir.z) &&
                 slow_push(slow, ctrl, make_float4(nr.orig.x, nr.orig.y, nr.orig.z, nr.orig.w), make_float4(nr.dir.x, nr.dir.y, nr.dir.z, nr.dir.w),
@@ -625,6 +634,8 @@ __global__ void __launch_bounds__(256) k_shade(RTMI_SHADE_PARAMS) { shade_pass<S
 __global__ void __launch_bounds__(256) k_shade_samples(RTMI_SHADE_PARAMS) { shade_pass<Samp::PASS>(RTMI_SHADE_ARGS); }
 __global__ void __launch_bounds__(256) k_shade_list(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list) { shade_pass<Samp::LIST>(RTMI_SHADE_ARGS, list); }
 __global__ void __launch_bounds__(256) k_shade_views(RTMI_SHADE_PARAMS, ViewTab vt) { shade_pass<Samp::VIEWS>(RTMI_SHADE_ARGS, nullptr, vt); }
+// Samp::RAYS (rtmi_render_rays*): v carries maxdepth, spp = the group size and dspp only; keys = the batch's RNG keys or null
+__global__ void __launch_bounds__(256) k_shade_rays(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ keys) { shade_pass<Samp::RAYS>(RTMI_SHADE_ARGS, keys); }
 
 // walk_ray_set's per-pixel accumulation (raytrace.rs:1414-1426): acc = 0; acc += sample_i in sample order; * (1/spp).
 // The sample colours of a pixel are consecutive in `scol` ([pixel][sample]), so one thread per pixel would read 16 B at a
@@ -2157,6 +2168,8 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
         hipLaunchKernelGGL(k_accum_list, ew_grid, ew_block, 0, st, np, c.spp, c.sample0, w.scol.p, (float*)c.accum, (float*)c.lp->sumsq,
                            c.lp->counts, (float*)c.out, list, pix0);
         break;
+    case Samp::RAYS:  // never a tile's mode: explicit rays have their own driver (render_rays)
+        break;
     }
     HIPCHK(hipEventRecord(w.ev[1], st));
     HIPCHK(hipGetLastError());
@@ -3260,6 +3273,234 @@ int rtmi_occluded(rtmi_scene_t* s, uint64_t n, const float* orig4, const float* 
     HIPCHK(hipMemcpyAsync(occluded, s->occ_out.p, n, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return collect_occluded(w, st, stats, -1.f);
+    RTMI_GUARD_END
+}
+
+// ---------------------------------------------------------------- explicit rays (rtmi_render_rays*, rtmi_trace_device)
+// Buffers of a call as the byte ranges it reads and writes; a null pointer takes no part.  Returns the first pair that overlaps.
+struct ByteRange { const void* p; uint64_t bytes; const char* name; };
+static bool ranges_overlap(const ByteRange* r, size_t n, size_t& a, size_t& b) {
+    for (a = 0; a < n; a++)
+        for (b = a + 1; b < n; b++)
+            if (r[a].p && r[b].p && (uintptr_t)r[a].p < (uintptr_t)r[b].p + r[b].bytes && (uintptr_t)r[b].p < (uintptr_t)r[a].p + r[a].bytes)
+                return true;
+    return false;
+}
+
+// Checks that come before any HIP call (a CPU-only caller reaches them); only the last one reads the scene.
+static int check_rays(const rtmi_scene_t* s, uint64_t n, const void* orig4, const void* dir4, const void* keys, const rtmi_rays_t* rp,
+                      const rtmi_rays_out_t* out, rtmi_stats_t* stats, bool& empty) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    empty = false;
+    if (!s) return fail(RTMI_ERR_INVALID, "render_rays: NULL argument (scene)");
+    if (!rp) return fail(RTMI_ERR_INVALID, "render_rays: NULL argument (rays)");
+    if (!out) return fail(RTMI_ERR_INVALID, "render_rays: NULL argument (out)");
+    if (rp->group == 0) return fail(RTMI_ERR_INVALID, "render_rays: group must be >= 1");
+    if (rp->flags & ~(uint32_t)RTMI_RAYS_MAKE_RAY) return fail(RTMI_ERR_INVALID, "render_rays: unknown flag bits");
+    if (n % rp->group != 0) return fail(RTMI_ERR_INVALID, "render_rays: n must be a multiple of group");
+    if (n == 0) { empty = true; return RTMI_OK; }
+    if (!orig4) return fail(RTMI_ERR_INVALID, "render_rays: NULL argument (orig4)");
+    if (!dir4) return fail(RTMI_ERR_INVALID, "render_rays: NULL argument (dir4)");
+    if (!out->color && !out->mean && !out->albedo && !out->normal && !out->ids)
+        return fail(RTMI_ERR_INVALID, "render_rays: all five outputs are NULL");
+    const uint64_t m = std::min<uint64_t>(n, 1ull << 40), g = m / rp->group;  // (a count that is refused below anyway: the sizes must not wrap)
+    const ByteRange r[8] = {{orig4, m * 16, "orig4"}, {dir4, m * 16, "dir4"}, {keys, m * 8, "keys"}, {out->color, m * 16, "color"},
+                            {out->mean, g * 16, "mean"}, {out->albedo, g * 16, "albedo"}, {out->normal, g * 16, "normal"}, {out->ids, g * 4, "ids"}};
+    size_t a, b;
+    if (ranges_overlap(r, 8, a, b))
+        return fail(RTMI_ERR_INVALID, std::string("render_rays: buffers overlap (") + r[a].name + " and " + r[b].name + ")");
+    if (!keys && (uint64_t)rp->pixel0 + n / rp->group - 1 >= (1ull << 32))
+        return fail(RTMI_ERR_INVALID, "render_rays: pixel0 + n / group - 1 must stay below 2^32 (the RNG key is 32 bits)");
+    if (n >= (1ull << 31)) return fail(RTMI_ERR_UNSUPPORTED, "render_rays: more than 2^31 rays per call");
+    if (rp->maxdepth > RTMI_MAX_PASSES) return fail(RTMI_ERR_UNSUPPORTED, "render_rays: maxdepth above 32");
+    if (rp->group > 65536u) return fail(RTMI_ERR_UNSUPPORTED, "render_rays: group above 65536");
+    if ((out->albedo || out->normal || out->ids) && s->d.nspheres)
+        return fail(RTMI_ERR_UNSUPPORTED, "render_rays: no guide buffers (albedo, normal, ids) for scenes with analytic spheres");
+    return RTMI_OK;
+}
+
+// Both variants.  Batches of whole groups on the library's stream 0, each the per-pass pipeline with the rays themselves as
+// queue 0: k_rays_begin, then per pass the scene's closest-hit launch and k_shade_rays (after pass 0: k_features for the
+// guides), then k_accum for the means.  Device variant: the rays, keys and outputs are the caller's buffers, used in place
+// (shade_hit writes the sample colours straight into `color` when it is asked for).  Host variant: a batch's rays are staged
+// in the workspace queue, its keys and group outputs in the host variants' per-pixel buffers of the handle (alist[0], tile,
+// acc, asq, acnt: no call keeps anything in them between calls), and copied out batch by batch.
+static int render_rays(rtmi_scene_t* s, uint64_t n, const void* orig4, const void* dir4, const void* keys, uint64_t seed,
+                       const rtmi_rays_t* rp, const rtmi_rays_out_t* out, void* hip_stream, rtmi_stats_t* stats, bool host) {
+    bool empty;
+    int rc = check_rays(s, n, orig4, dir4, keys, rp, out, stats, empty);
+    if (rc != RTMI_OK || empty) return rc;
+    RTMI_GUARD_BEGIN
+    (void)hipGetLastError();
+    HIPCHK(hipSetDevice(s->device));
+    const uint32_t G = rp->group, maxdepth = rp->maxdepth;
+    const bool guides = out->albedo || out->normal || out->ids;
+    const bool shade = maxdepth != 0 && (out->color || out->mean);
+    const bool make = (rp->flags & RTMI_RAYS_MAKE_RAY) != 0, counting = (s->options & RTMI_OPT_COUNTERS) != 0;
+    Work& w = s->w[0];
+    hipStream_t st = s->istream[0], ust = host ? st : (hipStream_t)hip_stream;
+    // batches hold whole groups: batch_paths rounded down to a multiple of G, at least G
+    const uint64_t B = std::min<uint64_t>(std::max<uint64_t>(s->tune.batch_paths / G * G, G), n), gB = B / G;
+    if (shade || guides) {
+        rc = ensure_workspace(w, (size_t)B, std::max(maxdepth, 1u));
+        if (rc != RTMI_OK) return rc;
+    }
+    if (host) {
+        if (keys && shade) HIPCHK(s->alist[0].ensure(2 * B));
+        if (out->mean && shade) HIPCHK(s->tile.ensure(gB));
+        if (out->albedo) HIPCHK(s->acc.ensure(gB));
+        if (out->normal) HIPCHK(s->asq.ensure(gB));
+        if (out->ids) HIPCHK(s->acnt.ensure(gB));
+    }
+    s->active_streams = 1;
+    // the library's stream starts after whatever the caller queued on its stream, and that stream waits for it
+    HIPCHK(hipEventRecord(s->fork_ev, ust));
+    if (!host) HIPCHK(hipStreamWaitEvent(st, s->fork_ev, 0));
+    if (maxdepth == 0) {  // project_ray returns black immediately (raytrace.rs:1261-1263)
+        if (host) {
+            if (out->color) memset(out->color, 0, n * 16);
+            if (out->mean) memset(out->mean, 0, n / G * 16);
+        } else {
+            if (out->color) HIPCHK(hipMemsetAsync(out->color, 0, n * 16, st));
+            if (out->mean) HIPCHK(hipMemsetAsync(out->mean, 0, n / G * 16, st));
+        }
+    }
+    DView dv{};  // what shade_pass<Samp::RAYS> reads of it: the depth, and the group size with its divisor
+    dv.maxdepth = maxdepth; dv.spp = G;
+    view_set_divisors(dv);
+    const dim3 ew_grid((unsigned)(s->num_cu * 8)), ew_block(256);
+    const uint32_t npass = shade ? maxdepth : guides ? 1u : 0u;
+    rtmi_stats_t sum{};
+    float trace_ms = 0.f;
+    uint32_t launches = 0;
+    for (uint64_t base = 0; base < n && npass; base += B) {
+        const uint32_t nb = (uint32_t)std::min<uint64_t>(B, n - base), ng = nb / G;
+        const uint64_t gbase = base / G;
+        const float4 *qo = (const float4*)orig4 + base, *qd = (const float4*)dir4 + base;
+        const uint32_t* kq = keys && shade ? (const uint32_t*)keys + 2 * base : nullptr;
+        float4 *mean = out->mean ? (float4*)out->mean + gbase : nullptr, *albedo = out->albedo ? (float4*)out->albedo + gbase : nullptr,
+               *normal = out->normal ? (float4*)out->normal + gbase : nullptr;
+        uint32_t* ids = out->ids ? (uint32_t*)out->ids + gbase : nullptr;
+        float4* scol = out->color && shade ? (float4*)out->color + base : w.scol.p;
+        if (host) {
+            HIPCHK(hipMemcpyAsync(w.qo[0].p, qo, (size_t)nb * 16, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(w.qd[0].p, qd, (size_t)nb * 16, hipMemcpyHostToDevice, st));
+            if (kq) HIPCHK(hipMemcpyAsync(s->alist[0].p, kq, (size_t)nb * 8, hipMemcpyHostToDevice, st));
+            qo = w.qo[0].p; qd = w.qd[0].p; kq = kq ? s->alist[0].p : nullptr;
+            scol = w.scol.p;
+            mean = mean ? s->tile.p : nullptr; albedo = albedo ? s->acc.p : nullptr; normal = normal ? s->asq.p : nullptr;
+            ids = ids ? s->acnt.p : nullptr;
+        }
+        HIPCHK(hipMemsetAsync(w.ctrl.p, 0, sizeof(DCtrl), st));
+        hipLaunchKernelGGL(k_rays_begin, ew_grid, ew_block, 0, st, nb, make ? qd : nullptr, w.qd[0].p, w.qpath[0].p, w.ctrl.p);
+        HIPCHK(hipGetLastError());
+        if (make) qd = w.qd[0].p;
+        for (uint32_t pass = 0; pass < npass; pass++) {
+            const int a = pass & 1, b = a ^ 1;
+            const float4 *pqo = pass ? w.qo[a].p : qo, *pqd = pass ? w.qd[a].p : qd;  // pass 0 traces the rays where they are
+            HIPCHK(hipEventRecord(w.pass_ev[2 * pass], st));
+            launch_trace(s, w, st, pqo, pqd, (int)pass, counting, w.pass_ev[2 * pass + 1]);
+            HIPCHK(hipGetLastError());
+            if (pass == 0 && guides)  // before pass 1 rewrites the hit records
+                hipLaunchKernelGGL(k_features, ew_grid, ew_block, 0, st, s->d, ng, G, w.hit_tf.p, w.hit_t.p, (float*)albedo, (float*)normal, ids,
+                                   0u, ng, 1u, 0u, make_fastdiv(ng), make_fastdiv(G));
+            if (shade)
+                hipLaunchKernelGGL(k_shade_rays, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(rp->pixel0 + gbase), nb, (int)pass, pqo, pqd,
+                                   w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, scol, w.ctrl.p,
+                                   SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, kq);
+            HIPCHK(hipGetLastError());
+        }
+        if (shade && mean)
+            hipLaunchKernelGGL(k_accum, ew_grid, ew_block, 0, st, ng, G, scol, (float*)mean, 0u, ng, 1u, 0u, make_fastdiv(ng));
+        HIPCHK(hipGetLastError());
+        if (host) {
+            if (out->color && shade) HIPCHK(hipMemcpyAsync((float4*)out->color + base, scol, (size_t)nb * 16, hipMemcpyDeviceToHost, st));
+            if (mean && shade) HIPCHK(hipMemcpyAsync((float4*)out->mean + gbase, mean, (size_t)ng * 16, hipMemcpyDeviceToHost, st));
+            if (albedo) HIPCHK(hipMemcpyAsync((float4*)out->albedo + gbase, albedo, (size_t)ng * 16, hipMemcpyDeviceToHost, st));
+            if (normal) HIPCHK(hipMemcpyAsync((float4*)out->normal + gbase, normal, (size_t)ng * 16, hipMemcpyDeviceToHost, st));
+            if (ids) HIPCHK(hipMemcpyAsync((uint32_t*)out->ids + gbase, ids, (size_t)ng * 4, hipMemcpyDeviceToHost, st));
+        }
+        // the batch's counters and the time of every pass's closest-hit launch; the next batch reuses the workspace
+        DCtrl h;
+        HIPCHK(hipMemcpyAsync(&h, w.ctrl.p, sizeof(DCtrl), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        add_counters(sum, ctrl_counters(h));
+        for (uint32_t pass = 0; pass < npass; pass++) {
+            float pm = 0.f;
+            HIPCHK(hipEventElapsedTime(&pm, w.pass_ev[2 * pass], w.pass_ev[2 * pass + 1]));
+            launches++;
+            trace_ms += pm;
+            if (s->verbose) fprintf(stderr, "[rtmi] rays batch@%llu pass %u: %u rays, trace %.3f ms\n", (unsigned long long)base, pass, h.count[pass], pm);
+        }
+    }
+    if (!host) {
+        HIPCHK(hipEventRecord(s->join_ev[0], st));
+        HIPCHK(hipStreamWaitEvent(ust, s->join_ev[0], 0));
+    }
+    HIPCHK(hipEventRecord(s->end_ev, ust));
+    HIPCHK(hipEventSynchronize(s->end_ev));
+    float kernel_ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&kernel_ms, s->fork_ev, s->end_ev));
+    if (stats) {
+        add_counters(*stats, sum);
+        stats->kernel_ms = kernel_ms; stats->trace_ms = trace_ms; stats->trace_launches = launches; stats->streams = 1;
+        stats->pipeline = 1u;
+    }
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+int rtmi_render_rays_device(rtmi_scene_t* s, uint64_t n, const void* orig4_device, const void* dir4_device, const void* keys_device,
+                            uint64_t seed, const rtmi_rays_t* rays, const rtmi_rays_out_t* out_device, void* hip_stream,
+                            rtmi_stats_t* stats) {
+    return render_rays(s, n, orig4_device, dir4_device, keys_device, seed, rays, out_device, hip_stream, stats, false);
+}
+
+int rtmi_render_rays(rtmi_scene_t* s, uint64_t n, const float* orig4, const float* dir4, const uint32_t* keys, uint64_t seed,
+                     const rtmi_rays_t* rays, const rtmi_rays_out_t* out_host, rtmi_stats_t* stats) {
+    return render_rays(s, n, orig4, dir4, keys, seed, rays, out_host, nullptr, stats, true);
+}
+
+// rtmi_trace on device buffers: the rays are read where they are, one closest-hit launch, one elementwise kernel
+int rtmi_trace_device(rtmi_scene_t* s, uint64_t n, const void* orig4_device, const void* dir4_device, void* tri_device, void* t_device,
+                      void* face_device, void* hip_stream, rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!s) return fail(RTMI_ERR_INVALID, "trace_device: NULL argument (scene)");
+    if (n == 0) return RTMI_OK;
+    if (!orig4_device || !dir4_device || !tri_device || !t_device || !face_device)
+        return fail(RTMI_ERR_INVALID, "trace_device: NULL argument (orig4, dir4, tri, t and face are required)");
+    const uint64_t m = std::min<uint64_t>(n, 1ull << 40);
+    const ByteRange r[5] = {{orig4_device, m * 16, "orig4"}, {dir4_device, m * 16, "dir4"}, {tri_device, m * 4, "tri"}, {t_device, m * 4, "t"},
+                            {face_device, m * 4, "face"}};
+    size_t a, b;
+    if (ranges_overlap(r, 5, a, b))
+        return fail(RTMI_ERR_INVALID, std::string("trace_device: buffers overlap (") + r[a].name + " and " + r[b].name + ")");
+    if (n >= (1ull << 31)) return fail(RTMI_ERR_UNSUPPORTED, "trace_device: more than 2^31 rays per call");
+    RTMI_GUARD_BEGIN
+    (void)hipGetLastError();
+    HIPCHK(hipSetDevice(s->device));
+    Work& w = s->w[0];
+    int rc = ensure_workspace(w, (size_t)n, 1);
+    if (rc != RTMI_OK) return rc;
+    hipStream_t st = s->istream[0], ust = (hipStream_t)hip_stream;
+    HIPCHK(hipEventRecord(s->fork_ev, ust));
+    HIPCHK(hipStreamWaitEvent(st, s->fork_ev, 0));
+    HIPCHK(hipMemsetAsync(w.ctrl.p, 0, sizeof(DCtrl), st));
+    hipLaunchKernelGGL(k_set_count, dim3(1), dim3(1), 0, st, w.ctrl.p, (uint32_t)n);
+    HIPCHK(hipEventRecord(w.ev[0], st));
+    s->active_streams = 1;
+    launch_trace(s, w, st, (const float4*)orig4_device, (const float4*)dir4_device, 0, (s->options & RTMI_OPT_COUNTERS) != 0, w.ev[1]);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_unpack_hits, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)s->num_cu * 8)), dim3(256), 0, st, (uint32_t)n,
+                       w.hit_tf.p, w.hit_t.p, (uint32_t*)tri_device, (float*)t_device, (uint32_t*)face_device);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(s->join_ev[0], st));
+    HIPCHK(hipStreamWaitEvent(ust, s->join_ev[0], 0));
+    HIPCHK(hipEventRecord(s->end_ev, ust));
+    HIPCHK(hipEventSynchronize(s->end_ev));
+    float kernel_ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&kernel_ms, s->fork_ev, s->end_ev));
+    return collect_occluded(w, st, stats, kernel_ms);
     RTMI_GUARD_END
 }
 

@@ -66,7 +66,10 @@ __device__ inline void tile_pixel(const DView& v, uint32_t lp, uint32_t& row, ui
 // sub_off = 0).  The list pointer is an argument of the list kernels only, so the other kernels keep their launch constants.
 // VIEWS: a batch of views of one scene (rtmi_render_views*), FRAME semantics over a stacked image whose row
 // k * height + r is row r of view k; each view has its own camera and seed (ViewTab, an argument of the views kernels only).
-enum class Samp { FRAME, PASS, LIST, VIEWS };
+// RAYS: caller-supplied rays (rtmi_render_rays*).  There is no camera and no tile: path i of a batch is its i-th
+// ray and its RNG key comes from rays_key() below.  No generation kernel and no path kernel exists for this mode; only
+// shade_pass is instantiated for it (k_shade_rays), in a branch of its own, so the other modes keep the code they had.
+enum class Samp { FRAME, PASS, LIST, VIEWS, RAYS };
 // Samp::VIEWS: view k's camera (lane 3 of every vector +0, as mk() makes them) and seed
 struct VCam { float4 orig, cam, vu, vv; unsigned long long seed; uint32_t pad[2]; };
 // the view table of a VIEWS launch: one VCam per view, and n / height (height = the rows of ONE view, DView::height)
@@ -100,6 +103,21 @@ __device__ inline void path_pixel(const DView& v, uint32_t pix0, uint32_t path, 
     const uint32_t q = fdiv(path, v.dspp);
     sample = (S != Samp::FRAME && S != Samp::VIEWS ? (v.sample_key & ~RTMI_KEY_JITTER) : 0u) + (path - q * v.spp);
     tile_pixel(v, S == Samp::LIST ? list[pix0 + q] : pix0 + q, row, col);
+}
+
+// Samp::RAYS: the RNG key (pixel, sample) of path `path` of a batch.  keys != null: the caller's pair for that ray (the batch's
+// slice of the n x 2 array).  Otherwise rays come in groups of G = v.spp consecutive rays, group g of the batch is "pixel"
+// pix0 + g (pix0: the key of the batch's first group) and a ray's sample is its place in its group.
+__device__ inline void rays_key(const DView& v, uint32_t pix0, uint32_t path, const uint32_t* __restrict__ keys, uint32_t& pixel,
+                                uint32_t& sample) {
+    if (keys) {
+        pixel = keys[2u * path];
+        sample = keys[2u * path + 1u];
+    } else {
+        const uint32_t g = fdiv(path, v.dspp);
+        pixel = pix0 + g;
+        sample = path - g * v.spp;
+    }
 }
 
 struct RayV { V4 orig, dir; };

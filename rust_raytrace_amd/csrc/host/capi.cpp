@@ -523,6 +523,32 @@ int rth_caster_trace(rth_scene_t* s, uint64_t n, const float* o4, const float* d
     });
 }
 
+int rth_caster_trace_device(rth_scene_t* s, uint64_t n, const void* orig4_device, const void* dir4_device, void* tri_device, void* t_device,
+                            void* face_device, void* hip_stream, rtmi_stats_t* stats) {
+    return guarded([&] { caster_of(s).trace_device(s->scene, n, orig4_device, dir4_device, tri_device, t_device, face_device, hip_stream, stats); });
+}
+int rth_caster_walk_rays_explicit(rth_scene_t* s, uint64_t n, const float* o4, const float* d4, const uint32_t* keys, const rtmi_rays_t* rays,
+                                  const rtmi_rays_out_t* out_host, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_rays_explicit(s->scene, n, o4, d4, keys, rays, out_host, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
+int rth_caster_walk_rays_explicit_device(rth_scene_t* s, uint64_t n, const void* orig4_device, const void* dir4_device, const void* keys_device,
+                                         const rtmi_rays_t* rays, const rtmi_rays_out_t* out_device, void* hip_stream, rtmi_stats_t* stats,
+                                         double* wall) {
+    return guarded([&] {
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_rays_explicit_device(s->scene, n, orig4_device, dir4_device, keys_device, rays, out_device, hip_stream, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
+
 int rth_caster_trace_records(rth_scene_t* s, uint64_t n, const float* o4, const float* d4, rtmi_ray_record_t* recs, uint32_t* leaf_ids,
                              uint64_t leaf_cap, uint64_t* leaf_total, rtmi_stats_t* stats) {
     return guarded([&] {

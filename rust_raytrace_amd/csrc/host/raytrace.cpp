@@ -761,6 +761,36 @@ void HipRayCaster::occluded_device(const Scene& s, uint64_t n, const void* orig4
         throw std::runtime_error(std::string("rtmi_occluded_device: ") + rtmi_last_error());
 }
 
+void HipRayCaster::trace_device(const Scene& s, uint64_t n, const void* orig4_device, const void* dir4_device, void* tri_device, void* t_device,
+                                void* face_device, void* hip_stream, rtmi_stats_t* stats) {
+    rtmi_scene_t* h = resident(s);
+    if (rtmi_trace_device(h, n, orig4_device, dir4_device, tri_device, t_device, face_device, hip_stream, stats) != RTMI_OK)
+        throw std::runtime_error(std::string("rtmi_trace_device: ") + rtmi_last_error());
+}
+
+void HipRayCaster::walk_rays_explicit(const Scene& s, uint64_t n, const float* orig4, const float* dir4, const uint32_t* keys,
+                                      const rtmi_rays_t* rays, const rtmi_rays_out_t* out_host, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_rays(h, n, orig4, dir4, keys, seed, rays, out_host, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_rays: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
+void HipRayCaster::walk_rays_explicit_device(const Scene& s, uint64_t n, const void* orig4_device, const void* dir4_device,
+                                             const void* keys_device, const rtmi_rays_t* rays, const rtmi_rays_out_t* out_device,
+                                             void* hip_stream, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_rays_device(h, n, orig4_device, dir4_device, keys_device, seed, rays, out_device, hip_stream, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_rays_device: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
 void HipRayCaster::walk_rays_ao(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
                                 const rtmi_ao_t& ao, float* out, ProgressCtx& progress) {
     rtmi_scene_t* h = resident(s);

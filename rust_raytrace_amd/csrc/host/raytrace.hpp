@@ -226,6 +226,15 @@ public:
                   rtmi_stats_t* stats = nullptr);
     void occluded_device(const Scene& s, uint64_t n, const void* orig4_device, const void* dir4_device, const void* tmax_device,
                          void* occluded_device, void* hip_stream, rtmi_stats_t* stats = nullptr);
+    // rtmi_trace on device buffers (rtmi_trace_device): rays read in place, tri / t / face written in place.
+    void trace_device(const Scene& s, uint64_t n, const void* orig4_device, const void* dir4_device, void* tri_device, void* t_device,
+                      void* face_device, void* hip_stream, rtmi_stats_t* stats = nullptr);
+    // Path tracing of caller-supplied rays (rtmi_render_rays / rtmi_render_rays_device, which rtmi.h defines) with the caster's
+    // seed: per-ray colours, per-group means and the groups' first-hit guide buffers.  keys: n x 2 uint32 or null.
+    void walk_rays_explicit(const Scene& s, uint64_t n, const float* orig4, const float* dir4, const uint32_t* keys, const rtmi_rays_t* rays,
+                            const rtmi_rays_out_t* out_host, ProgressCtx& progress);
+    void walk_rays_explicit_device(const Scene& s, uint64_t n, const void* orig4_device, const void* dir4_device, const void* keys_device,
+                                   const rtmi_rays_t* rays, const rtmi_rays_out_t* out_device, void* hip_stream, ProgressCtx& progress);
     // Ambient occlusion (rtmi_render_ao / rtmi_render_ao_device, which rtmi.h defines): one float per pixel, the share of
     // ao.rays hemisphere rays per primary sample of [sample0, sample0 + nsamples) that are not occluded within ao.radius.
     void walk_rays_ao(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,

@@ -1195,6 +1195,121 @@ class HipRayCaster:
                                                    C.c_void_p(ptrs[2]), C.c_void_p(stream or 0), C.byref(st)))
         return st.as_dict()
 
+    def trace_device(self, s, orig4, dir4, tri, t, face, stream=None):
+        """trace() on torch tensors on the scene's device (rtmi_trace_device): orig4 and dir4 are contiguous float32 tensors of
+        n * 4 elements, read in place; tri and face (int32 or uint32) and t (float32) are contiguous tensors of n elements,
+        written in place.  The work starts after what is queued on `stream` (a torch stream, a raw HIP stream pointer or None)
+        and that stream waits for it.  -> stats."""
+        n = self._ray_tensors(orig4, dir4)
+        for name, x, dts in (("tri", tri, ("torch.int32", "torch.uint32")), ("t", t, ("torch.float32",)), ("face", face, ("torch.int32", "torch.uint32"))):
+            self._tensor(name, x, n, dts)
+        self._config(s)
+        st = _ffi.Stats()
+        _chk(_ffi.lib().rth_caster_trace_device(s.h, n, C.c_void_p(orig4.data_ptr()), C.c_void_p(dir4.data_ptr()), C.c_void_p(tri.data_ptr()),
+                                                C.c_void_p(t.data_ptr()), C.c_void_p(face.data_ptr()),
+                                                C.c_void_p(getattr(stream, "cuda_stream", stream) or 0), C.byref(st)))
+        return st.as_dict()
+
+    RAYS_MAKE_RAY = 1
+    RAYS_OUTPUTS = ("color", "mean", "albedo", "normal", "ids")
+
+    @staticmethod
+    def _tensor(name, x, want, dts):
+        if not hasattr(x, "data_ptr") or not x.is_cuda or str(x.dtype) not in dts or not x.is_contiguous() or x.numel() != want:
+            raise ValueError(f"{name} must be a contiguous {dts[0][6:]} tensor of {want} elements on the device")
+
+    @classmethod
+    def _ray_tensors(cls, orig4, dir4):
+        if not hasattr(orig4, "data_ptr") or orig4.numel() % 4:
+            raise ValueError("orig4 must be a contiguous float32 tensor of n * 4 elements on the device")
+        n = orig4.numel() // 4
+        cls._tensor("orig4", orig4, 4 * n, ("torch.float32",))
+        cls._tensor("dir4", dir4, 4 * n, ("torch.float32",))
+        return n
+
+    @classmethod
+    def _rays_args(cls, n, maxdepth, group, pixel0, make_ray, keyed):
+        maxdepth, group, pixel0 = int(maxdepth), int(group), int(pixel0)
+        if not 0 <= maxdepth <= 32:
+            raise ValueError("maxdepth must be in [0, 32]")
+        if not 1 <= group <= 65536:
+            raise ValueError("group must be in [1, 65536]")
+        if n % group:
+            raise ValueError("the number of rays must be a multiple of group")
+        if n >= 1 << 31:
+            raise ValueError("at most 2^31 - 1 rays per call")
+        if pixel0 < 0 or (not keyed and n and pixel0 + n // group - 1 >= 1 << 32):
+            raise ValueError("pixel0 + n / group - 1 must stay below 2^32")
+        return _ffi.Rays(maxdepth, group, pixel0 & 0xFFFFFFFF, cls.RAYS_MAKE_RAY if make_ray else 0)
+
+    def walk_rays_explicit(self, s, orig4, dir4, maxdepth, group=1, keys=None, pixel0=0, make_ray=False, color=True, mean=False,
+                           albedo=False, normal=False, ids=False):
+        """Path tracing of caller-supplied rays (rtmi_render_rays; include/rtmi.h defines it): orig4 and dir4 are (n, 4) float32
+        arrays, a ray's origin and unit direction as make_ray stores them (make_ray=True: the library normalises the
+        directions).  The RNG key of ray i is keys[i] = (pixel, sample) ((n, 2) uint32) or, without keys, (pixel0 + i // group,
+        i % group).  Outputs, each produced when its flag is true: color (n, 4) float32, the colour project_ray returns for each
+        ray at depth `maxdepth`; mean (n // group, 4), the f32 mean of each group of `group` consecutive rays in walk_ray_set's
+        order; albedo and normal (n // group, 4) and ids (n // group) uint32, the first-hit feature buffers with a group
+        standing for a pixel.  Returns (dict of the requested arrays, ctx)."""
+        o4, d4 = _f(orig4).reshape(-1, 4), _f(dir4).reshape(-1, 4)
+        n = o4.shape[0]
+        if d4.shape[0] != n:
+            raise ValueError("orig4 and dir4 must hold the same number of rays")
+        kk = None
+        if keys is not None:
+            kk = np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1, 2)
+            if kk.shape[0] != n:
+                raise ValueError("keys must hold one (pixel, sample) pair per ray")
+        r = self._rays_args(n, maxdepth, group, pixel0, make_ray, kk is not None)
+        ng = n // r.group
+        shapes = {"color": ((n, 4), np.float32), "mean": ((ng, 4), np.float32), "albedo": ((ng, 4), np.float32),
+                  "normal": ((ng, 4), np.float32), "ids": ((ng,), np.uint32)}
+        want = dict(color=color, mean=mean, albedo=albedo, normal=normal, ids=ids)
+        bufs = {k: np.zeros(*shapes[k]) for k in self.RAYS_OUTPUTS if want[k]}
+        if not bufs:
+            raise ValueError("at least one of color, mean, albedo, normal and ids must be produced")
+        out = _ffi.RaysOut(*[_p(bufs[k]) if k in bufs else None for k in self.RAYS_OUTPUTS])
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_rays_explicit(s.h, n, _p(o4), _p(d4), _p(kk) if kk is not None else None, C.byref(r), C.byref(out),
+                                                      C.byref(st), C.byref(wall)))
+        return bufs, ProgressCtx(st.rays, wall.value, st.as_dict())
+
+    def walk_rays_explicit_device(self, s, orig4, dir4, maxdepth, group=1, keys=None, pixel0=0, make_ray=False, color=None, mean=None,
+                                  albedo=None, normal=None, ids=None, stream=None):
+        """The same on torch tensors on the scene's device (rtmi_render_rays_device), read and written in place: orig4 and dir4
+        contiguous float32 of n * 4 elements, keys None or contiguous int32 / uint32 of n * 2; each output a contiguous tensor or
+        None (not all): color float32 of n * 4, mean, albedo and normal float32 of (n // group) * 4, ids int32 or uint32 of
+        n // group; no two buffers may overlap.  The work starts after what is queued on `stream` (a torch stream, a raw HIP
+        stream pointer or None) and that stream waits for it.  Returns ctx."""
+        n = self._ray_tensors(orig4, dir4)
+        if keys is not None:
+            self._tensor("keys", keys, 2 * n, ("torch.int32", "torch.uint32"))
+        r = self._rays_args(n, maxdepth, group, pixel0, make_ray, keys is not None)
+        ng = n // r.group
+        spec = (("color", color, 4 * n, ("torch.float32",)), ("mean", mean, 4 * ng, ("torch.float32",)),
+                ("albedo", albedo, 4 * ng, ("torch.float32",)), ("normal", normal, 4 * ng, ("torch.float32",)),
+                ("ids", ids, ng, ("torch.int32", "torch.uint32")))
+        for name, x, want, dts in spec:
+            if x is not None:
+                self._tensor(name, x, want, dts)
+        if all(x is None for _, x, _, _ in spec):
+            raise ValueError("at least one of color, mean, albedo, normal and ids must be given")
+        spans = [(orig4.data_ptr(), 16 * n), (dir4.data_ptr(), 16 * n)] + ([(keys.data_ptr(), 8 * n)] if keys is not None else [])
+        spans = sorted(spans + [(x.data_ptr(), 4 * want) for _, x, want, _ in spec if x is not None])
+        if any(a[0] + a[1] > b[0] for a, b in zip(spans, spans[1:]) if a[1] and b[1]):
+            raise ValueError("the buffers must not overlap")
+        self._config(s)
+        out = _ffi.RaysOut(*[x.data_ptr() if x is not None else None for _, x, _, _ in spec])
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_rays_explicit_device(s.h, n, C.c_void_p(orig4.data_ptr()), C.c_void_p(dir4.data_ptr()),
+                                                             C.c_void_p(keys.data_ptr()) if keys is not None else None, C.byref(r),
+                                                             C.byref(out), C.c_void_p(getattr(stream, "cuda_stream", stream) or 0),
+                                                             C.byref(st), C.byref(wall)))
+        return ProgressCtx(st.rays, wall.value, st.as_dict())
+
     def _records(self, n, call, pixel=None):
         """Size query, then the fill (rth_caster_*_records)"""
         recs = np.zeros(n, REC_DTYPE)
