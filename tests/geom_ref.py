@@ -336,7 +336,10 @@ def tri_box_penetration(corners, centre, half):
 def leaf_completeness(g, geo, topo, refs, margin=BOX_MARGIN):
     """Every leaf of a flattened tree (geo (nb, 4) centre + half edge, topo (nb, 4) first / count / is_leaf / depth, refs) must
     list every triangle 1..n-1 that reaches more than `margin` into its box.  -> dict(missing: list of (box, triangle),
-    required: pairs that must be listed, skipped: pairs within +-margin (not judged), leaves)."""
+    required: pairs that must be listed, skipped: pairs within +-margin (not judged), leaves).
+    A triangle lying exactly in a split plane of the octree touches every box on either side with a penetration of 0, inside
+    the +-margin: such pairs are skipped, so this check does not see that the reference's builder lists that triangle in NO
+    leaf (DESIGN.md 2 (vii); tests/test_draw_cpu.py::test_floor_in_a_split_plane_is_listed_in_no_leaf states that behaviour)."""
     geo, topo, refs = np.asarray(geo, np.float64), np.asarray(topo), np.asarray(refs, np.int64)
     boxes = np.nonzero(topo[:, 2] == 1)[0]
     leaves, ntri = len(boxes), len(g.corners)
