@@ -94,6 +94,7 @@ typedef struct rtmi_stats {
     double bounce_ms;       /* the bounce passes' closest-hit launches (k_trace_oct)                               */
     /* (rtmi_render_ao*: primary_ms = the primary rays' closest-hit launches, bounce_ms = the AO rays' walk launches)     */
     /* (rtmi_render_light*: likewise, bounce_ms = the live shadow rays' walk launches)                                    */
+    /* (rtmi_render_shadowed*: primary_ms = the closest-hit launches of ALL passes, bounce_ms = the shadow rays' walk launches) */
     int32_t peer_access;    /* 1 = this device writes the root device's memory directly (peer access enabled, or the
                              * same device); 0 = the runtime refused: the band is staged (rtmi_last_error() carries a
                              * warning although the call returns RTMI_OK)                                      */
@@ -532,8 +533,9 @@ int rtmi_trace(rtmi_scene_t* scene, uint64_t n, const float* orig4, const float*
  * n == 0: RTMI_OK, nothing is touched (checked after the scene, before the buffers).  RTMI_ERR_INVALID, before any HIP call
  * and before the scene is used: a NULL scene, orig4, dir4 or occluded; an output that overlaps an input (as byte ranges of 16 n,
  * 16 n, 4 n and n bytes).  RTMI_ERR_UNSUPPORTED: n >= 2^31, as for rtmi_trace.  stats come back cleared on failure.
- * Not here: shadow rays in shading, occlusion for batches of views and for rtmi_render_frame_multi.  (The
- * ambient-occlusion buffer is rtmi_render_ao*, the shadow layer of a box light rtmi_render_light*, both below.) */
+ * Not here: occlusion for batches of views and for rtmi_render_frame_multi.  (The
+ * ambient-occlusion buffer is rtmi_render_ao*, the shadow layer of a box light rtmi_render_light*, shadow rays inside the
+ * shading of every bounce rtmi_render_shadowed*, all below.) */
 int rtmi_occluded(rtmi_scene_t* scene, uint64_t n, const float* orig4, const float* dir4, const float* tmax /* n floats or NULL */,
                   uint8_t* occluded, rtmi_stats_t* stats);
 int rtmi_occluded_device(rtmi_scene_t* scene, uint64_t n, const void* orig4_device, const void* dir4_device,
@@ -734,8 +736,8 @@ int rtmi_render_ao(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed
  * 4 B per candidate) lives on the handle, grows on demand and is freed by rtmi_scene_destroy; a batch holds at most
  * batch_paths candidates.  No tuning changes a bit of the result.  The device variant enqueues on hip_stream like
  * rtmi_render_tile_device; the host variant renders rows [row0, row0 + nrows) and copies 4 B per pixel and plane out.
- * Not here: shadow rays inside color_ray, batches of views and rtmi_render_frame_multi, the buffer as a denoiser
- * guide, importance sampling.  (Several lights in one call, each with a colour, composed per sample with albedo and AO:
+ * Not here: batches of views and rtmi_render_frame_multi, the buffer as a denoiser guide, importance sampling.  (Shadow rays
+ * inside color_ray, at every hit of every bounce: rtmi_render_shadowed*, below.)  (Several lights in one call, each with a colour, composed per sample with albedo and AO:
  * rtmi_render_preview*, below, which also returns these two planes for every light.) */
 enum { RTMI_LIGHT_UNBOUNDED = 1u << 0 };
 typedef struct rtmi_light {
@@ -752,6 +754,59 @@ int rtmi_render_light_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uin
 int rtmi_render_light(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
                       uint32_t sample0, uint32_t nsamples, const rtmi_light_t* light, float* shadow_host, float* irradiance_host,
                       rtmi_stats_t* stats);
+
+/* Path tracing with the reference's shadow rays inside color_ray: a progressive pass in which every surface
+ * hit of every bounce is tested against ONE box light and shows black where it is shadowed.  The reference spells the test
+ * out in color_ray (raytrace.rs:1203-1224: `let shadowed = ...; if !shadowed {color} else {black}` for Solid, Matte and
+ * Reflective alike) around _get_shadow_ray (:600-610) and never runs it, so the image is build-defined like
+ * rtmi_render_light*: what follows IS the definition, and tests/shadowed_ref.py pins it bit for bit.  rtmi_render and
+ * rtmi_render_samples* are unchanged.  All arithmetic is f32 on all four lanes, no contraction.
+ * Contract: rtmi_render_samples[_device]'s in every respect -- samples [sample0, sample0 + nsamples) of a frame of S =
+ * vp->samples_per_pixel samples, accum continued (read only when sample0 > 0) and rewritten, out (may be NULL) = accum *
+ * (1.f / (float)(sample0 + nsamples)), the tile's layout, the stream's semantics, maxdepth == 0 writes zeros -- plus:
+ * Paths: the rays of every pass are exactly those of rtmi_render_samples_device for the same arguments.  The shadow bit
+ *   changes colours only: never a ray, never an RNG block 0 .. maxdepth, never the "Rays" a plain render counts.
+ * Shadow test: made at the hit of a path's ray number j (j = the bounces behind it, 0 for the primary ray) when the hit is
+ *   neither a miss nor an edge face (face & 2): Solid, Matte and Reflective, including the last ray of a path whose depth is
+ *   exhausted.  With (ro, rd) that ray, (tri, t, face) its closest hit as rtmi_trace returns it under the handle's options,
+ *   (p, s) the path's pixel (row * width + col) and sample number:
+ *     point = rd * t + ro                          (a multiplication, then an addition);
+ *     n     = the triangle's norm, * (-1.f) when face & 1;
+ *     w     = RNG block 0xC0000000 | j of (seed, p, s), u_c = top 24 bits of w_c * 2^-24;
+ *     adj, v, d2, r, dir, o, c                     exactly as rtmi_render_light* states them, from light->orig, len2, bias;
+ *     shadowed_j = !(c > 0.f) || rtmi_occluded's answer for (o, dir, tmax = r), the NULL tmax with RTMI_LIGHT_UNBOUNDED.
+ *   ONE candidate per hit: light->rays must be 1.  At j = 0 this is candidate k = 0 of rtmi_render_light* on the same sample.
+ * Colour: color_ray's (shade_hit's), with the surface colour of level j replaced by (0, 0, 0) where shadowed_j:
+ *   c = mix_color(shadowed_j ? black : color_j, c, alpha_j), evaluated inside-out over the path's Matte / Reflective levels;
+ *   a terminal Solid shows shadowed ? black : color.  The sky, edge faces and the black of an exhausted depth are untouched.
+ * Per pixel: rtmi_render_samples_device's sums (acc = acc + sample colour in sample order; * the reciprocal).
+ * Scenes: octree, linear list, generic tree and RTMI_OPT_GENERIC are exact; RTMI_OPT_FAST / RTMI_OPT_BVH give their own
+ *   modes' hits and answers.  RTMI_ERR_UNSUPPORTED for a scene with analytic spheres.
+ * RTMI_ERR_INVALID, before any HIP call and before the scene is used, stats cleared: every check of
+ *   rtmi_render_samples[_device] (NULL scene, viewport, tile or accum; accum == out; nsamples == 0; sample0 + nsamples > S;
+ *   the viewport and tile checks), every parameter check of rtmi_render_light* on light (NULL; rays 0 or above 256; unknown
+ *   flag bits; len2 NaN, negative or infinite; a non-finite orig or bias), and rays != 1.  An empty tile returns RTMI_OK.
+ * stats: rays = the plain call's rays + the live shadow rays traced (live = c > 0.f); pipeline = 1, slow_paths = 0 (no slow
+ *   queue: a ray with a zero direction component is traced in place); trace_launches counts, per batch and pass, the
+ *   closest-hit launch and the shadow rays' walk launch (2 * maxdepth per batch); trace_ms is their summed time, primary_ms
+ *   the closest-hit launches' share (all passes, not only the primary rays'), bounce_ms the walks' share.  With
+ *   RTMI_OPT_COUNTERS the five work counters are the plain call's closest-hit work plus the walks' actual work.
+ * How: always the per-pass pipeline (rtmi_tuning_t.pipeline is not consulted), batches, sub-tiles and streams as for
+ *   rtmi_render_samples_device.  Per pass: the closest-hit launch; k_shadow_rays builds the candidates and compacts the live
+ *   ones into a shadow queue whose counter stays on the device (a second control block per stream); the scene's any-hit walk
+ *   of that queue (its closest-hit launch where rtmi_occluded uses that, with hit records of its own); k_shade_shadowed
+ *   shades with the answers, keeping one mask word per path (bit j = shadowed_j).  Nothing is copied to the host between
+ *   passes.  The buffers (45 B per path at most beside the plain workspace, plus 8 B per path on scenes without an any-hit
+ *   kernel) live on the handle, grow on demand and are freed by rtmi_scene_destroy.  No tuning changes a bit of the result.
+ * Not here: several or coloured lights inside the path, more than one light sample per hit, falloff or a cosine term (the
+ *   reference's test is binary), shadowed variants of rtmi_render_rays*, adaptive passes, batches of views,
+ *   rtmi_render_frame_multi and the path kernels (pipeline 3). */
+int rtmi_render_shadowed_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile,
+                                uint32_t sample0, uint32_t nsamples, const rtmi_light_t* light, void* accum_device,
+                                void* out_device /* or NULL */, void* hip_stream, rtmi_stats_t* stats);
+int rtmi_render_shadowed(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
+                         uint32_t sample0, uint32_t nsamples, const rtmi_light_t* light, float* accum_host,
+                         float* out_host /* or NULL */, rtmi_stats_t* stats);
 
 /* A shaded preview in one call: albedo, ambient occlusion and up to four coloured box lights composed PER
  * SAMPLE on the device, from one primary pass per batch and one any-hit walk of the AO rays and every light's live shadow
@@ -799,7 +854,7 @@ int rtmi_render_light(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t s
  * order.  A path counts as Ka + the sum of K_l queue entries: a batch's entries stay within batch_paths.  The queue lives on
  * the handle, grows on demand and is freed by rtmi_scene_destroy.  No tuning changes a bit of the result.
  * Not here: previews of batches of views and of rtmi_render_frame_multi, sums continued across calls, importance sampling,
- * shadow rays inside color_ray, a denoised-preview one-call wrapper. */
+ * shadow rays inside color_ray (rtmi_render_shadowed*, above), a denoised-preview one-call wrapper. */
 enum { RTMI_PREVIEW_MAX_LIGHTS = 4 };
 typedef struct rtmi_preview {
     float ambient[3];          /* offset 0                                                  */

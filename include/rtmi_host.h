@@ -154,6 +154,17 @@ int rth_caster_walk_light_device(rth_scene_t* s, uint32_t w, uint32_t h, const f
                                  const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, const rtmi_light_t* light,
                                  void* shadow_device, void* irradiance_device, void* hip_stream, rtmi_stats_t* stats,
                                  double* wall_seconds);
+/* Path tracing with the reference's shadow rays switched on (rtmi_render_shadowed / rtmi_render_shadowed_device in rtmi.h,
+ * which defines it): rth_caster_walk_samples[_device] in every respect, with every surface hit of every bounce tested against
+ * `light`, which becomes the scene's light (the host mirror's Scene::light, the reference's commented-out field).
+ * light->rays must be 1. */
+int rth_caster_walk_shadowed(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp, uint64_t row0,
+                             uint64_t nrows, uint32_t sample0, uint32_t nsamples, const rtmi_light_t* light, float* accum_host,
+                             float* out_host, rtmi_stats_t* stats, double* wall_seconds);
+int rth_caster_walk_shadowed_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                                    const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, const rtmi_light_t* light,
+                                    void* accum_device, void* out_device, void* hip_stream, rtmi_stats_t* stats,
+                                    double* wall_seconds);
 /* The shaded preview (rtmi_render_preview / rtmi_render_preview_device, which rtmi.h defines) on the scene's resident copy:
  * albedo, ambient occlusion and up to four coloured box lights composed per sample, with the layers `out` asks for.  maxdepth
  * is not consulted; the primary rays use the caster's seed. */

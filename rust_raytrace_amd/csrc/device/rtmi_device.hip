@@ -381,6 +381,7 @@ __global__ void __launch_bounds__(256) k_trace(DScene sc, const float4* __restri
 #include "light.hpp"
 #include "preview.hpp"
 #include "rays.hpp"
+#include "shadowed.hpp"
 namespace rtmi {
 
 
@@ -1115,6 +1116,19 @@ struct rtmi_scene {
     } pv[RTMI_MAX_STREAMS];
     DevBuf<float4> pv_out4;
     DevBuf<float> pv_out1;
+    // rtmi_render_shadowed*: per stream, the shadow-ray queue of ONE pass of a batch (origins, directions, limits), each path
+    // queue entry's shadow queue entry, the answer bytes and each path's mask of shadowed levels (grow only), and what the
+    // walks need beside the path queues: `walk` holds the second control block (shadow queue j counts in count[j + 1]), hit
+    // records of its own for scenes whose walk is a closest-hit launch, and the walks' event pairs; nothing else of it is
+    // allocated.  No other call reads or writes them.
+    struct ShadowBuf {
+        DevBuf<float4> qo, qd;
+        DevBuf<float> tmax;
+        DevBuf<uint32_t> slot, mask;
+        DevBuf<uint8_t> occ;
+        Work walk;
+        void release() { qo.release(); qd.release(); tmax.release(); slot.release(); mask.release(); occ.release(); walk.release(); }
+    } shadow[RTMI_MAX_STREAMS];
     DevBuf<uint8_t> mstage, mframe;  // rtmi_render_frame_multi, root scene: received bands / the frame
     hipStream_t mstream = nullptr;   // rtmi_render_frame_multi: this scene's band stream
     std::vector<ncclComm_t> comms;   // root scene, RTMI_FRAME_RCCL: one communicator per scene of the last device list
@@ -1562,6 +1576,7 @@ int rtmi_scene_destroy(rtmi_scene_t* s) {
     for (auto& l : s->light) l.release();
     s->light_out.release();
     for (auto& b : s->pv) b.release();
+    for (auto& b : s->shadow) b.release();
     s->pv_out4.release(); s->pv_out1.release();
     if (s->vcams_ev) (void)hipEventDestroy(s->vcams_ev);
     if (s->mstream) (void)hipStreamDestroy(s->mstream);
@@ -1856,6 +1871,8 @@ struct PreviewCall {
     float4* color; FeatOut fo; float* ao; float* shadow; float* irradiance;
     size_t plane;
 };
+// A shadowed path-trace (rtmi_render_shadowed*): the light every surface hit of every bounce is tested against
+struct ShadowCall { rtmi_light_t p; };
 // One render_tile call: what it renders, and its plan (plan_tile)
 struct TileCall {
     uint64_t seed;
@@ -1866,6 +1883,7 @@ struct TileCall {
     const AoCall* ao;   // an AO call: a features call's primary pass, then k_ao_rays, the any-hit walk of queue 1 and k_ao_resolve
     const LightCall* li;  // a direct-light call: likewise with k_light_rays and k_light_resolve
     const PreviewCall* pv;  // a preview call: the primary pass once, k_preview_rays, one walk of queue 1, k_preview_resolve
+    const ShadowCall* sh;  // a shadowed path-trace: a progressive pass (accum) of the per-pass pipeline with k_shadow_rays, an any-hit walk and k_shade_shadowed per bounce pass
     ViewTab vt;  // VIEWS: the view table (cams == nullptr otherwise)
     Samp mode;  // LIST with lp, PASS with accum, fo, ao, li or pv, VIEWS with vt.cams, FRAME otherwise
     bool counting, path_kernels;
@@ -1907,7 +1925,7 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
     // path kernels (pipeline 3; 0 = automatic): exact-octree scenes get pass 0 from k_path_primary, which generates, traces and
     // shades the primary rays in one kernel.  Everything else (pipeline 1, linear list, generic tree, BVH mode,
     // analytic spheres) starts with k_gen.  Both then run one closest-hit + one shading launch per bounce pass.
-    c.path_kernels = !c.fo && !c.ao && !c.li && !c.pv && s->tune.pipeline != 1u && s->octree && !s->root_is_leaf &&
+    c.path_kernels = !c.fo && !c.ao && !c.li && !c.pv && !c.sh && s->tune.pipeline != 1u && s->octree && !s->root_is_leaf &&
                      !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) && s->d.nspheres == 0;
     // streams = 0 (automatic): one stream for path-kernel tiles of 2^26 paths and more, three otherwise (the per-pass
     // pipelines -- BVH mode: 29.6 ms on three streams, 35.2 on one -- have elementwise kernels to hide).  Since k_shade stopped being
@@ -1987,6 +2005,18 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
             rtmi_scene::PreviewBuf& b = s->pv[t];
             HIPCHK(b.qo.ensure(nao)); HIPCHK(b.qd.ensure(nao)); HIPCHK(b.tmax.ensure(nao)); HIPCHK(b.c.ensure(nao)); HIPCHK(b.occ.ensure(nao));
             HIPCHK(b.alb.ensure(paths)); HIPCHK(b.aslot.ensure(paths)); HIPCHK(b.lslot.ensure(paths * (c.pv->per_path - c.pv->a.Ka)));
+        }
+        if (c.sh) {  // a pass tests at most one ray per path
+            rtmi_scene::ShadowBuf& b = s->shadow[t];
+            HIPCHK(b.qo.ensure(paths)); HIPCHK(b.qd.ensure(paths)); HIPCHK(b.slot.ensure(paths)); HIPCHK(b.mask.ensure(paths)); HIPCHK(b.occ.ensure(paths));
+            if (!(c.sh->p.flags & RTMI_LIGHT_UNBOUNDED)) HIPCHK(b.tmax.ensure(paths));
+            HIPCHK(b.walk.ctrl.ensure(1));
+            if (!occluded_anyhit(s)) { HIPCHK(b.walk.hit_tf.ensure(paths)); HIPCHK(b.walk.hit_t.ensure(paths)); }
+            while (b.walk.pass_ev.size() < 2 * (size_t)c.maxdepth) {
+                hipEvent_t e;
+                HIPCHK(hipEventCreate(&e));
+                b.walk.pass_ev.push_back(e);
+            }
         }
     }
     return RTMI_OK;
@@ -2126,6 +2156,34 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
         HIPCHK(hipGetLastError());
         return RTMI_OK;
     }
+    if (c.sh) {  // per pass: the closest hits of path queue j, its live shadow rays compacted into shadow queue j, their any-hit walk, the shading with the answers
+        const rtmi_light_t& p = c.sh->p;
+        rtmi_scene::ShadowBuf& sb = s->shadow[t];
+        float* tmax = (p.flags & RTMI_LIGHT_UNBOUNDED) ? nullptr : sb.tmax.p;  // unbounded: the walk's NULL tmax
+        HIPCHK(hipMemsetAsync(sb.walk.ctrl.p, 0, sizeof(DCtrl), st));
+        for (uint32_t pass = 0; pass < c.maxdepth; pass++) {
+            const int a = pass & 1, b = a ^ 1;
+            HIPCHK(hipEventRecord(w.pass_ev[2 * pass], st));
+            launch_trace(s, w, st, w.qo[a].p, w.qd[a].p, (int)pass, c.counting, w.pass_ev[2 * pass + 1]);
+            HIPCHK(hipGetLastError());
+            // sb.walk.ctrl->count[pass + 1] (zero since the memset above) is the compaction's counter and then the walk's ray count
+            hipLaunchKernelGGL(k_shadow_rays, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, (int)pass, mk(p.orig[0], p.orig[1], p.orig[2]),
+                               p.len2, p.bias, w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.ctrl.p, sb.qo.p, sb.qd.p, tmax,
+                               sb.slot.p, sb.walk.ctrl.p);
+            HIPCHK(hipEventRecord(sb.walk.pass_ev[2 * pass], st));
+            launch_occluded(s, sb.walk, st, npaths, sb.qo.p, sb.qd.p, tmax, sb.occ.p, (int)pass + 1, sb.walk.pass_ev[2 * pass + 1]);
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(k_shade_shadowed, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
+                               w.qpath[a].p, w.hit_tf.p, w.hit_t.p, sb.slot.p, sb.occ.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p,
+                               sb.mask.p, w.scol.p, w.ctrl.p);
+            HIPCHK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_accum_samples, ew_grid, ew_block, 0, st, np, c.spp, c.sample0, w.scol.p, (float*)c.accum, (float*)c.out,
+                           pix0, c.W, c.nsub, t, make_fastdiv(c.W));
+        HIPCHK(hipEventRecord(w.ev[1], st));
+        HIPCHK(hipGetLastError());
+        return RTMI_OK;
+    }
     for (uint32_t pass = pass0; pass < c.maxdepth; pass++) {
         const int a = pass & 1, b = a ^ 1;
         HIPCHK(hipEventRecord(w.pass_ev[2 * pass], st));
@@ -2190,7 +2248,7 @@ static int collect_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
         sum.launches++;
         sum.trace_ms += pm;
         if (c.path_kernels) { if (pass == 0) sum.primary_ms += pm; else sum.bounce_ms += pm; }
-        if (c.ao || c.li || c.pv) sum.primary_ms += pm;
+        if (c.ao || c.li || c.pv || c.sh) sum.primary_ms += pm;
         if (s->verbose) fprintf(stderr, "[rtmi] stream %u batch@%llu pass %u: %u rays, trace %.3f ms, %.1f Mrays/s\n", t, (unsigned long long)p0, pass, h.count[pass], pm, h.count[pass] / (pm * 1e3));
     }
     if (c.ao) {  // the AO rays' walk: queue 1
@@ -2209,6 +2267,21 @@ static int collect_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
         sum.trace_ms += pm;
         sum.bounce_ms += pm;
         if (s->verbose) fprintf(stderr, "[rtmi] stream %u batch@%llu light: %u live rays, walk %.3f ms\n", t, (unsigned long long)p0, h.count[1], pm);
+    }
+    if (c.sh) {  // the shadow rays' walks, one per pass: their control block's rays and work counters, their times
+        Work& sw = s->shadow[t].walk;
+        DCtrl hs;
+        HIPCHK(hipMemcpyAsync(&hs, sw.ctrl.p, sizeof(DCtrl), hipMemcpyDeviceToHost, s->istream[t]));
+        HIPCHK(hipStreamSynchronize(s->istream[t]));
+        add_counters(sum.counters, ctrl_counters(hs));
+        for (uint32_t pass = 0; pass < c.maxdepth; pass++) {
+            float pm = 0.f;
+            HIPCHK(hipEventElapsedTime(&pm, sw.pass_ev[2 * pass], sw.pass_ev[2 * pass + 1]));
+            sum.launches++;
+            sum.trace_ms += pm;
+            sum.bounce_ms += pm;
+            if (s->verbose) fprintf(stderr, "[rtmi] stream %u batch@%llu pass %u shadow: %u live rays, walk %.3f ms\n", t, (unsigned long long)p0, pass, hs.count[pass + 1], pm);
+        }
     }
     if (c.pv && c.pv->per_path) {  // the one walk of the AO rays and every light's live rays: queue 1
         float pm = 0.f;
@@ -2238,12 +2311,15 @@ static int collect_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
 // pv != nullptr (no accum, no out_device; maxdepth = 1 likewise): a preview call (rtmi_render_preview_device).  Its batches run
 // a features call's primary pass once (with k_features when pv->fo asks), k_preview_rays, ONE any-hit walk of the AO rays and
 // all lights' live rays and k_preview_resolve, which writes pv's colour and planes.  A batch is sized in queue entries.
+// sh != nullptr (with accum): a shadowed path-trace (rtmi_render_shadowed_device).  A progressive pass in every respect, always
+// on the per-pass pipeline, whose batches run k_shadow_rays, the scene's any-hit walk of the pass's live shadow rays and
+// k_shade_shadowed (for k_shade_samples) in every bounce pass.
 // views > 0 (no accum): a batch of views (Samp::VIEWS, rtmi_render_views_device); vp is the stacked image (height = views *
 // the views' height) and s->hvcams holds the view table, uploaded here on hip_stream before the internal streams fork.
 static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile, uint32_t sample0,
                        uint32_t nsamples, float4* accum, void* out_device, void* hip_stream, rtmi_stats_t* stats,
                        const ListPass* lp = nullptr, uint32_t views = 0, const FeatOut* fo = nullptr, const AoCall* ao = nullptr,
-                       const LightCall* li = nullptr, const PreviewCall* pv = nullptr) {
+                       const LightCall* li = nullptr, const PreviewCall* pv = nullptr, const ShadowCall* sh = nullptr) {
     if (stats) memset(stats, 0, sizeof(*stats));
     if (tile->nrows == 0) return RTMI_OK;
     RTMI_GUARD_BEGIN
@@ -2265,7 +2341,7 @@ static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed
     }
     TileCall c;
     c.seed = seed; c.sample0 = sample0; c.spp = nsamples; c.maxdepth = vp->maxdepth; c.W = vp->width;
-    c.accum = accum; c.out = out; c.lp = lp; c.fo = fo; c.ao = ao; c.li = li; c.pv = pv; c.vt = ViewTab{nullptr, FastDiv{}};
+    c.accum = accum; c.out = out; c.lp = lp; c.fo = fo; c.ao = ao; c.li = li; c.pv = pv; c.sh = sh; c.vt = ViewTab{nullptr, FastDiv{}};
     c.mode = lp ? Samp::LIST : (accum || fo || ao || li || pv) ? Samp::PASS : views ? Samp::VIEWS : Samp::FRAME;
     c.counting = (s->options & RTMI_OPT_COUNTERS) != 0;
     rc = plan_tile(s, vp, tile, c);
@@ -2564,6 +2640,73 @@ int rtmi_render_light(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed,
     if (rc != RTMI_OK) return rc;
     if (d_sh) HIPCHK(hipMemcpy(shadow_host, d_sh, npix * sizeof(float), hipMemcpyDeviceToHost));
     if (d_ir) HIPCHK(hipMemcpy(irradiance_host, d_ir, npix * sizeof(float), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+// ---------------------------------------------------------------- shadowed path-trace (rtmi_render_shadowed*)
+// Checks of the shadowed entry points that come before any HIP call and before the scene is used (a CPU-only caller reaches
+// them): rtmi_render_samples_device's, then rtmi_render_light*'s on the light, then rays == 1.
+static int check_shadowed(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint32_t sample0, uint32_t nsamples, const rtmi_light_t* li,
+                          const void* accum, const void* out) {
+    const int rc = check_samples(s, vp, sample0, nsamples, accum, out);
+    if (rc != RTMI_OK) return rc;
+    if (!li) return fail(RTMI_ERR_INVALID, "shadowed: NULL argument (rtmi_light_t)");
+    if (li->rays == 0 || li->rays > 256) return fail(RTMI_ERR_INVALID, "shadowed: rays must be in [1, 256]");
+    if (li->flags & ~(uint32_t)RTMI_LIGHT_UNBOUNDED) return fail(RTMI_ERR_INVALID, "shadowed: unknown flags");
+    if (!(li->len2 >= 0.f) || std::isinf(li->len2)) return fail(RTMI_ERR_INVALID, "shadowed: len2 must be >= 0, finite and not NaN");
+    if (!std::isfinite(li->orig[0]) || !std::isfinite(li->orig[1]) || !std::isfinite(li->orig[2]))
+        return fail(RTMI_ERR_INVALID, "shadowed: orig must be finite");
+    if (!std::isfinite(li->bias)) return fail(RTMI_ERR_INVALID, "shadowed: bias must be finite");
+    if (li->rays != 1) return fail(RTMI_ERR_INVALID, "shadowed: rays must be 1 (the reference draws one shadow ray per hit)");
+    return RTMI_OK;
+}
+static int refuse_spheres_shadowed(const rtmi_scene_t* s) {
+    if (s->d.nspheres)
+        return fail(RTMI_ERR_UNSUPPORTED, "shadowed: the scene has analytic spheres (a build-defined primitive whose normal needs the hit point)");
+    return RTMI_OK;
+}
+
+int rtmi_render_shadowed_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile, uint32_t sample0,
+                                uint32_t nsamples, const rtmi_light_t* li, void* accum_device, void* out_device, void* hip_stream,
+                                rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    int rc = check_shadowed(s, vp, sample0, nsamples, li, accum_device, out_device);
+    if (rc != RTMI_OK) return rc;
+    if (!tile) return fail(RTMI_ERR_INVALID, "NULL argument (tile)");
+    if (tile->nrows == 0) return RTMI_OK;
+    rc = check_view(vp, tile);
+    if (rc != RTMI_OK) return rc;
+    rc = refuse_spheres_shadowed(s);
+    if (rc != RTMI_OK) return rc;
+    const ShadowCall call{*li};
+    return render_tile(s, vp, seed, tile, sample0, nsamples, (float4*)accum_device, out_device, hip_stream, stats, nullptr, 0, nullptr,
+                       nullptr, nullptr, nullptr, &call);
+}
+
+// Host variant: rtmi_render_samples' copies (accum in only when sample0 > 0, accum and out back).
+int rtmi_render_shadowed(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows, uint32_t sample0,
+                         uint32_t nsamples, const rtmi_light_t* li, float* accum_host, float* out_host, rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    int rc = check_shadowed(s, vp, sample0, nsamples, li, accum_host, out_host);
+    if (rc != RTMI_OK) return rc;
+    const uint64_t npix = (uint64_t)nrows * vp->width;
+    if (npix == 0) return RTMI_OK;
+    if ((uint64_t)row0 + nrows > vp->height) return fail(RTMI_ERR_INVALID, "row range outside the viewport");
+    const rtmi_tile_t tile{row0, nrows, nrows, 0u};
+    rc = check_view(vp, &tile);
+    if (rc != RTMI_OK) return rc;
+    rc = refuse_spheres_shadowed(s);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(s->acc.ensure(npix));
+    if (out_host) HIPCHK(s->tile.ensure(npix));
+    if (sample0 > 0) HIPCHK(hipMemcpy(s->acc.p, accum_host, npix * sizeof(float4), hipMemcpyHostToDevice));
+    const ShadowCall call{*li};
+    rc = render_tile(s, vp, seed, &tile, sample0, nsamples, s->acc.p, out_host ? (void*)s->tile.p : nullptr, nullptr, stats, nullptr, 0,
+                     nullptr, nullptr, nullptr, nullptr, &call);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(hipMemcpy(accum_host, s->acc.p, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    if (out_host) HIPCHK(hipMemcpy(out_host, s->tile.p, npix * sizeof(float4), hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
 

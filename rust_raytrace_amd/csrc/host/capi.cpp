@@ -345,6 +345,39 @@ int rth_caster_walk_light_device(rth_scene_t* s, uint32_t w, uint32_t h, const f
         if (stats) *stats = ctx.stats;
     });
 }
+int rth_caster_walk_shadowed(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp, uint64_t row0,
+                             uint64_t nrows, uint32_t sample0, uint32_t nsamples, const rtmi_light_t* light, float* accum_host,
+                             float* out_host, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!light) throw std::runtime_error("NULL rtmi_light_t");
+        if (light->rays != 1) throw std::runtime_error("shadowed: rays must be 1 (the reference draws one shadow ray per hit)");
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        s->scene.light = LightSource{make_vec(light->orig), light->len2};  // the reference's Scene.light; not uploaded, no touch()
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_rays_shadowed(v, s->scene, (size_t)row0, (size_t)nrows, sample0, nsamples, light->flags, light->bias,
+                                        reinterpret_cast<Color*>(accum_host), reinterpret_cast<Color*>(out_host), ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
+int rth_caster_walk_shadowed_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                                    const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, const rtmi_light_t* light,
+                                    void* accum_device, void* out_device, void* hip_stream, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!tile) throw std::runtime_error("NULL tile");
+        if (!light) throw std::runtime_error("NULL rtmi_light_t");
+        if (light->rays != 1) throw std::runtime_error("shadowed: rays must be 1 (the reference draws one shadow ray per hit)");
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        s->scene.light = LightSource{make_vec(light->orig), light->len2};
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_shadowed_device(v, s->scene, *tile, sample0, nsamples, light->flags, light->bias, accum_device, out_device,
+                                          hip_stream, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
 int rth_caster_walk_preview(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp, uint64_t row0,
                             uint64_t nrows, uint32_t sample0, uint32_t nsamples, const rtmi_preview_t* preview,
                             const rtmi_preview_out_t* out_host, rtmi_stats_t* stats, double* wall) {

@@ -847,6 +847,36 @@ void HipRayCaster::walk_light_device(const Viewport& v, const Scene& s, const rt
     progress.stats = st;
 }
 
+void HipRayCaster::walk_rays_shadowed(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
+                                      uint32_t flags, float bias, Color* accum, Color* out, ProgressCtx& progress) {
+    if (!s.light) throw std::runtime_error("walk_rays_shadowed: the scene has no light (Scene::light)");
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    const rtmi_light_t li = light_abi(*s.light, 1u, flags, bias);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_shadowed(h, &av, seed, (uint32_t)row0, (uint32_t)nrows, sample0, nsamples, &li,
+                                        reinterpret_cast<float*>(accum), reinterpret_cast<float*>(out), &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_shadowed: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
+void HipRayCaster::walk_shadowed_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
+                                        uint32_t flags, float bias, void* accum_device, void* out_device, void* hip_stream,
+                                        ProgressCtx& progress) {
+    if (!s.light) throw std::runtime_error("walk_shadowed_device: the scene has no light (Scene::light)");
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    const rtmi_light_t li = light_abi(*s.light, 1u, flags, bias);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_shadowed_device(h, &av, seed, &tile, sample0, nsamples, &li, accum_device, out_device, hip_stream, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_shadowed_device: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
 void HipRayCaster::walk_rays_preview(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
                                      const rtmi_preview_t& preview, const rtmi_preview_out_t& out, ProgressCtx& progress) {
     rtmi_scene_t* h = resident(s);

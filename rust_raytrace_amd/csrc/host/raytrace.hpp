@@ -12,6 +12,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <functional>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <tuple>
@@ -106,7 +107,8 @@ BoundingBox build_trivial_bounding_box(const std::vector<Triangle>& tris, const 
 
 // raytrace.rs:595-598: a box light, `orig` its corner and `len2` its edge (0: a point light).  The reference declares it and
 // spells its shadow ray out in a comment (_get_shadow_ray, :600-610) without running either; here it is the light of the
-// direct-light buffer (HipRayCaster::walk_rays_light, rtmi_render_light* in rtmi.h, which defines the shadow ray).
+// direct-light buffer (HipRayCaster::walk_rays_light, rtmi_render_light* in rtmi.h, which defines the shadow ray) and, as
+// Scene::light, of the shadowed path-trace (HipRayCaster::walk_rays_shadowed, rtmi_render_shadowed*).
 struct LightSource {
     Point orig;
     float len2;
@@ -135,6 +137,10 @@ struct Scene {
     std::vector<Triangle> tris;
     BoundingBox boxes;
     std::vector<Sphere> spheres;  // analytic spheres: a flat list tested against every ray after the box tree
+    // The reference's commented-out `light: LightSource` field.  walk_rays never looks at it (the reference's color_ray does not
+    // either: its shadow block is commented out); walk_rays_shadowed / walk_shadowed_device need it.  Not part of the uploaded
+    // scene: setting it needs no touch().
+    std::optional<LightSource> light;
     // debug_en: walk_rays also records sample 0's primary ray of every pixel into `debug` (the reference's debug_ctx, which
     // walk_rays fills through a &Scene: hence mutable).  Octree scenes only; walk_rays throws before rendering otherwise.
     bool debug_en = false;
@@ -250,6 +256,15 @@ public:
     void walk_light_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
                            const LightSource& light, uint32_t rays, uint32_t flags, float bias, void* shadow_device,
                            void* irradiance_device, void* hip_stream, ProgressCtx& progress);
+    // Path tracing with the reference's shadow rays switched on (rtmi_render_shadowed / rtmi_render_shadowed_device, which
+    // rtmi.h defines): walk_samples / walk_samples_device in every respect, with every surface hit of every bounce tested
+    // against s.light (one shadow ray per hit) and shown black where it is shadowed.  Throws when s.light is empty.
+    // flags: RTMI_LIGHT_UNBOUNDED or 0; bias: the smudge factor (the reference's 0.005).
+    void walk_rays_shadowed(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
+                            uint32_t flags, float bias, Color* accum, Color* out, ProgressCtx& progress);
+    void walk_shadowed_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
+                              uint32_t flags, float bias, void* accum_device, void* out_device, void* hip_stream,
+                              ProgressCtx& progress);
     // Shaded preview (rtmi_render_preview / rtmi_render_preview_device, which rtmi.h defines): albedo, AO and up to four
     // coloured box lights composed per sample from one primary pass; `out` names the colour image and the layers wanted.
     void walk_rays_preview(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,

@@ -802,6 +802,65 @@ class HipRayCaster:
                                                      C.byref(st), C.byref(wall)))
         return ProgressCtx(st.rays, wall.value, st.as_dict())
 
+    def _shadowed_args(self, v, sample0, nsamples, orig, len2, unbounded, bias):
+        k0, n = self._feature_samples(v, sample0, nsamples)
+        if orig is None:
+            raise ValueError("orig (the light's corner) is needed")
+        return k0, n, self.light_params(orig, len2, 1, unbounded, bias)
+
+    def walk_rays_shadowed(self, v, s, data=None, orig=None, len2=None, unbounded=False, bias=None, sample0=0, nsamples=None, accum=None):
+        """Path tracing of the whole frame with the reference's shadow rays switched on (rtmi_render_shadowed; include/rtmi.h
+        defines it): walk_rays' paths, with every surface hit of every bounce tested against one box light (corner `orig`,
+        edge `len2`; 0 = a point light; one shadow ray per hit) and shown black where it is shadowed.  Samples [sample0,
+        sample0 + nsamples) (default: all from sample0) of the frame's v.samples_per_pixel; accum ((H, W, 4) float32, None
+        allocates it) holds the running per-pixel sums as in walk_samples: read when sample0 > 0, always rewritten.  data
+        ((H, W, 4) float32, None allocates it) receives accum * (1 / (sample0 + nsamples)): the image once every sample is in.
+        unbounded: anything along a shadow ray shadows, even beyond the light.  Returns (data, ctx); ctx.accum is the sums."""
+        k0, n, a = self._shadowed_args(v, sample0, nsamples, orig, len2, unbounded, bias)
+        shape = (v.height, v.width, 4)
+        bufs = []
+        for name, x in (("data", data), ("accum", accum)):
+            if x is None:
+                x = np.zeros(shape, np.float32)
+            elif not isinstance(x, np.ndarray) or x.dtype != np.float32 or not x.flags.c_contiguous or x.size != v.height * v.width * 4:
+                raise ValueError(f"{name} must be a C-contiguous float32 array of height*width*4 elements")
+            bufs.append(x)
+        if np.shares_memory(bufs[0], bufs[1]):
+            raise ValueError("data and accum must not alias")
+        if k0 > 0 and accum is None:
+            raise ValueError("sample0 > 0 continues the sums of the earlier samples: pass their accum")
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_shadowed(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, 0, v.height, k0, n,
+                                                 C.byref(a), _p(bufs[1]), _p(bufs[0]), C.byref(st), C.byref(wall)))
+        ctx = ProgressCtx(st.rays, wall.value, st.as_dict())
+        ctx.accum = bufs[1]
+        return bufs[0], ctx
+
+    def walk_rays_shadowed_device(self, v, s, accum, out=None, tile=None, orig=None, len2=None, unbounded=False, bias=None, sample0=0,
+                                  nsamples=None, stream=None):
+        """The same on torch tensors on the scene's device (rtmi_render_shadowed_device) for a striped row set tile = (row0,
+        nrows, stripe_rows, stripe_step) (default: the whole frame): `accum` and `out` (may be None: no preview) are contiguous
+        float32 tensors of nrows * width * 4 elements that do not overlap, read and written by work enqueued on `stream` (a
+        torch stream, a raw HIP stream pointer or None).  Returns ctx."""
+        k0, n, a = self._shadowed_args(v, sample0, nsamples, orig, len2, unbounded, bias)
+        t = _ffi.Tile(*[int(x) for x in (tile if tile is not None else (0, v.height, v.height, 0))])
+        want = int(t.nrows) * int(v.width) * 4
+        for name, x in (("accum", accum), ("out", out)):
+            if (x is not None or name == "accum") and (not hasattr(x, "data_ptr") or not x.is_cuda or str(x.dtype) != "torch.float32"
+                                                       or not x.is_contiguous() or x.numel() != want):
+                raise ValueError(f"{name} must be a contiguous float32 tensor of {want} elements on the device")
+        if out is not None and abs(accum.data_ptr() - out.data_ptr()) < 4 * want:
+            raise ValueError("accum and out must not overlap")
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_shadowed_device(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, C.byref(t), k0, n,
+                                                        C.byref(a), C.c_void_p(accum.data_ptr()), C.c_void_p(out.data_ptr() if out is not None else 0),
+                                                        C.c_void_p(getattr(stream, "cuda_stream", stream) or 0), C.byref(st), C.byref(wall)))
+        return ProgressCtx(st.rays, wall.value, st.as_dict())
+
     PREVIEW_MAX_LIGHTS = _ffi.PREVIEW_MAX_LIGHTS
     _PREVIEW_OUTPUTS = ("color", "albedo", "normal", "ids", "ao", "shadow", "irradiance")  # rtmi_preview_out_t's order
 
