@@ -82,12 +82,14 @@ struct DScene {
     float root_half;
     uint32_t olevels;
     uint32_t noblocks;  // reference blocks in `oblocks`
+    // block cull records, 2 x uint4 per reference block (trace_oct.hpp, "Block cull"); null: the cull is off
+    const uint4* ocull;
 };
 #define RTMI_FN_WIDE 0x10000u
 
 #define RTMI_MAX_PASSES 32
 #define RTMI_MAX_STREAMS 4  // interleaved sub-tiles of one tile, each on its own internal stream
-#define RTMI_NDBG 26        // step statistics of the counting build (trace_oct.hpp: what each entry counts)
+#define RTMI_NDBG 31        // step statistics of the counting build (trace_oct.hpp: what each entry counts)
 struct DCtrl {
     uint32_t count[RTMI_MAX_PASSES + 1];  // rays queued for pass k
     uint32_t head[RTMI_MAX_PASSES + 1];   // work-fetch cursor of pass k
@@ -1036,7 +1038,7 @@ struct rtmi_scene {
     DevBuf<float4> tplane, tedge, mats, spheres;
     std::vector<float4> hmats;  // the triangles' surface table (host copy): sphere surfaces are appended to it
     std::vector<rtmi_triangle_t> htris;  // the records (host copy): the fast-mode BVH is rebuilt from them when corners arrive
-    DevBuf<uint4> fnodes, oblocks;
+    DevBuf<uint4> fnodes, oblocks, ocull;
     DevBuf<uint32_t> wlinks;
     std::vector<uint32_t> leaf_box;  // OctForm::leafbox: leaf ids of k_trace_record -> box index
     // rtmi_trace_records / rtmi_primary_records: per-ray counters, leaf-list offsets and leaf ids of the last call
@@ -1145,6 +1147,7 @@ struct rtmi_scene {
     bool verbose = false;
     int vote[4] = {3, 2, 3, 2};  // SELECT : LEAF vote weights of the walk, primary rays / bounce rays (experiments: RTMI_VOTE="a,b,c,d")
     int occl_from_hits = 0;      // rtmi_occluded* runs the closest-hit launch + k_occl_from_hits everywhere (RTMI_OCCLUDED_ANYHIT=0, for comparison)
+    int block_cull = 1;          // k_trace_oct skips reference blocks by their cull records (RTMI_BLOCK_CULL=0: off, no records)
     int packet_cull = 1;         // k_path_primary culls leaf triangles per pixel packet (RTMI_PACKET_CULL=0: off, for comparison)
     // k_path_primary traces the mirror reflections of its primary rays itself when a wave has at least this many
     // (RTMI_MIRROR_INPLACE=n; 0: off, everything above 64: never)
@@ -1373,6 +1376,54 @@ static void build_oct_form(const rtmi_box_t* boxes, uint64_t nboxes, const uint3
     if (!ok) { hfn.clear(); hob.clear(); hwl.clear(); f.leafbox.clear(); f.nwide = 0; }
 }
 
+// The block cull records of `nb` reference blocks (trace_oct.hpp, "Block cull").  hp: the plane records
+// (incenter.xyz, r2) (norm.xyz, material) of `ntris` triangles.  Boxes in double, rounded outward to f32 / int8.
+static void build_block_cull(const uint4* blocks, size_t nb, const float4* hp, uint64_t ntris, std::vector<uint4>& out) {
+    auto fb = [](float v) { uint32_t u; memcpy(&u, &v, 4); return u; };
+    auto down = [](double v) { float f = (float)v; return (double)f > v ? std::nextafterf(f, -INFINITY) : f; };
+    auto up = [](double v) { float f = (float)v; return (double)f < v ? std::nextafterf(f, INFINITY) : f; };
+    auto in_range = [](double v) { return std::isfinite(v) && v >= 1e-15 && v <= 1e15; };
+    const double K = 1e-5;
+    out.assign(2 * nb, make_uint4(0u, 0u, 0u, 0u));
+    for (size_t b = 0; b < nb; b++) {
+        const uint4 blk = blocks[b];
+        const uint32_t ids[4] = {blk.x, blk.y, blk.z, blk.w & 0x7FFFFFFFu};
+        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        int nlo[3] = {127, 127, 127}, nhi[3] = {-127, -127, -127};
+        uint32_t flags = (blk.w == 0u || (blk.w >> 31)) ? BC_END : 0u;
+        bool any = false;
+        for (int k = 0; k < 4; k++) {
+            if (ids[k] == 0u) continue;  // padding behind the list's end
+            if (ids[k] >= ntris) { flags |= BC_NEVER; continue; }
+            any = true;
+            const float4 p0 = hp[2 * (size_t)ids[k]], p1 = hp[2 * (size_t)ids[k] + 1];
+            const double c[3] = {p0.x, p0.y, p0.z}, n[3] = {p1.x, p1.y, p1.z};
+            const double c1 = (std::fabs(c[0]) + std::fabs(c[1])) + std::fabs(c[2]);
+            const double nn = std::sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+            if (!in_range(c1) || !in_range(nn) || !in_range((double)p0.w)) { flags |= BC_NEVER; continue; }
+            const double rho = std::sqrt((double)p0.w);
+            const double pad = rho * (1.0 + K) + K * (c1 + rho);
+            for (int a = 0; a < 3; a++) {
+                lo[a] = std::min(lo[a], c[a] - pad);
+                hi[a] = std::max(hi[a], c[a] + pad);
+                const double u = 127.0 * (n[a] / nn);
+                nlo[a] = std::min(nlo[a], std::max(-127, (int)std::floor(u - 1e-6)));
+                nhi[a] = std::max(nhi[a], std::min(127, (int)std::ceil(u + 1e-6)));
+            }
+        }
+        float flo[3], fhi[3];
+        for (int a = 0; a < 3; a++) {
+            // no real reference (or none in range): the empty box
+            flo[a] = any && !(flags & BC_NEVER) ? down(lo[a]) : FLT_MAX;
+            fhi[a] = any && !(flags & BC_NEVER) ? up(hi[a]) : -FLT_MAX;
+        }
+        auto b8 = [](int v) { return (uint32_t)(uint8_t)(int8_t)v; };
+        out[2 * b] = make_uint4(fb(flo[0]), fb(flo[1]), fb(flo[2]), fb(fhi[0]));
+        out[2 * b + 1] = make_uint4(fb(fhi[1]), fb(fhi[2]), b8(nlo[0]) | (b8(nlo[1]) << 8) | (b8(nlo[2]) << 16) | (b8(nhi[0]) << 24),
+                                    b8(nhi[1]) | (b8(nhi[2]) << 8) | (flags << 16));
+    }
+}
+
 // LDS of an octree-walk launch: the counting build keeps 2 more memo words per lane (the list's plane and edge tests)
 // and every launch room for the LDS header of k_path_primary (trace_oct.hpp, PrimHdr: its packet and pass-2 queue)
 static_assert(sizeof(PrimHdr) % 16 == 0 && sizeof(PrimHdr) <= 96, "header slot in LDS");
@@ -1476,6 +1527,7 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
     s->tune.slow_path_off = (uint32_t)std::min<size_t>(env_size("RTMI_SLOW_PATH_OFF", 0), 1);
     s->verbose = getenv("RTMI_VERBOSE") != nullptr;
     if (const char* v = getenv("RTMI_PACKET_CULL")) s->packet_cull = strcmp(v, "0") != 0;  // (env_size treats 0 as unset)
+    if (const char* v = getenv("RTMI_BLOCK_CULL")) s->block_cull = strcmp(v, "0") != 0;
     if (const char* v = getenv("RTMI_OCCLUDED_ANYHIT")) s->occl_from_hits = strcmp(v, "0") == 0;
     if (const char* v = getenv("RTMI_DENOISE_LDS_STEP")) s->dn_lds_max_step = std::min<uint32_t>((uint32_t)strtoul(v, nullptr, 10), DN_LDS_MAX_STEP);
     if (const char* v = getenv("RTMI_DENOISE_VAR_LDS_STEP")) s->dnv_lds_max_step = std::min<uint32_t>((uint32_t)strtoul(v, nullptr, 10), DN_LDS_MAX_STEP);
@@ -1515,6 +1567,13 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
         e = up(s->oblocks, hobp);
     }
     if (e == hipSuccess && s->octree) e = up(s->wlinks, hwl);
+    const bool bcull = s->octree && s->block_cull && hob.size() < (1ull << 27);  // (32-bit byte offsets, 32 B per record)
+    if (e == hipSuccess && bcull) {
+        std::vector<uint4> hoc;
+        build_block_cull(hob.data(), hob.size(), hp.data(), ntris, hoc);
+        hoc.resize(hoc.size() + 2, make_uint4(0u, 0u, 0u, 0u));  // the LEAF step reads a block's record and the next one's
+        e = up(s->ocull, hoc);
+    }
     for (int k = 0; k < RTMI_MAX_STREAMS && e == hipSuccess; k++) {
         e = s->w[k].ctrl.ensure(1);
         // zeroed once here (each batch zeroes its own): rtmi_debug_counters_n also reads the blocks of streams no render used
@@ -1529,7 +1588,7 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
     if (e != hipSuccess) return fail(hip_code(e), std::string("scene upload: ") + hipGetErrorString(e));
     s->d = DScene{s->nodes.p, s->refs.p, s->tplane.p, s->tedge.p, s->mats.p,
                   (uint32_t)nboxes, (uint32_t)ntris, (uint32_t)matmap.size(), levels,
-                  s->octree ? s->fnodes.p : nullptr, s->octree ? s->oblocks.p : nullptr, s->octree ? s->wlinks.p : nullptr, nullptr, 0u, boxes[0].len2, max_inner_depth + 1, (uint32_t)hob.size()};
+                  s->octree ? s->fnodes.p : nullptr, s->octree ? s->oblocks.p : nullptr, s->octree ? s->wlinks.p : nullptr, nullptr, 0u, boxes[0].len2, max_inner_depth + 1, (uint32_t)hob.size(), bcull ? s->ocull.p : nullptr};
     s->hmats = hm;
     s->leaf_box = std::move(of.leafbox);
     if (s->octree) {
@@ -1557,7 +1616,7 @@ int rtmi_scene_destroy(rtmi_scene_t* s) {
     if (!s) return RTMI_OK;
     (void)hipSetDevice(s->device);
     s->nodes.release(); s->refs.release(); s->tplane.release(); s->tedge.release(); s->mats.release();
-    s->fnodes.release(); s->oblocks.release(); s->wlinks.release(); s->bnodes.release(); s->bleaves.release(); s->spheres.release();
+    s->fnodes.release(); s->oblocks.release(); s->ocull.release(); s->wlinks.release(); s->bnodes.release(); s->bleaves.release(); s->spheres.release();
     for (int k = 0; k < RTMI_MAX_STREAMS; k++) {
         s->w[k].release();
         if (s->istream[k]) (void)hipStreamDestroy(s->istream[k]);
@@ -3890,6 +3949,43 @@ int rtmi_debug_packet_cull(const float* rays, uint32_t n, const float* recs, uin
     *on = ok && packet_finish(p, so, sd) ? 1 : 0;
     for (uint64_t j = 0; j < m; j++) cull[j] = *on && packet_culls(p, f4(recs + 8 * j), f4(recs + 8 * j + 4)) ? 1 : 0;
     return RTMI_OK;
+}
+
+// Development aid (not in rtmi.h): the block cull of k_trace_oct on the host with the kernel's own functions (trace_oct.hpp).
+// recs: m plane records (incenter.xyz, r2, norm.xyz, material: 8 floats each; record 0 is the sentinel); blocks: nb blocks of
+// 4 indices into recs in the form of oblocks (0: padding; a 4th word of 0 or with bit 31 set ends a list); rays: n rays
+// (o.xyzw, d.xyzw).  records (8 words per block, or NULL) <- the cull records; rayok[i] (or NULL) <- block_cull_ray of ray i;
+// out[b n + i] (or NULL) <- bit 0: the half-line misses the box, bit 1: the sign certificate holds, bit 2: block b is
+// culled for ray i.  Needs no device.
+int rtmi_debug_block_cull(const float* recs, uint64_t m, const uint32_t* blocks, uint64_t nb, const float* rays, uint64_t n,
+                          uint32_t* records, uint8_t* rayok, uint8_t* out) {
+    if (!recs || m < 1 || (nb > 0 && !blocks) || (n > 0 && !rays)) return fail(RTMI_ERR_INVALID, "NULL argument");
+    RTMI_GUARD_BEGIN
+    std::vector<uint4> hoc, hb(nb);
+    std::vector<float4> hp(2 * m);
+    if (nb) memcpy(hb.data(), blocks, nb * sizeof(uint4));
+    memcpy(hp.data(), recs, m * 8 * sizeof(float));
+    build_block_cull(hb.data(), nb, hp.data(), m, hoc);
+    if (records && nb) memcpy(records, hoc.data(), hoc.size() * sizeof(uint4));
+    std::vector<uint8_t> ok(n);
+    std::vector<float> inv(3 * n);
+    for (uint64_t i = 0; i < n; i++) {
+        const float* v = rays + 8 * i;
+        ok[i] = block_cull_ray(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7])) ? 1 : 0;
+        for (int k = 0; k < 3; k++) inv[3 * i + k] = 1.f / v[4 + k];  // make_rayk
+        if (rayok) rayok[i] = ok[i];
+    }
+    if (out)
+        for (uint64_t b = 0; b < nb; b++)
+            for (uint64_t i = 0; i < n; i++) {
+                const float* v = rays + 8 * i;
+                const uint4 c0 = hoc[2 * b], c1 = hoc[2 * b + 1];
+                const uint32_t parts = block_cull_parts(c0, c1, v[0], v[1], v[2], v[4], v[5], v[6], inv[3 * i], inv[3 * i + 1], inv[3 * i + 2]);
+                const bool cut = ok[i] && block_culls(c0, c1, v[0], v[1], v[2], v[4], v[5], v[6], inv[3 * i], inv[3 * i + 1], inv[3 * i + 2]);
+                out[b * n + i] = (uint8_t)(parts | (cut ? 4u : 0u));
+            }
+    return RTMI_OK;
+    RTMI_GUARD_END
 }
 
 int rtmi_make_triangles(int device, const float* corners9_host, uint64_t n, const rtmi_triangle_t* proto, rtmi_triangle_t* out_host) {

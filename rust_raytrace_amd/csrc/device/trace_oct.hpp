@@ -53,6 +53,8 @@
 //             (the sentinel triangle is never in a tree, raytrace.rs:791) or after a full block whose 4th
 //             index has bit 31 set.  Each DISTINCT list is stored once (leaves with the same list share its blocks), so
 //             a list's first block is its identity -- what the leaf memo of oct_walk compares.
+//   ocull   : 2 x uint4 (32 B) per reference block, same index: a box around the block's triangles and one around their
+//             normals, by which k_trace_oct rejects the whole block for a ray ("Block cull" below); null: no block cull.
 #pragma once
 
 namespace rtmi {
@@ -225,6 +227,66 @@ __host__ __device__ inline bool packet_culls(const Packet& p, float4 p0, float4 
     return (c1 <= 1e15f) & (nn <= 1e15f) & (fabsf(den0) > X + X) & (x2 > (y * y) * (1.f + PK_K));
 }
 
+// ---- Block cull (W_TRACE, DESIGN.md 4.1 "Block cull"; rtmi_debug_block_cull runs the same functions on the host).
+// Bounce rays share nothing, so their bound is static: rtmi_scene_create stores one 32-B record per reference block (DScene::
+// ocull, the block's index), two uint4:
+//   c0 = (lo.x, lo.y, lo.z, hi.x)   c1 = (hi.y, hi.z, nlo.xyz | nhi.x << 24, nhi.y | nhi.z << 8 | flags << 16)
+// [lo, hi]: the box of the incenter spheres of the block's real references, each grown by rho K + K (|c|_1 + rho), rounded
+// outward; [nlo, nhi]: the box of their unit normals in units of 1/127 (int8), rounded outward.  block_culls() proves that
+// the exact plane test rejects all of them for one ray; a lane then skips the block at the cost of two loads.  Only IEEE
+// + - * /, min and max.
+#define BC_END 1u    // this block ends its list (oblocks: `blk.w == 0 || blk.w >> 31`)
+#define BC_NEVER 2u  // a record of the block is outside the ranges of the proof: never culled
+#define BC_K 1e-5f
+// A ray the cull may be used for: lane 3 zero, |o|_1 <= 1e15, every direction component nonzero with
+// 1e-10 <= max |d_k| <= 1e10 and min |d_k| >= 2^-40 max |d_k| (so every 1 / d_k is finite and the t of a reference whose
+// den the certificate bounds is < 1e30).  A NaN anywhere gives false.
+__host__ __device__ inline bool block_cull_ray(float4 o, float4 d) {
+    const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
+    const float dmax = fmaxf(fmaxf(ax, ay), az), dmin = fminf(fminf(ax, ay), az);
+    const float o1 = (fabsf(o.x) + fabsf(o.y)) + fabsf(o.z);
+    // (fmaxf / fminf skip a NaN operand: each component is compared on its own)
+    return (o.w == 0.f) & (d.w == 0.f) & (o1 <= 1e15f) & (ax > 0.f) & (ay > 0.f) & (az > 0.f) & (ax <= 1e10f) & (ay <= 1e10f) &
+           (az <= 1e10f) & (dmax >= 1e-10f) & (dmin >= 0x1p-40f * dmax);
+}
+// Bit 0: (b) the half-line t >= 0 misses the box; bit 1: (a) no norm . dir of the block can be zero.  For a ray that
+// block_cull_ray() accepts (ix, iy, iz = 1 / d as the walk keeps them).
+__host__ __device__ inline uint32_t block_cull_parts(uint4 c0, uint4 c1, float ox, float oy, float oz, float dx, float dy, float dz,
+                                                     float ix, float iy, float iz) {
+    auto f = [](uint32_t u) {
+#ifdef __HIP_DEVICE_COMPILE__
+        return __uint_as_float(u);
+#else
+        float v; memcpy(&v, &u, 4); return v;
+#endif
+    };
+    auto s8 = [](uint32_t w, int sh) { return (float)((int32_t)(w << (24 - sh)) >> 24); };
+    // (a) sign certificate over the normal box, in units of 1/127: L <= 127 u . d <= H for every unit normal u of the block
+    const float d1 = (fabsf(dx) + fabsf(dy)) + fabsf(dz);
+    const float ax0 = s8(c1.z, 0) * dx, ax1 = s8(c1.z, 24) * dx;
+    const float ay0 = s8(c1.z, 8) * dy, ay1 = s8(c1.w, 0) * dy;
+    const float az0 = s8(c1.z, 16) * dz, az1 = s8(c1.w, 8) * dz;
+    const float L = (fminf(ax0, ax1) + fminf(ay0, ay1)) + fminf(az0, az1);
+    const float H = (fmaxf(ax0, ax1) + fmaxf(ay0, ay1)) + fmaxf(az0, az1);
+    const float m = 0.127f * d1;  // 1e-3 |d|_1 in the same units
+    const bool sign = (L > m) | (H < -m);
+    // (b) slab test of the box grown by K |o|_1
+    const float e = BC_K * ((fabsf(ox) + fabsf(oy)) + fabsf(oz));
+    const float x0 = ((f(c0.x) - e) - ox) * ix, x1 = ((f(c0.w) + e) - ox) * ix;
+    const float y0 = ((f(c0.y) - e) - oy) * iy, y1 = ((f(c1.x) + e) - oy) * iy;
+    const float z0 = ((f(c0.z) - e) - oz) * iz, z1 = ((f(c1.y) + e) - oz) * iz;
+    // a NaN end (inf - inf, 0 * inf) must not be skipped by min / max: it turns the test off
+    const bool num = (x0 == x0) & (x1 == x1) & (y0 == y0) & (y1 == y1) & (z0 == z0) & (z1 == z1);
+    const float tn = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fminf(z0, z1));
+    const float tf = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fmaxf(z0, z1));
+    const bool miss = num & ((tf < 0.f) | (tn - tf > BC_K * (fabsf(tn) + fabsf(tf))));
+    return (miss ? 1u : 0u) | (sign ? 2u : 0u);
+}
+__host__ __device__ inline bool block_culls(uint4 c0, uint4 c1, float ox, float oy, float oz, float dx, float dy, float dz, float ix,
+                                            float iy, float iz) {
+    return (block_cull_parts(c0, c1, ox, oy, oz, dx, dy, dz, ix, iy, iz) == 3u) & !((c1.w >> 16) & BC_NEVER);
+}
+
 // S: the batch's sampling mode (W_PRIMARY / W_SLOW; Samp::LIST takes the batch's pixels from `list`, path_pixel, shade.hpp;
 // Samp::VIEWS each pixel's camera and seed from `vt`, pixel_key)
 template <bool COUNT, bool FAST, int MODE, Samp S = Samp::FRAME>
@@ -259,6 +321,9 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     // predicate culls, violations (a culled reference whose exact test passed: must stay 0)
     // dbg[21..23] (W_PRIMARY): primary rays whose path goes on through a Reflective hit (and not to the slow path), those
     // of them traced in place, exchange steps with >= 32 such lanes (low 32 bits) | with 64 such lanes (high 32 bits)
+    // dbg[26..30] (W_TRACE, block cull): blocks seen by lanes with a qualifying ray, blocks whose box the half-line misses,
+    // blocks culled, culled blocks that end their list, violations (a culled block with a reference whose exact test
+    // passed: must stay 0)
     // dbg[24..25] (W_PRIMARY): leaf visits whose first LEAF step is a packet step (the whole-list cull starts at the list's
     // first block), whole-list culls (= the LEAF steps that the fast build spends on packet steps)
     unsigned long long dbg[RTMI_NDBG] = {};
@@ -321,6 +386,8 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     // against *pkl
     enum : uint32_t { PK_OFF = 0, PK_NEW = 1, PK_ON = 2 };
     uint32_t pk = PK_OFF;
+    // W_TRACE (wave-uniform, a scalar pair): the lanes whose ray block_cull_ray() accepts, updated where lanes take rays
+    unsigned long long bcm = 0ull;
     auto take_leaf = [&](float t, uint32_t tf) {  // a finished leaf's hit into the frame and the running best
         if (!(fw & O_HAS) || t < ft) ft = t;
         fw |= O_HAS;
@@ -454,6 +521,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                     if (base < hi) break;
                     if (++tries == nranges) { exhausted = true; break; }
                 }
+                bool took = false;  // W_TRACE: this lane takes a queued ray here
                 if (!exhausted && mode == M_IDLE) {
                     const uint32_t i = base + (uint32_t)__popcll(m_want & lt_mask);
                     if (i < hi) {
@@ -479,6 +547,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                             ghave = false; gt = 0.f; gtf = 0;
                             if (MEMO) memo[0] = 0xFFFFFFFFu;  // no block index (< 2^28)
                             mode = M_SELECT;
+                            took = true;
                             if constexpr (MODE == W_OCCL) tmx = oc.tmax ? oc.tmax[i] : __uint_as_float(inf_bits);
                             if constexpr (MODE == W_RECORD) {  // this ray's counters start here; its leaf list at lfirst[i]
 #pragma unroll
@@ -486,6 +555,12 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                                 lcur = rec.lids ? rec.lfirst[i] : 0ull;
                             }
                         }
+                    }
+                }
+                if constexpr (MODE == W_TRACE) {
+                    if (sc.ocull) {
+                        const bool cb = took && block_cull_ray(make_float4(r.ox, r.oy, r.oz, r.ow), make_float4(r.dx, r.dy, r.dz, r.dw));
+                        bcm = (bcm & ~__ballot(took)) | __ballot(cb);
                     }
                 }
             }
@@ -785,13 +860,49 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                 const bool real = id != 0u;
                 if (COUNT) cnt[1] += real ? 1u : 0u;
                 const bool c = real & !(t < 0.f) & !(l2 > a0.w);
-                if (COUNT && c && culled) dbg[20]++;  // the packet predicate was wrong: must never happen
+                if (COUNT && c && culled) dbg[MODE == W_TRACE ? 30 : 20]++;  // the packet (block) predicate was wrong: must never happen
                 if (c & (q.tri != 0u)) resolve(q);  // second candidate of this lane in one block: rare
                 q.tri = c ? id : q.tri;
                 q.t = c ? t : q.t;
                 q.ix = c ? ix : q.ix; q.iy = c ? iy : q.iy; q.iz = c ? iz : q.iz;
                 q.den = c ? den : q.den;
             };
+            // ---- block cull (W_TRACE, DESIGN.md 4.1 "Block cull"): a lane whose ray qualifies reads the cull record of its
+            // block first and skips the block when block_culls() rejects its references, up to 2 blocks per step (the sweep
+            // of the count is in DESIGN.md).  A culled block that ends its list finishes the leaf like the full step does
+            // (lhave of earlier blocks is kept, the memo entry is written).  The counting build evaluates the predicate for
+            // the block of the full step and still tests every reference.
+            bool bcut = false;  // COUNT: the predicate culls this lane's block
+            if constexpr (MODE == W_TRACE) {
+                if (sc.ocull) {
+                    const bool cl = (mode == M_LEAF) & (((bcm >> lane) & 1ull) != 0ull);
+                    if (COUNT) {
+                        if (cl) {
+                            const uint4 c0 = ld_off32(sc.ocull, lblock << 5), c1 = ld_off32(sc.ocull, (lblock << 5) + 16u);
+                            const uint32_t parts = block_cull_parts(c0, c1, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, r.ix, r.iy, r.iz);
+                            bcut = block_culls(c0, c1, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, r.ix, r.iy, r.iz);
+                            dbg[26]++; dbg[27] += parts & 1u; dbg[28] += bcut ? 1u : 0u;
+                            dbg[29] += (bcut && ((c1.w >> 16) & BC_END)) ? 1u : 0u;
+                        }
+                    } else {
+                        // this block's record and the next one's in one round trip: the lane skips 0, 1 or 2 blocks (the
+                        // second record only counts when the first block is culled and the list goes on; behind the
+                        // array's last record lies a zero one)
+                        bool bfin = false;
+                        if (cl) {
+                            const uint4 c0 = ld_off32(sc.ocull, lblock << 5), c1 = ld_off32(sc.ocull, (lblock << 5) + 16u);
+                            const uint4 e0 = ld_off32(sc.ocull, (lblock << 5) + 32u), e1 = ld_off32(sc.ocull, (lblock << 5) + 48u);
+                            const bool cutA = block_culls(c0, c1, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, r.ix, r.iy, r.iz);
+                            const bool cutB = block_culls(e0, e1, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, r.ix, r.iy, r.iz);
+                            const bool endA = ((c1.w >> 16) & BC_END) != 0u, endB = ((e1.w >> 16) & BC_END) != 0u;
+                            const bool goA = cutA & !endA, goB = goA & cutB & !endB;
+                            bfin = (cutA & endA) | (goA & cutB & endB);
+                            lblock += (goA ? 1u : 0u) + (goB ? 1u : 0u);
+                        }
+                        if (bfin) finish_leaf();
+                    }
+                }
+            }
             bool lm = mode == M_LEAF;  // this lane runs the full LEAF step below
             const uint32_t* const oref = reinterpret_cast<const uint32_t*>(sc.oblocks);  // the references one word at a time
             bool fin = false;          // W_PRIMARY: this lane's list ended in this step
@@ -874,7 +985,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                 if (more) lblock++;
                 Cand q{0u, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int k = 0; k < 4; k++) plane(q, ids[k], p0[k], p1[k], (cullm >> k) & 1u);
+                for (int k = 0; k < 4; k++) plane(q, ids[k], p0[k], p1[k], MODE == W_TRACE ? bcut : (bool)((cullm >> k) & 1u));
                 if (q.tri != 0u) resolve(q);
                 // (W_PRIMARY: one call of finish_leaf after both steps; the other modes keep it here, their code unchanged)
                 if constexpr (MODE == W_OCCL) {  // the any-hit exit, mid-list or at its end

@@ -19,14 +19,15 @@ print(ctx.stats)
 # the resident scene handle lives inside the C++ caster; fetch the debug counters through a tiny helper
 lib = _ffi.lib()
 lib.rth_debug_counters_n.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-out = (C.c_ulonglong * 26)()
-lib.rth_debug_counters_n(scene.h, out, 26)
+out = (C.c_ulonglong * 31)()
+lib.rth_debug_counters_n(scene.h, out, 31)
 d = list(out)
 names = ["S steps", "S lanes", "L steps", "L lanes", "refills", "refill lanes", "edge blocks", "edge lanes", "S cycles", "L cycles", "refill cycles", "wave cycles",
          "leaf visits", "memo hits", "planes skipped", "edges skipped",
          "packet L steps", "primary L steps", "packet refs", "refs culled", "violations",
          "mirror rays", "mirror in place", "mirror steps",
-         "packet visits", "list culls"]
+         "packet visits", "list culls",
+         "cull blocks", "box missed", "blocks culled", "lists culled", "cull violations"]
 for n, v in zip(names, d):
     print(f"{n:14s} {v}")
 rays = ctx.stats["rays"]
@@ -53,3 +54,9 @@ if d[25]:
     # an estimate: the counting build still steps block by block, so its lanes may line up differently from the fast build's
     print(f"estimated primary LEAF steps of the fast build: {d[17] - d[16] + d[25]} (counting build: {d[17]}; whole-list culls "
           f"replacing its {d[16]} packet block steps)")
+# dbg[26..30]: the block cull of k_trace_oct (bounce passes; RTMI_BLOCK_CULL=0: all 0).  The counting build evaluates the
+# predicate for the block of every full LEAF step of a lane whose ray qualifies and still tests every reference.
+print(f"block cull (k_trace_oct, RTMI_BLOCK_CULL={os.environ.get('RTMI_BLOCK_CULL', 'default')}): {d[26]} blocks seen by lanes with a "
+      f"qualifying ray ({d[26] / max(d[3], 1):.3f} of all LEAF lane-steps); box missed by the half-line {d[27]} "
+      f"({d[27] / max(d[26], 1):.3f}); culled {d[28]} ({d[28] / max(d[26], 1):.3f}); lists ended by a culled block {d[29]}; "
+      f"violations {d[30]} (must be 0)")
