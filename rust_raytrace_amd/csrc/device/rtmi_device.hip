@@ -22,6 +22,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <array>
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -82,14 +83,24 @@ struct DScene {
     float root_half;
     uint32_t olevels;
     uint32_t noblocks;  // reference blocks in `oblocks`
-    // block cull records, 2 x uint4 per reference block (trace_oct.hpp, "Block cull"); null: the cull is off
+    // packed block cull records, one uint4 per reference block (trace_oct.hpp, "Block cull"); null: the cull is off
     const uint4* ocull;
+    // the sign certificate's direction table (trace_oct.hpp, ray_sign_certified); null exactly when ocull is
+    const uint32_t* cert;
 };
 #define RTMI_FN_WIDE 0x10000u
+// What build_ray_cert made: cells per face edge, distinct normals, list entries, the longest list, table bytes, seconds
+struct CertStats {
+    uint32_t g, normals;
+    uint64_t entries;
+    uint32_t longest;
+    uint64_t bytes;
+    double seconds;
+};
 
 #define RTMI_MAX_PASSES 32
 #define RTMI_MAX_STREAMS 4  // interleaved sub-tiles of one tile, each on its own internal stream
-#define RTMI_NDBG 31        // step statistics of the counting build (trace_oct.hpp: what each entry counts)
+#define RTMI_NDBG 33        // step statistics of the counting build (trace_oct.hpp: what each entry counts)
 struct DCtrl {
     uint32_t count[RTMI_MAX_PASSES + 1];  // rays queued for pass k
     uint32_t head[RTMI_MAX_PASSES + 1];   // work-fetch cursor of pass k
@@ -1039,7 +1050,7 @@ struct rtmi_scene {
     std::vector<float4> hmats;  // the triangles' surface table (host copy): sphere surfaces are appended to it
     std::vector<rtmi_triangle_t> htris;  // the records (host copy): the fast-mode BVH is rebuilt from them when corners arrive
     DevBuf<uint4> fnodes, oblocks, ocull;
-    DevBuf<uint32_t> wlinks;
+    DevBuf<uint32_t> wlinks, cert;
     std::vector<uint32_t> leaf_box;  // OctForm::leafbox: leaf ids of k_trace_record -> box index
     // rtmi_trace_records / rtmi_primary_records: per-ray counters, leaf-list offsets and leaf ids of the last call
     DevBuf<uint32_t> rec_cnt, rec_ids;
@@ -1148,6 +1159,8 @@ struct rtmi_scene {
     int vote[4] = {3, 2, 3, 2};  // SELECT : LEAF vote weights of the walk, primary rays / bounce rays (experiments: RTMI_VOTE="a,b,c,d")
     int occl_from_hits = 0;      // rtmi_occluded* runs the closest-hit launch + k_occl_from_hits everywhere (RTMI_OCCLUDED_ANYHIT=0, for comparison)
     int block_cull = 1;          // k_trace_oct skips reference blocks by their cull records (RTMI_BLOCK_CULL=0: off, no records)
+    int block_cull_n = 4;        // cull records a LEAF step of k_trace_oct reads, 2..4 (experiments: RTMI_BLOCK_CULL_N)
+    CertStats cert_stats{};      // the sign certificate's table (rtmi_debug_cert_stats)
     int packet_cull = 1;         // k_path_primary culls leaf triangles per pixel packet (RTMI_PACKET_CULL=0: off, for comparison)
     // k_path_primary traces the mirror reflections of its primary rays itself when a wave has at least this many
     // (RTMI_MIRROR_INPLACE=n; 0: off, everything above 64: never)
@@ -1424,6 +1437,111 @@ static void build_block_cull(const uint4* blocks, size_t nb, const float4* hp, u
     }
 }
 
+// The packed 16-B records (trace_oct.hpp, "Packed cull record") from the 32-B ones: bf16 ends, lo toward -inf, hi toward +inf
+static void pack_block_cull(const std::vector<uint4>& recs, std::vector<uint4>& out) {
+    auto down = [](uint32_t u) -> uint32_t {  // bf16 <= the f32 with bits u
+        if (!(u >> 31)) return u >> 16;
+        return (u & 0xFFFFu) ? (u >> 16) + 1u : u >> 16;  // negative: the magnitude grows (up to -inf)
+    };
+    auto up = [](uint32_t u) -> uint32_t {  // bf16 >= the f32 with bits u
+        if (u >> 31) return u >> 16;
+        return (u & 0xFFFFu) ? (u >> 16) + 1u : u >> 16;
+    };
+    const size_t nb = recs.size() / 2;
+    out.assign(nb, make_uint4(0u, 0u, 0u, 0u));
+    for (size_t b = 0; b < nb; b++) {
+        const uint4 c0 = recs[2 * b], c1 = recs[2 * b + 1];
+        const uint32_t flags = c1.w >> 16;
+        uint32_t lo[3] = {down(c0.x), down(c0.y), down(c0.z)}, hi[3] = {up(c0.w), up(c1.x), up(c1.y)};
+        if (flags & BC_NEVER)
+            for (int a = 0; a < 3; a++) { lo[a] = 0xFF80u; hi[a] = 0x7F80u; }  // [-inf, +inf]: no half-line misses it
+        out[b] = make_uint4(lo[0] | (lo[1] << 16), lo[2] | (hi[0] << 16), hi[1] | (hi[2] << 16), flags);
+    }
+}
+
+// The direction table of the sign certificate (trace_oct.hpp, ray_sign_certified).  hp: the plane records of
+// `ntris` triangles.  The distinct normals (bitwise; those with |n| outside [1e-15, 1e15] make their block never-cull and are
+// left out) are binned by the cell of d / d_major = (1, a, b): cell (face, i, j) covers a in [-1 + 2 i / G, -1 + 2 (i + 1) / G]
+// and b likewise, both grown by CELL_PAD (the kernel finds the cell in f32: its a, b and the product with G / 2 are off by
+// less than 1e-6).  A unit normal u is listed when |u_m + u_a a + u_b b| <= 3.001 tau somewhere in the grown cell -- |d|_1 <=
+// 3.001 there --, evaluated row by row in double.  False: more than `max_normals` distinct normals, or more than 2^32 list entries.
+static bool build_ray_cert(const float4* hp, uint64_t ntris, uint32_t G, size_t max_normals, std::vector<uint32_t>& out, CertStats& st) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const double CELL_PAD = 1e-5, T = 3.001 * CERT_TAU;
+    struct Key { uint32_t x, y, z; bool operator<(const Key& o) const { return std::tie(x, y, z) < std::tie(o.x, o.y, o.z); } };
+    std::map<Key, uint32_t> seen;
+    std::vector<float4> nrm;
+    for (uint64_t i = 1; i < ntris; i++) {
+        const float4 p1 = hp[2 * i + 1];
+        const double nn = std::sqrt(((double)p1.x * p1.x + (double)p1.y * p1.y) + (double)p1.z * p1.z);
+        if (!(std::isfinite(nn) && nn >= 1e-15 && nn <= 1e15)) continue;
+        Key k;
+        memcpy(&k.x, &p1.x, 4); memcpy(&k.y, &p1.y, 4); memcpy(&k.z, &p1.z, 4);
+        if (seen.emplace(k, (uint32_t)nrm.size()).second) nrm.push_back(make_float4(p1.x, p1.y, p1.z, (fabsf(p1.x) + fabsf(p1.y)) + fabsf(p1.z)));
+    }
+    st = CertStats{0u, (uint32_t)nrm.size(), 0u, 0u, 0u, 0.0};
+    if (nrm.size() > max_normals) return false;
+    const size_t ncell = (size_t)3 * G * G;
+    std::vector<uint32_t> cnt(ncell + 1, 0u);
+    // the columns [j0, j1] of row i on `face` that list normal u (j0 > j1: none)
+    auto row = [&](const double* u, int face, uint32_t i, int& j0, int& j1) {
+        const double um = u[face], ua = u[(face + 1) % 3], ub = u[(face + 2) % 3];
+        const double a0 = -1.0 + 2.0 * i / G - CELL_PAD, a1 = -1.0 + 2.0 * (i + 1) / G + CELL_PAD;
+        const double p0 = std::min(ua * a0, ua * a1), p1 = std::max(ua * a0, ua * a1);
+        const double q0 = -T - um - p1, q1 = T - um - p0;  // u_b b must lie in [q0, q1]
+        j0 = 0; j1 = (int)G - 1;
+        if (ub == 0.0) { if (!(q0 <= 0.0 && 0.0 <= q1)) j1 = -1; return; }
+        double b0 = std::min(q0 / ub, q1 / ub), b1 = std::max(q0 / ub, q1 / ub);
+        if (b1 < -1.0 - CELL_PAD || b0 > 1.0 + CELL_PAD) { j1 = -1; return; }
+        b0 = std::max(b0, -2.0); b1 = std::min(b1, 2.0);
+        // (2 CELL_PAD: the cell's own growth and the roundings here, which are below 1e-13)
+        j0 = std::max(0, (int)std::floor((b0 - 2.0 * CELL_PAD + 1.0) * 0.5 * G));
+        j1 = std::min((int)G - 1, (int)std::floor((b1 + 2.0 * CELL_PAD + 1.0) * 0.5 * G));
+    };
+    std::vector<std::array<double, 3>> un(nrm.size());
+    for (size_t k = 0; k < nrm.size(); k++) {
+        const double x = nrm[k].x, y = nrm[k].y, z = nrm[k].z, nn = std::sqrt((x * x + y * y) + z * z);
+        un[k] = {x / nn, y / nn, z / nn};
+    }
+    uint64_t total = 0;
+    for (int fill = 0; fill < 2; fill++) {
+        if (fill) {
+            if (total >= (1ull << 32)) return false;
+            uint32_t run = 0;
+            for (size_t c = 0; c <= ncell; c++) { const uint32_t n = cnt[c]; cnt[c] = run; run += n; }
+        }
+        const bool wide = nrm.size() > 65536;
+        const size_t idx_words = wide ? total : (total + 1) / 2;
+        const size_t idx0 = 4 + ncell + 1, nrm0 = (idx0 + idx_words + 3) & ~(size_t)3;
+        std::vector<uint32_t> cur;
+        if (fill) {
+            out.assign(nrm0 + 4 * nrm.size(), 0u);
+            out[0] = G; out[1] = (uint32_t)idx0; out[2] = (uint32_t)nrm0; out[3] = wide ? 1u : 0u;
+            memcpy(&out[4], cnt.data(), (ncell + 1) * 4);
+            if (!nrm.empty()) memcpy(&out[nrm0], nrm.data(), nrm.size() * sizeof(float4));
+            cur.assign(cnt.begin(), cnt.end() - 1);
+        }
+        uint16_t* const i16 = fill ? reinterpret_cast<uint16_t*>(&out[idx0]) : nullptr;
+        for (size_t k = 0; k < nrm.size(); k++)
+            for (int face = 0; face < 3; face++)
+                for (uint32_t i = 0; i < G; i++) {
+                    int j0, j1;
+                    row(un[k].data(), face, i, j0, j1);
+                    for (int j = j0; j <= j1; j++) {
+                        const size_t c = ((size_t)face * G + i) * G + (size_t)j;
+                        if (!fill) { cnt[c]++; total++; }
+                        else if (wide) out[idx0 + cur[c]++] = (uint32_t)k;
+                        else i16[cur[c]++] = (uint16_t)k;
+                    }
+                }
+    }
+    uint32_t longest = 0;
+    for (size_t c = 0; c < ncell; c++) longest = std::max(longest, cnt[c + 1] - cnt[c]);
+    st = CertStats{G, (uint32_t)nrm.size(), total, longest, (uint64_t)out.size() * 4,
+                   std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()};
+    return true;
+}
+
 // LDS of an octree-walk launch: the counting build keeps 2 more memo words per lane (the list's plane and edge tests)
 // and every launch room for the LDS header of k_path_primary (trace_oct.hpp, PrimHdr: its packet and pass-2 queue)
 static_assert(sizeof(PrimHdr) % 16 == 0 && sizeof(PrimHdr) <= 96, "header slot in LDS");
@@ -1528,6 +1646,7 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
     s->verbose = getenv("RTMI_VERBOSE") != nullptr;
     if (const char* v = getenv("RTMI_PACKET_CULL")) s->packet_cull = strcmp(v, "0") != 0;  // (env_size treats 0 as unset)
     if (const char* v = getenv("RTMI_BLOCK_CULL")) s->block_cull = strcmp(v, "0") != 0;
+    s->block_cull_n = (int)std::min<size_t>(std::max<size_t>(env_size("RTMI_BLOCK_CULL_N", 4), 2), 4);
     if (const char* v = getenv("RTMI_OCCLUDED_ANYHIT")) s->occl_from_hits = strcmp(v, "0") == 0;
     if (const char* v = getenv("RTMI_DENOISE_LDS_STEP")) s->dn_lds_max_step = std::min<uint32_t>((uint32_t)strtoul(v, nullptr, 10), DN_LDS_MAX_STEP);
     if (const char* v = getenv("RTMI_DENOISE_VAR_LDS_STEP")) s->dnv_lds_max_step = std::min<uint32_t>((uint32_t)strtoul(v, nullptr, 10), DN_LDS_MAX_STEP);
@@ -1567,12 +1686,30 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
         e = up(s->oblocks, hobp);
     }
     if (e == hipSuccess && s->octree) e = up(s->wlinks, hwl);
-    const bool bcull = s->octree && s->block_cull && hob.size() < (1ull << 27);  // (32-bit byte offsets, 32 B per record)
+    bool cert_on = false;
+    const bool bcull = s->octree && s->block_cull && hob.size() < (1ull << 27);  // (32-bit byte offsets)
     if (e == hipSuccess && bcull) {
-        std::vector<uint4> hoc;
+        // The table's size grows with (distinct normals) x G and a ray's list with (distinct normals) / G: it pays for scenes
+        // of up to RTMI_CERT_MAX_NORMALS distinct normals (the canonical scene has 6 717).  A scene with more
+        // keeps the 32-B records and their normal box.
+        std::vector<uint32_t> hcert;
+        std::vector<uint4> hoc, hpk;
+        const uint32_t G = (uint32_t)std::min<size_t>(std::max<size_t>(env_size("RTMI_CERT_G", 1024), 8), 1024);
         build_block_cull(hob.data(), hob.size(), hp.data(), ntris, hoc);
-        hoc.resize(hoc.size() + 2, make_uint4(0u, 0u, 0u, 0u));  // the LEAF step reads a block's record and the next one's
-        e = up(s->ocull, hoc);
+        if (!build_ray_cert(hp.data(), ntris, G, env_size("RTMI_CERT_MAX_NORMALS", 8192), hcert, s->cert_stats)) {
+            hoc.resize(hoc.size() + 2, make_uint4(0u, 0u, 0u, 0u));  // the LEAF step reads a block's record and the next one's
+            e = up(s->ocull, hoc);
+        } else {
+            cert_on = true;
+            pack_block_cull(hoc, hpk);
+            hpk.resize(hpk.size() + 3, make_uint4(0u, 0u, 0u, 0u));  // the LEAF step reads a block's record and the next three
+            e = up(s->ocull, hpk);
+            if (e == hipSuccess) e = up(s->cert, hcert);
+            if (s->verbose)
+                fprintf(stderr, "rtmi: sign certificate: G %u, %u distinct normals, %llu list entries (%.1f per cell, longest %u), %.1f MB, %.3f s\n",
+                        G, s->cert_stats.normals, (unsigned long long)s->cert_stats.entries, (double)s->cert_stats.entries / (3.0 * G * G),
+                        s->cert_stats.longest, (double)s->cert_stats.bytes / 1e6, s->cert_stats.seconds);
+        }
     }
     for (int k = 0; k < RTMI_MAX_STREAMS && e == hipSuccess; k++) {
         e = s->w[k].ctrl.ensure(1);
@@ -1588,7 +1725,7 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
     if (e != hipSuccess) return fail(hip_code(e), std::string("scene upload: ") + hipGetErrorString(e));
     s->d = DScene{s->nodes.p, s->refs.p, s->tplane.p, s->tedge.p, s->mats.p,
                   (uint32_t)nboxes, (uint32_t)ntris, (uint32_t)matmap.size(), levels,
-                  s->octree ? s->fnodes.p : nullptr, s->octree ? s->oblocks.p : nullptr, s->octree ? s->wlinks.p : nullptr, nullptr, 0u, boxes[0].len2, max_inner_depth + 1, (uint32_t)hob.size(), bcull ? s->ocull.p : nullptr};
+                  s->octree ? s->fnodes.p : nullptr, s->octree ? s->oblocks.p : nullptr, s->octree ? s->wlinks.p : nullptr, nullptr, 0u, boxes[0].len2, max_inner_depth + 1, (uint32_t)hob.size(), bcull ? s->ocull.p : nullptr, cert_on ? s->cert.p : nullptr};
     s->hmats = hm;
     s->leaf_box = std::move(of.leafbox);
     if (s->octree) {
@@ -1616,7 +1753,7 @@ int rtmi_scene_destroy(rtmi_scene_t* s) {
     if (!s) return RTMI_OK;
     (void)hipSetDevice(s->device);
     s->nodes.release(); s->refs.release(); s->tplane.release(); s->tedge.release(); s->mats.release();
-    s->fnodes.release(); s->oblocks.release(); s->ocull.release(); s->wlinks.release(); s->bnodes.release(); s->bleaves.release(); s->spheres.release();
+    s->fnodes.release(); s->oblocks.release(); s->ocull.release(); s->cert.release(); s->wlinks.release(); s->bnodes.release(); s->bleaves.release(); s->spheres.release();
     for (int k = 0; k < RTMI_MAX_STREAMS; k++) {
         s->w[k].release();
         if (s->istream[k]) (void)hipStreamDestroy(s->istream[k]);
@@ -1794,6 +1931,7 @@ static void launch_trace(rtmi_scene* s, Work& w, hipStream_t st, const float4* q
         OctArgs a{};
         a.qo = qo; a.qd = qd; a.hit_tf = w.hit_tf.p; a.hit_t = w.hit_t.p; a.pass = pass;
         a.vote_s = pass == 0 ? s->vote[0] : s->vote[2]; a.vote_l = pass == 0 ? s->vote[1] : s->vote[3];
+        a.bcn = s->block_cull_n;
         hipLaunchKernelGGL(trace_oct_variant[count][(s->options & RTMI_OPT_FAST) != 0], oct_grid(s), dim3(64), oct_launch_lds(s, count), st,
                            s->d, a, w.ctrl.p, refill, xcd);
     } else {
@@ -3986,6 +4124,63 @@ int rtmi_debug_block_cull(const float* recs, uint64_t m, const uint32_t* blocks,
             }
     return RTMI_OK;
     RTMI_GUARD_END
+}
+
+// Development aid (not in rtmi.h): what k_trace_oct culls by, on the host with the kernel's own functions -- the per-ray sign
+// certificate and the packed box-only records.  recs, blocks, rays: as for rtmi_debug_block_cull; G: cells per face edge of
+// the direction table.  Every output may be NULL: packed (4 words per block) <- the packed records; cert[i] <- ray i is
+// certified; ncand[i] <- length of its cell's list (0 for a ray block_cull_ray refuses); cell[i] <- its cell; out[b n + i] <-
+// bit 0: the half-line misses the packed box, bit 2: block b is culled for ray i; table (room for table_cap words) <- the
+// direction table when it fits, *table_words <- its size in words.  Needs no device.
+int rtmi_debug_ray_cull(const float* recs, uint64_t m, const uint32_t* blocks, uint64_t nb, const float* rays, uint64_t n, uint32_t G,
+                        uint32_t* packed, uint8_t* cert, uint32_t* ncand, uint32_t* cell, uint8_t* out, uint32_t* table,
+                        uint64_t table_cap, uint64_t* table_words) {
+    if (!recs || m < 1 || (nb > 0 && !blocks) || (n > 0 && !rays) || G < 8 || G > 1024) return fail(RTMI_ERR_INVALID, "NULL argument or G out of range");
+    RTMI_GUARD_BEGIN
+    std::vector<uint4> hoc, hpk, hb(nb);
+    std::vector<float4> hp(2 * m);
+    if (nb) memcpy(hb.data(), blocks, nb * sizeof(uint4));
+    memcpy(hp.data(), recs, m * 8 * sizeof(float));
+    build_block_cull(hb.data(), nb, hp.data(), m, hoc);
+    pack_block_cull(hoc, hpk);
+    if (packed && nb) memcpy(packed, hpk.data(), nb * sizeof(uint4));
+    std::vector<uint32_t> hcert;
+    CertStats st{};
+    if (!build_ray_cert(hp.data(), m, G, SIZE_MAX, hcert, st)) return fail(RTMI_ERR_UNSUPPORTED, "direction table too large");
+    if (table_words) *table_words = hcert.size();
+    if (table && hcert.size() <= table_cap) memcpy(table, hcert.data(), hcert.size() * 4);
+    std::vector<uint8_t> ok(n);
+    for (uint64_t i = 0; i < n; i++) {
+        const float* v = rays + 8 * i;
+        const float4 o = make_float4(v[0], v[1], v[2], v[3]), d = make_float4(v[4], v[5], v[6], v[7]);
+        uint32_t nc = 0;
+        ok[i] = ray_sign_certified(hcert.data(), o, d, &nc) ? 1 : 0;
+        if (cert) cert[i] = ok[i];
+        if (ncand) ncand[i] = nc;
+        if (cell) cell[i] = block_cull_ray(o, d) ? ray_cert_cell(G, d) : 0xFFFFFFFFu;
+    }
+    if (out) {
+        std::vector<float> inv(3 * n);
+        for (uint64_t i = 0; i < n; i++)
+            for (int k = 0; k < 3; k++) inv[3 * i + k] = 1.f / rays[8 * i + 4 + k];  // make_rayk
+        for (uint64_t b = 0; b < nb; b++)
+            for (uint64_t i = 0; i < n; i++) {
+                const float* v = rays + 8 * i;
+                const bool miss = packed_block_miss(hpk[b], v[0], v[1], v[2], inv[3 * i], inv[3 * i + 1], inv[3 * i + 2]);
+                out[b * n + i] = (uint8_t)((miss ? 1u : 0u) | (miss && ok[i] ? 4u : 0u));
+            }
+    }
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+// Development aid (not in rtmi.h): the direction table of a scene's sign certificate: out[0..5] = cells per face edge, distinct
+// normals, list entries, longest list, table bytes, build time in microseconds (all 0: the block cull is off)
+int rtmi_debug_cert_stats(const rtmi_scene_t* s, unsigned long long* out) {
+    if (!s || !out) return fail(RTMI_ERR_INVALID, "NULL argument");
+    const CertStats& c = s->cert_stats;
+    out[0] = c.g; out[1] = c.normals; out[2] = c.entries; out[3] = c.longest; out[4] = c.bytes; out[5] = (unsigned long long)(c.seconds * 1e6);
+    return RTMI_OK;
 }
 
 int rtmi_make_triangles(int device, const float* corners9_host, uint64_t n, const rtmi_triangle_t* proto, rtmi_triangle_t* out_host) {

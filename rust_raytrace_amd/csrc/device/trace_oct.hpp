@@ -53,8 +53,12 @@
 //             (the sentinel triangle is never in a tree, raytrace.rs:791) or after a full block whose 4th
 //             index has bit 31 set.  Each DISTINCT list is stored once (leaves with the same list share its blocks), so
 //             a list's first block is its identity -- what the leaf memo of oct_walk compares.
-//   ocull   : 2 x uint4 (32 B) per reference block, same index: a box around the block's triangles and one around their
-//             normals, by which k_trace_oct rejects the whole block for a ray ("Block cull" below); null: no block cull.
+//   ocull   : per reference block, same index, a record by which k_trace_oct rejects the whole block for a ray ("Block cull"
+//             below); null: no block cull.  With `cert`: one uint4 (16 B), a bf16 box around the block's triangles; without:
+//             2 x uint4 (32 B), an f32 box and a box around the triangles' normals.
+//   cert    : the distinct normals of the scene binned by ray direction; a ray uses the 16-B records only when it is certified
+//             against its cell's list ("Sign certificate per ray" below); null: the scene has too many distinct normals for
+//             the table (or no block cull).
 #pragma once
 
 namespace rtmi {
@@ -102,6 +106,7 @@ struct OctArgs {
     uint32_t slow_k;  // W_SLOW: which consumer launch this is (its range and cursor in the control block)
     int vote_s, vote_l;  // weights of the SELECT / LEAF vote (3 : 2)
     int pcull;           // W_PRIMARY: packet cull on (RTMI_PACKET_CULL, read at scene creation)
+    int bcn;             // W_TRACE: cull records a LEAF step reads and blocks it may skip, 2..4 (RTMI_BLOCK_CULL_N)
     // W_PRIMARY, mirror paths continued in place (RTMI_MIRROR_INPLACE): the pass-2 queue (ping-pong buffer 0, ctrl->count[2]
     // entries; pass 1's k_shade appends to it behind them) and the least number of a wave's mirror lanes for which the wave
     // traces their reflections itself (0: never)
@@ -249,17 +254,32 @@ __host__ __device__ inline bool block_cull_ray(float4 o, float4 d) {
     return (o.w == 0.f) & (d.w == 0.f) & (o1 <= 1e15f) & (ax > 0.f) & (ay > 0.f) & (az > 0.f) & (ax <= 1e10f) & (ay <= 1e10f) &
            (az <= 1e10f) & (dmax >= 1e-10f) & (dmin >= 0x1p-40f * dmax);
 }
+// (b) of the predicate, and the whole predicate of the packed records below: the half-line t >= 0 of a ray that
+// block_cull_ray() accepts (ix, iy, iz = 1 / d as the walk keeps them) misses the box [lo, hi] grown by K |o|_1.
+__host__ __device__ inline bool block_slab_miss(float lox, float loy, float loz, float hix, float hiy, float hiz, float ox, float oy,
+                                                float oz, float ix, float iy, float iz) {
+    const float e = BC_K * ((fabsf(ox) + fabsf(oy)) + fabsf(oz));
+    const float x0 = ((lox - e) - ox) * ix, x1 = ((hix + e) - ox) * ix;
+    const float y0 = ((loy - e) - oy) * iy, y1 = ((hiy + e) - oy) * iy;
+    const float z0 = ((loz - e) - oz) * iz, z1 = ((hiz + e) - oz) * iz;
+    // a NaN end (inf - inf, 0 * inf) must not be skipped by min / max: it turns the test off
+    const bool num = (x0 == x0) & (x1 == x1) & (y0 == y0) & (y1 == y1) & (z0 == z0) & (z1 == z1);
+    const float tn = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fminf(z0, z1));
+    const float tf = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fmaxf(z0, z1));
+    return num & ((tf < 0.f) | (tn - tf > BC_K * (fabsf(tn) + fabsf(tf))));
+}
+__host__ __device__ inline float bc_bits_float(uint32_t u) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return __uint_as_float(u);
+#else
+    float v; memcpy(&v, &u, 4); return v;
+#endif
+}
+// The 32-B record (scenes without a direction table, and rtmi_debug_block_cull; scenes with one use the packed records below).
 // Bit 0: (b) the half-line t >= 0 misses the box; bit 1: (a) no norm . dir of the block can be zero.  For a ray that
 // block_cull_ray() accepts (ix, iy, iz = 1 / d as the walk keeps them).
 __host__ __device__ inline uint32_t block_cull_parts(uint4 c0, uint4 c1, float ox, float oy, float oz, float dx, float dy, float dz,
                                                      float ix, float iy, float iz) {
-    auto f = [](uint32_t u) {
-#ifdef __HIP_DEVICE_COMPILE__
-        return __uint_as_float(u);
-#else
-        float v; memcpy(&v, &u, 4); return v;
-#endif
-    };
     auto s8 = [](uint32_t w, int sh) { return (float)((int32_t)(w << (24 - sh)) >> 24); };
     // (a) sign certificate over the normal box, in units of 1/127: L <= 127 u . d <= H for every unit normal u of the block
     const float d1 = (fabsf(dx) + fabsf(dy)) + fabsf(dz);
@@ -270,21 +290,70 @@ __host__ __device__ inline uint32_t block_cull_parts(uint4 c0, uint4 c1, float o
     const float H = (fmaxf(ax0, ax1) + fmaxf(ay0, ay1)) + fmaxf(az0, az1);
     const float m = 0.127f * d1;  // 1e-3 |d|_1 in the same units
     const bool sign = (L > m) | (H < -m);
-    // (b) slab test of the box grown by K |o|_1
-    const float e = BC_K * ((fabsf(ox) + fabsf(oy)) + fabsf(oz));
-    const float x0 = ((f(c0.x) - e) - ox) * ix, x1 = ((f(c0.w) + e) - ox) * ix;
-    const float y0 = ((f(c0.y) - e) - oy) * iy, y1 = ((f(c1.x) + e) - oy) * iy;
-    const float z0 = ((f(c0.z) - e) - oz) * iz, z1 = ((f(c1.y) + e) - oz) * iz;
-    // a NaN end (inf - inf, 0 * inf) must not be skipped by min / max: it turns the test off
-    const bool num = (x0 == x0) & (x1 == x1) & (y0 == y0) & (y1 == y1) & (z0 == z0) & (z1 == z1);
-    const float tn = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fminf(z0, z1));
-    const float tf = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fmaxf(z0, z1));
-    const bool miss = num & ((tf < 0.f) | (tn - tf > BC_K * (fabsf(tn) + fabsf(tf))));
+    const bool miss = block_slab_miss(bc_bits_float(c0.x), bc_bits_float(c0.y), bc_bits_float(c0.z), bc_bits_float(c0.w),
+                                      bc_bits_float(c1.x), bc_bits_float(c1.y), ox, oy, oz, ix, iy, iz);
     return (miss ? 1u : 0u) | (sign ? 2u : 0u);
 }
 __host__ __device__ inline bool block_culls(uint4 c0, uint4 c1, float ox, float oy, float oz, float dx, float dy, float dz, float ix,
                                             float iy, float iz) {
     return (block_cull_parts(c0, c1, ox, oy, oz, dx, dy, dz, ix, iy, iz) == 3u) & !((c1.w >> 16) & BC_NEVER);
+}
+
+// ---- Packed cull record (DScene::ocull, one uint4 = 16 B per reference block; DESIGN.md 4.1 "Sign certificate per ray"):
+//   x = lo.x | lo.y << 16   y = lo.z | hi.x << 16   z = hi.y | hi.z << 16   (bf16: the upper half of an f32)   w = flags
+// The box is the f32 box of build_block_cull with lo rounded toward -inf and hi toward +inf, so it contains that box and
+// parts (ii) / (iii) of the proof hold for it.  A never-cull block has the box [-inf, +inf], which no half-line misses (and
+// keeps BC_NEVER in w for the host); a block without a real reference keeps an empty box.  The normal box is gone: that no
+// norm . dir of the SCENE is zero is certified once per ray (ray_sign_certified), and only such a ray reads these records.
+__host__ __device__ inline bool packed_block_miss(uint4 c, float ox, float oy, float oz, float ix, float iy, float iz) {
+    return block_slab_miss(bc_bits_float(c.x << 16), bc_bits_float(c.x & 0xFFFF0000u), bc_bits_float(c.y << 16),
+                           bc_bits_float(c.y & 0xFFFF0000u), bc_bits_float(c.z << 16), bc_bits_float(c.z & 0xFFFF0000u), ox, oy, oz, ix,
+                           iy, iz);
+}
+
+// ---- Sign certificate per ray (W_TRACE; rtmi_debug_ray_cert runs the same function on the host).  norm . dir belongs to the
+// ray and the triangle, not to the block: rtmi_scene_create bins the scene's distinct normals by direction cell (a cube map
+// folded by d -> -d, G x G cells per face; build_ray_cert), a cell lists every normal u with |u . d| <= tau |d|_1 for some d
+// of the cell.  Table (words): G, first word of the index lists, first word of the normals, 1 = 32-bit indices (else 16-bit),
+// then 3 G G + 1 list offsets.  A normal is (n.xyz as in the plane record, |n|_1).
+#define CERT_TAU 1e-4     // an unlisted normal has |u . d| > tau |d|_1 for every direction of the cell
+#define CERT_KAPPA 1e-6f  // a listed normal must have |den| > kappa |n|_1 |d|_1 (rounding of den: < 4e-7 of that product)
+#define CERT_CAP 64u      // a longer list refuses the ray
+// The table cell of a direction that block_cull_ray() accepts
+__host__ __device__ inline uint32_t ray_cert_cell(uint32_t G, float4 d) {
+    const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
+    // the face of the largest component (a tie: either face lists what its border cells need), d / d_major = (1, a, b)
+    const bool fx = (ax >= ay) & (ax >= az), fy = !fx & (ay >= az);
+    const float dm = fx ? d.x : (fy ? d.y : d.z), da = fx ? d.y : (fy ? d.z : d.x), db = fx ? d.z : (fy ? d.x : d.y);
+    const uint32_t face = fx ? 0u : (fy ? 1u : 2u);
+    const float im = 1.f / dm, h = 0.5f * (float)G;
+    const int gi = (int)((da * im + 1.f) * h), gj = (int)((db * im + 1.f) * h);
+    const uint32_t i = (uint32_t)(gi < 0 ? 0 : (gi >= (int)G ? (int)G - 1 : gi)), j = (uint32_t)(gj < 0 ? 0 : (gj >= (int)G ? (int)G - 1 : gj));
+    return (face * G + i) * G + j;
+}
+// True: the ray may use the block cull -- block_cull_ray() accepts it and the plane test's den, evaluated here in the kernel's
+// own operation order for every listed normal, is nonzero with margin; with the table's guarantee for the unlisted ones every
+// triangle of the scene then has a nonzero den and a finite t for this ray.  *ncand <- length of the cell's list (host only).
+__host__ __device__ inline bool ray_sign_certified(const uint32_t* __restrict__ cert, float4 o, float4 d, uint32_t* ncand = nullptr) {
+    if (ncand) *ncand = 0u;
+    if (!block_cull_ray(o, d)) return false;
+    const uint32_t cell = ray_cert_cell(cert[0], d);
+    const uint32_t beg = cert[4u + cell], end = cert[5u + cell];
+    if (ncand) *ncand = end - beg;
+    if (end - beg > CERT_CAP) return false;
+    const uint16_t* const i16 = reinterpret_cast<const uint16_t*>(cert + cert[1]);
+    const uint32_t* const i32 = cert + cert[1];
+    const float4* const nrm = reinterpret_cast<const float4*>(cert + cert[2]);
+    const bool wide = cert[3] != 0u;
+    const float kd1 = CERT_KAPPA * ((fabsf(d.x) + fabsf(d.y)) + fabsf(d.z));
+    const float qd = 0.f * d.w;
+    bool ok = true;
+    for (uint32_t k = beg; k < end; k++) {
+        const float4 n = nrm[wide ? i32[k] : (uint32_t)i16[k]];
+        const float den = (((0.f + n.x * d.x) + n.y * d.y) + n.z * d.z) + qd;  // `plane` of the LEAF step
+        ok &= fabsf(den) > n.w * kd1;
+    }
+    return ok;
 }
 
 // S: the batch's sampling mode (W_PRIMARY / W_SLOW; Samp::LIST takes the batch's pixels from `list`, path_pixel, shade.hpp;
@@ -323,7 +392,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     // of them traced in place, exchange steps with >= 32 such lanes (low 32 bits) | with 64 such lanes (high 32 bits)
     // dbg[26..30] (W_TRACE, block cull): blocks seen by lanes with a qualifying ray, blocks whose box the half-line misses,
     // blocks culled, culled blocks that end their list, violations (a culled block with a reference whose exact test
-    // passed: must stay 0)
+    // passed: must stay 0); dbg[31..32]: rays k_trace_oct took with the cull on, those of them the certificate refused
     // dbg[24..25] (W_PRIMARY): leaf visits whose first LEAF step is a packet step (the whole-list cull starts at the list's
     // first block), whole-list culls (= the LEAF steps that the fast build spends on packet steps)
     unsigned long long dbg[RTMI_NDBG] = {};
@@ -386,7 +455,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     // against *pkl
     enum : uint32_t { PK_OFF = 0, PK_NEW = 1, PK_ON = 2 };
     uint32_t pk = PK_OFF;
-    // W_TRACE (wave-uniform, a scalar pair): the lanes whose ray block_cull_ray() accepts, updated where lanes take rays
+    // W_TRACE (wave-uniform, a scalar pair): the lanes whose ray ray_sign_certified() accepts, updated where lanes take rays
     unsigned long long bcm = 0ull;
     auto take_leaf = [&](float t, uint32_t tf) {  // a finished leaf's hit into the frame and the running best
         if (!(fw & O_HAS) || t < ft) ft = t;
@@ -559,8 +628,10 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                 }
                 if constexpr (MODE == W_TRACE) {
                     if (sc.ocull) {
-                        const bool cb = took && block_cull_ray(make_float4(r.ox, r.oy, r.oz, r.ow), make_float4(r.dx, r.dy, r.dz, r.dw));
+                        const float4 co = make_float4(r.ox, r.oy, r.oz, r.ow), cd = make_float4(r.dx, r.dy, r.dz, r.dw);
+                        const bool cb = took && (sc.cert ? ray_sign_certified(sc.cert, co, cd) : block_cull_ray(co, cd));
                         bcm = (bcm & ~__ballot(took)) | __ballot(cb);
+                        if (COUNT) { dbg[31] += took ? 1u : 0u; dbg[32] += (took && !cb) ? 1u : 0u; }
                     }
                 }
             }
@@ -868,8 +939,9 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                 q.den = c ? den : q.den;
             };
             // ---- block cull (W_TRACE, DESIGN.md 4.1 "Block cull"): a lane whose ray qualifies reads the cull record of its
-            // block first and skips the block when block_culls() rejects its references, up to 2 blocks per step (the sweep
-            // of the count is in DESIGN.md).  A culled block that ends its list finishes the leaf like the full step does
+            // block first and skips the block when the half-line misses its box (packed_block_miss; the ray is certified, so
+            // the miss rejects the block's references), up to a.bcn blocks per step (the sweep of the count is in DESIGN.md).
+            // A culled block that ends its list finishes the leaf like the full step does
             // (lhave of earlier blocks is kept, the memo entry is written).  The counting build evaluates the predicate for
             // the block of the full step and still tests every reference.
             bool bcut = false;  // COUNT: the predicate culls this lane's block
@@ -877,17 +949,47 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                 if (sc.ocull) {
                     const bool cl = (mode == M_LEAF) & (((bcm >> lane) & 1ull) != 0ull);
                     if (COUNT) {
-                        if (cl) {
+                        if (cl && sc.cert) {
+                            const uint4 c = ld_off32(sc.ocull, lblock << 4);
+                            bcut = packed_block_miss(c, r.ox, r.oy, r.oz, r.ix, r.iy, r.iz);
+                            // (a never-cull block has an infinite box: "box missed" and "culled" are one count here)
+                            dbg[26]++; dbg[27] += bcut ? 1u : 0u; dbg[28] += bcut ? 1u : 0u;
+                            dbg[29] += (bcut && (c.w & BC_END)) ? 1u : 0u;
+                        } else if (cl) {
                             const uint4 c0 = ld_off32(sc.ocull, lblock << 5), c1 = ld_off32(sc.ocull, (lblock << 5) + 16u);
                             const uint32_t parts = block_cull_parts(c0, c1, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, r.ix, r.iy, r.iz);
                             bcut = block_culls(c0, c1, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, r.ix, r.iy, r.iz);
                             dbg[26]++; dbg[27] += parts & 1u; dbg[28] += bcut ? 1u : 0u;
                             dbg[29] += (bcut && ((c1.w >> 16) & BC_END)) ? 1u : 0u;
                         }
+                    } else if (sc.cert) {
+                        // this block's record and the next ones' in one round trip, a.bcn of them (2..4, wave-uniform): the
+                        // lane skips blocks while they are culled and the list goes on (a later record only counts when
+                        // every block before it is culled and none of them ends the list; behind the array's last record
+                        // lie three zero ones)
+                        bool bfin = false;
+                        if (cl) {
+                            const uint32_t off = lblock << 4;
+                            const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+                            const uint4 c0 = ld_off32(sc.ocull, off), c1 = ld_off32(sc.ocull, off + 16u);
+                            const uint4 c2 = a.bcn > 2 ? ld_off32(sc.ocull, off + 32u) : z, c3 = a.bcn > 3 ? ld_off32(sc.ocull, off + 48u) : z;
+                            const uint4 cs[4] = {c0, c1, c2, c3};
+                            bool go = true;
+                            uint32_t adv = 0u;
+#pragma unroll
+                            for (int k = 0; k < 4; k++) {
+                                const bool cut = (k < a.bcn) & packed_block_miss(cs[k], r.ox, r.oy, r.oz, r.ix, r.iy, r.iz);
+                                const bool end = (cs[k].w & BC_END) != 0u;
+                                bfin = bfin | (go & cut & end);
+                                go = go & cut & !end;
+                                adv += go ? 1u : 0u;
+                            }
+                            lblock += adv;
+                        }
+                        if (bfin) finish_leaf();
                     } else {
-                        // this block's record and the next one's in one round trip: the lane skips 0, 1 or 2 blocks (the
-                        // second record only counts when the first block is culled and the list goes on; behind the
-                        // array's last record lies a zero one)
+                        // a scene without a direction table (too many distinct normals, rtmi_scene_create): the 32-B records
+                        // with their normal box, this block's and the next one's in one round trip
                         bool bfin = false;
                         if (cl) {
                             const uint4 c0 = ld_off32(sc.ocull, lblock << 5), c1 = ld_off32(sc.ocull, (lblock << 5) + 16u);

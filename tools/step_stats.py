@@ -19,15 +19,16 @@ print(ctx.stats)
 # the resident scene handle lives inside the C++ caster; fetch the debug counters through a tiny helper
 lib = _ffi.lib()
 lib.rth_debug_counters_n.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-out = (C.c_ulonglong * 31)()
-lib.rth_debug_counters_n(scene.h, out, 31)
+out = (C.c_ulonglong * 33)()
+lib.rth_debug_counters_n(scene.h, out, 33)
 d = list(out)
 names = ["S steps", "S lanes", "L steps", "L lanes", "refills", "refill lanes", "edge blocks", "edge lanes", "S cycles", "L cycles", "refill cycles", "wave cycles",
          "leaf visits", "memo hits", "planes skipped", "edges skipped",
          "packet L steps", "primary L steps", "packet refs", "refs culled", "violations",
          "mirror rays", "mirror in place", "mirror steps",
          "packet visits", "list culls",
-         "cull blocks", "box missed", "blocks culled", "lists culled", "cull violations"]
+         "cull blocks", "box missed", "blocks culled", "lists culled", "cull violations",
+         "cull rays", "rays refused"]
 for n, v in zip(names, d):
     print(f"{n:14s} {v}")
 rays = ctx.stats["rays"]
@@ -55,8 +56,14 @@ if d[25]:
     print(f"estimated primary LEAF steps of the fast build: {d[17] - d[16] + d[25]} (counting build: {d[17]}; whole-list culls "
           f"replacing its {d[16]} packet block steps)")
 # dbg[26..30]: the block cull of k_trace_oct (bounce passes; RTMI_BLOCK_CULL=0: all 0).  The counting build evaluates the
-# predicate for the block of every full LEAF step of a lane whose ray qualifies and still tests every reference.
+# predicate for the block of every full LEAF step of a lane whose ray is certified and still tests every reference.
+# dbg[31..32]: rays k_trace_oct took with the cull on, those of them the sign certificate refused.
 print(f"block cull (k_trace_oct, RTMI_BLOCK_CULL={os.environ.get('RTMI_BLOCK_CULL', 'default')}): {d[26]} blocks seen by lanes with a "
       f"qualifying ray ({d[26] / max(d[3], 1):.3f} of all LEAF lane-steps); box missed by the half-line {d[27]} "
       f"({d[27] / max(d[26], 1):.3f}); culled {d[28]} ({d[28] / max(d[26], 1):.3f}); lists ended by a culled block {d[29]}; "
-      f"violations {d[30]} (must be 0)")
+      f"violations {d[30]} (must be 0); sign certificate: {d[32]} of {d[31]} rays refused ({d[32] / max(d[31], 1):.4f})")
+st = (C.c_ulonglong * 6)()
+lib.rth_debug_cert_stats.argtypes = [C.c_void_p, C.c_void_p]
+if lib.rth_debug_cert_stats(scene.h, st) == 0:
+    print(f"direction table (G 0: none, the scene keeps the 32-B records): G {st[0]}, {st[1]} distinct normals, {st[2]} list entries ({st[2] / max(3 * st[0] * st[0], 1):.1f} per cell, "
+          f"longest {st[3]}), {st[4] / 1e6:.1f} MB, built in {st[5] / 1e6:.3f} s")
