@@ -87,6 +87,9 @@ struct DScene {
     const uint4* ocull;
     // the sign certificate's direction table (trace_oct.hpp, ray_sign_certified); null exactly when ocull is
     const uint32_t* cert;
+    // packed subtree cull records, one uint4 per `fnodes` record at the same index (trace_oct.hpp, "Node cull"); null: the
+    // node cull is off (always when cert is)
+    const uint4* fcull;
 };
 #define RTMI_FN_WIDE 0x10000u
 // What build_ray_cert made: cells per face edge, distinct normals, list entries, the longest list, table bytes, seconds
@@ -100,7 +103,7 @@ struct CertStats {
 
 #define RTMI_MAX_PASSES 32
 #define RTMI_MAX_STREAMS 4  // interleaved sub-tiles of one tile, each on its own internal stream
-#define RTMI_NDBG 33        // step statistics of the counting build (trace_oct.hpp: what each entry counts)
+#define RTMI_NDBG 38        // step statistics of the counting build (trace_oct.hpp: what each entry counts)
 struct DCtrl {
     uint32_t count[RTMI_MAX_PASSES + 1];  // rays queued for pass k
     uint32_t head[RTMI_MAX_PASSES + 1];   // work-fetch cursor of pass k
@@ -1049,7 +1052,7 @@ struct rtmi_scene {
     DevBuf<float4> tplane, tedge, mats, spheres;
     std::vector<float4> hmats;  // the triangles' surface table (host copy): sphere surfaces are appended to it
     std::vector<rtmi_triangle_t> htris;  // the records (host copy): the fast-mode BVH is rebuilt from them when corners arrive
-    DevBuf<uint4> fnodes, oblocks, ocull;
+    DevBuf<uint4> fnodes, oblocks, ocull, fcull;
     DevBuf<uint32_t> wlinks, cert;
     std::vector<uint32_t> leaf_box;  // OctForm::leafbox: leaf ids of k_trace_record -> box index
     // rtmi_trace_records / rtmi_primary_records: per-ray counters, leaf-list offsets and leaf ids of the last call
@@ -1161,6 +1164,9 @@ struct rtmi_scene {
     int block_cull = 1;          // k_trace_oct skips reference blocks by their cull records (RTMI_BLOCK_CULL=0: off, no records)
     int block_cull_n = 4;        // cull records a LEAF step of k_trace_oct reads, 2..4 (experiments: RTMI_BLOCK_CULL_N)
     CertStats cert_stats{};      // the sign certificate's table (rtmi_debug_cert_stats)
+    int node_cull = 1;           // k_trace_oct skips subtrees by their node cull records (RTMI_NODE_CULL=0: off, no records)
+    uint64_t node_cull_records = 0;  // node cull records built (0: none) and the seconds that took (rtmi_debug_node_cull_stats)
+    double node_cull_seconds = 0.0;
     int packet_cull = 1;         // k_path_primary culls leaf triangles per pixel packet (RTMI_PACKET_CULL=0: off, for comparison)
     // k_path_primary traces the mirror reflections of its primary rays itself when a wave has at least this many
     // (RTMI_MIRROR_INPLACE=n; 0: off, everything above 64: never)
@@ -1459,6 +1465,57 @@ static void pack_block_cull(const std::vector<uint4>& recs, std::vector<uint4>& 
     }
 }
 
+// The node cull records (trace_oct.hpp, "Node cull"): per inner record of `fn` (2 uint4 each) the union of the
+// f32 boxes of `recs` (build_block_cull: 2 uint4 per block of the `nb` blocks) over every block of every leaf list below it,
+// as a 32-B record of the same form (no normal box) -- pack_block_cull then rounds it outward like a block's.  A never-cull
+// block below makes the node never-cull (packed: [-inf, +inf]); a subtree without a real reference keeps the empty box.
+// Bottom-up: the inner children of a record have larger record indices (children follow their parent in box order).  A
+// shared list is walked once per leaf that carries it.
+static void build_node_cull(const std::vector<uint4>& fn, const std::vector<uint32_t>& wl, const std::vector<uint4>& recs, size_t nb,
+                            std::vector<uint4>& out) {
+    auto fb = [](float v) { uint32_t u; memcpy(&u, &v, 4); return u; };
+    auto bf = [](uint32_t u) { float v; memcpy(&v, &u, 4); return v; };
+    const size_t nrec = fn.size() / 2;
+    struct Box { float lo[3], hi[3]; bool never; };
+    std::vector<Box> box(nrec);
+    for (size_t r = nrec; r-- > 0;) {
+        const uint4 q0 = fn[2 * r], q1 = fn[2 * r + 1];
+        const uint32_t present = q0.w & 0xFFu, leafmask = (q0.w >> 8) & 0xFFu;
+        Box b{{FLT_MAX, FLT_MAX, FLT_MAX}, {-FLT_MAX, -FLT_MAX, -FLT_MAX}, false};
+        auto join = [&](const float* lo, const float* hi) {
+            for (int a = 0; a < 3; a++) { b.lo[a] = std::min(b.lo[a], lo[a]); b.hi[a] = std::max(b.hi[a], hi[a]); }
+        };
+        for (uint32_t oct = 0; oct < 8; oct++) {
+            const uint32_t bit = 1u << oct;
+            if (!(present & bit)) continue;
+            if (leafmask & bit) {
+                // the leaf's first block as oct_walk finds it, then its blocks up to the one that ends the list
+                size_t k = (q0.w & RTMI_FN_WIDE) ? wl[(size_t)q1.y * 8u + oct] : q1.y + (((oct < 4u ? q1.z : q1.w) >> ((oct & 3u) * 8u)) & 0xFFu);
+                for (; k < nb; k++) {
+                    const uint4 c0 = recs[2 * k], c1 = recs[2 * k + 1];
+                    const uint32_t flags = c1.w >> 16;
+                    if (flags & BC_NEVER) b.never = true;
+                    const float lo[3] = {bf(c0.x), bf(c0.y), bf(c0.z)}, hi[3] = {bf(c0.w), bf(c1.x), bf(c1.y)};
+                    join(lo, hi);
+                    if (flags & BC_END) break;
+                }
+            } else {
+                const size_t c = q1.x + (size_t)__builtin_popcount((present & ~leafmask) & (bit - 1u));
+                if (c <= r || c >= nrec) { b.never = true; continue; }  // (cannot happen in a form build_oct_form made)
+                b.never |= box[c].never;
+                join(box[c].lo, box[c].hi);
+            }
+        }
+        box[r] = b;
+    }
+    out.assign(2 * nrec, make_uint4(0u, 0u, 0u, 0u));
+    for (size_t r = 0; r < nrec; r++) {
+        const Box& b = box[r];
+        out[2 * r] = make_uint4(fb(b.lo[0]), fb(b.lo[1]), fb(b.lo[2]), fb(b.hi[0]));
+        out[2 * r + 1] = make_uint4(fb(b.hi[1]), fb(b.hi[2]), 0u, (b.never ? BC_NEVER : 0u) << 16);
+    }
+}
+
 // The direction table of the sign certificate (trace_oct.hpp, ray_sign_certified).  hp: the plane records of
 // `ntris` triangles.  The distinct normals (bitwise; those with |n| outside [1e-15, 1e15] make their block never-cull and are
 // left out) are binned by the cell of d / d_major = (1, a, b): cell (face, i, j) covers a in [-1 + 2 i / G, -1 + 2 (i + 1) / G]
@@ -1647,6 +1704,7 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
     if (const char* v = getenv("RTMI_PACKET_CULL")) s->packet_cull = strcmp(v, "0") != 0;  // (env_size treats 0 as unset)
     if (const char* v = getenv("RTMI_BLOCK_CULL")) s->block_cull = strcmp(v, "0") != 0;
     s->block_cull_n = (int)std::min<size_t>(std::max<size_t>(env_size("RTMI_BLOCK_CULL_N", 4), 2), 4);
+    if (const char* v = getenv("RTMI_NODE_CULL")) s->node_cull = strcmp(v, "0") != 0;
     if (const char* v = getenv("RTMI_OCCLUDED_ANYHIT")) s->occl_from_hits = strcmp(v, "0") == 0;
     if (const char* v = getenv("RTMI_DENOISE_LDS_STEP")) s->dn_lds_max_step = std::min<uint32_t>((uint32_t)strtoul(v, nullptr, 10), DN_LDS_MAX_STEP);
     if (const char* v = getenv("RTMI_DENOISE_VAR_LDS_STEP")) s->dnv_lds_max_step = std::min<uint32_t>((uint32_t)strtoul(v, nullptr, 10), DN_LDS_MAX_STEP);
@@ -1686,7 +1744,7 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
         e = up(s->oblocks, hobp);
     }
     if (e == hipSuccess && s->octree) e = up(s->wlinks, hwl);
-    bool cert_on = false;
+    bool cert_on = false, fcull_on = false;
     const bool bcull = s->octree && s->block_cull && hob.size() < (1ull << 27);  // (32-bit byte offsets)
     if (e == hipSuccess && bcull) {
         // The table's size grows with (distinct normals) x G and a ray's list with (distinct normals) / G: it pays for scenes
@@ -1709,6 +1767,20 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
                 fprintf(stderr, "rtmi: sign certificate: G %u, %u distinct normals, %llu list entries (%.1f per cell, longest %u), %.1f MB, %.3f s\n",
                         G, s->cert_stats.normals, (unsigned long long)s->cert_stats.entries, (double)s->cert_stats.entries / (3.0 * G * G),
                         s->cert_stats.longest, (double)s->cert_stats.bytes / 1e6, s->cert_stats.seconds);
+            if (e == hipSuccess && s->node_cull) {
+                // one packed record per inner record: the box of everything below it (only a certified ray may use it)
+                const auto t0 = std::chrono::steady_clock::now();
+                std::vector<uint4> hnc, hnk;
+                build_node_cull(hfn, hwl, hoc, hob.size(), hnc);
+                pack_block_cull(hnc, hnk);
+                s->node_cull_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+                s->node_cull_records = hnk.size();
+                e = up(s->fcull, hnk);
+                fcull_on = e == hipSuccess && !hnk.empty();
+                if (s->verbose)
+                    fprintf(stderr, "rtmi: node cull: %llu records, %.2f MB, %.3f s\n", (unsigned long long)hnk.size(), (double)hnk.size() * 16.0 / 1e6,
+                            s->node_cull_seconds);
+            }
         }
     }
     for (int k = 0; k < RTMI_MAX_STREAMS && e == hipSuccess; k++) {
@@ -1725,7 +1797,8 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
     if (e != hipSuccess) return fail(hip_code(e), std::string("scene upload: ") + hipGetErrorString(e));
     s->d = DScene{s->nodes.p, s->refs.p, s->tplane.p, s->tedge.p, s->mats.p,
                   (uint32_t)nboxes, (uint32_t)ntris, (uint32_t)matmap.size(), levels,
-                  s->octree ? s->fnodes.p : nullptr, s->octree ? s->oblocks.p : nullptr, s->octree ? s->wlinks.p : nullptr, nullptr, 0u, boxes[0].len2, max_inner_depth + 1, (uint32_t)hob.size(), bcull ? s->ocull.p : nullptr, cert_on ? s->cert.p : nullptr};
+                  s->octree ? s->fnodes.p : nullptr, s->octree ? s->oblocks.p : nullptr, s->octree ? s->wlinks.p : nullptr, nullptr, 0u, boxes[0].len2, max_inner_depth + 1, (uint32_t)hob.size(), bcull ? s->ocull.p : nullptr, cert_on ? s->cert.p : nullptr,
+                  fcull_on ? s->fcull.p : nullptr};
     s->hmats = hm;
     s->leaf_box = std::move(of.leafbox);
     if (s->octree) {
@@ -1753,7 +1826,7 @@ int rtmi_scene_destroy(rtmi_scene_t* s) {
     if (!s) return RTMI_OK;
     (void)hipSetDevice(s->device);
     s->nodes.release(); s->refs.release(); s->tplane.release(); s->tedge.release(); s->mats.release();
-    s->fnodes.release(); s->oblocks.release(); s->ocull.release(); s->cert.release(); s->wlinks.release(); s->bnodes.release(); s->bleaves.release(); s->spheres.release();
+    s->fnodes.release(); s->oblocks.release(); s->ocull.release(); s->fcull.release(); s->cert.release(); s->wlinks.release(); s->bnodes.release(); s->bleaves.release(); s->spheres.release();
     for (int k = 0; k < RTMI_MAX_STREAMS; k++) {
         s->w[k].release();
         if (s->istream[k]) (void)hipStreamDestroy(s->istream[k]);
@@ -4181,6 +4254,70 @@ int rtmi_debug_cert_stats(const rtmi_scene_t* s, unsigned long long* out) {
     const CertStats& c = s->cert_stats;
     out[0] = c.g; out[1] = c.normals; out[2] = c.entries; out[3] = c.longest; out[4] = c.bytes; out[5] = (unsigned long long)(c.seconds * 1e6);
     return RTMI_OK;
+}
+
+// Development aid (not in rtmi.h): a scene's node cull records: out[0..2] = records, bytes, build time in microseconds (all 0:
+// the node cull is off)
+int rtmi_debug_node_cull_stats(const rtmi_scene_t* s, unsigned long long* out) {
+    if (!s || !out) return fail(RTMI_ERR_INVALID, "NULL argument");
+    out[0] = s->d.fcull ? s->node_cull_records : 0ull;
+    out[1] = out[0] * 16ull;
+    out[2] = s->d.fcull ? (unsigned long long)(s->node_cull_seconds * 1e6) : 0ull;
+    return RTMI_OK;
+}
+
+// Development aid (not in rtmi.h): the node cull of k_trace_oct on the host with the kernel's own functions (trace_oct.hpp).
+// boxes, tri_refs, ntris: a flattened tree as for rtmi_debug_oct_form; recs: ntris plane records (8 floats each, record 0
+// the sentinel); rays: n rays (o.xyzw, d.xyzw); G: cells per face edge of the direction table.  *nrec <- inner records of the
+// octree form (call with every array NULL for it).  Every array may be NULL: records (4 words per inner record, the index
+// of `fnodes`) <- the packed node records; cert[i] <- ray i is certified; out[r n + i] <- bit 0: the half-line of ray i misses
+// the packed box of record r, bit 2: the walk culls the subtree of r for ray i (bit 0 and certified).  Needs no device.
+int rtmi_debug_node_cull(const rtmi_box_t* boxes, uint64_t nboxes, const uint32_t* tri_refs, uint64_t nrefs, uint64_t ntris, const float* recs,
+                         const float* rays, uint64_t n, uint32_t G, uint64_t* nrec, uint32_t* records, uint8_t* cert, uint8_t* out) {
+    if (!boxes || nboxes < 1 || !recs || ntris < 1 || !nrec || (nrefs > 0 && !tri_refs) || (n > 0 && !rays) || G < 8 || G > 1024)
+        return fail(RTMI_ERR_INVALID, "NULL argument or G out of range");
+    if (nboxes >= (1ull << 32) || nrefs >= (1ull << 32)) return fail(RTMI_ERR_UNSUPPORTED, "tree too large for 32-bit indices");
+    RTMI_GUARD_BEGIN
+    std::vector<uint32_t> depth;
+    uint32_t max_inner_depth = 0;
+    const std::string bad = validate_tree(boxes, nboxes, tri_refs, nrefs, ntris, depth, max_inner_depth);
+    if (!bad.empty()) return fail(RTMI_ERR_INVALID, bad);
+    OctForm f;
+    build_oct_form(boxes, nboxes, tri_refs, ntris, depth, f);
+    if (f.fn.empty()) return fail(RTMI_ERR_UNSUPPORTED, f.why);
+    *nrec = f.fn.size() / 2;
+    if (!records && !cert && !out) return RTMI_OK;
+    std::vector<float4> hp(2 * ntris);
+    memcpy(hp.data(), recs, ntris * 8 * sizeof(float));
+    std::vector<uint4> hoc, hnc, hnk;
+    build_block_cull(f.ob.data(), f.ob.size(), hp.data(), ntris, hoc);
+    build_node_cull(f.fn, f.wl, hoc, f.ob.size(), hnc);
+    pack_block_cull(hnc, hnk);
+    if (records && !hnk.empty()) memcpy(records, hnk.data(), hnk.size() * sizeof(uint4));
+    std::vector<uint8_t> ok(n, 0);
+    if (cert || out) {
+        std::vector<uint32_t> hcert;
+        CertStats st{};
+        if (!build_ray_cert(hp.data(), ntris, G, SIZE_MAX, hcert, st)) return fail(RTMI_ERR_UNSUPPORTED, "direction table too large");
+        for (uint64_t i = 0; i < n; i++) {
+            const float* v = rays + 8 * i;
+            ok[i] = ray_sign_certified(hcert.data(), make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7])) ? 1 : 0;
+            if (cert) cert[i] = ok[i];
+        }
+    }
+    if (out) {
+        std::vector<float> inv(3 * n);
+        for (uint64_t i = 0; i < n; i++)
+            for (int k = 0; k < 3; k++) inv[3 * i + k] = 1.f / rays[8 * i + 4 + k];  // make_rayk
+        for (uint64_t r = 0; r < hnk.size(); r++)
+            for (uint64_t i = 0; i < n; i++) {
+                const float* v = rays + 8 * i;
+                const bool miss = packed_block_miss(hnk[r], v[0], v[1], v[2], inv[3 * i], inv[3 * i + 1], inv[3 * i + 2]);
+                out[r * n + i] = (uint8_t)((miss ? 1u : 0u) | (miss && ok[i] ? 4u : 0u));
+            }
+    }
+    return RTMI_OK;
+    RTMI_GUARD_END
 }
 
 int rtmi_make_triangles(int device, const float* corners9_host, uint64_t n, const rtmi_triangle_t* proto, rtmi_triangle_t* out_host) {

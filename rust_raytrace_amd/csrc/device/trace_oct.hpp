@@ -59,6 +59,9 @@
 //   cert    : the distinct normals of the scene binned by ray direction; a ray uses the 16-B records only when it is certified
 //             against its cell's list ("Sign certificate per ray" below); null: the scene has too many distinct normals for
 //             the table (or no block cull).
+//   fcull   : per record of `fnodes`, same index, one uint4 (16 B) in the form of a packed ocull record: a bf16 box around every
+//             block box below that inner box, by which a certified ray rejects the whole subtree ("Node cull" below); null:
+//             no node cull (always when `cert` is null).
 #pragma once
 
 namespace rtmi {
@@ -311,6 +314,15 @@ __host__ __device__ inline bool packed_block_miss(uint4 c, float ox, float oy, f
                            iy, iz);
 }
 
+// ---- Node cull (W_TRACE, DESIGN.md 4.1 "Node cull"; rtmi_debug_node_cull runs the same functions on the host).  DScene::fcull
+// holds one packed record per inner box: the union of the f32 block boxes of every leaf list below the box, packed like a
+// block's (lo toward -inf, hi toward +inf; a never-cull block below: [-inf, +inf]; no real reference below: the empty box).
+// When the half-line of a certified ray misses that box (packed_block_miss, the predicate of the block cull), it misses
+// every block box inside it, so every reference of the subtree fails the exact plane test and the subtree's walk ends
+// without a hit: the SELECT step that first visits the box marks its frame done instead of choosing a child, which is the
+// state that walk leaves behind.  The reference's collides() would have entered the box -- it walks boxes behind the
+// origin too -- but nothing it does there reaches the result.
+
 // ---- Sign certificate per ray (W_TRACE; rtmi_debug_ray_cert runs the same function on the host).  norm . dir belongs to the
 // ray and the triangle, not to the block: rtmi_scene_create bins the scene's distinct normals by direction cell (a cube map
 // folded by d -> -d, G x G cells per face; build_ray_cert), a cell lists every normal u with |u . d| <= tau |d|_1 for some d
@@ -395,7 +407,13 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     // passed: must stay 0); dbg[31..32]: rays k_trace_oct took with the cull on, those of them the certificate refused
     // dbg[24..25] (W_PRIMARY): leaf visits whose first LEAF step is a packet step (the whole-list cull starts at the list's
     // first block), whole-list culls (= the LEAF steps that the fast build spends on packet steps)
+    // dbg[33..37] (W_TRACE, node cull): inner boxes a certified lane visits for the first time outside a missed subtree, those
+    // whose node record the half-line misses, then what the fast build saves -- SELECT lane-steps and leaf visits inside a
+    // missed subtree (the step that finds the miss not included) -- and violations (a hit taken inside a missed subtree:
+    // must stay 0)
     unsigned long long dbg[RTMI_NDBG] = {};
+    // COUNT, W_TRACE: depth of the box at which the missed subtree this lane walks began (-1: it is in none)
+    int mlvl = -1;
     const unsigned long long t_begin = COUNT ? __builtin_amdgcn_s_memtime() : 0ull;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     const float root_half = sc.root_half;
@@ -458,6 +476,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     // W_TRACE (wave-uniform, a scalar pair): the lanes whose ray ray_sign_certified() accepts, updated where lanes take rays
     unsigned long long bcm = 0ull;
     auto take_leaf = [&](float t, uint32_t tf) {  // a finished leaf's hit into the frame and the running best
+        if (COUNT && MODE == W_TRACE && mlvl >= 0) dbg[37]++;  // the node predicate was wrong: must never happen
         if (!(fw & O_HAS) || t < ft) ft = t;
         fw |= O_HAS;
         if (!ghave || t < gt) { gt = t; gtf = tf; }
@@ -617,6 +636,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                             if (MEMO) memo[0] = 0xFFFFFFFFu;  // no block index (< 2^28)
                             mode = M_SELECT;
                             took = true;
+                            if (COUNT && MODE == W_TRACE) mlvl = -1;
                             if constexpr (MODE == W_OCCL) tmx = oc.tmax ? oc.tmax[i] : __uint_as_float(inf_bits);
                             if constexpr (MODE == W_RECORD) {  // this ray's counters start here; its leaf list at lfirst[i]
 #pragma unroll
@@ -681,6 +701,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                         fw |= O_HAS;
                     }
                 }
+                if (COUNT && MODE == W_TRACE && lvl < mlvl) mlvl = -1;  // back above the box where the missed subtree began
                 if (fw & O_DONE) {  // the root frame is finished: the ray is
                     if (QUEUE) {
                         if constexpr (MODE == W_RECORD) {
@@ -699,6 +720,24 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                     } else mode = M_SHADE;  // shaded in the next exchange step, together with the other finished lanes
                 } else {
                     const uint4 q0 = ld_off32(sc.fnodes, fnode << 5), q1 = ld_off32(sc.fnodes, (fnode << 5) + 16u);
+                    // ---- node cull ("Node cull" above): the box's node record comes in the same round trip; a certified
+                    // lane that visits the box for the first time and whose half-line misses the record's box ends the box
+                    // here.  The counting build evaluates the same predicate, counts, and walks the subtree all the same.
+                    bool ncut = false;
+                    if constexpr (MODE == W_TRACE) {
+                        if (sc.fcull) {
+                            const uint4 nc = ld_off32(sc.fcull, fnode << 4);
+                            const bool first = (((bcm >> lane) & 1ull) != 0ull) & ((fw & 0xFFu) == 0u);
+                            const bool miss = first & packed_block_miss(nc, r.ox, r.oy, r.oz, r.ix, r.iy, r.iz);
+                            if (COUNT) {
+                                if (mlvl >= 0) dbg[35]++;
+                                else if (first) {
+                                    dbg[33]++;
+                                    if (miss) { dbg[34]++; mlvl = lvl; }
+                                }
+                            } else ncut = miss;
+                        }
+                    }
                     const float cx = __uint_as_float(q0.x), cy = __uint_as_float(q0.y), cz = __uint_as_float(q0.z);
                     const float hc = ldexpf(root_half, -(lvl + 1));  // half edge of the children (depth lvl + 1)
                     if (COUNT && (fw & 0xFFu) == 0u) { cnt[0] += __popc(q0.w & 0xFFu); cnt[3]++; }  // first visit: collides() on every child
@@ -753,7 +792,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                     // one, because every remaining tmin is >= this one.
                     // One compare does all of that: without a candidate m1 is +inf, with one it is in [-MAX, MAX] (a
                     // colliding tmin is never NaN or +inf), where `!= MAX` is `< MAX`; and `inf < ft` is false for every ft.
-                    const bool ok = m1 < ((fw & O_HAS) ? ft : FLT_MAX);
+                    const bool ok = (m1 < ((fw & O_HAS) ? ft : FLT_MAX)) & !ncut;  // (a culled box: nothing is selected, its frame is done)
                     uint32_t bit = 0u;
 #pragma unroll
                     for (int o = 7; o >= 0; o--) bit = (tm[o] == m1) ? (1u << o) : bit;
@@ -773,6 +812,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                             else lblock = q1.y + __builtin_amdgcn_ubfe(oct < 4u ? q1.z : q1.w, (oct & 3u) * 8u, 8u);
                             if (COUNT) cnt[4]++;
                             if (COUNT && MEMO) dbg[12]++;
+                            if (COUNT && MODE == W_TRACE && mlvl >= 0) dbg[36]++;
                             if (MEMO && memo[0] == lblock) {  // the list this ray scanned last: its result, no LEAF steps
                                 const uint32_t mtf = memo[2 * NT];
                                 if (mtf != 0u) take_leaf(__uint_as_float(memo[NT]), mtf);

@@ -639,6 +639,11 @@ int rth_debug_cert_stats(rth_scene_t* s, unsigned long long* out) {
     return guarded([&] { rtmi_debug_cert_stats(caster_of(s).resident(s->scene), out); });
 }
 
+int rtmi_debug_node_cull_stats(const rtmi_scene_t* s, unsigned long long* out);
+int rth_debug_node_cull_stats(rth_scene_t* s, unsigned long long* out) {
+    return guarded([&] { rtmi_debug_node_cull_stats(caster_of(s).resident(s->scene), out); });
+}
+
 void rth_quantize(const float* rgba, uint64_t npixels, uint8_t* rgb) {
     quantize_rgb8(reinterpret_cast<const Color*>(rgba), (size_t)npixels, rgb);
 }

@@ -19,8 +19,8 @@ print(ctx.stats)
 # the resident scene handle lives inside the C++ caster; fetch the debug counters through a tiny helper
 lib = _ffi.lib()
 lib.rth_debug_counters_n.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-out = (C.c_ulonglong * 33)()
-lib.rth_debug_counters_n(scene.h, out, 33)
+out = (C.c_ulonglong * 38)()
+lib.rth_debug_counters_n(scene.h, out, 38)
 d = list(out)
 names = ["S steps", "S lanes", "L steps", "L lanes", "refills", "refill lanes", "edge blocks", "edge lanes", "S cycles", "L cycles", "refill cycles", "wave cycles",
          "leaf visits", "memo hits", "planes skipped", "edges skipped",
@@ -28,7 +28,8 @@ names = ["S steps", "S lanes", "L steps", "L lanes", "refills", "refill lanes", 
          "mirror rays", "mirror in place", "mirror steps",
          "packet visits", "list culls",
          "cull blocks", "box missed", "blocks culled", "lists culled", "cull violations",
-         "cull rays", "rays refused"]
+         "cull rays", "rays refused",
+         "nodes seen", "nodes missed", "S lanes in missed", "leaves in missed", "node violations"]
 for n, v in zip(names, d):
     print(f"{n:14s} {v}")
 rays = ctx.stats["rays"]
@@ -67,3 +68,14 @@ lib.rth_debug_cert_stats.argtypes = [C.c_void_p, C.c_void_p]
 if lib.rth_debug_cert_stats(scene.h, st) == 0:
     print(f"direction table (G 0: none, the scene keeps the 32-B records): G {st[0]}, {st[1]} distinct normals, {st[2]} list entries ({st[2] / max(3 * st[0] * st[0], 1):.1f} per cell, "
           f"longest {st[3]}), {st[4] / 1e6:.1f} MB, built in {st[5] / 1e6:.3f} s")
+# dbg[33..37]: the node cull of k_trace_oct (bounce passes; RTMI_NODE_CULL=0 or no direction table: all 0).  The counting build
+# evaluates the node predicate at every first visit of an inner box by a certified lane outside a missed subtree and walks
+# the subtree all the same: what it does inside is what the fast build saves.
+print(f"node cull (k_trace_oct, RTMI_NODE_CULL={os.environ.get('RTMI_NODE_CULL', 'default')}): {d[33]} inner boxes first visited by "
+      f"certified lanes outside a missed subtree, node box missed by the half-line {d[34]} ({d[34] / max(d[33], 1):.3f}); inside "
+      f"missed subtrees: {d[35]} SELECT lane-steps ({d[35] / max(d[1], 1):.3f} of all), {d[36]} leaf visits "
+      f"({d[36] / max(d[12], 1):.3f} of all); violations {d[37]} (must be 0)")
+ns = (C.c_ulonglong * 3)()
+lib.rth_debug_node_cull_stats.argtypes = [C.c_void_p, C.c_void_p]
+if lib.rth_debug_node_cull_stats(scene.h, ns) == 0:
+    print(f"node cull records (0: none): {ns[0]}, {ns[1] / 1e6:.2f} MB, built in {ns[2] / 1e6:.3f} s")
