@@ -103,7 +103,7 @@ struct CertStats {
 
 #define RTMI_MAX_PASSES 32
 #define RTMI_MAX_STREAMS 4  // interleaved sub-tiles of one tile, each on its own internal stream
-#define RTMI_NDBG 38        // step statistics of the counting build (trace_oct.hpp: what each entry counts)
+#define RTMI_NDBG 52        // step statistics of the counting build (trace_oct.hpp: what each entry counts)
 struct DCtrl {
     uint32_t count[RTMI_MAX_PASSES + 1];  // rays queued for pass k
     uint32_t head[RTMI_MAX_PASSES + 1];   // work-fetch cursor of pass k
@@ -1052,7 +1052,7 @@ struct rtmi_scene {
     DevBuf<float4> tplane, tedge, mats, spheres;
     std::vector<float4> hmats;  // the triangles' surface table (host copy): sphere surfaces are appended to it
     std::vector<rtmi_triangle_t> htris;  // the records (host copy): the fast-mode BVH is rebuilt from them when corners arrive
-    DevBuf<uint4> fnodes, oblocks, ocull, fcull;
+    DevBuf<uint4> fnodes, oblocks, ocull;  // (fnodes: the node records, then the node cull records)
     DevBuf<uint32_t> wlinks, cert;
     std::vector<uint32_t> leaf_box;  // OctForm::leafbox: leaf ids of k_trace_record -> box index
     // rtmi_trace_records / rtmi_primary_records: per-ray counters, leaf-list offsets and leaf ids of the last call
@@ -1167,6 +1167,7 @@ struct rtmi_scene {
     int node_cull = 1;           // k_trace_oct skips subtrees by their node cull records (RTMI_NODE_CULL=0: off, no records)
     uint64_t node_cull_records = 0;  // node cull records built (0: none) and the seconds that took (rtmi_debug_node_cull_stats)
     double node_cull_seconds = 0.0;
+    int primary_node_cull = 1;   // k_path_primary skips subtrees by the node cull records too (RTMI_PRIMARY_NODE_CULL=0: off)
     int packet_cull = 1;         // k_path_primary culls leaf triangles per pixel packet (RTMI_PACKET_CULL=0: off, for comparison)
     // k_path_primary traces the mirror reflections of its primary rays itself when a wave has at least this many
     // (RTMI_MIRROR_INPLACE=n; 0: off, everything above 64: never)
@@ -1601,8 +1602,8 @@ static bool build_ray_cert(const float4* hp, uint64_t ntris, uint32_t G, size_t 
 
 // LDS of an octree-walk launch: the counting build keeps 2 more memo words per lane (the list's plane and edge tests)
 // and every launch room for the LDS header of k_path_primary (trace_oct.hpp, PrimHdr: its packet and pass-2 queue)
-static_assert(sizeof(PrimHdr) % 16 == 0 && sizeof(PrimHdr) <= 96, "header slot in LDS");
-static size_t oct_launch_lds(const rtmi_scene* s, bool count) { return s->oct_lds + (count ? 2 * 4 * 64 : 0) + 96; }
+static_assert(sizeof(PrimHdr) % 16 == 0 && sizeof(PrimHdr) <= 112, "header slot in LDS");
+static size_t oct_launch_lds(const rtmi_scene* s, bool count) { return s->oct_lds + (count ? 2 * 4 * 64 : 0) + 112; }
 
 extern "C" {
 
@@ -1705,6 +1706,7 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
     if (const char* v = getenv("RTMI_BLOCK_CULL")) s->block_cull = strcmp(v, "0") != 0;
     s->block_cull_n = (int)std::min<size_t>(std::max<size_t>(env_size("RTMI_BLOCK_CULL_N", 4), 2), 4);
     if (const char* v = getenv("RTMI_NODE_CULL")) s->node_cull = strcmp(v, "0") != 0;
+    if (const char* v = getenv("RTMI_PRIMARY_NODE_CULL")) s->primary_node_cull = strcmp(v, "0") != 0;
     if (const char* v = getenv("RTMI_OCCLUDED_ANYHIT")) s->occl_from_hits = strcmp(v, "0") == 0;
     if (const char* v = getenv("RTMI_DENOISE_LDS_STEP")) s->dn_lds_max_step = std::min<uint32_t>((uint32_t)strtoul(v, nullptr, 10), DN_LDS_MAX_STEP);
     if (const char* v = getenv("RTMI_DENOISE_VAR_LDS_STEP")) s->dnv_lds_max_step = std::min<uint32_t>((uint32_t)strtoul(v, nullptr, 10), DN_LDS_MAX_STEP);
@@ -1745,6 +1747,7 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
     }
     if (e == hipSuccess && s->octree) e = up(s->wlinks, hwl);
     bool cert_on = false, fcull_on = false;
+    size_t fcull_at = 0;  // where the node cull records begin in `fnodes`
     const bool bcull = s->octree && s->block_cull && hob.size() < (1ull << 27);  // (32-bit byte offsets)
     if (e == hipSuccess && bcull) {
         // The table's size grows with (distinct normals) x G and a ray's list with (distinct normals) / G: it pays for scenes
@@ -1775,8 +1778,12 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
                 pack_block_cull(hnc, hnk);
                 s->node_cull_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
                 s->node_cull_records = hnk.size();
-                e = up(s->fcull, hnk);
+                // behind the node records, in their buffer: the primary kernels address them from `fnodes` (PrimHdr::foff)
+                std::vector<uint4> hfk(hfn);
+                hfk.insert(hfk.end(), hnk.begin(), hnk.end());
+                e = up(s->fnodes, hfk);
                 fcull_on = e == hipSuccess && !hnk.empty();
+                fcull_at = hfn.size();
                 if (s->verbose)
                     fprintf(stderr, "rtmi: node cull: %llu records, %.2f MB, %.3f s\n", (unsigned long long)hnk.size(), (double)hnk.size() * 16.0 / 1e6,
                             s->node_cull_seconds);
@@ -1798,7 +1805,7 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
     s->d = DScene{s->nodes.p, s->refs.p, s->tplane.p, s->tedge.p, s->mats.p,
                   (uint32_t)nboxes, (uint32_t)ntris, (uint32_t)matmap.size(), levels,
                   s->octree ? s->fnodes.p : nullptr, s->octree ? s->oblocks.p : nullptr, s->octree ? s->wlinks.p : nullptr, nullptr, 0u, boxes[0].len2, max_inner_depth + 1, (uint32_t)hob.size(), bcull ? s->ocull.p : nullptr, cert_on ? s->cert.p : nullptr,
-                  fcull_on ? s->fcull.p : nullptr};
+                  fcull_on ? s->fnodes.p + fcull_at : nullptr};
     s->hmats = hm;
     s->leaf_box = std::move(of.leafbox);
     if (s->octree) {
@@ -1826,7 +1833,7 @@ int rtmi_scene_destroy(rtmi_scene_t* s) {
     if (!s) return RTMI_OK;
     (void)hipSetDevice(s->device);
     s->nodes.release(); s->refs.release(); s->tplane.release(); s->tedge.release(); s->mats.release();
-    s->fnodes.release(); s->oblocks.release(); s->ocull.release(); s->fcull.release(); s->cert.release(); s->wlinks.release(); s->bnodes.release(); s->bleaves.release(); s->spheres.release();
+    s->fnodes.release(); s->oblocks.release(); s->ocull.release(); s->cert.release(); s->wlinks.release(); s->bnodes.release(); s->bleaves.release(); s->spheres.release();
     for (int k = 0; k < RTMI_MAX_STREAMS; k++) {
         s->w[k].release();
         if (s->istream[k]) (void)hipStreamDestroy(s->istream[k]);
@@ -1981,12 +1988,16 @@ typedef void (*ListWalkKernel)(DScene, OctArgs, DCtrl*, int, int, const uint32_t
 static const WalkKernel trace_oct_variant[2][2] = RTMI_COUNT_FAST(k_trace_oct);
 typedef void (*OcclWalkKernel)(DScene, OctArgs, DCtrl*, int, int, OcclArgs);
 static const OcclWalkKernel occluded_oct_variant[2][2] = RTMI_COUNT_FAST(k_occluded_oct);
-static const WalkKernel path_variant[2][2][2][2] = {  // [slow][mode == Samp::PASS][count][fast]
+// (first index of the path kernels: 0 = primary, 1 = slow, 2 = primary with the node cull)
+static const WalkKernel path_variant[3][2][2][2] = {  // [which][mode == Samp::PASS][count][fast]
     {RTMI_COUNT_FAST(k_path_primary), RTMI_COUNT_FAST(k_path_primary_samples)},
-    {RTMI_COUNT_FAST(k_path_slow), RTMI_COUNT_FAST(k_path_slow_samples)}};
-static const ListWalkKernel path_list_variant[2][2][2] = {RTMI_COUNT_FAST(k_path_primary_list), RTMI_COUNT_FAST(k_path_slow_list)};
+    {RTMI_COUNT_FAST(k_path_slow), RTMI_COUNT_FAST(k_path_slow_samples)},
+    {RTMI_COUNT_FAST(k_path_primary_cull), RTMI_COUNT_FAST(k_path_primary_samples_cull)}};
+static const ListWalkKernel path_list_variant[3][2][2] = {RTMI_COUNT_FAST(k_path_primary_list), RTMI_COUNT_FAST(k_path_slow_list),
+                                                          RTMI_COUNT_FAST(k_path_primary_list_cull)};
 typedef void (*ViewsWalkKernel)(DScene, OctArgs, DCtrl*, int, int, ViewTab);
-static const ViewsWalkKernel path_views_variant[2][2][2] = {RTMI_COUNT_FAST(k_path_primary_views), RTMI_COUNT_FAST(k_path_slow_views)};
+static const ViewsWalkKernel path_views_variant[3][2][2] = {RTMI_COUNT_FAST(k_path_primary_views), RTMI_COUNT_FAST(k_path_slow_views),
+                                                            RTMI_COUNT_FAST(k_path_primary_views_cull)};
 
 static void launch_trace(rtmi_scene* s, Work& w, hipStream_t st, const float4* qo, const float4* qd, int pass, bool count, hipEvent_t stop) {
     // `stop` is recorded right after the closest-hit kernel, so that the event pair of the caller times exactly
@@ -2060,12 +2071,14 @@ static SlowQ slow_queue(rtmi_scene* s, Work& w) {
 static void launch_path(rtmi_scene* s, Work& w, hipStream_t st, dim3 grid, const OctArgs& a, int refill, int xcd, bool slow,
                         bool count, Samp mode, const uint32_t* list, const ViewTab& vt) {
     const bool fast = (s->options & RTMI_OPT_FAST) != 0;
+    // a scene with node cull records (and so with a direction table) gets the primary kernels that use them (trace_oct.hpp)
+    const int k = slow ? 1 : (s->d.fcull && s->primary_node_cull ? 2 : 0);
     if (mode == Samp::VIEWS)
-        hipLaunchKernelGGL(path_views_variant[slow][count][fast], grid, dim3(64), oct_launch_lds(s, count), st, s->d, a, w.ctrl.p, refill, xcd, vt);
+        hipLaunchKernelGGL(path_views_variant[k][count][fast], grid, dim3(64), oct_launch_lds(s, count), st, s->d, a, w.ctrl.p, refill, xcd, vt);
     else if (mode == Samp::LIST)
-        hipLaunchKernelGGL(path_list_variant[slow][count][fast], grid, dim3(64), oct_launch_lds(s, count), st, s->d, a, w.ctrl.p, refill, xcd, list);
+        hipLaunchKernelGGL(path_list_variant[k][count][fast], grid, dim3(64), oct_launch_lds(s, count), st, s->d, a, w.ctrl.p, refill, xcd, list);
     else
-        hipLaunchKernelGGL(path_variant[slow][mode == Samp::PASS][count][fast], grid, dim3(64), oct_launch_lds(s, count), st, s->d, a, w.ctrl.p, refill, xcd);
+        hipLaunchKernelGGL(path_variant[k][mode == Samp::PASS][count][fast], grid, dim3(64), oct_launch_lds(s, count), st, s->d, a, w.ctrl.p, refill, xcd);
 }
 // k_path_primary: the batch's primary rays generated, traced and shaded; the bounce rays go to queue 1, which pass 1 traces.
 // The mirror reflections it traces itself go on in queue 2 (ping-pong buffer 0, free until pass 1's k_shade appends to it).
@@ -2250,7 +2263,8 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
         pix_per_batch = max_sub_npix * 8 <= pix_per_batch * 9 ? max_sub_npix : (max_sub_npix + nb - 1) / nb;
     }
     pix_per_batch = std::min<uint64_t>(pix_per_batch, max_sub_npix);
-    if (pix_per_batch * per_pix >= (1ull << 31)) return fail(RTMI_ERR_UNSUPPORTED, "batch above 2^31 paths");
+    // (2^30: k_path_primary keeps a path's bounce and its certificate in the two bits above the path's index)
+    if (pix_per_batch * per_pix >= (1ull << 30)) return fail(RTMI_ERR_UNSUPPORTED, "batch above 2^30 paths");
     c.pix_per_batch = pix_per_batch;
     c.max_npix = max_sub_npix;
     for (uint32_t t = 0; t < nsub; t++) {
@@ -4256,6 +4270,29 @@ int rtmi_debug_cert_stats(const rtmi_scene_t* s, unsigned long long* out) {
     return RTMI_OK;
 }
 
+// Development aid (not in rtmi.h): the sign certificate alone, with its band as an argument (kappa = 0: CERT_KAPPA_PRIMARY,
+// the band of k_path_primary's node cull).  recs, rays, G: as for rtmi_debug_ray_cull; cert[i] <- ray i is certified;
+// ncand[i] (or NULL) <- length of its cell's list.  Needs no device.
+int rtmi_debug_ray_cert_kappa(const float* recs, uint64_t m, const float* rays, uint64_t n, uint32_t G, float kappa, uint8_t* cert,
+                              uint32_t* ncand) {
+    if (!recs || m < 1 || (n > 0 && (!rays || !cert)) || G < 8 || G > 1024) return fail(RTMI_ERR_INVALID, "NULL argument or G out of range");
+    RTMI_GUARD_BEGIN
+    if (kappa == 0.f) kappa = CERT_KAPPA_PRIMARY;
+    std::vector<float4> hp(2 * m);
+    memcpy(hp.data(), recs, m * 8 * sizeof(float));
+    std::vector<uint32_t> hcert;
+    CertStats st{};
+    if (!build_ray_cert(hp.data(), m, G, SIZE_MAX, hcert, st)) return fail(RTMI_ERR_UNSUPPORTED, "direction table too large");
+    for (uint64_t i = 0; i < n; i++) {
+        const float* v = rays + 8 * i;
+        uint32_t nc = 0;
+        cert[i] = ray_sign_certified(hcert.data(), make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), &nc, kappa) ? 1 : 0;
+        if (ncand) ncand[i] = nc;
+    }
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
 // Development aid (not in rtmi.h): a scene's node cull records: out[0..2] = records, bytes, build time in microseconds (all 0:
 // the node cull is off)
 int rtmi_debug_node_cull_stats(const rtmi_scene_t* s, unsigned long long* out) {
@@ -4272,8 +4309,19 @@ int rtmi_debug_node_cull_stats(const rtmi_scene_t* s, unsigned long long* out) {
 // octree form (call with every array NULL for it).  Every array may be NULL: records (4 words per inner record, the index
 // of `fnodes`) <- the packed node records; cert[i] <- ray i is certified; out[r n + i] <- bit 0: the half-line of ray i misses
 // the packed box of record r, bit 2: the walk culls the subtree of r for ray i (bit 0 and certified).  Needs no device.
+int rtmi_debug_node_cull_kappa(const rtmi_box_t* boxes, uint64_t nboxes, const uint32_t* tri_refs, uint64_t nrefs, uint64_t ntris,
+                               const float* recs, const float* rays, uint64_t n, uint32_t G, uint64_t* nrec, uint32_t* records, uint8_t* cert,
+                               uint8_t* out, float kappa);
 int rtmi_debug_node_cull(const rtmi_box_t* boxes, uint64_t nboxes, const uint32_t* tri_refs, uint64_t nrefs, uint64_t ntris, const float* recs,
                          const float* rays, uint64_t n, uint32_t G, uint64_t* nrec, uint32_t* records, uint8_t* cert, uint8_t* out) {
+    return rtmi_debug_node_cull_kappa(boxes, nboxes, tri_refs, nrefs, ntris, recs, rays, n, G, nrec, records, cert, out, CERT_KAPPA);
+}
+// ... and its twin with the certificate's band as an argument: kappa = 0 stands for CERT_KAPPA_PRIMARY, the band of
+// k_path_primary's node cull (trace_oct.hpp)
+int rtmi_debug_node_cull_kappa(const rtmi_box_t* boxes, uint64_t nboxes, const uint32_t* tri_refs, uint64_t nrefs, uint64_t ntris,
+                               const float* recs, const float* rays, uint64_t n, uint32_t G, uint64_t* nrec, uint32_t* records, uint8_t* cert,
+                               uint8_t* out, float kappa) {
+    if (kappa == 0.f) kappa = CERT_KAPPA_PRIMARY;
     if (!boxes || nboxes < 1 || !recs || ntris < 1 || !nrec || (nrefs > 0 && !tri_refs) || (n > 0 && !rays) || G < 8 || G > 1024)
         return fail(RTMI_ERR_INVALID, "NULL argument or G out of range");
     if (nboxes >= (1ull << 32) || nrefs >= (1ull << 32)) return fail(RTMI_ERR_UNSUPPORTED, "tree too large for 32-bit indices");
@@ -4301,7 +4349,7 @@ int rtmi_debug_node_cull(const rtmi_box_t* boxes, uint64_t nboxes, const uint32_
         if (!build_ray_cert(hp.data(), ntris, G, SIZE_MAX, hcert, st)) return fail(RTMI_ERR_UNSUPPORTED, "direction table too large");
         for (uint64_t i = 0; i < n; i++) {
             const float* v = rays + 8 * i;
-            ok[i] = ray_sign_certified(hcert.data(), make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7])) ? 1 : 0;
+            ok[i] = ray_sign_certified(hcert.data(), make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), nullptr, kappa) ? 1 : 0;
             if (cert) cert[i] = ok[i];
         }
     }

@@ -186,12 +186,19 @@ struct PrimHdr {
     Packet pk;
     unsigned long long q2[3];  // pass-2 queue: origins, directions, paths
     uint32_t minpl;            // least number of mirror lanes that a wave continues in place (65: never)
-    uint32_t pad;
+    // Node cull of the primary kernels: byte offset of DScene::fcull from DScene::fnodes (rtmi_scene_create keeps the node
+    // cull records behind the node records in one buffer), 0: no node cull.  Read in the SELECT step, where a pointer of
+    // its own would be two more scalar registers live over the whole loop.
+    uint32_t foff;
     // The last whole-list cull of the LEAF step: blocks [llo, lhi & 0x7FFFFFFF) of a list and, per reference (bit 4 j + k:
     // reference k of block llo + j), the references that survive it (fast build; bit 31 of lhi: the list ends among
     // these blocks) or that it culls (counting build: the range is emptied whenever the packet changes)
     unsigned long long lmask;
     uint32_t llo, lhi;
+    // The direction table (DScene::cert) for the certificate of a lane that takes a ray: read per lane where it is used,
+    // so that the table's addresses are vector arithmetic of the exchange step and hold no scalar register
+    unsigned long long cert;
+    unsigned long long pad;
 };
 #define PK_K 1e-5f  // relative slack: ~170 x the float rounding of any bound below
 // One ray of the packet: its spreads against the reference.  False: this ray turns culling off for the packet (nonzero
@@ -322,6 +329,9 @@ __host__ __device__ inline bool packed_block_miss(uint4 c, float ox, float oy, f
 // without a hit: the SELECT step that first visits the box marks its frame done instead of choosing a child, which is the
 // state that walk leaves behind.  The reference's collides() would have entered the box -- it walks boxes behind the
 // origin too -- but nothing it does there reaches the result.
+// The primary kernels of such a scene (k_path_primary*_cull, PNCULL below) do the same for primary rays and for the mirror
+// reflections they trace in place: the camera is outside the scene, and most of the cubes a primary ray crosses hold
+// nothing near it.  Their certificate has a band of its own (CERT_KAPPA_PRIMARY) and sits in bit 30 of `path`.
 
 // ---- Sign certificate per ray (W_TRACE; rtmi_debug_ray_cert runs the same function on the host).  norm . dir belongs to the
 // ray and the triangle, not to the block: rtmi_scene_create bins the scene's distinct normals by direction cell (a cube map
@@ -331,6 +341,13 @@ __host__ __device__ inline bool packed_block_miss(uint4 c, float ox, float oy, f
 #define CERT_TAU 1e-4     // an unlisted normal has |u . d| > tau |d|_1 for every direction of the cell
 #define CERT_KAPPA 1e-6f  // a listed normal must have |den| > kappa |n|_1 |d|_1 (rounding of den: < 4e-7 of that product)
 #define CERT_CAP 64u      // a longer list refuses the ray
+// The band of k_path_primary's certificate (DESIGN.md 4.1 "Node cull for primary rays"): den of a listed normal is known bit
+// for bit, so the band has nothing to absorb; it only has to keep t = num / den and every d_k * t finite, which any kappa
+// above 6e-14 does.  The 64 samples of a pixel share a wave and a table cell: the wide band refuses one lane in every other
+// pixel packet, and that lane then walks what the other 63 skip.
+#ifndef CERT_KAPPA_PRIMARY  // (RTMI_DEVDEFS=-DCERT_KAPPA_PRIMARY=1e-6f builds the comparison of DESIGN.md 4.1)
+#define CERT_KAPPA_PRIMARY 1e-9f
+#endif
 // The table cell of a direction that block_cull_ray() accepts
 __host__ __device__ inline uint32_t ray_cert_cell(uint32_t G, float4 d) {
     const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
@@ -346,7 +363,8 @@ __host__ __device__ inline uint32_t ray_cert_cell(uint32_t G, float4 d) {
 // True: the ray may use the block cull -- block_cull_ray() accepts it and the plane test's den, evaluated here in the kernel's
 // own operation order for every listed normal, is nonzero with margin; with the table's guarantee for the unlisted ones every
 // triangle of the scene then has a nonzero den and a finite t for this ray.  *ncand <- length of the cell's list (host only).
-__host__ __device__ inline bool ray_sign_certified(const uint32_t* __restrict__ cert, float4 o, float4 d, uint32_t* ncand = nullptr) {
+__host__ __device__ inline bool ray_sign_certified(const uint32_t* __restrict__ cert, float4 o, float4 d, uint32_t* ncand = nullptr,
+                                                   float kappa = CERT_KAPPA) {
     if (ncand) *ncand = 0u;
     if (!block_cull_ray(o, d)) return false;
     const uint32_t cell = ray_cert_cell(cert[0], d);
@@ -357,7 +375,7 @@ __host__ __device__ inline bool ray_sign_certified(const uint32_t* __restrict__ 
     const uint32_t* const i32 = cert + cert[1];
     const float4* const nrm = reinterpret_cast<const float4*>(cert + cert[2]);
     const bool wide = cert[3] != 0u;
-    const float kd1 = CERT_KAPPA * ((fabsf(d.x) + fabsf(d.y)) + fabsf(d.z));
+    const float kd1 = kappa * ((fabsf(d.x) + fabsf(d.y)) + fabsf(d.z));
     const float qd = 0.f * d.w;
     bool ok = true;
     for (uint32_t k = beg; k < end; k++) {
@@ -368,9 +386,15 @@ __host__ __device__ inline bool ray_sign_certified(const uint32_t* __restrict__ 
     return ok;
 }
 
+__device__ __attribute__((noinline)) bool primary_ray_certified(const uint32_t* cert, float4 o, float4 d) {
+    return ray_sign_certified(cert, o, d, nullptr, CERT_KAPPA_PRIMARY);
+}
+
 // S: the batch's sampling mode (W_PRIMARY / W_SLOW; Samp::LIST takes the batch's pixels from `list`, path_pixel, shade.hpp;
 // Samp::VIEWS each pixel's camera and seed from `vt`, pixel_key)
-template <bool COUNT, bool FAST, int MODE, Samp S = Samp::FRAME>
+// PNCULL (W_PRIMARY): the node cull of the primary kernels (k_path_primary*_cull); false: the walk without it, instruction for
+// instruction
+template <bool COUNT, bool FAST, int MODE, Samp S = Samp::FRAME, bool PNCULL = false>
 __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCtrl* __restrict__ ctrl, uint32_t* __restrict__ lds,
                                          int refill_min, int xcd_aware, const RecArgs& rec = RecArgs{},
                                          const uint32_t* __restrict__ list = nullptr, const ViewTab& vt = ViewTab{},
@@ -390,7 +414,8 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     const float4* __restrict__ qd = MODE == W_SLOW ? a.slow.d : a.qd;
     if (MODE == W_SLOW) refill_min = 1;
     // W_PRIMARY / W_SLOW: the path this lane works for (slot of its sample colour); W_PRIMARY keeps the bounce (0, or 1 for
-    // a mirror reflection traced in place) in bit 31 -- a batch has < 2^31 paths -- instead of in one more loop-carried register
+    // a mirror reflection traced in place) in bit 31 and, with the node cull, the ray's certificate in bit 30 -- a batch has
+    // < 2^30 paths -- instead of in more loop-carried registers
     uint32_t path = 0;
     uint32_t bounce = 0;  // W_SLOW: bounces the path has behind it = the reference's maxdepth - depth of the ray being traced
     uint32_t ncont = 0;   // W_SLOW: rays this lane cast that no queue counted (the "Rays" statistic)
@@ -411,9 +436,22 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     // whose node record the half-line misses, then what the fast build saves -- SELECT lane-steps and leaf visits inside a
     // missed subtree (the step that finds the miss not included) -- and violations (a hit taken inside a missed subtree:
     // must stay 0)
+    // dbg[38..44] (W_PRIMARY, node cull, primary rays) and dbg[45..51] (the mirror reflections it traces in place): lanes
+    // certified, lanes refused, then the five of dbg[33..37]
     unsigned long long dbg[RTMI_NDBG] = {};
-    // COUNT, W_TRACE: depth of the box at which the missed subtree this lane walks began (-1: it is in none)
+    // COUNT, W_TRACE / W_PRIMARY: depth of the box at which the missed subtree this lane walks began (-1: it is in none)
     int mlvl = -1;
+    // The node cull of W_PRIMARY (PNC_BIT of `path`: this lane's ray holds the certificate; a batch has < 2^30 paths)
+    constexpr bool PNC = MODE == W_PRIMARY && PNCULL;
+    constexpr uint32_t PNC_BIT = 0x40000000u;
+    // (wave-uniform; read from the LDS header where it is used, not kept in a register since the kernel's start.  It is
+    // never 0 in these kernels; the branches on it are kept because hipcc's register allocation is at its edge here: without
+    // them the running best `gt` is spilled and reloaded inside the SELECT and LEAF steps)
+    const uint32_t* const lds_hdr = lds;
+    auto pnc_off = [&]() {
+        return (uint32_t)__builtin_amdgcn_readfirstlane((int)reinterpret_cast<const volatile PrimHdr*>(lds_hdr)->foff);
+    };
+    auto pnc_count = [&](int k) { if (path >> 31) dbg[45 + k]++; else dbg[38 + k]++; };
     const unsigned long long t_begin = COUNT ? __builtin_amdgcn_s_memtime() : 0ull;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     const float root_half = sc.root_half;
@@ -464,6 +502,10 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
         if (lane == 0) {
             hdr->q2[0] = (unsigned long long)a.b2qo; hdr->q2[1] = (unsigned long long)a.b2qd; hdr->q2[2] = (unsigned long long)a.b2qpath;
             hdr->minpl = a.minpl ? (uint32_t)a.minpl : 65u;
+            if (PNC) {  // (launched only for scenes with node cull records, rtmi_device.hip launch_path)
+                hdr->cert = (unsigned long long)sc.cert;
+                hdr->foff = (uint32_t)(reinterpret_cast<const char*>(sc.fcull) - reinterpret_cast<const char*>(sc.fnodes));
+            }
             if (COUNT) { hdr->llo = 0u; hdr->lhi = 0u; }
         }
         lds += sizeof(PrimHdr) / 4;
@@ -477,6 +519,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     unsigned long long bcm = 0ull;
     auto take_leaf = [&](float t, uint32_t tf) {  // a finished leaf's hit into the frame and the running best
         if (COUNT && MODE == W_TRACE && mlvl >= 0) dbg[37]++;  // the node predicate was wrong: must never happen
+        if (COUNT && PNC && mlvl >= 0) pnc_count(6);
         if (!(fw & O_HAS) || t < ft) ft = t;
         fw |= O_HAS;
         if (!ghave || t < gt) { gt = t; gtf = tf; }
@@ -496,7 +539,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
             bool start = false;     // this lane begins a new ray below
             bool inplace = false;   // W_PRIMARY (wave-uniform): this wave continues its mirror paths, no refill
             float4 no = make_float4(0.f, 0.f, 0.f, 0.f), nd = make_float4(0.f, 0.f, 1.f, 0.f);
-            const uint32_t pth = MODE == W_PRIMARY ? path & 0x7FFFFFFFu : path, bnc = MODE == W_PRIMARY ? path >> 31 : bounce;
+            const uint32_t pth = MODE == W_PRIMARY ? path & (PNC ? PNC_BIT - 1u : 0x7FFFFFFFu) : path, bnc = MODE == W_PRIMARY ? path >> 31 : bounce;
             uint32_t npath = pth, nbounce = bnc;
             if (!QUEUE) {
                 bool push = false;  // W_PRIMARY: the path goes on -> its bounce ray is queued for pass bounce + 1
@@ -666,6 +709,16 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
             if (!QUEUE && start) {  // one place where a path kernel's lane takes a ray: bounce in place, or refill
                 if (MODE != W_SLOW) r = make_rayk(no, nd);
                 path = MODE == W_PRIMARY ? npath | (nbounce << 31) : npath; bounce = nbounce;
+                if constexpr (PNC) {
+                    // the certificate of this lane's ray (a primary ray, or a mirror reflection started in place), kept in a
+                    // spare bit of `path`: no register of its own across the steps
+                    if (pnc_off() != 0u) {
+                        const uint32_t* const ct = reinterpret_cast<const uint32_t*>(reinterpret_cast<const volatile PrimHdr*>(lds_hdr)->cert);
+                        const bool cb = primary_ray_certified(ct, make_float4(r.ox, r.oy, r.oz, r.ow), make_float4(r.dx, r.dy, r.dz, r.dw));
+                        path |= cb ? PNC_BIT : 0u;
+                        if (COUNT) { pnc_count(cb ? 0 : 1); mlvl = -1; }
+                    }
+                }
                 fnode = 0; fw = 0; ft = 0.f; lvl = 0;
                 ghave = false; gt = 0.f; gtf = 0;
                 if (MEMO) memo[0] = 0xFFFFFFFFu;
@@ -701,7 +754,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                         fw |= O_HAS;
                     }
                 }
-                if (COUNT && MODE == W_TRACE && lvl < mlvl) mlvl = -1;  // back above the box where the missed subtree began
+                if (COUNT && (MODE == W_TRACE || PNC) && lvl < mlvl) mlvl = -1;  // back above the box where the missed subtree began
                 if (fw & O_DONE) {  // the root frame is finished: the ray is
                     if (QUEUE) {
                         if constexpr (MODE == W_RECORD) {
@@ -736,6 +789,25 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                                     if (miss) { dbg[34]++; mlvl = lvl; }
                                 }
                             } else ncut = miss;
+                        }
+                    }
+                    // ... and the same for a certified lane of W_PRIMARY (the bit of `path`; CERT_KAPPA_PRIMARY).  The result is
+                    // not carried to `ok` in a register of its own (k_path_primary has none to give): a missed box gets every
+                    // octant marked visited, so the step finds no candidate, `ok` is false and the frame is done -- the visited
+                    // bits of a finished frame are never read again.
+                    if constexpr (PNC) {
+                        const uint32_t foff = pnc_off();
+                        if (foff != 0u) {
+                            const uint4 nc = ld_off32(sc.fnodes, foff + (fnode << 4));
+                            const bool first = ((path & PNC_BIT) != 0u) & ((fw & 0xFFu) == 0u);
+                            const bool miss = first & packed_block_miss(nc, r.ox, r.oy, r.oz, r.ix, r.iy, r.iz);
+                            if (COUNT) {
+                                if (mlvl >= 0) pnc_count(4);
+                                else if (first) {
+                                    pnc_count(2);
+                                    if (miss) { pnc_count(3); mlvl = lvl; }
+                                }
+                            } else fw |= miss ? 0xFFu : 0u;
                         }
                     }
                     const float cx = __uint_as_float(q0.x), cy = __uint_as_float(q0.y), cz = __uint_as_float(q0.z);
@@ -813,6 +885,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                             if (COUNT) cnt[4]++;
                             if (COUNT && MEMO) dbg[12]++;
                             if (COUNT && MODE == W_TRACE && mlvl >= 0) dbg[36]++;
+                            if (COUNT && PNC && mlvl >= 0) pnc_count(5);
                             if (MEMO && memo[0] == lblock) {  // the list this ray scanned last: its result, no LEAF steps
                                 const uint32_t mtf = memo[2 * NT];
                                 if (mtf != 0u) take_leaf(__uint_as_float(memo[NT]), mtf);
@@ -1057,8 +1130,12 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                     const volatile PrimHdr* const vh = hdr;
                     // counting build: a block that the last list mask covers (past the block it started at) is not culled again
                     if (!COUNT || !(lb0 > rf(vh->llo) && lb0 < rf(vh->lhi))) {
-                        uint32_t ln;  // (computed here: hipcc would otherwise keep lane >> 2, lane & 3 live over the whole loop)
-                        asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(lane));
+                        // the lane's number, computed here: hipcc would otherwise keep lane >> 2, lane & 3 live over the whole loop
+                        // (and counted, not copied from `lane`: a register the walk gives up elsewhere must not come back
+                        // from scratch in this step)
+                        uint32_t ln;
+                        if constexpr (PNC) asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+                        else asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(lane));
                         // one word per lane (the array has 15 zero blocks behind its last one: no bounds test)
                         const uint32_t w = ld_off32(oref, ((lb0 + (ln >> 2)) << 4) + ((ln & 3u) << 2));
                         const uint32_t id = w & 0x7FFFFFFFu;
@@ -1195,6 +1272,13 @@ __global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_primary(DScene sc,
     extern __shared__ uint32_t lds[];
     oct_walk<COUNT, FAST, W_PRIMARY>(sc, a, ctrl, lds, refill_min, xcd_aware);
 }
+// k_path_primary with the node cull (scenes with node cull records, RTMI_PRIMARY_NODE_CULL != 0); a kernel of its own, so
+// that every other scene runs k_path_primary as it was
+template <bool COUNT, bool FAST>
+__global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_primary_cull(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min, int xcd_aware) {
+    extern __shared__ uint32_t lds[];
+    oct_walk<COUNT, FAST, W_PRIMARY, Samp::FRAME, true>(sc, a, ctrl, lds, refill_min, xcd_aware);
+}
 template <bool COUNT, bool FAST>
 __global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_slow(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min, int xcd_aware) {
     extern __shared__ uint32_t lds[];
@@ -1205,6 +1289,12 @@ template <bool COUNT, bool FAST>
 __global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_primary_samples(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min, int xcd_aware) {
     extern __shared__ uint32_t lds[];
     oct_walk<COUNT, FAST, W_PRIMARY, Samp::PASS>(sc, a, ctrl, lds, refill_min, xcd_aware);
+}
+template <bool COUNT, bool FAST>
+__global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_primary_samples_cull(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min,
+                                                                                   int xcd_aware) {
+    extern __shared__ uint32_t lds[];
+    oct_walk<COUNT, FAST, W_PRIMARY, Samp::PASS, true>(sc, a, ctrl, lds, refill_min, xcd_aware);
 }
 template <bool COUNT, bool FAST>
 __global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_slow_samples(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min, int xcd_aware) {
@@ -1220,6 +1310,12 @@ __global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_primary_list(DScen
     oct_walk<COUNT, FAST, W_PRIMARY, Samp::LIST>(sc, a, ctrl, lds, refill_min, xcd_aware, RecArgs{}, list);
 }
 template <bool COUNT, bool FAST>
+__global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_primary_list_cull(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min,
+                                                                                int xcd_aware, const uint32_t* __restrict__ list) {
+    extern __shared__ uint32_t lds[];
+    oct_walk<COUNT, FAST, W_PRIMARY, Samp::LIST, true>(sc, a, ctrl, lds, refill_min, xcd_aware, RecArgs{}, list);
+}
+template <bool COUNT, bool FAST>
 __global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_slow_list(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min, int xcd_aware,
                                                                         const uint32_t* __restrict__ list) {
     extern __shared__ uint32_t lds[];
@@ -1232,6 +1328,12 @@ __global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_primary_views(DSce
                                                                             int xcd_aware, ViewTab vt) {
     extern __shared__ uint32_t lds[];
     oct_walk<COUNT, FAST, W_PRIMARY, Samp::VIEWS>(sc, a, ctrl, lds, refill_min, xcd_aware, RecArgs{}, nullptr, vt);
+}
+template <bool COUNT, bool FAST>
+__global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_primary_views_cull(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min,
+                                                                                 int xcd_aware, ViewTab vt) {
+    extern __shared__ uint32_t lds[];
+    oct_walk<COUNT, FAST, W_PRIMARY, Samp::VIEWS, true>(sc, a, ctrl, lds, refill_min, xcd_aware, RecArgs{}, nullptr, vt);
 }
 template <bool COUNT, bool FAST>
 __global__ void __launch_bounds__(64, RTMI_PATH_WAVES) k_path_slow_views(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min,

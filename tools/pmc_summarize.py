@@ -19,6 +19,8 @@ for f in glob.glob(os.path.join(root, "**", "*counter_collection.csv"), recursiv
         if not k.startswith("k_"):
             continue
         k = k.split("<")[0]
+        if k.endswith("_cull"):  # k_path_primary*_cull: the primary kernel of a scene with node cull records (bench.py reads k_path_primary)
+            k = k[:-5]
         tot[k][r["Counter_Name"]] += float(r["Counter_Value"])
         calls[k][r["Counter_Name"]] += 1
         try:

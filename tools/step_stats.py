@@ -19,8 +19,8 @@ print(ctx.stats)
 # the resident scene handle lives inside the C++ caster; fetch the debug counters through a tiny helper
 lib = _ffi.lib()
 lib.rth_debug_counters_n.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-out = (C.c_ulonglong * 38)()
-lib.rth_debug_counters_n(scene.h, out, 38)
+out = (C.c_ulonglong * 52)()
+lib.rth_debug_counters_n(scene.h, out, 52)
 d = list(out)
 names = ["S steps", "S lanes", "L steps", "L lanes", "refills", "refill lanes", "edge blocks", "edge lanes", "S cycles", "L cycles", "refill cycles", "wave cycles",
          "leaf visits", "memo hits", "planes skipped", "edges skipped",
@@ -30,6 +30,8 @@ names = ["S steps", "S lanes", "L steps", "L lanes", "refills", "refill lanes", 
          "cull blocks", "box missed", "blocks culled", "lists culled", "cull violations",
          "cull rays", "rays refused",
          "nodes seen", "nodes missed", "S lanes in missed", "leaves in missed", "node violations"]
+for who in ("prim", "refl"):
+    names += [f"{who} {x}" for x in ("certified", "refused", "nodes seen", "nodes missed", "S in missed", "leaves in missed", "violations")]
 for n, v in zip(names, d):
     print(f"{n:14s} {v}")
 rays = ctx.stats["rays"]
@@ -79,3 +81,14 @@ ns = (C.c_ulonglong * 3)()
 lib.rth_debug_node_cull_stats.argtypes = [C.c_void_p, C.c_void_p]
 if lib.rth_debug_node_cull_stats(scene.h, ns) == 0:
     print(f"node cull records (0: none): {ns[0]}, {ns[1] / 1e6:.2f} MB, built in {ns[2] / 1e6:.3f} s")
+# dbg[38..44] / dbg[45..51]: the node cull of k_path_primary (RTMI_PRIMARY_NODE_CULL=0, RTMI_NODE_CULL=0 or no direction
+# table: all 0), for primary rays and for the mirror reflections it traces in place: lanes that took a ray with / without the
+# certificate (CERT_KAPPA_PRIMARY), then the five of dbg[33..37].  d[1] and d[12] count all passes: the shares below are of
+# the whole frame's SELECT lane-steps and leaf visits.
+for who, b in (("primary rays", 38), ("mirror reflections in place", 45)):
+    p = d[b:b + 7]
+    print(f"node cull (k_path_primary, {who}, RTMI_PRIMARY_NODE_CULL={os.environ.get('RTMI_PRIMARY_NODE_CULL', 'default')}): lanes "
+          f"certified {p[0]}, refused {p[1]} ({p[1] / max(p[0] + p[1], 1):.4f}); {p[2]} inner boxes first visited by certified lanes "
+          f"outside a missed subtree, missed {p[3]} ({p[3] / max(p[2], 1):.3f}); inside missed subtrees: {p[4]} SELECT lane-steps "
+          f"({p[4] / max(p[0] + p[1], 1):.1f} per ray, {p[4] / max(d[1], 1):.3f} of the frame's), {p[5]} leaf visits "
+          f"({p[5] / max(p[0] + p[1], 1):.1f} per ray, {p[5] / max(d[12], 1):.3f} of the frame's); violations {p[6]} (must be 0)")
