@@ -4293,6 +4293,28 @@ int rtmi_debug_ray_cert_kappa(const float* recs, uint64_t m, const float* rays, 
     RTMI_GUARD_END
 }
 
+// Development aid (not in rtmi.h): rtmi_debug_ray_cert_kappa with the list walked an entry at a time
+// (ray_sign_certified_ref): the referee of the batched walk.  Same arguments, same outputs.  Needs no device.
+int rtmi_debug_ray_cert_ref(const float* recs, uint64_t m, const float* rays, uint64_t n, uint32_t G, float kappa, uint8_t* cert,
+                            uint32_t* ncand) {
+    if (!recs || m < 1 || (n > 0 && (!rays || !cert)) || G < 8 || G > 1024) return fail(RTMI_ERR_INVALID, "NULL argument or G out of range");
+    RTMI_GUARD_BEGIN
+    if (kappa == 0.f) kappa = CERT_KAPPA_PRIMARY;
+    std::vector<float4> hp(2 * m);
+    memcpy(hp.data(), recs, m * 8 * sizeof(float));
+    std::vector<uint32_t> hcert;
+    CertStats st{};
+    if (!build_ray_cert(hp.data(), m, G, SIZE_MAX, hcert, st)) return fail(RTMI_ERR_UNSUPPORTED, "direction table too large");
+    for (uint64_t i = 0; i < n; i++) {
+        const float* v = rays + 8 * i;
+        uint32_t nc = 0;
+        cert[i] = ray_sign_certified_ref(hcert.data(), make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), &nc, kappa) ? 1 : 0;
+        if (ncand) ncand[i] = nc;
+    }
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
 // Development aid (not in rtmi.h): a scene's node cull records: out[0..2] = records, bytes, build time in microseconds (all 0:
 // the node cull is off)
 int rtmi_debug_node_cull_stats(const rtmi_scene_t* s, unsigned long long* out) {

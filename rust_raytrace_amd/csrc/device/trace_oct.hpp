@@ -360,11 +360,60 @@ __host__ __device__ inline uint32_t ray_cert_cell(uint32_t G, float4 d) {
     const uint32_t i = (uint32_t)(gi < 0 ? 0 : (gi >= (int)G ? (int)G - 1 : gi)), j = (uint32_t)(gj < 0 ? 0 : (gj >= (int)G ? (int)G - 1 : gj));
     return (face * G + i) * G + j;
 }
+// How the list is walked (DESIGN.md 4.1 "Sign certificate per ray", the list walk).  The result is an AND of independent
+// comparisons, so the batch size cannot change a bit of it; RTMI_DEVDEFS=-DCERT_BATCH=1 builds the comparison.
+#ifndef CERT_BATCH  // entries of a list in flight together: their indices in one round trip, their normals in the next
+#define CERT_BATCH 4  // (1: an entry at a time, two dependent round trips each; 8: k_trace_oct needs 92 VGPRs, 5 waves per SIMD)
+#endif
+// One listed normal against the ray: kd1 = kappa |d|_1, qd = 0 * d.w
+__host__ __device__ __forceinline__ bool cert_entry_ok(float4 n, float4 d, float qd, float kd1) {
+    const float den = (((0.f + n.x * d.x) + n.y * d.y) + n.z * d.z) + qd;  // `plane` of the LEAF step
+    return fabsf(den) > n.w * kd1;
+}
+// Entries [beg, end) of the index lists, CERT_BATCH at a time.  A slot past the end of the list repeats the list's last
+// entry: no index outside [beg, end) is read (the last list of the table ends where the index area ends), no normal is
+// read through a word that is not an index, and testing an entry twice leaves the AND what it was.
+template <bool WIDE>
+__host__ __device__ __forceinline__ bool cert_walk(const uint32_t* __restrict__ cert, uint32_t beg, uint32_t end, float4 d, float qd, float kd1) {
+    const uint32_t* const i32 = cert + cert[1];
+    const uint16_t* const i16 = reinterpret_cast<const uint16_t*>(i32);
+    const float4* const nrm = reinterpret_cast<const float4*>(cert + cert[2]);
+    bool ok = true;
+    // (left to itself hipcc vectorizes this loop 32 wide: k_trace_oct then needs 128 VGPRs and 1.2 KB of scratch)
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+    for (uint32_t k = beg; k < end; k += CERT_BATCH) {
+        uint32_t ix[CERT_BATCH];
+        float4 n[CERT_BATCH];
+#pragma unroll
+        for (uint32_t j = 0; j < CERT_BATCH; j++) {
+            const uint32_t kj = k + j < end ? k + j : end - 1u;
+            ix[j] = WIDE ? i32[kj] : (uint32_t)i16[kj];
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < CERT_BATCH; j++) n[j] = nrm[ix[j]];
+#pragma unroll
+        for (uint32_t j = 0; j < CERT_BATCH; j++) ok &= cert_entry_ok(n[j], d, qd, kd1);
+    }
+    return ok;
+}
 // True: the ray may use the block cull -- block_cull_ray() accepts it and the plane test's den, evaluated here in the kernel's
 // own operation order for every listed normal, is nonzero with margin; with the table's guarantee for the unlisted ones every
 // triangle of the scene then has a nonzero den and a finite t for this ray.  *ncand <- length of the cell's list (host only).
-__host__ __device__ inline bool ray_sign_certified(const uint32_t* __restrict__ cert, float4 o, float4 d, uint32_t* ncand = nullptr,
+__host__ __device__ __forceinline__ bool ray_sign_certified(const uint32_t* __restrict__ cert, float4 o, float4 d, uint32_t* ncand = nullptr,
                                                    float kappa = CERT_KAPPA) {
+    if (ncand) *ncand = 0u;
+    if (!block_cull_ray(o, d)) return false;
+    const uint32_t cell = ray_cert_cell(cert[0], d);
+    const uint32_t beg = cert[4u + cell], end = cert[5u + cell];
+    if (ncand) *ncand = end - beg;
+    if (end - beg > CERT_CAP) return false;
+    const float kd1 = kappa * ((fabsf(d.x) + fabsf(d.y)) + fabsf(d.z));
+    const float qd = 0.f * d.w;
+    return cert[3] != 0u ? cert_walk<true>(cert, beg, end, d, qd, kd1) : cert_walk<false>(cert, beg, end, d, qd, kd1);
+}
+// The list walk as it was before the batches, an entry at a time: the referee of the walk above (rtmi_debug_ray_cert_ref,
+// tests/test_ray_cert_walk_cpu.py).  Host only.
+inline bool ray_sign_certified_ref(const uint32_t* cert, float4 o, float4 d, uint32_t* ncand = nullptr, float kappa = CERT_KAPPA) {
     if (ncand) *ncand = 0u;
     if (!block_cull_ray(o, d)) return false;
     const uint32_t cell = ray_cert_cell(cert[0], d);
@@ -380,12 +429,14 @@ __host__ __device__ inline bool ray_sign_certified(const uint32_t* __restrict__ 
     bool ok = true;
     for (uint32_t k = beg; k < end; k++) {
         const float4 n = nrm[wide ? i32[k] : (uint32_t)i16[k]];
-        const float den = (((0.f + n.x * d.x) + n.y * d.y) + n.z * d.z) + qd;  // `plane` of the LEAF step
+        const float den = (((0.f + n.x * d.x) + n.y * d.y) + n.z * d.z) + qd;
         ok &= fabsf(den) > n.w * kd1;
     }
     return ok;
 }
 
+// (One read of the list per pixel packet -- the lanes of a wave that share a cell load an entry each and hand the normals
+// round with v_readlane -- was built and measured: no gain, DESIGN.md 4.1.  Every lane walks its list.)
 __device__ __attribute__((noinline)) bool primary_ray_certified(const uint32_t* cert, float4 o, float4 d) {
     return ray_sign_certified(cert, o, d, nullptr, CERT_KAPPA_PRIMARY);
 }
