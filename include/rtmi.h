@@ -601,8 +601,9 @@ int rtmi_trace_device(rtmi_scene_t* scene, uint64_t n, const void* orig4_device,
  *     included (16 n, 16 n, 8 n; 16 n, and 16, 16, 16, 4 times n / G); keys == NULL and pixel0 + n / G - 1 >= 2^32;
  *   RTMI_ERR_UNSUPPORTED: n >= 2^31; maxdepth > 32; group > 65536; a guide buffer on a scene with analytic spheres.
  * Not here: the path kernels (pipeline 3) for explicit rays, several streams, rtmi_render_frame_multi, batches of views,
- * progressive or adaptive passes over explicit rays, built-in camera models, a denoised one-call wrapper (mean, albedo and normal
- * feed rtmi_denoise_device directly when the groups form an image). */
+ * progressive or adaptive passes over explicit rays, a denoised one-call wrapper (mean, albedo and normal feed
+ * rtmi_denoise_device directly when the groups form an image).  (Built-in thin-lens and orthographic cameras with progressive
+ * passes are rtmi_render_camera*, below; fisheye and panoramic cameras need sin / cos and stay with this call.) */
 enum { RTMI_RAYS_MAKE_RAY = 1u << 0 };
 typedef struct rtmi_rays {
     uint32_t maxdepth;  /* project_ray's depth, 0..32                                                            */
@@ -622,6 +623,87 @@ int rtmi_render_rays_device(rtmi_scene_t* scene, uint64_t n, const void* orig4_d
                             const rtmi_rays_out_t* out_device, void* hip_stream, rtmi_stats_t* stats);
 int rtmi_render_rays(rtmi_scene_t* scene, uint64_t n, const float* orig4, const float* dir4, const uint32_t* keys /* or NULL */,
                      uint64_t seed, const rtmi_rays_t* rays, const rtmi_rays_out_t* out_host, rtmi_stats_t* stats);
+
+/* Built-in camera models rendered on the device: rtmi_render_samples[_device] with a ray generator that is
+ * not only the reference's pinhole -- a thin lens (depth of field) and an orthographic camera -- and, optionally, the
+ * denoiser's guide buffers of the very same rays.  The rays never leave the device: nothing is generated, keyed, stored or
+ * folded by the caller.  The pinhole IS the reference's camera (Viewport::pixel_ray, raytrace.rs:1374-1394) and that mode is
+ * rtmi_render_samples_device bit for bit; the other two models are NOT part of the reference (it has one camera): build-defined,
+ * so what follows IS the definition, and tests/camera_ref.py pins it bit for bit.  Only + - * / and sqrt in f32 (all correctly
+ * rounded), every step rounded to f32 on all four lanes, no contraction, no transcendental function.
+ * Contract: rtmi_render_samples[_device]'s, word for word: samples [sample0, sample0 + nsamples) of every pixel of the tile of
+ * a frame of S = vp->samples_per_pixel samples; accum (one float4 per pixel of the tile) is read only when sample0 > 0 and
+ * always rewritten; out (optional, never the same buffer as accum) = accum * (1/(sample0 + nsamples)); passes must be issued
+ * in sample order, each continuing the previous one on the same accum; striped tiles, streams, sub-tiles and batches apply
+ * unchanged and no tuning changes a bit; maxdepth == 0 writes zeros to accum and out.
+ * The ray of (row, col, sample), with pixel = row * width + col, orig / cam / vu / vv the viewport's vectors with lane 3 = +0,
+ * and vadd, vsub, vmul (vector * scalar), vunit (the ordered four-lane dot (((0 + x x) + y y) + z z) + w w, r = sqrt(.),
+ * v * (1.f / r)), make_ray(o, d) = (o, vunit(d)) the reference's Vec3 operations (raytrace.rs:22-122, :201-210):
+ *   p = pixel_ray's image-plane point px_u, computed exactly as rtmi_render_samples_device computes it:
+ *       vu_delta = vmul(vu, 1.f / (float)width);  vv_delta = vmul(vv, 1.f / (float)height);
+ *       (u_off, v_off) = (0.5f, 0.5f) when S == 1, else the unit floats of words 0 and 1 of RNG block 0 of (seed, pixel, sample);
+ *       p = vadd(vadd(orig, vmul(vu_delta, (float)col + u_off)), vmul(vv_delta, (float)row + v_off)).
+ *   RTMI_CAMERA_PINHOLE:   make_ray(p, vunit(vsub(p, cam))): pixel_ray itself.
+ *   RTMI_CAMERA_ORTHO:     c = vadd(vadd(orig, vmul(vu, 0.5f)), vmul(vv, 0.5f))   (the centre of the image plane);
+ *                          axis = vunit(vsub(c, cam));  the ray is make_ray(p, axis).
+ *     The image covers the image-plane rectangle itself, every ray parallel to the camera's axis.  An axis-aligned
+ *     orthographic view makes EVERY ray a ray with exactly-zero direction components: the reference's expensive case
+ *     (BoundingBox::collides skips that axis' slab, raytrace.rs:872-900, ~150 x the work of an ordinary ray), which the
+ *     per-pass pipeline traces in place.  Tilt the camera by a hair when that cost matters.
+ *   RTMI_CAMERA_THIN_LENS: lens axes eu = vunit(vu), ev = vunit(vv).
+ *     Lens sample (x, y): for k = 0, 1 let w = RNG block 0x40000000 | k of (seed, pixel, sample); for j = 0, 1 the candidate
+ *       x = 2.f * u(w[2 j]) - 1.f,  y = 2.f * u(w[2 j + 1]) - 1.f      (u = top 24 bits * 2^-24; a product, then a difference);
+ *       the first candidate, in the order (k, j) = (0, 0), (0, 1), (1, 0), (1, 1), with (x * x) + (y * y) <= 1.f is taken.  If all
+ *       four fail the sample is (0.f, 0.f): the pinhole's ray.  That happens with probability (1 - pi/4)^4 ~ 0.0021, a
+ *       slight, stated over-weighting of the lens centre.  Blocks 0x40000000 | k are used by nothing else (bounces draw blocks
+ *       1..32, rtmi_render_ao* 0x80000000 | k, the lights 0xC0000000 | k).
+ *     o = vadd(vmul(eu, x * lens_radius), vmul(ev, y * lens_radius))          (the point on the lens, relative to cam)
+ *     e = vsub(p, cam);   F = vadd(cam, vmul(e, focus))                        (the point in focus)
+ *     O = vadd(p, vmul(o, 1.f - 1.f / focus))       (where the lens ray crosses the image plane: rays start where the
+ *                                                    reference's start, so what lies between eye and image plane stays unseen)
+ *     the ray is make_ray(O, vunit(vsub(F, vadd(cam, o)))).
+ *     lens_radius == 0.f runs the same arithmetic (it is not special-cased): the pinhole's picture, though signs of zero in
+ *     the origin may differ from the pinhole's.  ORTHO and PINHOLE ignore lens_radius and focus.
+ *   The RNG key of the path's bounces is unchanged: (seed, pixel, sample), blocks 1.. as in every render call.
+ * Guides (rtmi_camera_out_t, or a NULL pointer for none; each buffer may be NULL): rtmi_render_features*'s albedo, normal
+ * and ids (same layout, same arithmetic) for the samples of THIS call, computed by k_features from the hit records of pass 0,
+ * i.e. from the very rays that are shaded.  They are not continued across calls.  They do not depend on vp->maxdepth: with
+ * maxdepth == 0 the primary rays are traced for them alone.  Refused with RTMI_ERR_UNSUPPORTED on a scene with analytic
+ * spheres, as rtmi_render_features* is; the colours are not.
+ * Scenes: every kind rtmi_render takes, each with its own mode's hits.
+ * How: always the per-pass pipeline (rtmi_tuning_t.pipeline is not consulted: k_path_primary's packet culls assume that the
+ * samples of a pixel share one origin, and a lens breaks that).  Per batch k_gen_camera stands where k_gen_samples stands;
+ * then per pass the scene's closest-hit launch and k_shade_samples, k_features after pass 0 when a guide is asked for, and
+ * k_accum_samples.  Nothing new persists on the handle.
+ * stats: as rtmi_render_samples_device fills them, pipeline = 1, slow_paths = 0, trace_launches = passes x batches (with
+ * maxdepth == 0 and a guide: the features call's stats, rays = pixels * nsamples).
+ * Checks, all before any HIP call and before the scene is used, stats cleared: everything rtmi_render_samples_device refuses
+ * (a NULL scene, viewport, tile or accum; accum == out; nsamples == 0; sample0 + nsamples > S; the viewport and tile checks);
+ * RTMI_ERR_INVALID for a NULL camera, an unknown model, non-zero flags, THIN_LENS with lens_radius negative or not finite or
+ * focus not finite and > 0, and a guide buffer that is the same buffer as another buffer of the call.  An empty tile returns
+ * RTMI_OK and touches nothing.
+ * The device variant enqueues on hip_stream like rtmi_render_samples_device.  The host variant renders rows [row0, row0 +
+ * nrows), copies accum in (only when sample0 > 0) and accum, out and the guides out.
+ * Not here: fisheye and panoramic models (sin / cos cannot be pinned bit for bit; rtmi_render_rays* renders them), adaptive
+ * passes, batches of views and rtmi_render_frame_multi for these cameras, a path-kernel (pipeline 3) variant, AO, light,
+ * shadowed or preview calls through a lens. */
+enum { RTMI_CAMERA_PINHOLE = 0, RTMI_CAMERA_THIN_LENS = 1, RTMI_CAMERA_ORTHO = 2 };
+typedef struct rtmi_camera {
+    uint32_t model;        /* RTMI_CAMERA_*                                                                              */
+    uint32_t flags;        /* must be 0                                                                                  */
+    float    lens_radius;  /* THIN_LENS: world units, >= 0, finite                                                       */
+    float    focus;        /* THIN_LENS: distance of the plane in focus from the eye, in units of the image plane's
+                              distance from the eye (> 0, finite; 1 = the image plane)                                   */
+} rtmi_camera_t;           /* 16 bytes */
+typedef struct rtmi_camera_out { void *albedo, *normal, *ids; } rtmi_camera_out_t;  /* each may be NULL */
+void rtmi_camera_defaults(rtmi_camera_t* camera);  /* PINHOLE, 0, 0.f, 1.f */
+int rtmi_render_camera_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile,
+                              const rtmi_camera_t* camera, uint32_t sample0, uint32_t nsamples, void* accum_device,
+                              void* out_device /* or NULL */, const rtmi_camera_out_t* guides /* or NULL */, void* hip_stream,
+                              rtmi_stats_t* stats);
+int rtmi_render_camera(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
+                       const rtmi_camera_t* camera, uint32_t sample0, uint32_t nsamples, float* accum_host,
+                       float* out_host /* or NULL */, const rtmi_camera_out_t* guides_host /* or NULL */, rtmi_stats_t* stats);
 
 /* Ambient occlusion rendered on the device: one f32 per pixel, the share of K hemisphere rays per primary
  * sample that reach `radius` unoccluded -- a shaded preview, a contact-shadow layer, a guide image.  NOT part of the reference,

@@ -165,6 +165,16 @@ int rth_caster_walk_shadowed_device(rth_scene_t* s, uint32_t w, uint32_t h, cons
                                     const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, const rtmi_light_t* light,
                                     void* accum_device, void* out_device, void* hip_stream, rtmi_stats_t* stats,
                                     double* wall_seconds);
+/* Built-in camera models (rtmi_render_camera / rtmi_render_camera_device in rtmi.h, which defines them):
+ * rth_caster_walk_samples[_device] in every respect, with the rays of `camera` (pinhole, thin lens, orthographic) and, when
+ * guides is not NULL, rth_caster_walk_features' buffers of those rays. */
+int rth_caster_walk_camera(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp, uint64_t row0,
+                           uint64_t nrows, const rtmi_camera_t* camera, uint32_t sample0, uint32_t nsamples, float* accum_host,
+                           float* out_host, const rtmi_camera_out_t* guides_host, rtmi_stats_t* stats, double* wall_seconds);
+int rth_caster_walk_camera_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                                  const rtmi_tile_t* tile, const rtmi_camera_t* camera, uint32_t sample0, uint32_t nsamples,
+                                  void* accum_device, void* out_device, const rtmi_camera_out_t* guides, void* hip_stream,
+                                  rtmi_stats_t* stats, double* wall_seconds);
 /* The shaded preview (rtmi_render_preview / rtmi_render_preview_device, which rtmi.h defines) on the scene's resident copy:
  * albedo, ambient occlusion and up to four coloured box lights composed per sample, with the layers `out` asks for.  maxdepth
  * is not consulted; the primary rays use the caster's seed. */

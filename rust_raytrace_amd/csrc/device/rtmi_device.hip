@@ -49,6 +49,7 @@ static_assert(sizeof(rtmi_stats_t) == 128 && sizeof(rtmi_tuning_t) == 48 && size
 static_assert(sizeof(rtmi_adaptive_t) == 32 && offsetof(rtmi_adaptive_t, samples) == 24, "ABI struct layout changed");
 static_assert(sizeof(rtmi_denoise_t) == 24 && offsetof(rtmi_denoise_t, sigma_color) == 8, "ABI struct layout changed");
 static_assert(sizeof(rtmi_ao_t) == 16 && offsetof(rtmi_ao_t, radius) == 8, "ABI struct layout changed");
+static_assert(sizeof(rtmi_camera_t) == 16 && offsetof(rtmi_camera_t, lens_radius) == 8 && sizeof(rtmi_camera_out_t) == 3 * sizeof(void*), "ABI struct layout changed");
 static_assert(sizeof(rtmi_light_t) == 28 && offsetof(rtmi_light_t, rays) == 16 && offsetof(rtmi_light_t, bias) == 24, "ABI struct layout changed");
 
 namespace rtmi {
@@ -552,7 +553,8 @@ __global__ void __launch_bounds__(256) k_occl_from_hits(uint32_t n, const uint32
 // pixel_ray / color_ray themselves are in shade.hpp (shared with the path kernels of trace_oct.hpp).
 // S (shade.hpp): k_gen / k_shade are Samp::FRAME, k_gen_samples / k_shade_samples PASS, k_gen_list / k_shade_list LIST,
 // k_gen_views / k_shade_views VIEWS (the view table is an argument of these two only), k_shade_rays RAYS (no k_gen: the rays
-// are the caller's, rays.hpp has the kernel that stands in its place).
+// are the caller's, rays.hpp has the kernel that stands in its place).  k_gen_camera (camera.hpp, included below) is a second
+// PASS generator, for the built-in camera models; its passes are shaded by k_shade_samples.
 #define RTMI_GEN_PARAMS uint64_t seed, uint32_t pix0, uint32_t npaths, float4* __restrict__ qo, float4* __restrict__ qd, \
                         uint32_t* __restrict__ qpath, DCtrl* __restrict__ ctrl
 #define RTMI_GEN_ARGS v, seed, pix0, npaths, qo, qd, qpath, ctrl
@@ -575,6 +577,9 @@ __global__ void __launch_bounds__(256) k_gen(DView v, RTMI_GEN_PARAMS) { gen_pat
 __global__ void __launch_bounds__(256) k_gen_samples(DView v, RTMI_GEN_PARAMS) { gen_paths<Samp::PASS>(RTMI_GEN_ARGS); }
 __global__ void __launch_bounds__(256) k_gen_list(DView v, RTMI_GEN_PARAMS, const uint32_t* __restrict__ list) { gen_paths<Samp::LIST>(RTMI_GEN_ARGS, list); }
 __global__ void __launch_bounds__(256) k_gen_views(DView v, RTMI_GEN_PARAMS, ViewTab vt) { gen_paths<Samp::VIEWS>(RTMI_GEN_ARGS, nullptr, vt); }
+}  // namespace rtmi
+#include "camera.hpp"  // k_gen_camera: a PASS generator for the built-in camera models (rtmi_render_camera*)
+namespace rtmi {
 
 // color_ray + the tail of project_ray for every ray of pass `pass`.
 #define RTMI_SHADE_PARAMS DScene sc, DView v, uint64_t seed, uint32_t pix0, uint32_t npaths, int pass,                  \
@@ -2156,6 +2161,8 @@ struct PreviewCall {
 };
 // A shadowed path-trace (rtmi_render_shadowed*): the light every surface hit of every bounce is tested against
 struct ShadowCall { rtmi_light_t p; };
+// A camera call (rtmi_render_camera*): the model k_gen_camera generates the rays of, and the guides of those rays (each may be null)
+struct CameraCall { DCam cam; FeatOut fo; };
 // One render_tile call: what it renders, and its plan (plan_tile)
 struct TileCall {
     uint64_t seed;
@@ -2167,6 +2174,7 @@ struct TileCall {
     const LightCall* li;  // a direct-light call: likewise with k_light_rays and k_light_resolve
     const PreviewCall* pv;  // a preview call: the primary pass once, k_preview_rays, one walk of queue 1, k_preview_resolve
     const ShadowCall* sh;  // a shadowed path-trace: a progressive pass (accum) of the per-pass pipeline with k_shadow_rays, an any-hit walk and k_shade_shadowed per bounce pass
+    const CameraCall* cam;  // a camera call: a progressive pass (accum) of the per-pass pipeline, or a features call (fo), with k_gen_camera for k_gen_samples; k_features after pass 0 when cam->fo asks
     ViewTab vt;  // VIEWS: the view table (cams == nullptr otherwise)
     Samp mode;  // LIST with lp, PASS with accum, fo, ao, li or pv, VIEWS with vt.cams, FRAME otherwise
     bool counting, path_kernels;
@@ -2208,7 +2216,7 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
     // path kernels (pipeline 3; 0 = automatic): exact-octree scenes get pass 0 from k_path_primary, which generates, traces and
     // shades the primary rays in one kernel.  Everything else (pipeline 1, linear list, generic tree, BVH mode,
     // analytic spheres) starts with k_gen.  Both then run one closest-hit + one shading launch per bounce pass.
-    c.path_kernels = !c.fo && !c.ao && !c.li && !c.pv && !c.sh && s->tune.pipeline != 1u && s->octree && !s->root_is_leaf &&
+    c.path_kernels = !c.fo && !c.ao && !c.li && !c.pv && !c.sh && !c.cam && s->tune.pipeline != 1u && s->octree && !s->root_is_leaf &&
                      !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) && s->d.nspheres == 0;
     // streams = 0 (automatic): one stream for path-kernel tiles of 2^26 paths and more, three otherwise (the per-pass
     // pipelines -- BVH mode: 29.6 ms on three streams, 35.2 on one -- have elementwise kernels to hide).  Since k_shade stopped being
@@ -2361,6 +2369,8 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
         hipLaunchKernelGGL(k_gen_list, ew_grid, ew_block, 0, st, dv, c.seed, pix0, npaths, w.qo[0].p, w.qd[0].p, w.qpath[0].p, w.ctrl.p, list);
     } else if (c.mode == Samp::VIEWS) {
         hipLaunchKernelGGL(k_gen_views, ew_grid, ew_block, 0, st, dv, c.seed, pix0, npaths, w.qo[0].p, w.qd[0].p, w.qpath[0].p, w.ctrl.p, c.vt);
+    } else if (c.cam) {
+        hipLaunchKernelGGL(k_gen_camera, ew_grid, ew_block, 0, st, dv, c.cam->cam, c.seed, pix0, npaths, w.qo[0].p, w.qd[0].p, w.qpath[0].p, w.ctrl.p);
     } else {
         hipLaunchKernelGGL(c.mode == Samp::PASS ? k_gen_samples : k_gen, ew_grid, ew_block, 0, st, dv, c.seed, pix0, npaths, w.qo[0].p,
                            w.qd[0].p, w.qpath[0].p, w.ctrl.p);
@@ -2473,6 +2483,9 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
         HIPCHK(hipEventRecord(w.pass_ev[2 * pass], st));
         launch_trace(s, w, st, w.qo[a].p, w.qd[a].p, (int)pass, c.counting, w.pass_ev[2 * pass + 1]);
         HIPCHK(hipGetLastError());
+        if (pass == 0 && c.cam && (c.cam->fo.albedo || c.cam->fo.normal || c.cam->fo.ids))  // the guides, before pass 1 rewrites the hit records
+            hipLaunchKernelGGL(k_features, ew_grid, ew_block, 0, st, s->d, np, c.spp, w.hit_tf.p, w.hit_t.p, (float*)c.cam->fo.albedo,
+                               (float*)c.cam->fo.normal, c.cam->fo.ids, pix0, c.W, c.nsub, t, make_fastdiv(c.W), make_fastdiv(c.spp));
         if (c.counting && s->verbose && !c.path_kernels) {
             int rc = dump_pass_counters(s, w, st, t, pass);
             if (rc != RTMI_OK) return rc;
@@ -2598,12 +2611,16 @@ static int collect_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
 // sh != nullptr (with accum): a shadowed path-trace (rtmi_render_shadowed_device).  A progressive pass in every respect, always
 // on the per-pass pipeline, whose batches run k_shadow_rays, the scene's any-hit walk of the pass's live shadow rays and
 // k_shade_shadowed (for k_shade_samples) in every bounce pass.
+// cam != nullptr (with accum, or with fo): a camera call (rtmi_render_camera_device).  A progressive pass (or a features call)
+// in every respect, always on the per-pass pipeline, whose batches run k_gen_camera for k_gen_samples and, with accum,
+// k_features on pass 0's hit records when cam->fo asks.
 // views > 0 (no accum): a batch of views (Samp::VIEWS, rtmi_render_views_device); vp is the stacked image (height = views *
 // the views' height) and s->hvcams holds the view table, uploaded here on hip_stream before the internal streams fork.
 static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile, uint32_t sample0,
                        uint32_t nsamples, float4* accum, void* out_device, void* hip_stream, rtmi_stats_t* stats,
                        const ListPass* lp = nullptr, uint32_t views = 0, const FeatOut* fo = nullptr, const AoCall* ao = nullptr,
-                       const LightCall* li = nullptr, const PreviewCall* pv = nullptr, const ShadowCall* sh = nullptr) {
+                       const LightCall* li = nullptr, const PreviewCall* pv = nullptr, const ShadowCall* sh = nullptr,
+                       const CameraCall* cam = nullptr) {
     if (stats) memset(stats, 0, sizeof(*stats));
     if (tile->nrows == 0) return RTMI_OK;
     RTMI_GUARD_BEGIN
@@ -2625,7 +2642,7 @@ static int render_tile(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed
     }
     TileCall c;
     c.seed = seed; c.sample0 = sample0; c.spp = nsamples; c.maxdepth = vp->maxdepth; c.W = vp->width;
-    c.accum = accum; c.out = out; c.lp = lp; c.fo = fo; c.ao = ao; c.li = li; c.pv = pv; c.sh = sh; c.vt = ViewTab{nullptr, FastDiv{}};
+    c.accum = accum; c.out = out; c.lp = lp; c.fo = fo; c.ao = ao; c.li = li; c.pv = pv; c.sh = sh; c.cam = cam; c.vt = ViewTab{nullptr, FastDiv{}};
     c.mode = lp ? Samp::LIST : (accum || fo || ao || li || pv) ? Samp::PASS : views ? Samp::VIEWS : Samp::FRAME;
     c.counting = (s->options & RTMI_OPT_COUNTERS) != 0;
     rc = plan_tile(s, vp, tile, c);
@@ -2781,6 +2798,98 @@ int rtmi_render_features(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t se
     if (albedo_host) HIPCHK(hipMemcpy(albedo_host, fo.albedo, npix * sizeof(float4), hipMemcpyDeviceToHost));
     if (normal_host) HIPCHK(hipMemcpy(normal_host, fo.normal, npix * sizeof(float4), hipMemcpyDeviceToHost));
     if (ids_host) HIPCHK(hipMemcpy(ids_host, fo.ids, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+// ---------------------------------------------------------------- built-in camera models (rtmi_render_camera*)
+void rtmi_camera_defaults(rtmi_camera_t* c) {
+    if (!c) return;
+    c->model = RTMI_CAMERA_PINHOLE; c->flags = 0; c->lens_radius = 0.f; c->focus = 1.f;
+}
+
+// Checks of the camera entry points that come before any HIP call and before the scene is used (a CPU-only caller reaches
+// them): rtmi_render_samples_device's, then the camera's and the guides'.  RTMI_OK with *empty set: the tile has no rows.
+static int check_camera(rtmi_scene_t* s, const rtmi_viewport_t* vp, const rtmi_tile_t* tile, const rtmi_camera_t* cam, uint32_t sample0,
+                        uint32_t nsamples, const void* accum, const void* out, const rtmi_camera_out_t* g, bool* empty) {
+    *empty = false;
+    const int rc = check_samples(s, vp, sample0, nsamples, accum, out);
+    if (rc != RTMI_OK) return rc;
+    if (!tile) return fail(RTMI_ERR_INVALID, "NULL argument (tile)");
+    if (!cam) return fail(RTMI_ERR_INVALID, "camera: NULL argument (rtmi_camera_t)");
+    if (cam->model > RTMI_CAMERA_ORTHO) return fail(RTMI_ERR_INVALID, "camera: unknown model");
+    if (cam->flags != 0) return fail(RTMI_ERR_INVALID, "camera: flags must be 0");
+    if (cam->model == RTMI_CAMERA_THIN_LENS) {
+        if (!(cam->lens_radius >= 0.f) || !std::isfinite(cam->lens_radius))
+            return fail(RTMI_ERR_INVALID, "camera: lens_radius must be finite and >= 0");
+        if (!(cam->focus > 0.f) || !std::isfinite(cam->focus)) return fail(RTMI_ERR_INVALID, "camera: focus must be finite and > 0");
+    }
+    if (g) {
+        const void* b[5] = {accum, out, g->albedo, g->normal, g->ids};
+        for (int i = 2; i < 5; i++)
+            for (int j = 0; j < i; j++)
+                if (b[i] && b[i] == b[j]) return fail(RTMI_ERR_INVALID, "camera: a guide buffer aliases another buffer (accum, out, albedo, normal, ids)");
+    }
+    if (tile->nrows == 0) { *empty = true; return RTMI_OK; }
+    return check_view(vp, tile);
+}
+
+// Both variants, on device buffers, after check_camera.  maxdepth == 0: render_tile writes the zeros; the guides do not depend
+// on the depth and come from a features call with the camera's generator.
+static int render_camera(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile, const rtmi_camera_t* cam,
+                         uint32_t sample0, uint32_t nsamples, float4* accum, void* out, const FeatOut& fo, void* hip_stream,
+                         rtmi_stats_t* stats) {
+    const bool guides = fo.albedo || fo.normal || fo.ids;
+    if (guides && s->d.nspheres)
+        return fail(RTMI_ERR_UNSUPPORTED, "camera: no guide buffers (albedo, normal, ids) for scenes with analytic spheres");
+    const CameraCall cc{DCam{cam->model, cam->lens_radius, cam->focus}, fo};
+    const int rc = render_tile(s, vp, seed, tile, sample0, nsamples, accum, out, hip_stream, stats, nullptr, 0, nullptr, nullptr, nullptr,
+                               nullptr, nullptr, &cc);
+    if (rc != RTMI_OK || vp->maxdepth != 0 || !guides) return rc;
+    rtmi_viewport_t v1 = *vp;
+    v1.maxdepth = 1;
+    return render_tile(s, &v1, seed, tile, sample0, nsamples, nullptr, nullptr, hip_stream, stats, nullptr, 0, &cc.fo, nullptr, nullptr,
+                       nullptr, nullptr, &cc);
+}
+
+int rtmi_render_camera_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile,
+                              const rtmi_camera_t* camera, uint32_t sample0, uint32_t nsamples, void* accum_device, void* out_device,
+                              const rtmi_camera_out_t* guides, void* hip_stream, rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    bool empty;
+    const int rc = check_camera(s, vp, tile, camera, sample0, nsamples, accum_device, out_device, guides, &empty);
+    if (rc != RTMI_OK || empty) return rc;
+    const FeatOut fo = guides ? FeatOut{(float4*)guides->albedo, (float4*)guides->normal, (uint32_t*)guides->ids} : FeatOut{nullptr, nullptr, nullptr};
+    return render_camera(s, vp, seed, tile, camera, sample0, nsamples, (float4*)accum_device, out_device, fo, hip_stream, stats);
+}
+
+// Host variant: accum is copied in (only when sample0 > 0) and out again like rtmi_render_samples; the guides are rendered
+// into the host variants' per-pixel buffers of the handle (asq: albedo, then normal; acnt: ids) and copied out once.
+int rtmi_render_camera(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
+                       const rtmi_camera_t* camera, uint32_t sample0, uint32_t nsamples, float* accum_host, float* out_host,
+                       const rtmi_camera_out_t* guides_host, rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    const rtmi_tile_t tile{row0, nrows, nrows ? nrows : 1u, 0u};
+    bool empty;
+    const int rc0 = check_camera(s, vp, &tile, camera, sample0, nsamples, accum_host, out_host, guides_host, &empty);
+    if (rc0 != RTMI_OK || empty) return rc0;
+    const rtmi_camera_out_t g = guides_host ? *guides_host : rtmi_camera_out_t{nullptr, nullptr, nullptr};
+    if ((g.albedo || g.normal || g.ids) && s->d.nspheres)
+        return fail(RTMI_ERR_UNSUPPORTED, "camera: no guide buffers (albedo, normal, ids) for scenes with analytic spheres");
+    const uint64_t npix = (uint64_t)nrows * vp->width;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(s->acc.ensure(npix));
+    if (out_host) HIPCHK(s->tile.ensure(npix));
+    if (g.albedo || g.normal) HIPCHK(s->asq.ensure(2 * npix));
+    if (g.ids) HIPCHK(s->acnt.ensure(npix));
+    if (sample0 > 0) HIPCHK(hipMemcpy(s->acc.p, accum_host, npix * sizeof(float4), hipMemcpyHostToDevice));
+    const FeatOut fo{g.albedo ? s->asq.p : nullptr, g.normal ? s->asq.p + npix : nullptr, g.ids ? s->acnt.p : nullptr};
+    const int rc = render_camera(s, vp, seed, &tile, camera, sample0, nsamples, s->acc.p, out_host ? (void*)s->tile.p : nullptr, fo, nullptr, stats);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(hipMemcpy(accum_host, s->acc.p, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    if (out_host) HIPCHK(hipMemcpy(out_host, s->tile.p, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    if (g.albedo) HIPCHK(hipMemcpy(g.albedo, fo.albedo, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    if (g.normal) HIPCHK(hipMemcpy(g.normal, fo.normal, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    if (g.ids) HIPCHK(hipMemcpy(g.ids, fo.ids, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
 

@@ -378,6 +378,35 @@ int rth_caster_walk_shadowed_device(rth_scene_t* s, uint32_t w, uint32_t h, cons
         if (stats) *stats = ctx.stats;
     });
 }
+int rth_caster_walk_camera(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp, uint64_t row0,
+                           uint64_t nrows, const rtmi_camera_t* camera, uint32_t sample0, uint32_t nsamples, float* accum_host,
+                           float* out_host, const rtmi_camera_out_t* guides_host, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!camera) throw std::runtime_error("NULL rtmi_camera_t");
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_rays_camera(v, s->scene, (size_t)row0, (size_t)nrows, *camera, sample0, nsamples, reinterpret_cast<Color*>(accum_host),
+                                      reinterpret_cast<Color*>(out_host), guides_host, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
+int rth_caster_walk_camera_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                                  const rtmi_tile_t* tile, const rtmi_camera_t* camera, uint32_t sample0, uint32_t nsamples,
+                                  void* accum_device, void* out_device, const rtmi_camera_out_t* guides, void* hip_stream,
+                                  rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!tile) throw std::runtime_error("NULL tile");
+        if (!camera) throw std::runtime_error("NULL rtmi_camera_t");
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_camera_device(v, s->scene, *tile, *camera, sample0, nsamples, accum_device, out_device, guides, hip_stream, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
 int rth_caster_walk_preview(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp, uint64_t row0,
                             uint64_t nrows, uint32_t sample0, uint32_t nsamples, const rtmi_preview_t* preview,
                             const rtmi_preview_out_t* out_host, rtmi_stats_t* stats, double* wall) {

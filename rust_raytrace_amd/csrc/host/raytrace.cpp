@@ -877,6 +877,33 @@ void HipRayCaster::walk_shadowed_device(const Viewport& v, const Scene& s, const
     progress.stats = st;
 }
 
+void HipRayCaster::walk_rays_camera(const Viewport& v, const Scene& s, size_t row0, size_t nrows, const rtmi_camera_t& camera,
+                                    uint32_t sample0, uint32_t nsamples, Color* accum, Color* out, const rtmi_camera_out_t* guides,
+                                    ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_camera(h, &av, seed, (uint32_t)row0, (uint32_t)nrows, &camera, sample0, nsamples,
+                                      reinterpret_cast<float*>(accum), reinterpret_cast<float*>(out), guides, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_camera: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
+void HipRayCaster::walk_camera_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, const rtmi_camera_t& camera,
+                                      uint32_t sample0, uint32_t nsamples, void* accum_device, void* out_device,
+                                      const rtmi_camera_out_t* guides, void* hip_stream, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_camera_device(h, &av, seed, &tile, &camera, sample0, nsamples, accum_device, out_device, guides, hip_stream, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_camera_device: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
 void HipRayCaster::walk_rays_preview(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
                                      const rtmi_preview_t& preview, const rtmi_preview_out_t& out, ProgressCtx& progress) {
     rtmi_scene_t* h = resident(s);

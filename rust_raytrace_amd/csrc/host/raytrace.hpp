@@ -265,6 +265,14 @@ public:
     void walk_shadowed_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
                               uint32_t flags, float bias, void* accum_device, void* out_device, void* hip_stream,
                               ProgressCtx& progress);
+    // Built-in camera models (rtmi_render_camera / rtmi_render_camera_device, which rtmi.h defines): walk_samples /
+    // walk_samples_device in every respect, with the rays of `camera` (pinhole, thin lens, orthographic) and, when `guides` is
+    // not null, the feature buffers of those rays.
+    void walk_rays_camera(const Viewport& v, const Scene& s, size_t row0, size_t nrows, const rtmi_camera_t& camera, uint32_t sample0,
+                          uint32_t nsamples, Color* accum, Color* out, const rtmi_camera_out_t* guides, ProgressCtx& progress);
+    void walk_camera_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, const rtmi_camera_t& camera, uint32_t sample0,
+                            uint32_t nsamples, void* accum_device, void* out_device, const rtmi_camera_out_t* guides, void* hip_stream,
+                            ProgressCtx& progress);
     // Shaded preview (rtmi_render_preview / rtmi_render_preview_device, which rtmi.h defines): albedo, AO and up to four
     // coloured box lights composed per sample from one primary pass; `out` names the colour image and the layers wanted.
     void walk_rays_preview(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,

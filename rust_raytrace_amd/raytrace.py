@@ -645,6 +645,131 @@ class HipRayCaster:
                                                         C.c_void_p(stream_ptr or 0), C.byref(st), C.byref(wall)))
         return ProgressCtx(st.rays, wall.value, st.as_dict())
 
+    CAMERA_MODELS = {"pinhole": _ffi.CAMERA_PINHOLE, "thin_lens": _ffi.CAMERA_THIN_LENS, "ortho": _ffi.CAMERA_ORTHO}
+
+    @staticmethod
+    def camera_params(v, model="pinhole", aperture=0.0, focus_distance=None):
+        """rtmi_camera_t for viewport v (include/rtmi.h defines the models).  model: "pinhole" (the reference's camera),
+        "thin_lens" or "ortho".  aperture: the radius of the lens in world units.  focus_distance: the distance from the eye,
+        along the camera's axis, of the plane that is in focus, in world units (None: the image plane itself); it becomes
+        rtmi_camera_t.focus = focus_distance / |c - cam| with c the centre of the image plane, computed in float64 and rounded
+        once.  Both are ignored by the pinhole and the orthographic camera."""
+        if model not in HipRayCaster.CAMERA_MODELS:
+            raise ValueError(f"model must be one of {sorted(HipRayCaster.CAMERA_MODELS)}")
+        cam = _ffi.Camera()
+        _ffi.lib().rtmi_camera_defaults(C.byref(cam))
+        cam.model = HipRayCaster.CAMERA_MODELS[model]
+        if model == "thin_lens":
+            cam.lens_radius = float(aperture)
+            if focus_distance is not None:
+                vp = np.asarray(v.vp12, np.float64)
+                c = vp[0:3] + 0.5 * vp[6:9] + 0.5 * vp[9:12]
+                cam.focus = float(focus_distance) / float(np.sqrt(((c - vp[3:6]) ** 2).sum()))
+        return cam
+
+    @staticmethod
+    def _camera_guides(guides, shape4, shape1):
+        """(albedo, normal, ids) as given to a camera call -> arrays or None: None / False leaves a buffer out, True allocates it."""
+        out = []
+        for name, a, shape, dt in (("albedo", guides[0], shape4, np.float32), ("normal", guides[1], shape4, np.float32),
+                                   ("ids", guides[2], shape1, np.uint32)):
+            if a is None or a is False:
+                a = None
+            elif a is True:
+                a = np.zeros(shape, dt)
+            elif not isinstance(a, np.ndarray) or a.dtype != dt or not a.flags.c_contiguous or a.size != int(np.prod(shape)):
+                raise ValueError(f"{name} must be a C-contiguous {np.dtype(dt).name} array of {int(np.prod(shape))} elements")
+            out.append(a)
+        return out
+
+    def walk_samples_camera(self, v, s, row0, nrows, camera, sample0, nsamples, accum, out=None, albedo=None, normal=None, ids=None):
+        """walk_samples through a built-in camera model (rtmi_render_camera): samples [sample0, sample0 + nsamples) of rows
+        [row0, row0 + nrows) with the rays of `camera` (camera_params).  accum / out as in walk_samples.  albedo, normal
+        (nrows*width*4 f32) and ids (nrows*width u32): the feature buffers of THIS call's samples, traced with the same rays;
+        None leaves one out, True allocates it.  Returns ctx; ctx.albedo / .normal / .ids are the guide arrays (or None)."""
+        for name, a in (("accum", accum), ("out", out)):
+            if a is not None and (a.dtype != np.float32 or not a.flags.c_contiguous or a.size != nrows * v.width * 4):
+                raise ValueError(f"{name} must be a C-contiguous float32 array of nrows*width*4 elements")
+        g = self._camera_guides((albedo, normal, ids), (nrows, v.width, 4), (nrows, v.width))
+        go = _ffi.CameraOut(*[_p(a) if a is not None else None for a in g])
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_camera(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, row0, nrows,
+                                               C.byref(camera), sample0, nsamples, _p(accum), _p(out) if out is not None else None,
+                                               C.byref(go) if any(a is not None for a in g) else None, C.byref(st), C.byref(wall)))
+        ctx = ProgressCtx(st.rays, wall.value, st.as_dict())
+        ctx.albedo, ctx.normal, ctx.ids = g
+        return ctx
+
+    def walk_rays_camera(self, v, s, data, camera, pass_samples=None, albedo=None, normal=None, ids=None):
+        """walk_rays through a built-in camera model: the whole frame, all v.samples_per_pixel samples, in passes of
+        `pass_samples` samples (None: one pass) like walk_rays_progressive; `data` ((H, W, 4) f32) ends as the image, the same
+        bits whatever the passes.  albedo / normal / ids (None: left out, True: allocated, or an array to fill): the feature
+        buffers of the FIRST pass's samples (all samples with one pass).  Returns a ProgressCtx with the total rays, summed
+        stats, samples_done, accum and the guide arrays as .albedo / .normal / .ids."""
+        if data.dtype != np.float32 or not data.flags.c_contiguous or data.size != v.height * v.width * 4:
+            raise ValueError("data must be a C-contiguous float32 array of height*width*4 elements")
+        spp = int(v.samples_per_pixel)
+        step = spp if pass_samples is None else int(pass_samples)
+        if step < 1:
+            raise ValueError("pass_samples must be >= 1")
+        g = self._camera_guides((albedo, normal, ids), (v.height, v.width, 4), (v.height, v.width))
+        accum = np.zeros_like(data)
+        ctx = ProgressCtx(0, 0.0, None)
+        ctx.samples_done, ctx.accum = 0, accum
+        ctx.albedo, ctx.normal, ctx.ids = g
+        for k0 in range(0, spp, step):
+            n = min(step, spp - k0)
+            p = self.walk_samples_camera(v, s, 0, v.height, camera, k0, n, accum, data, *(g if k0 == 0 else (None, None, None)))
+            ctx.total_rays += p.total_rays
+            ctx.seconds += p.seconds
+            if ctx.stats is None:
+                ctx.stats = dict(p.stats)
+            else:
+                for k in ("rays", "box_tests", "tri_tests", "full_tests", "nodes", "leaves", "kernel_ms", "trace_ms", "trace_launches",
+                          "primary_ms", "bounce_ms", "slow_paths"):
+                    ctx.stats[k] += p.stats[k]
+            ctx.samples_done = k0 + n
+        return ctx
+
+    def walk_rays_camera_device(self, v, s, camera, accum, out=None, tile=None, sample0=0, nsamples=None, albedo=None, normal=None,
+                                ids=None, stream=None):
+        """The same on device memory (rtmi_render_camera_device) for a striped row set tile = (row0, nrows, stripe_rows,
+        stripe_step) (default: the whole frame): samples [sample0, sample0 + nsamples) (default: all from sample0).  accum, out,
+        albedo, normal (nrows * width float4) and ids (nrows * width uint32) are torch tensors on the scene's device or raw
+        device pointers (ints); out and the guides may be None.  The work is enqueued on `stream` (a torch stream, a raw HIP
+        stream pointer or None).  No host copies.  Returns ctx."""
+        k0, n = self._feature_samples(v, sample0, nsamples)
+        t = _ffi.Tile(*[int(x) for x in (tile if tile is not None else (0, v.height, v.height, 0))])
+        npix = int(t.nrows) * int(v.width)
+        ptrs = []
+        for name, x, want, dt in (("accum", accum, npix * 4, "torch.float32"), ("out", out, npix * 4, "torch.float32"),
+                                  ("albedo", albedo, npix * 4, "torch.float32"), ("normal", normal, npix * 4, "torch.float32"),
+                                  ("ids", ids, npix, "torch.int32")):
+            if x is None:
+                if name == "accum":
+                    raise ValueError("accum is needed")
+                ptrs.append(0)
+            elif hasattr(x, "data_ptr"):
+                dts = (dt, "torch.uint32") if name == "ids" else (dt,)
+                if not x.is_cuda or str(x.dtype) not in dts or not x.is_contiguous() or x.numel() != want:
+                    raise ValueError(f"{name} must be a contiguous {dt} tensor of {want} elements on the device")
+                ptrs.append(int(x.data_ptr()))
+            elif isinstance(x, int):
+                ptrs.append(x)
+            else:
+                raise ValueError(f"{name} must be a tensor on the device or a device pointer")
+        go = _ffi.CameraOut(*[C.c_void_p(p) if p else None for p in ptrs[2:]])
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_camera_device(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, C.byref(t),
+                                                      C.byref(camera), k0, n, C.c_void_p(ptrs[0]), C.c_void_p(ptrs[1]),
+                                                      C.byref(go) if any(ptrs[2:]) else None,
+                                                      C.c_void_p(getattr(stream, "cuda_stream", stream) or 0), C.byref(st), C.byref(wall)))
+        return ProgressCtx(st.rays, wall.value, st.as_dict())
+
     @staticmethod
     def ao_params(rays=None, radius=None, bias=None):
         """rtmi_ao_t from the library's defaults (rtmi_ao_defaults: 4 rays, radius +inf, bias 0.001) with the given fields
