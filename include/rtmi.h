@@ -624,6 +624,78 @@ int rtmi_render_rays_device(rtmi_scene_t* scene, uint64_t n, const void* orig4_d
 int rtmi_render_rays(rtmi_scene_t* scene, uint64_t n, const float* orig4, const float* dir4, const uint32_t* keys /* or NULL */,
                      uint64_t seed, const rtmi_rays_t* rays, const rtmi_rays_out_t* out_host, rtmi_stats_t* stats);
 
+/* Light baked at surface points and over triangles: "how much light arrives here", asked at M elements of the
+ * caller's choosing -- lightmap texels, vertices, probe positions (RTMI_BAKE_POINTS) or whole triangles, for per-face colours
+ * (RTMI_BAKE_TRIANGLES).  Per element K gather rays are made on the device, path-traced as rtmi_render_rays* traces them and
+ * folded; the rays never exist on the host.  The gather ray is the reference's Matte bounce (lambertian_ray's direction,
+ * raytrace.rs:292-297) and its colour the reference's project_ray, so light[m] is the colour color_ray mixes a white Matte
+ * surface at that point with.  The generator is NOT part of the reference: build-defined like rtmi_render_ao*, so what follows
+ * IS the definition, and tests/bake_ref.py pins it bit for bit.  Only + - * / and sqrt in f32 (all correctly rounded), every
+ * step rounded to f32 on all four lanes, no contraction, no transcendental function.
+ * Inputs: nrm4 = M float4, the side to bake: used as given on all four lanes and NOT normalised (pass a triangle's `norm` or
+ * its negative, lane 3 = +0).  pos4 = M float4 (POINTS), or 3 M float4 (TRIANGLES): corners c0, c1, c2 of element m at 3 m,
+ * 3 m + 1, 3 m + 2 (the scene keeps no corners on the device, and the triangles need not be the scene's).  16-byte aligned.
+ * Ray k of element m, k = 0 .. K-1, K = bake->rays; RNG key (seed, pixel = pixel0 + m, sample = k); vadd, vsub, vmul (vector *
+ * scalar), vunit (the ordered four-lane dot (((0 + x x) + y y) + z z) + w w, r = sqrt(.), v * (1.f / r)) the reference's Vec3
+ * operations (raytrace.rs:22-122), n = nrm4[m]:
+ *   point  POINTS:    pos4[m].
+ *          TRIANGLES: u, v = the unit floats (top 24 bits * 2^-24) of words 0 and 1 of RNG block 0x20000000 of the key;
+ *                     if (u + v > 1.f) { u = 1.f - u; v = 1.f - v; }    (the area-preserving fold of the square onto the
+ *                     triangle: no sqrt);  point = vadd(vadd(c0, vmul(vsub(c1, c0), u)), vmul(vsub(c2, c0), v)).
+ *                     Block 0x20000000 is new with this call and used by nothing else (a path's bounces draw blocks 1..32,
+ *                     the thin lens 0x40000000 | k, rtmi_render_ao* 0x80000000 | k, the lights 0xC0000000 | k).
+ *   rv   = random_vec (raytrace.rs:188-192) from block 0 of the key: three uniforms - 0.5f, made a unit vector.  Block 0 is
+ *          pixel_ray's jitter, which a path under rtmi_render_rays* never draws;
+ *   orig = vadd(point, vmul(n, bias));   dir = vunit(vadd(n, rv)): rtmi_render_ao*'s two lines, the offset along n and not
+ *          along rv for the reason measured in DESIGN.md 4.15.
+ * Outputs (rtmi_bake_out_t; any may be NULL, not all):
+ *   orig[m K + k], dir[m K + k]   the gather rays themselves;
+ *   light[m]   the colour of ray m K + k is exactly what rtmi_render_rays* gives that ray with keys == NULL, group = K, the
+ *              same pixel0, maxdepth and flags = 0 (bounce j of the path draws block j), and light[m] is that call's mean[m]:
+ *              acc = 0.f; acc = acc + color[m K + k] for k = 0 .. K-1; acc * (1.f / (float)K) (walk_ray_set's arithmetic,
+ *              raytrace.rs:1414-1426); lane 3 = 0;
+ *   open[m]    (float)misses * (1.f / (float)K), misses = the number of the element's rays whose closest hit (what rtmi_trace
+ *              returns for the ray under the handle's current options) has tri == 0: an integer count, so no order matters.
+ * maxdepth == 0: light is zeros (project_ray returns black at depth 0); open, orig and dir are still produced, and the rays are
+ * traced only if open is asked for.
+ * Scenes: every kind rtmi_render_rays* takes, each with its own mode's hits, analytic spheres included (open needs no surface
+ * record).  Stream semantics (device variant), stats and "no tuning changes a bit of the result" are rtmi_render_rays*'s: rays =
+ * every ray traced in any pass, trace_launches = passes x batches, streams = 1, pipeline = 1.
+ * How: always the per-pass pipeline on one stream of the library.  Per batch k_bake_rays stands where k_rays_begin stands (the
+ * rays, the queue's count and the identity path map), then per pass the scene's closest-hit launch and k_shade_rays,
+ * k_bake_open after pass 0 when open is asked for, k_accum for light.  The rays go into the workspace queue; the device
+ * variant writes them straight into orig / dir when those are given and traces them there.  A batch holds whole elements:
+ * rtmi_tuning_t.batch_paths rounded down to a multiple of K, at least K.  Nothing new persists on the handle.
+ * rtmi_bake: host buffers; each batch's elements are copied in and its outputs copied out.
+ * Checks, all before any HIP call and before the scene is used, stats cleared.  In this order:
+ *   RTMI_ERR_INVALID: a NULL scene, bake struct or out; an unknown mode; rays == 0; non-zero flags; bias NaN or infinite;
+ *   M == 0: RTMI_OK, nothing is touched;
+ *   RTMI_ERR_INVALID: a NULL pos4 or nrm4; all four outputs NULL; two buffers overlapping as byte ranges, inputs included
+ *     (16 M or 48 M, 16 M; 16 M, 4 M, 16 M K, 16 M K); pixel0 + M - 1 >= 2^32;
+ *   RTMI_ERR_UNSUPPORTED: rays > 65536; maxdepth > 32; M K >= 2^31.
+ * Not here: importance sampling towards lights, the shadowed path variant (rtmi_render_shadowed*'s shading), the path kernels
+ * (pipeline 3), several streams or devices, progressive continuation of a bake across calls, filtering of a lightmap. */
+enum { RTMI_BAKE_POINTS = 0, RTMI_BAKE_TRIANGLES = 1 };
+typedef struct rtmi_bake {
+    uint32_t mode;      /* RTMI_BAKE_*                                                                           */
+    uint32_t rays;      /* K gather rays per element, 1..65536                                                   */
+    uint32_t maxdepth;  /* project_ray's depth of every gather ray, 0..32                                        */
+    uint32_t pixel0;    /* RNG key of element 0                                                                  */
+    uint32_t flags;     /* must be 0                                                                             */
+    float    bias;      /* origin offset along the element's normal, finite                                      */
+} rtmi_bake_t;          /* 24 bytes */
+typedef struct rtmi_bake_out {   /* any may be NULL, not all; none may overlap another or an input */
+    void* light;    /* M float4: mean colour arriving at element m, lane 3 = 0                                   */
+    void* open;     /* M f32: share of the element's gather rays whose closest hit is a miss                     */
+    void* orig;     /* M*K float4 } the gather rays themselves, ray m*K + k                                      */
+    void* dir;      /* M*K float4 }                                                                              */
+} rtmi_bake_out_t;
+void rtmi_bake_defaults(rtmi_bake_t* bake);  /* POINTS, 64 rays, maxdepth 4, pixel0 0, flags 0, bias 0.001f */
+int rtmi_bake_device(rtmi_scene_t* scene, uint64_t M, const void* pos4_device, const void* nrm4_device, uint64_t seed,
+                     const rtmi_bake_t* bake, const rtmi_bake_out_t* out_device, void* hip_stream, rtmi_stats_t* stats);
+int rtmi_bake(rtmi_scene_t* scene, uint64_t M, const float* pos4, const float* nrm4, uint64_t seed, const rtmi_bake_t* bake,
+              const rtmi_bake_out_t* out_host, rtmi_stats_t* stats);
+
 /* Built-in camera models rendered on the device: rtmi_render_samples[_device] with a ray generator that is
  * not only the reference's pinhole -- a thin lens (depth of field) and an orthographic camera -- and, optionally, the
  * denoiser's guide buffers of the very same rays.  The rays never leave the device: nothing is generated, keyed, stored or
@@ -656,7 +728,8 @@ int rtmi_render_rays(rtmi_scene_t* scene, uint64_t n, const float* orig4, const 
  *       the first candidate, in the order (k, j) = (0, 0), (0, 1), (1, 0), (1, 1), with (x * x) + (y * y) <= 1.f is taken.  If all
  *       four fail the sample is (0.f, 0.f): the pinhole's ray.  That happens with probability (1 - pi/4)^4 ~ 0.0021, a
  *       slight, stated over-weighting of the lens centre.  Blocks 0x40000000 | k are used by nothing else (bounces draw blocks
- *       1..32, rtmi_render_ao* 0x80000000 | k, the lights 0xC0000000 | k).
+ *       1..32, rtmi_render_ao* 0x80000000 | k, the lights 0xC0000000 | k, rtmi_bake*'s point on a triangle the one block
+ *       0x20000000, which is used by nothing else either).
  *     o = vadd(vmul(eu, x * lens_radius), vmul(ev, y * lens_radius))          (the point on the lens, relative to cam)
  *     e = vsub(p, cam);   F = vadd(cam, vmul(e, focus))                        (the point in focus)
  *     O = vadd(p, vmul(o, 1.f - 1.f / focus))       (where the lens ray crosses the image plane: rays start where the

@@ -134,6 +134,13 @@ int rth_caster_walk_rays_explicit(rth_scene_t* s, uint64_t n, const float* orig4
 int rth_caster_walk_rays_explicit_device(rth_scene_t* s, uint64_t n, const void* orig4_device, const void* dir4_device,
                                          const void* keys_device, const rtmi_rays_t* rays, const rtmi_rays_out_t* out_device,
                                          void* hip_stream, rtmi_stats_t* stats, double* wall_seconds);
+/* Light baked at M surface points or over M triangles (rtmi_bake / rtmi_bake_device in rtmi.h, which defines it) on the scene's
+ * resident copy, with the caster's seed: bake->rays gather rays per element made on the device, path-traced and folded.
+ * pos4: M float4 (RTMI_BAKE_POINTS) or 3 M float4, a triangle's corners (RTMI_BAKE_TRIANGLES); nrm4: M float4. */
+int rth_caster_bake(rth_scene_t* s, uint64_t M, const float* pos4, const float* nrm4, const rtmi_bake_t* bake,
+                    const rtmi_bake_out_t* out_host, rtmi_stats_t* stats, double* wall_seconds);
+int rth_caster_bake_device(rth_scene_t* s, uint64_t M, const void* pos4_device, const void* nrm4_device, const rtmi_bake_t* bake,
+                           const rtmi_bake_out_t* out_device, void* hip_stream, rtmi_stats_t* stats, double* wall_seconds);
 /* Ambient occlusion (rtmi_render_ao / rtmi_render_ao_device in rtmi.h, which defines it): one f32 per pixel, the share of
  * ao->rays hemisphere rays per primary sample of [sample0, sample0 + nsamples) that are not occluded within ao->radius.
  * maxdepth is not consulted; the primary rays use the caster's seed. */

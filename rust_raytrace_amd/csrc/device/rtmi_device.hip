@@ -50,6 +50,8 @@ static_assert(sizeof(rtmi_adaptive_t) == 32 && offsetof(rtmi_adaptive_t, samples
 static_assert(sizeof(rtmi_denoise_t) == 24 && offsetof(rtmi_denoise_t, sigma_color) == 8, "ABI struct layout changed");
 static_assert(sizeof(rtmi_ao_t) == 16 && offsetof(rtmi_ao_t, radius) == 8, "ABI struct layout changed");
 static_assert(sizeof(rtmi_camera_t) == 16 && offsetof(rtmi_camera_t, lens_radius) == 8 && sizeof(rtmi_camera_out_t) == 3 * sizeof(void*), "ABI struct layout changed");
+static_assert(sizeof(rtmi_bake_t) == 24 && offsetof(rtmi_bake_t, pixel0) == 12 && offsetof(rtmi_bake_t, bias) == 20 &&
+              sizeof(rtmi_bake_out_t) == 4 * sizeof(void*) && offsetof(rtmi_bake_out_t, orig) == 2 * sizeof(void*), "ABI struct layout changed");
 static_assert(sizeof(rtmi_light_t) == 28 && offsetof(rtmi_light_t, rays) == 16 && offsetof(rtmi_light_t, bias) == 24, "ABI struct layout changed");
 
 namespace rtmi {
@@ -398,6 +400,7 @@ __global__ void __launch_bounds__(256) k_trace(DScene sc, const float4* __restri
 #include "light.hpp"
 #include "preview.hpp"
 #include "rays.hpp"
+#include "bake.hpp"
 #include "shadowed.hpp"
 namespace rtmi {
 
@@ -3995,6 +3998,183 @@ int rtmi_render_rays_device(rtmi_scene_t* s, uint64_t n, const void* orig4_devic
 int rtmi_render_rays(rtmi_scene_t* s, uint64_t n, const float* orig4, const float* dir4, const uint32_t* keys, uint64_t seed,
                      const rtmi_rays_t* rays, const rtmi_rays_out_t* out_host, rtmi_stats_t* stats) {
     return render_rays(s, n, orig4, dir4, keys, seed, rays, out_host, nullptr, stats, true);
+}
+
+// ---------------------------------------------------------------- light bake (rtmi_bake*, bake.hpp)
+void rtmi_bake_defaults(rtmi_bake_t* p) {
+    if (!p) return;
+    p->mode = RTMI_BAKE_POINTS; p->rays = 64; p->maxdepth = 4; p->pixel0 = 0; p->flags = 0;
+    p->bias = 0.001f;  // the reference's bounce offset (raytrace.rs:284-296), along the normal as rtmi_render_ao*'s
+}
+
+// Checks that come before any HIP call and before the scene is used (a CPU-only caller reaches them).
+static int check_bake(const rtmi_scene_t* s, uint64_t M, const void* pos4, const void* nrm4, const rtmi_bake_t* bp, const rtmi_bake_out_t* out,
+                      rtmi_stats_t* stats, bool& empty) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    empty = false;
+    if (!s) return fail(RTMI_ERR_INVALID, "bake: NULL argument (scene)");
+    if (!bp) return fail(RTMI_ERR_INVALID, "bake: NULL argument (rtmi_bake_t)");
+    if (!out) return fail(RTMI_ERR_INVALID, "bake: NULL argument (out)");
+    if (bp->mode != RTMI_BAKE_POINTS && bp->mode != RTMI_BAKE_TRIANGLES) return fail(RTMI_ERR_INVALID, "bake: unknown mode");
+    if (bp->rays == 0) return fail(RTMI_ERR_INVALID, "bake: rays must be >= 1");
+    if (bp->flags != 0) return fail(RTMI_ERR_INVALID, "bake: flags must be 0");
+    if (!std::isfinite(bp->bias)) return fail(RTMI_ERR_INVALID, "bake: bias must be finite");
+    if (M == 0) { empty = true; return RTMI_OK; }
+    if (!pos4) return fail(RTMI_ERR_INVALID, "bake: NULL argument (pos4)");
+    if (!nrm4) return fail(RTMI_ERR_INVALID, "bake: NULL argument (nrm4)");
+    if (!out->light && !out->open && !out->orig && !out->dir) return fail(RTMI_ERR_INVALID, "bake: all four outputs are NULL");
+    // (counts that are refused below anyway: the sizes must not wrap)
+    const uint64_t m = std::min<uint64_t>(M, 1ull << 40), n = m * std::min<uint32_t>(bp->rays, 65537u);
+    const ByteRange r[6] = {{pos4, m * (bp->mode == RTMI_BAKE_TRIANGLES ? 48u : 16u), "pos4"}, {nrm4, m * 16, "nrm4"}, {out->light, m * 16, "light"},
+                            {out->open, m * 4, "open"}, {out->orig, n * 16, "orig"}, {out->dir, n * 16, "dir"}};
+    size_t a, b;
+    if (ranges_overlap(r, 6, a, b))
+        return fail(RTMI_ERR_INVALID, std::string("bake: buffers overlap (") + r[a].name + " and " + r[b].name + ")");
+    if ((uint64_t)bp->pixel0 + M - 1 >= (1ull << 32))
+        return fail(RTMI_ERR_INVALID, "bake: pixel0 + M - 1 must stay below 2^32 (the RNG key is 32 bits)");
+    if (bp->rays > 65536u) return fail(RTMI_ERR_UNSUPPORTED, "bake: rays above 65536");
+    if (bp->maxdepth > RTMI_MAX_PASSES) return fail(RTMI_ERR_UNSUPPORTED, "bake: maxdepth above 32");
+    if (M >= (1ull << 31) || M * bp->rays >= (1ull << 31)) return fail(RTMI_ERR_UNSUPPORTED, "bake: M * rays must stay below 2^31");
+    return RTMI_OK;
+}
+
+// Both variants.  render_rays()'s batch loop with k_bake_rays where k_rays_begin stands: batches of whole elements on the
+// library's stream 0, per batch k_bake_rays, then per pass the scene's closest-hit launch and k_shade_rays (after pass 0:
+// k_bake_open), then k_accum for light.  Device variant: the elements and outputs are the caller's buffers, used in place; with
+// orig / dir given the rays are written there and pass 0 traces them there.  Host variant: a batch's elements are staged in
+// the host variants' per-pixel buffers of the handle (acc: pos4, asq: nrm4; tile: light, acnt: open; no call keeps anything in
+// them between calls), its rays in the workspace queue, copied out before pass 2 reuses that queue.
+static int bake(rtmi_scene_t* s, uint64_t M, const void* pos4, const void* nrm4, uint64_t seed, const rtmi_bake_t* bp,
+                const rtmi_bake_out_t* out, void* hip_stream, rtmi_stats_t* stats, bool host) {
+    bool empty;
+    int rc = check_bake(s, M, pos4, nrm4, bp, out, stats, empty);
+    if (rc != RTMI_OK || empty) return rc;
+    RTMI_GUARD_BEGIN
+    (void)hipGetLastError();
+    HIPCHK(hipSetDevice(s->device));
+    const uint32_t K = bp->rays, maxdepth = bp->maxdepth;
+    const bool tri = bp->mode == RTMI_BAKE_TRIANGLES;
+    const uint32_t pstride = tri ? 3u : 1u;  // float4 of pos4 per element
+    const bool shade = maxdepth != 0 && out->light, want_rays = out->orig || out->dir;
+    const bool traced = shade || out->open, counting = (s->options & RTMI_OPT_COUNTERS) != 0;
+    const uint64_t n = M * K;
+    Work& w = s->w[0];
+    hipStream_t st = s->istream[0], ust = host ? st : (hipStream_t)hip_stream;
+    // batches hold whole elements: batch_paths rounded down to a multiple of K, at least K
+    const uint64_t B = std::min<uint64_t>(std::max<uint64_t>(s->tune.batch_paths / K * K, K), n), mB = B / K;
+    if (traced || want_rays) {
+        rc = ensure_workspace(w, (size_t)B, std::max(maxdepth, 1u));
+        if (rc != RTMI_OK) return rc;
+    }
+    if (host) {
+        HIPCHK(s->acc.ensure(mB * pstride));
+        HIPCHK(s->asq.ensure(mB));
+        if (shade) HIPCHK(s->tile.ensure(mB));
+        if (out->open) HIPCHK(s->acnt.ensure(mB));
+    }
+    s->active_streams = 1;
+    // the library's stream starts after whatever the caller queued on its stream, and that stream waits for it
+    HIPCHK(hipEventRecord(s->fork_ev, ust));
+    if (!host) HIPCHK(hipStreamWaitEvent(st, s->fork_ev, 0));
+    if (maxdepth == 0 && out->light) {  // project_ray returns black immediately (raytrace.rs:1261-1263)
+        if (host) memset(out->light, 0, M * 16);
+        else HIPCHK(hipMemsetAsync(out->light, 0, M * 16, st));
+    }
+    DView dv{};  // what shade_pass<Samp::RAYS> reads of it: the depth, and the group size with its divisor
+    dv.maxdepth = maxdepth; dv.spp = K;
+    view_set_divisors(dv);
+    const dim3 ew_grid((unsigned)(s->num_cu * 8)), ew_block(256);
+    const uint32_t npass = shade ? maxdepth : traced ? 1u : 0u, epb = bake_step_elems(K);
+    const FastDiv dK = make_fastdiv(K);
+    rtmi_stats_t sum{};
+    float trace_ms = 0.f;
+    uint32_t launches = 0;
+    for (uint64_t base = 0; base < n && (traced || want_rays); base += B) {
+        const uint32_t nb = (uint32_t)std::min<uint64_t>(B, n - base), mb = nb / K;
+        const uint64_t mbase = base / K;
+        const float4 *pos = (const float4*)pos4 + mbase * pstride, *nrm = (const float4*)nrm4 + mbase;
+        float4* light = shade ? (float4*)out->light + mbase : nullptr;
+        float* open = out->open ? (float*)out->open + mbase : nullptr;
+        float4 *qo = out->orig && !host ? (float4*)out->orig + base : w.qo[0].p, *qd = out->dir && !host ? (float4*)out->dir + base : w.qd[0].p;
+        if (host) {
+            HIPCHK(hipMemcpyAsync(s->acc.p, pos, (size_t)mb * pstride * 16, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(s->asq.p, nrm, (size_t)mb * 16, hipMemcpyHostToDevice, st));
+            pos = s->acc.p; nrm = s->asq.p;
+            light = light ? s->tile.p : nullptr;
+            open = open ? (float*)s->acnt.p : nullptr;
+        }
+        HIPCHK(hipMemsetAsync(w.ctrl.p, 0, sizeof(DCtrl), st));
+        const dim3 gen_grid(std::min<unsigned>((unsigned)(s->num_cu * 8), (mb + epb - 1u) / epb));
+        if (tri)
+            hipLaunchKernelGGL(k_bake_rays<true>, gen_grid, ew_block, 0, st, mb, K, dK, epb, pos, nrm, seed, (uint32_t)(bp->pixel0 + mbase), bp->bias,
+                               qo, qd, w.qpath[0].p, w.ctrl.p);
+        else
+            hipLaunchKernelGGL(k_bake_rays<false>, gen_grid, ew_block, 0, st, mb, K, dK, epb, pos, nrm, seed, (uint32_t)(bp->pixel0 + mbase), bp->bias,
+                               qo, qd, w.qpath[0].p, w.ctrl.p);
+        HIPCHK(hipGetLastError());
+        if (host) {  // before pass 2 writes its queue over them
+            if (out->orig) HIPCHK(hipMemcpyAsync((float4*)out->orig + base, qo, (size_t)nb * 16, hipMemcpyDeviceToHost, st));
+            if (out->dir) HIPCHK(hipMemcpyAsync((float4*)out->dir + base, qd, (size_t)nb * 16, hipMemcpyDeviceToHost, st));
+        }
+        for (uint32_t pass = 0; pass < npass; pass++) {
+            const int a = pass & 1, b = a ^ 1;
+            const float4 *pqo = pass ? w.qo[a].p : qo, *pqd = pass ? w.qd[a].p : qd;  // pass 0 traces the rays where they are
+            HIPCHK(hipEventRecord(w.pass_ev[2 * pass], st));
+            launch_trace(s, w, st, pqo, pqd, (int)pass, counting, w.pass_ev[2 * pass + 1]);
+            HIPCHK(hipGetLastError());
+            if (pass == 0 && open)  // before pass 1 rewrites the hit records
+                hipLaunchKernelGGL(k_bake_open, dim3(std::min<unsigned>((unsigned)(s->num_cu * 8), (mb + RTMI_BAKE_OPEN_ELEMS - 1u) / RTMI_BAKE_OPEN_ELEMS)),
+                                   ew_block, 0, st, mb, K, w.hit_tf.p, open);
+            if (shade)
+                hipLaunchKernelGGL(k_shade_rays, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(bp->pixel0 + mbase), nb, (int)pass, pqo, pqd,
+                                   w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p,
+                                   SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, (const uint32_t*)nullptr);
+            HIPCHK(hipGetLastError());
+        }
+        if (shade) hipLaunchKernelGGL(k_accum, ew_grid, ew_block, 0, st, mb, K, w.scol.p, (float*)light, 0u, mb, 1u, 0u, make_fastdiv(mb));
+        HIPCHK(hipGetLastError());
+        if (host) {
+            if (shade) HIPCHK(hipMemcpyAsync((float4*)out->light + mbase, light, (size_t)mb * 16, hipMemcpyDeviceToHost, st));
+            if (open) HIPCHK(hipMemcpyAsync((float*)out->open + mbase, open, (size_t)mb * 4, hipMemcpyDeviceToHost, st));
+        }
+        // the batch's counters and the time of every pass's closest-hit launch; the next batch reuses the workspace
+        DCtrl h;
+        HIPCHK(hipMemcpyAsync(&h, w.ctrl.p, sizeof(DCtrl), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (npass) add_counters(sum, ctrl_counters(h));
+        for (uint32_t pass = 0; pass < npass; pass++) {
+            float pm = 0.f;
+            HIPCHK(hipEventElapsedTime(&pm, w.pass_ev[2 * pass], w.pass_ev[2 * pass + 1]));
+            launches++;
+            trace_ms += pm;
+            if (s->verbose) fprintf(stderr, "[rtmi] bake batch@%llu pass %u: %u rays, trace %.3f ms\n", (unsigned long long)base, pass, h.count[pass], pm);
+        }
+    }
+    if (!host) {
+        HIPCHK(hipEventRecord(s->join_ev[0], st));
+        HIPCHK(hipStreamWaitEvent(ust, s->join_ev[0], 0));
+    }
+    HIPCHK(hipEventRecord(s->end_ev, ust));
+    HIPCHK(hipEventSynchronize(s->end_ev));
+    float kernel_ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&kernel_ms, s->fork_ev, s->end_ev));
+    if (stats) {
+        add_counters(*stats, sum);
+        stats->kernel_ms = kernel_ms; stats->trace_ms = trace_ms; stats->trace_launches = launches; stats->streams = 1;
+        stats->pipeline = 1u;
+    }
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+int rtmi_bake_device(rtmi_scene_t* s, uint64_t M, const void* pos4_device, const void* nrm4_device, uint64_t seed, const rtmi_bake_t* bake_params,
+                     const rtmi_bake_out_t* out_device, void* hip_stream, rtmi_stats_t* stats) {
+    return bake(s, M, pos4_device, nrm4_device, seed, bake_params, out_device, hip_stream, stats, false);
+}
+
+int rtmi_bake(rtmi_scene_t* s, uint64_t M, const float* pos4, const float* nrm4, uint64_t seed, const rtmi_bake_t* bake_params,
+              const rtmi_bake_out_t* out_host, rtmi_stats_t* stats) {
+    return bake(s, M, pos4, nrm4, seed, bake_params, out_host, nullptr, stats, true);
 }
 
 // rtmi_trace on device buffers: the rays are read where they are, one closest-hit launch, one elementwise kernel

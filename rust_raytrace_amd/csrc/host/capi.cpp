@@ -611,6 +611,29 @@ int rth_caster_walk_rays_explicit_device(rth_scene_t* s, uint64_t n, const void*
     });
 }
 
+int rth_caster_bake(rth_scene_t* s, uint64_t M, const float* pos4, const float* nrm4, const rtmi_bake_t* bake, const rtmi_bake_out_t* out_host,
+                    rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!bake || !out_host) throw std::runtime_error("NULL bake or out");
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).bake(s->scene, M, pos4, nrm4, *bake, *out_host, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
+int rth_caster_bake_device(rth_scene_t* s, uint64_t M, const void* pos4_device, const void* nrm4_device, const rtmi_bake_t* bake,
+                           const rtmi_bake_out_t* out_device, void* hip_stream, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!bake || !out_device) throw std::runtime_error("NULL bake or out");
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).bake_device(s->scene, M, pos4_device, nrm4_device, *bake, *out_device, hip_stream, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
+
 int rth_caster_trace_records(rth_scene_t* s, uint64_t n, const float* o4, const float* d4, rtmi_ray_record_t* recs, uint32_t* leaf_ids,
                              uint64_t leaf_cap, uint64_t* leaf_total, rtmi_stats_t* stats) {
     return guarded([&] {

@@ -791,6 +791,28 @@ void HipRayCaster::walk_rays_explicit_device(const Scene& s, uint64_t n, const v
     progress.stats = st;
 }
 
+void HipRayCaster::bake(const Scene& s, uint64_t M, const float* pos4, const float* nrm4, const rtmi_bake_t& bake, const rtmi_bake_out_t& out_host,
+                        ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    rtmi_stats_t st;
+    const int rc = rtmi_bake(h, M, pos4, nrm4, seed, &bake, &out_host, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_bake: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
+void HipRayCaster::bake_device(const Scene& s, uint64_t M, const void* pos4_device, const void* nrm4_device, const rtmi_bake_t& bake,
+                               const rtmi_bake_out_t& out_device, void* hip_stream, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    rtmi_stats_t st;
+    const int rc = rtmi_bake_device(h, M, pos4_device, nrm4_device, seed, &bake, &out_device, hip_stream, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_bake_device: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
 void HipRayCaster::walk_rays_ao(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
                                 const rtmi_ao_t& ao, float* out, ProgressCtx& progress) {
     rtmi_scene_t* h = resident(s);

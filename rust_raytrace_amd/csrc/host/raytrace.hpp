@@ -241,6 +241,13 @@ public:
                             const rtmi_rays_out_t* out_host, ProgressCtx& progress);
     void walk_rays_explicit_device(const Scene& s, uint64_t n, const void* orig4_device, const void* dir4_device, const void* keys_device,
                                    const rtmi_rays_t* rays, const rtmi_rays_out_t* out_device, void* hip_stream, ProgressCtx& progress);
+    // Light baked at M surface points or over M triangles (rtmi_bake / rtmi_bake_device, which rtmi.h defines) with the caster's
+    // seed: bake.rays gather rays per element made on the device, path-traced and folded to light / open; the rays themselves on
+    // request.  pos4: M float4 (points) or 3 M float4 (triangle corners); nrm4: M float4, the side to bake.
+    void bake(const Scene& s, uint64_t M, const float* pos4, const float* nrm4, const rtmi_bake_t& bake, const rtmi_bake_out_t& out_host,
+              ProgressCtx& progress);
+    void bake_device(const Scene& s, uint64_t M, const void* pos4_device, const void* nrm4_device, const rtmi_bake_t& bake,
+                     const rtmi_bake_out_t& out_device, void* hip_stream, ProgressCtx& progress);
     // Ambient occlusion (rtmi_render_ao / rtmi_render_ao_device, which rtmi.h defines): one float per pixel, the share of
     // ao.rays hemisphere rays per primary sample of [sample0, sample0 + nsamples) that are not occluded within ao.radius.
     void walk_rays_ao(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,

@@ -1494,6 +1494,118 @@ class HipRayCaster:
                                                              C.byref(st), C.byref(wall)))
         return ProgressCtx(st.rays, wall.value, st.as_dict())
 
+    BAKE_MODES = {"points": _ffi.BAKE_POINTS, "triangles": _ffi.BAKE_TRIANGLES}
+    BAKE_OUTPUTS = ("light", "open", "orig", "dir")
+
+    @staticmethod
+    def bake_params(mode="points", rays=None, maxdepth=None, pixel0=None, bias=None):
+        """rtmi_bake_t from the library's defaults (rtmi_bake_defaults: points, 64 rays, maxdepth 4, pixel0 0, bias 0.001) with
+        the given fields replaced.  Raises ValueError for what the library would refuse."""
+        if mode not in HipRayCaster.BAKE_MODES:
+            raise ValueError(f"mode must be one of {sorted(HipRayCaster.BAKE_MODES)}")
+        b = _ffi.Bake()
+        _ffi.lib().rtmi_bake_defaults(C.byref(b))
+        b.mode = HipRayCaster.BAKE_MODES[mode]
+        if rays is not None:
+            if not 1 <= int(rays) <= 65536:
+                raise ValueError("rays must be in [1, 65536]")
+            b.rays = int(rays)
+        if maxdepth is not None:
+            if not 0 <= int(maxdepth) <= 32:
+                raise ValueError("maxdepth must be in [0, 32]")
+            b.maxdepth = int(maxdepth)
+        if pixel0 is not None:
+            if not 0 <= int(pixel0) < 1 << 32:
+                raise ValueError("pixel0 must be in [0, 2^32)")
+            b.pixel0 = int(pixel0)
+        if bias is not None:
+            if not np.isfinite(float(bias)):
+                raise ValueError("bias must be finite")
+            b.bias = float(bias)
+        return b
+
+    @staticmethod
+    def _bake_count(b, npos, nnrm):
+        """M of a bake call whose pos4 holds npos float4 and nrm4 nnrm float4"""
+        per = 3 if b.mode == _ffi.BAKE_TRIANGLES else 1
+        if npos != per * nnrm:
+            raise ValueError("pos4 must hold one float4 per element (points) or three (triangles), nrm4 one per element")
+        if nnrm * b.rays >= 1 << 31:
+            raise ValueError("elements * rays must stay below 2^31")
+        if nnrm and b.pixel0 + nnrm - 1 >= 1 << 32:
+            raise ValueError("pixel0 + M - 1 must stay below 2^32")
+        return nnrm
+
+    def bake(self, s, pos4, nrm4, params, light=True, open=False, orig=False, dir=False):
+        """Light baked at surface points or over triangles (rtmi_bake; include/rtmi.h defines it).  params: bake_params().
+        nrm4: (M, 4) float32, the side to bake of each element, used as given.  pos4: (M, 4) float32 points, or (3 M, 4), the
+        corners of M triangles.  Per element params.rays gather rays are made on the device and path-traced at depth
+        params.maxdepth.  Outputs, each produced when its flag is true: light (M, 4) float32, the mean colour arriving; open (M,)
+        float32, the share of the element's rays that hit nothing; orig and dir (M * rays, 4), the gather rays themselves.
+        Returns (dict of the requested arrays, ctx)."""
+        p4, n4 = _f(pos4).reshape(-1, 4), _f(nrm4).reshape(-1, 4)
+        m = self._bake_count(params, p4.shape[0], n4.shape[0])
+        n = m * params.rays
+        shapes = {"light": (m, 4), "open": (m,), "orig": (n, 4), "dir": (n, 4)}
+        want = dict(light=light, open=open, orig=orig, dir=dir)
+        bufs = {k: np.zeros(shapes[k], np.float32) for k in self.BAKE_OUTPUTS if want[k]}
+        if not bufs:
+            raise ValueError("at least one of light, open, orig and dir must be produced")
+        out = _ffi.BakeOut(*[_p(bufs[k]) if k in bufs else None for k in self.BAKE_OUTPUTS])
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_bake(s.h, m, _p(p4), _p(n4), C.byref(params), C.byref(out), C.byref(st), C.byref(wall)))
+        return bufs, ProgressCtx(st.rays, wall.value, st.as_dict())
+
+    def bake_device(self, s, pos4, nrm4, params, light=None, open=None, orig=None, dir=None, stream=None):
+        """The same on torch tensors on the scene's device (rtmi_bake_device), read and written in place: nrm4 contiguous
+        float32 of M * 4 elements, pos4 of M * 4 (points) or 3 M * 4 (triangles); each output a contiguous float32 tensor or None
+        (not all): light of M * 4, open of M, orig and dir of M * rays * 4; no two buffers may overlap.  The work starts after
+        what is queued on `stream` (a torch stream, a raw HIP stream pointer or None) and that stream waits for it.
+        Returns ctx."""
+        for name, x in (("pos4", pos4), ("nrm4", nrm4)):
+            if not hasattr(x, "data_ptr") or x.numel() % 4:
+                raise ValueError(f"{name} must be a contiguous float32 tensor of whole float4 on the device")
+            self._tensor(name, x, x.numel(), ("torch.float32",))
+        m = self._bake_count(params, pos4.numel() // 4, nrm4.numel() // 4)
+        n = m * params.rays
+        spec = (("light", light, 4 * m), ("open", open, m), ("orig", orig, 4 * n), ("dir", dir, 4 * n))
+        for name, x, want in spec:
+            if x is not None:
+                self._tensor(name, x, want, ("torch.float32",))
+        if all(x is None for _, x, _ in spec):
+            raise ValueError("at least one of light, open, orig and dir must be given")
+        spans = sorted([(pos4.data_ptr(), 4 * pos4.numel()), (nrm4.data_ptr(), 16 * m)] +
+                       [(x.data_ptr(), 4 * want) for _, x, want in spec if x is not None])
+        if any(a[0] + a[1] > b[0] for a, b in zip(spans, spans[1:]) if a[1] and b[1]):
+            raise ValueError("the buffers must not overlap")
+        self._config(s)
+        out = _ffi.BakeOut(*[x.data_ptr() if x is not None else None for _, x, _ in spec])
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_bake_device(s.h, m, C.c_void_p(pos4.data_ptr()), C.c_void_p(nrm4.data_ptr()), C.byref(params),
+                                               C.byref(out), C.c_void_p(getattr(stream, "cuda_stream", stream) or 0), C.byref(st),
+                                               C.byref(wall)))
+        return ProgressCtx(st.rays, wall.value, st.as_dict())
+
+    def bake_triangles(self, s, corners, normals, rays=None, maxdepth=None, pixel0=None, bias=None, light=True, open=False,
+                       orig=False, dir=False):
+        """bake() over whole triangles: corners (M, 3, 3) or (M, 3, 4) float32, normals (M, 3) or (M, 4), the side of each
+        triangle to bake (its `norm` or the negative); three-component vectors get lane 3 = +0.  One colour per face, for a
+        flat-shaded view of the scene.  Returns (dict of the requested arrays, ctx)."""
+        c = _f(corners)
+        if c.ndim != 3 or c.shape[1] != 3 or c.shape[2] not in (3, 4):
+            raise ValueError("corners must be (M, 3, 3) or (M, 3, 4)")
+        nn = _f(normals)
+        if nn.ndim != 2 or nn.shape[0] != c.shape[0] or nn.shape[1] not in (3, 4):
+            raise ValueError("normals must be (M, 3) or (M, 4), one per triangle")
+        p4 = np.zeros((c.shape[0] * 3, 4), np.float32)
+        p4[:, : c.shape[2]] = c.reshape(-1, c.shape[2])
+        n4 = np.zeros((c.shape[0], 4), np.float32)
+        n4[:, : nn.shape[1]] = nn
+        return self.bake(s, p4, n4, self.bake_params("triangles", rays, maxdepth, pixel0, bias), light=light, open=open, orig=orig, dir=dir)
+
     def _records(self, n, call, pixel=None):
         """Size query, then the fill (rth_caster_*_records)"""
         recs = np.zeros(n, REC_DTYPE)
