@@ -30,8 +30,9 @@ enum {
     RTMI_ERR_DEVICE = 5        /* any other HIP runtime / kernel failure    */
 };
 
-/* SurfaceKind (raytrace.rs:303-308) */
-enum { RTMI_SOLID = 0, RTMI_MATTE = 1, RTMI_REFLECTIVE = 2 };
+/* SurfaceKind (raytrace.rs:303-308), and one kind the reference does not have: RTMI_DIELECTRIC, clear or tinted glass, whose
+ * `scattering` field carries the INDEX OF REFRACTION (the definition follows the sphere record below). */
+enum { RTMI_SOLID = 0, RTMI_MATTE = 1, RTMI_REFLECTIVE = 2, RTMI_DIELECTRIC = 3 };
 
 /* One `Triangle` (raytrace.rs:326-337) reduced to the fields the hot path
  * reads (intersects/normal/getsurface, raytrace.rs:399-461).  Lane 3 of every
@@ -44,10 +45,10 @@ typedef struct rtmi_triangle {
     float sides[3][3];
     float side_lens[3];
     float edge_thickness;
-    uint32_t surface_kind; /* RTMI_SOLID / RTMI_MATTE / RTMI_REFLECTIVE */
+    uint32_t surface_kind; /* RTMI_SOLID / RTMI_MATTE / RTMI_REFLECTIVE / RTMI_DIELECTRIC */
     float color[3];
-    float alpha;      /* Matte, Reflective */
-    float scattering; /* Reflective */
+    float alpha;      /* Matte, Reflective, Dielectric */
+    float scattering; /* Reflective; Dielectric: the index of refraction `ior`, finite and > 0 */
 } rtmi_triangle_t;
 
 /* One `BoundingBox` (raytrace.rs:618-623), flattened.  Inner box: its children
@@ -127,11 +128,60 @@ typedef struct rtmi_tile {
 typedef struct rtmi_sphere {
     float center[3];
     float radius;
-    uint32_t surface_kind; /* RTMI_SOLID / RTMI_MATTE / RTMI_REFLECTIVE */
+    uint32_t surface_kind; /* RTMI_SOLID / RTMI_MATTE / RTMI_REFLECTIVE / RTMI_DIELECTRIC */
     float color[3];
     float alpha;
-    float scattering;
+    float scattering; /* Reflective; Dielectric: the index of refraction `ior`, finite and > 0 */
 } rtmi_sphere_t;
+
+/* RTMI_DIELECTRIC: refraction and Fresnel reflection.  NOT part of the reference, which has no surface that
+ * transmits light, so this build defines one, operation by operation like the camera models and the bake.  `color` and `alpha`
+ * mean what they mean for Matte and Reflective -- the level's terms in color_ray's mix_color(color, c, alpha): alpha = 1 is clear
+ * glass, smaller values tint it -- and `scattering` carries the index of refraction `ior`.  rtmi_scene_create and
+ * rtmi_scene_set_spheres refuse an ior that is NaN, infinite or <= 0 with RTMI_ERR_INVALID and name the first offender; kinds
+ * above 3 stay "unknown surface kind".  The surface table's key of a dielectric includes alpha and ior, so distinct glasses stay
+ * distinct surfaces.
+ *
+ * Everything but the bounce ray is Matte's: the surface is pushed on the path's stack, an exhausted depth is black, the fold
+ * is the existing loop, the edge faces of a glass triangle stay Solid black.  The bounce ray of the hit of a path's ray number
+ * `pass` with remaining depth maxdepth - pass - 1 != 0 -- (ro, rd) the ray, point = rd * t + ro, norm the surface's normal
+ * (already * -1.f on a back face, `face & 1`; an analytic sphere's is (point - center).unit(), and its far root is the back
+ * face, so a glass ball refracts in and out), rv = random_vec of RNG block pass + 1 -- uses only + - * / and sqrt in f32, no
+ * contraction, every step rounded on all four lanes:
+ *     ci   = fabsf(vdot(rd, norm))                         (reflect_ray's ddot)
+ *     eta  = (face & 1) ? ior : 1.f / ior                  (front face: entering the solid; back face: leaving it)
+ *     s2   = 1.f - ci * ci
+ *     k    = 1.f - (eta * eta) * s2
+ *     tir  = !(k >= 0.f)                                   (total internal reflection; a NaN reflects)
+ *     ct   = sqrtf(k)                                      (cosine of the transmitted angle; unused when tir)
+ *     cs   = (face & 1) ? ct : ci                          (Schlick takes the cosine on the thin side)
+ *     r0   = (1.f - ior) / (1.f + ior);  r0 = r0 * r0
+ *     x    = 1.f - cs;  x2 = x * x;  x5 = (x2 * x2) * x
+ *     R    = r0 + (1.f - r0) * x5
+ *     u    = unit float (top 24 bits * 2^-24) of WORD 3 of RNG block pass + 1 of (seed, pixel, sample): the block random_vec
+ *            already draws words 0-2 of; no new block, and no other draw moves
+ *     reflect iff tir || u < R
+ * Reflected ray: reflect_ray's statements (raytrace.rs:278-290) with scattering = 0.f, the double normalisation included.
+ * Refracted ray:
+ *     perp = vmul(vadd(rd, vmul(norm, ci)), eta)
+ *     par  = vmul(norm, -ct)
+ *     td   = vunit(vadd(perp, par))
+ *     ray  = make_ray(vadd(point, vmul(td, 0.001f)), td)   (the origin is offset along the new direction, as every bounce's)
+ * There are no clamps and no special cases.  As a consequence a ci that is a rounding error above 1 gives a slightly negative s2
+ * and x, and ior = 1.f runs the same arithmetic (eta = 1, r0 = 0, R = x5).
+ * FRONT MEANS OUTSIDE: the front face of a triangle (the side its `norm` points to) is taken to be the outside of the solid.  A
+ * mesh whose norms point into the solid behaves as a bubble of the inverse index.
+ *
+ * A scene with at least one dielectric triangle or sphere renders on the per-pass pipeline (stats.pipeline = 1, slow_paths = 0;
+ * zero-component rays are traced in place) with the glass shading kernels (k_shade*_glass), whatever the scene kind and options:
+ * rtmi_render, _device, _tile_device, rtmi_render_samples*, rtmi_render_adaptive*, rtmi_render_views*, rtmi_render_frame_multi,
+ * rtmi_render_camera*, rtmi_render_rays*, rtmi_bake* and the two denoised wrappers all gain it.  Scenes without one take exactly
+ * the path they took before the kind existed.
+ * Unchanged: rtmi_trace*, rtmi_occluded* and the records; rtmi_render_features*, _ao*, _light*, _preview*, which read first hits
+ * only -- glass shows its `color` as albedo and occludes AO and shadow rays like any other surface.
+ * rtmi_render_shadowed* returns RTMI_ERR_UNSUPPORTED for a scene with a dielectric, before any HIP call.
+ * Not here: transparent shadows, Beer-Lambert absorption, rough glass, nested media (no stack of indices: every back face leaves
+ * into ior 1), glass in the path kernels (pipeline 3), glass under rtmi_render_shadowed*. */
 
 typedef struct rtmi_scene rtmi_scene_t;
 

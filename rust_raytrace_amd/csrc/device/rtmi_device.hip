@@ -592,7 +592,8 @@ namespace rtmi {
                           uint32_t* __restrict__ qpath_n, uint16_t* __restrict__ mstack, float4* __restrict__ scol,    \
                           DCtrl* __restrict__ ctrl, SlowQ slow
 #define RTMI_SHADE_ARGS sc, v, seed, pix0, npaths, pass, qo, qd, qpath, hit_tf, hit_t, qo_n, qd_n, qpath_n, mstack, scol, ctrl, slow
-template <Samp S>
+// GLASS (k_shade*_glass): shade_hit<true>, which knows RTMI_DIELECTRIC; the launch sites pick them for scenes with a dielectric
+template <Samp S, bool GLASS = false>
 __device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list = nullptr, const ViewTab& vt = ViewTab{}) {
     __shared__ uint32_t s_cnt[4], s_base;
     const uint32_t count = ctrl->count[pass];
@@ -616,14 +617,14 @@ __device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __
             if constexpr (S == Samp::RAYS) {  // `list` = the batch's RNG keys (or null), pix0 = the key of its first group
                 uint32_t pixel, sample;
                 rays_key(v, pix0, path, list, pixel, sample);
-                push = shade_hit(sc, v.maxdepth, seed, npaths, path, pixel, sample, (uint32_t)pass, tf, t, V4{o4.x, o4.y, o4.z, o4.w},
-                                 V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr);
+                push = shade_hit<GLASS>(sc, v.maxdepth, seed, npaths, path, pixel, sample, (uint32_t)pass, tf, t, V4{o4.x, o4.y, o4.z, o4.w},
+                                        V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr);
             } else {
             uint32_t prow, pcol, sample;
             path_pixel<S>(v, pix0, path, prow, pcol, sample, list);
             const PixKey key = pixel_key<S>(v, prow, vt);
-            push = shade_hit(sc, v.maxdepth, key_seed<S>(key, vt, seed), npaths, path, key.row * v.width + pcol, sample, (uint32_t)pass, tf, t,
-                             V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr);
+            push = shade_hit<GLASS>(sc, v.maxdepth, key_seed<S>(key, vt, seed), npaths, path, key.row * v.width + pcol, sample, (uint32_t)pass, tf, t,
+                                    V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr);
             }
             // a bounce ray with an exactly-zero direction component goes to the slow path (SlowQ), not to the next pass
             if (push && slow.cap && has_zero_component(nr.dir.x, nr.dir.y, nr.dir.z) &&
@@ -661,6 +662,12 @@ __global__ void __launch_bounds__(256) k_shade_list(RTMI_SHADE_PARAMS, const uin
 __global__ void __launch_bounds__(256) k_shade_views(RTMI_SHADE_PARAMS, ViewTab vt) { shade_pass<Samp::VIEWS>(RTMI_SHADE_ARGS, nullptr, vt); }
 // Samp::RAYS (rtmi_render_rays*): v carries maxdepth, spp = the group size and dspp only; keys = the batch's RNG keys or null
 __global__ void __launch_bounds__(256) k_shade_rays(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ keys) { shade_pass<Samp::RAYS>(RTMI_SHADE_ARGS, keys); }
+// The same five for scenes with a dielectric surface (RTMI_DIELECTRIC)
+__global__ void __launch_bounds__(256) k_shade_glass(RTMI_SHADE_PARAMS) { shade_pass<Samp::FRAME, true>(RTMI_SHADE_ARGS); }
+__global__ void __launch_bounds__(256) k_shade_samples_glass(RTMI_SHADE_PARAMS) { shade_pass<Samp::PASS, true>(RTMI_SHADE_ARGS); }
+__global__ void __launch_bounds__(256) k_shade_list_glass(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list) { shade_pass<Samp::LIST, true>(RTMI_SHADE_ARGS, list); }
+__global__ void __launch_bounds__(256) k_shade_views_glass(RTMI_SHADE_PARAMS, ViewTab vt) { shade_pass<Samp::VIEWS, true>(RTMI_SHADE_ARGS, nullptr, vt); }
+__global__ void __launch_bounds__(256) k_shade_rays_glass(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ keys) { shade_pass<Samp::RAYS, true>(RTMI_SHADE_ARGS, keys); }
 
 // walk_ray_set's per-pixel accumulation (raytrace.rs:1414-1426): acc = 0; acc += sample_i in sample order; * (1/spp).
 // The sample colours of a pixel are consecutive in `scol` ([pixel][sample]), so one thread per pixel would read 16 B at a
@@ -1059,6 +1066,8 @@ struct rtmi_scene {
     DevBuf<uint32_t> refs;
     DevBuf<float4> tplane, tedge, mats, spheres;
     std::vector<float4> hmats;  // the triangles' surface table (host copy): sphere surfaces are appended to it
+    // a triangle / a triangle or a sphere is RTMI_DIELECTRIC: such a scene renders on the per-pass pipeline with k_shade*_glass
+    bool tris_dielectric = false, has_dielectric = false;
     std::vector<rtmi_triangle_t> htris;  // the records (host copy): the fast-mode BVH is rebuilt from them when corners arrive
     DevBuf<uint4> fnodes, oblocks, ocull;  // (fnodes: the node records, then the node cull records)
     DevBuf<uint32_t> wlinks, cert;
@@ -1662,14 +1671,20 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
 
     std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t>, uint32_t> matmap;
     std::vector<float4> hm, hp(2 * ntris), he(4 * ntris);
+    bool has_dielectric = false;
     auto bits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
     auto fbits = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
     for (uint64_t i = 0; i < ntris; i++) {
         const rtmi_triangle_t& t = tris[i];
-        if (t.surface_kind > RTMI_REFLECTIVE) return fail(RTMI_ERR_INVALID, "unknown surface kind");
+        if (t.surface_kind > RTMI_DIELECTRIC) return fail(RTMI_ERR_INVALID, "unknown surface kind");
+        if (t.surface_kind == RTMI_DIELECTRIC) {  // scattering carries the index of refraction
+            if (!(std::isfinite(t.scattering) && t.scattering > 0.f))
+                return fail(RTMI_ERR_INVALID, "triangle " + std::to_string(i) + ": a dielectric's index of refraction (scattering) must be finite and > 0");
+            has_dielectric = true;
+        }
         // fields a kind does not carry do not distinguish materials
         const float alpha = t.surface_kind == RTMI_SOLID ? 0.f : t.alpha;
-        const float scat = t.surface_kind == RTMI_REFLECTIVE ? t.scattering : 0.f;
+        const float scat = t.surface_kind >= RTMI_REFLECTIVE ? t.scattering : 0.f;
         auto key = std::make_tuple(t.surface_kind, bits(t.color[0]), bits(t.color[1]), bits(t.color[2]), bits(alpha), bits(scat));
         auto it = matmap.find(key);
         uint32_t mid;
@@ -1815,6 +1830,7 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
                   s->octree ? s->fnodes.p : nullptr, s->octree ? s->oblocks.p : nullptr, s->octree ? s->wlinks.p : nullptr, nullptr, 0u, boxes[0].len2, max_inner_depth + 1, (uint32_t)hob.size(), bcull ? s->ocull.p : nullptr, cert_on ? s->cert.p : nullptr,
                   fcull_on ? s->fnodes.p + fcull_at : nullptr};
     s->hmats = hm;
+    s->tris_dielectric = s->has_dielectric = has_dielectric;
     s->leaf_box = std::move(of.leafbox);
     if (s->octree) {
         // 2 words per level per lane (frame stack) + 3 per lane (leaf memo: key, t, tri | face; trace_oct.hpp)
@@ -1883,10 +1899,16 @@ int rtmi_scene_set_spheres(rtmi_scene_t* s, const rtmi_sphere_t* sp, uint64_t n)
     RTMI_GUARD_BEGIN
     auto fbits = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
     std::vector<float4> mats = s->hmats, rec(2 * n);
+    bool has_dielectric = s->tris_dielectric;
     for (uint64_t i = 0; i < n; i++) {
-        if (sp[i].surface_kind > RTMI_REFLECTIVE) return fail(RTMI_ERR_INVALID, "unknown surface kind");
+        if (sp[i].surface_kind > RTMI_DIELECTRIC) return fail(RTMI_ERR_INVALID, "unknown surface kind");
+        if (sp[i].surface_kind == RTMI_DIELECTRIC) {  // scattering carries the index of refraction
+            if (!(std::isfinite(sp[i].scattering) && sp[i].scattering > 0.f))
+                return fail(RTMI_ERR_INVALID, "sphere " + std::to_string(i) + ": a dielectric's index of refraction (scattering) must be finite and > 0");
+            has_dielectric = true;
+        }
         const float alpha = sp[i].surface_kind == RTMI_SOLID ? 0.f : sp[i].alpha;
-        const float scat = sp[i].surface_kind == RTMI_REFLECTIVE ? sp[i].scattering : 0.f;
+        const float scat = sp[i].surface_kind >= RTMI_REFLECTIVE ? sp[i].scattering : 0.f;
         const uint32_t mid = (uint32_t)(mats.size() / 2);
         mats.push_back(make_float4(sp[i].color[0], sp[i].color[1], sp[i].color[2], alpha));
         mats.push_back(make_float4(scat, fbits(sp[i].surface_kind), 0.f, 0.f));
@@ -1904,6 +1926,7 @@ int rtmi_scene_set_spheres(rtmi_scene_t* s, const rtmi_sphere_t* sp, uint64_t n)
     s->d.nmats = (uint32_t)(mats.size() / 2);
     s->d.spheres = s->spheres.p;
     s->d.nspheres = (uint32_t)n;
+    s->has_dielectric = has_dielectric;
     return RTMI_OK;
     RTMI_GUARD_END
 }
@@ -2220,7 +2243,7 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
     // shades the primary rays in one kernel.  Everything else (pipeline 1, linear list, generic tree, BVH mode,
     // analytic spheres) starts with k_gen.  Both then run one closest-hit + one shading launch per bounce pass.
     c.path_kernels = !c.fo && !c.ao && !c.li && !c.pv && !c.sh && !c.cam && s->tune.pipeline != 1u && s->octree && !s->root_is_leaf &&
-                     !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) && s->d.nspheres == 0;
+                     !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) && s->d.nspheres == 0 && !s->has_dielectric;
     // streams = 0 (automatic): one stream for path-kernel tiles of 2^26 paths and more, three otherwise (the per-pass
     // pipelines -- BVH mode: 29.6 ms on three streams, 35.2 on one -- have elementwise kernels to hide).  Since k_shade stopped being
     // atomic-bound (round 3) there is little left for a second stream to hide: the full config-3 frame takes 366.9 ms on one
@@ -2493,14 +2516,16 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
             int rc = dump_pass_counters(s, w, st, t, pass);
             if (rc != RTMI_OK) return rc;
         }
+        const bool glass = s->has_dielectric;  // (never with c.path_kernels: sq is off and k_path_slow, which has no glass arm, never runs)
         if (list)
-            hipLaunchKernelGGL(k_shade_list, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
+            hipLaunchKernelGGL(glass ? k_shade_list_glass : k_shade_list, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
                                w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, list);
         else if (c.mode == Samp::VIEWS)
-            hipLaunchKernelGGL(k_shade_views, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
+            hipLaunchKernelGGL(glass ? k_shade_views_glass : k_shade_views, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
                                w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, c.vt);
         else
-            hipLaunchKernelGGL(c.mode == Samp::PASS ? k_shade_samples : k_shade, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths,
+            hipLaunchKernelGGL(c.mode == Samp::PASS ? (glass ? k_shade_samples_glass : k_shade_samples) : (glass ? k_shade_glass : k_shade),
+                               ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths,
                                (int)pass, w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p,
                                w.mstack.p, w.scol.p, w.ctrl.p, sq);
         HIPCHK(hipGetLastError());
@@ -3056,9 +3081,12 @@ static int check_shadowed(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint32_t s
     if (li->rays != 1) return fail(RTMI_ERR_INVALID, "shadowed: rays must be 1 (the reference draws one shadow ray per hit)");
     return RTMI_OK;
 }
-static int refuse_spheres_shadowed(const rtmi_scene_t* s) {
+// scenes the shadowed shading (shadowed.hpp has its own shade_hit) does not take; before any HIP call
+static int refuse_scene_shadowed(const rtmi_scene_t* s) {
     if (s->d.nspheres)
         return fail(RTMI_ERR_UNSUPPORTED, "shadowed: the scene has analytic spheres (a build-defined primitive whose normal needs the hit point)");
+    if (s->has_dielectric)
+        return fail(RTMI_ERR_UNSUPPORTED, "shadowed: the scene has a dielectric surface (the shadowed shading has no glass arm)");
     return RTMI_OK;
 }
 
@@ -3072,7 +3100,7 @@ int rtmi_render_shadowed_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint
     if (tile->nrows == 0) return RTMI_OK;
     rc = check_view(vp, tile);
     if (rc != RTMI_OK) return rc;
-    rc = refuse_spheres_shadowed(s);
+    rc = refuse_scene_shadowed(s);
     if (rc != RTMI_OK) return rc;
     const ShadowCall call{*li};
     return render_tile(s, vp, seed, tile, sample0, nsamples, (float4*)accum_device, out_device, hip_stream, stats, nullptr, 0, nullptr,
@@ -3091,7 +3119,7 @@ int rtmi_render_shadowed(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t se
     const rtmi_tile_t tile{row0, nrows, nrows, 0u};
     rc = check_view(vp, &tile);
     if (rc != RTMI_OK) return rc;
-    rc = refuse_spheres_shadowed(s);
+    rc = refuse_scene_shadowed(s);
     if (rc != RTMI_OK) return rc;
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(s->acc.ensure(npix));
@@ -3944,7 +3972,7 @@ static int render_rays(rtmi_scene_t* s, uint64_t n, const void* orig4, const voi
                 hipLaunchKernelGGL(k_features, ew_grid, ew_block, 0, st, s->d, ng, G, w.hit_tf.p, w.hit_t.p, (float*)albedo, (float*)normal, ids,
                                    0u, ng, 1u, 0u, make_fastdiv(ng), make_fastdiv(G));
             if (shade)
-                hipLaunchKernelGGL(k_shade_rays, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(rp->pixel0 + gbase), nb, (int)pass, pqo, pqd,
+                hipLaunchKernelGGL(s->has_dielectric ? k_shade_rays_glass : k_shade_rays, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(rp->pixel0 + gbase), nb, (int)pass, pqo, pqd,
                                    w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, scol, w.ctrl.p,
                                    SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, kq);
             HIPCHK(hipGetLastError());
@@ -4126,7 +4154,7 @@ static int bake(rtmi_scene_t* s, uint64_t M, const void* pos4, const void* nrm4,
                 hipLaunchKernelGGL(k_bake_open, dim3(std::min<unsigned>((unsigned)(s->num_cu * 8), (mb + RTMI_BAKE_OPEN_ELEMS - 1u) / RTMI_BAKE_OPEN_ELEMS)),
                                    ew_block, 0, st, mb, K, w.hit_tf.p, open);
             if (shade)
-                hipLaunchKernelGGL(k_shade_rays, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(bp->pixel0 + mbase), nb, (int)pass, pqo, pqd,
+                hipLaunchKernelGGL(s->has_dielectric ? k_shade_rays_glass : k_shade_rays, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(bp->pixel0 + mbase), nb, (int)pass, pqo, pqd,
                                    w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p,
                                    SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, (const uint32_t*)nullptr);
             HIPCHK(hipGetLastError());

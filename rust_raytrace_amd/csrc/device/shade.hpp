@@ -153,6 +153,14 @@ __device__ inline V4 random_vec(uint64_t seed, uint32_t pixel, uint32_t sample, 
     rng_block(seed, pixel, sample, k, w);
     return vunit(mk(u32_to_unit_f32(w[0]) - 0.5f, u32_to_unit_f32(w[1]) - 0.5f, u32_to_unit_f32(w[2]) - 0.5f));
 }
+// random_vec that also hands out word 3 of its block as a unit float: the dielectric's reflect-or-refract draw (include/rtmi.h,
+// RTMI_DIELECTRIC).  random_vec never reads that word, so the draw costs no block and moves no other draw.
+__device__ inline V4 random_vec_u(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t k, float& u3) {
+    uint32_t w[4];
+    rng_block(seed, pixel, sample, k, w);
+    u3 = u32_to_unit_f32(w[3]);
+    return vunit(mk(u32_to_unit_f32(w[0]) - 0.5f, u32_to_unit_f32(w[1]) - 0.5f, u32_to_unit_f32(w[2]) - 0.5f));
+}
 // mix_color (raytrace.rs:299-301)
 __device__ inline V4 mix_color(V4 c1, V4 c2, float a) { return vadd(vmul(c1, 1.f - a), vmul(c2, a)); }
 
@@ -163,6 +171,11 @@ __device__ inline V4 mix_color(V4 c1, V4 c2, float a) { return vadd(vmul(c1, 1.f
 // here: sky, Solid, edge face (Solid black, raytrace.rs:452-457) or depth exhausted (black, raytrace.rs:1261-1263); the
 // nested mix_color calls (raytrace.rs:1233-1251) are then evaluated inside-out over the stack and the sample colour is
 // written to scol[path].  `mirror` (optional): set to true when the path goes on through a Reflective surface.
+// GLASS: the kernels of scenes with a dielectric (k_shade*_glass, rtmi_device.hip) also know RTMI_DIELECTRIC, operation by
+// operation as include/rtmi.h defines it: the level is pushed like Matte's, the bounce ray is the refracted one or, on total
+// internal reflection or with Schlick's probability, reflect_ray's with scattering 0.f.  Without it (every other kernel, the
+// path kernels among them) the arm is not compiled and the function is the one it was.
+template <bool GLASS = false>
 __device__ inline bool shade_hit(const DScene& sc, uint32_t maxdepth, uint64_t seed, uint32_t npaths, uint32_t path, uint32_t pixel,
                                  uint32_t sample, uint32_t pass, uint32_t tf, float t, V4 ro, V4 rd, uint16_t* __restrict__ mstack,
                                  float4* __restrict__ scol, RayV& nr, bool* mirror = nullptr) {
@@ -195,7 +208,35 @@ __device__ inline bool shade_hit(const DScene& sc, uint32_t maxdepth, uint64_t s
                     norm = vunit(vsub(point, mk(sc0.x, sc0.y, sc0.z)));
                 }
                 if (face & 1u) norm = vmul(norm, -1.f);                       // raytrace.rs:441-449
-                const V4 rv = random_vec(seed, pixel, sample, pass + 1u);
+                float u3 = 0.f;
+                V4 rv;
+                if constexpr (GLASS) rv = random_vec_u(seed, pixel, sample, pass + 1u, u3);
+                else rv = random_vec(seed, pixel, sample, pass + 1u);
+                float scat = m1.x;
+                if constexpr (GLASS) {
+                    if (kind == RTMI_DIELECTRIC) {  // m1.x = ior
+                        const float ior = m1.x;
+                        const float ci = fabsf(vdot(rd, norm));
+                        const float eta = (face & 1u) ? ior : 1.f / ior;
+                        const float s2 = 1.f - ci * ci;
+                        const float k = 1.f - (eta * eta) * s2;
+                        const bool tir = !(k >= 0.f);
+                        const float ct = sqrtf(k);
+                        const float cs = (face & 1u) ? ct : ci;
+                        float r0 = (1.f - ior) / (1.f + ior);
+                        r0 = r0 * r0;
+                        const float x = 1.f - cs, x2 = x * x, x5 = (x2 * x2) * x;
+                        const float R = r0 + (1.f - r0) * x5;
+                        if (!(tir || u3 < R)) {
+                            const V4 perp = vmul(vadd(rd, vmul(norm, ci)), eta);
+                            const V4 par = vmul(norm, -ct);
+                            const V4 td = vunit(vadd(perp, par));
+                            nr = make_ray(vadd(point, vmul(td, 0.001f)), td);
+                            return true;
+                        }
+                        scat = 0.f;  // reflect_ray below with scattering = 0.f
+                    }
+                }
                 if (kind == RTMI_MATTE) {
                     nr = make_ray(vadd(point, vmul(rv, 0.001f)), vadd(norm, rv));  // lambertian_ray, :292-297
                 } else {
@@ -203,7 +244,7 @@ __device__ inline bool shade_hit(const DScene& sc, uint32_t maxdepth, uint64_t s
                     const V4 dir_p = vmul(norm, ddot);
                     const V4 dir_o = vadd(rd, dir_p);
                     const V4 reflect = vadd(dir_p, dir_o);
-                    const V4 rvf = vmul(rv, m1.x);
+                    const V4 rvf = vmul(rv, scat);
                     const V4 reflect_dir = vunit(vadd(reflect, rvf));
                     nr = make_ray(vadd(point, vmul(reflect_dir, 0.001f)), vunit(vadd(reflect, rvf)));
                     if (mirror) *mirror = true;

@@ -1,5 +1,6 @@
 // capi.cpp — extern "C" view (include/rtmi_host.h) of the C++ host mirror.
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <memory>
 
@@ -25,7 +26,9 @@ static int guarded(F&& f) {
 }
 static Vec3 v3(const float* p) { return make_vec(p[0], p[1], p[2]); }
 static SurfaceKind surf(uint32_t kind, const float* c, float alpha, float scat) {
-    if (kind > RTMI_REFLECTIVE) throw std::runtime_error("unknown surface kind");
+    if (kind > RTMI_DIELECTRIC) throw std::runtime_error("unknown surface kind");
+    if (kind == RTMI_DIELECTRIC && !(std::isfinite(scat) && scat > 0.f))
+        throw std::runtime_error("a dielectric's index of refraction (scattering) must be finite and > 0");
     return SurfaceKind{(SurfaceKind::Tag)kind, v3(c), alpha, scat};
 }
 static HipRayCaster& caster_of(rth_scene* s) {

@@ -48,15 +48,17 @@ Color make_color(uint8_t r, uint8_t g, uint8_t b);  // raytrace.rs:176-180
 struct Ray { Point orig; Vec3 dir; Vec3 inv_dir; };
 Ray make_ray(const Point& orig, const Vec3& dir);
 
-// raytrace.rs:303-308
+// raytrace.rs:303-308, and Dielectric (include/rtmi.h, RTMI_DIELECTRIC: not in the reference), whose `scattering` is the
+// index of refraction
 struct SurfaceKind {
-    enum Tag : uint32_t { Solid = RTMI_SOLID, Matte = RTMI_MATTE, Reflective = RTMI_REFLECTIVE } tag;
+    enum Tag : uint32_t { Solid = RTMI_SOLID, Matte = RTMI_MATTE, Reflective = RTMI_REFLECTIVE, Dielectric = RTMI_DIELECTRIC } tag;
     Color color;
     float alpha;
-    float scattering;
+    float scattering;  // Reflective; Dielectric: the index of refraction
     static SurfaceKind solid(const Color& c) { return SurfaceKind{Solid, c, 0.f, 0.f}; }
     static SurfaceKind matte(const Color& c, float alpha) { return SurfaceKind{Matte, c, alpha, 0.f}; }
     static SurfaceKind reflective(float scattering, const Color& c, float alpha) { return SurfaceKind{Reflective, c, alpha, scattering}; }
+    static SurfaceKind dielectric(float ior, const Color& c, float alpha) { return SurfaceKind{Dielectric, c, alpha, ior}; }
 };
 
 // raytrace.rs:326-337

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _ffi
 
-SOLID, MATTE, REFLECTIVE = 0, 1, 2
+SOLID, MATTE, REFLECTIVE, DIELECTRIC = 0, 1, 2, 3
 OPT_COUNTERS, OPT_GENERIC, OPT_FAST, OPT_BVH = 1, 2, 4, 8
 
 
@@ -56,7 +56,7 @@ def create_transform(direction, d_roll):
 
 
 class SurfaceKind:
-    """raytrace.rs:303-308"""
+    """raytrace.rs:303-308, and Dielectric (include/rtmi.h, RTMI_DIELECTRIC), whose `scattering` is the index of refraction"""
 
     def __init__(self, kind, color, alpha=0.0, scattering=0.0):
         self.kind, self.color, self.alpha, self.scattering = kind, _f(color), float(alpha), float(scattering)
@@ -72,6 +72,10 @@ class SurfaceKind:
     @staticmethod
     def Reflective(scattering, color, alpha):
         return SurfaceKind(REFLECTIVE, color, alpha, scattering)
+
+    @staticmethod
+    def Dielectric(ior, color, alpha=1.0):
+        return SurfaceKind(DIELECTRIC, color, alpha, ior)
 
     def args(self):
         return (self.kind, _p(self.color), self.alpha, self.scattering)
