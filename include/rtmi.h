@@ -201,6 +201,72 @@ int rtmi_scene_destroy(rtmi_scene_t* scene);
 /* Replace the scene's list of analytic spheres (n may be 0).  At most 4096 spheres (they are not in the tree). */
 int rtmi_scene_set_spheres(rtmi_scene_t* scene, const rtmi_sphere_t* spheres, uint64_t n);
 
+/* THE ENVIRONMENT OF A SCENE: an HDR map looked up where a path escapes.  NOT part of the reference, whose
+ * color_ray returns one constant for every miss ((128, 180, 255) / 255, raytrace.rs:1264), so this build defines it, operation
+ * by operation like the camera models and the dielectric.  A scene with an environment starts the fold of a path that leaves it
+ * at the map's colour in the direction of the path's last ray.  Nothing else of color_ray's chain moves: no RNG draw, no ray
+ * count, black at exhausted depth and at edge faces.
+ *
+ * The map is an n x n table over the octahedral map of the directions (pole axis: map-space z), 1 <= n <= 4096; `rgb` is
+ * n * n * 3 floats, row-major, texel (i, j) = row j, column i at rgb[3 * (j * n + i)].  Texels may be any float: values above 1
+ * are the point, the float image carries them and rtmi_quantize* clamps as it always did.  `frame` holds the rows r0, r1, r2 that
+ * take a world direction to map space.  On the device the table is one float4 per texel with lane 3 +0.f, as the sky
+ * constant's is; so is lane 3 of r0..r2.
+ *
+ * The lookup for a unit direction d, float32 throughout, + - * /, fabsf, floorf and comparisons only, every step rounded (no
+ * fused multiply-add), plain loads (no texture unit, whose fixed-point weights could not be restated), mix_color =
+ * c1 * (1.f - a) + c2 * a lane by lane (raytrace.rs:299-301), vdot the ordered sum seeded with +0 (raytrace.rs:65-77):
+ *     m  = (vdot(r0, d), vdot(r1, d), vdot(r2, d))
+ *     a  = (|m.x| + |m.y|) + |m.z|;  px = m.x / a;  py = m.y / a
+ *     if m.z < 0.f:  (px, py) = ((1.f - |py|) * sg(px), (1.f - |px|) * sg(py)), both from the old values, sg(v) = v >= 0.f ? 1.f : -1.f
+ *     fx = (px * 0.5f + 0.5f) * (float)n - 0.5f;  fy likewise from py
+ *     cx = !(fx >= -1.f) ? -1.f : (fx > (float)n ? (float)n : fx);  cy likewise     (a NaN becomes -1)
+ *     ix = (int)floorf(cx);  iy = (int)floorf(cy);  tx = fx - floorf(fx);  ty = fy - floorf(fy)
+ *     texel(i, j):  ox = i < 0 || i >= n;  oy = j < 0 || j >= n;  ic = clamp(i, 0, n - 1);  jc = clamp(j, 0, n - 1);
+ *                   if ox: jc = n - 1 - jc;  if oy: ic = n - 1 - ic;  the table's entry jc * n + ic
+ *     c  = mix_color(mix_color(texel(ix, iy), texel(ix + 1, iy), tx), mix_color(texel(ix, iy + 1), texel(ix + 1, iy + 1), tx), ty)
+ * The border rule is the octahedral map's: points x and -x of an outer edge of the square are the same direction, so the filter
+ * stays continuous across the fold instead of clamping to the edge.  The indices come from the clamped coordinates, so no
+ * direction reads outside the table; the weights come from the unclamped ones.  For every direction that is not NaN the clamp
+ * changes nothing (|px|, |py| <= 1, so fx lies in [-0.5, n - 0.5]) and the two are the same numbers; a NaN, infinite or zero
+ * direction reads four texels of the table's corners and yields a NaN colour.
+ *
+ * rtmi_scene_set_environment: rgb == NULL or n == 0 removes the environment, and the scene is exactly the scene it was before.
+ * env == NULL: the defaults (identity frame, flags 0).  n > 4096, a frame entry that is not finite or flags != 0:
+ * RTMI_ERR_INVALID before any HIP call.  Setting, replacing or removing waits for the scene's work to finish first (one call at
+ * a time per handle, as everywhere).
+ * rtmi_scene_set_sky fills the table on the device (k_env_sky) under the identity frame, so that the feature is usable without
+ * an HDR file.  Texel (i, j) runs the inverse of the map:
+ *     px = ((float)i + 0.5f) / (float)n * 2.f - 1.f;  py likewise from j;  z = (1.f - |px|) - |py|
+ *     if z < 0.f: the same swap-and-sign rule on the old (px, py);  dir = vunit(px, py, z)
+ *     h = vdot(dir, vunit(up));  c = h < 0.f ? ground : mix_color(horizon, zenith, h)
+ *     if vdot(dir, vunit(sun_dir)) >= sun_cos:  c = c + sun_color
+ * sun_cos is the cosine of the sun disc's angular radius.  n outside 1..4096, a zero or non-finite up or sun_dir:
+ * RTMI_ERR_INVALID before any HIP call.
+ * rtmi_scene_get_environment copies the device table back as rgb (rgb_out may be NULL); *n_out = 0 means there is none.
+ *
+ * A scene with an environment renders on the per-pass pipeline (stats.pipeline = 1, slow_paths = 0) with the environment shading
+ * kernels (k_shade*_env, which also know RTMI_DIELECTRIC), whatever the scene kind and options: rtmi_render, _device,
+ * _tile_device, rtmi_render_samples*, rtmi_render_adaptive*, rtmi_render_views*, rtmi_render_frame_multi (each scene handle
+ * carries its own table), rtmi_render_camera*, rtmi_render_rays*, rtmi_bake* (`light`; `open` counts misses as before) and the
+ * two denoised wrappers all gain it.  Scenes without one take exactly the path they took before.
+ * Unchanged: rtmi_trace*, rtmi_occluded*, the records; rtmi_render_features*, _ao*, _light*, _preview* and the guide buffers of
+ * the camera and explicit-ray calls, which read first hits only: a miss's albedo stays the sky constant with coverage 0.
+ * rtmi_render_shadowed* returns RTMI_ERR_UNSUPPORTED for a scene with an environment, before any HIP call.
+ * Not here: importance sampling of the map, next-event estimation towards the sun, an environment in the path kernels
+ * (pipeline 3), image file loading, equirectangular input, mip-mapped lookups. */
+typedef struct rtmi_environment { float frame[9]; uint32_t flags; /* 0 */ } rtmi_environment_t;
+void rtmi_environment_defaults(rtmi_environment_t* env); /* identity frame, flags 0 */
+int rtmi_scene_set_environment(rtmi_scene_t* scene, const float* rgb /* n * n * 3, or NULL */, uint32_t n,
+                               const rtmi_environment_t* env /* or NULL = defaults */);
+int rtmi_scene_get_environment(rtmi_scene_t* scene, float* rgb_out /* n * n * 3, or NULL */, uint32_t* n_out);
+typedef struct rtmi_sky {
+    float up[3], sun_dir[3], sun_cos;
+    float zenith[3], horizon[3], ground[3], sun_color[3];
+} rtmi_sky_t;
+void rtmi_sky_defaults(rtmi_sky_t* sky); /* up +y, a sun of 5.7 degrees radius up and to the left behind the canonical camera */
+int rtmi_scene_set_sky(rtmi_scene_t* scene, uint32_t n, const rtmi_sky_t* sky /* or NULL = defaults */);
+
 /* Optional: the corners the triangle records were made from (`Triangle.corners`, raytrace.rs:326-337), 9 floats per
  * triangle, n = ntris (entry 0 = the sentinel's, ignored).  Only RTMI_OPT_BVH uses them: its boxes become the triangles'
  * own boxes (intersected with the bounding-radius disc's) instead of the disc's alone -- fewer boxes per ray, same hits.

@@ -54,6 +54,15 @@ int rth_add_triangles_gpu(rth_scene_t* s, const float* pts9, uint64_t n, uint32_
 /* analytic sphere: a build-defined extension (rtmi_sphere_t in rtmi.h), not a reference API */
 int rth_add_analytic_sphere(rth_scene_t* s, const float* center3, float radius, uint32_t kind, const float* color3, float alpha,
                             float scattering);
+/* The environment of the scene (rtmi_scene_set_environment / rtmi_scene_set_sky in rtmi.h, which defines it): kept with the
+ * scene and applied to its resident copy on every device at the next call that uses one; the scene is not uploaded again.
+ * rgb == NULL or n == 0 removes it; frame9 == NULL is the identity; sky == NULL the defaults.  Refusals as in rtmi.h.
+ * rth_scene_environment_size: n of what was set, 0 for none.  rth_caster_environment uploads if need be and reads the device's
+ * table back (n * n * 3 floats, at most cap_floats). */
+int rth_scene_set_environment(rth_scene_t* s, const float* rgb, uint32_t n, const float* frame9);
+int rth_scene_set_sky(rth_scene_t* s, uint32_t n, const rtmi_sky_t* sky);
+int rth_scene_environment_size(const rth_scene_t* s, uint32_t* n_out);
+int rth_caster_environment(rth_scene_t* s, float* rgb_out, uint64_t cap_floats, uint32_t* n_out);
 void rth_populate_triangle_numbers(rth_scene_t* s);
 
 /* build_bounding_box / build_trivial_bounding_box into Scene.boxes */

@@ -593,8 +593,11 @@ namespace rtmi {
                           DCtrl* __restrict__ ctrl, SlowQ slow
 #define RTMI_SHADE_ARGS sc, v, seed, pix0, npaths, pass, qo, qd, qpath, hit_tf, hit_t, qo_n, qd_n, qpath_n, mstack, scol, ctrl, slow
 // GLASS (k_shade*_glass): shade_hit<true>, which knows RTMI_DIELECTRIC; the launch sites pick them for scenes with a dielectric
-template <Samp S, bool GLASS = false>
-__device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list = nullptr, const ViewTab& vt = ViewTab{}) {
+// ENV (k_shade*_env): shade_hit<GLASS, true>, whose misses look the scene's environment up in their ray's direction; the launch
+// sites pick them, before the glass ones, for scenes with an environment
+template <Samp S, bool GLASS = false, bool ENV = false>
+__device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list = nullptr, const ViewTab& vt = ViewTab{},
+                                           const EnvTab* env = nullptr) {
     __shared__ uint32_t s_cnt[4], s_base;
     const uint32_t count = ctrl->count[pass];
     const uint32_t stride = gridDim.x * blockDim.x;
@@ -614,17 +617,20 @@ __device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __
             float t = 0.f;
             float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f), d4 = make_float4(0.f, 0.f, 1.f, 0.f);
             if ((tf & 0x3FFFFFFFu) != 0u && !((tf >> 30) & 2u)) { t = hit_t[i]; o4 = qo[i]; d4 = qd[i]; }
+            if constexpr (ENV) {  // a miss looks the environment up in its ray's direction
+                if ((tf & 0x3FFFFFFFu) == 0u) d4 = qd[i];
+            }
             if constexpr (S == Samp::RAYS) {  // `list` = the batch's RNG keys (or null), pix0 = the key of its first group
                 uint32_t pixel, sample;
                 rays_key(v, pix0, path, list, pixel, sample);
-                push = shade_hit<GLASS>(sc, v.maxdepth, seed, npaths, path, pixel, sample, (uint32_t)pass, tf, t, V4{o4.x, o4.y, o4.z, o4.w},
-                                        V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr);
+                push = shade_hit<GLASS, ENV>(sc, v.maxdepth, seed, npaths, path, pixel, sample, (uint32_t)pass, tf, t, V4{o4.x, o4.y, o4.z, o4.w},
+                                             V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr, nullptr, env);
             } else {
             uint32_t prow, pcol, sample;
             path_pixel<S>(v, pix0, path, prow, pcol, sample, list);
             const PixKey key = pixel_key<S>(v, prow, vt);
-            push = shade_hit<GLASS>(sc, v.maxdepth, key_seed<S>(key, vt, seed), npaths, path, key.row * v.width + pcol, sample, (uint32_t)pass, tf, t,
-                                    V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr);
+            push = shade_hit<GLASS, ENV>(sc, v.maxdepth, key_seed<S>(key, vt, seed), npaths, path, key.row * v.width + pcol, sample, (uint32_t)pass, tf, t,
+                                         V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr, nullptr, env);
             }
             // a bounce ray with an exactly-zero direction component goes to the slow path (SlowQ), not to the next pass
             if (push && slow.cap && has_zero_component(nr.dir.x, nr.dir.y, nr.dir.z) &&
@@ -668,6 +674,30 @@ __global__ void __launch_bounds__(256) k_shade_samples_glass(RTMI_SHADE_PARAMS) 
 __global__ void __launch_bounds__(256) k_shade_list_glass(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list) { shade_pass<Samp::LIST, true>(RTMI_SHADE_ARGS, list); }
 __global__ void __launch_bounds__(256) k_shade_views_glass(RTMI_SHADE_PARAMS, ViewTab vt) { shade_pass<Samp::VIEWS, true>(RTMI_SHADE_ARGS, nullptr, vt); }
 __global__ void __launch_bounds__(256) k_shade_rays_glass(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ keys) { shade_pass<Samp::RAYS, true>(RTMI_SHADE_ARGS, keys); }
+// And for scenes with an environment (rtmi_scene_set_environment / rtmi_scene_set_sky), with or without glass
+__global__ void __launch_bounds__(256) k_shade_env(RTMI_SHADE_PARAMS, EnvTab env) { shade_pass<Samp::FRAME, true, true>(RTMI_SHADE_ARGS, nullptr, ViewTab{}, &env); }
+__global__ void __launch_bounds__(256) k_shade_samples_env(RTMI_SHADE_PARAMS, EnvTab env) { shade_pass<Samp::PASS, true, true>(RTMI_SHADE_ARGS, nullptr, ViewTab{}, &env); }
+__global__ void __launch_bounds__(256) k_shade_list_env(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list, EnvTab env) { shade_pass<Samp::LIST, true, true>(RTMI_SHADE_ARGS, list, ViewTab{}, &env); }
+__global__ void __launch_bounds__(256) k_shade_views_env(RTMI_SHADE_PARAMS, ViewTab vt, EnvTab env) { shade_pass<Samp::VIEWS, true, true>(RTMI_SHADE_ARGS, nullptr, vt, &env); }
+__global__ void __launch_bounds__(256) k_shade_rays_env(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ keys, EnvTab env) { shade_pass<Samp::RAYS, true, true>(RTMI_SHADE_ARGS, keys, ViewTab{}, &env); }
+
+// rtmi_scene_set_sky: texel (i, j) of an n x n environment table from the inverse of env_lookup's map -- the direction of the
+// texel's centre -- and a gradient sky with a sun disc, operation by operation as include/rtmi.h lists it.  One thread per texel.
+struct SkyArgs { float4 up, sun_dir, zenith, horizon, ground, sun_color; float sun_cos; };
+__global__ void __launch_bounds__(256) k_env_sky(float4* __restrict__ tab, uint32_t n, float fn, SkyArgs a) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n * n) return;
+    const uint32_t j = k / n, i = k - j * n;
+    auto v4 = [](float4 q) { return V4{q.x, q.y, q.z, q.w}; };
+    float px = ((float)i + 0.5f) / fn * 2.f - 1.f, py = ((float)j + 0.5f) / fn * 2.f - 1.f;
+    const float z = (1.f - fabsf(px)) - fabsf(py);
+    if (z < 0.f) oct_fold(px, py);
+    const V4 dir = vunit(mk(px, py, z));
+    const float h = vdot(dir, vunit(v4(a.up)));
+    V4 c = h < 0.f ? v4(a.ground) : mix_color(v4(a.horizon), v4(a.zenith), h);
+    if (vdot(dir, vunit(v4(a.sun_dir))) >= a.sun_cos) c = vadd(c, v4(a.sun_color));
+    tab[k] = make_float4(c.x, c.y, c.z, 0.f);
+}
 
 // walk_ray_set's per-pixel accumulation (raytrace.rs:1414-1426): acc = 0; acc += sample_i in sample order; * (1/spp).
 // The sample colours of a pixel are consecutive in `scol` ([pixel][sample]), so one thread per pixel would read 16 B at a
@@ -1068,6 +1098,11 @@ struct rtmi_scene {
     std::vector<float4> hmats;  // the triangles' surface table (host copy): sphere surfaces are appended to it
     // a triangle / a triangle or a sphere is RTMI_DIELECTRIC: such a scene renders on the per-pass pipeline with k_shade*_glass
     bool tris_dielectric = false, has_dielectric = false;
+    // rtmi_scene_set_environment / rtmi_scene_set_sky: the table (one float4 per texel) and what the k_shade*_env kernels get of
+    // it.  A scene with one renders on the per-pass pipeline with those kernels, with or without glass.
+    DevBuf<float4> env;
+    EnvTab envtab{};
+    bool has_env = false;
     std::vector<rtmi_triangle_t> htris;  // the records (host copy): the fast-mode BVH is rebuilt from them when corners arrive
     DevBuf<uint4> fnodes, oblocks, ocull;  // (fnodes: the node records, then the node cull records)
     DevBuf<uint32_t> wlinks, cert;
@@ -1857,7 +1892,7 @@ int rtmi_scene_destroy(rtmi_scene_t* s) {
     if (!s) return RTMI_OK;
     (void)hipSetDevice(s->device);
     s->nodes.release(); s->refs.release(); s->tplane.release(); s->tedge.release(); s->mats.release();
-    s->fnodes.release(); s->oblocks.release(); s->ocull.release(); s->cert.release(); s->wlinks.release(); s->bnodes.release(); s->bleaves.release(); s->spheres.release();
+    s->fnodes.release(); s->oblocks.release(); s->ocull.release(); s->cert.release(); s->wlinks.release(); s->bnodes.release(); s->bleaves.release(); s->spheres.release(); s->env.release();
     for (int k = 0; k < RTMI_MAX_STREAMS; k++) {
         s->w[k].release();
         if (s->istream[k]) (void)hipStreamDestroy(s->istream[k]);
@@ -1927,6 +1962,107 @@ int rtmi_scene_set_spheres(rtmi_scene_t* s, const rtmi_sphere_t* sp, uint64_t n)
     s->d.spheres = s->spheres.p;
     s->d.nspheres = (uint32_t)n;
     s->has_dielectric = has_dielectric;
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+void rtmi_environment_defaults(rtmi_environment_t* e) {
+    if (!e) return;
+    const float id[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    memcpy(e->frame, id, sizeof id);
+    e->flags = 0u;
+}
+
+void rtmi_sky_defaults(rtmi_sky_t* k) {
+    if (!k) return;
+    const rtmi_sky_t d = {{0.f, 1.f, 0.f},        {-0.5f, 0.7f, -0.5f},   0.995f,          {0.15f, 0.35f, 0.9f},
+                          {0.85f, 0.9f, 1.f},     {0.25f, 0.22f, 0.2f},   {40.f, 36.f, 28.f}};
+    *k = d;
+}
+
+// the table is in place (or gone): what the k_shade*_env kernels get of it
+static void env_set(rtmi_scene_t* s, uint32_t n, const float* frame) {
+    s->envtab.tab = n ? s->env.p : nullptr;
+    s->envtab.n = n;
+    s->envtab.fn = (float)n;
+    if (n) {
+        s->envtab.r0 = make_float4(frame[0], frame[1], frame[2], 0.f);
+        s->envtab.r1 = make_float4(frame[3], frame[4], frame[5], 0.f);
+        s->envtab.r2 = make_float4(frame[6], frame[7], frame[8], 0.f);
+    }
+    s->has_env = n != 0u;
+}
+
+int rtmi_scene_set_environment(rtmi_scene_t* s, const float* rgb, uint32_t n, const rtmi_environment_t* env) {
+    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
+    rtmi_environment_t e;
+    rtmi_environment_defaults(&e);
+    if (env) e = *env;
+    if (rgb && n) {
+        if (n > 4096u) return fail(RTMI_ERR_INVALID, "environment: n must be 1 to 4096");
+        if (e.flags != 0u) return fail(RTMI_ERR_INVALID, "environment: flags must be 0");
+        for (int k = 0; k < 9; k++)
+            if (!std::isfinite(e.frame[k])) return fail(RTMI_ERR_INVALID, "environment: frame entry " + std::to_string(k) + " is not finite");
+    }
+    RTMI_GUARD_BEGIN
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipDeviceSynchronize());  // no render of this scene is in flight: its streams are done with the old table
+    if (!rgb || !n) {
+        env_set(s, 0u, nullptr);
+        s->env.release();
+        return RTMI_OK;
+    }
+    const size_t nt = (size_t)n * n;
+    std::vector<float4> tab(nt);
+    for (size_t k = 0; k < nt; k++) tab[k] = make_float4(rgb[3 * k], rgb[3 * k + 1], rgb[3 * k + 2], 0.f);
+    env_set(s, 0u, nullptr);  // (a failure below leaves the scene without an environment, not with a stale one)
+    HIPCHK(s->env.ensure(nt));
+    HIPCHK(hipMemcpy(s->env.p, tab.data(), nt * sizeof(float4), hipMemcpyHostToDevice));
+    env_set(s, n, e.frame);
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+int rtmi_scene_set_sky(rtmi_scene_t* s, uint32_t n, const rtmi_sky_t* sky) {
+    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
+    if (n < 1u || n > 4096u) return fail(RTMI_ERR_INVALID, "sky: n must be 1 to 4096");
+    rtmi_sky_t k;
+    rtmi_sky_defaults(&k);
+    if (sky) k = *sky;
+    auto usable = [](const float* v) {
+        return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]) && (v[0] != 0.f || v[1] != 0.f || v[2] != 0.f);
+    };
+    if (!usable(k.up)) return fail(RTMI_ERR_INVALID, "sky: up must be finite and not zero");
+    if (!usable(k.sun_dir)) return fail(RTMI_ERR_INVALID, "sky: sun_dir must be finite and not zero");
+    RTMI_GUARD_BEGIN
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipDeviceSynchronize());  // no render of this scene is in flight: its streams are done with the old table
+    const size_t nt = (size_t)n * n;
+    env_set(s, 0u, nullptr);
+    HIPCHK(s->env.ensure(nt));
+    auto f4 = [](const float* v) { return make_float4(v[0], v[1], v[2], 0.f); };
+    const SkyArgs a{f4(k.up), f4(k.sun_dir), f4(k.zenith), f4(k.horizon), f4(k.ground), f4(k.sun_color), k.sun_cos};
+    hipLaunchKernelGGL(k_env_sky, dim3((unsigned)((nt + 255u) / 256u)), dim3(256), 0, 0, s->env.p, n, (float)n, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    rtmi_environment_t e;
+    rtmi_environment_defaults(&e);
+    env_set(s, n, e.frame);
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+int rtmi_scene_get_environment(rtmi_scene_t* s, float* rgb_out, uint32_t* n_out) {
+    if (!s || !n_out) return fail(RTMI_ERR_INVALID, "NULL argument");
+    *n_out = s->has_env ? s->envtab.n : 0u;
+    if (!s->has_env || !rgb_out) return RTMI_OK;
+    RTMI_GUARD_BEGIN
+    const size_t nt = (size_t)s->envtab.n * s->envtab.n;
+    std::vector<float4> tab(nt);
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(tab.data(), s->env.p, nt * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < nt; k++) { rgb_out[3 * k] = tab[k].x; rgb_out[3 * k + 1] = tab[k].y; rgb_out[3 * k + 2] = tab[k].z; }
     return RTMI_OK;
     RTMI_GUARD_END
 }
@@ -2243,7 +2379,7 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
     // shades the primary rays in one kernel.  Everything else (pipeline 1, linear list, generic tree, BVH mode,
     // analytic spheres) starts with k_gen.  Both then run one closest-hit + one shading launch per bounce pass.
     c.path_kernels = !c.fo && !c.ao && !c.li && !c.pv && !c.sh && !c.cam && s->tune.pipeline != 1u && s->octree && !s->root_is_leaf &&
-                     !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) && s->d.nspheres == 0 && !s->has_dielectric;
+                     !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) && s->d.nspheres == 0 && !s->has_dielectric && !s->has_env;
     // streams = 0 (automatic): one stream for path-kernel tiles of 2^26 paths and more, three otherwise (the per-pass
     // pipelines -- BVH mode: 29.6 ms on three streams, 35.2 on one -- have elementwise kernels to hide).  Since k_shade stopped being
     // atomic-bound (round 3) there is little left for a second stream to hide: the full config-3 frame takes 366.9 ms on one
@@ -2517,7 +2653,18 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
             if (rc != RTMI_OK) return rc;
         }
         const bool glass = s->has_dielectric;  // (never with c.path_kernels: sq is off and k_path_slow, which has no glass arm, never runs)
-        if (list)
+        // a scene with an environment (never with c.path_kernels either): the _env kernels, which also know glass
+        if (s->has_env && list)
+            hipLaunchKernelGGL(k_shade_list_env, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
+                               w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, list, s->envtab);
+        else if (s->has_env && c.mode == Samp::VIEWS)
+            hipLaunchKernelGGL(k_shade_views_env, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
+                               w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, c.vt, s->envtab);
+        else if (s->has_env)
+            hipLaunchKernelGGL(c.mode == Samp::PASS ? k_shade_samples_env : k_shade_env, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths,
+                               (int)pass, w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p,
+                               w.mstack.p, w.scol.p, w.ctrl.p, sq, s->envtab);
+        else if (list)
             hipLaunchKernelGGL(glass ? k_shade_list_glass : k_shade_list, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
                                w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, list);
         else if (c.mode == Samp::VIEWS)
@@ -3087,6 +3234,8 @@ static int refuse_scene_shadowed(const rtmi_scene_t* s) {
         return fail(RTMI_ERR_UNSUPPORTED, "shadowed: the scene has analytic spheres (a build-defined primitive whose normal needs the hit point)");
     if (s->has_dielectric)
         return fail(RTMI_ERR_UNSUPPORTED, "shadowed: the scene has a dielectric surface (the shadowed shading has no glass arm)");
+    if (s->has_env)
+        return fail(RTMI_ERR_UNSUPPORTED, "shadowed: the scene has an environment (the shadowed shading has no environment arm)");
     return RTMI_OK;
 }
 
@@ -3971,7 +4120,11 @@ static int render_rays(rtmi_scene_t* s, uint64_t n, const void* orig4, const voi
             if (pass == 0 && guides)  // before pass 1 rewrites the hit records
                 hipLaunchKernelGGL(k_features, ew_grid, ew_block, 0, st, s->d, ng, G, w.hit_tf.p, w.hit_t.p, (float*)albedo, (float*)normal, ids,
                                    0u, ng, 1u, 0u, make_fastdiv(ng), make_fastdiv(G));
-            if (shade)
+            if (shade && s->has_env)
+                hipLaunchKernelGGL(k_shade_rays_env, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(rp->pixel0 + gbase), nb, (int)pass, pqo, pqd,
+                                   w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, scol, w.ctrl.p,
+                                   SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, kq, s->envtab);
+            else if (shade)
                 hipLaunchKernelGGL(s->has_dielectric ? k_shade_rays_glass : k_shade_rays, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(rp->pixel0 + gbase), nb, (int)pass, pqo, pqd,
                                    w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, scol, w.ctrl.p,
                                    SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, kq);
@@ -4153,7 +4306,11 @@ static int bake(rtmi_scene_t* s, uint64_t M, const void* pos4, const void* nrm4,
             if (pass == 0 && open)  // before pass 1 rewrites the hit records
                 hipLaunchKernelGGL(k_bake_open, dim3(std::min<unsigned>((unsigned)(s->num_cu * 8), (mb + RTMI_BAKE_OPEN_ELEMS - 1u) / RTMI_BAKE_OPEN_ELEMS)),
                                    ew_block, 0, st, mb, K, w.hit_tf.p, open);
-            if (shade)
+            if (shade && s->has_env)
+                hipLaunchKernelGGL(k_shade_rays_env, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(bp->pixel0 + mbase), nb, (int)pass, pqo, pqd,
+                                   w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p,
+                                   SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, (const uint32_t*)nullptr, s->envtab);
+            else if (shade)
                 hipLaunchKernelGGL(s->has_dielectric ? k_shade_rays_glass : k_shade_rays, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(bp->pixel0 + mbase), nb, (int)pass, pqo, pqd,
                                    w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p,
                                    SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, (const uint32_t*)nullptr);

@@ -164,6 +164,47 @@ __device__ inline V4 random_vec_u(uint64_t seed, uint32_t pixel, uint32_t sample
 // mix_color (raytrace.rs:299-301)
 __device__ inline V4 mix_color(V4 c1, V4 c2, float a) { return vadd(vmul(c1, 1.f - a), vmul(c2, a)); }
 
+// The environment of a scene (rtmi_scene_set_environment / rtmi_scene_set_sky, include/rtmi.h): an n x n table of
+// one float4 per texel (lane 3 +0) over the octahedral map of the directions, texel (i, j) at tab[j * n + i], and the rows of the
+// frame that takes a world direction to map space (lane 3 +0).  An argument of the k_shade*_env kernels only, as ViewTab and the
+// pixel list are of theirs: DScene, and with it every other kernel's argument block, stays as it is.
+struct EnvTab { const float4* __restrict__ tab; uint32_t n; float fn; float4 r0, r1, r2; };
+// the octahedral map's fold of the lower hemisphere (m.z < 0) over the outer triangles of the square, and its own inverse: both
+// results from the OLD values
+__device__ inline void oct_fold(float& px, float& py) {
+    const float ox = px, oy = py;
+    px = (1.f - fabsf(oy)) * (ox >= 0.f ? 1.f : -1.f);
+    py = (1.f - fabsf(ox)) * (oy >= 0.f ? 1.f : -1.f);
+}
+// texel (i, j) of the table, i and j in [-1, n], through the octahedral border rule: points x and -x of an outer edge are the
+// same direction, so a texel one step outside a column range mirrors its row, and the other way round
+__device__ inline uint32_t env_texel(int i, int j, int n) {
+    const bool ox = i < 0 || i >= n, oy = j < 0 || j >= n;
+    int ic = i < 0 ? 0 : (i > n - 1 ? n - 1 : i);
+    int jc = j < 0 ? 0 : (j > n - 1 ? n - 1 : j);
+    if (ox) jc = n - 1 - jc;
+    if (oy) ic = n - 1 - ic;
+    return (uint32_t)jc * (uint32_t)n + (uint32_t)ic;
+}
+// The colour of the environment in unit direction d, operation by operation as include/rtmi.h lists it: + - * /, fabsf, floorf
+// and comparisons in f32, plain loads.  The indices come from the clamped texel coordinates, so that no value of d reads outside
+// the table; the weights from the unclamped ones, which the clamp leaves alone unless they are NaN, so that a NaN stays one.
+// The four loads do not depend on each other and are requested together.
+__device__ inline V4 env_lookup(const EnvTab& e, V4 d) {
+    auto v4 = [](float4 a) { return V4{a.x, a.y, a.z, a.w}; };
+    const float mx = vdot(v4(e.r0), d), my = vdot(v4(e.r1), d), mz = vdot(v4(e.r2), d);
+    const float a = (fabsf(mx) + fabsf(my)) + fabsf(mz);
+    float px = mx / a, py = my / a;
+    if (mz < 0.f) oct_fold(px, py);
+    const float fx = (px * 0.5f + 0.5f) * e.fn - 0.5f, fy = (py * 0.5f + 0.5f) * e.fn - 0.5f;
+    const float cx = !(fx >= -1.f) ? -1.f : (fx > e.fn ? e.fn : fx), cy = !(fy >= -1.f) ? -1.f : (fy > e.fn ? e.fn : fy);
+    const int ix = (int)floorf(cx), iy = (int)floorf(cy), n = (int)e.n;
+    const float tx = fx - floorf(fx), ty = fy - floorf(fy);
+    const uint32_t k00 = env_texel(ix, iy, n), k10 = env_texel(ix + 1, iy, n), k01 = env_texel(ix, iy + 1, n), k11 = env_texel(ix + 1, iy + 1, n);
+    const float4 c00 = e.tab[k00], c10 = e.tab[k10], c01 = e.tab[k01], c11 = e.tab[k11];
+    return mix_color(mix_color(v4(c00), v4(c10), tx), mix_color(v4(c01), v4(c11), tx), ty);
+}
+
 // color_ray + the tail of project_ray for ONE traced ray of a path.  `pass` = bounces the path has behind it (the ray's
 // remaining depth is maxdepth - pass >= 1); tf = hit triangle | face << 30 (0 = miss), t = hit time; (ro, rd) the ray.
 // Returns true when the path goes on: its surface has been pushed on the path's stack (mstack[pass][path]) and `nr` is
@@ -175,15 +216,19 @@ __device__ inline V4 mix_color(V4 c1, V4 c2, float a) { return vadd(vmul(c1, 1.f
 // operation as include/rtmi.h defines it: the level is pushed like Matte's, the bounce ray is the refracted one or, on total
 // internal reflection or with Schlick's probability, reflect_ray's with scattering 0.f.  Without it (every other kernel, the
 // path kernels among them) the arm is not compiled and the function is the one it was.
-template <bool GLASS = false>
+// ENV: the kernels of scenes with an environment (k_shade*_env) start a miss's fold at env_lookup(*env, rd) instead of the sky
+// constant -- rd must then be the ray's direction for a miss too -- and nothing else moves: no draw, no ray, black at an edge
+// face and at exhausted depth.  Without it `env` is never read.
+template <bool GLASS = false, bool ENV = false>
 __device__ inline bool shade_hit(const DScene& sc, uint32_t maxdepth, uint64_t seed, uint32_t npaths, uint32_t path, uint32_t pixel,
                                  uint32_t sample, uint32_t pass, uint32_t tf, float t, V4 ro, V4 rd, uint16_t* __restrict__ mstack,
-                                 float4* __restrict__ scol, RayV& nr, bool* mirror = nullptr) {
+                                 float4* __restrict__ scol, RayV& nr, bool* mirror = nullptr, const EnvTab* env = nullptr) {
     const uint32_t tri = tf & 0x3FFFFFFFu, face = tf >> 30;
     V4 c;
     uint32_t npushed = pass;
     if (tri == 0) {
-        c = mk(128.f / 255.f, 180.f / 255.f, 255.f / 255.f);  // raytrace.rs:1264
+        if constexpr (ENV) c = env_lookup(*env, rd);
+        else c = mk(128.f / 255.f, 180.f / 255.f, 255.f / 255.f);  // raytrace.rs:1264
     } else if (face & 2u) {
         c = mk(0.f / 255.f, 0.f / 255.f, 0.f / 255.f);  // edge faces are Solid black, raytrace.rs:452-457
     } else {

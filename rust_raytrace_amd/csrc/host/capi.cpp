@@ -118,6 +118,51 @@ int rth_add_analytic_sphere(rth_scene_t* s, const float* center3, float r, uint3
         s->scene.touch();
     });
 }
+int rth_scene_set_environment(rth_scene_t* s, const float* rgb, uint32_t n, const float* frame9) {
+    return guarded([&] {
+        if (!rgb || n == 0) { s->scene.environment.reset(); s->scene.env_generation++; return; }
+        if (n > 4096) throw std::runtime_error("environment: n must be 1 to 4096");
+        Environment e;
+        e.n = n;
+        for (int k = 0; frame9 && k < 9; k++) {
+            if (!std::isfinite(frame9[k])) throw std::runtime_error("environment: frame entry " + std::to_string(k) + " is not finite");
+            e.frame[k] = frame9[k];
+        }
+        e.rgb.assign(rgb, rgb + (size_t)n * n * 3);
+        s->scene.environment = std::move(e);
+        s->scene.env_generation++;
+    });
+}
+int rth_scene_set_sky(rth_scene_t* s, uint32_t n, const rtmi_sky_t* sky) {
+    return guarded([&] {
+        if (n < 1 || n > 4096) throw std::runtime_error("sky: n must be 1 to 4096");
+        Environment e;
+        e.n = n;
+        e.generated = true;
+        rtmi_sky_defaults(&e.sky);
+        if (sky) e.sky = *sky;
+        auto usable = [](const float* v) {
+            return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]) && (v[0] != 0.f || v[1] != 0.f || v[2] != 0.f);
+        };
+        if (!usable(e.sky.up)) throw std::runtime_error("sky: up must be finite and not zero");
+        if (!usable(e.sky.sun_dir)) throw std::runtime_error("sky: sun_dir must be finite and not zero");
+        s->scene.environment = std::move(e);
+        s->scene.env_generation++;
+    });
+}
+int rth_scene_environment_size(const rth_scene_t* s, uint32_t* n_out) {
+    *n_out = s->scene.environment ? s->scene.environment->n : 0u;
+    return 0;
+}
+int rth_caster_environment(rth_scene_t* s, float* rgb_out, uint64_t cap_floats, uint32_t* n_out) {
+    return guarded([&] {
+        uint32_t n = 0;
+        const std::vector<float> rgb = caster_of(s).environment(s->scene, n);
+        if (rgb.size() > cap_floats) throw std::runtime_error("rth_caster_environment: the buffer is too small");
+        if (!rgb.empty()) memcpy(rgb_out, rgb.data(), rgb.size() * sizeof(float));
+        *n_out = n;
+    });
+}
 void rth_populate_triangle_numbers(rth_scene_t* s) { populate_triangle_numbers(s->scene.tris); s->scene.touch(); }
 
 int rth_build_bounding_box(rth_scene_t* s, const float* orig3, float len2, uint64_t maxdepth, uint64_t minobjs, uint32_t threads) {

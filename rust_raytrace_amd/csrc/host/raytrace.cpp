@@ -553,6 +553,48 @@ void HipRayCaster::invalidate() {
     for (rtmi_scene_t* h : extra_) rtmi_scene_destroy(h);
     extra_.clear();
     handle_ = nullptr; key_scene_ = nullptr;
+    env_applied_ = false;
+}
+
+void HipRayCaster::apply_environment(const Scene& s) {
+    if (env_applied_ && key_env_generation_ == s.env_generation) return;
+    std::vector<rtmi_scene_t*> all{handle_};
+    all.insert(all.end(), extra_.begin(), extra_.end());
+    for (rtmi_scene_t* hh : all) {
+        int rc;
+        const char* what;
+        if (!s.environment) {
+            if (!env_applied_) continue;  // fresh handles have none
+            what = "rtmi_scene_set_environment";
+            rc = rtmi_scene_set_environment(hh, nullptr, 0, nullptr);
+        } else if (s.environment->generated) {
+            what = "rtmi_scene_set_sky";
+            rc = rtmi_scene_set_sky(hh, s.environment->n, &s.environment->sky);
+        } else {
+            what = "rtmi_scene_set_environment";
+            rtmi_environment_t e;
+            rtmi_environment_defaults(&e);
+            for (int k = 0; k < 9; k++) e.frame[k] = s.environment->frame[k];
+            rc = rtmi_scene_set_environment(hh, s.environment->rgb.data(), s.environment->n, &e);
+        }
+        if (rc != RTMI_OK) {
+            const std::string msg = std::string(what) + ": " + rtmi_last_error();
+            invalidate();
+            throw std::runtime_error(msg);
+        }
+    }
+    env_applied_ = true;
+    key_env_generation_ = s.env_generation;
+}
+
+std::vector<float> HipRayCaster::environment(const Scene& s, uint32_t& n) {
+    rtmi_scene_t* h = resident(s);
+    n = 0;
+    if (rtmi_scene_get_environment(h, nullptr, &n) != RTMI_OK) throw std::runtime_error(std::string("rtmi_scene_get_environment: ") + rtmi_last_error());
+    std::vector<float> rgb((size_t)n * n * 3);
+    if (n && rtmi_scene_get_environment(h, rgb.data(), &n) != RTMI_OK)
+        throw std::runtime_error(std::string("rtmi_scene_get_environment: ") + rtmi_last_error());
+    return rgb;
 }
 
 void HipRayCaster::set_devices(const std::vector<int>& devices) {
@@ -590,6 +632,7 @@ void HipRayCaster::apply_settings() {
 rtmi_scene_t* HipRayCaster::resident(const Scene& s) {
     if (handle_ && key_scene_ == &s && key_generation_ == s.generation && key_ntris_ == s.tris.size() &&
         key_nboxes_ == s.boxes.boxes.size() && key_nrefs_ == s.boxes.tri_refs.size()) {
+        apply_environment(s);
         apply_settings();
         return handle_;
     }
@@ -645,6 +688,7 @@ rtmi_scene_t* HipRayCaster::resident(const Scene& s) {
     rtmi_scene_get_tuning(handle_, &defaults_);
     key_scene_ = &s; key_generation_ = s.generation; key_ntris_ = s.tris.size();
     key_nboxes_ = s.boxes.boxes.size(); key_nrefs_ = s.boxes.tri_refs.size();
+    apply_environment(s);
     apply_settings();
     return handle_;
 }

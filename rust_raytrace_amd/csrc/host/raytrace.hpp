@@ -125,6 +125,17 @@ struct Sphere {
     SurfaceKind surface;
 };
 
+// The environment of a scene (include/rtmi.h, rtmi_scene_set_environment / rtmi_scene_set_sky): NOT in the
+// reference, whose paths that leave the scene all return one constant.  Either a table of n x n RGB texels with the frame that
+// takes a world direction to map space, or (generated) the parameters of a sky the device fills the table from.
+struct Environment {
+    uint32_t n = 0;
+    bool generated = false;
+    std::vector<float> rgb;  // n * n * 3, row j, column i; empty when generated
+    float frame[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    rtmi_sky_t sky{};
+};
+
 // Per-ray records of the octree walk (rtmi_trace_records / rtmi_primary_records), the reference's DebugCtx (debug.rs):
 // record i's leaves are leaf_ids[recs[i].leaf_first .. + recs[i].nleaves), indices into Scene.boxes.boxes.  pixel[i] =
 // (row, col) of record i for primary records; empty for explicit rays.
@@ -143,6 +154,11 @@ struct Scene {
     // either: its shadow block is commented out); walk_rays_shadowed / walk_shadowed_device need it.  Not part of the uploaded
     // scene: setting it needs no touch().
     std::optional<LightSource> light;
+    // The environment, or none.  A HipRayCaster applies it to its resident copies on every device when env_generation differs
+    // from the one it saw; the scene itself is not uploaded again, so code that edits `environment` bumps env_generation, not
+    // generation.
+    std::optional<Environment> environment;
+    uint64_t env_generation = 0;
     // debug_en: walk_rays also records sample 0's primary ray of every pixel into `debug` (the reference's debug_ctx, which
     // walk_rays fills through a &Scene: hence mutable).  Octree scenes only; walk_rays throws before rendering otherwise.
     bool debug_en = false;
@@ -336,6 +352,9 @@ public:
     // Uploads on first use, and again when another Scene object is passed or Scene::generation changed.
     rtmi_scene_t* resident(const Scene& s);
     void invalidate();
+    // The environment table of the scene's resident copy on the first device (rtmi_scene_get_environment): n * n * 3 floats,
+    // empty and n = 0 when the scene has none.
+    std::vector<float> environment(const Scene& s, uint32_t& n);
     uint64_t seed;
     int device;
 
@@ -345,6 +364,9 @@ private:
     std::vector<rtmi_scene_t*> extra_;         // handles of devices_[1..]
     const Scene* key_scene_ = nullptr;
     uint64_t key_generation_ = 0;
+    uint64_t key_env_generation_ = 0;
+    bool env_applied_ = false;                 // the handles carry Scene::environment as of key_env_generation_
+    void apply_environment(const Scene& s);
     size_t key_ntris_ = 0, key_nboxes_ = 0, key_nrefs_ = 0;
     uint32_t options_ = 0;
     rtmi_tuning_t tuning_{}, defaults_{};

@@ -162,6 +162,36 @@ class Scene:
     def populate_triangle_numbers(self):
         _ffi.lib().rth_populate_triangle_numbers(self.h)
 
+    # --- the environment: a build-defined extension (include/rtmi.h, "THE ENVIRONMENT OF A SCENE")
+    def set_environment(self, rgb, frame=None):
+        """Light the scene by an HDR map: a path that leaves the scene starts its fold at the map's colour in the direction of
+        its last ray instead of the reference's sky constant.  rgb: (n, n, 3) f32 texels over the octahedral map of the
+        directions, row j, column i, any float (values above 1 are the point); frame: 3 x 3, its rows take a world direction to
+        map space (default: the identity).  Kept with the scene; HipRayCaster applies it on every device it uploads to."""
+        t = _f(rgb)
+        if t.ndim != 3 or t.shape[0] != t.shape[1] or t.shape[2] != 3 or t.shape[0] < 1:
+            raise ValueError(f"environment: rgb must be (n, n, 3) with n >= 1, not {t.shape}")
+        fr = None if frame is None else _f(frame).reshape(9)
+        _chk(_ffi.lib().rth_scene_set_environment(self.h, _p(t), t.shape[0], None if fr is None else _p(fr)))
+
+    def set_sky(self, n, **sky):
+        """A generated environment (rtmi_scene_set_sky): an n x n table the device fills with a gradient sky and a sun disc.
+        Keywords are rtmi_sky_t's fields (up, sun_dir, sun_cos, zenith, horizon, ground, sun_color); the rest keep their defaults."""
+        k = _ffi.Sky()
+        _ffi.lib().rtmi_sky_defaults(C.byref(k))
+        for name, val in sky.items():
+            if name not in dict(_ffi.Sky._fields_):
+                raise TypeError(f"set_sky: unknown field {name!r}")
+            if name == "sun_cos":
+                k.sun_cos = float(val)
+            else:
+                setattr(k, name, (C.c_float * 3)(*[float(x) for x in val]))
+        _chk(_ffi.lib().rth_scene_set_sky(self.h, int(n), C.byref(k)))
+
+    def clear_environment(self):
+        """Back to the reference's sky constant: the scene is exactly the scene it was before it had an environment."""
+        _chk(_ffi.lib().rth_scene_set_environment(self.h, None, 0, None))
+
     # --- Scene.boxes
     def build_bounding_box(self, orig, len2, maxdepth, minobjs, threads=0, gpu_device=None):
         """raytrace.rs:790-845.  gpu_device: evaluate the box/triangle overlap tests of every level on that GPU
@@ -1332,8 +1362,21 @@ class HipRayCaster:
         _chk(_ffi.lib().rth_caster_quantize_device(s.h, C.c_void_p(rgba_ptr), npixels, C.c_void_p(rgb_ptr), C.c_void_p(stream_ptr or 0)))
 
     def upload(self, s):
+        """Make the scene, and its environment if it has one, resident on every device of the caster"""
         self._config(s)
         _chk(_ffi.lib().rth_caster_upload(s.h))
+
+    def environment(self, s):
+        """The environment table as the first device holds it (rtmi_scene_get_environment): (n, n, 3) f32, or None when the
+        scene has none.  Uploads first if need be."""
+        self._config(s)
+        n = C.c_uint32(0)
+        _chk(_ffi.lib().rth_scene_environment_size(s.h, C.byref(n)))
+        if n.value == 0:
+            return None
+        rgb = np.zeros((n.value, n.value, 3), np.float32)
+        _chk(_ffi.lib().rth_caster_environment(s.h, _p(rgb), rgb.size, C.byref(n)))
+        return rgb
 
     def trace(self, s, orig4, dir4):
         """Closest hit per explicit ray (rtmi_trace): -> tri, t, face, stats."""
