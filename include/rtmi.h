@@ -267,6 +267,62 @@ typedef struct rtmi_sky {
 void rtmi_sky_defaults(rtmi_sky_t* sky); /* up +y, a sun of 5.7 degrees radius up and to the left behind the canonical camera */
 int rtmi_scene_set_sky(rtmi_scene_t* scene, uint32_t n, const rtmi_sky_t* sky /* or NULL = defaults */);
 
+/* VERTEX NORMALS OF A SCENE: smooth shading, per-vertex normals interpolated at every hit.  NOT part of the
+ * reference, which shades every hit with its triangle's one geometric normal, so this build defines it, operation by operation
+ * like the camera models, the dielectric and the environment.  A scene may carry, per triangle, its three corners c0, c1, c2 and
+ * three corner normals n0, n1, n2: 9 + 9 floats per triangle, n = ntris, entry 0 the sentinel's and ignored.  Lane 3 of every
+ * vector is +0 on the device.  A triangle whose nine normal floats are all zero is flat.
+ *
+ * All arithmetic is f32, + - * / and sqrt only, no contraction, every step rounded on all lanes; vdot (the ordered sum seeded
+ * with +0), vunit (multiply by 1.f / sqrtf(vdot(a, a))), vadd, vsub, vmul are the reference's Vec3 operations.
+ * Per triangle, once, when the normals are set:
+ *     e1 = c1 - c0;  e2 = c2 - c0
+ *     d00 = vdot(e1, e1);  d01 = vdot(e1, e2);  d11 = vdot(e2, e2);  den = d00 * d11 - d01 * d01
+ * At a hit of a triangle (not an analytic sphere, not an edge face), with point = rd * t + ro as color_ray computes it and ng the
+ * record's normal, already * -1.f on a back face:
+ *     w   = point - c0;  d20 = vdot(w, e1);  d21 = vdot(w, e2)
+ *     b1  = (d11 * d20 - d01 * d21) / den;  b2 = (d00 * d21 - d01 * d20) / den;  b0 = (1.f - b1) - b2
+ *     ns  = vunit(vadd(vadd(vmul(n0, b0), vmul(n1, b1)), vmul(n2, b2)));  if (face & 1) ns = vmul(ns, -1.f)
+ *     use = vdot(ns, ng) > 0.f && vdot(rd, ns) < 0.f
+ *     norm = use ? ns : ng
+ * There are no clamps and no special cases.  A flat triangle gives vunit(0) = NaN, so `use` is false and it is shaded exactly as
+ * without normals; so is a degenerate one (den = 0).  A shading normal that faces away from the incoming ray, or away from the
+ * geometric side that was hit, falls back to ng.  Hits in the edge band extrapolate slightly (b outside [0, 1]).
+ * `norm` feeds the bounce unchanged: lambertian_ray, reflect_ray, the whole RTMI_DIELECTRIC arm.  One more rule keeps a bounce ray
+ * on the right side of the real surface.  Evaluate the kind's bounce with `norm`; let dir be the direction as passed to make_ray
+ * (Matte: norm + rv; reflection: vunit(reflect + rv * scattering); refraction: td) and side = -1.f for a refracted ray, +1.f
+ * otherwise.  If use && !(side * vdot(dir, ng) > 0.f), evaluate the whole bounce again from the top with norm = ng: the same rv,
+ * the same u, no new draw.  No RNG draw moves; the fold, the stack push, black at exhausted depth and at edge faces are untouched.
+ * Only hits that bounce (not Solid, remaining depth not exhausted) look at the normals.
+ * Guide normals (rtmi_render_features*, the guides of rtmi_render_camera*, rtmi_render_rays* and rtmi_render_preview*): a triangle
+ * hit's normal is `norm` as above, from the primary ray's ro and rd, whatever the surface kind (no second rule: nothing bounces).
+ * Albedo, coverage, depth and ids do not change.
+ *
+ * rtmi_scene_set_normals: n must equal ntris.  normals9 == NULL or n == 0 removes the normals, and the scene is exactly the scene
+ * it was before.  A corner or normal that is not finite (entry 0 aside): RTMI_ERR_INVALID before any HIP call.  Setting,
+ * replacing or removing waits for the scene's work to finish first.  The corners must be the ones the records came from.
+ * rtmi_scene_get_normals copies the device table's normals back (normals9_out may be NULL; entry 0 reads as zeros); *n_out = 0
+ * means there are none.
+ *
+ * rtmi_smooth_normals generates corner normals from shared corner POSITIONS (host code, no device needed; no sentinel: all n
+ * triangles count).  facenorm3: the records' normals.  Per triangle g: x = cross(c1 - c0, c2 - c0), components written out as
+ * a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x; a_g = sqrtf(vdot(x, x)); w_g = vmul(facenorm_g, a_g).
+ * Corner k of triangle f: s = +0; for g in increasing index, if some corner of g compares == to c_fk in all three components, and
+ * g == f or vdot(facenorm_f, facenorm_g) >= crease_cos, then s = vadd(s, w_g), each g at most once per corner; n_fk = vunit(s).
+ * Area-weighted, so slivers do not tilt a vertex; crease_cos keeps edges sharper than its angle sharp (1: every corner gets its own
+ * face's normal; -1: everything that shares the position is averaged).  crease_cos outside [-1, 1] or NaN: RTMI_ERR_INVALID.
+ *
+ * A scene with vertex normals renders on the per-pass pipeline (stats.pipeline = 1, slow_paths = 0) with the smooth shading
+ * kernels (k_shade*_smooth, which also know RTMI_DIELECTRIC and the environment) and k_features_smooth, whatever the scene kind
+ * and options: every call that gains glass gains this.  rtmi_bake*'s generator takes the caller's normal as before; its traced
+ * paths bounce smoothly.  Unchanged: rtmi_trace*, rtmi_occluded*, the records, rtmi_render_ao*, _light* and the AO and light of
+ * _preview*, which use the geometric normal.  rtmi_render_shadowed* returns RTMI_ERR_UNSUPPORTED, before any HIP call.
+ * Not here: vertex normals in AO, light and preview shading; in the path kernels (pipeline 3); under rtmi_render_shadowed*; texture
+ * coordinates; normal maps; a softened shadow terminator. */
+int rtmi_scene_set_normals(rtmi_scene_t* scene, const float* corners9, const float* normals9 /* or NULL */, uint64_t n);
+int rtmi_scene_get_normals(rtmi_scene_t* scene, float* normals9_out /* n * 9, or NULL */, uint64_t* n_out);
+int rtmi_smooth_normals(const float* corners9, const float* facenorm3, uint64_t n, float crease_cos, float* normals9_out);
+
 /* Optional: the corners the triangle records were made from (`Triangle.corners`, raytrace.rs:326-337), 9 floats per
  * triangle, n = ntris (entry 0 = the sentinel's, ignored).  Only RTMI_OPT_BVH uses them: its boxes become the triangles'
  * own boxes (intersected with the bounding-radius disc's) instead of the disc's alone -- fewer boxes per ray, same hits.

@@ -63,6 +63,23 @@ int rth_scene_set_environment(rth_scene_t* s, const float* rgb, uint32_t n, cons
 int rth_scene_set_sky(rth_scene_t* s, uint32_t n, const rtmi_sky_t* sky);
 int rth_scene_environment_size(const rth_scene_t* s, uint32_t* n_out);
 int rth_caster_environment(rth_scene_t* s, float* rgb_out, uint64_t cap_floats, uint32_t* n_out);
+/* Vertex normals (rtmi_scene_set_normals / rtmi_smooth_normals in rtmi.h, which defines them): kept with the scene, 9 floats per
+ * triangle, and applied with the triangles' own corners to its resident copy on every device at the next call that uses one; the
+ * scene is not uploaded again.  Triangles that were never given normals, those appended later among them, are flat (zeros).
+ * rth_scene_set_normals: normals of triangles [first, first + count), first >= 1; normals9 == NULL removes all of them.
+ * rth_scene_smooth_normals: generated from the shared corner positions of that range alone (count = UINT64_MAX: to the end).
+ * rth_scene_normals_size: the number of triangles when the scene has normals, else 0.  rth_scene_get_normals: the scene's copy,
+ * ntris * 9 floats; rth_caster_normals uploads if need be and reads the device's table back.
+ * rth_add_obj_normals: rth_add_obj_mode, then normals for the new triangles: 0 none, 1 the file's `vn` (each through the
+ * transform and unit(); a corner without a normal index is an error), 2 generated with crease_cos. */
+int rth_scene_set_normals(rth_scene_t* s, const float* normals9, uint64_t first, uint64_t count);
+int rth_scene_smooth_normals(rth_scene_t* s, uint64_t first, uint64_t count, float crease_cos);
+int rth_scene_normals_size(const rth_scene_t* s, uint64_t* n_out);
+int rth_scene_get_normals(const rth_scene_t* s, float* normals9_out, uint64_t cap_floats);
+int rth_caster_normals(rth_scene_t* s, float* normals9_out, uint64_t cap_floats, uint64_t* n_out);
+int rth_add_obj_normals(rth_scene_t* s, const char* path, const float* offset3, float scale, const float* basis9, uint32_t kind,
+                        const float* color3, float alpha, float scattering, float edge_thickness, uint32_t robust, uint32_t normals,
+                        float crease_cos);
 void rth_populate_triangle_numbers(rth_scene_t* s);
 
 /* build_bounding_box / build_trivial_bounding_box into Scene.boxes */

@@ -595,9 +595,11 @@ namespace rtmi {
 // GLASS (k_shade*_glass): shade_hit<true>, which knows RTMI_DIELECTRIC; the launch sites pick them for scenes with a dielectric
 // ENV (k_shade*_env): shade_hit<GLASS, true>, whose misses look the scene's environment up in their ray's direction; the launch
 // sites pick them, before the glass ones, for scenes with an environment
-template <Samp S, bool GLASS = false, bool ENV = false>
+// SMOOTH (k_shade*_smooth): shade_hit<true, true, true>, which shades with the scene's vertex normals; the launch
+// sites pick them first, for scenes with normals, with or without glass and an environment (an EnvTab of n = 0 is "none")
+template <Samp S, bool GLASS = false, bool ENV = false, bool SMOOTH = false>
 __device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list = nullptr, const ViewTab& vt = ViewTab{},
-                                           const EnvTab* env = nullptr) {
+                                           const EnvTab* env = nullptr, const SmoothTab* sm = nullptr) {
     __shared__ uint32_t s_cnt[4], s_base;
     const uint32_t count = ctrl->count[pass];
     const uint32_t stride = gridDim.x * blockDim.x;
@@ -623,14 +625,14 @@ __device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __
             if constexpr (S == Samp::RAYS) {  // `list` = the batch's RNG keys (or null), pix0 = the key of its first group
                 uint32_t pixel, sample;
                 rays_key(v, pix0, path, list, pixel, sample);
-                push = shade_hit<GLASS, ENV>(sc, v.maxdepth, seed, npaths, path, pixel, sample, (uint32_t)pass, tf, t, V4{o4.x, o4.y, o4.z, o4.w},
-                                             V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr, nullptr, env);
+                push = shade_hit<GLASS, ENV, SMOOTH>(sc, v.maxdepth, seed, npaths, path, pixel, sample, (uint32_t)pass, tf, t, V4{o4.x, o4.y, o4.z, o4.w},
+                                                     V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr, nullptr, env, sm);
             } else {
             uint32_t prow, pcol, sample;
             path_pixel<S>(v, pix0, path, prow, pcol, sample, list);
             const PixKey key = pixel_key<S>(v, prow, vt);
-            push = shade_hit<GLASS, ENV>(sc, v.maxdepth, key_seed<S>(key, vt, seed), npaths, path, key.row * v.width + pcol, sample, (uint32_t)pass, tf, t,
-                                         V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr, nullptr, env);
+            push = shade_hit<GLASS, ENV, SMOOTH>(sc, v.maxdepth, key_seed<S>(key, vt, seed), npaths, path, key.row * v.width + pcol, sample, (uint32_t)pass, tf, t,
+                                                 V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr, nullptr, env, sm);
             }
             // a bounce ray with an exactly-zero direction component goes to the slow path (SlowQ), not to the next pass
             if (push && slow.cap && has_zero_component(nr.dir.x, nr.dir.y, nr.dir.z) &&
@@ -680,6 +682,12 @@ __global__ void __launch_bounds__(256) k_shade_samples_env(RTMI_SHADE_PARAMS, En
 __global__ void __launch_bounds__(256) k_shade_list_env(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list, EnvTab env) { shade_pass<Samp::LIST, true, true>(RTMI_SHADE_ARGS, list, ViewTab{}, &env); }
 __global__ void __launch_bounds__(256) k_shade_views_env(RTMI_SHADE_PARAMS, ViewTab vt, EnvTab env) { shade_pass<Samp::VIEWS, true, true>(RTMI_SHADE_ARGS, nullptr, vt, &env); }
 __global__ void __launch_bounds__(256) k_shade_rays_env(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ keys, EnvTab env) { shade_pass<Samp::RAYS, true, true>(RTMI_SHADE_ARGS, keys, ViewTab{}, &env); }
+// And for scenes with vertex normals (rtmi_scene_set_normals), with or without glass and an environment
+__global__ void __launch_bounds__(256) k_shade_smooth(RTMI_SHADE_PARAMS, EnvTab env, SmoothTab sm) { shade_pass<Samp::FRAME, true, true, true>(RTMI_SHADE_ARGS, nullptr, ViewTab{}, &env, &sm); }
+__global__ void __launch_bounds__(256) k_shade_samples_smooth(RTMI_SHADE_PARAMS, EnvTab env, SmoothTab sm) { shade_pass<Samp::PASS, true, true, true>(RTMI_SHADE_ARGS, nullptr, ViewTab{}, &env, &sm); }
+__global__ void __launch_bounds__(256) k_shade_list_smooth(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list, EnvTab env, SmoothTab sm) { shade_pass<Samp::LIST, true, true, true>(RTMI_SHADE_ARGS, list, ViewTab{}, &env, &sm); }
+__global__ void __launch_bounds__(256) k_shade_views_smooth(RTMI_SHADE_PARAMS, ViewTab vt, EnvTab env, SmoothTab sm) { shade_pass<Samp::VIEWS, true, true, true>(RTMI_SHADE_ARGS, nullptr, vt, &env, &sm); }
+__global__ void __launch_bounds__(256) k_shade_rays_smooth(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ keys, EnvTab env, SmoothTab sm) { shade_pass<Samp::RAYS, true, true, true>(RTMI_SHADE_ARGS, keys, ViewTab{}, &env, &sm); }
 
 // rtmi_scene_set_sky: texel (i, j) of an n x n environment table from the inverse of env_lookup's map -- the direction of the
 // texel's centre -- and a gradient sky with a sun disc, operation by operation as include/rtmi.h lists it.  One thread per texel.
@@ -834,6 +842,51 @@ __global__ void __launch_bounds__(256) k_features(DScene sc, uint32_t npixels, u
             __syncthreads();  // the previous chunk has been consumed
             for (uint32_t k = tid; k < n; k += 256u) {
                 const HitFeat f = hit_features(sc, hit_tf[f0 + r0 + k], hit_t[f0 + r0 + k]);
+                const uint32_t e = feat_slot(k, rot * fdiv(r0 + k, dS));
+                stage[2u * e] = f.a;
+                stage[2u * e + 1u] = f.n;
+            }
+            __syncthreads();
+            if (j < npb) {
+                const uint32_t lo = max(my0, r0), hi = min(my1, r0 + n);
+                for (uint32_t s = lo; s < hi; s++) acc = acc + stage_f[feat_slot(s - r0, rot * j) * 8u + l];
+            }
+        }
+        if (j < npb) {
+            const uint32_t lp = pix0 + pb + j, lr = fdiv(lp, dW), col = lp - lr * W;
+            const size_t o = ((size_t)lr * nsub + sub) * W + col;
+            float* __restrict__ dst = l < 4u ? albedo : normal;
+            if (dst) store_stream(&dst[o * 4u + (l & 3u)], acc * inv);
+            if (ids && l == 0u) store_stream(&ids[o], hit_tf[f0 + my0]);
+        }
+    }
+}
+// k_features for a scene with vertex normals: the same kernel statement for statement, but the normal is
+// hit_features_smooth's, which needs the primary rays (qo, qd: queue slot == path) beside the hit records.  A kernel of its own
+// and not a template over both, which changed k_features' register allocation.
+__global__ void __launch_bounds__(256) k_features_smooth(DScene sc, uint32_t npixels, uint32_t nsamples, const uint32_t* __restrict__ hit_tf,
+                                                         const float* __restrict__ hit_t, float* __restrict__ albedo, float* __restrict__ normal,
+                                                         uint32_t* __restrict__ ids, uint32_t pix0, uint32_t W, uint32_t nsub, uint32_t sub,
+                                                         FastDiv dW, FastDiv dS, const float4* __restrict__ qo, const float4* __restrict__ qd,
+                                                         SmoothTab sm) {
+    __shared__ float4 stage[2 * RTMI_FEAT_CHUNK];
+    const float* stage_f = reinterpret_cast<const float*>(stage);
+    const uint32_t tid = threadIdx.x, j = tid >> 3, l = tid & 7u;
+    const uint32_t rot = (nsamples & 3u) == 0u ? 1u : 0u;
+    const float inv = 1.f / (float)nsamples;
+    for (uint32_t pb = blockIdx.x * RTMI_FEAT_PIX; pb < npixels; pb += gridDim.x * RTMI_FEAT_PIX) {
+        const uint32_t npb = min((uint32_t)RTMI_FEAT_PIX, npixels - pb);
+        const uint32_t f0 = pb * nsamples, nb = npb * nsamples;  // the block's paths: hit_*[f0 .. f0 + nb)
+        const uint32_t my0 = j * nsamples, my1 = my0 + nsamples;  // this thread's pixel among them (when j < npb)
+        float acc = 0.f;
+        for (uint32_t r0 = 0; r0 < nb; r0 += RTMI_FEAT_CHUNK) {
+            const uint32_t n = min((uint32_t)RTMI_FEAT_CHUNK, nb - r0);
+            __syncthreads();  // the previous chunk has been consumed
+            for (uint32_t k = tid; k < n; k += 256u) {
+                const uint32_t tf = hit_tf[f0 + r0 + k];
+                float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f), d4 = make_float4(0.f, 0.f, 1.f, 0.f);
+                if ((tf & 0x3FFFFFFFu) != 0u && !((tf >> 30) & 2u)) { o4 = qo[f0 + r0 + k]; d4 = qd[f0 + r0 + k]; }
+                const HitFeat f = hit_features_smooth(sc, sm, tf, hit_t[f0 + r0 + k], V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w});
                 const uint32_t e = feat_slot(k, rot * fdiv(r0 + k, dS));
                 stage[2u * e] = f.a;
                 stage[2u * e + 1u] = f.n;
@@ -1103,6 +1156,11 @@ struct rtmi_scene {
     DevBuf<float4> env;
     EnvTab envtab{};
     bool has_env = false;
+    // rtmi_scene_set_normals: six float4 per triangle (SmoothTab, shade.hpp).  A scene with them renders on the per-pass pipeline
+    // with the k_shade*_smooth kernels, which also know glass and the environment, and k_features_smooth.
+    DevBuf<float4> smooth;
+    SmoothTab smoothtab{};
+    bool has_normals = false;
     std::vector<rtmi_triangle_t> htris;  // the records (host copy): the fast-mode BVH is rebuilt from them when corners arrive
     DevBuf<uint4> fnodes, oblocks, ocull;  // (fnodes: the node records, then the node cull records)
     DevBuf<uint32_t> wlinks, cert;
@@ -1892,7 +1950,7 @@ int rtmi_scene_destroy(rtmi_scene_t* s) {
     if (!s) return RTMI_OK;
     (void)hipSetDevice(s->device);
     s->nodes.release(); s->refs.release(); s->tplane.release(); s->tedge.release(); s->mats.release();
-    s->fnodes.release(); s->oblocks.release(); s->ocull.release(); s->cert.release(); s->wlinks.release(); s->bnodes.release(); s->bleaves.release(); s->spheres.release(); s->env.release();
+    s->fnodes.release(); s->oblocks.release(); s->ocull.release(); s->cert.release(); s->wlinks.release(); s->bnodes.release(); s->bleaves.release(); s->spheres.release(); s->env.release(); s->smooth.release();
     for (int k = 0; k < RTMI_MAX_STREAMS; k++) {
         s->w[k].release();
         if (s->istream[k]) (void)hipStreamDestroy(s->istream[k]);
@@ -2063,6 +2121,139 @@ int rtmi_scene_get_environment(rtmi_scene_t* s, float* rgb_out, uint32_t* n_out)
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(tab.data(), s->env.p, nt * sizeof(float4), hipMemcpyDeviceToHost));
     for (size_t k = 0; k < nt; k++) { rgb_out[3 * k] = tab[k].x; rgb_out[3 * k + 1] = tab[k].y; rgb_out[3 * k + 2] = tab[k].z; }
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+// the table is in place (or gone): what the k_shade*_smooth / k_features_smooth kernels get of it
+static void smooth_set(rtmi_scene_t* s, uint32_t n) {
+    s->smoothtab.tab = n ? s->smooth.p : nullptr;
+    s->smoothtab.n = n;
+    s->has_normals = n != 0u;
+}
+
+int rtmi_scene_set_normals(rtmi_scene_t* s, const float* corners9, const float* normals9, uint64_t n) {
+    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
+    const bool set = normals9 && n;
+    if (set) {
+        if (!corners9) return fail(RTMI_ERR_INVALID, "normals: corners is NULL");
+        if (n != s->d.ntris) return fail(RTMI_ERR_INVALID, "normals: n must equal ntris");
+        for (uint64_t k = 9; k < n * 9; k++) {  // (entry 0 is the sentinel's and is ignored)
+            if (!std::isfinite(corners9[k])) return fail(RTMI_ERR_INVALID, "normals: a corner of triangle " + std::to_string(k / 9) + " is not finite");
+            if (!std::isfinite(normals9[k])) return fail(RTMI_ERR_INVALID, "normals: a normal of triangle " + std::to_string(k / 9) + " is not finite");
+        }
+    }
+    RTMI_GUARD_BEGIN
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipDeviceSynchronize());  // no render of this scene is in flight: its streams are done with the old table
+    if (!set) {
+        smooth_set(s, 0u);
+        s->smooth.release();
+        return RTMI_OK;
+    }
+    // the per-triangle part of the definition, once: f32, every step rounded (this file is compiled without contraction)
+    std::vector<float4> tab((size_t)n * 6, make_float4(0.f, 0.f, 0.f, 0.f));
+    for (uint64_t g = 1; g < n; g++) {
+        const float *c = corners9 + 9 * g, *nn = normals9 + 9 * g;
+        const V4 c0 = mk(c[0], c[1], c[2]), e1 = vsub(mk(c[3], c[4], c[5]), c0), e2 = vsub(mk(c[6], c[7], c[8]), c0);
+        const float d00 = vdot(e1, e1), d01 = vdot(e1, e2), d11 = vdot(e2, e2), den = d00 * d11 - d01 * d01;
+        float4* r = &tab[(size_t)g * 6];
+        r[0] = make_float4(c0.x, c0.y, c0.z, d00);
+        r[1] = make_float4(e1.x, e1.y, e1.z, d01);
+        r[2] = make_float4(e2.x, e2.y, e2.z, d11);
+        r[3] = make_float4(nn[0], nn[1], nn[2], den);
+        r[4] = make_float4(nn[3], nn[4], nn[5], 0.f);
+        r[5] = make_float4(nn[6], nn[7], nn[8], 0.f);
+    }
+    smooth_set(s, 0u);  // (a failure below leaves the scene without normals, not with stale ones)
+    HIPCHK(s->smooth.ensure(tab.size()));
+    HIPCHK(hipMemcpy(s->smooth.p, tab.data(), tab.size() * sizeof(float4), hipMemcpyHostToDevice));
+    smooth_set(s, (uint32_t)n);
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+int rtmi_scene_get_normals(rtmi_scene_t* s, float* normals9_out, uint64_t* n_out) {
+    if (!s || !n_out) return fail(RTMI_ERR_INVALID, "NULL argument");
+    *n_out = s->has_normals ? s->smoothtab.n : 0u;
+    if (!s->has_normals || !normals9_out) return RTMI_OK;
+    RTMI_GUARD_BEGIN
+    const size_t n = s->smoothtab.n;
+    std::vector<float4> tab(n * 6);
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(tab.data(), s->smooth.p, tab.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t g = 0; g < n; g++)
+        for (int k = 0; k < 3; k++) {
+            const float4 q = tab[g * 6 + 3 + k];
+            normals9_out[9 * g + 3 * k] = q.x; normals9_out[9 * g + 3 * k + 1] = q.y; normals9_out[9 * g + 3 * k + 2] = q.z;
+        }
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+// rtmi_smooth_normals (include/rtmi.h): host code, no HIP call.  The definition sums, per corner, the area-weighted face normals of
+// the triangles that share the corner's position, in increasing triangle index.  Here the positions are hashed once (-0 as +0,
+// which == does not tell apart; a NaN equals nothing and is left out) to the increasing list of the triangles that touch them, so
+// a corner walks its own position's list only: the same additions in the same order, in about O(n).
+int rtmi_smooth_normals(const float* corners9, const float* facenorm3, uint64_t n, float crease_cos, float* normals9_out) {
+    if (!(crease_cos >= -1.f && crease_cos <= 1.f)) return fail(RTMI_ERR_INVALID, "smooth_normals: crease_cos must be in [-1, 1]");
+    if (n == 0) return RTMI_OK;
+    if (!corners9 || !facenorm3 || !normals9_out) return fail(RTMI_ERR_INVALID, "NULL argument");
+    if (n > 0x3FFFFFFFull) return fail(RTMI_ERR_INVALID, "smooth_normals: too many triangles");
+    RTMI_GUARD_BEGIN
+    struct Key {
+        uint32_t x, y, z;
+        bool operator==(const Key& o) const { return x == o.x && y == o.y && z == o.z; }
+    };
+    struct KeyHash {
+        size_t operator()(const Key& k) const {
+            uint64_t h = k.x * 0x9E3779B97F4A7C15ull;
+            h = (h ^ (h >> 29) ^ k.y) * 0xBF58476D1CE4E5B9ull;
+            h = (h ^ (h >> 32) ^ k.z) * 0x94D049BB133111EBull;
+            return (size_t)(h ^ (h >> 31));
+        }
+    };
+    auto key_of = [](const float* p, Key& k) {
+        if (p[0] != p[0] || p[1] != p[1] || p[2] != p[2]) return false;
+        const float q[3] = {p[0] + 0.f, p[1] + 0.f, p[2] + 0.f};  // -0 + 0 = +0
+        memcpy(&k, q, sizeof k);
+        return true;
+    };
+    std::vector<V4> wg(n);
+    std::unordered_map<Key, uint32_t, KeyHash> slot;
+    slot.reserve((size_t)n * 3 / 2 + 16);
+    std::vector<std::vector<uint32_t>> touch;
+    for (uint64_t g = 0; g < n; g++) {
+        const float* c = corners9 + 9 * g;
+        const V4 a = vsub(mk(c[3], c[4], c[5]), mk(c[0], c[1], c[2])), b = vsub(mk(c[6], c[7], c[8]), mk(c[0], c[1], c[2]));
+        const V4 x = mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
+        wg[g] = vmul(mk(facenorm3[3 * g], facenorm3[3 * g + 1], facenorm3[3 * g + 2]), sqrtf(vdot(x, x)));
+        for (int k = 0; k < 3; k++) {
+            Key key;
+            if (!key_of(c + 3 * k, key)) continue;
+            auto it = slot.find(key);
+            if (it == slot.end()) {
+                it = slot.emplace(key, (uint32_t)touch.size()).first;
+                touch.emplace_back();
+            }
+            std::vector<uint32_t>& l = touch[it->second];
+            if (l.empty() || l.back() != (uint32_t)g) l.push_back((uint32_t)g);  // each g at most once per position
+        }
+    }
+    for (uint64_t f = 0; f < n; f++) {
+        const V4 nf = mk(facenorm3[3 * f], facenorm3[3 * f + 1], facenorm3[3 * f + 2]);
+        for (int k = 0; k < 3; k++) {
+            V4 s = mk(0.f, 0.f, 0.f);
+            Key key;
+            if (key_of(corners9 + 9 * f + 3 * k, key))
+                for (uint32_t g : touch[slot.find(key)->second])
+                    if (g == f || vdot(nf, mk(facenorm3[3 * g], facenorm3[3 * g + 1], facenorm3[3 * g + 2])) >= crease_cos) s = vadd(s, wg[g]);
+            const V4 u = vunit(s);
+            float* o = normals9_out + 9 * f + 3 * k;
+            o[0] = u.x; o[1] = u.y; o[2] = u.z;
+        }
+    }
     return RTMI_OK;
     RTMI_GUARD_END
 }
@@ -2368,6 +2559,19 @@ static int check_view(const rtmi_viewport_t* vp, const rtmi_tile_t* tile) {
 }
 
 // The plan of a call: its streams, their sub-tiles and the batch size, with every stream's workspace sized for it.
+// k_features on the hit records of the primary queue (qo, qd), or k_features_smooth for a scene with vertex normals: the queue is
+// still intact at every site that calls this (the shading of pass 0 writes the OTHER queue)
+static void launch_features(rtmi_scene* s, dim3 grid, dim3 block, hipStream_t st, uint32_t npixels, uint32_t nsamples, const uint32_t* hit_tf,
+                            const float* hit_t, float* albedo, float* normal, uint32_t* ids, uint32_t pix0, uint32_t W, uint32_t nsub, uint32_t sub,
+                            const float4* qo, const float4* qd) {
+    if (s->has_normals)
+        hipLaunchKernelGGL(k_features_smooth, grid, block, 0, st, s->d, npixels, nsamples, hit_tf, hit_t, albedo, normal, ids, pix0, W, nsub, sub,
+                           make_fastdiv(W), make_fastdiv(nsamples), qo, qd, s->smoothtab);
+    else
+        hipLaunchKernelGGL(k_features, grid, block, 0, st, s->d, npixels, nsamples, hit_tf, hit_t, albedo, normal, ids, pix0, W, nsub, sub,
+                           make_fastdiv(W), make_fastdiv(nsamples));
+}
+
 static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t* tile, TileCall& c) {
     const uint32_t nrows = tile->nrows, spp = c.spp;
     const uint64_t npix = (uint64_t)nrows * c.W;
@@ -2379,7 +2583,7 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
     // shades the primary rays in one kernel.  Everything else (pipeline 1, linear list, generic tree, BVH mode,
     // analytic spheres) starts with k_gen.  Both then run one closest-hit + one shading launch per bounce pass.
     c.path_kernels = !c.fo && !c.ao && !c.li && !c.pv && !c.sh && !c.cam && s->tune.pipeline != 1u && s->octree && !s->root_is_leaf &&
-                     !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) && s->d.nspheres == 0 && !s->has_dielectric && !s->has_env;
+                     !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) && s->d.nspheres == 0 && !s->has_dielectric && !s->has_env && !s->has_normals;
     // streams = 0 (automatic): one stream for path-kernel tiles of 2^26 paths and more, three otherwise (the per-pass
     // pipelines -- BVH mode: 29.6 ms on three streams, 35.2 on one -- have elementwise kernels to hide).  Since k_shade stopped being
     // atomic-bound (round 3) there is little left for a second stream to hide: the full config-3 frame takes 366.9 ms on one
@@ -2542,8 +2746,8 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
         HIPCHK(hipEventRecord(w.pass_ev[0], st));
         launch_trace(s, w, st, w.qo[0].p, w.qd[0].p, 0, c.counting, w.pass_ev[1]);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_features, ew_grid, ew_block, 0, st, s->d, np, c.spp, w.hit_tf.p, w.hit_t.p, (float*)c.fo->albedo,
-                           (float*)c.fo->normal, c.fo->ids, pix0, c.W, c.nsub, t, make_fastdiv(c.W), make_fastdiv(c.spp));
+        launch_features(s, ew_grid, ew_block, st, np, c.spp, w.hit_tf.p, w.hit_t.p, (float*)c.fo->albedo, (float*)c.fo->normal, c.fo->ids, pix0,
+                        c.W, c.nsub, t, w.qo[0].p, w.qd[0].p);
         HIPCHK(hipEventRecord(w.ev[1], st));
         HIPCHK(hipGetLastError());
         return RTMI_OK;
@@ -2595,8 +2799,8 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
         HIPCHK(hipGetLastError());
         // before the walk: its closest-hit fallback writes the workspace's hit records
         if (p.fo.albedo || p.fo.normal || p.fo.ids)
-            hipLaunchKernelGGL(k_features, ew_grid, ew_block, 0, st, s->d, np, c.spp, w.hit_tf.p, w.hit_t.p, (float*)p.fo.albedo,
-                               (float*)p.fo.normal, p.fo.ids, pix0, c.W, c.nsub, t, make_fastdiv(c.W), make_fastdiv(c.spp));
+            launch_features(s, ew_grid, ew_block, st, np, c.spp, w.hit_tf.p, w.hit_t.p, (float*)p.fo.albedo, (float*)p.fo.normal, p.fo.ids, pix0,
+                            c.W, c.nsub, t, w.qo[0].p, w.qd[0].p);
         // ctrl->count[1] (zero since the batch's memset) is the compaction's counter and then the walk's ray count
         hipLaunchKernelGGL(k_preview_rays, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, p.a, w.qo[0].p, w.qd[0].p, w.hit_tf.p,
                            w.hit_t.p, b.qo.p, b.qd.p, b.tmax.p, b.c.p, b.aslot.p, b.lslot.p, b.alb.p, w.ctrl.p);
@@ -2646,15 +2850,29 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
         launch_trace(s, w, st, w.qo[a].p, w.qd[a].p, (int)pass, c.counting, w.pass_ev[2 * pass + 1]);
         HIPCHK(hipGetLastError());
         if (pass == 0 && c.cam && (c.cam->fo.albedo || c.cam->fo.normal || c.cam->fo.ids))  // the guides, before pass 1 rewrites the hit records
-            hipLaunchKernelGGL(k_features, ew_grid, ew_block, 0, st, s->d, np, c.spp, w.hit_tf.p, w.hit_t.p, (float*)c.cam->fo.albedo,
-                               (float*)c.cam->fo.normal, c.cam->fo.ids, pix0, c.W, c.nsub, t, make_fastdiv(c.W), make_fastdiv(c.spp));
+            launch_features(s, ew_grid, ew_block, st, np, c.spp, w.hit_tf.p, w.hit_t.p, (float*)c.cam->fo.albedo, (float*)c.cam->fo.normal,
+                            c.cam->fo.ids, pix0, c.W, c.nsub, t, w.qo[a].p, w.qd[a].p);
         if (c.counting && s->verbose && !c.path_kernels) {
             int rc = dump_pass_counters(s, w, st, t, pass);
             if (rc != RTMI_OK) return rc;
         }
         const bool glass = s->has_dielectric;  // (never with c.path_kernels: sq is off and k_path_slow, which has no glass arm, never runs)
         // a scene with an environment (never with c.path_kernels either): the _env kernels, which also know glass
-        if (s->has_env && list)
+        // a scene with vertex normals (never with c.path_kernels either): the _smooth kernels, which know glass and the environment
+        // (s->envtab.n = 0 without one)
+        if (s->has_normals && list)
+            hipLaunchKernelGGL(k_shade_list_smooth, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
+                               w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, list, s->envtab,
+                               s->smoothtab);
+        else if (s->has_normals && c.mode == Samp::VIEWS)
+            hipLaunchKernelGGL(k_shade_views_smooth, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
+                               w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, c.vt, s->envtab,
+                               s->smoothtab);
+        else if (s->has_normals)
+            hipLaunchKernelGGL(c.mode == Samp::PASS ? k_shade_samples_smooth : k_shade_smooth, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths,
+                               (int)pass, w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p,
+                               w.mstack.p, w.scol.p, w.ctrl.p, sq, s->envtab, s->smoothtab);
+        else if (s->has_env && list)
             hipLaunchKernelGGL(k_shade_list_env, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
                                w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, list, s->envtab);
         else if (s->has_env && c.mode == Samp::VIEWS)
@@ -3236,6 +3454,8 @@ static int refuse_scene_shadowed(const rtmi_scene_t* s) {
         return fail(RTMI_ERR_UNSUPPORTED, "shadowed: the scene has a dielectric surface (the shadowed shading has no glass arm)");
     if (s->has_env)
         return fail(RTMI_ERR_UNSUPPORTED, "shadowed: the scene has an environment (the shadowed shading has no environment arm)");
+    if (s->has_normals)
+        return fail(RTMI_ERR_UNSUPPORTED, "shadowed: the scene has vertex normals (the shadowed shading has no smooth arm)");
     return RTMI_OK;
 }
 
@@ -4118,9 +4338,12 @@ static int render_rays(rtmi_scene_t* s, uint64_t n, const void* orig4, const voi
             launch_trace(s, w, st, pqo, pqd, (int)pass, counting, w.pass_ev[2 * pass + 1]);
             HIPCHK(hipGetLastError());
             if (pass == 0 && guides)  // before pass 1 rewrites the hit records
-                hipLaunchKernelGGL(k_features, ew_grid, ew_block, 0, st, s->d, ng, G, w.hit_tf.p, w.hit_t.p, (float*)albedo, (float*)normal, ids,
-                                   0u, ng, 1u, 0u, make_fastdiv(ng), make_fastdiv(G));
-            if (shade && s->has_env)
+                launch_features(s, ew_grid, ew_block, st, ng, G, w.hit_tf.p, w.hit_t.p, (float*)albedo, (float*)normal, ids, 0u, ng, 1u, 0u, pqo, pqd);
+            if (shade && s->has_normals)
+                hipLaunchKernelGGL(k_shade_rays_smooth, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(rp->pixel0 + gbase), nb, (int)pass, pqo, pqd,
+                                   w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, scol, w.ctrl.p,
+                                   SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, kq, s->envtab, s->smoothtab);
+            else if (shade && s->has_env)
                 hipLaunchKernelGGL(k_shade_rays_env, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(rp->pixel0 + gbase), nb, (int)pass, pqo, pqd,
                                    w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, scol, w.ctrl.p,
                                    SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, kq, s->envtab);
@@ -4306,7 +4529,11 @@ static int bake(rtmi_scene_t* s, uint64_t M, const void* pos4, const void* nrm4,
             if (pass == 0 && open)  // before pass 1 rewrites the hit records
                 hipLaunchKernelGGL(k_bake_open, dim3(std::min<unsigned>((unsigned)(s->num_cu * 8), (mb + RTMI_BAKE_OPEN_ELEMS - 1u) / RTMI_BAKE_OPEN_ELEMS)),
                                    ew_block, 0, st, mb, K, w.hit_tf.p, open);
-            if (shade && s->has_env)
+            if (shade && s->has_normals)
+                hipLaunchKernelGGL(k_shade_rays_smooth, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(bp->pixel0 + mbase), nb, (int)pass, pqo, pqd,
+                                   w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p,
+                                   SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, (const uint32_t*)nullptr, s->envtab, s->smoothtab);
+            else if (shade && s->has_env)
                 hipLaunchKernelGGL(k_shade_rays_env, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(bp->pixel0 + mbase), nb, (int)pass, pqo, pqd,
                                    w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p,
                                    SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, (const uint32_t*)nullptr, s->envtab);

@@ -205,6 +205,75 @@ __device__ inline V4 env_lookup(const EnvTab& e, V4 d) {
     return mix_color(mix_color(v4(c00), v4(c10), tx), mix_color(v4(c01), v4(c11), tx), ty);
 }
 
+// The vertex normals of a scene (rtmi_scene_set_normals, include/rtmi.h "VERTEX NORMALS OF A SCENE"): six float4
+// per triangle, (c0, d00) (e1, d01) (e2, d11) (n0, den) (n1, 0) (n2, 0) -- corner 0, the two edges from it, their dot products and
+// the three corner normals -- entry 0 the sentinel's, n = ntris.  An argument of the k_shade*_smooth and k_features_smooth kernels
+// only, as EnvTab is of its kernels: DScene, and with it every other kernel's argument block, stays as it is.
+struct SmoothTab { const float4* __restrict__ tab; uint32_t n; };
+// The shading normal at `point` of triangle `tri` (< sm.n), operation by operation as include/rtmi.h lists it: barycentric
+// coordinates from the stored dot products, the corner normals interpolated and normalised, * -1.f on a back face.  ng = the
+// record's normal, already * -1.f on a back face.  use: the result faces the geometric side that was hit and the incoming ray;
+// otherwise (a flat triangle's NaN among the cases) the caller shades with ng.  The six loads do not depend on each other and
+// are requested together.
+__device__ inline V4 smooth_normal(const SmoothTab& sm, uint32_t tri, uint32_t face, V4 point, V4 rd, V4 ng, bool& use) {
+    const float4* __restrict__ r = sm.tab + (size_t)tri * 6u;
+    const float4 q0 = r[0], q1 = r[1], q2 = r[2], q3 = r[3], q4 = r[4], q5 = r[5];
+    const V4 e1 = mk(q1.x, q1.y, q1.z), e2 = mk(q2.x, q2.y, q2.z);
+    const float d00 = q0.w, d01 = q1.w, d11 = q2.w, den = q3.w;
+    const V4 w = vsub(point, mk(q0.x, q0.y, q0.z));
+    const float d20 = vdot(w, e1), d21 = vdot(w, e2);
+    const float b1 = (d11 * d20 - d01 * d21) / den, b2 = (d00 * d21 - d01 * d20) / den, b0 = (1.f - b1) - b2;
+    V4 ns = vunit(vadd(vadd(vmul(mk(q3.x, q3.y, q3.z), b0), vmul(mk(q4.x, q4.y, q4.z), b1)), vmul(mk(q5.x, q5.y, q5.z), b2)));
+    if (face & 1u) ns = vmul(ns, -1.f);
+    use = vdot(ns, ng) > 0.f && vdot(rd, ns) < 0.f;
+    return ns;
+}
+// The bounce of one hit with normal `norm`: shade_hit's three arms (lambertian_ray, reflect_ray, the dielectric of include/rtmi.h)
+// statement for statement, for the kernels that may evaluate it twice (SMOOTH).  dir: the direction as passed to make_ray;
+// side: -1.f for a refracted ray, +1.f otherwise.
+template <bool GLASS>
+__device__ inline RayV bounce_ray(uint32_t kind, float m1x, uint32_t face, V4 point, V4 norm, V4 rd, V4 rv, float u3, V4& dir, float& side) {
+    float scat = m1x;
+    side = 1.f;
+    if constexpr (GLASS) {
+        if (kind == RTMI_DIELECTRIC) {  // m1x = ior
+            const float ior = m1x;
+            const float ci = fabsf(vdot(rd, norm));
+            const float eta = (face & 1u) ? ior : 1.f / ior;
+            const float s2 = 1.f - ci * ci;
+            const float k = 1.f - (eta * eta) * s2;
+            const bool tir = !(k >= 0.f);
+            const float ct = sqrtf(k);
+            const float cs = (face & 1u) ? ct : ci;
+            float r0 = (1.f - ior) / (1.f + ior);
+            r0 = r0 * r0;
+            const float x = 1.f - cs, x2 = x * x, x5 = (x2 * x2) * x;
+            const float R = r0 + (1.f - r0) * x5;
+            if (!(tir || u3 < R)) {
+                const V4 perp = vmul(vadd(rd, vmul(norm, ci)), eta);
+                const V4 par = vmul(norm, -ct);
+                const V4 td = vunit(vadd(perp, par));
+                dir = td;
+                side = -1.f;
+                return make_ray(vadd(point, vmul(td, 0.001f)), td);
+            }
+            scat = 0.f;
+        }
+    }
+    if (kind == RTMI_MATTE) {
+        dir = vadd(norm, rv);
+        return make_ray(vadd(point, vmul(rv, 0.001f)), dir);
+    }
+    const float ddot = fabsf(vdot(rd, norm));
+    const V4 dir_p = vmul(norm, ddot);
+    const V4 dir_o = vadd(rd, dir_p);
+    const V4 reflect = vadd(dir_p, dir_o);
+    const V4 rvf = vmul(rv, scat);
+    const V4 reflect_dir = vunit(vadd(reflect, rvf));
+    dir = vunit(vadd(reflect, rvf));
+    return make_ray(vadd(point, vmul(reflect_dir, 0.001f)), dir);
+}
+
 // color_ray + the tail of project_ray for ONE traced ray of a path.  `pass` = bounces the path has behind it (the ray's
 // remaining depth is maxdepth - pass >= 1); tf = hit triangle | face << 30 (0 = miss), t = hit time; (ro, rd) the ray.
 // Returns true when the path goes on: its surface has been pushed on the path's stack (mstack[pass][path]) and `nr` is
@@ -219,15 +288,21 @@ __device__ inline V4 env_lookup(const EnvTab& e, V4 d) {
 // ENV: the kernels of scenes with an environment (k_shade*_env) start a miss's fold at env_lookup(*env, rd) instead of the sky
 // constant -- rd must then be the ray's direction for a miss too -- and nothing else moves: no draw, no ray, black at an edge
 // face and at exhausted depth.  Without it `env` is never read.
-template <bool GLASS = false, bool ENV = false>
+// SMOOTH: the kernels of scenes with vertex normals (k_shade*_smooth, always with GLASS and ENV) shade a bouncing triangle hit
+// with smooth_normal's result where it is usable, and evaluate the bounce again with the geometric normal when the ray it gives
+// leaves on the wrong side of the real surface: same rv, same u3, no new draw.  Their `env` may be an empty table (n = 0: the
+// scene has normals and no environment), and a miss then starts at the sky constant.  Without it `sm` is never read.
+template <bool GLASS = false, bool ENV = false, bool SMOOTH = false>
 __device__ inline bool shade_hit(const DScene& sc, uint32_t maxdepth, uint64_t seed, uint32_t npaths, uint32_t path, uint32_t pixel,
                                  uint32_t sample, uint32_t pass, uint32_t tf, float t, V4 ro, V4 rd, uint16_t* __restrict__ mstack,
-                                 float4* __restrict__ scol, RayV& nr, bool* mirror = nullptr, const EnvTab* env = nullptr) {
+                                 float4* __restrict__ scol, RayV& nr, bool* mirror = nullptr, const EnvTab* env = nullptr,
+                                 const SmoothTab* sm = nullptr) {
     const uint32_t tri = tf & 0x3FFFFFFFu, face = tf >> 30;
     V4 c;
     uint32_t npushed = pass;
     if (tri == 0) {
-        if constexpr (ENV) c = env_lookup(*env, rd);
+        if constexpr (ENV && SMOOTH) c = env->n ? env_lookup(*env, rd) : mk(128.f / 255.f, 180.f / 255.f, 255.f / 255.f);
+        else if constexpr (ENV) c = env_lookup(*env, rd);
         else c = mk(128.f / 255.f, 180.f / 255.f, 255.f / 255.f);  // raytrace.rs:1264
     } else if (face & 2u) {
         c = mk(0.f / 255.f, 0.f / 255.f, 0.f / 255.f);  // edge faces are Solid black, raytrace.rs:452-457
@@ -257,6 +332,21 @@ __device__ inline bool shade_hit(const DScene& sc, uint32_t maxdepth, uint64_t s
                 V4 rv;
                 if constexpr (GLASS) rv = random_vec_u(seed, pixel, sample, pass + 1u, u3);
                 else rv = random_vec(seed, pixel, sample, pass + 1u);
+                if constexpr (SMOOTH) {
+                    bool use = false;
+                    V4 n = norm;
+                    if (!is_sphere && tri < sm->n) n = smooth_normal(*sm, tri, face, point, rd, norm, use);
+                    if (!use) n = norm;
+                    for (;;) {
+                        V4 dir;
+                        float side;
+                        nr = bounce_ray<GLASS>(kind, m1.x, face, point, n, rd, rv, u3, dir, side);
+                        if (!use || side * vdot(dir, norm) > 0.f) break;
+                        n = norm;  // the ray leaves on the wrong side of the real surface: the whole bounce again with ng
+                        use = false;
+                    }
+                    return true;
+                }
                 float scat = m1.x;
                 if constexpr (GLASS) {
                     if (kind == RTMI_DIELECTRIC) {  // m1.x = ior
@@ -332,6 +422,19 @@ __device__ inline HitFeat hit_features(const DScene& sc, uint32_t tf, float t) {
     f.n.y = hit ? norm.y : 0.f;
     f.n.z = hit ? norm.z : 0.f;
     f.n.w = hit ? t : 0.f;
+    return f;
+}
+// hit_features for a scene with vertex normals (k_features_smooth): the normal of a triangle hit that is no edge face is the
+// shading normal of include/rtmi.h -- smooth_normal at the hit point of the primary ray (ro, rd) where it is usable, the
+// geometric one otherwise.  Albedo, coverage and depth are hit_features'.
+__device__ inline HitFeat hit_features_smooth(const DScene& sc, const SmoothTab& sm, uint32_t tf, float t, V4 ro, V4 rd) {
+    HitFeat f = hit_features(sc, tf, t);
+    const uint32_t tri = tf & 0x3FFFFFFFu, face = tf >> 30;
+    if (tri != 0u && !(face & 2u) && tri < sm.n) {
+        bool use = false;
+        const V4 ns = smooth_normal(sm, tri, face, vadd(vmul(rd, t), ro), rd, mk(f.n.x, f.n.y, f.n.z), use);
+        if (use) { f.n.x = ns.x; f.n.y = ns.y; f.n.z = ns.z; }
+    }
     return f;
 }
 

@@ -86,6 +86,36 @@ int rth_add_obj_mode(rth_scene_t* s, const char* path, const float* off, float s
         s->scene.touch();
     });
 }
+// rth_add_obj_mode, and (normals = 1) the file's vn normals for the new triangles, or (normals = 2) generated ones
+// (rtmi_smooth_normals over the new triangles with crease_cos)
+int rth_add_obj_normals(rth_scene_t* s, const char* path, const float* off, float scale, const float* b9, uint32_t kind, const float* c,
+                        float alpha, float scat, float edge, uint32_t robust, uint32_t normals, float crease_cos) {
+    if (normals == 0) return rth_add_obj_mode(s, path, off, scale, b9, kind, c, alpha, scat, edge, robust);
+    if (normals > 2) return guarded([] { throw std::runtime_error("rth_add_obj_normals: normals must be 0 (none), 1 (file) or 2 (smooth)"); });
+    if (normals == 2 && !(crease_cos >= -1.f && crease_cos <= 1.f))
+        return guarded([] { throw std::runtime_error("smooth_normals: crease_cos must be in [-1, 1]"); });
+    const uint64_t first = s->scene.tris.size();
+    uint64_t count = 0;
+    const int rc = guarded([&] {
+        std::vector<float> n9;
+        auto t = obj_parser::parse_obj(path, v3(off), scale, std::make_tuple(v3(b9), v3(b9 + 3), v3(b9 + 6)), surf(kind, c, alpha, scat), edge,
+                                       robust ? obj_parser::ObjMode::Robust : obj_parser::ObjMode::Reference, normals == 1 ? &n9 : nullptr);
+        count = t.size();
+        if (first == 0 && count) throw std::runtime_error("vertex normals: the scene needs its sentinel triangle first");
+        s->scene.tris.insert(s->scene.tris.end(), t.begin(), t.end());
+        s->scene.touch();
+        if (normals == 1 && count) {
+            for (float x : n9)
+                if (!std::isfinite(x)) throw std::runtime_error("parse_obj: a vn normal is zero or not finite");
+            std::vector<float>& v = s->scene.normals;
+            v.resize((first + count) * 9, 0.f);
+            std::copy(n9.begin(), n9.end(), v.begin() + first * 9);
+            s->scene.normals_generation++;
+        }
+    });
+    if (rc != 0 || normals != 2 || count == 0) return rc;
+    return rth_scene_smooth_normals(s, first, count, crease_cos);
+}
 int rth_add_disk(rth_scene_t* s, const float* orig3, const float* norm3, float r, float d, uint64_t n, uint32_t kind,
                  const float* c, float alpha, float scat, uint32_t skind, const float* sc, float salpha, float sscat, float edge) {
     return guarded([&] {
@@ -161,6 +191,64 @@ int rth_caster_environment(rth_scene_t* s, float* rgb_out, uint64_t cap_floats, 
         if (rgb.size() > cap_floats) throw std::runtime_error("rth_caster_environment: the buffer is too small");
         if (!rgb.empty()) memcpy(rgb_out, rgb.data(), rgb.size() * sizeof(float));
         *n_out = n;
+    });
+}
+// [first, first + count) clipped to the scene's triangles; count = UINT64_MAX: to the end.  The sentinel (0) is not a triangle.
+static void normals_range(const rth_scene_t* s, uint64_t first, uint64_t& count) {
+    const uint64_t n = s->scene.tris.size();
+    if (first < 1 || first > n) throw std::runtime_error("vertex normals: first must be 1 to the number of triangles");
+    if (count == UINT64_MAX) count = n - first;
+    if (count > n - first) throw std::runtime_error("vertex normals: the range ends beyond the last triangle");
+}
+int rth_scene_set_normals(rth_scene_t* s, const float* normals9, uint64_t first, uint64_t count) {
+    return guarded([&] {
+        if (!normals9) { s->scene.normals.clear(); s->scene.normals_generation++; return; }
+        normals_range(s, first, count);
+        for (uint64_t k = 0; k < count * 9; k++)
+            if (!std::isfinite(normals9[k])) throw std::runtime_error("vertex normals: a normal of triangle " + std::to_string(first + k / 9) + " is not finite");
+        std::vector<float>& v = s->scene.normals;
+        if (v.size() < (first + count) * 9) v.resize((first + count) * 9, 0.f);
+        std::copy(normals9, normals9 + count * 9, v.begin() + first * 9);
+        s->scene.normals_generation++;
+    });
+}
+int rth_scene_smooth_normals(rth_scene_t* s, uint64_t first, uint64_t count, float crease_cos) {
+    return guarded([&] {
+        normals_range(s, first, count);
+        std::vector<float> corners(count * 9), fn(count * 3), out(count * 9);
+        for (uint64_t i = 0; i < count; i++) {
+            const Triangle& t = s->scene.tris[first + i];
+            for (int k = 0; k < 3; k++) memcpy(&corners[9 * i + 3 * k], t.corners[k].v, 12);
+            memcpy(&fn[3 * i], t.norm.v, 12);
+        }
+        if (rtmi_smooth_normals(corners.data(), fn.data(), count, crease_cos, out.data()) != RTMI_OK)
+            throw std::runtime_error(std::string("rtmi_smooth_normals: ") + rtmi_last_error());
+        for (float x : out)
+            if (!std::isfinite(x)) throw std::runtime_error("smooth_normals: a generated normal is not finite (a degenerate triangle?)");
+        std::vector<float>& v = s->scene.normals;
+        if (v.size() < (first + count) * 9) v.resize((first + count) * 9, 0.f);
+        std::copy(out.begin(), out.end(), v.begin() + first * 9);
+        s->scene.normals_generation++;
+    });
+}
+int rth_scene_normals_size(const rth_scene_t* s, uint64_t* n_out) {
+    *n_out = s->scene.normals.empty() ? 0u : s->scene.tris.size();
+    return 0;
+}
+int rth_scene_get_normals(const rth_scene_t* s, float* normals9_out, uint64_t cap_floats) {
+    return guarded([&] {
+        const size_t want = s->scene.normals.empty() ? 0 : s->scene.tris.size() * 9;
+        if (want > cap_floats) throw std::runtime_error("rth_scene_get_normals: the buffer is too small");
+        std::fill(normals9_out, normals9_out + want, 0.f);
+        std::copy(s->scene.normals.begin(), s->scene.normals.begin() + std::min(want, s->scene.normals.size()), normals9_out);
+    });
+}
+int rth_caster_normals(rth_scene_t* s, float* normals9_out, uint64_t cap_floats, uint64_t* n_out) {
+    return guarded([&] {
+        const std::vector<float> v = caster_of(s).vertex_normals(s->scene);
+        if (v.size() > cap_floats) throw std::runtime_error("rth_caster_normals: the buffer is too small");
+        if (!v.empty()) memcpy(normals9_out, v.data(), v.size() * sizeof(float));
+        *n_out = v.size() / 9;
     });
 }
 void rth_populate_triangle_numbers(rth_scene_t* s) { populate_triangle_numbers(s->scene.tris); s->scene.touch(); }

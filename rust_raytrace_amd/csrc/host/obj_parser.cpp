@@ -55,15 +55,31 @@ size_t parse_index_relative(const std::string& tok, const std::string& line, siz
     }
     return parse_index(tok, line);
 }
+// normals9: the third field of a face corner "a/b/c" or "a//c" as a 1-based index into the vn lines (Robust: "-k" counts back from
+// the normals read so far); 0 = none or invalid
+size_t parse_normal_index(const std::string& tok, size_t nnormals, bool robust) {
+    const size_t s1 = tok.find('/');
+    const size_t s2 = s1 == std::string::npos ? s1 : tok.find('/', s1 + 1);
+    if (s2 == std::string::npos) return 0;
+    const std::string f = tok.substr(s2 + 1);
+    if (robust && f.size() > 1 && f[0] == '-' && f.find_first_not_of("0123456789", 1) == std::string::npos) {
+        const size_t back = (size_t)strtoull(f.c_str() + 1, nullptr, 10);
+        return back >= 1 && back <= nnormals ? nnormals - back + 1 : 0;
+    }
+    if (f.empty() || f.find_first_not_of("0123456789") != std::string::npos) return 0;
+    return (size_t)strtoull(f.c_str(), nullptr, 10);
+}
 }  // namespace
 
 std::vector<Triangle> parse_obj(const std::string& path, const Vec3& offset, float scale,
                                 const std::tuple<Vec3, Vec3, Vec3>& transform, const SurfaceKind& surface,
-                                float edge_thickness, ObjMode mode) {
+                                float edge_thickness, ObjMode mode, std::vector<float>* normals9) {
     std::ifstream f(path, std::ios::binary);
     if (!f) throw std::runtime_error("parse_obj: cannot read " + path);
     std::vector<Vec3> vertices;
     std::vector<std::vector<size_t>> faces;
+    std::vector<Vec3> vnormals;                 // normals9 only
+    std::vector<std::vector<size_t>> fnormals;  // normals9 only: per face, the corners' normal indices
     std::string line;
     while (std::getline(f, line)) {
         if (!line.empty() && line.back() == '\r') line.pop_back();
@@ -76,6 +92,15 @@ std::vector<Triangle> parse_obj(const std::string& path, const Vec3& offset, flo
             for (const auto& tok : fields(line.substr(2)))
                 corners.push_back(mode == ObjMode::Robust ? parse_index_relative(tok, line, vertices.size()) : parse_index(tok, line));
             faces.push_back(std::move(corners));
+            if (normals9) {
+                std::vector<size_t> ni;
+                for (const auto& tok : fields(line.substr(2))) ni.push_back(parse_normal_index(tok, vnormals.size(), mode == ObjMode::Robust));
+                fnormals.push_back(std::move(ni));
+            }
+        } else if (normals9 && line.compare(0, 3, "vn ") == 0) {
+            const auto parts = fields(line.substr(3));
+            if (parts.size() != 3) throw std::runtime_error("parse_obj: normal line needs exactly 3 numbers: " + line);
+            vnormals.push_back(make_vec(parse_f32(parts[0], line), parse_f32(parts[1], line), parse_f32(parts[2], line)));
         }
     }
     std::vector<Triangle> objs;
@@ -84,17 +109,29 @@ std::vector<Triangle> parse_obj(const std::string& path, const Vec3& offset, flo
         if (idx < 1 || idx > vertices.size()) throw std::runtime_error("parse_obj: face index out of range");
         return vertices[idx - 1].mult(scale).change_basis(transform).add(offset);
     };
-    for (const auto& face : faces) {
+    auto push_normals = [&](size_t fi, size_t a, size_t b, size_t c) {  // of the triangle just pushed: corners a, b, c of face fi
+        if (!normals9) return;
+        for (size_t k : {a, b, c}) {
+            const size_t idx = fnormals[fi][k];
+            if (idx < 1 || idx > vnormals.size()) throw std::runtime_error("parse_obj: a face corner has no normal index, or one out of range");
+            const Vec3 n = vnormals[idx - 1].change_basis(transform).unit();
+            normals9->insert(normals9->end(), n.v, n.v + 3);
+        }
+    };
+    for (size_t fi = 0; fi < faces.size(); fi++) {
+        const auto& face = faces[fi];
         if (face.size() < 3) throw std::runtime_error("parse_obj: face with fewer than 3 corners");
         if (mode == ObjMode::Reference) {  // first three corners, whatever follows (obj_parser.rs:63-65)
             Vec3 pts[3] = {place(face[0]), place(face[1]), place(face[2])};
             objs.push_back(make_triangle(pts, surface, edge_thickness));
+            push_normals(fi, 0, 1, 2);
             continue;
         }
         for (size_t k = 1; k + 1 < face.size(); k++) {  // fan: (c0, ck, ck+1)
             Vec3 pts[3] = {place(face[0]), place(face[k]), place(face[k + 1])};
             try { objs.push_back(make_triangle(pts, surface, edge_thickness)); }
-            catch (const std::runtime_error&) {}  // degenerate sliver of a polygon: skipped (the reference would panic, raytrace.rs:357)
+            catch (const std::runtime_error&) { continue; }  // degenerate sliver of a polygon: skipped (the reference would panic, raytrace.rs:357)
+            push_normals(fi, 0, k, k + 1);
         }
     }
     return objs;

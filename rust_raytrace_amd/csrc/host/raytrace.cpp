@@ -554,6 +554,45 @@ void HipRayCaster::invalidate() {
     extra_.clear();
     handle_ = nullptr; key_scene_ = nullptr;
     env_applied_ = false;
+    normals_applied_ = false;
+}
+
+void HipRayCaster::apply_normals(const Scene& s) {
+    if (normals_applied_ && key_normals_generation_ == s.normals_generation) return;
+    std::vector<rtmi_scene_t*> all{handle_};
+    all.insert(all.end(), extra_.begin(), extra_.end());
+    std::vector<float> corners, normals;
+    if (!s.normals.empty()) {
+        const size_t n = s.tris.size();
+        corners.assign(n * 9, 0.f);
+        normals.assign(n * 9, 0.f);  // triangles beyond the ones that were given normals are flat
+        for (size_t i = 1; i < n; i++)
+            for (int k = 0; k < 3; k++)
+                for (int c = 0; c < 3; c++) corners[9 * i + 3 * k + c] = s.tris[i].corners[k].v[c];
+        std::copy(s.normals.begin(), s.normals.begin() + std::min(s.normals.size(), normals.size()), normals.begin());
+    }
+    for (rtmi_scene_t* hh : all) {
+        if (s.normals.empty() && !normals_applied_) continue;  // fresh handles have none
+        const int rc = s.normals.empty() ? rtmi_scene_set_normals(hh, nullptr, nullptr, 0)
+                                         : rtmi_scene_set_normals(hh, corners.data(), normals.data(), s.tris.size());
+        if (rc != RTMI_OK) {
+            const std::string msg = std::string("rtmi_scene_set_normals: ") + rtmi_last_error();
+            invalidate();
+            throw std::runtime_error(msg);
+        }
+    }
+    normals_applied_ = true;
+    key_normals_generation_ = s.normals_generation;
+}
+
+std::vector<float> HipRayCaster::vertex_normals(const Scene& s) {
+    rtmi_scene_t* h = resident(s);
+    uint64_t n = 0;
+    if (rtmi_scene_get_normals(h, nullptr, &n) != RTMI_OK) throw std::runtime_error(std::string("rtmi_scene_get_normals: ") + rtmi_last_error());
+    std::vector<float> out((size_t)n * 9);
+    if (n && rtmi_scene_get_normals(h, out.data(), &n) != RTMI_OK)
+        throw std::runtime_error(std::string("rtmi_scene_get_normals: ") + rtmi_last_error());
+    return out;
 }
 
 void HipRayCaster::apply_environment(const Scene& s) {
@@ -633,6 +672,7 @@ rtmi_scene_t* HipRayCaster::resident(const Scene& s) {
     if (handle_ && key_scene_ == &s && key_generation_ == s.generation && key_ntris_ == s.tris.size() &&
         key_nboxes_ == s.boxes.boxes.size() && key_nrefs_ == s.boxes.tri_refs.size()) {
         apply_environment(s);
+        apply_normals(s);
         apply_settings();
         return handle_;
     }
@@ -689,6 +729,7 @@ rtmi_scene_t* HipRayCaster::resident(const Scene& s) {
     key_scene_ = &s; key_generation_ = s.generation; key_ntris_ = s.tris.size();
     key_nboxes_ = s.boxes.boxes.size(); key_nrefs_ = s.boxes.tri_refs.size();
     apply_environment(s);
+    apply_normals(s);
     apply_settings();
     return handle_;
 }

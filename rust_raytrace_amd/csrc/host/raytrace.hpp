@@ -159,6 +159,11 @@ struct Scene {
     // generation.
     std::optional<Environment> environment;
     uint64_t env_generation = 0;
+    // Vertex normals (include/rtmi.h, "VERTEX NORMALS OF A SCENE"), or none (empty): 9 floats per triangle, entry
+    // i for tris[i], all zero = flat.  May be shorter than tris: triangles appended after the normals were set are flat.  Applied
+    // like the environment: code that edits `normals` bumps normals_generation, not generation.
+    std::vector<float> normals;
+    uint64_t normals_generation = 0;
     // debug_en: walk_rays also records sample 0's primary ray of every pixel into `debug` (the reference's debug_ctx, which
     // walk_rays fills through a &Scene: hence mutable).  Octree scenes only; walk_rays throws before rendering otherwise.
     bool debug_en = false;
@@ -355,6 +360,9 @@ public:
     // The environment table of the scene's resident copy on the first device (rtmi_scene_get_environment): n * n * 3 floats,
     // empty and n = 0 when the scene has none.
     std::vector<float> environment(const Scene& s, uint32_t& n);
+    // The vertex normals of the scene's resident copy on the first device (rtmi_scene_get_normals): ntris * 9 floats, empty when
+    // the scene has none.
+    std::vector<float> vertex_normals(const Scene& s);
     uint64_t seed;
     int device;
 
@@ -367,6 +375,9 @@ private:
     uint64_t key_env_generation_ = 0;
     bool env_applied_ = false;                 // the handles carry Scene::environment as of key_env_generation_
     void apply_environment(const Scene& s);
+    uint64_t key_normals_generation_ = 0;
+    bool normals_applied_ = false;             // the handles carry Scene::normals as of key_normals_generation_
+    void apply_normals(const Scene& s);
     size_t key_ntris_ = 0, key_nboxes_ = 0, key_nrefs_ = 0;
     uint32_t options_ = 0;
     rtmi_tuning_t tuning_{}, defaults_{};
@@ -387,7 +398,10 @@ namespace obj_parser {
 enum class ObjMode { Reference = 0, Robust = 1 };
 std::vector<Triangle> parse_obj(const std::string& path, const Vec3& offset, float scale,
                                 const std::tuple<Vec3, Vec3, Vec3>& transform, const SurfaceKind& surface,
-                                float edge_thickness, ObjMode mode = ObjMode::Reference);
+                                float edge_thickness, ObjMode mode = ObjMode::Reference, std::vector<float>* normals9 = nullptr);
+// normals9 (an extension; NULL: the loader above exactly): also read the `vn` lines and the third field of every a/b/c or a//c
+// face corner, in either mode, and append 9 floats per returned triangle: each corner's normal through change_basis(transform)
+// and unit(), no scale and no offset.  A corner without a normal index, or one out of range, throws.
 }  // namespace obj_parser
 
 // raytrace.rs:1460-1478: quantisation only ((c*255.) as u8); PNG encoding stays with the caller.

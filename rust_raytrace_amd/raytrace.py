@@ -139,11 +139,20 @@ class Scene:
         pts = _f(points).reshape(-1, 9)
         _chk(_ffi.lib().rth_add_triangles_gpu(self.h, _p(pts), pts.shape[0], *surface.args(), edge_thickness, device))
 
-    def extend_parse_obj(self, path, offset, scale, transform, surface, edge_thickness, robust=False):
+    def extend_parse_obj(self, path, offset, scale, transform, surface, edge_thickness, robust=False, normals=None, crease_cos=0.5):
         """obj_data.extend(obj_parser::parse_obj(...)) — obj_parser.rs:47-73.  robust=True is an opt-in loader extension
-        (fan-triangulated polygons, negative indices, degenerate triangles skipped); the default is the reference's loader."""
-        _chk(_ffi.lib().rth_add_obj_mode(self.h, path.encode(), _p(_f(offset)), scale, _p(_f(transform)), *surface.args(),
-                                         edge_thickness, 1 if robust else 0))
+        (fan-triangulated polygons, negative indices, degenerate triangles skipped); the default is the reference's loader.
+        normals (an extension, include/rtmi.h "VERTEX NORMALS OF A SCENE"): None leaves the mesh flat; "file" reads the `vn` lines
+        and the third field of every a/b/c or a//c face corner (each normal through the transform and unit(); a corner without a
+        normal index is an error); "smooth" generates them from the mesh's shared corner positions (smooth_normals)."""
+        if normals not in (None, "file", "smooth"):
+            raise ValueError(f"extend_parse_obj: normals must be None, 'file' or 'smooth', not {normals!r}")
+        if normals is None:
+            _chk(_ffi.lib().rth_add_obj_mode(self.h, path.encode(), _p(_f(offset)), scale, _p(_f(transform)), *surface.args(),
+                                             edge_thickness, 1 if robust else 0))
+        else:
+            _chk(_ffi.lib().rth_add_obj_normals(self.h, path.encode(), _p(_f(offset)), scale, _p(_f(transform)), *surface.args(),
+                                                edge_thickness, 1 if robust else 0, 1 if normals == "file" else 2, float(crease_cos)))
 
     def extend_make_disk(self, orig, norm, r, d, num_tris, surface, side_surface, edge_thickness):
         """obj_data.extend(make_disk(...)) — raytrace.rs:531-592"""
@@ -191,6 +200,35 @@ class Scene:
     def clear_environment(self):
         """Back to the reference's sky constant: the scene is exactly the scene it was before it had an environment."""
         _chk(_ffi.lib().rth_scene_set_environment(self.h, None, 0, None))
+
+    # --- vertex normals: a build-defined extension (include/rtmi.h, "VERTEX NORMALS OF A SCENE")
+    def smooth_normals(self, first=1, count=None, crease_cos=0.5):
+        """Generate vertex normals for triangles [first, first + count) (default: all), for example one mesh, from the corner
+        positions they share among themselves (rtmi_smooth_normals): area-weighted face normals, averaged across the edges whose
+        faces' normals have a cosine of at least crease_cos.  Triangles outside the range keep what they had (flat if nothing)."""
+        _chk(_ffi.lib().rth_scene_smooth_normals(self.h, int(first), 2 ** 64 - 1 if count is None else int(count), float(crease_cos)))
+
+    def set_vertex_normals(self, normals, first=1):
+        """Corner normals of triangles first, first + 1, ...: (n, 3, 3) f32, corner k of triangle i at [i, k].  A triangle whose
+        nine floats are zero is flat.  Kept with the scene; HipRayCaster applies them on every device it uploads to."""
+        t = _f(normals)
+        if t.ndim != 3 or t.shape[1:] != (3, 3):
+            raise ValueError(f"vertex normals must be (n, 3, 3), not {t.shape}")
+        _chk(_ffi.lib().rth_scene_set_normals(self.h, _p(t), int(first), t.shape[0]))
+
+    def vertex_normals(self):
+        """The scene's vertex normals, (ntris, 3, 3) f32 with entry 0 the sentinel's (zeros), or None when it has none"""
+        n = C.c_uint64(0)
+        _chk(_ffi.lib().rth_scene_normals_size(self.h, C.byref(n)))
+        if n.value == 0:
+            return None
+        out = np.zeros((n.value, 3, 3), np.float32)
+        _chk(_ffi.lib().rth_scene_get_normals(self.h, _p(out), out.size))
+        return out
+
+    def clear_vertex_normals(self):
+        """Back to flat shading: the scene is exactly the scene it was before it had vertex normals."""
+        _chk(_ffi.lib().rth_scene_set_normals(self.h, None, 0, 0))
 
     # --- Scene.boxes
     def build_bounding_box(self, orig, len2, maxdepth, minobjs, threads=0, gpu_device=None):
@@ -1378,6 +1416,18 @@ class HipRayCaster:
         _chk(_ffi.lib().rth_caster_environment(s.h, _p(rgb), rgb.size, C.byref(n)))
         return rgb
 
+    def vertex_normals(self, s):
+        """The vertex normals as the first device holds them (rtmi_scene_get_normals): (ntris, 3, 3) f32, or None when the scene
+        has none.  Uploads first if need be."""
+        self._config(s)
+        n = C.c_uint64(0)
+        _chk(_ffi.lib().rth_scene_normals_size(s.h, C.byref(n)))
+        if n.value == 0:
+            return None
+        out = np.zeros((n.value, 3, 3), np.float32)
+        _chk(_ffi.lib().rth_caster_normals(s.h, _p(out), out.size, C.byref(n)))
+        return out
+
     def trace(self, s, orig4, dir4):
         """Closest hit per explicit ray (rtmi_trace): -> tri, t, face, stats."""
         o4, d4 = _f(orig4).reshape(-1, 4), _f(dir4).reshape(-1, 4)
@@ -1692,11 +1742,12 @@ def quantize(rgba):
 
 
 # ---------------------------------------------------------------- scenes of the benchmark configs
-def canonical_scene(obj_path, accel="octree", maxdepth=10, minobjs=19, teapot_surface=None, threads=0, gpu_build=None):
-    """The scene of raytrace/src/main.rs:116-164."""
+def canonical_scene(obj_path, accel="octree", maxdepth=10, minobjs=19, teapot_surface=None, threads=0, gpu_build=None, smooth=False):
+    """The scene of raytrace/src/main.rs:116-164.  smooth (an extension): the teapot gets generated vertex normals."""
     s = Scene(with_dummy=True)
     tsurf = teapot_surface or SurfaceKind.Matte(make_color(252, 119, 0), 0.2)
-    s.extend_parse_obj(obj_path, [0.0, 0.5, 5.0], 1.0, create_transform(unit([0.0, 0.3, 1.0]), to_radians(270.0)), tsurf, 0.05)
+    s.extend_parse_obj(obj_path, [0.0, 0.5, 5.0], 1.0, create_transform(unit([0.0, 0.3, 1.0]), to_radians(270.0)), tsurf, 0.05,
+                       normals="smooth" if smooth else None)
     side = SurfaceKind.Matte(make_color(40, 40, 40), 0.2)
     s.extend_make_disk([4.0, 4.0, 7.0], unit([-0.3, -0.55, -0.5]), 2.0, 0.1, 50,
                        SurfaceKind.Reflective(0.0002, make_color(230, 230, 230), 0.7), side, -1.0)
