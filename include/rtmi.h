@@ -317,11 +317,71 @@ int rtmi_scene_set_sky(rtmi_scene_t* scene, uint32_t n, const rtmi_sky_t* sky /*
  * and options: every call that gains glass gains this.  rtmi_bake*'s generator takes the caller's normal as before; its traced
  * paths bounce smoothly.  Unchanged: rtmi_trace*, rtmi_occluded*, the records, rtmi_render_ao*, _light* and the AO and light of
  * _preview*, which use the geometric normal.  rtmi_render_shadowed* returns RTMI_ERR_UNSUPPORTED, before any HIP call.
- * Not here: vertex normals in AO, light and preview shading; in the path kernels (pipeline 3); under rtmi_render_shadowed*; texture
- * coordinates; normal maps; a softened shadow terminator. */
+ * Not here: vertex normals in AO, light and preview shading; in the path kernels (pipeline 3); under rtmi_render_shadowed*; normal
+ * maps; a softened shadow terminator. */
 int rtmi_scene_set_normals(rtmi_scene_t* scene, const float* corners9, const float* normals9 /* or NULL */, uint64_t n);
 int rtmi_scene_get_normals(rtmi_scene_t* scene, float* normals9_out /* n * 9, or NULL */, uint64_t* n_out);
 int rtmi_smooth_normals(const float* corners9, const float* facenorm3, uint64_t n, float crease_cos, float* normals9_out);
+
+/* TEXTURES OF A SCENE: per-corner texture coordinates and a bilinear image lookup at every hit.  NOT part of the
+ * reference, which has neither uvs nor images, so this build defines it, operation by operation like the environment and the
+ * vertex normals.  All arithmetic is f32: + - * /, floorf and comparisons only, plain loads (not the texture unit), no
+ * contraction, every step rounded.  vdot, mix_color are the reference's.
+ *
+ * Images: rtmi_texture_t.rgb is width * height * 3 floats, row-major, texel (i, j) at rgb[3 * (j * width + i)], row 0 is v = 0.
+ * Any float value is allowed.  On the device a texel is one float4 with lane 3 = +0; all images sit in one buffer behind a table
+ * of (offset, width, height) per image.  Limits: ntex <= 256, width and height 1..8192, at most 2^26 texels in all; flags = 0.
+ * UVs: n must equal ntris, entry 0 the sentinel's and ignored; uvs6 = (u0, v0, u1, v1, u2, v2) per triangle; tex_of_tri[i] = 0 for
+ * no texture or 1..ntex; corners9 as in rtmi_scene_set_normals.  Per triangle, once, by exactly that section's statements:
+ *     e1 = c1 - c0;  e2 = c2 - c0
+ *     d00 = vdot(e1, e1);  d01 = vdot(e1, e2);  d11 = vdot(e2, e2);  den = d00 * d11 - d01 * d01
+ * A triangle with den == 0.f is stored with texture 0.
+ *
+ * The colour of a hit of a triangle (not an analytic sphere, not an edge face) with tex_of_tri != 0, image W x H, with
+ * point = rd * t + ro as color_ray computes it:
+ *     w = point - c0;  d20 = vdot(w, e1);  d21 = vdot(w, e2)
+ *     b1 = (d11 * d20 - d01 * d21) / den;  b2 = (d00 * d21 - d01 * d20) / den;  b0 = (1.f - b1) - b2
+ *     u = (u0 * b0 + u1 * b1) + u2 * b2;  v = (v0 * b0 + v1 * b1) + v2 * b2
+ *     fu = u - floorf(u);  fv = v - floorf(v)                                                        (repeat)
+ *     fx = fu * (float)W - 0.5f;  fy = fv * (float)H - 0.5f
+ *     cx = !(fx >= -1.f) ? -1.f : (fx > (float)W - 1.f ? (float)W - 1.f : fx);  cy likewise with H    (indices only; a NaN gives -1)
+ *     ix = (int)floorf(cx);  iy = (int)floorf(cy);  tx = fx - floorf(fx);  ty = fy - floorf(fy)      (weights: the unclamped values)
+ *     wrap(i, N) = i < 0 ? i + N : (i >= N ? i - N : i);  T(i, j) = texel (wrap(i, W), wrap(j, H))
+ *     tc = mix_color(mix_color(T(ix, iy), T(ix + 1, iy), tx), mix_color(T(ix, iy + 1), T(ix + 1, iy + 1), tx), ty)
+ *     colour = (material.color.x * tc.x, material.color.y * tc.y, material.color.z * tc.z, +0)
+ * For every value that is not NaN the clamp changes no index: fx lies in [-0.5, W - 0.5] (fu == 1.f, which a tiny negative u rounds
+ * to, included), so ix is in [-1, W - 1] and one wrap step is enough down to W = 1.  A NaN coordinate reads texels near index
+ * W - 1 or 0 and gives a NaN colour.  alpha, scattering and the kind stay the material's; an untextured hit's colour is the
+ * material's, unmodified.  The four loads are issued together.
+ * Where the colour goes: a Solid hit ends its path with `colour`.  Every other hit pushes (colour.rgb, material.alpha) on a colour
+ * stack beside the surface stack, and the fold of the nested mix_color calls reads the level's colour and alpha there.  No draw and
+ * no ray count moves; black at edge faces and at exhausted depth (the level is still pushed and coloured).  Guides: the albedo of
+ * rtmi_render_features* and of the guides of rtmi_render_camera* and rtmi_render_rays* is `colour` for such a hit; coverage, normal,
+ * depth and ids are unchanged.
+ *
+ * rtmi_scene_set_textures: tex == NULL or ntex == 0 removes everything, and the scene is exactly the scene it was before.
+ * RTMI_ERR_INVALID before any HIP call, naming the first offender: flags != 0, a limit exceeded, a tex_of_tri above ntex, a corner
+ * or uv of a textured triangle that is not finite.  Setting, replacing or removing waits for the scene's work to finish first.
+ * rtmi_scene_get_uvs copies the device table's uvs and texture numbers back (either may be NULL; *n_out = 0: no textures; a
+ * degenerate triangle reads as texture 0).  rtmi_scene_get_texture: image k = 1..ntex of the device's buffer (rgb_out may be NULL
+ * for the size alone).
+ * rtmi_project_uvs (host code, no device needed; no sentinel: all n triangles count) is a box projection.  Per triangle the axis a
+ * is that of the largest |facenorm| component: x if |x| >= |y| and |x| >= |z|, else y if |y| >= |z|, else z.  Corner p gets
+ * (u, v) = ((p[j] - lo[j]) * scale, (p[k] - lo[k]) * scale) with (j, k) = (y, z) for a = x, (z, x) for a = y, (x, y) for a = z.
+ *
+ * A scene with textures renders on the per-pass pipeline (stats.pipeline = 1, slow_paths = 0) with the k_shade*_tex kernels (which
+ * also know RTMI_DIELECTRIC, the environment and vertex normals) and k_features_tex, whatever the scene kind and options: every call
+ * that gains vertex normals gains this.  Unchanged: rtmi_trace*, rtmi_occluded*, the records, rtmi_render_ao*, _light*.
+ * rtmi_render_shadowed* and rtmi_render_preview* return RTMI_ERR_UNSUPPORTED, before any HIP call.
+ * Not here: mip maps and any minification filter, clamp or mirror wrap modes, textures on analytic spheres, normal, roughness and
+ * alpha maps, sRGB decoding and image file loading, textures in the path kernels (pipeline 3), under the preview and the shadowed
+ * call. */
+typedef struct rtmi_texture { const float* rgb; uint32_t width, height, flags /* 0 */; } rtmi_texture_t;
+int rtmi_scene_set_textures(rtmi_scene_t* scene, const rtmi_texture_t* tex /* or NULL */, uint32_t ntex, const float* corners9,
+                            const float* uvs6, const uint32_t* tex_of_tri, uint64_t n);
+int rtmi_scene_get_uvs(rtmi_scene_t* scene, float* uvs6_out /* n * 6, or NULL */, uint32_t* tex_of_tri_out /* n, or NULL */, uint64_t* n_out);
+int rtmi_scene_get_texture(rtmi_scene_t* scene, uint32_t k, float* rgb_out /* or NULL */, uint32_t* w_out, uint32_t* h_out);
+int rtmi_project_uvs(const float* corners9, const float* facenorm3, uint64_t n, const float lo[3], float scale, float* uvs6_out);
 
 /* Optional: the corners the triangle records were made from (`Triangle.corners`, raytrace.rs:326-337), 9 floats per
  * triangle, n = ntris (entry 0 = the sentinel's, ignored).  Only RTMI_OPT_BVH uses them: its boxes become the triangles'

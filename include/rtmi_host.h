@@ -80,6 +80,27 @@ int rth_caster_normals(rth_scene_t* s, float* normals9_out, uint64_t cap_floats,
 int rth_add_obj_normals(rth_scene_t* s, const char* path, const float* offset3, float scale, const float* basis9, uint32_t kind,
                         const float* color3, float alpha, float scattering, float edge_thickness, uint32_t robust, uint32_t normals,
                         float crease_cos);
+/* Textures (rtmi_scene_set_textures / rtmi_project_uvs in rtmi.h, which defines them): kept with the scene and applied with the
+ * triangles' own corners to its resident copy on every device at the next call that uses one; the scene is not uploaded again.
+ * Triangles that were never given uvs, those appended later among them, are untextured.
+ * rth_scene_set_textures: the images (copied); tex == NULL or ntex == 0 removes the images, the uvs and the texture numbers.
+ * rth_scene_set_uvs: uvs (6 floats) and texture numbers of triangles [first, first + count), first >= 1.
+ * rth_scene_project_uvs: rtmi_project_uvs over that range (count = UINT64_MAX: to the end), which gets texture number `texture`.
+ * rth_scene_textures_size: the number of images, and the number of triangles when the scene has images or uvs, else 0.
+ * rth_scene_get_uvs / rth_scene_get_texture: the scene's copy; rth_caster_uvs / rth_caster_texture upload if need be and read the
+ * device's tables back (k = 1..ntex; rgb_out = NULL in rth_scene_get_texture: the size alone).
+ * rth_add_obj_uvs: rth_add_obj_mode, then the file's `vt` coordinates for the new triangles (the second field of every a/b or a/b/c
+ * corner; a corner without one is an error), which get texture number `texture`. */
+int rth_scene_set_textures(rth_scene_t* s, const rtmi_texture_t* tex, uint32_t ntex);
+int rth_scene_set_uvs(rth_scene_t* s, const float* uvs6, const uint32_t* tex_of_tri, uint64_t first, uint64_t count);
+int rth_scene_project_uvs(rth_scene_t* s, uint64_t first, uint64_t count, const float* lo3, float scale, uint32_t texture);
+int rth_scene_textures_size(const rth_scene_t* s, uint32_t* ntex_out, uint64_t* n_out);
+int rth_scene_get_uvs(const rth_scene_t* s, float* uvs6_out, uint32_t* tex_of_tri_out, uint64_t cap_tris);
+int rth_scene_get_texture(const rth_scene_t* s, uint32_t k, float* rgb_out, uint64_t cap_floats, uint32_t* w_out, uint32_t* h_out);
+int rth_caster_uvs(rth_scene_t* s, float* uvs6_out, uint32_t* tex_of_tri_out, uint64_t cap_tris, uint64_t* n_out);
+int rth_caster_texture(rth_scene_t* s, uint32_t k, float* rgb_out, uint64_t cap_floats, uint32_t* w_out, uint32_t* h_out);
+int rth_add_obj_uvs(rth_scene_t* s, const char* path, const float* offset3, float scale, const float* basis9, uint32_t kind,
+                    const float* color3, float alpha, float scattering, float edge_thickness, uint32_t robust, uint32_t texture);
 void rth_populate_triangle_numbers(rth_scene_t* s);
 
 /* build_bounding_box / build_trivial_bounding_box into Scene.boxes */

@@ -597,9 +597,13 @@ namespace rtmi {
 // sites pick them, before the glass ones, for scenes with an environment
 // SMOOTH (k_shade*_smooth): shade_hit<true, true, true>, which shades with the scene's vertex normals; the launch
 // sites pick them first, for scenes with normals, with or without glass and an environment (an EnvTab of n = 0 is "none")
-template <Samp S, bool GLASS = false, bool ENV = false, bool SMOOTH = false>
+// TEX (k_shade*_tex): shade_hit<true, true, true, true>, which colours a hit from the scene's textures and folds over the colour
+// stack; the launch sites pick them before all others, for scenes with textures, with or without glass, an
+// environment and vertex normals (a SmoothTab of n = 0 is "none")
+template <Samp S, bool GLASS = false, bool ENV = false, bool SMOOTH = false, bool TEX = false>
 __device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list = nullptr, const ViewTab& vt = ViewTab{},
-                                           const EnvTab* env = nullptr, const SmoothTab* sm = nullptr) {
+                                           const EnvTab* env = nullptr, const SmoothTab* sm = nullptr, const TexTab* tex = nullptr,
+                                           float4* __restrict__ cstack = nullptr) {
     __shared__ uint32_t s_cnt[4], s_base;
     const uint32_t count = ctrl->count[pass];
     const uint32_t stride = gridDim.x * blockDim.x;
@@ -625,14 +629,14 @@ __device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __
             if constexpr (S == Samp::RAYS) {  // `list` = the batch's RNG keys (or null), pix0 = the key of its first group
                 uint32_t pixel, sample;
                 rays_key(v, pix0, path, list, pixel, sample);
-                push = shade_hit<GLASS, ENV, SMOOTH>(sc, v.maxdepth, seed, npaths, path, pixel, sample, (uint32_t)pass, tf, t, V4{o4.x, o4.y, o4.z, o4.w},
-                                                     V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr, nullptr, env, sm);
+                push = shade_hit<GLASS, ENV, SMOOTH, TEX>(sc, v.maxdepth, seed, npaths, path, pixel, sample, (uint32_t)pass, tf, t, V4{o4.x, o4.y, o4.z, o4.w},
+                                                     V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr, nullptr, env, sm, tex, cstack);
             } else {
             uint32_t prow, pcol, sample;
             path_pixel<S>(v, pix0, path, prow, pcol, sample, list);
             const PixKey key = pixel_key<S>(v, prow, vt);
-            push = shade_hit<GLASS, ENV, SMOOTH>(sc, v.maxdepth, key_seed<S>(key, vt, seed), npaths, path, key.row * v.width + pcol, sample, (uint32_t)pass, tf, t,
-                                                 V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr, nullptr, env, sm);
+            push = shade_hit<GLASS, ENV, SMOOTH, TEX>(sc, v.maxdepth, key_seed<S>(key, vt, seed), npaths, path, key.row * v.width + pcol, sample, (uint32_t)pass, tf, t,
+                                                 V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr, nullptr, env, sm, tex, cstack);
             }
             // a bounce ray with an exactly-zero direction component goes to the slow path (SlowQ), not to the next pass
             if (push && slow.cap && has_zero_component(nr.dir.x, nr.dir.y, nr.dir.z) &&
@@ -688,6 +692,13 @@ __global__ void __launch_bounds__(256) k_shade_samples_smooth(RTMI_SHADE_PARAMS,
 __global__ void __launch_bounds__(256) k_shade_list_smooth(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list, EnvTab env, SmoothTab sm) { shade_pass<Samp::LIST, true, true, true>(RTMI_SHADE_ARGS, list, ViewTab{}, &env, &sm); }
 __global__ void __launch_bounds__(256) k_shade_views_smooth(RTMI_SHADE_PARAMS, ViewTab vt, EnvTab env, SmoothTab sm) { shade_pass<Samp::VIEWS, true, true, true>(RTMI_SHADE_ARGS, nullptr, vt, &env, &sm); }
 __global__ void __launch_bounds__(256) k_shade_rays_smooth(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ keys, EnvTab env, SmoothTab sm) { shade_pass<Samp::RAYS, true, true, true>(RTMI_SHADE_ARGS, keys, ViewTab{}, &env, &sm); }
+// And for scenes with textures (rtmi_scene_set_textures), with or without glass, an environment and vertex normals.
+// cstack: the colour stack, one float4 (colour.rgb, alpha) beside every mstack entry.
+__global__ void __launch_bounds__(256) k_shade_tex(RTMI_SHADE_PARAMS, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack) { shade_pass<Samp::FRAME, true, true, true, true>(RTMI_SHADE_ARGS, nullptr, ViewTab{}, &env, &sm, &tex, cstack); }
+__global__ void __launch_bounds__(256) k_shade_samples_tex(RTMI_SHADE_PARAMS, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack) { shade_pass<Samp::PASS, true, true, true, true>(RTMI_SHADE_ARGS, nullptr, ViewTab{}, &env, &sm, &tex, cstack); }
+__global__ void __launch_bounds__(256) k_shade_list_tex(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack) { shade_pass<Samp::LIST, true, true, true, true>(RTMI_SHADE_ARGS, list, ViewTab{}, &env, &sm, &tex, cstack); }
+__global__ void __launch_bounds__(256) k_shade_views_tex(RTMI_SHADE_PARAMS, ViewTab vt, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack) { shade_pass<Samp::VIEWS, true, true, true, true>(RTMI_SHADE_ARGS, nullptr, vt, &env, &sm, &tex, cstack); }
+__global__ void __launch_bounds__(256) k_shade_rays_tex(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ keys, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack) { shade_pass<Samp::RAYS, true, true, true, true>(RTMI_SHADE_ARGS, keys, ViewTab{}, &env, &sm, &tex, cstack); }
 
 // rtmi_scene_set_sky: texel (i, j) of an n x n environment table from the inverse of env_lookup's map -- the direction of the
 // texel's centre -- and a gradient sky with a sun disc, operation by operation as include/rtmi.h lists it.  One thread per texel.
@@ -887,6 +898,50 @@ __global__ void __launch_bounds__(256) k_features_smooth(DScene sc, uint32_t npi
                 float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f), d4 = make_float4(0.f, 0.f, 1.f, 0.f);
                 if ((tf & 0x3FFFFFFFu) != 0u && !((tf >> 30) & 2u)) { o4 = qo[f0 + r0 + k]; d4 = qd[f0 + r0 + k]; }
                 const HitFeat f = hit_features_smooth(sc, sm, tf, hit_t[f0 + r0 + k], V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w});
+                const uint32_t e = feat_slot(k, rot * fdiv(r0 + k, dS));
+                stage[2u * e] = f.a;
+                stage[2u * e + 1u] = f.n;
+            }
+            __syncthreads();
+            if (j < npb) {
+                const uint32_t lo = max(my0, r0), hi = min(my1, r0 + n);
+                for (uint32_t s = lo; s < hi; s++) acc = acc + stage_f[feat_slot(s - r0, rot * j) * 8u + l];
+            }
+        }
+        if (j < npb) {
+            const uint32_t lp = pix0 + pb + j, lr = fdiv(lp, dW), col = lp - lr * W;
+            const size_t o = ((size_t)lr * nsub + sub) * W + col;
+            float* __restrict__ dst = l < 4u ? albedo : normal;
+            if (dst) store_stream(&dst[o * 4u + (l & 3u)], acc * inv);
+            if (ids && l == 0u) store_stream(&ids[o], hit_tf[f0 + my0]);
+        }
+    }
+}
+// k_features for a scene with textures: k_features_smooth statement for statement, with hit_features_tex's albedo
+// (sm may be an empty table).  A kernel of its own for k_features_smooth's reason.
+__global__ void __launch_bounds__(256) k_features_tex(DScene sc, uint32_t npixels, uint32_t nsamples, const uint32_t* __restrict__ hit_tf,
+                                                      const float* __restrict__ hit_t, float* __restrict__ albedo, float* __restrict__ normal,
+                                                      uint32_t* __restrict__ ids, uint32_t pix0, uint32_t W, uint32_t nsub, uint32_t sub,
+                                                      FastDiv dW, FastDiv dS, const float4* __restrict__ qo, const float4* __restrict__ qd,
+                                                      SmoothTab sm, TexTab tex) {
+    __shared__ float4 stage[2 * RTMI_FEAT_CHUNK];
+    const float* stage_f = reinterpret_cast<const float*>(stage);
+    const uint32_t tid = threadIdx.x, j = tid >> 3, l = tid & 7u;
+    const uint32_t rot = (nsamples & 3u) == 0u ? 1u : 0u;
+    const float inv = 1.f / (float)nsamples;
+    for (uint32_t pb = blockIdx.x * RTMI_FEAT_PIX; pb < npixels; pb += gridDim.x * RTMI_FEAT_PIX) {
+        const uint32_t npb = min((uint32_t)RTMI_FEAT_PIX, npixels - pb);
+        const uint32_t f0 = pb * nsamples, nb = npb * nsamples;  // the block's paths: hit_*[f0 .. f0 + nb)
+        const uint32_t my0 = j * nsamples, my1 = my0 + nsamples;  // this thread's pixel among them (when j < npb)
+        float acc = 0.f;
+        for (uint32_t r0 = 0; r0 < nb; r0 += RTMI_FEAT_CHUNK) {
+            const uint32_t n = min((uint32_t)RTMI_FEAT_CHUNK, nb - r0);
+            __syncthreads();  // the previous chunk has been consumed
+            for (uint32_t k = tid; k < n; k += 256u) {
+                const uint32_t tf = hit_tf[f0 + r0 + k];
+                float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f), d4 = make_float4(0.f, 0.f, 1.f, 0.f);
+                if ((tf & 0x3FFFFFFFu) != 0u && !((tf >> 30) & 2u)) { o4 = qo[f0 + r0 + k]; d4 = qd[f0 + r0 + k]; }
+                const HitFeat f = hit_features_tex(sc, sm, tex, tf, hit_t[f0 + r0 + k], V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w});
                 const uint32_t e = feat_slot(k, rot * fdiv(r0 + k, dS));
                 stage[2u * e] = f.a;
                 stage[2u * e + 1u] = f.n;
@@ -1116,6 +1171,7 @@ struct Work {
     DevBuf<uint32_t> qpath[2], hit_tf;
     DevBuf<float> hit_t;
     DevBuf<uint16_t> mstack;
+    DevBuf<float4> cstack;  // the colour stack of the k_shade*_tex kernels: allocated only for calls on a textured scene
     DevBuf<DCtrl> ctrl;
     // slow path (SlowQ): its queue, the side stream its consumer launches run on, "producer k done" / "slow path done" events
     DevBuf<float4> sqo, sqd;
@@ -1127,7 +1183,7 @@ struct Work {
     std::vector<hipEvent_t> pass_ev;  // start/stop of the trace kernel of every pass
     void release() {
         for (int k = 0; k < 2; k++) { qo[k].release(); qd[k].release(); qpath[k].release(); }
-        scol.release(); hit_tf.release(); hit_t.release(); mstack.release(); ctrl.release();
+        scol.release(); hit_tf.release(); hit_t.release(); mstack.release(); cstack.release(); ctrl.release();
         for (int k = 0; k < 2; k++) if (ev[k]) { (void)hipEventDestroy(ev[k]); ev[k] = nullptr; }
         for (hipEvent_t e : pass_ev) (void)hipEventDestroy(e);
         pass_ev.clear();
@@ -1161,6 +1217,14 @@ struct rtmi_scene {
     DevBuf<float4> smooth;
     SmoothTab smoothtab{};
     bool has_normals = false;
+    // rtmi_scene_set_textures: five float4 per triangle, one uint4 per image and the texels of all images (TexTab, shade.hpp).  A
+    // scene with them renders on the per-pass pipeline with the k_shade*_tex kernels, which also know glass, the environment and
+    // vertex normals, and k_features_tex.
+    DevBuf<float4> textri, texels;
+    DevBuf<uint4> texhdr;
+    TexTab textab{};
+    uint32_t ntex = 0;
+    bool has_tex = false;
     std::vector<rtmi_triangle_t> htris;  // the records (host copy): the fast-mode BVH is rebuilt from them when corners arrive
     DevBuf<uint4> fnodes, oblocks, ocull;  // (fnodes: the node records, then the node cull records)
     DevBuf<uint32_t> wlinks, cert;
@@ -1950,7 +2014,7 @@ int rtmi_scene_destroy(rtmi_scene_t* s) {
     if (!s) return RTMI_OK;
     (void)hipSetDevice(s->device);
     s->nodes.release(); s->refs.release(); s->tplane.release(); s->tedge.release(); s->mats.release();
-    s->fnodes.release(); s->oblocks.release(); s->ocull.release(); s->cert.release(); s->wlinks.release(); s->bnodes.release(); s->bleaves.release(); s->spheres.release(); s->env.release(); s->smooth.release();
+    s->fnodes.release(); s->oblocks.release(); s->ocull.release(); s->cert.release(); s->wlinks.release(); s->bnodes.release(); s->bleaves.release(); s->spheres.release(); s->env.release(); s->smooth.release(); s->textri.release(); s->texels.release(); s->texhdr.release();
     for (int k = 0; k < RTMI_MAX_STREAMS; k++) {
         s->w[k].release();
         if (s->istream[k]) (void)hipStreamDestroy(s->istream[k]);
@@ -2258,6 +2322,147 @@ int rtmi_smooth_normals(const float* corners9, const float* facenorm3, uint64_t 
     RTMI_GUARD_END
 }
 
+// the tables are in place (or gone): what the k_shade*_tex / k_features_tex kernels get of them
+static void tex_set(rtmi_scene_t* s, uint32_t n, uint32_t ntex) {
+    s->textab.tri = n ? s->textri.p : nullptr;
+    s->textab.hdr = n ? s->texhdr.p : nullptr;
+    s->textab.texels = n ? s->texels.p : nullptr;
+    s->textab.n = n;
+    s->ntex = n ? ntex : 0u;
+    s->has_tex = n != 0u;
+}
+
+int rtmi_scene_set_textures(rtmi_scene_t* s, const rtmi_texture_t* tex, uint32_t ntex, const float* corners9, const float* uvs6,
+                            const uint32_t* tex_of_tri, uint64_t n) {
+    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
+    const bool set = tex && ntex;
+    uint64_t total = 0;
+    if (set) {
+        if (!corners9 || !uvs6 || !tex_of_tri) return fail(RTMI_ERR_INVALID, "textures: corners, uvs or tex_of_tri is NULL");
+        if (n != s->d.ntris) return fail(RTMI_ERR_INVALID, "textures: n must equal ntris");
+        if (ntex > 256u) return fail(RTMI_ERR_INVALID, "textures: more than 256 textures");
+        for (uint32_t k = 0; k < ntex; k++) {
+            const std::string name = "textures: texture " + std::to_string(k + 1);
+            if (tex[k].flags != 0u) return fail(RTMI_ERR_INVALID, name + " has flags != 0");
+            if (!tex[k].rgb) return fail(RTMI_ERR_INVALID, name + " has no texels (rgb is NULL)");
+            if (tex[k].width < 1u || tex[k].width > 8192u || tex[k].height < 1u || tex[k].height > 8192u)
+                return fail(RTMI_ERR_INVALID, name + ": width and height must be 1 to 8192");
+            total += (uint64_t)tex[k].width * tex[k].height;
+            if (total > (1ull << 26)) return fail(RTMI_ERR_INVALID, name + ": more than 2^26 texels in all");
+        }
+        for (uint64_t g = 1; g < n; g++) {  // (entry 0 is the sentinel's and is ignored)
+            if (tex_of_tri[g] > ntex)
+                return fail(RTMI_ERR_INVALID, "textures: tex_of_tri of triangle " + std::to_string(g) + " is above ntex");
+            if (tex_of_tri[g] == 0u) continue;
+            for (int k = 0; k < 9; k++)
+                if (!std::isfinite(corners9[9 * g + k])) return fail(RTMI_ERR_INVALID, "textures: a corner of triangle " + std::to_string(g) + " is not finite");
+            for (int k = 0; k < 6; k++)
+                if (!std::isfinite(uvs6[6 * g + k])) return fail(RTMI_ERR_INVALID, "textures: a uv of triangle " + std::to_string(g) + " is not finite");
+        }
+    }
+    RTMI_GUARD_BEGIN
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipDeviceSynchronize());  // no render of this scene is in flight: its streams are done with the old tables
+    if (!set) {
+        tex_set(s, 0u, 0u);
+        s->textri.release(); s->texhdr.release(); s->texels.release();
+        return RTMI_OK;
+    }
+    // the per-triangle part of the definition, by the statements of rtmi_scene_set_normals: f32, every step rounded
+    std::vector<float4> tab((size_t)n * 5, make_float4(0.f, 0.f, 0.f, 0.f));
+    for (uint64_t g = 1; g < n; g++) {
+        const float *c = corners9 + 9 * g, *uv = uvs6 + 6 * g;
+        const V4 c0 = mk(c[0], c[1], c[2]), e1 = vsub(mk(c[3], c[4], c[5]), c0), e2 = vsub(mk(c[6], c[7], c[8]), c0);
+        const float d00 = vdot(e1, e1), d01 = vdot(e1, e2), d11 = vdot(e2, e2), den = d00 * d11 - d01 * d01;
+        const uint32_t k = den == 0.f ? 0u : tex_of_tri[g];  // a degenerate triangle has no barycentric coordinates: no texture
+        float kf;
+        memcpy(&kf, &k, sizeof kf);
+        float4* r = &tab[(size_t)g * 5];
+        r[0] = make_float4(c0.x, c0.y, c0.z, d00);
+        r[1] = make_float4(e1.x, e1.y, e1.z, d01);
+        r[2] = make_float4(e2.x, e2.y, e2.z, d11);
+        r[3] = make_float4(uv[0], uv[2], uv[4], den);
+        r[4] = make_float4(uv[1], uv[3], uv[5], kf);
+    }
+    std::vector<uint4> hdr(ntex);
+    std::vector<float4> texels((size_t)total);
+    size_t off = 0;
+    for (uint32_t k = 0; k < ntex; k++) {
+        const size_t m = (size_t)tex[k].width * tex[k].height;
+        hdr[k] = make_uint4((uint32_t)off, tex[k].width, tex[k].height, 0u);
+        for (size_t i = 0; i < m; i++) texels[off + i] = make_float4(tex[k].rgb[3 * i], tex[k].rgb[3 * i + 1], tex[k].rgb[3 * i + 2], 0.f);
+        off += m;
+    }
+    tex_set(s, 0u, 0u);  // (a failure below leaves the scene without textures, not with stale ones)
+    HIPCHK(s->textri.ensure(tab.size()));
+    HIPCHK(s->texhdr.ensure(hdr.size()));
+    HIPCHK(s->texels.ensure(texels.size()));
+    HIPCHK(hipMemcpy(s->textri.p, tab.data(), tab.size() * sizeof(float4), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->texhdr.p, hdr.data(), hdr.size() * sizeof(uint4), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->texels.p, texels.data(), texels.size() * sizeof(float4), hipMemcpyHostToDevice));
+    tex_set(s, (uint32_t)n, ntex);
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+int rtmi_scene_get_uvs(rtmi_scene_t* s, float* uvs6_out, uint32_t* tex_of_tri_out, uint64_t* n_out) {
+    if (!s || !n_out) return fail(RTMI_ERR_INVALID, "NULL argument");
+    *n_out = s->has_tex ? s->textab.n : 0u;
+    if (!s->has_tex || (!uvs6_out && !tex_of_tri_out)) return RTMI_OK;
+    RTMI_GUARD_BEGIN
+    const size_t n = s->textab.n;
+    std::vector<float4> tab(n * 5);
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(tab.data(), s->textri.p, tab.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t g = 0; g < n; g++) {
+        const float4 qu = tab[g * 5 + 3], qv = tab[g * 5 + 4];
+        if (uvs6_out) {
+            float* o = uvs6_out + 6 * g;
+            o[0] = qu.x; o[1] = qv.x; o[2] = qu.y; o[3] = qv.y; o[4] = qu.z; o[5] = qv.z;
+        }
+        if (tex_of_tri_out) memcpy(&tex_of_tri_out[g], &qv.w, sizeof(uint32_t));
+    }
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+int rtmi_scene_get_texture(rtmi_scene_t* s, uint32_t k, float* rgb_out, uint32_t* w_out, uint32_t* h_out) {
+    if (!s || !w_out || !h_out) return fail(RTMI_ERR_INVALID, "NULL argument");
+    if (!s->has_tex || k < 1u || k > s->ntex) return fail(RTMI_ERR_INVALID, "get_texture: k must be 1 to the number of textures");
+    RTMI_GUARD_BEGIN
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipDeviceSynchronize());
+    uint4 h;
+    HIPCHK(hipMemcpy(&h, s->texhdr.p + (k - 1u), sizeof h, hipMemcpyDeviceToHost));
+    *w_out = h.y;
+    *h_out = h.z;
+    if (!rgb_out) return RTMI_OK;
+    std::vector<float4> t((size_t)h.y * h.z);
+    HIPCHK(hipMemcpy(t.data(), s->texels.p + h.x, t.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < t.size(); i++) { rgb_out[3 * i] = t[i].x; rgb_out[3 * i + 1] = t[i].y; rgb_out[3 * i + 2] = t[i].z; }
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+// rtmi_project_uvs (include/rtmi.h): host code, no HIP call, no sentinel.  A box projection: the axis of the largest |facenorm|
+// component is dropped and the other two, in cyclic order, become (u, v).
+int rtmi_project_uvs(const float* corners9, const float* facenorm3, uint64_t n, const float lo[3], float scale, float* uvs6_out) {
+    if (n == 0) return RTMI_OK;
+    if (!corners9 || !facenorm3 || !lo || !uvs6_out) return fail(RTMI_ERR_INVALID, "NULL argument");
+    for (uint64_t g = 0; g < n; g++) {
+        const float ax = fabsf(facenorm3[3 * g]), ay = fabsf(facenorm3[3 * g + 1]), az = fabsf(facenorm3[3 * g + 2]);
+        const int a = ax >= ay && ax >= az ? 0 : (ay >= az ? 1 : 2);
+        const int j = (a + 1) % 3, k = (a + 2) % 3;
+        for (int p = 0; p < 3; p++) {
+            const float* c = corners9 + 9 * g + 3 * p;
+            uvs6_out[6 * g + 2 * p] = (c[j] - lo[j]) * scale;
+            uvs6_out[6 * g + 2 * p + 1] = (c[k] - lo[k]) * scale;
+        }
+    }
+    return RTMI_OK;
+}
+
 int rtmi_scene_set_corners(rtmi_scene_t* s, const float* corners9, uint64_t n) {
     if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
     if (!corners9) return fail(RTMI_ERR_INVALID, "corners is NULL");
@@ -2323,6 +2528,13 @@ static int ensure_workspace(Work& w, size_t cap, uint32_t maxdepth) {
     }
     w.cap = cap;
     w.cap_depth = maxdepth;
+    return RTMI_OK;
+}
+// The colour stack of a call on a textured scene: one float4 beside every mstack entry of the workspace ensure_workspace has sized.
+// Every other call leaves it unallocated.
+static int ensure_cstack(const rtmi_scene* s, Work& w) {
+    if (!s->has_tex) return RTMI_OK;
+    HIPCHK(w.cstack.ensure(w.cap * (size_t)w.cap_depth));
     return RTMI_OK;
 }
 
@@ -2564,7 +2776,10 @@ static int check_view(const rtmi_viewport_t* vp, const rtmi_tile_t* tile) {
 static void launch_features(rtmi_scene* s, dim3 grid, dim3 block, hipStream_t st, uint32_t npixels, uint32_t nsamples, const uint32_t* hit_tf,
                             const float* hit_t, float* albedo, float* normal, uint32_t* ids, uint32_t pix0, uint32_t W, uint32_t nsub, uint32_t sub,
                             const float4* qo, const float4* qd) {
-    if (s->has_normals)
+    if (s->has_tex)
+        hipLaunchKernelGGL(k_features_tex, grid, block, 0, st, s->d, npixels, nsamples, hit_tf, hit_t, albedo, normal, ids, pix0, W, nsub, sub,
+                           make_fastdiv(W), make_fastdiv(nsamples), qo, qd, s->smoothtab, s->textab);
+    else if (s->has_normals)
         hipLaunchKernelGGL(k_features_smooth, grid, block, 0, st, s->d, npixels, nsamples, hit_tf, hit_t, albedo, normal, ids, pix0, W, nsub, sub,
                            make_fastdiv(W), make_fastdiv(nsamples), qo, qd, s->smoothtab);
     else
@@ -2583,7 +2798,7 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
     // shades the primary rays in one kernel.  Everything else (pipeline 1, linear list, generic tree, BVH mode,
     // analytic spheres) starts with k_gen.  Both then run one closest-hit + one shading launch per bounce pass.
     c.path_kernels = !c.fo && !c.ao && !c.li && !c.pv && !c.sh && !c.cam && s->tune.pipeline != 1u && s->octree && !s->root_is_leaf &&
-                     !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) && s->d.nspheres == 0 && !s->has_dielectric && !s->has_env && !s->has_normals;
+                     !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) && s->d.nspheres == 0 && !s->has_dielectric && !s->has_env && !s->has_normals && !s->has_tex;
     // streams = 0 (automatic): one stream for path-kernel tiles of 2^26 paths and more, three otherwise (the per-pass
     // pipelines -- BVH mode: 29.6 ms on three streams, 35.2 on one -- have elementwise kernels to hide).  Since k_shade stopped being
     // atomic-bound (round 3) there is little left for a second stream to hide: the full config-3 frame takes 366.9 ms on one
@@ -2648,6 +2863,8 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
         // (a direct-light call likewise: its candidates bound its live rays)
         const size_t nao = c.ao ? paths * c.ao->p.rays : c.li ? paths * c.li->p.rays : c.pv ? paths * c.pv->per_path : 0;
         int rc = ensure_workspace(s->w[t], nao && !occluded_anyhit(s) ? nao : paths, c.maxdepth);
+        if (rc != RTMI_OK) return rc;
+        rc = ensure_cstack(s, s->w[t]);
         if (rc != RTMI_OK) return rc;
         if (c.ao) {
             rtmi_scene::AoBuf& a = s->ao[t];
@@ -2860,7 +3077,21 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
         // a scene with an environment (never with c.path_kernels either): the _env kernels, which also know glass
         // a scene with vertex normals (never with c.path_kernels either): the _smooth kernels, which know glass and the environment
         // (s->envtab.n = 0 without one)
-        if (s->has_normals && list)
+        // a scene with textures (never with c.path_kernels either): the _tex kernels, which know all of the above (s->smoothtab.n = 0
+        // without normals) and fold over the colour stack
+        if (s->has_tex && list)
+            hipLaunchKernelGGL(k_shade_list_tex, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
+                               w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, list, s->envtab,
+                               s->smoothtab, s->textab, w.cstack.p);
+        else if (s->has_tex && c.mode == Samp::VIEWS)
+            hipLaunchKernelGGL(k_shade_views_tex, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
+                               w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, c.vt, s->envtab,
+                               s->smoothtab, s->textab, w.cstack.p);
+        else if (s->has_tex)
+            hipLaunchKernelGGL(c.mode == Samp::PASS ? k_shade_samples_tex : k_shade_tex, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths,
+                               (int)pass, w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p,
+                               w.mstack.p, w.scol.p, w.ctrl.p, sq, s->envtab, s->smoothtab, s->textab, w.cstack.p);
+        else if (s->has_normals && list)
             hipLaunchKernelGGL(k_shade_list_smooth, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
                                w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, list, s->envtab,
                                s->smoothtab);
@@ -3456,6 +3687,8 @@ static int refuse_scene_shadowed(const rtmi_scene_t* s) {
         return fail(RTMI_ERR_UNSUPPORTED, "shadowed: the scene has an environment (the shadowed shading has no environment arm)");
     if (s->has_normals)
         return fail(RTMI_ERR_UNSUPPORTED, "shadowed: the scene has vertex normals (the shadowed shading has no smooth arm)");
+    if (s->has_tex)
+        return fail(RTMI_ERR_UNSUPPORTED, "shadowed: the scene has textures (the shadowed shading has no texture arm)");
     return RTMI_OK;
 }
 
@@ -3617,6 +3850,8 @@ int rtmi_render_preview_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint6
     if (rc != RTMI_OK || empty) return rc;
     if (s->d.nspheres)
         return fail(RTMI_ERR_UNSUPPORTED, "preview: the scene has analytic spheres (a build-defined primitive whose normal needs the hit point)");
+    if (s->has_tex)
+        return fail(RTMI_ERR_UNSUPPORTED, "preview: the scene has textures (the preview's composition has no texture arm)");
     const PreviewCall call = preview_call(*preview, *out_device, (uint64_t)tile->nrows * vp->width);
     return render_tile(s, &v1, seed, tile, sample0, nsamples, nullptr, nullptr, hip_stream, stats, nullptr, 0, nullptr, nullptr, nullptr, &call);
 }
@@ -3632,6 +3867,8 @@ int rtmi_render_preview(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t see
     if (rc0 != RTMI_OK || empty) return rc0;
     if (s->d.nspheres)
         return fail(RTMI_ERR_UNSUPPORTED, "preview: the scene has analytic spheres (a build-defined primitive whose normal needs the hit point)");
+    if (s->has_tex)
+        return fail(RTMI_ERR_UNSUPPORTED, "preview: the scene has textures (the preview's composition has no texture arm)");
     const uint64_t npix = (uint64_t)nrows * vp->width;
     const uint32_t nl = preview->nlights;
     HIPCHK(hipSetDevice(s->device));
@@ -4279,6 +4516,7 @@ static int render_rays(rtmi_scene_t* s, uint64_t n, const void* orig4, const voi
     const uint64_t B = std::min<uint64_t>(std::max<uint64_t>(s->tune.batch_paths / G * G, G), n), gB = B / G;
     if (shade || guides) {
         rc = ensure_workspace(w, (size_t)B, std::max(maxdepth, 1u));
+        if (rc == RTMI_OK) rc = ensure_cstack(s, w);
         if (rc != RTMI_OK) return rc;
     }
     if (host) {
@@ -4339,7 +4577,11 @@ static int render_rays(rtmi_scene_t* s, uint64_t n, const void* orig4, const voi
             HIPCHK(hipGetLastError());
             if (pass == 0 && guides)  // before pass 1 rewrites the hit records
                 launch_features(s, ew_grid, ew_block, st, ng, G, w.hit_tf.p, w.hit_t.p, (float*)albedo, (float*)normal, ids, 0u, ng, 1u, 0u, pqo, pqd);
-            if (shade && s->has_normals)
+            if (shade && s->has_tex)
+                hipLaunchKernelGGL(k_shade_rays_tex, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(rp->pixel0 + gbase), nb, (int)pass, pqo, pqd,
+                                   w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, scol, w.ctrl.p,
+                                   SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, kq, s->envtab, s->smoothtab, s->textab, w.cstack.p);
+            else if (shade && s->has_normals)
                 hipLaunchKernelGGL(k_shade_rays_smooth, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(rp->pixel0 + gbase), nb, (int)pass, pqo, pqd,
                                    w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, scol, w.ctrl.p,
                                    SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, kq, s->envtab, s->smoothtab);
@@ -4468,6 +4710,7 @@ static int bake(rtmi_scene_t* s, uint64_t M, const void* pos4, const void* nrm4,
     const uint64_t B = std::min<uint64_t>(std::max<uint64_t>(s->tune.batch_paths / K * K, K), n), mB = B / K;
     if (traced || want_rays) {
         rc = ensure_workspace(w, (size_t)B, std::max(maxdepth, 1u));
+        if (rc == RTMI_OK) rc = ensure_cstack(s, w);
         if (rc != RTMI_OK) return rc;
     }
     if (host) {
@@ -4529,7 +4772,11 @@ static int bake(rtmi_scene_t* s, uint64_t M, const void* pos4, const void* nrm4,
             if (pass == 0 && open)  // before pass 1 rewrites the hit records
                 hipLaunchKernelGGL(k_bake_open, dim3(std::min<unsigned>((unsigned)(s->num_cu * 8), (mb + RTMI_BAKE_OPEN_ELEMS - 1u) / RTMI_BAKE_OPEN_ELEMS)),
                                    ew_block, 0, st, mb, K, w.hit_tf.p, open);
-            if (shade && s->has_normals)
+            if (shade && s->has_tex)
+                hipLaunchKernelGGL(k_shade_rays_tex, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(bp->pixel0 + mbase), nb, (int)pass, pqo, pqd,
+                                   w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p,
+                                   SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, (const uint32_t*)nullptr, s->envtab, s->smoothtab, s->textab, w.cstack.p);
+            else if (shade && s->has_normals)
                 hipLaunchKernelGGL(k_shade_rays_smooth, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(bp->pixel0 + mbase), nb, (int)pass, pqo, pqd,
                                    w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p,
                                    SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, (const uint32_t*)nullptr, s->envtab, s->smoothtab);

@@ -274,6 +274,47 @@ __device__ inline RayV bounce_ray(uint32_t kind, float m1x, uint32_t face, V4 po
     return make_ray(vadd(point, vmul(reflect_dir, 0.001f)), dir);
 }
 
+// The textures of a scene (rtmi_scene_set_textures, include/rtmi.h "TEXTURES OF A SCENE").  tri: five float4 per
+// triangle, (c0, d00) (e1, d01) (e2, d11) (u0, u1, u2, den) (v0, v1, v2, bits of tex_of_tri) -- SmoothTab's barycentric data, the
+// corner uvs and the texture number (0: none) -- entry 0 the sentinel's, n = ntris.  hdr: per image k = 1..ntex at hdr[k - 1],
+// (offset into texels, width, height, 0).  texels: all images in one buffer, one float4 per texel (lane 3 +0), texel (i, j) of an
+// image at offset + j * width + i.  An argument of the k_shade*_tex and k_features_tex kernels only, as EnvTab and SmoothTab are
+// of theirs: DScene, and with it every other kernel's argument block, stays as it is.
+struct TexTab { const float4* __restrict__ tri; const uint4* __restrict__ hdr; const float4* __restrict__ texels; uint32_t n; };
+// one wrap step of the repeat: i in [-1, N]
+__device__ inline uint32_t tex_wrap(int i, int N) { return (uint32_t)(i < 0 ? i + N : (i >= N ? i - N : i)); }
+// The colour of a hit at `point` of triangle `tri` (< tx.n) whose material colour is m0, operation by operation as include/rtmi.h
+// lists it: barycentric coordinates by smooth_normal's statements, the corner uvs interpolated, the repeat, a bilinear lookup with
+// plain loads whose indices come from the clamped texel coordinates (no value reads outside the image) and whose weights come from
+// the unclamped ones (a NaN stays one), times the material's colour.  An untextured triangle gives m0's colour unmodified.  The
+// five record loads are requested together, and so are the four texel loads.
+__device__ inline V4 tex_colour(const TexTab& tx, uint32_t tri, V4 point, float4 m0) {
+    const float4* __restrict__ r = tx.tri + (size_t)tri * 5u;
+    const float4 q0 = r[0], q1 = r[1], q2 = r[2], q3 = r[3], q4 = r[4];
+    const uint32_t k = __float_as_uint(q4.w);
+    if (k == 0u) return mk(m0.x, m0.y, m0.z);
+    const uint4 h = tx.hdr[k - 1u];
+    const V4 e1 = mk(q1.x, q1.y, q1.z), e2 = mk(q2.x, q2.y, q2.z);
+    const float d00 = q0.w, d01 = q1.w, d11 = q2.w, den = q3.w;
+    const V4 w = vsub(point, mk(q0.x, q0.y, q0.z));
+    const float d20 = vdot(w, e1), d21 = vdot(w, e2);
+    const float b1 = (d11 * d20 - d01 * d21) / den, b2 = (d00 * d21 - d01 * d20) / den, b0 = (1.f - b1) - b2;
+    const float u = (q3.x * b0 + q3.y * b1) + q3.z * b2, v = (q4.x * b0 + q4.y * b1) + q4.z * b2;
+    const float fu = u - floorf(u), fv = v - floorf(v);
+    const int W = (int)h.y, H = (int)h.z;
+    const float fW = (float)h.y, fH = (float)h.z;
+    const float fx = fu * fW - 0.5f, fy = fv * fH - 0.5f;
+    const float cx = !(fx >= -1.f) ? -1.f : (fx > fW - 1.f ? fW - 1.f : fx), cy = !(fy >= -1.f) ? -1.f : (fy > fH - 1.f ? fH - 1.f : fy);
+    const int ix = (int)floorf(cx), iy = (int)floorf(cy);
+    const float tx_ = fx - floorf(fx), ty_ = fy - floorf(fy);
+    const uint32_t x0 = tex_wrap(ix, W), x1 = tex_wrap(ix + 1, W), y0 = tex_wrap(iy, H) * h.y, y1 = tex_wrap(iy + 1, H) * h.y;
+    const float4* __restrict__ img = tx.texels + h.x;
+    const float4 c00 = img[y0 + x0], c10 = img[y0 + x1], c01 = img[y1 + x0], c11 = img[y1 + x1];
+    auto v4 = [](float4 a) { return V4{a.x, a.y, a.z, a.w}; };
+    const V4 tc = mix_color(mix_color(v4(c00), v4(c10), tx_), mix_color(v4(c01), v4(c11), tx_), ty_);
+    return mk(m0.x * tc.x, m0.y * tc.y, m0.z * tc.z);
+}
+
 // color_ray + the tail of project_ray for ONE traced ray of a path.  `pass` = bounces the path has behind it (the ray's
 // remaining depth is maxdepth - pass >= 1); tf = hit triangle | face << 30 (0 = miss), t = hit time; (ro, rd) the ray.
 // Returns true when the path goes on: its surface has been pushed on the path's stack (mstack[pass][path]) and `nr` is
@@ -292,11 +333,15 @@ __device__ inline RayV bounce_ray(uint32_t kind, float m1x, uint32_t face, V4 po
 // with smooth_normal's result where it is usable, and evaluate the bounce again with the geometric normal when the ray it gives
 // leaves on the wrong side of the real surface: same rv, same u3, no new draw.  Their `env` may be an empty table (n = 0: the
 // scene has normals and no environment), and a miss then starts at the sky constant.  Without it `sm` is never read.
-template <bool GLASS = false, bool ENV = false, bool SMOOTH = false>
+// TEX: the kernels of scenes with textures (k_shade*_tex, always with GLASS, ENV and SMOOTH; their `sm` may be an empty table too)
+// give a triangle hit that is no edge face tex_colour's colour: a Solid hit ends with it, every other hit pushes it with the
+// material's alpha on the colour stack cstack[pass][path], and the fold reads the level's colour there and not in the material
+// table.  Nothing else moves.  Without it `tex` and `cstack` are never read.
+template <bool GLASS = false, bool ENV = false, bool SMOOTH = false, bool TEX = false>
 __device__ inline bool shade_hit(const DScene& sc, uint32_t maxdepth, uint64_t seed, uint32_t npaths, uint32_t path, uint32_t pixel,
                                  uint32_t sample, uint32_t pass, uint32_t tf, float t, V4 ro, V4 rd, uint16_t* __restrict__ mstack,
                                  float4* __restrict__ scol, RayV& nr, bool* mirror = nullptr, const EnvTab* env = nullptr,
-                                 const SmoothTab* sm = nullptr) {
+                                 const SmoothTab* sm = nullptr, const TexTab* tex = nullptr, float4* __restrict__ cstack = nullptr) {
     const uint32_t tri = tf & 0x3FFFFFFFu, face = tf >> 30;
     V4 c;
     uint32_t npushed = pass;
@@ -314,10 +359,16 @@ __device__ inline bool shade_hit(const DScene& sc, uint32_t maxdepth, uint64_t s
         const uint32_t mat = __float_as_uint(is_sphere ? p1.x : p1.w);
         const float4 m0 = sc.mats[2 * mat], m1 = sc.mats[2 * mat + 1];
         const uint32_t kind = __float_as_uint(m1.y);
+        V4 tcol = mk(m0.x, m0.y, m0.z);
+        if constexpr (TEX) {
+            if (!is_sphere && tri < tex->n) tcol = tex_colour(*tex, tri, vadd(vmul(rd, t), ro), m0);
+        }
         if (kind == RTMI_SOLID) {
-            c = mk(m0.x, m0.y, m0.z);
+            if constexpr (TEX) c = tcol;
+            else c = mk(m0.x, m0.y, m0.z);
         } else {
             mstack[(size_t)pass * npaths + path] = (uint16_t)mat;
+            if constexpr (TEX) cstack[(size_t)pass * npaths + path] = make_float4(tcol.x, tcol.y, tcol.z, m0.w);
             npushed = pass + 1;
             c = mk(0.f / 255.f, 0.f / 255.f, 0.f / 255.f);  // project_ray at depth 0, raytrace.rs:1261-1263
             if (maxdepth - pass - 1u != 0u) {
@@ -390,8 +441,13 @@ __device__ inline bool shade_hit(const DScene& sc, uint32_t maxdepth, uint64_t s
     }
     // inside-out evaluation of the nested mix_color calls (raytrace.rs:1233-1251)
     for (int j = (int)npushed - 1; j >= 0; j--) {
-        const uint32_t mj = mstack[(size_t)j * npaths + path];
-        const float4 mm = sc.mats[2 * mj];
+        float4 mm;
+        if constexpr (TEX) {
+            mm = cstack[(size_t)j * npaths + path];
+        } else {
+            const uint32_t mj = mstack[(size_t)j * npaths + path];
+            mm = sc.mats[2 * mj];
+        }
         c = mix_color(mk(mm.x, mm.y, mm.z), c, mm.w);
     }
     store_stream(&scol[path], make_float4(c.x, c.y, c.z, c.w));
@@ -434,6 +490,19 @@ __device__ inline HitFeat hit_features_smooth(const DScene& sc, const SmoothTab&
         bool use = false;
         const V4 ns = smooth_normal(sm, tri, face, vadd(vmul(rd, t), ro), rd, mk(f.n.x, f.n.y, f.n.z), use);
         if (use) { f.n.x = ns.x; f.n.y = ns.y; f.n.z = ns.z; }
+    }
+    return f;
+}
+
+// hit_features for a scene with textures (k_features_tex): the albedo of a triangle hit that is no edge face is tex_colour's at
+// the hit point of the primary ray (ro, rd); the normal is hit_features_smooth's (sm may be empty).  Coverage and depth are
+// hit_features'.
+__device__ inline HitFeat hit_features_tex(const DScene& sc, const SmoothTab& sm, const TexTab& tx, uint32_t tf, float t, V4 ro, V4 rd) {
+    HitFeat f = hit_features_smooth(sc, sm, tf, t, ro, rd);
+    const uint32_t tri = tf & 0x3FFFFFFFu, face = tf >> 30;
+    if (tri != 0u && !(face & 2u) && tri < tx.n) {
+        const V4 c = tex_colour(tx, tri, vadd(vmul(rd, t), ro), f.a);
+        f.a.x = c.x; f.a.y = c.y; f.a.z = c.z;
     }
     return f;
 }

@@ -194,11 +194,11 @@ int rth_caster_environment(rth_scene_t* s, float* rgb_out, uint64_t cap_floats, 
     });
 }
 // [first, first + count) clipped to the scene's triangles; count = UINT64_MAX: to the end.  The sentinel (0) is not a triangle.
-static void normals_range(const rth_scene_t* s, uint64_t first, uint64_t& count) {
+static void normals_range(const rth_scene_t* s, uint64_t first, uint64_t& count, const std::string& what = "vertex normals") {
     const uint64_t n = s->scene.tris.size();
-    if (first < 1 || first > n) throw std::runtime_error("vertex normals: first must be 1 to the number of triangles");
+    if (first < 1 || first > n) throw std::runtime_error(what + ": first must be 1 to the number of triangles");
     if (count == UINT64_MAX) count = n - first;
-    if (count > n - first) throw std::runtime_error("vertex normals: the range ends beyond the last triangle");
+    if (count > n - first) throw std::runtime_error(what + ": the range ends beyond the last triangle");
 }
 int rth_scene_set_normals(rth_scene_t* s, const float* normals9, uint64_t first, uint64_t count) {
     return guarded([&] {
@@ -249,6 +249,147 @@ int rth_caster_normals(rth_scene_t* s, float* normals9_out, uint64_t cap_floats,
         if (v.size() > cap_floats) throw std::runtime_error("rth_caster_normals: the buffer is too small");
         if (!v.empty()) memcpy(normals9_out, v.data(), v.size() * sizeof(float));
         *n_out = v.size() / 9;
+    });
+}
+// --- textures (rtmi_scene_set_textures / rtmi_project_uvs in rtmi.h, which defines them)
+static void uvs_grow(Scene& sc, uint64_t end) {
+    if (sc.uvs.size() < end * 6) sc.uvs.resize(end * 6, 0.f);
+    if (sc.tex_of_tri.size() < end) sc.tex_of_tri.resize(end, 0u);
+}
+int rth_scene_set_textures(rth_scene_t* s, const rtmi_texture_t* tex, uint32_t ntex) {
+    return guarded([&] {
+        Scene& sc = s->scene;
+        if (!tex || ntex == 0) {  // everything goes: images, uvs, texture numbers
+            sc.textures.clear(); sc.uvs.clear(); sc.tex_of_tri.clear(); sc.tex_generation++;
+            return;
+        }
+        if (ntex > 256u) throw std::runtime_error("textures: more than 256 textures");
+        uint64_t total = 0;
+        std::vector<Scene::Texture> v(ntex);
+        for (uint32_t k = 0; k < ntex; k++) {
+            const std::string name = "textures: texture " + std::to_string(k + 1);
+            if (tex[k].flags != 0u) throw std::runtime_error(name + " has flags != 0");
+            if (!tex[k].rgb) throw std::runtime_error(name + " has no texels (rgb is NULL)");
+            if (tex[k].width < 1u || tex[k].width > 8192u || tex[k].height < 1u || tex[k].height > 8192u)
+                throw std::runtime_error(name + ": width and height must be 1 to 8192");
+            total += (uint64_t)tex[k].width * tex[k].height;
+            if (total > (1ull << 26)) throw std::runtime_error(name + ": more than 2^26 texels in all");
+            v[k].width = tex[k].width; v[k].height = tex[k].height;
+            v[k].rgb.assign(tex[k].rgb, tex[k].rgb + (size_t)tex[k].width * tex[k].height * 3);
+        }
+        for (size_t i = 1; i < sc.tex_of_tri.size(); i++)
+            if (sc.tex_of_tri[i] > ntex) throw std::runtime_error("textures: tex_of_tri of triangle " + std::to_string(i) + " is above ntex");
+        sc.textures = std::move(v);
+        sc.tex_generation++;
+    });
+}
+int rth_scene_set_uvs(rth_scene_t* s, const float* uvs6, const uint32_t* tex_of_tri, uint64_t first, uint64_t count) {
+    return guarded([&] {
+        Scene& sc = s->scene;
+        if (!uvs6 || !tex_of_tri) throw std::runtime_error("textures: uvs or tex_of_tri is NULL");
+        normals_range(s, first, count, "textures");
+        for (uint64_t i = 0; i < count; i++) {
+            if (!sc.textures.empty() && tex_of_tri[i] > sc.textures.size())
+                throw std::runtime_error("textures: tex_of_tri of triangle " + std::to_string(first + i) + " is above ntex");
+            if (tex_of_tri[i] > 256u) throw std::runtime_error("textures: tex_of_tri of triangle " + std::to_string(first + i) + " is above 256");
+            if (tex_of_tri[i] == 0u) continue;
+            for (int k = 0; k < 6; k++)
+                if (!std::isfinite(uvs6[6 * i + k])) throw std::runtime_error("textures: a uv of triangle " + std::to_string(first + i) + " is not finite");
+        }
+        uvs_grow(sc, first + count);
+        std::copy(uvs6, uvs6 + count * 6, sc.uvs.begin() + first * 6);
+        std::copy(tex_of_tri, tex_of_tri + count, sc.tex_of_tri.begin() + first);
+        sc.tex_generation++;
+    });
+}
+int rth_scene_project_uvs(rth_scene_t* s, uint64_t first, uint64_t count, const float* lo3, float scale, uint32_t texture) {
+    return guarded([&] {
+        Scene& sc = s->scene;
+        normals_range(s, first, count, "textures");
+        if (texture > 256u || (!sc.textures.empty() && texture > sc.textures.size())) throw std::runtime_error("textures: texture is above ntex");
+        std::vector<float> corners(count * 9), fn(count * 3), out(count * 6);
+        for (uint64_t i = 0; i < count; i++) {
+            const Triangle& t = sc.tris[first + i];
+            for (int k = 0; k < 3; k++) memcpy(&corners[9 * i + 3 * k], t.corners[k].v, 12);
+            memcpy(&fn[3 * i], t.norm.v, 12);
+        }
+        if (rtmi_project_uvs(corners.data(), fn.data(), count, lo3, scale, out.data()) != RTMI_OK)
+            throw std::runtime_error(std::string("rtmi_project_uvs: ") + rtmi_last_error());
+        if (texture)
+            for (float x : out)
+                if (!std::isfinite(x)) throw std::runtime_error("project_uvs: a projected uv is not finite");
+        uvs_grow(sc, first + count);
+        std::copy(out.begin(), out.end(), sc.uvs.begin() + first * 6);
+        std::fill(sc.tex_of_tri.begin() + first, sc.tex_of_tri.begin() + first + count, texture);
+        sc.tex_generation++;
+    });
+}
+int rth_scene_textures_size(const rth_scene_t* s, uint32_t* ntex_out, uint64_t* n_out) {
+    *ntex_out = (uint32_t)s->scene.textures.size();
+    *n_out = s->scene.textures.empty() && s->scene.uvs.empty() ? 0u : s->scene.tris.size();
+    return 0;
+}
+int rth_scene_get_uvs(const rth_scene_t* s, float* uvs6_out, uint32_t* tex_of_tri_out, uint64_t cap_tris) {
+    return guarded([&] {
+        const Scene& sc = s->scene;
+        const size_t n = sc.tris.size();
+        if (n > cap_tris) throw std::runtime_error("rth_scene_get_uvs: the buffer is too small");
+        std::fill(uvs6_out, uvs6_out + n * 6, 0.f);
+        std::fill(tex_of_tri_out, tex_of_tri_out + n, 0u);
+        std::copy(sc.uvs.begin(), sc.uvs.begin() + std::min(n * 6, sc.uvs.size()), uvs6_out);
+        std::copy(sc.tex_of_tri.begin(), sc.tex_of_tri.begin() + std::min(n, sc.tex_of_tri.size()), tex_of_tri_out);
+    });
+}
+int rth_scene_get_texture(const rth_scene_t* s, uint32_t k, float* rgb_out, uint64_t cap_floats, uint32_t* w_out, uint32_t* h_out) {
+    return guarded([&] {
+        const Scene& sc = s->scene;
+        if (k < 1u || k > sc.textures.size()) throw std::runtime_error("rth_scene_get_texture: k must be 1 to the number of textures");
+        const Scene::Texture& t = sc.textures[k - 1];
+        *w_out = t.width; *h_out = t.height;
+        if (!rgb_out) return;
+        if (t.rgb.size() > cap_floats) throw std::runtime_error("rth_scene_get_texture: the buffer is too small");
+        std::copy(t.rgb.begin(), t.rgb.end(), rgb_out);
+    });
+}
+int rth_caster_uvs(rth_scene_t* s, float* uvs6_out, uint32_t* tex_of_tri_out, uint64_t cap_tris, uint64_t* n_out) {
+    return guarded([&] {
+        std::vector<float> uv;
+        std::vector<uint32_t> tt;
+        caster_of(s).texture_uvs(s->scene, uv, tt);
+        if (tt.size() > cap_tris) throw std::runtime_error("rth_caster_uvs: the buffer is too small");
+        if (!tt.empty()) {
+            memcpy(uvs6_out, uv.data(), uv.size() * sizeof(float));
+            memcpy(tex_of_tri_out, tt.data(), tt.size() * sizeof(uint32_t));
+        }
+        *n_out = tt.size();
+    });
+}
+int rth_caster_texture(rth_scene_t* s, uint32_t k, float* rgb_out, uint64_t cap_floats, uint32_t* w_out, uint32_t* h_out) {
+    return guarded([&] {
+        const std::vector<float> v = caster_of(s).texture_image(s->scene, k, *w_out, *h_out);
+        if (v.size() > cap_floats) throw std::runtime_error("rth_caster_texture: the buffer is too small");
+        memcpy(rgb_out, v.data(), v.size() * sizeof(float));
+    });
+}
+// rth_add_obj_mode, and the file's `vt` texture coordinates for the new triangles, which get texture number `texture`
+int rth_add_obj_uvs(rth_scene_t* s, const char* path, const float* off, float scale, const float* b9, uint32_t kind, const float* c,
+                    float alpha, float scat, float edge, uint32_t robust, uint32_t texture) {
+    return guarded([&] {
+        Scene& sc = s->scene;
+        if (texture > 256u || (!sc.textures.empty() && texture > sc.textures.size())) throw std::runtime_error("textures: texture is above ntex");
+        const uint64_t first = sc.tris.size();
+        if (first == 0) throw std::runtime_error("textures: the scene needs its sentinel triangle first");
+        std::vector<float> uv;
+        auto t = obj_parser::parse_obj(path, v3(off), scale, std::make_tuple(v3(b9), v3(b9 + 3), v3(b9 + 6)), surf(kind, c, alpha, scat), edge,
+                                       robust ? obj_parser::ObjMode::Robust : obj_parser::ObjMode::Reference, nullptr, &uv);
+        for (float x : uv)
+            if (!std::isfinite(x)) throw std::runtime_error("parse_obj: a vt texture coordinate is not finite");
+        sc.tris.insert(sc.tris.end(), t.begin(), t.end());
+        sc.touch();
+        uvs_grow(sc, first + t.size());
+        std::copy(uv.begin(), uv.end(), sc.uvs.begin() + first * 6);
+        std::fill(sc.tex_of_tri.begin() + first, sc.tex_of_tri.end(), texture);
+        sc.tex_generation++;
     });
 }
 void rth_populate_triangle_numbers(rth_scene_t* s) { populate_triangle_numbers(s->scene.tris); s->scene.touch(); }

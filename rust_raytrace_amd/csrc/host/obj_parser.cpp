@@ -69,17 +69,33 @@ size_t parse_normal_index(const std::string& tok, size_t nnormals, bool robust) 
     if (f.empty() || f.find_first_not_of("0123456789") != std::string::npos) return 0;
     return (size_t)strtoull(f.c_str(), nullptr, 10);
 }
+// uvs6: the second field of a face corner "a/b" or "a/b/c" as a 1-based index into the vt lines (Robust: "-k" counts back from the
+// ones read so far); 0 = none or invalid
+size_t parse_uv_index(const std::string& tok, size_t nuvs, bool robust) {
+    const size_t s1 = tok.find('/');
+    if (s1 == std::string::npos) return 0;
+    const size_t s2 = tok.find('/', s1 + 1);
+    const std::string f = tok.substr(s1 + 1, s2 == std::string::npos ? std::string::npos : s2 - s1 - 1);
+    if (robust && f.size() > 1 && f[0] == '-' && f.find_first_not_of("0123456789", 1) == std::string::npos) {
+        const size_t back = (size_t)strtoull(f.c_str() + 1, nullptr, 10);
+        return back >= 1 && back <= nuvs ? nuvs - back + 1 : 0;
+    }
+    if (f.empty() || f.find_first_not_of("0123456789") != std::string::npos) return 0;
+    return (size_t)strtoull(f.c_str(), nullptr, 10);
+}
 }  // namespace
 
 std::vector<Triangle> parse_obj(const std::string& path, const Vec3& offset, float scale,
                                 const std::tuple<Vec3, Vec3, Vec3>& transform, const SurfaceKind& surface,
-                                float edge_thickness, ObjMode mode, std::vector<float>* normals9) {
+                                float edge_thickness, ObjMode mode, std::vector<float>* normals9, std::vector<float>* uvs6) {
     std::ifstream f(path, std::ios::binary);
     if (!f) throw std::runtime_error("parse_obj: cannot read " + path);
     std::vector<Vec3> vertices;
     std::vector<std::vector<size_t>> faces;
     std::vector<Vec3> vnormals;                 // normals9 only
     std::vector<std::vector<size_t>> fnormals;  // normals9 only: per face, the corners' normal indices
+    std::vector<std::pair<float, float>> vuvs;  // uvs6 only
+    std::vector<std::vector<size_t>> fuvs;      // uvs6 only: per face, the corners' uv indices
     std::string line;
     while (std::getline(f, line)) {
         if (!line.empty() && line.back() == '\r') line.pop_back();
@@ -97,6 +113,15 @@ std::vector<Triangle> parse_obj(const std::string& path, const Vec3& offset, flo
                 for (const auto& tok : fields(line.substr(2))) ni.push_back(parse_normal_index(tok, vnormals.size(), mode == ObjMode::Robust));
                 fnormals.push_back(std::move(ni));
             }
+            if (uvs6) {
+                std::vector<size_t> ui;
+                for (const auto& tok : fields(line.substr(2))) ui.push_back(parse_uv_index(tok, vuvs.size(), mode == ObjMode::Robust));
+                fuvs.push_back(std::move(ui));
+            }
+        } else if (uvs6 && line.compare(0, 3, "vt ") == 0) {
+            const auto parts = fields(line.substr(3));
+            if (parts.size() < 2 || parts.size() > 3) throw std::runtime_error("parse_obj: texture coordinate line needs 2 or 3 numbers: " + line);
+            vuvs.emplace_back(parse_f32(parts[0], line), parse_f32(parts[1], line));
         } else if (normals9 && line.compare(0, 3, "vn ") == 0) {
             const auto parts = fields(line.substr(3));
             if (parts.size() != 3) throw std::runtime_error("parse_obj: normal line needs exactly 3 numbers: " + line);
@@ -118,6 +143,15 @@ std::vector<Triangle> parse_obj(const std::string& path, const Vec3& offset, flo
             normals9->insert(normals9->end(), n.v, n.v + 3);
         }
     };
+    auto push_uvs = [&](size_t fi, size_t a, size_t b, size_t c) {  // of the triangle just pushed, likewise
+        if (!uvs6) return;
+        for (size_t k : {a, b, c}) {
+            const size_t idx = fuvs[fi][k];
+            if (idx < 1 || idx > vuvs.size()) throw std::runtime_error("parse_obj: a face corner has no texture coordinate index, or one out of range");
+            uvs6->push_back(vuvs[idx - 1].first);
+            uvs6->push_back(vuvs[idx - 1].second);
+        }
+    };
     for (size_t fi = 0; fi < faces.size(); fi++) {
         const auto& face = faces[fi];
         if (face.size() < 3) throw std::runtime_error("parse_obj: face with fewer than 3 corners");
@@ -125,6 +159,7 @@ std::vector<Triangle> parse_obj(const std::string& path, const Vec3& offset, flo
             Vec3 pts[3] = {place(face[0]), place(face[1]), place(face[2])};
             objs.push_back(make_triangle(pts, surface, edge_thickness));
             push_normals(fi, 0, 1, 2);
+            push_uvs(fi, 0, 1, 2);
             continue;
         }
         for (size_t k = 1; k + 1 < face.size(); k++) {  // fan: (c0, ck, ck+1)
@@ -132,6 +167,7 @@ std::vector<Triangle> parse_obj(const std::string& path, const Vec3& offset, flo
             try { objs.push_back(make_triangle(pts, surface, edge_thickness)); }
             catch (const std::runtime_error&) { continue; }  // degenerate sliver of a polygon: skipped (the reference would panic, raytrace.rs:357)
             push_normals(fi, 0, k, k + 1);
+            push_uvs(fi, 0, k, k + 1);
         }
     }
     return objs;

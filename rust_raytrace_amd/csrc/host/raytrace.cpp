@@ -555,6 +555,61 @@ void HipRayCaster::invalidate() {
     handle_ = nullptr; key_scene_ = nullptr;
     env_applied_ = false;
     normals_applied_ = false;
+    tex_applied_ = false;
+}
+
+void HipRayCaster::apply_textures(const Scene& s) {
+    if (tex_applied_ && key_tex_generation_ == s.tex_generation) return;
+    std::vector<rtmi_scene_t*> all{handle_};
+    all.insert(all.end(), extra_.begin(), extra_.end());
+    const bool none = s.textures.empty();
+    std::vector<float> corners, uvs;
+    std::vector<uint32_t> tot;
+    std::vector<rtmi_texture_t> tex;
+    if (!none) {
+        const size_t n = s.tris.size();
+        corners.assign(n * 9, 0.f);
+        uvs.assign(n * 6, 0.f);  // triangles beyond the ones that were given uvs are untextured
+        tot.assign(n, 0u);
+        for (size_t i = 1; i < n; i++)
+            for (int k = 0; k < 3; k++)
+                for (int c = 0; c < 3; c++) corners[9 * i + 3 * k + c] = s.tris[i].corners[k].v[c];
+        std::copy(s.uvs.begin(), s.uvs.begin() + std::min(s.uvs.size(), uvs.size()), uvs.begin());
+        std::copy(s.tex_of_tri.begin(), s.tex_of_tri.begin() + std::min(s.tex_of_tri.size(), tot.size()), tot.begin());
+        for (const Scene::Texture& t : s.textures) tex.push_back(rtmi_texture_t{t.rgb.data(), t.width, t.height, 0u});
+    }
+    for (rtmi_scene_t* hh : all) {
+        if (none && !tex_applied_) continue;  // fresh handles have none
+        const int rc = none ? rtmi_scene_set_textures(hh, nullptr, 0, nullptr, nullptr, nullptr, 0)
+                            : rtmi_scene_set_textures(hh, tex.data(), (uint32_t)tex.size(), corners.data(), uvs.data(), tot.data(), s.tris.size());
+        if (rc != RTMI_OK) {
+            const std::string msg = std::string("rtmi_scene_set_textures: ") + rtmi_last_error();
+            invalidate();
+            throw std::runtime_error(msg);
+        }
+    }
+    tex_applied_ = true;
+    key_tex_generation_ = s.tex_generation;
+}
+
+void HipRayCaster::texture_uvs(const Scene& s, std::vector<float>& uvs6, std::vector<uint32_t>& tex_of_tri) {
+    rtmi_scene_t* h = resident(s);
+    uint64_t n = 0;
+    if (rtmi_scene_get_uvs(h, nullptr, nullptr, &n) != RTMI_OK) throw std::runtime_error(std::string("rtmi_scene_get_uvs: ") + rtmi_last_error());
+    uvs6.assign((size_t)n * 6, 0.f);
+    tex_of_tri.assign((size_t)n, 0u);
+    if (n && rtmi_scene_get_uvs(h, uvs6.data(), tex_of_tri.data(), &n) != RTMI_OK)
+        throw std::runtime_error(std::string("rtmi_scene_get_uvs: ") + rtmi_last_error());
+}
+
+std::vector<float> HipRayCaster::texture_image(const Scene& s, uint32_t k, uint32_t& width, uint32_t& height) {
+    rtmi_scene_t* h = resident(s);
+    if (rtmi_scene_get_texture(h, k, nullptr, &width, &height) != RTMI_OK)
+        throw std::runtime_error(std::string("rtmi_scene_get_texture: ") + rtmi_last_error());
+    std::vector<float> out((size_t)width * height * 3);
+    if (rtmi_scene_get_texture(h, k, out.data(), &width, &height) != RTMI_OK)
+        throw std::runtime_error(std::string("rtmi_scene_get_texture: ") + rtmi_last_error());
+    return out;
 }
 
 void HipRayCaster::apply_normals(const Scene& s) {
@@ -673,6 +728,7 @@ rtmi_scene_t* HipRayCaster::resident(const Scene& s) {
         key_nboxes_ == s.boxes.boxes.size() && key_nrefs_ == s.boxes.tri_refs.size()) {
         apply_environment(s);
         apply_normals(s);
+        apply_textures(s);
         apply_settings();
         return handle_;
     }
@@ -730,6 +786,7 @@ rtmi_scene_t* HipRayCaster::resident(const Scene& s) {
     key_nboxes_ = s.boxes.boxes.size(); key_nrefs_ = s.boxes.tri_refs.size();
     apply_environment(s);
     apply_normals(s);
+    apply_textures(s);
     apply_settings();
     return handle_;
 }

@@ -164,6 +164,14 @@ struct Scene {
     // like the environment: code that edits `normals` bumps normals_generation, not generation.
     std::vector<float> normals;
     uint64_t normals_generation = 0;
+    // Textures (include/rtmi.h, "TEXTURES OF A SCENE"), or none (no images).  uvs: 6 floats per triangle
+    // (u0, v0, u1, v1, u2, v2), entry i for tris[i]; tex_of_tri: 0 = none, or 1..images.  Both may be shorter than tris: triangles
+    // appended later are untextured.  Applied like the normals: code that edits them bumps tex_generation, not generation.
+    struct Texture { uint32_t width = 0, height = 0; std::vector<float> rgb; };
+    std::vector<Texture> textures;
+    std::vector<float> uvs;
+    std::vector<uint32_t> tex_of_tri;
+    uint64_t tex_generation = 0;
     // debug_en: walk_rays also records sample 0's primary ray of every pixel into `debug` (the reference's debug_ctx, which
     // walk_rays fills through a &Scene: hence mutable).  Octree scenes only; walk_rays throws before rendering otherwise.
     bool debug_en = false;
@@ -363,6 +371,10 @@ public:
     // The vertex normals of the scene's resident copy on the first device (rtmi_scene_get_normals): ntris * 9 floats, empty when
     // the scene has none.
     std::vector<float> vertex_normals(const Scene& s);
+    // The uvs and texture numbers of the scene's resident copy on the first device (rtmi_scene_get_uvs): ntris * 6 floats and
+    // ntris numbers, empty when the scene has no textures; and image k = 1.. of it (rtmi_scene_get_texture).
+    void texture_uvs(const Scene& s, std::vector<float>& uvs6, std::vector<uint32_t>& tex_of_tri);
+    std::vector<float> texture_image(const Scene& s, uint32_t k, uint32_t& width, uint32_t& height);
     uint64_t seed;
     int device;
 
@@ -378,6 +390,9 @@ private:
     uint64_t key_normals_generation_ = 0;
     bool normals_applied_ = false;             // the handles carry Scene::normals as of key_normals_generation_
     void apply_normals(const Scene& s);
+    uint64_t key_tex_generation_ = 0;
+    bool tex_applied_ = false;                 // the handles carry Scene::textures / uvs as of key_tex_generation_
+    void apply_textures(const Scene& s);
     size_t key_ntris_ = 0, key_nboxes_ = 0, key_nrefs_ = 0;
     uint32_t options_ = 0;
     rtmi_tuning_t tuning_{}, defaults_{};
@@ -398,10 +413,13 @@ namespace obj_parser {
 enum class ObjMode { Reference = 0, Robust = 1 };
 std::vector<Triangle> parse_obj(const std::string& path, const Vec3& offset, float scale,
                                 const std::tuple<Vec3, Vec3, Vec3>& transform, const SurfaceKind& surface,
-                                float edge_thickness, ObjMode mode = ObjMode::Reference, std::vector<float>* normals9 = nullptr);
+                                float edge_thickness, ObjMode mode = ObjMode::Reference, std::vector<float>* normals9 = nullptr,
+                                std::vector<float>* uvs6 = nullptr);
 // normals9 (an extension; NULL: the loader above exactly): also read the `vn` lines and the third field of every a/b/c or a//c
 // face corner, in either mode, and append 9 floats per returned triangle: each corner's normal through change_basis(transform)
 // and unit(), no scale and no offset.  A corner without a normal index, or one out of range, throws.
+// uvs6 (an extension likewise): also read the `vt` lines (their first two numbers) and the second field of every a/b or a/b/c face
+// corner, and append 6 floats per returned triangle, (u, v) per corner as the file has them.  A corner without one throws.
 }  // namespace obj_parser
 
 // raytrace.rs:1460-1478: quantisation only ((c*255.) as u8); PNG encoding stays with the caller.

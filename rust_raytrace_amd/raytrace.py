@@ -139,20 +139,35 @@ class Scene:
         pts = _f(points).reshape(-1, 9)
         _chk(_ffi.lib().rth_add_triangles_gpu(self.h, _p(pts), pts.shape[0], *surface.args(), edge_thickness, device))
 
-    def extend_parse_obj(self, path, offset, scale, transform, surface, edge_thickness, robust=False, normals=None, crease_cos=0.5):
+    def extend_parse_obj(self, path, offset, scale, transform, surface, edge_thickness, robust=False, normals=None, crease_cos=0.5,
+                         uvs=None, texture=1):
         """obj_data.extend(obj_parser::parse_obj(...)) — obj_parser.rs:47-73.  robust=True is an opt-in loader extension
         (fan-triangulated polygons, negative indices, degenerate triangles skipped); the default is the reference's loader.
         normals (an extension, include/rtmi.h "VERTEX NORMALS OF A SCENE"): None leaves the mesh flat; "file" reads the `vn` lines
         and the third field of every a/b/c or a//c face corner (each normal through the transform and unit(); a corner without a
-        normal index is an error); "smooth" generates them from the mesh's shared corner positions (smooth_normals)."""
+        normal index is an error); "smooth" generates them from the mesh's shared corner positions (smooth_normals).
+        uvs (an extension, include/rtmi.h "TEXTURES OF A SCENE"): None leaves the mesh untextured; "file" reads the `vt` lines and
+        the second field of every a/b or a/b/c face corner (a corner without one is an error); "box" projects them (project_uvs
+        with lo = (0, 0, 0), scale = 1).  The new triangles get texture number `texture`.  "file" cannot be combined with normals."""
         if normals not in (None, "file", "smooth"):
             raise ValueError(f"extend_parse_obj: normals must be None, 'file' or 'smooth', not {normals!r}")
+        if uvs not in (None, "file", "box"):
+            raise ValueError(f"extend_parse_obj: uvs must be None, 'file' or 'box', not {uvs!r}")
+        if uvs == "file":
+            if normals is not None:
+                raise ValueError("extend_parse_obj: uvs='file' cannot be combined with normals")
+            _chk(_ffi.lib().rth_add_obj_uvs(self.h, path.encode(), _p(_f(offset)), scale, _p(_f(transform)), *surface.args(),
+                                            edge_thickness, 1 if robust else 0, int(texture)))
+            return
+        first = self.num_tris()
         if normals is None:
             _chk(_ffi.lib().rth_add_obj_mode(self.h, path.encode(), _p(_f(offset)), scale, _p(_f(transform)), *surface.args(),
                                              edge_thickness, 1 if robust else 0))
         else:
             _chk(_ffi.lib().rth_add_obj_normals(self.h, path.encode(), _p(_f(offset)), scale, _p(_f(transform)), *surface.args(),
                                                 edge_thickness, 1 if robust else 0, 1 if normals == "file" else 2, float(crease_cos)))
+        if uvs == "box" and self.num_tris() > first:
+            self.project_uvs(first=first, count=self.num_tris() - first, texture=texture)
 
     def extend_make_disk(self, orig, norm, r, d, num_tris, surface, side_surface, edge_thickness):
         """obj_data.extend(make_disk(...)) — raytrace.rs:531-592"""
@@ -229,6 +244,61 @@ class Scene:
     def clear_vertex_normals(self):
         """Back to flat shading: the scene is exactly the scene it was before it had vertex normals."""
         _chk(_ffi.lib().rth_scene_set_normals(self.h, None, 0, 0))
+
+    # --- textures: a build-defined extension (include/rtmi.h, "TEXTURES OF A SCENE")
+    def set_textures(self, images, uvs, tex_of_tri, first=1, flip_v=False):
+        """The scene's images, and uvs and texture numbers of triangles first, first + 1, ...: images a list of (h, w, 3) f32
+        arrays, row 0 at v = 0 (flip_v=True: the arrays are stored top row first, as image files are); uvs (n, 3, 2) f32, corner k
+        of triangle i at [i, k]; tex_of_tri (n,) with 0 = no texture, or 1..len(images).  uvs=None sets the images alone and keeps
+        the uvs the scene has.  Kept with the scene; HipRayCaster applies them on every device it uploads to."""
+        imgs = []
+        for k, im in enumerate(images):
+            a = _f(im)
+            if a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError(f"texture {k + 1} must be (h, w, 3), not {a.shape}")
+            imgs.append(np.ascontiguousarray(a[::-1]) if flip_v else a)
+        arr = (_ffi.Texture * max(len(imgs), 1))()
+        for k, a in enumerate(imgs):
+            arr[k] = _ffi.Texture(a.ctypes.data, a.shape[1], a.shape[0], 0)
+        if uvs is not None:
+            t, tt = _f(uvs), np.ascontiguousarray(tex_of_tri, dtype=np.uint32)
+            if t.ndim != 3 or t.shape[1:] != (3, 2) or tt.shape != (t.shape[0],):
+                raise ValueError(f"uvs must be (n, 3, 2) and tex_of_tri (n,), not {t.shape} and {tt.shape}")
+            if imgs and tt.size and int(tt.max()) > len(imgs):
+                raise RuntimeError(f"textures: tex_of_tri of triangle {int(first) + int(np.argmax(tt > len(imgs)))} is above ntex")
+        if not imgs:
+            raise ValueError("set_textures: no images (clear_textures() removes them)")
+        _chk(_ffi.lib().rth_scene_set_textures(self.h, arr, len(imgs)))
+        if uvs is not None:
+            _chk(_ffi.lib().rth_scene_set_uvs(self.h, _p(t), _p(tt), int(first), t.shape[0]))
+
+    def project_uvs(self, first=1, count=None, lo=(0, 0, 0), scale=1.0, texture=1):
+        """Box-projected uvs (rtmi_project_uvs) for triangles [first, first + count) (default: all), for example one mesh, which get
+        texture number `texture`: per triangle the two coordinates other than the face normal's largest, (p - lo) * scale."""
+        _chk(_ffi.lib().rth_scene_project_uvs(self.h, int(first), 2 ** 64 - 1 if count is None else int(count), _p(_f(lo).reshape(3)),
+                                              float(scale), int(texture)))
+
+    def textures(self):
+        """The scene's textures: (images, uvs (ntris, 3, 2) f32, tex_of_tri (ntris,) u32) with entry 0 the sentinel's, or None when it
+        has neither images nor uvs"""
+        ntex, n = C.c_uint32(0), C.c_uint64(0)
+        _chk(_ffi.lib().rth_scene_textures_size(self.h, C.byref(ntex), C.byref(n)))
+        if n.value == 0:
+            return None
+        uv, tt = np.zeros((n.value, 3, 2), np.float32), np.zeros(n.value, np.uint32)
+        _chk(_ffi.lib().rth_scene_get_uvs(self.h, _p(uv), _p(tt), n.value))
+        images = []
+        for k in range(1, ntex.value + 1):
+            w, h = C.c_uint32(0), C.c_uint32(0)
+            _chk(_ffi.lib().rth_scene_get_texture(self.h, k, None, 0, C.byref(w), C.byref(h)))
+            im = np.zeros((h.value, w.value, 3), np.float32)
+            _chk(_ffi.lib().rth_scene_get_texture(self.h, k, _p(im), im.size, C.byref(w), C.byref(h)))
+            images.append(im)
+        return images, uv, tt
+
+    def clear_textures(self):
+        """Back to one colour per material: the scene is exactly the scene it was before it had textures."""
+        _chk(_ffi.lib().rth_scene_set_textures(self.h, None, 0))
 
     # --- Scene.boxes
     def build_bounding_box(self, orig, len2, maxdepth, minobjs, threads=0, gpu_device=None):
@@ -1428,6 +1498,26 @@ class HipRayCaster:
         _chk(_ffi.lib().rth_caster_normals(s.h, _p(out), out.size, C.byref(n)))
         return out
 
+    def textures(self, s):
+        """The textures as the first device holds them (rtmi_scene_get_uvs, rtmi_scene_get_texture): (images, uvs (ntris, 3, 2) f32,
+        tex_of_tri (ntris,) u32; a degenerate triangle reads as texture 0), or None when the scene has no images.  Uploads first if
+        need be."""
+        self._config(s)
+        ntex, n = C.c_uint32(0), C.c_uint64(0)
+        _chk(_ffi.lib().rth_scene_textures_size(s.h, C.byref(ntex), C.byref(n)))
+        if ntex.value == 0:
+            return None
+        uv, tt = np.zeros((n.value, 3, 2), np.float32), np.zeros(n.value, np.uint32)
+        _chk(_ffi.lib().rth_caster_uvs(s.h, _p(uv), _p(tt), n.value, C.byref(n)))
+        images = []
+        for k in range(1, ntex.value + 1):
+            w, h = C.c_uint32(0), C.c_uint32(0)
+            _chk(_ffi.lib().rth_scene_get_texture(s.h, k, None, 0, C.byref(w), C.byref(h)))
+            im = np.zeros((h.value, w.value, 3), np.float32)
+            _chk(_ffi.lib().rth_caster_texture(s.h, k, _p(im), im.size, C.byref(w), C.byref(h)))
+            images.append(im)
+        return images, uv, tt
+
     def trace(self, s, orig4, dir4):
         """Closest hit per explicit ray (rtmi_trace): -> tri, t, face, stats."""
         o4, d4 = _f(orig4).reshape(-1, 4), _f(dir4).reshape(-1, 4)
@@ -1742,12 +1832,16 @@ def quantize(rgba):
 
 
 # ---------------------------------------------------------------- scenes of the benchmark configs
-def canonical_scene(obj_path, accel="octree", maxdepth=10, minobjs=19, teapot_surface=None, threads=0, gpu_build=None, smooth=False):
-    """The scene of raytrace/src/main.rs:116-164.  smooth (an extension): the teapot gets generated vertex normals."""
+def canonical_scene(obj_path, accel="octree", maxdepth=10, minobjs=19, teapot_surface=None, threads=0, gpu_build=None, smooth=False,
+                    texture=None):
+    """The scene of raytrace/src/main.rs:116-164.  smooth (an extension): the teapot gets generated vertex normals.  texture (an
+    extension): an (h, w, 3) f32 image the teapot gets through box-projected uvs."""
     s = Scene(with_dummy=True)
     tsurf = teapot_surface or SurfaceKind.Matte(make_color(252, 119, 0), 0.2)
     s.extend_parse_obj(obj_path, [0.0, 0.5, 5.0], 1.0, create_transform(unit([0.0, 0.3, 1.0]), to_radians(270.0)), tsurf, 0.05,
-                       normals="smooth" if smooth else None)
+                       normals="smooth" if smooth else None, uvs=None if texture is None else "box")
+    if texture is not None:
+        s.set_textures([texture], None, None)
     side = SurfaceKind.Matte(make_color(40, 40, 40), 0.2)
     s.extend_make_disk([4.0, 4.0, 7.0], unit([-0.3, -0.55, -0.5]), 2.0, 0.1, 50,
                        SurfaceKind.Reflective(0.0002, make_color(230, 230, 230), 0.7), side, -1.0)
