@@ -317,8 +317,8 @@ int rtmi_scene_set_sky(rtmi_scene_t* scene, uint32_t n, const rtmi_sky_t* sky /*
  * and options: every call that gains glass gains this.  rtmi_bake*'s generator takes the caller's normal as before; its traced
  * paths bounce smoothly.  Unchanged: rtmi_trace*, rtmi_occluded*, the records, rtmi_render_ao*, _light* and the AO and light of
  * _preview*, which use the geometric normal.  rtmi_render_shadowed* returns RTMI_ERR_UNSUPPORTED, before any HIP call.
- * Not here: vertex normals in AO, light and preview shading; in the path kernels (pipeline 3); under rtmi_render_shadowed*; normal
- * maps; a softened shadow terminator. */
+ * Not here: vertex normals in AO, light and preview shading; in the path kernels (pipeline 3); under rtmi_render_shadowed*; a
+ * softened shadow terminator.  (Normal maps: the section after the textures'.) */
 int rtmi_scene_set_normals(rtmi_scene_t* scene, const float* corners9, const float* normals9 /* or NULL */, uint64_t n);
 int rtmi_scene_get_normals(rtmi_scene_t* scene, float* normals9_out /* n * 9, or NULL */, uint64_t* n_out);
 int rtmi_smooth_normals(const float* corners9, const float* facenorm3, uint64_t n, float crease_cos, float* normals9_out);
@@ -373,8 +373,10 @@ int rtmi_smooth_normals(const float* corners9, const float* facenorm3, uint64_t 
  * also know RTMI_DIELECTRIC, the environment and vertex normals) and k_features_tex, whatever the scene kind and options: every call
  * that gains vertex normals gains this.  Unchanged: rtmi_trace*, rtmi_occluded*, the records, rtmi_render_ao*, _light*.
  * rtmi_render_shadowed* and rtmi_render_preview* return RTMI_ERR_UNSUPPORTED, before any HIP call.
- * Not here: mip maps and any minification filter, clamp or mirror wrap modes, textures on analytic spheres, normal, roughness and
- * alpha maps, sRGB decoding and image file loading, textures in the path kernels (pipeline 3), under the preview and the shadowed
+ * rtmi_scene_set_textures (set, replace or remove) also removes the scene's normal maps (the next section): the image numbers they
+ * name are gone.  A scene without maps behaves as it always did.
+ * Not here: mip maps and any minification filter, clamp or mirror wrap modes, textures on analytic spheres, roughness and alpha
+ * maps, sRGB decoding and image file loading, textures in the path kernels (pipeline 3), under the preview and the shadowed
  * call. */
 typedef struct rtmi_texture { const float* rgb; uint32_t width, height, flags /* 0 */; } rtmi_texture_t;
 int rtmi_scene_set_textures(rtmi_scene_t* scene, const rtmi_texture_t* tex /* or NULL */, uint32_t ntex, const float* corners9,
@@ -382,6 +384,72 @@ int rtmi_scene_set_textures(rtmi_scene_t* scene, const rtmi_texture_t* tex /* or
 int rtmi_scene_get_uvs(rtmi_scene_t* scene, float* uvs6_out /* n * 6, or NULL */, uint32_t* tex_of_tri_out /* n, or NULL */, uint64_t* n_out);
 int rtmi_scene_get_texture(rtmi_scene_t* scene, uint32_t k, float* rgb_out /* or NULL */, uint32_t* w_out, uint32_t* h_out);
 int rtmi_project_uvs(const float* corners9, const float* facenorm3, uint64_t n, const float lo[3], float scale, float* uvs6_out);
+
+/* NORMAL MAPS OF A SCENE: tangent-space normals looked up at every bouncing hit.  NOT part of the reference, which
+ * has nothing of the kind, so this build defines it, operation by operation like its neighbours.  All arithmetic is f32: + - * /,
+ * sqrt, floorf and comparisons only, plain loads, no contraction, every step rounded, lane 3 of every vector +0.  vdot, vunit,
+ * vadd, vsub, vmul are the reference's; cross(a, b) is written out component by component as in rtmi_smooth_normals:
+ * (a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x, +0).
+ *
+ * A normal map is one of the images rtmi_scene_set_textures stored; its texel rgb encodes a tangent-space vector as 2 * rgb - 1.
+ * A triangle names its map by nmap_of_tri (0 = none, 1..ntex), independent of tex_of_tri: a triangle may have a map and no colour
+ * texture, and its colour is then the material's, bit for bit.  The uvs are the ones rtmi_scene_set_textures stored.
+ * Per triangle, once, on the host, when the maps are set; e1, e2, den by the texture section's statements from corners9, (u0, v0),
+ * (u1, v1), (u2, v2) the stored uvs, ngeom the record's (front) normal:
+ *     du1 = u1 - u0;  du2 = u2 - u0;  dv1 = v1 - v0;  dv2 = v2 - v0
+ *     det = du1 * dv2 - du2 * dv1
+ *     T = vsub(vmul(e1, dv2), vmul(e2, dv1));  B = vsub(vmul(e2, du1), vmul(e1, du2));  if (det < 0.f) both vmul(., -1.f)
+ *     hand = vdot(cross(ngeom, T), B) >= 0.f ? 1.f : -1.f
+ * A triangle with det == 0.f or den == 0.f is stored with map 0.  T is stored as computed (not normalised); B is used for hand only.
+ *
+ * At a hit that bounces (a triangle, not an analytic sphere, not an edge face, not Solid, remaining depth not exhausted) of a
+ * triangle with a map: N is the vertex-normal section's `norm` (ns or ng, already on the hit side; ng without vertex normals),
+ * (u, v) the texture section's, M that section's bilinear lookup (tc) of image nmap_of_tri at (u, v):
+ *     x = (M.x * 2.f - 1.f) * strength;  y = (M.y * 2.f - 1.f) * strength;  z = M.z * 2.f - 1.f
+ *     t = vunit(vsub(T, vmul(N, vdot(N, T))))
+ *     b = vmul(cross(N, t), (face & 1) ? -hand : hand)          (t and b are the same world vectors seen from either face)
+ *     nm = vunit(vadd(vadd(vmul(t, x), vmul(b, y)), vmul(N, z)))
+ *     usem = vdot(nm, ng) > 0.f && vdot(rd, nm) < 0.f
+ *     norm = usem ? nm : N
+ * There are no clamps and no special cases.  A texel of (0.5, 0.5, 0.5), or T parallel to N, gives vunit(0) = NaN; usem is then
+ * false and the hit is shaded exactly as without the map.  A mapped normal that faces away from the ray or from the side that was
+ * hit falls back to N.  The wrong-side rule of the vertex-normal section is unchanged with (use || usem) where it says use: if the
+ * bounce evaluated with `norm` leaves on the wrong side of ng, the whole bounce is evaluated again with ng, the same rv, the same
+ * u, no new draw.  No RNG draw moves; the fold, the surface and colour stacks, black at edge faces and at exhausted depth are
+ * untouched.  A triangle with map 0 is shaded bit for bit as before.  NOT promised: that a flat map (texel (0.5, 0.5, 1)) is
+ * bit-identical to no map -- vunit(N) need not return N's bits.
+ * Guides: the normal of rtmi_render_features*, and of the guides of rtmi_render_camera* and rtmi_render_rays*, is `norm` as above,
+ * from the primary ray, whatever the surface kind.  Albedo, coverage, depth and ids do not change.
+ *
+ * rtmi_scene_set_normal_maps: n must equal ntris, entry 0 the sentinel's; corners9 as in rtmi_scene_set_normals; opt == NULL: the
+ * defaults (strength 1.f, flags 0).  nmap_of_tri == NULL or n == 0 removes the maps, and the scene is exactly what it was.
+ * RTMI_ERR_INVALID before any HIP call, naming the first offender: the scene has no textures, flags != 0, a strength that is not
+ * finite, an entry above ntex, a corner of a mapped triangle that is not finite.  Setting, replacing or removing waits for the
+ * scene's work first.  rtmi_scene_set_textures (set, replace or remove) removes the maps.  rtmi_scene_get_normal_maps copies the
+ * device table's numbers back (*n_out = 0: no maps; a degenerate triangle reads as map 0).
+ * rtmi_normal_map_frames (host code, no device needed; no sentinel: all n triangles count) is the per-triangle part alone, which
+ * rtmi_scene_set_normal_maps applies: frames4_out gets (T.x, T.y, T.z, bits) per triangle, bits 0-30 the stored map number and
+ * bit 31 set when hand = -1.f; all zero for a triangle stored with map 0.  facenorm3: the records' normals.
+ * rtmi_normal_map_from_height (host code, no device needed) makes a map from a height field h(i, j) = height[j * w + i] with
+ * repeat-wrapped central differences:
+ *     dx = ((h(i + 1, j) - h(i - 1, j)) * 0.5f) * scale;  dy = ((h(i, j + 1) - h(i, j - 1)) * 0.5f) * scale
+ *     n = vunit((-dx, -dy, 1.f));  rgb = (n.x * 0.5f + 0.5f, n.y * 0.5f + 0.5f, n.z * 0.5f + 0.5f)
+ * A null pointer with w * h > 0 is refused; a size of 0 succeeds.
+ *
+ * A scene with normal maps renders on the per-pass pipeline with the k_shade*_nmap kernels (which know everything the _tex kernels
+ * do) and k_features_nmap: every call that gains textures gains this.  Unchanged: rtmi_trace*, rtmi_occluded*, the records,
+ * rtmi_render_ao*, _light*, which use the geometric normal; rtmi_bake*'s generator takes the caller's normal as before and its
+ * traced paths bounce about mapped normals; rtmi_render_shadowed* and rtmi_render_preview* refuse a textured scene as before.
+ * Not here: roughness and alpha maps, object-space normal maps, per-vertex tangents from a file, mip maps, normal maps on spheres,
+ * in AO, light, preview and shadowed shading, in the path kernels (pipeline 3), a softened shadow terminator. */
+typedef struct rtmi_normal_maps { float strength; /* 1.f */ uint32_t flags; /* 0 */ } rtmi_normal_maps_t;
+void rtmi_normal_maps_defaults(rtmi_normal_maps_t* opt);
+int rtmi_scene_set_normal_maps(rtmi_scene_t* scene, const float* corners9, const uint32_t* nmap_of_tri /* n, or NULL */, uint64_t n,
+                               const rtmi_normal_maps_t* opt /* or NULL */);
+int rtmi_scene_get_normal_maps(rtmi_scene_t* scene, uint32_t* nmap_of_tri_out /* or NULL */, float* strength_out /* or NULL */, uint64_t* n_out);
+int rtmi_normal_map_frames(const float* corners9, const float* uvs6, const float* facenorm3, const uint32_t* nmap_of_tri, uint64_t n,
+                           float* frames4_out);
+int rtmi_normal_map_from_height(const float* height, uint32_t w, uint32_t h, float scale, float* rgb_out);
 
 /* Optional: the corners the triangle records were made from (`Triangle.corners`, raytrace.rs:326-337), 9 floats per
  * triangle, n = ntris (entry 0 = the sentinel's, ignored).  Only RTMI_OPT_BVH uses them: its boxes become the triangles'

@@ -101,6 +101,22 @@ int rth_caster_uvs(rth_scene_t* s, float* uvs6_out, uint32_t* tex_of_tri_out, ui
 int rth_caster_texture(rth_scene_t* s, uint32_t k, float* rgb_out, uint64_t cap_floats, uint32_t* w_out, uint32_t* h_out);
 int rth_add_obj_uvs(rth_scene_t* s, const char* path, const float* offset3, float scale, const float* basis9, uint32_t kind,
                     const float* color3, float alpha, float scattering, float edge_thickness, uint32_t robust, uint32_t texture);
+/* Normal maps (rtmi_scene_set_normal_maps in rtmi.h, which defines them): kept with the scene and applied, after the textures and
+ * with the triangles' own corners, to its resident copy on every device at the next call that uses one.  A map is one of the
+ * scene's texture images, so the scene needs images first, and rth_scene_set_textures (set or remove) removes the maps.
+ * rth_scene_set_normal_maps: map numbers of triangles [first, first + count), first >= 1 (count = UINT64_MAX: to the end), and
+ * the strength of all maps; nmap_of_tri == NULL or count == 0 removes the maps.  Refused: no images, flags != 0, a strength that
+ * is not finite, a number above the number of images.
+ * rth_scene_normal_maps_size: the number of triangles when the scene has maps, else 0.  rth_scene_get_normal_maps: the scene's
+ * copy.  rth_scene_normal_map_frames: rtmi_normal_map_frames over the scene (4 floats per triangle, entry 0 zeros): what a device
+ * stores.  rth_caster_normal_maps uploads if need be and reads the device's numbers back (a degenerate triangle reads as 0).
+ * rth_normal_map_from_height: rtmi_normal_map_from_height. */
+int rth_scene_set_normal_maps(rth_scene_t* s, const uint32_t* nmap_of_tri, uint64_t first, uint64_t count, float strength, uint32_t flags);
+int rth_scene_normal_maps_size(const rth_scene_t* s, uint64_t* n_out);
+int rth_scene_get_normal_maps(const rth_scene_t* s, uint32_t* nmap_of_tri_out, float* strength_out, uint64_t cap_tris);
+int rth_scene_normal_map_frames(const rth_scene_t* s, float* frames4_out, uint64_t cap_tris);
+int rth_caster_normal_maps(rth_scene_t* s, uint32_t* nmap_of_tri_out, float* strength_out, uint64_t cap_tris, uint64_t* n_out);
+int rth_normal_map_from_height(const float* height, uint32_t w, uint32_t h, float scale, float* rgb_out);
 void rth_populate_triangle_numbers(rth_scene_t* s);
 
 /* build_bounding_box / build_trivial_bounding_box into Scene.boxes */

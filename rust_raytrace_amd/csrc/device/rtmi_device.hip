@@ -600,10 +600,12 @@ namespace rtmi {
 // TEX (k_shade*_tex): shade_hit<true, true, true, true>, which colours a hit from the scene's textures and folds over the colour
 // stack; the launch sites pick them before all others, for scenes with textures, with or without glass, an
 // environment and vertex normals (a SmoothTab of n = 0 is "none")
-template <Samp S, bool GLASS = false, bool ENV = false, bool SMOOTH = false, bool TEX = false>
+// NMAP (k_shade*_nmap): shade_hit<true, true, true, true, true>, which also looks up the scene's normal maps; the
+// launch sites pick them before the _tex ones, for scenes with normal maps (which always have textures)
+template <Samp S, bool GLASS = false, bool ENV = false, bool SMOOTH = false, bool TEX = false, bool NMAP = false>
 __device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list = nullptr, const ViewTab& vt = ViewTab{},
                                            const EnvTab* env = nullptr, const SmoothTab* sm = nullptr, const TexTab* tex = nullptr,
-                                           float4* __restrict__ cstack = nullptr) {
+                                           float4* __restrict__ cstack = nullptr, const NmapTab* nm = nullptr) {
     __shared__ uint32_t s_cnt[4], s_base;
     const uint32_t count = ctrl->count[pass];
     const uint32_t stride = gridDim.x * blockDim.x;
@@ -629,14 +631,14 @@ __device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __
             if constexpr (S == Samp::RAYS) {  // `list` = the batch's RNG keys (or null), pix0 = the key of its first group
                 uint32_t pixel, sample;
                 rays_key(v, pix0, path, list, pixel, sample);
-                push = shade_hit<GLASS, ENV, SMOOTH, TEX>(sc, v.maxdepth, seed, npaths, path, pixel, sample, (uint32_t)pass, tf, t, V4{o4.x, o4.y, o4.z, o4.w},
-                                                     V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr, nullptr, env, sm, tex, cstack);
+                push = shade_hit<GLASS, ENV, SMOOTH, TEX, NMAP>(sc, v.maxdepth, seed, npaths, path, pixel, sample, (uint32_t)pass, tf, t, V4{o4.x, o4.y, o4.z, o4.w},
+                                                     V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr, nullptr, env, sm, tex, cstack, nm);
             } else {
             uint32_t prow, pcol, sample;
             path_pixel<S>(v, pix0, path, prow, pcol, sample, list);
             const PixKey key = pixel_key<S>(v, prow, vt);
-            push = shade_hit<GLASS, ENV, SMOOTH, TEX>(sc, v.maxdepth, key_seed<S>(key, vt, seed), npaths, path, key.row * v.width + pcol, sample, (uint32_t)pass, tf, t,
-                                                 V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr, nullptr, env, sm, tex, cstack);
+            push = shade_hit<GLASS, ENV, SMOOTH, TEX, NMAP>(sc, v.maxdepth, key_seed<S>(key, vt, seed), npaths, path, key.row * v.width + pcol, sample, (uint32_t)pass, tf, t,
+                                                 V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr, nullptr, env, sm, tex, cstack, nm);
             }
             // a bounce ray with an exactly-zero direction component goes to the slow path (SlowQ), not to the next pass
             if (push && slow.cap && has_zero_component(nr.dir.x, nr.dir.y, nr.dir.z) &&
@@ -699,6 +701,13 @@ __global__ void __launch_bounds__(256) k_shade_samples_tex(RTMI_SHADE_PARAMS, En
 __global__ void __launch_bounds__(256) k_shade_list_tex(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack) { shade_pass<Samp::LIST, true, true, true, true>(RTMI_SHADE_ARGS, list, ViewTab{}, &env, &sm, &tex, cstack); }
 __global__ void __launch_bounds__(256) k_shade_views_tex(RTMI_SHADE_PARAMS, ViewTab vt, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack) { shade_pass<Samp::VIEWS, true, true, true, true>(RTMI_SHADE_ARGS, nullptr, vt, &env, &sm, &tex, cstack); }
 __global__ void __launch_bounds__(256) k_shade_rays_tex(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ keys, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack) { shade_pass<Samp::RAYS, true, true, true, true>(RTMI_SHADE_ARGS, keys, ViewTab{}, &env, &sm, &tex, cstack); }
+// And for scenes with normal maps (rtmi_scene_set_normal_maps), which always have textures; with or without glass,
+// an environment and vertex normals.
+__global__ void __launch_bounds__(256) k_shade_nmap(RTMI_SHADE_PARAMS, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack, NmapTab nm) { shade_pass<Samp::FRAME, true, true, true, true, true>(RTMI_SHADE_ARGS, nullptr, ViewTab{}, &env, &sm, &tex, cstack, &nm); }
+__global__ void __launch_bounds__(256) k_shade_samples_nmap(RTMI_SHADE_PARAMS, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack, NmapTab nm) { shade_pass<Samp::PASS, true, true, true, true, true>(RTMI_SHADE_ARGS, nullptr, ViewTab{}, &env, &sm, &tex, cstack, &nm); }
+__global__ void __launch_bounds__(256) k_shade_list_nmap(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack, NmapTab nm) { shade_pass<Samp::LIST, true, true, true, true, true>(RTMI_SHADE_ARGS, list, ViewTab{}, &env, &sm, &tex, cstack, &nm); }
+__global__ void __launch_bounds__(256) k_shade_views_nmap(RTMI_SHADE_PARAMS, ViewTab vt, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack, NmapTab nm) { shade_pass<Samp::VIEWS, true, true, true, true, true>(RTMI_SHADE_ARGS, nullptr, vt, &env, &sm, &tex, cstack, &nm); }
+__global__ void __launch_bounds__(256) k_shade_rays_nmap(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ keys, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack, NmapTab nm) { shade_pass<Samp::RAYS, true, true, true, true, true>(RTMI_SHADE_ARGS, keys, ViewTab{}, &env, &sm, &tex, cstack, &nm); }
 
 // rtmi_scene_set_sky: texel (i, j) of an n x n environment table from the inverse of env_lookup's map -- the direction of the
 // texel's centre -- and a gradient sky with a sun disc, operation by operation as include/rtmi.h lists it.  One thread per texel.
@@ -942,6 +951,51 @@ __global__ void __launch_bounds__(256) k_features_tex(DScene sc, uint32_t npixel
                 float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f), d4 = make_float4(0.f, 0.f, 1.f, 0.f);
                 if ((tf & 0x3FFFFFFFu) != 0u && !((tf >> 30) & 2u)) { o4 = qo[f0 + r0 + k]; d4 = qd[f0 + r0 + k]; }
                 const HitFeat f = hit_features_tex(sc, sm, tex, tf, hit_t[f0 + r0 + k], V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w});
+                const uint32_t e = feat_slot(k, rot * fdiv(r0 + k, dS));
+                stage[2u * e] = f.a;
+                stage[2u * e + 1u] = f.n;
+            }
+            __syncthreads();
+            if (j < npb) {
+                const uint32_t lo = max(my0, r0), hi = min(my1, r0 + n);
+                for (uint32_t s = lo; s < hi; s++) acc = acc + stage_f[feat_slot(s - r0, rot * j) * 8u + l];
+            }
+        }
+        if (j < npb) {
+            const uint32_t lp = pix0 + pb + j, lr = fdiv(lp, dW), col = lp - lr * W;
+            const size_t o = ((size_t)lr * nsub + sub) * W + col;
+            float* __restrict__ dst = l < 4u ? albedo : normal;
+            if (dst) store_stream(&dst[o * 4u + (l & 3u)], acc * inv);
+            if (ids && l == 0u) store_stream(&ids[o], hit_tf[f0 + my0]);
+        }
+    }
+}
+
+// k_features for a scene with normal maps: k_features_tex statement for statement, with hit_features_nmap's
+// normal.  A kernel of its own for k_features_smooth's reason.
+__global__ void __launch_bounds__(256) k_features_nmap(DScene sc, uint32_t npixels, uint32_t nsamples, const uint32_t* __restrict__ hit_tf,
+                                                      const float* __restrict__ hit_t, float* __restrict__ albedo, float* __restrict__ normal,
+                                                      uint32_t* __restrict__ ids, uint32_t pix0, uint32_t W, uint32_t nsub, uint32_t sub,
+                                                      FastDiv dW, FastDiv dS, const float4* __restrict__ qo, const float4* __restrict__ qd,
+                                                      SmoothTab sm, TexTab tex, NmapTab nm) {
+    __shared__ float4 stage[2 * RTMI_FEAT_CHUNK];
+    const float* stage_f = reinterpret_cast<const float*>(stage);
+    const uint32_t tid = threadIdx.x, j = tid >> 3, l = tid & 7u;
+    const uint32_t rot = (nsamples & 3u) == 0u ? 1u : 0u;
+    const float inv = 1.f / (float)nsamples;
+    for (uint32_t pb = blockIdx.x * RTMI_FEAT_PIX; pb < npixels; pb += gridDim.x * RTMI_FEAT_PIX) {
+        const uint32_t npb = min((uint32_t)RTMI_FEAT_PIX, npixels - pb);
+        const uint32_t f0 = pb * nsamples, nb = npb * nsamples;  // the block's paths: hit_*[f0 .. f0 + nb)
+        const uint32_t my0 = j * nsamples, my1 = my0 + nsamples;  // this thread's pixel among them (when j < npb)
+        float acc = 0.f;
+        for (uint32_t r0 = 0; r0 < nb; r0 += RTMI_FEAT_CHUNK) {
+            const uint32_t n = min((uint32_t)RTMI_FEAT_CHUNK, nb - r0);
+            __syncthreads();  // the previous chunk has been consumed
+            for (uint32_t k = tid; k < n; k += 256u) {
+                const uint32_t tf = hit_tf[f0 + r0 + k];
+                float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f), d4 = make_float4(0.f, 0.f, 1.f, 0.f);
+                if ((tf & 0x3FFFFFFFu) != 0u && !((tf >> 30) & 2u)) { o4 = qo[f0 + r0 + k]; d4 = qd[f0 + r0 + k]; }
+                const HitFeat f = hit_features_nmap(sc, sm, tex, nm, tf, hit_t[f0 + r0 + k], V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w});
                 const uint32_t e = feat_slot(k, rot * fdiv(r0 + k, dS));
                 stage[2u * e] = f.a;
                 stage[2u * e + 1u] = f.n;
@@ -1225,6 +1279,11 @@ struct rtmi_scene {
     TexTab textab{};
     uint32_t ntex = 0;
     bool has_tex = false;
+    // rtmi_scene_set_normal_maps: one float4 per triangle (NmapTab, shade.hpp); the maps' texels are images of `texels`.  A scene
+    // with them renders with the k_shade*_nmap kernels, which know everything the _tex ones do, and k_features_nmap.
+    DevBuf<float4> nmaptri;
+    NmapTab nmaptab{};
+    bool has_nmap = false;
     std::vector<rtmi_triangle_t> htris;  // the records (host copy): the fast-mode BVH is rebuilt from them when corners arrive
     DevBuf<uint4> fnodes, oblocks, ocull;  // (fnodes: the node records, then the node cull records)
     DevBuf<uint32_t> wlinks, cert;
@@ -2014,7 +2073,7 @@ int rtmi_scene_destroy(rtmi_scene_t* s) {
     if (!s) return RTMI_OK;
     (void)hipSetDevice(s->device);
     s->nodes.release(); s->refs.release(); s->tplane.release(); s->tedge.release(); s->mats.release();
-    s->fnodes.release(); s->oblocks.release(); s->ocull.release(); s->cert.release(); s->wlinks.release(); s->bnodes.release(); s->bleaves.release(); s->spheres.release(); s->env.release(); s->smooth.release(); s->textri.release(); s->texels.release(); s->texhdr.release();
+    s->fnodes.release(); s->oblocks.release(); s->ocull.release(); s->cert.release(); s->wlinks.release(); s->bnodes.release(); s->bleaves.release(); s->spheres.release(); s->env.release(); s->smooth.release(); s->textri.release(); s->texels.release(); s->texhdr.release(); s->nmaptri.release();
     for (int k = 0; k < RTMI_MAX_STREAMS; k++) {
         s->w[k].release();
         if (s->istream[k]) (void)hipStreamDestroy(s->istream[k]);
@@ -2323,6 +2382,12 @@ int rtmi_smooth_normals(const float* corners9, const float* facenorm3, uint64_t 
 }
 
 // the tables are in place (or gone): what the k_shade*_tex / k_features_tex kernels get of them
+static void nmap_set(rtmi_scene_t* s, uint32_t n, float strength) {
+    s->nmaptab.tri = n ? s->nmaptri.p : nullptr;
+    s->nmaptab.n = n;
+    s->nmaptab.strength = n ? strength : 0.f;
+    s->has_nmap = n != 0u;
+}
 static void tex_set(rtmi_scene_t* s, uint32_t n, uint32_t ntex) {
     s->textab.tri = n ? s->textri.p : nullptr;
     s->textab.hdr = n ? s->texhdr.p : nullptr;
@@ -2363,6 +2428,9 @@ int rtmi_scene_set_textures(rtmi_scene_t* s, const rtmi_texture_t* tex, uint32_t
     RTMI_GUARD_BEGIN
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(hipDeviceSynchronize());  // no render of this scene is in flight: its streams are done with the old tables
+    // the normal maps name images by number: set, replace or remove the images and they are gone
+    nmap_set(s, 0u, 0.f);
+    s->nmaptri.release();
     if (!set) {
         tex_set(s, 0u, 0u);
         s->textri.release(); s->texhdr.release(); s->texels.release();
@@ -2458,6 +2526,131 @@ int rtmi_project_uvs(const float* corners9, const float* facenorm3, uint64_t n, 
             const float* c = corners9 + 9 * g + 3 * p;
             uvs6_out[6 * g + 2 * p] = (c[j] - lo[j]) * scale;
             uvs6_out[6 * g + 2 * p + 1] = (c[k] - lo[k]) * scale;
+        }
+    }
+    return RTMI_OK;
+}
+
+void rtmi_normal_maps_defaults(rtmi_normal_maps_t* o) {
+    if (!o) return;
+    o->strength = 1.f;
+    o->flags = 0u;
+}
+
+// rtmi_normal_map_frames (include/rtmi.h "NORMAL MAPS OF A SCENE"): the per-triangle part of the definition.  Host code, no HIP call,
+// no sentinel.  frames4_out: (T.xyz, bits) per triangle, NmapTab's record.
+int rtmi_normal_map_frames(const float* corners9, const float* uvs6, const float* facenorm3, const uint32_t* nmap_of_tri, uint64_t n,
+                           float* frames4_out) {
+    if (n == 0) return RTMI_OK;
+    if (!corners9 || !uvs6 || !facenorm3 || !nmap_of_tri || !frames4_out) return fail(RTMI_ERR_INVALID, "NULL argument");
+    for (uint64_t g = 0; g < n; g++) {
+        float* out = frames4_out + 4 * g;
+        out[0] = out[1] = out[2] = out[3] = 0.f;
+        if (nmap_of_tri[g] == 0u) continue;
+        const float *c = corners9 + 9 * g, *uv = uvs6 + 6 * g, *nn = facenorm3 + 3 * g;
+        const V4 c0 = mk(c[0], c[1], c[2]), e1 = vsub(mk(c[3], c[4], c[5]), c0), e2 = vsub(mk(c[6], c[7], c[8]), c0);
+        const float d00 = vdot(e1, e1), d01 = vdot(e1, e2), d11 = vdot(e2, e2), den = d00 * d11 - d01 * d01;
+        const float du1 = uv[2] - uv[0], du2 = uv[4] - uv[0], dv1 = uv[3] - uv[1], dv2 = uv[5] - uv[1];
+        const float det = du1 * dv2 - du2 * dv1;
+        if (det == 0.f || den == 0.f) continue;  // no tangent frame: stored with map 0
+        V4 T = vsub(vmul(e1, dv2), vmul(e2, dv1)), B = vsub(vmul(e2, du1), vmul(e1, du2));
+        if (det < 0.f) { T = vmul(T, -1.f); B = vmul(B, -1.f); }
+        const V4 ng = mk(nn[0], nn[1], nn[2]);
+        const V4 x = mk(ng.y * T.z - ng.z * T.y, ng.z * T.x - ng.x * T.z, ng.x * T.y - ng.y * T.x);
+        const bool neg = !(vdot(x, B) >= 0.f);
+        const uint32_t bits = nmap_of_tri[g] | (neg ? 0x80000000u : 0u);
+        out[0] = T.x; out[1] = T.y; out[2] = T.z;
+        memcpy(&out[3], &bits, sizeof bits);
+    }
+    return RTMI_OK;
+}
+
+// rtmi_scene_set_normal_maps (include/rtmi.h "NORMAL MAPS OF A SCENE"): the per-triangle frame, once, on the host.  The uvs are
+// read back from the texture table, where rtmi_scene_set_textures stored them.
+int rtmi_scene_set_normal_maps(rtmi_scene_t* s, const float* corners9, const uint32_t* nmap_of_tri, uint64_t n, const rtmi_normal_maps_t* opt) {
+    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
+    const bool set = nmap_of_tri && n;
+    rtmi_normal_maps_t o;
+    rtmi_normal_maps_defaults(&o);
+    if (opt) o = *opt;
+    if (set) {
+        if (!s->has_tex) return fail(RTMI_ERR_INVALID, "normal maps: the scene has no textures (a map is one of rtmi_scene_set_textures' images)");
+        if (!corners9) return fail(RTMI_ERR_INVALID, "normal maps: corners is NULL");
+        if (n != s->d.ntris) return fail(RTMI_ERR_INVALID, "normal maps: n must equal ntris");
+        if (o.flags != 0u) return fail(RTMI_ERR_INVALID, "normal maps: flags != 0");
+        if (!std::isfinite(o.strength)) return fail(RTMI_ERR_INVALID, "normal maps: strength is not finite");
+        for (uint64_t g = 1; g < n; g++) {  // (entry 0 is the sentinel's and is ignored)
+            if (nmap_of_tri[g] > s->ntex)
+                return fail(RTMI_ERR_INVALID, "normal maps: nmap_of_tri of triangle " + std::to_string(g) + " is above ntex");
+            if (nmap_of_tri[g] == 0u) continue;
+            for (int k = 0; k < 9; k++)
+                if (!std::isfinite(corners9[9 * g + k])) return fail(RTMI_ERR_INVALID, "normal maps: a corner of triangle " + std::to_string(g) + " is not finite");
+        }
+    }
+    RTMI_GUARD_BEGIN
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipDeviceSynchronize());  // no render of this scene is in flight: its streams are done with the old table
+    if (!set) {
+        nmap_set(s, 0u, 0.f);
+        s->nmaptri.release();
+        return RTMI_OK;
+    }
+    std::vector<float4> ttab((size_t)n * 5);
+    HIPCHK(hipMemcpy(ttab.data(), s->textri.p, ttab.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    std::vector<float4> tab((size_t)n, make_float4(0.f, 0.f, 0.f, 0.f));
+    {
+        std::vector<float> uvs((size_t)n * 6), fn((size_t)n * 3);
+        for (uint64_t g = 0; g < n; g++) {
+            const float4 qu = ttab[(size_t)g * 5 + 3], qv = ttab[(size_t)g * 5 + 4];
+            float* o = &uvs[6 * g];
+            o[0] = qu.x; o[1] = qv.x; o[2] = qu.y; o[3] = qv.y; o[4] = qu.z; o[5] = qv.z;
+            memcpy(&fn[3 * g], s->htris[g].norm, 12);
+        }
+        // (entry 0, the sentinel's, stays zero)
+        const int rc = rtmi_normal_map_frames(corners9 + 9, uvs.data() + 6, fn.data() + 3, nmap_of_tri + 1, n - 1, reinterpret_cast<float*>(tab.data() + 1));
+        if (rc != RTMI_OK) return rc;
+    }
+    nmap_set(s, 0u, 0.f);  // (a failure below leaves the scene without maps, not with stale ones)
+    HIPCHK(s->nmaptri.ensure(tab.size()));
+    HIPCHK(hipMemcpy(s->nmaptri.p, tab.data(), tab.size() * sizeof(float4), hipMemcpyHostToDevice));
+    nmap_set(s, (uint32_t)n, o.strength);
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+int rtmi_scene_get_normal_maps(rtmi_scene_t* s, uint32_t* nmap_of_tri_out, float* strength_out, uint64_t* n_out) {
+    if (!s || !n_out) return fail(RTMI_ERR_INVALID, "NULL argument");
+    *n_out = s->has_nmap ? s->nmaptab.n : 0u;
+    if (strength_out) *strength_out = s->has_nmap ? s->nmaptab.strength : 0.f;
+    if (!s->has_nmap || !nmap_of_tri_out) return RTMI_OK;
+    RTMI_GUARD_BEGIN
+    const size_t n = s->nmaptab.n;
+    std::vector<float4> tab(n);
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(tab.data(), s->nmaptri.p, tab.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t g = 0; g < n; g++) {
+        uint32_t bits;
+        memcpy(&bits, &tab[g].w, sizeof bits);
+        nmap_of_tri_out[g] = bits & 0x7FFFFFFFu;
+    }
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+// rtmi_normal_map_from_height (include/rtmi.h): host code, no HIP call.  Repeat-wrapped central differences of a height field.
+int rtmi_normal_map_from_height(const float* height, uint32_t w, uint32_t h, float scale, float* rgb_out) {
+    if ((uint64_t)w * h == 0) return RTMI_OK;
+    if (!height || !rgb_out) return fail(RTMI_ERR_INVALID, "NULL argument");
+    for (uint32_t j = 0; j < h; j++) {
+        const size_t jm = (size_t)(j == 0 ? h - 1 : j - 1) * w, jp = (size_t)(j == h - 1 ? 0 : j + 1) * w, jj = (size_t)j * w;
+        for (uint32_t i = 0; i < w; i++) {
+            const uint32_t im = i == 0 ? w - 1 : i - 1, ip = i == w - 1 ? 0 : i + 1;
+            const float dx = ((height[jj + ip] - height[jj + im]) * 0.5f) * scale;
+            const float dy = ((height[jp + i] - height[jm + i]) * 0.5f) * scale;
+            const V4 nn = vunit(mk(dx * -1.f, dy * -1.f, 1.f));
+            float* o = rgb_out + 3 * (jj + i);
+            o[0] = nn.x * 0.5f + 0.5f; o[1] = nn.y * 0.5f + 0.5f; o[2] = nn.z * 0.5f + 0.5f;
         }
     }
     return RTMI_OK;
@@ -2776,7 +2969,10 @@ static int check_view(const rtmi_viewport_t* vp, const rtmi_tile_t* tile) {
 static void launch_features(rtmi_scene* s, dim3 grid, dim3 block, hipStream_t st, uint32_t npixels, uint32_t nsamples, const uint32_t* hit_tf,
                             const float* hit_t, float* albedo, float* normal, uint32_t* ids, uint32_t pix0, uint32_t W, uint32_t nsub, uint32_t sub,
                             const float4* qo, const float4* qd) {
-    if (s->has_tex)
+    if (s->has_nmap)
+        hipLaunchKernelGGL(k_features_nmap, grid, block, 0, st, s->d, npixels, nsamples, hit_tf, hit_t, albedo, normal, ids, pix0, W, nsub, sub,
+                           make_fastdiv(W), make_fastdiv(nsamples), qo, qd, s->smoothtab, s->textab, s->nmaptab);
+    else if (s->has_tex)
         hipLaunchKernelGGL(k_features_tex, grid, block, 0, st, s->d, npixels, nsamples, hit_tf, hit_t, albedo, normal, ids, pix0, W, nsub, sub,
                            make_fastdiv(W), make_fastdiv(nsamples), qo, qd, s->smoothtab, s->textab);
     else if (s->has_normals)
@@ -2798,7 +2994,7 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
     // shades the primary rays in one kernel.  Everything else (pipeline 1, linear list, generic tree, BVH mode,
     // analytic spheres) starts with k_gen.  Both then run one closest-hit + one shading launch per bounce pass.
     c.path_kernels = !c.fo && !c.ao && !c.li && !c.pv && !c.sh && !c.cam && s->tune.pipeline != 1u && s->octree && !s->root_is_leaf &&
-                     !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) && s->d.nspheres == 0 && !s->has_dielectric && !s->has_env && !s->has_normals && !s->has_tex;
+                     !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) && s->d.nspheres == 0 && !s->has_dielectric && !s->has_env && !s->has_normals && !s->has_tex && !s->has_nmap;
     // streams = 0 (automatic): one stream for path-kernel tiles of 2^26 paths and more, three otherwise (the per-pass
     // pipelines -- BVH mode: 29.6 ms on three streams, 35.2 on one -- have elementwise kernels to hide).  Since k_shade stopped being
     // atomic-bound (round 3) there is little left for a second stream to hide: the full config-3 frame takes 366.9 ms on one
@@ -3079,7 +3275,20 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
         // (s->envtab.n = 0 without one)
         // a scene with textures (never with c.path_kernels either): the _tex kernels, which know all of the above (s->smoothtab.n = 0
         // without normals) and fold over the colour stack
-        if (s->has_tex && list)
+        // a scene with normal maps (it has textures): the _nmap kernels, which know all of that and the maps
+        if (s->has_nmap && list)
+            hipLaunchKernelGGL(k_shade_list_nmap, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
+                               w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, list, s->envtab,
+                               s->smoothtab, s->textab, w.cstack.p, s->nmaptab);
+        else if (s->has_nmap && c.mode == Samp::VIEWS)
+            hipLaunchKernelGGL(k_shade_views_nmap, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
+                               w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, c.vt, s->envtab,
+                               s->smoothtab, s->textab, w.cstack.p, s->nmaptab);
+        else if (s->has_nmap)
+            hipLaunchKernelGGL(c.mode == Samp::PASS ? k_shade_samples_nmap : k_shade_nmap, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths,
+                               (int)pass, w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p,
+                               w.mstack.p, w.scol.p, w.ctrl.p, sq, s->envtab, s->smoothtab, s->textab, w.cstack.p, s->nmaptab);
+        else if (s->has_tex && list)
             hipLaunchKernelGGL(k_shade_list_tex, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
                                w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, list, s->envtab,
                                s->smoothtab, s->textab, w.cstack.p);
@@ -4577,7 +4786,11 @@ static int render_rays(rtmi_scene_t* s, uint64_t n, const void* orig4, const voi
             HIPCHK(hipGetLastError());
             if (pass == 0 && guides)  // before pass 1 rewrites the hit records
                 launch_features(s, ew_grid, ew_block, st, ng, G, w.hit_tf.p, w.hit_t.p, (float*)albedo, (float*)normal, ids, 0u, ng, 1u, 0u, pqo, pqd);
-            if (shade && s->has_tex)
+            if (shade && s->has_nmap)
+                hipLaunchKernelGGL(k_shade_rays_nmap, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(rp->pixel0 + gbase), nb, (int)pass, pqo, pqd,
+                                   w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, scol, w.ctrl.p,
+                                   SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, kq, s->envtab, s->smoothtab, s->textab, w.cstack.p, s->nmaptab);
+            else if (shade && s->has_tex)
                 hipLaunchKernelGGL(k_shade_rays_tex, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(rp->pixel0 + gbase), nb, (int)pass, pqo, pqd,
                                    w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, scol, w.ctrl.p,
                                    SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, kq, s->envtab, s->smoothtab, s->textab, w.cstack.p);
@@ -4772,7 +4985,12 @@ static int bake(rtmi_scene_t* s, uint64_t M, const void* pos4, const void* nrm4,
             if (pass == 0 && open)  // before pass 1 rewrites the hit records
                 hipLaunchKernelGGL(k_bake_open, dim3(std::min<unsigned>((unsigned)(s->num_cu * 8), (mb + RTMI_BAKE_OPEN_ELEMS - 1u) / RTMI_BAKE_OPEN_ELEMS)),
                                    ew_block, 0, st, mb, K, w.hit_tf.p, open);
-            if (shade && s->has_tex)
+            if (shade && s->has_nmap)
+                hipLaunchKernelGGL(k_shade_rays_nmap, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(bp->pixel0 + mbase), nb, (int)pass, pqo, pqd,
+                                   w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p,
+                                   SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, (const uint32_t*)nullptr, s->envtab, s->smoothtab, s->textab, w.cstack.p,
+                                   s->nmaptab);
+            else if (shade && s->has_tex)
                 hipLaunchKernelGGL(k_shade_rays_tex, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(bp->pixel0 + mbase), nb, (int)pass, pqo, pqd,
                                    w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p,
                                    SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, (const uint32_t*)nullptr, s->envtab, s->smoothtab, s->textab, w.cstack.p);

@@ -283,6 +283,38 @@ __device__ inline RayV bounce_ray(uint32_t kind, float m1x, uint32_t face, V4 po
 struct TexTab { const float4* __restrict__ tri; const uint4* __restrict__ hdr; const float4* __restrict__ texels; uint32_t n; };
 // one wrap step of the repeat: i in [-1, N]
 __device__ inline uint32_t tex_wrap(int i, int N) { return (uint32_t)(i < 0 ? i + N : (i >= N ? i - N : i)); }
+// tex_colour's statements in three parts, for tex_colour_nmap below, where the colour and the normal map share one (u, v).
+// tex_colour itself keeps them written out: calling these parts from it changed the machine code of the k_shade*_tex kernels.
+// (u, v) at `point` of a triangle whose record is q0 .. q4: barycentric coordinates by smooth_normal's statements and the corner
+// uvs interpolated, as include/rtmi.h lists them.
+__device__ inline void tex_uv(float4 q0, float4 q1, float4 q2, float4 q3, float4 q4, V4 point, float& u, float& v) {
+    const V4 e1 = mk(q1.x, q1.y, q1.z), e2 = mk(q2.x, q2.y, q2.z);
+    const float d00 = q0.w, d01 = q1.w, d11 = q2.w, den = q3.w;
+    const V4 w = vsub(point, mk(q0.x, q0.y, q0.z));
+    const float d20 = vdot(w, e1), d21 = vdot(w, e2);
+    const float b1 = (d11 * d20 - d01 * d21) / den, b2 = (d00 * d21 - d01 * d20) / den, b0 = (1.f - b1) - b2;
+    u = (q3.x * b0 + q3.y * b1) + q3.z * b2;
+    v = (q4.x * b0 + q4.y * b1) + q4.z * b2;
+}
+// The four texels and the two weights of the bilinear, repeating lookup of the image with header h at (u, v): indices (relative to
+// the image's first texel) from the clamped texel coordinates, weights from the unclamped ones.
+struct TexTap { uint32_t i00, i10, i01, i11; float tx, ty; };
+__device__ inline TexTap tex_tap(uint4 h, float u, float v) {
+    const float fu = u - floorf(u), fv = v - floorf(v);
+    const int W = (int)h.y, H = (int)h.z;
+    const float fW = (float)h.y, fH = (float)h.z;
+    const float fx = fu * fW - 0.5f, fy = fv * fH - 0.5f;
+    const float cx = !(fx >= -1.f) ? -1.f : (fx > fW - 1.f ? fW - 1.f : fx), cy = !(fy >= -1.f) ? -1.f : (fy > fH - 1.f ? fH - 1.f : fy);
+    const int ix = (int)floorf(cx), iy = (int)floorf(cy);
+    const float tx_ = fx - floorf(fx), ty_ = fy - floorf(fy);
+    const uint32_t x0 = tex_wrap(ix, W), x1 = tex_wrap(ix + 1, W), y0 = tex_wrap(iy, H) * h.y, y1 = tex_wrap(iy + 1, H) * h.y;
+    return TexTap{y0 + x0, y0 + x1, y1 + x0, y1 + x1, tx_, ty_};
+}
+// the bilinear mix of four loaded texels
+__device__ inline V4 tex_mix(float4 c00, float4 c10, float4 c01, float4 c11, float tx_, float ty_) {
+    auto v4 = [](float4 a) { return V4{a.x, a.y, a.z, a.w}; };
+    return mix_color(mix_color(v4(c00), v4(c10), tx_), mix_color(v4(c01), v4(c11), tx_), ty_);
+}
 // The colour of a hit at `point` of triangle `tri` (< tx.n) whose material colour is m0, operation by operation as include/rtmi.h
 // lists it: barycentric coordinates by smooth_normal's statements, the corner uvs interpolated, the repeat, a bilinear lookup with
 // plain loads whose indices come from the clamped texel coordinates (no value reads outside the image) and whose weights come from
@@ -315,6 +347,52 @@ __device__ inline V4 tex_colour(const TexTab& tx, uint32_t tri, V4 point, float4
     return mk(m0.x * tc.x, m0.y * tc.y, m0.z * tc.z);
 }
 
+// The normal maps of a scene (rtmi_scene_set_normal_maps, include/rtmi.h "NORMAL MAPS OF A SCENE").  tri: one float4
+// per triangle, (T.xyz, bits): bits 0-30 the map's image number among TexTab's images (0: none), bit 31 set when hand = -1.f; entry
+// 0 the sentinel's, n = ntris.  An argument of the k_shade*_nmap and k_features_nmap kernels only: DScene, and with it every other
+// kernel's argument block, stays as it is.
+struct NmapTab { const float4* __restrict__ tri; uint32_t n; float strength; };
+// tex_colour for the kernels of scenes with normal maps: the colour of the hit and, for a mapped triangle (kmap != 0), the map's
+// bilinear lookup M at the same (u, v).  fr: the triangle's NmapTab record.  The two header loads are requested together, and
+// after them the eight texel loads; an image number of 0 borrows the other's so that both lookups read valid texels, and its
+// result is not used.  A triangle without a colour texture keeps m0's colour bit for bit.
+__device__ inline V4 tex_colour_nmap(const TexTab& tx, const NmapTab& nt, uint32_t tri, V4 point, float4 m0, V4& M, float4& fr, uint32_t& kmap) {
+    const float4* __restrict__ r = tx.tri + (size_t)tri * 5u;
+    const float4 q0 = r[0], q1 = r[1], q2 = r[2], q3 = r[3], q4 = r[4];
+    fr = tri < nt.n ? nt.tri[tri] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const uint32_t k = __float_as_uint(q4.w);
+    kmap = __float_as_uint(fr.w) & 0x7FFFFFFFu;
+    M = mk(0.f, 0.f, 0.f);
+    if (k == 0u && kmap == 0u) return mk(m0.x, m0.y, m0.z);
+    const uint4 hc = tx.hdr[(k ? k : kmap) - 1u], hm = tx.hdr[(kmap ? kmap : k) - 1u];
+    float u, v;
+    tex_uv(q0, q1, q2, q3, q4, point, u, v);
+    const TexTap a = tex_tap(hc, u, v), b = tex_tap(hm, u, v);
+    const float4* __restrict__ ic = tx.texels + hc.x;
+    const float4* __restrict__ im = tx.texels + hm.x;
+    const float4 c00 = ic[a.i00], c10 = ic[a.i10], c01 = ic[a.i01], c11 = ic[a.i11];
+    const float4 m00 = im[b.i00], m10 = im[b.i10], m01 = im[b.i01], m11 = im[b.i11];
+    const V4 tc = tex_mix(c00, c10, c01, c11, a.tx, a.ty);
+    M = tex_mix(m00, m10, m01, m11, b.tx, b.ty);
+    return k ? mk(m0.x * tc.x, m0.y * tc.y, m0.z * tc.z) : mk(m0.x, m0.y, m0.z);
+}
+// The mapped normal of a hit, operation by operation as include/rtmi.h lists it: the texel M decoded and scaled, the stored
+// tangent T made orthogonal to the shading normal N (Gram-Schmidt) and normalised, the bitangent from their cross product and the
+// stored handedness (negated on a back face, where N is negated, so that t and b are the same world vectors), the sum normalised.
+// usem: the result faces the geometric side that was hit (ng) and the incoming ray; otherwise (a NaN among the cases) the caller
+// shades with N.
+__device__ inline V4 nmap_normal(float4 fr, V4 M, float strength, uint32_t face, V4 N, V4 ng, V4 rd, bool& usem) {
+    const V4 T = mk(fr.x, fr.y, fr.z);
+    const float hand = (__float_as_uint(fr.w) >> 31) ? -1.f : 1.f;
+    const float x = (M.x * 2.f - 1.f) * strength, y = (M.y * 2.f - 1.f) * strength, z = M.z * 2.f - 1.f;
+    const V4 t = vunit(vsub(T, vmul(N, vdot(N, T))));
+    const V4 c = mk(N.y * t.z - N.z * t.y, N.z * t.x - N.x * t.z, N.x * t.y - N.y * t.x);
+    const V4 b = vmul(c, (face & 1u) ? -hand : hand);
+    const V4 nm = vunit(vadd(vadd(vmul(t, x), vmul(b, y)), vmul(N, z)));
+    usem = vdot(nm, ng) > 0.f && vdot(rd, nm) < 0.f;
+    return nm;
+}
+
 // color_ray + the tail of project_ray for ONE traced ray of a path.  `pass` = bounces the path has behind it (the ray's
 // remaining depth is maxdepth - pass >= 1); tf = hit triangle | face << 30 (0 = miss), t = hit time; (ro, rd) the ray.
 // Returns true when the path goes on: its surface has been pushed on the path's stack (mstack[pass][path]) and `nr` is
@@ -337,11 +415,16 @@ __device__ inline V4 tex_colour(const TexTab& tx, uint32_t tri, V4 point, float4
 // give a triangle hit that is no edge face tex_colour's colour: a Solid hit ends with it, every other hit pushes it with the
 // material's alpha on the colour stack cstack[pass][path], and the fold reads the level's colour there and not in the material
 // table.  Nothing else moves.  Without it `tex` and `cstack` are never read.
-template <bool GLASS = false, bool ENV = false, bool SMOOTH = false, bool TEX = false>
+// NMAP: the kernels of scenes with normal maps (k_shade*_nmap, always with GLASS, ENV, SMOOTH and TEX) look the map up with the
+// colour (tex_colour_nmap: one (u, v)) and shade a bouncing hit of a mapped triangle with nmap_normal's result where it is usable;
+// the wrong-side rule is SMOOTH's with (use || usem).  The mapped normal is used where it is computed and is not stacked.
+// Without it `nm` is never read.
+template <bool GLASS = false, bool ENV = false, bool SMOOTH = false, bool TEX = false, bool NMAP = false>
 __device__ inline bool shade_hit(const DScene& sc, uint32_t maxdepth, uint64_t seed, uint32_t npaths, uint32_t path, uint32_t pixel,
                                  uint32_t sample, uint32_t pass, uint32_t tf, float t, V4 ro, V4 rd, uint16_t* __restrict__ mstack,
                                  float4* __restrict__ scol, RayV& nr, bool* mirror = nullptr, const EnvTab* env = nullptr,
-                                 const SmoothTab* sm = nullptr, const TexTab* tex = nullptr, float4* __restrict__ cstack = nullptr) {
+                                 const SmoothTab* sm = nullptr, const TexTab* tex = nullptr, float4* __restrict__ cstack = nullptr,
+                                 const NmapTab* nm = nullptr) {
     const uint32_t tri = tf & 0x3FFFFFFFu, face = tf >> 30;
     V4 c;
     uint32_t npushed = pass;
@@ -360,7 +443,12 @@ __device__ inline bool shade_hit(const DScene& sc, uint32_t maxdepth, uint64_t s
         const float4 m0 = sc.mats[2 * mat], m1 = sc.mats[2 * mat + 1];
         const uint32_t kind = __float_as_uint(m1.y);
         V4 tcol = mk(m0.x, m0.y, m0.z);
-        if constexpr (TEX) {
+        V4 mapM = mk(0.f, 0.f, 0.f);
+        float4 mapfr = make_float4(0.f, 0.f, 0.f, 0.f);
+        uint32_t kmap = 0u;
+        if constexpr (TEX && NMAP) {
+            if (!is_sphere && tri < tex->n) tcol = tex_colour_nmap(*tex, *nm, tri, vadd(vmul(rd, t), ro), m0, mapM, mapfr, kmap);
+        } else if constexpr (TEX) {
             if (!is_sphere && tri < tex->n) tcol = tex_colour(*tex, tri, vadd(vmul(rd, t), ro), m0);
         }
         if (kind == RTMI_SOLID) {
@@ -388,6 +476,13 @@ __device__ inline bool shade_hit(const DScene& sc, uint32_t maxdepth, uint64_t s
                     V4 n = norm;
                     if (!is_sphere && tri < sm->n) n = smooth_normal(*sm, tri, face, point, rd, norm, use);
                     if (!use) n = norm;
+                    if constexpr (NMAP) {
+                        if (kmap != 0u) {
+                            bool usem = false;
+                            const V4 mn = nmap_normal(mapfr, mapM, nm->strength, face, n, norm, rd, usem);
+                            if (usem) { n = mn; use = true; }
+                        }
+                    }
                     for (;;) {
                         V4 dir;
                         float side;
@@ -503,6 +598,30 @@ __device__ inline HitFeat hit_features_tex(const DScene& sc, const SmoothTab& sm
     if (tri != 0u && !(face & 2u) && tri < tx.n) {
         const V4 c = tex_colour(tx, tri, vadd(vmul(rd, t), ro), f.a);
         f.a.x = c.x; f.a.y = c.y; f.a.z = c.z;
+    }
+    return f;
+}
+
+// hit_features for a scene with normal maps (k_features_nmap): the normal of a hit of a mapped triangle that is no edge face is
+// nmap_normal's about hit_features_tex's normal N at the hit point of the primary ray (ro, rd) where it is usable, N otherwise.
+// Albedo, coverage and depth are hit_features_tex's.
+__device__ inline HitFeat hit_features_nmap(const DScene& sc, const SmoothTab& sm, const TexTab& tx, const NmapTab& nt, uint32_t tf, float t,
+                                            V4 ro, V4 rd) {
+    HitFeat f = hit_features_tex(sc, sm, tx, tf, t, ro, rd);
+    const uint32_t tri = tf & 0x3FFFFFFFu, face = tf >> 30;
+    if (tri != 0u && !(face & 2u) && tri < tx.n && tri < nt.n) {
+        const float4 p1 = sc.tplane[2 * tri + 1];
+        V4 ng = mk(p1.x, p1.y, p1.z);
+        if (face & 1u) ng = vmul(ng, -1.f);
+        V4 M;
+        float4 fr;
+        uint32_t kmap;
+        (void)tex_colour_nmap(tx, nt, tri, vadd(vmul(rd, t), ro), f.a, M, fr, kmap);
+        if (kmap != 0u) {
+            bool usem = false;
+            const V4 mn = nmap_normal(fr, M, nt.strength, face, mk(f.n.x, f.n.y, f.n.z), ng, rd, usem);
+            if (usem) { f.n.x = mn.x; f.n.y = mn.y; f.n.z = mn.z; }
+        }
     }
     return f;
 }

@@ -261,6 +261,7 @@ int rth_scene_set_textures(rth_scene_t* s, const rtmi_texture_t* tex, uint32_t n
         Scene& sc = s->scene;
         if (!tex || ntex == 0) {  // everything goes: images, uvs, texture numbers
             sc.textures.clear(); sc.uvs.clear(); sc.tex_of_tri.clear(); sc.tex_generation++;
+            sc.nmap_of_tri.clear(); sc.nmap_generation++;  // the maps name images by number
             return;
         }
         if (ntex > 256u) throw std::runtime_error("textures: more than 256 textures");
@@ -281,6 +282,7 @@ int rth_scene_set_textures(rth_scene_t* s, const rtmi_texture_t* tex, uint32_t n
             if (sc.tex_of_tri[i] > ntex) throw std::runtime_error("textures: tex_of_tri of triangle " + std::to_string(i) + " is above ntex");
         sc.textures = std::move(v);
         sc.tex_generation++;
+        sc.nmap_of_tri.clear(); sc.nmap_generation++;  // the maps name images by number: new images, no maps
     });
 }
 int rth_scene_set_uvs(rth_scene_t* s, const float* uvs6, const uint32_t* tex_of_tri, uint64_t first, uint64_t count) {
@@ -390,6 +392,76 @@ int rth_add_obj_uvs(rth_scene_t* s, const char* path, const float* off, float sc
         std::copy(uv.begin(), uv.end(), sc.uvs.begin() + first * 6);
         std::fill(sc.tex_of_tri.begin() + first, sc.tex_of_tri.end(), texture);
         sc.tex_generation++;
+    });
+}
+// --- normal maps (rtmi_scene_set_normal_maps in rtmi.h, which defines them)
+int rth_scene_set_normal_maps(rth_scene_t* s, const uint32_t* nmap_of_tri, uint64_t first, uint64_t count, float strength, uint32_t flags) {
+    return guarded([&] {
+        Scene& sc = s->scene;
+        if (!nmap_of_tri || count == 0) {  // none
+            sc.nmap_of_tri.clear(); sc.nmap_strength = 1.f; sc.nmap_generation++;
+            return;
+        }
+        if (sc.textures.empty()) throw std::runtime_error("normal maps: the scene has no textures (a map is one of its images)");
+        if (flags != 0u) throw std::runtime_error("normal maps: flags != 0");
+        if (!std::isfinite(strength)) throw std::runtime_error("normal maps: strength is not finite");
+        normals_range(s, first, count, "normal maps");
+        for (uint64_t i = 0; i < count; i++)
+            if (nmap_of_tri[i] > sc.textures.size())
+                throw std::runtime_error("normal maps: nmap_of_tri of triangle " + std::to_string(first + i) + " is above ntex");
+        if (sc.nmap_of_tri.size() < first + count) sc.nmap_of_tri.resize(first + count, 0u);
+        std::copy(nmap_of_tri, nmap_of_tri + count, sc.nmap_of_tri.begin() + first);
+        sc.nmap_strength = strength;
+        sc.nmap_generation++;
+    });
+}
+int rth_scene_normal_maps_size(const rth_scene_t* s, uint64_t* n_out) {
+    *n_out = s->scene.nmap_of_tri.empty() ? 0u : s->scene.tris.size();
+    return 0;
+}
+int rth_scene_get_normal_maps(const rth_scene_t* s, uint32_t* nmap_of_tri_out, float* strength_out, uint64_t cap_tris) {
+    return guarded([&] {
+        const Scene& sc = s->scene;
+        const size_t n = sc.tris.size();
+        if (n > cap_tris) throw std::runtime_error("rth_scene_get_normal_maps: the buffer is too small");
+        std::fill(nmap_of_tri_out, nmap_of_tri_out + n, 0u);
+        std::copy(sc.nmap_of_tri.begin(), sc.nmap_of_tri.begin() + std::min(n, sc.nmap_of_tri.size()), nmap_of_tri_out);
+        *strength_out = sc.nmap_strength;
+    });
+}
+// rtmi_normal_map_frames over the scene's triangles, with its corners, uvs and records' normals: what a device stores
+int rth_scene_normal_map_frames(const rth_scene_t* s, float* frames4_out, uint64_t cap_tris) {
+    return guarded([&] {
+        const Scene& sc = s->scene;
+        const size_t n = sc.tris.size();
+        if (n > cap_tris) throw std::runtime_error("rth_scene_normal_map_frames: the buffer is too small");
+        std::vector<float> corners(n * 9, 0.f), fn(n * 3, 0.f), uvs(n * 6, 0.f);
+        std::vector<uint32_t> nm(n, 0u);
+        for (size_t i = 1; i < n; i++) {
+            for (int k = 0; k < 3; k++) memcpy(&corners[9 * i + 3 * k], sc.tris[i].corners[k].v, 12);
+            memcpy(&fn[3 * i], sc.tris[i].norm.v, 12);
+        }
+        std::copy(sc.uvs.begin(), sc.uvs.begin() + std::min(sc.uvs.size(), uvs.size()), uvs.begin());
+        std::copy(sc.nmap_of_tri.begin(), sc.nmap_of_tri.begin() + std::min(n, sc.nmap_of_tri.size()), nm.begin());
+        std::fill(frames4_out, frames4_out + n * 4, 0.f);
+        if (n > 1 && rtmi_normal_map_frames(corners.data() + 9, uvs.data() + 6, fn.data() + 3, nm.data() + 1, n - 1, frames4_out + 4) != RTMI_OK)
+            throw std::runtime_error(std::string("rtmi_normal_map_frames: ") + rtmi_last_error());
+    });
+}
+int rth_caster_normal_maps(rth_scene_t* s, uint32_t* nmap_of_tri_out, float* strength_out, uint64_t cap_tris, uint64_t* n_out) {
+    return guarded([&] {
+        float strength = 0.f;
+        const std::vector<uint32_t> v = caster_of(s).normal_maps(s->scene, strength);
+        if (v.size() > cap_tris) throw std::runtime_error("rth_caster_normal_maps: the buffer is too small");
+        if (!v.empty()) memcpy(nmap_of_tri_out, v.data(), v.size() * sizeof(uint32_t));
+        *strength_out = strength;
+        *n_out = v.size();
+    });
+}
+int rth_normal_map_from_height(const float* height, uint32_t w, uint32_t h, float scale, float* rgb_out) {
+    return guarded([&] {
+        if (rtmi_normal_map_from_height(height, w, h, scale, rgb_out) != RTMI_OK)
+            throw std::runtime_error(std::string("rtmi_normal_map_from_height: ") + rtmi_last_error());
     });
 }
 void rth_populate_triangle_numbers(rth_scene_t* s) { populate_triangle_numbers(s->scene.tris); s->scene.touch(); }

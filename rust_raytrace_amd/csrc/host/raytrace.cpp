@@ -556,6 +556,8 @@ void HipRayCaster::invalidate() {
     env_applied_ = false;
     normals_applied_ = false;
     tex_applied_ = false;
+    nmap_applied_ = false;
+    nmap_on_device_ = false;
 }
 
 void HipRayCaster::apply_textures(const Scene& s) {
@@ -590,6 +592,52 @@ void HipRayCaster::apply_textures(const Scene& s) {
     }
     tex_applied_ = true;
     key_tex_generation_ = s.tex_generation;
+    nmap_applied_ = false;  // rtmi_scene_set_textures removed the handles' normal maps: apply_normal_maps puts them back
+    nmap_on_device_ = false;
+}
+
+void HipRayCaster::apply_normal_maps(const Scene& s) {
+    if (nmap_applied_ && key_nmap_generation_ == s.nmap_generation) return;
+    std::vector<rtmi_scene_t*> all{handle_};
+    all.insert(all.end(), extra_.begin(), extra_.end());
+    const bool none = s.nmap_of_tri.empty() || s.textures.empty();
+    std::vector<float> corners;
+    std::vector<uint32_t> nm;
+    if (!none) {
+        const size_t n = s.tris.size();
+        corners.assign(n * 9, 0.f);
+        nm.assign(n, 0u);  // triangles beyond the ones that were given a map have none
+        for (size_t i = 1; i < n; i++)
+            for (int k = 0; k < 3; k++)
+                for (int c = 0; c < 3; c++) corners[9 * i + 3 * k + c] = s.tris[i].corners[k].v[c];
+        std::copy(s.nmap_of_tri.begin(), s.nmap_of_tri.begin() + std::min(s.nmap_of_tri.size(), nm.size()), nm.begin());
+    }
+    const rtmi_normal_maps_t opt{s.nmap_strength, 0u};
+    for (rtmi_scene_t* hh : all) {
+        if (none && !nmap_on_device_) continue;  // fresh handles, and handles whose textures were just set, have none
+        const int rc = none ? rtmi_scene_set_normal_maps(hh, nullptr, nullptr, 0, nullptr)
+                            : rtmi_scene_set_normal_maps(hh, corners.data(), nm.data(), s.tris.size(), &opt);
+        if (rc != RTMI_OK) {
+            const std::string msg = std::string("rtmi_scene_set_normal_maps: ") + rtmi_last_error();
+            invalidate();
+            throw std::runtime_error(msg);
+        }
+    }
+    nmap_on_device_ = !none;
+    nmap_applied_ = true;
+    key_nmap_generation_ = s.nmap_generation;
+}
+
+std::vector<uint32_t> HipRayCaster::normal_maps(const Scene& s, float& strength) {
+    rtmi_scene_t* h = resident(s);
+    uint64_t n = 0;
+    strength = 0.f;
+    if (rtmi_scene_get_normal_maps(h, nullptr, &strength, &n) != RTMI_OK)
+        throw std::runtime_error(std::string("rtmi_scene_get_normal_maps: ") + rtmi_last_error());
+    std::vector<uint32_t> out((size_t)n, 0u);
+    if (n && rtmi_scene_get_normal_maps(h, out.data(), &strength, &n) != RTMI_OK)
+        throw std::runtime_error(std::string("rtmi_scene_get_normal_maps: ") + rtmi_last_error());
+    return out;
 }
 
 void HipRayCaster::texture_uvs(const Scene& s, std::vector<float>& uvs6, std::vector<uint32_t>& tex_of_tri) {
@@ -729,6 +777,7 @@ rtmi_scene_t* HipRayCaster::resident(const Scene& s) {
         apply_environment(s);
         apply_normals(s);
         apply_textures(s);
+        apply_normal_maps(s);
         apply_settings();
         return handle_;
     }
@@ -787,6 +836,7 @@ rtmi_scene_t* HipRayCaster::resident(const Scene& s) {
     apply_environment(s);
     apply_normals(s);
     apply_textures(s);
+    apply_normal_maps(s);
     apply_settings();
     return handle_;
 }

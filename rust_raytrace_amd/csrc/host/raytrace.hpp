@@ -172,6 +172,12 @@ struct Scene {
     std::vector<float> uvs;
     std::vector<uint32_t> tex_of_tri;
     uint64_t tex_generation = 0;
+    // Normal maps (include/rtmi.h, "NORMAL MAPS OF A SCENE"), or none (empty): per triangle 0 = none, or the number
+    // 1..images of the texture that is its map; may be shorter than tris.  Applied after the textures: code that edits them bumps
+    // nmap_generation.  Setting or clearing the images clears them.
+    std::vector<uint32_t> nmap_of_tri;
+    float nmap_strength = 1.f;
+    uint64_t nmap_generation = 0;
     // debug_en: walk_rays also records sample 0's primary ray of every pixel into `debug` (the reference's debug_ctx, which
     // walk_rays fills through a &Scene: hence mutable).  Octree scenes only; walk_rays throws before rendering otherwise.
     bool debug_en = false;
@@ -375,6 +381,9 @@ public:
     // ntris numbers, empty when the scene has no textures; and image k = 1.. of it (rtmi_scene_get_texture).
     void texture_uvs(const Scene& s, std::vector<float>& uvs6, std::vector<uint32_t>& tex_of_tri);
     std::vector<float> texture_image(const Scene& s, uint32_t k, uint32_t& width, uint32_t& height);
+    // The map numbers and the strength of the scene's resident copy on the first device (rtmi_scene_get_normal_maps): ntris numbers,
+    // empty when the scene has no normal maps.
+    std::vector<uint32_t> normal_maps(const Scene& s, float& strength);
     uint64_t seed;
     int device;
 
@@ -393,6 +402,10 @@ private:
     uint64_t key_tex_generation_ = 0;
     bool tex_applied_ = false;                 // the handles carry Scene::textures / uvs as of key_tex_generation_
     void apply_textures(const Scene& s);
+    uint64_t key_nmap_generation_ = 0;
+    bool nmap_applied_ = false;                // the handles carry Scene::nmap_of_tri as of key_nmap_generation_
+    bool nmap_on_device_ = false;              // ... and that is a table, not "none"
+    void apply_normal_maps(const Scene& s);
     size_t key_ntris_ = 0, key_nboxes_ = 0, key_nrefs_ = 0;
     uint32_t options_ = 0;
     rtmi_tuning_t tuning_{}, defaults_{};

@@ -297,8 +297,42 @@ class Scene:
         return images, uv, tt
 
     def clear_textures(self):
-        """Back to one colour per material: the scene is exactly the scene it was before it had textures."""
+        """Back to one colour per material: the scene is exactly the scene it was before it had textures.  Its normal maps, which
+        are images of the textures, go too."""
         _chk(_ffi.lib().rth_scene_set_textures(self.h, None, 0))
+
+    # --- normal maps: a build-defined extension (include/rtmi.h, "NORMAL MAPS OF A SCENE")
+    def set_normal_maps(self, nmap_of_tri, first=1, strength=1.0):
+        """Normal maps of triangles first, first + 1, ...: nmap_of_tri (n,) with 0 = no map, or the number 1..len(images) of the
+        texture image (set_textures) whose rgb encodes the tangent-space normal as 2 * rgb - 1; strength scales x and y of every
+        map.  Independent of tex_of_tri.  Kept with the scene; set_textures and clear_textures remove the maps."""
+        nm = np.ascontiguousarray(nmap_of_tri, dtype=np.uint32).reshape(-1)
+        if nm.size == 0:
+            raise ValueError("set_normal_maps: no entries (clear_normal_maps() removes the maps)")
+        _chk(_ffi.lib().rth_scene_set_normal_maps(self.h, _p(nm), int(first), nm.size, float(strength), 0))
+
+    def normal_maps(self):
+        """The scene's normal maps: (nmap_of_tri (ntris,) u32 with entry 0 the sentinel's, strength), or None when it has none"""
+        n = C.c_uint64(0)
+        _chk(_ffi.lib().rth_scene_normal_maps_size(self.h, C.byref(n)))
+        if n.value == 0:
+            return None
+        nm, st = np.zeros(n.value, np.uint32), C.c_float(0)
+        _chk(_ffi.lib().rth_scene_get_normal_maps(self.h, _p(nm), C.byref(st), n.value))
+        return nm, float(st.value)
+
+    def normal_map_frames(self):
+        """What a device stores per triangle for the scene's maps (rtmi_normal_map_frames): (T (ntris, 3) f32, hand (ntris,) f32 of
+        +-1, nmap (ntris,) u32 -- 0 where the triangle has no map or no tangent frame), entry 0 the sentinel's."""
+        n = self.num_tris()
+        fr = np.zeros((n, 4), np.float32)
+        _chk(_ffi.lib().rth_scene_normal_map_frames(self.h, _p(fr), n))
+        bits = np.ascontiguousarray(fr[:, 3]).view(np.uint32)
+        return np.ascontiguousarray(fr[:, :3]), np.where(bits >> 31 != 0, np.float32(-1.0), np.float32(1.0)), bits & np.uint32(0x7FFFFFFF)
+
+    def clear_normal_maps(self):
+        """No normal maps: the scene is exactly the scene it was before it had them."""
+        _chk(_ffi.lib().rth_scene_set_normal_maps(self.h, None, 0, 0, 1.0, 0))
 
     # --- Scene.boxes
     def build_bounding_box(self, orig, len2, maxdepth, minobjs, threads=0, gpu_device=None):
@@ -1518,6 +1552,18 @@ class HipRayCaster:
             images.append(im)
         return images, uv, tt
 
+    def normal_maps(self, s):
+        """The normal maps as the first device holds them (rtmi_scene_get_normal_maps): (nmap_of_tri (ntris,) u32, strength; a
+        triangle without a tangent frame reads as map 0), or None when the scene has none.  Uploads first if need be."""
+        self._config(s)
+        n = C.c_uint64(0)
+        _chk(_ffi.lib().rth_scene_normal_maps_size(s.h, C.byref(n)))
+        if n.value == 0:
+            return None
+        nm, st = np.zeros(n.value, np.uint32), C.c_float(0)
+        _chk(_ffi.lib().rth_caster_normal_maps(s.h, _p(nm), C.byref(st), n.value, C.byref(n)))
+        return nm[:n.value], float(st.value)
+
     def trace(self, s, orig4, dir4):
         """Closest hit per explicit ray (rtmi_trace): -> tri, t, face, stats."""
         o4, d4 = _f(orig4).reshape(-1, 4), _f(dir4).reshape(-1, 4)
@@ -1831,17 +1877,33 @@ def quantize(rgba):
     return out
 
 
+def normal_map_from_height(height, scale=1.0):
+    """A normal map (h, w, 3) f32 from a height field (h, w) (rtmi_normal_map_from_height): repeat-wrapped central differences,
+    n = unit(-dx, -dy, 1), rgb = n * 0.5 + 0.5.  Host code; needs no device."""
+    hh = _f(height)
+    if hh.ndim != 2:
+        raise ValueError(f"height must be (h, w), not {hh.shape}")
+    out = np.zeros(hh.shape + (3,), np.float32)
+    _chk(_ffi.lib().rth_normal_map_from_height(_p(hh), hh.shape[1], hh.shape[0], float(scale), _p(out)))
+    return out
+
+
 # ---------------------------------------------------------------- scenes of the benchmark configs
 def canonical_scene(obj_path, accel="octree", maxdepth=10, minobjs=19, teapot_surface=None, threads=0, gpu_build=None, smooth=False,
-                    texture=None):
+                    texture=None, normal_map=None):
     """The scene of raytrace/src/main.rs:116-164.  smooth (an extension): the teapot gets generated vertex normals.  texture (an
-    extension): an (h, w, 3) f32 image the teapot gets through box-projected uvs."""
+    extension): an (h, w, 3) f32 image the teapot gets through box-projected uvs.  normal_map (an extension): an (h, w, 3) f32
+    tangent-space normal map for the teapot, appended to the scene's images; the teapot is box-projected if it has no uvs yet."""
     s = Scene(with_dummy=True)
     tsurf = teapot_surface or SurfaceKind.Matte(make_color(252, 119, 0), 0.2)
     s.extend_parse_obj(obj_path, [0.0, 0.5, 5.0], 1.0, create_transform(unit([0.0, 0.3, 1.0]), to_radians(270.0)), tsurf, 0.05,
-                       normals="smooth" if smooth else None, uvs=None if texture is None else "box")
-    if texture is not None:
-        s.set_textures([texture], None, None)
+                       normals="smooth" if smooth else None, uvs=None if texture is None and normal_map is None else "box",
+                       texture=0 if texture is None else 1)
+    if texture is not None or normal_map is not None:
+        s.set_textures([im for im in (texture, normal_map) if im is not None], None, None)
+    if normal_map is not None:
+        nteapot = s.num_tris() - 1
+        s.set_normal_maps(np.full(nteapot, 1 if texture is None else 2, np.uint32))
     side = SurfaceKind.Matte(make_color(40, 40, 40), 0.2)
     s.extend_make_disk([4.0, 4.0, 7.0], unit([-0.3, -0.55, -0.5]), 2.0, 0.1, 50,
                        SurfaceKind.Reflective(0.0002, make_color(230, 230, 230), 0.7), side, -1.0)
