@@ -452,9 +452,9 @@ int rtmi_normal_map_frames(const float* corners9, const float* uvs6, const float
 int rtmi_normal_map_from_height(const float* height, uint32_t w, uint32_t h, float scale, float* rgb_out);
 
 /* Optional: the corners the triangle records were made from (`Triangle.corners`, raytrace.rs:326-337), 9 floats per
- * triangle, n = ntris (entry 0 = the sentinel's, ignored).  Only RTMI_OPT_BVH uses them: its boxes become the triangles'
- * own boxes (intersected with the bounding-radius disc's) instead of the disc's alone -- fewer boxes per ray, same hits.
- * The corners must be the ones the records came from (make_triangle, raytrace.rs:340-383); the exact modes ignore them. */
+ * triangle, n = ntris (entry 0 = the sentinel's, ignored).  Accepted and checked for size, no longer used: the BVH's boxes
+ * are the triangles' own boxes (intersected with the bounding-radius disc's) for every scene, the corners solved from the
+ * records' edge tests at scene creation, so that no render depends on the caller's corners being right. */
 int rtmi_scene_set_corners(rtmi_scene_t* scene, const float* corners9, uint64_t n);
 
 /* Option switches (all default 0): */

@@ -16,9 +16,9 @@
 // <= 4 triangles, then collapsed to 4-WIDE nodes (one 128-byte record = one cache line per node: the 4 child boxes as
 // six float4 planes + 4 links).  A triangle can only be hit in its plane inside its bounding radius (the reference's own
 // radius test, raytrace.rs:411-413), so the axis-aligned box of that disc (half-extent r*sqrt(1 - n_k^2), widened) bounds
-// every hit point and the records of rtmi_triangle_t suffice; when the caller also hands over the corners
-// (rtmi_scene_set_corners; `Triangle.corners`, raytrace.rs:326-337) the box is that disc box INTERSECTED with the
-// corners' box -- the three half-plane tests (raytrace.rs:415-424) accept points of the triangle only.  Traversal:
+// every hit point and the records of rtmi_triangle_t suffice; the box is that disc box INTERSECTED with the box of the
+// triangle's corners -- the three half-plane tests (raytrace.rs:415-424) accept points of the triangle only -- and the
+// corners are solved from the record's own edge tests (record_corners), not taken from the caller.  Traversal:
 // persistent waves, one lane = one ray, per-lane stack of links in LDS, the wave alternates INNER steps (4 slab tests,
 // the hit children pushed far-to-near so that the nearest is visited next) and LEAF steps (<= 4 triangles: four
 // branch-free plane tests, the edge part once per step for the lanes that have a candidate, as in k_trace_oct) by
@@ -49,42 +49,98 @@ struct BBox {
     }
 };
 
+// The corners of a triangle from its own record, relative to the incenter: an accepted hit point p has, for each k,
+// fl((p - incenter) . side_k) <= side_len_k (raytrace.rs:415-424), so the region of the plane the record accepts is the
+// triangle whose corners are the points of the plane where two of the three tests hold with equality.  Solved in float64
+// (Cramer).  amp[v] <- 1 / sin of the angle between the two edges that meet at corner v: a rounding slack delta in those two
+// tests moves the accepted region's corner by up to delta * amp[v], so that is what the corner's margin is scaled by.
+// false: the record is degenerate (two edge directions parallel within 1e-6, a corner that is not finite or that fails the
+// third test, i.e. the three half-planes do not bound a triangle) -- the caller keeps the disc box.
+static bool record_corners(const rtmi_triangle_t& t, double v[3][3], double amp[3]) {
+    const double n[3] = {t.norm[0], t.norm[1], t.norm[2]};
+    const double nn = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    auto cross = [](const double* a, const double* b, double* c) {
+        c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
+    };
+    for (int c = 0; c < 3; c++) {
+        const int i = c, j = (c + 1) % 3, k = (c + 2) % 3;
+        const double si[3] = {t.sides[i][0], t.sides[i][1], t.sides[i][2]}, sj[3] = {t.sides[j][0], t.sides[j][1], t.sides[j][2]};
+        const double li = t.side_lens[i], lj = t.side_lens[j];
+        const double ni = std::sqrt(si[0] * si[0] + si[1] * si[1] + si[2] * si[2]), nj = std::sqrt(sj[0] * sj[0] + sj[1] * sj[1] + sj[2] * sj[2]);
+        // x with n . x = 0, si . x = li, sj . x = lj:  x = (li (sj x n) + lj (n x si)) / (n . (si x sj))
+        double sxs[3], sjn[3], nsi[3];
+        cross(si, sj, sxs); cross(sj, n, sjn); cross(n, si, nsi);
+        const double det = n[0] * sxs[0] + n[1] * sxs[1] + n[2] * sxs[2];
+        const double scale = nn * ni * nj;
+        if (!(scale > 0.0) || !(std::fabs(det) > 1e-6 * scale)) return false;
+        amp[c] = scale / std::fabs(det);
+        for (int a = 0; a < 3; a++) {
+            v[c][a] = (li * sjn[a] + lj * nsi[a]) / det;
+            if (!std::isfinite(v[c][a])) return false;
+        }
+        const double dk = v[c][0] * t.sides[k][0] + v[c][1] * t.sides[k][1] + v[c][2] * t.sides[k][2];
+        const double nk = std::sqrt((double)t.sides[k][0] * t.sides[k][0] + (double)t.sides[k][1] * t.sides[k][1] + (double)t.sides[k][2] * t.sides[k][2]);
+        const double vl = std::sqrt(v[c][0] * v[c][0] + v[c][1] * v[c][1] + v[c][2] * v[c][2]);
+        if (!(dk <= (double)t.side_lens[k] + 1e-6 * (nk * vl + std::fabs((double)t.side_lens[k])))) return false;
+    }
+    return true;
+}
+
+// The clip box of triangle t: the disc box (below) intersected with the box of the record's own corners, each widened.
+// derived <- the corners entered the box (false: a degenerate record keeps the disc box).  false: a record is not finite.
+static bool bvh_clip_box(const rtmi_triangle_t& t, BBox& b, bool& derived, double corners[3][3]) {
+    derived = false;
+    // Every hit point the reference accepts lies in the triangle's plane (it is dir*t + orig with t solved from
+    // the plane equation) and has fl(|p - c|^2) <= r2: it is in the disc of radius r around the centroid in that
+    // plane, whose axis-aligned box has half-extent r*sqrt(1 - n_k^2) along axis k.  Widened by a margin far above
+    // the rounding of p (~2^-23 of the coordinates involved).
+    const float r = std::sqrt(t.bounding_r2) * 1.00001f;
+    const float cabs = std::fabs(t.incenter[0]) + std::fabs(t.incenter[1]) + std::fabs(t.incenter[2]);
+    const float eps = 2e-5f * (cabs + r + 1.f);
+    if (!std::isfinite(r) || r < 0.f) return false;
+    for (int k = 0; k < 3; k++) {
+        if (!std::isfinite(t.incenter[k]) || !std::isfinite(t.norm[k])) return false;
+        const float s2 = 1.f - t.norm[k] * t.norm[k];
+        const float half = r * std::sqrt(s2 > 0.f ? s2 : 0.f) * 1.0001f + eps;
+        b.lo[k] = t.incenter[k] - half;
+        b.hi[k] = t.incenter[k] + half;
+    }
+    // an accepted hit point also passes the three half-plane tests: it lies in the record's triangle up to the rounding of the
+    // tests, i.e. inside the box of its corners, each corner given the margin eps scaled by its amplification
+    double amp[3];
+    if (!record_corners(t, corners, amp)) return true;
+    BBox c;
+    c.reset();
+    for (int v = 0; v < 3; v++)
+        for (int k = 0; k < 3; k++) {
+            const double m = (double)eps * amp[v], p = (double)t.incenter[k] + corners[v][k];
+            c.lo[k] = std::min(c.lo[k], std::nextafter((float)(p - m), -FLT_MAX));
+            c.hi[k] = std::max(c.hi[k], std::nextafter((float)(p + m), FLT_MAX));
+        }
+    BBox x = b;
+    for (int k = 0; k < 3; k++) {
+        x.lo[k] = std::max(b.lo[k], c.lo[k]);
+        x.hi[k] = std::min(b.hi[k], c.hi[k]);
+        if (!(x.lo[k] <= x.hi[k])) return true;  // inconsistent record: keep the disc box
+    }
+    b = x;
+    derived = true;
+    return true;
+}
+
 // Builds over triangles 1 .. n-1 (0 is the sentinel).  Returns false when a record is not finite (then no BVH).
-// corners9: optional, 9 floats per triangle (the corners the records were made from), index 0 = the sentinel
-static bool bvh_build(const rtmi_triangle_t* tris, uint64_t ntris, BvhBuild& out, const float* corners9 = nullptr) {
+// The boxes come from the records alone (bvh_clip_box): corners a caller hands over (rtmi_scene_set_corners) are not needed
+// for them and are not trusted with them -- the hybrid pass (hybrid.hpp) relies on this BVH finding every hit.
+static bool bvh_build(const rtmi_triangle_t* tris, uint64_t ntris, BvhBuild& out) {
     out = BvhBuild();
     if (ntris < 2) return false;
     const uint32_t n = (uint32_t)(ntris - 1);
     std::vector<BBox> box(n);
     std::vector<uint32_t> idx(n);
     for (uint32_t i = 0; i < n; i++) {
-        const rtmi_triangle_t& t = tris[i + 1];
-        // Every hit point the reference accepts lies in the triangle's plane (it is dir*t + orig with t solved from
-        // the plane equation) and has fl(|p - c|^2) <= r2: it is in the disc of radius r around the centroid in that
-        // plane, whose axis-aligned box has half-extent r*sqrt(1 - n_k^2) along axis k.  Widened by a margin far above
-        // the rounding of p (~2^-23 of the coordinates involved).
-        const float r = std::sqrt(t.bounding_r2) * 1.00001f;
-        const float cabs = std::fabs(t.incenter[0]) + std::fabs(t.incenter[1]) + std::fabs(t.incenter[2]);
-        const float eps = 2e-5f * (cabs + r + 1.f);
-        if (!std::isfinite(r) || r < 0.f) return false;
-        for (int k = 0; k < 3; k++) {
-            if (!std::isfinite(t.incenter[k]) || !std::isfinite(t.norm[k])) return false;
-            const float s2 = 1.f - t.norm[k] * t.norm[k];
-            const float half = r * std::sqrt(s2 > 0.f ? s2 : 0.f) * 1.0001f + eps;
-            box[i].lo[k] = t.incenter[k] - half;
-            box[i].hi[k] = t.incenter[k] + half;
-            if (corners9) {
-                // an accepted hit point also passes the three half-plane tests (raytrace.rs:415-424): it lies in the triangle
-                // (up to the same rounding margin), i.e. inside the box of the corners
-                const float* c = corners9 + 9 * (size_t)(i + 1);
-                if (!std::isfinite(c[k]) || !std::isfinite(c[3 + k]) || !std::isfinite(c[6 + k])) return false;
-                const float clo = std::min(c[k], std::min(c[3 + k], c[6 + k])) - eps;
-                const float chi = std::max(c[k], std::max(c[3 + k], c[6 + k])) + eps;
-                box[i].lo[k] = std::max(box[i].lo[k], clo);
-                box[i].hi[k] = std::min(box[i].hi[k], chi);
-                if (box[i].lo[k] > box[i].hi[k]) { box[i].lo[k] = t.incenter[k] - half; box[i].hi[k] = t.incenter[k] + half; }  // inconsistent input: keep the disc box
-            }
-        }
+        bool derived;
+        double corners[3][3];
+        if (!bvh_clip_box(tris[i + 1], box[i], derived, corners)) return false;
         idx[i] = i;
     }
     struct Task { uint32_t lo, hi, depth; int32_t parent; int side; };
@@ -247,16 +303,25 @@ __device__ inline bool bvh_slab(float lox, float loy, float loz, float hix, floa
     return (tmin <= tmax) & (tmin <= tbest) & (tmin < INFINITY);
 }
 
-template <bool COUNT>
-__global__ void __launch_bounds__(64, 5) k_trace_bvh(DScene sc, const float4* __restrict__ bnodes, const uint4* __restrict__ bleaves,
-                                                  uint32_t root_link, const float4* __restrict__ qo, const float4* __restrict__ qd,
-                                                  DCtrl* __restrict__ ctrl, int pass, uint32_t* __restrict__ hit_tf,
-                                                  float* __restrict__ hit_t, int refill_min) {
+// HYB: the proposing walk of a hybrid pass (hybrid.hpp) -- a lane that takes a ray evaluates the sign certificate first (the
+// band HYB_KAPPA: only finiteness is needed) and the origin bound (hybrid_origin_ok, hybrid.hpp) and appends a refused ray to the pass's fallback list `fb` without walking
+// it; a ray that ends with the tie flag set (hybrid_tie_flag), or that met a passing triangle whose time is not finite, goes
+// there too, with HYB_PENDING as its record.  false: the opt-in mode's walk, instruction for instruction.
+template <bool COUNT, bool HYB>
+__device__ __forceinline__ void bvh_walk(const DScene& sc, const float4* __restrict__ bnodes, const uint4* __restrict__ bleaves,
+                                         uint32_t root_link, const float4* __restrict__ qo, const float4* __restrict__ qd,
+                                         DCtrl* __restrict__ ctrl, int pass, uint32_t* __restrict__ hit_tf,
+                                         float* __restrict__ hit_t, int refill_min, uint32_t* __restrict__ fb, bool add_rays = true, float omax = 0.f) {
     extern __shared__ uint32_t lds[];  // [level][lane] links waiting to be visited
     const int lane = threadIdx.x;
     constexpr int NT = 64;
     const uint32_t count = ctrl->count[pass];
-    if (blockIdx.x == 0 && lane == 0) atomicAdd(&ctrl->rays, (unsigned long long)count);
+    if (blockIdx.x == 0 && lane == 0) {
+        if (!HYB || add_rays) atomicAdd(&ctrl->rays, (unsigned long long)count);  // (the referee's launch: the exact walk has counted them)
+        if (HYB) atomicAdd(&ctrl->hyb[0], (unsigned long long)count);
+    }
+    bool tie = false, odd = false;                    // HYB: the lane's tie flag; it met a passing time that is not finite
+    uint32_t nref = 0u, nmiss = 0u, ntie = 0u;        // HYB (wave-uniform): refusals, misses, ties of this wave
     unsigned long long cnt[5] = {0, 0, 0, 0, 0};
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     uint32_t mode = B_IDLE;
@@ -285,6 +350,7 @@ __global__ void __launch_bounds__(64, 5) k_trace_bvh(DScene sc, const float4* __
             }
             const uint32_t base = wnext;
             wnext = min(wnext + (uint32_t)__popcll(m_idle), wend);
+            bool refused = false;
             if (!exhausted && mode == B_IDLE) {
                 const uint32_t i = base + (uint32_t)__popcll(m_idle & lt_mask);
                 if (i < wend) {
@@ -293,14 +359,21 @@ __global__ void __launch_bounds__(64, 5) k_trace_bvh(DScene sc, const float4* __
                     cur = root_link; sp = 0;
                     bt = INFINITY; btf = 0;
                     mode = (root_link >> 31) ? B_LEAF : B_INNER;
+                    if (HYB) {
+                        tie = false; odd = false;
+                        const float4 co = make_float4(r.ox, r.oy, r.oz, r.ow);
+                        refused = !hybrid_origin_ok(co, omax) || !ray_sign_certified(sc.cert, co, make_float4(r.dx, r.dy, r.dz, r.dw), nullptr, HYB_KAPPA);
+                        if (refused) { hit_tf[i] = HYB_PENDING; mode = B_IDLE; }
+                    }
                 }
             }
+            if (HYB) nref += hybrid_append(refused, ridx, fb, ctrl, pass, lane);
         }
         const unsigned long long mI = __ballot(mode == B_INNER), mL = __ballot(mode == B_LEAF);
         const int nI = __builtin_popcount((uint32_t)mI) + __builtin_popcount((uint32_t)(mI >> 32));
         const int nL = __builtin_popcount((uint32_t)mL) + __builtin_popcount((uint32_t)(mL >> 32));
         const bool stepI = nI >= nL;
-        bool pop = false;
+        bool pop = false, done = false;  // (done, HYB: the lane's ray ended in this iteration)
         if (stepI) {
             // ================================================= INNER step: the node's 4 children
             if (mode == B_INNER) {
@@ -354,6 +427,12 @@ __global__ void __launch_bounds__(64, 5) k_trace_bvh(DScene sc, const float4* __
                     const bool edge = (d0 > e3.x) | (d1 > e3.y) | (d2 > e3.z);
                     const uint32_t face = (pden > 0.f ? 1u : 0u) | (edge ? 2u : 0u);
                     // finite hit times only (see top); strict `<` of the index-order scan: equal times keep the lower index
+                    if (HYB) {
+                        // (a certified ray has no such time; if one turns up all the same, the proof does not cover the ray)
+                        const bool fin = fabsf(pt) < INFINITY;
+                        if (inside & fin) tie = hybrid_tie_flag(tie, pt, ptri, bt, btf & 0x3FFFFFFFu);
+                        odd |= inside & !fin;
+                    }
                     const bool take = inside & (fabsf(pt) < INFINITY) & ((pt < bt) | ((pt == bt) & (ptri < (btf & 0x3FFFFFFFu))));
                     bt = take ? pt : bt;
                     btf = take ? (ptri | (face << 30)) : btf;
@@ -387,10 +466,16 @@ __global__ void __launch_bounds__(64, 5) k_trace_bvh(DScene sc, const float4* __
                 cur = lds[sp * NT + lane];
                 mode = (cur >> 31) ? B_LEAF : B_INNER;
             } else {
-                hit_tf[ridx] = btf;
+                // (HYB: a ray that ties is not proposed; k_oct_verify confirms the others that hit)
+                hit_tf[ridx] = (HYB && (tie | odd)) ? HYB_PENDING : btf;
                 hit_t[ridx] = btf ? bt : 0.f;
                 mode = B_IDLE;
+                done = true;
             }
+        }
+        if (HYB) {  // (outside the divergent branch: the append is a wave operation)
+            ntie += hybrid_append(done & (tie | odd), ridx, fb, ctrl, pass, lane);
+            nmiss += (uint32_t)__popcll(__ballot(done & !(tie | odd) & (btf == 0u)));
         }
     }
     if (COUNT) {
@@ -398,6 +483,27 @@ __global__ void __launch_bounds__(64, 5) k_trace_bvh(DScene sc, const float4* __
         for (int k = 0; k < 5; k++)
             if (cnt[k]) atomicAdd(&ctrl->counters[k], cnt[k]);
     }
+    if (HYB && lane == 0) {
+        if (nref) atomicAdd(&ctrl->hyb[1], (unsigned long long)nref);
+        if (nmiss) atomicAdd(&ctrl->hyb[2], (unsigned long long)nmiss);
+        if (ntie) atomicAdd(&ctrl->hyb[3], (unsigned long long)ntie);
+        if (nref + ntie) atomicAdd(&ctrl->hyb[8], (unsigned long long)(nref + ntie));
+    }
+}
+
+template <bool COUNT>
+__global__ void __launch_bounds__(64, 5) k_trace_bvh(DScene sc, const float4* __restrict__ bnodes, const uint4* __restrict__ bleaves,
+                                                  uint32_t root_link, const float4* __restrict__ qo, const float4* __restrict__ qd,
+                                                  DCtrl* __restrict__ ctrl, int pass, uint32_t* __restrict__ hit_tf,
+                                                  float* __restrict__ hit_t, int refill_min) {
+    bvh_walk<COUNT, false>(sc, bnodes, bleaves, root_link, qo, qd, ctrl, pass, hit_tf, hit_t, refill_min, nullptr);
+}
+// The proposing walk of a hybrid pass: k_trace_bvh's launch plus the pass's fallback list
+__global__ void __launch_bounds__(64, 5) k_hybrid_bvh(DScene sc, const float4* __restrict__ bnodes, const uint4* __restrict__ bleaves,
+                                                   uint32_t root_link, const float4* __restrict__ qo, const float4* __restrict__ qd,
+                                                   DCtrl* __restrict__ ctrl, int pass, uint32_t* __restrict__ hit_tf,
+                                                   float* __restrict__ hit_t, int refill_min, uint32_t* __restrict__ fb, int add_rays, float omax) {
+    bvh_walk<false, true>(sc, bnodes, bleaves, root_link, qo, qd, ctrl, pass, hit_tf, hit_t, refill_min, fb, add_rays != 0, omax);
 }
 
 }  // namespace rtmi

@@ -106,6 +106,7 @@ struct CertStats {
 
 #define RTMI_MAX_PASSES 32
 #define RTMI_MAX_STREAMS 4  // interleaved sub-tiles of one tile, each on its own internal stream
+#define RTMI_NHYB 12        // statistics of the hybrid passes (hybrid.hpp: what each entry counts)
 #define RTMI_NDBG 52        // step statistics of the counting build (trace_oct.hpp: what each entry counts)
 struct DCtrl {
     uint32_t count[RTMI_MAX_PASSES + 1];  // rays queued for pass k
@@ -118,6 +119,10 @@ struct DCtrl {
     unsigned long long rays;              // sum of count[] (the "Rays" statistic)
     unsigned long long counters[5];       // box_tests tri_tests full_tests nodes leaves
     unsigned long long dbg[RTMI_NDBG];    // step statistics of the counting build (tools/step_stats.py)
+    // hybrid passes (hybrid.hpp): rays on the fallback list of pass k, the exact walk's cursors over it, the statistics
+    uint32_t fbcount[RTMI_MAX_PASSES + 1];
+    uint32_t fbhead[RTMI_MAX_PASSES + 1][8];
+    unsigned long long hyb[RTMI_NHYB];
 };
 
 // The slow-path queue of one stream's batch.  A ray whose unit direction has an exactly-zero component skips that axis'
@@ -394,6 +399,7 @@ __global__ void __launch_bounds__(256) k_trace(DScene sc, const float4* __restri
 #include "build_octree.hpp"
 #include "shade.hpp"
 #include "trace_oct.hpp"
+#include "hybrid.hpp"
 #include "bvh_fast.hpp"
 #include "denoise.hpp"
 #include "ao.hpp"
@@ -1224,6 +1230,10 @@ struct Work {
     DevBuf<float4> qo[2], qd[2], scol;
     DevBuf<uint32_t> qpath[2], hit_tf;
     DevBuf<float> hit_t;
+    // hybrid passes (hybrid.hpp): the fallback list of the pass in flight, one entry per hit record, and the scratch hit
+    // records a counting launch runs the hybrid into (allocated by the first such launch)
+    DevBuf<uint32_t> fb, ref_tf;
+    DevBuf<float> ref_t;
     DevBuf<uint16_t> mstack;
     DevBuf<float4> cstack;  // the colour stack of the k_shade*_tex kernels: allocated only for calls on a textured scene
     DevBuf<DCtrl> ctrl;
@@ -1237,7 +1247,7 @@ struct Work {
     std::vector<hipEvent_t> pass_ev;  // start/stop of the trace kernel of every pass
     void release() {
         for (int k = 0; k < 2; k++) { qo[k].release(); qd[k].release(); qpath[k].release(); }
-        scol.release(); hit_tf.release(); hit_t.release(); mstack.release(); cstack.release(); ctrl.release();
+        scol.release(); hit_tf.release(); hit_t.release(); fb.release(); ref_tf.release(); ref_t.release(); mstack.release(); cstack.release(); ctrl.release();
         for (int k = 0; k < 2; k++) if (ev[k]) { (void)hipEventDestroy(ev[k]); ev[k] = nullptr; }
         for (hipEvent_t e : pass_ev) (void)hipEventDestroy(e);
         pass_ev.clear();
@@ -1284,7 +1294,7 @@ struct rtmi_scene {
     DevBuf<float4> nmaptri;
     NmapTab nmaptab{};
     bool has_nmap = false;
-    std::vector<rtmi_triangle_t> htris;  // the records (host copy): the fast-mode BVH is rebuilt from them when corners arrive
+    std::vector<rtmi_triangle_t> htris;  // the records (host copy): the BVH is built from them
     DevBuf<uint4> fnodes, oblocks, ocull;  // (fnodes: the node records, then the node cull records)
     DevBuf<uint32_t> wlinks, cert;
     std::vector<uint32_t> leaf_box;  // OctForm::leafbox: leaf ids of k_trace_record -> box index
@@ -1397,6 +1407,9 @@ struct rtmi_scene {
     int block_cull = 1;          // k_trace_oct skips reference blocks by their cull records (RTMI_BLOCK_CULL=0: off, no records)
     int block_cull_n = 4;        // cull records a LEAF step of k_trace_oct reads, 2..4 (experiments: RTMI_BLOCK_CULL_N)
     CertStats cert_stats{};      // the sign certificate's table (rtmi_debug_cert_stats)
+    int hybrid = 1;              // bounce passes propose hits with the BVH and confirm them against the octree (RTMI_HYBRID=0: off; hybrid.hpp)
+    float hybrid_omax = 0.f;     // the largest |o|_1 of a ray a hybrid pass proposes a hit for (hybrid_origin_max, hybrid.hpp)
+    uint32_t nfn = 0;            // inner records of the octree form (the bound of k_oct_verify's descent)
     int node_cull = 1;           // k_trace_oct skips subtrees by their node cull records (RTMI_NODE_CULL=0: off, no records)
     uint64_t node_cull_records = 0;  // node cull records built (0: none) and the seconds that took (rtmi_debug_node_cull_stats)
     double node_cull_seconds = 0.0;
@@ -1440,11 +1453,11 @@ static Rccl* rccl_api() {
     return api.ok ? &api : nullptr;
 }
 
-// (Re)build the fast-mode BVH (bvh_fast.hpp) from the scene's triangle records and, when given, their corners.
-static int upload_bvh(rtmi_scene* s, const float* corners9) {
+// Build the BVH (bvh_fast.hpp) of the opt-in fast mode and of the hybrid passes from the scene's triangle records.
+static int upload_bvh(rtmi_scene* s) {
     s->bvh_ok = false;
     BvhBuild bb;
-    if (s->htris.size() >= (1u << 26) || !bvh_build(s->htris.data(), s->htris.size(), bb, corners9)) return RTMI_OK;  // no BVH: RTMI_OPT_BVH is then ignored
+    if (s->htris.size() >= (1u << 26) || !bvh_build(s->htris.data(), s->htris.size(), bb)) return RTMI_OK;  // no BVH: RTMI_OPT_BVH is then ignored, no hybrid passes
     if (bb.wide.empty()) bb.wide.resize(8, make_float4(0.f, 0.f, 0.f, 0.f));
     auto up = [&](auto& buf, const auto& host) -> hipError_t {
         hipError_t e = buf.ensure(std::max<size_t>(host.size(), 1));
@@ -1455,6 +1468,14 @@ static int upload_bvh(rtmi_scene* s, const float* corners9) {
     if (be == hipSuccess) be = up(s->bleaves, bb.leaves);
     if (be != hipSuccess) return fail(hip_code(be), std::string("scene upload (BVH): ") + hipGetErrorString(be));
     s->bvh_root = bb.root_link;
+    {
+        float m = FLT_MAX;  // the smallest |c|_1 + r over the triangles (the sentinel aside)
+        for (size_t i = 1; i < s->htris.size(); i++) {
+            const rtmi_triangle_t& t = s->htris[i];
+            m = std::min(m, ((std::fabs(t.incenter[0]) + std::fabs(t.incenter[1])) + std::fabs(t.incenter[2])) + std::sqrt(t.bounding_r2));
+        }
+        s->hybrid_omax = hybrid_origin_max(m);
+    }
     s->bvh_lds = (size_t)(3 * bb.depth + 2) * 64 * 4;  // an INNER step leaves at most 3 links waiting per level
     int nb = 0;
     if (s->bvh_lds <= 64 * 1024 &&
@@ -1945,6 +1966,7 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
     if (const char* v = getenv("RTMI_BLOCK_CULL")) s->block_cull = strcmp(v, "0") != 0;
     s->block_cull_n = (int)std::min<size_t>(std::max<size_t>(env_size("RTMI_BLOCK_CULL_N", 4), 2), 4);
     if (const char* v = getenv("RTMI_NODE_CULL")) s->node_cull = strcmp(v, "0") != 0;
+    if (const char* v = getenv("RTMI_HYBRID")) s->hybrid = strcmp(v, "0") != 0;
     if (const char* v = getenv("RTMI_PRIMARY_NODE_CULL")) s->primary_node_cull = strcmp(v, "0") != 0;
     if (const char* v = getenv("RTMI_OCCLUDED_ANYHIT")) s->occl_from_hits = strcmp(v, "0") == 0;
     if (const char* v = getenv("RTMI_DENOISE_LDS_STEP")) s->dn_lds_max_step = std::min<uint32_t>((uint32_t)strtoul(v, nullptr, 10), DN_LDS_MAX_STEP);
@@ -1974,6 +1996,7 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
     if (e == hipSuccess) e = up(s->tedge, he);
     if (e == hipSuccess) e = up(s->mats, hm);
     s->octree = !hfn.empty();
+    s->nfn = (uint32_t)(hfn.size() / 2);
     s->root_is_leaf = boxes[0].is_leaf != 0;
     s->why_generic = why;
     if (e == hipSuccess && s->octree) e = up(s->fnodes, hfn);
@@ -2058,9 +2081,9 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
                 s->oct_blocks_per_cu = nb;
         }
     }
-    s->htris.assign(tris, tris + ntris);  // rtmi_scene_set_corners rebuilds the fast-mode BVH from them
+    s->htris.assign(tris, tris + ntris);
     {   // fast-mode BVH (cheap: binned SAH over the triangles' disc boxes); absent when a record is not finite
-        const int rc = upload_bvh(s, nullptr);
+        const int rc = upload_bvh(s);
         if (rc != RTMI_OK) return rc;
     }
     own.s = nullptr;
@@ -2663,7 +2686,9 @@ int rtmi_scene_set_corners(rtmi_scene_t* s, const float* corners9, uint64_t n) {
     RTMI_GUARD_BEGIN
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(hipDeviceSynchronize());  // no render of this scene is in flight (one call at a time per handle)
-    return upload_bvh(s, corners9);
+    // The BVH's boxes come from the records' own edge tests since the hybrid passes rely on them (bvh_clip_box, bvh_fast.hpp):
+    // the corners no longer enter them, and the tree built at scene creation stays.
+    return RTMI_OK;
     RTMI_GUARD_END
 }
 
@@ -2696,6 +2721,7 @@ static int ensure_workspace(Work& w, size_t cap, uint32_t maxdepth) {
     HIPCHK(w.scol.ensure(cap));
     HIPCHK(w.hit_tf.ensure(cap));
     HIPCHK(w.hit_t.ensure(cap));
+    HIPCHK(w.fb.ensure(cap));
     HIPCHK(w.mstack.ensure(cap * (size_t)maxdepth));
     HIPCHK(w.sqo.ensure(RTMI_SLOW_CAP)); HIPCHK(w.sqd.ensure(RTMI_SLOW_CAP));
     HIPCHK(w.sqpath.ensure(RTMI_SLOW_CAP)); HIPCHK(w.sqbounce.ensure(RTMI_SLOW_CAP));
@@ -2764,8 +2790,28 @@ static const ViewsWalkKernel path_views_variant[3][2][2] = {RTMI_COUNT_FAST(k_pa
 
 static void launch_trace(rtmi_scene* s, Work& w, hipStream_t st, const float4* qo, const float4* qd, int pass, bool count, hipEvent_t stop) {
     // `stop` is recorded right after the closest-hit kernel, so that the event pair of the caller times exactly
-    // the kernel rocprofv3 lists as k_trace_oct / k_trace_linear / k_trace
-    if ((s->options & RTMI_OPT_BVH) && s->bvh_ok) {
+    // the kernel rocprofv3 lists as k_trace_oct / k_trace_linear / k_trace (a hybrid pass: its three launches)
+    // Hybrid pass (hybrid.hpp): an exact octree with a direction table, a usable BVH, none of the options that select another
+    // walk, a workspace with a fallback list as long as its hit records.  A counting launch walks the octree as ever and then
+    // runs the hybrid into scratch records for the referee.
+    const bool hybrid = s->hybrid && s->octree && s->d.cert && s->bvh_ok && !s->root_is_leaf &&
+                        !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_FAST | RTMI_OPT_BVH)) && w.fb.p && w.fb.n >= w.hit_tf.n;
+    auto launch_hybrid = [&](uint32_t* tf, float* ht, int add_rays) {
+        const dim3 grid((unsigned)(s->num_cu * s->bvh_blocks_per_cu)), block(64);
+        hipLaunchKernelGGL(k_hybrid_bvh, grid, block, s->bvh_lds, st, s->d, s->bnodes.p, s->bleaves.p, s->bvh_root, qo, qd, w.ctrl.p, pass, tf, ht,
+                           (int)(pass == 0 ? s->tune.refill_min0 : s->tune.refill_min), w.fb.p, add_rays, s->hybrid_omax);
+        hipLaunchKernelGGL(k_oct_verify, dim3((unsigned)(s->num_cu * 8)), dim3(256), 0, st, s->d, s->nfn, qo, qd, w.ctrl.p, pass, tf, ht, w.fb.p);
+        OctArgs a{};
+        a.qo = qo; a.qd = qd; a.hit_tf = tf; a.hit_t = ht; a.pass = pass;
+        a.vote_s = pass == 0 ? s->vote[0] : s->vote[2]; a.vote_l = pass == 0 ? s->vote[1] : s->vote[3];
+        a.bcn = s->block_cull_n;
+        hipLaunchKernelGGL(k_trace_oct_list, oct_grid(s), dim3(64), oct_launch_lds(s, false), st, s->d, a, w.ctrl.p,
+                           (int)(pass == 0 ? s->tune.refill_min0 : s->tune.refill_min),
+                           (int)(s->tune.xcd_aware % 3u), (const uint32_t*)w.fb.p);
+    };
+    if (hybrid && !count) {
+        launch_hybrid(w.hit_tf.p, w.hit_t.p, 1);
+    } else if ((s->options & RTMI_OPT_BVH) && s->bvh_ok) {
         const dim3 grid((unsigned)(s->num_cu * s->bvh_blocks_per_cu)), block(64);
         hipLaunchKernelGGL(count ? k_trace_bvh<true> : k_trace_bvh<false>, grid, block, s->bvh_lds, st, s->d, s->bnodes.p, s->bleaves.p,
                            s->bvh_root, qo, qd, w.ctrl.p, pass, w.hit_tf.p, w.hit_t.p, (int)(pass == 0 ? s->tune.refill_min0 : s->tune.refill_min));
@@ -2789,6 +2835,13 @@ static void launch_trace(rtmi_scene* s, Work& w, hipStream_t st, const float4* q
                            w.hit_tf.p, w.hit_t.p);
     }
     (void)hipEventRecord(stop, st);
+    if (hybrid && count && w.ref_tf.ensure(w.hit_tf.n) == hipSuccess && w.ref_t.ensure(w.hit_tf.n) == hipSuccess) {
+        // the referee of the counting build: the same pass once more through the hybrid, into scratch records, and every record
+        // the hybrid stands by against the exact walk's (the queue's "Rays" were counted by the walk above, not again)
+        launch_hybrid(w.ref_tf.p, w.ref_t.p, 0);
+        hipLaunchKernelGGL(k_hybrid_referee, dim3((unsigned)(s->num_cu * 8)), dim3(256), 0, st, w.ctrl.p, pass, w.hit_tf.p, w.hit_t.p, w.ref_tf.p,
+                           w.ref_t.p);
+    }
     if (s->d.nspheres)  // analytic spheres: a flat list against every ray, after the tree (not part of the timed trace kernel)
         hipLaunchKernelGGL(k_trace_spheres, dim3((unsigned)(s->num_cu * 8)), dim3(256), 0, st, s->d, qo, qd, w.ctrl.p, pass, w.hit_tf.p, w.hit_t.p);
 }
@@ -5554,6 +5607,115 @@ int rtmi_debug_node_cull_kappa(const rtmi_box_t* boxes, uint64_t nboxes, const u
     }
     return RTMI_OK;
     RTMI_GUARD_END
+}
+
+// Test hooks of the hybrid passes (not in rtmi.h; hybrid.hpp, bvh_fast.hpp).  None needs a device.
+// rtmi_debug_hybrid_verify: the tree, plane records and rays as rtmi_debug_node_cull takes them, plus per ray a proposed hit
+// (t, tri).  cert[i] <- ray i holds the certificate in the band k_hybrid_bvh uses and its origin is within the bound
+// (*omax_out <- the scene's bound, may be NULL); out[i] <- what the guided descent and the
+// list scan of k_oct_verify answer for the proposal (HV_OK = 0: confirmed; 1 absent child, 2 no collision, 3 tmin >= t, 4 the
+// leaf's list lacks the triangle, 5 out of bounds), evaluated with the kernel's own function on the octree form
+// rtmi_scene_create would upload.  A ray is accepted when cert[i] != 0 and out[i] == 0.
+int rtmi_debug_hybrid_verify(const rtmi_box_t* boxes, uint64_t nboxes, const uint32_t* tri_refs, uint64_t nrefs, uint64_t ntris,
+                             const float* recs, const float* rays, uint64_t n, uint32_t G, const float* t, const uint32_t* tri,
+                             uint8_t* cert, uint8_t* out, float* omax_out) {
+    if (!boxes || nboxes < 1 || !recs || ntris < 1 || (nrefs > 0 && !tri_refs) || (n > 0 && (!rays || !t || !tri || !cert || !out)) || G < 8 ||
+        G > 1024)
+        return fail(RTMI_ERR_INVALID, "NULL argument or G out of range");
+    if (nboxes >= (1ull << 32) || nrefs >= (1ull << 32)) return fail(RTMI_ERR_UNSUPPORTED, "tree too large for 32-bit indices");
+    RTMI_GUARD_BEGIN
+    std::vector<uint32_t> depth;
+    uint32_t max_inner_depth = 0;
+    const std::string bad = validate_tree(boxes, nboxes, tri_refs, nrefs, ntris, depth, max_inner_depth);
+    if (!bad.empty()) return fail(RTMI_ERR_INVALID, bad);
+    OctForm f;
+    build_oct_form(boxes, nboxes, tri_refs, ntris, depth, f);
+    if (f.fn.empty()) return fail(RTMI_ERR_UNSUPPORTED, f.why);
+    std::vector<float4> hp(2 * ntris);
+    memcpy(hp.data(), recs, ntris * 8 * sizeof(float));
+    std::vector<uint32_t> hcert;
+    CertStats st{};
+    if (!build_ray_cert(hp.data(), ntris, G, SIZE_MAX, hcert, st)) return fail(RTMI_ERR_UNSUPPORTED, "direction table too large");
+    if (f.wl.empty()) f.wl.push_back(0u);
+    float m = FLT_MAX;
+    for (uint64_t k = 1; k < ntris; k++)
+        m = std::min(m, ((std::fabs(recs[8 * k]) + std::fabs(recs[8 * k + 1])) + std::fabs(recs[8 * k + 2])) + std::sqrt(recs[8 * k + 3]));
+    const float omax = hybrid_origin_max(m);
+    if (omax_out) *omax_out = omax;
+    for (uint64_t i = 0; i < n; i++) {
+        const float* v = rays + 8 * i;
+        const float4 o = make_float4(v[0], v[1], v[2], v[3]), d = make_float4(v[4], v[5], v[6], v[7]);
+        cert[i] = (hybrid_origin_ok(o, omax) && ray_sign_certified(hcert.data(), o, d, nullptr, HYB_KAPPA)) ? 1 : 0;
+        out[i] = (tri[i] == 0u || tri[i] >= ntris) ? (uint8_t)HV_BOUNDS
+                                                   : (uint8_t)hybrid_verify(f.fn.data(), f.ob.data(), f.wl.data(), (uint32_t)(f.fn.size() / 2),
+                                                                            (uint32_t)f.ob.size(), max_inner_depth + 1, boxes[0].len2, o, d, t[i], tri[i]);
+    }
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+// rtmi_debug_hybrid_slab: n child boxes as (parent centre xyz, the children's half edge hc, octant) and n rays (o.xyz,
+// d.xyz): tmin[i], hit[i] <- hybrid_child_slab with 1 / d as make_rayk forms it.
+int rtmi_debug_hybrid_slab(const float* parent4, const uint32_t* oct, const float* rays6, uint64_t n, float* tmin, uint8_t* hit) {
+    if (n > 0 && (!parent4 || !oct || !rays6 || !tmin || !hit)) return fail(RTMI_ERR_INVALID, "NULL argument");
+    for (uint64_t i = 0; i < n; i++) {
+        const float* p = parent4 + 4 * i;
+        const float* r = rays6 + 6 * i;
+        hit[i] = hybrid_child_slab(p[0], p[1], p[2], p[3], oct[i] & 7u, r[0], r[1], r[2], 1.f / r[3], 1.f / r[4], 1.f / r[5], tmin[i]) ? 1 : 0;
+    }
+    return RTMI_OK;
+}
+// rtmi_debug_hybrid_tie: a sequence of n passing triangles (t, tri) as a lane of k_hybrid_bvh meets them: flag <- the tie
+// flag at the end (hybrid_tie_flag and the kernel's take rule), best_tri / best_t <- the lane's best.
+int rtmi_debug_hybrid_tie(const float* t, const uint32_t* tri, uint64_t n, uint8_t* flag, uint32_t* best_tri, float* best_t) {
+    if ((n > 0 && (!t || !tri)) || !flag || !best_tri || !best_t) return fail(RTMI_ERR_INVALID, "NULL argument");
+    bool tie = false;
+    float bt = INFINITY;
+    uint32_t btri = 0u;
+    for (uint64_t i = 0; i < n; i++) {
+        tie = hybrid_tie_flag(tie, t[i], tri[i], bt, btri);
+        const bool take = (t[i] < bt) | ((t[i] == bt) & (tri[i] < btri));  // bvh_walk's `take` for a finite time
+        bt = take ? t[i] : bt;
+        btri = take ? tri[i] : btri;
+    }
+    *flag = tie ? 1 : 0; *best_tri = btri; *best_t = bt;
+    return RTMI_OK;
+}
+// rtmi_debug_record_boxes: n triangle records (the first 20 floats of rtmi_triangle_t each: incenter, norm, bounding_r2, sides,
+// side_lens, edge_thickness).  corners9[i] <- the corners solved from record i's edge tests (absolute; zeros when the record
+// is degenerate), box6[i] <- the BVH's clip box (lo.xyz, hi.xyz), derived[i] <- 1 when the corners entered it, 0 when it is
+// the disc box, 2 when the record is not finite (no BVH).
+int rtmi_debug_record_boxes(const float* recs20, uint64_t n, float* corners9, float* box6, uint8_t* derived) {
+    if (n > 0 && (!recs20 || !corners9 || !box6 || !derived)) return fail(RTMI_ERR_INVALID, "NULL argument");
+    for (uint64_t i = 0; i < n; i++) {
+        rtmi_triangle_t t{};
+        memcpy(&t, recs20 + 20 * i, 20 * sizeof(float));
+        BBox b;
+        b.reset();
+        bool der = false;
+        double c[3][3] = {};
+        const bool ok = bvh_clip_box(t, b, der, c);
+        for (int v = 0; v < 3; v++)
+            for (int k = 0; k < 3; k++) corners9[9 * i + 3 * v + k] = der ? (float)((double)t.incenter[k] + c[v][k]) : 0.f;
+        for (int k = 0; k < 3; k++) { box6[6 * i + k] = b.lo[k]; box6[6 * i + 3 + k] = b.hi[k]; }
+        derived[i] = !ok ? 2 : (der ? 1 : 0);
+    }
+    return RTMI_OK;
+}
+// rtmi_debug_hybrid_counters: DCtrl::hyb of the scene's last render or trace call, summed over its streams (hybrid.hpp: what
+// each of the RTMI_NHYB = 12 entries counts).  on <- 1 when the SCENE qualifies for hybrid passes; a launch on a workspace without a
+// fallback list (the shadow walks' own workspace) still takes the one k_trace_oct launch.
+int rtmi_debug_hybrid_counters(rtmi_scene_t* s, unsigned long long* out12, int* on) {
+    if (!s || !out12) return fail(RTMI_ERR_INVALID, "NULL argument");
+    HIPCHK(hipSetDevice(s->device));
+    memset(out12, 0, RTMI_NHYB * sizeof(unsigned long long));
+    for (int k = 0; k < RTMI_MAX_STREAMS; k++) {
+        DCtrl h;
+        HIPCHK(hipMemcpy(&h, s->w[k].ctrl.p, sizeof(DCtrl), hipMemcpyDeviceToHost));
+        for (int j = 0; j < RTMI_NHYB; j++) out12[j] += h.hyb[j];
+    }
+    if (on) *on = (s->hybrid && s->octree && s->d.cert && s->bvh_ok && !s->root_is_leaf &&
+                   !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_FAST | RTMI_OPT_BVH))) ? 1 : 0;
+    return RTMI_OK;
 }
 
 int rtmi_make_triangles(int device, const float* corners9_host, uint64_t n, const rtmi_triangle_t* proto, rtmi_triangle_t* out_host) {

@@ -445,7 +445,10 @@ __device__ __attribute__((noinline)) bool primary_ray_certified(const uint32_t* 
 // Samp::VIEWS each pixel's camera and seed from `vt`, pixel_key)
 // PNCULL (W_PRIMARY): the node cull of the primary kernels (k_path_primary*_cull); false: the walk without it, instruction for
 // instruction
-template <bool COUNT, bool FAST, int MODE, Samp S = Samp::FRAME, bool PNCULL = false>
+// VIA (W_TRACE): the launch drains the fallback list of the hybrid pass `a.pass` (hybrid.hpp) instead of the pass's queue: `list`
+// holds the queue indices of its rays, count and cursors are DCtrl::fbcount / fbhead, the result goes to the ray's own index, and
+// the rays -- which the queue's launch counted -- are not added to "Rays".  false: the walk without it, instruction for instruction
+template <bool COUNT, bool FAST, int MODE, Samp S = Samp::FRAME, bool PNCULL = false, bool VIA = false>
 __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCtrl* __restrict__ ctrl, uint32_t* __restrict__ lds,
                                          int refill_min, int xcd_aware, const RecArgs& rec = RecArgs{},
                                          const uint32_t* __restrict__ list = nullptr, const ViewTab& vt = ViewTab{},
@@ -458,9 +461,9 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
     // which queue of the control block this launch drains: W_TRACE pass `pass`, W_PRIMARY the implicit queue of all paths
     // of the batch (slot 0); W_SLOW does not use it (its launch drains a range of the slow-path queue)
     const int pass = QUEUE ? a.pass : 0;
-    const uint32_t count = MODE == W_PRIMARY ? a.npaths : (MODE == W_SLOW ? ctrl->shi[a.slow_k] : ctrl->count[pass]);
+    const uint32_t count = MODE == W_PRIMARY ? a.npaths : (MODE == W_SLOW ? ctrl->shi[a.slow_k] : (VIA ? ctrl->fbcount[pass] : ctrl->count[pass]));
     // "Rays": every queued ray of this launch (the slow path counts its rays one by one, below)
-    if (MODE != W_SLOW && blockIdx.x == 0 && lane == 0) atomicAdd(&ctrl->rays, (unsigned long long)count);
+    if (MODE != W_SLOW && !VIA && blockIdx.x == 0 && lane == 0) atomicAdd(&ctrl->rays, (unsigned long long)count);
     const float4* __restrict__ qo = MODE == W_SLOW ? a.slow.o : a.qo;
     const float4* __restrict__ qd = MODE == W_SLOW ? a.slow.d : a.qd;
     if (MODE == W_SLOW) refill_min = 1;
@@ -698,7 +701,7 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                     const uint32_t x = (home + tries) % nranges;
                     hi = (uint32_t)(((unsigned long long)count * (x + 1)) / nranges);
                     const uint32_t lo = (uint32_t)(((unsigned long long)count * x) / nranges);
-                    if (lane == 0) base = lo + atomicAdd(&ctrl->xhead[pass][x], n);
+                    if (lane == 0) base = lo + atomicAdd(VIA ? &ctrl->fbhead[pass][x] : &ctrl->xhead[pass][x], n);
                     base = __builtin_amdgcn_readfirstlane(base);
                     if (base < hi) break;
                     if (++tries == nranges) { exhausted = true; break; }
@@ -721,8 +724,8 @@ __device__ __forceinline__ void oct_walk(const DScene& sc, const OctArgs& a, DCt
                             // samples of the pixel would wait for it -> its path is traced by k_path_slow
                             if (a.slow.cap && has_zero_component(nd.x, nd.y, nd.z) && slow_push(a.slow, ctrl, no, nd, i, 0u)) start = false;
                         } else {
-                            ridx = i;
-                            r = make_rayk(qo[i], qd[i]);
+                            ridx = VIA ? list[i] : i;
+                            r = make_rayk(qo[ridx], qd[ridx]);
                             // the root box itself is never slab-tested (raytrace.rs:1272 calls
                             // get_object_intersection_for_ray on it directly): start with its frame
                             fnode = 0; fw = 0; ft = 0.f; lvl = 0;
@@ -1298,6 +1301,12 @@ template <bool COUNT, bool FAST>
 __global__ void __launch_bounds__(64, RTMI_TRACE_WAVES) k_trace_oct(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min, int xcd_aware) {
     extern __shared__ uint32_t lds[];
     oct_walk<COUNT, FAST, W_TRACE>(sc, a, ctrl, lds, refill_min, xcd_aware);
+}
+// The exact walk over the fallback list of a hybrid pass (hybrid.hpp): k_trace_oct's walk, its rays taken through `list`
+__global__ void __launch_bounds__(64, RTMI_TRACE_WAVES) k_trace_oct_list(DScene sc, OctArgs a, DCtrl* __restrict__ ctrl, int refill_min, int xcd_aware,
+                                                                         const uint32_t* __restrict__ list) {
+    extern __shared__ uint32_t lds[];
+    oct_walk<false, false, W_TRACE, Samp::FRAME, false, true>(sc, a, ctrl, lds, refill_min, xcd_aware, RecArgs{}, list);
 }
 // 6 waves per SIMD = at most 80 VGPRs, the occupancy k_trace_oct has (24 waves per CU is where this walk peaks, DESIGN.md
 // 4.1).  The exchange step (Philox + shading with the whole traversal state live) needs ~95; with the cap hipcc keeps the

@@ -1045,6 +1045,14 @@ int rth_debug_node_cull_stats(rth_scene_t* s, unsigned long long* out) {
     return guarded([&] { rtmi_debug_node_cull_stats(caster_of(s).resident(s->scene), out); });
 }
 
+// the statistics of the hybrid passes (device/hybrid.hpp) of the last batch of the resident scene's last call
+int rtmi_debug_hybrid_counters(rtmi_scene_t* s, unsigned long long* out12, int* on);
+int rth_debug_hybrid_counters(rth_scene_t* s, unsigned long long* out12, int* on) {
+    int rc = 0;
+    const int g = guarded([&] { rc = rtmi_debug_hybrid_counters(caster_of(s).resident(s->scene), out12, on); });
+    return g ? g : rc;
+}
+
 void rth_quantize(const float* rgba, uint64_t npixels, uint8_t* rgb) {
     quantize_rgb8(reinterpret_cast<const Color*>(rgba), (size_t)npixels, rgb);
 }

@@ -77,6 +77,18 @@ print(f"node cull (k_trace_oct, RTMI_NODE_CULL={os.environ.get('RTMI_NODE_CULL',
       f"certified lanes outside a missed subtree, node box missed by the half-line {d[34]} ({d[34] / max(d[33], 1):.3f}); inside "
       f"missed subtrees: {d[35]} SELECT lane-steps ({d[35] / max(d[1], 1):.3f} of all), {d[36]} leaf visits "
       f"({d[36] / max(d[12], 1):.3f} of all); violations {d[37]} (must be 0)")
+# DCtrl::hyb: the hybrid bounce passes (hybrid.hpp; RTMI_HYBRID=0 or no direction table: all 0).  The counting launch walks the
+# octree as ever and runs the hybrid into scratch records; violations = records the hybrid stands by that differ from the walk's.
+hy, hon = (C.c_ulonglong * 12)(), C.c_int(0)
+lib.rth_debug_hybrid_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+if lib.rth_debug_hybrid_counters(scene.h, hy, C.byref(hon)) == 0:
+    h = list(hy)
+    n = max(h[0], 1)
+    print(f"hybrid passes (RTMI_HYBRID={os.environ.get('RTMI_HYBRID', 'default')}, on {hon.value}; last batch of each stream): "
+          f"{h[0]} rays offered; certificate refusals {h[1]} ({h[1] / n:.4f}); BVH misses {h[2]} ({h[2] / n:.4f}); ties {h[3]} "
+          f"({h[3] / n:.6f}); descents failed: absent child {h[4]}, no collision {h[5]}, tmin >= t* {h[6]} "
+          f"({(h[4] + h[5] + h[6]) / n:.6f}); lists without the hit {h[7]} ({h[7] / n:.6f}); out of bounds {h[10]} (must be 0); "
+          f"confirmed {h[11]} ({h[11] / n:.4f}); fallbacks {h[8]} ({h[8] / n:.4f}); violations {h[9]} (must be 0)")
 ns = (C.c_ulonglong * 3)()
 lib.rth_debug_node_cull_stats.argtypes = [C.c_void_p, C.c_void_p]
 if lib.rth_debug_node_cull_stats(scene.h, ns) == 0:
