@@ -253,8 +253,9 @@ int rtmi_scene_set_spheres(rtmi_scene_t* scene, const rtmi_sphere_t* spheres, ui
  * Unchanged: rtmi_trace*, rtmi_occluded*, the records; rtmi_render_features*, _ao*, _light*, _preview* and the guide buffers of
  * the camera and explicit-ray calls, which read first hits only: a miss's albedo stays the sky constant with coverage 0.
  * rtmi_render_shadowed* returns RTMI_ERR_UNSUPPORTED for a scene with an environment, before any HIP call.
- * Not here: importance sampling of the map, next-event estimation towards the sun, an environment in the path kernels
- * (pipeline 3), image file loading, equirectangular input, mip-mapped lookups. */
+ * Importance sampling of the map, with next-event estimation towards its bright texels: rtmi_render_envlight*, "SAMPLING THE
+ * ENVIRONMENT" below.
+ * Not here: an environment in the path kernels (pipeline 3), image file loading, equirectangular input, mip-mapped lookups. */
 typedef struct rtmi_environment { float frame[9]; uint32_t flags; /* 0 */ } rtmi_environment_t;
 void rtmi_environment_defaults(rtmi_environment_t* env); /* identity frame, flags 0 */
 int rtmi_scene_set_environment(rtmi_scene_t* scene, const float* rgb /* n * n * 3, or NULL */, uint32_t n,
@@ -1261,6 +1262,85 @@ int rtmi_render_shadowed_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, 
                                 void* out_device /* or NULL */, void* hip_stream, rtmi_stats_t* stats);
 int rtmi_render_shadowed(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
                          uint32_t sample0, uint32_t nsamples, const rtmi_light_t* light, float* accum_host,
+                         float* out_host /* or NULL */, rtmi_stats_t* stats);
+
+/* SAMPLING THE ENVIRONMENT at matte hits: next-event estimation towards the map's bright texels.  A progressive
+ * pass that renders, in expectation, the image rtmi_render_samples[_device] renders of a scene with an environment, with less
+ * noise where a small bright region (a sun) lights matte surfaces: at every Matte hit that bounces, one shadow ray is also sent
+ * towards a direction drawn from the map's brightness, and combined with the bounce's own escape by the balance heuristic.  NOT part
+ * of the reference; build-defined like the environment itself: what follows IS the definition, tests/envlight_ref.py pins it bit
+ * for bit.  float32 throughout, every step rounded (no fused multiply-add), vdot the ordered sum seeded with +0, all four lanes.
+ *
+ * The sampler table of an n x n environment, in integers, so that no summation order exists.  For texel (i, j) with colour (r, g, b):
+ *     lum = (r + g) + b;  a lum that is not finite or not > 0.f counts as 0.f
+ *     px = ((float)i + 0.5f) / (float)n * 2.f - 1.f;  py likewise from j;  z = (1.f - |px|) - |py|;  if z < 0.f: the fold on the
+ *     old (px, py)                                   (the texel centre's map point as rtmi_scene_set_sky has it before vunit)
+ *     r2 = (px * px + py * py) + z * z;  w = lum / (r2 * sqrtf(r2));  a w that is not finite (an overflow) counts as 0.f
+ *     (a piece dpx dpy of the square covers the solid angle dpx dpy / r^3: w makes the pdf per solid angle proportional to lum)
+ *     wmax = the maximum of w over the table
+ *     s = w * (1048576.f / wmax);  s = !(s >= 0.f) ? 0.f : (s > 1048576.f ? 1048576.f : s);  q(i, j) = 1 + (uint32)s
+ *     wmax == 0.f: q = 1 everywhere.  The + 1 keeps the pdf positive in every direction; the estimator is unbiased because of it.
+ *     total = the sum of q (uint64);  C = the inclusive prefix sum of q in row-major order (uint64)
+ * The table is built on the device on the first call that needs it, kept on the scene handle, and dropped by
+ * rtmi_scene_set_environment and rtmi_scene_set_sky (setting, replacing or clearing).  rtmi_scene_get_env_sampler copies q back
+ * (n * n uint32, row-major; q_out may be NULL) with total and n, building the table if need be; *n_out = 0: no environment.
+ *
+ * pe(d), the environment's pdf per solid angle of a world unit direction d:
+ *     m, a, px, py and the fold exactly as the lookup above computes them
+ *     gx = floorf((px * 0.5f + 0.5f) * (float)n);  gx = !(gx >= 0.f) ? 0.f : (gx > (float)n - 1.f ? (float)n - 1.f : gx);  i = (int)gx;
+ *     j likewise from py
+ *     pe = (((float)q(i, j) / (float)total) * (((float)n * (float)n) * 0.25f)) / ((a * a) * a)
+ *   Right for a rotation frame only: RTMI_ERR_UNSUPPORTED, before any HIP call, when some |vdot(r_i, r_j) - delta_ij| > 1e-4f.
+ * pb(n, d, s), the pdf per solid angle of the reference's Matte bounce dir = unit(n + s), s = random_vec (the unit vector of a
+ * uniform point of the cube: density 1 / (24 m^3) per solid angle, m = max |s_c|; the map s -> unit(n + s) has the Jacobian 4 cos):
+ *     cos = vdot(n, d);  m = fmaxf(fmaxf(|s.x|, |s.y|), |s.z|);  pb = cos > 0.f ? cos / (6.f * ((m * m) * m)) : 0.f
+ *
+ * The pass.  Contract: rtmi_render_samples[_device]'s in every respect, as rtmi_render_shadowed* states it.  The rays of every pass
+ * are exactly those of rtmi_render_samples_device for the same arguments: no ray, no RNG block 0 .. maxdepth and no plain "Rays"
+ * count moves.  At the hit of a path's ray number j, when the hit is a Matte surface (neither a miss nor an edge face) and the path
+ * bounces (maxdepth - j - 1 != 0: an exhausted level gets no sample, as the plain render shows black there):
+ *     point = rd * t + ro;  n = the triangle's norm, * (-1.f) when face & 1
+ *     w = RNG block 0xC0000000 | j of (seed, pixel, sample);  T = the upper 64 bits of ((uint64)w0 << 32 | w1) * total
+ *     texel (i, j'): the first k = j' * n + i with C[k] > T
+ *     px = ((float)i + u(w2)) / (float)n * 2.f - 1.f;  py likewise from j' and u(w3);  u(x) = top 24 bits of x * 2^-24
+ *     z = (1.f - |px|) - |py|;  if z < 0.f: the fold;  m = vunit(px, py, z)
+ *     omega = vunit((r0 * m.x + r1 * m.y) + r2 * m.z)                                  (the transposed frame)
+ *     cos = vdot(n, omega);  s = omega * (2.f * cos) - n                              (the random_vec whose bounce is omega)
+ *     o = point + s * bias                  (where that bounce ray starts when bias = 0.001f: the shadow ray sees what it would)
+ *     culled when !(cos > 0.f); otherwise L = the lookup of omega, wgt = pb(n, omega, s) / (pb + pe(omega))
+ *     live when wgt > 0.f and some lane 0..2 of L != 0.f;  direct_j = L * wgt when live and rtmi_occluded's answer for
+ *     (o, omega, no tmax) is 0, else (0, 0, 0)
+ *   and with nr the bounce ray (lambertian_ray with rv = random_vec of block j + 1): wb = pb(n, nr.dir, rv) / (pb + pe(nr.dir)).
+ *   A Reflective level has direct_j = 0 and wb = 1.f; so has the primary ray (wb) and an exhausted level (direct_j).
+ * Colour: a miss is lookup(rd) * wb, wb that of the path's last bounce; the fold is c = mix_color(color_j, c + direct_j, alpha_j),
+ *   inside-out over the path's Matte / Reflective levels.  Edge faces, Solid ends and the black of exhausted depth as in color_ray.
+ * (The reference's Matte bounce starts at point + rv * 0.001f, which lies behind the surface for half of the draws and then hits
+ *  that surface from behind; a shadow ray from point + n * bias sees a different scene, and the two estimators then differ in
+ *  expectation.  Hence o above.)
+ * bias: ONLY bias == 0.001f, the reference's own offset of a bounce ray and the default, renders rtmi_render_samples*'s image in
+ *   expectation.  Every other finite value is accepted and is BIASED against it: the shadow rays then start elsewhere than the
+ *   bounce rays they stand for and see a different scene.
+ * RTMI_ERR_UNSUPPORTED, before any HIP call, for a scene without an environment, with analytic spheres, with a dielectric, with
+ *   vertex normals, with textures or with normal maps, and for a frame that is no rotation.
+ * RTMI_ERR_INVALID, before any HIP call and before the scene is used, stats cleared: every check of rtmi_render_samples[_device],
+ *   a bias that is not finite, flags != 0.  env == NULL: the defaults.  An empty tile returns RTMI_OK.
+ * stats: as rtmi_render_shadowed* fills them: rays = the plain rays + the live shadow rays, trace_launches = 2 per pass and batch,
+ *   primary_ms the closest-hit launches' share, bounce_ms the walks'.
+ * How: rtmi_render_shadowed*'s pass structure and buffers: k_envlight_rays, the occlusion walk, k_shade_envlight per pass (on an
+ *   octree the walk is the scene's closest-hit launch, which is faster than the any-hit kernel on rays that mostly escape; the
+ *   answers are the same; no launch but the shading at the exhausted pass); beside them
+ *   16 B per shadow queue entry, 16 B per path and level (the direct stack) and 4 B per path, allocated by this call only.
+ * Not here: smooth, textured, normal-mapped and glass scenes; samples at the exhausted level; more than one environment sample per
+ *   hit; box lights in the same pass; adaptive variants, view batches and denoised wrappers; the path kernels (pipeline 3). */
+typedef struct rtmi_envlight { float bias; /* default 0.001f */ uint32_t flags; /* 0 */ } rtmi_envlight_t;
+void rtmi_envlight_defaults(rtmi_envlight_t* env);
+int rtmi_scene_get_env_sampler(rtmi_scene_t* scene, uint32_t* q_out /* n * n, or NULL */, uint64_t* total_out /* or NULL */,
+                               uint32_t* n_out);
+int rtmi_render_envlight_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile,
+                                uint32_t sample0, uint32_t nsamples, const rtmi_envlight_t* env /* or NULL = defaults */,
+                                void* accum_device, void* out_device /* or NULL */, void* hip_stream, rtmi_stats_t* stats);
+int rtmi_render_envlight(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
+                         uint32_t sample0, uint32_t nsamples, const rtmi_envlight_t* env /* or NULL = defaults */, float* accum_host,
                          float* out_host /* or NULL */, rtmi_stats_t* stats);
 
 /* A shaded preview in one call: albedo, ambient occlusion and up to four coloured box lights composed PER

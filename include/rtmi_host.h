@@ -235,6 +235,17 @@ int rth_caster_walk_shadowed_device(rth_scene_t* s, uint32_t w, uint32_t h, cons
                                     const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, const rtmi_light_t* light,
                                     void* accum_device, void* out_device, void* hip_stream, rtmi_stats_t* stats,
                                     double* wall_seconds);
+/* Path tracing with the environment sampled at matte hits (rtmi_render_envlight / rtmi_render_envlight_device in rtmi.h, which
+ * defines it): rth_caster_walk_samples[_device] in every respect; env may be NULL (the defaults).  rth_caster_env_sampler uploads
+ * if need be and reads the sampler table back (rtmi_scene_get_env_sampler): n * n weights, at most cap of them, q_out may be NULL. */
+int rth_caster_walk_envlight(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp, uint64_t row0,
+                             uint64_t nrows, uint32_t sample0, uint32_t nsamples, const rtmi_envlight_t* env, float* accum_host,
+                             float* out_host, rtmi_stats_t* stats, double* wall_seconds);
+int rth_caster_walk_envlight_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                                    const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, const rtmi_envlight_t* env,
+                                    void* accum_device, void* out_device, void* hip_stream, rtmi_stats_t* stats,
+                                    double* wall_seconds);
+int rth_caster_env_sampler(rth_scene_t* s, uint32_t* q_out, uint64_t cap, uint64_t* total_out, uint32_t* n_out);
 /* Built-in camera models (rtmi_render_camera / rtmi_render_camera_device in rtmi.h, which defines them):
  * rth_caster_walk_samples[_device] in every respect, with the rays of `camera` (pinhole, thin lens, orthographic) and, when
  * guides is not NULL, rth_caster_walk_features' buffers of those rays. */

@@ -727,6 +727,51 @@ int rth_caster_walk_shadowed_device(rth_scene_t* s, uint32_t w, uint32_t h, cons
         if (stats) *stats = ctx.stats;
     });
 }
+static rtmi_envlight_t envlight_or_defaults(const rtmi_envlight_t* env) {
+    rtmi_envlight_t e;
+    rtmi_envlight_defaults(&e);
+    if (env) e = *env;
+    return e;
+}
+int rth_caster_walk_envlight(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp, uint64_t row0,
+                             uint64_t nrows, uint32_t sample0, uint32_t nsamples, const rtmi_envlight_t* env, float* accum_host,
+                             float* out_host, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_rays_envlight(v, s->scene, (size_t)row0, (size_t)nrows, sample0, nsamples, envlight_or_defaults(env),
+                                        reinterpret_cast<Color*>(accum_host), reinterpret_cast<Color*>(out_host), ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
+int rth_caster_walk_envlight_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                                    const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, const rtmi_envlight_t* env,
+                                    void* accum_device, void* out_device, void* hip_stream, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!tile) throw std::runtime_error("NULL tile");
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_envlight_device(v, s->scene, *tile, sample0, nsamples, envlight_or_defaults(env), accum_device, out_device,
+                                          hip_stream, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
+int rth_caster_env_sampler(rth_scene_t* s, uint32_t* q_out, uint64_t cap, uint64_t* total_out, uint32_t* n_out) {
+    return guarded([&] {
+        if (!n_out) throw std::runtime_error("rth_caster_env_sampler: NULL n_out");
+        uint32_t n = 0;
+        uint64_t total = 0;
+        const std::vector<uint32_t> q = caster_of(s).env_sampler(s->scene, n, total);
+        if (q_out && q.size() > cap) throw std::runtime_error("rth_caster_env_sampler: the buffer is too small");
+        if (q_out && !q.empty()) memcpy(q_out, q.data(), q.size() * sizeof(uint32_t));
+        if (total_out) *total_out = total;
+        *n_out = n;
+    });
+}
 int rth_caster_walk_camera(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp, uint64_t row0,
                            uint64_t nrows, const rtmi_camera_t* camera, uint32_t sample0, uint32_t nsamples, float* accum_host,
                            float* out_host, const rtmi_camera_out_t* guides_host, rtmi_stats_t* stats, double* wall) {

@@ -1091,6 +1091,44 @@ void HipRayCaster::walk_shadowed_device(const Viewport& v, const Scene& s, const
     progress.stats = st;
 }
 
+void HipRayCaster::walk_rays_envlight(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
+                                      const rtmi_envlight_t& env, Color* accum, Color* out, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_envlight(h, &av, seed, (uint32_t)row0, (uint32_t)nrows, sample0, nsamples, &env,
+                                        reinterpret_cast<float*>(accum), reinterpret_cast<float*>(out), &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_envlight: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
+void HipRayCaster::walk_envlight_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
+                                        const rtmi_envlight_t& env, void* accum_device, void* out_device, void* hip_stream,
+                                        ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_envlight_device(h, &av, seed, &tile, sample0, nsamples, &env, accum_device, out_device, hip_stream, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_envlight_device: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
+std::vector<uint32_t> HipRayCaster::env_sampler(const Scene& s, uint32_t& n, uint64_t& total) {
+    n = 0;
+    total = 0;
+    if (!s.environment) return {};
+    rtmi_scene_t* h = resident(s);  // (applies the environment: the device's table has the scene's n)
+    std::vector<uint32_t> q((size_t)s.environment->n * s.environment->n);
+    if (rtmi_scene_get_env_sampler(h, q.data(), &total, &n) != RTMI_OK)
+        throw std::runtime_error(std::string("rtmi_scene_get_env_sampler: ") + rtmi_last_error());
+    if (n != s.environment->n) throw std::runtime_error("env_sampler: the device's environment is not the scene's");
+    return q;
+}
+
 void HipRayCaster::walk_rays_camera(const Viewport& v, const Scene& s, size_t row0, size_t nrows, const rtmi_camera_t& camera,
                                     uint32_t sample0, uint32_t nsamples, Color* accum, Color* out, const rtmi_camera_out_t* guides,
                                     ProgressCtx& progress) {

@@ -309,6 +309,15 @@ public:
     void walk_shadowed_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
                               uint32_t flags, float bias, void* accum_device, void* out_device, void* hip_stream,
                               ProgressCtx& progress);
+    // Path tracing with the environment sampled at matte hits (rtmi_render_envlight / rtmi_render_envlight_device, which rtmi.h
+    // defines): walk_samples / walk_samples_device in every respect.
+    void walk_rays_envlight(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
+                            const rtmi_envlight_t& env, Color* accum, Color* out, ProgressCtx& progress);
+    void walk_envlight_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
+                              const rtmi_envlight_t& env, void* accum_device, void* out_device, void* hip_stream, ProgressCtx& progress);
+    // The sampler table of the environment of the scene's resident copy on the first device (rtmi_scene_get_env_sampler): n * n
+    // weights and their sum, empty and n = 0 when the scene has no environment.
+    std::vector<uint32_t> env_sampler(const Scene& s, uint32_t& n, uint64_t& total);
     // Built-in camera models (rtmi_render_camera / rtmi_render_camera_device, which rtmi.h defines): walk_samples /
     // walk_samples_device in every respect, with the rays of `camera` (pinhole, thin lens, orthographic) and, when `guides` is
     // not null, the feature buffers of those rays.

@@ -1162,6 +1162,84 @@ class HipRayCaster:
                                                         C.c_void_p(getattr(stream, "cuda_stream", stream) or 0), C.byref(st), C.byref(wall)))
         return ProgressCtx(st.rays, wall.value, st.as_dict())
 
+    @staticmethod
+    def envlight_params(bias=None):
+        """rtmi_envlight_t from the library's defaults (bias 0.001) with the given field replaced; ValueError for what the library
+        would refuse"""
+        a = _ffi.Envlight()
+        _ffi.lib().rtmi_envlight_defaults(C.byref(a))
+        if bias is not None:
+            if not np.isfinite(float(bias)):
+                raise ValueError("bias must be finite")
+            a.bias = float(bias)
+        return a
+
+    def walk_rays_envlight(self, v, s, data=None, bias=None, sample0=0, nsamples=None, accum=None):
+        """Path tracing of the whole frame with the scene's environment sampled at every Matte hit that bounces
+        (rtmi_render_envlight; include/rtmi.h defines it): walk_rays' paths and, in expectation, walk_rays' image of a scene with
+        an environment, with less noise where a small bright region of the map lights matte surfaces.  Samples [sample0, sample0 +
+        nsamples) (default: all from sample0) of the frame's v.samples_per_pixel; data and accum as in walk_rays_shadowed.  bias:
+        the offset of a shadow ray's origin along the bounce vector (default 0.001, the reference's own for a bounce ray: any other
+        value is biased against walk_rays).
+        Returns (data, ctx); ctx.accum is the sums."""
+        k0, n = self._feature_samples(v, sample0, nsamples)
+        a = self.envlight_params(bias)
+        shape = (v.height, v.width, 4)
+        bufs = []
+        for name, x in (("data", data), ("accum", accum)):
+            if x is None:
+                x = np.zeros(shape, np.float32)
+            elif not isinstance(x, np.ndarray) or x.dtype != np.float32 or not x.flags.c_contiguous or x.size != v.height * v.width * 4:
+                raise ValueError(f"{name} must be a C-contiguous float32 array of height*width*4 elements")
+            bufs.append(x)
+        if np.shares_memory(bufs[0], bufs[1]):
+            raise ValueError("data and accum must not alias")
+        if k0 > 0 and accum is None:
+            raise ValueError("sample0 > 0 continues the sums of the earlier samples: pass their accum")
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_envlight(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, 0, v.height, k0, n,
+                                                 C.byref(a), _p(bufs[1]), _p(bufs[0]), C.byref(st), C.byref(wall)))
+        ctx = ProgressCtx(st.rays, wall.value, st.as_dict())
+        ctx.accum = bufs[1]
+        return bufs[0], ctx
+
+    def walk_rays_envlight_device(self, v, s, accum, out=None, tile=None, bias=None, sample0=0, nsamples=None, stream=None):
+        """The same on torch tensors on the scene's device (rtmi_render_envlight_device) for a striped row set tile = (row0,
+        nrows, stripe_rows, stripe_step) (default: the whole frame); accum, out and stream as in walk_rays_shadowed_device.
+        Returns ctx."""
+        k0, n = self._feature_samples(v, sample0, nsamples)
+        a = self.envlight_params(bias)
+        t = _ffi.Tile(*[int(x) for x in (tile if tile is not None else (0, v.height, v.height, 0))])
+        want = int(t.nrows) * int(v.width) * 4
+        for name, x in (("accum", accum), ("out", out)):
+            if (x is not None or name == "accum") and (not hasattr(x, "data_ptr") or not x.is_cuda or str(x.dtype) != "torch.float32"
+                                                       or not x.is_contiguous() or x.numel() != want):
+                raise ValueError(f"{name} must be a contiguous float32 tensor of {want} elements on the device")
+        if out is not None and abs(accum.data_ptr() - out.data_ptr()) < 4 * want:
+            raise ValueError("accum and out must not overlap")
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_envlight_device(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, C.byref(t), k0, n,
+                                                        C.byref(a), C.c_void_p(accum.data_ptr()), C.c_void_p(out.data_ptr() if out is not None else 0),
+                                                        C.c_void_p(getattr(stream, "cuda_stream", stream) or 0), C.byref(st), C.byref(wall)))
+        return ProgressCtx(st.rays, wall.value, st.as_dict())
+
+    def env_sampler(self, s):
+        """The sampler table of the scene's environment as the first device holds it (rtmi_scene_get_env_sampler): (q (n, n) uint32,
+        total), or None when the scene has no environment.  Uploads, and builds the table, if need be."""
+        self._config(s)
+        n = C.c_uint32(0)
+        _chk(_ffi.lib().rth_scene_environment_size(s.h, C.byref(n)))
+        if n.value == 0:
+            return None
+        q = np.zeros((n.value, n.value), np.uint32)
+        total = C.c_uint64(0)
+        _chk(_ffi.lib().rth_caster_env_sampler(s.h, _p(q), q.size, C.byref(total), C.byref(n)))
+        return q, int(total.value)
+
     PREVIEW_MAX_LIGHTS = _ffi.PREVIEW_MAX_LIGHTS
     _PREVIEW_OUTPUTS = ("color", "albedo", "normal", "ids", "ao", "shadow", "irradiance")  # rtmi_preview_out_t's order
 
