@@ -599,17 +599,8 @@ namespace rtmi {
                           uint32_t* __restrict__ qpath_n, uint16_t* __restrict__ mstack, float4* __restrict__ scol,    \
                           DCtrl* __restrict__ ctrl, SlowQ slow
 #define RTMI_SHADE_ARGS sc, v, seed, pix0, npaths, pass, qo, qd, qpath, hit_tf, hit_t, qo_n, qd_n, qpath_n, mstack, scol, ctrl, slow
-// GLASS (k_shade*_glass): shade_hit<true>, which knows RTMI_DIELECTRIC; the launch sites pick them for scenes with a dielectric
-// ENV (k_shade*_env): shade_hit<GLASS, true>, whose misses look the scene's environment up in their ray's direction; the launch
-// sites pick them, before the glass ones, for scenes with an environment
-// SMOOTH (k_shade*_smooth): shade_hit<true, true, true>, which shades with the scene's vertex normals; the launch
-// sites pick them first, for scenes with normals, with or without glass and an environment (an EnvTab of n = 0 is "none")
-// TEX (k_shade*_tex): shade_hit<true, true, true, true>, which colours a hit from the scene's textures and folds over the colour
-// stack; the launch sites pick them before all others, for scenes with textures, with or without glass, an
-// environment and vertex normals (a SmoothTab of n = 0 is "none")
-// NMAP (k_shade*_nmap): shade_hit<true, true, true, true, true>, which also looks up the scene's normal maps; the
-// launch sites pick them before the _tex ones, for scenes with normal maps (which always have textures)
-template <Samp S, bool GLASS = false, bool ENV = false, bool SMOOTH = false, bool TEX = false, bool NMAP = false>
+// L: the shading level (Shade, shade.hpp); the level's tables follow the mode's own argument.
+template <Samp S, Shade L = Shade::PLAIN>
 __device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list = nullptr, const ViewTab& vt = ViewTab{},
                                            const EnvTab* env = nullptr, const SmoothTab* sm = nullptr, const TexTab* tex = nullptr,
                                            float4* __restrict__ cstack = nullptr, const NmapTab* nm = nullptr) {
@@ -632,19 +623,19 @@ __device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __
             float t = 0.f;
             float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f), d4 = make_float4(0.f, 0.f, 1.f, 0.f);
             if ((tf & 0x3FFFFFFFu) != 0u && !((tf >> 30) & 2u)) { t = hit_t[i]; o4 = qo[i]; d4 = qd[i]; }
-            if constexpr (ENV) {  // a miss looks the environment up in its ray's direction
+            if constexpr (L >= Shade::ENV) {  // a miss looks the environment up in its ray's direction
                 if ((tf & 0x3FFFFFFFu) == 0u) d4 = qd[i];
             }
             if constexpr (S == Samp::RAYS) {  // `list` = the batch's RNG keys (or null), pix0 = the key of its first group
                 uint32_t pixel, sample;
                 rays_key(v, pix0, path, list, pixel, sample);
-                push = shade_hit<GLASS, ENV, SMOOTH, TEX, NMAP>(sc, v.maxdepth, seed, npaths, path, pixel, sample, (uint32_t)pass, tf, t, V4{o4.x, o4.y, o4.z, o4.w},
+                push = shade_hit<L>(sc, v.maxdepth, seed, npaths, path, pixel, sample, (uint32_t)pass, tf, t, V4{o4.x, o4.y, o4.z, o4.w},
                                                      V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr, nullptr, env, sm, tex, cstack, nm);
             } else {
             uint32_t prow, pcol, sample;
             path_pixel<S>(v, pix0, path, prow, pcol, sample, list);
             const PixKey key = pixel_key<S>(v, prow, vt);
-            push = shade_hit<GLASS, ENV, SMOOTH, TEX, NMAP>(sc, v.maxdepth, key_seed<S>(key, vt, seed), npaths, path, key.row * v.width + pcol, sample, (uint32_t)pass, tf, t,
+            push = shade_hit<L>(sc, v.maxdepth, key_seed<S>(key, vt, seed), npaths, path, key.row * v.width + pcol, sample, (uint32_t)pass, tf, t,
                                                  V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w}, mstack, scol, nr, nullptr, env, sm, tex, cstack, nm);
             }
             // a bounce ray with an exactly-zero direction component goes to the slow path (SlowQ), not to the next pass
@@ -677,44 +668,47 @@ __device__ __forceinline__ void shade_pass(RTMI_SHADE_PARAMS, const uint32_t* __
         __syncthreads();  // s_cnt / s_base are rewritten by the next iteration
     }
 }
-__global__ void __launch_bounds__(256) k_shade(RTMI_SHADE_PARAMS) { shade_pass<Samp::FRAME>(RTMI_SHADE_ARGS); }
-__global__ void __launch_bounds__(256) k_shade_samples(RTMI_SHADE_PARAMS) { shade_pass<Samp::PASS>(RTMI_SHADE_ARGS); }
-__global__ void __launch_bounds__(256) k_shade_list(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list) { shade_pass<Samp::LIST>(RTMI_SHADE_ARGS, list); }
-__global__ void __launch_bounds__(256) k_shade_views(RTMI_SHADE_PARAMS, ViewTab vt) { shade_pass<Samp::VIEWS>(RTMI_SHADE_ARGS, nullptr, vt); }
-// Samp::RAYS (rtmi_render_rays*): v carries maxdepth, spp = the group size and dspp only; keys = the batch's RNG keys or null
-__global__ void __launch_bounds__(256) k_shade_rays(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ keys) { shade_pass<Samp::RAYS>(RTMI_SHADE_ARGS, keys); }
-// The same five for scenes with a dielectric surface (RTMI_DIELECTRIC)
-__global__ void __launch_bounds__(256) k_shade_glass(RTMI_SHADE_PARAMS) { shade_pass<Samp::FRAME, true>(RTMI_SHADE_ARGS); }
-__global__ void __launch_bounds__(256) k_shade_samples_glass(RTMI_SHADE_PARAMS) { shade_pass<Samp::PASS, true>(RTMI_SHADE_ARGS); }
-__global__ void __launch_bounds__(256) k_shade_list_glass(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list) { shade_pass<Samp::LIST, true>(RTMI_SHADE_ARGS, list); }
-__global__ void __launch_bounds__(256) k_shade_views_glass(RTMI_SHADE_PARAMS, ViewTab vt) { shade_pass<Samp::VIEWS, true>(RTMI_SHADE_ARGS, nullptr, vt); }
-__global__ void __launch_bounds__(256) k_shade_rays_glass(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ keys) { shade_pass<Samp::RAYS, true>(RTMI_SHADE_ARGS, keys); }
-// And for scenes with an environment (rtmi_scene_set_environment / rtmi_scene_set_sky), with or without glass
-__global__ void __launch_bounds__(256) k_shade_env(RTMI_SHADE_PARAMS, EnvTab env) { shade_pass<Samp::FRAME, true, true>(RTMI_SHADE_ARGS, nullptr, ViewTab{}, &env); }
-__global__ void __launch_bounds__(256) k_shade_samples_env(RTMI_SHADE_PARAMS, EnvTab env) { shade_pass<Samp::PASS, true, true>(RTMI_SHADE_ARGS, nullptr, ViewTab{}, &env); }
-__global__ void __launch_bounds__(256) k_shade_list_env(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list, EnvTab env) { shade_pass<Samp::LIST, true, true>(RTMI_SHADE_ARGS, list, ViewTab{}, &env); }
-__global__ void __launch_bounds__(256) k_shade_views_env(RTMI_SHADE_PARAMS, ViewTab vt, EnvTab env) { shade_pass<Samp::VIEWS, true, true>(RTMI_SHADE_ARGS, nullptr, vt, &env); }
-__global__ void __launch_bounds__(256) k_shade_rays_env(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ keys, EnvTab env) { shade_pass<Samp::RAYS, true, true>(RTMI_SHADE_ARGS, keys, ViewTab{}, &env); }
-// And for scenes with vertex normals (rtmi_scene_set_normals), with or without glass and an environment
-__global__ void __launch_bounds__(256) k_shade_smooth(RTMI_SHADE_PARAMS, EnvTab env, SmoothTab sm) { shade_pass<Samp::FRAME, true, true, true>(RTMI_SHADE_ARGS, nullptr, ViewTab{}, &env, &sm); }
-__global__ void __launch_bounds__(256) k_shade_samples_smooth(RTMI_SHADE_PARAMS, EnvTab env, SmoothTab sm) { shade_pass<Samp::PASS, true, true, true>(RTMI_SHADE_ARGS, nullptr, ViewTab{}, &env, &sm); }
-__global__ void __launch_bounds__(256) k_shade_list_smooth(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list, EnvTab env, SmoothTab sm) { shade_pass<Samp::LIST, true, true, true>(RTMI_SHADE_ARGS, list, ViewTab{}, &env, &sm); }
-__global__ void __launch_bounds__(256) k_shade_views_smooth(RTMI_SHADE_PARAMS, ViewTab vt, EnvTab env, SmoothTab sm) { shade_pass<Samp::VIEWS, true, true, true>(RTMI_SHADE_ARGS, nullptr, vt, &env, &sm); }
-__global__ void __launch_bounds__(256) k_shade_rays_smooth(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ keys, EnvTab env, SmoothTab sm) { shade_pass<Samp::RAYS, true, true, true>(RTMI_SHADE_ARGS, keys, ViewTab{}, &env, &sm); }
-// And for scenes with textures (rtmi_scene_set_textures), with or without glass, an environment and vertex normals.
-// cstack: the colour stack, one float4 (colour.rgb, alpha) beside every mstack entry.
-__global__ void __launch_bounds__(256) k_shade_tex(RTMI_SHADE_PARAMS, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack) { shade_pass<Samp::FRAME, true, true, true, true>(RTMI_SHADE_ARGS, nullptr, ViewTab{}, &env, &sm, &tex, cstack); }
-__global__ void __launch_bounds__(256) k_shade_samples_tex(RTMI_SHADE_PARAMS, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack) { shade_pass<Samp::PASS, true, true, true, true>(RTMI_SHADE_ARGS, nullptr, ViewTab{}, &env, &sm, &tex, cstack); }
-__global__ void __launch_bounds__(256) k_shade_list_tex(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack) { shade_pass<Samp::LIST, true, true, true, true>(RTMI_SHADE_ARGS, list, ViewTab{}, &env, &sm, &tex, cstack); }
-__global__ void __launch_bounds__(256) k_shade_views_tex(RTMI_SHADE_PARAMS, ViewTab vt, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack) { shade_pass<Samp::VIEWS, true, true, true, true>(RTMI_SHADE_ARGS, nullptr, vt, &env, &sm, &tex, cstack); }
-__global__ void __launch_bounds__(256) k_shade_rays_tex(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ keys, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack) { shade_pass<Samp::RAYS, true, true, true, true>(RTMI_SHADE_ARGS, keys, ViewTab{}, &env, &sm, &tex, cstack); }
-// And for scenes with normal maps (rtmi_scene_set_normal_maps), which always have textures; with or without glass,
-// an environment and vertex normals.
-__global__ void __launch_bounds__(256) k_shade_nmap(RTMI_SHADE_PARAMS, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack, NmapTab nm) { shade_pass<Samp::FRAME, true, true, true, true, true>(RTMI_SHADE_ARGS, nullptr, ViewTab{}, &env, &sm, &tex, cstack, &nm); }
-__global__ void __launch_bounds__(256) k_shade_samples_nmap(RTMI_SHADE_PARAMS, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack, NmapTab nm) { shade_pass<Samp::PASS, true, true, true, true, true>(RTMI_SHADE_ARGS, nullptr, ViewTab{}, &env, &sm, &tex, cstack, &nm); }
-__global__ void __launch_bounds__(256) k_shade_list_nmap(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack, NmapTab nm) { shade_pass<Samp::LIST, true, true, true, true, true>(RTMI_SHADE_ARGS, list, ViewTab{}, &env, &sm, &tex, cstack, &nm); }
-__global__ void __launch_bounds__(256) k_shade_views_nmap(RTMI_SHADE_PARAMS, ViewTab vt, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack, NmapTab nm) { shade_pass<Samp::VIEWS, true, true, true, true, true>(RTMI_SHADE_ARGS, nullptr, vt, &env, &sm, &tex, cstack, &nm); }
-__global__ void __launch_bounds__(256) k_shade_rays_nmap(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ keys, EnvTab env, SmoothTab sm, TexTab tex, float4* __restrict__ cstack, NmapTab nm) { shade_pass<Samp::RAYS, true, true, true, true, true>(RTMI_SHADE_ARGS, keys, ViewTab{}, &env, &sm, &tex, cstack, &nm); }
+// The 30 shading kernels: one per sampling mode (k_shade, k_shade_samples, k_shade_list, k_shade_views, k_shade_rays) and shading
+// level (no suffix, _glass, _env, _smooth, _tex, _nmap).  A level's kernels take, after the mode's own argument, the tables of the
+// level and of every level below it (RTMI_TAIL_P_<level>), and hand them to shade_pass (RTMI_TAIL_A_<level>).  cstack: the colour
+// stack, one float4 (colour.rgb, alpha) beside every mstack entry.  k_shade_rays (rtmi_render_rays*): v carries maxdepth, spp = the
+// group size and dspp only; keys = the batch's RNG keys or null.
+#define RTMI_TAIL_P_PLAIN
+#define RTMI_TAIL_A_PLAIN
+#define RTMI_TAIL_P_GLASS
+#define RTMI_TAIL_A_GLASS
+#define RTMI_TAIL_P_ENV , EnvTab env
+#define RTMI_TAIL_A_ENV , &env
+#define RTMI_TAIL_P_SMOOTH RTMI_TAIL_P_ENV, SmoothTab sm
+#define RTMI_TAIL_A_SMOOTH RTMI_TAIL_A_ENV, &sm
+#define RTMI_TAIL_P_TEX RTMI_TAIL_P_SMOOTH, TexTab tex, float4* __restrict__ cstack
+#define RTMI_TAIL_A_TEX RTMI_TAIL_A_SMOOTH, &tex, cstack
+#define RTMI_TAIL_P_NMAP RTMI_TAIL_P_TEX, NmapTab nm
+#define RTMI_TAIL_A_NMAP RTMI_TAIL_A_TEX, &nm
+#define RTMI_SHADE_KERNELS(sfx, LV)                                                                                                       \
+    __global__ void __launch_bounds__(256) k_shade##sfx(RTMI_SHADE_PARAMS RTMI_TAIL_P_##LV) {                                             \
+        shade_pass<Samp::FRAME, Shade::LV>(RTMI_SHADE_ARGS, nullptr, ViewTab{} RTMI_TAIL_A_##LV);                                         \
+    }                                                                                                                                     \
+    __global__ void __launch_bounds__(256) k_shade_samples##sfx(RTMI_SHADE_PARAMS RTMI_TAIL_P_##LV) {                                     \
+        shade_pass<Samp::PASS, Shade::LV>(RTMI_SHADE_ARGS, nullptr, ViewTab{} RTMI_TAIL_A_##LV);                                          \
+    }                                                                                                                                     \
+    __global__ void __launch_bounds__(256) k_shade_list##sfx(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ list RTMI_TAIL_P_##LV) {     \
+        shade_pass<Samp::LIST, Shade::LV>(RTMI_SHADE_ARGS, list, ViewTab{} RTMI_TAIL_A_##LV);                                             \
+    }                                                                                                                                     \
+    __global__ void __launch_bounds__(256) k_shade_views##sfx(RTMI_SHADE_PARAMS, ViewTab vt RTMI_TAIL_P_##LV) {                           \
+        shade_pass<Samp::VIEWS, Shade::LV>(RTMI_SHADE_ARGS, nullptr, vt RTMI_TAIL_A_##LV);                                                \
+    }                                                                                                                                     \
+    __global__ void __launch_bounds__(256) k_shade_rays##sfx(RTMI_SHADE_PARAMS, const uint32_t* __restrict__ keys RTMI_TAIL_P_##LV) {     \
+        shade_pass<Samp::RAYS, Shade::LV>(RTMI_SHADE_ARGS, keys, ViewTab{} RTMI_TAIL_A_##LV);                                             \
+    }
+RTMI_SHADE_KERNELS(, PLAIN)
+RTMI_SHADE_KERNELS(_glass, GLASS)   // RTMI_DIELECTRIC, DESIGN.md 4.22
+RTMI_SHADE_KERNELS(_env, ENV)       // rtmi_scene_set_environment / rtmi_scene_set_sky, DESIGN.md 4.23
+RTMI_SHADE_KERNELS(_smooth, SMOOTH) // rtmi_scene_set_normals, DESIGN.md 4.24
+RTMI_SHADE_KERNELS(_tex, TEX)       // rtmi_scene_set_textures, DESIGN.md 4.25
+RTMI_SHADE_KERNELS(_nmap, NMAP)     // rtmi_scene_set_normal_maps, DESIGN.md 4.26
+// one mode's six kernels in level order, for launch_shade
+#define RTMI_SHADE_ROW(k) k, k##_glass, k##_env, k##_smooth, k##_tex, k##_nmap
 
 // rtmi_scene_set_sky: texel (i, j) of an n x n environment table from the inverse of env_lookup's map -- the direction of the
 // texel's centre -- and a gradient sky with a sun disc, operation by operation as include/rtmi.h lists it.  One thread per texel.
@@ -850,10 +844,17 @@ __global__ void __launch_bounds__(256) k_accum_list(uint32_t npixels, uint32_t n
 __device__ inline uint32_t feat_slot(uint32_t k, uint32_t rot) { return (k & ~3u) | ((k + rot) & 3u); }
 // Sub-tile and stripe addressing of the outputs is accum_pixels<Samp::PASS>'s.  albedo / normal (float4 per pixel) and ids
 // (uint32 per pixel) may each be NULL.  dS: n / nsamples.
-__global__ void __launch_bounds__(256) k_features(DScene sc, uint32_t npixels, uint32_t nsamples, const uint32_t* __restrict__ hit_tf,
-                                                  const float* __restrict__ hit_t, float* __restrict__ albedo, float* __restrict__ normal,
-                                                  uint32_t* __restrict__ ids, uint32_t pix0, uint32_t W, uint32_t nsub, uint32_t sub,
-                                                  FastDiv dW, FastDiv dS) {
+// L: the shading level (Shade, shade.hpp) picks the gather.  Below SMOOTH it is hit_features, and glass and the environment do not
+// show in a first hit.  From SMOOTH on it is the level's hit_features_* (the normal is the shading normal; TEX: the
+// albedo is tex_colour's, 4.25; NMAP: the normal is the mapped one, 4.26), which needs the primary rays (qo, qd: queue slot ==
+// path) beside the hit records, and the level's tables (sm may be an empty table).
+#define RTMI_FEAT_PARAMS DScene sc, uint32_t npixels, uint32_t nsamples, const uint32_t* __restrict__ hit_tf,                          \
+                         const float* __restrict__ hit_t, float* __restrict__ albedo, float* __restrict__ normal,                     \
+                         uint32_t* __restrict__ ids, uint32_t pix0, uint32_t W, uint32_t nsub, uint32_t sub, FastDiv dW, FastDiv dS
+#define RTMI_FEAT_ARGS sc, npixels, nsamples, hit_tf, hit_t, albedo, normal, ids, pix0, W, nsub, sub, dW, dS
+template <Shade L>
+__device__ __forceinline__ void features_pass(RTMI_FEAT_PARAMS, const float4* __restrict__ qo = nullptr, const float4* __restrict__ qd = nullptr,
+                                              const SmoothTab* sm = nullptr, const TexTab* tex = nullptr, const NmapTab* nm = nullptr) {
     __shared__ float4 stage[2 * RTMI_FEAT_CHUNK];
     const float* stage_f = reinterpret_cast<const float*>(stage);
     const uint32_t tid = threadIdx.x, j = tid >> 3, l = tid & 7u;
@@ -868,7 +869,18 @@ __global__ void __launch_bounds__(256) k_features(DScene sc, uint32_t npixels, u
             const uint32_t n = min((uint32_t)RTMI_FEAT_CHUNK, nb - r0);
             __syncthreads();  // the previous chunk has been consumed
             for (uint32_t k = tid; k < n; k += 256u) {
-                const HitFeat f = hit_features(sc, hit_tf[f0 + r0 + k], hit_t[f0 + r0 + k]);
+                HitFeat f;
+                if constexpr (L < Shade::SMOOTH) {
+                    f = hit_features(sc, hit_tf[f0 + r0 + k], hit_t[f0 + r0 + k]);
+                } else {
+                    const uint32_t tf = hit_tf[f0 + r0 + k];
+                    float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f), d4 = make_float4(0.f, 0.f, 1.f, 0.f);
+                    if ((tf & 0x3FFFFFFFu) != 0u && !((tf >> 30) & 2u)) { o4 = qo[f0 + r0 + k]; d4 = qd[f0 + r0 + k]; }
+                    const V4 ro{o4.x, o4.y, o4.z, o4.w}, rd{d4.x, d4.y, d4.z, d4.w};
+                    if constexpr (L == Shade::SMOOTH) f = hit_features_smooth(sc, *sm, tf, hit_t[f0 + r0 + k], ro, rd);
+                    else if constexpr (L == Shade::TEX) f = hit_features_tex(sc, *sm, *tex, tf, hit_t[f0 + r0 + k], ro, rd);
+                    else f = hit_features_nmap(sc, *sm, *tex, *nm, tf, hit_t[f0 + r0 + k], ro, rd);
+                }
                 const uint32_t e = feat_slot(k, rot * fdiv(r0 + k, dS));
                 stage[2u * e] = f.a;
                 stage[2u * e + 1u] = f.n;
@@ -888,139 +900,17 @@ __global__ void __launch_bounds__(256) k_features(DScene sc, uint32_t npixels, u
         }
     }
 }
-// k_features for a scene with vertex normals: the same kernel statement for statement, but the normal is
-// hit_features_smooth's, which needs the primary rays (qo, qd: queue slot == path) beside the hit records.  A kernel of its own
-// and not a template over both, which changed k_features' register allocation.
-__global__ void __launch_bounds__(256) k_features_smooth(DScene sc, uint32_t npixels, uint32_t nsamples, const uint32_t* __restrict__ hit_tf,
-                                                         const float* __restrict__ hit_t, float* __restrict__ albedo, float* __restrict__ normal,
-                                                         uint32_t* __restrict__ ids, uint32_t pix0, uint32_t W, uint32_t nsub, uint32_t sub,
-                                                         FastDiv dW, FastDiv dS, const float4* __restrict__ qo, const float4* __restrict__ qd,
-                                                         SmoothTab sm) {
-    __shared__ float4 stage[2 * RTMI_FEAT_CHUNK];
-    const float* stage_f = reinterpret_cast<const float*>(stage);
-    const uint32_t tid = threadIdx.x, j = tid >> 3, l = tid & 7u;
-    const uint32_t rot = (nsamples & 3u) == 0u ? 1u : 0u;
-    const float inv = 1.f / (float)nsamples;
-    for (uint32_t pb = blockIdx.x * RTMI_FEAT_PIX; pb < npixels; pb += gridDim.x * RTMI_FEAT_PIX) {
-        const uint32_t npb = min((uint32_t)RTMI_FEAT_PIX, npixels - pb);
-        const uint32_t f0 = pb * nsamples, nb = npb * nsamples;  // the block's paths: hit_*[f0 .. f0 + nb)
-        const uint32_t my0 = j * nsamples, my1 = my0 + nsamples;  // this thread's pixel among them (when j < npb)
-        float acc = 0.f;
-        for (uint32_t r0 = 0; r0 < nb; r0 += RTMI_FEAT_CHUNK) {
-            const uint32_t n = min((uint32_t)RTMI_FEAT_CHUNK, nb - r0);
-            __syncthreads();  // the previous chunk has been consumed
-            for (uint32_t k = tid; k < n; k += 256u) {
-                const uint32_t tf = hit_tf[f0 + r0 + k];
-                float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f), d4 = make_float4(0.f, 0.f, 1.f, 0.f);
-                if ((tf & 0x3FFFFFFFu) != 0u && !((tf >> 30) & 2u)) { o4 = qo[f0 + r0 + k]; d4 = qd[f0 + r0 + k]; }
-                const HitFeat f = hit_features_smooth(sc, sm, tf, hit_t[f0 + r0 + k], V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w});
-                const uint32_t e = feat_slot(k, rot * fdiv(r0 + k, dS));
-                stage[2u * e] = f.a;
-                stage[2u * e + 1u] = f.n;
-            }
-            __syncthreads();
-            if (j < npb) {
-                const uint32_t lo = max(my0, r0), hi = min(my1, r0 + n);
-                for (uint32_t s = lo; s < hi; s++) acc = acc + stage_f[feat_slot(s - r0, rot * j) * 8u + l];
-            }
-        }
-        if (j < npb) {
-            const uint32_t lp = pix0 + pb + j, lr = fdiv(lp, dW), col = lp - lr * W;
-            const size_t o = ((size_t)lr * nsub + sub) * W + col;
-            float* __restrict__ dst = l < 4u ? albedo : normal;
-            if (dst) store_stream(&dst[o * 4u + (l & 3u)], acc * inv);
-            if (ids && l == 0u) store_stream(&ids[o], hit_tf[f0 + my0]);
-        }
-    }
+__global__ void __launch_bounds__(256) k_features(RTMI_FEAT_PARAMS) { features_pass<Shade::PLAIN>(RTMI_FEAT_ARGS); }
+__global__ void __launch_bounds__(256) k_features_smooth(RTMI_FEAT_PARAMS, const float4* __restrict__ qo, const float4* __restrict__ qd, SmoothTab sm) {
+    features_pass<Shade::SMOOTH>(RTMI_FEAT_ARGS, qo, qd, &sm);
 }
-// k_features for a scene with textures: k_features_smooth statement for statement, with hit_features_tex's albedo
-// (sm may be an empty table).  A kernel of its own for k_features_smooth's reason.
-__global__ void __launch_bounds__(256) k_features_tex(DScene sc, uint32_t npixels, uint32_t nsamples, const uint32_t* __restrict__ hit_tf,
-                                                      const float* __restrict__ hit_t, float* __restrict__ albedo, float* __restrict__ normal,
-                                                      uint32_t* __restrict__ ids, uint32_t pix0, uint32_t W, uint32_t nsub, uint32_t sub,
-                                                      FastDiv dW, FastDiv dS, const float4* __restrict__ qo, const float4* __restrict__ qd,
-                                                      SmoothTab sm, TexTab tex) {
-    __shared__ float4 stage[2 * RTMI_FEAT_CHUNK];
-    const float* stage_f = reinterpret_cast<const float*>(stage);
-    const uint32_t tid = threadIdx.x, j = tid >> 3, l = tid & 7u;
-    const uint32_t rot = (nsamples & 3u) == 0u ? 1u : 0u;
-    const float inv = 1.f / (float)nsamples;
-    for (uint32_t pb = blockIdx.x * RTMI_FEAT_PIX; pb < npixels; pb += gridDim.x * RTMI_FEAT_PIX) {
-        const uint32_t npb = min((uint32_t)RTMI_FEAT_PIX, npixels - pb);
-        const uint32_t f0 = pb * nsamples, nb = npb * nsamples;  // the block's paths: hit_*[f0 .. f0 + nb)
-        const uint32_t my0 = j * nsamples, my1 = my0 + nsamples;  // this thread's pixel among them (when j < npb)
-        float acc = 0.f;
-        for (uint32_t r0 = 0; r0 < nb; r0 += RTMI_FEAT_CHUNK) {
-            const uint32_t n = min((uint32_t)RTMI_FEAT_CHUNK, nb - r0);
-            __syncthreads();  // the previous chunk has been consumed
-            for (uint32_t k = tid; k < n; k += 256u) {
-                const uint32_t tf = hit_tf[f0 + r0 + k];
-                float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f), d4 = make_float4(0.f, 0.f, 1.f, 0.f);
-                if ((tf & 0x3FFFFFFFu) != 0u && !((tf >> 30) & 2u)) { o4 = qo[f0 + r0 + k]; d4 = qd[f0 + r0 + k]; }
-                const HitFeat f = hit_features_tex(sc, sm, tex, tf, hit_t[f0 + r0 + k], V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w});
-                const uint32_t e = feat_slot(k, rot * fdiv(r0 + k, dS));
-                stage[2u * e] = f.a;
-                stage[2u * e + 1u] = f.n;
-            }
-            __syncthreads();
-            if (j < npb) {
-                const uint32_t lo = max(my0, r0), hi = min(my1, r0 + n);
-                for (uint32_t s = lo; s < hi; s++) acc = acc + stage_f[feat_slot(s - r0, rot * j) * 8u + l];
-            }
-        }
-        if (j < npb) {
-            const uint32_t lp = pix0 + pb + j, lr = fdiv(lp, dW), col = lp - lr * W;
-            const size_t o = ((size_t)lr * nsub + sub) * W + col;
-            float* __restrict__ dst = l < 4u ? albedo : normal;
-            if (dst) store_stream(&dst[o * 4u + (l & 3u)], acc * inv);
-            if (ids && l == 0u) store_stream(&ids[o], hit_tf[f0 + my0]);
-        }
-    }
+__global__ void __launch_bounds__(256) k_features_tex(RTMI_FEAT_PARAMS, const float4* __restrict__ qo, const float4* __restrict__ qd, SmoothTab sm,
+                                                      TexTab tex) {
+    features_pass<Shade::TEX>(RTMI_FEAT_ARGS, qo, qd, &sm, &tex);
 }
-
-// k_features for a scene with normal maps: k_features_tex statement for statement, with hit_features_nmap's
-// normal.  A kernel of its own for k_features_smooth's reason.
-__global__ void __launch_bounds__(256) k_features_nmap(DScene sc, uint32_t npixels, uint32_t nsamples, const uint32_t* __restrict__ hit_tf,
-                                                      const float* __restrict__ hit_t, float* __restrict__ albedo, float* __restrict__ normal,
-                                                      uint32_t* __restrict__ ids, uint32_t pix0, uint32_t W, uint32_t nsub, uint32_t sub,
-                                                      FastDiv dW, FastDiv dS, const float4* __restrict__ qo, const float4* __restrict__ qd,
-                                                      SmoothTab sm, TexTab tex, NmapTab nm) {
-    __shared__ float4 stage[2 * RTMI_FEAT_CHUNK];
-    const float* stage_f = reinterpret_cast<const float*>(stage);
-    const uint32_t tid = threadIdx.x, j = tid >> 3, l = tid & 7u;
-    const uint32_t rot = (nsamples & 3u) == 0u ? 1u : 0u;
-    const float inv = 1.f / (float)nsamples;
-    for (uint32_t pb = blockIdx.x * RTMI_FEAT_PIX; pb < npixels; pb += gridDim.x * RTMI_FEAT_PIX) {
-        const uint32_t npb = min((uint32_t)RTMI_FEAT_PIX, npixels - pb);
-        const uint32_t f0 = pb * nsamples, nb = npb * nsamples;  // the block's paths: hit_*[f0 .. f0 + nb)
-        const uint32_t my0 = j * nsamples, my1 = my0 + nsamples;  // this thread's pixel among them (when j < npb)
-        float acc = 0.f;
-        for (uint32_t r0 = 0; r0 < nb; r0 += RTMI_FEAT_CHUNK) {
-            const uint32_t n = min((uint32_t)RTMI_FEAT_CHUNK, nb - r0);
-            __syncthreads();  // the previous chunk has been consumed
-            for (uint32_t k = tid; k < n; k += 256u) {
-                const uint32_t tf = hit_tf[f0 + r0 + k];
-                float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f), d4 = make_float4(0.f, 0.f, 1.f, 0.f);
-                if ((tf & 0x3FFFFFFFu) != 0u && !((tf >> 30) & 2u)) { o4 = qo[f0 + r0 + k]; d4 = qd[f0 + r0 + k]; }
-                const HitFeat f = hit_features_nmap(sc, sm, tex, nm, tf, hit_t[f0 + r0 + k], V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w});
-                const uint32_t e = feat_slot(k, rot * fdiv(r0 + k, dS));
-                stage[2u * e] = f.a;
-                stage[2u * e + 1u] = f.n;
-            }
-            __syncthreads();
-            if (j < npb) {
-                const uint32_t lo = max(my0, r0), hi = min(my1, r0 + n);
-                for (uint32_t s = lo; s < hi; s++) acc = acc + stage_f[feat_slot(s - r0, rot * j) * 8u + l];
-            }
-        }
-        if (j < npb) {
-            const uint32_t lp = pix0 + pb + j, lr = fdiv(lp, dW), col = lp - lr * W;
-            const size_t o = ((size_t)lr * nsub + sub) * W + col;
-            float* __restrict__ dst = l < 4u ? albedo : normal;
-            if (dst) store_stream(&dst[o * 4u + (l & 3u)], acc * inv);
-            if (ids && l == 0u) store_stream(&ids[o], hit_tf[f0 + my0]);
-        }
-    }
+__global__ void __launch_bounds__(256) k_features_nmap(RTMI_FEAT_PARAMS, const float4* __restrict__ qo, const float4* __restrict__ qd, SmoothTab sm,
+                                                       TexTab tex, NmapTab nm) {
+    features_pass<Shade::NMAP>(RTMI_FEAT_ARGS, qo, qd, &sm, &tex, &nm);
 }
 
 // ---------------------------------------------------------------- adaptive sampling: the stop rule and the next list
@@ -2893,6 +2783,7 @@ static void launch_occluded(rtmi_scene* s, Work& w, hipStream_t st, uint64_t n, 
     }
 }
 // where a stream's zero-component rays go; cap 0 (tuning slow_path = 0... or the queue not allocated) keeps them in place
+static const SlowQ SLOW_OFF{nullptr, nullptr, nullptr, nullptr, 0u};  // no slow path: nothing is set aside (cap = 0)
 static SlowQ slow_queue(rtmi_scene* s, Work& w) {
     const bool on = s->tune.slow_path_off == 0u && w.sqo.p && w.sstream;
     return SlowQ{w.sqo.p, w.sqd.p, w.sqpath.p, w.sqbounce.p, on ? RTMI_SLOW_CAP : 0u};
@@ -3032,24 +2923,70 @@ static int check_view(const rtmi_viewport_t* vp, const rtmi_tile_t* tile) {
     return RTMI_OK;
 }
 
-// The plan of a call: its streams, their sub-tiles and the batch size, with every stream's workspace sized for it.
-// k_features on the hit records of the primary queue (qo, qd), or k_features_smooth for a scene with vertex normals: the queue is
-// still intact at every site that calls this (the shading of pass 0 writes the OTHER queue)
+// The shading level of a scene (Shade, shade.hpp): THE place that reads the has_* flags to choose kernels.  Each feature's kernels
+// know every earlier feature, so the level is the latest feature the scene has, and a table of a lower level that the scene lacks is
+// passed empty (envtab.n = 0, smoothtab.n = 0).  Only Shade::PLAIN renders with the path kernels (plan_tile): k_path_slow has no
+// arm for any level above it.
+static Shade shade_level(const rtmi_scene* s) {
+    if (s->has_nmap) return Shade::NMAP;  // (a scene with normal maps has textures)
+    if (s->has_tex) return Shade::TEX;
+    if (s->has_normals) return Shade::SMOOTH;
+    if (s->has_env) return Shade::ENV;
+    if (s->has_dielectric) return Shade::GLASS;
+    return Shade::PLAIN;
+}
+
+// The shading launch of pass `pass` of a batch on workspace w, THE launch site of the 30 k_shade* kernels: the kernel of (mode,
+// shade_level(s)) shades the rays (qo, qd) of queue pass & 1 -- pass 0 of explicit rays has them where the caller put them -- into
+// the other queue and scol.  list, vt: the mode's own argument (LIST: the pixel list; RAYS: the batch's RNG keys or null; VIEWS:
+// the view table).  The level's tables are appended here.  Every launch is a typed call: an argument list that does not fit its
+// kernel does not compile.
+static void launch_shade(rtmi_scene* s, Work& w, hipStream_t st, Samp mode, const DView& dv, uint64_t seed, uint32_t pix0, uint32_t npaths,
+                         uint32_t pass, const float4* qo, const float4* qd, float4* scol, const SlowQ& slow, const uint32_t* list = nullptr,
+                         const ViewTab& vt = ViewTab{}) {
+    const int a = pass & 1, b = a ^ 1;
+    const dim3 grid((unsigned)(s->num_cu * 8)), block(256);
+    // a mode's six kernels in level order (RTMI_SHADE_ROW), then the mode's own argument
+    auto row = [&](auto plain, auto glass, auto env, auto smooth, auto tex, auto nmap, auto... m) {
+        auto go = [&](auto k, auto... tail) {
+            hipLaunchKernelGGL(k, grid, block, 0, st, s->d, dv, seed, pix0, npaths, (int)pass, qo, qd, w.qpath[a].p, w.hit_tf.p, w.hit_t.p,
+                               w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, scol, w.ctrl.p, slow, m..., tail...);
+        };
+        switch (shade_level(s)) {
+        case Shade::PLAIN: go(plain); break;
+        case Shade::GLASS: go(glass); break;
+        case Shade::ENV: go(env, s->envtab); break;
+        case Shade::SMOOTH: go(smooth, s->envtab, s->smoothtab); break;
+        case Shade::TEX: go(tex, s->envtab, s->smoothtab, s->textab, w.cstack.p); break;
+        case Shade::NMAP: go(nmap, s->envtab, s->smoothtab, s->textab, w.cstack.p, s->nmaptab); break;
+        }
+    };
+    switch (mode) {
+    case Samp::FRAME: row(RTMI_SHADE_ROW(k_shade)); break;
+    case Samp::PASS: row(RTMI_SHADE_ROW(k_shade_samples)); break;
+    case Samp::LIST: row(RTMI_SHADE_ROW(k_shade_list), list); break;
+    case Samp::VIEWS: row(RTMI_SHADE_ROW(k_shade_views), vt); break;
+    case Samp::RAYS: row(RTMI_SHADE_ROW(k_shade_rays), list); break;
+    }
+}
+
+// The feature kernel of the scene's level on the hit records of the primary queue (qo, qd): the queue is still intact at every site
+// that calls this (the shading of pass 0 writes the OTHER queue).  Glass and the environment do not show in a first hit's features.
 static void launch_features(rtmi_scene* s, dim3 grid, dim3 block, hipStream_t st, uint32_t npixels, uint32_t nsamples, const uint32_t* hit_tf,
                             const float* hit_t, float* albedo, float* normal, uint32_t* ids, uint32_t pix0, uint32_t W, uint32_t nsub, uint32_t sub,
                             const float4* qo, const float4* qd) {
-    if (s->has_nmap)
-        hipLaunchKernelGGL(k_features_nmap, grid, block, 0, st, s->d, npixels, nsamples, hit_tf, hit_t, albedo, normal, ids, pix0, W, nsub, sub,
-                           make_fastdiv(W), make_fastdiv(nsamples), qo, qd, s->smoothtab, s->textab, s->nmaptab);
-    else if (s->has_tex)
-        hipLaunchKernelGGL(k_features_tex, grid, block, 0, st, s->d, npixels, nsamples, hit_tf, hit_t, albedo, normal, ids, pix0, W, nsub, sub,
-                           make_fastdiv(W), make_fastdiv(nsamples), qo, qd, s->smoothtab, s->textab);
-    else if (s->has_normals)
-        hipLaunchKernelGGL(k_features_smooth, grid, block, 0, st, s->d, npixels, nsamples, hit_tf, hit_t, albedo, normal, ids, pix0, W, nsub, sub,
-                           make_fastdiv(W), make_fastdiv(nsamples), qo, qd, s->smoothtab);
-    else
-        hipLaunchKernelGGL(k_features, grid, block, 0, st, s->d, npixels, nsamples, hit_tf, hit_t, albedo, normal, ids, pix0, W, nsub, sub,
-                           make_fastdiv(W), make_fastdiv(nsamples));
+    auto go = [&](auto k, auto... tail) {
+        hipLaunchKernelGGL(k, grid, block, 0, st, s->d, npixels, nsamples, hit_tf, hit_t, albedo, normal, ids, pix0, W, nsub, sub,
+                           make_fastdiv(W), make_fastdiv(nsamples), tail...);
+    };
+    switch (shade_level(s)) {
+    case Shade::PLAIN:
+    case Shade::GLASS:
+    case Shade::ENV: go(k_features); break;
+    case Shade::SMOOTH: go(k_features_smooth, qo, qd, s->smoothtab); break;
+    case Shade::TEX: go(k_features_tex, qo, qd, s->smoothtab, s->textab); break;
+    case Shade::NMAP: go(k_features_nmap, qo, qd, s->smoothtab, s->textab, s->nmaptab); break;
+    }
 }
 
 // An envlight call walks its shadow rays with the scene's closest-hit launch on an octree: they leave a hit in every direction
@@ -3059,6 +2996,7 @@ static void launch_features(rtmi_scene* s, dim3 grid, dim3 block, hipStream_t st
 // (profiles/envlight_kernel_stats_anyhit.csv).  The linear list keeps its any-hit kernel, which stops at the first hit.
 static bool envlight_from_hits(const rtmi_scene* s, const TileCall& c) { return c.sh && c.sh->el && !s->root_is_leaf; }
 
+// The plan of a call: its streams, their sub-tiles and the batch size, with every stream's workspace sized for it.
 static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t* tile, TileCall& c) {
     const uint32_t nrows = tile->nrows, spp = c.spp;
     const uint64_t npix = (uint64_t)nrows * c.W;
@@ -3070,7 +3008,7 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
     // shades the primary rays in one kernel.  Everything else (pipeline 1, linear list, generic tree, BVH mode,
     // analytic spheres) starts with k_gen.  Both then run one closest-hit + one shading launch per bounce pass.
     c.path_kernels = !c.fo && !c.ao && !c.li && !c.pv && !c.sh && !c.cam && s->tune.pipeline != 1u && s->octree && !s->root_is_leaf &&
-                     !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) && s->d.nspheres == 0 && !s->has_dielectric && !s->has_env && !s->has_normals && !s->has_tex && !s->has_nmap;
+                     !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_BVH)) && s->d.nspheres == 0 && shade_level(s) == Shade::PLAIN;
     // streams = 0 (automatic): one stream for path-kernel tiles of 2^26 paths and more, three otherwise (the per-pass
     // pipelines -- BVH mode: 29.6 ms on three streams, 35.2 on one -- have elementwise kernels to hide).  Since k_shade stopped being
     // atomic-bound (round 3) there is little left for a second stream to hide: the full config-3 frame takes 366.9 ms on one
@@ -3209,7 +3147,7 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
     pa.v = dv; pa.seed = c.seed; pa.pix0 = pix0; pa.npaths = npaths;
     pa.mstack = w.mstack.p; pa.scol = w.scol.p; pa.slow = slow_queue(s, w);
     // the slow path: zero-component rays that k_path_primary and k_shade set aside, traced beside the following passes
-    const SlowQ sq = c.path_kernels ? pa.slow : SlowQ{nullptr, nullptr, nullptr, nullptr, 0u};
+    const SlowQ sq = c.path_kernels ? pa.slow : SLOW_OFF;
     auto slow_after = [&](uint32_t k) {  // after producer k: k_path_primary (0) or the shading of pass k
         if (sq.cap == 0u) return;
         (void)hipEventRecord(w.sev[k], st);
@@ -3356,7 +3294,7 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
         return RTMI_OK;
     }
     for (uint32_t pass = pass0; pass < c.maxdepth; pass++) {
-        const int a = pass & 1, b = a ^ 1;
+        const int a = pass & 1;
         HIPCHK(hipEventRecord(w.pass_ev[2 * pass], st));
         launch_trace(s, w, st, w.qo[a].p, w.qd[a].p, (int)pass, c.counting, w.pass_ev[2 * pass + 1]);
         HIPCHK(hipGetLastError());
@@ -3367,70 +3305,7 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
             int rc = dump_pass_counters(s, w, st, t, pass);
             if (rc != RTMI_OK) return rc;
         }
-        const bool glass = s->has_dielectric;  // (never with c.path_kernels: sq is off and k_path_slow, which has no glass arm, never runs)
-        // a scene with an environment (never with c.path_kernels either): the _env kernels, which also know glass
-        // a scene with vertex normals (never with c.path_kernels either): the _smooth kernels, which know glass and the environment
-        // (s->envtab.n = 0 without one)
-        // a scene with textures (never with c.path_kernels either): the _tex kernels, which know all of the above (s->smoothtab.n = 0
-        // without normals) and fold over the colour stack
-        // a scene with normal maps (it has textures): the _nmap kernels, which know all of that and the maps
-        if (s->has_nmap && list)
-            hipLaunchKernelGGL(k_shade_list_nmap, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
-                               w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, list, s->envtab,
-                               s->smoothtab, s->textab, w.cstack.p, s->nmaptab);
-        else if (s->has_nmap && c.mode == Samp::VIEWS)
-            hipLaunchKernelGGL(k_shade_views_nmap, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
-                               w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, c.vt, s->envtab,
-                               s->smoothtab, s->textab, w.cstack.p, s->nmaptab);
-        else if (s->has_nmap)
-            hipLaunchKernelGGL(c.mode == Samp::PASS ? k_shade_samples_nmap : k_shade_nmap, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths,
-                               (int)pass, w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p,
-                               w.mstack.p, w.scol.p, w.ctrl.p, sq, s->envtab, s->smoothtab, s->textab, w.cstack.p, s->nmaptab);
-        else if (s->has_tex && list)
-            hipLaunchKernelGGL(k_shade_list_tex, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
-                               w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, list, s->envtab,
-                               s->smoothtab, s->textab, w.cstack.p);
-        else if (s->has_tex && c.mode == Samp::VIEWS)
-            hipLaunchKernelGGL(k_shade_views_tex, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
-                               w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, c.vt, s->envtab,
-                               s->smoothtab, s->textab, w.cstack.p);
-        else if (s->has_tex)
-            hipLaunchKernelGGL(c.mode == Samp::PASS ? k_shade_samples_tex : k_shade_tex, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths,
-                               (int)pass, w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p,
-                               w.mstack.p, w.scol.p, w.ctrl.p, sq, s->envtab, s->smoothtab, s->textab, w.cstack.p);
-        else if (s->has_normals && list)
-            hipLaunchKernelGGL(k_shade_list_smooth, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
-                               w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, list, s->envtab,
-                               s->smoothtab);
-        else if (s->has_normals && c.mode == Samp::VIEWS)
-            hipLaunchKernelGGL(k_shade_views_smooth, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
-                               w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, c.vt, s->envtab,
-                               s->smoothtab);
-        else if (s->has_normals)
-            hipLaunchKernelGGL(c.mode == Samp::PASS ? k_shade_samples_smooth : k_shade_smooth, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths,
-                               (int)pass, w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p,
-                               w.mstack.p, w.scol.p, w.ctrl.p, sq, s->envtab, s->smoothtab);
-        else if (s->has_env && list)
-            hipLaunchKernelGGL(k_shade_list_env, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
-                               w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, list, s->envtab);
-        else if (s->has_env && c.mode == Samp::VIEWS)
-            hipLaunchKernelGGL(k_shade_views_env, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
-                               w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, c.vt, s->envtab);
-        else if (s->has_env)
-            hipLaunchKernelGGL(c.mode == Samp::PASS ? k_shade_samples_env : k_shade_env, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths,
-                               (int)pass, w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p,
-                               w.mstack.p, w.scol.p, w.ctrl.p, sq, s->envtab);
-        else if (list)
-            hipLaunchKernelGGL(glass ? k_shade_list_glass : k_shade_list, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
-                               w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, list);
-        else if (c.mode == Samp::VIEWS)
-            hipLaunchKernelGGL(glass ? k_shade_views_glass : k_shade_views, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, w.qo[a].p, w.qd[a].p,
-                               w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p, sq, c.vt);
-        else
-            hipLaunchKernelGGL(c.mode == Samp::PASS ? (glass ? k_shade_samples_glass : k_shade_samples) : (glass ? k_shade_glass : k_shade),
-                               ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths,
-                               (int)pass, w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p,
-                               w.mstack.p, w.scol.p, w.ctrl.p, sq);
+        launch_shade(s, w, st, c.mode, dv, c.seed, pix0, npaths, pass, w.qo[a].p, w.qd[a].p, w.scol.p, sq, list, c.vt);
         HIPCHK(hipGetLastError());
         if (pass + 1 < c.maxdepth) {  // the last pass's shading emits no rays
             slow_after(pass);
@@ -5001,33 +4876,15 @@ static int render_rays(rtmi_scene_t* s, uint64_t n, const void* orig4, const voi
         HIPCHK(hipGetLastError());
         if (make) qd = w.qd[0].p;
         for (uint32_t pass = 0; pass < npass; pass++) {
-            const int a = pass & 1, b = a ^ 1;
+            const int a = pass & 1;
             const float4 *pqo = pass ? w.qo[a].p : qo, *pqd = pass ? w.qd[a].p : qd;  // pass 0 traces the rays where they are
             HIPCHK(hipEventRecord(w.pass_ev[2 * pass], st));
             launch_trace(s, w, st, pqo, pqd, (int)pass, counting, w.pass_ev[2 * pass + 1]);
             HIPCHK(hipGetLastError());
             if (pass == 0 && guides)  // before pass 1 rewrites the hit records
                 launch_features(s, ew_grid, ew_block, st, ng, G, w.hit_tf.p, w.hit_t.p, (float*)albedo, (float*)normal, ids, 0u, ng, 1u, 0u, pqo, pqd);
-            if (shade && s->has_nmap)
-                hipLaunchKernelGGL(k_shade_rays_nmap, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(rp->pixel0 + gbase), nb, (int)pass, pqo, pqd,
-                                   w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, scol, w.ctrl.p,
-                                   SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, kq, s->envtab, s->smoothtab, s->textab, w.cstack.p, s->nmaptab);
-            else if (shade && s->has_tex)
-                hipLaunchKernelGGL(k_shade_rays_tex, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(rp->pixel0 + gbase), nb, (int)pass, pqo, pqd,
-                                   w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, scol, w.ctrl.p,
-                                   SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, kq, s->envtab, s->smoothtab, s->textab, w.cstack.p);
-            else if (shade && s->has_normals)
-                hipLaunchKernelGGL(k_shade_rays_smooth, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(rp->pixel0 + gbase), nb, (int)pass, pqo, pqd,
-                                   w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, scol, w.ctrl.p,
-                                   SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, kq, s->envtab, s->smoothtab);
-            else if (shade && s->has_env)
-                hipLaunchKernelGGL(k_shade_rays_env, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(rp->pixel0 + gbase), nb, (int)pass, pqo, pqd,
-                                   w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, scol, w.ctrl.p,
-                                   SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, kq, s->envtab);
-            else if (shade)
-                hipLaunchKernelGGL(s->has_dielectric ? k_shade_rays_glass : k_shade_rays, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(rp->pixel0 + gbase), nb, (int)pass, pqo, pqd,
-                                   w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, scol, w.ctrl.p,
-                                   SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, kq);
+            if (shade)
+                launch_shade(s, w, st, Samp::RAYS, dv, seed, (uint32_t)(rp->pixel0 + gbase), nb, pass, pqo, pqd, scol, SLOW_OFF, kq);
             HIPCHK(hipGetLastError());
         }
         if (shade && mean)
@@ -5199,7 +5056,7 @@ static int bake(rtmi_scene_t* s, uint64_t M, const void* pos4, const void* nrm4,
             if (out->dir) HIPCHK(hipMemcpyAsync((float4*)out->dir + base, qd, (size_t)nb * 16, hipMemcpyDeviceToHost, st));
         }
         for (uint32_t pass = 0; pass < npass; pass++) {
-            const int a = pass & 1, b = a ^ 1;
+            const int a = pass & 1;
             const float4 *pqo = pass ? w.qo[a].p : qo, *pqd = pass ? w.qd[a].p : qd;  // pass 0 traces the rays where they are
             HIPCHK(hipEventRecord(w.pass_ev[2 * pass], st));
             launch_trace(s, w, st, pqo, pqd, (int)pass, counting, w.pass_ev[2 * pass + 1]);
@@ -5207,27 +5064,8 @@ static int bake(rtmi_scene_t* s, uint64_t M, const void* pos4, const void* nrm4,
             if (pass == 0 && open)  // before pass 1 rewrites the hit records
                 hipLaunchKernelGGL(k_bake_open, dim3(std::min<unsigned>((unsigned)(s->num_cu * 8), (mb + RTMI_BAKE_OPEN_ELEMS - 1u) / RTMI_BAKE_OPEN_ELEMS)),
                                    ew_block, 0, st, mb, K, w.hit_tf.p, open);
-            if (shade && s->has_nmap)
-                hipLaunchKernelGGL(k_shade_rays_nmap, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(bp->pixel0 + mbase), nb, (int)pass, pqo, pqd,
-                                   w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p,
-                                   SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, (const uint32_t*)nullptr, s->envtab, s->smoothtab, s->textab, w.cstack.p,
-                                   s->nmaptab);
-            else if (shade && s->has_tex)
-                hipLaunchKernelGGL(k_shade_rays_tex, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(bp->pixel0 + mbase), nb, (int)pass, pqo, pqd,
-                                   w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p,
-                                   SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, (const uint32_t*)nullptr, s->envtab, s->smoothtab, s->textab, w.cstack.p);
-            else if (shade && s->has_normals)
-                hipLaunchKernelGGL(k_shade_rays_smooth, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(bp->pixel0 + mbase), nb, (int)pass, pqo, pqd,
-                                   w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p,
-                                   SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, (const uint32_t*)nullptr, s->envtab, s->smoothtab);
-            else if (shade && s->has_env)
-                hipLaunchKernelGGL(k_shade_rays_env, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(bp->pixel0 + mbase), nb, (int)pass, pqo, pqd,
-                                   w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p,
-                                   SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, (const uint32_t*)nullptr, s->envtab);
-            else if (shade)
-                hipLaunchKernelGGL(s->has_dielectric ? k_shade_rays_glass : k_shade_rays, ew_grid, ew_block, 0, st, s->d, dv, seed, (uint32_t)(bp->pixel0 + mbase), nb, (int)pass, pqo, pqd,
-                                   w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, w.scol.p, w.ctrl.p,
-                                   SlowQ{nullptr, nullptr, nullptr, nullptr, 0u}, (const uint32_t*)nullptr);
+            if (shade)
+                launch_shade(s, w, st, Samp::RAYS, dv, seed, (uint32_t)(bp->pixel0 + mbase), nb, pass, pqo, pqd, w.scol.p, SLOW_OFF);
             HIPCHK(hipGetLastError());
         }
         if (shade) hipLaunchKernelGGL(k_accum, ew_grid, ew_block, 0, st, mb, K, w.scol.p, (float*)light, 0u, mb, 1u, 0u, make_fastdiv(mb));

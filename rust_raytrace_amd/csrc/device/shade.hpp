@@ -228,14 +228,21 @@ __device__ inline V4 smooth_normal(const SmoothTab& sm, uint32_t tri, uint32_t f
     use = vdot(ns, ng) > 0.f && vdot(rd, ns) < 0.f;
     return ns;
 }
+// The shading level of a scene.  Every surface feature came with all earlier ones, so the kernels that shade a path form a ladder
+// and not a product: each level knows what the levels below it know, and a table of a lower level that the scene lacks is passed
+// empty (n = 0).  GLASS: RTMI_DIELECTRIC; ENV: + the environment; SMOOTH: + vertex normals; TEX: + textures and the colour stack;
+// NMAP: + normal maps (shade_hit below says what each adds).  The host picks a scene's level in one place, shade_level()
+// (rtmi_device.hip), and launches the level's kernels through launch_shade() and launch_features().
+enum class Shade { PLAIN, GLASS, ENV, SMOOTH, TEX, NMAP };
+
 // The bounce of one hit with normal `norm`: shade_hit's three arms (lambertian_ray, reflect_ray, the dielectric of include/rtmi.h)
 // statement for statement, for the kernels that may evaluate it twice (SMOOTH).  dir: the direction as passed to make_ray;
 // side: -1.f for a refracted ray, +1.f otherwise.
-template <bool GLASS>
+template <Shade L>
 __device__ inline RayV bounce_ray(uint32_t kind, float m1x, uint32_t face, V4 point, V4 norm, V4 rd, V4 rv, float u3, V4& dir, float& side) {
     float scat = m1x;
     side = 1.f;
-    if constexpr (GLASS) {
+    if constexpr (L >= Shade::GLASS) {
         if (kind == RTMI_DIELECTRIC) {  // m1x = ior
             const float ior = m1x;
             const float ci = fabsf(vdot(rd, norm));
@@ -400,6 +407,7 @@ __device__ inline V4 nmap_normal(float4 fr, V4 M, float strength, uint32_t face,
 // here: sky, Solid, edge face (Solid black, raytrace.rs:452-457) or depth exhausted (black, raytrace.rs:1261-1263); the
 // nested mix_color calls (raytrace.rs:1233-1251) are then evaluated inside-out over the stack and the sample colour is
 // written to scol[path].  `mirror` (optional): set to true when the path goes on through a Reflective surface.
+// L (Shade, above) adds to that, level by level:
 // GLASS: the kernels of scenes with a dielectric (k_shade*_glass, rtmi_device.hip) also know RTMI_DIELECTRIC, operation by
 // operation as include/rtmi.h defines it: the level is pushed like Matte's, the bounce ray is the refracted one or, on total
 // internal reflection or with Schlick's probability, reflect_ray's with scattering 0.f.  Without it (every other kernel, the
@@ -407,24 +415,25 @@ __device__ inline V4 nmap_normal(float4 fr, V4 M, float strength, uint32_t face,
 // ENV: the kernels of scenes with an environment (k_shade*_env) start a miss's fold at env_lookup(*env, rd) instead of the sky
 // constant -- rd must then be the ray's direction for a miss too -- and nothing else moves: no draw, no ray, black at an edge
 // face and at exhausted depth.  Without it `env` is never read.
-// SMOOTH: the kernels of scenes with vertex normals (k_shade*_smooth, always with GLASS and ENV) shade a bouncing triangle hit
+// SMOOTH: the kernels of scenes with vertex normals (k_shade*_smooth) shade a bouncing triangle hit
 // with smooth_normal's result where it is usable, and evaluate the bounce again with the geometric normal when the ray it gives
 // leaves on the wrong side of the real surface: same rv, same u3, no new draw.  Their `env` may be an empty table (n = 0: the
 // scene has normals and no environment), and a miss then starts at the sky constant.  Without it `sm` is never read.
-// TEX: the kernels of scenes with textures (k_shade*_tex, always with GLASS, ENV and SMOOTH; their `sm` may be an empty table too)
+// TEX: the kernels of scenes with textures (k_shade*_tex; their `sm` may be an empty table too)
 // give a triangle hit that is no edge face tex_colour's colour: a Solid hit ends with it, every other hit pushes it with the
 // material's alpha on the colour stack cstack[pass][path], and the fold reads the level's colour there and not in the material
 // table.  Nothing else moves.  Without it `tex` and `cstack` are never read.
-// NMAP: the kernels of scenes with normal maps (k_shade*_nmap, always with GLASS, ENV, SMOOTH and TEX) look the map up with the
+// NMAP: the kernels of scenes with normal maps (k_shade*_nmap) look the map up with the
 // colour (tex_colour_nmap: one (u, v)) and shade a bouncing hit of a mapped triangle with nmap_normal's result where it is usable;
 // the wrong-side rule is SMOOTH's with (use || usem).  The mapped normal is used where it is computed and is not stacked.
 // Without it `nm` is never read.
-template <bool GLASS = false, bool ENV = false, bool SMOOTH = false, bool TEX = false, bool NMAP = false>
+template <Shade L = Shade::PLAIN>
 __device__ inline bool shade_hit(const DScene& sc, uint32_t maxdepth, uint64_t seed, uint32_t npaths, uint32_t path, uint32_t pixel,
                                  uint32_t sample, uint32_t pass, uint32_t tf, float t, V4 ro, V4 rd, uint16_t* __restrict__ mstack,
                                  float4* __restrict__ scol, RayV& nr, bool* mirror = nullptr, const EnvTab* env = nullptr,
                                  const SmoothTab* sm = nullptr, const TexTab* tex = nullptr, float4* __restrict__ cstack = nullptr,
                                  const NmapTab* nm = nullptr) {
+    constexpr bool GLASS = L >= Shade::GLASS, ENV = L >= Shade::ENV, SMOOTH = L >= Shade::SMOOTH, TEX = L >= Shade::TEX, NMAP = L >= Shade::NMAP;
     const uint32_t tri = tf & 0x3FFFFFFFu, face = tf >> 30;
     V4 c;
     uint32_t npushed = pass;
@@ -486,7 +495,7 @@ __device__ inline bool shade_hit(const DScene& sc, uint32_t maxdepth, uint64_t s
                     for (;;) {
                         V4 dir;
                         float side;
-                        nr = bounce_ray<GLASS>(kind, m1.x, face, point, n, rd, rv, u3, dir, side);
+                        nr = bounce_ray<L>(kind, m1.x, face, point, n, rd, rv, u3, dir, side);
                         if (!use || side * vdot(dir, norm) > 0.f) break;
                         n = norm;  // the ray leaves on the wrong side of the real surface: the whole bounce again with ng
                         use = false;
