@@ -1254,8 +1254,8 @@ int rtmi_render_light(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t s
  *   shades with the answers, keeping one mask word per path (bit j = shadowed_j).  Nothing is copied to the host between
  *   passes.  The buffers (45 B per path at most beside the plain workspace, plus 8 B per path on scenes without an any-hit
  *   kernel) live on the handle, grow on demand and are freed by rtmi_scene_destroy.  No tuning changes a bit of the result.
- * Not here: several or coloured lights inside the path, more than one light sample per hit, falloff or a cosine term (the
- *   reference's test is binary), shadowed variants of rtmi_render_rays*, adaptive passes, batches of views,
+ * Not here: several or coloured lights inside the path, falloff or a cosine term (the reference's test is binary; light that
+ *   ADDS energy, with both: rtmi_render_lit*, "BOX LIGHTS IN THE PATH" below), more than one light sample per hit, shadowed variants of rtmi_render_rays*, adaptive passes, batches of views,
  *   rtmi_render_frame_multi and the path kernels (pipeline 3). */
 int rtmi_render_shadowed_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile,
                                 uint32_t sample0, uint32_t nsamples, const rtmi_light_t* light, void* accum_device,
@@ -1342,6 +1342,73 @@ int rtmi_render_envlight_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, 
 int rtmi_render_envlight(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
                          uint32_t sample0, uint32_t nsamples, const rtmi_envlight_t* env /* or NULL = defaults */, float* accum_host,
                          float* out_host /* or NULL */, rtmi_stats_t* stats);
+
+/* BOX LIGHTS IN THE PATH: direct light from up to four coloured box lights at every matte hit.  A box light
+ * (rtmi_light_t, the reference's LightSource { orig, len2 }) is not geometry: no bounce ray can hit one.  This progressive pass puts
+ * its light into the paths by next-event estimation: at every Matte hit that bounces, one shadow ray per light is sent to a point
+ * of the light's box, and what arrives unoccluded is added to the light the surface passes on.  NOT part of the reference (which
+ * declares the light and never uses it); build-defined like rtmi_render_light* and rtmi_render_envlight*: what follows IS the
+ * definition, and tests/lit_ref.py pins it bit for bit.  All arithmetic is f32 on all four lanes, every step rounded (no fused
+ * multiply-add), + - * / and sqrt only.
+ * Contract: rtmi_render_samples[_device]'s in every respect, as rtmi_render_shadowed* states it: samples [sample0, sample0 +
+ *   nsamples) of a frame of S samples, accum continued and rewritten, out (may be NULL) = accum * (1.f / (float)(sample0 +
+ *   nsamples)), the tile's layout, the stream's semantics, maxdepth == 0 writes zeros, an empty tile returns RTMI_OK.
+ * Paths: the rays of every pass are exactly those of rtmi_render_samples_device for the same arguments: no ray, no RNG block
+ *   0 .. maxdepth and no plain "Rays" count moves.
+ * Candidates: made at the hit of a path's ray number j when the hit is a Matte surface (neither a miss nor an edge face) and the
+ *   path bounces there (maxdepth - j - 1 != 0: an exhausted level gets no sample, as in rtmi_render_envlight*).  With point and n
+ *   as rtmi_render_shadowed* states them, for l = 0 .. nlights-1:
+ *     w      = RNG block 0xC0000000 | (l << 16) | j of (seed, pixel, sample); for l = 0 that is rtmi_render_shadowed*'s block.
+ *              Every light has a stream of its own: the lights' jitter is independent, unlike rtmi_render_preview*'s lights,
+ *              which share their blocks so that each layer equals its single call;
+ *     adj, v, d2, r, dir, o, c   exactly as rtmi_render_light* states them, from lights[l].orig, len2, bias;
+ *     culled when !(c > 0.f); otherwise visible iff rtmi_occluded's definition gives 0 for (o, dir, tmax = r), the NULL limit
+ *              when lights[l].flags has RTMI_LIGHT_UNBOUNDED;
+ *     g_l    = c, or with RTMI_LIT_INVERSE_SQUARE  c / d2.
+ * Direct light of a level: direct_j = (0, 0, 0, 0); then for l ascending over the live and visible candidates, per channel
+ *   ch = 0 .. 2:  direct_j[ch] = direct_j[ch] + light_color[l][ch] * g_l  (a multiplication, then an addition); lane 3 stays 0.
+ *   A Reflective level and an exhausted level have direct_j = 0.
+ * Colour: the fold is c = mix_color(color_j, c + direct_j, alpha_j), inside-out over the path's Matte / Reflective levels, as
+ *   in rtmi_render_envlight*.  A miss is the sky constant; on a scene with an environment it is the plain lookup of the ray's
+ *   direction, unweighted (there is no second estimator to balance against).  Solid ends, edge faces and the black of exhausted
+ *   depth as in color_ray.  No case is special: non-finite values propagate as the arithmetic gives them.
+ * Per pixel: rtmi_render_samples_device's sums.
+ * nlights == 0 is valid: no candidate kernel and no walk is launched.  The image is then rtmi_render_samples_device's wherever
+ *   no inner colour of a fold is -0.f (c + 0.f turns a -0.f into +0.f, which mix_color may show in the sign of a zero).
+ * Scenes: octree, linear list, generic tree and RTMI_OPT_GENERIC are exact; RTMI_OPT_FAST / RTMI_OPT_BVH give their own modes'
+ *   hits and answers.  With or without an environment.  RTMI_ERR_UNSUPPORTED, before any HIP call, for a scene with analytic
+ *   spheres, a dielectric, vertex normals, textures or normal maps; the handle stays usable.
+ * RTMI_ERR_INVALID, before any HIP call and before the scene is used, stats cleared: every check of
+ *   rtmi_render_samples[_device]; lit == NULL; nlights > RTMI_LIT_MAX_LIGHTS; unknown flag bits; every parameter check of
+ *   rtmi_render_light* on each used light (the message names the light's index), and rays != 1; a non-finite used colour.
+ * stats: as rtmi_render_shadowed* fills them: rays = the plain rays + the live candidates traced, trace_launches = 2 per pass
+ *   and batch (an empty event pair where no walk runs), primary_ms the closest-hit launches' share, bounce_ms the walks',
+ *   pipeline = 1, slow_paths = 0.
+ * How: rtmi_render_shadowed*'s pass structure: k_lit_rays builds a hit's candidates in registers and compacts the live ones
+ *   of all lights into ONE shadow queue per pass (one atomic per block of 256 paths), with one limit array (r, or +inf for an
+ *   unbounded light) and a float4 weight per entry; the occlusion walk of that queue (on an octree the scene's closest-hit
+ *   launch, which is faster than the any-hit kernel here as it is for rtmi_render_envlight*; the answers are the same);
+ *   k_shade_lit sums the weights of an entry's unoccluded candidates in l order and folds.  Beside the plain workspace, per
+ *   path and light: 53 B of queue, 4 B of slot and, on an octree, 12 B of hit records; per path and level 16 B (the direct
+ *   stack); allocated by this call only.  No tuning changes a bit.
+ * Not here: lights on smooth, textured, normal-mapped or glass scenes; more than one sample per light and hit; lights chosen
+ *   by importance; rtmi_render_envlight*'s sampling in the same pass; lights at Reflective or exhausted levels; adaptive
+ *   variants, view batches, rtmi_render_rays*, bake and denoised wrappers; the path kernels (pipeline 3). */
+enum { RTMI_LIT_MAX_LIGHTS = 4, RTMI_LIT_INVERSE_SQUARE = 1u << 0 };
+typedef struct rtmi_lit {
+    uint32_t nlights;          /* 0: 0..RTMI_LIT_MAX_LIGHTS                                                       */
+    uint32_t flags;            /* 4: RTMI_LIT_INVERSE_SQUARE or 0                                                 */
+    rtmi_light_t lights[4];    /* 8: entries >= nlights are ignored; rays must be 1; flags may hold               */
+                               /*    RTMI_LIGHT_UNBOUNDED                                                         */
+    float light_color[4][3];   /* 120: the radiance scale per light; any finite float                             */
+} rtmi_lit_t;                  /* 168 bytes */
+void rtmi_lit_defaults(rtmi_lit_t* lit);  /* nlights 0, flags 0, rtmi_light_defaults x 4 with rays = 1, colours 1 */
+int rtmi_render_lit_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile,
+                           uint32_t sample0, uint32_t nsamples, const rtmi_lit_t* lit, void* accum_device,
+                           void* out_device /* or NULL */, void* hip_stream, rtmi_stats_t* stats);
+int rtmi_render_lit(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
+                    uint32_t sample0, uint32_t nsamples, const rtmi_lit_t* lit, float* accum_host,
+                    float* out_host /* or NULL */, rtmi_stats_t* stats);
 
 /* A shaded preview in one call: albedo, ambient occlusion and up to four coloured box lights composed PER
  * SAMPLE on the device, from one primary pass per batch and one any-hit walk of the AO rays and every light's live shadow

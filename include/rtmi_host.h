@@ -246,6 +246,14 @@ int rth_caster_walk_envlight_device(rth_scene_t* s, uint32_t w, uint32_t h, cons
                                     void* accum_device, void* out_device, void* hip_stream, rtmi_stats_t* stats,
                                     double* wall_seconds);
 int rth_caster_env_sampler(rth_scene_t* s, uint32_t* q_out, uint64_t cap, uint64_t* total_out, uint32_t* n_out);
+/* Path tracing with up to four coloured box lights sampled at every matte hit (rtmi_render_lit / rtmi_render_lit_device in rtmi.h,
+ * which defines it): rth_caster_walk_samples[_device] in every respect; lit must not be NULL. */
+int rth_caster_walk_lit(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp, uint64_t row0,
+                        uint64_t nrows, uint32_t sample0, uint32_t nsamples, const rtmi_lit_t* lit, float* accum_host, float* out_host,
+                        rtmi_stats_t* stats, double* wall_seconds);
+int rth_caster_walk_lit_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                               const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, const rtmi_lit_t* lit, void* accum_device,
+                               void* out_device, void* hip_stream, rtmi_stats_t* stats, double* wall_seconds);
 /* Built-in camera models (rtmi_render_camera / rtmi_render_camera_device in rtmi.h, which defines them):
  * rth_caster_walk_samples[_device] in every respect, with the rays of `camera` (pinhole, thin lens, orthographic) and, when
  * guides is not NULL, rth_caster_walk_features' buffers of those rays. */

@@ -409,6 +409,7 @@ __global__ void __launch_bounds__(256) k_trace(DScene sc, const float4* __restri
 #include "bake.hpp"
 #include "shadowed.hpp"
 #include "envlight.hpp"
+#include "lit.hpp"
 namespace rtmi {
 
 
@@ -1286,6 +1287,8 @@ struct rtmi_scene {
         // ([pass][path]) and each path's balance weight.  Allocated by that call only.
         DevBuf<float4> lw, dstack;
         DevBuf<float> wb;
+        // rtmi_render_lit*, the same pass structure with up to nlights shadow rays per path and pass: qo, qd, tmax, lw and occ then
+        // hold paths * nlights entries, slot paths * nlights words ([light][path]); dstack as above.  Sized by that call only.
         Work walk;
         void release() { qo.release(); qd.release(); tmax.release(); slot.release(); mask.release(); occ.release(); lw.release(); dstack.release(); wb.release(); walk.release(); }
     } shadow[RTMI_MAX_STREAMS];
@@ -1304,6 +1307,7 @@ struct rtmi_scene {
     rtmi_tuning_t tune{};
     bool verbose = false;
     int vote[4] = {3, 2, 3, 2};  // SELECT : LEAF vote weights of the walk, primary rays / bounce rays (experiments: RTMI_VOTE="a,b,c,d")
+    int lit_from_hits = 1;       // rtmi_render_lit* walks its shadow rays with the closest-hit launch on an octree (RTMI_LIT_FROM_HITS=0: the any-hit kernel, for comparison)
     int occl_from_hits = 0;      // rtmi_occluded* runs the closest-hit launch + k_occl_from_hits everywhere (RTMI_OCCLUDED_ANYHIT=0, for comparison)
     int block_cull = 1;          // k_trace_oct skips reference blocks by their cull records (RTMI_BLOCK_CULL=0: off, no records)
     int block_cull_n = 4;        // cull records a LEAF step of k_trace_oct reads, 2..4 (experiments: RTMI_BLOCK_CULL_N)
@@ -1870,6 +1874,7 @@ int rtmi_scene_create(const rtmi_triangle_t* tris, uint64_t ntris, const rtmi_bo
     if (const char* v = getenv("RTMI_HYBRID")) s->hybrid = strcmp(v, "0") != 0;
     if (const char* v = getenv("RTMI_PRIMARY_NODE_CULL")) s->primary_node_cull = strcmp(v, "0") != 0;
     if (const char* v = getenv("RTMI_OCCLUDED_ANYHIT")) s->occl_from_hits = strcmp(v, "0") == 0;
+    if (const char* v = getenv("RTMI_LIT_FROM_HITS")) s->lit_from_hits = strcmp(v, "0") != 0;
     if (const char* v = getenv("RTMI_DENOISE_LDS_STEP")) s->dn_lds_max_step = std::min<uint32_t>((uint32_t)strtoul(v, nullptr, 10), DN_LDS_MAX_STEP);
     if (const char* v = getenv("RTMI_DENOISE_VAR_LDS_STEP")) s->dnv_lds_max_step = std::min<uint32_t>((uint32_t)strtoul(v, nullptr, 10), DN_LDS_MAX_STEP);
     if (const char* v = getenv("RTMI_MIRROR_INPLACE")) {
@@ -2878,7 +2883,9 @@ struct PreviewCall {
 // A shadowed path-trace (rtmi_render_shadowed*): the light every surface hit of every bounce is tested against
 // el != nullptr: an envlight path-trace (rtmi_render_envlight*), the same pass structure with k_envlight_rays and k_shade_envlight;
 // p is then an unbounded light that is never read beyond its flags (no tmax)
-struct ShadowCall { rtmi_light_t p; const rtmi_envlight_t* el = nullptr; };
+// lit != nullptr: a lit path-trace (rtmi_render_lit*), the same pass structure with k_lit_rays and k_shade_lit and up to
+// lit->nlights shadow rays per path and pass; p is then never read
+struct ShadowCall { rtmi_light_t p; const rtmi_envlight_t* el = nullptr; const LitArgs* lit = nullptr; };
 // A camera call (rtmi_render_camera*): the model k_gen_camera generates the rays of, and the guides of those rays (each may be null)
 struct CameraCall { DCam cam; FeatOut fo; };
 // One render_tile call: what it renders, and its plan (plan_tile)
@@ -2995,6 +3002,12 @@ static void launch_features(rtmi_scene* s, dim3 grid, dim3 block, hipStream_t st
 // k_occluded_oct per 16 samples for 10 M shadow rays, against 26 ms of closest-hit launches for the 94 M path rays
 // (profiles/envlight_kernel_stats_anyhit.csv).  The linear list keeps its any-hit kernel, which stops at the first hit.
 static bool envlight_from_hits(const rtmi_scene* s, const TileCall& c) { return c.sh && c.sh->el && !s->root_is_leaf; }
+// A lit call walks its shadow rays with the scene's closest-hit launch on an octree too, although they end at a lamp and four in
+// ten of them meet an occluder, where the any-hit kernel stops: measured on the canonical 2048 x 2048 frame with lights A + B,
+// 20.4 M shadow rays per 16 samples cost k_occluded_oct 59.9 ms and the hybrid pass 12.2 ms on top of the path rays' 26.3 ms
+// (profiles/lit_kernel_stats_anyhit.csv against lit_kernel_stats.csv).  RTMI_LIT_FROM_HITS=0 brings the any-hit
+// kernel back for that comparison; the answers are the same bytes.  The linear list keeps its any-hit kernel.
+static bool lit_from_hits(const rtmi_scene* s, const TileCall& c) { return c.sh && c.sh->lit && s->lit_from_hits && !s->root_is_leaf; }
 
 // The plan of a call: its streams, their sub-tiles and the batch size, with every stream's workspace sized for it.
 static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t* tile, TileCall& c) {
@@ -3091,7 +3104,20 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
             HIPCHK(b.qo.ensure(nao)); HIPCHK(b.qd.ensure(nao)); HIPCHK(b.tmax.ensure(nao)); HIPCHK(b.c.ensure(nao)); HIPCHK(b.occ.ensure(nao));
             HIPCHK(b.alb.ensure(paths)); HIPCHK(b.aslot.ensure(paths)); HIPCHK(b.lslot.ensure(paths * (c.pv->per_path - c.pv->a.Ka)));
         }
-        if (c.sh) {  // a pass tests at most one ray per path
+        if (c.sh && c.sh->lit) {  // a pass tests at most nlights rays per path: every queue of the walk holds paths * nlights entries
+            rtmi_scene::ShadowBuf& b = s->shadow[t];
+            const size_t nq = paths * c.sh->lit->nlights;
+            HIPCHK(b.qo.ensure(nq)); HIPCHK(b.qd.ensure(nq)); HIPCHK(b.tmax.ensure(nq)); HIPCHK(b.lw.ensure(nq)); HIPCHK(b.occ.ensure(nq));
+            HIPCHK(b.slot.ensure(nq)); HIPCHK(b.dstack.ensure(paths * c.maxdepth));
+            HIPCHK(b.walk.ctrl.ensure(1));
+            if (nq && (!occluded_anyhit(s) || lit_from_hits(s, c))) { HIPCHK(b.walk.hit_tf.ensure(nq)); HIPCHK(b.walk.hit_t.ensure(nq)); }
+            if (nq && lit_from_hits(s, c)) HIPCHK(b.walk.fb.ensure(b.walk.hit_tf.n));
+            while (b.walk.pass_ev.size() < 2 * (size_t)c.maxdepth) {
+                hipEvent_t e;
+                HIPCHK(hipEventCreate(&e));
+                b.walk.pass_ev.push_back(e);
+            }
+        } else if (c.sh) {  // a pass tests at most one ray per path
             rtmi_scene::ShadowBuf& b = s->shadow[t];
             HIPCHK(b.qo.ensure(paths)); HIPCHK(b.qd.ensure(paths)); HIPCHK(b.slot.ensure(paths)); HIPCHK(b.mask.ensure(paths)); HIPCHK(b.occ.ensure(paths));
             if (!(c.sh->p.flags & RTMI_LIGHT_UNBOUNDED)) HIPCHK(b.tmax.ensure(paths));
@@ -3256,6 +3282,26 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
             launch_trace(s, w, st, w.qo[a].p, w.qd[a].p, (int)pass, c.counting, w.pass_ev[2 * pass + 1]);
             HIPCHK(hipGetLastError());
             // sb.walk.ctrl->count[pass + 1] (zero since the memset above) is the compaction's counter and then the walk's ray count
+            if (c.sh->lit) {
+                const LitArgs& la = *c.sh->lit;
+                if (c.maxdepth - pass - 1u != 0u && la.nlights != 0u) {
+                    hipLaunchKernelGGL(k_lit_rays, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, la, w.qo[a].p, w.qd[a].p,
+                                       w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.ctrl.p, sb.qo.p, sb.qd.p, sb.tmax.p, sb.lw.p, sb.slot.p,
+                                       sb.walk.ctrl.p);
+                    HIPCHK(hipEventRecord(sb.walk.pass_ev[2 * pass], st));
+                    launch_occluded(s, sb.walk, st, (uint64_t)npaths * la.nlights, sb.qo.p, sb.qd.p, sb.tmax.p, sb.occ.p, (int)pass + 1,
+                                    sb.walk.pass_ev[2 * pass + 1], lit_from_hits(s, c));
+                    HIPCHK(hipGetLastError());
+                } else {  // no candidates (the exhausted level, or no lights): no walk, an empty event pair for collect_batch
+                    HIPCHK(hipEventRecord(sb.walk.pass_ev[2 * pass], st));
+                    HIPCHK(hipEventRecord(sb.walk.pass_ev[2 * pass + 1], st));
+                }
+                hipLaunchKernelGGL(s->has_env ? k_shade_lit<true> : k_shade_lit<false>, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths,
+                                   (int)pass, s->envtab, la.nlights, w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, sb.slot.p, sb.occ.p,
+                                   sb.lw.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, sb.dstack.p, w.scol.p, w.ctrl.p);
+                HIPCHK(hipGetLastError());
+                continue;
+            }
             if (c.sh->el) {
                 if (c.maxdepth - pass - 1u != 0u) {
                     hipLaunchKernelGGL(k_envlight_rays, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, (int)pass, s->envtab, s->envsamp,
@@ -4036,6 +4082,114 @@ int rtmi_render_envlight(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t se
     if (out_host) HIPCHK(s->tile.ensure(npix));
     if (sample0 > 0) HIPCHK(hipMemcpy(s->acc.p, accum_host, npix * sizeof(float4), hipMemcpyHostToDevice));
     rc = rtmi_render_envlight_device(s, vp, seed, &tile, sample0, nsamples, el, s->acc.p, out_host ? (void*)s->tile.p : nullptr, nullptr, stats);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(hipMemcpy(accum_host, s->acc.p, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    if (out_host) HIPCHK(hipMemcpy(out_host, s->tile.p, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+// ---------------------------------------------------------------- box lights in the path (rtmi_render_lit*)
+void rtmi_lit_defaults(rtmi_lit_t* p) {
+    if (!p) return;
+    p->nlights = 0; p->flags = 0;
+    for (int l = 0; l < RTMI_LIT_MAX_LIGHTS; l++) {
+        rtmi_light_defaults(&p->lights[l]);
+        p->lights[l].rays = 1;
+        p->light_color[l][0] = p->light_color[l][1] = p->light_color[l][2] = 1.f;
+    }
+}
+
+// Checks of the lit entry points that come before any HIP call and before the scene is used: rtmi_render_samples_device's, then
+// the parameters, each used light as rtmi_render_shadowed* checks its one
+static int check_lit(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint32_t sample0, uint32_t nsamples, const rtmi_lit_t* p, const void* accum,
+                     const void* out) {
+    const int rc = check_samples(s, vp, sample0, nsamples, accum, out);
+    if (rc != RTMI_OK) return rc;
+    if (!p) return fail(RTMI_ERR_INVALID, "lit: NULL argument (rtmi_lit_t)");
+    if (p->nlights > (uint32_t)RTMI_LIT_MAX_LIGHTS) return fail(RTMI_ERR_INVALID, "lit: nlights above RTMI_LIT_MAX_LIGHTS");
+    if (p->flags & ~(uint32_t)RTMI_LIT_INVERSE_SQUARE) return fail(RTMI_ERR_INVALID, "lit: unknown flags");
+    for (uint32_t l = 0; l < p->nlights; l++) {
+        const rtmi_light_t& li = p->lights[l];
+        char msg[160];
+        const char* bad = nullptr;
+        if (li.rays == 0 || li.rays > 256) bad = "rays must be in [1, 256]";
+        else if (li.flags & ~(uint32_t)RTMI_LIGHT_UNBOUNDED) bad = "unknown flags";
+        else if (!(li.len2 >= 0.f) || std::isinf(li.len2)) bad = "len2 must be >= 0, finite and not NaN";
+        else if (!std::isfinite(li.orig[0]) || !std::isfinite(li.orig[1]) || !std::isfinite(li.orig[2])) bad = "orig must be finite";
+        else if (!std::isfinite(li.bias)) bad = "bias must be finite";
+        else if (li.rays != 1) bad = "rays must be 1 (one shadow ray per light and hit)";
+        else if (!std::isfinite(p->light_color[l][0]) || !std::isfinite(p->light_color[l][1]) || !std::isfinite(p->light_color[l][2]))
+            bad = "light_color must be finite";
+        if (bad) {
+            snprintf(msg, sizeof msg, "lit: light %u: %s", l, bad);
+            return fail(RTMI_ERR_INVALID, msg);
+        }
+    }
+    return RTMI_OK;
+}
+// scenes the lit shading (lit.hpp has its own shade_hit) does not take; before any HIP call.  An environment is fine.
+static int refuse_scene_lit(const rtmi_scene_t* s) {
+    if (s->d.nspheres)
+        return fail(RTMI_ERR_UNSUPPORTED, "lit: the scene has analytic spheres (a build-defined primitive whose normal needs the hit point)");
+    if (s->has_dielectric) return fail(RTMI_ERR_UNSUPPORTED, "lit: the scene has a dielectric surface (the lit shading has no glass arm)");
+    if (s->has_normals) return fail(RTMI_ERR_UNSUPPORTED, "lit: the scene has vertex normals (the lit shading has no smooth arm)");
+    if (s->has_nmap) return fail(RTMI_ERR_UNSUPPORTED, "lit: the scene has normal maps (the lit shading has no normal-map arm)");
+    if (s->has_tex) return fail(RTMI_ERR_UNSUPPORTED, "lit: the scene has textures (the lit shading has no texture arm)");
+    return RTMI_OK;
+}
+static LitArgs lit_args(const rtmi_lit_t& p) {
+    LitArgs a{};
+    a.nlights = p.nlights;
+    a.inverse_square = (p.flags & RTMI_LIT_INVERSE_SQUARE) ? 1u : 0u;
+    for (uint32_t l = 0; l < p.nlights; l++) {
+        const rtmi_light_t& li = p.lights[l];
+        LitLight& d = a.li[l];
+        d.orig = mk(li.orig[0], li.orig[1], li.orig[2]);
+        d.len2 = li.len2; d.bias = li.bias;
+        d.unbounded = (li.flags & RTMI_LIGHT_UNBOUNDED) ? 1u : 0u;
+        for (int c = 0; c < 3; c++) d.col[c] = p.light_color[l][c];
+    }
+    return a;
+}
+
+int rtmi_render_lit_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile, uint32_t sample0,
+                           uint32_t nsamples, const rtmi_lit_t* lit, void* accum_device, void* out_device, void* hip_stream,
+                           rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    int rc = check_lit(s, vp, sample0, nsamples, lit, accum_device, out_device);
+    if (rc != RTMI_OK) return rc;
+    if (!tile) return fail(RTMI_ERR_INVALID, "NULL argument (tile)");
+    if (tile->nrows == 0) return RTMI_OK;
+    rc = check_view(vp, tile);
+    if (rc != RTMI_OK) return rc;
+    rc = refuse_scene_lit(s);
+    if (rc != RTMI_OK) return rc;
+    const LitArgs la = lit_args(*lit);
+    ShadowCall call{};
+    call.lit = &la;
+    return render_tile(s, vp, seed, tile, sample0, nsamples, (float4*)accum_device, out_device, hip_stream, stats, nullptr, 0, nullptr,
+                       nullptr, nullptr, nullptr, &call);
+}
+
+// Host variant: rtmi_render_samples' copies (accum in only when sample0 > 0, accum and out back).
+int rtmi_render_lit(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows, uint32_t sample0,
+                    uint32_t nsamples, const rtmi_lit_t* lit, float* accum_host, float* out_host, rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    int rc = check_lit(s, vp, sample0, nsamples, lit, accum_host, out_host);
+    if (rc != RTMI_OK) return rc;
+    const uint64_t npix = (uint64_t)nrows * vp->width;
+    if (npix == 0) return RTMI_OK;
+    if ((uint64_t)row0 + nrows > vp->height) return fail(RTMI_ERR_INVALID, "row range outside the viewport");
+    const rtmi_tile_t tile{row0, nrows, nrows, 0u};
+    rc = check_view(vp, &tile);
+    if (rc != RTMI_OK) return rc;
+    rc = refuse_scene_lit(s);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(s->acc.ensure(npix));
+    if (out_host) HIPCHK(s->tile.ensure(npix));
+    if (sample0 > 0) HIPCHK(hipMemcpy(s->acc.p, accum_host, npix * sizeof(float4), hipMemcpyHostToDevice));
+    rc = rtmi_render_lit_device(s, vp, seed, &tile, sample0, nsamples, lit, s->acc.p, out_host ? (void*)s->tile.p : nullptr, nullptr, stats);
     if (rc != RTMI_OK) return rc;
     HIPCHK(hipMemcpy(accum_host, s->acc.p, npix * sizeof(float4), hipMemcpyDeviceToHost));
     if (out_host) HIPCHK(hipMemcpy(out_host, s->tile.p, npix * sizeof(float4), hipMemcpyDeviceToHost));

@@ -760,6 +760,34 @@ int rth_caster_walk_envlight_device(rth_scene_t* s, uint32_t w, uint32_t h, cons
         if (stats) *stats = ctx.stats;
     });
 }
+int rth_caster_walk_lit(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp, uint64_t row0,
+                        uint64_t nrows, uint32_t sample0, uint32_t nsamples, const rtmi_lit_t* lit, float* accum_host, float* out_host,
+                        rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!lit) throw std::runtime_error("NULL rtmi_lit_t");
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_rays_lit(v, s->scene, (size_t)row0, (size_t)nrows, sample0, nsamples, *lit, reinterpret_cast<Color*>(accum_host),
+                                   reinterpret_cast<Color*>(out_host), ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
+int rth_caster_walk_lit_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                               const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, const rtmi_lit_t* lit, void* accum_device,
+                               void* out_device, void* hip_stream, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!tile) throw std::runtime_error("NULL tile");
+        if (!lit) throw std::runtime_error("NULL rtmi_lit_t");
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_lit_device(v, s->scene, *tile, sample0, nsamples, *lit, accum_device, out_device, hip_stream, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
 int rth_caster_env_sampler(rth_scene_t* s, uint32_t* q_out, uint64_t cap, uint64_t* total_out, uint32_t* n_out) {
     return guarded([&] {
         if (!n_out) throw std::runtime_error("rth_caster_env_sampler: NULL n_out");

@@ -1117,6 +1117,31 @@ void HipRayCaster::walk_envlight_device(const Viewport& v, const Scene& s, const
     progress.stats = st;
 }
 
+void HipRayCaster::walk_rays_lit(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
+                                 const rtmi_lit_t& lit, Color* accum, Color* out, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_lit(h, &av, seed, (uint32_t)row0, (uint32_t)nrows, sample0, nsamples, &lit, reinterpret_cast<float*>(accum),
+                                   reinterpret_cast<float*>(out), &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_lit: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
+void HipRayCaster::walk_lit_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
+                                   const rtmi_lit_t& lit, void* accum_device, void* out_device, void* hip_stream, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_lit_device(h, &av, seed, &tile, sample0, nsamples, &lit, accum_device, out_device, hip_stream, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_lit_device: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
 std::vector<uint32_t> HipRayCaster::env_sampler(const Scene& s, uint32_t& n, uint64_t& total) {
     n = 0;
     total = 0;

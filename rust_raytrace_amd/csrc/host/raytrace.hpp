@@ -315,6 +315,12 @@ public:
                             const rtmi_envlight_t& env, Color* accum, Color* out, ProgressCtx& progress);
     void walk_envlight_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
                               const rtmi_envlight_t& env, void* accum_device, void* out_device, void* hip_stream, ProgressCtx& progress);
+    // Path tracing with box lights sampled at every matte hit (rtmi_render_lit / rtmi_render_lit_device, which rtmi.h defines):
+    // walk_samples / walk_samples_device in every respect.
+    void walk_rays_lit(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
+                       const rtmi_lit_t& lit, Color* accum, Color* out, ProgressCtx& progress);
+    void walk_lit_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
+                         const rtmi_lit_t& lit, void* accum_device, void* out_device, void* hip_stream, ProgressCtx& progress);
     // The sampler table of the environment of the scene's resident copy on the first device (rtmi_scene_get_env_sampler): n * n
     // weights and their sum, empty and n = 0 when the scene has no environment.
     std::vector<uint32_t> env_sampler(const Scene& s, uint32_t& n, uint64_t& total);

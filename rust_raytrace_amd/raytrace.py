@@ -1240,6 +1240,98 @@ class HipRayCaster:
         _chk(_ffi.lib().rth_caster_env_sampler(s.h, _p(q), q.size, C.byref(total), C.byref(n)))
         return q, int(total.value)
 
+    LIT_MAX_LIGHTS = _ffi.LIT_MAX_LIGHTS
+    LIT_INVERSE_SQUARE = _ffi.LIT_INVERSE_SQUARE
+
+    @staticmethod
+    def lit_params(lights=(), inverse_square=False):
+        """rtmi_lit_t from the library's defaults (rtmi_lit_defaults: no lights, white, one ray each) with the given lights: up to
+        four dicts of orig, len2, bias (light_params' arguments), color = three finite numbers (default white) and either
+        unbounded=True or flags=LIGHT_UNBOUNDED, as preview_params takes them (one shadow ray per light and hit: no rays key).
+        inverse_square: the light's cosine is divided by the squared distance.  Raises ValueError for what the library would
+        refuse."""
+        p = _ffi.Lit()
+        _ffi.lib().rtmi_lit_defaults(C.byref(p))
+        lights = list(lights)
+        if len(lights) > HipRayCaster.LIT_MAX_LIGHTS:
+            raise ValueError(f"at most {HipRayCaster.LIT_MAX_LIGHTS} lights")
+        for l, li in enumerate(lights):
+            kw = dict(li)
+            unknown = set(kw) - {"orig", "len2", "unbounded", "flags", "bias", "color"}
+            if unknown:
+                raise ValueError(f"light {l}: unknown keys {sorted(unknown)}")
+            col = kw.pop("color", None)
+            flags = kw.pop("flags", None)
+            if flags is not None:
+                if int(flags) & ~HipRayCaster.LIGHT_UNBOUNDED:
+                    raise ValueError(f"light {l}: unknown flags")
+                kw["unbounded"] = bool(kw.get("unbounded")) or bool(int(flags) & HipRayCaster.LIGHT_UNBOUNDED)
+            if kw.get("orig") is None:
+                raise ValueError(f"light {l}: orig (the light's corner) is needed")
+            try:
+                p.lights[l] = HipRayCaster.light_params(rays=1, **kw)
+            except ValueError as e:
+                raise ValueError(f"light {l}: {e}") from None
+            if col is not None:
+                c = [float(x) for x in col]
+                if len(c) != 3 or not all(np.isfinite(x) for x in c):
+                    raise ValueError(f"light {l}: color must be three finite numbers")
+                p.light_color[l][0], p.light_color[l][1], p.light_color[l][2] = c
+        p.nlights = len(lights)
+        p.flags = HipRayCaster.LIT_INVERSE_SQUARE if inverse_square else 0
+        return p
+
+    def walk_rays_lit(self, v, s, lit, data=None, sample0=0, nsamples=None, accum=None):
+        """Path tracing of the whole frame with box lights sampled at every Matte hit that bounces (rtmi_render_lit; include/rtmi.h
+        defines it): walk_rays' paths, and at each such hit one shadow ray per light of `lit` (lit_params' result, or its lights
+        argument) whose unoccluded light is added to what the surface passes on.  Samples [sample0, sample0 + nsamples) (default:
+        all from sample0) of the frame's v.samples_per_pixel; data and accum as in walk_rays_shadowed.
+        Returns (data, ctx); ctx.accum is the sums."""
+        k0, n = self._feature_samples(v, sample0, nsamples)
+        a = lit if isinstance(lit, _ffi.Lit) else self.lit_params(lit)
+        shape = (v.height, v.width, 4)
+        bufs = []
+        for name, x in (("data", data), ("accum", accum)):
+            if x is None:
+                x = np.zeros(shape, np.float32)
+            elif not isinstance(x, np.ndarray) or x.dtype != np.float32 or not x.flags.c_contiguous or x.size != v.height * v.width * 4:
+                raise ValueError(f"{name} must be a C-contiguous float32 array of height*width*4 elements")
+            bufs.append(x)
+        if np.shares_memory(bufs[0], bufs[1]):
+            raise ValueError("data and accum must not alias")
+        if k0 > 0 and accum is None:
+            raise ValueError("sample0 > 0 continues the sums of the earlier samples: pass their accum")
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_lit(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, 0, v.height, k0, n,
+                                            C.byref(a), _p(bufs[1]), _p(bufs[0]), C.byref(st), C.byref(wall)))
+        ctx = ProgressCtx(st.rays, wall.value, st.as_dict())
+        ctx.accum = bufs[1]
+        return bufs[0], ctx
+
+    def walk_rays_lit_device(self, v, s, lit, accum, out=None, tile=None, sample0=0, nsamples=None, stream=None):
+        """The same on torch tensors on the scene's device (rtmi_render_lit_device) for a striped row set tile = (row0, nrows,
+        stripe_rows, stripe_step) (default: the whole frame); accum, out and stream as in walk_rays_shadowed_device.
+        Returns ctx."""
+        k0, n = self._feature_samples(v, sample0, nsamples)
+        a = lit if isinstance(lit, _ffi.Lit) else self.lit_params(lit)
+        t = _ffi.Tile(*[int(x) for x in (tile if tile is not None else (0, v.height, v.height, 0))])
+        want = int(t.nrows) * int(v.width) * 4
+        for name, x in (("accum", accum), ("out", out)):
+            if (x is not None or name == "accum") and (not hasattr(x, "data_ptr") or not x.is_cuda or str(x.dtype) != "torch.float32"
+                                                       or not x.is_contiguous() or x.numel() != want):
+                raise ValueError(f"{name} must be a contiguous float32 tensor of {want} elements on the device")
+        if out is not None and abs(accum.data_ptr() - out.data_ptr()) < 4 * want:
+            raise ValueError("accum and out must not overlap")
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_lit_device(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, C.byref(t), k0, n,
+                                                   C.byref(a), C.c_void_p(accum.data_ptr()), C.c_void_p(out.data_ptr() if out is not None else 0),
+                                                   C.c_void_p(getattr(stream, "cuda_stream", stream) or 0), C.byref(st), C.byref(wall)))
+        return ProgressCtx(st.rays, wall.value, st.as_dict())
+
     PREVIEW_MAX_LIGHTS = _ffi.PREVIEW_MAX_LIGHTS
     _PREVIEW_OUTPUTS = ("color", "albedo", "normal", "ids", "ao", "shadow", "irradiance")  # rtmi_preview_out_t's order
 
