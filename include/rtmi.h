@@ -974,7 +974,8 @@ int rtmi_render_rays(rtmi_scene_t* scene, uint64_t n, const float* orig4, const 
  *   RTMI_ERR_INVALID: a NULL pos4 or nrm4; all four outputs NULL; two buffers overlapping as byte ranges, inputs included
  *     (16 M or 48 M, 16 M; 16 M, 4 M, 16 M K, 16 M K); pixel0 + M - 1 >= 2^32;
  *   RTMI_ERR_UNSUPPORTED: rays > 65536; maxdepth > 32; M K >= 2^31.
- * Not here: importance sampling towards lights, the shadowed path variant (rtmi_render_shadowed*'s shading), the path kernels
+ * Not here: box lights (rtmi_bake_lit*, "BOX LIGHTS ON EXPLICIT RAYS AND IN THE BAKE" below, samples them at the element and at
+ * every Matte bounce), the shadowed path variant (rtmi_render_shadowed*'s shading), the path kernels
  * (pipeline 3), several streams or devices, progressive continuation of a bake across calls, filtering of a lightmap. */
 enum { RTMI_BAKE_POINTS = 0, RTMI_BAKE_TRIANGLES = 1 };
 typedef struct rtmi_bake {
@@ -1393,7 +1394,8 @@ int rtmi_render_envlight(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_
  *   stack); allocated by this call only.  No tuning changes a bit.
  * Not here: lights on smooth, textured, normal-mapped or glass scenes; more than one sample per light and hit; lights chosen
  *   by importance; rtmi_render_envlight*'s sampling in the same pass; lights at Reflective or exhausted levels; adaptive
- *   variants, view batches, rtmi_render_rays*, bake and denoised wrappers; the path kernels (pipeline 3). */
+ *   variants, view batches and denoised wrappers; the path kernels (pipeline 3).  (Explicit rays and the bake with these lights:
+ *   rtmi_render_rays_lit*, rtmi_bake_lit*, below.) */
 enum { RTMI_LIT_MAX_LIGHTS = 4, RTMI_LIT_INVERSE_SQUARE = 1u << 0 };
 typedef struct rtmi_lit {
     uint32_t nlights;          /* 0: 0..RTMI_LIT_MAX_LIGHTS                                                       */
@@ -1409,6 +1411,75 @@ int rtmi_render_lit_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint6
 int rtmi_render_lit(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
                     uint32_t sample0, uint32_t nsamples, const rtmi_lit_t* lit, float* accum_host,
                     float* out_host /* or NULL */, rtmi_stats_t* stats);
+
+/* BOX LIGHTS ON EXPLICIT RAYS AND IN THE BAKE.  Build-defined like the calls they extend; what follows IS the
+ * definition, and tests/bake_lit_ref.py pins it bit for bit.  f32 on all four lanes, every step rounded, no fused multiply-add.
+ *
+ * rtmi_render_rays_lit[_device]: rtmi_render_rays[_device] with "BOX LIGHTS IN THE PATH" above in every path.
+ * Contract: rtmi_render_rays*'s in every respect: groups, RTMI_RAYS_MAKE_RAY, keys or the ray's place in its group, color / mean /
+ *   albedo / normal / ids, batches of whole groups, the stream's semantics, maxdepth == 0.  The paths, the RNG blocks 0 .. maxdepth,
+ *   the plain ray count and the guide buffers are rtmi_render_rays*'s for the same arguments.
+ * Candidates: at the hit of a path's ray number j that is a Matte surface and bounces (maxdepth - j - 1 != 0), exactly as
+ *   rtmi_render_lit* states them: w = RNG block 0xC0000000 | (l << 16) | j of the ray's key (seed, pixel, sample), the key
+ *   rtmi_render_rays* gives the ray (its keys entry, or pixel0 + its group and its place in the group); adj, v, d2, r, dir, o, c;
+ *   culled when !(c > 0.f); the limit r, or none for RTMI_LIGHT_UNBOUNDED; g_l, RTMI_LIT_INVERSE_SQUARE; direct_j and the fold
+ *   c = mix_color(color_j, c + direct_j, alpha_j); a miss is the sky constant or the environment's plain lookup.
+ * RTMI_ERR_INVALID: every check of rtmi_render_rays*, then every check rtmi_render_lit* makes on `lit`, before any HIP call, stats
+ *   cleared.  RTMI_ERR_UNSUPPORTED: rtmi_render_rays*'s, then the scenes rtmi_render_lit* refuses, with its wording; the handle
+ *   stays usable.
+ * stats: rays = the plain rays + the live candidates traced; trace_launches = 2 per pass and batch (an empty event pair where no
+ *   walk runs); otherwise rtmi_render_rays*'s.
+ * How: rtmi_render_rays*'s batch loop with, per pass, k_lit_rays_explicit, the occlusion walk of its shadow queue (rtmi_render_lit*'s
+ *   route: the closest-hit launch on an octree) and k_shade_lit_explicit: k_lit_rays' and k_shade_lit's bodies with rays_key's key.
+ *
+ * rtmi_bake_lit[_device]: rtmi_bake[_device] with lamps.  orig, dir and open are rtmi_bake*'s: the same bits for the same arguments.
+ *   light[m]   exactly rtmi_render_rays_lit*'s mean[m] of the gather rays with keys == NULL, group = K, the same pixel0, maxdepth
+ *              and lit: the indirect light, with the lamps lighting every Matte bounce of every gather path.
+ *   direct[m]  M float4, lane 3 = 0: the lamps' light arriving at the element itself.  For ray index k = 0 .. K-1, key (seed,
+ *              pixel0 + m, k), n = nrm4[m] as given on all four lanes and NOT normalised (c below scales with its length: pass a
+ *              unit normal):
+ *     point  POINTS: pos4[m].  TRIANGLES: the very point gather ray k starts from (the same draw of block 0x20000000, the same
+ *            fold, the same vadd(vadd(c0, ..), ..));
+ *     for l = 0 .. nlights-1, with vdot the ordered four-lane dot (((0 + x x) + y y) + z z) + w w:
+ *       w    = RNG block 0xC000FFFF | (l << 16) of the key (level field 0xFFFF; see the list of blocks below);
+ *       adj  = (orig[0] + u(w[0]) * len2, orig[1] + u(w[1]) * len2, orig[2] + u(w[2]) * len2, 0), u = top 24 bits * 2^-24;
+ *       v = vsub(adj, point); d2 = vdot(v, v); r = sqrt(d2); dir = vmul(v, 1.f / r);
+ *       o = vadd(point, vmul(n, bias_l * (u(w[3]) + 1.f))); c = vdot(n, dir)      (rtmi_render_light*'s arithmetic);
+ *       culled when !(c > 0.f); otherwise visible iff rtmi_occluded's definition gives 0 for (o, dir, tmax = r), the NULL limit
+ *       when lights[l].flags has RTMI_LIGHT_UNBOUNDED;  g_l = c, or with RTMI_LIT_INVERSE_SQUARE c / d2;
+ *     d_k = (0, 0, 0, 0); then for l ascending over the live and visible candidates d_k[ch] = d_k[ch] + light_color[l][ch] * g_l;
+ *     direct[m] = walk_ray_set's fold of d_0 .. d_{K-1}: acc = 0.f; acc = acc + d_k; acc * (1.f / (float)K).
+ *   direct does not depend on maxdepth; like open it is produced at maxdepth == 0.  With every output but direct NULL no gather
+ *   ray is traced.
+ *   A lightmap texel of a surface (color, alpha) is then mix_color(color, light[m] + direct[m], alpha).
+ * RNG blocks drawn under one key, pairwise distinct: 0 (the gather ray), 0x20000000 (the point), 1 .. 32 (the bounces),
+ *   0xC0000000 | l << 16 | j with j <= 31 (the candidates of path level j) and 0xC000FFFF | l << 16 (the element's candidates):
+ *   no path level has the level field 0xFFFF.
+ * Checks, before any HIP call and before the scene is used, stats cleared: rtmi_bake*'s in their order, with "all five outputs
+ *   NULL" and the overlap check extended to direct (16 M bytes); then rtmi_render_lit*'s checks of `lit`; then its scene refusals.
+ * stats: rtmi_bake*'s, and rays also counts the live candidates of the paths and of the elements; trace_launches = 2 per pass
+ *   and batch, + 1 per batch for the elements' walk when direct is asked for.
+ * How: per batch, when direct is asked for: k_bake_lit_rays (k_bake_rays' staging, k_lit_rays' candidates and compaction, one
+ *   thread per (element, k)), the occlusion walk, k_bake_lit_resolve (d_k), k_accum; then rtmi_bake*'s batch with the lit passes.
+ *   The shadow queue, limits, weights, answers and slots are sized batch x nlights, the direct stack batch x depth, allocated by
+ *   these calls only.  No tuning changes a bit.
+ * Not here: lights on the scenes rtmi_render_lit* refuses; more than one sample per light and hit; rtmi_render_envlight*'s
+ *   sampling in the same pass; adaptive, view and denoised variants. */
+typedef struct rtmi_bake_lit_out {   /* rtmi_bake_out_t and direct: any may be NULL, not all; none may overlap another or an input */
+    void *light, *open, *orig, *dir;
+    void* direct;   /* M float4: the lamps' light at element m, lane 3 = 0 */
+} rtmi_bake_lit_out_t;
+int rtmi_render_rays_lit_device(rtmi_scene_t* scene, uint64_t n, const void* orig4_device, const void* dir4_device,
+                                const void* keys_device /* or NULL */, uint64_t seed, const rtmi_rays_t* rays, const rtmi_lit_t* lit,
+                                const rtmi_rays_out_t* out_device, void* hip_stream, rtmi_stats_t* stats);
+int rtmi_render_rays_lit(rtmi_scene_t* scene, uint64_t n, const float* orig4, const float* dir4, const uint32_t* keys /* or NULL */,
+                         uint64_t seed, const rtmi_rays_t* rays, const rtmi_lit_t* lit, const rtmi_rays_out_t* out_host,
+                         rtmi_stats_t* stats);
+int rtmi_bake_lit_device(rtmi_scene_t* scene, uint64_t M, const void* pos4_device, const void* nrm4_device, uint64_t seed,
+                         const rtmi_bake_t* bake, const rtmi_lit_t* lit, const rtmi_bake_lit_out_t* out_device, void* hip_stream,
+                         rtmi_stats_t* stats);
+int rtmi_bake_lit(rtmi_scene_t* scene, uint64_t M, const float* pos4, const float* nrm4, uint64_t seed, const rtmi_bake_t* bake,
+                  const rtmi_lit_t* lit, const rtmi_bake_lit_out_t* out_host, rtmi_stats_t* stats);
 
 /* A shaded preview in one call: albedo, ambient occlusion and up to four coloured box lights composed PER
  * SAMPLE on the device, from one primary pass per batch and one any-hit walk of the AO rays and every light's live shadow

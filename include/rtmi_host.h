@@ -204,6 +204,21 @@ int rth_caster_bake(rth_scene_t* s, uint64_t M, const float* pos4, const float* 
                     const rtmi_bake_out_t* out_host, rtmi_stats_t* stats, double* wall_seconds);
 int rth_caster_bake_device(rth_scene_t* s, uint64_t M, const void* pos4_device, const void* nrm4_device, const rtmi_bake_t* bake,
                            const rtmi_bake_out_t* out_device, void* hip_stream, rtmi_stats_t* stats, double* wall_seconds);
+/* Both with box lights (rtmi_render_rays_lit* / rtmi_bake_lit* in rtmi.h, which defines them): rth_caster_walk_rays_explicit* and
+ * rth_caster_bake* in every respect, the lamps sampled at every Matte hit of every path and, for the bake, at the element itself
+ * (out->direct); lit must not be NULL. */
+int rth_caster_walk_rays_explicit_lit(rth_scene_t* s, uint64_t n, const float* orig4, const float* dir4, const uint32_t* keys,
+                                      const rtmi_rays_t* rays, const rtmi_lit_t* lit, const rtmi_rays_out_t* out_host,
+                                      rtmi_stats_t* stats, double* wall_seconds);
+int rth_caster_walk_rays_explicit_lit_device(rth_scene_t* s, uint64_t n, const void* orig4_device, const void* dir4_device,
+                                             const void* keys_device, const rtmi_rays_t* rays, const rtmi_lit_t* lit,
+                                             const rtmi_rays_out_t* out_device, void* hip_stream, rtmi_stats_t* stats,
+                                             double* wall_seconds);
+int rth_caster_bake_lit(rth_scene_t* s, uint64_t M, const float* pos4, const float* nrm4, const rtmi_bake_t* bake,
+                        const rtmi_lit_t* lit, const rtmi_bake_lit_out_t* out_host, rtmi_stats_t* stats, double* wall_seconds);
+int rth_caster_bake_lit_device(rth_scene_t* s, uint64_t M, const void* pos4_device, const void* nrm4_device, const rtmi_bake_t* bake,
+                               const rtmi_lit_t* lit, const rtmi_bake_lit_out_t* out_device, void* hip_stream, rtmi_stats_t* stats,
+                               double* wall_seconds);
 /* Ambient occlusion (rtmi_render_ao / rtmi_render_ao_device in rtmi.h, which defines it): one f32 per pixel, the share of
  * ao->rays hemisphere rays per primary sample of [sample0, sample0 + nsamples) that are not occluded within ao->radius.
  * maxdepth is not consulted; the primary rays use the caster's seed. */

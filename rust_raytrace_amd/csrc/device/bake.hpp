@@ -77,6 +77,16 @@ __global__ void __launch_bounds__(256) k_bake_rays(uint32_t nelems, uint32_t K, 
     if (blockIdx.x == 0 && threadIdx.x == 0) ctrl->count[0] = nelems * K;
 }
 
+// The point gather ray k of a TRIANGLES element starts from, for what else is computed there (lit.hpp's k_bake_lit_rays: the lamps'
+// candidates at the element): k_bake_rays' draw and fold above, operation for operation.  c0, e1, e2 as k_bake_rays stages them.
+__device__ inline V4 bake_triangle_point(uint64_t seed, uint32_t pixel, uint32_t k, V4 c0, V4 e1, V4 e2) {
+    uint32_t w[4];
+    rng_block(seed, pixel, k, RTMI_BAKE_BLOCK_POINT, w);
+    float u = u32_to_unit_f32(w[0]), v = u32_to_unit_f32(w[1]);
+    if (u + v > 1.f) { u = 1.f - u; v = 1.f - v; }
+    return vadd(vadd(c0, vmul(e1, u)), vmul(e2, v));
+}
+
 // Eight lanes per element (k_ao_resolve's grouping: a block takes 32 consecutive elements).  Lane l counts the misses (tri == 0)
 // among entries l, l + 8, ... of the element's K hit records of pass 0; consecutive lanes read consecutive words.  The eight
 // counts are added across the lanes and lane 0 stores open = (float)misses * (1.f / (float)K): integers, so the order is free.

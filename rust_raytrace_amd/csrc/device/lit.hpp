@@ -10,6 +10,8 @@
 //                 direct stack and added in the fold; no balance weight, the environment only where the scene has one
 // The rays, the RNG blocks 0 .. maxdepth and the queue order rules are shade_pass's.  Included by rtmi_device.hip after
 // envlight.hpp (RTMI_SHADOW_NONE is shadowed.hpp's, env_lookup shade.hpp's).
+// The same two kernels for explicit rays (rtmi_render_rays_lit*, rtmi_bake_lit*): k_lit_rays_explicit and
+// k_shade_lit_explicit, and the bake's own pair for the lamps' light at an element: k_bake_lit_rays, k_bake_lit_resolve (below).
 #pragma once
 
 namespace rtmi {
@@ -34,102 +36,26 @@ struct LitArgs {
 // LDS, ONE atomic per block of four waves on sctrl->count[pass + 1]; so consecutive live lanes of a light store consecutive
 // entries.  slot[l * npaths + i] = the shadow queue entry of candidate l of path queue entry i, or RTMI_SHADOW_NONE (no candidate,
 // or culled).  The caller sizes the shadow queue for npaths * nlights entries: count <= npaths bounds every index.
-__global__ void __launch_bounds__(256) k_lit_rays(DScene sc, DView v, uint64_t seed, uint32_t pix0, uint32_t npaths, int pass, LitArgs la,
-                                                  const float4* __restrict__ qo, const float4* __restrict__ qd,
-                                                  const uint32_t* __restrict__ qpath, const uint32_t* __restrict__ hit_tf,
-                                                  const float* __restrict__ hit_t, const DCtrl* __restrict__ ctrl,
-                                                  float4* __restrict__ lq_o, float4* __restrict__ lq_d, float* __restrict__ lq_tmax,
-                                                  float4* __restrict__ lw, uint32_t* __restrict__ slot, DCtrl* __restrict__ sctrl) {
-    __shared__ uint32_t s_cnt[4], s_base;
-    const uint32_t count = min(ctrl->count[pass], npaths);
-    const uint32_t stride = gridDim.x * blockDim.x;
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    const uint32_t bound = (count + 255u) & ~255u;  // whole blocks stay converged for the ballots and the barriers
-    const uint32_t nl = min(la.nlights, (uint32_t)RTMI_LIT_LIGHTS);
-    // (launched for the passes whose Matte hits bounce, maxdepth - pass - 1 != 0: an exhausted level gets no sample)
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < bound; i += stride) {
-        bool cand = false;
-        V4 point{}, n{};
-        uint32_t pixel = 0, sample = 0;
-        if (i < count) {
-            const uint32_t tf = hit_tf[i], tri = tf & 0x3FFFFFFFu;
-            if (tri != 0u && !((tf >> 30) & 2u)) {
-                const float4 p1 = sc.tplane[2 * tri + 1];
-                const float4 m1 = sc.mats[2 * __float_as_uint(p1.w) + 1];
-                if (__float_as_uint(m1.y) == RTMI_MATTE) {
-                    cand = true;
-                    const float t = hit_t[i];
-                    const float4 o4 = qo[i], d4 = qd[i];
-                    point = vadd(vmul(V4{d4.x, d4.y, d4.z, d4.w}, t), V4{o4.x, o4.y, o4.z, o4.w});
-                    n = mk(p1.x, p1.y, p1.z);
-                    if ((tf >> 30) & 1u) n = vmul(n, -1.f);
-                    uint32_t row, col;
-                    path_pixel<Samp::PASS>(v, pix0, qpath[i], row, col, sample, nullptr);
-                    pixel = row * v.width + col;
-                }
-            }
-        }
-        bool live[RTMI_LIT_LIGHTS];
-        V4 o[RTMI_LIT_LIGHTS], dir[RTMI_LIT_LIGHTS];
-        float r[RTMI_LIT_LIGHTS], g[RTMI_LIT_LIGHTS];
-        uint32_t place[RTMI_LIT_LIGHTS];  // the lane's place among the wave's live candidates
-        uint32_t wtotal = 0;
-        const unsigned long long below = (1ull << lane) - 1ull;
-#pragma unroll
-        for (uint32_t l = 0; l < RTMI_LIT_LIGHTS; l++) {
-            live[l] = false;
-            o[l] = V4{}; dir[l] = V4{};
-            r[l] = 0.f; g[l] = 0.f;
-            place[l] = 0;
-            if (l < nl) {
-                if (cand) {
-                    const LitLight& L = la.li[l];
-                    uint32_t w[4];
-                    rng_block(seed, pixel, sample, 0xC0000000u | (l << 16) | (uint32_t)pass, w);
-                    const V4 adj{L.orig.x + u32_to_unit_f32(w[0]) * L.len2, L.orig.y + u32_to_unit_f32(w[1]) * L.len2,
-                                 L.orig.z + u32_to_unit_f32(w[2]) * L.len2, 0.f};
-                    const V4 vv = vsub(adj, point);
-                    const float d2 = vdot(vv, vv);
-                    r[l] = sqrtf(d2);
-                    dir[l] = vmul(vv, 1.f / r[l]);
-                    o[l] = vadd(point, vmul(n, L.bias * (u32_to_unit_f32(w[3]) + 1.f)));
-                    const float c = vdot(n, dir[l]);
-                    live[l] = c > 0.f;  // false for the light behind the surface, for a NaN and for the light at the point
-                    g[l] = la.inverse_square ? c / d2 : c;
-                }
-                const unsigned long long mask = __ballot(live[l]);
-                place[l] = wtotal + (uint32_t)__popcll(mask & below);
-                wtotal += (uint32_t)__popcll(mask);
-            }
-        }
-        if (lane == 0) s_cnt[wv] = wtotal;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const uint32_t total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-            s_base = total ? atomicAdd(&sctrl->count[pass + 1], total) : 0u;
-        }
-        __syncthreads();
-        uint32_t base = s_base;
-        for (uint32_t k = 0; k < wv; k++) base += s_cnt[k];
-#pragma unroll
-        for (uint32_t l = 0; l < RTMI_LIT_LIGHTS; l++) {
-            if (l < nl) {
-                if (live[l]) {
-                    const LitLight& L = la.li[l];
-                    const uint32_t q = base + place[l];
-                    store_stream(&lq_o[q], make_float4(o[l].x, o[l].y, o[l].z, o[l].w));
-                    store_stream(&lq_d[q], make_float4(dir[l].x, dir[l].y, dir[l].z, dir[l].w));
-                    store_stream(&lq_tmax[q], L.unbounded ? INFINITY : r[l]);
-                    store_stream(&lw[q], make_float4(L.col[0] * g[l], L.col[1] * g[l], L.col[2] * g[l], 0.f));
-                    store_stream(&slot[(size_t)l * npaths + i], q);
-                } else if (i < count) {
-                    store_stream(&slot[(size_t)l * npaths + i], RTMI_SHADOW_NONE);
-                }
-            }
-        }
-        __syncthreads();  // s_cnt / s_base are rewritten by the next iteration
-    }
-}
+// The kernel's text is lit_rays_kernel.hpp, compiled once per sampling mode: k_lit_rays with a frame's key (Samp::PASS), and
+// k_lit_rays_explicit (rtmi_render_rays_lit*, rtmi_bake_lit*) with rays_key()'s: keys = the batch's RNG keys or null,
+// pix0 = the key of its first group.  Nothing else differs.
+#define RTMI_LIT_KERNEL k_lit_rays
+#define RTMI_LIT_KEYS_PARAM
+#define RTMI_LIT_RAYS_KEY                                                         \
+    uint32_t row, col;                                                            \
+    path_pixel<Samp::PASS>(v, pix0, qpath[i], row, col, sample, nullptr);         \
+    pixel = row * v.width + col;
+#include "lit_rays_kernel.hpp"
+#undef RTMI_LIT_KERNEL
+#undef RTMI_LIT_KEYS_PARAM
+#undef RTMI_LIT_RAYS_KEY
+#define RTMI_LIT_KERNEL k_lit_rays_explicit
+#define RTMI_LIT_KEYS_PARAM , const uint32_t* __restrict__ keys
+#define RTMI_LIT_RAYS_KEY rays_key(v, pix0, qpath[i], keys, pixel, sample);
+#include "lit_rays_kernel.hpp"
+#undef RTMI_LIT_KERNEL
+#undef RTMI_LIT_KEYS_PARAM
+#undef RTMI_LIT_RAYS_KEY
 
 // shade_hit's plain arm (Solid, Matte, Reflective, flat triangles) for ONE traced ray of a lit path: the same rays, stack and
 // return value.  `direct` is the level's light (the sum of the weights of its unoccluded candidates, else 0): stored on
@@ -193,66 +119,168 @@ __device__ inline bool shade_hit_lit(const DScene& sc, const EnvTab& env, uint32
 }
 
 // k_shade_envlight's loop with the sum of the entry's unoccluded weights, l ascending from (0, 0, 0, 0), for its direct light
+// The kernel's text is lit_shade_kernel.hpp, once per sampling mode as above: k_shade_lit<ENV> and k_shade_lit_explicit<ENV>.  The
+// sample colour goes to scol[path]: the caller's `color` buffer when an explicit-ray call asks for it.
+#define RTMI_LIT_KERNEL k_shade_lit
+#define RTMI_LIT_KEYS_PARAM
+#define RTMI_LIT_SHADE_KEY                                                        \
+    uint32_t prow, pcol, sample;                                                  \
+    path_pixel<Samp::PASS>(v, pix0, path, prow, pcol, sample, nullptr);
+#define RTMI_LIT_SHADE_PIXEL prow * v.width + pcol
 template <bool ENV>
-__global__ void __launch_bounds__(256) k_shade_lit(DScene sc, DView v, uint64_t seed, uint32_t pix0, uint32_t npaths, int pass, EnvTab env,
-                                                   uint32_t nlights, const float4* __restrict__ qo, const float4* __restrict__ qd,
-                                                   const uint32_t* __restrict__ qpath, const uint32_t* __restrict__ hit_tf,
-                                                   const float* __restrict__ hit_t, const uint32_t* __restrict__ slot,
-                                                   const uint8_t* __restrict__ occ, const float4* __restrict__ lw,
-                                                   float4* __restrict__ qo_n, float4* __restrict__ qd_n, uint32_t* __restrict__ qpath_n,
-                                                   uint16_t* __restrict__ mstack, float4* __restrict__ dstack, float4* __restrict__ scol,
-                                                   DCtrl* __restrict__ ctrl) {
+#include "lit_shade_kernel.hpp"
+#undef RTMI_LIT_KERNEL
+#undef RTMI_LIT_KEYS_PARAM
+#undef RTMI_LIT_SHADE_KEY
+#undef RTMI_LIT_SHADE_PIXEL
+#define RTMI_LIT_KERNEL k_shade_lit_explicit
+#define RTMI_LIT_KEYS_PARAM , const uint32_t* __restrict__ keys
+#define RTMI_LIT_SHADE_KEY                                                        \
+    uint32_t pixel, sample;                                                       \
+    rays_key(v, pix0, path, keys, pixel, sample);
+#define RTMI_LIT_SHADE_PIXEL pixel
+template <bool ENV>
+#include "lit_shade_kernel.hpp"
+#undef RTMI_LIT_KERNEL
+#undef RTMI_LIT_KEYS_PARAM
+#undef RTMI_LIT_SHADE_KEY
+#undef RTMI_LIT_SHADE_PIXEL
+
+// ---------------------------------------------------------------- the lamps' light at a bake element (rtmi_bake_lit*: `direct`)
+// k_bake_rays' loop (bake.hpp: a block stages `epb` whole elements per step in LDS, thread e of the step's (element h, ray k) pairs, k
+// fastest) with k_lit_rays' candidates and compaction where the gather ray is made: the point is gather ray k's (POINTS: the
+// element's; TRIANGLES: the same draw of block 0x20000000 and the same fold), n the element's normal on all four lanes as given, the
+// key (seed, pix0 + element, k), the candidate of light l from block 0xC000FFFF | l << 16 (level field 0xFFFF: no path level has
+// it).  The live candidates go to the shadow queue counted in sctrl->count[q]; slot[l * (nelems * K) + entry] = the queue entry of
+// candidate l of ray `entry` = element * K + k, or RTMI_SHADOW_NONE.  The caller sizes the queue for nelems * K * nlights entries.
+#define RTMI_BAKE_LIT_LEVEL 0xFFFFu
+template <bool TRI>
+__global__ void __launch_bounds__(256) k_bake_lit_rays(uint32_t nelems, uint32_t K, FastDiv dK, uint32_t epb, const float4* __restrict__ pos,
+                                                       const float4* __restrict__ nrm, uint64_t seed, uint32_t pix0, LitArgs la,
+                                                       float4* __restrict__ lq_o, float4* __restrict__ lq_d, float* __restrict__ lq_tmax,
+                                                       float4* __restrict__ lw, uint32_t* __restrict__ slot, DCtrl* __restrict__ sctrl, int q) {
+    __shared__ float s_pt[TRI ? 12 : 4][RTMI_BAKE_STEP_MAX], s_n[4][RTMI_BAKE_STEP_MAX];  // [lane of the vector][element of the step]
     __shared__ uint32_t s_cnt[4], s_base;
-    const uint32_t count = min(ctrl->count[pass], npaths);
-    const uint32_t stride = gridDim.x * blockDim.x;
+    const uint32_t nsteps = (nelems + epb - 1u) / epb;
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    const uint32_t bound = (count + 255u) & ~255u;  // whole blocks stay converged for the ballot and the queue reservation
-    // (the exhausted pass has no candidates: k_lit_rays is not launched for it and the slots are stale)
-    const uint32_t nl = v.maxdepth - (uint32_t)pass - 1u != 0u ? min(nlights, (uint32_t)RTMI_LIT_LIGHTS) : 0u;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < bound; i += stride) {
-        bool push = false;
-        RayV nr;
-        uint32_t path = 0;
-        if (i < count) {
-            path = qpath[i];
-            const uint32_t tf = hit_tf[i];
-            float t = 0.f;
-            const float4 o4 = qo[i], d4 = qd[i];  // (with ENV a miss looks the environment up in its ray's direction)
-            V4 direct{0.f, 0.f, 0.f, 0.f};
-            if ((tf & 0x3FFFFFFFu) != 0u && !((tf >> 30) & 2u)) {
-                t = hit_t[i];
-                for (uint32_t l = 0; l < nl; l++) {
-                    const uint32_t e = slot[(size_t)l * npaths + i];
-                    if (e != RTMI_SHADOW_NONE && occ[e] == 0) {
-                        const float4 l4 = lw[e];
-                        direct = vadd(direct, V4{l4.x, l4.y, l4.z, l4.w});
+    const uint32_t nl = min(la.nlights, (uint32_t)RTMI_LIT_LIGHTS);
+    const size_t nentries = (size_t)nelems * K;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (uint32_t step = blockIdx.x; step < nsteps; step += gridDim.x) {  // uniform per block: the barriers stay converged
+        const uint32_t m0 = step * epb, cnt = min(epb, nelems - m0);
+        if (threadIdx.x < cnt) {
+            const uint32_t j = threadIdx.x, m = m0 + j;
+            const float4 n = nrm[m];
+            s_n[0][j] = n.x; s_n[1][j] = n.y; s_n[2][j] = n.z; s_n[3][j] = n.w;
+            if constexpr (TRI) {
+                const float4 a = pos[3u * m], b = pos[3u * m + 1u], c = pos[3u * m + 2u];
+                const V4 c0{a.x, a.y, a.z, a.w};
+                const V4 e1 = vsub(V4{b.x, b.y, b.z, b.w}, c0), e2 = vsub(V4{c.x, c.y, c.z, c.w}, c0);
+                s_pt[0][j] = c0.x; s_pt[1][j] = c0.y; s_pt[2][j] = c0.z; s_pt[3][j] = c0.w;
+                s_pt[4][j] = e1.x; s_pt[5][j] = e1.y; s_pt[6][j] = e1.z; s_pt[7][j] = e1.w;
+                s_pt[8][j] = e2.x; s_pt[9][j] = e2.y; s_pt[10][j] = e2.z; s_pt[11][j] = e2.w;
+            } else {
+                const float4 p = pos[m];
+                s_pt[0][j] = p.x; s_pt[1][j] = p.y; s_pt[2][j] = p.z; s_pt[3][j] = p.w;
+            }
+        }
+        __syncthreads();
+        const uint32_t base = m0 * K, nrays = cnt * K;  // the step's first entry (nelems * K < 2^31)
+        for (uint32_t e0 = 0; e0 < nrays; e0 += 256u) {  // whole blocks stay converged for the ballots and the barriers
+            const uint32_t e = e0 + threadIdx.x;
+            const bool cand = e < nrays;
+            V4 point{}, n{};
+            uint32_t pixel = 0, k = 0;
+            if (cand) {
+                const uint32_t h = fdiv(e, dK);
+                k = e - h * K;
+                pixel = pix0 + m0 + h;
+                n = V4{s_n[0][h], s_n[1][h], s_n[2][h], s_n[3][h]};
+                point = V4{s_pt[0][h], s_pt[1][h], s_pt[2][h], s_pt[3][h]};
+                if constexpr (TRI) {
+                    const V4 e1{s_pt[4][h], s_pt[5][h], s_pt[6][h], s_pt[7][h]}, e2{s_pt[8][h], s_pt[9][h], s_pt[10][h], s_pt[11][h]};
+                    point = bake_triangle_point(seed, pixel, k, point, e1, e2);
+                }
+            }
+            bool live[RTMI_LIT_LIGHTS];
+            V4 o[RTMI_LIT_LIGHTS], dir[RTMI_LIT_LIGHTS];
+            float r[RTMI_LIT_LIGHTS], g[RTMI_LIT_LIGHTS];
+            uint32_t place[RTMI_LIT_LIGHTS];  // the lane's place among the wave's live candidates
+            uint32_t wtotal = 0;
+#pragma unroll
+            for (uint32_t l = 0; l < RTMI_LIT_LIGHTS; l++) {
+                live[l] = false;
+                o[l] = V4{}; dir[l] = V4{};
+                r[l] = 0.f; g[l] = 0.f;
+                place[l] = 0;
+                if (l < nl) {
+                    if (cand) {
+                        const LitLight& L = la.li[l];
+                        uint32_t w[4];
+                        rng_block(seed, pixel, k, 0xC0000000u | (l << 16) | RTMI_BAKE_LIT_LEVEL, w);
+                        const V4 adj{L.orig.x + u32_to_unit_f32(w[0]) * L.len2, L.orig.y + u32_to_unit_f32(w[1]) * L.len2,
+                                     L.orig.z + u32_to_unit_f32(w[2]) * L.len2, 0.f};
+                        const V4 vv = vsub(adj, point);
+                        const float d2 = vdot(vv, vv);
+                        r[l] = sqrtf(d2);
+                        dir[l] = vmul(vv, 1.f / r[l]);
+                        o[l] = vadd(point, vmul(n, L.bias * (u32_to_unit_f32(w[3]) + 1.f)));
+                        const float c = vdot(n, dir[l]);
+                        live[l] = c > 0.f;  // false for the light behind the element, for a NaN and for the light at the point
+                        g[l] = la.inverse_square ? c / d2 : c;
+                    }
+                    const unsigned long long mask = __ballot(live[l]);
+                    place[l] = wtotal + (uint32_t)__popcll(mask & below);
+                    wtotal += (uint32_t)__popcll(mask);
+                }
+            }
+            if (lane == 0) s_cnt[wv] = wtotal;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                const uint32_t total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+                s_base = total ? atomicAdd(&sctrl->count[q], total) : 0u;
+            }
+            __syncthreads();
+            uint32_t qb = s_base;
+            for (uint32_t x = 0; x < wv; x++) qb += s_cnt[x];
+#pragma unroll
+            for (uint32_t l = 0; l < RTMI_LIT_LIGHTS; l++) {
+                if (l < nl) {
+                    if (live[l]) {
+                        const LitLight& L = la.li[l];
+                        const uint32_t qe = qb + place[l];
+                        store_stream(&lq_o[qe], make_float4(o[l].x, o[l].y, o[l].z, o[l].w));
+                        store_stream(&lq_d[qe], make_float4(dir[l].x, dir[l].y, dir[l].z, dir[l].w));
+                        store_stream(&lq_tmax[qe], L.unbounded ? INFINITY : r[l]);
+                        store_stream(&lw[qe], make_float4(L.col[0] * g[l], L.col[1] * g[l], L.col[2] * g[l], 0.f));
+                        store_stream(&slot[(size_t)l * nentries + base + e], qe);
+                    } else if (cand) {
+                        store_stream(&slot[(size_t)l * nentries + base + e], RTMI_SHADOW_NONE);
                     }
                 }
             }
-            uint32_t prow, pcol, sample;
-            path_pixel<Samp::PASS>(v, pix0, path, prow, pcol, sample, nullptr);
-            push = shade_hit_lit<ENV>(sc, env, v.maxdepth, seed, npaths, path, prow * v.width + pcol, sample, (uint32_t)pass, tf, t,
-                                      V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w}, direct, mstack, dstack, scol, nr);
+            __syncthreads();  // s_cnt / s_base are rewritten by the next iteration, the staged elements by the next step
         }
-        const unsigned long long mask = __ballot(push);
-        if (lane == 0) s_cnt[wv] = (uint32_t)__popcll(mask);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const uint32_t total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-            s_base = total ? atomicAdd(&ctrl->count[pass + 1], total) : 0u;
-        }
-        __syncthreads();
-        {
-            uint32_t base = s_base;
-            for (uint32_t k = 0; k < wv; k++) base += s_cnt[k];
-            if (push) {
-                const uint32_t q = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-                store_stream(&qo_n[q], make_float4(nr.orig.x, nr.orig.y, nr.orig.z, nr.orig.w));
-                store_stream(&qd_n[q], make_float4(nr.dir.x, nr.dir.y, nr.dir.z, nr.dir.w));
-                store_stream(&qpath_n[q], path);
+    }
+}
+
+// One thread per (element, k): d_k = the weights of the ray's unoccluded candidates summed in l order from (0, 0, 0, 0), as
+// k_shade_lit sums a level's.  k_accum then folds an element's K of them to direct[m].
+__global__ void __launch_bounds__(256) k_bake_lit_resolve(uint32_t nentries, uint32_t nlights, const uint32_t* __restrict__ slot,
+                                                          const uint8_t* __restrict__ occ, const float4* __restrict__ lw,
+                                                          float4* __restrict__ dk) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    const uint32_t nl = min(nlights, (uint32_t)RTMI_LIT_LIGHTS);
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nentries; i += stride) {
+        V4 d{0.f, 0.f, 0.f, 0.f};
+        for (uint32_t l = 0; l < nl; l++) {
+            const uint32_t e = slot[(size_t)l * nentries + i];
+            if (e != RTMI_SHADOW_NONE && occ[e] == 0) {
+                const float4 l4 = lw[e];
+                d = vadd(d, V4{l4.x, l4.y, l4.z, l4.w});
             }
         }
-        __syncthreads();  // s_cnt / s_base are rewritten by the next iteration
+        store_stream(&dk[i], make_float4(d.x, d.y, d.z, d.w));
     }
 }
 

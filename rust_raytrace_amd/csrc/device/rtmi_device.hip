@@ -1289,6 +1289,8 @@ struct rtmi_scene {
         DevBuf<float> wb;
         // rtmi_render_lit*, the same pass structure with up to nlights shadow rays per path and pass: qo, qd, tmax, lw and occ then
         // hold paths * nlights entries, slot paths * nlights words ([light][path]); dstack as above.  Sized by that call only.
+        // rtmi_render_rays_lit* and rtmi_bake_lit* run the same passes on stream 0's buffers (ensure_lit_rays sizes them); the bake's
+        // element candidates use them before its gather paths do, their shadow queue counted in walk's count[RTMI_MAX_PASSES].
         Work walk;
         void release() { qo.release(); qd.release(); tmax.release(); slot.release(); mask.release(); occ.release(); lw.release(); dstack.release(); wb.release(); walk.release(); }
     } shadow[RTMI_MAX_STREAMS];
@@ -4101,10 +4103,15 @@ void rtmi_lit_defaults(rtmi_lit_t* p) {
 
 // Checks of the lit entry points that come before any HIP call and before the scene is used: rtmi_render_samples_device's, then
 // the parameters, each used light as rtmi_render_shadowed* checks its one
+static int check_lit_params(const rtmi_lit_t* p);
 static int check_lit(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint32_t sample0, uint32_t nsamples, const rtmi_lit_t* p, const void* accum,
                      const void* out) {
     const int rc = check_samples(s, vp, sample0, nsamples, accum, out);
     if (rc != RTMI_OK) return rc;
+    return check_lit_params(p);
+}
+// the parameters alone: rtmi_render_rays_lit* and rtmi_bake_lit* make these checks after their own
+static int check_lit_params(const rtmi_lit_t* p) {
     if (!p) return fail(RTMI_ERR_INVALID, "lit: NULL argument (rtmi_lit_t)");
     if (p->nlights > (uint32_t)RTMI_LIT_MAX_LIGHTS) return fail(RTMI_ERR_INVALID, "lit: nlights above RTMI_LIT_MAX_LIGHTS");
     if (p->flags & ~(uint32_t)RTMI_LIT_INVERSE_SQUARE) return fail(RTMI_ERR_INVALID, "lit: unknown flags");
@@ -4920,6 +4927,70 @@ static bool ranges_overlap(const ByteRange* r, size_t n, size_t& a, size_t& b) {
     return false;
 }
 
+// ---- box lights on explicit rays and in the bake (rtmi_render_rays_lit*, rtmi_bake_lit*; lit.hpp)
+// The lit variants run rtmi_render_lit*'s passes on stream 0's shadow buffers (rtmi_scene::ShadowBuf): THE site that sizes them for
+// a call whose batches hold B rays of depth maxdepth.  Every queue of the walk holds B * nlights entries, the direct stack B *
+// maxdepth; the walk's event pairs: one per pass, and one more for the walk of a bake's element candidates.
+static bool lit_rays_from_hits(const rtmi_scene* s) { return s->lit_from_hits && !s->root_is_leaf; }
+static int ensure_lit_rays(rtmi_scene* s, size_t B, uint32_t maxdepth, const LitArgs& la) {
+    rtmi_scene::ShadowBuf& b = s->shadow[0];
+    const size_t nq = B * la.nlights;
+    const bool from_hits = lit_rays_from_hits(s);
+    HIPCHK(b.qo.ensure(nq)); HIPCHK(b.qd.ensure(nq)); HIPCHK(b.tmax.ensure(nq)); HIPCHK(b.lw.ensure(nq)); HIPCHK(b.occ.ensure(nq));
+    HIPCHK(b.slot.ensure(nq)); HIPCHK(b.dstack.ensure(B * std::max(maxdepth, 1u)));
+    HIPCHK(b.walk.ctrl.ensure(1));
+    if (nq && (!occluded_anyhit(s) || from_hits)) { HIPCHK(b.walk.hit_tf.ensure(nq)); HIPCHK(b.walk.hit_t.ensure(nq)); }
+    if (nq && from_hits) HIPCHK(b.walk.fb.ensure(b.walk.hit_tf.n));  // the hybrid pass's fallback list, as long as the hit records
+    while (b.walk.pass_ev.size() < 2 * ((size_t)maxdepth + 1)) {
+        hipEvent_t e;
+        HIPCHK(hipEventCreate(&e));
+        b.walk.pass_ev.push_back(e);
+    }
+    return RTMI_OK;
+}
+// Pass `pass` of a batch of nb explicit rays after its closest-hit launch, where launch_shade stands in the plain calls:
+// enqueue_batch's lit arm with the RAYS kernels.  (qo, qd): the pass's queue; keys: the batch's RNG keys or null.
+static int lit_rays_pass(rtmi_scene* s, Work& w, hipStream_t st, const DView& dv, uint64_t seed, uint32_t pix0, uint32_t nb, uint32_t pass,
+                         const LitArgs& la, const float4* qo, const float4* qd, const uint32_t* keys, float4* scol) {
+    rtmi_scene::ShadowBuf& sb = s->shadow[0];
+    const int a = pass & 1, b = a ^ 1;
+    const dim3 ew_grid((unsigned)(s->num_cu * 8)), ew_block(256);
+    // sb.walk.ctrl->count[pass + 1] (zero since the batch's memset) is the compaction's counter and then the walk's ray count
+    if (dv.maxdepth - pass - 1u != 0u && la.nlights != 0u) {
+        hipLaunchKernelGGL(k_lit_rays_explicit, ew_grid, ew_block, 0, st, s->d, dv, seed, pix0, nb, (int)pass, la, qo, qd, w.qpath[a].p, w.hit_tf.p,
+                           w.hit_t.p, w.ctrl.p, sb.qo.p, sb.qd.p, sb.tmax.p, sb.lw.p, sb.slot.p, sb.walk.ctrl.p, keys);
+        HIPCHK(hipEventRecord(sb.walk.pass_ev[2 * pass], st));
+        launch_occluded(s, sb.walk, st, (uint64_t)nb * la.nlights, sb.qo.p, sb.qd.p, sb.tmax.p, sb.occ.p, (int)pass + 1,
+                        sb.walk.pass_ev[2 * pass + 1], lit_rays_from_hits(s));
+        HIPCHK(hipGetLastError());
+    } else {  // no candidates (the exhausted level, or no lights): no walk, an empty event pair
+        HIPCHK(hipEventRecord(sb.walk.pass_ev[2 * pass], st));
+        HIPCHK(hipEventRecord(sb.walk.pass_ev[2 * pass + 1], st));
+    }
+    hipLaunchKernelGGL(s->has_env ? k_shade_lit_explicit<true> : k_shade_lit_explicit<false>, ew_grid, ew_block, 0, st, s->d, dv, seed, pix0, nb,
+                       (int)pass, s->envtab, la.nlights, qo, qd, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, sb.slot.p, sb.occ.p, sb.lw.p, w.qo[b].p,
+                       w.qd[b].p, w.qpath[b].p, w.mstack.p, sb.dstack.p, scol, w.ctrl.p, keys);
+    HIPCHK(hipGetLastError());
+    return RTMI_OK;
+}
+// After a batch's stream has finished it: the walks' control block (the live candidates in rays, the work counters) and their
+// event pairs [first_pair, end_pair).
+static int lit_rays_collect(rtmi_scene* s, hipStream_t st, uint32_t first_pair, uint32_t end_pair, rtmi_stats_t& sum, float& trace_ms,
+                            uint32_t& launches) {
+    Work& sw = s->shadow[0].walk;
+    DCtrl hs;
+    HIPCHK(hipMemcpyAsync(&hs, sw.ctrl.p, sizeof(DCtrl), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    add_counters(sum, ctrl_counters(hs));
+    for (uint32_t k = first_pair; k < end_pair; k++) {
+        float pm = 0.f;
+        HIPCHK(hipEventElapsedTime(&pm, sw.pass_ev[2 * k], sw.pass_ev[2 * k + 1]));
+        launches++;
+        trace_ms += pm;
+    }
+    return RTMI_OK;
+}
+
 // Checks that come before any HIP call (a CPU-only caller reaches them); only the last one reads the scene.
 static int check_rays(const rtmi_scene_t* s, uint64_t n, const void* orig4, const void* dir4, const void* keys, const rtmi_rays_t* rp,
                       const rtmi_rays_out_t* out, rtmi_stats_t* stats, bool& empty) {
@@ -4959,7 +5030,8 @@ static int check_rays(const rtmi_scene_t* s, uint64_t n, const void* orig4, cons
 // in the workspace queue, its keys and group outputs in the host variants' per-pixel buffers of the handle (alist[0], tile,
 // acc, asq, acnt: no call keeps anything in them between calls), and copied out batch by batch.
 static int render_rays(rtmi_scene_t* s, uint64_t n, const void* orig4, const void* dir4, const void* keys, uint64_t seed,
-                       const rtmi_rays_t* rp, const rtmi_rays_out_t* out, void* hip_stream, rtmi_stats_t* stats, bool host) {
+                       const rtmi_rays_t* rp, const rtmi_rays_out_t* out, void* hip_stream, rtmi_stats_t* stats, bool host,
+                       const LitArgs* lit = nullptr) {
     bool empty;
     int rc = check_rays(s, n, orig4, dir4, keys, rp, out, stats, empty);
     if (rc != RTMI_OK || empty) return rc;
@@ -4977,6 +5049,10 @@ static int render_rays(rtmi_scene_t* s, uint64_t n, const void* orig4, const voi
     if (shade || guides) {
         rc = ensure_workspace(w, (size_t)B, std::max(maxdepth, 1u));
         if (rc == RTMI_OK) rc = ensure_cstack(s, w);
+        if (rc != RTMI_OK) return rc;
+    }
+    if (lit && shade) {  // rtmi_render_rays_lit*: the shadow queue, answers, slots and direct stack of a batch
+        rc = ensure_lit_rays(s, (size_t)B, maxdepth, *lit);
         if (rc != RTMI_OK) return rc;
     }
     if (host) {
@@ -5026,6 +5102,7 @@ static int render_rays(rtmi_scene_t* s, uint64_t n, const void* orig4, const voi
             ids = ids ? s->acnt.p : nullptr;
         }
         HIPCHK(hipMemsetAsync(w.ctrl.p, 0, sizeof(DCtrl), st));
+        if (lit && shade) HIPCHK(hipMemsetAsync(s->shadow[0].walk.ctrl.p, 0, sizeof(DCtrl), st));
         hipLaunchKernelGGL(k_rays_begin, ew_grid, ew_block, 0, st, nb, make ? qd : nullptr, w.qd[0].p, w.qpath[0].p, w.ctrl.p);
         HIPCHK(hipGetLastError());
         if (make) qd = w.qd[0].p;
@@ -5037,8 +5114,12 @@ static int render_rays(rtmi_scene_t* s, uint64_t n, const void* orig4, const voi
             HIPCHK(hipGetLastError());
             if (pass == 0 && guides)  // before pass 1 rewrites the hit records
                 launch_features(s, ew_grid, ew_block, st, ng, G, w.hit_tf.p, w.hit_t.p, (float*)albedo, (float*)normal, ids, 0u, ng, 1u, 0u, pqo, pqd);
-            if (shade)
+            if (shade && lit) {
+                rc = lit_rays_pass(s, w, st, dv, seed, (uint32_t)(rp->pixel0 + gbase), nb, pass, *lit, pqo, pqd, kq, scol);
+                if (rc != RTMI_OK) return rc;
+            } else if (shade) {
                 launch_shade(s, w, st, Samp::RAYS, dv, seed, (uint32_t)(rp->pixel0 + gbase), nb, pass, pqo, pqd, scol, SLOW_OFF, kq);
+            }
             HIPCHK(hipGetLastError());
         }
         if (shade && mean)
@@ -5062,6 +5143,10 @@ static int render_rays(rtmi_scene_t* s, uint64_t n, const void* orig4, const voi
             launches++;
             trace_ms += pm;
             if (s->verbose) fprintf(stderr, "[rtmi] rays batch@%llu pass %u: %u rays, trace %.3f ms\n", (unsigned long long)base, pass, h.count[pass], pm);
+        }
+        if (lit && shade) {  // the shadow rays' walks, one event pair per pass
+            rc = lit_rays_collect(s, st, 0u, npass, sum, trace_ms, launches);
+            if (rc != RTMI_OK) return rc;
         }
     }
     if (!host) {
@@ -5092,6 +5177,33 @@ int rtmi_render_rays(rtmi_scene_t* s, uint64_t n, const float* orig4, const floa
     return render_rays(s, n, orig4, dir4, keys, seed, rays, out_host, nullptr, stats, true);
 }
 
+// rtmi_render_rays_lit*: rtmi_render_rays*'s checks, then rtmi_render_lit*'s of its parameters, then its scene refusals; all before
+// any HIP call.  (An empty call returns where rtmi_render_rays* returns.)
+static int render_rays_lit(rtmi_scene_t* s, uint64_t n, const void* orig4, const void* dir4, const void* keys, uint64_t seed,
+                           const rtmi_rays_t* rp, const rtmi_lit_t* lit, const rtmi_rays_out_t* out, void* hip_stream, rtmi_stats_t* stats,
+                           bool host) {
+    bool empty;
+    int rc = check_rays(s, n, orig4, dir4, keys, rp, out, stats, empty);
+    if (rc != RTMI_OK || empty) return rc;
+    rc = check_lit_params(lit);
+    if (rc != RTMI_OK) return rc;
+    rc = refuse_scene_lit(s);
+    if (rc != RTMI_OK) return rc;
+    const LitArgs la = lit_args(*lit);
+    return render_rays(s, n, orig4, dir4, keys, seed, rp, out, hip_stream, stats, host, &la);
+}
+
+int rtmi_render_rays_lit_device(rtmi_scene_t* s, uint64_t n, const void* orig4_device, const void* dir4_device, const void* keys_device,
+                                uint64_t seed, const rtmi_rays_t* rays, const rtmi_lit_t* lit, const rtmi_rays_out_t* out_device,
+                                void* hip_stream, rtmi_stats_t* stats) {
+    return render_rays_lit(s, n, orig4_device, dir4_device, keys_device, seed, rays, lit, out_device, hip_stream, stats, false);
+}
+
+int rtmi_render_rays_lit(rtmi_scene_t* s, uint64_t n, const float* orig4, const float* dir4, const uint32_t* keys, uint64_t seed,
+                         const rtmi_rays_t* rays, const rtmi_lit_t* lit, const rtmi_rays_out_t* out_host, rtmi_stats_t* stats) {
+    return render_rays_lit(s, n, orig4, dir4, keys, seed, rays, lit, out_host, nullptr, stats, true);
+}
+
 // ---------------------------------------------------------------- light bake (rtmi_bake*, bake.hpp)
 void rtmi_bake_defaults(rtmi_bake_t* p) {
     if (!p) return;
@@ -5101,7 +5213,7 @@ void rtmi_bake_defaults(rtmi_bake_t* p) {
 
 // Checks that come before any HIP call and before the scene is used (a CPU-only caller reaches them).
 static int check_bake(const rtmi_scene_t* s, uint64_t M, const void* pos4, const void* nrm4, const rtmi_bake_t* bp, const rtmi_bake_out_t* out,
-                      rtmi_stats_t* stats, bool& empty) {
+                      rtmi_stats_t* stats, bool& empty, bool lit_call = false, const void* direct = nullptr) {
     if (stats) memset(stats, 0, sizeof(*stats));
     empty = false;
     if (!s) return fail(RTMI_ERR_INVALID, "bake: NULL argument (scene)");
@@ -5114,13 +5226,14 @@ static int check_bake(const rtmi_scene_t* s, uint64_t M, const void* pos4, const
     if (M == 0) { empty = true; return RTMI_OK; }
     if (!pos4) return fail(RTMI_ERR_INVALID, "bake: NULL argument (pos4)");
     if (!nrm4) return fail(RTMI_ERR_INVALID, "bake: NULL argument (nrm4)");
-    if (!out->light && !out->open && !out->orig && !out->dir) return fail(RTMI_ERR_INVALID, "bake: all four outputs are NULL");
+    if (!out->light && !out->open && !out->orig && !out->dir && !direct)
+        return fail(RTMI_ERR_INVALID, lit_call ? "bake: all five outputs are NULL" : "bake: all four outputs are NULL");
     // (counts that are refused below anyway: the sizes must not wrap)
     const uint64_t m = std::min<uint64_t>(M, 1ull << 40), n = m * std::min<uint32_t>(bp->rays, 65537u);
-    const ByteRange r[6] = {{pos4, m * (bp->mode == RTMI_BAKE_TRIANGLES ? 48u : 16u), "pos4"}, {nrm4, m * 16, "nrm4"}, {out->light, m * 16, "light"},
-                            {out->open, m * 4, "open"}, {out->orig, n * 16, "orig"}, {out->dir, n * 16, "dir"}};
+    const ByteRange r[7] = {{pos4, m * (bp->mode == RTMI_BAKE_TRIANGLES ? 48u : 16u), "pos4"}, {nrm4, m * 16, "nrm4"}, {out->light, m * 16, "light"},
+                            {out->open, m * 4, "open"}, {out->orig, n * 16, "orig"}, {out->dir, n * 16, "dir"}, {direct, m * 16, "direct"}};
     size_t a, b;
-    if (ranges_overlap(r, 6, a, b))
+    if (ranges_overlap(r, 7, a, b))
         return fail(RTMI_ERR_INVALID, std::string("bake: buffers overlap (") + r[a].name + " and " + r[b].name + ")");
     if ((uint64_t)bp->pixel0 + M - 1 >= (1ull << 32))
         return fail(RTMI_ERR_INVALID, "bake: pixel0 + M - 1 must stay below 2^32 (the RNG key is 32 bits)");
@@ -5137,9 +5250,10 @@ static int check_bake(const rtmi_scene_t* s, uint64_t M, const void* pos4, const
 // the host variants' per-pixel buffers of the handle (acc: pos4, asq: nrm4; tile: light, acnt: open; no call keeps anything in
 // them between calls), its rays in the workspace queue, copied out before pass 2 reuses that queue.
 static int bake(rtmi_scene_t* s, uint64_t M, const void* pos4, const void* nrm4, uint64_t seed, const rtmi_bake_t* bp,
-                const rtmi_bake_out_t* out, void* hip_stream, rtmi_stats_t* stats, bool host) {
+                const rtmi_bake_out_t* out, void* hip_stream, rtmi_stats_t* stats, bool host, const LitArgs* lit = nullptr,
+                void* direct_out = nullptr) {
     bool empty;
-    int rc = check_bake(s, M, pos4, nrm4, bp, out, stats, empty);
+    int rc = check_bake(s, M, pos4, nrm4, bp, out, stats, empty, lit != nullptr, direct_out);
     if (rc != RTMI_OK || empty) return rc;
     RTMI_GUARD_BEGIN
     (void)hipGetLastError();
@@ -5149,20 +5263,26 @@ static int bake(rtmi_scene_t* s, uint64_t M, const void* pos4, const void* nrm4,
     const uint32_t pstride = tri ? 3u : 1u;  // float4 of pos4 per element
     const bool shade = maxdepth != 0 && out->light, want_rays = out->orig || out->dir;
     const bool traced = shade || out->open, counting = (s->options & RTMI_OPT_COUNTERS) != 0;
+    // rtmi_bake_lit*: the elements' own candidates, their walk and fold (with no light, direct is zeros and nothing is launched)
+    const bool want_direct = lit && direct_out, direct_walk = want_direct && lit->nlights != 0u;
     const uint64_t n = M * K;
     Work& w = s->w[0];
     hipStream_t st = s->istream[0], ust = host ? st : (hipStream_t)hip_stream;
     // batches hold whole elements: batch_paths rounded down to a multiple of K, at least K
     const uint64_t B = std::min<uint64_t>(std::max<uint64_t>(s->tune.batch_paths / K * K, K), n), mB = B / K;
-    if (traced || want_rays) {
+    if (traced || want_rays || direct_walk) {
         rc = ensure_workspace(w, (size_t)B, std::max(maxdepth, 1u));
         if (rc == RTMI_OK) rc = ensure_cstack(s, w);
+        if (rc != RTMI_OK) return rc;
+    }
+    if (lit && (shade || direct_walk)) {  // the shadow queue, answers, slots and direct stack of a batch
+        rc = ensure_lit_rays(s, (size_t)B, maxdepth, *lit);
         if (rc != RTMI_OK) return rc;
     }
     if (host) {
         HIPCHK(s->acc.ensure(mB * pstride));
         HIPCHK(s->asq.ensure(mB));
-        if (shade) HIPCHK(s->tile.ensure(mB));
+        if (shade || direct_walk) HIPCHK(s->tile.ensure(mB));
         if (out->open) HIPCHK(s->acnt.ensure(mB));
     }
     s->active_streams = 1;
@@ -5173,16 +5293,21 @@ static int bake(rtmi_scene_t* s, uint64_t M, const void* pos4, const void* nrm4,
         if (host) memset(out->light, 0, M * 16);
         else HIPCHK(hipMemsetAsync(out->light, 0, M * 16, st));
     }
+    if (want_direct && !direct_walk) {  // no light: d_k = (0, 0, 0, 0) for every k
+        if (host) memset(direct_out, 0, M * 16);
+        else HIPCHK(hipMemsetAsync(direct_out, 0, M * 16, st));
+    }
     DView dv{};  // what shade_pass<Samp::RAYS> reads of it: the depth, and the group size with its divisor
     dv.maxdepth = maxdepth; dv.spp = K;
     view_set_divisors(dv);
     const dim3 ew_grid((unsigned)(s->num_cu * 8)), ew_block(256);
     const uint32_t npass = shade ? maxdepth : traced ? 1u : 0u, epb = bake_step_elems(K);
     const FastDiv dK = make_fastdiv(K);
+    const bool lit_walks = lit && (shade || direct_walk);
     rtmi_stats_t sum{};
     float trace_ms = 0.f;
     uint32_t launches = 0;
-    for (uint64_t base = 0; base < n && (traced || want_rays); base += B) {
+    for (uint64_t base = 0; base < n && (traced || want_rays || direct_walk); base += B) {
         const uint32_t nb = (uint32_t)std::min<uint64_t>(B, n - base), mb = nb / K;
         const uint64_t mbase = base / K;
         const float4 *pos = (const float4*)pos4 + mbase * pstride, *nrm = (const float4*)nrm4 + mbase;
@@ -5198,10 +5323,35 @@ static int bake(rtmi_scene_t* s, uint64_t M, const void* pos4, const void* nrm4,
         }
         HIPCHK(hipMemsetAsync(w.ctrl.p, 0, sizeof(DCtrl), st));
         const dim3 gen_grid(std::min<unsigned>((unsigned)(s->num_cu * 8), (mb + epb - 1u) / epb));
-        if (tri)
+        if (lit_walks) HIPCHK(hipMemsetAsync(s->shadow[0].walk.ctrl.p, 0, sizeof(DCtrl), st));
+        if (direct_walk) {
+            // The elements' own candidates, before the gather paths use the shadow buffers and the sample colours: the live ones
+            // into the shadow queue counted in the walk's count[RTMI_MAX_PASSES] (no path level's: those are 1 .. maxdepth - 1),
+            // their walk, d_k into the workspace's sample colours, k_accum's fold into direct (host: staged in `tile`, which
+            // light's fold rewrites after the copy).
+            rtmi_scene::ShadowBuf& sb = s->shadow[0];
+            float4* direct = host ? s->tile.p : (float4*)direct_out + mbase;
+            if (tri)
+                hipLaunchKernelGGL(k_bake_lit_rays<true>, gen_grid, ew_block, 0, st, mb, K, dK, epb, pos, nrm, seed, (uint32_t)(bp->pixel0 + mbase),
+                                   *lit, sb.qo.p, sb.qd.p, sb.tmax.p, sb.lw.p, sb.slot.p, sb.walk.ctrl.p, (int)RTMI_MAX_PASSES);
+            else
+                hipLaunchKernelGGL(k_bake_lit_rays<false>, gen_grid, ew_block, 0, st, mb, K, dK, epb, pos, nrm, seed, (uint32_t)(bp->pixel0 + mbase),
+                                   *lit, sb.qo.p, sb.qd.p, sb.tmax.p, sb.lw.p, sb.slot.p, sb.walk.ctrl.p, (int)RTMI_MAX_PASSES);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(sb.walk.pass_ev[2 * maxdepth], st));
+            launch_occluded(s, sb.walk, st, (uint64_t)nb * lit->nlights, sb.qo.p, sb.qd.p, sb.tmax.p, sb.occ.p, (int)RTMI_MAX_PASSES,
+                            sb.walk.pass_ev[2 * maxdepth + 1], lit_rays_from_hits(s));
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(k_bake_lit_resolve, ew_grid, ew_block, 0, st, nb, lit->nlights, sb.slot.p, sb.occ.p, sb.lw.p, w.scol.p);
+            hipLaunchKernelGGL(k_accum, ew_grid, ew_block, 0, st, mb, K, w.scol.p, (float*)direct, 0u, mb, 1u, 0u, make_fastdiv(mb));
+            HIPCHK(hipGetLastError());
+            if (host) HIPCHK(hipMemcpyAsync((float4*)direct_out + mbase, direct, (size_t)mb * 16, hipMemcpyDeviceToHost, st));
+        }
+        const bool gather = traced || want_rays;  // false with direct alone: no gather ray is made
+        if (gather && tri)
             hipLaunchKernelGGL(k_bake_rays<true>, gen_grid, ew_block, 0, st, mb, K, dK, epb, pos, nrm, seed, (uint32_t)(bp->pixel0 + mbase), bp->bias,
                                qo, qd, w.qpath[0].p, w.ctrl.p);
-        else
+        else if (gather)
             hipLaunchKernelGGL(k_bake_rays<false>, gen_grid, ew_block, 0, st, mb, K, dK, epb, pos, nrm, seed, (uint32_t)(bp->pixel0 + mbase), bp->bias,
                                qo, qd, w.qpath[0].p, w.ctrl.p);
         HIPCHK(hipGetLastError());
@@ -5218,8 +5368,12 @@ static int bake(rtmi_scene_t* s, uint64_t M, const void* pos4, const void* nrm4,
             if (pass == 0 && open)  // before pass 1 rewrites the hit records
                 hipLaunchKernelGGL(k_bake_open, dim3(std::min<unsigned>((unsigned)(s->num_cu * 8), (mb + RTMI_BAKE_OPEN_ELEMS - 1u) / RTMI_BAKE_OPEN_ELEMS)),
                                    ew_block, 0, st, mb, K, w.hit_tf.p, open);
-            if (shade)
+            if (shade && lit) {
+                rc = lit_rays_pass(s, w, st, dv, seed, (uint32_t)(bp->pixel0 + mbase), nb, pass, *lit, pqo, pqd, nullptr, w.scol.p);
+                if (rc != RTMI_OK) return rc;
+            } else if (shade) {
                 launch_shade(s, w, st, Samp::RAYS, dv, seed, (uint32_t)(bp->pixel0 + mbase), nb, pass, pqo, pqd, w.scol.p, SLOW_OFF);
+            }
             HIPCHK(hipGetLastError());
         }
         if (shade) hipLaunchKernelGGL(k_accum, ew_grid, ew_block, 0, st, mb, K, w.scol.p, (float*)light, 0u, mb, 1u, 0u, make_fastdiv(mb));
@@ -5239,6 +5393,10 @@ static int bake(rtmi_scene_t* s, uint64_t M, const void* pos4, const void* nrm4,
             launches++;
             trace_ms += pm;
             if (s->verbose) fprintf(stderr, "[rtmi] bake batch@%llu pass %u: %u rays, trace %.3f ms\n", (unsigned long long)base, pass, h.count[pass], pm);
+        }
+        if (lit_walks) {  // the shadow rays' walks: one event pair per pass of the gather paths, the elements' own at [maxdepth]
+            rc = lit_rays_collect(s, st, shade ? 0u : maxdepth, direct_walk ? maxdepth + 1u : maxdepth, sum, trace_ms, launches);
+            if (rc != RTMI_OK) return rc;
         }
     }
     if (!host) {
@@ -5266,6 +5424,35 @@ int rtmi_bake_device(rtmi_scene_t* s, uint64_t M, const void* pos4_device, const
 int rtmi_bake(rtmi_scene_t* s, uint64_t M, const float* pos4, const float* nrm4, uint64_t seed, const rtmi_bake_t* bake_params,
               const rtmi_bake_out_t* out_host, rtmi_stats_t* stats) {
     return bake(s, M, pos4, nrm4, seed, bake_params, out_host, nullptr, stats, true);
+}
+
+// rtmi_bake_lit*: rtmi_bake*'s checks (direct among the outputs), then rtmi_render_lit*'s of its parameters, then its scene
+// refusals; all before any HIP call.  (An empty call returns where rtmi_bake* returns.)
+static_assert(offsetof(rtmi_bake_lit_out_t, direct) == sizeof(rtmi_bake_out_t) && offsetof(rtmi_bake_lit_out_t, dir) == offsetof(rtmi_bake_out_t, dir),
+              "rtmi_bake_lit_out_t begins with rtmi_bake_out_t");
+static int bake_lit(rtmi_scene_t* s, uint64_t M, const void* pos4, const void* nrm4, uint64_t seed, const rtmi_bake_t* bp, const rtmi_lit_t* lit,
+                    const rtmi_bake_lit_out_t* out, void* hip_stream, rtmi_stats_t* stats, bool host) {
+    rtmi_bake_out_t plain{};
+    if (out) { plain.light = out->light; plain.open = out->open; plain.orig = out->orig; plain.dir = out->dir; }
+    bool empty;
+    int rc = check_bake(s, M, pos4, nrm4, bp, out ? &plain : nullptr, stats, empty, true, out ? out->direct : nullptr);
+    if (rc != RTMI_OK || empty) return rc;
+    rc = check_lit_params(lit);
+    if (rc != RTMI_OK) return rc;
+    rc = refuse_scene_lit(s);
+    if (rc != RTMI_OK) return rc;
+    const LitArgs la = lit_args(*lit);
+    return bake(s, M, pos4, nrm4, seed, bp, &plain, hip_stream, stats, host, &la, out->direct);
+}
+
+int rtmi_bake_lit_device(rtmi_scene_t* s, uint64_t M, const void* pos4_device, const void* nrm4_device, uint64_t seed, const rtmi_bake_t* bake_params,
+                         const rtmi_lit_t* lit, const rtmi_bake_lit_out_t* out_device, void* hip_stream, rtmi_stats_t* stats) {
+    return bake_lit(s, M, pos4_device, nrm4_device, seed, bake_params, lit, out_device, hip_stream, stats, false);
+}
+
+int rtmi_bake_lit(rtmi_scene_t* s, uint64_t M, const float* pos4, const float* nrm4, uint64_t seed, const rtmi_bake_t* bake_params,
+                  const rtmi_lit_t* lit, const rtmi_bake_lit_out_t* out_host, rtmi_stats_t* stats) {
+    return bake_lit(s, M, pos4, nrm4, seed, bake_params, lit, out_host, nullptr, stats, true);
 }
 
 // rtmi_trace on device buffers: the rays are read where they are, one closest-hit launch, one elementwise kernel

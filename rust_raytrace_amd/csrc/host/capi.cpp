@@ -1056,6 +1056,50 @@ int rth_caster_bake_device(rth_scene_t* s, uint64_t M, const void* pos4_device, 
     });
 }
 
+int rth_caster_walk_rays_explicit_lit(rth_scene_t* s, uint64_t n, const float* o4, const float* d4, const uint32_t* keys, const rtmi_rays_t* rays,
+                                      const rtmi_lit_t* lit, const rtmi_rays_out_t* out_host, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_rays_explicit_lit(s->scene, n, o4, d4, keys, rays, lit, out_host, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
+int rth_caster_walk_rays_explicit_lit_device(rth_scene_t* s, uint64_t n, const void* orig4_device, const void* dir4_device,
+                                             const void* keys_device, const rtmi_rays_t* rays, const rtmi_lit_t* lit,
+                                             const rtmi_rays_out_t* out_device, void* hip_stream, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_rays_explicit_lit_device(s->scene, n, orig4_device, dir4_device, keys_device, rays, lit, out_device, hip_stream, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
+int rth_caster_bake_lit(rth_scene_t* s, uint64_t M, const float* pos4, const float* nrm4, const rtmi_bake_t* bake, const rtmi_lit_t* lit,
+                        const rtmi_bake_lit_out_t* out_host, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!bake || !lit || !out_host) throw std::runtime_error("NULL bake, lit or out");
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).bake_lit(s->scene, M, pos4, nrm4, *bake, *lit, *out_host, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
+int rth_caster_bake_lit_device(rth_scene_t* s, uint64_t M, const void* pos4_device, const void* nrm4_device, const rtmi_bake_t* bake,
+                               const rtmi_lit_t* lit, const rtmi_bake_lit_out_t* out_device, void* hip_stream, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!bake || !lit || !out_device) throw std::runtime_error("NULL bake, lit or out");
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).bake_lit_device(s->scene, M, pos4_device, nrm4_device, *bake, *lit, *out_device, hip_stream, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
+
 int rth_caster_trace_records(rth_scene_t* s, uint64_t n, const float* o4, const float* d4, rtmi_ray_record_t* recs, uint32_t* leaf_ids,
                              uint64_t leaf_cap, uint64_t* leaf_total, rtmi_stats_t* stats) {
     return guarded([&] {

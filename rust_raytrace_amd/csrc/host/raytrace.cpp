@@ -1005,6 +1005,52 @@ void HipRayCaster::bake_device(const Scene& s, uint64_t M, const void* pos4_devi
     progress.stats = st;
 }
 
+void HipRayCaster::walk_rays_explicit_lit(const Scene& s, uint64_t n, const float* orig4, const float* dir4, const uint32_t* keys,
+                                          const rtmi_rays_t* rays, const rtmi_lit_t* lit, const rtmi_rays_out_t* out_host,
+                                          ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_rays_lit(h, n, orig4, dir4, keys, seed, rays, lit, out_host, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_rays_lit: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
+void HipRayCaster::walk_rays_explicit_lit_device(const Scene& s, uint64_t n, const void* orig4_device, const void* dir4_device,
+                                                 const void* keys_device, const rtmi_rays_t* rays, const rtmi_lit_t* lit,
+                                                 const rtmi_rays_out_t* out_device, void* hip_stream, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_rays_lit_device(h, n, orig4_device, dir4_device, keys_device, seed, rays, lit, out_device, hip_stream, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_rays_lit_device: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
+void HipRayCaster::bake_lit(const Scene& s, uint64_t M, const float* pos4, const float* nrm4, const rtmi_bake_t& bake, const rtmi_lit_t& lit,
+                            const rtmi_bake_lit_out_t& out_host, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    rtmi_stats_t st;
+    const int rc = rtmi_bake_lit(h, M, pos4, nrm4, seed, &bake, &lit, &out_host, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_bake_lit: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
+void HipRayCaster::bake_lit_device(const Scene& s, uint64_t M, const void* pos4_device, const void* nrm4_device, const rtmi_bake_t& bake,
+                                   const rtmi_lit_t& lit, const rtmi_bake_lit_out_t& out_device, void* hip_stream, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    rtmi_stats_t st;
+    const int rc = rtmi_bake_lit_device(h, M, pos4_device, nrm4_device, seed, &bake, &lit, &out_device, hip_stream, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_bake_lit_device: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
 void HipRayCaster::walk_rays_ao(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
                                 const rtmi_ao_t& ao, float* out, ProgressCtx& progress) {
     rtmi_scene_t* h = resident(s);

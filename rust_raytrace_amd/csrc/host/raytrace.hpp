@@ -285,6 +285,17 @@ public:
               ProgressCtx& progress);
     void bake_device(const Scene& s, uint64_t M, const void* pos4_device, const void* nrm4_device, const rtmi_bake_t& bake,
                      const rtmi_bake_out_t& out_device, void* hip_stream, ProgressCtx& progress);
+    // Both with box lights (rtmi_render_rays_lit* / rtmi_bake_lit*, which rtmi.h defines): the lamps sampled at every Matte hit
+    // of every path, and for the bake at the element itself (out.direct).
+    void walk_rays_explicit_lit(const Scene& s, uint64_t n, const float* orig4, const float* dir4, const uint32_t* keys, const rtmi_rays_t* rays,
+                                const rtmi_lit_t* lit, const rtmi_rays_out_t* out_host, ProgressCtx& progress);
+    void walk_rays_explicit_lit_device(const Scene& s, uint64_t n, const void* orig4_device, const void* dir4_device, const void* keys_device,
+                                       const rtmi_rays_t* rays, const rtmi_lit_t* lit, const rtmi_rays_out_t* out_device, void* hip_stream,
+                                       ProgressCtx& progress);
+    void bake_lit(const Scene& s, uint64_t M, const float* pos4, const float* nrm4, const rtmi_bake_t& bake, const rtmi_lit_t& lit,
+                  const rtmi_bake_lit_out_t& out_host, ProgressCtx& progress);
+    void bake_lit_device(const Scene& s, uint64_t M, const void* pos4_device, const void* nrm4_device, const rtmi_bake_t& bake,
+                         const rtmi_lit_t& lit, const rtmi_bake_lit_out_t& out_device, void* hip_stream, ProgressCtx& progress);
     // Ambient occlusion (rtmi_render_ao / rtmi_render_ao_device, which rtmi.h defines): one float per pixel, the share of
     // ao.rays hemisphere rays per primary sample of [sample0, sample0 + nsamples) that are not occluded within ao.radius.
     void walk_rays_ao(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,

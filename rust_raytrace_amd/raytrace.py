@@ -1830,7 +1830,7 @@ class HipRayCaster:
         return _ffi.Rays(maxdepth, group, pixel0 & 0xFFFFFFFF, cls.RAYS_MAKE_RAY if make_ray else 0)
 
     def walk_rays_explicit(self, s, orig4, dir4, maxdepth, group=1, keys=None, pixel0=0, make_ray=False, color=True, mean=False,
-                           albedo=False, normal=False, ids=False):
+                           albedo=False, normal=False, ids=False, _lit=None):
         """Path tracing of caller-supplied rays (rtmi_render_rays; include/rtmi.h defines it): orig4 and dir4 are (n, 4) float32
         arrays, a ray's origin and unit direction as make_ray stores them (make_ray=True: the library normalises the
         directions).  The RNG key of ray i is keys[i] = (pixel, sample) ((n, 2) uint32) or, without keys, (pixel0 + i // group,
@@ -1859,12 +1859,16 @@ class HipRayCaster:
         self._config(s)
         st = _ffi.Stats()
         wall = C.c_double(0)
-        _chk(_ffi.lib().rth_caster_walk_rays_explicit(s.h, n, _p(o4), _p(d4), _p(kk) if kk is not None else None, C.byref(r), C.byref(out),
-                                                      C.byref(st), C.byref(wall)))
+        if _lit is not None:
+            _chk(_ffi.lib().rth_caster_walk_rays_explicit_lit(s.h, n, _p(o4), _p(d4), _p(kk) if kk is not None else None, C.byref(r),
+                                                              C.byref(_lit), C.byref(out), C.byref(st), C.byref(wall)))
+        else:
+            _chk(_ffi.lib().rth_caster_walk_rays_explicit(s.h, n, _p(o4), _p(d4), _p(kk) if kk is not None else None, C.byref(r), C.byref(out),
+                                                          C.byref(st), C.byref(wall)))
         return bufs, ProgressCtx(st.rays, wall.value, st.as_dict())
 
     def walk_rays_explicit_device(self, s, orig4, dir4, maxdepth, group=1, keys=None, pixel0=0, make_ray=False, color=None, mean=None,
-                                  albedo=None, normal=None, ids=None, stream=None):
+                                  albedo=None, normal=None, ids=None, stream=None, _lit=None):
         """The same on torch tensors on the scene's device (rtmi_render_rays_device), read and written in place: orig4 and dir4
         contiguous float32 of n * 4 elements, keys None or contiguous int32 / uint32 of n * 2; each output a contiguous tensor or
         None (not all): color float32 of n * 4, mean, albedo and normal float32 of (n // group) * 4, ids int32 or uint32 of
@@ -1891,11 +1895,28 @@ class HipRayCaster:
         out = _ffi.RaysOut(*[x.data_ptr() if x is not None else None for _, x, _, _ in spec])
         st = _ffi.Stats()
         wall = C.c_double(0)
-        _chk(_ffi.lib().rth_caster_walk_rays_explicit_device(s.h, n, C.c_void_p(orig4.data_ptr()), C.c_void_p(dir4.data_ptr()),
-                                                             C.c_void_p(keys.data_ptr()) if keys is not None else None, C.byref(r),
-                                                             C.byref(out), C.c_void_p(getattr(stream, "cuda_stream", stream) or 0),
-                                                             C.byref(st), C.byref(wall)))
+        kp = C.c_void_p(keys.data_ptr()) if keys is not None else None
+        sp = C.c_void_p(getattr(stream, "cuda_stream", stream) or 0)
+        if _lit is not None:
+            _chk(_ffi.lib().rth_caster_walk_rays_explicit_lit_device(s.h, n, C.c_void_p(orig4.data_ptr()), C.c_void_p(dir4.data_ptr()), kp,
+                                                                     C.byref(r), C.byref(_lit), C.byref(out), sp, C.byref(st), C.byref(wall)))
+        else:
+            _chk(_ffi.lib().rth_caster_walk_rays_explicit_device(s.h, n, C.c_void_p(orig4.data_ptr()), C.c_void_p(dir4.data_ptr()), kp,
+                                                                 C.byref(r), C.byref(out), sp, C.byref(st), C.byref(wall)))
         return ProgressCtx(st.rays, wall.value, st.as_dict())
+
+    def walk_rays_explicit_lit(self, s, orig4, dir4, maxdepth, lit, **kw):
+        """walk_rays_explicit with box lights sampled at every Matte hit that bounces (rtmi_render_rays_lit; include/rtmi.h defines
+        it): the same rays, keys, groups and outputs, and at each such hit one shadow ray per light of `lit` (lit_params' result,
+        or its lights argument) whose unoccluded light is added to what the surface passes on.  Returns (dict, ctx)."""
+        a = lit if isinstance(lit, _ffi.Lit) else self.lit_params(lit)
+        return self.walk_rays_explicit(s, orig4, dir4, maxdepth, _lit=a, **kw)
+
+    def walk_rays_explicit_lit_device(self, s, orig4, dir4, maxdepth, lit, **kw):
+        """The same on torch tensors on the scene's device (rtmi_render_rays_lit_device): walk_rays_explicit_device's arguments.
+        Returns ctx."""
+        a = lit if isinstance(lit, _ffi.Lit) else self.lit_params(lit)
+        return self.walk_rays_explicit_device(s, orig4, dir4, maxdepth, _lit=a, **kw)
 
     BAKE_MODES = {"points": _ffi.BAKE_POINTS, "triangles": _ffi.BAKE_TRIANGLES}
     BAKE_OUTPUTS = ("light", "open", "orig", "dir")
@@ -1939,7 +1960,7 @@ class HipRayCaster:
             raise ValueError("pixel0 + M - 1 must stay below 2^32")
         return nnrm
 
-    def bake(self, s, pos4, nrm4, params, light=True, open=False, orig=False, dir=False):
+    def bake(self, s, pos4, nrm4, params, light=True, open=False, orig=False, dir=False, _lit=None, _direct=False):
         """Light baked at surface points or over triangles (rtmi_bake; include/rtmi.h defines it).  params: bake_params().
         nrm4: (M, 4) float32, the side to bake of each element, used as given.  pos4: (M, 4) float32 points, or (3 M, 4), the
         corners of M triangles.  Per element params.rays gather rays are made on the device and path-traced at depth
@@ -1951,17 +1972,26 @@ class HipRayCaster:
         n = m * params.rays
         shapes = {"light": (m, 4), "open": (m,), "orig": (n, 4), "dir": (n, 4)}
         want = dict(light=light, open=open, orig=orig, dir=dir)
-        bufs = {k: np.zeros(shapes[k], np.float32) for k in self.BAKE_OUTPUTS if want[k]}
+        names = self.BAKE_OUTPUTS
+        if _lit is not None:
+            shapes["direct"], want["direct"], names = (m, 4), _direct, self.BAKE_LIT_OUTPUTS
+        bufs = {k: np.zeros(shapes[k], np.float32) for k in names if want[k]}
         if not bufs:
-            raise ValueError("at least one of light, open, orig and dir must be produced")
-        out = _ffi.BakeOut(*[_p(bufs[k]) if k in bufs else None for k in self.BAKE_OUTPUTS])
+            raise ValueError("at least one of " + ", ".join(names[:-1]) + " and " + names[-1] + " must be produced")
+        ptrs = [_p(bufs[k]) if k in bufs else None for k in names]
         self._config(s)
         st = _ffi.Stats()
         wall = C.c_double(0)
-        _chk(_ffi.lib().rth_caster_bake(s.h, m, _p(p4), _p(n4), C.byref(params), C.byref(out), C.byref(st), C.byref(wall)))
+        if _lit is not None:
+            out = _ffi.BakeLitOut(*ptrs)
+            _chk(_ffi.lib().rth_caster_bake_lit(s.h, m, _p(p4), _p(n4), C.byref(params), C.byref(_lit), C.byref(out), C.byref(st),
+                                                C.byref(wall)))
+        else:
+            out = _ffi.BakeOut(*ptrs)
+            _chk(_ffi.lib().rth_caster_bake(s.h, m, _p(p4), _p(n4), C.byref(params), C.byref(out), C.byref(st), C.byref(wall)))
         return bufs, ProgressCtx(st.rays, wall.value, st.as_dict())
 
-    def bake_device(self, s, pos4, nrm4, params, light=None, open=None, orig=None, dir=None, stream=None):
+    def bake_device(self, s, pos4, nrm4, params, light=None, open=None, orig=None, dir=None, stream=None, _lit=None, _direct=None):
         """The same on torch tensors on the scene's device (rtmi_bake_device), read and written in place: nrm4 contiguous
         float32 of M * 4 elements, pos4 of M * 4 (points) or 3 M * 4 (triangles); each output a contiguous float32 tensor or None
         (not all): light of M * 4, open of M, orig and dir of M * rays * 4; no two buffers may overlap.  The work starts after
@@ -1974,26 +2004,51 @@ class HipRayCaster:
         m = self._bake_count(params, pos4.numel() // 4, nrm4.numel() // 4)
         n = m * params.rays
         spec = (("light", light, 4 * m), ("open", open, m), ("orig", orig, 4 * n), ("dir", dir, 4 * n))
+        if _lit is not None:
+            spec += (("direct", _direct, 4 * m),)
         for name, x, want in spec:
             if x is not None:
                 self._tensor(name, x, want, ("torch.float32",))
         if all(x is None for _, x, _ in spec):
-            raise ValueError("at least one of light, open, orig and dir must be given")
+            raise ValueError("at least one of " + ", ".join(k for k, _, _ in spec[:-1]) + " and " + spec[-1][0] + " must be given")
         spans = sorted([(pos4.data_ptr(), 4 * pos4.numel()), (nrm4.data_ptr(), 16 * m)] +
                        [(x.data_ptr(), 4 * want) for _, x, want in spec if x is not None])
         if any(a[0] + a[1] > b[0] for a, b in zip(spans, spans[1:]) if a[1] and b[1]):
             raise ValueError("the buffers must not overlap")
         self._config(s)
-        out = _ffi.BakeOut(*[x.data_ptr() if x is not None else None for _, x, _ in spec])
+        ptrs = [x.data_ptr() if x is not None else None for _, x, _ in spec]
         st = _ffi.Stats()
         wall = C.c_double(0)
-        _chk(_ffi.lib().rth_caster_bake_device(s.h, m, C.c_void_p(pos4.data_ptr()), C.c_void_p(nrm4.data_ptr()), C.byref(params),
-                                               C.byref(out), C.c_void_p(getattr(stream, "cuda_stream", stream) or 0), C.byref(st),
-                                               C.byref(wall)))
+        sp = C.c_void_p(getattr(stream, "cuda_stream", stream) or 0)
+        if _lit is not None:
+            out = _ffi.BakeLitOut(*ptrs)
+            _chk(_ffi.lib().rth_caster_bake_lit_device(s.h, m, C.c_void_p(pos4.data_ptr()), C.c_void_p(nrm4.data_ptr()), C.byref(params),
+                                                       C.byref(_lit), C.byref(out), sp, C.byref(st), C.byref(wall)))
+        else:
+            out = _ffi.BakeOut(*ptrs)
+            _chk(_ffi.lib().rth_caster_bake_device(s.h, m, C.c_void_p(pos4.data_ptr()), C.c_void_p(nrm4.data_ptr()), C.byref(params),
+                                                   C.byref(out), sp, C.byref(st), C.byref(wall)))
         return ProgressCtx(st.rays, wall.value, st.as_dict())
 
+    BAKE_LIT_OUTPUTS = BAKE_OUTPUTS + ("direct",)
+
+    def bake_lit(self, s, pos4, nrm4, params, lit, light=True, open=False, orig=False, dir=False, direct=True):
+        """bake() with box lights (rtmi_bake_lit; include/rtmi.h defines it).  lit: lit_params' result, or its lights argument.
+        light is then the indirect light with the lamps lighting every Matte bounce of every gather path, and direct (M, 4)
+        float32 the lamps' light arriving at the element itself; a lightmap texel of a surface (color, alpha) is
+        mix_color(color, light + direct, alpha).  Pass unit normals: direct scales with their length.
+        Returns (dict of the requested arrays, ctx)."""
+        a = lit if isinstance(lit, _ffi.Lit) else self.lit_params(lit)
+        return self.bake(s, pos4, nrm4, params, light=light, open=open, orig=orig, dir=dir, _lit=a, _direct=direct)
+
+    def bake_lit_device(self, s, pos4, nrm4, params, lit, light=None, open=None, orig=None, dir=None, direct=None, stream=None):
+        """The same on torch tensors on the scene's device (rtmi_bake_lit_device): bake_device's arguments and direct, a
+        contiguous float32 tensor of M * 4 or None.  Returns ctx."""
+        a = lit if isinstance(lit, _ffi.Lit) else self.lit_params(lit)
+        return self.bake_device(s, pos4, nrm4, params, light=light, open=open, orig=orig, dir=dir, stream=stream, _lit=a, _direct=direct)
+
     def bake_triangles(self, s, corners, normals, rays=None, maxdepth=None, pixel0=None, bias=None, light=True, open=False,
-                       orig=False, dir=False):
+                       orig=False, dir=False, _lit=None, _direct=False):
         """bake() over whole triangles: corners (M, 3, 3) or (M, 3, 4) float32, normals (M, 3) or (M, 4), the side of each
         triangle to bake (its `norm` or the negative); three-component vectors get lane 3 = +0.  One colour per face, for a
         flat-shaded view of the scene.  Returns (dict of the requested arrays, ctx)."""
@@ -2007,7 +2062,14 @@ class HipRayCaster:
         p4[:, : c.shape[2]] = c.reshape(-1, c.shape[2])
         n4 = np.zeros((c.shape[0], 4), np.float32)
         n4[:, : nn.shape[1]] = nn
-        return self.bake(s, p4, n4, self.bake_params("triangles", rays, maxdepth, pixel0, bias), light=light, open=open, orig=orig, dir=dir)
+        return self.bake(s, p4, n4, self.bake_params("triangles", rays, maxdepth, pixel0, bias), light=light, open=open, orig=orig, dir=dir,
+                         _lit=_lit, _direct=_direct)
+
+    def bake_triangles_lit(self, s, corners, normals, lit, direct=True, **kw):
+        """bake_triangles() with box lights (bake_lit over whole triangles): bake_triangles' arguments, lit as bake_lit takes it.
+        Returns (dict of the requested arrays, ctx)."""
+        a = lit if isinstance(lit, _ffi.Lit) else self.lit_params(lit)
+        return self.bake_triangles(s, corners, normals, _lit=a, _direct=direct, **kw)
 
     def _records(self, n, call, pixel=None):
         """Size query, then the fill (rth_caster_*_records)"""
