@@ -1481,6 +1481,85 @@ int rtmi_bake_lit_device(rtmi_scene_t* scene, uint64_t M, const void* pos4_devic
 int rtmi_bake_lit(rtmi_scene_t* scene, uint64_t M, const float* pos4, const float* nrm4, uint64_t seed, const rtmi_bake_t* bake,
                   const rtmi_lit_t* lit, const rtmi_bake_lit_out_t* out_host, rtmi_stats_t* stats);
 
+/* EMISSIVE TRIANGLES sampled at matte hits: next-event estimation towards lamps that are part of the scene.  A
+ * Solid triangle ends a path with its surface colour, and nothing limits that colour to 1: a bright Solid triangle IS an area
+ * light in rtmi_render* (visible, reflected, with the penumbrae of its shape), found only by the bounces that happen to hit it.
+ * rtmi_scene_set_emitters marks such triangles as lamps; rtmi_render_emissive[_device] is a progressive pass that renders, in
+ * expectation, the image rtmi_render_samples[_device] renders of the same scene, with less noise where small lamps light matte
+ * surfaces: at every Matte hit that bounces, one shadow ray is also sent to a point drawn on the lamps, and combined with the
+ * bounce's own chance of hitting a lamp by the balance heuristic.  NOT part of the reference; build-defined: what follows IS the
+ * definition, tests/emissive_ref.py pins it bit for bit.  float32 throughout, every step rounded (no fused multiply-add), vdot the
+ * ordered sum seeded with +0, all four lanes; + - * /, sqrt, fabsf and comparisons only.
+ *
+ * rtmi_scene_set_emitters(scene, corners9, emit_of_tri, n): n == ntris bytes, entry 0 the sentinel's (ignored); a non-zero byte
+ *   marks the triangle.  corners9 as in rtmi_scene_set_normals (read for the marked triangles only).  A marked triangle's surface
+ *   must be Solid and its corners finite, else RTMI_ERR_INVALID naming the triangle and the marks stay as they were.  A lamp's
+ *   radiance is its surface colour (any float; scene creation does not limit a colour).  emit_of_tri == NULL or
+ *   n == 0 clears the marks.  Marking changes no other call: every other entry point renders the scene exactly as before.
+ * The lamps are numbered e = 1 .. L in triangle order.  Per lamp, from its corners c0, c1, c2 and its radiance (r, g, b):
+ *     e1 = c1 - c0;  e2 = c2 - c0;  x = (e1.y * e2.z - e1.z * e2.y, e1.z * e2.x - e1.x * e2.z, e1.x * e2.y - e1.y * e2.x)
+ *     A = 0.5f * sqrtf(vdot(x, x));  n_e = the triangle record's norm (unit, as every shading statement uses it)
+ *     w = A * ((r + g) + b);  a w that is not > 0.f (a NaN too) or not finite counts as 0.f
+ *     wmax = the maximum of w over the lamps
+ *     s = w * (1048576.f / wmax);  s = !(s >= 0.f) ? 0.f : (s > 1048576.f ? 1048576.f : s);  q_e = 1 + (uint32)s
+ *     wmax == 0.f: q = 1 for every lamp.  total = the sum of q (uint64);  C = the inclusive prefix sum of q over e (uint64)
+ *   The tables are built on the device on the first call that needs them, kept on the handle and dropped by
+ *   rtmi_scene_set_emitters.  rtmi_scene_get_emitter_sampler copies them back, building them if need be (every pointer but
+ *   nlamps_out may be NULL): q (L uint32), C (L uint64), the lamp number of every triangle (ntris uint32, 0 = not a lamp), the
+ *   records (L * 20 floats: (c0, A), (e1, w), (e2, 0), (n_e, 0), (r, g, b, 0)), total and L.  *nlamps_out = 0: no lamps.
+ *
+ * pe(e, x2, dir) = ((((float)q_e / (float)total) / A) * x2) / fabsf(vdot(n_e, dir)): the density per solid angle of the point where
+ *   a ray along dir meets lamp e, x2 the squared distance to it.
+ * pb(n, d, s): rtmi_render_envlight*'s, the pdf per solid angle of the Matte bounce.
+ *
+ * The pass.  Contract: rtmi_render_samples[_device]'s in every respect, as rtmi_render_shadowed* states it.  The rays of every pass
+ * are exactly those of rtmi_render_samples_device for the same arguments: no ray, no RNG block 0 .. maxdepth and no plain "Rays"
+ * count moves.  At the hit of a path's ray number j, when the hit is a Matte surface (neither a miss nor an edge face) and the path
+ * bounces (maxdepth - j - 1 != 0: an exhausted level gets no sample):
+ *     point = rd * t + ro;  n = the triangle's norm, * (-1.f) when face & 1
+ *     w = RNG block 0xC0040000 | j of (seed, pixel, sample)   (distinct from every block of rtmi_render_lit*, rtmi_render_rays_lit*
+ *         and rtmi_bake_lit* under one key: those are 0xC0000000 | l << 16 | level with l <= 3)
+ *     T = the upper 64 bits of ((uint64)w0 << 32 | w1) * total;  lamp e: the first e with C[e] > T
+ *     a = u(w2);  b = u(w3);  if a + b > 1.f: a = 1.f - a, b = 1.f - b;  y = (c0 + e1 * a) + e2 * b
+ *     dv = y - point;  d2 = vdot(dv, dv);  omega = vunit(dv);  cos = vdot(n, omega);  s = omega * (2.f * cos) - n
+ *     o = point + s * 0.001f                      (where the bounce along omega starts: the shadow ray sees what it would)
+ *     live when cos > 0.f and fabsf(vdot(n_e, omega)) > 0.f and some lane 0..2 of the radiance != 0.f
+ *     the shadow ray (o, omega) is traced by the scene's closest-hit definition (rtmi_trace's); it counts when its first hit is
+ *     lamp e itself on a non-edge face (tri == the lamp's triangle, !(face & 2)), at time ts:
+ *       pbv = pb(n, omega, s);  pe' = pe(e, ts * ts, omega);  pet = pe(e, d2, omega);  wB = pe' / (pbv + pe')
+ *       direct_j = radiance * ((pbv / pet) * wB);  otherwise direct_j = (0, 0, 0)
+ *   and with nr the bounce ray (lambertian_ray with rv = random_vec of block j + 1): wp = pb(n, nr.dir, rv).
+ *   A Reflective level has direct_j = 0 and wp = "no sample"; so has the primary ray (wp) and an exhausted level (direct_j).
+ * Colour: a ray number j >= 1 whose hit is a lamp's non-edge face, with wp >= 0.f from the level before: the lamp's colour *
+ *   (wp / (wp + pe(e, t * t, rd))), e and t from the hit.  Every other Solid end (a primary ray's, a mirror's, a Solid triangle
+ *   that is no lamp), edge faces, misses (the sky constant, or the environment's plain lookup) and the black of exhausted depth as
+ *   in color_ray.  The fold is c = mix_color(color_j, c + direct_j, alpha_j), inside-out over the path's Matte / Reflective levels.
+ *   Both strategies evaluate pe from the hit record of their own ray by the same statements, so their weights sum to one for one
+ *   ray.  (Occlusion, the edge band and lamps behind lamps need no limit and no epsilon: a candidate is paid exactly where the
+ *   bounce ray along omega would have been.)  No case is special: non-finite values propagate as the arithmetic gives them.
+ * Scenes: octree, linear list, generic tree and RTMI_OPT_GENERIC; with or without an environment.  RTMI_ERR_UNSUPPORTED, before
+ *   any HIP call, stats cleared: a scene without lamps; with analytic spheres, a dielectric, vertex normals, textures or normal
+ *   maps; RTMI_OPT_BVH (a non-exact first hit would break the "first hit is lamp e" test).  The handle stays usable.
+ * RTMI_ERR_INVALID, before any HIP call and before the scene is used, stats cleared: every check of rtmi_render_samples[_device].
+ * stats: as rtmi_render_shadowed* fills them: rays = the plain rays + the live shadow rays, trace_launches = 2 per pass and batch
+ *   (an empty event pair at the exhausted pass), primary_ms the path rays' closest-hit launches, bounce_ms the shadow rays'.
+ * How: rtmi_render_envlight*'s pass structure: k_emissive_rays, the scene's closest-hit launch of the shadow queue into hit records
+ *   of its own, k_shade_emissive per pass; beside the plain workspace 64 B per path (queue, weights, slot, hit records, wp; 4 B more on an octree) and 16 B
+ *   per path and level (the direct stack), allocated by this call only.
+ * Not here: lamps on smooth, textured, normal-mapped or glass scenes; Matte or textured emitters; more than one sample per hit; box
+ *   lights or the environment's sampling in the same pass; explicit rays, bakes, adaptive variants, view batches and denoised
+ *   wrappers; the path kernels (pipeline 3). */
+int rtmi_scene_set_emitters(rtmi_scene_t* scene, const float* corners9, const uint8_t* emit_of_tri /* n bytes, or NULL: clear */,
+                            uint64_t n);
+int rtmi_scene_get_emitter_sampler(rtmi_scene_t* scene, uint32_t* q_out, uint64_t* cum_out, uint32_t* lamp_of_tri_out,
+                                   float* lamps_out, uint64_t* total_out, uint32_t* nlamps_out);
+int rtmi_render_emissive_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile,
+                                uint32_t sample0, uint32_t nsamples, void* accum_device, void* out_device /* or NULL */,
+                                void* hip_stream, rtmi_stats_t* stats);
+int rtmi_render_emissive(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
+                         uint32_t sample0, uint32_t nsamples, float* accum_host, float* out_host /* or NULL */,
+                         rtmi_stats_t* stats);
+
 /* A shaded preview in one call: albedo, ambient occlusion and up to four coloured box lights composed PER
  * SAMPLE on the device, from one primary pass per batch and one any-hit walk of the AO rays and every light's live shadow
  * rays together.  The per-pixel buffers of rtmi_render_features*, rtmi_render_ao* and rtmi_render_light* are means over a

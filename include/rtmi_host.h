@@ -261,6 +261,22 @@ int rth_caster_walk_envlight_device(rth_scene_t* s, uint32_t w, uint32_t h, cons
                                     void* accum_device, void* out_device, void* hip_stream, rtmi_stats_t* stats,
                                     double* wall_seconds);
 int rth_caster_env_sampler(rth_scene_t* s, uint32_t* q_out, uint64_t cap, uint64_t* total_out, uint32_t* n_out);
+/* Emissive triangles (rtmi_scene_set_emitters in rtmi.h, which defines them).  rth_scene_set_emitters marks triangles first,
+ * first + 1, ... (count bytes, non-zero = a lamp; a marked triangle must be Solid); NULL or count 0 clears every mark.  Kept with
+ * the scene: a caster applies the marks to every resident copy.  rth_scene_get_emitters: one byte per triangle of the scene.
+ * rth_caster_walk_emissive[_device] (rtmi_render_emissive / rtmi_render_emissive_device): rth_caster_walk_samples[_device] in every
+ * respect.  rth_caster_emitter_sampler uploads if need be and reads the lamps' tables back (rtmi_scene_get_emitter_sampler): at
+ * most cap_lamps lamps and cap_tris triangles; with every output pointer NULL it returns the lamp count and the total alone. */
+int rth_scene_set_emitters(rth_scene_t* s, const uint8_t* emit_of_tri, uint64_t first, uint64_t count);
+int rth_scene_get_emitters(const rth_scene_t* s, uint8_t* emit_of_tri_out, uint64_t cap_tris);
+int rth_caster_walk_emissive(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp, uint64_t row0,
+                             uint64_t nrows, uint32_t sample0, uint32_t nsamples, float* accum_host, float* out_host, rtmi_stats_t* stats,
+                             double* wall_seconds);
+int rth_caster_walk_emissive_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                                    const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, void* accum_device, void* out_device,
+                                    void* hip_stream, rtmi_stats_t* stats, double* wall_seconds);
+int rth_caster_emitter_sampler(rth_scene_t* s, uint32_t* q_out, uint64_t* cum_out, uint32_t* lamp_of_tri_out, float* lamps_out,
+                               uint64_t cap_lamps, uint64_t cap_tris, uint64_t* total_out, uint32_t* nlamps_out);
 /* Path tracing with up to four coloured box lights sampled at every matte hit (rtmi_render_lit / rtmi_render_lit_device in rtmi.h,
  * which defines it): rth_caster_walk_samples[_device] in every respect; lit must not be NULL. */
 int rth_caster_walk_lit(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp, uint64_t row0,

@@ -356,6 +356,15 @@ def lib():
     L.rth_caster_walk_envlight.argtypes = [vp, u32, u32, vp, u64, u64, u64, u64, u32, u32, vp, vp, vp, vp, vp]
     L.rth_caster_walk_envlight_device.argtypes = [vp, u32, u32, vp, u64, u64, vp, u32, u32, vp, vp, vp, vp, vp, vp]
     L.rth_caster_env_sampler.argtypes = [vp, vp, u64, vp, vp]
+    L.rtmi_scene_set_emitters.argtypes = [vp, vp, vp, u64]
+    L.rtmi_scene_get_emitter_sampler.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.rtmi_render_emissive.argtypes = [vp, vp, u64, u32, u32, u32, u32, vp, vp, vp]
+    L.rtmi_render_emissive_device.argtypes = [vp, vp, u64, vp, u32, u32, vp, vp, vp, vp]
+    L.rth_scene_set_emitters.argtypes = [vp, vp, u64, u64]
+    L.rth_scene_get_emitters.argtypes = [vp, vp, u64]
+    L.rth_caster_walk_emissive.argtypes = [vp, u32, u32, vp, u64, u64, u64, u64, u32, u32, vp, vp, vp, vp]
+    L.rth_caster_walk_emissive_device.argtypes = [vp, u32, u32, vp, u64, u64, vp, u32, u32, vp, vp, vp, vp, vp]
+    L.rth_caster_emitter_sampler.argtypes = [vp, vp, vp, vp, vp, u64, u64, vp, vp]
     L.rtmi_lit_defaults.restype = None
     L.rtmi_lit_defaults.argtypes = [vp]
     L.rtmi_render_lit.argtypes = [vp, vp, u64, u32, u32, u32, u32, vp, vp, vp, vp]
@@ -389,10 +398,10 @@ def lib():
 # every symbol include/rtmi.h and include/rtmi_host.h declare
 RTMI_SYMBOLS = ["rtmi_device_count", "rtmi_scene_create", "rtmi_scene_destroy", "rtmi_scene_set_options",
                 "rtmi_scene_get_tuning", "rtmi_scene_set_tuning", "rtmi_scene_set_spheres", "rtmi_environment_defaults", "rtmi_scene_set_environment", "rtmi_scene_get_environment", "rtmi_sky_defaults", "rtmi_scene_set_sky", "rtmi_scene_set_normals", "rtmi_scene_get_normals", "rtmi_smooth_normals", "rtmi_scene_set_textures", "rtmi_scene_get_uvs", "rtmi_scene_get_texture", "rtmi_project_uvs", "rtmi_normal_maps_defaults", "rtmi_scene_set_normal_maps", "rtmi_scene_get_normal_maps", "rtmi_normal_map_frames", "rtmi_normal_map_from_height", "rtmi_scene_set_corners", "rtmi_render", "rtmi_render_frame_multi",
-                "rtmi_render_device", "rtmi_render_tile_device", "rtmi_render_samples", "rtmi_render_samples_device", "rtmi_render_features", "rtmi_render_features_device", "rtmi_denoise_defaults", "rtmi_denoise", "rtmi_denoise_device", "rtmi_render_denoised", "rtmi_denoise_var_defaults", "rtmi_variance", "rtmi_variance_device", "rtmi_denoise_var", "rtmi_denoise_var_device", "rtmi_render_adaptive_denoised", "rtmi_render_adaptive", "rtmi_render_adaptive_device", "rtmi_render_views", "rtmi_render_views_device", "rtmi_trace", "rtmi_occluded", "rtmi_occluded_device", "rtmi_trace_device", "rtmi_render_rays", "rtmi_render_rays_device", "rtmi_bake_defaults", "rtmi_bake", "rtmi_bake_device", "rtmi_camera_defaults", "rtmi_render_camera", "rtmi_render_camera_device", "rtmi_ao_defaults", "rtmi_render_ao", "rtmi_render_ao_device", "rtmi_light_defaults", "rtmi_render_light", "rtmi_render_light_device", "rtmi_render_shadowed", "rtmi_render_shadowed_device", "rtmi_envlight_defaults", "rtmi_scene_get_env_sampler", "rtmi_render_envlight", "rtmi_render_envlight_device", "rtmi_lit_defaults", "rtmi_render_lit", "rtmi_render_lit_device", "rtmi_render_rays_lit", "rtmi_render_rays_lit_device", "rtmi_bake_lit", "rtmi_bake_lit_device", "rtmi_preview_defaults", "rtmi_render_preview", "rtmi_render_preview_device", "rtmi_trace_records", "rtmi_primary_records", "rtmi_quantize", "rtmi_quantize_device", "rtmi_make_triangles", "rtmi_builder_create", "rtmi_builder_filter", "rtmi_builder_destroy", "rtmi_last_error"]
+                "rtmi_render_device", "rtmi_render_tile_device", "rtmi_render_samples", "rtmi_render_samples_device", "rtmi_render_features", "rtmi_render_features_device", "rtmi_denoise_defaults", "rtmi_denoise", "rtmi_denoise_device", "rtmi_render_denoised", "rtmi_denoise_var_defaults", "rtmi_variance", "rtmi_variance_device", "rtmi_denoise_var", "rtmi_denoise_var_device", "rtmi_render_adaptive_denoised", "rtmi_render_adaptive", "rtmi_render_adaptive_device", "rtmi_render_views", "rtmi_render_views_device", "rtmi_trace", "rtmi_occluded", "rtmi_occluded_device", "rtmi_trace_device", "rtmi_render_rays", "rtmi_render_rays_device", "rtmi_bake_defaults", "rtmi_bake", "rtmi_bake_device", "rtmi_camera_defaults", "rtmi_render_camera", "rtmi_render_camera_device", "rtmi_ao_defaults", "rtmi_render_ao", "rtmi_render_ao_device", "rtmi_light_defaults", "rtmi_render_light", "rtmi_render_light_device", "rtmi_render_shadowed", "rtmi_render_shadowed_device", "rtmi_envlight_defaults", "rtmi_scene_get_env_sampler", "rtmi_render_envlight", "rtmi_render_envlight_device", "rtmi_scene_set_emitters", "rtmi_scene_get_emitter_sampler", "rtmi_render_emissive", "rtmi_render_emissive_device", "rtmi_lit_defaults", "rtmi_render_lit", "rtmi_render_lit_device", "rtmi_render_rays_lit", "rtmi_render_rays_lit_device", "rtmi_bake_lit", "rtmi_bake_lit_device", "rtmi_preview_defaults", "rtmi_render_preview", "rtmi_render_preview_device", "rtmi_trace_records", "rtmi_primary_records", "rtmi_quantize", "rtmi_quantize_device", "rtmi_make_triangles", "rtmi_builder_create", "rtmi_builder_filter", "rtmi_builder_destroy", "rtmi_last_error"]
 RTH_SYMBOLS = ["rth_last_error", "rth_make_color", "rth_unit", "rth_to_radians", "rth_create_transform",
                "rth_create_viewport", "rth_scene_new", "rth_scene_free", "rth_num_tris", "rth_add_triangle", "rth_add_triangles_gpu", "rth_add_obj", "rth_add_obj_mode",
                "rth_add_disk", "rth_add_sphere", "rth_add_analytic_sphere", "rth_scene_set_environment", "rth_scene_set_sky", "rth_scene_environment_size", "rth_caster_environment", "rth_scene_set_normals", "rth_scene_smooth_normals", "rth_scene_normals_size", "rth_scene_get_normals", "rth_caster_normals", "rth_add_obj_normals", "rth_scene_set_textures", "rth_scene_set_uvs", "rth_scene_project_uvs", "rth_scene_textures_size", "rth_scene_get_uvs", "rth_scene_get_texture", "rth_caster_uvs", "rth_caster_texture", "rth_add_obj_uvs", "rth_scene_set_normal_maps", "rth_scene_normal_maps_size", "rth_scene_get_normal_maps", "rth_scene_normal_map_frames", "rth_caster_normal_maps", "rth_normal_map_from_height", "rth_populate_triangle_numbers", "rth_build_bounding_box", "rth_build_bounding_box_gpu",
                "rth_build_trivial_bounding_box", "rth_box_contains_polygon", "rth_face_contains_triangle",
                "rth_get_triangles", "rth_tree_sizes", "rth_tree_get", "rth_caster_config", "rth_caster_walk_rows",
-               "rth_caster_walk_rows_device", "rth_caster_walk_tile_device", "rth_caster_walk_samples", "rth_caster_walk_samples_device", "rth_caster_walk_features", "rth_caster_walk_features_device", "rth_caster_denoise", "rth_caster_denoise_device", "rth_caster_walk_denoised", "rth_caster_variance", "rth_caster_variance_device", "rth_caster_denoise_var", "rth_caster_denoise_var_device", "rth_caster_walk_adaptive_denoised", "rth_caster_walk_adaptive", "rth_caster_walk_adaptive_device", "rth_caster_walk_views", "rth_caster_walk_views_device", "rth_caster_trace", "rth_caster_occluded", "rth_caster_occluded_device", "rth_caster_trace_device", "rth_caster_walk_rays_explicit", "rth_caster_walk_rays_explicit_device", "rth_caster_bake", "rth_caster_bake_device", "rth_caster_walk_camera", "rth_caster_walk_camera_device", "rth_caster_walk_ao", "rth_caster_walk_ao_device", "rth_caster_walk_light", "rth_caster_walk_light_device", "rth_caster_walk_shadowed", "rth_caster_walk_shadowed_device", "rth_caster_walk_envlight", "rth_caster_walk_envlight_device", "rth_caster_env_sampler", "rth_caster_walk_lit", "rth_caster_walk_lit_device", "rth_caster_walk_rays_explicit_lit", "rth_caster_walk_rays_explicit_lit_device", "rth_caster_bake_lit", "rth_caster_bake_lit_device", "rth_caster_walk_preview", "rth_caster_walk_preview_device", "rth_caster_trace_records", "rth_caster_primary_records", "rth_scene_set_debug", "rth_scene_debug_records", "rth_caster_upload", "rth_caster_set_tuning", "rth_caster_set_devices", "rth_caster_walk_frame_multi", "rth_caster_quantize_device", "rth_quantize"]
+               "rth_caster_walk_rows_device", "rth_caster_walk_tile_device", "rth_caster_walk_samples", "rth_caster_walk_samples_device", "rth_caster_walk_features", "rth_caster_walk_features_device", "rth_caster_denoise", "rth_caster_denoise_device", "rth_caster_walk_denoised", "rth_caster_variance", "rth_caster_variance_device", "rth_caster_denoise_var", "rth_caster_denoise_var_device", "rth_caster_walk_adaptive_denoised", "rth_caster_walk_adaptive", "rth_caster_walk_adaptive_device", "rth_caster_walk_views", "rth_caster_walk_views_device", "rth_caster_trace", "rth_caster_occluded", "rth_caster_occluded_device", "rth_caster_trace_device", "rth_caster_walk_rays_explicit", "rth_caster_walk_rays_explicit_device", "rth_caster_bake", "rth_caster_bake_device", "rth_caster_walk_camera", "rth_caster_walk_camera_device", "rth_caster_walk_ao", "rth_caster_walk_ao_device", "rth_caster_walk_light", "rth_caster_walk_light_device", "rth_caster_walk_shadowed", "rth_caster_walk_shadowed_device", "rth_caster_walk_envlight", "rth_caster_walk_envlight_device", "rth_caster_env_sampler", "rth_scene_set_emitters", "rth_scene_get_emitters", "rth_caster_walk_emissive", "rth_caster_walk_emissive_device", "rth_caster_emitter_sampler", "rth_caster_walk_lit", "rth_caster_walk_lit_device", "rth_caster_walk_rays_explicit_lit", "rth_caster_walk_rays_explicit_lit_device", "rth_caster_bake_lit", "rth_caster_bake_lit_device", "rth_caster_walk_preview", "rth_caster_walk_preview_device", "rth_caster_trace_records", "rth_caster_primary_records", "rth_scene_set_debug", "rth_scene_debug_records", "rth_caster_upload", "rth_caster_set_tuning", "rth_caster_set_devices", "rth_caster_walk_frame_multi", "rth_caster_quantize_device", "rth_quantize"]

@@ -410,6 +410,7 @@ __global__ void __launch_bounds__(256) k_trace(DScene sc, const float4* __restri
 #include "shadowed.hpp"
 #include "envlight.hpp"
 #include "lit.hpp"
+#include "emissive.hpp"
 namespace rtmi {
 
 
@@ -1174,6 +1175,16 @@ struct rtmi_scene {
     DevBuf<unsigned long long> envrows, envrowsum;
     EnvSampler envsamp{};
     bool envsamp_ok = false;
+    // rtmi_scene_set_emitters: the lamps' triangles in triangle order and their corners (host copies, 9 floats per lamp).
+    // rtmi_render_emissive* / rtmi_scene_get_emitter_sampler: the lamps' tables (EmTab, emissive.hpp), built on the first call that
+    // needs them (ensure_emitters) and dropped by whatever sets or clears the marks.  No other call reads any of it.
+    std::vector<uint32_t> em_tris;
+    std::vector<float> em_corners;
+    DevBuf<uint32_t> em_idx, em_list, em_q, em_max;
+    DevBuf<float4> em_lamp, em_c;
+    DevBuf<unsigned long long> em_cum;
+    EmTab emtab{};
+    bool emtab_ok = false;
     // rtmi_scene_set_normals: six float4 per triangle (SmoothTab, shade.hpp).  A scene with them renders on the per-pass pipeline
     // with the k_shade*_smooth kernels, which also know glass and the environment, and k_features_smooth.
     DevBuf<float4> smooth;
@@ -2004,7 +2015,7 @@ int rtmi_scene_destroy(rtmi_scene_t* s) {
     if (!s) return RTMI_OK;
     (void)hipSetDevice(s->device);
     s->nodes.release(); s->refs.release(); s->tplane.release(); s->tedge.release(); s->mats.release();
-    s->fnodes.release(); s->oblocks.release(); s->ocull.release(); s->cert.release(); s->wlinks.release(); s->bnodes.release(); s->bleaves.release(); s->spheres.release(); s->env.release(); s->envq.release(); s->envex.release(); s->envq_max.release(); s->envrows.release(); s->envrowsum.release(); s->smooth.release(); s->textri.release(); s->texels.release(); s->texhdr.release(); s->nmaptri.release();
+    s->fnodes.release(); s->oblocks.release(); s->ocull.release(); s->cert.release(); s->wlinks.release(); s->bnodes.release(); s->bleaves.release(); s->spheres.release(); s->env.release(); s->envq.release(); s->envex.release(); s->envq_max.release(); s->envrows.release(); s->envrowsum.release(); s->em_idx.release(); s->em_list.release(); s->em_q.release(); s->em_max.release(); s->em_lamp.release(); s->em_c.release(); s->em_cum.release(); s->smooth.release(); s->textri.release(); s->texels.release(); s->texhdr.release(); s->nmaptri.release();
     for (int k = 0; k < RTMI_MAX_STREAMS; k++) {
         s->w[k].release();
         if (s->istream[k]) (void)hipStreamDestroy(s->istream[k]);
@@ -2887,7 +2898,9 @@ struct PreviewCall {
 // p is then an unbounded light that is never read beyond its flags (no tmax)
 // lit != nullptr: a lit path-trace (rtmi_render_lit*), the same pass structure with k_lit_rays and k_shade_lit and up to
 // lit->nlights shadow rays per path and pass; p is then never read
-struct ShadowCall { rtmi_light_t p; const rtmi_envlight_t* el = nullptr; const LitArgs* lit = nullptr; };
+// em != nullptr: an emissive path-trace (rtmi_render_emissive*), the same pass structure with k_emissive_rays and k_shade_emissive,
+// whose walk is the scene's closest-hit launch into the shadow queue's own hit records; p is then never read
+struct ShadowCall { rtmi_light_t p; const rtmi_envlight_t* el = nullptr; const LitArgs* lit = nullptr; const EmTab* em = nullptr; };
 // A camera call (rtmi_render_camera*): the model k_gen_camera generates the rays of, and the guides of those rays (each may be null)
 struct CameraCall { DCam cam; FeatOut fo; };
 // One render_tile call: what it renders, and its plan (plan_tile)
@@ -3119,6 +3132,17 @@ static int plan_tile(rtmi_scene* s, const rtmi_viewport_t* vp, const rtmi_tile_t
                 HIPCHK(hipEventCreate(&e));
                 b.walk.pass_ev.push_back(e);
             }
+        } else if (c.sh && c.sh->em) {  // one candidate per path: the shadow queue, its hit records, weights, slots and the direct stack
+            rtmi_scene::ShadowBuf& b = s->shadow[t];
+            HIPCHK(b.qo.ensure(paths)); HIPCHK(b.qd.ensure(paths)); HIPCHK(b.slot.ensure(paths)); HIPCHK(b.lw.ensure(paths));
+            HIPCHK(b.dstack.ensure(paths * c.maxdepth)); HIPCHK(b.wb.ensure(paths));
+            HIPCHK(b.walk.ctrl.ensure(1)); HIPCHK(b.walk.hit_tf.ensure(paths)); HIPCHK(b.walk.hit_t.ensure(paths));
+            if (!s->root_is_leaf) HIPCHK(b.walk.fb.ensure(b.walk.hit_tf.n));  // the hybrid pass's fallback list, as long as the hit records
+            while (b.walk.pass_ev.size() < 2 * (size_t)c.maxdepth) {
+                hipEvent_t e;
+                HIPCHK(hipEventCreate(&e));
+                b.walk.pass_ev.push_back(e);
+            }
         } else if (c.sh) {  // a pass tests at most one ray per path
             rtmi_scene::ShadowBuf& b = s->shadow[t];
             HIPCHK(b.qo.ensure(paths)); HIPCHK(b.qd.ensure(paths)); HIPCHK(b.slot.ensure(paths)); HIPCHK(b.mask.ensure(paths)); HIPCHK(b.occ.ensure(paths));
@@ -3301,6 +3325,24 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
                 hipLaunchKernelGGL(s->has_env ? k_shade_lit<true> : k_shade_lit<false>, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths,
                                    (int)pass, s->envtab, la.nlights, w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, sb.slot.p, sb.occ.p,
                                    sb.lw.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, sb.dstack.p, w.scol.p, w.ctrl.p);
+                HIPCHK(hipGetLastError());
+                continue;
+            }
+            if (c.sh->em) {
+                if (c.maxdepth - pass - 1u != 0u) {
+                    hipLaunchKernelGGL(k_emissive_rays, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, (int)pass, *c.sh->em, w.qo[a].p, w.qd[a].p,
+                                       w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.ctrl.p, sb.qo.p, sb.qd.p, sb.lw.p, sb.slot.p, sb.walk.ctrl.p);
+                    HIPCHK(hipEventRecord(sb.walk.pass_ev[2 * pass], st));
+                    launch_trace(s, sb.walk, st, sb.qo.p, sb.qd.p, (int)pass + 1, c.counting, sb.walk.pass_ev[2 * pass + 1]);
+                    HIPCHK(hipGetLastError());
+                } else {  // the exhausted level gets no sample: no candidates, no walk (an empty event pair for collect_batch)
+                    HIPCHK(hipEventRecord(sb.walk.pass_ev[2 * pass], st));
+                    HIPCHK(hipEventRecord(sb.walk.pass_ev[2 * pass + 1], st));
+                }
+                hipLaunchKernelGGL(s->has_env ? k_shade_emissive<true> : k_shade_emissive<false>, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0,
+                                   npaths, (int)pass, s->envtab, *c.sh->em, w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, sb.slot.p,
+                                   sb.qd.p, sb.lw.p, sb.walk.hit_tf.p, sb.walk.hit_t.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p,
+                                   sb.dstack.p, sb.wb.p, w.scol.p, w.ctrl.p);
                 HIPCHK(hipGetLastError());
                 continue;
             }
@@ -4084,6 +4126,147 @@ int rtmi_render_envlight(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t se
     if (out_host) HIPCHK(s->tile.ensure(npix));
     if (sample0 > 0) HIPCHK(hipMemcpy(s->acc.p, accum_host, npix * sizeof(float4), hipMemcpyHostToDevice));
     rc = rtmi_render_envlight_device(s, vp, seed, &tile, sample0, nsamples, el, s->acc.p, out_host ? (void*)s->tile.p : nullptr, nullptr, stats);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(hipMemcpy(accum_host, s->acc.p, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    if (out_host) HIPCHK(hipMemcpy(out_host, s->tile.p, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+// ---------------------------------------------------------------- emissive triangles sampled at matte hits (rtmi_render_emissive*)
+int rtmi_scene_set_emitters(rtmi_scene_t* s, const float* corners9, const uint8_t* emit_of_tri, uint64_t n) {
+    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
+    const bool set = emit_of_tri && n;
+    if (set) {
+        if (!corners9) return fail(RTMI_ERR_INVALID, "emitters: corners is NULL");
+        if (n != s->d.ntris) return fail(RTMI_ERR_INVALID, "emitters: n must equal ntris");
+        for (uint64_t g = 1; g < n; g++) {  // (entry 0 is the sentinel's and is ignored)
+            if (!emit_of_tri[g]) continue;
+            for (int k = 0; k < 9; k++)
+                if (!std::isfinite(corners9[9 * g + k])) return fail(RTMI_ERR_INVALID, "emitters: a corner of triangle " + std::to_string(g) + " is not finite");
+            if (s->htris[g].surface_kind != RTMI_SOLID)
+                return fail(RTMI_ERR_INVALID, "emitters: triangle " + std::to_string(g) + " is marked and its surface is not Solid");
+        }
+    }
+    RTMI_GUARD_BEGIN
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipDeviceSynchronize());  // no render of this scene is in flight: its streams are done with the old tables
+    s->emtab_ok = false;
+    s->emtab = EmTab{};
+    s->em_tris.clear();
+    s->em_corners.clear();
+    if (!set) return RTMI_OK;
+    for (uint64_t g = 1; g < n; g++)
+        if (emit_of_tri[g]) {
+            s->em_tris.push_back((uint32_t)g);
+            s->em_corners.insert(s->em_corners.end(), corners9 + 9 * g, corners9 + 9 * g + 9);
+        }
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+// The lamps' tables (emissive.hpp), built once per set of marks: the records and wmax (a thread per lamp), then q and the prefix
+// sums (one block).  The triangle -> lamp index is integers only and comes from the host's list.
+static int ensure_emitters(rtmi_scene_t* s) {
+    if (s->emtab_ok) return RTMI_OK;
+    RTMI_GUARD_BEGIN
+    const uint32_t n = (uint32_t)s->em_tris.size(), ntris = s->d.ntris;
+    std::vector<uint32_t> idx(ntris, 0u);
+    std::vector<float4> cs((size_t)n * 3);
+    for (uint32_t k = 0; k < n; k++) {
+        idx[s->em_tris[k]] = k + 1u;
+        const float* c = &s->em_corners[(size_t)9 * k];
+        for (int j = 0; j < 3; j++) cs[(size_t)3 * k + j] = make_float4(c[3 * j], c[3 * j + 1], c[3 * j + 2], 0.f);
+    }
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(s->em_idx.ensure(ntris)); HIPCHK(s->em_list.ensure(n)); HIPCHK(s->em_c.ensure((size_t)n * 3));
+    HIPCHK(s->em_lamp.ensure((size_t)n * RTMI_EMISSIVE_REC)); HIPCHK(s->em_q.ensure(n)); HIPCHK(s->em_cum.ensure((size_t)n + 1));
+    HIPCHK(s->em_max.ensure(1));
+    HIPCHK(hipMemcpy(s->em_idx.p, idx.data(), (size_t)ntris * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->em_list.p, s->em_tris.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->em_c.p, cs.data(), cs.size() * sizeof(float4), hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(s->em_max.p, 0, sizeof(uint32_t), 0));
+    hipLaunchKernelGGL(k_emq_lamps, dim3((n + 255u) / 256u), dim3(256), 0, 0, s->d, s->em_list.p, s->em_c.p, n, s->em_lamp.p, s->em_max.p);
+    hipLaunchKernelGGL(k_emq_scan, dim3(1), dim3(256), 0, 0, s->em_lamp.p, n, s->em_max.p, s->em_q.p, s->em_cum.p, s->em_cum.p + n);
+    HIPCHK(hipGetLastError());
+    unsigned long long total = 0ull;
+    HIPCHK(hipMemcpy(&total, s->em_cum.p + n, sizeof total, hipMemcpyDeviceToHost));  // (synchronises with the two kernels)
+    s->emtab = EmTab{s->em_idx.p, s->em_lamp.p, s->em_q.p, s->em_cum.p, total, n};
+    s->emtab_ok = true;
+    return RTMI_OK;
+    RTMI_GUARD_END
+}
+
+int rtmi_scene_get_emitter_sampler(rtmi_scene_t* s, uint32_t* q_out, uint64_t* cum_out, uint32_t* lamp_of_tri_out, float* lamps_out,
+                                   uint64_t* total_out, uint32_t* n_out) {
+    if (!s || !n_out) return fail(RTMI_ERR_INVALID, "NULL argument");
+    const uint32_t n = (uint32_t)s->em_tris.size();
+    *n_out = n;
+    if (total_out) *total_out = 0u;
+    if (n == 0u) return RTMI_OK;
+    const int rc = ensure_emitters(s);
+    if (rc != RTMI_OK) return rc;
+    if (total_out) *total_out = s->emtab.total;
+    if (q_out) HIPCHK(hipMemcpy(q_out, s->em_q.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (cum_out) HIPCHK(hipMemcpy(cum_out, s->em_cum.p, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (lamp_of_tri_out) HIPCHK(hipMemcpy(lamp_of_tri_out, s->em_idx.p, (size_t)s->d.ntris * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (lamps_out) HIPCHK(hipMemcpy(lamps_out, s->em_lamp.p, (size_t)n * RTMI_EMISSIVE_REC * sizeof(float4), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+// scenes the call does not take; before any HIP call
+static int refuse_scene_emissive(const rtmi_scene_t* s) {
+    if (s->em_tris.empty()) return fail(RTMI_ERR_UNSUPPORTED, "emissive: the scene has no emitters (rtmi_scene_set_emitters)");
+    if (s->d.nspheres)
+        return fail(RTMI_ERR_UNSUPPORTED, "emissive: the scene has analytic spheres (a build-defined primitive whose normal needs the hit point)");
+    if (s->has_dielectric) return fail(RTMI_ERR_UNSUPPORTED, "emissive: the scene has a dielectric surface (the emissive shading has no glass arm)");
+    if (s->has_normals) return fail(RTMI_ERR_UNSUPPORTED, "emissive: the scene has vertex normals (the emissive shading has no smooth arm)");
+    if (s->has_nmap) return fail(RTMI_ERR_UNSUPPORTED, "emissive: the scene has normal maps (the emissive shading has no normal-map arm)");
+    if (s->has_tex) return fail(RTMI_ERR_UNSUPPORTED, "emissive: the scene has textures (the emissive shading has no texture arm)");
+    if (s->options & RTMI_OPT_BVH)
+        return fail(RTMI_ERR_UNSUPPORTED, "emissive: RTMI_OPT_BVH (a non-exact first hit would break the test that a shadow ray's first hit is its lamp)");
+    return RTMI_OK;
+}
+
+int rtmi_render_emissive_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, const rtmi_tile_t* tile, uint32_t sample0,
+                                uint32_t nsamples, void* accum_device, void* out_device, void* hip_stream, rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    int rc = check_samples(s, vp, sample0, nsamples, accum_device, out_device);
+    if (rc != RTMI_OK) return rc;
+    if (!tile) return fail(RTMI_ERR_INVALID, "NULL argument (tile)");
+    if (tile->nrows == 0) return RTMI_OK;
+    rc = check_view(vp, tile);
+    if (rc != RTMI_OK) return rc;
+    rc = refuse_scene_emissive(s);
+    if (rc != RTMI_OK) return rc;
+    if (vp->maxdepth != 0) {  // (depth 0 writes zeros and needs no table)
+        rc = ensure_emitters(s);
+        if (rc != RTMI_OK) return rc;
+    }
+    ShadowCall call{};
+    call.em = &s->emtab;
+    return render_tile(s, vp, seed, tile, sample0, nsamples, (float4*)accum_device, out_device, hip_stream, stats, nullptr, 0, nullptr,
+                       nullptr, nullptr, nullptr, &call);
+}
+
+// Host variant: rtmi_render_samples' copies (accum in only when sample0 > 0, accum and out back).
+int rtmi_render_emissive(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows, uint32_t sample0,
+                         uint32_t nsamples, float* accum_host, float* out_host, rtmi_stats_t* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    int rc = check_samples(s, vp, sample0, nsamples, accum_host, out_host);
+    if (rc != RTMI_OK) return rc;
+    const uint64_t npix = (uint64_t)nrows * vp->width;
+    if (npix == 0) return RTMI_OK;
+    if ((uint64_t)row0 + nrows > vp->height) return fail(RTMI_ERR_INVALID, "row range outside the viewport");
+    const rtmi_tile_t tile{row0, nrows, nrows, 0u};
+    rc = check_view(vp, &tile);
+    if (rc != RTMI_OK) return rc;
+    rc = refuse_scene_emissive(s);
+    if (rc != RTMI_OK) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(s->acc.ensure(npix));
+    if (out_host) HIPCHK(s->tile.ensure(npix));
+    if (sample0 > 0) HIPCHK(hipMemcpy(s->acc.p, accum_host, npix * sizeof(float4), hipMemcpyHostToDevice));
+    rc = rtmi_render_emissive_device(s, vp, seed, &tile, sample0, nsamples, s->acc.p, out_host ? (void*)s->tile.p : nullptr, nullptr, stats);
     if (rc != RTMI_OK) return rc;
     HIPCHK(hipMemcpy(accum_host, s->acc.p, npix * sizeof(float4), hipMemcpyDeviceToHost));
     if (out_host) HIPCHK(hipMemcpy(out_host, s->tile.p, npix * sizeof(float4), hipMemcpyDeviceToHost));

@@ -788,6 +788,71 @@ int rth_caster_walk_lit_device(rth_scene_t* s, uint32_t w, uint32_t h, const flo
         if (stats) *stats = ctx.stats;
     });
 }
+// --- emitters (rtmi_scene_set_emitters in rtmi.h, which defines them)
+int rth_scene_set_emitters(rth_scene_t* s, const uint8_t* emit_of_tri, uint64_t first, uint64_t count) {
+    return guarded([&] {
+        Scene& sc = s->scene;
+        if (!emit_of_tri || count == 0) { sc.emitters.clear(); sc.emit_generation++; return; }
+        normals_range(s, first, count, "emitters");
+        for (uint64_t i = 0; i < count; i++)
+            if (emit_of_tri[i] && sc.tris[first + i].surface.tag != RTMI_SOLID)
+                throw std::runtime_error("emitters: triangle " + std::to_string(first + i) + " is marked and its surface is not Solid");
+        if (sc.emitters.size() < first + count) sc.emitters.resize(first + count, 0);
+        for (uint64_t i = 0; i < count; i++) sc.emitters[first + i] = emit_of_tri[i] ? 1 : 0;
+        sc.emit_generation++;
+    });
+}
+int rth_scene_get_emitters(const rth_scene_t* s, uint8_t* emit_of_tri_out, uint64_t cap_tris) {
+    return guarded([&] {
+        const Scene& sc = s->scene;
+        const size_t n = sc.tris.size();
+        if (n > cap_tris) throw std::runtime_error("rth_scene_get_emitters: the buffer is too small");
+        std::fill(emit_of_tri_out, emit_of_tri_out + n, (uint8_t)0);
+        std::copy(sc.emitters.begin(), sc.emitters.begin() + std::min(n, sc.emitters.size()), emit_of_tri_out);
+    });
+}
+int rth_caster_walk_emissive(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp, uint64_t row0,
+                             uint64_t nrows, uint32_t sample0, uint32_t nsamples, float* accum_host, float* out_host, rtmi_stats_t* stats,
+                             double* wall) {
+    return guarded([&] {
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_rays_emissive(v, s->scene, (size_t)row0, (size_t)nrows, sample0, nsamples, reinterpret_cast<Color*>(accum_host),
+                                        reinterpret_cast<Color*>(out_host), ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
+int rth_caster_walk_emissive_device(rth_scene_t* s, uint32_t w, uint32_t h, const float* vp12, uint64_t maxdepth, uint64_t spp,
+                                    const rtmi_tile_t* tile, uint32_t sample0, uint32_t nsamples, void* accum_device, void* out_device,
+                                    void* hip_stream, rtmi_stats_t* stats, double* wall) {
+    return guarded([&] {
+        if (!tile) throw std::runtime_error("NULL tile");
+        const Viewport v = vp_from(w, h, vp12, maxdepth, spp);
+        ProgressCtx ctx;
+        const auto t0 = std::chrono::steady_clock::now();
+        caster_of(s).walk_emissive_device(v, s->scene, *tile, sample0, nsamples, accum_device, out_device, hip_stream, ctx);
+        if (wall) *wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = ctx.stats;
+    });
+}
+// The lamps' tables of the resident copy; sizes first (every pointer but nlamps_out NULL), then the copy
+int rth_caster_emitter_sampler(rth_scene_t* s, uint32_t* q_out, uint64_t* cum_out, uint32_t* lamp_of_tri_out, float* lamps_out,
+                               uint64_t cap_lamps, uint64_t cap_tris, uint64_t* total_out, uint32_t* nlamps_out) {
+    return guarded([&] {
+        if (!nlamps_out) throw std::runtime_error("rth_caster_emitter_sampler: NULL nlamps_out");
+        const HipRayCaster::EmitterSampler e = caster_of(s).emitter_sampler(s->scene);
+        *nlamps_out = (uint32_t)e.q.size();
+        if (total_out) *total_out = e.total;
+        if (!q_out && !cum_out && !lamp_of_tri_out && !lamps_out) return;
+        if (e.q.size() > cap_lamps || e.lamp_of_tri.size() > cap_tris) throw std::runtime_error("rth_caster_emitter_sampler: the buffer is too small");
+        if (q_out && !e.q.empty()) memcpy(q_out, e.q.data(), e.q.size() * sizeof(uint32_t));
+        if (cum_out && !e.cum.empty()) memcpy(cum_out, e.cum.data(), e.cum.size() * sizeof(uint64_t));
+        if (lamp_of_tri_out && !e.lamp_of_tri.empty()) memcpy(lamp_of_tri_out, e.lamp_of_tri.data(), e.lamp_of_tri.size() * sizeof(uint32_t));
+        if (lamps_out && !e.lamps.empty()) memcpy(lamps_out, e.lamps.data(), e.lamps.size() * sizeof(float));
+    });
+}
 int rth_caster_env_sampler(rth_scene_t* s, uint32_t* q_out, uint64_t cap, uint64_t* total_out, uint32_t* n_out) {
     return guarded([&] {
         if (!n_out) throw std::runtime_error("rth_caster_env_sampler: NULL n_out");

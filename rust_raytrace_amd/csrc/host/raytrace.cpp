@@ -558,6 +558,77 @@ void HipRayCaster::invalidate() {
     tex_applied_ = false;
     nmap_applied_ = false;
     nmap_on_device_ = false;
+    emit_applied_ = false;
+    emit_on_device_ = false;
+}
+
+void HipRayCaster::apply_emitters(const Scene& s) {
+    if (emit_applied_ && key_emit_generation_ == s.emit_generation) return;
+    std::vector<rtmi_scene_t*> all{handle_};
+    all.insert(all.end(), extra_.begin(), extra_.end());
+    bool none = true;
+    for (uint8_t m : s.emitters) none = none && m == 0;
+    std::vector<float> corners;
+    std::vector<uint8_t> marks;
+    if (!none) {
+        const size_t n = s.tris.size();
+        corners.assign(n * 9, 0.f);
+        marks.assign(n, 0);  // triangles beyond the ones that were given a mark are no lamps
+        for (size_t i = 1; i < n; i++)
+            for (int k = 0; k < 3; k++)
+                for (int c = 0; c < 3; c++) corners[9 * i + 3 * k + c] = s.tris[i].corners[k].v[c];
+        std::copy(s.emitters.begin(), s.emitters.begin() + std::min(s.emitters.size(), marks.size()), marks.begin());
+    }
+    for (rtmi_scene_t* hh : all) {
+        if (none && !emit_on_device_) continue;  // fresh handles have none
+        const int rc = none ? rtmi_scene_set_emitters(hh, nullptr, nullptr, 0) : rtmi_scene_set_emitters(hh, corners.data(), marks.data(), s.tris.size());
+        if (rc != RTMI_OK) {
+            const std::string msg = std::string("rtmi_scene_set_emitters: ") + rtmi_last_error();
+            invalidate();
+            throw std::runtime_error(msg);
+        }
+    }
+    emit_on_device_ = !none;
+    emit_applied_ = true;
+    key_emit_generation_ = s.emit_generation;
+}
+
+HipRayCaster::EmitterSampler HipRayCaster::emitter_sampler(const Scene& s) {
+    EmitterSampler e;
+    rtmi_scene_t* h = resident(s);
+    uint32_t n = 0;
+    if (rtmi_scene_get_emitter_sampler(h, nullptr, nullptr, nullptr, nullptr, nullptr, &n) != RTMI_OK)
+        throw std::runtime_error(std::string("rtmi_scene_get_emitter_sampler: ") + rtmi_last_error());
+    if (n == 0) return e;
+    e.q.resize(n); e.cum.resize(n); e.lamp_of_tri.resize(s.tris.size()); e.lamps.resize((size_t)n * 20);
+    if (rtmi_scene_get_emitter_sampler(h, e.q.data(), e.cum.data(), e.lamp_of_tri.data(), e.lamps.data(), &e.total, &n) != RTMI_OK)
+        throw std::runtime_error(std::string("rtmi_scene_get_emitter_sampler: ") + rtmi_last_error());
+    return e;
+}
+
+void HipRayCaster::walk_rays_emissive(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples,
+                                      Color* accum, Color* out, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_emissive(h, &av, seed, (uint32_t)row0, (uint32_t)nrows, sample0, nsamples, reinterpret_cast<float*>(accum),
+                                        reinterpret_cast<float*>(out), &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_emissive: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
+}
+
+void HipRayCaster::walk_emissive_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
+                                        void* accum_device, void* out_device, void* hip_stream, ProgressCtx& progress) {
+    rtmi_scene_t* h = resident(s);
+    const rtmi_viewport_t av = to_abi(v);
+    rtmi_stats_t st;
+    const int rc = rtmi_render_emissive_device(h, &av, seed, &tile, sample0, nsamples, accum_device, out_device, hip_stream, &st);
+    if (rc != RTMI_OK) throw std::runtime_error(std::string("rtmi_render_emissive_device: ") + rtmi_last_error());
+    progress.total_rays += st.rays;
+    progress.kernel_seconds += st.kernel_ms * 1e-3;
+    progress.stats = st;
 }
 
 void HipRayCaster::apply_textures(const Scene& s) {
@@ -778,6 +849,7 @@ rtmi_scene_t* HipRayCaster::resident(const Scene& s) {
         apply_normals(s);
         apply_textures(s);
         apply_normal_maps(s);
+        apply_emitters(s);
         apply_settings();
         return handle_;
     }
@@ -837,6 +909,7 @@ rtmi_scene_t* HipRayCaster::resident(const Scene& s) {
     apply_normals(s);
     apply_textures(s);
     apply_normal_maps(s);
+    apply_emitters(s);
     apply_settings();
     return handle_;
 }

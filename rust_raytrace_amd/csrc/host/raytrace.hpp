@@ -178,6 +178,11 @@ struct Scene {
     std::vector<uint32_t> nmap_of_tri;
     float nmap_strength = 1.f;
     uint64_t nmap_generation = 0;
+    // Emitters (include/rtmi.h, "EMISSIVE TRIANGLES"), or none (empty): one byte per triangle, non-zero = a lamp;
+    // may be shorter than tris: triangles appended later are no lamps.  Applied like the normals: code that edits them bumps
+    // emit_generation.
+    std::vector<uint8_t> emitters;
+    uint64_t emit_generation = 0;
     // debug_en: walk_rays also records sample 0's primary ray of every pixel into `debug` (the reference's debug_ctx, which
     // walk_rays fills through a &Scene: hence mutable).  Octree scenes only; walk_rays throws before rendering otherwise.
     bool debug_en = false;
@@ -332,6 +337,16 @@ public:
                        const rtmi_lit_t& lit, Color* accum, Color* out, ProgressCtx& progress);
     void walk_lit_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
                          const rtmi_lit_t& lit, void* accum_device, void* out_device, void* hip_stream, ProgressCtx& progress);
+    // Path tracing with the scene's emissive triangles sampled at matte hits (rtmi_render_emissive / rtmi_render_emissive_device,
+    // which rtmi.h defines): walk_samples / walk_samples_device in every respect.
+    void walk_rays_emissive(const Viewport& v, const Scene& s, size_t row0, size_t nrows, uint32_t sample0, uint32_t nsamples, Color* accum,
+                            Color* out, ProgressCtx& progress);
+    void walk_emissive_device(const Viewport& v, const Scene& s, const rtmi_tile_t& tile, uint32_t sample0, uint32_t nsamples,
+                              void* accum_device, void* out_device, void* hip_stream, ProgressCtx& progress);
+    // The lamps' tables of the scene's resident copy on the first device (rtmi_scene_get_emitter_sampler): L weights, L prefix sums,
+    // ntris lamp numbers, L * 20 floats of records and the total; all empty when the scene has no lamps.
+    struct EmitterSampler { std::vector<uint32_t> q, lamp_of_tri; std::vector<uint64_t> cum; std::vector<float> lamps; uint64_t total = 0; };
+    EmitterSampler emitter_sampler(const Scene& s);
     // The sampler table of the environment of the scene's resident copy on the first device (rtmi_scene_get_env_sampler): n * n
     // weights and their sum, empty and n = 0 when the scene has no environment.
     std::vector<uint32_t> env_sampler(const Scene& s, uint32_t& n, uint64_t& total);
@@ -432,6 +447,10 @@ private:
     bool nmap_applied_ = false;                // the handles carry Scene::nmap_of_tri as of key_nmap_generation_
     bool nmap_on_device_ = false;              // ... and that is a table, not "none"
     void apply_normal_maps(const Scene& s);
+    uint64_t key_emit_generation_ = 0;
+    bool emit_applied_ = false;                // the handles carry Scene::emitters as of key_emit_generation_
+    bool emit_on_device_ = false;              // ... and that is a set of marks, not "none"
+    void apply_emitters(const Scene& s);
     size_t key_ntris_ = 0, key_nboxes_ = 0, key_nrefs_ = 0;
     uint32_t options_ = 0;
     rtmi_tuning_t tuning_{}, defaults_{};

@@ -334,6 +334,40 @@ class Scene:
         """No normal maps: the scene is exactly the scene it was before it had them."""
         _chk(_ffi.lib().rth_scene_set_normal_maps(self.h, None, 0, 0, 1.0, 0))
 
+    # --- emitters: a build-defined extension (include/rtmi.h, "EMISSIVE TRIANGLES")
+    def set_emitters(self, mask_or_indices, first=1):
+        """Mark Solid triangles as lamps for HipRayCaster.walk_rays_emissive*: a boolean (or uint8) mask for triangles first, first + 1,
+        ..., or an integer array of triangle numbers (first is then ignored; every other triangle keeps its mark).  A lamp's radiance
+        is its surface colour, which may exceed 1.  No other call changes: the scene renders everywhere else exactly as before.  Kept
+        with the scene like its vertex normals (triangles appended later are no lamps); HipRayCaster applies the marks on every
+        device it uploads to, where a marked triangle that is not Solid is an error."""
+        a = np.asarray(mask_or_indices)
+        if a.ndim != 1 or a.size == 0:
+            raise ValueError("set_emitters: a non-empty 1-d mask or index array (clear_emitters() removes the marks)")
+        if a.dtype == np.bool_ or a.dtype == np.uint8:
+            m = np.ascontiguousarray(a != 0, dtype=np.uint8)
+            _chk(_ffi.lib().rth_scene_set_emitters(self.h, _p(m), int(first), m.size))
+            return
+        if not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"set_emitters: a boolean mask or integer triangle numbers, not {a.dtype}")
+        n = self.num_tris()
+        if a.min() < 1 or a.max() >= n:
+            raise ValueError("set_emitters: triangle numbers must be 1 to the number of triangles - 1")
+        m = self.emitters()
+        m = np.zeros(n, np.uint8) if m is None else m.astype(np.uint8)
+        m[a] = 1
+        _chk(_ffi.lib().rth_scene_set_emitters(self.h, _p(np.ascontiguousarray(m[1:])), 1, n - 1))
+
+    def emitters(self):
+        """The scene's lamp marks, (ntris,) bool with entry 0 the sentinel's (False), or None when no triangle is marked"""
+        m = np.zeros(self.num_tris(), np.uint8)
+        _chk(_ffi.lib().rth_scene_get_emitters(self.h, _p(m), m.size))
+        return m.astype(bool) if m.any() else None
+
+    def clear_emitters(self):
+        """No lamps: walk_rays_emissive* refuses the scene again; every other call is as it always was."""
+        _chk(_ffi.lib().rth_scene_set_emitters(self.h, None, 0, 0))
+
     # --- Scene.boxes
     def build_bounding_box(self, orig, len2, maxdepth, minobjs, threads=0, gpu_device=None):
         """raytrace.rs:790-845.  gpu_device: evaluate the box/triangle overlap tests of every level on that GPU
@@ -1239,6 +1273,69 @@ class HipRayCaster:
         total = C.c_uint64(0)
         _chk(_ffi.lib().rth_caster_env_sampler(s.h, _p(q), q.size, C.byref(total), C.byref(n)))
         return q, int(total.value)
+
+    def walk_rays_emissive(self, v, s, data=None, sample0=0, nsamples=None, accum=None):
+        """Path tracing of the whole frame with the scene's lamps (Scene.set_emitters) sampled at every Matte hit that bounces
+        (rtmi_render_emissive; include/rtmi.h defines it): walk_rays' paths and, in expectation, walk_rays' image, with less noise
+        where small bright Solid triangles light matte surfaces.  Samples [sample0, sample0 + nsamples) (default: all from sample0)
+        of the frame's v.samples_per_pixel; data and accum as in walk_rays_shadowed.
+        Returns (data, ctx); ctx.accum is the sums."""
+        k0, n = self._feature_samples(v, sample0, nsamples)
+        shape = (v.height, v.width, 4)
+        bufs = []
+        for name, x in (("data", data), ("accum", accum)):
+            if x is None:
+                x = np.zeros(shape, np.float32)
+            elif not isinstance(x, np.ndarray) or x.dtype != np.float32 or not x.flags.c_contiguous or x.size != v.height * v.width * 4:
+                raise ValueError(f"{name} must be a C-contiguous float32 array of height*width*4 elements")
+            bufs.append(x)
+        if np.shares_memory(bufs[0], bufs[1]):
+            raise ValueError("data and accum must not alias")
+        if k0 > 0 and accum is None:
+            raise ValueError("sample0 > 0 continues the sums of the earlier samples: pass their accum")
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_emissive(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, 0, v.height, k0, n,
+                                                 _p(bufs[1]), _p(bufs[0]), C.byref(st), C.byref(wall)))
+        ctx = ProgressCtx(st.rays, wall.value, st.as_dict())
+        ctx.accum = bufs[1]
+        return bufs[0], ctx
+
+    def walk_rays_emissive_device(self, v, s, accum, out=None, tile=None, sample0=0, nsamples=None, stream=None):
+        """The same on torch tensors on the scene's device (rtmi_render_emissive_device) for a striped row set tile = (row0,
+        nrows, stripe_rows, stripe_step) (default: the whole frame); accum, out and stream as in walk_rays_shadowed_device.
+        Returns ctx."""
+        k0, n = self._feature_samples(v, sample0, nsamples)
+        t = _ffi.Tile(*[int(x) for x in (tile if tile is not None else (0, v.height, v.height, 0))])
+        want = int(t.nrows) * int(v.width) * 4
+        for name, x in (("accum", accum), ("out", out)):
+            if (x is not None or name == "accum") and (not hasattr(x, "data_ptr") or not x.is_cuda or str(x.dtype) != "torch.float32"
+                                                       or not x.is_contiguous() or x.numel() != want):
+                raise ValueError(f"{name} must be a contiguous float32 tensor of {want} elements on the device")
+        if out is not None and abs(accum.data_ptr() - out.data_ptr()) < 4 * want:
+            raise ValueError("accum and out must not overlap")
+        self._config(s)
+        st = _ffi.Stats()
+        wall = C.c_double(0)
+        _chk(_ffi.lib().rth_caster_walk_emissive_device(s.h, v.width, v.height, _p(v.vp12), v.maxdepth, v.samples_per_pixel, C.byref(t), k0, n,
+                                                        C.c_void_p(accum.data_ptr()), C.c_void_p(out.data_ptr() if out is not None else 0),
+                                                        C.c_void_p(getattr(stream, "cuda_stream", stream) or 0), C.byref(st), C.byref(wall)))
+        return ProgressCtx(st.rays, wall.value, st.as_dict())
+
+    def emitter_sampler(self, s):
+        """The lamps' tables of the scene as the first device holds them (rtmi_scene_get_emitter_sampler): a namespace q (L,) uint32,
+        cum (L,) uint64, lamp_of_tri (ntris,) uint32 (0 = not a lamp), lamps (L, 5, 4) float32 -- (c0, A), (e1, w), (e2, 0), (n, 0),
+        (radiance, 0) -- and total, or None when the scene has no lamps.  Uploads, and builds the tables, if need be."""
+        self._config(s)
+        n, total = C.c_uint32(0), C.c_uint64(0)
+        _chk(_ffi.lib().rth_caster_emitter_sampler(s.h, None, None, None, None, 0, 0, C.byref(total), C.byref(n)))
+        if n.value == 0:
+            return None
+        L, nt = n.value, s.num_tris()
+        q, cum, idx, lamps = np.zeros(L, np.uint32), np.zeros(L, np.uint64), np.zeros(nt, np.uint32), np.zeros((L, 5, 4), np.float32)
+        _chk(_ffi.lib().rth_caster_emitter_sampler(s.h, _p(q), _p(cum), _p(idx), _p(lamps), L, nt, C.byref(total), C.byref(n)))
+        return SimpleNamespace(q=q, cum=cum, lamp_of_tri=idx, lamps=lamps, total=int(total.value))
 
     LIT_MAX_LIGHTS = _ffi.LIT_MAX_LIGHTS
     LIT_INVERSE_SQUARE = _ffi.LIT_INVERSE_SQUARE
