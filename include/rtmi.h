@@ -1378,7 +1378,8 @@ int rtmi_render_envlight(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_
  *   no inner colour of a fold is -0.f (c + 0.f turns a -0.f into +0.f, which mix_color may show in the sign of a zero).
  * Scenes: octree, linear list, generic tree and RTMI_OPT_GENERIC are exact; RTMI_OPT_FAST / RTMI_OPT_BVH give their own modes'
  *   hits and answers.  With or without an environment.  RTMI_ERR_UNSUPPORTED, before any HIP call, for a scene with analytic
- *   spheres, a dielectric, vertex normals, textures or normal maps; the handle stays usable.
+ *   spheres, a dielectric, vertex normals, textures or normal maps; the handle stays usable.  (With RTMI_LIT_SURFACES only
+ *   analytic spheres are refused: "BOX LIGHTS ON SHADED SURFACES" below.)
  * RTMI_ERR_INVALID, before any HIP call and before the scene is used, stats cleared: every check of
  *   rtmi_render_samples[_device]; lit == NULL; nlights > RTMI_LIT_MAX_LIGHTS; unknown flag bits; every parameter check of
  *   rtmi_render_light* on each used light (the message names the light's index), and rays != 1; a non-finite used colour.
@@ -1392,14 +1393,16 @@ int rtmi_render_envlight(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_
  *   k_shade_lit sums the weights of an entry's unoccluded candidates in l order and folds.  Beside the plain workspace, per
  *   path and light: 53 B of queue, 4 B of slot and, on an octree, 12 B of hit records; per path and level 16 B (the direct
  *   stack); allocated by this call only.  No tuning changes a bit.
- * Not here: lights on smooth, textured, normal-mapped or glass scenes; more than one sample per light and hit; lights chosen
+ * Not here: more than one sample per light and hit; lights chosen
  *   by importance; rtmi_render_envlight*'s sampling in the same pass; lights at Reflective or exhausted levels; adaptive
  *   variants, view batches and denoised wrappers; the path kernels (pipeline 3).  (Explicit rays and the bake with these lights:
  *   rtmi_render_rays_lit*, rtmi_bake_lit*, below.) */
-enum { RTMI_LIT_MAX_LIGHTS = 4, RTMI_LIT_INVERSE_SQUARE = 1u << 0 };
+/* rtmi_lit_t.flags: bit 0 RTMI_LIT_INVERSE_SQUARE, bit 2 RTMI_LIT_SURFACES ("BOX LIGHTS ON SHADED SURFACES" below).  Bit 1 is not
+ * assigned: it and every higher bit are unknown flags and refused. */
+enum { RTMI_LIT_MAX_LIGHTS = 4, RTMI_LIT_INVERSE_SQUARE = 1u << 0, RTMI_LIT_SURFACES = 1u << 2 };
 typedef struct rtmi_lit {
     uint32_t nlights;          /* 0: 0..RTMI_LIT_MAX_LIGHTS                                                       */
-    uint32_t flags;            /* 4: RTMI_LIT_INVERSE_SQUARE or 0                                                 */
+    uint32_t flags;            /* 4: RTMI_LIT_INVERSE_SQUARE, RTMI_LIT_SURFACES, both or 0                        */
     rtmi_light_t lights[4];    /* 8: entries >= nlights are ignored; rays must be 1; flags may hold               */
                                /*    RTMI_LIGHT_UNBOUNDED                                                         */
     float light_color[4][3];   /* 120: the radiance scale per light; any finite float                             */
@@ -1411,6 +1414,47 @@ int rtmi_render_lit_device(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint6
 int rtmi_render_lit(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t seed, uint32_t row0, uint32_t nrows,
                     uint32_t sample0, uint32_t nsamples, const rtmi_lit_t* lit, float* accum_host,
                     float* out_host /* or NULL */, rtmi_stats_t* stats);
+
+/* BOX LIGHTS ON SHADED SURFACES: rtmi_render_lit*, rtmi_render_rays_lit* and rtmi_bake_lit* on scenes with a
+ * dielectric, vertex normals, textures and normal maps.  Opt-in: a call whose rtmi_lit_t.flags has RTMI_LIT_SURFACES takes these
+ * scenes; without the flag every call behaves as stated above, refusals and their wording included.  Analytic spheres stay refused
+ * with the same message.  On a scene without any of these features the flag changes no bit and no stat.  Build-defined; what
+ * follows IS the definition, and tests/lit_surfaces_ref.py pins it bit for bit.  f32 on all four lanes, every step rounded, no
+ * fused multiply-add.
+ * Everything of "BOX LIGHTS IN THE PATH" holds except what follows.  The paths, the RNG blocks 0 .. maxdepth, the queue order and
+ *   the plain ray count are those of the plain render (rtmi_render_samples*, rtmi_render_rays*, rtmi_bake*) of the same scene on its
+ *   own shading level.  Unchanged: the light blocks 0xC0000000 | l << 16 | j and their four draws; adj, v, d2, r, dir; the limit;
+ *   g_l = c or c / d2; the sum over l ascending.
+ * Normals at a Matte hit that bounces:
+ *   ng = the record's normal, * -1.f on a back face;
+ *   N  = the hit's shading normal, exactly the normal the bounce is first evaluated with: ng to start with; the result of "VERTEX
+ *        NORMALS OF A SCENE" where it is usable (use); the result of "NORMAL MAPS OF A SCENE" about that where it is usable (usem).
+ *        N does not depend on the bounce's random vector: the bounce's own fall-back to ng, when its ray leaves on the wrong side
+ *        of the real surface, does not touch the lamp term.
+ * Candidate l:
+ *   c = vdot(N, dir);
+ *   o = vadd(point, vmul(ng, bias_l * (u(w[3]) + 1.f))): the geometric normal, because an offset along a shading normal can start
+ *       under a neighbouring facet;
+ *   live when c > 0.f && vdot(ng, dir) > 0.f: the second test keeps a lamp behind the real surface from lighting it through a
+ *       tilted normal.  On a hit with N == ng this is "BOX LIGHTS IN THE PATH"'s candidate bit for bit.
+ * Other surface kinds: a Dielectric level gets no candidate and direct_j = 0, like a Reflective level.  Glass occludes a shadow
+ *   ray like any other surface (no transparent shadows).
+ * Colour: the fold c = mix_color(colour_j, c + direct_j, alpha_j) reads a level's colour where the plain render of the scene reads
+ *   it: on a textured scene "TEXTURES OF A SCENE"'s colour of the hit.  A textured Solid hit ends with that colour.  The lamp's
+ *   weight is not textured: the albedo acts in the fold.
+ * Bounce: the plain render's, statement for statement: the same normal, the same wrong-side re-evaluation, RTMI_DIELECTRIC's
+ *   reflect-or-refract draw from word 3 of the level's block.
+ * rtmi_bake_lit*: direct keeps the caller's element normal for both roles (c and the offset), as stated above; the flag only lets
+ *   it run on these scenes, and light is rtmi_render_rays_lit*'s with the flag.
+ * stats: rays = the plain rays + the live candidates traced.
+ * How: scenes whose shading level is above the environment's, or that have a dielectric, run k_lit_rays_surf and k_shade_lit_surf
+ *   (and their _explicit forms): k_lit_rays' compaction with N computed once before the light loop, and k_shade_lit's slot loop in
+ *   front of a lit arm of the top shading level, which computes N again and reads no record of the candidate kernel.  One set for
+ *   every featured scene: a table the scene lacks is passed empty and tested at run time.  The colour stack is the plain render's,
+ *   allocated on a textured scene only.  Every other scene runs the kernels it ran before, with or without the flag.
+ * Not here: rtmi_render_emissive* and rtmi_render_envlight* on these scenes (their balance heuristic needs the bounce's density,
+ *   which is a mixture under a shading normal with the wrong-side re-evaluation); transparent shadows; textured lamp weights;
+ *   analytic spheres; adaptive, view-batch and denoised variants; the path kernels (pipeline 3). */
 
 /* BOX LIGHTS ON EXPLICIT RAYS AND IN THE BAKE.  Build-defined like the calls they extend; what follows IS the
  * definition, and tests/bake_lit_ref.py pins it bit for bit.  f32 on all four lanes, every step rounded, no fused multiply-add.
@@ -1463,7 +1507,7 @@ int rtmi_render_lit(rtmi_scene_t* scene, const rtmi_viewport_t* vp, uint64_t see
  *   thread per (element, k)), the occlusion walk, k_bake_lit_resolve (d_k), k_accum; then rtmi_bake*'s batch with the lit passes.
  *   The shadow queue, limits, weights, answers and slots are sized batch x nlights, the direct stack batch x depth, allocated by
  *   these calls only.  No tuning changes a bit.
- * Not here: lights on the scenes rtmi_render_lit* refuses; more than one sample per light and hit; rtmi_render_envlight*'s
+ * Not here: more than one sample per light and hit; rtmi_render_envlight*'s
  *   sampling in the same pass; adaptive, view and denoised variants. */
 typedef struct rtmi_bake_lit_out {   /* rtmi_bake_out_t and direct: any may be NULL, not all; none may overlap another or an input */
     void *light, *open, *orig, *dir;

@@ -70,6 +70,7 @@ class Preview(C.Structure):
 
 LIT_MAX_LIGHTS = 4        # RTMI_LIT_MAX_LIGHTS
 LIT_INVERSE_SQUARE = 1    # RTMI_LIT_INVERSE_SQUARE
+LIT_SURFACES = 4          # RTMI_LIT_SURFACES (bit 1 is not assigned)
 
 
 class Lit(C.Structure):

@@ -127,6 +127,7 @@ __device__ inline bool shade_hit_lit(const DScene& sc, const EnvTab& env, uint32
     uint32_t prow, pcol, sample;                                                  \
     path_pixel<Samp::PASS>(v, pix0, path, prow, pcol, sample, nullptr);
 #define RTMI_LIT_SHADE_PIXEL prow * v.width + pcol
+#define RTMI_LIT_SHADE_HIT shade_hit_lit<ENV>
 template <bool ENV>
 #include "lit_shade_kernel.hpp"
 #undef RTMI_LIT_KERNEL
@@ -145,6 +146,174 @@ template <bool ENV>
 #undef RTMI_LIT_KEYS_PARAM
 #undef RTMI_LIT_SHADE_KEY
 #undef RTMI_LIT_SHADE_PIXEL
+#undef RTMI_LIT_SHADE_HIT
+
+// ---------------------------------------------------------------- box lights on shaded surfaces (RTMI_LIT_SURFACES; include/rtmi.h
+// "BOX LIGHTS ON SHADED SURFACES"): the kernels above for scenes with a dielectric, vertex normals, textures or normal
+// maps.  One set at the top of the shading ladder (Shade::NMAP): a table the scene lacks is passed empty (n = 0) and tested at run
+// time, cstack is null on a scene without textures.  The shading kernel computes the hit's shading normal again, as shade_hit<NMAP>
+// does, and reads no record from the candidate kernel.
+
+// The map's texel of a hit of triangle tri at `point`: tex_colour_nmap's M without the colour's lookup (the same record, header,
+// (u, v), taps and mix).  kmap = 0: the triangle has no map and M is not set.
+__device__ inline V4 lit_nmap_texel(const TexTab& tx, const NmapTab& nt, uint32_t tri, V4 point, float4& fr, uint32_t& kmap) {
+    fr = tri < nt.n ? nt.tri[tri] : make_float4(0.f, 0.f, 0.f, 0.f);
+    kmap = __float_as_uint(fr.w) & 0x7FFFFFFFu;
+    if (kmap == 0u) return mk(0.f, 0.f, 0.f);
+    const float4* __restrict__ r = tx.tri + (size_t)tri * 5u;
+    const float4 q0 = r[0], q1 = r[1], q2 = r[2], q3 = r[3], q4 = r[4];
+    const uint4 hm = tx.hdr[kmap - 1u];
+    float u, v;
+    tex_uv(q0, q1, q2, q3, q4, point, u, v);
+    const TexTap b = tex_tap(hm, u, v);
+    const float4* __restrict__ im = tx.texels + hm.x;
+    const float4 m00 = im[b.i00], m10 = im[b.i10], m01 = im[b.i01], m11 = im[b.i11];
+    return tex_mix(m00, m10, m01, m11, b.tx, b.ty);
+}
+// N of a hit: the value n has in shade_hit<Shade::NMAP> before its wrong-side loop.  ng: the record's normal, * -1.f on a back face.
+__device__ inline V4 lit_shading_normal(const SmoothTab& sm, const TexTab& tx, const NmapTab& nt, uint32_t tri, uint32_t face, V4 point, V4 rd,
+                                        V4 ng) {
+    bool use = false;
+    V4 n = ng;
+    if (tri < sm.n) n = smooth_normal(sm, tri, face, point, rd, ng, use);
+    if (!use) n = ng;
+    if (tri < tx.n) {
+        float4 fr;
+        uint32_t kmap;
+        const V4 M = lit_nmap_texel(tx, nt, tri, point, fr, kmap);
+        if (kmap != 0u) {
+            bool usem = false;
+            const V4 mn = nmap_normal(fr, M, nt.strength, face, n, ng, rd, usem);
+            if (usem) n = mn;
+        }
+    }
+    return n;
+}
+
+#define RTMI_LIT_SURFACES_KERNEL
+#define RTMI_LIT_KERNEL k_lit_rays_surf
+#define RTMI_LIT_KEYS_PARAM , SmoothTab sm, TexTab tex, NmapTab nm
+#define RTMI_LIT_RAYS_KEY                                                         \
+    uint32_t row, col;                                                            \
+    path_pixel<Samp::PASS>(v, pix0, qpath[i], row, col, sample, nullptr);         \
+    pixel = row * v.width + col;
+#include "lit_rays_kernel.hpp"
+#undef RTMI_LIT_KERNEL
+#undef RTMI_LIT_KEYS_PARAM
+#undef RTMI_LIT_RAYS_KEY
+#define RTMI_LIT_KERNEL k_lit_rays_surf_explicit
+#define RTMI_LIT_KEYS_PARAM , const uint32_t* __restrict__ keys, SmoothTab sm, TexTab tex, NmapTab nm
+#define RTMI_LIT_RAYS_KEY rays_key(v, pix0, qpath[i], keys, pixel, sample);
+#include "lit_rays_kernel.hpp"
+#undef RTMI_LIT_KERNEL
+#undef RTMI_LIT_KEYS_PARAM
+#undef RTMI_LIT_RAYS_KEY
+#undef RTMI_LIT_SURFACES_KERNEL
+
+// shade_hit<Shade::NMAP> (triangles only: the caller refuses analytic spheres) for ONE traced ray of a lit path: the same rays,
+// stacks and return value, the bounce and its wrong-side re-evaluation statement for statement.  `direct` as in shade_hit_lit: it
+// is stored for a Matte level that bounces, 0 for a Reflective or Dielectric level and at exhausted depth.  On a textured scene
+// (tex.n != 0) a level's colour and alpha are pushed on cstack and the fold reads them there; otherwise it reads the material table.
+__device__ inline bool shade_hit_lit_surf(const DScene& sc, const EnvTab& env, uint32_t maxdepth, uint64_t seed, uint32_t npaths, uint32_t path,
+                                          uint32_t pixel, uint32_t sample, uint32_t pass, uint32_t tf, float t, V4 ro, V4 rd, V4 direct,
+                                          uint16_t* __restrict__ mstack, float4* __restrict__ dstack, float4* __restrict__ scol, RayV& nr,
+                                          const SmoothTab& sm, const TexTab& tex, float4* __restrict__ cstack, const NmapTab& nm) {
+    const uint32_t tri = tf & 0x3FFFFFFFu, face = tf >> 30;
+    const bool textured = tex.n != 0u;
+    V4 c;
+    uint32_t npushed = pass;
+    if (tri == 0) {
+        c = env.n ? env_lookup(env, rd) : mk(128.f / 255.f, 180.f / 255.f, 255.f / 255.f);
+    } else if (face & 2u) {
+        c = mk(0.f / 255.f, 0.f / 255.f, 0.f / 255.f);
+    } else {
+        const float4 p1 = sc.tplane[2 * tri + 1];
+        const uint32_t mat = __float_as_uint(p1.w);
+        const float4 m0 = sc.mats[2 * mat], m1 = sc.mats[2 * mat + 1];
+        const uint32_t kind = __float_as_uint(m1.y);
+        V4 tcol = mk(m0.x, m0.y, m0.z);
+        V4 mapM = mk(0.f, 0.f, 0.f);
+        float4 mapfr = make_float4(0.f, 0.f, 0.f, 0.f);
+        uint32_t kmap = 0u;
+        if (tri < tex.n) tcol = tex_colour_nmap(tex, nm, tri, vadd(vmul(rd, t), ro), m0, mapM, mapfr, kmap);
+        if (kind == RTMI_SOLID) {
+            c = tcol;
+        } else {
+            mstack[(size_t)pass * npaths + path] = (uint16_t)mat;
+            if (textured) cstack[(size_t)pass * npaths + path] = make_float4(tcol.x, tcol.y, tcol.z, m0.w);
+            npushed = pass + 1;
+            c = mk(0.f / 255.f, 0.f / 255.f, 0.f / 255.f);
+            if (maxdepth - pass - 1u != 0u) {
+                const V4 point = vadd(vmul(rd, t), ro);
+                V4 norm = mk(p1.x, p1.y, p1.z);
+                if (face & 1u) norm = vmul(norm, -1.f);
+                float u3 = 0.f;
+                const V4 rv = random_vec_u(seed, pixel, sample, pass + 1u, u3);
+                bool use = false;
+                V4 n = norm;
+                if (tri < sm.n) n = smooth_normal(sm, tri, face, point, rd, norm, use);
+                if (!use) n = norm;
+                if (kmap != 0u) {
+                    bool usem = false;
+                    const V4 mn = nmap_normal(mapfr, mapM, nm.strength, face, n, norm, rd, usem);
+                    if (usem) { n = mn; use = true; }
+                }
+                for (;;) {
+                    V4 dir;
+                    float side;
+                    nr = bounce_ray<Shade::NMAP>(kind, m1.x, face, point, n, rd, rv, u3, dir, side);
+                    if (!use || side * vdot(dir, norm) > 0.f) break;
+                    n = norm;  // the ray leaves on the wrong side of the real surface: the whole bounce again with ng
+                    use = false;
+                }
+                if (kind != RTMI_MATTE) direct = V4{0.f, 0.f, 0.f, 0.f};
+                store_stream(&dstack[(size_t)pass * npaths + path], make_float4(direct.x, direct.y, direct.z, direct.w));
+                return true;
+            }
+            dstack[(size_t)pass * npaths + path] = make_float4(0.f, 0.f, 0.f, 0.f);  // no sample at exhausted depth
+        }
+    }
+    // inside-out evaluation of the nested mix_color calls, each level's inner colour plus its direct light
+    for (int j = (int)npushed - 1; j >= 0; j--) {
+        float4 mm;
+        if (textured) {
+            mm = cstack[(size_t)j * npaths + path];
+        } else {
+            const uint32_t mj = mstack[(size_t)j * npaths + path];
+            mm = sc.mats[2 * mj];
+        }
+        const float4 dj = dstack[(size_t)j * npaths + path];
+        c = mix_color(mk(mm.x, mm.y, mm.z), vadd(c, V4{dj.x, dj.y, dj.z, dj.w}), mm.w);
+    }
+    store_stream(&scol[path], make_float4(c.x, c.y, c.z, c.w));
+    return false;
+}
+
+// k_shade_lit's slot loop in front of shade_hit_lit_surf: the text is lit_shade_kernel.hpp's, once per sampling mode
+#define RTMI_LIT_SHADE_HIT(...) shade_hit_lit_surf(__VA_ARGS__, sm, tex, cstack, nm)
+#define RTMI_LIT_KERNEL k_shade_lit_surf
+#define RTMI_LIT_KEYS_PARAM , SmoothTab sm, TexTab tex, float4* __restrict__ cstack, NmapTab nm
+#define RTMI_LIT_SHADE_KEY                                                        \
+    uint32_t prow, pcol, sample;                                                  \
+    path_pixel<Samp::PASS>(v, pix0, path, prow, pcol, sample, nullptr);
+#define RTMI_LIT_SHADE_PIXEL prow * v.width + pcol
+#include "lit_shade_kernel.hpp"
+#undef RTMI_LIT_KERNEL
+#undef RTMI_LIT_KEYS_PARAM
+#undef RTMI_LIT_SHADE_KEY
+#undef RTMI_LIT_SHADE_PIXEL
+#define RTMI_LIT_KERNEL k_shade_lit_surf_explicit
+#define RTMI_LIT_KEYS_PARAM , const uint32_t* __restrict__ keys, SmoothTab sm, TexTab tex, float4* __restrict__ cstack, NmapTab nm
+#define RTMI_LIT_SHADE_KEY                                                        \
+    uint32_t pixel, sample;                                                       \
+    rays_key(v, pix0, path, keys, pixel, sample);
+#define RTMI_LIT_SHADE_PIXEL pixel
+#include "lit_shade_kernel.hpp"
+#undef RTMI_LIT_KERNEL
+#undef RTMI_LIT_KEYS_PARAM
+#undef RTMI_LIT_SHADE_KEY
+#undef RTMI_LIT_SHADE_PIXEL
+#undef RTMI_LIT_SHADE_HIT
 
 // ---------------------------------------------------------------- the lamps' light at a bake element (rtmi_bake_lit*: `direct`)
 // k_bake_rays' loop (bake.hpp: a block stages `epb` whole elements per step in LDS, thread e of the step's (element h, ray k) pairs, k

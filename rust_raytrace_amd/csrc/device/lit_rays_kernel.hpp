@@ -4,6 +4,20 @@
 //   RTMI_LIT_RAYS_KEY    the statements that set `pixel` and `sample`, the RNG key of the path of queue entry i
 // so that every mode's kernel is compiled from the same lines and k_lit_rays keeps the machine code it had (a shared device
 // function does not: the grid built-ins and the argument loads are scheduled differently around an inlined body).
+// With RTMI_LIT_SURFACES_KERNEL defined (the kernels of scenes with surface features, lit.hpp; RTMI_LIT_KEYS_PARAM then ends with
+// `, SmoothTab sm, TexTab tex, NmapTab nm`) the candidate has two normals: ns, the hit's shading normal, gives c; n, the geometric
+// one, gives the origin's offset and the second liveness test.  Without it the three hooks below expand to the text the kernel had.
+#ifdef RTMI_LIT_SURFACES_KERNEL
+#define RTMI_LIT_SHADING_NORMAL_DECL V4 ns{};
+#define RTMI_LIT_SHADING_NORMAL ns = lit_shading_normal(sm, tex, nm, tri, tf >> 30, point, V4{d4.x, d4.y, d4.z, d4.w}, n);
+#define RTMI_LIT_N ns
+#define RTMI_LIT_LIVE c > 0.f && vdot(n, dir[l]) > 0.f
+#else
+#define RTMI_LIT_SHADING_NORMAL_DECL
+#define RTMI_LIT_SHADING_NORMAL
+#define RTMI_LIT_N n
+#define RTMI_LIT_LIVE c > 0.f
+#endif
 __global__ void __launch_bounds__(256) RTMI_LIT_KERNEL(DScene sc, DView v, uint64_t seed, uint32_t pix0, uint32_t npaths, int pass, LitArgs la,
                                                   const float4* __restrict__ qo, const float4* __restrict__ qd,
                                                   const uint32_t* __restrict__ qpath, const uint32_t* __restrict__ hit_tf,
@@ -21,6 +35,7 @@ __global__ void __launch_bounds__(256) RTMI_LIT_KERNEL(DScene sc, DView v, uint6
         bool cand = false;
         V4 point{}, n{};
         uint32_t pixel = 0, sample = 0;
+        RTMI_LIT_SHADING_NORMAL_DECL
         if (i < count) {
             const uint32_t tf = hit_tf[i], tri = tf & 0x3FFFFFFFu;
             if (tri != 0u && !((tf >> 30) & 2u)) {
@@ -34,6 +49,7 @@ __global__ void __launch_bounds__(256) RTMI_LIT_KERNEL(DScene sc, DView v, uint6
                     n = mk(p1.x, p1.y, p1.z);
                     if ((tf >> 30) & 1u) n = vmul(n, -1.f);
                     RTMI_LIT_RAYS_KEY
+                    RTMI_LIT_SHADING_NORMAL
                 }
             }
         }
@@ -61,8 +77,8 @@ __global__ void __launch_bounds__(256) RTMI_LIT_KERNEL(DScene sc, DView v, uint6
                     r[l] = sqrtf(d2);
                     dir[l] = vmul(vv, 1.f / r[l]);
                     o[l] = vadd(point, vmul(n, L.bias * (u32_to_unit_f32(w[3]) + 1.f)));
-                    const float c = vdot(n, dir[l]);
-                    live[l] = c > 0.f;  // false for the light behind the surface, for a NaN and for the light at the point
+                    const float c = vdot(RTMI_LIT_N, dir[l]);
+                    live[l] = RTMI_LIT_LIVE;  // false for the light behind the surface, for a NaN and for the light at the point
                     g[l] = la.inverse_square ? c / d2 : c;
                 }
                 const unsigned long long mask = __ballot(live[l]);
@@ -98,3 +114,7 @@ __global__ void __launch_bounds__(256) RTMI_LIT_KERNEL(DScene sc, DView v, uint6
         __syncthreads();  // s_cnt / s_base are rewritten by the next iteration
     }
 }
+#undef RTMI_LIT_SHADING_NORMAL_DECL
+#undef RTMI_LIT_SHADING_NORMAL
+#undef RTMI_LIT_N
+#undef RTMI_LIT_LIVE

@@ -2,6 +2,8 @@
 // (no include guard) with RTMI_LIT_KERNEL and RTMI_LIT_KEYS_PARAM as in lit_rays_kernel.hpp and
 //   RTMI_LIT_SHADE_KEY    the statements that declare `sample` and what RTMI_LIT_SHADE_PIXEL names, the RNG key of `path`
 //   RTMI_LIT_SHADE_PIXEL  the key's pixel
+//   RTMI_LIT_SHADE_HIT    the shading function: shade_hit_lit<ENV>, or for the kernels of scenes with surface features (no template
+//                         line; RTMI_LIT_KEYS_PARAM then ends with the tables and the colour stack) a macro that appends them
 __global__ void __launch_bounds__(256) RTMI_LIT_KERNEL(DScene sc, DView v, uint64_t seed, uint32_t pix0, uint32_t npaths, int pass, EnvTab env,
                                                    uint32_t nlights, const float4* __restrict__ qo, const float4* __restrict__ qd,
                                                    const uint32_t* __restrict__ qpath, const uint32_t* __restrict__ hit_tf,
@@ -38,7 +40,7 @@ __global__ void __launch_bounds__(256) RTMI_LIT_KERNEL(DScene sc, DView v, uint6
                 }
             }
             RTMI_LIT_SHADE_KEY
-            push = shade_hit_lit<ENV>(sc, env, v.maxdepth, seed, npaths, path, RTMI_LIT_SHADE_PIXEL, sample, (uint32_t)pass, tf, t,
+            push = RTMI_LIT_SHADE_HIT(sc, env, v.maxdepth, seed, npaths, path, RTMI_LIT_SHADE_PIXEL, sample, (uint32_t)pass, tf, t,
                                       V4{o4.x, o4.y, o4.z, o4.w}, V4{d4.x, d4.y, d4.z, d4.w}, direct, mstack, dstack, scol, nr);
         }
         const unsigned long long mask = __ballot(push);

@@ -3022,6 +3022,9 @@ static bool envlight_from_hits(const rtmi_scene* s, const TileCall& c) { return 
 // 20.4 M shadow rays per 16 samples cost k_occluded_oct 59.9 ms and the hybrid pass 12.2 ms on top of the path rays' 26.3 ms
 // (profiles/lit_kernel_stats_anyhit.csv against lit_kernel_stats.csv).  RTMI_LIT_FROM_HITS=0 brings the any-hit
 // kernel back for that comparison; the answers are the same bytes.  The linear list keeps its any-hit kernel.
+// The kernel set of a lit call: the *_surf kernels (lit.hpp) for a scene with a surface feature, today's for every other.  Levels
+// PLAIN and ENV take the old set unless the scene has a dielectric, which Shade::ENV's kernels know and the old lit kernels do not.
+static bool lit_surfaces(const rtmi_scene* s) { return shade_level(s) >= Shade::SMOOTH || s->has_dielectric; }
 static bool lit_from_hits(const rtmi_scene* s, const TileCall& c) { return c.sh && c.sh->lit && s->lit_from_hits && !s->root_is_leaf; }
 
 // The plan of a call: its streams, their sub-tiles and the batch size, with every stream's workspace sized for it.
@@ -3311,9 +3314,14 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
             if (c.sh->lit) {
                 const LitArgs& la = *c.sh->lit;
                 if (c.maxdepth - pass - 1u != 0u && la.nlights != 0u) {
-                    hipLaunchKernelGGL(k_lit_rays, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, la, w.qo[a].p, w.qd[a].p,
-                                       w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.ctrl.p, sb.qo.p, sb.qd.p, sb.tmax.p, sb.lw.p, sb.slot.p,
-                                       sb.walk.ctrl.p);
+                    if (lit_surfaces(s))
+                        hipLaunchKernelGGL(k_lit_rays_surf, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, la, w.qo[a].p,
+                                           w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.ctrl.p, sb.qo.p, sb.qd.p, sb.tmax.p, sb.lw.p, sb.slot.p,
+                                           sb.walk.ctrl.p, s->smoothtab, s->textab, s->nmaptab);
+                    else
+                        hipLaunchKernelGGL(k_lit_rays, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, la, w.qo[a].p, w.qd[a].p,
+                                           w.qpath[a].p, w.hit_tf.p, w.hit_t.p, w.ctrl.p, sb.qo.p, sb.qd.p, sb.tmax.p, sb.lw.p, sb.slot.p,
+                                           sb.walk.ctrl.p);
                     HIPCHK(hipEventRecord(sb.walk.pass_ev[2 * pass], st));
                     launch_occluded(s, sb.walk, st, (uint64_t)npaths * la.nlights, sb.qo.p, sb.qd.p, sb.tmax.p, sb.occ.p, (int)pass + 1,
                                     sb.walk.pass_ev[2 * pass + 1], lit_from_hits(s, c));
@@ -3322,9 +3330,14 @@ static int enqueue_batch(rtmi_scene* s, const TileCall& c, uint32_t t, uint64_t 
                     HIPCHK(hipEventRecord(sb.walk.pass_ev[2 * pass], st));
                     HIPCHK(hipEventRecord(sb.walk.pass_ev[2 * pass + 1], st));
                 }
-                hipLaunchKernelGGL(s->has_env ? k_shade_lit<true> : k_shade_lit<false>, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths,
-                                   (int)pass, s->envtab, la.nlights, w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, sb.slot.p, sb.occ.p,
-                                   sb.lw.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, sb.dstack.p, w.scol.p, w.ctrl.p);
+                if (lit_surfaces(s))
+                    hipLaunchKernelGGL(k_shade_lit_surf, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths, (int)pass, s->envtab, la.nlights,
+                                       w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, sb.slot.p, sb.occ.p, sb.lw.p, w.qo[b].p, w.qd[b].p,
+                                       w.qpath[b].p, w.mstack.p, sb.dstack.p, w.scol.p, w.ctrl.p, s->smoothtab, s->textab, w.cstack.p, s->nmaptab);
+                else
+                    hipLaunchKernelGGL(s->has_env ? k_shade_lit<true> : k_shade_lit<false>, ew_grid, ew_block, 0, st, s->d, dv, c.seed, pix0, npaths,
+                                       (int)pass, s->envtab, la.nlights, w.qo[a].p, w.qd[a].p, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, sb.slot.p,
+                                       sb.occ.p, sb.lw.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, sb.dstack.p, w.scol.p, w.ctrl.p);
                 HIPCHK(hipGetLastError());
                 continue;
             }
@@ -4297,7 +4310,7 @@ static int check_lit(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint32_t sample
 static int check_lit_params(const rtmi_lit_t* p) {
     if (!p) return fail(RTMI_ERR_INVALID, "lit: NULL argument (rtmi_lit_t)");
     if (p->nlights > (uint32_t)RTMI_LIT_MAX_LIGHTS) return fail(RTMI_ERR_INVALID, "lit: nlights above RTMI_LIT_MAX_LIGHTS");
-    if (p->flags & ~(uint32_t)RTMI_LIT_INVERSE_SQUARE) return fail(RTMI_ERR_INVALID, "lit: unknown flags");
+    if (p->flags & ~(uint32_t)(RTMI_LIT_INVERSE_SQUARE | RTMI_LIT_SURFACES)) return fail(RTMI_ERR_INVALID, "lit: unknown flags");
     for (uint32_t l = 0; l < p->nlights; l++) {
         const rtmi_light_t& li = p->lights[l];
         char msg[160];
@@ -4317,10 +4330,12 @@ static int check_lit_params(const rtmi_lit_t* p) {
     }
     return RTMI_OK;
 }
-// scenes the lit shading (lit.hpp has its own shade_hit) does not take; before any HIP call.  An environment is fine.
-static int refuse_scene_lit(const rtmi_scene_t* s) {
+// scenes the lit shading (lit.hpp has its own shade_hit) does not take; before any HIP call.  An environment is fine.  With
+// RTMI_LIT_SURFACES in the call's flags only analytic spheres are refused: the surface features run through the *_surf kernels.
+static int refuse_scene_lit(const rtmi_scene_t* s, uint32_t flags) {
     if (s->d.nspheres)
         return fail(RTMI_ERR_UNSUPPORTED, "lit: the scene has analytic spheres (a build-defined primitive whose normal needs the hit point)");
+    if (flags & RTMI_LIT_SURFACES) return RTMI_OK;
     if (s->has_dielectric) return fail(RTMI_ERR_UNSUPPORTED, "lit: the scene has a dielectric surface (the lit shading has no glass arm)");
     if (s->has_normals) return fail(RTMI_ERR_UNSUPPORTED, "lit: the scene has vertex normals (the lit shading has no smooth arm)");
     if (s->has_nmap) return fail(RTMI_ERR_UNSUPPORTED, "lit: the scene has normal maps (the lit shading has no normal-map arm)");
@@ -4352,7 +4367,7 @@ int rtmi_render_lit_device(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t 
     if (tile->nrows == 0) return RTMI_OK;
     rc = check_view(vp, tile);
     if (rc != RTMI_OK) return rc;
-    rc = refuse_scene_lit(s);
+    rc = refuse_scene_lit(s, lit->flags);
     if (rc != RTMI_OK) return rc;
     const LitArgs la = lit_args(*lit);
     ShadowCall call{};
@@ -4373,7 +4388,7 @@ int rtmi_render_lit(rtmi_scene_t* s, const rtmi_viewport_t* vp, uint64_t seed, u
     const rtmi_tile_t tile{row0, nrows, nrows, 0u};
     rc = check_view(vp, &tile);
     if (rc != RTMI_OK) return rc;
-    rc = refuse_scene_lit(s);
+    rc = refuse_scene_lit(s, lit->flags);
     if (rc != RTMI_OK) return rc;
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(s->acc.ensure(npix));
@@ -5140,8 +5155,13 @@ static int lit_rays_pass(rtmi_scene* s, Work& w, hipStream_t st, const DView& dv
     const dim3 ew_grid((unsigned)(s->num_cu * 8)), ew_block(256);
     // sb.walk.ctrl->count[pass + 1] (zero since the batch's memset) is the compaction's counter and then the walk's ray count
     if (dv.maxdepth - pass - 1u != 0u && la.nlights != 0u) {
-        hipLaunchKernelGGL(k_lit_rays_explicit, ew_grid, ew_block, 0, st, s->d, dv, seed, pix0, nb, (int)pass, la, qo, qd, w.qpath[a].p, w.hit_tf.p,
-                           w.hit_t.p, w.ctrl.p, sb.qo.p, sb.qd.p, sb.tmax.p, sb.lw.p, sb.slot.p, sb.walk.ctrl.p, keys);
+        if (lit_surfaces(s))
+            hipLaunchKernelGGL(k_lit_rays_surf_explicit, ew_grid, ew_block, 0, st, s->d, dv, seed, pix0, nb, (int)pass, la, qo, qd, w.qpath[a].p,
+                               w.hit_tf.p, w.hit_t.p, w.ctrl.p, sb.qo.p, sb.qd.p, sb.tmax.p, sb.lw.p, sb.slot.p, sb.walk.ctrl.p, keys, s->smoothtab,
+                               s->textab, s->nmaptab);
+        else
+            hipLaunchKernelGGL(k_lit_rays_explicit, ew_grid, ew_block, 0, st, s->d, dv, seed, pix0, nb, (int)pass, la, qo, qd, w.qpath[a].p,
+                               w.hit_tf.p, w.hit_t.p, w.ctrl.p, sb.qo.p, sb.qd.p, sb.tmax.p, sb.lw.p, sb.slot.p, sb.walk.ctrl.p, keys);
         HIPCHK(hipEventRecord(sb.walk.pass_ev[2 * pass], st));
         launch_occluded(s, sb.walk, st, (uint64_t)nb * la.nlights, sb.qo.p, sb.qd.p, sb.tmax.p, sb.occ.p, (int)pass + 1,
                         sb.walk.pass_ev[2 * pass + 1], lit_rays_from_hits(s));
@@ -5150,9 +5170,14 @@ static int lit_rays_pass(rtmi_scene* s, Work& w, hipStream_t st, const DView& dv
         HIPCHK(hipEventRecord(sb.walk.pass_ev[2 * pass], st));
         HIPCHK(hipEventRecord(sb.walk.pass_ev[2 * pass + 1], st));
     }
-    hipLaunchKernelGGL(s->has_env ? k_shade_lit_explicit<true> : k_shade_lit_explicit<false>, ew_grid, ew_block, 0, st, s->d, dv, seed, pix0, nb,
-                       (int)pass, s->envtab, la.nlights, qo, qd, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, sb.slot.p, sb.occ.p, sb.lw.p, w.qo[b].p,
-                       w.qd[b].p, w.qpath[b].p, w.mstack.p, sb.dstack.p, scol, w.ctrl.p, keys);
+    if (lit_surfaces(s))
+        hipLaunchKernelGGL(k_shade_lit_surf_explicit, ew_grid, ew_block, 0, st, s->d, dv, seed, pix0, nb, (int)pass, s->envtab, la.nlights, qo, qd,
+                           w.qpath[a].p, w.hit_tf.p, w.hit_t.p, sb.slot.p, sb.occ.p, sb.lw.p, w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p,
+                           sb.dstack.p, scol, w.ctrl.p, keys, s->smoothtab, s->textab, w.cstack.p, s->nmaptab);
+    else
+        hipLaunchKernelGGL(s->has_env ? k_shade_lit_explicit<true> : k_shade_lit_explicit<false>, ew_grid, ew_block, 0, st, s->d, dv, seed, pix0,
+                           nb, (int)pass, s->envtab, la.nlights, qo, qd, w.qpath[a].p, w.hit_tf.p, w.hit_t.p, sb.slot.p, sb.occ.p, sb.lw.p,
+                           w.qo[b].p, w.qd[b].p, w.qpath[b].p, w.mstack.p, sb.dstack.p, scol, w.ctrl.p, keys);
     HIPCHK(hipGetLastError());
     return RTMI_OK;
 }
@@ -5370,7 +5395,7 @@ static int render_rays_lit(rtmi_scene_t* s, uint64_t n, const void* orig4, const
     if (rc != RTMI_OK || empty) return rc;
     rc = check_lit_params(lit);
     if (rc != RTMI_OK) return rc;
-    rc = refuse_scene_lit(s);
+    rc = refuse_scene_lit(s, lit->flags);
     if (rc != RTMI_OK) return rc;
     const LitArgs la = lit_args(*lit);
     return render_rays(s, n, orig4, dir4, keys, seed, rp, out, hip_stream, stats, host, &la);
@@ -5622,7 +5647,7 @@ static int bake_lit(rtmi_scene_t* s, uint64_t M, const void* pos4, const void* n
     if (rc != RTMI_OK || empty) return rc;
     rc = check_lit_params(lit);
     if (rc != RTMI_OK) return rc;
-    rc = refuse_scene_lit(s);
+    rc = refuse_scene_lit(s, lit->flags);
     if (rc != RTMI_OK) return rc;
     const LitArgs la = lit_args(*lit);
     return bake(s, M, pos4, nrm4, seed, bp, &plain, hip_stream, stats, host, &la, out->direct);

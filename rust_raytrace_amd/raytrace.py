@@ -1339,14 +1339,16 @@ class HipRayCaster:
 
     LIT_MAX_LIGHTS = _ffi.LIT_MAX_LIGHTS
     LIT_INVERSE_SQUARE = _ffi.LIT_INVERSE_SQUARE
+    LIT_SURFACES = _ffi.LIT_SURFACES
 
     @staticmethod
-    def lit_params(lights=(), inverse_square=False):
+    def lit_params(lights=(), inverse_square=False, surfaces=False):
         """rtmi_lit_t from the library's defaults (rtmi_lit_defaults: no lights, white, one ray each) with the given lights: up to
         four dicts of orig, len2, bias (light_params' arguments), color = three finite numbers (default white) and either
         unbounded=True or flags=LIGHT_UNBOUNDED, as preview_params takes them (one shadow ray per light and hit: no rays key).
-        inverse_square: the light's cosine is divided by the squared distance.  Raises ValueError for what the library would
-        refuse."""
+        inverse_square: the light's cosine is divided by the squared distance.  surfaces: RTMI_LIT_SURFACES, the call takes scenes
+        with a dielectric, vertex normals, textures and normal maps (include/rtmi.h "BOX LIGHTS ON SHADED SURFACES"); every lit
+        call that is given the result carries it.  Raises ValueError for what the library would refuse."""
         p = _ffi.Lit()
         _ffi.lib().rtmi_lit_defaults(C.byref(p))
         lights = list(lights)
@@ -1375,7 +1377,7 @@ class HipRayCaster:
                     raise ValueError(f"light {l}: color must be three finite numbers")
                 p.light_color[l][0], p.light_color[l][1], p.light_color[l][2] = c
         p.nlights = len(lights)
-        p.flags = HipRayCaster.LIT_INVERSE_SQUARE if inverse_square else 0
+        p.flags = (HipRayCaster.LIT_INVERSE_SQUARE if inverse_square else 0) | (HipRayCaster.LIT_SURFACES if surfaces else 0)
         return p
 
     def walk_rays_lit(self, v, s, lit, data=None, sample0=0, nsamples=None, accum=None):
