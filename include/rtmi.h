@@ -1584,6 +1584,8 @@ int rtmi_bake_lit(rtmi_scene_t* scene, uint64_t M, const float* pos4, const floa
  * Scenes: octree, linear list, generic tree and RTMI_OPT_GENERIC; with or without an environment.  RTMI_ERR_UNSUPPORTED, before
  *   any HIP call, stats cleared: a scene without lamps; with analytic spheres, a dielectric, vertex normals, textures or normal
  *   maps; RTMI_OPT_BVH (a non-exact first hit would break the "first hit is lamp e" test).  The handle stays usable.
+ *   RTMI_OPT_FAST is taken and gives that mode's hits: path rays and shadow rays go through the same trace, so "first hit is
+ *   lamp e" is decided on the hits the paths see (the frame is this definition on rtmi_trace's hits under the same option).
  * RTMI_ERR_INVALID, before any HIP call and before the scene is used, stats cleared: every check of rtmi_render_samples[_device].
  * stats: as rtmi_render_shadowed* fills them: rays = the plain rays + the live shadow rays, trace_launches = 2 per pass and batch
  *   (an empty event pair at the exhausted pass), primary_ms the path rays' closest-hit launches, bounce_ms the shadow rays'.

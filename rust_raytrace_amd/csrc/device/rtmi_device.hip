@@ -6259,7 +6259,9 @@ int rtmi_debug_record_boxes(const float* recs20, uint64_t n, float* corners9, fl
 }
 // rtmi_debug_hybrid_counters: DCtrl::hyb of the scene's last render or trace call, summed over its streams (hybrid.hpp: what
 // each of the RTMI_NHYB = 12 entries counts).  on <- 1 when the SCENE qualifies for hybrid passes; a launch on a workspace without a
-// fallback list (the shadow walks' own workspace) still takes the one k_trace_oct launch.
+// fallback list as long as its hit records (the shadow walks' own workspace in rtmi_render_shadowed*, which walks any-hit) still
+// takes the one k_trace_oct launch.  The shadow workspaces of the lit, envlight and emissive calls have the list and take the
+// hybrid pass: the function below reads their statistics.
 int rtmi_debug_hybrid_counters(rtmi_scene_t* s, unsigned long long* out12, int* on) {
     if (!s || !out12) return fail(RTMI_ERR_INVALID, "NULL argument");
     HIPCHK(hipSetDevice(s->device));
@@ -6271,6 +6273,22 @@ int rtmi_debug_hybrid_counters(rtmi_scene_t* s, unsigned long long* out12, int* 
     }
     if (on) *on = (s->hybrid && s->octree && s->d.cert && s->bvh_ok && !s->root_is_leaf &&
                    !(s->options & (RTMI_OPT_GENERIC | RTMI_OPT_FAST | RTMI_OPT_BVH))) ? 1 : 0;
+    return RTMI_OK;
+}
+// rtmi_debug_shadow_hybrid_counters: the same twelve entries of the shadow walks' own control blocks (shadow[k].walk.ctrl: the last
+// batch of every stream of the scene's last rtmi_render_shadowed* / _lit* / _envlight* / _emissive* call), summed over the streams
+// whose block is allocated; zeros where none is (no such call yet).  As in the function above, a stream the last call did not
+// use keeps the block of the call that last used it: read it on a scene whose calls all ran on the same streams.
+int rtmi_debug_shadow_hybrid_counters(rtmi_scene_t* s, unsigned long long* out12) {
+    if (!s || !out12) return fail(RTMI_ERR_INVALID, "NULL argument");
+    HIPCHK(hipSetDevice(s->device));
+    memset(out12, 0, RTMI_NHYB * sizeof(unsigned long long));
+    for (int k = 0; k < RTMI_MAX_STREAMS; k++) {
+        if (!s->shadow[k].walk.ctrl.p) continue;
+        DCtrl h;
+        HIPCHK(hipMemcpy(&h, s->shadow[k].walk.ctrl.p, sizeof(DCtrl), hipMemcpyDeviceToHost));
+        for (int j = 0; j < RTMI_NHYB; j++) out12[j] += h.hyb[j];
+    }
     return RTMI_OK;
 }
 

@@ -1234,6 +1234,13 @@ int rth_debug_hybrid_counters(rth_scene_t* s, unsigned long long* out12, int* on
     const int g = guarded([&] { rc = rtmi_debug_hybrid_counters(caster_of(s).resident(s->scene), out12, on); });
     return g ? g : rc;
 }
+// ... and of the shadow walks' own workspace (rtmi_render_shadowed* / _lit* / _envlight* / _emissive*)
+int rtmi_debug_shadow_hybrid_counters(rtmi_scene_t* s, unsigned long long* out12);
+int rth_debug_shadow_hybrid_counters(rth_scene_t* s, unsigned long long* out12) {
+    int rc = 0;
+    const int g = guarded([&] { rc = rtmi_debug_shadow_hybrid_counters(caster_of(s).resident(s->scene), out12); });
+    return g ? g : rc;
+}
 
 void rth_quantize(const float* rgba, uint64_t npixels, uint8_t* rgb) {
     quantize_rgb8(reinterpret_cast<const Color*>(rgba), (size_t)npixels, rgb);

@@ -12,6 +12,7 @@ import pytest
 import conftest as CT
 from conftest import assert_bits_equal
 import env_ref as ER
+from envlight_cases import SUN, hdr as _hdr, rotation as _rotation  # shared with tests/shadow_matrix_cases.py
 import envlight_ref as EL
 import features_ref as FR
 
@@ -21,8 +22,6 @@ W = H = 32
 SPP, SEED, MAXDEPTH = 4, 5, 4
 FULL = None  # tile: the whole frame through the host variant
 TILE = (1, 12, 3, 8)
-# a sun of 18 degrees radius low on the -x side of the canonical camera (which looks down +z)
-SUN = dict(sun_dir=(-0.75, 0.25, 0.6), sun_cos=0.95, sun_color=(30.0, 24.0, 16.0))
 NTEAPOT = 6320  # triangles 1 .. 6320 of the canonical scene are the teapot's
 _REFS = {}
 
@@ -35,18 +34,6 @@ def _orc():
 def _R():
     from rust_raytrace_amd import raytrace as R
     return R
-
-
-def _rotation():
-    a, b = 0.7, -0.4
-    ra = np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]])
-    rb = np.array([[1, 0, 0], [0, np.cos(b), -np.sin(b)], [0, np.sin(b), np.cos(b)]])
-    return (ra @ rb).astype(F32)
-
-
-def _hdr(n):
-    """A strongly non-uniform random HDR table, values up to 1e4"""
-    return (np.random.default_rng(100 + n).random((n, n, 3)) ** 8 * 1e4).astype(F32)
 
 
 @pytest.fixture(scope="module")
